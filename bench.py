@@ -10,7 +10,7 @@ inference.main run.  Successive batches alternate between `--pipeline` (default 
 low-occupancy layers of one batch (deep encoder / early decoder levels) overlap the chip-filling layers of the other — what a
 serving loop does; every batch is still a full 128-frame pass and K steps are K batches.  `--pipeline 1` is strictly serial.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 128] [--no-cpu-baseline] [--profile-layers]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 128] [--no-cpu-baseline] [--profile-layers] [--dump-outputs DIR]
         (N > 1 without WORLD_SIZE in the environment: re-executes itself as N ranks under torch.distributed.run, free port)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
@@ -77,7 +77,34 @@ def parse():
     ap.add_argument("--dist-timeout", type=float, default=180.0, help="seconds before the rendezvous / a collective gives up: a rank "
                     "that never arrives ends the job with a non-zero exit instead of hanging rank 0 at the barrier")
     ap.add_argument("--inject-failure", type=int, default=-1, help="(launch test) this rank exits before the rendezvous")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, rank 0 writes what the timed "
+                    "path returned for its last step as DIR/<name>.npy (float32, %d MB at most in all; larger outputs as a fixed "
+                    "seeded sample of frames, the frame numbers in DIR/<name>_rows.npy): inputs and weights are seeded, so two "
+                    "builds can be compared output for output" % (DUMP_BYTES >> 20))
     return ap.parse_args()
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as float32 DIR/<name>.npy; an array over its share of DUMP_BYTES keeps a fixed seeded
+    sample of its leading (frame) axis, in order, and the sampled frame numbers go to DIR/<name>_rows.npy (float64).
+    Returns {file name: shape} for the result line."""
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_BYTES - (1 << 20)) // len(arrays)        # each array with its row file; 1 MB left for the .npy headers
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        row = a[0].nbytes if a.ndim and len(a) else 1
+        if a.nbytes > share:
+            rows = np.sort(np.random.default_rng(0).choice(len(a), max(1, share // (row + 8)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            written[name + "_rows.npy"] = list(rows.shape)
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name + ".npy"] = list(a.shape)
+    return written
 
 
 def free_port():
@@ -149,6 +176,7 @@ def dry_run(args, world, rank, dist):
     dist.all_gather(rates, torch.tensor([B * args.steps / dt_local], dtype=torch.float64))
     okt = torch.tensor([1 if ok else 0])
     dist.all_reduce(okt, op=dist.ReduceOp.MIN)
+    dumped = dump_outputs(args.dump_outputs, {"frames_u8": last.numpy()}) if args.dump_outputs and rank == 0 else None
     if rank == 0:
         print(json.dumps({
             "metric": "face-frames/sec (96x96, mel T=16)", "value": round(world * B * args.steps / dt, 1), "unit": "face-frames/sec",
@@ -158,7 +186,8 @@ def dry_run(args, world, rank, dist):
             "per_rank_frames_per_s": [round(float(r.item()), 1) for r in rates],
             "config": {"workload": "DRY RUN: partition + pipelined all-gather + fence only, no kernels (not a measurement)",
                        "frames_per_gpu_per_step": B, "parallelism": "dp%d" % world, "batches_in_flight_per_gpu": gather.depth,
-                       "collective_world_size": dist.get_world_size(), "collective_backend": dist.get_backend()}}), flush=True)
+                       "collective_world_size": dist.get_world_size(), "collective_backend": dist.get_backend()},
+            **({"dump_outputs": {"dir": args.dump_outputs, "files": dumped}} if dumped is not None else {})}), flush=True)
     dist.destroy_process_group()
     if not okt.item():
         sys.exit("dry run: gathered frames out of order")
@@ -541,6 +570,14 @@ def main():
         done += n
     fence()
     dt_s = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step, before the rates below reuse the lanes: its uint8 frames as the caller receives them (with N > 1
+        # the all-gathered frames of every rank) and the generator's float prediction behind them
+        k_last = (counter[0] - 1) % depth
+        frames_last = outs_u8[k_last] if gather is None else gather.recv[(gather.i - 1) % gather.depth]
+        dumped = dump_outputs(args.dump_outputs, {"frames_u8": frames_last.cpu().numpy(),
+                                                  "pred_nchw": runner.lanes[k_last].last_pred_nchw().cpu().numpy()})
     if dist is not None:
         t = torch.tensor([dt_s], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -738,6 +775,14 @@ def main():
     # the rate this launch plan would reach if every launch ran its matrix pipe at peak: value / frac (the bound `frac` implies)
     result["bound_frames_per_s"] = round(result["value"] / max(1e-9, result["roofline"]["frac"]), 1)
     result.update(extra)
+    if dumped is not None:
+        result["dump_outputs"] = {
+            "dir": args.dump_outputs, "files": dumped, "step": "the last timed step (lane %d of %d)" % (k_last, depth),
+            "contents": {"frames_u8": ("the uint8 BGR frames [frame, y, x, c] the runner returned, as float32" if world == 1 else
+                                       "the all-gathered uint8 BGR frames of all %d ranks [rank-major frame, y, x, c], as float32"
+                                       % world),
+                         "pred_nchw": ("the generator's float32 prediction [frame, c, y, x] behind frames_u8" if world == 1 else
+                                       "rank 0's float32 prediction [frame, c, y, x] only: the first %d frames of frames_u8" % B)}}
     nsplit = sum(1 for _, _, fam, _ in resolved if fam in BF16_FAMS)
     if nsplit:
         result["arithmetic"] = ("fp32 tensors, fp32 accumulation; %d of %d conv launches multiply on the bf16 matrix cores with every "

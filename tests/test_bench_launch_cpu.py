@@ -46,6 +46,34 @@ def test_bench_dry_run_eight_ranks_the_scale_step_shape():
     assert r["config"]["batches_in_flight_per_gpu"] == 4
 
 
+def test_dump_outputs_writes_the_last_timed_step_as_float32(tmp_path):
+    """--dump-outputs DIR: rank 0 writes the last timed step's gathered frames as float32 .npy and names them in the result line"""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = _run(["--gpus", "2", "--backend", "gloo", "--dry-run", "--steps", "5", "--warmup", "1", "--windows", "2", "--batch", "3",
+              "--dump-outputs", str(out)])
+    assert r["dump_outputs"]["files"] == {"frames_u8.npy": [6, 4, 4, 3]} and sorted(os.listdir(out)) == ["frames_u8.npy"]
+    frames = np.load(out / "frames_u8.npy")
+    assert frames.dtype == np.float32 and frames.shape == (6, 4, 4, 3)
+    assert all((frames[3 * rank:3 * rank + 3] == (17 * rank + 4) % 251).all() for rank in range(2))    # step 4 of 0..4
+
+
+def test_dump_outputs_samples_a_large_output_in_budget_and_reproducibly(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 << 20)
+    big = np.arange(64 * 96 * 96 * 3, dtype=np.uint8).reshape(64, 96, 96, 3)
+    files = bench.dump_outputs(str(tmp_path / "a"), {"frames_u8": big, "small": np.ones((2, 3), np.float64)})
+    assert files["small.npy"] == [2, 3] and "small_rows.npy" not in files
+    rows = np.load(tmp_path / "a" / "frames_u8_rows.npy")
+    got = np.load(tmp_path / "a" / "frames_u8.npy")
+    assert rows.dtype == np.float64 and got.dtype == np.float32 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got, big[rows.astype(np.int64)].astype(np.float32))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 4 << 20
+    bench.dump_outputs(str(tmp_path / "b"), {"frames_u8": big, "small": np.ones((2, 3), np.float64)})
+    assert np.array_equal(np.load(tmp_path / "b" / "frames_u8_rows.npy"), rows)
+
+
 def test_a_failing_rank_ends_the_job_with_a_nonzero_exit_instead_of_hanging():
     """rank 1 exits before the rendezvous (--inject-failure): `python bench.py --gpus 2` and `python tools/train_bench.py --gpus 2`
     must come back non-zero well inside the collective timeout - the elastic agent stops rank 0 - and print no result line"""

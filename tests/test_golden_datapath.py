@@ -7,7 +7,6 @@ import json
 import os
 
 import numpy as np
-import pytest
 import torch
 
 from conftest import ROOT
@@ -125,7 +124,6 @@ def test_command_line_surfaces_equal_the_reference_scripts():
     assert a.wav2lip_batch_size == 128 and a.pads == [0, 10, 0, 0] and a.box == [-1, -1, -1, -1] and a.static is False
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference checkout (build container only)")
 def test_fixture_generator_names_the_reference_files_it_executes():
     src = open(os.path.join(ROOT, "tests", "golden", "make_golden_datapath.py")).read()
     for mod in ("import audio as ref_audio", "import inference as ref_inf", '"wav2lip_train"', '"color_syncnet_train"'):

@@ -263,6 +263,25 @@ def test_write_result_takes_the_loop_output_and_the_driving_wav(tmp_path):
     assert np.array_equal(container.read_avi(inference.write_result(str(tmp_path / "mute.avi"), frames, 25.0))["frames"], np.stack(frames))
 
 
+def test_face_path_is_an_image_by_the_reference_test_on_its_file_name(tmp_path):
+    """inference.py:56 / 185 test `face.split('.')[1]`: the package applies that test to the file name, so a directory with a dot
+    in its name (a pytest or CI temp directory) does not turn `face.png` into a video; every dot-free directory gets the
+    reference's answer"""
+    from wav2lip_amd import inference
+    names = ["face.png", "face.jpg", "face.jpeg", "clip.avi", "clip.mp4", "x.png.avi", "x.avi.png", "face.PNG", "a.b.c"]
+    for name in names:
+        for d in ("", "/data/", "rel/dir/"):
+            assert inference.is_image_path(d + name) == ((d + name).split('.')[1] in ['jpg', 'png', 'jpeg']), d + name
+        assert inference.is_image_path("/tmp/run.v2/" + name) == inference.is_image_path(name), name
+    with pytest.raises(IndexError):
+        inference.is_image_path("/data/face")                  # as the reference's own `split('.')[1]`
+    d = tmp_path / "run.v2"
+    d.mkdir()
+    face = d / "face.png"
+    face.write_bytes(b"")
+    assert inference.parse_args(["--checkpoint_path", "c", "--face", str(face), "--audio", "a.wav"]).static is True
+
+
 def test_no_cpu_fallback_for_resampling_and_the_clip_store():
     """the product path fails loudly without a HIP device instead of routing through a CPU implementation"""
     if torch.cuda.is_available():

@@ -62,11 +62,18 @@ def build_parser():
 parser = build_parser()
 
 
+def is_image_path(path):
+    """inference.py:56 / 185: `path.split('.')[1] in ['jpg', 'png', 'jpeg']`, applied to the file name.  On the whole path the
+    test reads past a dot in a directory name (`/tmp/run.v2/face.png` -> 'v2/face'), and an image becomes a video; on the file
+    name it is the reference's test, unchanged (`x.png.avi` is an image, a name without a dot raises IndexError)."""
+    return os.path.basename(path).split('.')[1] in ['jpg', 'png', 'jpeg']
+
+
 def parse_args(argv=None):
     """inference.py:53-57: parse, then `img_size = 96` and `static = True` for an image input"""
     a = parser.parse_args(argv)
     a.img_size = img_size
-    if os.path.isfile(a.face) and a.face.split('.')[1] in ['jpg', 'png', 'jpeg']:
+    if os.path.isfile(a.face) and is_image_path(a.face):
         a.static = True
     return a
 
@@ -491,7 +498,7 @@ def read_frames(a):
     which this image does not have and which is not arithmetic of the path."""
     if not os.path.isfile(a.face):
         raise ValueError('--face argument must be a valid path to video/image file')
-    if a.face.split('.')[1] in ['jpg', 'png', 'jpeg']:
+    if is_image_path(a.face):
         return [read_image_bgr(a.face)], a.fps
     from . import container
     try:
