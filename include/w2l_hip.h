@@ -148,6 +148,8 @@ int w2l_nhwc_to_nchw(void* stream, int N, int C, int H, int W, const float* x, i
  * ch0-2 = face with rows >= S/2 zeroed, ch3-5 = face, all (float)((double)v/255.0); ch6..c_zero_to-1 = 0.
  * inference.py:136-139,259 */
 int w2l_datagen_pack(void* stream, int N, int S, const uint8_t* faces, float* y, int y_cs, int c_zero_to);
+/* the same packing into bf16 [N,S,S,y_cs] for the bf16-storage generator: each fp32 value above rounded once (RNE) */
+int w2l_datagen_pack_bf16(void* stream, int N, int S, const uint8_t* faces, void* y, int y_cs, int c_zero_to);
 /* pred fp32 [N,H,W,x_cs] (first 3 ch, values in [0,1]) -> u8 [N,H,W,3] = (uint8)(v*255.f) (truncation).
  * inference.py:265,269 */
 int w2l_frames_to_u8(void* stream, int N, int H, int W, const float* x, int x_cs, uint8_t* y);
@@ -209,6 +211,9 @@ int w2l_melspectrogram(const w2l_mel_t* m, void* stream, const float* wav, long 
 /* mel [80][T] + starts int32[B] (device) -> out fp32 [B][80][16][out_cs] channel 0 (others zero up to c_zero_to) */
 int w2l_mel_gather(void* stream, const float* mel, int T, const int32_t* starts, int B, float* out,
                    int out_cs, int c_zero_to);
+/* the same windows as bf16 (each value rounded once, RNE) for the bf16-storage generator: out bf16 [B][80][16][out_cs] */
+int w2l_mel_gather_bf16(void* stream, const float* mel, int T, const int32_t* starts, int B, void* out,
+                        int out_cs, int c_zero_to);
 
 /* Sample-rate conversion of audio.load_wav (audio.py:9-10 -> librosa.core.load(path, sr=16000) -> resampy.resample(...,
  * filter='kaiser_best')).  x fp32 [n_in], tr f64 [n_out] = the interpolator's time register at every output sample (the host
@@ -304,6 +309,18 @@ int w2l_convb_forward_bnbwd(const w2l_convb_t* c, void* stream, int N, int H, in
  * caller runs w2l_act_bwd_bf16 (and w2l_col_sum_bf16). */
 int w2l_convb_forward_actbwd(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, void* y, int y_cs,
                              const void* res, int res_cs, const void* by, int by_cs, int bact, float* dbias, int* fused_out);
+/* Fuse a following 1x1 convolution + activation into the layer (the generator's output block on the bf16-storage inference path,
+ * models/wav2lip.py:83-85: Conv2d(80,32,3)+BN+ReLU -> nn.Conv2d(32,head_c,1) -> Sigmoid), the bf16 form of w2l_conv_attach_head.
+ * The layer must be a 3x3 stride-1 pad-1 conv with cin % 16 == 0 and 32 couts; `weight` is its fp32 master tensor again (the head
+ * kernel keeps its own bf16 copy, re-packed by w2l_convb_update / _update_many), head_weight [head_c][32], head_bias [head_c] or
+ * NULL: device fp32, head_c <= 4.  Such a layer runs through w2l_convb_forward_head only. */
+int w2l_convb_attach_head(w2l_convb_t* c, const float* weight, const float* head_weight, const float* head_bias, int head_c,
+                          int head_act, void* stream);
+/* x bf16 [N,H,W,x_cs] (16-byte aligned, x_cs % 8 == 0); scale / shift fp32 [32] (the folded BatchNorm, applied to the fp32
+ * accumulators).  The head output v (fp32, never rounded to bf16) goes to frames u8 [N,H,W,head_c] = (uint8)(v*255.f), the
+ * truncation of w2l_frames_to_u8, and - if y32 != NULL - to y32 fp32 [N,H,W,y32_cs] as well. */
+int w2l_convb_forward_head(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, uint8_t* frames,
+                           float* y32, int y32_cs, const float* scale, const float* shift);
 /* tile override for tests / tuning: -1 = automatic */
 int w2l_convb_set_tile(w2l_convb_t* c, int tile);
 int w2l_convb_num_tiles(void);
@@ -424,6 +441,14 @@ int w2l_plan_destroy(w2l_plan_t* p);
 /* record one conv launch with fixed buffers/shapes; replayed in order by w2l_plan_run */
 int w2l_plan_add_conv(w2l_plan_t* p, const w2l_conv_t* c, int N, int H, int W, const float* x, int x_cs,
                       float* y, int y_cs, const float* res, int res_cs);
+/* record one bf16-storage launch (w2l_convb_forward with ksplit_force 0) with its per-item scale / shift; validated when recorded.
+ * Its configuration comes from the shape (the convb rules): w2l_plan_autotune skips it, w2l_plan_get_config reports (-1, 1) and
+ * w2l_plan_set_config accepts only that; w2l_plan_executed_flops reports configuration id -1. */
+int w2l_plan_add_convb(w2l_plan_t* p, const w2l_convb_t* c, int N, int H, int W, const void* x, int x_cs, void* y, int y_cs,
+                       const void* res, int res_cs, const float* scale, const float* shift);
+/* record one w2l_convb_forward_head launch (a layer with w2l_convb_attach_head), same rules */
+int w2l_plan_add_convb_head(w2l_plan_t* p, const w2l_convb_t* c, int N, int H, int W, const void* x, int x_cs, uint8_t* frames,
+                            float* y32, int y32_cs, const float* scale, const float* shift);
 /* append a copy of launch `index` of `src` (same layer, buffers and configuration) to `dst`: sub-plans for multi-stream runs */
 int w2l_plan_copy_item(w2l_plan_t* dst, const w2l_plan_t* src, int index);
 int w2l_plan_run(const w2l_plan_t* p, void* stream);

@@ -47,6 +47,7 @@ SIGNATURES = {
     "w2l_nchw_to_nhwc": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i]),
     "w2l_nhwc_to_nchw": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "w2l_datagen_pack": (_i, [_vp, _i, _i, _vp, _vp, _i, _i]),
+    "w2l_datagen_pack_bf16": (_i, [_vp, _i, _i, _vp, _vp, _i, _i]),
     "w2l_frames_to_u8": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "w2l_crop_resize_u8": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
     "w2l_resize_u8": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i]),
@@ -61,6 +62,7 @@ SIGNATURES = {
     "w2l_mel_num_frames": (_i, [_ll]),
     "w2l_melspectrogram": (_i, [_vp, _vp, _vp, _ll, _vp]),
     "w2l_mel_gather": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i]),
+    "w2l_mel_gather_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i]),
     "w2l_resample_sinc": (_i, [_vp, _vp, _i, _vp, _i, C.c_double, _vp, _vp, _i, _i, _vp]),
     "w2l_l2norm_rows": (_i, [_vp, _i, _i, _vp, _i, _vp]),
     "w2l_cosine_bce": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -73,6 +75,8 @@ SIGNATURES = {
     "w2l_convb_update_many": (_i, [_i, _vp, _vp, _vp]),
     "w2l_convb_destroy": (_i, [_vp]),
     "w2l_convb_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i]),
+    "w2l_convb_attach_head": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "w2l_convb_forward_head": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "w2l_convb_forward_bn": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "w2l_convb_forward_bnbwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                      C.POINTER(C.c_int)]),
@@ -110,6 +114,8 @@ SIGNATURES = {
     "w2l_plan_create": (_i, [C.POINTER(_vp)]),
     "w2l_plan_destroy": (_i, [_vp]),
     "w2l_plan_add_conv": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i]),
+    "w2l_plan_add_convb": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "w2l_plan_add_convb_head": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "w2l_plan_copy_item": (_i, [_vp, _vp, _i]),
     "w2l_plan_run": (_i, [_vp, _vp]),
     "w2l_plan_size": (_i, [_vp]),

@@ -83,10 +83,34 @@ class ConvB:
         weights = (C.c_void_p * n)(*[w.data_ptr() for _, w in many])
         check(many[0][0]._lib.w2l_convb_update_many(n, handles, weights, current_stream()), "convb_update_many")
 
+    def attach_head(self, weight, head_conv, head_act):
+        """fuse a following 1x1 conv + activation (the generator's output block, w2l_convb_attach_head); `weight` is this layer's
+        fp32 master tensor.  The layer then runs through forward_head / Plan.add_convb_head only, with `cout` = the head's."""
+        w = weight.detach().contiguous().float()
+        hw = head_conv.weight.detach().float().contiguous().view(head_conv.out_channels, self.cout)
+        hb = head_conv.bias.detach().float().contiguous() if head_conv.bias is not None else None
+        check(self._lib.w2l_convb_attach_head(self.handle, ptr(w), ptr(hw), ptr(hb), head_conv.out_channels, int(head_act),
+                                              current_stream()), "convb_attach_head")
+        self.cout_inner = self.cout
+        self.cout = head_conv.out_channels
+
+    def forward_head(self, x, frames, out32=None, scale=None, shift=None):
+        """x: ActB; frames: uint8 [N,H,W,head_c] device tensor; out32: optional fp32 engine.Act (w2l_convb_forward_head)"""
+        check(self._lib.w2l_convb_forward_head(self.handle, current_stream(), x.N, x.H, x.W, x.ptr, x.cs, ptr(frames),
+                                               out32.ptr if out32 is not None else None, out32.cs if out32 is not None else 0,
+                                               ptr(scale), ptr(shift)), "convb_forward_head")
+
     def out_hw(self, H, W):
         ho, wo = C.c_int(), C.c_int()
         check(self._lib.w2l_conv_out_hw(C.byref(self.geom), H, W, C.byref(ho), C.byref(wo)), "conv_out_hw")
         return ho.value, wo.value
+
+    def macs(self, N, H, W):
+        m = int(self._lib.w2l_conv_macs(C.byref(self.geom), N, H, W))
+        if getattr(self, "cout_inner", None) is not None:
+            ho, wo = self.out_hw(H, W)
+            m += N * ho * wo * self.cout_inner * self.cout
+        return m
 
     def set_tile(self, tile):
         check(self._lib.w2l_convb_set_tile(self.handle, tile), "convb_set_tile")

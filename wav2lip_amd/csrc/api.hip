@@ -25,6 +25,10 @@ int conv_forward_impl(const w2l_conv* c, hipStream_t stream, int N, int H, int W
 int conv_num_tiles();
 int conv_num_igemm_tiles();
 void tune_store_launch(const w2l_conv* c, int N, int H, int W, bool has_res, int tile, int ksplit);
+int convb_plan_launch(const w2l_convb* c, void* stream, int N, int H, int W, const void* x, int x_cs, void* y, int y_cs,
+                      const void* res, int res_cs, const float* scale, const float* shift, long long* flops_out);   // conv_bf16.hip
+int convb_head_impl(const w2l_convb* c, void* stream, int N, int H, int W, const void* x, int x_cs, uint8_t* frames, float* y32,
+                    int y32_cs, const float* scale, const float* shift, long long* flops_out);
 
 // ---- executed-FLOP counter (w2l_flops_begin / w2l_flops_end): while counting, every conv / weight-gradient launch of the
 // PROCESS adds the multiply-add work its matrix cores execute (padded tiles and K, Winograd products) - launches still happen.
@@ -114,9 +118,11 @@ __global__ void nhwc_to_nchw_kernel(int C, int HW, const float* __restrict__ x, 
 }
 
 // ---------------------------------------------------------------- datagen
-// one thread per pixel: 3 bytes in, c_zero_to floats out (vector stores when the row is 16-B aligned)
+// one thread per pixel: 3 bytes in, c_zero_to values out (vector stores when the row is 16-B aligned).  T = float, or __bf16 for the
+// bf16-storage inference path: the fp32 value below rounded once (RNE)
+template <typename T>
 __global__ void datagen_pack_kernel(long long npix, int S, const uint8_t* __restrict__ faces,
-                                    float* __restrict__ y, int y_cs, int c_zero_to) {
+                                    T* __restrict__ y, int y_cs, int c_zero_to) {
     const int half = S / 2;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < npix;
          i += (long long)gridDim.x * blockDim.x) {
@@ -126,14 +132,25 @@ __global__ void datagen_pack_kernel(long long npix, int S, const uint8_t* __rest
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[c] = (float)((double)f[c] / 255.0);  // f64 divide, then f32 round
         const bool masked = row >= half;
-        float* o = y + i * y_cs;
+        T* o = y + i * y_cs;
         float out[8] = {masked ? 0.f : v[0], masked ? 0.f : v[1], masked ? 0.f : v[2], v[0], v[1], v[2], 0.f, 0.f};
-        if (c_zero_to == 8 && (y_cs & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) {
-            reinterpret_cast<float4*>(o)[0] = make_float4(out[0], out[1], out[2], out[3]);
-            reinterpret_cast<float4*>(o)[1] = make_float4(out[4], out[5], out[6], out[7]);
+        if constexpr (sizeof(T) == 2) {
+            if (c_zero_to == 8 && (y_cs & 7) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) {
+                typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+                bf16x8 q;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) q[c] = (__bf16)out[c];
+                *reinterpret_cast<bf16x8*>(o) = q;
+                continue;
+            }
         } else {
-            for (int c = 0; c < c_zero_to; ++c) o[c] = c < 6 ? out[c] : 0.f;
+            if (c_zero_to == 8 && (y_cs & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) {
+                reinterpret_cast<float4*>(o)[0] = make_float4(out[0], out[1], out[2], out[3]);
+                reinterpret_cast<float4*>(o)[1] = make_float4(out[4], out[5], out[6], out[7]);
+                continue;
+            }
         }
+        for (int c = 0; c < c_zero_to; ++c) o[c] = (T)(c < 6 ? out[c] : 0.f);
     }
 }
 
@@ -207,21 +224,42 @@ __global__ void bce_mean_kernel(int N, const float* __restrict__ p, const float*
 
 using namespace w2l;
 
+enum PlanKind { kPlanConv = 0, kPlanConvB = 1, kPlanConvBHead = 2 };
 struct PlanItem {
-    const w2l_conv* c;
+    const w2l_conv* c;        // kPlanConv
     int N, H, W;
-    const float* x;
+    const void* x;            // fp32 (kPlanConv) or bf16
     int x_cs;
-    float* y;
+    void* y;                  // fp32, bf16 (kPlanConvB) or the uint8 frames (kPlanConvBHead)
     int y_cs;
-    const float* res;
+    const void* res;
     int res_cs;
     int tile;     // -1: heuristic
     int ksplit;
+    int kind = kPlanConv;
+    const w2l_convb* cb = nullptr;      // kPlanConvB / kPlanConvBHead: the layer, its per-item fp32 scale / shift
+    const float* scale = nullptr;
+    const float* shift = nullptr;
+    float* y32 = nullptr;               // kPlanConvBHead: optional fp32 copy of the head output
+    int y32_cs = 0;
 };
 struct w2l_plan {
     std::vector<PlanItem> items;
 };
+
+// one recorded launch; flops_out / cfg_out != NULL: dry run (launches nothing).  bf16-storage items resolve their launch from the
+// shape (the convb rules): configuration id -1, split-K as resolved (reported as 1)
+static int plan_item_run(const PlanItem& it, hipStream_t s, int tile, int ksplit, long long* flops_out, int* cfg_out) {
+    if (it.kind == kPlanConv)
+        return conv_forward_impl(it.c, s, it.N, it.H, it.W, static_cast<const float*>(it.x), it.x_cs, static_cast<float*>(it.y), it.y_cs,
+                                 static_cast<const float*>(it.res), it.res_cs, tile, ksplit, flops_out, cfg_out);
+    if (cfg_out) { cfg_out[0] = -1; cfg_out[1] = 1; }
+    if (it.kind == kPlanConvB)
+        return convb_plan_launch(it.cb, s, it.N, it.H, it.W, it.x, it.x_cs, it.y, it.y_cs, it.res, it.res_cs, it.scale, it.shift,
+                                 flops_out);
+    return convb_head_impl(it.cb, s, it.N, it.H, it.W, it.x, it.x_cs, static_cast<uint8_t*>(it.y), it.y32, it.y32_cs, it.scale,
+                           it.shift, flops_out);
+}
 
 extern "C" {
 
@@ -273,15 +311,30 @@ int w2l_nhwc_to_nchw(void* stream, int N, int C, int H, int W, const float* x, i
     return W2L_OK;
 }
 
-int w2l_datagen_pack(void* stream, int N, int S, const uint8_t* faces, float* y, int y_cs, int c_zero_to) {
+}  // extern "C"
+
+namespace w2l {
+template <typename T>
+static int datagen_pack_t(void* stream, int N, int S, const uint8_t* faces, T* y, int y_cs, int c_zero_to) {
     W2L_REQUIRE(faces && y && N >= 1 && S >= 2, "bad datagen_pack arguments");
     if (c_zero_to < 6) c_zero_to = 6;
     W2L_REQUIRE(c_zero_to <= 8 && y_cs >= c_zero_to, "datagen_pack: need 6 <= c_zero_to <= 8 <= y_cs");
     const long long npix = (long long)N * S * S;
-    hipLaunchKernelGGL(datagen_pack_kernel, dim3(grid_for(npix, 256)), dim3(256), 0,
+    hipLaunchKernelGGL(datagen_pack_kernel<T>, dim3(grid_for(npix, 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), npix, S, faces, y, y_cs, c_zero_to);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
+}
+}  // namespace w2l
+
+extern "C" {
+
+int w2l_datagen_pack(void* stream, int N, int S, const uint8_t* faces, float* y, int y_cs, int c_zero_to) {
+    return datagen_pack_t<float>(stream, N, S, faces, y, y_cs, c_zero_to);
+}
+
+int w2l_datagen_pack_bf16(void* stream, int N, int S, const uint8_t* faces, void* y, int y_cs, int c_zero_to) {
+    return datagen_pack_t<__bf16>(stream, N, S, faces, static_cast<__bf16*>(y), y_cs, c_zero_to);
 }
 
 int w2l_frames_to_u8(void* stream, int N, int H, int W, const float* x, int x_cs, uint8_t* y) {
@@ -343,6 +396,30 @@ int w2l_plan_add_conv(w2l_plan_t* p, const w2l_conv_t* c, int N, int H, int W, c
     return W2L_OK;
 }
 
+int w2l_plan_add_convb(w2l_plan_t* p, const w2l_convb_t* c, int N, int H, int W, const void* x, int x_cs, void* y, int y_cs,
+                       const void* res, int res_cs, const float* scale, const float* shift) {
+    W2L_REQUIRE(p && c && x && y, "NULL argument");
+    PlanItem it{nullptr, N, H, W, x, x_cs, y, y_cs, res, res_cs, -1, 1};
+    it.kind = kPlanConvB; it.cb = c; it.scale = scale; it.shift = shift;
+    long long f = 0;      // validates the item now (shapes, strides, alignment) instead of at the first run
+    const int rc = plan_item_run(it, nullptr, -1, 1, &f, nullptr);
+    if (rc != W2L_OK) return rc;
+    p->items.push_back(it);
+    return W2L_OK;
+}
+
+int w2l_plan_add_convb_head(w2l_plan_t* p, const w2l_convb_t* c, int N, int H, int W, const void* x, int x_cs, uint8_t* frames,
+                            float* y32, int y32_cs, const float* scale, const float* shift) {
+    W2L_REQUIRE(p && c && x && frames, "NULL argument");
+    PlanItem it{nullptr, N, H, W, x, x_cs, frames, 0, nullptr, 0, -1, 1};
+    it.kind = kPlanConvBHead; it.cb = c; it.scale = scale; it.shift = shift; it.y32 = y32; it.y32_cs = y32_cs;
+    long long f = 0;
+    const int rc = plan_item_run(it, nullptr, -1, 1, &f, nullptr);
+    if (rc != W2L_OK) return rc;
+    p->items.push_back(it);
+    return W2L_OK;
+}
+
 int w2l_plan_copy_item(w2l_plan_t* dst, const w2l_plan_t* src, int index) {
     W2L_REQUIRE(dst && src && index >= 0 && index < (int)src->items.size(), "bad plan_copy_item arguments");
     dst->items.push_back(src->items[index]);
@@ -354,7 +431,7 @@ int w2l_plan_run(const w2l_plan_t* p, void* stream) {
     W2L_REQUIRE(p, "NULL plan");
     hipStream_t s = static_cast<hipStream_t>(stream);
     for (const PlanItem& it : p->items) {
-        const int rc = conv_forward_impl(it.c, s, it.N, it.H, it.W, it.x, it.x_cs, it.y, it.y_cs, it.res, it.res_cs, it.tile, it.ksplit, nullptr, nullptr);
+        const int rc = plan_item_run(it, s, it.tile, it.ksplit, nullptr, nullptr);
         if (rc != W2L_OK) return rc;
     }
     return W2L_OK;
@@ -364,8 +441,7 @@ int w2l_plan_executed_flops(const w2l_plan_t* p, long long* flops_out, int* conf
     W2L_REQUIRE(p && flops_out, "bad plan_executed_flops arguments");
     for (size_t i = 0; i < p->items.size(); ++i) {
         const PlanItem& it = p->items[i];
-        const int rc = conv_forward_impl(it.c, nullptr, it.N, it.H, it.W, it.x, it.x_cs, it.y, it.y_cs, it.res, it.res_cs,
-                                         it.tile, it.ksplit, &flops_out[i], config_out ? config_out + 2 * i : nullptr);
+        const int rc = plan_item_run(it, nullptr, it.tile, it.ksplit, &flops_out[i], config_out ? config_out + 2 * i : nullptr);
         if (rc != W2L_OK) return rc;
     }
     return W2L_OK;
@@ -446,6 +522,7 @@ int w2l_plan_autotune(w2l_plan_t* p, void* stream, int reps) {
     int rc = W2L_OK;
     const int ksplits[] = {1, 2, 4, 8, 16};
     for (PlanItem& it : p->items) {
+        if (it.kind != kPlanConv) continue;     // bf16-storage launches: configuration from the shape only
         float best = 1e30f;
         int best_tile = -1, best_ks = 1;
         for (int tile = 0; tile < conv_num_tiles() && rc == W2L_OK; ++tile) {
@@ -458,8 +535,7 @@ int w2l_plan_autotune(w2l_plan_t* p, void* stream, int reps) {
                 // Resolve first (dry run, launches nothing) and time only candidates that resolve to themselves.
                 long long fl = 0;
                 int resolved[2] = {-1, -1};
-                rc = conv_forward_impl(it.c, nullptr, it.N, it.H, it.W, it.x, it.x_cs, it.y, it.y_cs, it.res, it.res_cs, tile, ks,
-                                       &fl, resolved);
+                rc = plan_item_run(it, nullptr, tile, ks, &fl, resolved);
                 if (rc != W2L_OK) break;
                 if (resolved[0] != tile) break;        // another kernel would run: no split of it is a candidate either
                 const int rks = resolved[1];           // split-K as it resolves (clamped to the K-steps, dropped by kernels without it)
@@ -468,8 +544,7 @@ int w2l_plan_autotune(w2l_plan_t* p, void* stream, int reps) {
                 float tmin = 1e30f;
                 for (int r = 0; r <= reps && rc == W2L_OK; ++r) {   // r == 0: warm-up
                     (void)hipEventRecord(e0, s);
-                    rc = conv_forward_impl(it.c, s, it.N, it.H, it.W, it.x, it.x_cs, it.y, it.y_cs, it.res, it.res_cs,
-                                           tile, rks, nullptr, nullptr);
+                    rc = plan_item_run(it, s, tile, rks, nullptr, nullptr);
                     (void)hipEventRecord(e1, s);
                     if (hipEventSynchronize(e1) != hipSuccess) { set_error("sync failed in plan_autotune"); rc = W2L_ERR_HIP; }
                     float ms = 0.f;
@@ -505,6 +580,8 @@ int w2l_plan_get_config(const w2l_plan_t* p, int index, int* tile, int* ksplit) 
 int w2l_plan_set_config(w2l_plan_t* p, int index, int tile, int ksplit) {
     W2L_REQUIRE(p && index >= 0 && index < (int)p->items.size(), "bad plan_set_config arguments");
     W2L_REQUIRE(tile >= -1 && tile < conv_num_tiles() && ksplit >= 1 && ksplit <= 64, "bad config (%d, %d)", tile, ksplit);
+    W2L_REQUIRE(p->items[index].kind == kPlanConv || (tile == -1 && ksplit == 1),
+                "plan_set_config: launch %d is a bf16-storage launch, configured by its shape only (-1, 1)", index);
     p->items[index].tile = tile;
     p->items[index].ksplit = ksplit;
     return W2L_OK;
@@ -522,7 +599,7 @@ int w2l_plan_profile(const w2l_plan_t* p, void* stream, int reps, float* ms_out)
         (void)hipEventRecord(ev[0], s);
         for (size_t i = 0; i < n && rc == W2L_OK; ++i) {
             const PlanItem& it = p->items[i];
-            rc = conv_forward_impl(it.c, s, it.N, it.H, it.W, it.x, it.x_cs, it.y, it.y_cs, it.res, it.res_cs, it.tile, it.ksplit, nullptr, nullptr);
+            rc = plan_item_run(it, s, it.tile, it.ksplit, nullptr, nullptr);
             (void)hipEventRecord(ev[i + 1], s);
         }
         if (hipStreamSynchronize(s) != hipSuccess) { set_error("sync failed in plan_profile"); rc = W2L_ERR_HIP; }

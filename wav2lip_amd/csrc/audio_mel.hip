@@ -86,8 +86,10 @@ __global__ __launch_bounds__(256) void mel_frame_kernel(const MelKArgs a) {
     }
 }
 
-__global__ void mel_gather_kernel(const float* __restrict__ mel, int T, const int* __restrict__ starts, int B,
-                                  float* __restrict__ out, int out_cs, int c_zero_to) {
+// T = float, or __bf16 (the bf16-storage inference path: each value rounded once, RNE)
+template <typename T>
+__global__ void mel_gather_kernel(const float* __restrict__ mel, int T_, const int* __restrict__ starts, int B,
+                                  T* __restrict__ out, int out_cs, int c_zero_to) {
     const long long total = (long long)B * kMels * 16;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (long long)gridDim.x * blockDim.x) {
@@ -95,9 +97,9 @@ __global__ void mel_gather_kernel(const float* __restrict__ mel, int T, const in
         const int m = (int)((i >> 4) % kMels);
         const int b = (int)(i / (16 * kMels));
         const int s = starts[b] + j;
-        float* o = out + i * out_cs;
-        o[0] = (s >= 0 && s < T) ? mel[(long long)m * T + s] : 0.f;
-        for (int c = 1; c < c_zero_to; ++c) o[c] = 0.f;
+        T* o = out + i * out_cs;
+        o[0] = (T)((s >= 0 && s < T_) ? mel[(long long)m * T_ + s] : 0.f);
+        for (int c = 1; c < c_zero_to; ++c) o[c] = (T)0.f;
     }
 }
 
@@ -206,18 +208,34 @@ int w2l_melspectrogram(const w2l_mel_t* m, void* stream, const float* wav, long 
     return W2L_OK;
 }
 
-int w2l_mel_gather(void* stream, const float* mel, int T, const int32_t* starts, int B, float* out, int out_cs,
-                   int c_zero_to) {
+}  // extern "C"
+
+namespace w2l {
+template <typename T_>
+static int mel_gather_t(void* stream, const float* mel, int T, const int32_t* starts, int B, T_* out, int out_cs, int c_zero_to) {
     W2L_REQUIRE(mel && starts && out && T >= 16 && B >= 1, "bad mel_gather arguments");
     if (c_zero_to < 1) c_zero_to = 1;
     W2L_REQUIRE(out_cs >= c_zero_to, "out_cs=%d < %d", out_cs, c_zero_to);
     const long long total = (long long)B * kMels * 16;
     long long g = (total + 255) / 256;
     if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(mel_gather_kernel, dim3((unsigned)g), dim3(256), 0, static_cast<hipStream_t>(stream), mel, T,
+    hipLaunchKernelGGL(mel_gather_kernel<T_>, dim3((unsigned)g), dim3(256), 0, static_cast<hipStream_t>(stream), mel, T,
                        starts, B, out, out_cs, c_zero_to);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
+}
+}  // namespace w2l
+
+extern "C" {
+
+int w2l_mel_gather(void* stream, const float* mel, int T, const int32_t* starts, int B, float* out, int out_cs,
+                   int c_zero_to) {
+    return mel_gather_t<float>(stream, mel, T, starts, B, out, out_cs, c_zero_to);
+}
+
+int w2l_mel_gather_bf16(void* stream, const float* mel, int T, const int32_t* starts, int B, void* out, int out_cs,
+                        int c_zero_to) {
+    return mel_gather_t<__bf16>(stream, mel, T, starts, B, static_cast<__bf16*>(out), out_cs, c_zero_to);
 }
 
 int w2l_resample_sinc(void* stream, const float* x, int n_in, const double* tr, int n_out, double sample_ratio,

@@ -677,6 +677,11 @@ struct w2l_convb {
     w2l::BVariant generic;
     w2l::BVariant unit_in;   // transposed, stride 1, 1x1 input: one single-tap phase per output position
     int tile_override = -1;
+    // fused 1x1 head (w2l_convb_attach_head): the layer then runs on conv_k3s_kernel's bf16 form, uint8 frames out
+    __bf16* k3_u = nullptr;  // the weights in that kernel's fragment order (one bf16 plane)
+    float* head_w = nullptr; // [head_c][cout]
+    float* head_b = nullptr;
+    int head_c = 0, head_act = 0;
 };
 
 namespace w2l {
@@ -865,6 +870,7 @@ int w2l_convb_update(w2l_convb_t* c, const float* weight, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = packb(c, c->generic, weight, s);
     if (rc == W2L_OK && c->unit_in.built) rc = packb(c, c->unit_in, weight, s);
+    if (rc == W2L_OK && c->k3_u) rc = k3sb_pack(weight, c->k3_u, c->g.cin, s);
     return rc;
 }
 
@@ -936,6 +942,8 @@ int w2l_convb_update_many(int n, w2l_convb_t* const* handles, const float* const
     }
     hipLaunchKernelGGL(pack_weights_bf16_many_kernel, dim3((unsigned)grp->nblocks), dim3(256), 0, s, grp->tab, grp->blk);
     W2L_HIP_CHECK(hipGetLastError());
+    for (int i = 0; i < n; ++i)        // layers with a fused head also hold the head kernel's copy
+        if (handles[i]->k3_u && k3sb_pack(weights[i], handles[i]->k3_u, handles[i]->g.cin, s) != W2L_OK) return W2L_ERR_HIP;
     return W2L_OK;
 }
 
@@ -961,7 +969,49 @@ int w2l_convb_destroy(w2l_convb_t* c) {
     if (!c) return W2L_OK;
     freeb(c->generic);
     freeb(c->unit_in);
+    if (c->k3_u) (void)hipFree(c->k3_u);
+    if (c->head_w) (void)hipFree(c->head_w);
+    if (c->head_b) (void)hipFree(c->head_b);
     delete c;
+    return W2L_OK;
+}
+
+int w2l_convb_attach_head(w2l_convb_t* c, const float* weight, const float* head_weight, const float* head_bias, int head_c,
+                          int head_act, void* stream) {
+    W2L_REQUIRE(c && weight && head_weight, "NULL argument");
+    W2L_REQUIRE(head_c >= 1 && head_c <= 4, "head_c=%d: 1..4 output channels supported", head_c);
+    W2L_REQUIRE(head_act >= W2L_ACT_NONE && head_act <= W2L_ACT_LEAKY, "bad head act %d", head_act);
+    W2L_REQUIRE(k3s_ok(c->g), "convb_attach_head: the fused head needs a 3x3 stride-1 pad-1 conv with cin %% 16 == 0 and 32 couts");
+    W2L_REQUIRE(c->k3_u == nullptr, "head already attached");
+    {
+        static std::mutex m;
+        std::lock_guard<std::mutex> lock(m);
+        if (k3sb_init_attrs() != W2L_OK) return W2L_ERR_HIP;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = W2L_OK;
+    if (hipMalloc(&c->k3_u, sizeof(__bf16) * k3sb_u_elems(c->g.cin)) != hipSuccess ||
+        hipMalloc(&c->head_w, sizeof(float) * head_c * c->g.cout) != hipSuccess ||
+        (head_bias && hipMalloc(&c->head_b, sizeof(float) * head_c) != hipSuccess)) {
+        set_error("convb_attach_head: hipMalloc failed");
+        rc = W2L_ERR_NOMEM;
+    }
+    if (rc == W2L_OK) rc = k3sb_pack(weight, c->k3_u, c->g.cin, s);
+    if (rc == W2L_OK && hipMemcpyAsync(c->head_w, head_weight, sizeof(float) * head_c * c->g.cout, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        rc = W2L_ERR_HIP;
+    if (rc == W2L_OK && head_bias && hipMemcpyAsync(c->head_b, head_bias, sizeof(float) * head_c, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        rc = W2L_ERR_HIP;
+    if (rc == W2L_OK && hipStreamSynchronize(s) != hipSuccess) rc = W2L_ERR_HIP;
+    if (rc != W2L_OK) {
+        if (rc == W2L_ERR_HIP) set_error("convb_attach_head: HIP call failed");
+        if (c->k3_u) (void)hipFree(c->k3_u);
+        if (c->head_w) (void)hipFree(c->head_w);
+        if (c->head_b) (void)hipFree(c->head_b);
+        c->k3_u = nullptr; c->head_w = nullptr; c->head_b = nullptr;
+        return rc;
+    }
+    c->head_c = head_c;
+    c->head_act = head_act;
     return W2L_OK;
 }
 
@@ -986,6 +1036,9 @@ struct BnBwdOperands {      // the BatchNorm block whose dy this launch produces
     const float* shift;
     int store_g;            // ReLU block: the launch stores the masked gradient (W2L_BNBWD_STORE_MASKED)
 };
+
+// set by a dry run (w2l_plan_executed_flops): the launch that would run stores its executed FLOPs here and launches nothing
+static thread_local long long* t_dry_flops = nullptr;
 
 static int convb_forward_impl(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, void* y, int y_cs,
                               const void* res, int res_cs, const float* scale, const float* shift, int ksplit_force,
@@ -1028,6 +1081,7 @@ static int convb_forward_impl(const w2l_convb_t* c, void* stream, int N, int H, 
         v.ph[0].ntaps == g.kh * g.kw && Ho == H && Wo == W && v.sy == 1 && v.sx == 1 && (g.kh == 7 || box_level != 2) &&
         stem_ok(g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, c->cin_p, g.cout, N, H, W, res != nullptr)) {
         if (stats_out) *stats_out = nullptr;      // no partials / sums: the stand-alone reductions follow (few channels: cheap passes)
+        if (t_dry_flops) { *t_dry_flops = 2ll * N * H * W * c->cout_p * v.ph[0].kp; return W2L_OK; }
         if (flops_counting()) flops_add(2ll * N * H * W * c->cout_p * v.ph[0].kp, 5);
         return stem_launch(static_cast<hipStream_t>(stream), x, x_cs, y, y_cs, res, res_cs, v.w_dev, c->cout_p, v.ph[0].kp, scale, shift,
                            v.taps_dev, N, H, W, g.kh, c->cin_p, g.cout, g.act);
@@ -1036,6 +1090,7 @@ static int convb_forward_impl(const w2l_convb_t* c, void* stream, int N, int H, 
         v.ph[0].kp == 576 && box64_ok(v.nphase, v.ph[0].ntaps, c->cin_p, g.cout, c->cout_p, N, H, W, Ho, Wo, v.sy, v.sx)) {
         // forward statistics, or (bb) the BatchNorm-backward sums of the block whose dy this launch completes: per-wave partials
         static const bool box_bwd = [] { const char* e = getenv("W2L_BOX_BWD_SUMS"); return e ? atoi(e) != 0 : true; }();   // A/B switch
+        if (t_dry_flops) { *t_dry_flops = 2ll * N * H * W * 64 * 576; return W2L_OK; }
         hipStream_t s = static_cast<hipStream_t>(stream);
         float* stats = nullptr;
         BoxBwd bw;
@@ -1063,6 +1118,12 @@ static int convb_forward_impl(const w2l_convb_t* c, void* stream, int N, int H, 
     static const bool tp2b_on = [] { const char* e = getenv("W2L_CONVB_TP2B"); return e ? atoi(e) != 0 : true; }();
     if (tp2b_on && !unit && c->tile_override < 0 && ksplit_force < 1 &&
         tp2b_ok(g.transposed, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, v.nphase, v.ph, v.taps_host.data(), c->cin_p, c->cout_p, N, H, W, Ho, Wo)) {
+        if (t_dry_flops) {
+            long long kp = 0;
+            for (int i = 0; i < v.nphase; ++i) kp += (long long)v.ph[i].ntaps * c->cin_p;
+            *t_dry_flops = 2ll * N * H * W * c->cout_p * kp;
+            return W2L_OK;
+        }
         hipStream_t s = static_cast<hipStream_t>(stream);
         float* stats = nullptr;
         if (stats_out) {
@@ -1097,6 +1158,12 @@ static int convb_forward_impl(const w2l_convb_t* c, void* stream, int N, int H, 
     a.bz = nullptr; a.by = nullptr; a.bmean = nullptr; a.brstd = nullptr; a.bscale = nullptr; a.bshift = nullptr;
     a.bz_cs = 0; a.by_cs = 0; a.bneg = 1.f; a.bstore_g = 0; a.bmask_only = 0;
     const BTile& tc = kBTiles[ti];
+    if (t_dry_flops) {
+        long long kp = 0;
+        for (int i = 0; i < v.nphase; ++i) kp += v.ph[i].kp;
+        *t_dry_flops = 2ll * ceil_div(a.M, tc.bm) * tc.bm * ceil_div(c->cout_p, tc.bn) * tc.bn * kp;
+        return W2L_OK;
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long long npix = (long long)N * Ho * Wo;
     if (stats_out && !(bb && bb->z == nullptr)) {
@@ -1181,7 +1248,51 @@ extern "C" {
 
 int w2l_convb_forward(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, void* y, int y_cs,
                       const void* res, int res_cs, const float* scale, const float* shift, int ksplit_force) {
+    W2L_REQUIRE(c == nullptr || c->k3_u == nullptr, "convb_forward: the layer has a fused head, run it with w2l_convb_forward_head");
     return convb_forward_impl(c, stream, N, H, W, x, x_cs, y, y_cs, res, res_cs, scale, shift, ksplit_force, nullptr, nullptr);
+}
+
+}  // extern "C"
+
+namespace w2l {
+// the head launch of w2l_convb_forward_head / a plan item; flops_out != NULL: dry run (launches nothing)
+int convb_head_impl(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, uint8_t* frames, float* y32,
+                    int y32_cs, const float* scale, const float* shift, long long* flops_out) {
+    W2L_REQUIRE(c && x && frames && scale && shift, "NULL argument");
+    W2L_REQUIRE(c->k3_u != nullptr, "convb_forward_head: no head attached (w2l_convb_attach_head)");
+    W2L_REQUIRE(N >= 1 && H >= 1 && W >= 1, "bad shape N=%d H=%d W=%d", N, H, W);
+    W2L_REQUIRE(x_cs >= c->g.cin && (x_cs & 7) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0,
+                "x_cs=%d must be a multiple of 8 and >= %d, x 16-byte aligned", x_cs, c->g.cin);
+    W2L_REQUIRE(y32 == nullptr || y32_cs >= c->head_c, "y32_cs=%d < %d", y32_cs, c->head_c);
+    W2L_REQUIRE(((long long)N * H * W * x_cs) * 2 < (1ll << 31) && (y32 == nullptr || ((long long)N * H * W * y32_cs) * 4 < (1ll << 31)),
+                "activation buffer larger than 2 GiB: split the batch");
+    if (!flops_out && flops_counting()) {
+        long long f = 0;
+        k3sb_launch(static_cast<const __bf16*>(x), x_cs, frames, y32, y32_cs, c->k3_u, scale, shift, c->head_w, c->head_b, c->head_c,
+                    c->head_act, N, H, W, c->g.cin, c->g.act, nullptr, &f);
+        flops_add(f, 5);
+    }
+    return k3sb_launch(static_cast<const __bf16*>(x), x_cs, frames, y32, y32_cs, c->k3_u, scale, shift, c->head_w, c->head_b, c->head_c,
+                       c->head_act, N, H, W, c->g.cin, c->g.act, static_cast<hipStream_t>(stream), flops_out);
+}
+
+// plan items (api.hip): a plain launch; flops_out != NULL: dry run
+int convb_plan_launch(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, void* y, int y_cs,
+                      const void* res, int res_cs, const float* scale, const float* shift, long long* flops_out) {
+    if (!flops_out) return convb_forward_impl(c, stream, N, H, W, x, x_cs, y, y_cs, res, res_cs, scale, shift, 0, nullptr, nullptr);
+    // executed FLOPs of the launch the shape rules resolve to, counted as w2l_flops_begin counts them; nothing is launched
+    t_dry_flops = flops_out;
+    const int rc = convb_forward_impl(c, stream, N, H, W, x, x_cs, y, y_cs, res, res_cs, scale, shift, 0, nullptr, nullptr);
+    t_dry_flops = nullptr;
+    return rc;
+}
+}  // namespace w2l
+
+extern "C" {
+
+int w2l_convb_forward_head(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, uint8_t* frames, float* y32,
+                           int y32_cs, const float* scale, const float* shift) {
+    return convb_head_impl(c, stream, N, H, W, x, x_cs, frames, y32, y32_cs, scale, shift, nullptr);
 }
 
 int w2l_convb_forward_bn(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, void* z, int z_cs,

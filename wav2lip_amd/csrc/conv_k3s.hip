@@ -8,6 +8,9 @@
 // the MFMAs of tap t; pre-split weights stream from L2 in fragment order through a three-tap ring (all four waves read the same ones).
 // Why: the layer ran on F(2x2) Winograd on the fp32 pipe (4 fp32-pipe units per output and (cin, cout) pair); direct split products are
 // 9 x 6 / 16 = 3.4, and the kernel leaves half a CU's LDS to the other batches in flight.
+// The bf16-storage inference path (w2l_convb_attach_head) runs the same kernel with kBf16In: the input is already bf16 NHWC, so a slot
+// loads 16 bytes into ONE plane and every product is one MFMA; with kU8Out the epilogue (fp32) writes the uint8 frames (the truncation of
+// w2l_frames_to_u8) and, optionally, the fp32 head output beside them.
 #include "w2l_common.h"
 
 namespace w2l {
@@ -34,8 +37,9 @@ constexpr int kK3LdsBytes = kK3MainBytes + kK3BM * 4;
 static_assert(kK3StageBytes <= kK3MainBytes && 2 * kK3LdsBytes <= 160 * 1024, "two workgroups per CU");
 
 struct K3sKArgs {
-    const float* x;
-    float* y;
+    const void* x;       // fp32, or bf16 with kBf16In
+    float* y;            // kU8Out: optional fp32 copy of the head output (y_cs channels per pixel)
+    uint8_t* frames;     // kU8Out: [N,H,W,head_c] = (uint8)(v * 255.f)
     const float* res;
     const __bf16* u;     // k3s_pack below
     const float* scale;
@@ -69,12 +73,15 @@ __device__ __forceinline__ float k3_act(float v, int act) {
     return v;
 }
 
+template <bool kBf16In, bool kU8Out>
 __global__ __launch_bounds__(256, 2) void conv_k3s_kernel(const K3sKArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int* s_opix = reinterpret_cast<int*>(smem + kK3MainBytes);        // [256] output pixel of a row or -1
+    constexpr int kEl = kBf16In ? 2 : 4;          // bytes per input element
+    constexpr int kNP = kBf16In ? 1 : 3;          // operand planes (bf16 pieces) per value
 
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.x), 0, (int)((((long long)a.N * a.H * a.W - 1) * a.x_cs + a.cin) * 4), 0x00020000);
+        const_cast<void*>(a.x), 0, (int)((((long long)a.N * a.H * a.W - 1) * a.x_cs + a.cin) * kEl), 0x00020000);
     const int bhw = a.bh * a.bw;
 
     const unsigned total = (unsigned)a.total;
@@ -114,7 +121,7 @@ __global__ __launch_bounds__(256, 2) void conv_k3s_kernel(const K3sKArgs a) {
             const int n = gi * a.ni + il;
             const int iy = by_i * a.bh + ry - 1, ix = bx_i * a.bw + rxx - 1;
             if (n < a.N && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W)
-                off = ((unsigned)((n * a.H + iy) * a.W + ix) * (unsigned)a.x_cs + (unsigned)(kh * 8)) * 4u;
+                off = ((unsigned)((n * a.H + iy) * a.W + ix) * (unsigned)a.x_cs + (unsigned)(kh * 8)) * (unsigned)kEl;
         }
         goff[k] = off;
         lds_off[k] = kh * kK3KhBytes + p * 16;
@@ -125,18 +132,23 @@ __global__ __launch_bounds__(256, 2) void conv_k3s_kernel(const K3sKArgs a) {
     for (int k = 0; k < 3; ++k) slot_on[k] = (256 * k + wave * 64) < 2 * a.RP;
     f32x4 rawreg[3][2];
     auto raw_gload = [&](int step) {
-        const unsigned soff = (unsigned)(step * kK3KS * 4);
+        const unsigned soff = (unsigned)(step * kK3KS * kEl);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             if (!slot_on[k]) continue;
             rawreg[k][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)goff[k], (int)soff, 0));
-            rawreg[k][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(goff[k] + 16u), (int)soff, 0));
+            if constexpr (!kBf16In)
+                rawreg[k][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(goff[k] + 16u), (int)soff, 0));
         }
     };
-    auto raw_store = [&](int buf) {      // split once, three 16-byte stores per slot
+    auto raw_store = [&](int buf) {      // split once, three 16-byte stores per slot (bf16 input: the 16 bytes as they are)
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             if (!slot_on[k]) continue;
+            if constexpr (kBf16In) {
+                *reinterpret_cast<f32x4*>(smem + buf * kK3BufBytes + lds_off[k]) = rawreg[k][0];
+                continue;
+            }
             unsigned h[4], m[4], l[4];
             k3_split3_pair(rawreg[k][0][0], rawreg[k][0][1], h[0], m[0], l[0]);
             k3_split3_pair(rawreg[k][0][2], rawreg[k][0][3], h[1], m[1], l[1]);
@@ -162,15 +174,15 @@ __global__ __launch_bounds__(256, 2) void conv_k3s_kernel(const K3sKArgs a) {
     }
     const int rw16 = a.RW * 16;
 
-    // ---- B operand: u[((kc * 9 + tap) * 3 + plane) * 512 + lane * 8 + e] = piece `plane` of w[lane&31][kc*16 + 8*(lane>>5) + e][tap]
-    const int F = a.nkc * 27;
+    // ---- B operand: u[((kc * 9 + tap) * kNP + plane) * 512 + lane * 8 + e] = piece `plane` of w[lane&31][kc*16 + 8*(lane>>5) + e][tap]
+    const int F = a.nkc * 9 * kNP;
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(a.u), 0, F * 1024, 0x00020000);
     const unsigned bl_lane = (unsigned)(lane * 16);
     auto bload = [&](int kc, int tap, int plane) {       // past-the-end chunks read zero (never used)
-        return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ru, (int)bl_lane, (int)((unsigned)((kc * 9 + tap) * 3 + plane) * 1024u), 0));
+        return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ru, (int)bl_lane, (int)((unsigned)((kc * 9 + tap) * kNP + plane) * 1024u), 0));
     };
     constexpr int RING = 3;
-    bf16x8 bq[RING][3];
+    bf16x8 bq[RING][kNP];
 
     f32x16 acc[2];
 #pragma unroll
@@ -183,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void conv_k3s_kernel(const K3sKArgs a) {
 #pragma unroll
     for (int i = 0; i < RING; ++i)
 #pragma unroll
-        for (int p = 0; p < 3; ++p) bq[i][p] = bload(0, i, p);
+        for (int p = 0; p < kNP; ++p) bq[i][p] = bload(0, i, p);
     raw_store(0);
     raw_gload(1);
     __syncthreads();
@@ -196,13 +208,13 @@ __global__ __launch_bounds__(256, 2) void conv_k3s_kernel(const K3sKArgs a) {
         raw_store(buf ^ 1);              // raw(step+1) -> LDS[buf^1] (last read during step-1, a barrier ago)
         raw_gload(step + 2);
         const char* Ab = smem + buf * kK3BufBytes;
-        bf16x8 af[2][2][3];
+        bf16x8 af[2][2][kNP];
         auto aload = [&](int set, int tap) {
             const int sh = (tap / 3) * rw16 + (tap % 3) * 16;
 #pragma unroll
             for (int b = 0; b < 2; ++b)
 #pragma unroll
-                for (int p = 0; p < 3; ++p)
+                for (int p = 0; p < kNP; ++p)
                     af[set][b][p] = *reinterpret_cast<const bf16x8*>(Ab + p * kK3PlaneBytes + abase[b] + sh);
         };
         aload(0, 0);
@@ -210,18 +222,24 @@ __global__ __launch_bounds__(256, 2) void conv_k3s_kernel(const K3sKArgs a) {
         for (int tap = 0; tap < 9; ++tap) {
             const int cur = tap & 1;
             if (tap + 1 < 9) aload(cur ^ 1, tap + 1);
-            bf16x8 bc[3];
+            bf16x8 bc[kNP];
 #pragma unroll
-            for (int p = 0; p < 3; ++p) bc[p] = bq[tap % RING][p];
+            for (int p = 0; p < kNP; ++p) bc[p] = bq[tap % RING][p];
 #pragma unroll
-            for (int p = 0; p < 3; ++p)      // ring of 3: taps 3..8 of this chunk, then 0..2 of the next
+            for (int p = 0; p < kNP; ++p)    // ring of 3: taps 3..8 of this chunk, then 0..2 of the next
                 bq[tap % RING][p] = (tap < 6) ? bload(step, tap + 3, p) : bload(step + 1, tap - 6, p);
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 6; ++u)
+            if constexpr (kBf16In) {
 #pragma unroll
                 for (int b = 0; b < 2; ++b)
-                    acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[cur][b][kPa[u]], bc[kPb[u]], acc[b], 0, 0, 0);
+                    acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[cur][b][0], bc[0], acc[b], 0, 0, 0);
+            } else {
+#pragma unroll
+                for (int u = 0; u < 6; ++u)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b)
+                        acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[cur][b][kPa[u]], bc[kPb[u]], acc[b], 0, 0, 0);
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
         __syncthreads();
@@ -266,7 +284,14 @@ __global__ __launch_bounds__(256, 2) void conv_k3s_kernel(const K3sKArgs a) {
                     *reinterpret_cast<f32x4*>(a.y + (long long)opix * a.y_cs + 4 * g) = v;
                 }
             }
-            if (a.head_w) {
+            if constexpr (kU8Out) {
+                // the generator output stays fp32 up to the uint8 truncation of w2l_frames_to_u8 (numpy: f32 * 255., astype(uint8))
+                for (int o = 0; o < a.head_c; ++o) {
+                    const float v = k3_act(hacc[o] + (a.head_b ? a.head_b[o] : 0.f), a.head_act);
+                    if (a.y) a.y[(long long)opix * a.y_cs + o] = v;
+                    a.frames[(long long)opix * a.head_c + o] = (uint8_t)(int)(v * 255.0f);
+                }
+            } else if (a.head_w) {
                 float* dst = a.y + (long long)opix * a.y_cs;
                 for (int o = 0; o < a.head_c; ++o) dst[o] = k3_act(hacc[o] + (a.head_b ? a.head_b[o] : 0.f), a.head_act);
             }
@@ -283,6 +308,7 @@ struct K3sPackArgs {
     int cin;
 };
 
+template <int kNP>
 __global__ void k3s_pack_kernel(const K3sPackArgs a) {
     const long long total = (long long)kK3BC * a.cin * 9;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -294,12 +320,14 @@ __global__ void k3s_pack_kernel(const K3sPackArgs a) {
         const int co = ln & 31, ci = kc * 16 + 8 * (ln >> 5) + e;
         const float v = a.w[((long long)co * a.cin + ci) * 9 + tap];
         const __bf16 hp = (__bf16)v;
-        const float r1 = v - (float)hp;
-        const __bf16 mp = (__bf16)r1;
-        __bf16* d = a.u + ((long long)kc * 9 + tap) * (3 * 512) + ln * 8 + e;
+        __bf16* d = a.u + ((long long)kc * 9 + tap) * (kNP * 512) + ln * 8 + e;
         d[0] = hp;
-        d[512] = mp;
-        d[1024] = (__bf16)(r1 - (float)mp);
+        if constexpr (kNP == 3) {
+            const float r1 = v - (float)hp;
+            const __bf16 mp = (__bf16)r1;
+            d[512] = mp;
+            d[1024] = (__bf16)(r1 - (float)mp);
+        }
     }
 }
 
@@ -326,32 +354,46 @@ bool k3s_ok(const w2l_conv_geom& g) {
 }
 
 long long k3s_u_elems(int cin) { return (long long)kK3BC * cin * 9 * 3; }
+long long k3sb_u_elems(int cin) { return (long long)kK3BC * cin * 9; }
 
-int k3s_pack(const float* w, __bf16* u, int cin, hipStream_t stream) {
+template <int kNP>
+static int k3s_pack_t(const float* w, __bf16* u, int cin, hipStream_t stream) {
     K3sPackArgs pa;
     pa.w = w; pa.u = u; pa.cin = cin;
     long long blocks = ((long long)kK3BC * cin * 9 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k3s_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, pa);
+    hipLaunchKernelGGL(k3s_pack_kernel<kNP>, dim3((unsigned)blocks), dim3(256), 0, stream, pa);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }
+int k3s_pack(const float* w, __bf16* u, int cin, hipStream_t stream) { return k3s_pack_t<3>(w, u, cin, stream); }
+// bf16-storage layers: the weights rounded once (RNE), one plane - the rounding w2l_convb_create applies to every other layer
+int k3sb_pack(const float* w, __bf16* u, int cin, hipStream_t stream) { return k3s_pack_t<1>(w, u, cin, stream); }
 
 int k3s_init_attrs() {   // called under the lock of init_kernel_attrs (conv_igemm.hip)
     static bool done = false;
     if (done) return W2L_OK;
-    W2L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_k3s_kernel),
+    W2L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_k3s_kernel<false, false>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, kK3LdsBytes));
     done = true;
     return W2L_OK;
 }
 
-// y: 32 channels per pixel, or head_c when head_w != NULL; res (32 channels) may alias x
-int k3s_launch(const float* x, int x_cs, float* y, int y_cs, const float* res, int res_cs, const __bf16* u, const float* scale,
-               const float* shift, const float* head_w, const float* head_b, int head_c, int head_act, int N, int H, int W, int cin,
-               int act, hipStream_t stream, long long* flops_out) {
+int k3sb_init_attrs() {  // called under the lock of convb_init_attrs (conv_bf16.hip)
+    static bool done = false;
+    if (done) return W2L_OK;
+    W2L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_k3s_kernel<true, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, kK3LdsBytes));
+    done = true;
+    return W2L_OK;
+}
+
+template <bool kBf16In, bool kU8Out>
+static int k3s_launch_t(const void* x, int x_cs, float* y, int y_cs, uint8_t* frames, const float* res, int res_cs, const __bf16* u,
+                        const float* scale, const float* shift, const float* head_w, const float* head_b, int head_c, int head_act,
+                        int N, int H, int W, int cin, int act, hipStream_t stream, long long* flops_out) {
     K3sKArgs a;
-    a.x = x; a.y = y; a.res = res; a.u = u; a.scale = scale; a.shift = shift;
+    a.x = x; a.y = y; a.frames = frames; a.res = res; a.u = u; a.scale = scale; a.shift = shift;
     a.head_w = head_w; a.head_b = head_b; a.head_c = head_c; a.head_act = head_act;
     a.N = N; a.H = H; a.W = W; a.cin = cin; a.x_cs = x_cs; a.y_cs = y_cs; a.res_cs = res_cs; a.act = act;
     const K3Block b = k3s_pick_block(N, H, W);
@@ -366,15 +408,33 @@ int k3s_launch(const float* x, int x_cs, float* y, int y_cs, const float* res, i
     a.total = (long long)a.ngi * a.nby * a.nbx;
     W2L_REQUIRE(a.total < (1ll << 31), "grid too large");
     W2L_REQUIRE(head_w == nullptr || (head_c >= 1 && head_c <= 4), "fused head: 1 .. 4 channels");
-    if (flops_out) {   // dry run: 9 tap GEMMs of [items*256] x [32] x cin, six bf16 piece products per product
-        *flops_out = 6ll * 2 * 9 * a.total * kK3BM * kK3BC * cin;
+    if (flops_out) {   // dry run: 9 tap GEMMs of [items*256] x [32] x cin, six bf16 piece products per product (one with bf16 input)
+        *flops_out = (kBf16In ? 1ll : 6ll) * 2 * 9 * a.total * kK3BM * kK3BC * cin;
         return W2L_OK;
     }
     long long grid = (a.total + 7) / 8 * 8;
     if (grid > 512) grid = 512;
-    hipLaunchKernelGGL(conv_k3s_kernel, dim3((unsigned)grid), dim3(256), kK3LdsBytes, stream, a);
+    hipLaunchKernelGGL((conv_k3s_kernel<kBf16In, kU8Out>), dim3((unsigned)grid), dim3(256), kK3LdsBytes, stream, a);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
+}
+
+// y: 32 channels per pixel, or head_c when head_w != NULL; res (32 channels) may alias x
+int k3s_launch(const float* x, int x_cs, float* y, int y_cs, const float* res, int res_cs, const __bf16* u, const float* scale,
+               const float* shift, const float* head_w, const float* head_b, int head_c, int head_act, int N, int H, int W, int cin,
+               int act, hipStream_t stream, long long* flops_out) {
+    return k3s_launch_t<false, false>(x, x_cs, y, y_cs, nullptr, res, res_cs, u, scale, shift, head_w, head_b, head_c, head_act, N, H,
+                                      W, cin, act, stream, flops_out);
+}
+
+// bf16 input x [N,H,W,x_cs] (16-byte aligned, x_cs % 8 == 0) with the fused head: frames u8 [N,H,W,head_c] and, if y != NULL,
+// the same values in fp32 at y [N,H,W,y_cs]
+int k3sb_launch(const __bf16* x, int x_cs, uint8_t* frames, float* y, int y_cs, const __bf16* u, const float* scale, const float* shift,
+                const float* head_w, const float* head_b, int head_c, int head_act, int N, int H, int W, int cin, int act,
+                hipStream_t stream, long long* flops_out) {
+    W2L_REQUIRE(head_w != nullptr && frames != nullptr, "k3sb: the bf16 form always runs with its head and writes uint8 frames");
+    return k3s_launch_t<true, true>(x, x_cs, y, y_cs, frames, nullptr, 0, u, scale, shift, head_w, head_b, head_c, head_act, N, H, W,
+                                    cin, act, stream, flops_out);
 }
 
 }  // namespace w2l

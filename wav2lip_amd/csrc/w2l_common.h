@@ -221,6 +221,13 @@ int k3s_init_attrs();
 int k3s_launch(const float* x, int x_cs, float* y, int y_cs, const float* res, int res_cs, const __bf16* u, const float* scale,
                const float* shift, const float* head_w, const float* head_b, int head_c, int head_act, int N, int H, int W, int cin,
                int act, hipStream_t stream, long long* flops_out);
+// its bf16-storage form with the head always fused (w2l_convb_attach_head): one plane, uint8 frames (+ optional fp32) out
+long long k3sb_u_elems(int cin);
+int k3sb_pack(const float* w, __bf16* u, int cin, hipStream_t stream);
+int k3sb_init_attrs();
+int k3sb_launch(const __bf16* x, int x_cs, uint8_t* frames, float* y, int y_cs, const __bf16* u, const float* scale, const float* shift,
+                const float* head_w, const float* head_b, int head_c, int head_act, int N, int H, int W, int cin, int act,
+                hipStream_t stream, long long* flops_out);
 // the generator's 7x7 first layer with split operands (conv_stem7s.hip): region staged and split once, contraction out of LDS
 bool stem7s_ok(const w2l_conv_geom& g);
 long long stem7s_u_elems();

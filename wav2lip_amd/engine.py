@@ -105,7 +105,9 @@ def apply_plan_configs(plan, kind, N, doc=None, strict=False):
 #           weights / weight gradients / BatchNorm statistics / losses / Adam stay fp32 (csrc/conv_bf16.hip, wgrad_bf16.hip,
 #           train_bf16.hip);
 #   "bf16c" round 2's contraction-only variant (fp32 tensors, operands rounded inside the fp32-layout kernels), kept for A/B.
-# Inference plans always run fp32 (the 1e-3 pixel parity path).
+# Inference plans run fp32 by default (the 1e-3 pixel parity path); the generator also has an OPT-IN bf16-storage plan
+# (`Wav2Lip.graph(..., precision="bf16")`, `precision=` on the runners / lipsync, `--precision bf16` on the CLI): bf16 NHWC
+# activations and weights, BatchNorm folded into fp32 epilogues, the output block writing uint8 frames from fp32.
 TRAIN_PRECISION = [os.environ.get("W2L_TRAIN_PRECISION", "f32")]
 
 
@@ -278,6 +280,30 @@ class Plan:
         self.records.append((name, layer, src.N, src.H, src.W))
         self.has_res.append(res is not None)
 
+    def add_convb(self, name, layer, src, dst, res=None, scale=None, shift=None):
+        """record one bf16-storage launch (bf16.ConvB over bf16.ActB slices) with its fp32 per-channel scale / shift
+        (w2l_plan_add_convb); its configuration comes from the shape"""
+        ho, wo = layer.out_hw(src.H, src.W)
+        if src.C < layer.cin or (dst.N, dst.H, dst.W) != (src.N, ho, wo) or dst.C != layer.cout:
+            raise RuntimeError("plan %s: slices %s -> %s do not match the layer" % (name, (src.N, src.H, src.W, src.C),
+                                                                                    (dst.N, dst.H, dst.W, dst.C)))
+        check(self._lib.w2l_plan_add_convb(self.handle, layer.handle, src.N, src.H, src.W, src.ptr, src.cs, dst.ptr, dst.cs,
+                                           res.ptr if res is not None else None, res.cs if res is not None else 0,
+                                           ptr(scale), ptr(shift)), "plan_add_convb")
+        self.keep += [layer, src.buf, dst.buf, scale, shift] + ([res.buf] if res is not None else [])
+        self.records.append((name, layer, src.N, src.H, src.W))
+        self.has_res.append(res is not None)
+
+    def add_convb_head(self, name, layer, src, frames, out32=None, scale=None, shift=None):
+        """record the bf16-storage output block with its fused head (w2l_plan_add_convb_head): uint8 frames [N,H,W,head_c] and,
+        with `out32` (an fp32 Act), the same values in fp32"""
+        check(self._lib.w2l_plan_add_convb_head(self.handle, layer.handle, src.N, src.H, src.W, src.ptr, src.cs, ptr(frames),
+                                                out32.ptr if out32 is not None else None, out32.cs if out32 is not None else 0,
+                                                ptr(scale), ptr(shift)), "plan_add_convb_head")
+        self.keep += [layer, src.buf, frames, scale, shift] + ([out32.buf] if out32 is not None else [])
+        self.records.append((name, layer, src.N, src.H, src.W))
+        self.has_res.append(False)
+
     def add_raw(self, other, index):
         """re-record launch `index` of plan `other` (same layer handle and buffers)"""
         check(self._lib.w2l_plan_copy_item(self.handle, other.handle, index), "plan_copy_item")
@@ -348,7 +374,8 @@ class Plan:
         fl = (C.c_longlong * n)()
         cfg = (C.c_int * (2 * n))()
         check(self._lib.w2l_plan_executed_flops(self.handle, fl, cfg), "plan_executed_flops")
-        fam = {0: "igemm", 1: "wino", 2: "wino2", 3: "tp2", 4: "wino4", 5: "split", 6: "wino2s", 7: "tp2s", 8: "stem7s", 9: "k3s"}
+        fam = {0: "igemm", 1: "wino", 2: "wino2", 3: "tp2", 4: "wino4", 5: "split", 6: "wino2s", 7: "tp2s", 8: "stem7s", 9: "k3s",
+               -1: "convb"}     # -1: a bf16-storage launch (configured by its shape)
         return [(self.records[i][0], int(fl[i]), fam[self._lib.w2l_conv_config_family(int(cfg[2 * i]))],
                  (int(cfg[2 * i]), int(cfg[2 * i + 1]))) for i in range(n)]
 

@@ -5,6 +5,9 @@
     faces u8 [B,96,96,3] --w2l_datagen_pack--> x fp32 NHWC8 --+
     mel [80,T] + starts --w2l_mel_gather----> m fp32 NHWC4 ---+--> generator plan --> w2l_frames_to_u8 --> u8 [B,96,96,3]
 
+With `precision="bf16"` (opt-in; `--precision bf16` on the command line) the same loop runs the bf16-storage generator plan:
+w2l_datagen_pack_bf16 / w2l_mel_gather_bf16 fill bf16 NHWC8 inputs and the plan's last launch writes the uint8 frames itself.
+
 Either side of that, also on the device: the face crop + `cv2.resize(face, (96, 96))` of
 inference.py:121-126 (w2l_crop_resize_u8) and the `cv2.resize` to the box size + paste-back of :270-271
 (w2l_resize_paste_u8), so that full uint8 frames go in and full uint8 frames come out (`Wav2LipRunner.run_frames`).
@@ -59,7 +62,21 @@ def build_parser():
     return parser
 
 
+def build_cli_parser():
+    """the command line `main()` parses: the reference's flags (`build_parser`, whose surface stays the reference's) plus one
+    documented addition that is not among them, `--precision {fp32,bf16}` (default fp32): the generator's arithmetic"""
+    p = build_parser()
+    p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
+                   help='Generator arithmetic: fp32 (default, matches the reference) or bf16 storage (faster; frames differ by '
+                        'about one uint8 level in a few percent of the bytes)')
+    return p
+
+
+CLI_PRECISION = {"fp32": "f32", "bf16": "bf16"}     # --precision value -> the `precision=` of the runners / lipsync
+
+
 parser = build_parser()
+cli_parser = build_cli_parser()
 
 
 def is_image_path(path):
@@ -70,8 +87,9 @@ def is_image_path(path):
 
 
 def parse_args(argv=None):
-    """inference.py:53-57: parse, then `img_size = 96` and `static = True` for an image input"""
-    a = parser.parse_args(argv)
+    """inference.py:53-57: parse (the reference's flags + `--precision`), then `img_size = 96` and `static = True` for an image
+    input"""
+    a = cli_parser.parse_args(argv)
     a.img_size = img_size
     if os.path.isfile(a.face) and is_image_path(a.face):
         a.static = True
@@ -80,7 +98,7 @@ def parse_args(argv=None):
 
 # The reference parses sys.argv at import time into a module global that `datagen` / `face_detect` read (inference.py:53).  A
 # library cannot do that; `args` holds the defaults until `main()` (or a caller) replaces it.
-args = parser.parse_args(['--checkpoint_path', '', '--face', '', '--audio', ''])
+args = cli_parser.parse_args(['--checkpoint_path', '', '--face', '', '--audio', ''])
 args.img_size = img_size
 device = 'cuda'      # inference.py:157 (`'cuda' if torch.cuda.is_available() else 'cpu'`): this engine has no CPU path
 
@@ -103,10 +121,12 @@ def mel_chunk_starts(n_mel_frames, fps):
 class Wav2LipRunner:
     """Device-resident replacement of the body of the reference's batch loop for one model and batch size."""
 
-    def __init__(self, model, batch_size=128, lane=0):
+    def __init__(self, model, batch_size=128, lane=0, precision="f32"):
+        from .models.wav2lip import check_precision
         self.model = model
         self.batch_size = batch_size
         self.lane = lane
+        self.precision = check_precision(precision)
         self.device = next(model.parameters()).device
         if self.device.type != "cuda":
             raise RuntimeError("wav2lip_amd.inference: the model must be on a HIP device (no CPU path)")
@@ -114,7 +134,7 @@ class Wav2LipRunner:
         self._out_u8 = {}
 
     def _graph(self, n):
-        return self.model.graph(n, img_size, img_size, self.device, lane=self.lane)
+        return self.model.graph(n, img_size, img_size, self.device, lane=self.lane, precision=self.precision)
 
     def run_batch(self, faces_u8, mel_windows=None, mel=None, starts=None, out=None):
         """faces_u8: torch uint8 [n,96,96,3] on the device.  Audio either as ready windows `mel_windows`
@@ -137,13 +157,22 @@ class Wav2LipRunner:
         g = self._graph(n)
         s = current_stream()
         faces_u8 = faces_u8.contiguous()
-        check(self.lib.w2l_datagen_pack(s, n, img_size, ptr(faces_u8), ptr(g.x_in), 8, 8), "datagen_pack")
-        if mel_windows is not None:
-            mw = mel_windows.contiguous().float().view(n, 1, 80, 16)
-            check(self.lib.w2l_nchw_to_nhwc(s, n, 1, 80, 16, ptr(mw), ptr(g.mel_in), 4, 4), "nchw_to_nhwc")
+        if self.precision == "bf16":
+            check(self.lib.w2l_datagen_pack_bf16(s, n, img_size, ptr(faces_u8), ptr(g.x_in), 8, 8), "datagen_pack_bf16")
+            if mel_windows is not None:
+                mw = mel_windows.contiguous().float().view(n, 1, 80, 16)
+                check(self.lib.w2l_nchw_to_nhwc_bf16(s, n, 1, 80, 16, ptr(mw), ptr(g.mel_in), 8, 8), "nchw_to_nhwc_bf16")
+            else:
+                check(self.lib.w2l_mel_gather_bf16(s, ptr(mel), mel.shape[1], ptr(starts), n, ptr(g.mel_in), 8, 8),
+                      "mel_gather_bf16")
         else:
-            check(self.lib.w2l_mel_gather(s, ptr(mel), mel.shape[1], ptr(starts), n, ptr(g.mel_in), 4, 4),
-                  "mel_gather")
+            check(self.lib.w2l_datagen_pack(s, n, img_size, ptr(faces_u8), ptr(g.x_in), 8, 8), "datagen_pack")
+            if mel_windows is not None:
+                mw = mel_windows.contiguous().float().view(n, 1, 80, 16)
+                check(self.lib.w2l_nchw_to_nhwc(s, n, 1, 80, 16, ptr(mw), ptr(g.mel_in), 4, 4), "nchw_to_nhwc")
+            else:
+                check(self.lib.w2l_mel_gather(s, ptr(mel), mel.shape[1], ptr(starts), n, ptr(g.mel_in), 4, 4),
+                      "mel_gather")
         g.run()
         if out is not None:
             if out.dtype != torch.uint8 or tuple(out.shape) != (n, img_size, img_size, 3) or not out.is_cuda or not out.is_contiguous():
@@ -153,7 +182,10 @@ class Wav2LipRunner:
         if out is None:
             out = torch.empty((n, img_size, img_size, 3), dtype=torch.uint8, device=self.device)
             self._out_u8[n] = out
-        check(self.lib.w2l_frames_to_u8(s, n, img_size, img_size, g.out.ptr, g.out.cs, ptr(out)), "frames_to_u8")
+        if self.precision == "bf16":
+            out.copy_(g.frames)         # the plan's last launch wrote the uint8 frames
+        else:
+            check(self.lib.w2l_frames_to_u8(s, n, img_size, img_size, g.out.ptr, g.out.cs, ptr(out)), "frames_to_u8")
         self._last = g
         return out
 
@@ -195,8 +227,8 @@ class PipelinedRunner:
     ticket; `result(ticket)` makes the caller's stream wait for that batch and returns its uint8 frames (valid until the lane is
     reused `depth` submits later)."""
 
-    def __init__(self, model, batch_size=128, depth=2):
-        self.lanes = [Wav2LipRunner(model, batch_size, lane=k) for k in range(depth)]
+    def __init__(self, model, batch_size=128, depth=2, precision="f32"):
+        self.lanes = [Wav2LipRunner(model, batch_size, lane=k, precision=precision) for k in range(depth)]
         dev = self.lanes[0].device
         self.streams = [torch.cuda.Stream(device=dev) for _ in range(depth)]
         self.depth = depth
@@ -331,13 +363,21 @@ def datagen_u8(frames, mels, batch_size=128, static=False, box=None, first=0):
 LIPSYNC_DEPTH = 4     # batches in flight in lipsync() / main(): the depth bench.py measures (bench.py --pipeline)
 
 
-def lipsync(model, frames, wav, fps=25., batch_size=128, static=False, box=None, ranks=None, depth=None):
+def _precision_kw(precision):
+    """runner keyword for a non-default precision: fp32 runs build their runner with the same arguments as before the option"""
+    return {} if precision == "f32" else {"precision": precision}
+
+
+def lipsync(model, frames, wav, fps=25., batch_size=128, static=False, box=None, ranks=None, depth=None, precision="f32"):
     """End-to-end body of inference.py:main for in-memory inputs: returns the list of output frames (uint8).
+    `precision`: "f32" (default) or "bf16" - the generator's arithmetic (Wav2LipRunner); everything else is the same.
 
     `ranks` (sharding.init_from_env(), one process per GPU): the mel chunks are cut into contiguous per-rank shards
     (sharding.shard_range), every rank runs ITS chunks through its own runner with the replicated weights, and the generated
     frames are all-gathered in frame order to rank 0 (sharding.gather_shards_to_writer), which alone returns them - every other
     rank returns None (the reference's loop, inference.py:249-272, is single-process)."""
+    from .models.wav2lip import check_precision
+    check_precision(precision)
     dev = next(model.parameters()).device
     mel = audio.melspectrogram_device(wav, dev)
     if bool(torch.isnan(mel).any()):
@@ -348,7 +388,8 @@ def lipsync(model, frames, wav, fps=25., batch_size=128, static=False, box=None,
     rank = 0 if world == 1 else ranks.rank
     from . import sharding
     first, last = sharding.shard_range(len(starts), rank, world)
-    runner = PipelinedRunner(model, batch_size, depth=depth or LIPSYNC_DEPTH)   # later batches are enqueued before batch i is collected
+    # later batches are enqueued before batch i is collected; the default precision constructs the runner exactly as before
+    runner = PipelinedRunner(model, batch_size, depth=depth or LIPSYNC_DEPTH, **_precision_kw(precision))
     out_frames = []
     starts_dev = torch.tensor(starts, dtype=torch.int32, device=dev)
     shapes = {tuple(f.shape) for f in frames}
@@ -529,7 +570,8 @@ def main(argv=None, keep_frames=True, backend="nccl"):
     """inference.py:181-277 on the HIP path.  Same flags, same steps, same messages; differences, all on the file-format
     side: video input is the uncompressed AVI of wav2lip_amd/container.py (no codecs here), `--audio` must be a WAV (the
     reference shells out to ffmpeg for anything else), and the result - the reference's `temp/result.avi` + ffmpeg mux - is
-    written as ONE AVI (BGR video + the driving audio as PCM16) at `--outfile`.
+    written as ONE AVI (BGR video + the driving audio as PCM16) at `--outfile`.  One flag the reference does not have:
+    `--precision {fp32,bf16}` (default fp32) selects the generator's arithmetic.
 
     Like the reference's loop (inference.py:249-274) this one STREAMS: every batch uploads only the frames it pastes into
     (deduplicated, `frame_idx` remapped) and its output frames go to the AVI writer as soon as they are back, so device and host
@@ -573,7 +615,7 @@ def main(argv=None, keep_frames=True, backend="nccl"):
         idx = [0 if args.static else i % len(full_frames) for i in range(n)]
         boxes = [validate_boxes([coords[0 if args.static else j]], *full_frames[j].shape[:2])[0] for j in idx]
         starts_dev = torch.tensor(starts, dtype=torch.int32, device=dev)
-        runner = PipelinedRunner(model, args.wav2lip_batch_size, depth=LIPSYNC_DEPTH)
+        runner = PipelinedRunner(model, args.wav2lip_batch_size, depth=LIPSYNC_DEPTH, **_precision_kw(CLI_PRECISION[args.precision]))
         bs = args.wav2lip_batch_size
         first, last = sharding.shard_range(n, ranks.rank, ranks.world)
         frame_h, frame_w = full_frames[0].shape[:2]

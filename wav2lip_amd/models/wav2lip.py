@@ -8,8 +8,8 @@ Architecture tables: each row is (kind, cin, cout, kernel, stride, padding, extr
 import torch
 from torch import nn
 
-from .. import autograd, engine
-from .._lib import ACT_NONE, ACT_SIGMOID, check, current_stream, load, ptr
+from .. import autograd, bf16, engine
+from .._lib import ACT_NONE, ACT_SIGMOID, ConvGeom, check, current_stream, load, ptr
 from .conv import Conv2d, Conv2dTranspose, HeadFusedBlock, PlainConv, nonorm_Conv2d
 
 
@@ -209,6 +209,156 @@ class _GeneratorGraph:
         return y
 
 
+PRECISIONS = ("f32", "bf16")
+
+
+def check_precision(precision):
+    if precision not in PRECISIONS:
+        raise ValueError("precision must be 'f32' or 'bf16', got %r" % (precision,))
+    return precision
+
+
+class _FoldedConvB:
+    """one block as a bf16-storage layer for inference: the bf16.ConvB handle (unscaled bf16 weights) and the block's eval-mode
+    BatchNorm (+ conv bias) folded into fp32 scale / shift vectors that the launch applies to its fp32 accumulators - the fold of
+    NodeB's "bn_eval" kind.  The scale is NOT folded into the bf16 weights: that would round them a second time."""
+
+    def __init__(self, blk, device):
+        conv = blk.conv_block[0]
+        bn = blk.conv_block[1] if blk._norm else None
+        if bn is not None and bn.training:
+            blk.fused()          # raises: a train-mode BatchNorm block has no folded form
+        kh, kw = engine._pair(conv.kernel_size)
+        sh, sw = engine._pair(conv.stride)
+        ph, pw = engine._pair(conv.padding)
+        oph, opw = engine._pair(conv.output_padding) if blk._transposed else (0, 0)
+        self.geom = ConvGeom(int(blk._transposed), conv.in_channels, conv.out_channels, kh, kw, sh, sw, ph, pw, oph, opw, blk._act)
+        self.layer = bf16.ConvB(self.geom, conv.weight)
+        self.weight = conv.weight
+        self.residual = blk.residual
+        cout = conv.out_channels
+        cp = (cout + 31) // 32 * 32
+        self.scale = torch.zeros(cp, device=device)
+        self.shift = torch.zeros(cp, device=device)
+        bias = conv.bias.detach().float().contiguous() if conv.bias is not None else None
+        if bn is not None:
+            check(load().w2l_bn_fold(current_stream(), cout, ptr(bias), ptr(bn.weight.detach().float().contiguous()),
+                                     ptr(bn.bias.detach().float().contiguous()), ptr(bn.running_mean.detach().float().contiguous()),
+                                     ptr(bn.running_var.detach().float().contiguous()), float(bn.eps), ptr(self.scale),
+                                     ptr(self.shift)), "bn_fold")
+        else:
+            check(load().w2l_bn_fold(current_stream(), cout, ptr(bias), None, None, None, None, 0.0, ptr(self.scale), ptr(self.shift)),
+                  "bn_fold")
+        self._keep = bias
+
+
+class _BufPoolB(engine.BufPool):
+    """BufPool of NHWC bf16 scratch buffers"""
+
+    def get(self, N, H, W, Ctot):
+        key = (N, H, W, bf16.round8(Ctot))
+        lst = self.free.get(key)
+        if lst:
+            return lst.pop()
+        self.total_bytes += 2 * N * H * W * key[3]
+        return bf16.new_buf(N, H, W, Ctot, self.device)
+
+
+def _run_chain_b(plan, pool, name, blocks, src, device, final_dst=None):
+    """engine.run_chain on the bf16-storage path: src / final_dst are bf16.ActB slices"""
+    x, owned = src, None
+    for j, blk in enumerate(blocks):
+        f = _FoldedConvB(blk, device)
+        ho, wo = f.layer.out_hw(x.H, x.W)
+        if j == len(blocks) - 1 and final_dst is not None:
+            dst, new_owned = final_dst, None
+        else:
+            buf = pool.get(x.N, ho, wo, f.layer.cout)
+            dst, new_owned = bf16.ActB(buf, 0, f.layer.cout), buf
+        plan.add_convb("%s.%d" % (name, j), f.layer, x, dst, x if f.residual else None, f.scale, f.shift)
+        plan.keep.append(f)
+        if owned is not None:
+            pool.put(owned)
+        owned, x = new_owned, dst
+    return x, owned
+
+
+class _GeneratorGraphB(_GeneratorGraph):
+    """The generator's bf16-STORAGE inference plan for one (batch, height, width, device): the same concat-buffer layout (8-channel
+    granules), face / audio two-stream split, optional HIP-graph replay and three sub-plans as _GeneratorGraph, over bf16 NHWC
+    buffers and bf16.ConvB launches (w2l_plan_add_convb).  The output block runs with its 1x1 head fused
+    (w2l_plan_add_convb_head): fp32 epilogue, uint8 frames in `frames`, the fp32 prediction in `out`."""
+
+    def __init__(self, model, N, H, W, device):
+        self.lib = load()
+        self.N, self.H, self.W = N, H, W
+        pool = _BufPoolB(device)
+        pool_audio = _BufPoolB(device)
+        plan = engine.Plan()
+        enc = model.face_encoder_blocks
+        dec = model.face_decoder_blocks
+        self.x_in = bf16.new_buf(N, H, W, 8, device)          # 6 image channels + 2 zero pad
+        self.mel_in = bf16.new_buf(N, 80, 16, 8, device)      # 1 mel channel + 7 zero pad
+        enc_hw, h, w = [], H, W
+        for blk in enc:
+            for b in blk:
+                h, w = _out_hw(b, h, w)
+            enc_hw.append((h, w, blk[-1].conv_block[0].out_channels))
+        nb = len(dec)
+        cats = []
+        for i, blk in enumerate(dec):
+            eh, ew, ec = enc_hw[nb - 1 - i]
+            dc = blk[-1].conv_block[0].out_channels
+            cats.append((bf16.new_buf(N, eh, ew, dc + ec, device), dc, ec))
+        x = bf16.ActB(self.x_in, 0, 6)
+        for i, blk in enumerate(enc):
+            buf, dc, ec = cats[nb - 1 - i]
+            x, _ = _run_chain_b(plan, pool, "face_encoder_blocks.%d" % i, list(blk), x, device, bf16.ActB(buf, dc, ec))
+        self.n_face = len(plan.records)
+        a, _ = _run_chain_b(plan, pool_audio, "audio_encoder", list(model.audio_encoder), bf16.ActB(self.mel_in, 0, 1), device)
+        self.n_audio = len(plan.records) - self.n_face
+        if (a.H, a.W) != (1, 1):
+            raise RuntimeError("audio encoder must reduce the mel window to 1x1, got %dx%d" % (a.H, a.W))
+        x = a
+        for i, blk in enumerate(dec):
+            buf, dc, ec = cats[i]
+            x, _ = _run_chain_b(plan, pool, "face_decoder_blocks.%d" % i, list(blk), x, device, bf16.ActB(buf, 0, dc))
+            x = bf16.ActB(buf, 0, dc + ec)
+        if (x.H, x.W) != (H, W):
+            raise RuntimeError("generator output is %dx%d for a %dx%d input" % (x.H, x.W, H, W))
+        head = _FoldedConvB(model.output_block[0], device)
+        head.layer.attach_head(head.weight, model.output_block[1], ACT_SIGMOID)
+        self.frames = torch.empty((N, H, W, 3), dtype=torch.uint8, device=device)
+        self.out = engine.Act(engine.new_buf(N, H, W, 4, device, zero=True), 0, 3)
+        plan.add_convb_head("output_block.0", head.layer, x, self.frames, self.out, head.scale, head.shift)
+        plan.keep.append(head)
+        plan.tuned = True          # launch configurations come from the shapes: nothing to autotune
+        self.plan = plan
+        self.scratch_bytes = pool.total_bytes + pool_audio.total_bytes
+        self.parts = None
+        self.hip_graph = None
+        self.side = torch.cuda.Stream(device=device) if device.type == "cuda" and engine.TWO_STREAM_ENCODERS else None
+
+    def load_nchw(self, audio, face):
+        s = current_stream()
+        check(self.lib.w2l_nchw_to_nhwc_bf16(s, self.N, 6, self.H, self.W, ptr(face), ptr(self.x_in), 8, 8), "nchw_to_nhwc_bf16")
+        check(self.lib.w2l_nchw_to_nhwc_bf16(s, self.N, 1, 80, 16, ptr(audio), ptr(self.mel_in), 8, 8), "nchw_to_nhwc_bf16")
+
+
+def _out_hw(blk, H, W):
+    """output size of a block's conv (the library's rule, w2l_conv_out_hw)"""
+    import ctypes as C
+    conv = blk.conv_block[0]
+    kh, kw = engine._pair(conv.kernel_size)
+    sh, sw = engine._pair(conv.stride)
+    ph, pw = engine._pair(conv.padding)
+    oph, opw = engine._pair(conv.output_padding) if blk._transposed else (0, 0)
+    g = ConvGeom(int(blk._transposed), conv.in_channels, conv.out_channels, kh, kw, sh, sw, ph, pw, oph, opw, blk._act)
+    ho, wo = C.c_int(), C.c_int()
+    check(load().w2l_conv_out_hw(C.byref(g), H, W, C.byref(ho), C.byref(wo)), "conv_out_hw")
+    return ho.value, wo.value
+
+
 class Wav2Lip(nn.Module):
     MAX_PLAN_BATCH = 512      # frames per static plan: larger inference batches are chunked (see forward)
 
@@ -224,20 +374,26 @@ class Wav2Lip(nn.Module):
         self._graphs = {}
         object.__setattr__(self, "_train_graphs", autograd.GraphCache(autograd.build_generator))
 
-    def graph(self, N, H=96, W=96, device=None, lane=0):
+    def graph(self, N, H=96, W=96, device=None, lane=0, precision="f32"):
         """the static launch plan for batch N (built on first use, rebuilt if the weights changed); `lane` selects one of
-        several independent buffer sets for batches in flight on different streams (inference.PipelinedRunner)"""
+        several independent buffer sets for batches in flight on different streams (inference.PipelinedRunner); `precision`
+        "f32" (default, the parity path) or "bf16" (the opt-in bf16-storage plan, _GeneratorGraphB)"""
+        check_precision(precision)
         device = device or next(self.parameters()).device
         ver = engine.param_version(self)
-        key = (N, H, W, str(device), lane)
+        key = (N, H, W, str(device), lane, precision)
         g = self._graphs.get(key)
         if g is None or g[0] != ver:
             if any(v[0] != ver for v in self._graphs.values()):
                 self._graphs.clear()
+            if precision == "bf16":
+                g = (ver, _GeneratorGraphB(self, N, H, W, torch.device(device)))
+                self._graphs[key] = g
+                return g[1]
             g = (ver, _GeneratorGraph(self, N, H, W, torch.device(device)))
             if (H, W) == (96, 96):    # batch sizes the launch table does not hold: committed per-plan configurations (engine.py)
                 engine.apply_plan_configs(g[1].plan, "generator_96", N)
-            twin = next((v[1] for k, v in self._graphs.items() if k[:4] == key[:4] and v[1].plan.tuned), None)
+            twin = next((v[1] for k, v in self._graphs.items() if k[:4] == key[:4] and k[5] == precision and v[1].plan.tuned), None)
             if twin is not None:      # another lane of the same geometry is already tuned: same launches, same configurations
                 for i, (_, t_, k_) in enumerate(twin.plan.configs()):
                     g[1].plan.set_config(i, t_, k_)
