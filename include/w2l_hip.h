@@ -195,6 +195,31 @@ int w2l_s3fd_decode(void* stream, int B, int FH, int FW, int stride, const float
 int w2l_s3fd_nms(void* stream, int B, int P, const float* table, float gate, float thresh, int* keep, int* counts,
                  void* scratch, long long scratch_bytes);
 
+/* The opt-in bf16-storage detector (face_detection/s3fd.py, precision="bf16"): the backbone convolutions are w2l_convb layers
+ * (scale 1, shift = bias, ReLU); these are the ops between them and the fused detection head.  Tensors are NHWC bf16 with channel
+ * strides that are multiples of 8, 16-byte aligned; no buffer may reach 2 GiB (the convb rule: split the batch). */
+/* bgr u8 [npix][3] -> y bf16 [npix][y_cs]: the values of w2l_s3fd_pack (api.py:62 + detect.py:57, integers with |v| <= 152, so
+ * exact), channels 3 .. y_cs-1 zero */
+int w2l_s3fd_pack_bf16(void* stream, long long npix, const uint8_t* bgr, void* y, int y_cs);
+/* F.max_pool2d(x, 2, 2) on bf16 NHWC (net_s3fd.py:75-97, floor semantics): bit-equal to torch on the same tensor; C %% 8 == 0 */
+int w2l_maxpool2x2_bf16(void* stream, int N, int H, int W, int C, const void* x, int x_cs, void* y, int y_cs);
+/* L2Norm (net_s3fd.py:6-19) on bf16 rows: sum of squares and x / (sqrt(.) + 1e-10) * weight[c] in fp32 (weight fp32 [C]),
+ * one RNE rounding on the store; C %% 8 == 0 */
+int w2l_l2norm_scale_bf16(void* stream, long long rows, int C, const void* x, int x_cs, const float* weight, void* y, int y_cs);
+/* One detection level fused (net_s3fd.py:99-126 + detect.py:66-84): the conf (ncls = 4 or 2) and loc (4) 3x3 convolutions of
+ * bf16 features x [B,FH,FW,x_cs] as ONE contraction (bf16 MFMA, fp32 accumulation, + fp32 bias), decoded from the accumulators
+ * with w2l_s3fd_decode's operations into table fp32 [B][FH*FW][5] = (x1, y1, x2, y2, score).  The handle owns the weights rounded
+ * to bf16 once: conf_w [ncls][cin][3][3], loc_w [4][cin][3][3] fp32 device tensors, biases fp32 [ncls] / [4] or NULL (zero);
+ * cin %% 32 == 0.  update re-packs them (asynchronous on `stream`). */
+typedef struct w2l_s3fd_headb w2l_s3fd_headb_t;
+int w2l_s3fd_headb_create(int cin, int ncls, const float* conf_w, const float* conf_b, const float* loc_w, const float* loc_b,
+                          void* stream, w2l_s3fd_headb_t** out);
+int w2l_s3fd_headb_update(w2l_s3fd_headb_t* h, const float* conf_w, const float* conf_b, const float* loc_w, const float* loc_b,
+                          void* stream);
+int w2l_s3fd_headb_destroy(w2l_s3fd_headb_t* h);
+int w2l_s3fd_headb_decode(const w2l_s3fd_headb_t* h, void* stream, int B, int FH, int FW, int stride, const void* x, int x_cs,
+                          float* table);
+
 /* ---------------------------------------------------------------- audio */
 
 /* A mel context owns the device copies of the constant tables: the Slaney mel basis fp32 [80][401] and the

@@ -1,5 +1,6 @@
 """`FaceAlignment` (face_detection/api.py:41-77) over the HIP S3FD detector: `get_detections_for_batch(images)` takes the
-reference's numpy uint8 BGR batch [B,H,W,3] and returns one (x1, y1, x2, y2) int tuple or None per image."""
+reference's numpy uint8 BGR batch [B,H,W,3] and returns one (x1, y1, x2, y2) int tuple or None per image.  `precision="bf16"`
+(opt-in) runs the detector network on its bf16-storage graph; the gate, NMS and thresholds are the same."""
 import os
 from enum import Enum
 
@@ -27,7 +28,9 @@ DEFAULT_WEIGHTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "s3fd
 
 class FaceAlignment:
     def __init__(self, landmarks_type=LandmarksType._2D, network_size=NetworkSize.LARGE, device="cuda", flip_input=False,
-                 face_detector="sfd", verbose=False, path_to_detector=None, state_dict=None):
+                 face_detector="sfd", verbose=False, path_to_detector=None, state_dict=None, precision="f32"):
+        from ..models.wav2lip import check_precision
+        self.precision = check_precision(precision)
         if face_detector != "sfd":
             raise NotImplementedError("only the 'sfd' detector of the reference is mirrored")
         if not torch.cuda.is_available() or "cuda" not in str(device):
@@ -50,7 +53,7 @@ class FaceAlignment:
         if isinstance(images_bgr, np.ndarray):
             images_bgr = torch.from_numpy(np.ascontiguousarray(images_bgr)).to(self.device)
         with torch.no_grad():
-            levels = self.face_detector.dense_boxes(images_bgr)
+            levels = self.face_detector.dense_boxes(images_bgr, precision=self.precision)
             table = torch.cat(levels, dim=1).contiguous()       # [B, sum FH*FW, 5]
             keep, counts = nms_batch(table, 0.05, 0.3)          # gate + NMS on the device: only the survivors cross PCIe
             counts_h = counts.cpu().tolist()

@@ -2,15 +2,19 @@
 fused HIP launches: every convolution is a `w2l_conv` layer (bias + ReLU folded into the launch; 3x3 / stride 1 layers go
 through the Winograd kernel), max-pools, L2Norm and the box decode are the glue kernels of csrc/detect.hip.
 Activations are NHWC fp32; the detection heads write (conf, loc) maps that `w2l_s3fd_decode` turns into dense
-(x1, y1, x2, y2, score) tables, one per pyramid level."""
+(x1, y1, x2, y2, score) tables, one per pyramid level.
+
+`dense_boxes(images, precision="bf16")` runs the opt-in bf16-storage graph (_GraphB) instead: bf16 NHWC activations, the
+convolutions as `w2l_convb` launches (bias as the fp32 shift, ReLU), the bf16 glue kernels of csrc/detect_bf16.hip and one fused
+head per level (`w2l_s3fd_headb_decode`: conf + loc contraction and decode, the logits never leave the chip)."""
 import ctypes as C
 
 import numpy as np
 import torch
 from torch import nn
 
-from .. import engine
-from .._lib import ACT_NONE, ACT_RELU, check, current_stream, load, ptr
+from .. import bf16, engine
+from .._lib import ACT_NONE, ACT_RELU, ConvGeom, check, current_stream, load, ptr
 from ..engine import Act
 
 # (name, cin, cout, kernel, stride, padding), net_s3fd.py:25-48
@@ -117,6 +121,179 @@ class _Graph:
         return self.dense
 
 
+BUF_LIMIT = 1 << 31      # bytes: the per-buffer rule of the bf16 kernels (32-bit byte offsets, W2L_REQUIRE in every launch)
+
+
+def _bf16_buffer_sizes(B, H, W):
+    """bytes of every buffer _GraphB would allocate for (B, H, W), computed from the shapes alone"""
+    sizes = [2 * B * H * W * 8]                                   # packed input, 8 channels
+    h, w, taps = H, W, {}
+    for item in BACKBONE:
+        if item == "pool":
+            if h < 2 or w < 2:
+                raise RuntimeError("image too small for the S3FD pyramid")
+            h, w = h // 2, w // 2
+            sizes.append(2 * B * h * w * c)
+        elif isinstance(item, str):
+            taps[item[4:]] = (h, w, c)
+        else:
+            _, _, c, k, st, p = item
+            h, w = (h + 2 * p - k) // st + 1, (w + 2 * p - k) // st + 1
+            if h < 1 or w < 1:
+                raise RuntimeError("image too small for the S3FD pyramid")
+            sizes.append(2 * B * h * w * bf16.round8(c))
+    for feat, norm, _ in HEADS:
+        fh, fw, c = taps[feat]
+        if norm is not None:
+            sizes.append(2 * B * fh * fw * c)
+        sizes.append(4 * B * fh * fw * 5)                         # the level's dense table (fp32)
+    return sizes
+
+
+class _ConvBiasB:
+    """one plain convolution (bias + activation, no BatchNorm) as a bf16-storage layer: the bf16.ConvB handle and the bias as the
+    fp32 shift with scale 1 (w2l_bn_fold without BatchNorm), applied to the fp32 accumulators - the counterpart of
+    models.wav2lip._FoldedConvB"""
+
+    def __init__(self, conv, act, device):
+        kh, kw = engine._pair(conv.kernel_size)
+        sh, sw = engine._pair(conv.stride)
+        ph, pw = engine._pair(conv.padding)
+        self.geom = ConvGeom(0, conv.in_channels, conv.out_channels, kh, kw, sh, sw, ph, pw, 0, 0, act)
+        self.layer = bf16.ConvB(self.geom, conv.weight)
+        cp = (conv.out_channels + 31) // 32 * 32
+        self.scale = torch.zeros(cp, device=device)
+        self.shift = torch.zeros(cp, device=device)
+        bias = conv.bias.detach().float().contiguous() if conv.bias is not None else None
+        check(load().w2l_bn_fold(current_stream(), conv.out_channels, ptr(bias), None, None, None, None, 0.0, ptr(self.scale),
+                                 ptr(self.shift)), "bn_fold")
+        self._keep = bias
+
+
+class _HeadB:
+    """one pyramid level's conf + loc convolutions and box decode as ONE launch (w2l_s3fd_headb_*): weights rounded to bf16 once"""
+
+    def __init__(self, conf, loc, ncls):
+        self._lib = load()
+        self.cin, self.ncls = conf.in_channels, ncls
+        t = [conf.weight, conf.bias, loc.weight, loc.bias]
+        self._keep = [p.detach().float().contiguous() if p is not None else None for p in t]
+        h = C.c_void_p()
+        check(self._lib.w2l_s3fd_headb_create(self.cin, ncls, *[ptr(p) for p in self._keep], current_stream(), C.byref(h)),
+              "s3fd_headb_create")
+        self.handle = h
+
+    def decode(self, x, stride, out):
+        """x: bf16.ActB features [B, FH, FW, >= cin]; out: float32 [B, FH*FW, 5]"""
+        check(self._lib.w2l_s3fd_headb_decode(self.handle, current_stream(), x.N, x.H, x.W, stride, x.ptr, x.cs, ptr(out)),
+              "s3fd_headb_decode")
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                self._lib.w2l_s3fd_headb_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+class _GraphB:
+    """the bf16-storage detector for one (batch, height, width): bf16 NHWC buffers, the backbone as convb plans (bias as shift,
+    ReLU), bf16 max-pools and L2Norms, one fused head per level writing the dense tables directly"""
+
+    def __init__(self, model, B, H, W, device):
+        big = max(_bf16_buffer_sizes(B, H, W))
+        if big >= BUF_LIMIT:
+            # checked before anything is allocated: inference._detect_rects halves the batch on this error, as for fp32
+            raise RuntimeError("S3FD bf16: a %d x %d x %d batch needs a %d-byte buffer, over the kernels' 2 GiB limit: split the "
+                               "batch" % (B, H, W, big))
+        self.lib = load()
+        self.B, self.H, self.W = B, H, W
+        self.x_in = bf16.new_buf(B, H, W, 8, device)
+        self.ops = []          # ("convs", Plan) | ("pool", src, dst) | ("l2norm", src, weight, dst) | ("head", _HeadB, src, stride, out)
+        self.plans = []
+        plan = None
+
+        def flush():
+            nonlocal plan
+            if plan is not None:
+                plan.tuned = True          # launch configurations come from the shapes: nothing to autotune
+                self.ops.append(("convs", plan))
+                self.plans.append(plan)
+                plan = None
+
+        x = bf16.ActB(self.x_in, 0, 3)
+        taps = {}
+        for item in BACKBONE:
+            if item == "pool":
+                flush()
+                dst = bf16.ActB(bf16.new_buf(B, x.H // 2, x.W // 2, x.C, device), 0, x.C)
+                self.ops.append(("pool", x, dst))
+                x = dst
+            elif isinstance(item, str):
+                taps[item[4:]] = x
+            else:
+                f = _ConvBiasB(getattr(model, item[0]), ACT_RELU, device)
+                ho, wo = f.layer.out_hw(x.H, x.W)
+                dst = bf16.ActB(bf16.new_buf(B, ho, wo, f.layer.cout, device), 0, f.layer.cout)
+                if plan is None:
+                    plan = engine.Plan()
+                plan.add_convb(item[0], f.layer, x, dst, None, f.scale, f.shift)
+                plan.keep.append(f)
+                x = dst
+        flush()
+        self.dense = []
+        for i, (feat, norm, ncls) in enumerate(HEADS):
+            src = taps[feat]
+            prefix = feat
+            if norm is not None:
+                nb = bf16.ActB(bf16.new_buf(B, src.H, src.W, src.C, device), 0, src.C)
+                self.ops.append(("l2norm", src, getattr(model, norm).weight, nb))
+                src = nb
+                prefix = norm
+            head = _HeadB(getattr(model, prefix + "_mbox_conf"), getattr(model, prefix + "_mbox_loc"), ncls)
+            out = torch.empty((B, src.H * src.W, 5), device=device, dtype=torch.float32)
+            self.ops.append(("head", head, src, 2 ** (i + 2), out))
+            self.dense.append(out)
+
+    def run(self):
+        s = current_stream()
+        lib = self.lib
+        for op in self.ops:
+            if op[0] == "convs":
+                op[1].run()
+            elif op[0] == "pool":
+                _, a, d = op
+                check(lib.w2l_maxpool2x2_bf16(s, a.N, a.H, a.W, a.C, a.ptr, a.cs, d.ptr, d.cs), "maxpool2x2_bf16")
+            elif op[0] == "l2norm":
+                _, a, w, d = op
+                check(lib.w2l_l2norm_scale_bf16(s, a.N * a.H * a.W, a.C, a.ptr, a.cs, ptr(w.detach()), d.ptr, d.cs),
+                      "l2norm_scale_bf16")
+            else:
+                _, head, a, stride, out = op
+                head.decode(a, stride, out)
+        return self.dense
+
+    def resolved(self):
+        """[(layer, kernel family)] of every launch in order: the convb plans' Plan.resolved() families and the glue launches
+        (pool1..pool5, the L2Norm modules, the heads named by their feature)"""
+        fams, npool, heads = [], 0, iter(HEADS)
+        for op in self.ops:
+            if op[0] == "convs":
+                fams += [(name, fam) for name, _, fam, _ in op[1].resolved()]
+            elif op[0] == "pool":
+                npool += 1
+                fams.append(("pool%d" % npool, "maxpool2x2_bf16"))
+            elif op[0] == "l2norm":
+                fams.append(("l2norm", "l2norm_scale_bf16"))
+            else:
+                feat, norm, _ = next(heads)
+                fams.append(("%s_mbox" % (norm or feat), "s3fd_headb"))
+                if norm is not None:
+                    fams[-2] = (norm, "l2norm_scale_bf16")
+        return fams
+
+
 class s3fd(nn.Module):
     def __init__(self):
         super().__init__()
@@ -142,14 +319,14 @@ class s3fd(nn.Module):
             self._layers[key] = engine.FusedConv(getattr(self, name), None, act)
         return self._layers[key]
 
-    def _graph(self, B, H, W, device):
+    def _graph(self, B, H, W, device, precision="f32"):
         ver = engine.param_version(self)
         if ver != self._version:
             self._layers, self._graphs, self._version = {}, {}, ver
-        key = (B, H, W, str(device))
+        key = (B, H, W, str(device), precision)
         g = self._graphs.get(key)
         if g is None:
-            g = _Graph(self, B, H, W, torch.device(device))
+            g = (_GraphB if precision == "bf16" else _Graph)(self, B, H, W, torch.device(device))
             self._graphs = {key: g}        # one live geometry: VGG activations of a video frame batch are large
         return g
 
@@ -174,15 +351,21 @@ class s3fd(nn.Module):
         outs[0] = torch.cat([torch.max(torch.max(chunk[0], chunk[1]), chunk[2]), chunk[3]], dim=1)
         return outs
 
-    def dense_boxes(self, images_bgr_u8):
+    def dense_boxes(self, images_bgr_u8, precision="f32"):
         """images: torch uint8 [B,H,W,3] BGR on the device -> per level torch float32 [B, FH*FW, 5] (x1,y1,x2,y2,score):
-        api.py:62 (BGR->RGB) + detect.py:57-84 for every position"""
+        api.py:62 (BGR->RGB) + detect.py:57-84 for every position.  `precision`: "f32" (default) or "bf16" (the opt-in
+        bf16-storage graph; a batch whose buffers would reach 2 GiB raises RuntimeError before anything is allocated)"""
+        from ..models.wav2lip import check_precision
+        check_precision(precision)
         if images_bgr_u8.dtype != torch.uint8 or images_bgr_u8.dim() != 4 or images_bgr_u8.shape[3] != 3:
             raise RuntimeError("dense_boxes: images must be uint8 [B,H,W,3]")
         engine.require_cuda(images_bgr_u8, "images")
         img = images_bgr_u8.contiguous()
         B, H, W = img.shape[:3]
-        g = self._graph(B, H, W, img.device)
+        g = self._graph(B, H, W, img.device, precision)
+        if precision == "bf16":
+            check(load().w2l_s3fd_pack_bf16(current_stream(), B * H * W, ptr(img), ptr(g.x_in), 8), "s3fd_pack_bf16")
+            return g.run()
         check(load().w2l_s3fd_pack(current_stream(), B * H * W, ptr(img), ptr(g.x_in), 4), "s3fd_pack")
         g.run()
         return g.decode()

@@ -16,6 +16,7 @@ of wav2lip_amd/container.py (uncompressed AVI with the PCM16 audio interleaved).
 (`cv2.VideoCapture` of mp4 input), audio extraction from non-WAV containers (the reference's first ffmpeg call).
 """
 import argparse
+import copy
 import os
 
 import numpy as np
@@ -63,16 +64,20 @@ def build_parser():
 
 
 def build_cli_parser():
-    """the command line `main()` parses: the reference's flags (`build_parser`, whose surface stays the reference's) plus one
-    documented addition that is not among them, `--precision {fp32,bf16}` (default fp32): the generator's arithmetic"""
+    """the command line `main()` parses: the reference's flags (`build_parser`, whose surface stays the reference's) plus two
+    documented additions that are not among them, each fp32 by default and independent of the other:
+    `--precision {fp32,bf16}`, the generator's arithmetic, and `--face_det_precision {fp32,bf16}`, the S3FD detector's"""
     p = build_parser()
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
                    help='Generator arithmetic: fp32 (default, matches the reference) or bf16 storage (faster; frames differ by '
                         'about one uint8 level in a few percent of the bytes)')
+    p.add_argument('--face_det_precision', default='fp32', choices=['fp32', 'bf16'],
+                   help='Face detector arithmetic: fp32 (default, matches the reference) or bf16 storage (faster; boxes move by '
+                        'about what bf16 rounding alone moves them)')
     return p
 
 
-CLI_PRECISION = {"fp32": "f32", "bf16": "bf16"}     # --precision value -> the `precision=` of the runners / lipsync
+CLI_PRECISION = {"fp32": "f32", "bf16": "bf16"}     # --precision / --face_det_precision value -> the `precision=` of the API
 
 
 parser = build_parser()
@@ -87,7 +92,7 @@ def is_image_path(path):
 
 
 def parse_args(argv=None):
-    """inference.py:53-57: parse (the reference's flags + `--precision`), then `img_size = 96` and `static = True` for an image
+    """inference.py:53-57: parse (the reference's flags + `--precision` and `--face_det_precision`), then `img_size = 96` and `static = True` for an image
     input"""
     a = cli_parser.parse_args(argv)
     a.img_size = img_size
@@ -486,15 +491,26 @@ def _detect_rects(images, detector, batch_size, ranks=None):
             print('Recovering from OOM error; New batch size: {}'.format(batch_size))
 
 
-def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None, ranks=None):
+def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None, ranks=None, precision=None):
     """inference.py:68-104: S3FD boxes per frame (HIP detector), padding, temporal smoothing; returns
     [[face crop, (y1, y2, x1, x2)], ...].  Called as the reference calls it - `face_detect(images)` - pads / nosmooth /
     face_det_batch_size come from the module-level `args` and the detector is built as inference.py:69-70 does
     (`face_detection.FaceAlignment(LandmarksType._2D, flip_input=False, device=device)`, weights `face_detection/s3fd.pth`);
-    a ready `wav2lip_amd.face_detection.FaceAlignment` may be passed instead."""
+    a ready `wav2lip_amd.face_detection.FaceAlignment` may be passed instead.  `precision` ("f32" or "bf16") selects the
+    detector's arithmetic; None means: a passed detector keeps its own, a built one takes the module-level
+    `args.face_det_precision` (fp32 when absent)."""
+    from .models.wav2lip import check_precision
+    if precision is not None:
+        check_precision(precision)
     if detector is None:
         from . import face_detection
-        detector = face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False, device=device)
+        if precision is None:
+            precision = check_precision(CLI_PRECISION[getattr(args, "face_det_precision", "fp32")])
+        detector = face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False, device=device,
+                                                **_precision_kw(precision))
+    elif precision is not None and precision != getattr(detector, "precision", "f32"):
+        detector = copy.copy(detector)          # same network and graph cache, the other arithmetic
+        detector.precision = precision
     pads = args.pads if pads is None else pads
     nosmooth = args.nosmooth if nosmooth is None else nosmooth
     batch_size = args.face_det_batch_size if batch_size is None else batch_size
@@ -570,8 +586,9 @@ def main(argv=None, keep_frames=True, backend="nccl"):
     """inference.py:181-277 on the HIP path.  Same flags, same steps, same messages; differences, all on the file-format
     side: video input is the uncompressed AVI of wav2lip_amd/container.py (no codecs here), `--audio` must be a WAV (the
     reference shells out to ffmpeg for anything else), and the result - the reference's `temp/result.avi` + ffmpeg mux - is
-    written as ONE AVI (BGR video + the driving audio as PCM16) at `--outfile`.  One flag the reference does not have:
-    `--precision {fp32,bf16}` (default fp32) selects the generator's arithmetic.
+    written as ONE AVI (BGR video + the driving audio as PCM16) at `--outfile`.  Two flags the reference does not have, both
+    fp32 by default and independent: `--precision {fp32,bf16}` selects the generator's arithmetic, `--face_det_precision
+    {fp32,bf16}` the S3FD face detector's (every rank of a sharded run detects its shard with it).
 
     Like the reference's loop (inference.py:249-274) this one STREAMS: every batch uploads only the frames it pastes into
     (deduplicated, `frame_idx` remapped) and its output frames go to the AVI writer as soon as they are back, so device and host
@@ -604,7 +621,8 @@ def main(argv=None, keep_frames=True, backend="nccl"):
         say("Length of mel chunks: {}".format(len(starts)))
         full_frames = full_frames[:len(starts)]
         if args.box[0] == -1:
-            det = face_detect(full_frames if not args.static else [full_frames[0]], ranks=ranks)
+            det = face_detect(full_frames if not args.static else [full_frames[0]], ranks=ranks,
+                              precision=CLI_PRECISION[args.face_det_precision])
             coords = [c for _, c in det]
         else:
             say('Using the specified bounding box instead of face detection...')
