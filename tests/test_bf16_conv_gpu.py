@@ -56,7 +56,7 @@ def _ref(x, w, transposed, stride, pad, outpad, scale, shift, res, act):
 
 
 def _run(cuda, transposed, cin, cout, k, stride, pad, outpad, N, H, W, act=ACT_RELU, with_res=False, affine=True, tile=None,
-         ksplit=0, seed=0, wscale=None):
+         ksplit=0, seed=0, wscale=None, family=None):
     torch.manual_seed(seed)
     kh, kw = _pair(k)
     s, p, op = _pair(stride), _pair(pad), _pair(outpad)
@@ -89,6 +89,8 @@ def _run(cuda, transposed, cin, cout, k, stride, pad, outpad, N, H, W, act=ACT_R
         bad, err.numel(), float(err.max()), S, float((err / tol).max()))
     if bf16.round8(cout) > cout:
         assert bool((yb[..., cout:] == 0).all()), "pad channels must be written as zero"
+    if family is not None:          # the kernel the case is about is the one that ran (w2l_convb_resolve: the launcher's rules)
+        assert layer.resolve(N, H, W, res=with_res)[0] == family, (layer.resolve(N, H, W, res=with_res), family)
     return float((err / (ref.abs() / 256 + 1e-30)).median())
 
 
@@ -577,14 +579,14 @@ def test_thin_1x1_row_kernels(cin, cout, npix, act, cuda):
 @pytest.mark.parametrize("transposed", [False, True])
 @pytest.mark.parametrize("N,H,W,act,with_res", [(2048, 16, 16, ACT_RELU, False), (342, 48, 32, ACT_RELU, True), (57, 96, 96, ACT_NONE, True),
                                                 (1025, 32, 16, ACT_LEAKY, False), (2051, 16, 16, ACT_RELU, True), (228, 46, 47, ACT_RELU, True),
-                                                (700, 15, 30, ACT_NONE, True)])
+                                                (1100, 15, 30, ACT_NONE, True)])
 def test_lds_resident_box_kernel(transposed, N, H, W, act, with_res, cuda):
     """csrc/conv_box_bf16.hip (3x3, stride 1, 64 -> 64, extents divisible by 16: weights and the input box resident in LDS) through
     the same entry point and against the same float64 reference and tolerance as every other bf16 conv: forward geometry and the
     data-gradient (transposed) geometry, image borders (the box halo is zero-filled by out-of-range DMA), one tile and many tiles
     per workgroup, odd tile counts, ragged extents (SyncNet's 46x47, 15x30: the last tile row / column is masked), residual,
     activations.  Every shape is above the launcher's size rule (>= 2048 tiles, >= 85 % tile fill) - smaller ones run the implicit GEMM"""
-    _run(cuda, transposed, 64, 64, 3, 1, 1, 0, N, H, W, act=act, with_res=with_res, seed=N + H)
+    _run(cuda, transposed, 64, 64, 3, 1, 1, 0, N, H, W, act=act, with_res=with_res, seed=N + H, family="box64")
 
 
 @pytest.mark.parametrize("cin,cout,N,H,W,act", [(6, 16, 30, 96, 96, ACT_RELU), (15, 32, 60, 48, 96, ACT_RELU), (3, 32, 60, 48, 96, ACT_LEAKY),
@@ -594,7 +596,7 @@ def test_stem_7x7_kernel(cin, cout, N, H, W, act, cuda):
     generator, SyncNet and the discriminator; weights + the tile's 22x22 input box resident in LDS) through the same entry point and
     against the same float64 reference and tolerance as every other bf16 conv: both channel packings (one tap / two taps per MFMA
     K-step), image borders, ragged extents, pad couts, every activation.  Shapes sit above the launcher's size rule (>= 1024 tiles)"""
-    _run(cuda, False, cin, cout, 7, 1, 3, 0, N, H, W, act=act, with_res=False, seed=cin + N)
+    _run(cuda, False, cin, cout, 7, 1, 3, 0, N, H, W, act=act, with_res=False, seed=cin + N, family="stem1")
 
 
 @pytest.mark.parametrize("transposed,cin,cout,N,H,W,act,with_res", [
@@ -602,11 +604,12 @@ def test_stem_7x7_kernel(cin, cout, N, H, W, act, cuda):
     (True, 32, 80, 57, 96, 96, ACT_NONE, False),        # its data gradient: three cout tiles, 80 of 96 couts exist
     (False, 32, 32, 228, 48, 48, ACT_RELU, True),       # a 32 -> 32 residual block, two workgroups per CU
     (True, 32, 32, 228, 48, 48, ACT_NONE, True),        # its data gradient accumulating into the residual path
-    (False, 80, 24, 64, 46, 90, ACT_LEAKY, False)])     # ragged extents, pad couts
+    (False, 80, 24, 120, 46, 90, ACT_LEAKY, False)])    # ragged extents, pad couts (3x6 tiles a frame: >= 114 frames reach the rule)
 def test_small_channel_3x3_layers_on_the_resident_box_kernel(transposed, cin, cout, N, H, W, act, with_res, cuda):
     """the KS = 3 instantiations of csrc/conv_stem_bf16.hip (few channels on one side at full resolution: output block, its data
     gradient, the 32 -> 32 residual blocks) through the common entry point against the common float64 reference and tolerance"""
-    _run(cuda, transposed, cin, cout, 3, 1, 1, 0, N, H, W, act=act, with_res=with_res, seed=cin + cout)
+    fam = {80: "stem2", 32: "stem3"}[cin] if not transposed else {32: "stem3", 80: "stem4"}[cout]
+    _run(cuda, transposed, cin, cout, 3, 1, 1, 0, N, H, W, act=act, with_res=with_res, seed=cin + cout, family=fam)
 
 
 @pytest.mark.parametrize("cin,cout,k,N,H,W,with_res", [
@@ -618,18 +621,24 @@ def test_resident_box_kernels_decline_what_they_do_not_implement(cin, cout, k, N
     """shapes ABOVE the size rules of conv_box_bf16.hip / conv_stem_bf16.hip that those kernels cannot serve (a narrower cout
     than the 64 channels the box epilogue writes; a residual on the stem families) must give the common reference's result -
     i.e. run on the implicit GEMM - and leave the buffer's pad channels and neighbouring pixels alone"""
-    _run(cuda, False, cin, cout, k, 1, k // 2, 0, N, H, W, act=ACT_RELU, with_res=with_res, seed=cin + cout + k)
+    _run(cuda, False, cin, cout, k, 1, k // 2, 0, N, H, W, act=ACT_RELU, with_res=with_res, seed=cin + cout + k, family="igemm")
 
 
 # ---------------------------------------------------------------- conv_tp2b_bf16.hip: all four phases of a stride-2 transposed layer per workgroup
 TP2B_CASES = {
-    # name: (cin, cout, N, H, W, act, with_res, affine) - every one launches >= 512 workgroups, so the fused-phase kernel is chosen
+    # name: (cin, cout, N, H, W, act, with_res, affine)
     "dec6_160_64": (160, 64, 20, 24, 24, ACT_NONE, False, True),         # models/wav2lip.py:76 at a smaller batch / extent
     "dec5_320_128": (320, 128, 12, 16, 24, ACT_RELU, False, True),       # two cout tiles
     "ragged_96_72": (96, 72, 9, 13, 11, ACT_LEAKY, True, True),          # ragged tiles, cout not a multiple of 32, residual
-    "thin_32_16": (32, 16, 40, 24, 24, ACT_NONE, True, False),           # the 32-cout tile half empty: face_encoder_blocks.1.0's data gradient
-    "thin_64_32": (64, 32, 24, 16, 32, ACT_NONE, False, False),
+    "thin_32_16": (32, 16, 120, 24, 24, ACT_NONE, True, False),          # the 32-cout tile half empty: face_encoder_blocks.1.0's data gradient
+    "thin_64_32": (64, 32, 128, 16, 32, ACT_NONE, False, False),
+    "ragged_96_24": (96, 24, 260, 13, 11, ACT_LEAKY, True, True),        # ragged tiles, pad couts, residual on the fused-phase kernel
+    "dec_64_32": (64, 32, 120, 24, 24, ACT_RELU, False, True),
 }
+# The fused-phase kernel takes a layer with one 32-cout tile once the launch has >= 256 workgroups (2048 4x8 pixel groups); one
+# with 33..64 couts only past 400000 input pixels (the generator's 160 -> 64 layer from 174 frames on, covered by the whole-model
+# batch sweep in test_infer_bf16_gpu.py); wider ones not at the default level.  These cases keep the four-phase implicit GEMM.
+TP2B_ON_IGEMM = {"dec6_160_64", "dec5_320_128", "ragged_96_72"}
 
 
 @pytest.mark.parametrize("case", sorted(TP2B_CASES))
@@ -638,7 +647,8 @@ def test_fused_phase_transposed_kernel_forward(case, cuda):
     float64 transposed convolution of the same bf16 operands (tolerance of this file), and against the four-phase implicit GEMM the
     layer ran on before (selected by a tile override): the same math in another summation order - equal within one bf16 step."""
     cin, cout, N, H, W, act, with_res, affine = TP2B_CASES[case]
-    _run(cuda, True, cin, cout, 3, 2, 1, 1, N, H, W, act=act, with_res=with_res, affine=affine, seed=hash(case) % 1000)
+    _run(cuda, True, cin, cout, 3, 2, 1, 1, N, H, W, act=act, with_res=with_res, affine=affine, seed=hash(case) % 1000,
+         family="igemm" if case in TP2B_ON_IGEMM else "tp2b")
     # same inputs on both kernels
     torch.manual_seed(5)
     w = torch.randn(cin, cout, 3, 3) / np.sqrt(cin * 9)
@@ -658,7 +668,7 @@ def test_fused_phase_transposed_kernel_forward(case, cuda):
     assert float((d > 0).double().mean()) <= 0.05
 
 
-@pytest.mark.parametrize("case", ["dec6_160_64", "dec5_320_128", "ragged_96_72"])
+@pytest.mark.parametrize("case", ["dec6_160_64", "dec5_320_128", "ragged_96_72", "ragged_96_24", "dec_64_32"])
 def test_fused_phase_transposed_kernel_batch_statistics(case, cuda):
     """w2l_convb_forward_bn through conv_tp2b_bf16.hip: z as the plain launch writes it and mean / rstd / scale / shift / running
     statistics from the kernel's per-wave partials equal to the statistics of the STORED z (float64), as the implicit GEMM's route"""
@@ -668,6 +678,7 @@ def test_fused_phase_transposed_kernel_batch_statistics(case, cuda):
     x = torch.randn(N, cin, H, W)
     g = ConvGeom(1, cin, cout, 3, 3, 2, 2, 1, 1, 1, 1, ACT_NONE)
     layer = bf16.ConvB(g, w.to(cuda))
+    assert layer.resolve(N, H, W)[0] == ("igemm" if case in TP2B_ON_IGEMM else "tp2b")
     Cp = bf16.round8(cout)
     xb = _nhwc(x).to(cuda)
     z0 = torch.full((N, 2 * H, 2 * W, Cp), 3.0, dtype=torch.bfloat16, device=cuda)

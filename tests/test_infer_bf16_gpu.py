@@ -137,26 +137,143 @@ def _run_bf16(G, faces, mels, cuda, runner=None):
     return u8, r.last_pred_nchw().cpu()
 
 
-def test_baseline_cfg2_batch_against_the_oracle_within_the_yardstick(cuda, yardstick):
-    G, sd = _load(0, cuda)
+@pytest.fixture(scope="module")
+def cfg2_oracle():
+    """the 128 BASELINE cfg2 frames (face_crops_u8 / mel_windows, seed 5) and the CPU oracle's prediction for them under the seed-0
+    weights: (faces, mels, prediction [128,3,96,96])"""
+    sd = synth.synthetic_state_dict({k: tuple(v.shape) for k, v in amd_models.Wav2Lip().state_dict().items()}, seed=0)
     faces, mels = synth.face_crops_u8(128, seed=5), synth.mel_windows(128, seed=5)
-    u8, y = _run_bf16(G, faces, mels, cuda)
     img, mel = datagen_ref.to_model_inputs(*datagen_ref.datagen_batch(faces, mels))
     with torch.no_grad():
         ref = torch.cat([models_ref.wav2lip_forward(sd, torch.from_numpy(mel[lo:lo + 16]), torch.from_numpy(img[lo:lo + 16]))
                          for lo in range(0, 128, 16)])
-    d = (y - ref).abs()
-    linf, mean = float(d.max()), float(d.mean())
-    ref_u8 = _u8(ref.numpy())
+    return faces, mels, ref
+
+
+def _against_the_oracle(label, u8, y, ref, ref_u8, yardstick):
+    """the yardstick assertions: prediction `y` (or None) within twice the yardstick of `ref` (L-inf and mean), the uint8 frames
+    `u8` the truncation of `y` and at most one level further from the oracle's frames `ref_u8` than the yardstick allows"""
     du = np.abs(u8.astype(np.int32) - ref_u8.astype(np.int32))
-    assert np.array_equal(u8, _u8(y.numpy()))                      # the frames are the truncation of the fp32 prediction
-    msg = ("bf16 vs oracle, 128 frames: L-inf %.3e (yardstick %.3e), mean %.3e (yardstick %.3e), uint8: %.2f %% of bytes differ, "
-           "worst %d levels (yardstick %d)" % (linf, yardstick["linf"], mean, yardstick["mean"], 100.0 * float((du != 0).mean()),
-                                              int(du.max()), yardstick["u8"]))
+    msg = "bf16 vs oracle, %s: uint8: %.2f %% of bytes differ, worst %d levels (yardstick %d)" % (
+        label, 100.0 * float((du != 0).mean()), int(du.max()), yardstick["u8"])
+    if y is not None:
+        d = (y - ref).abs()
+        linf, mean = float(d.max()), float(d.mean())
+        msg += "; L-inf %.3e (yardstick %.3e), mean %.3e (yardstick %.3e)" % (linf, yardstick["linf"], mean, yardstick["mean"])
+        assert np.array_equal(u8, _u8(y.numpy())), msg               # the frames are the truncation of the fp32 prediction
     print(msg)
-    assert linf <= 2 * yardstick["linf"], msg
-    assert mean <= 2 * yardstick["mean"], msg
+    if y is not None:
+        assert linf <= 2 * yardstick["linf"], msg
+        assert mean <= 2 * yardstick["mean"], msg
     assert int(du.max()) <= yardstick["u8"] + 1, msg
+
+
+def test_baseline_cfg2_batch_against_the_oracle_within_the_yardstick(cuda, yardstick, cfg2_oracle):
+    G, _ = _load(0, cuda)
+    faces, mels, ref = cfg2_oracle
+    u8, y = _run_bf16(G, faces, mels, cuda)
+    _against_the_oracle("128 frames", u8, y, ref, _u8(ref.numpy()), yardstick)
+
+
+def _dispatch_map(G):
+    """{N: ((record, family, tile, ksplit), ...)} of the bf16 generator plan for N = 1..MAX_PLAN_BATCH (ConvB.resolve: the launcher's
+    own rules, nothing launched)"""
+    from wav2lip_amd.inference import Wav2LipRunner
+    g = Wav2LipRunner(G, batch_size=1, precision="bf16")._graph(1)
+    return {n: tuple(g.dispatch(n)) for n in range(1, G.MAX_PLAN_BATCH + 1)}
+
+
+def _chunks(n, cap):
+    return [min(cap, n - lo) for lo in range(0, n, cap)]
+
+
+def _pick_batch_sizes(dmap, fixed, cap):
+    """`fixed` plus a greedy cover of every (record, family) pair and every (record, tile, split-K) an igemm launch takes in `dmap`"""
+    def keys(n):
+        out = set()
+        for name, fam, tile, ks in dmap[n]:
+            out.add((name, fam))
+            if fam == "igemm":
+                out.add((name, fam, tile, ks))
+        return out
+    want = set().union(*(keys(n) for n in dmap))
+    sizes = set(fixed)
+    have = set().union(*(keys(c) for n in sizes for c in _chunks(n, cap)))
+    while want - have:
+        best = max(sorted(dmap), key=lambda n: len(keys(n) - have))      # ties: the smallest batch
+        sizes.add(best)
+        have |= keys(best)
+    return sorted(sizes), want
+
+
+def _boundaries(dmap):
+    """per record: [(first N, family, tile, ksplit)] at every N where its launch changes"""
+    out = {}
+    for n in sorted(dmap):
+        for name, fam, tile, ks in dmap[n]:
+            seq = out.setdefault(name, [])
+            if not seq or seq[-1][1:] != (fam, tile, ks):
+                seq.append((n, fam, tile, ks))
+    return out
+
+
+def test_bf16_batch_sizes_across_the_dispatch_map_against_the_oracle(cuda, yardstick, cfg2_oracle):
+    """The same layer runs a different kernel (stem / box64 / tp2b / igemm with its tile and split-K) at different batch sizes.
+    Batch sizes chosen from the dispatch map so that every (layer, family) and every (layer, igemm tile, split-K) the plans take
+    runs once, plus 1, 2, 128, 129, 512 and a chunked 600 (512 + 88): input j is pool frame j mod 128, so one oracle run serves
+    every size.  Each size is held to the yardstick; frames with identical inputs are bit-identical within a batch (folded
+    BatchNorm: no result depends on a frame's position in M - tile masking and the split-K workspace are what would break it),
+    and two sizes whose launches all resolve alike agree bit for bit on the frames they share."""
+    from wav2lip_amd.inference import Wav2LipRunner
+    G, _ = _load(0, cuda)
+    cap = G.MAX_PLAN_BATCH
+    dmap = _dispatch_map(G)
+    sizes, want = _pick_batch_sizes(dmap, (1, 2, 128, 129, 512, 600), cap)
+    for n0 in (15, 129):                   # and the largest batch that resolves every launch as n0 does: more M tiles, same kernels
+        sizes = sorted(set(sizes) | {n0, max(n for n in dmap if dmap[n] == dmap[n0])})
+    bounds = _boundaries(dmap)
+    for name, seq in bounds.items():
+        print("%-28s %s" % (name, "  ".join("N>=%d: %s%s" % (n, f, "" if f != "igemm" else " t%d k%d" % (t, k)) for n, f, t, k in seq)))
+    print("batch sizes: %s (%d (layer, family / tile, split-K) keys)" % (sizes, len(want)))
+    fams = {fam for m in dmap.values() for _, fam, _, _ in m}
+    assert {"igemm", "box64", "tp2b", "k3s_head"} <= fams and any(f.startswith("stem") for f in fams), fams
+    faces, mels, ref = cfg2_oracle
+    ref_u8 = _u8(ref.numpy())
+    sig_count = {}
+    for n in sizes:
+        if n <= cap:
+            sig_count[dmap[n]] = sig_count.get(dmap[n], 0) + 1
+    shared, compared = {}, 0
+    for n in sizes:
+        G._graphs.clear()                  # one resident plan at a time
+        idx = np.arange(n) % 128
+        r = Wav2LipRunner(G, batch_size=n, precision="bf16")
+        u8, y = _run_bf16(G, faces[idx], mels[idx], cuda, r)
+        del r
+        last = _chunks(n, cap)[-1]
+        lo = n - last                      # last_pred_nchw covers the last chunk
+        if lo:
+            _against_the_oracle("N=%d (first %d frames)" % (n, lo), u8[:lo], None, None, ref_u8[idx[:lo]], yardstick)
+        _against_the_oracle("N=%d%s" % (n, "" if not lo else " (last chunk of %d)" % last), u8[lo:], y, ref[idx[lo:]],
+                            ref_u8[idx[lo:]], yardstick)
+        pos = np.arange(n)
+        dup = pos[pos - 128 >= pos // cap * cap]     # frame j and frame j - 128 of the same chunk (plan) have identical inputs
+        assert np.array_equal(u8[dup], u8[dup - 128]), "N=%d: frames with identical inputs differ" % n
+        if lo == 0 and len(dup):
+            yb = _bits(y)
+            assert torch.equal(yb[dup], yb[dup - 128]), "N=%d: predictions with identical inputs differ" % n
+        if n <= cap and sig_count[dmap[n]] > 1:
+            prev = shared.get(dmap[n])
+            if prev is None:
+                shared[dmap[n]] = (n, _bits(y[:128]), u8[:128].copy())
+            else:
+                m = min(n, prev[0], 128)
+                assert torch.equal(_bits(y[:m]), prev[1][:m]) and np.array_equal(u8[:m], prev[2][:m]), \
+                    "N=%d and N=%d resolve alike but differ" % (prev[0], n)
+                compared += 1
+    G._graphs.clear()
+    print("%d batch sizes compared bit for bit with another size of the same dispatch" % compared)
+    assert compared >= 2
 
 
 def test_same_batch_twice_gives_identical_bytes(cuda):

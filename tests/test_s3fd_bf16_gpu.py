@@ -126,10 +126,15 @@ def test_every_backbone_geometry_on_convb_against_fp64(cuda, name, cin, cout, k,
 
 
 def test_conv1_2_at_480x640_large_m(cuda):
-    _convb_check(cuda, 64, 64, 3, 1, 1, N=1, H=480, W=640, seed=7)
+    _convb_check(cuda, 64, 64, 3, 1, 1, N=1, H=480, W=640, seed=7, family="igemm")       # 1200 tiles: under the box kernel's rule
 
 
-def _convb_check(cuda, cin, cout, k, st, p, N, H, W, seed):
+def test_conv1_2_at_480x640_on_the_resident_box_kernel(cuda):
+    """two frames: 2400 16x16 tiles, over the 2048-tile rule - conv1_2 of the benchmarked detector batches runs on box64"""
+    _convb_check(cuda, 64, 64, 3, 1, 1, N=2, H=480, W=640, seed=8, family="box64")
+
+
+def _convb_check(cuda, cin, cout, k, st, p, N, H, W, seed, family=None):
     from wav2lip_amd.face_detection.s3fd import _ConvBiasB
     g = torch.Generator().manual_seed(seed)
     conv = torch.nn.Conv2d(cin, cout, k, stride=st, padding=p)
@@ -150,6 +155,8 @@ def _convb_check(cuda, cin, cout, k, st, p, N, H, W, seed):
     tol = 2.0 ** -8 * ref.abs() + 1e-5 * float(ref.abs().max())
     bad = (got - ref).abs() > tol
     assert not bool(bad.any()), (int(bad.sum()), float((got - ref).abs().max()))
+    if family is not None:
+        assert f.layer.resolve(N, H, W)[0] == family
 
 
 # ---------------------------------------------------------------- whole detector against the oracle
@@ -158,14 +165,22 @@ def _frame_sets():
     return [synth.s3fd_frames(seed=k) for k in (1, 2, 3, 4)] + [synth.s3fd_frames(B=1, H=192, W=256)]
 
 
-@pytest.fixture(scope="module")
-def oracle_runs():
+def _geometry_sets():
+    """production-like and edge geometries: 480x640 (conv1_2 over the box kernel's 2048-tile rule at B = 2, as in the benchmarked
+    B = 16 batches), 250x333 (extents no power of two divides: odd pooled maps, ragged head boxes, fc6's padding of 3 on an odd
+    map) and 33x47, the smallest kind of frame the network takes (pool5 is 1x1; fc6's padding makes fc7 5x5, so no level is
+    narrower than 2)"""
+    return [synth.s3fd_frames(seed=6, B=2, H=480, W=640), synth.s3fd_frames(seed=7, B=3, H=250, W=333),
+            synth.s3fd_frames(seed=8, B=2, H=33, W=47)]
+
+
+def _oracle_runs(frame_sets):
     """per frame set: the clean fp64 oracle's dense tables and those of three bf16_storage_noise seeds"""
     torch.set_num_threads(16)
     sd64 = {k: v.double() for k, v in synth.s3fd_state_dict(0).items()}
     runs = []
     with torch.no_grad():
-        for img in _frame_sets():
+        for img in frame_sets:
             x = s3fd_ref.preprocess(img).double()
             clean = s3fd_ref.dense_boxes(s3fd_ref.s3fd_forward(sd64, x))
             noisy = []
@@ -176,9 +191,50 @@ def oracle_runs():
     return runs
 
 
+@pytest.fixture(scope="module")
+def oracle_runs():
+    return _oracle_runs(_frame_sets())
+
+
+@pytest.fixture(scope="module")
+def geometry_runs():
+    return _oracle_runs(_geometry_sets())
+
+
 def test_whole_detector_against_the_oracle_within_the_yardstick(cuda, oracle_runs):
+    _dense_within_the_yardstick(cuda, oracle_runs)
+
+
+def test_whole_detector_at_production_and_edge_geometries(cuda, geometry_runs):
+    """the yardstick at the geometries of _geometry_sets; at 480x640 the plan must run conv1_2 on box64"""
     fa = _detector(cuda)
-    for img, clean, noisy in oracle_runs:
+    _dense_within_the_yardstick(cuda, geometry_runs, fa)
+    for img, _, _ in geometry_runs:
+        B, H, W = img.shape[:3]
+        disp = fa.face_detector._graph(B, H, W, torch.device(cuda), precision="bf16").dispatch()
+        print("%dx%dx%d: %s" % (B, H, W, ", ".join("%s %s%s" % (n, f, "" if f != "igemm" else " t%d k%d" % (t, k))
+                                                    for n, f, t, k in disp)))
+        assert len(disp) == len(_backbone_layers())
+        if (H, W) == (480, 640):
+            assert dict((n, f) for n, f, _, _ in disp)["conv1_2"] == "box64", disp
+
+
+def test_fp32_detector_against_the_oracle(cuda, oracle_runs, geometry_runs):
+    """the fp32 detector's dense tables against the same clean fp64 oracle, at the tolerance of test_s3fd_gpu.py"""
+    fa = _detector(cuda, precision="f32")
+    for img, clean, _ in oracle_runs + geometry_runs:
+        got = [t.cpu().double().numpy() for t in fa.face_detector.dense_boxes(torch.from_numpy(img).to(cuda))]
+        assert len(got) == len(clean) == 6
+        for lv, (g, c) in enumerate(zip(got, clean)):
+            assert g.shape == c.shape
+            err = float(np.abs(g - c).max())
+            print("fp32 %s level %d: L-inf %.3e" % (img.shape, lv, err))
+            assert err <= 2e-3, (img.shape, lv, err)
+
+
+def _dense_within_the_yardstick(cuda, runs, fa=None):
+    fa = fa or _detector(cuda)
+    for img, clean, noisy in runs:
         got = [t.cpu().double().numpy() for t in fa.face_detector.dense_boxes(torch.from_numpy(img).to(cuda), precision="bf16")]
         assert len(got) == len(clean) == 6
         for lv, (g, c) in enumerate(zip(got, clean)):
@@ -193,13 +249,21 @@ def test_whole_detector_against_the_oracle_within_the_yardstick(cuda, oracle_run
 
 
 def test_rects_of_robust_coordinates_match_the_oracle(cuda, oracle_runs):
+    assert _rects_match(cuda, oracle_runs) >= 1
+
+
+def test_rects_at_production_and_edge_geometries(cuda, geometry_runs):
+    assert _rects_match(cuda, geometry_runs) >= 1
+
+
+def _rects_match(cuda, runs):
     """A rect coordinate is robust when every noisy oracle run gives the clean oracle's value; there the bf16 rect equals it within
     one pixel (truncation to int).  (Per coordinate, not per image: with the seeded weights bf16_storage_noise moves at least one
     coordinate of every test image by 1-2 pixels.)  Every other coordinate stays within twice the noisy runs' largest move plus
     one pixel, and an image where every oracle run finds a face gets one from bf16 as well."""
     fa = _detector(cuda)
     robust = 0
-    for img, clean, noisy in oracle_runs:
+    for img, clean, noisy in runs:
         want = s3fd_ref.rects(s3fd_ref.detections(clean))
         alts = [s3fd_ref.rects(s3fd_ref.detections(n)) for n in noisy]
         got = fa.get_detections_for_batch(img)
@@ -215,7 +279,7 @@ def test_rects_of_robust_coordinates_match_the_oracle(cuda, oracle_runs):
                     assert abs(got[b][k] - want[b][k]) <= 1, (b, k, got[b], want[b])
                 else:
                     assert abs(got[b][k] - want[b][k]) <= 2 * move + 1, (b, k, got[b], want[b], move)
-    assert robust >= 1
+    return robust
 
 
 # ---------------------------------------------------------------- determinism, invalidation

@@ -115,6 +115,20 @@ class ConvB:
     def set_tile(self, tile):
         check(self._lib.w2l_convb_set_tile(self.handle, tile), "convb_set_tile")
 
+    FAMILIES = {0: "igemm", 1: "stem", 2: "box64", 3: "tp2b", 4: "k3s_head"}     # W2L_CONVB_IGEMM .. W2L_CONVB_HEAD
+
+    def resolve(self, N, H, W, res=False):
+        """(family, tile, ksplit) of the kernel a launch over [N,H,W] (with a residual: `res`) runs (w2l_convb_resolve, the
+        launcher's own dry run): family "igemm" with its tile id and split-K, "stem<k>" (k = the stem kernel's layer family),
+        "box64", "tp2b" or "k3s_head" (a layer with a fused head) with tile -1 and split-K 1.  Launches nothing."""
+        fam, tile, ks = C.c_int(), C.c_int(), C.c_int()
+        check(self._lib.w2l_convb_resolve(self.handle, int(N), int(H), int(W), int(bool(res)), C.byref(fam), C.byref(tile),
+                                          C.byref(ks)), "convb_resolve")
+        name = self.FAMILIES[fam.value]
+        if name == "stem":
+            return "stem%d" % tile.value, -1, 1
+        return name, tile.value, ks.value
+
     def run(self, x, y, res=None, scale=None, shift=None, ksplit=0):
         check(self._lib.w2l_convb_forward(self.handle, current_stream(), x.N, x.H, x.W, x.ptr, x.cs, y.ptr, y.cs,
                                           res.ptr if res is not None else None, res.cs if res is not None else 0,
@@ -160,3 +174,13 @@ class ConvB:
                 self.handle = None
         except Exception:
             pass
+
+
+def plan_dispatch(plan, N=None):
+    """[(record name, family, tile, ksplit)] of every ConvB launch of an engine.Plan (ConvB.resolve of each record with its own
+    shape and residual flag); N: resolve the same layers at that batch size instead of the recorded one"""
+    out = []
+    for (name, layer, n, H, W), res in zip(plan.records, plan.has_res):
+        if isinstance(layer, ConvB):
+            out.append((name,) + layer.resolve(n if N is None else N, H, W, res))
+    return out

@@ -642,7 +642,7 @@ struct BVariant {
 float* conv_workspace(hipStream_t stream, size_t bytes);   // conv_igemm.hip: grow-only split-K scratch, one per stream
 // conv_box_bf16.hip: 3x3 / stride 1 / 64 -> 64 channels with the input box and the weight set resident in LDS
 // conv_stem_bf16.hip: 7x7 / stride 1 stems with 8 or 16 channels per pixel (input box + weight set resident in LDS)
-bool stem_ok(int kh, int kw, int sh, int sw, int ph, int pw, int cin_p, int cout, int N, int H, int W, bool has_res);
+int stem_ok(int kh, int kw, int sh, int sw, int ph, int pw, int cin_p, int cout, int N, int H, int W, bool has_res);   // family or 0
 int stem_launch(hipStream_t stream, const void* x, int x_cs, void* y, int y_cs, const void* res, int res_cs, const void* w, int cout_p,
                 int kp, const float* scale, const float* shift, const int* taps, int N, int H, int W, int kh, int cin_p, int cout, int act);
 bool box64_ok(int nphase, int ntaps, int cin_p, int cout, int cout_p, int N, int H, int W, int Ho, int Wo, int sy, int sx);
@@ -1037,8 +1037,13 @@ struct BnBwdOperands {      // the BatchNorm block whose dy this launch produces
     int store_g;            // ReLU block: the launch stores the masked gradient (W2L_BNBWD_STORE_MASKED)
 };
 
-// set by a dry run (w2l_plan_executed_flops): the launch that would run stores its executed FLOPs here and launches nothing
-static thread_local long long* t_dry_flops = nullptr;
+// set by a dry run (w2l_plan_executed_flops, w2l_convb_resolve): the branch that would launch stores its executed FLOPs and what it
+// chose here and launches nothing
+struct ConvbDry {
+    long long flops = 0;
+    int family = W2L_CONVB_IGEMM, tile = -1, ksplit = 1;
+};
+static thread_local ConvbDry* t_dry = nullptr;
 
 static int convb_forward_impl(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, void* y, int y_cs,
                               const void* res, int res_cs, const float* scale, const float* shift, int ksplit_force,
@@ -1077,11 +1082,16 @@ static int convb_forward_impl(const w2l_convb_t* c, void* stream, int N, int H, 
     // W2L_CONVB_BOX=0 (read once): every layer on the implicit GEMM below - A/B switch of the LDS-resident-box kernel
     static const int box_level = [] { const char* e = getenv("W2L_CONVB_BOX"); return e ? atoi(e) : 1; }();   // 2: without the 3x3 small-channel families (A/B)
     const bool box_on = box_level != 0;
+    int stem_fam = 0;
     if (box_on && !unit && (v.q_is_out || (v.omy == 1 && v.omx == 1)) && c->tile_override < 0 && ksplit_force < 1 && v.nphase == 1 &&
         v.ph[0].ntaps == g.kh * g.kw && Ho == H && Wo == W && v.sy == 1 && v.sx == 1 && (g.kh == 7 || box_level != 2) &&
-        stem_ok(g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, c->cin_p, g.cout, N, H, W, res != nullptr)) {
+        (stem_fam = stem_ok(g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, c->cin_p, g.cout, N, H, W, res != nullptr)) != 0) {
         if (stats_out) *stats_out = nullptr;      // no partials / sums: the stand-alone reductions follow (few channels: cheap passes)
-        if (t_dry_flops) { *t_dry_flops = 2ll * N * H * W * c->cout_p * v.ph[0].kp; return W2L_OK; }
+        if (t_dry) {
+            t_dry->flops = 2ll * N * H * W * c->cout_p * v.ph[0].kp;
+            t_dry->family = W2L_CONVB_STEM; t_dry->tile = stem_fam; t_dry->ksplit = 1;
+            return W2L_OK;
+        }
         if (flops_counting()) flops_add(2ll * N * H * W * c->cout_p * v.ph[0].kp, 5);
         return stem_launch(static_cast<hipStream_t>(stream), x, x_cs, y, y_cs, res, res_cs, v.w_dev, c->cout_p, v.ph[0].kp, scale, shift,
                            v.taps_dev, N, H, W, g.kh, c->cin_p, g.cout, g.act);
@@ -1090,7 +1100,11 @@ static int convb_forward_impl(const w2l_convb_t* c, void* stream, int N, int H, 
         v.ph[0].kp == 576 && box64_ok(v.nphase, v.ph[0].ntaps, c->cin_p, g.cout, c->cout_p, N, H, W, Ho, Wo, v.sy, v.sx)) {
         // forward statistics, or (bb) the BatchNorm-backward sums of the block whose dy this launch completes: per-wave partials
         static const bool box_bwd = [] { const char* e = getenv("W2L_BOX_BWD_SUMS"); return e ? atoi(e) != 0 : true; }();   // A/B switch
-        if (t_dry_flops) { *t_dry_flops = 2ll * N * H * W * 64 * 576; return W2L_OK; }
+        if (t_dry) {
+            t_dry->flops = 2ll * N * H * W * 64 * 576;
+            t_dry->family = W2L_CONVB_BOX64; t_dry->tile = -1; t_dry->ksplit = 1;
+            return W2L_OK;
+        }
         hipStream_t s = static_cast<hipStream_t>(stream);
         float* stats = nullptr;
         BoxBwd bw;
@@ -1118,10 +1132,11 @@ static int convb_forward_impl(const w2l_convb_t* c, void* stream, int N, int H, 
     static const bool tp2b_on = [] { const char* e = getenv("W2L_CONVB_TP2B"); return e ? atoi(e) != 0 : true; }();
     if (tp2b_on && !unit && c->tile_override < 0 && ksplit_force < 1 &&
         tp2b_ok(g.transposed, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, v.nphase, v.ph, v.taps_host.data(), c->cin_p, c->cout_p, N, H, W, Ho, Wo)) {
-        if (t_dry_flops) {
+        if (t_dry) {
             long long kp = 0;
             for (int i = 0; i < v.nphase; ++i) kp += (long long)v.ph[i].ntaps * c->cin_p;
-            *t_dry_flops = 2ll * N * H * W * c->cout_p * kp;
+            t_dry->flops = 2ll * N * H * W * c->cout_p * kp;
+            t_dry->family = W2L_CONVB_TP2B; t_dry->tile = -1; t_dry->ksplit = 1;
             return W2L_OK;
         }
         hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1158,10 +1173,11 @@ static int convb_forward_impl(const w2l_convb_t* c, void* stream, int N, int H, 
     a.bz = nullptr; a.by = nullptr; a.bmean = nullptr; a.brstd = nullptr; a.bscale = nullptr; a.bshift = nullptr;
     a.bz_cs = 0; a.by_cs = 0; a.bneg = 1.f; a.bstore_g = 0; a.bmask_only = 0;
     const BTile& tc = kBTiles[ti];
-    if (t_dry_flops) {
+    if (t_dry) {
         long long kp = 0;
         for (int i = 0; i < v.nphase; ++i) kp += v.ph[i].kp;
-        *t_dry_flops = 2ll * ceil_div(a.M, tc.bm) * tc.bm * ceil_div(c->cout_p, tc.bn) * tc.bn * kp;
+        t_dry->flops = 2ll * ceil_div(a.M, tc.bm) * tc.bm * ceil_div(c->cout_p, tc.bn) * tc.bn * kp;
+        t_dry->family = W2L_CONVB_IGEMM; t_dry->tile = ti; t_dry->ksplit = a.ksplit;
         return W2L_OK;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1281,9 +1297,11 @@ int convb_plan_launch(const w2l_convb_t* c, void* stream, int N, int H, int W, c
                       const void* res, int res_cs, const float* scale, const float* shift, long long* flops_out) {
     if (!flops_out) return convb_forward_impl(c, stream, N, H, W, x, x_cs, y, y_cs, res, res_cs, scale, shift, 0, nullptr, nullptr);
     // executed FLOPs of the launch the shape rules resolve to, counted as w2l_flops_begin counts them; nothing is launched
-    t_dry_flops = flops_out;
+    ConvbDry dry;
+    t_dry = &dry;
     const int rc = convb_forward_impl(c, stream, N, H, W, x, x_cs, y, y_cs, res, res_cs, scale, shift, 0, nullptr, nullptr);
-    t_dry_flops = nullptr;
+    t_dry = nullptr;
+    if (rc == W2L_OK) *flops_out = dry.flops;
     return rc;
 }
 }  // namespace w2l
@@ -1293,6 +1311,26 @@ extern "C" {
 int w2l_convb_forward_head(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, uint8_t* frames, float* y32,
                            int y32_cs, const float* scale, const float* shift) {
     return convb_head_impl(c, stream, N, H, W, x, x_cs, frames, y32, y32_cs, scale, shift, nullptr);
+}
+
+int w2l_convb_resolve(const w2l_convb_t* c, int N, int H, int W, int has_res, int* family, int* tile, int* ksplit) {
+    W2L_REQUIRE(c && family && tile && ksplit, "NULL argument");
+    if (c->k3_u) {        // a fused-head layer has the one kernel (convb_head_impl)
+        W2L_REQUIRE(N >= 1 && H >= 1 && W >= 1, "bad shape N=%d H=%d W=%d", N, H, W);
+        *family = W2L_CONVB_HEAD; *tile = -1; *ksplit = 1;
+        return W2L_OK;
+    }
+    // the launcher's dry run over dense strides; the operand pointers only pass its NULL / alignment checks, nothing reads them
+    alignas(16) static const unsigned char operand[16] = {};
+    const void* p = operand;
+    ConvbDry dry;
+    t_dry = &dry;
+    const int rc = convb_forward_impl(c, nullptr, N, H, W, p, c->cin_p, const_cast<void*>(p), c->cout_p, has_res ? p : nullptr,
+                                      c->cout_p, nullptr, nullptr, 0, nullptr, nullptr);
+    t_dry = nullptr;
+    if (rc != W2L_OK) return rc;
+    *family = dry.family; *tile = dry.tile; *ksplit = dry.ksplit;
+    return W2L_OK;
 }
 
 int w2l_convb_forward_bn(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, void* z, int z_cs,

@@ -281,7 +281,7 @@ __global__ __launch_bounds__(512) void conv_tp2b_bf16_kernel(const Tp2bArgs a) {
 // The geometry the kernel implements: a transposed 3x3 / stride 2 / padding 1 layer whose output is exactly 2H x 2W (output padding
 // 1: the decoder's layers, and the data gradient of a 3x3 / stride 2 / padding 1 conv over an even extent), four phases whose taps
 // reach input offsets 0 / 1 only, cin a multiple of the 32-channel chunk.  A shape-only rule (bit-reproducible): the launch must
-// fill the chip (>= 512 workgroups) - smaller ones keep the implicit GEMM and its split-K.
+// fill the chip (>= 256 workgroups) - smaller ones keep the implicit GEMM and its split-K.
 static int tp2b_level() {
     static const int level = [] { const char* e = getenv("W2L_CONVB_TP2B"); return e ? atoi(e) : 1; }();
     return level;

@@ -274,6 +274,10 @@ class _GraphB:
                 head.decode(a, stride, out)
         return self.dense
 
+    def dispatch(self):
+        """[(layer, family, tile, ksplit)] of every backbone convolution (bf16.plan_dispatch): the convb kernel each one runs"""
+        return [d for p in self.plans for d in bf16.plan_dispatch(p)]
+
     def resolved(self):
         """[(layer, kernel family)] of every launch in order: the convb plans' Plan.resolved() families and the glue launches
         (pool1..pool5, the L2Norm modules, the heads named by their feature)"""

@@ -339,6 +339,11 @@ class _GeneratorGraphB(_GeneratorGraph):
         self.hip_graph = None
         self.side = torch.cuda.Stream(device=device) if device.type == "cuda" and engine.TWO_STREAM_ENCODERS else None
 
+    def dispatch(self, N=None):
+        """[(record name, family, tile, ksplit)] of every launch of the plan (bf16.plan_dispatch): the kernel each one runs, or
+        would run at batch N"""
+        return bf16.plan_dispatch(self.plan, N)
+
     def load_nchw(self, audio, face):
         s = current_stream()
         check(self.lib.w2l_nchw_to_nhwc_bf16(s, self.N, 6, self.H, self.W, ptr(face), ptr(self.x_in), 8, 8), "nchw_to_nhwc_bf16")
