@@ -178,7 +178,7 @@ def test_split_operand_implicit_gemm(idx, tile, ksplit, cuda):
     configuration must be the kernel that runs"""
     from wav2lip_amd import _lib
     lib = _lib.load()
-    sid = lib.w2l_conv_num_tiles() - 10 + tile         # the six ids in front of the last four (conv_wino2s, conv_tp2s, conv_stem7s, conv_k3s)
+    sid = _lib.config_ids(lib, "split")[tile]
     assert lib.w2l_conv_config_family(sid) == 5
     plan = _plan_check(SIGS[idx], 2, cuda, sid, ksplit, seed=900 + idx, family="split")
     assert plan.resolved()[0][3][0] == sid
@@ -201,7 +201,7 @@ def test_split_operand_kernel_is_as_accurate_as_the_fp32_kernel(cuda):
     layer = m.to(cuda).fused()
     xin = x.permute(0, 2, 3, 1).contiguous().to(cuda)
     errs = {}
-    for name, tile in (("fp32", 0), ("split", lib.w2l_conv_num_tiles() - 10)):
+    for name, tile in (("fp32", 0), ("split", _lib.config_ids(lib, "split")[0])):
         y = torch.zeros(N, H, W, 512, device=cuda)
         plan = engine.Plan()
         plan.add("l", layer, engine.Act(xin, 0, 512), engine.Act(y, 0, 512), None)
@@ -490,7 +490,7 @@ def test_fused_phase_transposed_conv_matches_oracle(idx, N, cuda):
 def _tp2s_id():
     from wav2lip_amd import _lib
     lib = _lib.load()
-    sid = lib.w2l_conv_num_tiles() - 3
+    sid, = _lib.config_ids(lib, "tp2s")
     assert lib.w2l_conv_config_family(sid) == 7
     return sid
 
@@ -585,7 +585,7 @@ def test_fused_phase_split_operand_kernel_slices_accuracy_and_weight_updates(cud
 def _stem7s_id():
     from wav2lip_amd import _lib
     lib = _lib.load()
-    sid = lib.w2l_conv_num_tiles() - 2
+    sid, = _lib.config_ids(lib, "stem7s")
     assert lib.w2l_conv_config_family(sid) == 8
     return sid
 
@@ -643,7 +643,7 @@ def test_first_layer_split_operand_kernel_slices_accuracy_and_weight_updates(cud
 def _k3s_id():
     from wav2lip_amd import _lib
     lib = _lib.load()
-    sid = lib.w2l_conv_num_tiles() - 1
+    sid, = _lib.config_ids(lib, "k3s")
     assert lib.w2l_conv_config_family(sid) == 9
     return sid
 
@@ -798,7 +798,7 @@ WINO2S_EXTRA = [(64, 64, 13, 11, 1), (64, 64, 4, 4, 0), (80, 64, 33, 35, 0), (64
 def _wino2s_id():
     from wav2lip_amd import _lib
     lib = _lib.load()
-    sid = lib.w2l_conv_num_tiles() - 4
+    sid, = _lib.config_ids(lib, "wino2s")
     assert lib.w2l_conv_config_family(sid) == 6
     return sid
 

@@ -101,6 +101,30 @@ def test_batches_outside_the_launch_table_run_the_committed_plan_lists(cuda, n):
     assert (y[pick] - ref).abs().max() <= TOL
 
 
+def test_every_configuration_id_resolves_exactly_where_the_tune_predicate_accepts_it(cuda):
+    """the launcher's dry run and w2l_tune_entry_applicable share one shape rule: on every fp32 launch of the batch-128 generator
+    plan, forcing configuration id c resolves to c exactly when the launch's tune key accepts c - else a table entry could name a
+    kernel that never runs.  The key carries no activation: a sigmoid layer would be the one exception (the plan has none)."""
+    import ctypes as C
+    from wav2lip_amd import _lib
+    lib = _lib.load()
+    nk = lib.w2l_tune_key_ints()
+    G, _ = _load(amd_models.Wav2Lip(), 0, cuda)
+    plan = G.graph(128, 96, 96, cuda).plan
+    n = len(plan.records)
+    assert not any(layer.geom.act == _lib.ACT_SIGMOID for _, layer, _, _, _ in plan.records)
+    disagree = []
+    for cid in range(lib.w2l_conv_num_tiles()):
+        for i in range(n):
+            plan.set_config(i, cid, 1)
+        got = plan.resolved()
+        for i, (name, layer, N, H, W) in enumerate(plan.records):
+            key = layer.tune_key(N, H, W, has_res=plan.has_res[i])
+            if (got[i][3][0] == cid) != bool(lib.w2l_tune_entry_applicable((C.c_int * nk)(*key), cid)):
+                disagree.append((name, cid, got[i][3]))
+    assert n >= 40 and not disagree, disagree
+
+
 def test_oversized_inference_batch_is_chunked(cuda):
     """a batch larger than one static plan may hold (2 GiB per NHWC buffer: 728 frames at 96x96; plans are capped at
     Wav2Lip.MAX_PLAN_BATCH) runs as chunks, through forward() and through the uint8 runner, with the per-frame results of a

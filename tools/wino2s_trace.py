@@ -30,7 +30,7 @@ def main():
     m = Conv2d(cin, cout, 3, 1, 1, residual=(not args.nores) and cin == cout).to(dev).eval()
     layer = m.fused()
     lib = _lib.load()
-    layer.set_tile(lib.w2l_conv_num_tiles() - 1)
+    layer.set_tile(_lib.config_ids(lib, "wino2s")[0])
     x = engine.Act(torch.randn(args.N, H, W, cin, device=dev), 0, cin)
     y = engine.Act(torch.empty(args.N, H, W, cout, device=dev), 0, cout)
     plan = engine.Plan()

@@ -158,15 +158,24 @@ TUNE_TABLE_PATH = os.path.join(_HERE, "tune_table.json")
 # in frames/s.  Both tables are functions of the shape: either mode is bit-reproducible on its own.
 EXACT = os.environ.get("W2L_EXACT", "0") == "1"
 EXACT_TABLE_PATH = os.path.join(_HERE, "tune_table_exact.json")
-FAMILY_WINO4 = 4
-FAMILY_SPLIT = 5     # conv_igemm_bf16_kernel<.., 3>: fp32 operands as three bf16 pieces on the bf16 matrix cores
-FAMILY_WINO2S = 6    # conv_wino2s_kernel: F(2x2,3x3) Winograd with the transformed operands as three bf16 pieces
-FAMILY_TP2S = 7      # conv_tp2s_kernel: the fused-phase stride-2 transposed kernel with the operands as three bf16 pieces
-FAMILY_STEM7S = 8    # conv_stem7s_kernel: the 7x7 first layer, input region staged and split once, contraction out of LDS
-FAMILY_K3S = 9       # conv_k3s_kernel: direct 3x3 for 32-cout layers (+ fused 1x1 head), input block staged and split once per K-step
+# The kernel family of a configuration id (w2l_conv_config_family) names FAMILY_NAMES[family]: the implicit GEMM, F(2x2,3x3)
+# Winograd and its second form (conv_wino2, wino2q included), the fused-phase stride-2 transposed kernel, F(4x4,3x3) Winograd; then
+# the split-operand families, whose fp32 operands enter the bf16 matrix cores as three bf16 pieces: the implicit GEMM, F(2x2)
+# Winograd, the transposed kernel, the 7x7 first layer and the direct 3x3 for 32-cout layers (+ fused 1x1 head).
+FAMILY_NAMES = ("igemm", "wino", "wino2", "tp2", "wino4", "split", "wino2s", "tp2s", "stem7s", "k3s")
+SPLIT_FAMILIES = frozenset(FAMILY_NAMES.index(n) for n in ("split", "wino2s", "tp2s", "stem7s", "k3s"))
+# family numbers by name, for callers that name one family
+FAMILY_WINO4, FAMILY_SPLIT, FAMILY_WINO2S, FAMILY_TP2S, FAMILY_STEM7S, FAMILY_K3S = (
+    FAMILY_NAMES.index(n) for n in ("wino4", "split", "wino2s", "tp2s", "stem7s", "k3s"))
 
 
-# W2L_SPLIT=0 switches the split-operand implicit GEMM (family 5: fp32-accurate results on the bf16 matrix cores) off AND
+def config_ids(lib, family):
+    """configuration ids of the kernel family named `family` (FAMILY_NAMES), in id order"""
+    f = FAMILY_NAMES.index(family)
+    return [i for i in range(lib.w2l_conv_num_tiles()) if lib.w2l_conv_config_family(i) == f]
+
+
+# W2L_SPLIT=0 switches the split-operand families (fp32-accurate results on the bf16 matrix cores, DESIGN 3d) off AND
 # puts the tuned fp32-pipe entries back for the launches the committed table gives to that family (tune_table_nosplit.json), so
 # that the switch is an A/B against the tuned fp32 kernels, not against the heuristic.
 NO_SPLIT = os.environ.get("W2L_SPLIT", "1") == "0"
@@ -237,7 +246,7 @@ def load():
         fn.restype = res
         fn.argtypes = args
     # W2L_EXACT=1: no F(4x4) Winograd.  W2L_SPLIT=0: no split-operand implicit GEMM (see NO_SPLIT above).
-    mask = ((1 << FAMILY_WINO4) if EXACT else 0) | (((1 << FAMILY_SPLIT) | (1 << FAMILY_WINO2S) | (1 << FAMILY_TP2S) | (1 << FAMILY_STEM7S) | (1 << FAMILY_K3S)) if NO_SPLIT else 0)
+    mask = ((1 << FAMILY_WINO4) if EXACT else 0) | (sum(1 << f for f in SPLIT_FAMILIES) if NO_SPLIT else 0)
     if mask and lib.w2l_conv_exclude_families(mask) != 0:
         raise RuntimeError("wav2lip_amd: could not switch kernel families off (mask %d)" % mask)
     load_tune_table(lib)

@@ -480,20 +480,6 @@ long long w2l_flops_end(long long* by_family) {
     return g_flops.load();
 }
 
-int w2l_conv_config_family(int id) {
-    if (id < 0 || id >= conv_num_tiles()) return -1;
-    if (id < conv_num_igemm_tiles()) return 0;
-    if (id < conv_num_igemm_tiles() + wino_num_cfgs()) return 1;
-    if (id < conv_num_igemm_tiles() + wino_num_cfgs() + wino2_num_cfgs()) return 2;
-    const int tp2 = conv_num_igemm_tiles() + wino_num_cfgs() + wino2_num_cfgs();
-    if (id == conv_num_tiles() - 1) return 9;         // direct 3x3 kernel with split operands for 32-cout layers (conv_k3s.hip), the last id
-    if (id == conv_num_tiles() - 2) return 8;         // the 7x7 first-layer kernel with split operands (conv_stem7s.hip)
-    if (id == conv_num_tiles() - 3) return 7;         // fused-phase stride-2 transposed kernel with split operands (conv_tp2s.hip)
-    if (id == conv_num_tiles() - 4) return 6;         // split-operand F(2x2) Winograd (conv_wino2s.hip)
-    if (id >= tp2 + 3) return 5;                      // implicit-GEMM tile id - (tp2 + 3) with split fp32 operands
-    return id == tp2 ? 3 : (id == tp2 + 1 ? 4 : 2);   // the id behind conv_wino4's is the quarter-split conv_wino2 shape
-}
-
 // Kernel families a caller has switched off (bit mask over w2l_conv_config_family values): the autotune does not time them and
 // a table / forced id of such a family falls through to the next rule (conv_forward_impl).  Used to build and to run the
 // "exact" launch table (no F(4x4) Winograd: half the rounding error of the default table).

@@ -449,7 +449,7 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 //
-// NP = 3 ("split" kernel, configuration ids conv_split_id(tile)): an fp32 RESULT from the bf16 matrix cores.  An fp32 value is the
+// NP = 3 ("split" kernel, configuration ids 13-18, kIdList): an fp32 RESULT from the bf16 matrix cores.  An fp32 value is the
 // exact sum of three bf16 values (3 x 8 significant bits): x = x0 + x1 + x2 with x0 = bf16(x), x1 = bf16(x - x0),
 // x2 = bf16(x - x0 - x1).  Both operand tiles go to LDS as three bf16 planes and a K-chunk of 16 is six MFMAs, the piece products
 // a_i * b_j with i + j <= 2 (the three dropped ones are below 2^-24 of the product; each kept product is exact in the fp32
@@ -923,7 +923,7 @@ struct TileCfg {
     int lds;
     void (*kernel_bf16)(const ConvKArgs);   // same tile on the bf16 matrix cores (w2l_conv_set_precision)
     int lds_bf16;
-    void (*kernel_split)(const ConvKArgs);  // same tile, fp32 operands as three bf16 pieces (configuration id conv_split_id(tile))
+    void (*kernel_split)(const ConvKArgs);  // same tile, fp32 operands as three bf16 pieces (configuration ids 13-18, kIdList)
     int lds_split;
     int threads_split;
 };
@@ -963,6 +963,9 @@ struct Variant {
     bool built = false;
 };
 
+// Weight forms: packed copies of a layer's weights that only some configurations read (kForms below lists how each is built)
+enum WeightFormId { kFormWino, kFormWino4, kFormTp2, kFormStem7s, kFormK3s, kFormWino2s, kFormTp2s, kNumForms };
+
 }  // namespace w2l
 
 struct w2l_conv {
@@ -974,16 +977,7 @@ struct w2l_conv {
     w2l::Variant generic;   // any input size
     w2l::Variant unit_in;   // transposed, stride 1, 1x1 input: one single-tap phase per output position
     w2l::Variant xpair;     // conv with cout <= 16, x-stride 1: two horizontally adjacent output pixels per GEMM row
-    float* wino_u = nullptr;  // Winograd-transformed weights (3x3 s1 p1 layers), see conv_wino.hip
-    float* tp2_u = nullptr;   // fragment-ordered weights of the fused-phase stride-2 transposed kernel, see conv_tp2.hip
-    float* wino4_u = nullptr; // F(4x4,3x3) Winograd-transformed weights (36 positions), see conv_wino4.hip
-    // F(2x2,3x3) transformed weights as three bf16 planes in fragment order (conv_wino2s.hip): built by the first launch that names
-    // that configuration (lazy_weights below), refreshed by w2l_conv_update; layers that never run it carry nothing
-    mutable std::atomic<__bf16*> wino2s_u{nullptr};
-    // conv_tp2's weights as three bf16 planes in conv_tp2s.hip's fragment order: built the same way by the first launch on its id
-    mutable std::atomic<__bf16*> tp2s_u{nullptr};
-    __bf16* stem7s_u = nullptr;   // pre-split weights of the 7x7 first-layer kernel (conv_stem7s.hip), built with the layer
-    __bf16* k3s_u = nullptr;      // pre-split weights of the direct 3x3 kernel for 32-cout layers (conv_k3s.hip), built with the layer
+    mutable std::atomic<void*> form[w2l::kNumForms] = {};   // the other kernels' weight forms (kForms), NULL where not built
     float* head_w = nullptr;  // fused 1x1 head [head_c][cout] (device), see w2l_conv_attach_head
     float* head_b = nullptr;
     int head_c = 0, head_act = 0;
@@ -995,12 +989,10 @@ namespace w2l {
 
 enum VariantMode { kGeneric = 0, kUnitInput = 1, kXPair = 2 };
 
-// w_dev -> w_split, asynchronous on `stream`
-static int split_variant(const Variant& v, hipStream_t stream) {
-    __bf16* const ws = v.w_split.load(std::memory_order_acquire);
-    if (!ws) return W2L_OK;
+// w_dev -> three bf16 planes per phase at `out` (w_split, or the buffer that becomes it), asynchronous on `stream`
+static int split_weights(const Variant& v, __bf16* out, hipStream_t stream) {
     SplitWArgs sa;
-    sa.w = v.w_dev; sa.out = ws; sa.nphase = v.nphase;
+    sa.w = v.w_dev; sa.out = out; sa.nphase = v.nphase;
     long long maxtot = 1;
     for (int i = 0; i < v.nphase; ++i) {
         sa.off[i] = v.ph[i].w_off;
@@ -1039,7 +1031,8 @@ static int pack_variant(const w2l_conv* c, const Variant& v, const float* weight
     hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks, v.nphase), dim3(256), 0, stream, pa);
     W2L_HIP_CHECK(hipGetLastError());
     v.split_fresh = false;
-    return v.w_split.load() ? split_variant(v, stream) : W2L_OK;
+    __bf16* const ws = v.w_split.load(std::memory_order_acquire);
+    return ws ? split_weights(v, ws, stream) : W2L_OK;
 }
 
 static int build_variant(w2l_conv* c, Variant& v, VariantMode mode, hipStream_t stream) {
@@ -1158,44 +1151,13 @@ static int max_steps(const Variant& v) {
 // Heuristic launch configuration (tile id, split-K factor) when no tuned/forced one is given: minimise
 // rounds-of-256-CUs x tile area / measured tile efficiency; split K when the grid cannot fill the chip.
 // whole_row: the epilogue needs every GEMM column of a row in one workgroup and no split-K (fused head)
-static bool tile_allowed(const Variant& v, int tile, bool whole_row) {
-    return tile >= 0 && tile < kNumTiles && (!whole_row || kTiles[tile].bn >= v.cout_p);
-}
-
-int conv_tp2_id();
-int conv_wino4_id();
-int conv_wino2q_id();
-int conv_split_id(int tile);
-int conv_wino2s_id();
-int conv_tp2s_id();
-int conv_stem7s_id();
-int conv_k3s_id();
-bool conv_family_excluded(int id);   // api.hip
-
-// configuration ids conv_split_id(t), t < kNumTiles: implicit-GEMM tile t with the fp32 operands as three bf16 pieces (an fp32
-// result from the bf16 matrix cores, see conv_igemm_bf16_kernel<.., 3>); -1 if `id` is not one of them
-static int split_tile_of(int id) {
-    const int t = id - conv_split_id(0);
-    return (id >= 0 && t >= 0 && t < kNumTiles) ? t : -1;
-}
-
-// configuration ids kNumTiles + i select Winograd configuration i (conv_wino.hip) on eligible layers
-static bool wino_allowed(const w2l_conv* c, int tile, int x_cs) {   // + wino_io_ok() on the output side
-    if (!(c->wino_u != nullptr && c->precision == W2L_PREC_F32 && c->g.act != W2L_ACT_SIGMOID && tile >= kNumTiles &&
-          tile < conv_tp2_id() && (x_cs & 3) == 0))
-        return false;
-    const int wc = tile - kNumTiles;
-    if (wc < wino_num_cfgs()) return c->head_w == nullptr && wino_cfg_ok(wc, c->g.cin, c->g.cout);
-    return wino2_ok(wc - wino_num_cfgs(), c->g.cin, c->g.cout, c->head_w ? c->head_c : 0);   // conv_wino2.hip (fuses a 1x1 head)
-}
-
-static void pick_config(const w2l_conv* c, const Variant& v, int M, bool whole_row, int* tile, int* ksplit) {
+static void pick_config(const Variant& v, int M, bool whole_row, int* tile, int* ksplit) {
     int best = -1, best_ks = 1;
     double best_cost = 1e300;
     const int steps = max_steps(v);
     for (int i = 0; i < kNumTiles; ++i) {
         const TileCfg& tc = kTiles[i];
-        if (!tile_allowed(v, i, whole_row)) continue;
+        if (whole_row && tc.bn < v.cout_p) continue;
         const long long blocks = (long long)ceil_div(M, tc.bm) * ceil_div(v.cout_p, tc.bn) * v.nphase;
         for (int ks = 1; ks <= 16; ks *= 2) {
             if (ks > 1 && (whole_row || v.pair > 1)) break;
@@ -1208,9 +1170,8 @@ static void pick_config(const w2l_conv* c, const Variant& v, int M, bool whole_r
             if (cost < best_cost) { best_cost = cost; best = i; best_ks = ks; }
         }
     }
-    const bool ov = tile_allowed(v, c->tile_override, whole_row);
-    *tile = ov ? c->tile_override : best;
-    *ksplit = ov ? 1 : best_ks;
+    *tile = best;
+    *ksplit = best_ks;
 }
 
 // grow-only device scratch for split-K partial sums (stream-ordered reuse across layers of one stream)
@@ -1248,8 +1209,8 @@ float* conv_workspace(hipStream_t stream, size_t bytes) { return stream_workspac
 // pointer is published with release / read with acquire, and a stream that is being captured into a graph is refused - the build
 // allocates and synchronises - with a message that says what to do (run the plan once before capturing it).
 static std::mutex g_lazy_mutex;
-template <class Fill>
-static int lazy_weights(std::atomic<__bf16*>& slot, size_t elems, hipStream_t stream, const char* what, Fill fill) {
+template <class T, class Fill>
+static int lazy_weights(std::atomic<T*>& slot, size_t bytes, hipStream_t stream, const char* what, Fill fill) {
     if (slot.load(std::memory_order_acquire)) return W2L_OK;
     std::lock_guard<std::mutex> lock(g_lazy_mutex);
     if (slot.load(std::memory_order_acquire)) return W2L_OK;
@@ -1258,8 +1219,8 @@ static int lazy_weights(std::atomic<__bf16*>& slot, size_t elems, hipStream_t st
         set_error("%s are built by the first launch of the layer: run it once before capturing the stream", what);
         return W2L_ERR_ARG;
     }
-    __bf16* p = nullptr;
-    if (hipMalloc(&p, sizeof(__bf16) * (elems > 0 ? elems : 1)) != hipSuccess) {
+    T* p = nullptr;
+    if (hipMalloc((void**)&p, bytes > 0 ? bytes : 1) != hipSuccess) {
         set_error("hipMalloc(%s) failed", what);
         return W2L_ERR_NOMEM;
     }
@@ -1301,216 +1262,252 @@ void tune_store_launch(const w2l_conv* c, int N, int H, int W, bool has_res, int
     g_tune[tune_key(c, N, H, W, has_res)] = std::make_pair(tile, ksplit);
 }
 
-// flops_out != NULL: dry run - resolve the configuration exactly as a launch would, report the multiply-add work the matrix
-// cores would EXECUTE (padded tiles, padded K, Winograd's 16 products per 2x2 tile; x2 = FLOPs) and launch nothing
-extern "C" int w2l_conv_config_family(int id);   // api.hip
-int conv_forward_impl(const w2l_conv* c, hipStream_t stream, int N, int H, int W, const float* x,
-                      int x_cs, float* y, int y_cs, const float* res, int res_cs, int force_tile, int force_ksplit,
-                      long long* flops_out, int* cfg_out) {
-    W2L_REQUIRE(c && x && y, "NULL argument");
-    if (!flops_out && flops_counting()) {   // w2l_flops_begin: resolve this launch once more as a dry run and book its work
-        long long f = 0;
-        int cfg[2];
-        if (conv_forward_impl(c, stream, N, H, W, x, x_cs, y, y_cs, res, res_cs, force_tile, force_ksplit, &f, cfg) == W2L_OK)
-            // 3: bf16 matrix-core work - the bf16c precision and EVERY split-operand family (5..9: ids of conv_igemm_bf16_kernel<..,3>,
-            // conv_wino2s, conv_tp2s, conv_stem7s, conv_k3s), whose dry runs count six bf16 piece products per product
-            flops_add(f, (c->precision == W2L_PREC_BF16 || w2l_conv_config_family(cfg[0]) >= 5) ? 3 : 0);
+// ---- configuration ids: one list, in id order, of (family, number of ids).  A family's ids are numbered on across its ranges
+// (ConfigId::index): the F(2x2) second form's quarter-split shape, wino2q, is its index kNumWino2Cfgs.  Ids are append-only:
+// committed tune tables and plan_configs.json name them.  bf16_pipe: the family runs its fp32 operands as three bf16 pieces on
+// the bf16 matrix cores - its dry run counts six bf16 piece products per product, booked as bf16 matrix-core work.
+enum ConvFamily { kFamIgemm, kFamWino, kFamWino2, kFamTp2, kFamWino4, kFamSplit, kFamWino2s, kFamTp2s, kFamStem7s, kFamK3s, kNumFamilies };
+static const struct { int family, count; bool bf16_pipe; } kIdList[] = {
+    {kFamIgemm, kNumTiles, false},       // 0-5    implicit-GEMM tiles (kTiles)
+    {kFamWino, kNumWinoCfgs, false},     // 6-7    F(2x2,3x3) Winograd (conv_wino.hip)
+    {kFamWino2, kNumWino2Cfgs, false},   // 8-9    its second form (conv_wino2.hip; fuses a 1x1 head on the 32-cout shape)
+    {kFamTp2, 1, false},                 // 10     fused-phase stride-2 transposed 3x3 (conv_tp2.hip)
+    {kFamWino4, 1, false},               // 11     F(4x4,3x3) Winograd (conv_wino4.hip)
+    {kFamWino2, 1, false},               // 12     the second form's quarter-split shape, wino2q (fused head allowed)
+    {kFamSplit, kNumTiles, true},        // 13-18  the implicit-GEMM tiles with split operands (conv_igemm_bf16_kernel<.., 3>)
+    {kFamWino2s, 1, true},               // 19     split-operand F(2x2) Winograd (conv_wino2s.hip)
+    {kFamTp2s, 1, true},                 // 20     split-operand tp2 (conv_tp2s.hip)
+    {kFamStem7s, 1, true},               // 21     the 7x7 first layer (conv_stem7s.hip)
+    {kFamK3s, 1, true},                  // 22     direct 3x3 for 32-cout layers, fuses a 1x1 head (conv_k3s.hip)
+};
+
+struct ConfigId {
+    int family = -1, index = -1;   // family -1: not a configuration id
+    bool bf16_pipe = false;
+};
+static ConfigId config_decode(int id) {
+    if (id < 0) return ConfigId{};
+    int seen[kNumFamilies] = {};
+    for (const auto& r : kIdList) {
+        if (id < r.count) return ConfigId{r.family, seen[r.family] + id, r.bf16_pipe};
+        seen[r.family] += r.count;
+        id -= r.count;
     }
-    // a per-layer override of a family switched off by w2l_conv_exclude_families (W2L_EXACT) counts as no override: exact mode
-    // is a property of the library, whichever way a launch names its configuration
-    const int tile_override = (c->tile_override >= 0 && conv_family_excluded(c->tile_override)) ? -1 : c->tile_override;
-    // an explicit id of a switched-off family counts as no choice at all (w2l_conv_exclude_families): the launch then resolves as an
-    // unconfigured one does - the shape-keyed table first (W2L_SPLIT=0 overlays the fp32-pipe predecessors there), then the
-    // heuristic.  (Dropping it AFTER the table lookup sent such launches - the borrowed per-plan lists of untuned batch sizes name
-    // split ids - straight to the heuristic at split-K 1.)
-    if (force_tile >= 0 && conv_family_excluded(force_tile)) { force_tile = -1; force_ksplit = 1; }
-    if (force_tile < 0 && tile_override < 0) {   // no explicit choice: the shape-keyed table, else the heuristic below
-        int tt, tk;
-        if (tune_lookup(tune_key(c, N, H, W, res != nullptr), &tt, &tk)) { force_tile = tt; force_ksplit = tk; }
-    }
-    if (force_tile >= 0 && conv_family_excluded(force_tile)) { force_tile = -1; force_ksplit = 1; }   // a table entry of such a family
-    W2L_REQUIRE(N >= 1 && H >= 1 && W >= 1, "bad shape N=%d H=%d W=%d", N, H, W);
-    W2L_REQUIRE(x_cs >= c->cin_p && (x_cs & 3) == 0, "x_cs=%d must be a multiple of 4 and >= %d", x_cs, c->cin_p);
-    W2L_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0, "x must be 16-byte aligned");
-    W2L_REQUIRE(c->head_w != nullptr || y_cs >= c->g.cout, "y_cs=%d < cout=%d", y_cs, c->g.cout);
-    W2L_REQUIRE(res == nullptr || res_cs >= c->g.cout, "res_cs=%d < cout", res_cs);
-    int Ho, Wo;
-    if (w2l_conv_out_hw(&c->g, H, W, &Ho, &Wo) != W2L_OK) return W2L_ERR_ARG;
-    W2L_REQUIRE(Ho >= 1 && Wo >= 1, "empty output %dx%d", Ho, Wo);
-    const bool unit = c->g.transposed && c->g.sh == 1 && c->g.sw == 1 && H == 1 && W == 1 && c->unit_in.built;
-    const bool head = c->head_w != nullptr;
-    W2L_REQUIRE(!head || (y_cs >= c->head_c && res == nullptr), "fused head: y_cs=%d < %d or residual given", y_cs, c->head_c);
-    const bool y_vec_ok = (c->g.cout & 3) == 0 && (y_cs & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
-    const bool xp = c->xpair.built && !head && res == nullptr && (Wo % 2) == 0 && y_vec_ok;
-    const Variant& v = unit ? c->unit_in : (xp ? c->xpair : c->generic);
-    ConvKArgs a;
-    a.x = x; a.y = y; a.res = res; a.w = v.w_dev; a.wsplit = v.w_split.load(std::memory_order_acquire); a.scale = c->scale; a.shift = c->shift; a.taps = v.taps_dev;
-    a.N = N; a.H = H; a.W = W; a.cin_p = c->cin_p; a.x_cs = x_cs;
-    a.Ho = Ho; a.Wo = Wo; a.cout = c->g.cout; a.cout_p = v.cout_p; a.y_cs = y_cs; a.res_cs = res_cs;
-    a.pair = v.pair; a.ncols = v.pair * c->g.cout;
-    a.head_w = c->head_w; a.head_b = c->head_b; a.head_c = c->head_c; a.head_act = c->head_act;
-    if (unit) { a.Hq = 1; a.Wq = 1; }
-    else if (v.q_is_out) { a.Hq = Ho; a.Wq = Wo; }
-    else { a.Hq = ceil_div(Ho, v.omy); a.Wq = ceil_div(Wo, v.omx); }
-    a.sy = v.sy; a.sx = v.sx; a.omy = v.omy; a.omx = v.omx;
-    a.act = c->g.act;
-    // float4 epilogue needs 16-byte aligned rows on y / res / scale / shift
-    a.vec_epilogue = (y_vec_ok && (res == nullptr || ((res_cs & 3) == 0 && (reinterpret_cast<uintptr_t>(res) & 15) == 0)))
-                         ? 1 : 0;
-    const long long lim = 1ll << 31;  // buffer descriptors use 32-bit byte offsets with 0x80000000 as "out of range"
-    W2L_REQUIRE(((long long)N * H * W * x_cs) * 4 < lim && ((long long)N * Ho * Wo * y_cs) * 4 < lim &&
-                    (res == nullptr || ((long long)N * Ho * Wo * res_cs) * 4 < lim),
-                "activation buffer larger than 2 GiB: split the batch");
-    const long long M = (long long)N * a.Hq * a.Wq;
-    W2L_REQUIRE(M < (1ll << 31) && (long long)N * H * W < (1ll << 31) && (long long)N * Ho * Wo < (1ll << 31), "tensor too large");
-    a.M = (int)M;
-    for (int i = 0; i < v.nphase; ++i) a.ph[i] = v.ph[i];
-    // the direct 3x3 kernel with split operands for 32-cout layers (fuses the 1x1 head): only by explicit configuration id
-    if (c->k3s_u != nullptr && c->precision == W2L_PREC_F32 && (x_cs & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-        (head || ((y_cs & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0)) &&
-        (res == nullptr || ((res_cs & 3) == 0 && (reinterpret_cast<uintptr_t>(res) & 15) == 0)) && (!head || c->head_c <= 4) &&
-        (force_tile == conv_k3s_id() || (force_tile < 0 && tile_override == conv_k3s_id()))) {
-        if (cfg_out) { cfg_out[0] = conv_k3s_id(); cfg_out[1] = 1; }
-        return k3s_launch(x, x_cs, y, y_cs, res, res_cs, c->k3s_u, c->scale, c->shift, head ? c->head_w : nullptr, c->head_b, c->head_c,
-                          c->head_act, N, H, W, c->g.cin, c->g.act, stream, flops_out);
-    }
-    // the 7x7 first-layer kernel with split operands: only by explicit configuration id
-    if (c->stem7s_u != nullptr && c->precision == W2L_PREC_F32 && !head && res == nullptr && x_cs >= 8 &&
-        (force_tile == conv_stem7s_id() || (force_tile < 0 && tile_override == conv_stem7s_id()))) {
-        if (cfg_out) { cfg_out[0] = conv_stem7s_id(); cfg_out[1] = 1; }
-        return stem7s_launch(x, x_cs, y, y_cs, c->stem7s_u, c->scale, c->shift, N, H, W, c->g.act, stream, flops_out);
-    }
-    // fused-phase stride-2 transposed kernel with split operands: only by explicit configuration id
-    if (c->tp2_u != nullptr && c->precision == W2L_PREC_F32 && !head && res == nullptr && !unit && tp2s_ok(c->g) && (y_cs & 3) == 0 &&
-        (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
-        (force_tile == conv_tp2s_id() || (force_tile < 0 && tile_override == conv_tp2s_id()))) {
-        int ks = force_tile == conv_tp2s_id() ? force_ksplit : 1;      // a per-layer override (tile_override) carries no split-K
-        if (ks < 1) ks = 1;
-        if (ks > c->g.cin / 16) ks = c->g.cin / 16;
-        const int sps = ceil_div(c->g.cin / 16, ks);
-        ks = ceil_div(c->g.cin / 16, sps);
-        if (cfg_out) { cfg_out[0] = conv_tp2s_id(); cfg_out[1] = ks; }
-        float* ws = nullptr;
-        const long long npix = (long long)N * 4 * H * W;
-        if (!flops_out) {
-            const int rc = lazy_weights(c->tp2s_u, (size_t)tp2s_u_elems(c->g.cin, c->g.cout), stream, "split-operand transposed weights",
-                                        [&](__bf16* p) { return tp2s_pack(c->tp2_u, p, c->g.cin, c->g.cout, stream); });
-            if (rc != W2L_OK) return rc;
-            if (ks > 1) {
-                ws = stream_workspace(stream, (size_t)ks * npix * c->g.cout * sizeof(float));
-                if (!ws) return W2L_ERR_NOMEM;
-            }
+    return ConfigId{};
+}
+static int config_id(int family, int index) {   // config_decode's inverse
+    int id = 0;
+    for (const auto& r : kIdList) {
+        if (r.family == family) {
+            if (index < r.count) return id + index;
+            index -= r.count;
         }
-        int used = 1;
-        const int rc = tp2s_launch(x, x_cs, y, y_cs, c->tp2s_u.load(std::memory_order_acquire), c->scale, c->shift, N, H, W, c->g.cin,
-                                   c->g.cout, c->g.act, ks, ws, &used, stream, flops_out);
-        if (rc != W2L_OK || flops_out || used == 1) return rc;
-        ReduceArgs r;
-        r.ws = ws; r.y = y; r.res = nullptr; r.scale = c->scale; r.shift = c->shift;
-        r.npix = npix; r.ksplit = used; r.cout = c->g.cout; r.cout_p = c->g.cout;
-        r.y_cs = y_cs; r.res_cs = 0; r.act = c->g.act;
-        long long g = (npix * c->g.cout + 255) / 256;
-        if (g > 4096) g = 4096;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, stream, r);
-        W2L_HIP_CHECK(hipGetLastError());
+        id += r.count;
+    }
+    return -1;
+}
+int conv_num_tiles() {
+    int n = 0;
+    for (const auto& r : kIdList) n += r.count;
+    return n;
+}
+int conv_num_igemm_tiles() { return kNumTiles; }
+bool conv_family_excluded(int id);   // api.hip
+
+// ---- weight forms (WeightFormId): eager forms are packed by w2l_conv_create from the caller's weights when the layer's geometry
+// needs them (needs_form); lazy forms - fp32 values as three bf16 planes - are split from their source form by the first launch
+// that reads them (lazy_form), so layers that never run such a configuration carry nothing.  w2l_conv_update repacks every form
+// that exists in list order (a lazy form after its source).  The implicit GEMM's forms (Variant::w_dev, w_split) go with their variant.
+struct WeightForm {
+    const char* what;
+    int source;   // lazy: the form it is split from; -1: eager, from the caller's weights
+    size_t (*bytes)(const w2l_conv_geom& g);
+    int (*pack)(const w2l_conv_geom& g, const float* src, void* dst, hipStream_t s);
+};
+static const WeightForm kForms[kNumForms] = {
+    {"winograd weights", -1, [](const w2l_conv_geom& g) -> size_t { return sizeof(float) * wino_u_floats(g.cin, g.cout); },
+     [](const w2l_conv_geom& g, const float* w, void* u, hipStream_t s) { return wino_pack(w, (float*)u, g.cin, g.cout, g.transposed, s); }},
+    {"F(4x4) winograd weights", -1, [](const w2l_conv_geom& g) -> size_t { return sizeof(float) * wino4_u_floats(g.cin, g.cout); },
+     [](const w2l_conv_geom& g, const float* w, void* u, hipStream_t s) { return wino4_pack(w, (float*)u, g.cin, g.cout, g.transposed, s); }},
+    {"transposed-conv fragment weights", -1, [](const w2l_conv_geom& g) -> size_t { return sizeof(float) * tp2_u_floats(g.cin, g.cout); },
+     [](const w2l_conv_geom& g, const float* w, void* u, hipStream_t s) { return tp2_pack(w, (float*)u, g.cin, g.cout, s); }},
+    {"first-layer split weights", -1, [](const w2l_conv_geom& g) -> size_t { return sizeof(__bf16) * stem7s_u_elems(); },
+     [](const w2l_conv_geom& g, const float* w, void* u, hipStream_t s) { return stem7s_pack(w, (__bf16*)u, g.cin, s); }},
+    {"direct 3x3 split weights", -1, [](const w2l_conv_geom& g) -> size_t { return sizeof(__bf16) * k3s_u_elems(g.cin); },
+     [](const w2l_conv_geom& g, const float* w, void* u, hipStream_t s) { return k3s_pack(w, (__bf16*)u, g.cin, s); }},
+    {"split-operand F(2x2) weights", kFormWino, [](const w2l_conv_geom& g) -> size_t { return sizeof(__bf16) * wino2s_u_elems(g.cin, g.cout); },
+     [](const w2l_conv_geom& g, const float* u32, void* u, hipStream_t s) { return wino2s_pack(u32, (__bf16*)u, g.cin, g.cout, s); }},
+    {"split-operand transposed weights", kFormTp2, [](const w2l_conv_geom& g) -> size_t { return sizeof(__bf16) * tp2s_u_elems(g.cin, g.cout); },
+     [](const w2l_conv_geom& g, const float* u32, void* u, hipStream_t s) { return tp2s_pack(u32, (__bf16*)u, g.cin, g.cout, s); }},
+};
+
+template <class T>
+static const T* form_of(const w2l_conv* c, int f) { return static_cast<const T*>(c->form[f].load(std::memory_order_acquire)); }
+
+// 3x3 / stride 1 / pad 1, or the transposed form of such a conv (its data gradient: the same conv with the kernel flipped and the
+// channel roles swapped, which only changes how the packer reads the weight tensor)
+static bool k3s1p1(const w2l_conv_geom& g) {
+    return g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1 && g.oph == 0 && g.opw == 0;
+}
+
+// Does w2l_conv_create pack form f for this geometry?  Every configuration that reads a form requires this of its layer (config_fits).
+static bool needs_form(int f, const w2l_conv_geom& g) {
+    switch (f) {
+    case kFormWino: {   // some F(2x2) configuration fits the channels of a head-less layer
+        bool any = false;
+        for (int i = 0; i < kNumWinoCfgs; ++i) any = any || wino_cfg_ok(i, g.cin, g.cout);
+        for (int i = 0; i < kNumWino2Cfgs; ++i) any = any || wino2_ok(i, g.cin, g.cout, 0);
+        return k3s1p1(g) && any;
+    }
+    case kFormWino4: return k3s1p1(g) && wino4_ok(g.cin, g.cout);
+    case kFormTp2: return tp2_ok(g);
+    case kFormStem7s: return stem7s_ok(g);
+    case kFormK3s: return k3s_ok(g);
+    }
+    return false;   // lazy forms
+}
+
+static int lazy_form(const w2l_conv* c, int f, hipStream_t stream) {
+    const WeightForm& wf = kForms[f];
+    return lazy_weights(c->form[f], wf.bytes(c->g), stream, wf.what,
+                        [&](void* p) { return wf.pack(c->g, form_of<float>(c, wf.source), p, stream); });
+}
+
+// ---- which configurations can run a launch at all: a pure function of the shape - the layer's geometry (its activation
+// included), precision, whether a residual is added and the fused head's channels (0: none).  The tune key carries all of it but
+// the activation (w2l_tune_entry_applicable).  The launcher adds the buffers' alignment (io_fits).
+struct ConvShape {
+    w2l_conv_geom g;
+    int precision, has_res, head_c;
+};
+static bool config_fits(int id, const ConvShape& s) {
+    const ConfigId ci = config_decode(id);
+    const w2l_conv_geom& g = s.g;
+    if (ci.family != kFamIgemm && s.precision != W2L_PREC_F32) return false;   // every other family is fp32-only
+    const bool plain = s.head_c == 0 && !s.has_res;
+    const bool no_sigmoid = g.act != W2L_ACT_SIGMOID;                          // no Winograd epilogue has it
+    const bool wino = needs_form(kFormWino, g) && no_sigmoid;
+    switch (ci.family) {
+    case kFamIgemm:
+    case kFamSplit: return s.head_c == 0 || kTiles[ci.index].bn >= round_up(g.cout, 32);   // a fused head needs a whole row
+    case kFamWino: return wino && s.head_c == 0 && wino_cfg_ok(ci.index, g.cin, g.cout);
+    case kFamWino2:
+        return wino && (ci.index < kNumWino2Cfgs ? wino2_ok(ci.index, g.cin, g.cout, s.head_c) : wino2q_ok(g.cin, g.cout, s.head_c));
+    case kFamTp2: return tp2_ok(g) && plain;
+    case kFamWino4: return needs_form(kFormWino4, g) && no_sigmoid && s.head_c == 0;
+    case kFamWino2s: return wino && s.head_c == 0 && wino2s_ok(g.cin, g.cout);
+    case kFamTp2s: return tp2s_ok(g) && plain;
+    case kFamStem7s: return stem7s_ok(g) && plain;
+    case kFamK3s: return k3s_ok(g) && s.head_c <= 4;
+    }
+    return false;
+}
+
+// 16-byte rows: a multiple of 4 floats per pixel from a 16-byte aligned base
+static bool io16(const void* p, int cs) { return (cs & 3) == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// the buffers a family's kernel takes beyond those of every launch (x in 16-byte rows); the implicit GEMM takes any
+static bool io_fits(int family, const ConvKArgs& a, bool head) {
+    const bool res_ok = a.res == nullptr || io16(a.res, a.res_cs);
+    switch (family) {
+    case kFamK3s: return (head || io16(a.y, a.y_cs)) && res_ok;
+    case kFamStem7s: return a.x_cs >= 8;
+    case kFamTp2:
+    case kFamTp2s: return io16(a.y, a.y_cs);
+    case kFamWino:
+    case kFamWino2:
+    case kFamWino4:
+    case kFamWino2s: return io16(a.y, a.y_cs) && res_ok;   // the Winograd epilogues move float4 rows
+    }
+    return true;
+}
+
+// Which (configuration id, split-K) a launch runs.  The order:
+//  1. A per-layer override (w2l_conv_set_tile) of a family switched off by w2l_conv_exclude_families (W2L_EXACT, W2L_SPLIT=0)
+//     counts as no override, and a forced id of such a family as no forced id: exact mode is a property of the library, whichever
+//     way a launch names its configuration.
+//  2. With neither a forced id nor an override, the shape-keyed table names the id and split-K; an entry of a switched-off family
+//     counts as none.  (Dropping an excluded forced id only after the lookup sent such launches - the borrowed per-plan lists of
+//     untuned batch sizes name split ids - straight to the heuristic at split-K 1.)
+//  3. A non-GEMM id runs if config_fits and io_fits accept it: the forced id, or the override when no id is forced.  Its split-K
+//     is 1, but tp2s takes a forced id's split-K, clamped to its cin / 16 K-steps.
+//  4. With neither a forced id nor an override: F(2x2) Winograd (id 6) when its grid fills the chip.
+//  5. The implicit GEMM, first of: a fitting forced tile with its split-K; a fitting split-operand tile - the forced id with its
+//     split-K, or the override when no id is forced, split-K 1; an implicit-GEMM override, split-K 1 (taken even when a forced
+//     non-GEMM id did not fit, unlike a split override); the pick_config heuristic.
+static int resolve_config(const w2l_conv* c, const Variant& v, const ConvKArgs& a, int force, int force_ks, int cfg[2]) {
+    const bool head = c->head_w != nullptr;
+    const ConvShape s{c->g, c->precision, a.res != nullptr, c->head_c};
+    const int ov = (c->tile_override >= 0 && conv_family_excluded(c->tile_override)) ? -1 : c->tile_override;
+    if (force >= 0 && conv_family_excluded(force)) { force = -1; force_ks = 1; }
+    if (force < 0 && ov < 0) {
+        tune_lookup(tune_key(c, a.N, a.H, a.W, a.res != nullptr), &force, &force_ks);
+        if (force >= 0 && conv_family_excluded(force)) { force = -1; force_ks = 1; }
+    }
+    const int named = force >= 0 ? force : ov;
+    const ConfigId ci = config_decode(named);
+    const bool fits = config_fits(named, s);
+    if (ci.family != kFamIgemm && ci.family != kFamSplit && fits && io_fits(ci.family, a, head)) {
+        int ks = 1;
+        if (ci.family == kFamTp2s && force >= 0) {
+            const int steps = c->g.cin / 16;
+            ks = force_ks < 1 ? 1 : (force_ks > steps ? steps : force_ks);
+            ks = ceil_div(steps, ceil_div(steps, ks));   // no empty trailing splits
+        }
+        cfg[0] = named; cfg[1] = ks;
         return W2L_OK;
     }
-    // fused-phase stride-2 transposed kernel: only by explicit configuration id (forced, per-layer override or tune table)
-    if (c->tp2_u != nullptr && c->precision == W2L_PREC_F32 && !head && res == nullptr && !unit && (y_cs & 3) == 0 &&
-        (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
-        (force_tile == conv_tp2_id() || (force_tile < 0 && tile_override == conv_tp2_id()))) {
-        if (cfg_out) { cfg_out[0] = conv_tp2_id(); cfg_out[1] = 1; }
-        return tp2_launch(x, x_cs, y, y_cs, c->tp2_u, c->scale, c->shift, N, H, W, c->g.cin, c->g.cout, c->g.act, stream, flops_out);
+    if (force < 0 && ov < 0 && config_fits(config_id(kFamWino, 0), s) && io_fits(kFamWino, a, head) &&
+        (long long)a.N * ((a.H + 1) / 2) * ((a.W + 1) / 2) / 64 * (c->g.cout / 64) >= 192) {
+        cfg[0] = config_id(kFamWino, 0); cfg[1] = 1;
+        return W2L_OK;
     }
-    // split-operand F(2x2,3x3) Winograd kernel: only by explicit configuration id (forced, per-layer override or tune table)
-    if (c->wino_u != nullptr && c->precision == W2L_PREC_F32 && !head && c->g.act != W2L_ACT_SIGMOID && wino2s_ok(c->g.cin, c->g.cout) &&
-        (x_cs & 3) == 0 && (y_cs & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
-        (res == nullptr || ((res_cs & 3) == 0 && (reinterpret_cast<uintptr_t>(res) & 15) == 0)) &&
-        (force_tile == conv_wino2s_id() || (force_tile < 0 && tile_override == conv_wino2s_id()))) {
-        WinoKArgs wa;
-        wa.x = x; wa.y = y; wa.res = res; wa.u = c->wino_u; wa.scale = c->scale; wa.shift = c->shift;
-        wa.N = N; wa.H = H; wa.W = W; wa.cin = c->g.cin; wa.x_cs = x_cs;
-        wa.cout = c->g.cout; wa.y_cs = y_cs; wa.res_cs = res_cs; wa.act = c->g.act;
-        if (cfg_out) { cfg_out[0] = conv_wino2s_id(); cfg_out[1] = 1; }
-        if (!flops_out) {
-            const int rc = lazy_weights(c->wino2s_u, (size_t)wino2s_u_elems(c->g.cin, c->g.cout), stream, "split-operand F(2x2) weights",
-                                        [&](__bf16* p) { return wino2s_pack(c->wino_u, p, c->g.cin, c->g.cout, stream); });
-            if (rc != W2L_OK) return rc;
-        }
-        return wino2s_launch(wa, c->wino2s_u.load(std::memory_order_acquire), stream, flops_out);
-    }
-    // F(4x4,3x3) Winograd kernel: only by explicit configuration id (forced, per-layer override or tune table)
-    if (c->wino4_u != nullptr && c->precision == W2L_PREC_F32 && !head && c->g.act != W2L_ACT_SIGMOID && (x_cs & 3) == 0 &&
-        (y_cs & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
-        (res == nullptr || ((res_cs & 3) == 0 && (reinterpret_cast<uintptr_t>(res) & 15) == 0)) &&
-        (force_tile == conv_wino4_id() || (force_tile < 0 && tile_override == conv_wino4_id()))) {
-        WinoKArgs wa;
-        wa.x = x; wa.y = y; wa.res = res; wa.u = c->wino4_u; wa.scale = c->scale; wa.shift = c->shift;
-        wa.N = N; wa.H = H; wa.W = W; wa.cin = c->g.cin; wa.x_cs = x_cs;
-        wa.cout = c->g.cout; wa.y_cs = y_cs; wa.res_cs = res_cs; wa.act = c->g.act;
-        if (cfg_out) { cfg_out[0] = conv_wino4_id(); cfg_out[1] = 1; }
-        return wino4_launch(wa, c->wino4_u, stream, flops_out);
-    }
-    // quarter-split F(2x2) kernel (32-cout layers, fused head allowed): only by explicit configuration id
-    if (c->wino_u != nullptr && c->precision == W2L_PREC_F32 && c->g.act != W2L_ACT_SIGMOID && (x_cs & 3) == 0 &&
-        (y_cs & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
-        (res == nullptr || ((res_cs & 3) == 0 && (reinterpret_cast<uintptr_t>(res) & 15) == 0)) &&
-        wino2q_ok(c->g.cin, c->g.cout, c->head_w ? c->head_c : 0) &&
-        (force_tile == conv_wino2q_id() || (force_tile < 0 && tile_override == conv_wino2q_id()))) {
-        WinoKArgs wa;
-        wa.x = x; wa.y = y; wa.res = res; wa.u = c->wino_u; wa.scale = c->scale; wa.shift = c->shift;
-        wa.N = N; wa.H = H; wa.W = W; wa.cin = c->g.cin; wa.x_cs = x_cs;
-        wa.cout = c->g.cout; wa.y_cs = y_cs; wa.res_cs = res_cs; wa.act = c->g.act;
-        if (cfg_out) { cfg_out[0] = conv_wino2q_id(); cfg_out[1] = 1; }
-        return wino2q_launch(wa, c->head_w, c->head_b, c->head_c, c->head_act, stream, flops_out);
-    }
-    {   // Winograd path: forced configuration id, or the heuristic default when the grid fills the chip
-        int wt = -1;
-        // the Winograd epilogue moves float4 rows: y and res must be 16-byte friendly (true for every plan buffer)
-        const bool wino_io_ok = (y_cs & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
-                                (res == nullptr || ((res_cs & 3) == 0 && (reinterpret_cast<uintptr_t>(res) & 15) == 0));
-        if (!wino_io_ok) wt = -2;
-        else if (wino_allowed(c, force_tile, x_cs)) wt = force_tile;
-        else if (force_tile < 0 && wino_allowed(c, tile_override, x_cs)) wt = tile_override;
-        else if (force_tile < 0 && tile_override < 0 && wino_allowed(c, kNumTiles, x_cs) &&
-                 (long long)N * ((H + 1) / 2) * ((W + 1) / 2) / 64 * (c->g.cout / 64) >= 192) wt = kNumTiles;
-        if (wt >= 0) {
-            WinoKArgs wa;
-            wa.x = x; wa.y = y; wa.res = res; wa.u = c->wino_u; wa.scale = c->scale; wa.shift = c->shift;
-            wa.N = N; wa.H = H; wa.W = W; wa.cin = c->g.cin; wa.x_cs = x_cs;
-            wa.cout = c->g.cout; wa.y_cs = y_cs; wa.res_cs = res_cs; wa.act = c->g.act;
-            if (cfg_out) { cfg_out[0] = wt; cfg_out[1] = 1; }
-            if (wt - kNumTiles >= wino_num_cfgs())
-                return wino2_launch(wt - kNumTiles - wino_num_cfgs(), wa, c->head_w, c->head_b, c->head_c, c->head_act, stream,
-                                    flops_out);
-            return wino_launch(wt - kNumTiles, wa, stream, flops_out);
-        }
-    }
-    int ti, ks;
-    pick_config(c, v, a.M, head, &ti, &ks);
-    W2L_REQUIRE(ti >= 0, "fused head: cout=%d does not fit one tile", c->g.cout);
-    if (tile_allowed(v, force_tile, head)) { ti = force_tile; ks = force_ksplit >= 1 ? force_ksplit : 1; }
-    // split-operand kernel: only by explicit configuration id (forced, per-layer override or tune table), fp32 layers only
+    int tile, ks = force_ks >= 1 ? force_ks : 1;
     bool split = false;
-    if (c->precision == W2L_PREC_F32) {
-        const int st = split_tile_of(force_tile >= 0 ? force_tile : tile_override);
-        if (st >= 0 && tile_allowed(v, st, head)) {
-            split = true;
-            ti = st;
-            ks = force_tile >= 0 ? (force_ksplit >= 1 ? force_ksplit : 1) : 1;
-        }
-    }
-    if (head || v.pair > 1) ks = 1;
-    const TileCfg& tc = kTiles[ti];
+    if (ci.family == kFamIgemm && fits && force >= 0) tile = force;
+    else if (ci.family == kFamSplit && fits) { split = true; tile = ci.index; ks = force >= 0 ? ks : 1; }
+    else if (config_decode(ov).family == kFamIgemm && config_fits(ov, s)) { tile = ov; ks = 1; }
+    else pick_config(v, a.M, head, &tile, &ks);
+    W2L_REQUIRE(tile >= 0, "fused head: cout=%d does not fit one tile", c->g.cout);
     const int steps = max_steps(v);
+    if (head || v.pair > 1) ks = 1;
     if (ks > steps) ks = steps;
-    if (ks < 1) ks = 1;
-    a.ksplit = ks;
-    a.steps_per_split = ceil_div(steps, ks);
-    a.ksplit = ceil_div(steps, a.steps_per_split);   // drop empty trailing splits
+    cfg[0] = split ? config_id(kFamSplit, tile) : tile;
+    cfg[1] = ceil_div(steps, ceil_div(steps, ks));   // no empty trailing splits
+    return W2L_OK;
+}
+
+static WinoKArgs wino_args(const w2l_conv* c, const ConvKArgs& a, const float* u) {
+    WinoKArgs wa;
+    wa.x = a.x; wa.y = a.y; wa.res = a.res; wa.u = u; wa.scale = c->scale; wa.shift = c->shift;
+    wa.N = a.N; wa.H = a.H; wa.W = a.W; wa.cin = c->g.cin; wa.x_cs = a.x_cs;
+    wa.cout = c->g.cout; wa.y_cs = a.y_cs; wa.res_cs = a.res_cs; wa.act = c->g.act;
+    return wa;
+}
+
+// y = act( sum of the split-K partial sums ws[ksplit][npix][ws_cs] * scale + shift (+ res) )
+static int splitk_reduce(const w2l_conv* c, const float* ws, int ws_cs, long long npix, int ksplit, float* y, int y_cs,
+                         const float* res, int res_cs, hipStream_t stream) {
+    ReduceArgs r;
+    r.ws = ws; r.y = y; r.res = res; r.scale = c->scale; r.shift = c->shift;
+    r.npix = npix; r.ksplit = ksplit; r.cout = c->g.cout; r.cout_p = ws_cs;
+    r.y_cs = y_cs; r.res_cs = res_cs; r.act = c->g.act;
+    long long g = (npix * c->g.cout + 255) / 256;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, stream, r);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+// the implicit GEMM on tile `ti` with `ksplit` K-ranges (resolve_config drops empty ones), fp32 operands as three bf16 pieces if `split`
+static int igemm_launch(const w2l_conv* c, const Variant& v, ConvKArgs a, int ti, bool split, int ksplit, hipStream_t stream,
+                        long long* flops_out) {
+    const TileCfg& tc = kTiles[ti];
+    const bool unit = &v == &c->unit_in;
+    a.ksplit = ksplit;
+    a.steps_per_split = ceil_div(max_steps(v), ksplit);
     a.ws = nullptr;
-    const long long npix = (long long)N * Ho * Wo;
-    if (cfg_out) { cfg_out[0] = split ? conv_split_id(ti) : ti; cfg_out[1] = a.ksplit; }
+    const long long npix = (long long)a.N * a.Ho * a.Wo;
     if (flops_out) {
         long long kp = 0;
         for (int i = 0; i < v.nphase; ++i) kp += v.ph[i].kp;
@@ -1521,7 +1518,7 @@ int conv_forward_impl(const w2l_conv* c, hipStream_t stream, int N, int H, int W
     if (a.ksplit > 1) {
         a.ws = stream_workspace(stream, (size_t)a.ksplit * npix * v.cout_p * sizeof(float));
         if (!a.ws) return W2L_ERR_NOMEM;
-        if (c->g.transposed && !unit && (Ho % v.omy || Wo % v.omx)) {
+        if (c->g.transposed && !unit && (a.Ho % v.omy || a.Wo % v.omx)) {
             // phases may not cover every output pixel of a ragged transposed conv: start the partials from zero
             W2L_HIP_CHECK(hipMemsetAsync(a.ws, 0, (size_t)a.ksplit * npix * v.cout_p * sizeof(float), stream));
         }
@@ -1538,7 +1535,7 @@ int conv_forward_impl(const w2l_conv* c, hipStream_t stream, int N, int H, int W
         long long wbytes = 0;
         for (int i = 0; i < v.nphase; ++i) wbytes += (long long)v.cout_p * v.ph[i].kp;
         wbytes *= split ? 6 : 4;
-        const long long xbytes = (long long)N * H * W * c->cin_p * 4;
+        const long long xbytes = (long long)a.N * a.H * a.W * c->cin_p * 4;
         a.order = kOrderPhaseMajor;
         a.order_r = 32 / a.tiles_n > 0 ? 32 / a.tiles_n : 1;   // one group's phase = one round of workgroups on an XCD's 32 CUs
         if (c->precision != W2L_PREC_BF16 && !unit) {
@@ -1557,24 +1554,10 @@ int conv_forward_impl(const w2l_conv* c, hipStream_t stream, int N, int H, int W
     }
     if (split) {
         // once per layer: filled and complete before the pointer is seen by a launch on any other stream
-        const int rc = lazy_weights(v.w_split, 3 * (size_t)v.w_floats, stream, "split-operand weights", [&](__bf16* p) {
-            SplitWArgs sa;
-            sa.w = v.w_dev; sa.out = p; sa.nphase = v.nphase;
-            long long maxtot = 1;
-            for (int i = 0; i < v.nphase; ++i) {
-                sa.off[i] = v.ph[i].w_off;
-                sa.count[i] = (long long)v.cout_p * v.ph[i].kp;
-                if (sa.count[i] > maxtot) maxtot = sa.count[i];
-            }
-            int blocks = (int)((maxtot + 255) / 256);
-            if (blocks > 4096) blocks = 4096;
-            hipLaunchKernelGGL(split_weights_kernel, dim3(blocks, v.nphase), dim3(256), 0, stream, sa);
-            W2L_HIP_CHECK(hipGetLastError());
-            v.split_fresh = true;
-            return W2L_OK;
-        });
+        const int rc = lazy_weights(v.w_split, 3 * sizeof(__bf16) * (size_t)v.w_floats, stream, "split-operand weights",
+                                    [&](__bf16* p) { return split_weights(v, p, stream); });
         if (rc != W2L_OK) return rc;
-        if (!v.split_fresh && split_variant(v, stream) != W2L_OK) return W2L_ERR_HIP;
+        if (!v.split_fresh && split_weights(v, v.w_split.load(std::memory_order_acquire), stream) != W2L_OK) return W2L_ERR_HIP;
         a.wsplit = v.w_split.load(std::memory_order_acquire);
     }
     if (split)
@@ -1584,31 +1567,109 @@ int conv_forward_impl(const w2l_conv* c, hipStream_t stream, int N, int H, int W
     else
         hipLaunchKernelGGL(tc.kernel, dim3((unsigned)nblk, v.nphase, a.ksplit), dim3(256), tc.lds, stream, a);
     W2L_HIP_CHECK(hipGetLastError());
-    if (a.ksplit > 1) {
-        ReduceArgs r;
-        r.ws = a.ws; r.y = y; r.res = res; r.scale = c->scale; r.shift = c->shift;
-        r.npix = npix; r.ksplit = a.ksplit; r.cout = c->g.cout; r.cout_p = v.cout_p;
-        r.y_cs = y_cs; r.res_cs = res_cs; r.act = c->g.act;
-        long long g = (npix * c->g.cout + 255) / 256;
-        if (g > 4096) g = 4096;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, stream, r);
-        W2L_HIP_CHECK(hipGetLastError());
-    }
-    return W2L_OK;
+    return a.ksplit > 1 ? splitk_reduce(c, a.ws, v.cout_p, npix, a.ksplit, a.y, a.y_cs, a.res, a.res_cs, stream) : W2L_OK;
 }
 
-// + conv_tp2.hip, conv_wino4.hip, wino2q, then the kNumTiles split-operand ids (appended: the ids of every earlier family keep
-// their values, so committed tune tables stay valid)
-int conv_num_tiles() { return kNumTiles + wino_num_cfgs() + wino2_num_cfgs() + 3 + kNumTiles + 4; }
-int conv_wino2s_id() { return conv_split_id(kNumTiles); }   // appended after the split ids: every earlier id keeps its meaning (committed tables)
-int conv_tp2s_id() { return conv_split_id(kNumTiles) + 1; }
-int conv_stem7s_id() { return conv_split_id(kNumTiles) + 2; }
-int conv_k3s_id() { return conv_split_id(kNumTiles) + 3; }   // appended last
-int conv_split_id(int tile) { return kNumTiles + wino_num_cfgs() + wino2_num_cfgs() + 3 + tile; }
-int conv_tp2_id() { return kNumTiles + wino_num_cfgs() + wino2_num_cfgs(); }
-int conv_wino4_id() { return conv_tp2_id() + 1; }
-int conv_wino2q_id() { return conv_tp2_id() + 2; }
-int conv_num_igemm_tiles() { return kNumTiles; }
+// Run the resolved configuration cfg = (id, split-K), or with flops_out != NULL report the multiply-add work the matrix cores would
+// EXECUTE (padded tiles, padded K, Winograd's 16 products per 2x2 tile; x2 = FLOPs) and launch nothing
+static int launch_config(const w2l_conv* c, const Variant& v, const ConvKArgs& a, const int cfg[2], hipStream_t stream,
+                         long long* flops_out) {
+    const ConfigId ci = config_decode(cfg[0]);
+    const w2l_conv_geom& g = c->g;
+    switch (ci.family) {
+    case kFamK3s:
+        return k3s_launch(a.x, a.x_cs, a.y, a.y_cs, a.res, a.res_cs, form_of<__bf16>(c, kFormK3s), c->scale, c->shift, c->head_w,
+                          c->head_b, c->head_c, c->head_act, a.N, a.H, a.W, g.cin, g.act, stream, flops_out);
+    case kFamStem7s:
+        return stem7s_launch(a.x, a.x_cs, a.y, a.y_cs, form_of<__bf16>(c, kFormStem7s), c->scale, c->shift, a.N, a.H, a.W, g.act, stream,
+                             flops_out);
+    case kFamTp2:
+        return tp2_launch(a.x, a.x_cs, a.y, a.y_cs, form_of<float>(c, kFormTp2), c->scale, c->shift, a.N, a.H, a.W, g.cin, g.cout,
+                          g.act, stream, flops_out);
+    case kFamTp2s: {
+        const long long npix = (long long)a.N * 4 * a.H * a.W;
+        float* ws = nullptr;
+        if (!flops_out) {
+            const int rc = lazy_form(c, kFormTp2s, stream);
+            if (rc != W2L_OK) return rc;
+            if (cfg[1] > 1 && !(ws = stream_workspace(stream, (size_t)cfg[1] * npix * g.cout * sizeof(float)))) return W2L_ERR_NOMEM;
+        }
+        int used = 1;
+        const int rc = tp2s_launch(a.x, a.x_cs, a.y, a.y_cs, form_of<__bf16>(c, kFormTp2s), c->scale, c->shift, a.N, a.H, a.W, g.cin,
+                                   g.cout, g.act, cfg[1], ws, &used, stream, flops_out);
+        if (rc != W2L_OK || flops_out || used == 1) return rc;
+        return splitk_reduce(c, ws, g.cout, npix, used, a.y, a.y_cs, nullptr, 0, stream);
+    }
+    case kFamWino2s:
+        if (!flops_out) {
+            const int rc = lazy_form(c, kFormWino2s, stream);
+            if (rc != W2L_OK) return rc;
+        }
+        return wino2s_launch(wino_args(c, a, form_of<float>(c, kFormWino)), form_of<__bf16>(c, kFormWino2s), stream, flops_out);
+    case kFamWino4:
+        return wino4_launch(wino_args(c, a, form_of<float>(c, kFormWino4)), form_of<float>(c, kFormWino4), stream, flops_out);
+    case kFamWino:
+        return wino_launch(ci.index, wino_args(c, a, form_of<float>(c, kFormWino)), stream, flops_out);
+    case kFamWino2:
+        if (ci.index < kNumWino2Cfgs)
+            return wino2_launch(ci.index, wino_args(c, a, form_of<float>(c, kFormWino)), c->head_w, c->head_b, c->head_c, c->head_act,
+                                stream, flops_out);
+        return wino2q_launch(wino_args(c, a, form_of<float>(c, kFormWino)), c->head_w, c->head_b, c->head_c, c->head_act, stream,
+                             flops_out);
+    }
+    return igemm_launch(c, v, a, ci.index, ci.family == kFamSplit, cfg[1], stream, flops_out);
+}
+
+int conv_forward_impl(const w2l_conv* c, hipStream_t stream, int N, int H, int W, const float* x,
+                      int x_cs, float* y, int y_cs, const float* res, int res_cs, int force_tile, int force_ksplit,
+                      long long* flops_out, int* cfg_out) {
+    W2L_REQUIRE(c && x && y, "NULL argument");
+    W2L_REQUIRE(N >= 1 && H >= 1 && W >= 1, "bad shape N=%d H=%d W=%d", N, H, W);
+    W2L_REQUIRE(x_cs >= c->cin_p && (x_cs & 3) == 0, "x_cs=%d must be a multiple of 4 and >= %d", x_cs, c->cin_p);
+    W2L_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0, "x must be 16-byte aligned");
+    W2L_REQUIRE(c->head_w != nullptr || y_cs >= c->g.cout, "y_cs=%d < cout=%d", y_cs, c->g.cout);
+    W2L_REQUIRE(res == nullptr || res_cs >= c->g.cout, "res_cs=%d < cout", res_cs);
+    int Ho, Wo;
+    if (w2l_conv_out_hw(&c->g, H, W, &Ho, &Wo) != W2L_OK) return W2L_ERR_ARG;
+    W2L_REQUIRE(Ho >= 1 && Wo >= 1, "empty output %dx%d", Ho, Wo);
+    const bool unit = c->g.transposed && c->g.sh == 1 && c->g.sw == 1 && H == 1 && W == 1 && c->unit_in.built;
+    const bool head = c->head_w != nullptr;
+    W2L_REQUIRE(!head || (y_cs >= c->head_c && res == nullptr), "fused head: y_cs=%d < %d or residual given", y_cs, c->head_c);
+    const bool y_vec_ok = (c->g.cout & 3) == 0 && io16(y, y_cs);
+    const bool xp = c->xpair.built && !head && res == nullptr && (Wo % 2) == 0 && y_vec_ok;
+    const Variant& v = unit ? c->unit_in : (xp ? c->xpair : c->generic);
+    ConvKArgs a;
+    a.x = x; a.y = y; a.res = res; a.w = v.w_dev; a.wsplit = v.w_split.load(std::memory_order_acquire); a.scale = c->scale; a.shift = c->shift; a.taps = v.taps_dev;
+    a.N = N; a.H = H; a.W = W; a.cin_p = c->cin_p; a.x_cs = x_cs;
+    a.Ho = Ho; a.Wo = Wo; a.cout = c->g.cout; a.cout_p = v.cout_p; a.y_cs = y_cs; a.res_cs = res_cs;
+    a.pair = v.pair; a.ncols = v.pair * c->g.cout;
+    a.head_w = c->head_w; a.head_b = c->head_b; a.head_c = c->head_c; a.head_act = c->head_act;
+    if (unit) { a.Hq = 1; a.Wq = 1; }
+    else if (v.q_is_out) { a.Hq = Ho; a.Wq = Wo; }
+    else { a.Hq = ceil_div(Ho, v.omy); a.Wq = ceil_div(Wo, v.omx); }
+    a.sy = v.sy; a.sx = v.sx; a.omy = v.omy; a.omx = v.omx;
+    a.act = c->g.act;
+    // float4 epilogue needs 16-byte aligned rows on y / res / scale / shift
+    a.vec_epilogue = (y_vec_ok && (res == nullptr || io16(res, res_cs))) ? 1 : 0;
+    const long long lim = 1ll << 31;  // buffer descriptors use 32-bit byte offsets with 0x80000000 as "out of range"
+    W2L_REQUIRE(((long long)N * H * W * x_cs) * 4 < lim && ((long long)N * Ho * Wo * y_cs) * 4 < lim &&
+                    (res == nullptr || ((long long)N * Ho * Wo * res_cs) * 4 < lim),
+                "activation buffer larger than 2 GiB: split the batch");
+    const long long M = (long long)N * a.Hq * a.Wq;
+    W2L_REQUIRE(M < (1ll << 31) && (long long)N * H * W < (1ll << 31) && (long long)N * Ho * Wo < (1ll << 31), "tensor too large");
+    a.M = (int)M;
+    for (int i = 0; i < v.nphase; ++i) a.ph[i] = v.ph[i];
+    int cfg[2];
+    if (resolve_config(c, v, a, force_tile, force_ksplit, cfg) != W2L_OK) return W2L_ERR_ARG;
+    if (cfg_out) { cfg_out[0] = cfg[0]; cfg_out[1] = cfg[1]; }
+    if (!flops_out && flops_counting()) {   // w2l_flops_begin: price this launch as a dry run and book its work
+        long long f = 0;
+        if (launch_config(c, v, a, cfg, stream, &f) == W2L_OK)
+            // 3: bf16 matrix-core work - the bf16c precision and every family on the bf16 pipe (kIdList)
+            flops_add(f, (c->precision == W2L_PREC_BF16 || config_decode(cfg[0]).bf16_pipe) ? 3 : 0);
+    }
+    return launch_config(c, v, a, cfg, stream, flops_out);
+}
 
 static int init_kernel_attrs() {
     static std::mutex m;
@@ -1692,59 +1753,20 @@ int w2l_conv_create(const w2l_conv_geom* g, const float* weight, const float* sc
             break;
         }
         rc = build_variant(c, c->generic, kGeneric, s);
-        if (rc != W2L_OK) break;
-        if (g->transposed && g->sh == 1 && g->sw == 1 && g->kh * g->kw <= kMaxPhases)
+        if (rc == W2L_OK && g->transposed && g->sh == 1 && g->sw == 1 && g->kh * g->kw <= kMaxPhases)
             rc = build_variant(c, c->unit_in, kUnitInput, s);
-        if (rc != W2L_OK) break;
-        // 3x3 / stride 1 / pad 1: Winograd; the transposed form (the data gradient of such a conv) is the same conv with the
-        // kernel flipped and the channel roles swapped, which only changes how the weight tensor is read by the packer
-        if (g->kh == 3 && g->kw == 3 && g->sh == 1 && g->sw == 1 && g->ph == 1 && g->pw == 1 && g->oph == 0 && g->opw == 0 &&
-            (wino_cfg_ok(0, g->cin, g->cout) || wino_cfg_ok(1, g->cin, g->cout) || wino2_ok(0, g->cin, g->cout, 0) ||
-             wino2_ok(1, g->cin, g->cout, 0))) {
-            if (hipMalloc(&c->wino_u, sizeof(float) * wino_u_floats(g->cin, g->cout)) != hipSuccess) {
-                set_error("hipMalloc(winograd weights) failed");
-                rc = W2L_ERR_NOMEM;
-                break;
-            }
-            rc = wino_pack(weight, c->wino_u, g->cin, g->cout, g->transposed, s);
-            if (rc != W2L_OK) break;
-        }
-        if (g->kh == 3 && g->kw == 3 && g->sh == 1 && g->sw == 1 && g->ph == 1 && g->pw == 1 && g->oph == 0 && g->opw == 0 &&
-            c->precision == W2L_PREC_F32 && wino4_ok(g->cin, g->cout)) {
-            if (hipMalloc(&c->wino4_u, sizeof(float) * wino4_u_floats(g->cin, g->cout)) != hipSuccess) {
-                set_error("hipMalloc(F(4x4) winograd weights) failed");
-                rc = W2L_ERR_NOMEM;
-                break;
-            }
-            rc = wino4_pack(weight, c->wino4_u, g->cin, g->cout, g->transposed, s);
-            if (rc != W2L_OK) break;
-        }
-        if (!g->transposed && g->sw == 1 && g->cout <= 16 && (g->cout & 3) == 0 && g->kh * (g->kw + 1) <= 64)
+        if (rc == W2L_OK && !g->transposed && g->sw == 1 && g->cout <= 16 && (g->cout & 3) == 0 && g->kh * (g->kw + 1) <= 64)
             rc = build_variant(c, c->xpair, kXPair, s);
-        if (rc != W2L_OK) break;
-        if (tp2_ok(*g)) {
-            if (hipMalloc(&c->tp2_u, sizeof(float) * tp2_u_floats(g->cin, g->cout)) != hipSuccess) {
-                set_error("hipMalloc(transposed-conv fragment weights) failed");
+        for (int f = 0; f < kNumForms && rc == W2L_OK; ++f) {
+            if (!needs_form(f, *g)) continue;   // (lazy forms: built by the first launch that reads them)
+            void* p = nullptr;
+            if (hipMalloc(&p, kForms[f].bytes(*g)) != hipSuccess) {
+                set_error("hipMalloc(%s) failed", kForms[f].what);
                 rc = W2L_ERR_NOMEM;
                 break;
             }
-            rc = tp2_pack(weight, c->tp2_u, g->cin, g->cout, s);
-        }
-        if (rc == W2L_OK && stem7s_ok(*g)) {
-            if (hipMalloc(&c->stem7s_u, sizeof(__bf16) * stem7s_u_elems()) != hipSuccess) {
-                set_error("hipMalloc(first-layer split weights) failed");
-                rc = W2L_ERR_NOMEM;
-                break;
-            }
-            rc = stem7s_pack(weight, c->stem7s_u, g->cin, s);
-        }
-        if (rc == W2L_OK && k3s_ok(*g)) {
-            if (hipMalloc(&c->k3s_u, sizeof(__bf16) * k3s_u_elems(g->cin)) != hipSuccess) {
-                set_error("hipMalloc(direct 3x3 split weights) failed");
-                rc = W2L_ERR_NOMEM;
-                break;
-            }
-            rc = k3s_pack(weight, c->k3s_u, g->cin, s);
+            c->form[f] = p;
+            rc = kForms[f].pack(*g, weight, p, s);
         }
     } while (0);
     // the packer reads the caller's weight tensor: finish before handing control back
@@ -1761,32 +1783,22 @@ int w2l_conv_update(w2l_conv_t* c, const float* weight, const float* scale, cons
     if (scale) W2L_HIP_CHECK(hipMemcpyAsync(c->scale, scale, sizeof(float) * c->g.cout, hipMemcpyDeviceToDevice, s));
     if (shift) W2L_HIP_CHECK(hipMemcpyAsync(c->shift, shift, sizeof(float) * c->g.cout, hipMemcpyDeviceToDevice, s));
     if (weight) {
-        Variant* vs[3] = {&c->generic, &c->unit_in, &c->xpair};
-        for (Variant* v : vs)
+        for (const Variant* v : {&c->generic, &c->unit_in, &c->xpair})
             if (v->built && pack_variant(c, *v, weight, s) != W2L_OK) return W2L_ERR_HIP;
-        if (c->wino_u && wino_pack(weight, c->wino_u, c->g.cin, c->g.cout, c->g.transposed, s) != W2L_OK) return W2L_ERR_HIP;
-        if (c->tp2_u && tp2_pack(weight, c->tp2_u, c->g.cin, c->g.cout, s) != W2L_OK) return W2L_ERR_HIP;
-        if (c->wino4_u && wino4_pack(weight, c->wino4_u, c->g.cin, c->g.cout, c->g.transposed, s) != W2L_OK) return W2L_ERR_HIP;
-        if (c->wino2s_u.load() && wino2s_pack(c->wino_u, c->wino2s_u.load(), c->g.cin, c->g.cout, s) != W2L_OK) return W2L_ERR_HIP;
-        if (c->tp2s_u.load() && tp2s_pack(c->tp2_u, c->tp2s_u.load(), c->g.cin, c->g.cout, s) != W2L_OK) return W2L_ERR_HIP;
-        if (c->stem7s_u && stem7s_pack(weight, c->stem7s_u, c->g.cin, s) != W2L_OK) return W2L_ERR_HIP;
-        if (c->k3s_u && k3s_pack(weight, c->k3s_u, c->g.cin, s) != W2L_OK) return W2L_ERR_HIP;
+        for (int f = 0; f < kNumForms; ++f) {   // a lazy form after the form it is split from
+            void* const u = c->form[f].load(std::memory_order_acquire);
+            const float* src = kForms[f].source < 0 ? weight : form_of<float>(c, kForms[f].source);
+            if (u && kForms[f].pack(c->g, src, u, s) != W2L_OK) return W2L_ERR_HIP;
+        }
     }
     return W2L_OK;
 }
 
 int w2l_conv_destroy(w2l_conv_t* c) {
     if (!c) return W2L_OK;
-    free_variant(c->generic);
-    free_variant(c->unit_in);
-    free_variant(c->xpair);
-    if (c->wino_u) (void)hipFree(c->wino_u);
-    if (c->tp2_u) (void)hipFree(c->tp2_u);
-    if (c->wino4_u) (void)hipFree(c->wino4_u);
-    if (c->wino2s_u.load()) (void)hipFree(c->wino2s_u.load());
-    if (c->tp2s_u.load()) (void)hipFree(c->tp2s_u.load());
-    if (c->stem7s_u) (void)hipFree(c->stem7s_u);
-    if (c->k3s_u) (void)hipFree(c->k3s_u);
+    for (Variant* v : {&c->generic, &c->unit_in, &c->xpair}) free_variant(*v);
+    for (auto& u : c->form)
+        if (u.load()) (void)hipFree(u.load());
     if (c->head_w) (void)hipFree(c->head_w);
     if (c->head_b) (void)hipFree(c->head_b);
     if (c->scale) (void)hipFree(c->scale);
@@ -1846,37 +1858,16 @@ int w2l_tune_set(const int* key, int tile, int ksplit) {
     return W2L_OK;
 }
 
-// Can configuration id `tile` run a launch with this key at all?  Pure host arithmetic on the key - the same predicates
-// w2l_conv_create / conv_forward_impl apply to a live handle: an id that fails here would silently fall through to the
-// heuristic at launch time, so a table entry carrying it misdescribes what runs (tools/make_tune_table.py and the CPU table
-// test reject such entries).
+// Can configuration id `tile` run a launch with this key at all?  config_fits, the launcher's own shape rule, on the key (which
+// carries no activation): an id that fails here would silently fall through to the next rule at launch time, so a table entry
+// carrying it misdescribes what runs (tools/make_tune_table.py and the CPU table test reject such entries).
 int w2l_tune_entry_applicable(const int* key, int tile) {
     W2L_REQUIRE(key, "NULL key");
-    if (tile < 0 || tile >= conv_num_tiles()) return 0;
-    w2l_conv_geom g;
-    g.transposed = key[0]; g.cin = key[1]; g.cout = key[2]; g.kh = key[3]; g.kw = key[4]; g.sh = key[5]; g.sw = key[6];
-    g.ph = key[7]; g.pw = key[8]; g.oph = key[9]; g.opw = key[10]; g.act = W2L_ACT_NONE;
-    const int prec = key[11], has_res = key[12], head_c = key[13];
-    if (tile < kNumTiles) return (head_c == 0 || kTiles[tile].bn >= round_up(g.cout, 32)) ? 1 : 0;
-    if (prec != W2L_PREC_F32) return 0;                       // every other family is fp32-only
-    if (split_tile_of(tile) >= 0) return (head_c == 0 || kTiles[split_tile_of(tile)].bn >= round_up(g.cout, 32)) ? 1 : 0;
-    if (tile == conv_tp2_id()) return (tp2_ok(g) && head_c == 0 && !has_res) ? 1 : 0;
-    if (tile == conv_tp2s_id()) return (tp2s_ok(g) && head_c == 0 && !has_res) ? 1 : 0;
-    if (tile == conv_stem7s_id()) return (stem7s_ok(g) && head_c == 0 && !has_res) ? 1 : 0;
-    if (tile == conv_k3s_id()) return (k3s_ok(g) && head_c <= 4) ? 1 : 0;
-    if (tile == conv_wino2s_id())
-        return (g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1 && g.oph == 0 && g.opw == 0 &&
-                wino2s_ok(g.cin, g.cout) && head_c == 0) ? 1 : 0;
-    const bool k3 = g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1 && g.oph == 0 && g.opw == 0;
-    if (!k3) return 0;
-    const bool has_u = wino_cfg_ok(0, g.cin, g.cout) || wino_cfg_ok(1, g.cin, g.cout) || wino2_ok(0, g.cin, g.cout, 0) ||
-                       wino2_ok(1, g.cin, g.cout, 0);        // w2l_conv_create packs the F(2x2) weights only then
-    if (tile == conv_wino4_id()) return (wino4_ok(g.cin, g.cout) && head_c == 0) ? 1 : 0;
-    if (tile == conv_wino2q_id()) return (has_u && wino2q_ok(g.cin, g.cout, head_c)) ? 1 : 0;
-    const int wc = tile - kNumTiles;
-    if (wc < wino_num_cfgs()) return (has_u && head_c == 0 && wino_cfg_ok(wc, g.cin, g.cout)) ? 1 : 0;
-    return (has_u && wino2_ok(wc - wino_num_cfgs(), g.cin, g.cout, head_c)) ? 1 : 0;
+    const w2l_conv_geom g{key[0], key[1], key[2], key[3], key[4], key[5], key[6], key[7], key[8], key[9], key[10], W2L_ACT_NONE};
+    return config_fits(tile, ConvShape{g, key[11], key[12], key[13]}) ? 1 : 0;
 }
+
+int w2l_conv_config_family(int id) { return config_decode(id).family; }
 
 int w2l_tune_clear(void) {
     std::lock_guard<std::mutex> lock(g_tune_mutex);

@@ -300,7 +300,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino_f32_kernel(const WinoKArgs a
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 // none / ReLU / LeakyReLU(0.01) without a branch per element: max(x,0) + slope * min(x,0) is exact for all three
-                // (one of the two terms is zero); sigmoid layers never come here (wino_allowed, conv_igemm.hip)
+                // (one of the two terms is zero); sigmoid layers never come here (config_fits, conv_igemm.hip)
                 const float x = c[e] + rv[i][e];
                 v[e] = fmaf(neg_slope, fminf(x, 0.f), fmaxf(x, 0.f));
             }
@@ -370,7 +370,7 @@ static const WinoCfg kWino[] = {
 };
 constexpr int kNumWino = sizeof(kWino) / sizeof(kWino[0]);
 
-int wino_num_cfgs() { return kNumWino; }
+static_assert(kNumWino == kNumWinoCfgs, "configuration ids count kNumWinoCfgs F(2x2) configurations");
 
 int wino_init_attrs() {   // called under the lock of init_kernel_attrs (conv_igemm.hip)
     static bool done = false;

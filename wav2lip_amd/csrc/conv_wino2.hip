@@ -771,7 +771,7 @@ static const W2Cfg kW2Cfgs[] = {
 };
 constexpr int kNumW2 = sizeof(kW2Cfgs) / sizeof(kW2Cfgs[0]);
 
-int wino2_num_cfgs() { return kNumW2; }
+static_assert(kNumW2 == kNumWino2Cfgs, "configuration ids count kNumWino2Cfgs configurations of the second form");
 
 // head_c > 0: the layer carries a fused 1x1 head (only the 32-cout shape implements it, and only with all couts in one tile)
 bool wino2_ok(int cfg, int cin, int cout, int head_c) {

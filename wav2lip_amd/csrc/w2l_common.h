@@ -173,14 +173,14 @@ struct WinoKArgs {
     int m_fastest;       // conv_wino.hip only: work items run M-tile fastest (weight-heavy layers), else cout-tile fastest
 };
 
-int wino_num_cfgs();
+constexpr int kNumWinoCfgs = 2;    // configurations of conv_wino.hip (kWino); configuration ids: kIdList in conv_igemm.hip
 int wino_init_attrs();
 bool wino_cfg_ok(int cfg, int cin, int cout);
 long long wino_u_floats(int cin, int cout);
 int wino_pack(const float* w, float* u, int cin, int cout, int transposed, hipStream_t stream);
 int wino_launch(int cfg, WinoKArgs a, hipStream_t stream, long long* flops_out);
-// second-generation kernel (conv_wino2.hip): configuration ids wino_num_cfgs() + [0, wino2_num_cfgs()) of the Winograd family
-int wino2_num_cfgs();
+// second-generation kernel (conv_wino2.hip)
+constexpr int kNumWino2Cfgs = 2;   // its configurations (kW2Cfgs)
 bool wino2_ok(int cfg, int cin, int cout, int head_c);
 int wino2_init_attrs();
 int wino2_launch(int cfg, const WinoKArgs& a, const float* head_w, const float* head_b, int head_c, int head_act,
@@ -200,8 +200,8 @@ int wino4_pack(const float* w, float* u, int cin, int cout, int transposed, hipS
 int wino4_init_attrs();
 int wino4_launch(const WinoKArgs& a, const float* u4, hipStream_t stream, long long* flops_out);
 
-// split-operand F(2x2,3x3) Winograd kernel (conv_wino2s.hip): fp32 result from the bf16 matrix cores; the LAST configuration id
-// (behind the split-operand implicit-GEMM ids); its own pre-split 16-position weight transform, split from the F(2x2) fp32 weights on first use
+// split-operand F(2x2,3x3) Winograd kernel (conv_wino2s.hip): fp32 result from the bf16 matrix cores; its own pre-split
+// 16-position weight transform, split from the F(2x2) fp32 weights on first use
 bool wino2s_ok(int cin, int cout);
 long long wino2s_u_elems(int cin, int cout);
 int wino2s_pack(const float* wino_u32, __bf16* u, int cin, int cout, hipStream_t stream);   // from wino_pack's fp32 U

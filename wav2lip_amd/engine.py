@@ -374,9 +374,8 @@ class Plan:
         fl = (C.c_longlong * n)()
         cfg = (C.c_int * (2 * n))()
         check(self._lib.w2l_plan_executed_flops(self.handle, fl, cfg), "plan_executed_flops")
-        fam = {0: "igemm", 1: "wino", 2: "wino2", 3: "tp2", 4: "wino4", 5: "split", 6: "wino2s", 7: "tp2s", 8: "stem7s", 9: "k3s",
-               -1: "convb"}     # -1: a bf16-storage launch (configured by its shape)
-        return [(self.records[i][0], int(fl[i]), fam[self._lib.w2l_conv_config_family(int(cfg[2 * i]))],
+        fam = [self._lib.w2l_conv_config_family(int(cfg[2 * i])) for i in range(n)]
+        return [(self.records[i][0], int(fl[i]), _lib.FAMILY_NAMES[fam[i]] if fam[i] >= 0 else "convb",   # -1: a bf16-storage launch
                  (int(cfg[2 * i]), int(cfg[2 * i + 1]))) for i in range(n)]
 
     def __del__(self):
