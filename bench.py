@@ -10,16 +10,19 @@ inference.main run.  Successive batches alternate between `--pipeline` (default 
 low-occupancy layers of one batch (deep encoder / early decoder levels) overlap the chip-filling layers of the other — what a
 serving loop does; every batch is still a full 128-frame pass and K steps are K batches.  `--pipeline 1` is strictly serial.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 128] [--no-cpu-baseline] [--profile-layers] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 128] [--full] [--profile-layers] [--dump-outputs DIR]
         (N > 1 without WORLD_SIZE in the environment: re-executes itself as N ranks under torch.distributed.run, free port)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (bound = fp32 MFMA, 157.3 TFLOP/s dense;
 achieved = FLOPs the matrix cores EXECUTE per step - Winograd layers at 16 (F(2x2)) or 9 (F(4x4)) instead of 36 products per 2x2 outputs, padded
-tiles included - over the HIP-event time of the timed region, so frac <= 1; the nominal direct-convolution rate and the
-dominant kernel's own fraction are reported beside it) and, at N == 1, `cpu_baseline` (the reference's CPU path timed on the
-host cores on a bounded sample) and `parity` (the timed path's last batch checked against that CPU forward).
+tiles included - over the HIP-event time of the timed region, so frac <= 1; the nominal direct-convolution rate is reported beside it).
+A plain run does only what that line's headline needs: setup, the W warm-up steps, the timed windows of K steps, the
+--dump-outputs arrays and the line.  `--full` adds everything measured beside it, each after the timed windows: the sustained
+window with its shader-clock samples, the dominant kernel's own fraction (a serial per-launch pass), and at N == 1 the extra
+rates (mel + copy to host, one batch in flight, --exact), `cpu_baseline` (the reference's CPU path timed on the host cores on a
+bounded sample), `parity` (the timed path's last batch checked against that CPU forward) and the training configs.
 Launch configurations are the committed tune table + heuristic (bit-reproducible); `--autotune` opts into stopwatch tuning.
 """
 import argparse
@@ -49,18 +52,23 @@ def parse():
     ap.add_argument("--windows", type=int, default=5, help="the timed region of exactly --steps steps is repeated this many "
                     "times (each bracketed by barrier + synchronize) and the MEDIAN window is reported, with min / max beside it")
     ap.add_argument("--batch", type=int, default=128, help="frames per GPU per step (BASELINE config: 128)")
-    ap.add_argument("--sustained-seconds", type=float, default=2.5, help="after the --windows timed regions, ONE more timed region of "
-                    "as many steps as fill this many seconds of GPU time (same fences, max over ranks) with the shader-clock probe "
-                    "running across all of it: `windows.sustained_value` - the steady-state rate of a long clip; 0 = skip")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=14.0, help="target CPU time of the cpu_baseline sample")
+    ap.add_argument("--full", action="store_true", help="after the timed windows also measure and check everything beside the "
+                    "headline figure: the sustained window, the dominant kernel, and at N == 1 the extra rates, cpu_baseline, "
+                    "parity and the training configs (off by default: a plain run times the steps and prints the line)")
+    ap.add_argument("--sustained-seconds", type=float, default=2.5, help="(--full) after the --windows timed regions, ONE more timed "
+                    "region of as many steps as fill this many seconds of GPU time (same fences, max over ranks) with the shader-clock "
+                    "probe running across all of it: `windows.sustained_value` - the steady-state rate of a long clip; 0 = the "
+                    "--steps steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the extra rates, cpu_baseline, parity and the "
+                    "training configs")
+    ap.add_argument("--cpu-seconds", type=float, default=14.0, help="(--full) target CPU time of the cpu_baseline sample")
     ap.add_argument("--autotune", action="store_true", help="opt into stopwatch tuning of the launch configurations (default: "
                     "the committed shape-keyed tune table + heuristic, bit-reproducible); recorded in config.launch_configs")
     ap.add_argument("--tune-cache", default=None, help="JSON file of launch configurations: loaded if it exists, else "
                     "written after --autotune (A/B runs and rocprof passes of one session share one set of choices)")
     ap.add_argument("--profile-layers", action="store_true", help="print per-launch HIP-event times to stderr")
-    ap.add_argument("--no-train-configs", action="store_true", help="skip the BASELINE configs 3/4 training-step timings that are "
-                    "appended (N = 1 only) as `other_configs` from a tools/train_bench.py subprocess")
+    ap.add_argument("--no-train-configs", action="store_true", help="(--full) skip the BASELINE configs 3/4 training-step timings "
+                    "that are appended (N = 1 only) as `other_configs` from a tools/train_bench.py subprocess")
     ap.add_argument("--pipeline", type=int, default=4, help="batches in flight per GPU: successive 128-frame batches alternate "
                     "between this many (buffer set, stream) pairs, so the low-occupancy layers of one batch overlap the heavy "
                     "layers of the other, as in a serving loop; 1 = strictly one batch at a time")
@@ -543,33 +551,49 @@ def main():
     # every `probe_every` steps.  (A probe that spins through the whole window was measured first, profiles/r04/b_*: its one wave
     # keeps a CU from taking a 512-thread workgroup that needs every register of the CU, the persistent kernels then run their
     # last workgroup alone, and the window read 14.0k frames/s instead of 24.6k.  Sampled, the probes hold one CU for ~2 % of the
-    # window.)  EVERY rank runs the window (its steps contain the all-gather); rank 0 alone launches the probes.
+    # window.)  EVERY rank runs the window (its steps contain the all-gather); rank 0 alone launches the probes.  --full only.
     clock_mhz, sustained = None, None
-    sust_steps = int(np.ceil(args.sustained_seconds * 1e3 / max(1e-3, sorted(gpu_ms)[len(gpu_ms) // 2]))) if args.sustained_seconds > 0 else 0
-    sust_steps = max(args.steps, sust_steps) if sust_steps else args.steps
-    if dist is not None:                                    # the same step count on every rank
-        t = torch.tensor([sust_steps], device=dev, dtype=torch.int64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        sust_steps = int(t.item())
-    probe_every = max(4, sust_steps // 24)
-    nprobe = (sust_steps + probe_every - 1) // probe_every if rank == 0 else 0
-    probe_stream = torch.cuda.Stream(device=dev) if rank == 0 else None
-    ticks = torch.zeros((max(1, nprobe), 2), dtype=torch.int64, device=dev)
-    fence()
-    t0 = time.perf_counter()
-    done = 0
-    while done < sust_steps:
+    if args.full:
+        sust_steps = (int(np.ceil(args.sustained_seconds * 1e3 / max(1e-3, sorted(gpu_ms)[len(gpu_ms) // 2])))
+                      if args.sustained_seconds > 0 else 0)
+        sust_steps = max(args.steps, sust_steps) if sust_steps else args.steps
+        if dist is not None:                                    # the same step count on every rank
+            t = torch.tensor([sust_steps], device=dev, dtype=torch.int64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            sust_steps = int(t.item())
+        probe_every = max(4, sust_steps // 24)
+        nprobe = (sust_steps + probe_every - 1) // probe_every if rank == 0 else 0
+        probe_stream = torch.cuda.Stream(device=dev) if rank == 0 else None
+        ticks = torch.zeros((max(1, nprobe), 2), dtype=torch.int64, device=dev)
+        fence()
+        t0 = time.perf_counter()
+        done = 0
+        while done < sust_steps:
+            if rank == 0:
+                # behind the newest enqueued step: the host runs ahead of the GPU, an unordered probe stream would take all its
+                # samples in the first milliseconds of the window
+                probe_stream.wait_stream(streams[(counter[0] - 1) % depth])
+                with torch.cuda.stream(probe_stream):
+                    check(lib.w2l_clock_probe(current_stream(), 2000, ptr(ticks[done // probe_every])), "clock_probe")
+            n = min(probe_every, sust_steps - done)
+            run_steps(n)
+            done += n
+        fence()
+        dt_s = time.perf_counter() - t0
+        if dist is not None:
+            t = torch.tensor([dt_s], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt_s = float(t.item())
+        clock_samples = None
         if rank == 0:
-            # behind the newest enqueued step: the host runs ahead of the GPU, an unordered probe stream would take all its
-            # samples in the first milliseconds of the window
-            probe_stream.wait_stream(streams[(counter[0] - 1) % depth])
-            with torch.cuda.stream(probe_stream):
-                check(lib.w2l_clock_probe(current_stream(), 2000, ptr(ticks[done // probe_every])), "clock_probe")
-        n = min(probe_every, sust_steps - done)
-        run_steps(n)
-        done += n
-    fence()
-    dt_s = time.perf_counter() - t0
+            tk = ticks.tolist()
+            mhz = [100.0 * c / r for c, r in tk if r > 0]
+            if mhz:
+                clock_mhz = round(100.0 * sum(c for c, r in tk if r > 0) / sum(r for c, r in tk if r > 0), 1)
+                clock_samples = {"n": len(mhz), "min_mhz": round(min(mhz), 1), "max_mhz": round(max(mhz), 1)}
+        if args.sustained_seconds > 0:
+            sustained = {"steps": sust_steps, "seconds": round(dt_s, 3), "value": round(world * B * sust_steps / dt_s, 1),
+                         "ms_per_step": round(dt_s / sust_steps * 1e3, 3), "clock_samples": clock_samples}
     dumped = None
     if args.dump_outputs and rank == 0:
         # the last timed step, before the rates below reuse the lanes: its uint8 frames as the caller receives them (with N > 1
@@ -578,28 +602,14 @@ def main():
         frames_last = outs_u8[k_last] if gather is None else gather.recv[(gather.i - 1) % gather.depth]
         dumped = dump_outputs(args.dump_outputs, {"frames_u8": frames_last.cpu().numpy(),
                                                   "pred_nchw": runner.lanes[k_last].last_pred_nchw().cpu().numpy()})
-    if dist is not None:
-        t = torch.tensor([dt_s], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt_s = float(t.item())
-    clock_samples = None
-    if rank == 0:
-        tk = ticks.tolist()
-        mhz = [100.0 * c / r for c, r in tk if r > 0]
-        if mhz:
-            clock_mhz = round(100.0 * sum(c for c, r in tk if r > 0) / sum(r for c, r in tk if r > 0), 1)
-            clock_samples = {"n": len(mhz), "min_mhz": round(min(mhz), 1), "max_mhz": round(max(mhz), 1)}
-    if args.sustained_seconds > 0:
-        sustained = {"steps": sust_steps, "seconds": round(dt_s, 3), "value": round(world * B * sust_steps / dt_s, 1),
-                     "ms_per_step": round(dt_s / sust_steps * 1e3, 3), "clock_samples": clock_samples}
-    # ---- three more rates beside `value` (one GPU; none of them is `value`):
+    # ---- three more rates beside `value` (one GPU, --full; none of them is `value`):
     #   with_mel_and_d2h    the same runner and depth, every step ALSO computes the mel spectrogram of its 128 frames' audio
     #                       (audio.melspectrogram_device on a wav resident in HBM: north_star names the STFT as hot path) and copies
     #                       its uint8 frames to pinned host memory (what inference.lipsync / main do with every batch)
     #   one_in_flight       the product's runner at depth 1: strictly one batch at a time
     #   exact               this file with --exact in a subprocess (the library reads W2L_EXACT when it is loaded)
     extra = {}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         def windows_of(step_fn, nwin=3):
             rates = []
             for _ in range(nwin):
@@ -691,15 +701,9 @@ def main():
     # MFMA FLOP's pipe time it occupies (2516.6 = 16 x 157.3) - so frac = achieved / 157.3 is exactly the share of the step the
     # matrix cores would need at their peak rates, and no launch can exceed 1
     achieved = (exec_f32 + exec_bf16 / 16.0) / (step_ms * 1e-3) / 1e12
-    # the dominant kernel on its own: per-launch HIP events of one serial pass of the plan (outside the timed region)
-    prof = g.plan.profile(reps=3)
-    fam_ms, fam_fl, fam_n = {}, {}, {}
-    for (name, ms, _), (_, fl, fam, _) in zip(prof, resolved):
-        fam_ms[fam] = fam_ms.get(fam, 0.) + ms
-        fam_fl[fam] = fam_fl.get(fam, 0.) + fl / (16.0 if fam in BF16_FAMS else 1.0)       # fp32-pipe equivalents, as `achieved`
-        fam_n[fam] = fam_n.get(fam, 0) + 1
-    serial_ms = sum(fam_ms.values())
-    dom = max(fam_ms, key=fam_ms.get)
+    # the dominant kernel on its own (--full or --profile-layers): per-launch HIP events of one serial pass of the plan (outside the
+    # timed region)
+    prof = g.plan.profile(reps=3) if args.full or args.profile_layers else None
     kname = {"wino": "conv_wino_f32_kernel (Winograd F(2x2,3x3), fp32 MFMA)",
              "wino2": "conv_wino2_f32_kernel (Winograd F(2x2,3x3), position-split waves, fp32 MFMA)",
              "wino4": "conv_wino4_f32_kernel (Winograd F(4x4,3x3), 36 positions split over 8 waves, fp32 MFMA)",
@@ -710,7 +714,20 @@ def main():
              "tp2s": "conv_tp2s_kernel (stride-2 transposed 3x3, four phases per workgroup, operands as three bf16 pieces, bf16 MFMA)",
              "stem7s": "conv_stem7s_kernel (7x7 first layer, region staged and split once, bf16 MFMA)",
              "k3s": "conv_k3s_kernel (direct 3x3 for 32-cout layers + fused head, operands as three bf16 pieces, bf16 MFMA)"}
-    dom_tf = fam_fl[dom] / (fam_ms[dom] * 1e-3) / 1e12
+    dominant, serial_ms = None, None
+    if prof is not None:
+        fam_ms, fam_fl, fam_n = {}, {}, {}
+        for (name, ms, _), (_, fl, fam, _) in zip(prof, resolved):
+            fam_ms[fam] = fam_ms.get(fam, 0.) + ms
+            fam_fl[fam] = fam_fl.get(fam, 0.) + fl / (16.0 if fam in BF16_FAMS else 1.0)       # fp32-pipe equivalents, as `achieved`
+            fam_n[fam] = fam_n.get(fam, 0) + 1
+        serial_ms = sum(fam_ms.values())
+        dom = max(fam_ms, key=fam_ms.get)
+        dom_tf = fam_fl[dom] / (fam_ms[dom] * 1e-3) / 1e12
+        dominant = {"name": kname[dom], "launches_per_step": fam_n[dom], "executed_gflop_per_step": round(fam_fl[dom] / 1e9, 2),
+                    "ms_per_step_serial": round(fam_ms[dom], 3), "avg_launch_ms": round(fam_ms[dom] / fam_n[dom], 4),
+                    "share_of_serial_step": round(fam_ms[dom] / serial_ms, 3),
+                    "achieved": round(dom_tf, 2), "frac": round(dom_tf / PEAK_FP32_MFMA_TFLOPS, 4)}
     result = {
         "metric": "face-frames/sec (96x96, mel T=16)",
         "value": round(frames / dt, 1),
@@ -733,7 +750,7 @@ def main():
                                "(BASELINE configs[1]); datagen pack + mel gather + generator + uint8 frames%s"
                                % (B, " + RCCL all-gather of uint8 frames" if world > 1 else ""),
                    "frames_per_gpu_per_step": B, "parallelism": "dp%d" % world, "batches_in_flight_per_gpu": depth,
-                   "launch_threads": nthreads,
+                   "launch_threads": nthreads, "full": bool(args.full),
                    "weights": "random-init (wav2lip_amd.synthetic seed 0)", "launch_configs": config_source,
                    "collective_world_size": (dist.get_world_size() if dist is not None else 1),
                    "collective_backend": (dist.get_backend() if dist is not None else None)},
@@ -758,13 +775,8 @@ def main():
                      "nominal_tflops": round(nominal_flop / (step_ms * 1e-3) / 1e12, 2),
                      "nominal_gflop_per_step": round(nominal_flop / 1e9, 2),
                      "nominal_gflop_per_frame": round(nominal_flop / 1e9 / B, 4),
-                     "dominant_kernel": {"name": kname[dom], "launches_per_step": fam_n[dom],
-                                         "executed_gflop_per_step": round(fam_fl[dom] / 1e9, 2),
-                                         "ms_per_step_serial": round(fam_ms[dom], 3),
-                                         "avg_launch_ms": round(fam_ms[dom] / fam_n[dom], 4),
-                                         "share_of_serial_step": round(fam_ms[dom] / serial_ms, 3),
-                                         "achieved": round(dom_tf, 2), "frac": round(dom_tf / PEAK_FP32_MFMA_TFLOPS, 4)},
-                     "serial_ms_per_step": round(serial_ms, 3),
+                     "dominant_kernel": dominant,
+                     "serial_ms_per_step": round(serial_ms, 3) if serial_ms is not None else None,
                      "sustained_clock_mhz": clock_mhz,
                      "frac_at_sustained_clock": (round(achieved / (PEAK_FP32_MFMA_TFLOPS * clock_mhz / 2400.0), 4)
                                                  if clock_mhz else None),
@@ -795,7 +807,7 @@ def main():
                              % (name, ms, 100 * ms / serial_ms, 2 * m / ms / 1e9, fl / ms / 1e9, " (bf16)" if fam in BF16_FAMS else "",
                                 fam, cfg[0], cfg[1]))
         sys.stderr.write("sum %.3f ms\n" % serial_ms)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # CPU baseline + in-run parity: the frames the timed loop just produced (lane of the last step) against the CPU
         # forward of the same crops / mel windows.  Tolerances: north star 1e-3 L-inf on fp32 pixels; uint8 frames may differ
         # where v*255 sits within rounding of an integer (truncation), bounded at 0.1 % of the bytes.
@@ -812,7 +824,7 @@ def main():
         result["parity"] = {"frames_checked": ncheck, "fp32_linf": linf, "fp32_tolerance": 1e-3,
                             "u8_mismatches": mism, "u8_values": int(got_u8.size), "against": base["kind"]}
         assert linf <= 1e-3 and mism <= got_u8.size // 1000, "timed path failed the in-run parity check: %s" % result["parity"]
-    if world == 1 and not args.no_train_configs and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_train_configs and not args.no_cpu_baseline:
         result["other_configs"] = train_configs()
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -6,7 +6,7 @@ TAG=${1:-order}; OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp; ROOT=$P
 CONDS=${CONDS:-"old:0:0:- new:-:-:- nocm:2:-:- r16:-:-:16 r24:-:-:24 r48:-:-:48 r64:-:-:64"}
 (timeout 900 python -m pytest tests/test_conv_gpu.py -m gpu -q -x 2>&1 | tail -2) > $OUT/pytest.log
 export W2L_HIP_LIB=$ROOT/wav2lip_amd/lib/libw2l_hip_orderenv.so
-B="python $ROOT/bench.py --no-cpu-baseline --no-train-configs --steps 20 --warmup 3 --sustained-seconds 1.5"
+B="python $ROOT/bench.py --full --no-cpu-baseline --no-train-configs --steps 20 --warmup 3 --sustained-seconds 1.5"
 setc() { IFS=: read name o m r <<< "$1"; unset W2L_IGEMM_ORDER W2L_WINO_MFAST W2L_IGEMM_R; [ "$r" != "-" ] && export W2L_IGEMM_R=$r; [ "$o" != "-" ] && export W2L_IGEMM_ORDER=$o; [ "$m" != "-" ] && export W2L_WINO_MFAST=$m; }
 for i in 1 2 3; do for c in $CONDS; do setc $c
   timeout 200 $B 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name value %.0f sustained %.0f serial %.3f ms' % (d['value'], d['windows']['sustained_value'], d['roofline']['serial_ms_per_step']))"

@@ -19,7 +19,7 @@ for l in sys.stdin:
 done
 for which in r5 r6; do
   d=.; [ $which = r5 ] && d=_r5
-  (cd $d && timeout -s KILL 300 python bench.py --no-cpu-baseline --no-train-configs --windows 5 2>/dev/null) | python -c "
+  (cd $d && timeout -s KILL 300 python bench.py --full --no-cpu-baseline --no-train-configs --windows 5 2>/dev/null) | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'): d = json.loads(l); print('$which', 'bench', d['value'], d['windows']['sustained_value'])

@@ -17,12 +17,12 @@ fi
 python -c "import bench; print(bench.source_fingerprint())" > $OUT/source_fingerprint.txt
 TUNE=""
 [ -n "$AUTOTUNE" ] && TUNE="--autotune --tune-cache $OUT/tune.json"
-(timeout 500 python bench.py --steps $STEPS --warmup 3 $TUNE --profile-layers $BENCH_ARGS 2>$OUT/layers.log | tail -1) > $OUT/bench.json
+(timeout 500 python bench.py --full --steps $STEPS --warmup 3 $TUNE --profile-layers $BENCH_ARGS 2>$OUT/layers.log | tail -1) > $OUT/bench.json
 for v in $VARIANTS; do
-  (W2L_HIP_LIB=$PWD/wav2lip_amd/lib/libw2l_hip_$v.so timeout 300 python bench.py --steps $STEPS --warmup 3 --no-cpu-baseline --profile-layers 2>$OUT/layers_$v.log | tail -1) > $OUT/bench_$v.json
+  (W2L_HIP_LIB=$PWD/wav2lip_amd/lib/libw2l_hip_$v.so timeout 300 python bench.py --full --steps $STEPS --warmup 3 --no-cpu-baseline --profile-layers 2>$OUT/layers_$v.log | tail -1) > $OUT/bench_$v.json
 done
 if [ -n "$PROFILE" ]; then
-  PB="python $ROOT/bench.py --no-cpu-baseline $BENCH_ARGS"
+  PB="python $ROOT/bench.py --full --no-cpu-baseline $BENCH_ARGS"
   [ -n "$AUTOTUNE" ] && PB="$PB --tune-cache $ROOT/$OUT/tune.json"
   cd /tmp
   (timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/prof_stats -o stats -- $PB --steps $STEPS --warmup 3 --windows 1 > $ROOT/$OUT/prof_stats.log 2>&1)
