@@ -194,6 +194,13 @@ int w2l_s3fd_decode(void* stream, int B, int FH, int FW, int stride, const float
  * of either sign order as floats do. */
 int w2l_s3fd_nms(void* stream, int B, int P, const float* table, float gate, float thresh, int* keep, int* counts,
                  void* scratch, long long scratch_bytes);
+/* The rect get_detections_for_batch keeps per image (sfd_detector.py:45 + api.py:61-77), from w2l_s3fd_nms's outputs after the
+ * caller has resolved any counts = -1 (counts final): the first row of keep[b][:counts[b]] whose score is > thresh, its (x1, y1,
+ * x2, y2) clipped at 0 and truncated to int as Python's int() does -> rects [B][4] int32, flags [B] int32: 1 found, 0 no row
+ * passes (rect zeros), 2 the host must decide (a coordinate of that row is NaN, +inf or >= 2^31, a kept index lies outside
+ * [0, P), or counts[b] is not in [0, P]; rect zeros).  The table is fp32 for either detector precision. */
+int w2l_s3fd_first_rect(void* stream, int B, int P, const float* table, const int* keep, const int* counts, float thresh,
+                        int* rects, int* flags);
 
 /* The opt-in bf16-storage detector (face_detection/s3fd.py, precision="bf16"): the backbone convolutions are w2l_convb layers
  * (scale 1, shift = bias, ReLU); these are the ops between them and the fused detection head.  Tensors are NHWC bf16 with channel

@@ -5,6 +5,7 @@
 //   w2l_l2norm_scale    net_s3fd.py:6-19             x / (sqrt(sum_c x^2) + 1e-10) * weight[c]
 //   w2l_s3fd_decode     net_s3fd.py:123-126 (max-out background), detect.py:66-84 (softmax, priors, decode)
 //   w2l_s3fd_nms        sfd_detector.py:39-45 gate + bbox.py:44-64 greedy NMS, bit-exact keep list
+//   w2l_s3fd_first_rect sfd_detector.py:45 + api.py:61-77  first kept box above 0.5 -> int rect, one row per image
 // All HBM-bound, NHWC, float4 where the channel count allows.
 #include "w2l_common.h"
 
@@ -182,6 +183,56 @@ __global__ __launch_bounds__(kNmsThreads) void s3fd_nms_kernel(int P, const floa
     if (t == 0) counts[b] = s_kept;
 }
 
+// ---- the per-frame rect of get_detections_for_batch (api.py:61-77) from the NMS output: the first kept row, in keep order, whose
+// score is > thresh (sfd_detector.py:45 `x[-1] > 0.5`, then d[0]), its coordinates clipped at 0 (`np.clip(d, 0, None)`) and
+// truncated as Python's int() truncates.  One wave per image scans the keep list 64 entries at a time; the lowest lane that
+// decides (a passing row, or a row index outside the table) writes the image's result.  A coordinate Python's int() would
+// refuse or that int32 cannot hold (NaN, inf, >= 2^31) is not converted: the image is flagged and the caller's host rule runs.
+constexpr int kRectNone = 0, kRectFound = 1, kRectHost = 2;
+
+__global__ __launch_bounds__(64) void s3fd_first_rect_kernel(int P, const float* __restrict__ table, const int* __restrict__ keep,
+                                                             const int* __restrict__ counts, float thresh, int* __restrict__ rects,
+                                                             int* __restrict__ flags) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const float* tb = table + (long long)b * P * 5;
+    const int* kp = keep + (long long)b * P;
+    const int n = counts[b];
+    int* r = rects + (long long)b * 4;
+    if (n < 0 || n > P) {                               // not a final count (an unresolved overflow): the host decides
+        if (lane == 0) { r[0] = r[1] = r[2] = r[3] = 0; flags[b] = kRectHost; }
+        return;
+    }
+    for (int base = 0; base < n; base += 64) {
+        const int i = base + lane;
+        int row = -1;
+        bool bad = false, pass = false;
+        if (i < n) {
+            row = kp[i];
+            bad = row < 0 || row >= P;
+            pass = !bad && tb[(long long)row * 5 + 4] > thresh;
+        }
+        const unsigned long long hit = __ballot(bad || pass);
+        if (hit == 0ull) continue;                      // uniform: every lane sees the same ballot
+        if (lane == __ffsll((long long)hit) - 1) {
+            int flag = kRectFound, v[4] = {0, 0, 0, 0};
+            if (bad) flag = kRectHost;
+            else {
+                const float* d = tb + (long long)row * 5;
+                for (int k = 0; k < 4; ++k) {
+                    const float x = d[k] > 0.f ? d[k] : 0.f;
+                    if (!(d[k] == d[k]) || !(x < 2147483648.f)) { flag = kRectHost; break; }   // NaN, +inf, >= 2^31
+                    v[k] = (int)x;                                                          // x >= 0: truncation = int()
+                }
+                if (flag == kRectHost) v[0] = v[1] = v[2] = v[3] = 0;
+            }
+            r[0] = v[0]; r[1] = v[1]; r[2] = v[2]; r[3] = v[3];
+            flags[b] = flag;
+        }
+        return;
+    }
+    if (lane == 0) { r[0] = r[1] = r[2] = r[3] = 0; flags[b] = kRectNone; }
+}
+
 static inline int grid1d(long long work, int block, int cap = 16384) {
     long long g = (work + block - 1) / block;
     if (g > cap) g = cap;
@@ -250,6 +301,16 @@ int w2l_s3fd_nms(void* stream, int B, int P, const float* table, float gate, flo
     int* order = reinterpret_cast<int*>(keys + (long long)B * P);
     hipLaunchKernelGGL(s3fd_nms_kernel, dim3(B), dim3(kNmsThreads), 0, static_cast<hipStream_t>(stream), P, table, gate, thresh,
                        keys, order, keep, counts);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_s3fd_first_rect(void* stream, int B, int P, const float* table, const int* keep, const int* counts, float thresh,
+                        int* rects, int* flags) {
+    W2L_REQUIRE(table && keep && counts && rects && flags && B >= 1 && P >= 1, "bad s3fd_first_rect arguments");
+    W2L_REQUIRE((long long)B * P * 5 < (1ll << 31), "s3fd_first_rect: table too large");
+    hipLaunchKernelGGL(s3fd_first_rect_kernel, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), P, table, keep, counts,
+                       thresh, rects, flags);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

@@ -7,7 +7,7 @@ from enum import Enum
 import numpy as np
 import torch
 
-from .s3fd import nms, nms_batch, s3fd
+from .s3fd import RECT_FOUND, RECT_HOST, first_rects, nms, nms_batch, s3fd
 
 
 class LandmarksType(Enum):
@@ -63,8 +63,19 @@ class FaceAlignment:
                 out.append([x for x in d if x[-1] > 0.5])
         return out
 
+    def _candidates(self, images_bgr):
+        """the batch's box table [B, P, 5] and its gated NMS (keep, counts), all on the device"""
+        if isinstance(images_bgr, np.ndarray):
+            images_bgr = torch.from_numpy(np.ascontiguousarray(images_bgr)).to(self.device)
+        levels = self.face_detector.dense_boxes(images_bgr, precision=self.precision)
+        table = torch.cat(levels, dim=1).contiguous()           # [B, sum FH*FW, 5]
+        keep, counts = nms_batch(table, 0.05, 0.3)
+        return table, keep, counts
+
     def get_detections_for_batch(self, images):
-        """api.py:61-77 (the BGR->RGB flip of :62 happens inside the device pack kernel)"""
+        """api.py:61-77 (the BGR->RGB flip of :62 happens inside the device pack kernel).  The rect of every image comes from one
+        launch (`w2l_s3fd_first_rect`) and one copy back per batch; an image the device flags (a non-finite or huge coordinate)
+        takes the per-image host rule below, which raises what Python's int() raises there."""
         def first_rect(dets):
             # the best-scoring detection, clipped at the image origin and truncated to ints; None when nothing survived NMS
             if len(dets) == 0:
@@ -72,4 +83,15 @@ class FaceAlignment:
             box = np.maximum(np.asarray(dets[0][:4]), 0)
             return tuple(int(v) for v in box)
 
-        return [first_rect(dets) for dets in self.detect_from_batch(images)]
+        with torch.no_grad():
+            table, keep, counts = self._candidates(images)
+            res = first_rects(table, keep, counts, 0.5)
+            out = []
+            for b, r in enumerate(res):
+                if r[4] == RECT_HOST:
+                    n = int(counts[b].item())
+                    d = table[b].index_select(0, keep[b, :n].long()).cpu().numpy()
+                    out.append(first_rect([x for x in d if x[-1] > 0.5]))
+                else:
+                    out.append(tuple(int(v) for v in r[:4]) if r[4] == RECT_FOUND else None)
+        return out

@@ -401,6 +401,29 @@ def nms_batch(table, gate, thresh):
     return keep, counts
 
 
+RECT_NONE, RECT_FOUND, RECT_HOST = 0, 1, 2       # w2l_s3fd_first_rect flags
+
+
+def first_rects(table, keep, counts, thresh):
+    """sfd_detector.py:45 + api.py:61-77 for a batch on the device (`w2l_s3fd_first_rect`): nms_batch's (keep, counts) over `table`
+    -> numpy int32 [B, 5] in ONE device-to-host copy, per image (x1, y1, x2, y2, flag): the first kept row above `thresh`, clipped
+    at 0 and truncated, with flag RECT_FOUND; RECT_NONE when no row passes; RECT_HOST when a coordinate is one the device does not
+    convert (NaN, +inf, >= 2^31) - the caller decides that image on the host."""
+    engine.require_cuda(table, "box table")
+    if table.dtype != torch.float32 or table.dim() != 3 or table.shape[2] != 5:
+        raise RuntimeError("first_rects: table must be float32 [B, P, 5]")
+    table = table.contiguous()
+    B, P = table.shape[:2]
+    if keep.dtype != torch.int32 or tuple(keep.shape) != (B, P) or counts.dtype != torch.int32 or tuple(counts.shape) != (B,):
+        raise RuntimeError("first_rects: keep must be int32 [B, P] and counts int32 [B] (nms_batch's outputs)")
+    keep, counts = keep.contiguous(), counts.contiguous()
+    out = torch.empty((5 * B,), device=table.device, dtype=torch.int32)       # rects [B][4], then flags [B]: one copy back
+    check(load().w2l_s3fd_first_rect(current_stream(), B, P, ptr(table), ptr(keep), ptr(counts), float(thresh), ptr(out),
+                                     ptr(out[4 * B:])), "s3fd_first_rect")
+    h = out.cpu().numpy()
+    return np.concatenate([h[:4 * B].reshape(B, 4), h[4 * B:].reshape(B, 1)], axis=1)
+
+
 def _nms_host(dets, thresh):
     """bbox.py:44-64 in its float32 operation order (numpy): kept row indices of `dets` [n, 5], best score first.  Only the
     overflow route of nms_batch comes here."""

@@ -120,6 +120,42 @@ def s3fd_frames(seed=1, B=2, H=96, W=128):
     return img
 
 
+def preprocess_frames(n, seed, H=160, W=160):
+    """uint8 BGR frames of a synthetic clip for the preprocessing path (LRS2 frames are 160x160): most are noise with one saturated
+    block at a seeded place - the seeded S3FD (s3fd_state_dict) finds a "face" there, well above the 0.5 threshold - and about one in
+    four is flat grey (120) with faint noise, on which it finds none"""
+    r = _rng(seed, "preprocess")
+    out = np.empty((n, H, W, 3), np.uint8)
+    for k in range(n):
+        if r.uniform() < 0.25:
+            out[k] = 120 + r.integers(-1, 2, (H, W, 3))
+            continue
+        out[k] = r.integers(0, 256, (H, W, 3), dtype=np.uint8)
+        h, w = r.integers(H // 4, H // 2), r.integers(W // 4, W // 2)
+        y, x = r.integers(0, H - h), r.integers(0, W - w)
+        out[k, y:y + h, x:x + w] = 255 if r.uniform() < 0.5 else 0
+    return out
+
+
+# (directory, clip name, frames, audio channels, audio rate): two directories, clip lengths that leave a ragged last batch at
+# batch size 4, a stereo track at another rate, and a clip without audio
+PREPROCESS_CLIPS = [("spk1", "00001", 11, 1, 16000), ("spk1", "00002", 5, 2, 22050), ("spk2", "00003", 9, 1, 16000),
+                    ("spk2", "00004", 3, 0, 0)]
+
+
+def preprocess_clips(seed=4, fps=25):
+    """[(directory, clip name, frames uint8 [T,160,160,3] BGR, audio int16 [n, channels] or None, audio rate)] of PREPROCESS_CLIPS"""
+    clips = []
+    for i, (d, name, t, ch, sr) in enumerate(PREPROCESS_CLIPS):
+        frames = preprocess_frames(t, seed * 100 + i)
+        pcm = None
+        if ch:
+            n = t * sr // fps
+            pcm = _rng(seed * 100 + i, "preprocess_audio").integers(-8000, 8000, (n, ch)).astype(np.int16)
+        clips.append((d, name, frames, pcm, sr))
+    return clips
+
+
 # ---------------------------------------------------------------- training batches at the BASELINE launch shapes
 def train_batch(cfg, B, seed=0, T=5):
     """Seeded inputs of one training step (BASELINE configs[2..4]; the committed goldens of tests/golden/
