@@ -419,6 +419,16 @@ def test_data_gradient_launch_reduces_the_batchnorm_backward_sums(case, cuda):
     torch.cuda.synchronize()
     Sb = float(g.abs().reshape(-1, cin).sum(0).max()) + 1e-30          # scale of a column sum: sum |g|
     assert float((db2[:cin].double().cpu() - ref_db).abs().max()) <= 1e-6 * Sb
+    # dgamma of the stand-alone path: fp64 sums of g * zhat, zhat formed in fp32 (relative 2^-23 per term)
+    Sgz = float((g * zh).abs().reshape(-1, cin).sum(0).max()) + 1e-30
+    assert float((dg2[:cin].double().cpu() - ref_dg).abs().max()) <= 1e-6 * Sgz, "stand-alone dgamma"
+    # its dz against float64 of the stored operands: scale * (g - mean g - zhat * mean(g * zhat)), one bf16 rounding plus
+    # fp32 arithmetic on the terms
+    sc64 = scale_d[:cin].double().cpu()
+    mg, mgz = g.reshape(-1, cin).mean(0), (g * zh).reshape(-1, cin).mean(0)
+    dz64 = sc64 * (g - mg - zh * mgz)
+    bound = 2.0 ** -8 * dz64.abs() + 1e-6 * sc64.abs() * (g.abs() + g.abs().reshape(-1, cin).mean(0) + zh.abs() * (g * zh).abs().reshape(-1, cin).mean(0))
+    assert bool(((dz_ref[..., :cin].double().cpu() - dz64).abs() <= bound).all()), "stand-alone dz against float64"
     if not fused:
         return
     # fp32 per-lane / per-wave partials, fp64 above: a few 1e-7 of sum |g| (|zhat| ~ 1)
