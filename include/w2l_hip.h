@@ -282,6 +282,28 @@ int w2l_conv_wgrad(const w2l_conv_geom* g, void* stream, int N, int H, int W, co
 int w2l_conv_wgrad_prec(const w2l_conv_geom* g, void* stream, int N, int H, int W, const float* x, int x_cs,
                         const float* dz, int dz_cs, float* dweight, int precision);
 
+/* What a call of w2l_conv_wgrad_prec with these arguments would run, from the launcher's own planning code (the launch executes
+ * the same plan).  Launches nothing, touches no device memory, needs no device.
+ *   family: W2L_WGRAD_WINO (F(3x3,2x2) Winograd), W2L_WGRAD_DIRECT (the GEMM kernels) or W2L_WGRAD_SMALL (heads of <= 4 channels);
+ *   cfg: tile configuration of the direct GEMM - 0..4 for W2L_PREC_F32, 0..5 for W2L_PREC_BF16 (2 * row size + [P width % 8 == 0]);
+ *        -1 for the other families;  K: length of the reduction (P-grid pixels; Winograd: 2x2 tiles), kstep: its step (small head:
+ *   pixel lanes), chunk: K per workgroup, ksplit = ceil(K / chunk) workgroups along K;  reduce_blocks: grid of the reduce kernel. */
+#define W2L_WGRAD_WINO 0
+#define W2L_WGRAD_DIRECT 1
+#define W2L_WGRAD_SMALL 2
+typedef struct w2l_wgrad_info {
+    int family, cfg, ksplit, chunk, K, kstep, reduce_blocks;
+} w2l_wgrad_info;
+int w2l_conv_wgrad_resolve(const w2l_conv_geom* g, int N, int H, int W, int x_cs, int dz_cs, int precision, w2l_wgrad_info* out);
+/* Tests / tuning: force tile configuration `cfg` of the fp32 direct GEMM (-1 = automatic; a configuration whose rows do not fit
+ * the layer is ignored; any forced value keeps the Winograd kernel off) and switch the Winograd kernel on / off (wino = 1 / 0).
+ * Process-wide; replaces what W2L_WGRAD_CFG / W2L_WINO_WGRAD gave. */
+int w2l_conv_wgrad_set_cfg(int cfg, int wino);
+/* The float-reciprocal index split of the weight-gradient kernels evaluated on the host, n times: which = 0 the direct GEMM's
+ * (pixel -> image, row, column), 1 the Winograd kernel's (tile -> image, tile row, tile column); q[i], r[i] = what the kernel
+ * computes for a[i] / d[i] with the reciprocal the launcher passes.  Test support. */
+int w2l_wgrad_divmod_host(int which, int n, const int* a, const int* d, int* q, int* r);
+
 /* ---------------------------------------------------------------- training in bf16 (BASELINE configs[3] / [4])
  * The bf16-STORAGE training path: activations, pre-BatchNorm conv outputs and their gradients live in HBM as NHWC bf16
  * (channel strides in ELEMENTS, multiples of 8, pad channels zero; 16-byte aligned pointers); master weights, weight
@@ -373,6 +395,13 @@ int w2l_convb_resolve(const w2l_convb_t* c, int N, int H, int W, int has_res, in
  * otherwise (zero pad channels, deterministic fixed-order split-K). */
 int w2l_conv_wgrad_bf16(const w2l_conv_geom* g, void* stream, int N, int H, int W, const void* x, int x_cs,
                         const void* dz, int dz_cs, float* dweight);
+/* The plan of that call, from the launcher's own planning code; launches nothing, needs no device.  A workgroup walks
+ * boxes_per_split boxes (the last split: the rest of nboxes) of ni images x bh x bw P pixels; ntg tap groups of tg taps, ncq
+ * 64-channel Q slices, mt / qp 32-channel planes of P / Q. */
+typedef struct w2l_wgrad_bf16_info {
+    int ni, bh, bw, nboxes, splits, boxes_per_split, ntg, tg, ncq, mt, qp;
+} w2l_wgrad_bf16_info;
+int w2l_conv_wgrad_bf16_resolve(const w2l_conv_geom* g, int N, int H, int W, int x_cs, int dz_cs, w2l_wgrad_bf16_info* out);
 
 /* BatchNorm (batch statistics) / activation / residual passes over bf16 tensors: the bf16 twins of the fp32 entry points
  * below (same arithmetic in fp32 / fp64, 8 channels = 16 bytes per thread and row).  C = channels of the row view, a multiple
@@ -412,6 +441,8 @@ int w2l_thin1x1_dgrad_bf16(void* stream, long long npix, int cin, int cout, cons
                            const void* res, int res_cs, void* dx, int dx_cs);
 int w2l_thin1x1_wgrad_bf16(void* stream, long long npix, int cin, int cout, const void* x, int x_cs, const void* dz, int dz_cs,
                            float* dweight, float* dbias);
+/* workgroups (= partial rows) w2l_thin1x1_wgrad_bf16 launches for npix pixels: the launcher's own rule */
+int w2l_thin1x1_wgrad_blocks(long long npix);
 /* graph boundary: x fp32 [N,C,H,W] -> y bf16 [N,H,W,y_cs] (channels [C, c_zero_to) zero-filled) and back */
 int w2l_nchw_to_nhwc_bf16(void* stream, int N, int C, int H, int W, const float* x, void* y, int y_cs, int c_zero_to);
 int w2l_nhwc_bf16_to_nchw(void* stream, int N, int C, int H, int W, const void* x, int x_cs, float* y);

@@ -31,7 +31,23 @@ def _nhwc(x, cs=None, off=0):
     return buf
 
 
-def _check(cuda, transposed, cin, cout, k, stride, pad, outpad, N, H, W, seed=0, x_extra=0, dz_extra=0):
+def _plan(transposed, cin, cout, k, stride, pad, outpad, N, H, W, x_extra=0, dz_extra=0):
+    """the launcher's own dry run (w2l_conv_wgrad_bf16_resolve) of the launch _check makes with these arguments"""
+    kh, kw = _pair(k)
+    s, p, op = _pair(stride), _pair(pad), _pair(outpad)
+    g = ConvGeom(int(transposed), cin, cout, kh, kw, s[0], s[1], p[0], p[1], op[0], op[1], ACT_NONE)
+    info = _lib.WgradBf16Info()
+    check(_lib.load().w2l_conv_wgrad_bf16_resolve(C.byref(g), N, H, W, bf16.round8(cin) + x_extra, bf16.round8(cout) + dz_extra,
+                                                  C.byref(info)), "conv_wgrad_bf16_resolve")
+    return info
+
+
+def _check(cuda, transposed, cin, cout, k, stride, pad, outpad, N, H, W, seed=0, x_extra=0, dz_extra=0, claim=None):
+    """claim: what the calling line's comment says about the launch, as a predicate over the dry run"""
+    if claim is not None:
+        i = _plan(transposed, cin, cout, k, stride, pad, outpad, N, H, W, x_extra, dz_extra)
+        assert claim(i), "the launch plan no longer is what this case was written for: " + ", ".join(
+            "%s %d" % (n, getattr(i, n)) for n, _ in i._fields_)
     torch.manual_seed(seed)
     kh, kw = _pair(k)
     s, p, op = _pair(stride), _pair(pad), _pair(outpad)
@@ -68,17 +84,31 @@ def test_weight_gradient_signature(idx, cuda):
 
 
 def test_ragged_boxes_batches_and_channel_slices(cuda):
-    _check(cuda, False, 64, 64, 3, 1, 1, 0, 1, 96, 96, seed=1)                   # batch 1
-    _check(cuda, False, 64, 64, 3, 1, 1, 0, 5, 13, 11, seed=2)                   # extents no box divides
-    _check(cuda, False, 24, 40, 3, 1, 1, 0, 3, 9, 7, seed=3)                     # channel counts that are not multiples of 32
-    _check(cuda, False, 80, 32, 3, 1, 1, 0, 2, 20, 20, seed=4)                   # Q of 80 channels: a 64 + 16 slice pair
-    _check(cuda, True, 160, 64, 3, 2, 1, 1, 2, 10, 12, seed=5)                   # P of 160 channels: 64 + 64 + 32
-    _check(cuda, False, 512, 512, 3, 1, 1, 0, 37, 3, 3, seed=6)                  # several whole images per box, ragged last box
-    _check(cuda, False, 512, 512, 1, 1, 0, 0, 50, 1, 1, seed=7)                  # 1x1 on 1x1: K = batch
-    _check(cuda, False, 32, 3, 1, 1, 0, 0, 2, 96, 96, seed=8)                    # RGB head: 3 couts
-    _check(cuda, False, 64, 64, 3, 1, 1, 0, 2, 24, 24, seed=9, x_extra=96, dz_extra=32)    # operands are slices of wider buffers
-    _check(cuda, True, 64, 32, 3, 2, 1, 0, 2, 7, 5, seed=10)                     # transposed without output padding
-    _check(cuda, False, 16, 32, 5, (1, 2), (2, 1), 0, 2, 11, 21, seed=11)        # 5x5, anisotropic stride / pad
+    """every line's comment is asserted from the dry run (claim=...): a rule change that makes a comment false fails here"""
+    _check(cuda, False, 64, 64, 3, 1, 1, 0, 1, 96, 96, seed=1,                   # batch 1
+           claim=lambda i: i.ni == 1 and i.nboxes == (96 // i.bh) * (96 // i.bw))
+    _check(cuda, False, 64, 64, 3, 1, 1, 0, 5, 13, 11, seed=2,                   # one whole (odd-sized) image per box
+           claim=lambda i: (i.ni, i.bh, i.bw, i.nboxes) == (1, 13, 11, 5))
+    _check(cuda, False, 64, 64, 3, 1, 1, 0, 2, 37, 41, seed=12,                  # extents no box divides
+           claim=lambda i: i.ni == 1 and 37 % i.bh != 0 and 41 % i.bw != 0)
+    _check(cuda, False, 24, 40, 3, 1, 1, 0, 3, 9, 7, seed=3,                     # channel counts that are not multiples of 32
+           claim=lambda i: (i.mt, i.qp) == (2, 1))
+    _check(cuda, False, 80, 32, 3, 1, 1, 0, 2, 20, 20, seed=4,                   # Q of 80 channels: a 64 + 16 slice pair
+           claim=lambda i: i.ncq == 2 and i.qp == 2 and i.mt == 1)
+    _check(cuda, True, 160, 64, 3, 2, 1, 1, 2, 10, 12, seed=5,                   # P of 160 channels: 64 + 64 + 32
+           claim=lambda i: i.mt == 2 and i.ncq == 1)
+    _check(cuda, False, 512, 512, 3, 1, 1, 0, 37, 3, 3, seed=6,                  # several whole images per box, ragged last box
+           claim=lambda i: i.ni == 5 and 37 % i.ni == 2 and (i.bh, i.bw) == (3, 3) and i.nboxes == 8)
+    _check(cuda, False, 512, 512, 1, 1, 0, 0, 50, 1, 1, seed=7,                  # 1x1 on 1x1: K = batch
+           claim=lambda i: (i.bh, i.bw) == (1, 1) and i.ni * i.nboxes >= 50 > i.ni * (i.nboxes - 1) and i.ntg == 1)
+    _check(cuda, False, 32, 3, 1, 1, 0, 0, 2, 96, 96, seed=8,                    # RGB head: 3 couts
+           claim=lambda i: (i.mt, i.qp, i.ncq) == (1, 1, 1))
+    _check(cuda, False, 64, 64, 3, 1, 1, 0, 2, 24, 24, seed=9, x_extra=96, dz_extra=32,    # operands are slices of wider buffers
+           claim=lambda i: i.ni == 1 and i.nboxes > 1)
+    _check(cuda, True, 64, 32, 3, 2, 1, 0, 2, 7, 5, seed=10,                     # transposed without output padding
+           claim=lambda i: i.ni == 2 and (i.bh, i.bw) == (7, 5))
+    _check(cuda, False, 16, 32, 5, (1, 2), (2, 1), 0, 2, 11, 21, seed=11,        # 5x5, anisotropic stride / pad
+           claim=lambda i: i.tg == 25 and i.ntg == 1)
 
 
 def test_weight_gradient_is_deterministic(cuda):

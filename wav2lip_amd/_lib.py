@@ -25,6 +25,18 @@ class AdamTensor(C.Structure):
                 ("n", C.c_longlong)]
 
 
+class WgradInfo(C.Structure):
+    """w2l_wgrad_info: what w2l_conv_wgrad_prec would run (w2l_conv_wgrad_resolve)"""
+    _fields_ = [(n, C.c_int) for n in ("family", "cfg", "ksplit", "chunk", "K", "kstep", "reduce_blocks")]
+
+
+class WgradBf16Info(C.Structure):
+    """w2l_wgrad_bf16_info: the plan of w2l_conv_wgrad_bf16 (w2l_conv_wgrad_bf16_resolve)"""
+    _fields_ = [(n, C.c_int) for n in ("ni", "bh", "bw", "nboxes", "splits", "boxes_per_split", "ntg", "tg", "ncq", "mt", "qp")]
+
+
+WGRAD_WINO, WGRAD_DIRECT, WGRAD_SMALL = 0, 1, 2
+
 _vp, _i, _ll, _f = C.c_void_p, C.c_int, C.c_longlong, C.c_float
 
 # name -> (restype, argtypes); must list every symbol of include/w2l_hip.h (tests/test_abi.py checks it)
@@ -78,6 +90,9 @@ SIGNATURES = {
     "w2l_conv_update": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "w2l_conv_wgrad": (_i, [C.POINTER(ConvGeom), _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "w2l_conv_wgrad_prec": (_i, [C.POINTER(ConvGeom), _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i]),
+    "w2l_conv_wgrad_resolve": (_i, [C.POINTER(ConvGeom), _i, _i, _i, _i, _i, _i, C.POINTER(WgradInfo)]),
+    "w2l_conv_wgrad_set_cfg": (_i, [_i, _i]),
+    "w2l_wgrad_divmod_host": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
     "w2l_convb_create": (_i, [C.POINTER(ConvGeom), _vp, _vp, C.POINTER(_vp)]),
     "w2l_convb_update": (_i, [_vp, _vp, _vp]),
     "w2l_convb_update_many": (_i, [_i, _vp, _vp, _vp]),
@@ -93,6 +108,7 @@ SIGNATURES = {
     "w2l_convb_num_tiles": (_i, []),
     "w2l_convb_resolve": (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "w2l_conv_wgrad_bf16": (_i, [C.POINTER(ConvGeom), _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "w2l_conv_wgrad_bf16_resolve": (_i, [C.POINTER(ConvGeom), _i, _i, _i, _i, _i, C.POINTER(WgradBf16Info)]),
     "w2l_bn_train_stats_bf16": (_i, [_vp, _ll, _i, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "w2l_affine_act_bf16": (_i, [_vp, _ll, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i]),
     "w2l_bn_train_bwd_bf16": (_i, [_vp, _ll, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i]),
@@ -103,6 +119,7 @@ SIGNATURES = {
     "w2l_thin1x1_forward_bf16": (_i, [_vp, _ll, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "w2l_thin1x1_dgrad_bf16": (_i, [_vp, _ll, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "w2l_thin1x1_wgrad_bf16": (_i, [_vp, _ll, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "w2l_thin1x1_wgrad_blocks": (_i, [_ll]),
     "w2l_nchw_to_nhwc_bf16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i]),
     "w2l_nhwc_bf16_to_nchw": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "w2l_bn_train_stats": (_i, [_vp, _ll, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -46,7 +46,7 @@ struct WgradKArgs {
 };
 
 // q = a / d, r = a % d for 0 <= a < 2^31 and a quotient below 2^22: float reciprocal estimate + one correction step
-__device__ __forceinline__ void fast_divmod(int a, int d, float inv_d, int& q, int& r) {
+__host__ __device__ __forceinline__ void fast_divmod(int a, int d, float inv_d, int& q, int& r) {
     q = (int)((float)a * inv_d);
     r = a - q * d;
     const int lo = r < 0 ? 1 : 0, hi = r >= d ? 1 : 0;   // branch-free single correction
@@ -587,24 +587,41 @@ static const WgradCfg kWgradBf16Cfgs[] = {   // [tile][P-grid width % 8 == 0]
     {32, 128, kWBK, conv_wgrad_bf16_kernel<32, 128, 1, 4, true>, wgrad_bf16_lds_bytes<32, 128>(), 3},
 };
 
-static int wgrad_force_cfg = -1;   // W2L_WGRAD_CFG=<id>: force a tile configuration (tuning / tests)
-static int wgrad_wino = 1;         // W2L_WINO_WGRAD=0: keep the direct GEMM for the 3x3 s1 p1 layers (A/B runs)
+static int wgrad_force_cfg = -1;   // W2L_WGRAD_CFG=<id> / w2l_conv_wgrad_set_cfg: force a tile configuration (tuning / tests)
+static int wgrad_wino = 1;         // W2L_WINO_WGRAD=0 / w2l_conv_wgrad_set_cfg: keep the direct GEMM for the 3x3 s1 p1 layers (A/B runs)
 
 // conv_wino_wgrad.hip
 bool wino_wgrad_ok(const w2l_conv_geom* g, int N, int H, int W, int x_cs, int dz_cs);
+void wino_wgrad_plan_info(const w2l_conv_geom* g, int N, int H, int W, int x_cs, int dz_cs, int* T, int* kstep, int* chunk,
+                          int* ksplit);
+void wino_divmod_host(int a, int d, int* q, int* r);
 int wino_wgrad_launch(const w2l_conv_geom* g, hipStream_t s, int N, int H, int W, const float* x, int x_cs, const float* dz,
                       int dz_cs, float* dweight);
+
+// grid of the reduce kernel: one thread per (cp, (tap, cq)), capped (the kernel strides over the rest)
+int wgrad_reduce_grid(int CP, int ncols) {
+    long long gr = ((long long)CP * ncols + 255) / 256;
+    if (gr > 8192) gr = 8192;
+    return (int)gr;
+}
 
 int wgrad_reduce_launch(hipStream_t s, const float* ws, float* dw, int ksplit, int Mp, int Np, int CP, int CQ, int CQp, int ntaps) {
     WgradReduceArgs r;
     r.ws = ws; r.dw = dw; r.colsum = nullptr;
     r.ksplit = ksplit; r.Mp = Mp; r.Np = Np; r.CP = CP; r.CQ = CQ; r.CQp = CQp;
     r.ntaps = ntaps; r.ncols = ntaps * CQp;
-    long long gr = ((long long)CP * r.ncols + 255) / 256;
-    if (gr > 8192) gr = 8192;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)gr), dim3(256), 0, s, r);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)wgrad_reduce_grid(CP, r.ncols)), dim3(256), 0, s, r);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
+}
+
+// the two environment switches, read once per process (no device needed: the dry run reads them too)
+static void wgrad_read_env() {
+    static bool done = false;
+    if (done) return;
+    if (const char* e = getenv("W2L_WGRAD_CFG")) wgrad_force_cfg = atoi(e);
+    if (const char* e = getenv("W2L_WINO_WGRAD")) wgrad_wino = atoi(e);
+    done = true;
 }
 
 int wgrad_init_attrs() {
@@ -616,9 +633,118 @@ int wgrad_init_attrs() {
     for (const WgradCfg& c : kWgradBf16Cfgs)
         W2L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(c.kernel),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, c.lds));
-    if (const char* e = getenv("W2L_WGRAD_CFG")) wgrad_force_cfg = atoi(e);
-    if (const char* e = getenv("W2L_WINO_WGRAD")) wgrad_wino = atoi(e);
     done = true;
+    return W2L_OK;
+}
+
+// What a launch of w2l_conv_wgrad(_prec) runs: filled by wgrad_plan, executed by wgrad_impl, reported by w2l_conv_wgrad_resolve
+struct WgradPlan {
+    int family;             // W2L_WGRAD_WINO / _DIRECT / _SMALL
+    int cfg_id;             // row of kWgradCfgs (fp32) or kWgradBf16Cfgs (bf16); -1 for the Winograd and small-head kernels
+    const WgradCfg* cfg;    // direct GEMM only
+    int ksplit;             // K ranges = workgroups along the split axis (small head: its blocks)
+    int K, kstep, chunk;    // reduction length, K-step and range length in P pixels (Winograd: in 2x2 tiles)
+    int CP, CQ;
+    long long tiles;        // direct GEMM: M x N tiles
+    WgradKArgs a;           // geometry of the direct / small-head kernels; p, q, ws unset
+};
+
+// the argument checks that need no pointer + every launch rule of the fp32 / split-operand bf16 weight gradient
+static int wgrad_plan(const w2l_conv_geom* g, int N, int H, int W, int x_cs, int dz_cs, int precision, WgradPlan* pl) {
+    W2L_REQUIRE(g, "NULL argument");
+    W2L_REQUIRE(precision == W2L_PREC_F32 || precision == W2L_PREC_BF16, "bad precision %d", precision);
+    W2L_REQUIRE(N >= 1 && H >= 1 && W >= 1, "bad shape N=%d H=%d W=%d", N, H, W);
+    int Ho, Wo;
+    if (w2l_conv_out_hw(g, H, W, &Ho, &Wo) != W2L_OK) return W2L_ERR_ARG;
+    const int cin_p = round_up(g->cin, 4), cout_p = round_up(g->cout, 4);
+    W2L_REQUIRE(x_cs >= cin_p && (x_cs & 3) == 0 && dz_cs >= cout_p && (dz_cs & 3) == 0,
+                "wgrad: x_cs=%d / dz_cs=%d must be multiples of 4 covering the padded channel counts %d / %d", x_cs, dz_cs,
+                cin_p, cout_p);
+    const long long lim = 1ll << 31;
+    W2L_REQUIRE((long long)N * H * W * x_cs * 4 < lim && (long long)N * Ho * Wo * dz_cs * 4 < lim,
+                "activation buffer larger than 2 GiB: split the batch");
+    wgrad_read_env();
+    WgradKArgs& a = pl->a;
+    a = WgradKArgs{};
+    pl->cfg = nullptr;
+    pl->cfg_id = -1;
+    pl->tiles = 0;
+    pl->CP = g->transposed ? g->cin : g->cout;
+    pl->CQ = g->transposed ? g->cout : g->cin;
+    if (precision == W2L_PREC_F32 && wgrad_wino && wgrad_force_cfg < 0 && wino_wgrad_ok(g, N, H, W, x_cs, dz_cs)) {
+        pl->family = W2L_WGRAD_WINO;
+        wino_wgrad_plan_info(g, N, H, W, x_cs, dz_cs, &pl->K, &pl->kstep, &pl->chunk, &pl->ksplit);
+        a.CQp = cin_p;
+        a.ncols = 9 * cin_p;
+        return W2L_OK;
+    }
+    a.N = N;
+    if (!g->transposed) {   // P = dz on the output grid, Q = x
+        a.Hp = Ho; a.Wp = Wo; a.CPp = cout_p; a.p_cs = dz_cs;
+        a.Hq = H; a.Wq = W; a.CQp = cin_p; a.q_cs = x_cs;
+    } else {                // P = x on the input grid, Q = dz
+        a.Hp = H; a.Wp = W; a.CPp = cin_p; a.p_cs = x_cs;
+        a.Hq = Ho; a.Wq = Wo; a.CQp = cout_p; a.q_cs = dz_cs;
+    }
+    a.sy = g->sh; a.sx = g->sw; a.py = g->ph; a.px = g->pw;
+    a.kh = g->kh; a.kw = g->kw;
+    a.K = N * a.Hp * a.Wp;
+    a.ncols = g->kh * g->kw * a.CQp;
+    a.inv_hw = 1.0f / (float)(a.Hp * a.Wp);
+    a.inv_w = 1.0f / (float)a.Wp;
+    pl->K = a.K;
+    if (a.CPp == 4 && a.ncols <= 1024) {   // tiny head: HBM-bound reduction kernel
+        pl->family = W2L_WGRAD_SMALL;
+        a.Mp = 4; a.Np = a.ncols; a.tiles_n = 1;
+        const int RPP = 256 / (a.ncols >> 2);
+        long long nb = a.K / ((long long)RPP * 64);
+        if (nb > 1024) nb = 1024;
+        if (nb < 1) nb = 1;
+        a.chunk = ceil_div(a.K, (int)nb);
+        pl->kstep = RPP;
+        pl->chunk = a.chunk;
+        pl->ksplit = ceil_div(a.K, a.chunk);
+        return W2L_OK;
+    }
+    pl->family = W2L_WGRAD_DIRECT;
+    // fast_divmod is exact for quotients below 2^22 only (image index n < N, row y < Hp; the numerators stay below 2^27 under
+    // the 2 GiB guard): a batch of more than four million tiny images would lose pixels silently
+    W2L_REQUIRE(N < (1 << 22) && a.Hp < (1 << 22), "wgrad: N=%d / %d rows exceed the index arithmetic's range (2^22): split the batch",
+                N, a.Hp);
+    // tile rows: 32 for CP <= 32, else 64 or 128 — whichever pads the channel axis less (ties: the larger tile);
+    // 32/64-row tiles come in two N widths: take the one that pads the (tap, cq) axis less (ties: the wider tile)
+    int ci = 0;
+    const bool rows64 = a.CPp <= 64 || round_up(a.CPp, 64) * 10 < round_up(a.CPp, 128) * 9;
+    if (a.CPp <= 32 || rows64) {
+        const int wide = a.CPp <= 32 ? 3 : 1;
+        ci = round_up(a.ncols, 128) * 10 < round_up(a.ncols, 256) * 9 ? wide + 1 : wide;
+    }
+    if (wgrad_force_cfg >= 0 && wgrad_force_cfg < (int)(sizeof(kWgradCfgs) / sizeof(kWgradCfgs[0])) &&
+        kWgradCfgs[wgrad_force_cfg].bm >= (a.CPp <= 32 ? 32 : 64))
+        ci = wgrad_force_cfg;
+    if (precision == W2L_PREC_BF16) ci = 2 * (a.CPp <= 32 ? 2 : ((a.CPp <= 64 || rows64) ? 1 : 0)) + ((a.Wp & 7) == 0 ? 1 : 0);
+    const WgradCfg& cfg = precision == W2L_PREC_BF16 ? kWgradBf16Cfgs[ci] : kWgradCfgs[ci];
+    pl->cfg = &cfg;
+    pl->cfg_id = ci;
+    const int tiles_m = ceil_div(a.CPp, cfg.bm);
+    a.tiles_n = ceil_div(a.ncols, cfg.bn);
+    a.Mp = tiles_m * cfg.bm;
+    a.Np = a.tiles_n * cfg.bn;
+    pl->tiles = (long long)tiles_m * a.tiles_n;
+    // K splits: all workgroups have equal work and run in lock step, so a grid slightly LARGER than the resident capacity
+    // (256 CUs x wg_per_cu) costs a whole extra round; size the split to fill exactly one round (at least 8 K-steps per
+    // workgroup, workspace capped at 512 MiB)
+    const long long slots = 256ll * cfg.wg_per_cu;
+    long long ks = pl->tiles >= slots ? 1 : slots / pl->tiles;
+    const long long max_by_k = a.K / (8 * cfg.bk) > 0 ? a.K / (8 * cfg.bk) : 1;
+    if (ks > max_by_k) ks = max_by_k;
+    const long long max_by_ws = (512ll << 20) / ((long long)a.Mp * a.Np * 4);
+    if (ks > max_by_ws) ks = max_by_ws;
+    if (ks < 1) ks = 1;
+    a.chunk = round_up(ceil_div(a.K, (int)ks), cfg.bk);
+    pl->kstep = cfg.bk;
+    pl->chunk = a.chunk;
+    pl->ksplit = ceil_div(a.K, a.chunk);
     return W2L_OK;
 }
 
@@ -636,109 +762,66 @@ extern "C" int w2l_conv_wgrad(const w2l_conv_geom* g, void* stream, int N, int H
 
 extern "C" int w2l_conv_wgrad_prec(const w2l_conv_geom* g, void* stream, int N, int H, int W, const float* x, int x_cs,
                                    const float* dz, int dz_cs, float* dweight, int precision) {
-    W2L_REQUIRE(precision == W2L_PREC_F32 || precision == W2L_PREC_BF16, "bad precision %d", precision);
     return wgrad_impl(g, stream, N, H, W, x, x_cs, dz, dz_cs, dweight, precision);
+}
+
+extern "C" int w2l_conv_wgrad_resolve(const w2l_conv_geom* g, int N, int H, int W, int x_cs, int dz_cs, int precision,
+                                      w2l_wgrad_info* out) {
+    W2L_REQUIRE(out, "NULL argument");
+    WgradPlan pl;
+    const int rc = wgrad_plan(g, N, H, W, x_cs, dz_cs, precision, &pl);
+    if (rc != W2L_OK) return rc;
+    out->family = pl.family;
+    out->cfg = pl.cfg_id;
+    out->ksplit = pl.ksplit;
+    out->chunk = pl.chunk;
+    out->K = pl.K;
+    out->kstep = pl.kstep;
+    out->reduce_blocks = wgrad_reduce_grid(pl.CP, pl.a.ncols);
+    return W2L_OK;
+}
+
+extern "C" int w2l_conv_wgrad_set_cfg(int cfg, int wino) {
+    W2L_REQUIRE(cfg >= -1 && cfg < (int)(sizeof(kWgradCfgs) / sizeof(kWgradCfgs[0])) && (wino == 0 || wino == 1),
+                "w2l_conv_wgrad_set_cfg: cfg %d / wino %d out of range", cfg, wino);
+    wgrad_read_env();   // a later first launch must not overwrite the values set here
+    wgrad_force_cfg = cfg;
+    wgrad_wino = wino;
+    return W2L_OK;
+}
+
+extern "C" int w2l_wgrad_divmod_host(int which, int n, const int* a, const int* d, int* q, int* r) {
+    W2L_REQUIRE((which == 0 || which == 1) && n >= 0 && a && d && q && r, "w2l_wgrad_divmod_host: bad argument");
+    for (int i = 0; i < n; ++i) {
+        W2L_REQUIRE(a[i] >= 0 && d[i] >= 1, "w2l_wgrad_divmod_host: a=%d d=%d", a[i], d[i]);
+        if (which == 0) fast_divmod(a[i], d[i], 1.0f / (float)d[i], q[i], r[i]);
+        else wino_divmod_host(a[i], d[i], &q[i], &r[i]);
+    }
+    return W2L_OK;
 }
 
 static int wgrad_impl(const w2l_conv_geom* g, void* stream, int N, int H, int W, const float* x, int x_cs, const float* dz,
                       int dz_cs, float* dweight, int precision) {
     W2L_REQUIRE(g && x && dz && dweight, "NULL argument");
-    W2L_REQUIRE(N >= 1 && H >= 1 && W >= 1, "bad shape N=%d H=%d W=%d", N, H, W);
-    int Ho, Wo;
-    if (w2l_conv_out_hw(g, H, W, &Ho, &Wo) != W2L_OK) return W2L_ERR_ARG;
-    const int cin_p = round_up(g->cin, 4), cout_p = round_up(g->cout, 4);
-    W2L_REQUIRE(x_cs >= cin_p && (x_cs & 3) == 0 && dz_cs >= cout_p && (dz_cs & 3) == 0,
-                "wgrad: x_cs=%d / dz_cs=%d must be multiples of 4 covering the padded channel counts %d / %d", x_cs, dz_cs,
-                cin_p, cout_p);
     W2L_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dz)) & 15) == 0, "x and dz must be 16-byte aligned");
-    const long long lim = 1ll << 31;
-    W2L_REQUIRE((long long)N * H * W * x_cs * 4 < lim && (long long)N * Ho * Wo * dz_cs * 4 < lim,
-                "activation buffer larger than 2 GiB: split the batch");
+    WgradPlan pl;
+    const int rc = wgrad_plan(g, N, H, W, x_cs, dz_cs, precision, &pl);
+    if (rc != W2L_OK) return rc;
     if (wgrad_init_attrs() != W2L_OK) return W2L_ERR_HIP;
-    if (precision == W2L_PREC_F32 && wgrad_wino && wgrad_force_cfg < 0 && wino_wgrad_ok(g, N, H, W, x_cs, dz_cs))
-        return wino_wgrad_launch(g, static_cast<hipStream_t>(stream), N, H, W, x, x_cs, dz, dz_cs, dweight);
-    WgradKArgs a;
-    a.N = N;
-    if (!g->transposed) {   // P = dz on the output grid, Q = x
-        a.p = dz; a.Hp = Ho; a.Wp = Wo; a.CPp = cout_p; a.p_cs = dz_cs;
-        a.q = x; a.Hq = H; a.Wq = W; a.CQp = cin_p; a.q_cs = x_cs;
-    } else {                // P = x on the input grid, Q = dz
-        a.p = x; a.Hp = H; a.Wp = W; a.CPp = cin_p; a.p_cs = x_cs;
-        a.q = dz; a.Hq = Ho; a.Wq = Wo; a.CQp = cout_p; a.q_cs = dz_cs;
-    }
-    const int CP = g->transposed ? g->cin : g->cout;
-    const int CQ = g->transposed ? g->cout : g->cin;
-    a.sy = g->sh; a.sx = g->sw; a.py = g->ph; a.px = g->pw;
-    a.kh = g->kh; a.kw = g->kw;
-    a.K = N * a.Hp * a.Wp;
-    a.ncols = g->kh * g->kw * a.CQp;
-    a.inv_hw = 1.0f / (float)(a.Hp * a.Wp);
-    a.inv_w = 1.0f / (float)a.Wp;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (a.CPp == 4 && a.ncols <= 1024) {   // tiny head: HBM-bound reduction kernel
-        a.Mp = 4; a.Np = a.ncols; a.tiles_n = 1;
-        const int RPP = 256 / (a.ncols >> 2);
-        long long nb = a.K / ((long long)RPP * 64);
-        if (nb > 1024) nb = 1024;
-        if (nb < 1) nb = 1;
-        a.chunk = ceil_div(a.K, (int)nb);
-        const int nblk = ceil_div(a.K, a.chunk);
-        a.ws = conv_workspace(s, (size_t)nblk * a.Mp * a.Np * sizeof(float));
-        if (!a.ws) return W2L_ERR_NOMEM;
-        if (flops_counting()) flops_add(2ll * a.Mp * a.Np * a.K, 7);
-        hipLaunchKernelGGL(conv_wgrad_small_kernel, dim3(nblk), dim3(256), 0, s, a);
-        W2L_HIP_CHECK(hipGetLastError());
-        WgradReduceArgs r;
-        r.ws = a.ws; r.dw = dweight; r.colsum = nullptr;
-        r.ksplit = nblk; r.Mp = a.Mp; r.Np = a.Np; r.CP = CP; r.CQ = CQ; r.CQp = a.CQp;
-        r.ntaps = g->kh * g->kw; r.ncols = a.ncols;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ceil_div(CP * a.ncols, 256)), dim3(256), 0, s, r);
-        W2L_HIP_CHECK(hipGetLastError());
-        return W2L_OK;
-    }
-    // tile rows: 32 for CP <= 32, else 64 or 128 — whichever pads the channel axis less (ties: the larger tile);
-    // 32/64-row tiles come in two N widths: take the one that pads the (tap, cq) axis less (ties: the wider tile)
-    int ci = 0;
-    const bool rows64 = a.CPp <= 64 || round_up(a.CPp, 64) * 10 < round_up(a.CPp, 128) * 9;
-    if (a.CPp <= 32 || rows64) {
-        const int wide = a.CPp <= 32 ? 3 : 1;
-        ci = round_up(a.ncols, 128) * 10 < round_up(a.ncols, 256) * 9 ? wide + 1 : wide;
-    }
-    if (wgrad_force_cfg >= 0 && wgrad_force_cfg < (int)(sizeof(kWgradCfgs) / sizeof(kWgradCfgs[0])) &&
-        kWgradCfgs[wgrad_force_cfg].bm >= (a.CPp <= 32 ? 32 : 64))
-        ci = wgrad_force_cfg;
-    const WgradCfg& cfg = precision == W2L_PREC_BF16
-                              ? kWgradBf16Cfgs[2 * (a.CPp <= 32 ? 2 : ((a.CPp <= 64 || rows64) ? 1 : 0)) + ((a.Wp & 7) == 0 ? 1 : 0)]
-                              : kWgradCfgs[ci];
-    const int tiles_m = ceil_div(a.CPp, cfg.bm);
-    a.tiles_n = ceil_div(a.ncols, cfg.bn);
-    a.Mp = tiles_m * cfg.bm;
-    a.Np = a.tiles_n * cfg.bn;
-    const long long tiles = (long long)tiles_m * a.tiles_n;
-    // K splits: all workgroups have equal work and run in lock step, so a grid slightly LARGER than the resident capacity
-    // (256 CUs x wg_per_cu) costs a whole extra round; size the split to fill exactly one round (at least 8 K-steps per
-    // workgroup, workspace capped at 512 MiB)
-    const long long slots = 256ll * cfg.wg_per_cu;
-    long long ks = tiles >= slots ? 1 : slots / tiles;
-    const long long max_by_k = a.K / (8 * cfg.bk) > 0 ? a.K / (8 * cfg.bk) : 1;
-    if (ks > max_by_k) ks = max_by_k;
-    const long long max_by_ws = (512ll << 20) / ((long long)a.Mp * a.Np * 4);
-    if (ks > max_by_ws) ks = max_by_ws;
-    if (ks < 1) ks = 1;
-    a.chunk = round_up(ceil_div(a.K, (int)ks), cfg.bk);
-    const int ksplit = ceil_div(a.K, a.chunk);
-    a.ws = conv_workspace(s, (size_t)ksplit * a.Mp * a.Np * sizeof(float));
+    if (pl.family == W2L_WGRAD_WINO) return wino_wgrad_launch(g, s, N, H, W, x, x_cs, dz, dz_cs, dweight);
+    WgradKArgs& a = pl.a;
+    a.p = g->transposed ? x : dz;
+    a.q = g->transposed ? dz : x;
+    a.ws = conv_workspace(s, (size_t)pl.ksplit * a.Mp * a.Np * sizeof(float));
     if (!a.ws) return W2L_ERR_NOMEM;
-    if (flops_counting()) flops_add(2ll * a.Mp * a.Np * (long long)ksplit * a.chunk, precision == W2L_PREC_BF16 ? 4 : 1);
-    hipLaunchKernelGGL(cfg.kernel, dim3((unsigned)tiles, 1, ksplit), dim3(256), cfg.lds, s, a);
+    if (pl.family == W2L_WGRAD_SMALL) {
+        if (flops_counting()) flops_add(2ll * a.Mp * a.Np * a.K, 7);
+        hipLaunchKernelGGL(conv_wgrad_small_kernel, dim3(pl.ksplit), dim3(256), 0, s, a);
+    } else {
+        if (flops_counting()) flops_add(2ll * a.Mp * a.Np * (long long)pl.ksplit * a.chunk, precision == W2L_PREC_BF16 ? 4 : 1);
+        hipLaunchKernelGGL(pl.cfg->kernel, dim3((unsigned)pl.tiles, 1, pl.ksplit), dim3(256), pl.cfg->lds, s, a);
+    }
     W2L_HIP_CHECK(hipGetLastError());
-    WgradReduceArgs r;
-    r.ws = a.ws; r.dw = dweight; r.colsum = nullptr;
-    r.ksplit = ksplit; r.Mp = a.Mp; r.Np = a.Np; r.CP = CP; r.CQ = CQ; r.CQp = a.CQp;
-    r.ntaps = g->kh * g->kw; r.ncols = a.ncols;
-    long long gr = ((long long)CP * a.ncols + 255) / 256;
-    if (gr > 8192) gr = 8192;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)gr), dim3(256), 0, s, r);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
+    return wgrad_reduce_launch(s, a.ws, dweight, pl.ksplit, a.Mp, a.Np, pl.CP, pl.CQ, a.CQp, g->kh * g->kw);
 }

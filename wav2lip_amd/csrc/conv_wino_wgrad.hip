@@ -47,7 +47,7 @@ __device__ __forceinline__ f32x4 qload4(__amdgpu_buffer_rsrc_t r, unsigned byte_
     return __builtin_bit_cast(f32x4, v);
 }
 
-__device__ __forceinline__ void divmod_f(int a, int d, float inv_d, int& q, int& r) {
+__host__ __device__ __forceinline__ void divmod_f(int a, int d, float inv_d, int& q, int& r) {
     q = (int)((float)a * inv_d);
     r = a - q * d;
     const int lo = r < 0 ? 1 : 0, hi = r >= d ? 1 : 0;
@@ -333,16 +333,10 @@ bool wino_wgrad_ok(const w2l_conv_geom* g, int N, int H, int W, int x_cs, int dz
     return T >= 64 * kKT && T / tiles >= 4 * kKT && T < (1ll << 24);    // enough tiles to amortise the 16-accumulator epilogue
 }
 
-int wino_wgrad_launch(const w2l_conv_geom* g, hipStream_t s, int N, int H, int W, const float* x, int x_cs, const float* dz,
-                      int dz_cs, float* dweight) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        W2L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_wgrad_f32_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, kWinoWgradLds));
-        attr_done = true;
-    }
-    WinoWgradArgs a;
-    a.x = x; a.dz = dz;
+// the tile grid and the K split of a launch: the one place these rules live (wino_wgrad_launch runs them, wino_wgrad_plan_info
+// reports them); returns the K split
+static int wino_wgrad_plan(const w2l_conv_geom* g, int N, int H, int W, int x_cs, int dz_cs, WinoWgradArgs* ap) {
+    WinoWgradArgs& a = *ap;
     a.N = N; a.H = H; a.W = W;
     a.cin = g->cin; a.cin_p = round_up(g->cin, 4); a.x_cs = x_cs;
     a.cout = g->cout; a.cout_p = round_up(g->cout, 4); a.dz_cs = dz_cs;
@@ -363,7 +357,33 @@ int wino_wgrad_launch(const w2l_conv_geom* g, hipStream_t s, int N, int H, int W
     if (ks > max_by_ws) ks = max_by_ws;
     if (ks < 1) ks = 1;
     a.chunk = round_up(ceil_div(a.T, (int)ks), kKT);
-    const int ksplit = ceil_div(a.T, a.chunk);
+    return ceil_div(a.T, a.chunk);
+}
+
+void wino_wgrad_plan_info(const w2l_conv_geom* g, int N, int H, int W, int x_cs, int dz_cs, int* T, int* kstep, int* chunk,
+                          int* ksplit) {
+    WinoWgradArgs a;
+    *ksplit = wino_wgrad_plan(g, N, H, W, x_cs, dz_cs, &a);
+    *T = a.T;
+    *kstep = kKT;
+    *chunk = a.chunk;
+}
+
+// divmod_f on the host with the reciprocal the launcher passes (tests/test_wgrad_divmod_cpu.py)
+void wino_divmod_host(int a, int d, int* q, int* r) { divmod_f(a, d, 1.0f / (float)d, *q, *r); }
+
+int wino_wgrad_launch(const w2l_conv_geom* g, hipStream_t s, int N, int H, int W, const float* x, int x_cs, const float* dz,
+                      int dz_cs, float* dweight) {
+    static bool attr_done = false;
+    if (!attr_done) {
+        W2L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino_wgrad_f32_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, kWinoWgradLds));
+        attr_done = true;
+    }
+    WinoWgradArgs a;
+    a.x = x; a.dz = dz;
+    const int ksplit = wino_wgrad_plan(g, N, H, W, x_cs, dz_cs, &a);
+    const int tiles = ceil_div(g->cout, 64) * a.tiles_n;
     a.ws = conv_workspace(s, (size_t)ksplit * a.Mp * a.Np * sizeof(float));
     if (!a.ws) return W2L_ERR_NOMEM;
     // the reduce only reads (co < cout, ci < cin), all of which the kernel writes: no clearing of the workspace

@@ -242,11 +242,21 @@ static int thin_grid(long long npix) {
     return (int)(g < 1 ? 1 : g);
 }
 
+// partial rows (= workgroups) of the weight gradient: what w2l_thin1x1_wgrad_bf16 launches and w2l_thin1x1_wgrad_blocks reports
+static int thin_wgrad_blocks(long long npix) {
+    long long nb = (npix + 256 * 8 - 1) / (256 * 8);      // >= 8 pixels per thread: the register partials are worth their fold
+    if (nb > 512) nb = 512;                               // two workgroups per CU; every partial row is one more row of the final walk
+    if (nb < 1) nb = 1;
+    return (int)nb;
+}
+
 }  // namespace w2l
 
 using namespace w2l;
 
 extern "C" {
+
+int w2l_thin1x1_wgrad_blocks(long long npix) { return thin_wgrad_blocks(npix); }
 
 int w2l_thin1x1_forward_bf16(void* stream, long long npix, int cin, int cout, const void* x, int x_cs, const float* w,
                              const float* bias, int act, void* y, int y_cs) {
@@ -287,9 +297,7 @@ int w2l_thin1x1_wgrad_bf16(void* stream, long long npix, int cin, int cout, cons
         return W2L_ERR_ARG;
     W2L_REQUIRE(dweight, "thin1x1_wgrad_bf16: NULL output");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    long long nb = (npix + 256 * 8 - 1) / (256 * 8);      // >= 8 pixels per thread: the register partials are worth their fold
-    if (nb > 512) nb = 512;                               // two workgroups per CU; every partial row is one more row of the final walk
-    if (nb < 1) nb = 1;
+    const int nb = thin_wgrad_blocks(npix);
     constexpr int NV = kThinMaxCout * kThinMaxCin + kThinMaxCout;
     ThinArgs a = {};
     a.x = static_cast<const __bf16*>(x); a.dz = static_cast<const __bf16*>(dz); a.npix = npix;
@@ -298,7 +306,7 @@ int w2l_thin1x1_wgrad_bf16(void* stream, long long npix, int cin, int cout, cons
     if (!a.partial) return W2L_ERR_NOMEM;
     hipLaunchKernelGGL(thin1x1_wgrad_bf16_kernel, dim3((unsigned)nb), dim3(256), 0, s, a);
     W2L_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(thin1x1_wgrad_final_kernel, dim3(1), dim3(1024), 0, s, a.partial, (int)nb, cin, cout, dweight, dbias);
+    hipLaunchKernelGGL(thin1x1_wgrad_final_kernel, dim3(1), dim3(1024), 0, s, a.partial, nb, cin, cout, dweight, dbias);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

@@ -315,9 +315,13 @@ static int wgb_init_attrs() {
 
 using namespace w2l;
 
-extern "C" int w2l_conv_wgrad_bf16(const w2l_conv_geom* g, void* stream, int N, int H, int W, const void* x, int x_cs,
-                                    const void* dz, int dz_cs, float* dweight) {
-    W2L_REQUIRE(g && x && dz && dweight, "NULL argument");
+// the argument checks that need no pointer + every launch rule of the bf16-storage weight gradient: box, tap groups, K split.
+// Fills everything of `a` but P, Q and ws.  The launch runs this plan, w2l_conv_wgrad_bf16_resolve reports it.
+static int wgb_plan(const w2l_conv_geom* g, int N, int H, int W, int x_cs, int dz_cs, WgB* ap, int* ntiles_out, int* splits_out,
+                    int* lds_out) {
+    WgB& a = *ap;
+    a = WgB{};
+    W2L_REQUIRE(g, "NULL argument");
     W2L_REQUIRE(N >= 1 && H >= 1 && W >= 1, "bad shape N=%d H=%d W=%d", N, H, W);
     int Ho, Wo;
     if (w2l_conv_out_hw(g, H, W, &Ho, &Wo) != W2L_OK) return W2L_ERR_ARG;
@@ -325,19 +329,16 @@ extern "C" int w2l_conv_wgrad_bf16(const w2l_conv_geom* g, void* stream, int N, 
     const int cin8 = round_up(g->cin, 8), cout8 = round_up(g->cout, 8);
     W2L_REQUIRE(x_cs >= cin8 && (x_cs & 7) == 0 && dz_cs >= cout8 && (dz_cs & 7) == 0,
                 "channel strides must be multiples of 8 covering the padded channels (x_cs=%d, dz_cs=%d)", x_cs, dz_cs);
-    W2L_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dz)) & 15) == 0, "x / dz must be 16-byte aligned");
     const long long lim = 1ll << 31;
     W2L_REQUIRE(((long long)N * H * W * x_cs) * 2 < lim && ((long long)N * Ho * Wo * dz_cs) * 2 < lim,
                 "activation buffer larger than 2 GiB: split the batch");
-    if (wgb_init_attrs() != W2L_OK) return W2L_ERR_HIP;
-    WgB a;
     a.N = N;
     if (!g->transposed) {   // P = dz on the output grid, Q = x
-        a.P = dz; a.Hp = Ho; a.Wp = Wo; a.p_cs = dz_cs; a.CP = g->cout;
-        a.Q = x; a.Hq = H; a.Wq = W; a.q_cs = x_cs; a.CQ = g->cin;
+        a.Hp = Ho; a.Wp = Wo; a.p_cs = dz_cs; a.CP = g->cout;
+        a.Hq = H; a.Wq = W; a.q_cs = x_cs; a.CQ = g->cin;
     } else {                // P = x on the input grid, Q = dz
-        a.P = x; a.Hp = H; a.Wp = W; a.p_cs = x_cs; a.CP = g->cin;
-        a.Q = dz; a.Hq = Ho; a.Wq = Wo; a.q_cs = dz_cs; a.CQ = g->cout;
+        a.Hp = H; a.Wp = W; a.p_cs = x_cs; a.CP = g->cin;
+        a.Hq = Ho; a.Wq = Wo; a.q_cs = dz_cs; a.CQ = g->cout;
     }
     a.CPp = round_up(a.CP, 8);
     a.CQp = round_up(a.CQ, 8);
@@ -391,12 +392,43 @@ extern "C" int w2l_conv_wgrad_bf16(const w2l_conv_geom* g, void* stream, int N, 
     if (splits > a.nboxes) splits = a.nboxes;
     a.boxes_per_split = ceil_div(a.nboxes, splits);
     splits = ceil_div(a.nboxes, a.boxes_per_split);
+    const int lds = a.mt * a.p_rows_pad * kWgRowB + a.qp * a.q_rows_pad * kWgRowB + kWgMaxKsub * 16 * 4;
+    W2L_REQUIRE(lds <= 80 * 1024, "weight gradient: LDS budget exceeded (%d bytes)", lds);
+    *ntiles_out = ntiles;
+    *splits_out = splits;
+    *lds_out = lds;
+    return W2L_OK;
+}
+
+extern "C" int w2l_conv_wgrad_bf16_resolve(const w2l_conv_geom* g, int N, int H, int W, int x_cs, int dz_cs,
+                                            w2l_wgrad_bf16_info* out) {
+    W2L_REQUIRE(out, "NULL argument");
+    WgB a;
+    int ntiles, splits, lds;
+    const int rc = wgb_plan(g, N, H, W, x_cs, dz_cs, &a, &ntiles, &splits, &lds);
+    if (rc != W2L_OK) return rc;
+    out->ni = a.ni; out->bh = a.bh; out->bw = a.bw;
+    out->nboxes = a.nboxes; out->splits = splits; out->boxes_per_split = a.boxes_per_split;
+    out->ntg = a.ntg; out->tg = a.tg; out->ncq = a.ncq; out->mt = a.mt; out->qp = a.qp;
+    return W2L_OK;
+}
+
+extern "C" int w2l_conv_wgrad_bf16(const w2l_conv_geom* g, void* stream, int N, int H, int W, const void* x, int x_cs,
+                                    const void* dz, int dz_cs, float* dweight) {
+    W2L_REQUIRE(g && x && dz && dweight, "NULL argument");
+    W2L_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dz)) & 15) == 0, "x / dz must be 16-byte aligned");
+    WgB a;
+    int ntiles, splits, lds;
+    const int rc = wgb_plan(g, N, H, W, x_cs, dz_cs, &a, &ntiles, &splits, &lds);
+    if (rc != W2L_OK) return rc;
+    if (wgb_init_attrs() != W2L_OK) return W2L_ERR_HIP;
+    a.P = g->transposed ? x : dz;
+    a.Q = g->transposed ? dz : x;
+    const int ncp = ceil_div(a.CPp, 64);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t ws_bytes = (size_t)splits * a.CP * a.wcols * sizeof(float);
     a.ws = conv_workspace(s, ws_bytes);
     if (!a.ws) return W2L_ERR_NOMEM;
-    const int lds = a.mt * a.p_rows_pad * kWgRowB + a.qp * a.q_rows_pad * kWgRowB + kWgMaxKsub * 16 * 4;
-    W2L_REQUIRE(lds <= 80 * 1024, "weight gradient: LDS budget exceeded (%d bytes)", lds);
     if (flops_counting()) {
         // per box and workgroup: ksubs K-substeps x mt M-tiles x (9 * 4 / mt) N-tile slots of which the valid ones issue an MFMA
         long long nt_sum = 0;
