@@ -9,7 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from test_conv_gpu import SIGS
-from wav2lip_amd import _lib, bf16
+from wav2lip_amd import _lib, autograd, bf16
 from wav2lip_amd._lib import ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID, ConvGeom
 
 pytestmark = pytest.mark.gpu
@@ -360,7 +360,7 @@ def test_data_gradient_launch_reduces_the_batchnorm_backward_sums(case, cuda):
         "box_res": (64, 64, 3, 1, 1, 32, 120, 124, True, True, ACT_RELU), "box_plain": (64, 64, 3, 1, 1, 32, 128, 128, False, False, ACT_RELU)}[case]
     w = torch.randn(cout2, cin, k, k) / np.sqrt(cin * k * k)
     Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-    dg = ConvGeom(1, cout2, cin, k, k, s, s, p, p, (H + 2 * p - k) % s, (W + 2 * p - k) % s, ACT_NONE)    # as autograd.NodeB builds it
+    dg = autograd.dgrad_geom(ConvGeom(0, cin, cout2, k, k, s, s, p, p, 0, 0, ACT_NONE), H, W)    # as the train graph's nodes build it
     layer = bf16.ConvB(dg, w.to(cuda))
     assert layer.out_hw(Ho, Wo) == (H, W)
     Cp = bf16.round8(cin)
@@ -715,14 +715,14 @@ def test_fused_phase_transposed_kernel_batch_statistics(case, cuda):
 
 @pytest.mark.parametrize("cin,cout,N,H,W", [(16, 32, 40, 48, 48), (64, 128, 16, 24, 32), (128, 256, 40, 12, 12)])
 def test_fused_phase_kernel_serves_the_data_gradient_of_stride_2_convs(cin, cout, N, H, W, cuda):
-    """The data gradient of `Conv2d(cin, cout, kernel_size=3, stride=2, padding=1)` (models/wav2lip.py:17-30) as autograd.NodeB
-    builds it - the weight tensor read as a transposed layer cout -> cin, accumulating into an existing gradient - against float64"""
+    """The data gradient of `Conv2d(cin, cout, kernel_size=3, stride=2, padding=1)` (models/wav2lip.py:17-30) as the train graph's
+    nodes build it (autograd.dgrad_geom) - the weight tensor read as a transposed layer cout -> cin, accumulating into an existing gradient - against float64"""
     torch.manual_seed(cin)
     Ho, Wo = H // 2, W // 2
     w = torch.randn(cout, cin, 3, 3) / np.sqrt(cout * 9)
     dz = torch.randn(N, cout, Ho, Wo)
     acc = torch.randn(N, cin, H, W)
-    g = ConvGeom(1, cout, cin, 3, 3, 2, 2, 1, 1, (H + 2 - 3) % 2, (W + 2 - 3) % 2, ACT_NONE)
+    g = autograd.dgrad_geom(ConvGeom(0, cin, cout, 3, 3, 2, 2, 1, 1, 0, 0, ACT_NONE), H, W)
     layer = bf16.ConvB(g, w.to(cuda))
     assert layer.out_hw(Ho, Wo) == (H, W)
     ref = F.conv_transpose2d(_rb(dz), _rb(w), None, 2, 1, 1) + _rb(acc)

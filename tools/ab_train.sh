@@ -1,7 +1,8 @@
 #!/bin/bash
 # Same-box A/B of two builds of libw2l_hip on the bf16 training steps: alternates W2L_HIP_LIB between the two libraries REPS times.
 #   gpurun --timeout 900 -- 'bash tools/ab_train.sh <tag> [base_lib] [new_lib]'      (CFGS="3 4 5" REPS=3 STEPS=10)
-# ENVA / ENVB: extra environment of the two sides ("W2L_BWD_PRUNE=0 ..."), for switches that live in the Python layer.
+# ENVA / ENVB: extra environment of the two sides ("W2L_WGRAD_OVERLAP=0 ..."), for switches that live in the Python layer (the
+# backward-pruning switch this example used to name was removed after its experiment, like the other A/B levers of kept changes).
 TAG=${1:?tag}
 A=${2:-wav2lip_amd/lib/libw2l_hip_base.so}
 B=${3:-wav2lip_amd/lib/libw2l_hip.so}

@@ -20,7 +20,6 @@ A gradient region that already holds a contribution from another consumer is acc
 input; nothing is ever zero-filled per step.
 """
 import ctypes as C
-import os
 
 import torch
 
@@ -66,9 +65,7 @@ class RawConv:
               "conv_update")
 
     def out_hw(self, H, W):
-        ho, wo = C.c_int(), C.c_int()
-        check(self._lib.w2l_conv_out_hw(C.byref(self.geom), H, W, C.byref(ho), C.byref(wo)), "conv_out_hw")
-        return ho.value, wo.value
+        return out_hw(self.geom, H, W)
 
     def _plan(self, x, y, res):
         lib = self._lib
@@ -130,26 +127,50 @@ def describe(blk):
     return blk._conv, None, blk._act, False, False
 
 
+def block_geom(blk, act=None):
+    """the ConvGeom of a block's conv, with the block's own activation or `act` in its place"""
+    conv, _, blk_act, transposed, _ = describe(blk)
+    kh, kw = engine._pair(conv.kernel_size)
+    sh, sw = engine._pair(conv.stride)
+    ph, pw = engine._pair(conv.padding)
+    oph, opw = engine._pair(conv.output_padding) if transposed else (0, 0)
+    return ConvGeom(int(transposed), conv.in_channels, conv.out_channels, kh, kw, sh, sw, ph, pw, oph, opw,
+                    blk_act if act is None else act)
+
+
+def out_hw(geom, H, W):
+    """output size of a conv geometry over an [H, W] input: the library's rule (w2l_conv_out_hw), no layer handle needed"""
+    ho, wo = C.c_int(), C.c_int()
+    check(_lib.load().w2l_conv_out_hw(C.byref(geom), H, W, C.byref(ho), C.byref(wo)), "conv_out_hw")
+    return ho.value, wo.value
+
+
+def dgrad_geom(geom, H, W):
+    """the data gradient of `geom` over an [H, W] input = the same weight tensor read with the other interpretation (conv <->
+    transposed conv); the output padding restores the rows and columns a strided conv's floor division dropped"""
+    g = geom
+    if g.transposed:
+        return ConvGeom(0, g.cout, g.cin, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, 0, 0, ACT_NONE)
+    return ConvGeom(1, g.cout, g.cin, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, (H + 2 * g.ph - g.kh) % g.sh, (W + 2 * g.pw - g.kw) % g.sw,
+                    ACT_NONE)
+
+
 def _ver(t):
     return None if t is None else (t.data_ptr(), t._version, engine.PARAM_EPOCH[0])
 
 
 class Node:
-    """one block of a TrainGraph: x slice -> y slice"""
+    """one block of a TrainGraph: x slice -> y slice.  This base holds what does not depend on how activations are stored: the
+    block's kind and geometries, the parameter-version state and the order of a backward pass.  `NodeF` (fp32 buffers) and `NodeB`
+    (bf16 buffers) supply the layer handles, `forward`, and the launches behind each backward step."""
 
-    def __init__(self, graph, name, blk, x, y):
-        self.graph, self.name, self.blk, self.x, self.y = graph, name, blk, x, y
+    def __init__(self, graph, name, blk, x, y, lane):
+        self.graph, self.name, self.blk, self.x, self.y, self.lane = graph, name, blk, x, y, lane
         conv, bn, act, transposed, residual = describe(blk)
         self.conv, self.bn, self.act, self.transposed, self.residual = conv, bn, act, transposed, residual
-        dev = graph.device
         self.lib = graph.lib
-        kh, kw = engine._pair(conv.kernel_size)
-        sh, sw = engine._pair(conv.stride)
-        ph, pw = engine._pair(conv.padding)
-        oph, opw = engine._pair(conv.output_padding) if transposed else (0, 0)
         cin, cout = conv.in_channels, conv.out_channels
-        self.cin, self.cout = cin, cout
-        self.cout_p = _round4(cout)
+        self.cin, self.cout, self.cout_p = cin, cout, graph.rnd(cout)
         if bn is None:
             self.kind = "plain"
         elif bn.training:
@@ -158,52 +179,129 @@ class Node:
                 raise NotImplementedError("BatchNorm2d variants other than the reference's default are not on the hot path")
         else:
             self.kind = "bn_eval"
-        fwd_act = ACT_NONE if self.kind == "bn" else act
-        self.geom = ConvGeom(int(transposed), cin, cout, kh, kw, sh, sw, ph, pw, oph, opw, fwd_act)
-        ones, zeros = const_vec(dev, cout, 1.0), const_vec(dev, cout, 0.0)
-        self.fold_scale = torch.ones(cout, device=dev)
-        self.fold_shift = torch.zeros(cout, device=dev)
         self.precision = engine.TRAIN_PRECISION[0]
-        self.fwd = RawConv(self.geom, conv.weight.detach(), ones, zeros, self.precision)
-        ho, wo = self.fwd.out_hw(x.H, x.W)
+        self.geom = block_geom(blk, ACT_NONE if self.kind == "bn" else act)
+        ho, wo = out_hw(self.geom, x.H, x.W)
         if (y.H, y.W, y.N) != (ho, wo, x.N) or y.C != cout:
             raise RuntimeError("train graph %s: output slice %s does not match %s" %
                                (name, (y.N, y.H, y.W, y.C), (x.N, ho, wo, cout)))
-        if x.C < cin or x.cs - x.off < _round4(cin):
-            raise RuntimeError("train graph %s: input slice too narrow" % name)
+        if x.C < cin or x.cs - x.off < graph.rnd(cin) or y.cs - y.off < self.cout_p:
+            raise RuntimeError("train graph %s: input / output slice too narrow" % name)
         self.rows = y.N * y.H * y.W
-        # data gradient = the same weight tensor read with the other interpretation (conv <-> transposed conv)
-        if not transposed:
-            dg = ConvGeom(1, cout, cin, kh, kw, sh, sw, ph, pw, (x.H + 2 * ph - kh) % sh, (x.W + 2 * pw - kw) % sw, ACT_NONE)
-        else:
-            dg = ConvGeom(0, cout, cin, kh, kw, sh, sw, ph, pw, 0, 0, ACT_NONE)
-        self.dgrad_geom = dg
-        self.dgrad = None          # built on first backward that needs it
-        if self.kind == "bn":
-            self.z = engine.new_buf(y.N, y.H, y.W, cout, dev)
-            self.mean = torch.empty(cout, device=dev)
-            self.rstd = torch.empty(cout, device=dev)
-            self.scale = torch.empty(cout, device=dev)
-            self.shift = torch.empty(cout, device=dev)
+        self.dgrad_geom = dgrad_geom(self.geom, x.H, x.W)
+        self.fwd = self.dgrad = None    # layer handles: the subclass builds `fwd`; `dgrad` on the first backward that needs it
         self._seen = None
         self._own_dz = None
+        self.sums_for = None      # the block whose dy this node's data gradient completes (TrainGraph._plan_bwd_fusion)
+        self._bwd_sums = None     # what the launch that wrote this block's dy already reduced in its epilogue (NodeB)
 
     # ---- parameters -> packed handles (weights change every optimiser step)
     def parameters(self):
         """the parameters this node can produce gradients for"""
         return (self.conv.weight, self.conv.bias) + ((self.bn.weight, self.bn.bias) if self.bn is not None else ())
 
-    def _zero_bias_grad(self):
-        """the bias of a conv in front of batch statistics has an exactly zero gradient: a slice of the backward pass's one zero
-        buffer (TrainGraph.zero_slice)"""
-        return self.graph.zero_slice(self.cout)
-
-    def refresh(self):
+    def _state(self):
         conv, bn = self.conv, self.bn
-        seen = (_ver(conv.weight), _ver(conv.bias)) + (
+        return (_ver(conv.weight), _ver(conv.bias)) + (
             (_ver(bn.weight), _ver(bn.bias), _ver(bn.running_mean), _ver(bn.running_var)) if self.kind == "bn_eval" else ())
-        if seen == self._seen:
-            return
+
+    def stale_weights(self):
+        """(layer handle, master weight) pairs that TrainGraph.forward re-packs for all its nodes in one launch before it calls
+        refresh(packed=True); none for a node that packs its own weights in refresh()"""
+        return ()
+
+    def refresh(self, packed=False):
+        seen = self._state()
+        if seen != self._seen:
+            self._update(packed)
+            self._seen = seen
+
+    # ---- backward: take a dz buffer -> activation / BatchNorm backward -> parameter gradients -> data gradient -> release
+    def backward(self, gy, gx, accumulate, want):
+        """gy: gradient slice of y (overwritten with the masked gradient when the block is residual); gx: gradient slice
+        of x or None; accumulate: gx already holds another consumer's contribution; want: parameter -> bool.
+        Returns {parameter: gradient tensor}."""
+        graph, y = self.graph, self.y
+        wstream = graph.wgrad_stream_for_step()
+        if wstream is not None:
+            # weight gradients run on their own stream (_side_wgrad): this block's dz must then outlive the next block's
+            # backward, so it gets a buffer of its own instead of a pooled one
+            if self._own_dz is None:
+                self._own_dz = torch.zeros((y.N, y.H, y.W, self.cout_p), device=graph.device, dtype=graph.dtype)
+                graph.bytes += self._own_dz.numel() * graph.esize
+            dz_buf = self._own_dz
+        else:
+            dz_buf = graph.scratch(y.N, y.H, y.W, self.cout_p, self.lane)
+        s = current_stream()
+        grads = {}
+        dz = self._dz(s, gy, graph.act(dz_buf, 0, self.cout), grads, want)
+        graph.tick(self, "bwd.bn_act")
+        if self.kind != "bn_eval":   # eval-mode blocks are frozen: data gradient only
+            self._param_grads(s, dz, wstream, grads, want)
+        if gx is not None:
+            self._data_grad(s, dz, gy, gx, accumulate, want)
+            graph.tick(self, "bwd.dgrad")
+        if wstream is None:
+            graph.release_scratch(dz_buf, self.lane)
+        return grads
+
+    def _side_wgrad(self, s, dz, wstream):
+        if wstream is None:
+            return self._wgrad(dz, s)
+        # The weight gradient is off the critical path (nothing in this backward pass consumes it) and compute-bound, while the
+        # next things on the critical path - this block's data gradient and the previous block's BatchNorm backward - are partly
+        # HBM-bound: it goes to a side stream behind an event that marks dz complete, and the two kinds of work share the chip.
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream())
+        with torch.cuda.stream(wstream):
+            wstream.wait_event(ready)
+            return self._wgrad(dz, current_stream())
+
+    def _param_grads(self, s, dz, wstream, grads, want):
+        conv = self.conv
+        if want(conv.weight):
+            grads[conv.weight.data_ptr()] = self._side_wgrad(s, dz, wstream)
+            self.graph.tick(self, "bwd.wgrad")
+        if conv.bias is not None and want(conv.bias):
+            if self.kind == "bn":
+                # a bias in front of a batch-statistics BatchNorm has gradient sum(dz) = 0 in exact arithmetic (the mean
+                # subtraction removes it); torch returns rounding noise here (~1e-9 of the weight gradient), we return 0: a
+                # slice of the backward pass's one zero buffer
+                grads[conv.bias.data_ptr()] = self.graph.zero_slice(self.cout)
+            else:
+                grads[conv.bias.data_ptr()] = self._bias_grad(s, dz)
+
+    def _data_grad(self, s, dz, gy, gx, accumulate, want):
+        """gx (+)= conv_transpose(dz, W) (+ the residual branch's gradient, which the activation backward left in gy)"""
+        if accumulate:
+            self.dgrad.run(dz, gx, gx)
+            if self.residual:
+                self._add_rows(s, gx, gy)
+        else:
+            self.dgrad.run(dz, gx, self.graph.act(gy.buf, gy.off, self.cout) if self.residual else None)
+
+
+class NodeF(Node):
+    """a block over NHWC fp32 buffers (engine.TRAIN_PRECISION "f32", and "bf16c": the same tensors with the contractions on the
+    bf16 matrix cores).  `RawConv` handles carry scale / shift; batch statistics are a launch of their own."""
+
+    def __init__(self, graph, name, blk, x, y, lane):
+        super().__init__(graph, name, blk, x, y, lane)
+        dev, cout = graph.device, self.cout
+        ones, zeros = const_vec(dev, cout, 1.0), const_vec(dev, cout, 0.0)
+        self.fold_scale = torch.ones(cout, device=dev)
+        self.fold_shift = torch.zeros(cout, device=dev)
+        self.fwd = RawConv(self.geom, self.conv.weight.detach(), ones, zeros, self.precision)
+        self.wgrad_prec = _lib.PREC_BF16 if self.precision == "bf16c" else _lib.PREC_F32
+        if self.kind == "bn":
+            self.z = engine.new_buf(y.N, y.H, y.W, cout, dev)
+            self.mean = torch.empty(cout, device=dev)
+            self.rstd = torch.empty(cout, device=dev)
+            self.scale = torch.empty(cout, device=dev)
+            self.shift = torch.empty(cout, device=dev)
+
+    def _update(self, packed):
+        conv, bn = self.conv, self.bn
         w = conv.weight.detach()
         bias = conv.bias.detach() if conv.bias is not None else const_vec(self.graph.device, self.cout, 0.0)
         if self.kind == "bn_eval":
@@ -215,7 +313,6 @@ class Node:
             self.fwd.update(w, None, bias)
         if self.dgrad is not None:
             self.dgrad.update(w)
-        self._seen = seen
 
     def forward(self):
         s = current_stream()
@@ -243,32 +340,11 @@ class Node:
         tick(self, "fwd.bn_apply")
         self.graph._bn_counters.append(bn.num_batches_tracked)   # incremented together at the end of the forward
 
-    def backward(self, gy, gx, accumulate, want):
-        """gy: gradient slice of y (overwritten with the masked gradient when the block is residual); gx: gradient slice
-        of x or None; accumulate: gx already holds another consumer's contribution; want: parameter -> bool.
-        Returns {parameter: gradient tensor}."""
-        s = current_stream()
-        lib = self.lib
-        x, y = self.x, self.y
-        dev = self.graph.device
-        Cp = self.cout_p
-        lane = getattr(self, "lane", 0)
-        wstream = self.graph.wgrad_stream_for_step()
-        if wstream is not None:
-            # weight gradients run on their own stream (below): this block's dz must then outlive the next block's backward,
-            # so it gets a buffer of its own instead of a pooled one
-            if self._own_dz is None:
-                self._own_dz = torch.zeros((y.N, y.H, y.W, Cp), device=dev, dtype=torch.float32)
-                self.graph.bytes += self._own_dz.numel() * 4
-            dz_buf = self._own_dz
-        else:
-            dz_buf = self.graph.scratch(y.N, y.H, y.W, Cp, lane)
-        dz = Act(dz_buf, 0, self.cout)
-        grads = {}
-        tick = self.graph.tick
+    def _dz(self, s, gy, dz, grads, want):
+        lib, y = self.lib, self.y
         g_ptr = gy.ptr if self.residual else None
         if self.kind == "bn":
-            bn = self.bn
+            bn, dev = self.bn, self.graph.device
             dgamma = torch.empty(self.cout, device=dev)
             dbeta = torch.empty(self.cout, device=dev)
             check(lib.w2l_bn_train_bwd(s, self.rows, self.cout, gy.ptr, gy.cs, y.ptr, y.cs, ptr(self.z), self.cout, self.act,
@@ -282,163 +358,73 @@ class Node:
             check(lib.w2l_act_bwd(s, self.rows, self.cout, gy.ptr, gy.cs, y.ptr, y.cs, self.act, ptr(self.fold_scale),
                                   dz.ptr, dz.cs, g_ptr, gy.cs), "act_bwd")
         else:
-            check(lib.w2l_act_bwd(s, self.rows, Cp, gy.ptr, gy.cs, y.ptr, y.cs, self.act, None, dz.ptr, dz.cs,
+            check(lib.w2l_act_bwd(s, self.rows, self.cout_p, gy.ptr, gy.cs, y.ptr, y.cs, self.act, None, dz.ptr, dz.cs,
                                   None, 0), "act_bwd")
-        tick(self, "bwd.bn_act")
-        if self.kind != "bn_eval":   # eval-mode blocks are frozen: data gradient only
-            conv = self.conv
-            if want(conv.weight):
-                prec = _lib.PREC_BF16 if self.precision == "bf16c" else _lib.PREC_F32
-                if wstream is not None:
-                    # The weight gradient is off the critical path (nothing in this backward pass consumes it) and
-                    # compute-bound, while the next things on the critical path — this block's data gradient and the previous
-                    # block's BatchNorm backward — are partly HBM-bound: it goes to a side stream behind an event that marks
-                    # dz complete, and the two kinds of work share the chip.
-                    ready = torch.cuda.Event()
-                    ready.record(torch.cuda.current_stream())
-                    with torch.cuda.stream(wstream):
-                        wstream.wait_event(ready)
-                        dw = torch.empty_like(conv.weight)
-                        check(lib.w2l_conv_wgrad_prec(C.byref(self.geom), current_stream(), x.N, x.H, x.W, x.ptr, x.cs, dz.ptr,
-                                                      dz.cs, ptr(dw), prec), "conv_wgrad")
-                else:
-                    dw = torch.empty_like(conv.weight)
-                    check(lib.w2l_conv_wgrad_prec(C.byref(self.geom), s, x.N, x.H, x.W, x.ptr, x.cs, dz.ptr, dz.cs, ptr(dw),
-                                                  prec), "conv_wgrad")
-                grads[conv.weight.data_ptr()] = dw
-                tick(self, "bwd.wgrad")
-            if conv.bias is not None and want(conv.bias):
-                if self.kind == "bn":
-                    # a bias in front of a batch-statistics BatchNorm has gradient sum(dz) = 0 in exact arithmetic (the mean
-                    # subtraction removes it); torch returns rounding noise here (~1e-9 of the weight gradient), we return 0
-                    grads[conv.bias.data_ptr()] = self._zero_bias_grad()
-                else:
-                    db = torch.empty(Cp, device=dev)
-                    check(lib.w2l_col_sum(s, self.rows, Cp, dz.ptr, dz.cs, ptr(db)), "col_sum")
-                    grads[conv.bias.data_ptr()] = db[:self.cout]
-                    tick(self, "bwd.bias")
-        if gx is not None:
-            if self.dgrad is None:
-                dg = self.dgrad_geom
-                self.dgrad = RawConv(dg, self.conv.weight.detach(), const_vec(dev, dg.cout, 1.0), const_vec(dev, dg.cout, 0.0),
-                                     self.precision)
-            dzin = Act(dz_buf, 0, Cp)
-            if accumulate:
-                self.dgrad.run(dzin, gx, gx)
-                if self.residual:
-                    check(lib.w2l_add_rows(s, x.N * x.H * x.W, self.cin, gx.ptr, gx.cs, gy.ptr, gy.cs, gx.ptr, gx.cs), "add_rows")
-            else:
-                self.dgrad.run(dzin, gx, Act(gy.buf, gy.off, self.cout) if self.residual else None)
-            tick(self, "bwd.dgrad")
-        if wstream is None:
-            self.graph.release_scratch(dz_buf, lane)
-        return grads
+        return dz
+
+    def _wgrad(self, dz, stream):
+        x = self.x
+        dw = torch.empty_like(self.conv.weight)
+        check(self.lib.w2l_conv_wgrad_prec(C.byref(self.geom), stream, x.N, x.H, x.W, x.ptr, x.cs, dz.ptr, dz.cs, ptr(dw),
+                                           self.wgrad_prec), "conv_wgrad")
+        return dw
+
+    def _bias_grad(self, s, dz):
+        Cp = self.cout_p
+        db = torch.empty(Cp, device=self.graph.device)
+        check(self.lib.w2l_col_sum(s, self.rows, Cp, dz.ptr, dz.cs, ptr(db)), "col_sum")
+        self.graph.tick(self, "bwd.bias")
+        return db[:self.cout]
+
+    def _data_grad(self, s, dz, gy, gx, accumulate, want):
+        if self.dgrad is None:
+            dg, dev = self.dgrad_geom, self.graph.device
+            self.dgrad = RawConv(dg, self.conv.weight.detach(), const_vec(dev, dg.cout, 1.0), const_vec(dev, dg.cout, 0.0),
+                                 self.precision)
+        super()._data_grad(s, dz, gy, gx, accumulate, want)
+
+    def _add_rows(self, s, gx, gy):
+        x = self.x
+        check(self.lib.w2l_add_rows(s, x.N * x.H * x.W, self.cin, gx.ptr, gx.cs, gy.ptr, gy.cs, gx.ptr, gx.cs),
+              "add_rows")
 
 
-# W2L_BWD_SUMS_IN_DGRAD=0: every BatchNorm block reduces its own backward sums (the stand-alone pass over dy, z, y) - A/B switch
-BWD_SUMS_IN_DGRAD = [os.environ.get("W2L_BWD_SUMS_IN_DGRAD", "1") != "0"]
-# W2L_THIN_1X1=0: the 32 -> 3 output layer of a bf16 graph runs on the implicit GEMM like every other layer - A/B switch
-THIN_1X1 = [os.environ.get("W2L_THIN_1X1", "1") != "0"]
-# backward passes skip the nodes nobody wants a gradient from (TrainGraph.backward); W2L_BWD_PRUNE=0 is the A/B switch
-BWD_PRUNE = [os.environ.get("W2L_BWD_PRUNE", "1") != "0"]
-# a data-gradient launch that carries a ReLU block's BatchNorm-backward sums also stores the MASKED gradient (W2L_BNBWD_STORE_MASKED);
-# W2L_STORE_MASKED_G=0 is the A/B switch
-STORE_MASKED_G = [os.environ.get("W2L_STORE_MASKED_G", "1") != "0"]
-# exactly-zero parameter gradients are slices of one fresh zero buffer per backward pass (TrainGraph.zero_slice); W2L_ZERO_POOL=0: A/B
-ZERO_POOL = [os.environ.get("W2L_ZERO_POOL", "1") != "0"]
-# activation blocks without BatchNorm: dz comes out of the data-gradient launch that completes their dy (W2L_ACT_BWD_IN_DGRAD=0: A/B)
-ACT_BWD_IN_DGRAD = [os.environ.get("W2L_ACT_BWD_IN_DGRAD", "1") != "0"]
-
-
-class NodeB:
-    """one block of a bf16-STORAGE TrainGraph (engine.TRAIN_PRECISION "bf16"): the same block arithmetic as `Node` over NHWC
+class NodeB(Node):
+    """a block of a bf16-STORAGE TrainGraph (engine.TRAIN_PRECISION "bf16"): the same block arithmetic as `NodeF` over NHWC
     bf16 buffers.  x, y, the pre-BatchNorm conv output z and the gradients dy / dz are bf16 in HBM; the contractions run on the
     bf16 matrix cores with fp32 accumulation (w2l_convb_forward for the forward and the data gradient, w2l_conv_wgrad_bf16 for
-    the weight gradient, which comes out fp32); BatchNorm statistics, per-channel vectors and parameter gradients are fp32."""
+    the weight gradient, which comes out fp32); BatchNorm statistics, per-channel vectors and parameter gradients are fp32.
+    `ConvB` handles take scale / shift per launch, batch statistics come out of the conv epilogue, and a data-gradient launch
+    can carry the BatchNorm / activation backward of the block whose dy it completes (`sums_for`, `_bwd_sums`)."""
 
-    def __init__(self, graph, name, blk, x, y):
-        self.graph, self.name, self.blk, self.x, self.y = graph, name, blk, x, y
-        conv, bn, act, transposed, residual = describe(blk)
-        self.conv, self.bn, self.act, self.transposed, self.residual = conv, bn, act, transposed, residual
-        dev = graph.device
-        self.lib = graph.lib
-        kh, kw = engine._pair(conv.kernel_size)
-        sh, sw = engine._pair(conv.stride)
-        ph, pw = engine._pair(conv.padding)
-        oph, opw = engine._pair(conv.output_padding) if transposed else (0, 0)
-        cin, cout = conv.in_channels, conv.out_channels
-        self.cin, self.cout = cin, cout
-        self.cout_p = round8(cout)
-        if bn is None:
-            self.kind = "plain"
-        elif bn.training:
-            self.kind = "bn"
-            if bn.momentum is None or not bn.track_running_stats or not bn.affine:
-                raise NotImplementedError("BatchNorm2d variants other than the reference's default are not on the hot path")
-        else:
-            self.kind = "bn_eval"
-        fwd_act = ACT_NONE if self.kind == "bn" else act
-        self.geom = ConvGeom(int(transposed), cin, cout, kh, kw, sh, sw, ph, pw, oph, opw, fwd_act)
-        self.precision = "bf16"
+    def __init__(self, graph, name, blk, x, y, lane):
+        super().__init__(graph, name, blk, x, y, lane)
+        dev, g, Cp = graph.device, self.geom, self.cout_p
         # the generator's output layer (32 -> 3, 1x1, models/wav2lip.py:83-85): HBM-bound row kernels, not a 128x32 GEMM tile
-        self.thin = (THIN_1X1[0] and self.kind == "plain" and not transposed and not residual and (kh, kw, sh, sw, ph, pw) == (1, 1, 1, 1, 0, 0)
-                     and cin <= 32 and cout <= 4)
-        self.fwd = None if self.thin else ConvB(self.geom, conv.weight)
-        ho, wo = (x.H, x.W) if self.thin else self.fwd.out_hw(x.H, x.W)
-        if (y.H, y.W, y.N) != (ho, wo, x.N) or y.C != cout:
-            raise RuntimeError("train graph %s: output slice %s does not match %s" %
-                               (name, (y.N, y.H, y.W, y.C), (x.N, ho, wo, cout)))
-        if x.C < cin or x.cs - x.off < round8(cin) or y.cs - y.off < self.cout_p:
-            raise RuntimeError("train graph %s: input / output slice too narrow" % name)
-        self.rows = y.N * y.H * y.W
-        if not transposed:
-            dg = ConvGeom(1, cout, cin, kh, kw, sh, sw, ph, pw, (x.H + 2 * ph - kh) % sh, (x.W + 2 * pw - kw) % sw, ACT_NONE)
-        else:
-            dg = ConvGeom(0, cout, cin, kh, kw, sh, sw, ph, pw, 0, 0, ACT_NONE)
-        self.dgrad_geom = dg
-        self.dgrad = None
-        Cp = self.cout_p
+        self.thin = (self.kind == "plain" and not self.transposed and not self.residual
+                     and (g.kh, g.kw, g.sh, g.sw, g.ph, g.pw) == (1, 1, 1, 1, 0, 0) and g.cin <= 32 and g.cout <= 4)
+        if not self.thin:
+            self.fwd = ConvB(g, self.conv.weight)
         # per-channel fp32 vectors carry Cp entries (pad entries zero): the elementwise kernels load them 8 at a time
         self.fold_scale = torch.zeros(Cp, device=dev)
         self.fold_shift = torch.zeros(Cp, device=dev)
         if self.kind == "bn":
-            self.z = bf16.new_buf(y.N, y.H, y.W, cout, dev)
+            self.z = bf16.new_buf(y.N, y.H, y.W, self.cout, dev)
             graph.bytes += self.z.numel() * 2
             self.mean = torch.zeros(Cp, device=dev)
             self.rstd = torch.zeros(Cp, device=dev)
             self.scale = torch.zeros(Cp, device=dev)
             self.shift = torch.zeros(Cp, device=dev)
-        self._seen = None
-        self._own_dz = None
-        self.sums_for = None      # the "bn" block whose dy this node's data gradient completes (TrainGraph._plan_bwd_fusion)
-        self._bwd_sums = None     # (dgamma, dbeta) already reduced in the epilogue of the launch that wrote this block's dy
-
-    def parameters(self):
-        """the parameters this node can produce gradients for"""
-        return (self.conv.weight, self.conv.bias) + ((self.bn.weight, self.bn.bias) if self.bn is not None else ())
-
-    def _zero_bias_grad(self):
-        """the bias of a conv in front of batch statistics has an exactly zero gradient: a slice of the backward pass's one zero
-        buffer (TrainGraph.zero_slice)"""
-        return self.graph.zero_slice(self.cout)
-
-    def _state(self):
-        conv, bn = self.conv, self.bn
-        return (_ver(conv.weight), _ver(conv.bias)) + (
-            (_ver(bn.weight), _ver(bn.bias), _ver(bn.running_mean), _ver(bn.running_var)) if self.kind == "bn_eval" else ())
+        self._fused_db = None     # the bias gradient that came with dz, between _dz and _bias_grad of one backward
 
     def stale_weights(self):
-        """(layer handle, master weight) pairs whose bf16 slabs are older than the weight; TrainGraph re-packs the pairs of all
-        its nodes in one launch (ConvB.update_many) and then calls refresh(packed=True)"""
+        """the bf16 slabs of this node's handles when they are older than the master weight"""
         if self.thin or self._state() == self._seen:
-            return []
+            return ()
         return [(self.fwd, self.conv.weight)] + ([(self.dgrad, self.conv.weight)] if self.dgrad is not None else [])
 
-    def refresh(self, packed=False):
+    def _update(self, packed):
         conv, bn = self.conv, self.bn
-        seen = self._state()
-        if seen == self._seen:
-            return
         if not packed and not self.thin:
             self.fwd.update(conv.weight)
             if self.dgrad is not None:
@@ -448,7 +434,6 @@ class NodeB:
             check(self.lib.w2l_bn_fold(current_stream(), self.cout, ptr(bias), ptr(bn.weight.detach()), ptr(bn.bias.detach()),
                                        ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), ptr(self.fold_scale),
                                        ptr(self.fold_shift)), "bn_fold")
-        self._seen = seen
 
     def forward(self):
         s = current_stream()
@@ -473,46 +458,33 @@ class NodeB:
             raise ValueError("Expected more than 1 value per channel when training, got input size %s" %
                              str([y.N, self.cout, y.H, y.W]))
         bn = self.bn
-        Cp = self.cout_p
         z = ActB(self.z, 0, self.cout)
         # the conv and the batch statistics of its output in one call: the sums come out of the conv epilogue
         self.fwd.run_bn(x, z, bias, bn.weight.detach(), bn.bias.detach(), bn.eps, bn.momentum, bn.running_mean, bn.running_var,
                         self.mean, self.rstd, self.scale, self.shift)
         tick(self, "fwd.conv")
-        check(self.lib.w2l_affine_act_bf16(s, self.rows, Cp, z.ptr, z.cs, ptr(self.scale), ptr(self.shift),
+        check(self.lib.w2l_affine_act_bf16(s, self.rows, self.cout_p, z.ptr, z.cs, ptr(self.scale), ptr(self.shift),
                                            res.ptr if res is not None else None, res.cs if res is not None else 0, self.act,
                                            y.ptr, y.cs), "affine_act_bf16")
         tick(self, "fwd.bn_apply")
         self.graph._bn_counters.append(bn.num_batches_tracked)   # incremented together at the end of the forward
 
-    def backward(self, gy, gx, accumulate, want):
-        s = current_stream()
-        lib = self.lib
-        x, y = self.x, self.y
-        dev = self.graph.device
-        Cp = self.cout_p
-        lane = getattr(self, "lane", 0)
-        wstream = self.graph.wgrad_stream_for_step()
-        if wstream is not None:
-            if self._own_dz is None:
-                self._own_dz = torch.zeros((y.N, y.H, y.W, Cp), device=dev, dtype=torch.bfloat16)
-                self.graph.bytes += self._own_dz.numel() * 2
-            dz_buf = self._own_dz
-        else:
-            dz_buf = self.graph.scratch(y.N, y.H, y.W, Cp, lane)
-        dz = ActB(dz_buf, 0, self.cout)
-        grads = {}
-        tick = self.graph.tick
+    def _dz(self, s, gy, dz, grads, want):
+        lib, y, Cp = self.lib, self.y, self.cout_p
         g_ptr = gy.ptr if self.residual else None
-        fused_db = None
+        sums, self._bwd_sums, self._fused_db = self._bwd_sums, None, None
         if self.kind == "bn":
             bn = self.bn
-            dgamma = torch.empty(Cp, device=dev)
-            dbeta = torch.empty(Cp, device=dev)
             # a ReLU block without residual: the mask is recomputed from z (the forward's own z*scale + shift), y is not read
             skip_y = (not self.residual) and self.act == ACT_RELU
-            sums, self._bwd_sums = self._bwd_sums, None
-            if sums is not None:
+            if sums is None:
+                dgamma = torch.empty(Cp, device=self.graph.device)
+                dbeta = torch.empty(Cp, device=self.graph.device)
+                check(lib.w2l_bn_train_bwd_bf16(s, self.rows, Cp, self.cout, gy.ptr, gy.cs, None if skip_y else y.ptr, y.cs,
+                                                ptr(self.z), Cp, self.act, ptr(self.mean), ptr(self.rstd), ptr(self.scale),
+                                                ptr(self.shift), ptr(dgamma), ptr(dbeta), dz.ptr, dz.cs, g_ptr, gy.cs),
+                      "bn_train_bwd_bf16")
+            else:
                 # the launch that completed this block's dy (the data gradient of its consumer) left the two column sums behind:
                 # only the elementwise half runs
                 dgamma, dbeta, premasked = sums
@@ -528,11 +500,6 @@ class NodeB:
                                                           ptr(self.z), Cp, self.act, ptr(self.mean), ptr(self.rstd), ptr(self.scale),
                                                           ptr(self.shift), ptr(dgamma), ptr(dbeta), dz.ptr, dz.cs, g_ptr, gy.cs),
                           "bn_train_bwd_apply_bf16")
-            else:
-                check(lib.w2l_bn_train_bwd_bf16(s, self.rows, Cp, self.cout, gy.ptr, gy.cs, None if skip_y else y.ptr, y.cs,
-                                                ptr(self.z), Cp, self.act, ptr(self.mean), ptr(self.rstd), ptr(self.scale),
-                                                ptr(self.shift), ptr(dgamma), ptr(dbeta), dz.ptr, dz.cs, g_ptr, gy.cs),
-                      "bn_train_bwd_bf16")
             if want(bn.weight):
                 grads[bn.weight.data_ptr()] = dgamma[:self.cout]
             if want(bn.bias):
@@ -540,98 +507,85 @@ class NodeB:
         elif self.kind == "bn_eval":
             check(lib.w2l_act_bwd_bf16(s, self.rows, Cp, gy.ptr, gy.cs, y.ptr, y.cs, self.act, ptr(self.fold_scale),
                                        dz.ptr, dz.cs, g_ptr, gy.cs), "act_bwd_bf16")
+        elif sums is not None and sums[2]:
+            # the launch that completed this block's dy already multiplied it by act'(y): gy IS dz (no launch, no copy; the
+            # gradient buffer of this block's output is not written again before the next backward pass), and the column sums
+            # that came with it are the bias gradient
+            self._fused_db = sums[0]
+            return ActB(gy.buf, gy.off, self.cout)
         else:
-            sums, self._bwd_sums = self._bwd_sums, None
-            if sums is not None and sums[2]:
-                # the launch that completed this block's dy already multiplied it by act'(y): gy IS dz (no launch, no copy; the
-                # gradient buffer of this block's output is not written again before the next backward pass)
-                dz = ActB(gy.buf, gy.off, self.cout)
-                fused_db = sums[0]
-            else:
-                check(lib.w2l_act_bwd_bf16(s, self.rows, Cp, gy.ptr, gy.cs, y.ptr, y.cs, self.act, None, dz.ptr, dz.cs,
-                                           None, 0), "act_bwd_bf16")
-        tick(self, "bwd.bn_act")
-        if self.thin:
-            conv = self.conv
-            if want(conv.weight) or (conv.bias is not None and want(conv.bias)):
-                dw = torch.empty_like(conv.weight)
-                db = torch.empty(self.cout, device=dev) if conv.bias is not None else None
-                check(lib.w2l_thin1x1_wgrad_bf16(s, self.rows, self.cin, self.cout, x.ptr, x.cs, dz.ptr, dz.cs, ptr(dw), ptr(db)),
-                      "thin1x1_wgrad_bf16")
-                if want(conv.weight):
-                    grads[conv.weight.data_ptr()] = dw
-                if db is not None and want(conv.bias):
-                    grads[conv.bias.data_ptr()] = db
-                tick(self, "bwd.wgrad")
-            if gx is not None:
-                check(lib.w2l_thin1x1_dgrad_bf16(s, self.rows, self.cin, self.cout, dz.ptr, dz.cs, ptr(conv.weight.detach()),
-                                                 gx.ptr if accumulate else None, gx.cs if accumulate else 0, gx.ptr, gx.cs),
-                      "thin1x1_dgrad_bf16")
-                tick(self, "bwd.dgrad")
-            if wstream is None:
-                self.graph.release_scratch(dz_buf, lane)
-            return grads
-        if self.kind != "bn_eval":
-            conv = self.conv
+            check(lib.w2l_act_bwd_bf16(s, self.rows, Cp, gy.ptr, gy.cs, y.ptr, y.cs, self.act, None, dz.ptr, dz.cs,
+                                       None, 0), "act_bwd_bf16")
+        return dz
+
+    def _param_grads(self, s, dz, wstream, grads, want):
+        if not self.thin:
+            return super()._param_grads(s, dz, wstream, grads, want)
+        # thin 1x1: one row kernel on the main stream writes the weight gradient and the bias gradient
+        conv, x = self.conv, self.x
+        if want(conv.weight) or (conv.bias is not None and want(conv.bias)):
+            dw = torch.empty_like(conv.weight)
+            db = torch.empty(self.cout, device=self.graph.device) if conv.bias is not None else None
+            check(self.lib.w2l_thin1x1_wgrad_bf16(s, self.rows, self.cin, self.cout, x.ptr, x.cs, dz.ptr, dz.cs,
+                                                  ptr(dw), ptr(db)), "thin1x1_wgrad_bf16")
             if want(conv.weight):
-                def wgrad(stream_ptr):
-                    dw = torch.empty_like(conv.weight)
-                    check(lib.w2l_conv_wgrad_bf16(C.byref(self.geom), stream_ptr, x.N, x.H, x.W, x.ptr, x.cs, dz.ptr, dz.cs,
-                                                  ptr(dw)), "conv_wgrad_bf16")
-                    return dw
-                if wstream is not None:
-                    ready = torch.cuda.Event()
-                    ready.record(torch.cuda.current_stream())
-                    with torch.cuda.stream(wstream):
-                        wstream.wait_event(ready)
-                        dw = wgrad(current_stream())
-                else:
-                    dw = wgrad(s)
                 grads[conv.weight.data_ptr()] = dw
-                tick(self, "bwd.wgrad")
-            if conv.bias is not None and want(conv.bias):
-                if self.kind == "bn":
-                    grads[conv.bias.data_ptr()] = self._zero_bias_grad()   # exactly zero in front of batch statistics
-                elif self.kind == "plain" and fused_db is not None:
-                    grads[conv.bias.data_ptr()] = fused_db[:self.cout]      # the column sums came with dz
-                else:
-                    db = torch.empty(Cp, device=dev)
-                    check(lib.w2l_col_sum_bf16(s, self.rows, Cp, dz.ptr, dz.cs, ptr(db)), "col_sum_bf16")
-                    grads[conv.bias.data_ptr()] = db[:self.cout]
-                    tick(self, "bwd.bias")
-        if gx is not None:
-            if self.dgrad is None:
-                self.dgrad = ConvB(self.dgrad_geom, self.conv.weight)
-            m = self.sums_for if BWD_SUMS_IN_DGRAD[0] else None
-            res = gx if accumulate else (ActB(gy.buf, gy.off, self.cout) if self.residual else None)
-            if m is not None and not (accumulate and self.residual):
-                # this launch writes the final dy of block m (its first consumer in forward order = its last writer here): the
-                # BatchNorm-backward column sums of m come out of the same epilogue
-                if m.kind == "plain":
-                    # ... with the column sums of that dz = the gradient of m's conv bias, when m has one that wants it
-                    mb = m.conv.bias
-                    db = torch.empty(m.cout_p, device=dev) if (mb is not None and want(mb)) else None
-                    fused = self.dgrad.run_actbwd(dz, gx, res, m.y, m.act, db)
-                    m._bwd_sums = (db, None, True) if fused else None
-                else:
-                    mCp = m.cout_p
-                    dgamma, dbeta = torch.empty(mCp, device=dev), torch.empty(mCp, device=dev)
-                    m_skip_y = (not m.residual) and m.act == ACT_RELU
-                    premask = STORE_MASKED_G[0] and m.act == ACT_RELU
-                    fused = self.dgrad.run_bnbwd(dz, gx, res, ActB(m.z, 0, m.cout), None if m_skip_y else m.y, m.act, m.mean, m.rstd,
-                                                 m.scale, m.shift, dgamma, dbeta, store_masked=premask)
-                    m._bwd_sums = (dgamma, dbeta, premask) if fused else None
-            elif accumulate:
-                self.dgrad.run(dz, gx, gx)
-                if self.residual:
-                    check(lib.w2l_add_rows_bf16(s, x.N * x.H * x.W, round8(self.cin), gx.ptr, gx.cs, gy.ptr, gy.cs, gx.ptr, gx.cs),
-                          "add_rows_bf16")
-            else:
-                self.dgrad.run(dz, gx, res)
-            tick(self, "bwd.dgrad")
-        if wstream is None:
-            self.graph.release_scratch(dz_buf, lane)
-        return grads
+            if db is not None and want(conv.bias):
+                grads[conv.bias.data_ptr()] = db
+            self.graph.tick(self, "bwd.wgrad")
+
+    def _wgrad(self, dz, stream):
+        x = self.x
+        dw = torch.empty_like(self.conv.weight)
+        check(self.lib.w2l_conv_wgrad_bf16(C.byref(self.geom), stream, x.N, x.H, x.W, x.ptr, x.cs, dz.ptr, dz.cs, ptr(dw)),
+              "conv_wgrad_bf16")
+        return dw
+
+    def _bias_grad(self, s, dz):
+        if self._fused_db is not None:
+            return self._fused_db[:self.cout]      # the column sums came with dz
+        Cp = self.cout_p
+        db = torch.empty(Cp, device=self.graph.device)
+        check(self.lib.w2l_col_sum_bf16(s, self.rows, Cp, dz.ptr, dz.cs, ptr(db)), "col_sum_bf16")
+        self.graph.tick(self, "bwd.bias")
+        return db[:self.cout]
+
+    def _data_grad(self, s, dz, gy, gx, accumulate, want):
+        if self.thin:
+            check(self.lib.w2l_thin1x1_dgrad_bf16(s, self.rows, self.cin, self.cout, dz.ptr, dz.cs,
+                                                  ptr(self.conv.weight.detach()), gx.ptr if accumulate else None,
+                                                  gx.cs if accumulate else 0, gx.ptr, gx.cs), "thin1x1_dgrad_bf16")
+            return
+        if self.dgrad is None:
+            self.dgrad = ConvB(self.dgrad_geom, self.conv.weight)
+        m = self.sums_for
+        if m is None or (accumulate and self.residual):
+            return super()._data_grad(s, dz, gy, gx, accumulate, want)
+        # this launch writes the final dy of block m (its first consumer in forward order = its last writer here): what m's
+        # backward would reduce from that dy comes out of the same epilogue.  A launch that cannot carry it (split-K) says
+        # so and m's own backward does the work.
+        dev = self.graph.device
+        res = gx if accumulate else (ActB(gy.buf, gy.off, self.cout) if self.residual else None)
+        if m.kind == "plain":
+            # m has no BatchNorm: dz = dy * act'(y) is stored directly, with the column sums of that dz = the gradient of m's
+            # conv bias, when m has one that wants it
+            mb = m.conv.bias
+            db = torch.empty(m.cout_p, device=dev) if (mb is not None and want(mb)) else None
+            fused = self.dgrad.run_actbwd(dz, gx, res, m.y, m.act, db)
+            m._bwd_sums = (db, None, True) if fused else None
+        else:
+            # m's two BatchNorm-backward column sums; for a ReLU block the MASKED gradient is stored (W2L_BNBWD_STORE_MASKED)
+            dgamma, dbeta = torch.empty(m.cout_p, device=dev), torch.empty(m.cout_p, device=dev)
+            m_skip_y = (not m.residual) and m.act == ACT_RELU
+            premask = m.act == ACT_RELU
+            fused = self.dgrad.run_bnbwd(dz, gx, res, ActB(m.z, 0, m.cout), None if m_skip_y else m.y, m.act, m.mean, m.rstd,
+                                         m.scale, m.shift, dgamma, dbeta, store_masked=premask)
+            m._bwd_sums = (dgamma, dbeta, premask) if fused else None
+
+    def _add_rows(self, s, gx, gy):
+        x = self.x
+        check(self.lib.w2l_add_rows_bf16(s, x.N * x.H * x.W, round8(self.cin), gx.ptr, gx.cs, gy.ptr, gy.cs,
+                                         gx.ptr, gx.cs), "add_rows_bf16")
 
 
 class TrainGraph:
@@ -640,10 +594,15 @@ class TrainGraph:
     def __init__(self, device):
         self.device = torch.device(device)
         self.lib = _lib.load()
-        # bf16-storage graph: NHWC bf16 buffers (channel counts rounded up to 8), NodeB blocks, bf16 boundary conversions
+        # what depends on the storage: buffer dtype and element size; `rnd`, the channel count rounded to the layout's granule
+        # (8 bf16 or 4 floats = 16 bytes); `act`, the channel-slice class; the node class; the NCHW fp32 <-> NHWC conversions
         self.bf16 = engine.TRAIN_PRECISION[0] == "bf16"
-        self.dtype = torch.bfloat16 if self.bf16 else torch.float32
-        self.esize = 2 if self.bf16 else 4
+        if self.bf16:
+            self.dtype, self.esize, self.rnd, self.act, self.node = torch.bfloat16, 2, round8, ActB, NodeB
+            self.to_nhwc, self.to_nchw = self.lib.w2l_nchw_to_nhwc_bf16, self.lib.w2l_nhwc_bf16_to_nchw
+        else:
+            self.dtype, self.esize, self.rnd, self.act, self.node = torch.float32, 4, _round4, Act, NodeF
+            self.to_nhwc, self.to_nchw = self.lib.w2l_nchw_to_nhwc, self.lib.w2l_nhwc_to_nchw
         self.nodes = []
         self.inputs = []     # (Act, channels) filled from NCHW tensors
         self.outputs = []    # Act
@@ -661,20 +620,20 @@ class TrainGraph:
         self._wstream_on = False
         self.events = None   # profiling: list of (node name, phase, cuda event) when enabled (W2L_TRAIN_PROFILE=1)
         self._bn_counters = []   # num_batches_tracked of the BatchNorms that ran in train mode during this forward
+        self._bwd_planned = False
+        self._zero_pool, self._zero_off = None, 0   # zero_slice
+        self.backward_nodes = []       # names of the nodes the last backward pass ran (tests)
+        self.reducer = None      # the GraphCache's sharding.GradReducer, if any (run_graph)
+        self.keep = None         # an adapter module the builder made for the last node: alive as long as the graph
 
     def zero_slice(self, n):
         """n zeros for a gradient that is exactly zero (conv biases in front of batch statistics).  ONE zero-filled buffer per backward
         pass, handed out in slices: torch's AccumulateGrad keeps a gradient it is the only holder of (a fresh view is one) and CLONES
         a tensor somebody else still references - the per-node cached zero tensors of rounds 2-5 were cloned every step, ~50
         device-to-device copies behind the generator's backward pass."""
-        if not ZERO_POOL[0]:           # A/B: a cached tensor per size (cloned by AccumulateGrad every step, as before)
-            cache = self.__dict__.setdefault("_zero_cache", {})
-            if n not in cache:
-                cache[n] = torch.zeros(n, device=self.device)
-            return cache[n]
-        pool = getattr(self, "_zero_pool", None)
+        pool = self._zero_pool
         if pool is None or self._zero_off + n > pool.numel():
-            total = sum(nd.cout for nd in self.nodes if getattr(nd, "kind", None) == "bn")
+            total = sum(nd.cout for nd in self.nodes if nd.kind == "bn")
             pool = self._zero_pool = torch.zeros(max(total, n), device=self.device)
             self._zero_off = 0
         out = pool[self._zero_off:self._zero_off + n]
@@ -719,13 +678,6 @@ class TrainGraph:
             out.append((name, phase, e0.elapsed_time(e1), macs))
         return out
 
-    def rnd(self, c):
-        """channel count rounded to the layout's granule: 4 floats or 8 bf16 = 16 bytes"""
-        return round8(c) if self.bf16 else _round4(c)
-
-    def act(self, buf, off, C_):
-        return ActB(buf, off, C_) if self.bf16 else Act(buf, off, C_)
-
     def buffer(self, N, H, W, Cn):
         Ct = self.rnd(Cn)
         b = torch.zeros((N, H, W, Ct), device=self.device, dtype=self.dtype)
@@ -754,17 +706,14 @@ class TrainGraph:
         self._scratch[tuple(buf.shape) + (lane,)].append(buf)
 
     def add(self, name, blk, x, y, lane=0):
-        n = (NodeB if self.bf16 else Node)(self, name, blk, x, y)
-        n.lane = lane
-        self.nodes.append(n)
+        self.nodes.append(self.node(self, name, blk, x, y, lane))
         return y
 
     def chain(self, name, blocks, x, final_dst=None, lane=0):
         """blocks applied in sequence; each output gets its own buffer (kept for backward) unless it is `final_dst`"""
         for j, blk in enumerate(blocks):
             conv = describe(blk)[0]
-            probe = RawConvShape(conv, describe(blk)[3])
-            ho, wo = probe.out_hw(x.H, x.W)
+            ho, wo = out_hw(block_geom(blk), x.H, x.W)
             if j == len(blocks) - 1 and final_dst is not None:
                 y = final_dst
             else:
@@ -807,15 +756,16 @@ class TrainGraph:
         """bf16 graphs: for every batch-statistics block m, the node whose data gradient COMPLETES m's dy - the first node in
         forward order (= the last in a backward pass) that reads m's output, provided it reads exactly m's slice (a reader of a
         wider concat slice, or of a part, writes other channels with the same launch: no fusion) on the same lane.  That node's
-        data-gradient launch also reduces m's two BatchNorm-backward column sums in its epilogue (NodeB.backward)."""
+        data-gradient launch also reduces m's two BatchNorm-backward column sums in its epilogue (NodeB._data_grad).  A host test plans
+        stand-in nodes that carry only the fields read for their kind: hence the tolerant reads."""
         self._bwd_planned = True
         if not self.bf16:
             return
         for i, m in enumerate(self.nodes):
-            kind = getattr(m, "kind", None)
-            # batch-statistics blocks (sums + masked store) and, this round, activation blocks WITHOUT BatchNorm (the discriminator's
+            kind = m.kind
+            # batch-statistics blocks (sums + masked store) and activation blocks WITHOUT BatchNorm (the discriminator's
             # conv + LeakyReLU): the launch that completes their dy stores dz = dy * act'(y) directly (w2l_convb_forward_actbwd)
-            plain_act = (kind == "plain" and ACT_BWD_IN_DGRAD[0] and getattr(m, "act", ACT_NONE) in (ACT_RELU, ACT_LEAKY)
+            plain_act = (kind == "plain" and getattr(m, "act", ACT_NONE) in (ACT_RELU, ACT_LEAKY)
                          and not getattr(m, "residual", False) and not getattr(m, "thin", False))
             if kind != "bn" and not plain_act:
                 continue
@@ -834,19 +784,16 @@ class TrainGraph:
         for (act, cch), t in zip(self.inputs, tensors):
             engine.require_cuda(t, "input")
             t = t.detach().contiguous().float()
-            to_nhwc = self.lib.w2l_nchw_to_nhwc_bf16 if self.bf16 else self.lib.w2l_nchw_to_nhwc
-            check(to_nhwc(s, act.N, cch, act.H, act.W, ptr(t), act.ptr, act.cs, act.cs - act.off), "nchw_to_nhwc")
+            check(self.to_nhwc(s, act.N, cch, act.H, act.W, ptr(t), act.ptr, act.cs, act.cs - act.off), "nchw_to_nhwc")
         self.profile_mark("inputs")
 
-        if self.bf16:
-            # one launch re-packs the bf16 weight slabs of every layer an optimiser step has touched
-            stale = [n for n in self.nodes if isinstance(n, NodeB)]
-            pairs = [p for n in stale for p in n.stale_weights()]
-            if pairs:
-                bf16.ConvB.update_many(pairs)
-                for n in stale:
-                    n.refresh(packed=True)
-                self.profile_mark("repack")
+        # one launch re-packs the bf16 weight slabs of every layer an optimiser step has touched
+        pairs = [p for n in self.nodes for p in n.stale_weights()]
+        if pairs:
+            ConvB.update_many(pairs)
+            for n in self.nodes:
+                n.refresh(packed=True)
+            self.profile_mark("repack")
 
         def fwd(n):
             n.refresh()
@@ -863,18 +810,16 @@ class TrainGraph:
         outs = []
         for o in self.outputs:
             y = torch.empty((o.N, o.C, o.H, o.W), device=self.device, dtype=torch.float32)
-            to_nchw = self.lib.w2l_nhwc_bf16_to_nchw if self.bf16 else self.lib.w2l_nhwc_to_nchw
-            check(to_nchw(s, o.N, o.C, o.H, o.W, o.ptr, o.cs, ptr(y)), "nhwc_to_nchw")
+            check(self.to_nchw(s, o.N, o.C, o.H, o.W, o.ptr, o.cs, ptr(y)), "nhwc_to_nchw")
             outs.append(y)
         return outs
 
     def backward(self, gouts, input_needs, want, reducer=None):
         s = current_stream()
-        if not getattr(self, "_bwd_planned", False):
+        if not self._bwd_planned:
             self._plan_bwd_fusion()
         for n in self.nodes:                       # sums left by a backward pass that did not reach their block: stale
-            if getattr(n, "_bwd_sums", None) is not None:
-                n._bwd_sums = None
+            n._bwd_sums = None
         self._wstream_on = self._wstream is not None and self.events is None and reducer is None
         if self._wstream_on:
             self._wstream.wait_stream(torch.cuda.current_stream())   # last step's optimiser reads of dW are ordered before
@@ -898,24 +843,22 @@ class TrainGraph:
                 ga.buf[..., ga.off:ga.off + self.rnd(ga.C)].zero_()
             else:
                 g = g.contiguous().float()
-                to_nhwc = self.lib.w2l_nchw_to_nhwc_bf16 if self.bf16 else self.lib.w2l_nchw_to_nhwc
-                check(to_nhwc(s, o.N, o.C, o.H, o.W, ptr(g), ga.ptr, ga.cs, self.rnd(o.C)), "nchw_to_nhwc")
+                check(self.to_nhwc(s, o.N, o.C, o.H, o.W, ptr(g), ga.ptr, ga.cs, self.rnd(o.C)), "nchw_to_nhwc")
             mark(ga)
         # Which buffers carry a gradient anybody asked for (what torch's engine decides per tensor with requires_grad): a graph
         # input that needs one, or the output of a node that owns a wanted parameter or reads such a buffer.  A node outside that
         # set is skipped entirely - e.g. the audio encoder of the frozen SyncNet in wav2lip_train.py:187-190,216: its input (the
         # mel) needs no gradient and its parameters are frozen, so the reference's autograd never walks it either.
-        input_bufs = {id(a.buf): need for (a, _), need in zip(self.inputs, input_needs)}
         buf_req = {id(a.buf): bool(need) for (a, _), need in zip(self.inputs, input_needs)}
         node_req = {}
         for n in self.nodes:
             owns = any(p is not None and want(p) for p in n.parameters())
-            r = owns or buf_req.get(id(n.x.buf), False) or not BWD_PRUNE[0]
+            r = owns or buf_req.get(id(n.x.buf), False)
             node_req[id(n)] = r
             buf_req[id(n.y.buf)] = buf_req.get(id(n.y.buf), False) or r
         grads = {}
         self._zero_pool = None         # a fresh zero buffer per backward pass (zero_slice): its slices become parameter gradients
-        self.backward_nodes = []       # names of the nodes the last backward pass ran (tests)
+        self.backward_nodes = []
         self.profile_mark("gouts")
         def bwd(n):
             gy = self.grad_act(n.y)
@@ -923,7 +866,7 @@ class TrainGraph:
                 return     # nothing downstream used this output
             if not node_req[id(n)]:
                 return     # no parameter of this node and nothing upstream of it wants a gradient
-            need_x = buf_req.get(id(n.x.buf), False) if BWD_PRUNE[0] else input_bufs.get(id(n.x.buf), True)
+            need_x = buf_req.get(id(n.x.buf), False)
             self.backward_nodes.append(n.name)
             gx = self.grad_act(n.x, n.cin) if need_x else None
             acc = covered(gx) if gx is not None else False
@@ -953,8 +896,7 @@ class TrainGraph:
             if not covered(ga):
                 t.zero_()
             else:
-                to_nchw = self.lib.w2l_nhwc_bf16_to_nchw if self.bf16 else self.lib.w2l_nhwc_to_nchw
-                check(to_nchw(s, a.N, cch, a.H, a.W, ga.ptr, ga.cs, ptr(t)), "nhwc_to_nchw")
+                check(self.to_nchw(s, a.N, cch, a.H, a.W, ga.ptr, ga.cs, ptr(t)), "nhwc_to_nchw")
             din.append(t)
         if reducer is not None:
             grads = reducer.finalize()
@@ -962,23 +904,6 @@ class TrainGraph:
             torch.cuda.current_stream().wait_stream(self._wstream)    # every weight gradient is complete before it is returned
             self._wstream_on = False
         return din, grads
-
-
-class RawConvShape:
-    """output-size arithmetic of a conv module without building a handle"""
-
-    def __init__(self, conv, transposed):
-        self.k = engine._pair(conv.kernel_size)
-        self.s = engine._pair(conv.stride)
-        self.p = engine._pair(conv.padding)
-        self.op = engine._pair(conv.output_padding) if transposed else (0, 0)
-        self.t = transposed
-
-    def out_hw(self, H, W):
-        if self.t:
-            return ((H - 1) * self.s[0] - 2 * self.p[0] + self.k[0] + self.op[0],
-                    (W - 1) * self.s[1] - 2 * self.p[1] + self.k[1] + self.op[1])
-        return ((H + 2 * self.p[0] - self.k[0]) // self.s[0] + 1, (W + 2 * self.p[1] - self.k[1]) // self.s[1] + 1)
 
 
 # ---------------------------------------------------------------- graph builders
@@ -994,7 +919,7 @@ def build_generator(model, N, H, W, device):
     enc_hw, h, w = [], H, W
     for blk in enc:
         for b in blk:
-            h, w = RawConvShape(*describe(b)[0:4:3]).out_hw(h, w)
+            h, w = out_hw(block_geom(b), h, w)
         enc_hw.append((h, w, describe(blk[-1])[0].out_channels))
     nb = len(dec)
     cats = []
@@ -1111,7 +1036,7 @@ class GraphFn(torch.autograd.Function):
         needs = ctx.needs_input_grad[2:]
         n_in = ctx.n_in
         want_ptrs = {p.data_ptr() for p, need in zip(ctx.params, needs[n_in:]) if need}
-        din, grads = g.backward(gouts, needs[:n_in], lambda p: p.data_ptr() in want_ptrs, getattr(g, "reducer", None))
+        din, grads = g.backward(gouts, needs[:n_in], lambda p: p.data_ptr() in want_ptrs, g.reducer)
         g.busy = False
         dparams = []
         for p, need in zip(ctx.params, needs[n_in:]):
