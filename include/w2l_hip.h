@@ -23,6 +23,9 @@
  *   w2l_frames_to_u8      inference.py:265,269 (x255, astype(uint8) truncation, NHWC)
  *   w2l_crop_resize_u8    inference.py:121-126 (face crop -> cv2.resize to 96x96)
  *   w2l_resize_paste_u8   inference.py:270-271 (cv2.resize of the generated crop to the box size + paste into the frame)
+ *   w2l_crop_resize_rows_u8  evaluation/gen_videos_from_filelist.py:85-95 (the same crop + resize, one frame per row)
+ *   w2l_compose_rows_u8   evaluation/gen_videos_from_filelist.py:221-227 (resize + paste + the frame copy, one pass)
+ *   w2l_mel_gather_rows   evaluation/gen_videos_from_filelist.py:176-183 (mel windows, one spectrogram per row)
  *   w2l_melspectrogram    audio.py:45-51 (preemphasis, STFT, mel basis, dB, normalise)
  *   w2l_mel_gather        inference.py:231-240 (16-frame mel windows at host-computed starts)
  *   w2l_resample_sinc     audio.py:9-10 (librosa.core.load's sample-rate conversion: resampy 'kaiser_best' sinc interpolation)
@@ -168,6 +171,38 @@ int w2l_resize_u8(void* stream, int B, const uint8_t* src, int Hs, int Ws, uint8
 int w2l_resize_paste_u8(void* stream, int B, const uint8_t* pred, int S, const int32_t* boxes, const int32_t* frame_idx,
                         uint8_t* frames, int H, int W, int max_box_pixels);
 
+/* Row-table forms (evaluation/gen_videos_from_filelist.py:85-95 crop + cv2.resize of every row's face, :221-227 cv2.resize of
+ * the generated crop + paste + out.write of the WHOLE frame): a row is one generator input and names its own frame, so rows
+ * of clips with different frame shapes share one launch.  Tables live in device memory, 16-byte aligned.
+ *
+ * w2l_frame_row, 48 bytes, alignment 16:
+ *   offset  0  uint64 src    device address of pixel (0,0) of the row's source frame, u8 [H,W,3] BGR
+ *   offset  8  uint64 dst    device address of the row's output frame u8 [H,W,3] (compose only; src == dst: paste in place)
+ *   offset 16  int32  H, W   that frame's size (differs from row to row)
+ *   offset 24  int32  y1, y2, x1, x2   face box, 0 <= y1 < y2 <= H, 0 <= x1 < x2 <= W (validated by the caller)
+ *   offset 40  int32  pad[2] unused (keeps consecutive rows 16-byte aligned)
+ * w2l_mel_row, 16 bytes, alignment 16:
+ *   offset  0  uint64 mel    device address of the row's spectrogram, fp32 [80][T]
+ *   offset  8  int32  T      its number of columns
+ *   offset 12  int32  start  the window is columns [start, start+16) (columns outside [0,T) read as 0) */
+typedef struct {
+    uint64_t src, dst;
+    int32_t H, W;
+    int32_t y1, y2, x1, x2;
+    int32_t pad[2];
+} w2l_frame_row;
+typedef struct {
+    uint64_t mel;
+    int32_t T, start;
+} w2l_mel_row;
+
+/* out u8 [B,S,S,3]: out[b] = resize(frame_b[y1:y2, x1:x2], (S,S)); byte-equal to w2l_crop_resize_u8 */
+int w2l_crop_resize_rows_u8(void* stream, int B, const w2l_frame_row* rows, int S, uint8_t* out);
+/* dst_b = src_b outside the box, resize(pred[b] (u8 [S,S,3]), (x2-x1, y2-y1)) inside it: ONE pass writes the whole output frame
+ * (byte-equal to a frame copy + w2l_resize_paste_u8).  src == dst: paste in place.  max_frame_pixels >= the largest H*W of
+ * the batch (sizes the launch). */
+int w2l_compose_rows_u8(void* stream, int B, const uint8_t* pred, int S, const w2l_frame_row* rows, int max_frame_pixels);
+
 /* ---------------------------------------------------------------- S3FD face detector glue (face_detection/detection/sfd/)
  * The detector's convolutions are w2l_conv_* layers (bias + ReLU, no BatchNorm); these are the ops between them. */
 
@@ -246,6 +281,11 @@ int w2l_mel_gather(void* stream, const float* mel, int T, const int32_t* starts,
 /* the same windows as bf16 (each value rounded once, RNE) for the bf16-storage generator: out bf16 [B][80][16][out_cs] */
 int w2l_mel_gather_bf16(void* stream, const float* mel, int T, const int32_t* starts, int B, void* out,
                         int out_cs, int c_zero_to);
+
+/* w2l_mel_gather / w2l_mel_gather_bf16 with one spectrogram per row (w2l_mel_row above): the mel chunking of
+ * evaluation/gen_videos_from_filelist.py:176-183 for rows of several clips in one batch */
+int w2l_mel_gather_rows(void* stream, const w2l_mel_row* rows, int B, float* out, int out_cs, int c_zero_to);
+int w2l_mel_gather_rows_bf16(void* stream, const w2l_mel_row* rows, int B, void* out, int out_cs, int c_zero_to);
 
 /* Sample-rate conversion of audio.load_wav (audio.py:9-10 -> librosa.core.load(path, sr=16000) -> resampy.resample(...,
  * filter='kaiser_best')).  x fp32 [n_in], tr f64 [n_out] = the interpolator's time register at every output sample (the host

@@ -35,6 +35,17 @@ class WgradBf16Info(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("ni", "bh", "bw", "nboxes", "splits", "boxes_per_split", "ntg", "tg", "ncq", "mt", "qp")]
 
 
+class FrameRow(C.Structure):
+    """w2l_frame_row (include/w2l_hip.h): one face row of the row-table kernels, 48 bytes"""
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("H", C.c_int32), ("W", C.c_int32), ("y1", C.c_int32),
+                ("y2", C.c_int32), ("x1", C.c_int32), ("x2", C.c_int32), ("pad", C.c_int32 * 2)]
+
+
+class MelRow(C.Structure):
+    """w2l_mel_row: one mel window of the row-table gather, 16 bytes"""
+    _fields_ = [("mel", C.c_uint64), ("T", C.c_int32), ("start", C.c_int32)]
+
+
 WGRAD_WINO, WGRAD_DIRECT, WGRAD_SMALL = 0, 1, 2
 
 _vp, _i, _ll, _f = C.c_void_p, C.c_int, C.c_longlong, C.c_float
@@ -64,6 +75,8 @@ SIGNATURES = {
     "w2l_crop_resize_u8": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
     "w2l_resize_u8": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i]),
     "w2l_resize_paste_u8": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i]),
+    "w2l_crop_resize_rows_u8": (_i, [_vp, _i, _vp, _i, _vp]),
+    "w2l_compose_rows_u8": (_i, [_vp, _i, _vp, _i, _vp, _i]),
     "w2l_s3fd_pack": (_i, [_vp, _ll, _vp, _vp, _i]),
     "w2l_maxpool2x2": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i]),
     "w2l_l2norm_scale": (_i, [_vp, _ll, _i, _vp, _i, _vp, _vp, _i]),
@@ -83,6 +96,8 @@ SIGNATURES = {
     "w2l_melspectrogram": (_i, [_vp, _vp, _vp, _ll, _vp]),
     "w2l_mel_gather": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i]),
     "w2l_mel_gather_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i]),
+    "w2l_mel_gather_rows": (_i, [_vp, _vp, _i, _vp, _i, _i]),
+    "w2l_mel_gather_rows_bf16": (_i, [_vp, _vp, _i, _vp, _i, _i]),
     "w2l_resample_sinc": (_i, [_vp, _vp, _i, _vp, _i, C.c_double, _vp, _vp, _i, _i, _vp]),
     "w2l_l2norm_rows": (_i, [_vp, _i, _i, _vp, _i, _vp]),
     "w2l_cosine_bce": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),

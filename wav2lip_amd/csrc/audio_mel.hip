@@ -103,6 +103,30 @@ __global__ void mel_gather_kernel(const float* __restrict__ mel, int T_, const i
     }
 }
 
+// mel_gather_kernel with one spectrogram per row (w2l_mel_row: rows of different clips share a batch)
+struct MelRow {
+    unsigned long long mel;
+    int T, start;
+};
+static_assert(sizeof(MelRow) == 16, "w2l_mel_row is 16 bytes");
+
+template <typename T>
+__global__ void mel_gather_rows_kernel(const MelRow* __restrict__ rows, int B, T* __restrict__ out, int out_cs, int c_zero_to) {
+    const long long total = (long long)B * kMels * 16;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (long long)gridDim.x * blockDim.x) {
+        const int j = (int)(i & 15);
+        const int m = (int)((i >> 4) % kMels);
+        const int b = (int)(i / (16 * kMels));
+        const MelRow r = rows[b];
+        const float* mel = reinterpret_cast<const float*>(r.mel);
+        const int s = r.start + j;
+        T* o = out + i * out_cs;
+        o[0] = (T)((s >= 0 && s < r.T) ? mel[(long long)m * r.T + s] : 0.f);
+        for (int c = 1; c < c_zero_to; ++c) o[c] = (T)0.f;
+    }
+}
+
 }  // namespace w2l
 
 using namespace w2l;
@@ -224,9 +248,32 @@ static int mel_gather_t(void* stream, const float* mel, int T, const int32_t* st
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }
+template <typename T_>
+static int mel_gather_rows_t(void* stream, const w2l_mel_row* rows, int B, T_* out, int out_cs, int c_zero_to) {
+    W2L_REQUIRE(rows && out, "bad mel_gather_rows arguments");
+    W2L_REQUIRE(B >= 1 && B <= 65535 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0,
+                "mel_gather_rows: 1 <= B <= 65535 and a 16-byte aligned row table");
+    if (c_zero_to < 1) c_zero_to = 1;
+    W2L_REQUIRE(out_cs >= c_zero_to, "out_cs=%d < %d", out_cs, c_zero_to);
+    const long long total = (long long)B * kMels * 16;
+    long long g = (total + 255) / 256;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(mel_gather_rows_kernel<T_>, dim3((unsigned)g), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const MelRow*>(rows), B, out, out_cs, c_zero_to);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
 }  // namespace w2l
 
 extern "C" {
+
+int w2l_mel_gather_rows(void* stream, const w2l_mel_row* rows, int B, float* out, int out_cs, int c_zero_to) {
+    return mel_gather_rows_t<float>(stream, rows, B, out, out_cs, c_zero_to);
+}
+
+int w2l_mel_gather_rows_bf16(void* stream, const w2l_mel_row* rows, int B, void* out, int out_cs, int c_zero_to) {
+    return mel_gather_rows_t<__bf16>(stream, rows, B, static_cast<__bf16*>(out), out_cs, c_zero_to);
+}
 
 int w2l_mel_gather(void* stream, const float* mel, int T, const int32_t* starts, int B, float* out, int out_cs,
                    int c_zero_to) {

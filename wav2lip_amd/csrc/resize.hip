@@ -110,6 +110,76 @@ __global__ void resize_frames_kernel(int B, const uint8_t* __restrict__ src, int
     }
 }
 
+// ---- row-table forms (evaluation/gen_videos_from_filelist.py:85-95, :221-227): every row names its own frame, so rows of
+// clips with different frame shapes share one launch.  Same resize_px arithmetic as the kernels above: byte-equal results.
+struct FrameRow {           // mirrors w2l_frame_row (include/w2l_hip.h), 48 bytes
+    unsigned long long src, dst;
+    int H, W, y1, y2, x1, x2;
+    int pad0, pad1;
+};
+static_assert(sizeof(FrameRow) == 48, "w2l_frame_row is 48 bytes");
+
+__global__ void crop_resize_rows_kernel(int B, const FrameRow* __restrict__ rows, int S, uint8_t* __restrict__ out) {
+    const int b = blockIdx.y;
+    const FrameRow r = rows[b];
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(r.src) + ((long long)r.y1 * r.W + r.x1) * 3;
+    const int Hs = r.y2 - r.y1, Ws = r.x2 - r.x1;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < S * S; i += gridDim.x * blockDim.x) {
+        const int dy = i / S, dx = i - dy * S;
+        uint8_t px[3];
+        resize_px(src, (long long)r.W * 3, Hs, Ws, dx, dy, S, S, px);
+        uint8_t* o = out + ((long long)b * S * S + i) * 3;
+        o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
+    }
+}
+
+// One pass over the whole output frame: a thread owns 4 consecutive pixels (12 bytes = 3 dwords of the flattened frame).  A
+// group that lies outside the box in 4-byte aligned frames moves as three dwords (skipped when the paste is in place); any
+// other group goes pixel by pixel, box pixels from the resized prediction.  HBM-bound byte traffic, no LDS.
+__global__ void compose_rows_kernel(int B, const uint8_t* __restrict__ pred, int S, const FrameRow* __restrict__ rows) {
+    const int b = blockIdx.y;
+    const FrameRow r = rows[b];
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(r.src);
+    uint8_t* dst = reinterpret_cast<uint8_t*>(r.dst);
+    const uint8_t* p = pred + (long long)b * S * S * 3;
+    const int h = r.y2 - r.y1, w = r.x2 - r.x1;
+    const int npx = r.H * r.W;                          // < 2^31 / 3 (checked by the caller's max_frame_pixels)
+    const int ngroups = (npx + 3) >> 2;
+    const bool in_place = src == dst;
+    const bool dwords = (((r.src | r.dst) & 3) == 0);
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += gridDim.x * blockDim.x) {
+        const int i0 = g << 2, i1 = min(i0 + 4, npx);
+        const int ya = i0 / r.W, xa = i0 - ya * r.W;
+        const int yb = (i1 - 1) / r.W, xb = (i1 - 1) - yb * r.W;
+        // the group touches the box iff one of its frame rows does within its span of columns (frames narrower than 4 pixels,
+        // where a group can span three rows or more, take the per-pixel path)
+        const bool a_in = ya >= r.y1 && ya < r.y2 && xa < r.x2 && (ya == yb ? xb : r.W - 1) >= r.x1;
+        const bool b_in = yb != ya && yb >= r.y1 && yb < r.y2 && xb >= r.x1;
+        if (r.W >= 4 && !a_in && !b_in) {
+            if (in_place) continue;
+            if (dwords && i1 - i0 == 4) {
+                const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src + (long long)i0 * 3);
+                uint32_t* d4 = reinterpret_cast<uint32_t*>(dst + (long long)i0 * 3);
+                const uint32_t v0 = s4[0], v1 = s4[1], v2 = s4[2];
+                d4[0] = v0; d4[1] = v1; d4[2] = v2;
+                continue;
+            }
+        }
+        for (int i = i0; i < i1; ++i) {
+            const int y = i / r.W, x = i - y * r.W;
+            uint8_t* o = dst + (long long)i * 3;
+            if (y >= r.y1 && y < r.y2 && x >= r.x1 && x < r.x2) {
+                uint8_t px[3];
+                resize_px(p, (long long)S * 3, S, S, x - r.x1, y - r.y1, w, h, px);
+                o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
+            } else if (!in_place) {
+                const uint8_t* q = src + (long long)i * 3;
+                o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
+            }
+        }
+    }
+}
+
 }  // namespace w2l
 
 using namespace w2l;
@@ -148,6 +218,30 @@ int w2l_resize_paste_u8(void* stream, int B, const uint8_t* pred, int S, const i
     if (gx > 256) gx = 256;
     hipLaunchKernelGGL(resize_paste_kernel, dim3(gx, B), dim3(256), 0, static_cast<hipStream_t>(stream), B, pred, S, boxes,
                        frame_idx, frames, H, W);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_crop_resize_rows_u8(void* stream, int B, const w2l_frame_row* rows, int S, uint8_t* out) {
+    W2L_REQUIRE(rows && out && S >= 1, "bad crop_resize_rows arguments");
+    W2L_REQUIRE(B >= 1 && B <= 65535 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0,
+                "crop_resize_rows: 1 <= B <= 65535 and a 16-byte aligned row table");
+    int gx = ceil_div(S * S, 256);
+    if (gx > 64) gx = 64;
+    hipLaunchKernelGGL(crop_resize_rows_kernel, dim3(gx, B), dim3(256), 0, static_cast<hipStream_t>(stream), B,
+                       reinterpret_cast<const FrameRow*>(rows), S, out);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_compose_rows_u8(void* stream, int B, const uint8_t* pred, int S, const w2l_frame_row* rows, int max_frame_pixels) {
+    W2L_REQUIRE(pred && rows && S >= 1 && max_frame_pixels >= 1 && max_frame_pixels <= (1 << 29), "bad compose_rows arguments");
+    W2L_REQUIRE(B >= 1 && B <= 65535 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0,
+                "compose_rows: 1 <= B <= 65535 and a 16-byte aligned row table");
+    int gx = ceil_div(ceil_div(max_frame_pixels, 4), 256);
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(compose_rows_kernel, dim3(gx, B), dim3(256), 0, static_cast<hipStream_t>(stream), B, pred, S,
+                       reinterpret_cast<const FrameRow*>(rows));
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

@@ -1,0 +1,201 @@
+"""The reference's evaluation/gen_videos_from_filelist.py on the HIP path: every line `audio_src video` of `--filelist` drives the
+lips of `<data_root>/<video>` with the audio of `<data_root>/<audio_src>` and writes `<results_dir>/<line index>.avi`.  This is how
+the benchmark videos for LSE-D / LSE-C are produced.
+
+    python -m wav2lip_amd.gen_videos_from_filelist --filelist test.txt --results_dir out/ --data_root LRS2/main \\
+        --checkpoint_path wav2lip.pth
+    python -m torch.distributed.run --nproc-per-node 8 -m wav2lip_amd.gen_videos_from_filelist ...
+
+The reference runs one clip at a time (:205-227), every clip a ragged batch of its own.  Here a producer reads a line, computes
+its mel and its face boxes and hands the clip to `multiclip.lipsync_many`, which packs the rows of successive clips into full
+generator batches; face detection of the next clip runs on the caller's stream while the lanes run earlier batches.
+
+Per line the steps are the reference's `main()` (:158-235).  Differences, all on the file-format side and the same ones
+`inference.main` and `preprocess` document: inputs are `<data_root>/<name>.avi`, the uncompressed AVI of container.py (24-bit BGR,
+PCM16 audio); the driving audio is the PCM track of `<audio_src>.avi`, written to a temporary WAV (the reference's
+`temp/temp.wav`, :167-171) and read back with `audio.load_wav(path, 16000)`, so the mono mix and the resampling are the existing
+ones; the result is ONE AVI with that audio muxed in (the reference's `temp/result.avi` + ffmpeg, :229-235).  An input that
+cannot be decoded is reported on stderr and skipped.
+
+A line is skipped without output, and the line index still advances, when the mel has NaN (:173), the video has fewer frames
+than mel chunks (:195) or a frame has no face (:200-203); every skip names its reason on stderr.  A clip whose audio is too short
+for one full 16-column window is skipped too: the reference would fail there on an unbound `out` (:229), no batch having opened
+the writer.  Detection is `inference.face_detect` per clip: pads from `--pads`, smoothing always on with T = 5 (:74).
+
+Two flags the reference does not have, as in `inference.main`: `--precision` and `--face_det_precision`.  Under
+torch.distributed.run rank r takes the lines i with i % WORLD_SIZE == r and writes its own result files; no collectives.
+"""
+import argparse
+import os
+import sys
+import tempfile
+import traceback
+import wave
+
+import numpy as np
+
+from . import container
+
+
+def build_parser():
+    """gen_videos_from_filelist.py:14-33: the reference's flags, names, types and defaults"""
+    parser = argparse.ArgumentParser(description='Code to generate results for test filelists')
+    parser.add_argument('--filelist', type=str, help='Filepath of filelist file to read', required=True)
+    parser.add_argument('--results_dir', type=str, help='Folder to save all results into', required=True)
+    parser.add_argument('--data_root', type=str, required=True)
+    parser.add_argument('--checkpoint_path', type=str, help='Name of saved checkpoint to load weights from', required=True)
+    parser.add_argument('--pads', nargs='+', type=int, default=[0, 0, 0, 0], help='Padding (top, bottom, left, right)')
+    parser.add_argument('--face_det_batch_size', type=int, help='Single GPU batch size for face detection', default=64)
+    parser.add_argument('--wav2lip_batch_size', type=int, help='Batch size for Wav2Lip', default=128)
+    return parser
+
+
+def build_cli_parser():
+    """the reference's flags plus the two additions `inference.main` has, each fp32 by default"""
+    p = build_parser()
+    p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
+                   help='Generator arithmetic: fp32 (default, matches the reference) or bf16 storage')
+    p.add_argument('--face_det_precision', default='fp32', choices=['fp32', 'bf16'],
+                   help='Face detector arithmetic: fp32 (default, matches the reference) or bf16 storage')
+    return p
+
+
+parser = build_parser()
+cli_parser = build_cli_parser()
+fps = 25                  # gen_videos_from_filelist.py:120
+
+
+def lines_of_rank(lines, ranks):
+    """[(line index, line)] this rank runs: line i belongs to rank i % world (the dealing of preprocess.py)"""
+    return [(i, line) for i, line in enumerate(lines) if i % ranks.world == ranks.rank]
+
+
+def _skip(idx, line, why):
+    print("line {} ({}): skipped: {}".format(idx, line.strip(), why), file=sys.stderr)
+
+
+def _load_audio(audio_src, tmpdir):
+    """:167-171: the audio track of `audio_src` as `temp.wav`, read back with audio.load_wav.  Returns (wav float32 at 16 kHz, the
+    track's PCM16 samples, its rate)"""
+    from . import audio
+    a = container.read_avi(audio_src)
+    if a["audio"] is None:
+        raise ValueError("%s has no audio track" % audio_src)
+    pcm = np.ascontiguousarray(a["audio"], dtype='<i2')
+    temp_audio = os.path.join(tmpdir, "temp.wav")
+    with wave.open(temp_audio, 'wb') as w:
+        w.setnchannels(pcm.shape[1])
+        w.setsampwidth(2)
+        w.setframerate(int(a["audio_sr"]))
+        w.writeframes(pcm.tobytes())
+    return audio.load_wav(temp_audio, 16000), pcm, int(a["audio_sr"])
+
+
+def clip_jobs(args, lines, ranks, detector, tracks):
+    """the producer: one multiclip.ClipJob per runnable line of this rank, in line order.  `tracks[line index]` receives
+    (frame size (w, h), PCM16 audio, rate) for the sink that opens the line's writer."""
+    import torch
+    from . import audio, inference, multiclip
+    with tempfile.TemporaryDirectory(prefix="w2l_filelist_") as tmpdir:
+        for idx, line in lines_of_rank(lines, ranks):
+            try:
+                audio_src, video = line.strip().split()
+                audio_src = os.path.join(args.data_root, audio_src) + '.avi'
+                video = os.path.join(args.data_root, video) + '.avi'
+                try:
+                    wav, pcm, sr = _load_audio(audio_src, tmpdir)
+                    clip = container.read_avi(video)
+                except KeyboardInterrupt:
+                    raise
+                except Exception:
+                    traceback.print_exc()
+                    _skip(idx, line, "an input could not be decoded (uncompressed BGR AVI with PCM16 audio only)")
+                    continue
+                mel = audio.melspectrogram_device(wav, ranks.device)
+                if bool(torch.isnan(mel).any()):
+                    _skip(idx, line, "the mel spectrogram contains NaN")
+                    continue
+                n_chunks = len(multiclip.filelist_chunk_starts(mel.shape[1]))
+                if n_chunks == 0:
+                    _skip(idx, line, "the audio is shorter than one 16-column mel window")
+                    continue
+                full_frames = list(clip["frames"])
+                if len(full_frames) < n_chunks:
+                    _skip(idx, line, "the video has fewer frames ({}) than mel chunks ({})".format(len(full_frames), n_chunks))
+                    continue
+                full_frames = full_frames[:n_chunks]
+                try:
+                    det = inference.face_detect(full_frames, detector=detector, pads=args.pads, nosmooth=False,
+                                                batch_size=args.face_det_batch_size)
+                except ValueError as e:
+                    _skip(idx, line, str(e))
+                    continue
+                rows = multiclip.rows_filelist(mel.shape[1], len(full_frames), [c for _, c in det])
+                frame_h, frame_w = full_frames[0].shape[:-1]
+                tracks[idx] = ((frame_w, frame_h), pcm, sr)
+                yield multiclip.ClipJob(idx, full_frames, mel, rows)
+            except KeyboardInterrupt:
+                raise
+            except ValueError as e:                      # a malformed line, a box outside its frame
+                traceback.print_exc()
+                _skip(idx, line, str(e))
+
+
+class ResultSink:
+    """one AviWriter per open job: `<results_dir>/<line index>.avi` with the driving audio (:211-212, :227-235)"""
+
+    def __init__(self, results_dir, tracks):
+        self.results_dir, self.tracks, self.open, self.written = results_dir, tracks, {}, []
+
+    def __call__(self, idx, frame):
+        if frame is None:
+            w = self.open.pop(idx, None)
+            if w is not None:
+                w.release()
+                self.written.append(idx)
+            return
+        w = self.open.get(idx)
+        if w is None:
+            size, pcm, sr = self.tracks.pop(idx)
+            w = self.open[idx] = container.AviWriter(os.path.join(self.results_dir, '{}.avi'.format(idx)), fps, size,
+                                                     audio=pcm, audio_sr=sr)
+        w.write(frame)
+
+    def close(self):
+        for w in self.open.values():
+            w.release()
+        self.open.clear()
+
+
+def main(argv=None, state_dict=None, backend="nccl"):
+    """gen_videos_from_filelist.py:152-235.  `state_dict` (S3FD weights) replaces face_detection/s3fd.pth; `backend` is the
+    process group's.  Returns the line indices this rank wrote, in order."""
+    from . import face_detection, inference, multiclip, sharding
+    args = cli_parser.parse_args(argv)
+    args.img_size = 96
+    ranks = sharding.init_from_env(backend)
+    try:
+        assert args.data_root is not None
+        if not os.path.isdir(args.results_dir):
+            os.makedirs(args.results_dir, exist_ok=True)
+        with open(args.filelist, 'r') as filelist:
+            lines = filelist.readlines()
+        print('Using {} for inference.'.format(ranks.device))
+        detector = face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False, device=str(ranks.device),
+                                                state_dict=state_dict,
+                                                **inference._precision_kw(inference.CLI_PRECISION[args.face_det_precision]))
+        model = inference.load_model(args.checkpoint_path, ranks.device)
+        tracks = {}
+        sink = ResultSink(args.results_dir, tracks)
+        try:
+            multiclip.lipsync_many(model, clip_jobs(args, lines, ranks, detector, tracks), batch_size=args.wav2lip_batch_size,
+                                   precision=inference.CLI_PRECISION[args.precision], sink=sink)
+        finally:
+            sink.close()
+        return sink.written
+    finally:
+        ranks.close()
+
+
+if __name__ == '__main__':
+    main()

@@ -28,6 +28,7 @@ from .checkpoint import _load, load_model  # noqa: F401  (inference.py:160-179: 
 
 mel_step_size = 16   # inference.py:156
 img_size = 96
+MEL_ROW_BYTES = 16   # sizeof(w2l_mel_row)
 
 
 # ---------------------------------------------------------------- the command-line surface (inference.py:11-57)
@@ -141,9 +142,10 @@ class Wav2LipRunner:
     def _graph(self, n):
         return self.model.graph(n, img_size, img_size, self.device, lane=self.lane, precision=self.precision)
 
-    def run_batch(self, faces_u8, mel_windows=None, mel=None, starts=None, out=None):
+    def run_batch(self, faces_u8, mel_windows=None, mel=None, starts=None, out=None, mel_rows=None):
         """faces_u8: torch uint8 [n,96,96,3] on the device.  Audio either as ready windows `mel_windows`
-        float32 [n,80,16], or as the full spectrogram `mel` [80,T] plus int32 `starts` [n] (device tensors).
+        float32 [n,80,16], or as the full spectrogram `mel` [80,T] plus int32 `starts` [n] (device tensors), or as
+        `mel_rows`: a device uint8 tensor holding n w2l_mel_row entries (one spectrogram per row, wav2lip_amd/multiclip.py).
         Returns torch uint8 [n,96,96,3] (BGR order preserved), valid until the next call; `out` (a contiguous uint8
         [n,96,96,3] device tensor, e.g. the send slot of the multi-GPU frame gatherer) receives the frames instead."""
         n = faces_u8.shape[0]
@@ -152,8 +154,9 @@ class Wav2LipRunner:
             parts = []
             for lo in range(0, n, cap):
                 hi = min(n, lo + cap)
+                rows_kw = {} if mel_rows is None else {"mel_rows": mel_rows[lo * MEL_ROW_BYTES:hi * MEL_ROW_BYTES]}
                 parts.append(self.run_batch(faces_u8[lo:hi], None if mel_windows is None else mel_windows[lo:hi], mel,
-                                            None if starts is None else starts[lo:hi].contiguous()).clone())
+                                            None if starts is None else starts[lo:hi].contiguous(), **rows_kw).clone())
             allf = torch.cat(parts, dim=0)
             if out is not None:
                 out.copy_(allf)
@@ -164,7 +167,9 @@ class Wav2LipRunner:
         faces_u8 = faces_u8.contiguous()
         if self.precision == "bf16":
             check(self.lib.w2l_datagen_pack_bf16(s, n, img_size, ptr(faces_u8), ptr(g.x_in), 8, 8), "datagen_pack_bf16")
-            if mel_windows is not None:
+            if mel_rows is not None:
+                check(self.lib.w2l_mel_gather_rows_bf16(s, ptr(mel_rows), n, ptr(g.mel_in), 8, 8), "mel_gather_rows_bf16")
+            elif mel_windows is not None:
                 mw = mel_windows.contiguous().float().view(n, 1, 80, 16)
                 check(self.lib.w2l_nchw_to_nhwc_bf16(s, n, 1, 80, 16, ptr(mw), ptr(g.mel_in), 8, 8), "nchw_to_nhwc_bf16")
             else:
@@ -172,7 +177,9 @@ class Wav2LipRunner:
                       "mel_gather_bf16")
         else:
             check(self.lib.w2l_datagen_pack(s, n, img_size, ptr(faces_u8), ptr(g.x_in), 8, 8), "datagen_pack")
-            if mel_windows is not None:
+            if mel_rows is not None:
+                check(self.lib.w2l_mel_gather_rows(s, ptr(mel_rows), n, ptr(g.mel_in), 4, 4), "mel_gather_rows")
+            elif mel_windows is not None:
                 mw = mel_windows.contiguous().float().view(n, 1, 80, 16)
                 check(self.lib.w2l_nchw_to_nhwc(s, n, 1, 80, 16, ptr(mw), ptr(g.mel_in), 4, 4), "nchw_to_nhwc")
             else:
@@ -196,6 +203,17 @@ class Wav2LipRunner:
 
     def last_pred_nchw(self):
         return self._last.output_nchw()
+
+    def run_rows(self, n, frame_rows, mel_rows, max_frame_pixels):
+        """`run_frames` for rows that each name their own frame (wav2lip_amd/multiclip.py): `frame_rows` / `mel_rows` are device
+        uint8 tensors holding n w2l_frame_row / w2l_mel_row entries.  Crops and resizes every row's face, runs the batch and
+        composes every row's output frame at its `dst` address in one pass (gen_videos_from_filelist.py:85-95, :221-227)."""
+        s = current_stream()
+        faces = torch.empty((n, img_size, img_size, 3), dtype=torch.uint8, device=self.device)
+        check(self.lib.w2l_crop_resize_rows_u8(s, n, ptr(frame_rows), img_size, ptr(faces)), "crop_resize_rows_u8")
+        pred = self.run_batch(faces, mel_rows=mel_rows)
+        check(self.lib.w2l_compose_rows_u8(s, n, ptr(pred), img_size, ptr(frame_rows), int(max_frame_pixels)), "compose_rows_u8")
+        return pred
 
     def run_frames(self, frames, frame_idx, boxes, mel_windows=None, mel=None, starts=None):
         """Full-frame variant of `run_batch` (inference.py:121-126 + :259-271).  frames: torch uint8 [F,H,W,3] on the
@@ -239,19 +257,32 @@ class PipelinedRunner:
         self.depth = depth
         self.n = 0
 
-    def submit(self, faces_u8, mel_windows=None, mel=None, starts=None, frames=None, frame_idx=None, boxes=None, out=None):
+    def submit(self, faces_u8, mel_windows=None, mel=None, starts=None, frames=None, frame_idx=None, boxes=None, out=None, *,
+               rows=None, upload=None, download=None, keep=()):
+        """`rows=(n, frame_rows, mel_rows, max_frame_pixels)` runs `Wav2LipRunner.run_rows` on the lane; `upload` / `download`
+        are (destination, source) tensor pairs copied on the lane's stream before / after the batch (pinned host memory on the
+        host side: the copies overlap the other lanes); `keep` are further device tensors the lane reads."""
         k = self.n % len(self.lanes)
         self.n += 1
         st = self.streams[k]
         st.wait_stream(torch.cuda.current_stream())       # inputs were produced on the caller's stream
-        for t in (faces_u8, mel_windows, mel, starts, frames):
+        extra = tuple(keep) + tuple(t for pair in (upload, download) if pair is not None for t in pair)
+        if rows is not None:
+            extra += (rows[1], rows[2])
+        for t in (faces_u8, mel_windows, mel, starts, frames) + extra:
             if isinstance(t, torch.Tensor) and t.is_cuda:
                 t.record_stream(st)                        # the allocator must not recycle them while the lane still reads
         with torch.cuda.stream(st):
-            if frames is not None:
+            if upload is not None:
+                upload[0].copy_(upload[1], non_blocking=True)
+            if rows is not None:
+                out = self.lanes[k].run_rows(*rows)
+            elif frames is not None:
                 out = self.lanes[k].run_frames(frames, frame_idx, boxes, mel_windows=mel_windows, mel=mel, starts=starts)
             else:
                 out = self.lanes[k].run_batch(faces_u8, mel_windows=mel_windows, mel=mel, starts=starts, out=out)
+            if download is not None:
+                download[0].copy_(download[1], non_blocking=True)
             done = torch.cuda.Event()
             done.record(st)
         return (out, done)

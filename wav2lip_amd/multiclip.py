@@ -1,0 +1,228 @@
+"""Many clips through the generator in shared batches: the loop of the reference's evaluation/gen_videos_from_filelist.py
+(:205-227, one clip at a time, every clip a ragged batch of its own) with the rows of successive clips packed into full batches.
+
+Frames are independent given the weights, so a batch may hold rows of several clips.  A row is one generator
+input: (frame of its clip, face box, first mel column).  Rows are appended across clip boundaries until a batch holds
+`batch_size` of them - only the very last batch of a run is ragged - so the model builds plans for at most two batch sizes
+per lane whatever the clip lengths, every batch but the last runs the committed launch configurations of `batch_size`, and
+`LIPSYNC_DEPTH` batches are in flight from the first clip to the last.
+
+Per batch (`BatchRunner.submit`): the (clip, frame) pairs the batch touches are deduplicated and staged in ONE pinned buffer
+together with the two row tables (w2l_frame_row / w2l_mel_row, include/w2l_hip.h), copied to the device once, then on the lane's
+stream  w2l_crop_resize_rows_u8 -> w2l_datagen_pack -> w2l_mel_gather_rows -> the plan -> w2l_frames_to_u8 (fp32 only) ->
+w2l_compose_rows_u8,  and the composed frames come back in one copy.  Frames of different clips may have different shapes.
+
+`rows_inference` / `rows_filelist` are the two row conventions of the reference (inference.py:231-240 and
+gen_videos_from_filelist.py:176-198); the packer knows nothing about either.
+"""
+import collections
+
+import numpy as np
+
+from .inference import LIPSYNC_DEPTH, mel_chunk_starts, mel_step_size, validate_boxes
+
+# numpy mirrors of w2l_frame_row (48 bytes) and w2l_mel_row (16 bytes); the ctypes mirrors are _lib.FrameRow / _lib.MelRow
+FRAME_ROW = np.dtype([("src", "<u8"), ("dst", "<u8"), ("H", "<i4"), ("W", "<i4"), ("y1", "<i4"), ("y2", "<i4"), ("x1", "<i4"),
+                      ("x2", "<i4"), ("pad", "<i4", (2,))])
+MEL_ROW = np.dtype([("mel", "<u8"), ("T", "<i4"), ("start", "<i4")])
+_ALIGN = 16          # every staged frame and both tables start on a 16-byte boundary
+
+ClipJob = collections.namedtuple("ClipJob", "key frames mel rows")
+ClipJob.__doc__ = """one clip: `frames` uint8 [H,W,3] BGR frames (one shape per clip; a list or an [F,H,W,3] array), `mel` the device
+[80,T] spectrogram (audio.melspectrogram_device), `rows` a list of (frame_index, (y1, y2, x1, x2), mel_start)"""
+
+
+def rows_inference(n_mel, n_frames, boxes, fps=25., static=False):
+    """rows of inference.py:231-240 + :108-131: one row per mel chunk at `fps`, the tail window re-anchored at the end, chunk i
+    on frame i % n_frames (frame 0 when static) with that frame's box"""
+    starts = mel_chunk_starts(n_mel, fps)
+    idx = [0 if static else i % n_frames for i in range(len(starts))]
+    return [(j, tuple(int(v) for v in boxes[j]), s) for j, s in zip(idx, starts)]
+
+
+def filelist_chunk_starts(n_mel):
+    """gen_videos_from_filelist.py:176-183: start column of every FULL 16-column window at 25 fps; no tail window"""
+    mel_idx_multiplier = 80. / 25
+    starts = []
+    i = 0
+    while True:
+        start_idx = int(i * mel_idx_multiplier)
+        if start_idx + mel_step_size > n_mel:
+            return starts
+        starts.append(start_idx)
+        i += 1
+
+
+def rows_filelist(n_mel, n_frames, boxes):
+    """rows of gen_videos_from_filelist.py:176-198 + :82-95: chunk i on frame i, frames truncated to the chunk count.  A clip
+    with fewer frames than chunks is not runnable (:195 skips it): ValueError"""
+    starts = filelist_chunk_starts(n_mel)
+    if n_frames < len(starts):
+        raise ValueError("%d frames for %d mel chunks: the video is shorter than its audio" % (n_frames, len(starts)))
+    return [(i, tuple(int(v) for v in boxes[i]), s) for i, s in enumerate(starts)]
+
+
+class _Job:
+    """a ClipJob while rows of it are undelivered"""
+
+    def __init__(self, job, n_rows):
+        self.key, self.frames, self.mel, self.n_rows, self.delivered = job.key, job.frames, job.mel, n_rows, 0
+        self.closed_after = []       # keys of zero-row jobs that follow this one: closed right after it, in job order
+
+    def release(self):
+        self.frames = self.mel = None
+
+
+def _align(n):
+    return (n + _ALIGN - 1) // _ALIGN * _ALIGN
+
+
+class BatchRunner:
+    """the device side of the packer: `submit(rows)` stages, launches and starts the copy back of one packed batch on the
+    next lane and returns a ticket, `result(ticket)` waits for it and returns one uint8 [H,W,3] array per row.
+    rows: [(job, frame_index, (y1, y2, x1, x2), mel_start)]"""
+
+    def __init__(self, model, batch_size, depth, precision):
+        import torch
+        from .inference import PipelinedRunner, _precision_kw
+        self.torch = torch
+        self.runner = PipelinedRunner(model, batch_size, depth=depth, **_precision_kw(precision))
+        self.device = self.runner.lanes[0].device
+
+    def submit(self, rows):
+        torch = self.torch
+        n = len(rows)
+        # ---- layout of the staging buffer: [frame-row table][mel-row table][deduplicated frames]; outputs in a buffer of their own
+        off = _align(n * FRAME_ROW.itemsize)
+        mel_off = off
+        off = _align(off + n * MEL_ROW.itemsize)
+        src_off, frames = {}, []
+        for job, fi, _, _ in rows:
+            if (id(job), fi) not in src_off:
+                f = np.asarray(job.frames[fi])
+                src_off[(id(job), fi)] = off
+                frames.append((off, f))
+                off = _align(off + f.nbytes)
+        out_off, out_bytes = [], 0
+        for job, fi, _, _ in rows:
+            out_off.append(out_bytes)
+            out_bytes = _align(out_bytes + np.asarray(job.frames[fi]).nbytes)
+        host = torch.empty(off, dtype=torch.uint8, pin_memory=True)
+        dev = torch.empty(off, dtype=torch.uint8, device=self.device)
+        dev_out = torch.empty(out_bytes, dtype=torch.uint8, device=self.device)
+        host_out = torch.empty(out_bytes, dtype=torch.uint8, pin_memory=True)
+        stage = host.numpy()
+        for o, f in frames:
+            stage[o:o + f.nbytes] = f.reshape(-1)
+        ft = stage[:n * FRAME_ROW.itemsize].view(FRAME_ROW)
+        mt = stage[mel_off:mel_off + n * MEL_ROW.itemsize].view(MEL_ROW)
+        shapes, mels, max_px = [], {}, 1
+        for r, (job, fi, (y1, y2, x1, x2), start) in enumerate(rows):
+            H, W = np.asarray(job.frames[fi]).shape[:2]
+            ft[r] = (dev.data_ptr() + src_off[(id(job), fi)], dev_out.data_ptr() + out_off[r], H, W, y1, y2, x1, x2, (0, 0))
+            mt[r] = (job.mel.data_ptr(), job.mel.shape[1], start)
+            mels[id(job)] = job.mel
+            shapes.append((H, W))
+            max_px = max(max_px, H * W)
+        ticket = self.runner.submit(None, rows=(n, dev[:n * FRAME_ROW.itemsize], dev[mel_off:mel_off + n * MEL_ROW.itemsize], max_px),
+                                    upload=(dev, host), download=(host_out, dev_out), keep=tuple(mels.values()))
+        return ticket, host_out, out_off, shapes
+
+    def result(self, item):
+        (_, done), host_out, out_off, shapes = item
+        done.synchronize()                       # the copy back is part of the lane's work: wait on the host, then read
+        buf = host_out.numpy()
+        return [buf[o:o + h * w * 3].reshape(h, w, 3).copy() for o, (h, w) in zip(out_off, shapes)]
+
+
+def _checked_rows(job):
+    """the job's rows with every box, frame number and mel window validated; a ValueError names the job"""
+    rows = []
+    T = int(job.mel.shape[1])
+    for fi, box, start in job.rows:
+        fi, start = int(fi), int(start)
+        try:
+            if not 0 <= fi < len(job.frames):
+                raise ValueError("frame index %d outside the clip's %d frames" % (fi, len(job.frames)))
+            f = job.frames[fi]
+            if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
+                raise ValueError("frames must be uint8 [H,W,3] arrays, got %s %s" % (f.dtype, f.shape))
+            if start < 0 or start + mel_step_size > T:
+                raise ValueError("mel window [%d, %d) outside the %d columns of the spectrogram" % (start, start + mel_step_size, T))
+            box = validate_boxes([box], f.shape[0], f.shape[1])[0]
+        except ValueError as e:
+            raise ValueError("job %r: %s" % (job.key, e)) from None
+        rows.append((fi, box, start))
+    return rows
+
+
+def lipsync_many(model, jobs, batch_size=128, depth=None, precision="f32", sink=None):
+    """Run every `ClipJob` of the iterable `jobs` (consumed lazily) through the generator, rows packed across job boundaries
+    into batches of `batch_size` (only the last one ragged) on `depth` (default LIPSYNC_DEPTH) lanes.
+
+    Every output frame (the row's frame with the generated mouth region pasted into its box) goes to `sink(key, frame_u8)` in
+    row order within its job, and `sink(key, None)` follows a job's last frame; jobs finish in the order they came.  Without a
+    sink the frames are collected and returned as {key: [frames]}.  Memory is bounded whatever the number of jobs: a job's
+    frames and mel are released when its last row has been delivered, and the jobs alive at any time are those the rows of at
+    most `depth + 1` batches touch, plus the one being read."""
+    from .models.wav2lip import check_precision
+    check_precision(precision)
+    if batch_size < 1:
+        raise ValueError("batch_size must be at least 1")
+    depth = depth or LIPSYNC_DEPTH
+    collected = None
+    if sink is None:
+        collected = {}
+
+        def sink(key, frame):
+            lst = collected.setdefault(key, [])
+            if frame is not None:
+                lst.append(frame)
+
+    runner = None
+    pending = collections.deque()      # (ticket, [job per row]) of the batches in flight, oldest first
+    batch = []                         # rows of the batch being filled
+    last = None                        # the newest job with undelivered rows
+
+    def finish(job):
+        job.release()
+        sink(job.key, None)
+        for key in job.closed_after:
+            sink(key, None)
+
+    def collect():
+        item, owners = pending.popleft()
+        for job, frame in zip(owners, runner.result(item)):
+            sink(job.key, frame)
+            job.delivered += 1
+            if job.delivered == job.n_rows:
+                finish(job)
+
+    def flush():
+        nonlocal batch
+        pending.append((runner.submit(batch), [r[0] for r in batch]))
+        batch = []
+        if len(pending) >= depth:
+            collect()
+
+    for cj in jobs:
+        rows = _checked_rows(cj)
+        if runner is None:
+            runner = BatchRunner(model, batch_size, depth, precision)
+        if not rows:                                   # nothing to run: closed in job order
+            if last is not None and last.delivered < last.n_rows:
+                last.closed_after.append(cj.key)
+            else:
+                sink(cj.key, None)
+            continue
+        job = last = _Job(cj, len(rows))
+        del cj
+        for fi, box, start in rows:
+            batch.append((job, fi, box, start))
+            if len(batch) == batch_size:
+                flush()
+    if batch:
+        flush()
+    while pending:
+        collect()
+    return collected

@@ -184,3 +184,43 @@ def sketch_vectors(name, n, k=4):
     DIRECTION in a golden file that cannot hold the tensor (E <d, r>^2 = |d|^2 for a difference d)"""
     r = np.random.default_rng([77, zlib.crc32(name.encode())])
     return r.integers(0, 2, (k, n), dtype=np.int8) * 2 - 1
+
+
+# ---------------------------------------------------------------- filelist generation (evaluation/gen_videos_from_filelist.py)
+FILELIST_SHAPES = [(160, 160), (128, 144)]      # (H, W) of the two frame shapes
+FILELIST_POOL = 6                                # distinct frames per shape; a clip cycles through its shape's pool
+# (clip name, shape index, frames, mel chunks of its audio, index of a face-less frame or None)
+FILELIST_CLIPS = [("c0", 0, 39, 37, None), ("c1", 1, 61, 61, None), ("c2", 1, 3, 9, None), ("c3", 0, 52, 50, None),
+                  ("c4", 1, 20, 18, 7), ("c5", 0, 10, 20, None)]
+# (audio source, video) per filelist line: 37, skipped (a face-less frame), 61, 9 (another clip's audio), skipped (fewer frames than
+# chunks), 50 rows: at batch 32 the packed batches are 32, 32, 32, 32, 29; the second holds rows of two clips, the fourth of three
+FILELIST_LINES = [("c0", "c0"), ("c4", "c4"), ("c1", "c1"), ("c2", "c0"), ("c5", "c5"), ("c3", "c3")]
+
+
+def filelist_frame(seed, H, W):
+    """one uint8 BGR noise frame with a saturated block at a seeded place: the seeded S3FD finds a "face" there"""
+    r = _rng(seed, "filelist")
+    out = r.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    h, w = r.integers(H // 4, H // 2), r.integers(W // 4, W // 2)
+    y, x = r.integers(0, H - h), r.integers(0, W - w)
+    out[y:y + h, x:x + w] = 255 if r.uniform() < 0.5 else 0
+    return out
+
+
+def filelist_samples(n_chunks):
+    """audio samples whose spectrogram (1 + n // 200 columns) holds exactly `n_chunks` full 16-column windows at 25 fps"""
+    return (int((n_chunks - 1) * 3.2) + 16 - 1) * 200 + 50
+
+
+def filelist_clips(seed=3):
+    """{clip name: (frames uint8 [T,H,W,3] BGR, mono PCM16 audio int16 [n,1] at 16 kHz)} of FILELIST_CLIPS"""
+    pools = [[filelist_frame(seed * 1000 + 10 * s + k, H, W) for k in range(FILELIST_POOL)] for s, (H, W) in enumerate(FILELIST_SHAPES)]
+    clips = {}
+    for i, (name, s, t, chunks, faceless) in enumerate(FILELIST_CLIPS):
+        frames = np.stack([pools[s][(k + i) % FILELIST_POOL] for k in range(t)])
+        if faceless is not None:
+            H, W = FILELIST_SHAPES[s]
+            frames[faceless] = 120 + _rng(seed * 1000 + i, "filelist_grey").integers(-1, 2, (H, W, 3))
+        pcm = _rng(seed * 1000 + i, "filelist_audio").integers(-8000, 8000, (filelist_samples(chunks), 1)).astype(np.int16)
+        clips[name] = (frames, pcm)
+    return clips
