@@ -1,5 +1,5 @@
-"""Train-mode BatchNorm, activation backward, column sums, row adds (csrc/train_bf16.hip and their fp32 twins in
-csrc/train.hip) and the bf16 graph-boundary layout changes, through the C ABI, against float64 references computed with torch on
+"""Train-mode BatchNorm, activation backward, column sums, row adds (csrc/train_rows.hip: one set of kernels instantiated for
+bf16 and fp32 storage) and the bf16 graph-boundary layout changes (csrc/api.hip), through the C ABI, against float64 references computed with torch on
 the CPU from the SAME values the device holds: inputs are rounded to the storage type first, then widened; the backward
 references take the fp32 mean / rstd / scale / shift vectors the kernel consumed.
 
@@ -23,7 +23,7 @@ stray read poisons the result), those outside an output's slice a sentinel that 
 per-channel outputs come out exactly 0; the per-channel inputs (gamma, beta, running stats) hold NaN / the sentinel there.
 
 The column reductions are run through every partial regime of their launch rule (launch_rule below, a transcription of
-colb_launch / col_reduce_launch): one workgroup, 2-12 workgroups (the finalize's 4-wide walk only), >= 16 workgroups (its
+col_reduce_launch): one workgroup, 2-12 workgroups (the finalize's 4-wide walk only), >= 16 workgroups (its
 16-wide walk, then the 4-wide tail) and the 512-workgroup cap with a ragged last workgroup."""
 import ctypes as C
 
@@ -64,8 +64,8 @@ def _rel(prec):
 
 
 def launch_rule(prec, C_, rows):
-    """(workgroups, rows per workgroup, row lanes RPP) of colb_launch (bf16) / col_reduce_launch (fp32): C / width threads per
-    row, RPP = 256 / (C / width) rows in flight, at least RPP * 8 (bf16) / RPP * 16 (fp32) rows per workgroup, at most 512"""
+    """(workgroups, rows per workgroup, row lanes RPP) of col_reduce_launch: C / width threads per row, RPP = 256 / (C / width)
+    rows in flight, at least RPP * 64 / width rows per workgroup (8 bf16, 16 fp32: 64 elements per thread), at most 512"""
     rpp = 256 // (C_ // _width(prec))
     min_rows = rpp * (8 if prec == BF16 else 16)
     per = max(-(-rows // 512), min_rows)

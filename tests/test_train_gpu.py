@@ -812,7 +812,7 @@ def _bf16_yardstick_check(what, named_params, groups, g64, noisy, loss_hip, loss
 
 def test_bf16_training_step_tracks_the_fp32_step(cuda):
     """The bf16-STORAGE training path (BASELINE configs[3] / [4]; wav2lip_amd/autograd.py NodeB, csrc/conv_bf16.hip,
-    wgrad_bf16.hip, train_bf16.hip) on a SyncNet step (color_syncnet_train.py:155-165, train-mode BatchNorm, batch 8) and on a
+    wgrad_bf16.hip, train_rows.hip) on a SyncNet step (color_syncnet_train.py:155-165, train-mode BatchNorm, batch 8) and on a
     generator L1 step (wav2lip_train.py:220-231, 6 frames): loss and EVERY parameter gradient against the fp64 evaluation of the
     oracle graph, bounded per parameter group by a MEASURED bf16 yardstick - 3x the largest distance of three / four fp64 evaluations
     with 2**-8 relative noise injected at every conv input, weight and output and at their gradients (_bf16_storage_noise) -

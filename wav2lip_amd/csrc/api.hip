@@ -59,13 +59,6 @@ __global__ void clock_probe_kernel(unsigned long long* out, unsigned spin_ticks)
     out[1] = r1 - r0;
 }
 
-static inline int grid_for(long long work, int block, int cap = 8192) {
-    long long g = (work + block - 1) / block;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 // ---------------------------------------------------------------- BN fold
 __global__ void bn_fold_kernel(int C, const float* bias, const float* gamma, const float* beta,
                                const float* mean, const float* var, float eps, float* scale, float* shift) {
@@ -82,8 +75,10 @@ __global__ void bn_fold_kernel(int C, const float* bias, const float* gamma, con
 }
 
 // ---------------------------------------------------------------- layout
-// NCHW -> NHWC through a 32x33 LDS tile over (C, HW): coalesced on both sides
-__global__ void nchw_to_nhwc_kernel(int C, int HW, const float* __restrict__ x, float* __restrict__ y,
+// fp32 NCHW -> NHWC through a 32x33 LDS tile over (C, HW): coalesced on both sides; channels [C, c_zero_to) zero-filled.
+// T is the NHWC element: float, or __bf16 at the boundary of a bf16-storage graph (one rounding, RNE)
+template <typename T>
+__global__ void nchw_to_nhwc_kernel(int C, int HW, const float* __restrict__ x, T* __restrict__ y,
                                     int y_cs, int c_zero_to) {
     __shared__ float tile[32][33];
     const int n = blockIdx.z;
@@ -96,11 +91,13 @@ __global__ void nchw_to_nhwc_kernel(int C, int HW, const float* __restrict__ x, 
     __syncthreads();
     for (int j = ty; j < 32; j += 8) {
         const int p = p0 + j, c = c0 + tx;
-        if (p < HW && c < c_zero_to) y[((long long)n * HW + p) * y_cs + c] = tile[tx][j];
+        if (p < HW && c < c_zero_to) y[((long long)n * HW + p) * y_cs + c] = (T)tile[tx][j];
     }
 }
 
-__global__ void nhwc_to_nchw_kernel(int C, int HW, const float* __restrict__ x, int x_cs,
+// NHWC (first C channels) -> fp32 NCHW
+template <typename T>
+__global__ void nhwc_to_nchw_kernel(int C, int HW, const T* __restrict__ x, int x_cs,
                                     float* __restrict__ y) {
     __shared__ float tile[32][33];
     const int n = blockIdx.z;
@@ -108,13 +105,38 @@ __global__ void nhwc_to_nchw_kernel(int C, int HW, const float* __restrict__ x, 
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     for (int j = ty; j < 32; j += 8) {
         const int p = p0 + j, c = c0 + tx;
-        tile[j][tx] = (c < C && p < HW) ? x[((long long)n * HW + p) * x_cs + c] : 0.f;
+        tile[j][tx] = (c < C && p < HW) ? (float)x[((long long)n * HW + p) * x_cs + c] : 0.f;
     }
     __syncthreads();
     for (int j = ty; j < 32; j += 8) {
         const int c = c0 + j, p = p0 + tx;
         if (c < C && p < HW) y[((long long)n * C + c) * HW + p] = tile[tx][j];
     }
+}
+
+// `what` names the entry point in the messages
+template <typename T>
+static int nchw_to_nhwc_t(void* stream, int N, int C, int H, int W, const float* x, T* y, int y_cs, int c_zero_to, const char* what) {
+    W2L_REQUIRE(x && y && N >= 1 && C >= 1 && H >= 1 && W >= 1, "bad %s arguments", what);
+    if (c_zero_to < C) c_zero_to = C;
+    W2L_REQUIRE(y_cs >= c_zero_to, "y_cs=%d < %d", y_cs, c_zero_to);
+    W2L_REQUIRE(N <= 65535, "N too large for one launch");
+    const int HW = H * W;
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, dim3(ceil_div(HW, 32), ceil_div(c_zero_to, 32), N), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), C, HW, x, y, y_cs, c_zero_to);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+template <typename T>
+static int nhwc_to_nchw_t(void* stream, int N, int C, int H, int W, const T* x, int x_cs, float* y, const char* what) {
+    W2L_REQUIRE(x && y && N >= 1 && C >= 1 && H >= 1 && W >= 1 && x_cs >= C, "bad %s arguments", what);
+    W2L_REQUIRE(N <= 65535, "N too large for one launch");
+    const int HW = H * W;
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, dim3(ceil_div(HW, 32), ceil_div(C, 32), N), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), C, HW, x, x_cs, y);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
 }
 
 // ---------------------------------------------------------------- datagen
@@ -290,25 +312,17 @@ int w2l_bn_fold(void* stream, int C, const float* bias, const float* gamma, cons
 }
 
 int w2l_nchw_to_nhwc(void* stream, int N, int C, int H, int W, const float* x, float* y, int y_cs, int c_zero_to) {
-    W2L_REQUIRE(x && y && N >= 1 && C >= 1 && H >= 1 && W >= 1, "bad nchw_to_nhwc arguments");
-    if (c_zero_to < C) c_zero_to = C;
-    W2L_REQUIRE(y_cs >= c_zero_to, "y_cs=%d < %d", y_cs, c_zero_to);
-    W2L_REQUIRE(N <= 65535, "N too large for one launch");
-    const int HW = H * W;
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(ceil_div(HW, 32), ceil_div(c_zero_to, 32), N), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), C, HW, x, y, y_cs, c_zero_to);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
+    return nchw_to_nhwc_t<float>(stream, N, C, H, W, x, y, y_cs, c_zero_to, "nchw_to_nhwc");
+}
+int w2l_nchw_to_nhwc_bf16(void* stream, int N, int C, int H, int W, const float* x, void* y, int y_cs, int c_zero_to) {
+    return nchw_to_nhwc_t<__bf16>(stream, N, C, H, W, x, static_cast<__bf16*>(y), y_cs, c_zero_to, "nchw_to_nhwc_bf16");
 }
 
 int w2l_nhwc_to_nchw(void* stream, int N, int C, int H, int W, const float* x, int x_cs, float* y) {
-    W2L_REQUIRE(x && y && N >= 1 && C >= 1 && H >= 1 && W >= 1 && x_cs >= C, "bad nhwc_to_nchw arguments");
-    W2L_REQUIRE(N <= 65535, "N too large for one launch");
-    const int HW = H * W;
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(ceil_div(HW, 32), ceil_div(C, 32), N), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), C, HW, x, x_cs, y);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
+    return nhwc_to_nchw_t<float>(stream, N, C, H, W, x, x_cs, y, "nhwc_to_nchw");
+}
+int w2l_nhwc_bf16_to_nchw(void* stream, int N, int C, int H, int W, const void* x, int x_cs, float* y) {
+    return nhwc_to_nchw_t<__bf16>(stream, N, C, H, W, static_cast<const __bf16*>(x), x_cs, y, "nhwc_bf16_to_nchw");
 }
 
 }  // extern "C"
@@ -320,7 +334,7 @@ static int datagen_pack_t(void* stream, int N, int S, const uint8_t* faces, T* y
     if (c_zero_to < 6) c_zero_to = 6;
     W2L_REQUIRE(c_zero_to <= 8 && y_cs >= c_zero_to, "datagen_pack: need 6 <= c_zero_to <= 8 <= y_cs");
     const long long npix = (long long)N * S * S;
-    hipLaunchKernelGGL(datagen_pack_kernel<T>, dim3(grid_for(npix, 256)), dim3(256), 0,
+    hipLaunchKernelGGL(datagen_pack_kernel<T>, dim3(grid_cap(npix, 256, 8192)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), npix, S, faces, y, y_cs, c_zero_to);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
@@ -340,7 +354,7 @@ int w2l_datagen_pack_bf16(void* stream, int N, int S, const uint8_t* faces, void
 int w2l_frames_to_u8(void* stream, int N, int H, int W, const float* x, int x_cs, uint8_t* y) {
     W2L_REQUIRE(x && y && N >= 1 && H >= 1 && W >= 1 && x_cs >= 3, "bad frames_to_u8 arguments");
     const long long npix = (long long)N * H * W;
-    hipLaunchKernelGGL(frames_to_u8_kernel, dim3(grid_for(npix, 256)), dim3(256), 0,
+    hipLaunchKernelGGL(frames_to_u8_kernel, dim3(grid_cap(npix, 256, 8192)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), npix, x, x_cs, y);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;

@@ -1252,14 +1252,6 @@ static int convb_forward_impl(const w2l_convb_t* c, void* stream, int N, int H, 
     return W2L_OK;
 }
 
-namespace w2l {
-int bn_stats_from_partials(hipStream_t s, const float* part, int npart, int cout_p, long long rows, int C, int Cvalid,
-                           const float* gamma, const float* beta, float eps, float momentum, float* running_mean, float* running_var,
-                           float* mean, float* rstd, float* scale, float* shift);   // train_bf16.hip
-int bn_bwd_sums_from_partials(hipStream_t s, const float* part, int npart, int cout_p, int C, int Cvalid, float* dgamma,
-                              float* dbeta);                                        // train_bf16.hip
-}
-
 extern "C" {
 
 int w2l_convb_forward(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, void* y, int y_cs,

@@ -59,6 +59,23 @@ __host__ __device__ __forceinline__ unsigned xcd_remap(unsigned id, unsigned) { 
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
+// workgroups for `work` items at `block` per workgroup, between 1 and `cap` (grid-stride kernels)
+static inline int grid_cap(long long work, int block, int cap) {
+    long long g = (work + block - 1) / block;
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+
+// ---- train_rows.hip, used by other translation units
+// the stream's fp64 reduction scratch (one fixed buffer per stream; NULL + error when `bytes` exceeds it): the caller enqueues the
+// kernel that fills it and the kernel that consumes it back to back on that stream
+double* partial_ws(hipStream_t stream, size_t bytes);
+// BatchNorm statistics / the two BatchNorm-backward column sums from a conv epilogue's fp32 per-wave partials [npart][2][cout_p]
+int bn_stats_from_partials(hipStream_t s, const float* part, int npart, int cout_p, long long rows, int C, int Cvalid,
+                           const float* gamma, const float* beta, float eps, float momentum, float* running_mean, float* running_var,
+                           float* mean, float* rstd, float* scale, float* shift);
+int bn_bwd_sums_from_partials(hipStream_t s, const float* part, int npart, int cout_p, int C, int Cvalid, float* dgamma, float* dbeta);
 
 // HBM bytes a launch fetches under the two tile orders of a (phase-major) grid whose 8 XCDs each walk a contiguous range of tiles,
 // x = input bytes, w = weight bytes, tn = cout-tiles, passes = phases: cout-tiles FASTEST - every XCD holds 1/8 of the M-tiles and

@@ -103,7 +103,7 @@ def apply_plan_configs(plan, kind, N, doc=None, strict=False):
 #   "bf16"  the bf16-STORAGE path BASELINE configs[3] / [4] name: activations, pre-BatchNorm conv outputs and their gradients are
 #           NHWC bf16 in HBM, every contraction multiplies bf16 operands on the bf16 matrix cores with fp32 accumulation, master
 #           weights / weight gradients / BatchNorm statistics / losses / Adam stay fp32 (csrc/conv_bf16.hip, wgrad_bf16.hip,
-#           train_bf16.hip);
+#           train_rows.hip);
 #   "bf16c" round 2's contraction-only variant (fp32 tensors, operands rounded inside the fp32-layout kernels), kept for A/B.
 # Inference plans run fp32 by default (the 1e-3 pixel parity path); the generator also has an OPT-IN bf16-storage plan
 # (`Wav2Lip.graph(..., precision="bf16")`, `precision=` on the runners / lipsync, `--precision bf16` on the CLI): bf16 NHWC
