@@ -275,6 +275,41 @@ int w2l_mel_destroy(w2l_mel_t* m);
 int w2l_mel_num_frames(long long nsamples);            /* 1 + nsamples/200 */
 /* wav fp32 [nsamples] (device) -> mel fp32 [80][T] row-major (as audio.melspectrogram returns it) */
 int w2l_melspectrogram(const w2l_mel_t* m, void* stream, const float* wav, long long nsamples, float* mel);
+/* The same spectrogram, incrementally and for MANY streams in one launch (wav2lip_amd/streaming.py): one workgroup per entry of
+ * the column table computes column `col` of stream `stream` from the samples the stream still holds, with the arithmetic of
+ * w2l_melspectrogram (one shared device function), so that a column equals the same column of the whole signal bit for bit once
+ * it is final: on an open stream (total = -1) when col*200 + 400 <= the samples fed so far (column 0: 401 samples), on a closed
+ * one (total = its length, > 400) every column 0 .. total/200.  Sample index j of a column: j < 0 reads -j; on a closed stream
+ * j >= total reads 2*(total-1) - j.  The caller checks that [first, first + held) covers what the listed columns read; the
+ * kernel clamps every index into that range and skips entries whose stream index, sample count or window position is out of
+ * range, so a wrong table gives wrong numbers, never a fault.  Tables live in device memory, 16-byte aligned.
+ *
+ * w2l_mel_stream, 48 bytes, alignment 16:
+ *   offset  0  uint64 samples  device address of the held samples, fp32 [held]
+ *   offset  8  int64  first    absolute index (in the stream's signal) of samples[0]
+ *   offset 16  int64  total    the signal's length once the stream is closed, -1 while it is open
+ *   offset 24  uint64 window   device address of the destination spectrogram window, fp32 [80][cap]
+ *   offset 32  int32  held     number of samples held
+ *   offset 36  int32  cap      columns of the window
+ *   offset 40  int64  col0     absolute column that sits at index 0 of the window
+ * w2l_mel_col, 16 bytes, alignment 16:
+ *   offset  0  int32  stream   row of the stream table
+ *   offset  4  int32  rsv      unused
+ *   offset  8  int64  col      absolute column; written to window[m][col - col0], m = 0..79 */
+typedef struct {
+    uint64_t samples;
+    int64_t first, total;
+    uint64_t window;
+    int32_t held, cap;
+    int64_t col0;
+} w2l_mel_stream;
+typedef struct {
+    int32_t stream, rsv;
+    int64_t col;
+} w2l_mel_col;
+/* 1 <= nstreams <= 65535, 1 <= ncols <= 1048576; non-zero with w2l_last_error() set otherwise, or for a NULL / misaligned table */
+int w2l_mel_stream_cols(const w2l_mel_t* m, void* stream, const w2l_mel_stream* streams, int nstreams, const w2l_mel_col* cols,
+                        int ncols);
 /* mel [80][T] + starts int32[B] (device) -> out fp32 [B][80][16][out_cs] channel 0 (others zero up to c_zero_to) */
 int w2l_mel_gather(void* stream, const float* mel, int T, const int32_t* starts, int B, float* out,
                    int out_cs, int c_zero_to);

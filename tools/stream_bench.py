@@ -1,0 +1,198 @@
+"""Streaming lip-sync in shared batches against the per-stream loop, alternated in one process.
+
+    python tools/stream_bench.py [--streams 1 8 64 256] [--ticks 250 250 80 40] [--paced_ticks 100 100 80 40] [--alternations 5]
+                                 [--paced_alternations 5] [--batch 128]
+
+The defaults are the sweep EXPERIMENTS.md reports: one JSON line per stream count (--ticks / --paced_ticks give one value per
+stream count, or one for all; fewer ticks at large S keep the per-stream loop's pass short).
+
+S synthetic 25 fps streams of 160x160 frames with a fixed 110x110 face box, audio in 40 ms ticks (640 samples: one row per
+stream per tick once the first window is there).  Two loops over the same seeded audio, each on a model of its own:
+
+  shared      `streaming.LipsyncStreams`: per tick `feed` every stream, one `step(flush=True)`; frames arrive through the sink
+  per_stream  what the public API offered before: per stream per tick `audio.melspectrogram_device` on the trailing samples
+              (from three columns before the first window wanted, so that the columns used are exact) and
+              `Wav2LipRunner.run_frames` on that stream's ready rows, frames copied to the host
+
+(a) un-paced: ticks as fast as the loop goes; frames/s, and streams held in real time = frames/s / 25.
+(b) paced: tick k is fed at k * 40 ms (a loop that cannot keep up falls behind and its latency grows); per row the time from the
+    `feed` that completed it to the delivery of its frame; p50 / p99 over all rows.  While it waits for the next tick the shared
+    loop polls `step()` (nothing new to compute: it only delivers what has finished).
+Pass 0 of each loop is its warm-up (plans built) and is not reported.  Then the loops alternate.  Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from wav2lip_amd import audio, inference, models, streaming  # noqa: E402
+from wav2lip_amd import synthetic as synth  # noqa: E402
+
+BOX = (30, 140, 25, 135)
+TICK = 640
+
+
+def model(dev):
+    G = models.Wav2Lip()
+    G.load_state_dict(synth.synthetic_state_dict({k: tuple(v.shape) for k, v in G.state_dict().items()}, seed=0))
+    return G.to(dev).eval()
+
+
+def ready_ticks(ticks):
+    """tick after whose feed row i is complete (the last row, the tail window, with the close at the last tick)"""
+    out, i = [], 0
+    for t in range(ticks):
+        final = streaming.final_columns((t + 1) * TICK, t == ticks - 1)
+        while streaming.row_start(i, 25.) + 16 <= final:
+            out.append(t)
+            i += 1
+    return out + [ticks - 1]
+
+
+class Clock:
+    """feed times per tick and delivery latencies per row"""
+
+    def __init__(self, ticks, pace):
+        self.ready, self.fed, self.lat, self.count, self.pace, self.t0 = ready_ticks(ticks), [0.0] * ticks, [], {}, pace, None
+
+    def wait(self, t, poll=None):
+        if self.t0 is None:
+            self.t0 = time.perf_counter()
+        if self.pace:
+            while time.perf_counter() < self.t0 + t * 0.040:
+                if poll is not None:
+                    poll()
+                time.sleep(0.0005)
+        self.fed[t] = time.perf_counter()
+
+    def sink(self, key, frame):
+        if frame is not None:
+            i = self.count.get(key, 0)
+            self.count[key] = i + 1
+            self.lat.append(time.perf_counter() - self.fed[self.ready[i]])
+
+
+def run_shared(G, wavs, frames, ticks, batch, dev, pace):
+    clock = Clock(ticks, pace)
+    ls = streaming.LipsyncStreams(G, batch_size=batch, sink=clock.sink)
+    for k in range(len(wavs)):
+        ls.open(k, frames, [BOX] * len(frames))
+    t_start = time.perf_counter()
+    for t in range(ticks):
+        clock.wait(t, ls.step)
+        for k, w in enumerate(wavs):
+            ls.feed(k, w[t * TICK:(t + 1) * TICK])
+            if t == ticks - 1:
+                ls.close(k)
+        ls.step(flush=True)
+    ls.drain()
+    torch.cuda.synchronize()
+    return clock, time.perf_counter() - t_start
+
+
+def run_per_stream(G, wavs, frames, ticks, batch, dev, pace):
+    clock = Clock(ticks, pace)
+    runner = inference.Wav2LipRunner(G, batch)
+    frames_dev = torch.from_numpy(np.stack(frames)).to(dev)
+    state = [dict(held=np.empty(0, np.float32), first=0, n=0, row=0) for _ in wavs]
+    t_start = time.perf_counter()
+    for t in range(ticks):
+        clock.wait(t)
+        closed = t == ticks - 1
+        for k, w in enumerate(wavs):
+            s = state[k]
+            s["held"] = np.concatenate([s["held"], w[t * TICK:(t + 1) * TICK]])
+            s["n"] += TICK
+            final = streaming.final_columns(s["n"], closed)
+            starts = []
+            while streaming.row_start(s["row"] + len(starts), 25.) + 16 <= final:
+                starts.append(streaming.row_start(s["row"] + len(starts), 25.))
+            if closed:
+                starts.append(final - 16)
+            if not starts:
+                continue
+            s0 = max(0, (starts[0] - 3) * 200)                       # columns >= s0/200 + 3 of the trailing signal are exact
+            mel = audio.melspectrogram_device(s["held"][s0 - s["first"]:], dev)
+            rel = torch.tensor([c - s0 // 200 for c in starts], dtype=torch.int32, device=dev)
+            idx = [(s["row"] + j) % len(frames) for j in range(len(starts))]
+            out = runner.run_frames(frames_dev, idx, [BOX] * len(starts), mel=mel, starts=rel).cpu().numpy()
+            for f in out:
+                clock.sink(k, f)
+            s["row"] += len(starts)
+            s["held"], s["first"] = s["held"][s0 - s["first"]:], s0
+    torch.cuda.synchronize()
+    return clock, time.perf_counter() - t_start
+
+
+def stats(v, nd=1):
+    return {"samples": [round(x, nd) for x in v], "median": round(float(np.median(v)), nd), "min": round(min(v), nd), "max": round(max(v), nd)}
+
+
+def bench_one(S, ticks, paced_ticks, a, dev):
+    r = np.random.default_rng(a.seed)
+    frames = list(r.integers(0, 256, (16, 160, 160, 3), dtype=np.uint8))
+    wavs = [synth.noise_wav(max(ticks, paced_ticks) * TICK, seed=a.seed * 100003 + k) for k in range(S)]
+    loops = {"shared": (run_shared, model(dev)), "per_stream": (run_per_stream, model(dev))}
+    out = {"streams": S, "ticks": ticks, "batch": a.batch, "alternations": a.alternations,
+           "paced_ticks": paced_ticks, "paced_alternations": a.paced_alternations}
+    res = {k: {"fps": [], "p50_ms": [], "p99_ms": [], "paced_behind_s": []} for k in loops}
+    for name, (fn, G) in loops.items():                   # pass 0: warm-up, plans built
+        clock, t = fn(G, wavs, frames, ticks, a.batch, dev, False)
+        res[name].update(frames=len(clock.lat), first_pass_s=round(t, 2))
+    for _ in range(a.alternations):
+        for name, (fn, G) in loops.items():
+            clock, t = fn(G, wavs, frames, ticks, a.batch, dev, False)
+            res[name]["fps"].append(len(clock.lat) / t)
+    for _ in range(a.paced_alternations):
+        for name, (fn, G) in loops.items():
+            clock, t = fn(G, wavs, frames, paced_ticks, a.batch, dev, True)
+            lat = np.array(clock.lat) * 1e3
+            res[name]["p50_ms"].append(float(np.percentile(lat, 50)))
+            res[name]["p99_ms"].append(float(np.percentile(lat, 99)))
+            res[name]["paced_behind_s"].append(t - paced_ticks * 0.040)        # well above one tick: the loop did not keep up
+    for name in loops:
+        x = res[name]
+        x["plans"] = sorted({k[0] for k in loops[name][1]._graphs})
+        x["fps"] = stats(x["fps"])
+        x["realtime_streams"] = round(x["fps"]["median"] / 25., 1)
+        for key in ("p50_ms", "p99_ms", "paced_behind_s"):
+            x[key] = stats(x[key], 2) if x[key] else None
+    out.update(res)
+    out["shared_over_per_stream_median"] = round(res["shared"]["fps"]["median"] / res["per_stream"]["fps"]["median"], 3)
+    out["ahead_by_more_than_the_spread"] = bool(res["shared"]["fps"]["min"] > res["per_stream"]["fps"]["max"])
+    if a.paced_alternations:                              # the same verdict for the paced latencies: lower is better
+        for key in ("p50_ms", "p99_ms"):
+            out["paced_%s_lower_by_more_than_the_spread" % key[:3]] = bool(res["shared"][key]["max"] < res["per_stream"][key]["min"])
+    return out
+
+
+def per_count(values, n, name):
+    if len(values) not in (1, n):
+        raise SystemExit("--%s takes one value, or one per stream count" % name)
+    return values * n if len(values) == 1 else values
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--streams", type=int, nargs="+", default=[1, 8, 64, 256])
+    ap.add_argument("--ticks", type=int, nargs="+", default=[250, 250, 80, 40])
+    ap.add_argument("--paced_ticks", type=int, nargs="+", default=[100, 100, 80, 40])
+    ap.add_argument("--alternations", type=int, default=5)
+    ap.add_argument("--paced_alternations", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=128)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args(argv)
+    dev = torch.device("cuda", 0)
+    ticks = per_count(a.ticks, len(a.streams), "ticks")
+    paced = per_count(a.paced_ticks, len(a.streams), "paced_ticks")
+    for S, t, pt in zip(a.streams, ticks, paced):
+        print(json.dumps(bench_one(S, t, pt, a, dev)), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -46,6 +46,17 @@ class MelRow(C.Structure):
     _fields_ = [("mel", C.c_uint64), ("T", C.c_int32), ("start", C.c_int32)]
 
 
+class MelStream(C.Structure):
+    """w2l_mel_stream: one stream of w2l_mel_stream_cols, 48 bytes"""
+    _fields_ = [("samples", C.c_uint64), ("first", C.c_int64), ("total", C.c_int64), ("window", C.c_uint64), ("held", C.c_int32),
+                ("cap", C.c_int32), ("col0", C.c_int64)]
+
+
+class MelCol(C.Structure):
+    """w2l_mel_col: one (stream, column) entry of w2l_mel_stream_cols, 16 bytes"""
+    _fields_ = [("stream", C.c_int32), ("rsv", C.c_int32), ("col", C.c_int64)]
+
+
 WGRAD_WINO, WGRAD_DIRECT, WGRAD_SMALL = 0, 1, 2
 
 _vp, _i, _ll, _f = C.c_void_p, C.c_int, C.c_longlong, C.c_float
@@ -94,6 +105,7 @@ SIGNATURES = {
     "w2l_mel_destroy": (_i, [_vp]),
     "w2l_mel_num_frames": (_i, [_ll]),
     "w2l_melspectrogram": (_i, [_vp, _vp, _vp, _ll, _vp]),
+    "w2l_mel_stream_cols": (_i, [_vp, _vp, _vp, _i, _vp, _i]),
     "w2l_mel_gather": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i]),
     "w2l_mel_gather_bf16": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i]),
     "w2l_mel_gather_rows": (_i, [_vp, _vp, _i, _vp, _i, _i]),

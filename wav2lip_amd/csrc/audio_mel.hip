@@ -31,28 +31,34 @@ struct MelKArgs {
     int T;
 };
 
-__device__ __forceinline__ double preemph_sample(const float* wav, long long j) {
+// One spectrogram column, shared by the whole-waveform kernel and the many-stream kernel: `src(j)` is sample j of the signal
+// (j already reflected into it) as a double; everything from the pre-emphasis on is this one body, so the two kernels agree bit
+// for bit.  out[m * out_stride] receives mel bin m of column t.
+template <typename Src>
+__device__ __forceinline__ double preemph_sample(const Src& src, long long j) {
     // scipy lfilter (direct form II transposed), b = [1, -k]: y[n] = x[n] + (-k * x[n-1]), products and sums
     // rounded separately in f64 (no fused multiply-add)
-    const double x0 = (double)wav[j];
+    const double x0 = src(j);
     if (j == 0) return x0;
-    return __dadd_rn(x0, __dmul_rn(-kPreemph, (double)wav[j - 1]));
+    return __dadd_rn(x0, __dmul_rn(-kPreemph, src(j - 1)));
 }
 
-__global__ __launch_bounds__(256) void mel_frame_kernel(const MelKArgs a) {
+template <typename Src>
+__device__ __forceinline__ void mel_column(const Src& src, long long t, long long nsamples, const float* __restrict__ basis,
+                                           const double* __restrict__ window, const double2* __restrict__ twiddle,
+                                           float* __restrict__ out, long long out_stride) {
     __shared__ double s_frame[kNfft];
     __shared__ double2 s_tw[kNfft];
     __shared__ float s_mag[kBins + 3];
-    const int t = blockIdx.x;
     const int tid = threadIdx.x;
     const long long pad = kNfft / 2;
 
     for (int n = tid; n < kNfft; n += 256) {
-        long long j = (long long)t * kHop + n - pad;
+        long long j = t * kHop + n - pad;
         if (j < 0) j = -j;                                   // np.pad(mode='reflect'): no edge repeat
-        if (j >= a.nsamples) j = 2 * (a.nsamples - 1) - j;
-        s_frame[n] = __dmul_rn(a.window[n], preemph_sample(a.wav, j));
-        s_tw[n] = a.twiddle[n];
+        if (nsamples >= 0 && j >= nsamples) j = 2 * (nsamples - 1) - j;   // nsamples < 0: the end is not known yet (open stream)
+        s_frame[n] = __dmul_rn(window[n], preemph_sample(src, j));
+        s_tw[n] = twiddle[n];
     }
     __syncthreads();
 
@@ -73,7 +79,7 @@ __global__ __launch_bounds__(256) void mel_frame_kernel(const MelKArgs a) {
     __syncthreads();
 
     if (tid < kMels) {
-        const float* b = a.basis + tid * kBins;
+        const float* b = basis + tid * kBins;
         float acc = 0.f;
         for (int k = 0; k < kBins; ++k) acc = fmaf(b[k], s_mag[k], acc);
         // _amp_to_db: min_level = exp(-100/20*ln 10) = 1e-5 ; 20*log10(max(min_level, x)) ; then - ref_level_db (20)
@@ -82,8 +88,65 @@ __global__ __launch_bounds__(256) void mel_frame_kernel(const MelKArgs a) {
         // _normalize, symmetric + clipping: clip(2*4*((S+100)/100) - 4, -4, 4)
         float v = 8.0f * ((S + 100.0f) / 100.0f) - 4.0f;
         v = fminf(fmaxf(v, -4.0f), 4.0f);
-        a.mel[(long long)tid * a.T + t] = v;
+        out[(long long)tid * out_stride] = v;
     }
+}
+
+struct WavSrc {
+    const float* wav;
+    __device__ __forceinline__ double operator()(long long j) const { return (double)wav[j]; }
+};
+
+__global__ __launch_bounds__(256) void mel_frame_kernel(const MelKArgs a) {
+    const int t = blockIdx.x;
+    mel_column(WavSrc{a.wav}, (long long)t, a.nsamples, a.basis, a.window, a.twiddle, a.mel + t, (long long)a.T);
+}
+
+// The newly final columns of MANY streams in one launch (w2l_mel_stream / w2l_mel_col, include/w2l_hip.h): one workgroup per
+// (stream, column) entry.  A stream holds only the samples [first, first + held) of its signal; the host checks that they cover
+// what the listed columns read, and the kernel clamps every index into the held range, so that a wrong table gives wrong
+// numbers and not a fault.  Entries that name no stream, hold no samples or fall outside the window write nothing.
+struct MelStream {
+    unsigned long long samples;
+    long long first, total;
+    unsigned long long window;
+    int held, cap;
+    long long col0;
+};
+struct MelCol {
+    int stream, rsv;
+    long long col;
+};
+static_assert(sizeof(MelStream) == 48 && sizeof(MelCol) == 16, "w2l_mel_stream is 48 bytes, w2l_mel_col 16");
+
+struct StreamSrc {
+    const float* samples;
+    long long first;
+    int held;
+    __device__ __forceinline__ double operator()(long long j) const {
+        long long i = j - first;
+        i = i < 0 ? 0 : (i >= held ? held - 1 : i);
+        return (double)samples[i];
+    }
+};
+
+struct MelStreamKArgs {
+    const MelStream* streams;
+    int nstreams;
+    const MelCol* cols;
+    const float* basis;
+    const double* window;
+    const double2* twiddle;
+};
+
+__global__ __launch_bounds__(256) void mel_stream_cols_kernel(const MelStreamKArgs a) {
+    const MelCol c = a.cols[blockIdx.x];
+    if (c.stream < 0 || c.stream >= a.nstreams) return;      // uniform over the workgroup: no barrier is skipped by a part of it
+    const MelStream s = a.streams[c.stream];
+    const long long rel = c.col - s.col0;
+    if (s.held < 1 || !s.samples || !s.window || c.col < 0 || rel < 0 || rel >= s.cap) return;
+    mel_column(StreamSrc{reinterpret_cast<const float*>(s.samples), s.first, s.held}, c.col, s.total, a.basis, a.window,
+               a.twiddle, reinterpret_cast<float*>(s.window) + rel, (long long)s.cap);
 }
 
 // T = float, or __bf16 (the bf16-storage inference path: each value rounded once, RNE)
@@ -228,6 +291,22 @@ int w2l_melspectrogram(const w2l_mel_t* m, void* stream, const float* wav, long 
     a.wav = wav; a.nsamples = nsamples; a.basis = m->basis; a.window = m->window; a.twiddle = m->twiddle;
     a.mel = mel; a.T = w2l_mel_num_frames(nsamples);
     hipLaunchKernelGGL(mel_frame_kernel, dim3(a.T), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_mel_stream_cols(const w2l_mel_t* m, void* stream, const w2l_mel_stream* streams, int nstreams, const w2l_mel_col* cols,
+                        int ncols) {
+    W2L_REQUIRE(m && streams && cols, "NULL argument");
+    W2L_REQUIRE(nstreams >= 1 && nstreams <= 65535 && ncols >= 1 && ncols <= (1 << 20),
+                "mel_stream_cols: 1 <= nstreams <= 65535 and 1 <= ncols <= 1048576 (got %d, %d)", nstreams, ncols);
+    W2L_REQUIRE(((reinterpret_cast<uintptr_t>(streams) | reinterpret_cast<uintptr_t>(cols)) & 15) == 0,
+                "mel_stream_cols: 16-byte aligned stream and column tables");
+    MelStreamKArgs a;
+    a.streams = reinterpret_cast<const MelStream*>(streams); a.nstreams = nstreams;
+    a.cols = reinterpret_cast<const MelCol*>(cols);
+    a.basis = m->basis; a.window = m->window; a.twiddle = m->twiddle;
+    hipLaunchKernelGGL(mel_stream_cols_kernel, dim3((unsigned)ncols), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

@@ -80,7 +80,11 @@ def _align(n):
 class BatchRunner:
     """the device side of the packer: `submit(rows)` stages, launches and starts the copy back of one packed batch on the
     next lane and returns a ticket, `result(ticket)` waits for it and returns one uint8 [H,W,3] array per row.
-    rows: [(job, frame_index, (y1, y2, x1, x2), mel_start)]"""
+    rows: [(job, frame_index, (y1, y2, x1, x2), mel_start)]; `job` is anything with `.frames`, and with `.mel` where
+    `mel_start` is a column of it.  A row may name its spectrogram itself instead: `mel_start` = (device tensor [80,T], T,
+    start relative to that tensor) - a stream's spectrogram window (wav2lip_amd/streaming.py).
+    `submit(rows, pad_to=m)` launches m >= len(rows) rows: the last row repeated with a scratch destination, so that a ragged
+    batch runs a plan of a committed size; the padded rows' outputs are dropped."""
 
     def __init__(self, model, batch_size, depth, precision):
         import torch
@@ -89,9 +93,10 @@ class BatchRunner:
         self.runner = PipelinedRunner(model, batch_size, depth=depth, **_precision_kw(precision))
         self.device = self.runner.lanes[0].device
 
-    def submit(self, rows):
+    def submit(self, rows, pad_to=None):
         torch = self.torch
-        n = len(rows)
+        real = len(rows)
+        n = max(real, pad_to or 0)
         # ---- layout of the staging buffer: [frame-row table][mel-row table][deduplicated frames]; outputs in a buffer of their own
         off = _align(n * FRAME_ROW.itemsize)
         mel_off = off
@@ -109,7 +114,10 @@ class BatchRunner:
             out_bytes = _align(out_bytes + np.asarray(job.frames[fi]).nbytes)
         host = torch.empty(off, dtype=torch.uint8, pin_memory=True)
         dev = torch.empty(off, dtype=torch.uint8, device=self.device)
-        dev_out = torch.empty(out_bytes, dtype=torch.uint8, device=self.device)
+        scratch = 0
+        if n > real:                             # one scratch frame behind the outputs for the padded rows
+            scratch = _align(np.asarray(rows[-1][0].frames[rows[-1][1]]).nbytes)
+        dev_out = torch.empty(out_bytes + scratch, dtype=torch.uint8, device=self.device)
         host_out = torch.empty(out_bytes, dtype=torch.uint8, pin_memory=True)
         stage = host.numpy()
         for o, f in frames:
@@ -120,12 +128,18 @@ class BatchRunner:
         for r, (job, fi, (y1, y2, x1, x2), start) in enumerate(rows):
             H, W = np.asarray(job.frames[fi]).shape[:2]
             ft[r] = (dev.data_ptr() + src_off[(id(job), fi)], dev_out.data_ptr() + out_off[r], H, W, y1, y2, x1, x2, (0, 0))
-            mt[r] = (job.mel.data_ptr(), job.mel.shape[1], start)
-            mels[id(job)] = job.mel
+            mel, T, start = start if isinstance(start, tuple) else (job.mel, job.mel.shape[1], start)
+            mt[r] = (mel.data_ptr(), T, start)
+            mels[id(mel)] = mel
             shapes.append((H, W))
             max_px = max(max_px, H * W)
+        # padding: the last row again, composed into the scratch frame.  All padded rows write that one frame at the same time,
+        # and all write the same bytes (the same row), so the overlap is harmless
+        for r in range(real, n):
+            ft[r], mt[r] = ft[real - 1], mt[real - 1]
+            ft["dst"][r] = dev_out.data_ptr() + out_bytes
         ticket = self.runner.submit(None, rows=(n, dev[:n * FRAME_ROW.itemsize], dev[mel_off:mel_off + n * MEL_ROW.itemsize], max_px),
-                                    upload=(dev, host), download=(host_out, dev_out), keep=tuple(mels.values()))
+                                    upload=(dev, host), download=(host_out, dev_out[:out_bytes] if scratch else dev_out), keep=tuple(mels.values()))
         return ticket, host_out, out_off, shapes
 
     def result(self, item):
@@ -133,6 +147,11 @@ class BatchRunner:
         done.synchronize()                       # the copy back is part of the lane's work: wait on the host, then read
         buf = host_out.numpy()
         return [buf[o:o + h * w * 3].reshape(h, w, 3).copy() for o, (h, w) in zip(out_off, shapes)]
+
+    @staticmethod
+    def ready(item):
+        """True when `result(item)` would not wait"""
+        return item[0][1].query()
 
 
 def _checked_rows(job):
