@@ -51,6 +51,9 @@
  *   w2l_bce_bwd           backward of F.binary_cross_entropy (models/wav2lip.py:171, hq_wav2lip_train.py:249,253)
  *   w2l_adam_*            optim.Adam (wav2lip_train.py:359, hq_wav2lip_train.py:418-421)
  *   w2l_shifted_pdist     calc_pdist of the LSE-D / LSE-C scorer (evaluation/scores_LSE/SyncNetInstance_calc_scores.py:19-31)
+ *   w2l_sync_window_rows  the scorer's window building (SyncNetInstance_calc_scores.py:105-127), one clip per row
+ *   w2l_lse_score_segments  its scores (SyncNetInstance_calc_scores.py:19-31,129-137) for every clip of a directory run
+ *                         (evaluation/scores_LSE/calculate_scores_LRS.py:28-50) in one launch
  */
 #ifndef W2L_HIP_H
 #define W2L_HIP_H
@@ -563,6 +566,49 @@ int w2l_bce_bwd(void* stream, int N, const float* p, const float* y, const float
  * out [T][2*vshift+1]: out[i][j] = || f1[i] - pad(f2)[i+j] + 1e-6 ||_2 with f2 zero-padded by vshift rows on both sides
  * (calc_pdist, evaluation/scores_LSE/SyncNetInstance_calc_scores.py:19-31); f1, f2 [T][C] fp32. */
 int w2l_shifted_pdist(void* stream, int T, int C, int vshift, const float* f1, const float* f2, float* out);
+
+/* ---------------------------------------------------------------- evaluation: scoring a directory of clips
+ * (evaluation/scores_LSE/calculate_scores_LRS.py:28-50 calls, per video, SyncNetInstance_calc_scores.py:105-137: windows of 5
+ * frames and of the matching audio features through the two encoders, calc_pdist (:19-31), mean over the windows, min, median.)
+ * Windows are independent given eval-mode weights, so windows of different clips share a SyncNet batch: a row names its own
+ * clip.  Tables live in device memory.
+ *
+ * w2l_sync_row, 32 bytes, alignment 16: one window (wav2lip_train.py:80,192-195 layout)
+ *   byte  0  uint64 frames  device address of the window's first frame: five consecutive face crops, u8 [5][S][S][3]
+ *   byte  8  uint64 mel     device address of the clip's spectrogram, fp32 [80][T]
+ *   byte 16  int32  T       its number of columns
+ *   byte 20  int32  start   the window is columns [start, start+16) (columns outside [0,T) read as 0)
+ *   byte 24  int32  pad[2]  unused (keeps consecutive rows 16-byte aligned)
+ * w2l_lse_segment, 8 bytes, alignment 8: one clip's rows of the two embedding arrays
+ *   byte  0  int32  row0    its first row
+ *   byte  4  int32  n       its number of rows */
+typedef struct {
+    uint64_t frames, mel;
+    int32_t T, start;
+    int32_t pad[2];
+} w2l_sync_row;
+typedef struct {
+    int32_t row0, n;
+} w2l_lse_segment;
+
+/* Both inputs of a SyncNet plan for B windows, written whole (pad channels included: the result does not depend on what the
+ * buffers held):
+ *   face_in fp32 [B][S/2][S][face_cs]:  [b][y][x][3*t+c] = float(frame[t][S/2+y][x][c]) / 255.f (correctly rounded: bit-equal to
+ *                                       numpy u8.astype(float32) / float32(255)), channels 15 .. face_cs-1 = 0
+ *   mel_in  fp32 [B][80][16][mel_cs]:   [b][r][k][0] = mel[r*T + start + k], channels 1 .. mel_cs-1 = 0
+ * face_cs >= 16 and mel_cs >= 4, both multiples of 4; outputs 16-byte aligned; 1 <= B <= 65535. */
+int w2l_sync_window_rows(void* stream, int B, const w2l_sync_row* rows, int S, float* face_in, int face_cs, float* mel_in,
+                         int mel_cs);
+/* SyncNetInstance_calc_scores.py:129-137 for n_seg clips in one launch.  face_emb, audio_emb fp32 [rows][C]; segment s owns rows
+ * [row0, row0+n) of both.  With win = 2*vshift+1 and dist(i, j) the entry of w2l_shifted_pdist run on the segment alone (zero
+ * padding at the segment's own ends; no row of another segment is read; the same arithmetic, bit for bit):
+ *   mdist  fp32 [n_seg][win]:  mdist[s][j] = mean over i of dist(i, j), summed in fp64 in row order, rounded to fp32 once
+ *   scores fp32 [n_seg][4]:    (min_j mdist, median_j mdist - min, vshift - argmin, n); the argmin is the lowest j among equal
+ *                              minima, the median the element of rank (win-1)/2 (torch.median's lower median)
+ * n_seg >= 1, C >= 1, 0 <= vshift <= 127 (win <= 255: one workgroup per segment).  A segment with n < 1 reads nothing and gets
+ * NaN scores with n = 0. */
+int w2l_lse_score_segments(void* stream, int n_seg, const w2l_lse_segment* segs, int C, int vshift, const float* face_emb,
+                           const float* audio_emb, float* mdist, float* scores);
 
 /* ---------------------------------------------------------------- training: fused multi-tensor Adam */
 typedef struct w2l_adam_tensor {

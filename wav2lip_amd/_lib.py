@@ -46,6 +46,16 @@ class MelRow(C.Structure):
     _fields_ = [("mel", C.c_uint64), ("T", C.c_int32), ("start", C.c_int32)]
 
 
+class SyncRow(C.Structure):
+    """w2l_sync_row: one scorer window of w2l_sync_window_rows, 32 bytes"""
+    _fields_ = [("frames", C.c_uint64), ("mel", C.c_uint64), ("T", C.c_int32), ("start", C.c_int32), ("pad", C.c_int32 * 2)]
+
+
+class LseSegment(C.Structure):
+    """w2l_lse_segment: one clip's rows of w2l_lse_score_segments, 8 bytes"""
+    _fields_ = [("row0", C.c_int32), ("n", C.c_int32)]
+
+
 class MelStream(C.Structure):
     """w2l_mel_stream: one stream of w2l_mel_stream_cols, 48 bytes"""
     _fields_ = [("samples", C.c_uint64), ("first", C.c_int64), ("total", C.c_int64), ("window", C.c_uint64), ("held", C.c_int32),
@@ -161,6 +171,8 @@ SIGNATURES = {
     "w2l_l2norm_bwd": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i]),
     "w2l_bce_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "w2l_shifted_pdist": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "w2l_sync_window_rows": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i]),
+    "w2l_lse_score_segments": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "w2l_adam_create": (_i, [_i, C.POINTER(_ll), C.POINTER(_vp)]),
     "w2l_adam_destroy": (_i, [_vp]),
     "w2l_adam_step": (_i, [_vp, _vp, C.POINTER(AdamTensor), _f, _f, _f, _f, _f, _i]),

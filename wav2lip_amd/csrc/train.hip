@@ -273,15 +273,8 @@ __global__ void shifted_pdist_kernel(int T, int C, int vshift, const float* __re
     const int i = item / win, j = item - i * win;
     const int r = i + j - vshift;                 // row of the unpadded f2
     const bool inside = r >= 0 && r < T;
-    const float* a = f1 + (long long)i * C;
-    const float* b = f2 + (long long)(inside ? r : 0) * C;
-    float s = 0.f;
-    for (int c = lane; c < C; c += 64) {
-        const float d = a[c] - (inside ? b[c] : 0.f) + 1e-6f;
-        s += d * d;
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) out[item] = sqrtf(s);
+    const float d = shifted_pdist_wave(f1 + (long long)i * C, f2 + (long long)(inside ? r : 0) * C, inside, C, lane);
+    if (lane == 0) out[item] = d;
 }
 }  // namespace w2l
 

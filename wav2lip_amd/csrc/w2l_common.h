@@ -43,6 +43,21 @@ __device__ __forceinline__ float act_leaky(float v, float neg) {
     return v < 0.f ? (nv == nv ? nv : 0.f) : v;
 }
 
+// One entry of calc_pdist (evaluation/scores_LSE/SyncNetInstance_calc_scores.py:19-31), computed by one wave: || a - b + 1e-6 ||_2
+// over C channels, `inside` false standing for a zero-padding row of b (b is then not read).  Lane l sums channels l, l + 64, ...,
+// a xor butterfly folds the 64 partials, every lane returns the root.  shifted_pdist_kernel (train.hip) and
+// lse_score_segments_kernel (sync_score.hip) both call it, so that their distances agree bit for bit.
+__device__ __forceinline__ float shifted_pdist_wave(const float* __restrict__ a, const float* __restrict__ b, bool inside, int C,
+                                                    int lane) {
+    float s = 0.f;
+    for (int c = lane; c < C; c += 64) {
+        const float d = a[c] - (inside ? b[c] : 0.f) + 1e-6f;
+        s += d * d;
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    return sqrtf(s);
+}
+
 // Workgroup ids are dealt round-robin to the 8 XCDs (id % 8), each with its own L2.  This maps the hardware id to a
 // logical id such that every XCD walks one CONTIGUOUS range of logical ids: neighbouring tiles (which share input halos
 // and A/B operand tiles) then meet in the same L2 instead of being fetched from HBM once per XCD.

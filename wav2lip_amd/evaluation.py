@@ -12,7 +12,12 @@ that arithmetic on the embeddings of the in-tree expert `SyncNet_color` (the net
 
 With identical weights on both sides, equal scores for the engine's frames and the CPU path's frames is the stand-in for
 "LSE-D / LSE-C parity"; the absolute values are not comparable to the paper's (different scorer network).
+
+`lse_like` scores one clip per call.  `lse_many` scores a whole filelist (evaluation/scores_LSE/calculate_scores_LRS.py:28-50): the
+windows of successive clips are rows of SyncNet batches of one size, and a group of clips is scored in one launch.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -20,6 +25,16 @@ from ._lib import check, current_stream, load, ptr
 
 syncnet_T = 5
 mel_step = 16
+img_size = 96
+
+# numpy mirrors of w2l_sync_row (32 bytes) and w2l_lse_segment (8 bytes); the ctypes mirrors are _lib.SyncRow / _lib.LseSegment
+SYNC_ROW = np.dtype([("frames", "<u8"), ("mel", "<u8"), ("T", "<i4"), ("start", "<i4"), ("pad", "<i4", (2,))])
+LSE_SEGMENT = np.dtype([("row0", "<i4"), ("n", "<i4")])
+GROUP_BATCHES = 16   # lse_many closes a group of clips once it holds this many full batches of windows
+
+ScoreJob = collections.namedtuple("ScoreJob", "key faces mel")
+ScoreJob.__doc__ = """one clip to score: `faces` uint8 [T,96,96,3] face crops (a device tensor or a host array), `mel` the device fp32
+[80,Tm] spectrogram (audio.melspectrogram_device)"""
 
 
 def sync_windows(frames_u8, mel, fps=25.):
@@ -71,3 +86,149 @@ def lse_like(syncnet, frames_u8, mel, fps=25., vshift=15, batch_size=64):
     finally:
         syncnet.train(was_training)
     return dict(offset=offset, lse_c=conf, lse_d=minval, n=int(faces.shape[0]), mdist=mdist.cpu().numpy())
+
+
+# ---------------------------------------------------------------- many clips, shared SyncNet batches
+def sync_rows(T, Tm, fps=25.):
+    """the (first frame v, first mel column) of every window `sync_windows` makes of T frames and Tm mel columns: the same
+    expression and the same stop rule"""
+    rows = []
+    for v in range(0, T - syncnet_T + 1):
+        s = int(80. * (v / float(fps)))
+        if s + mel_step > Tm:
+            break
+        rows.append((v, s))
+    return rows
+
+
+def _align(n):
+    return (n + 15) // 16 * 16
+
+
+def _score_segments(n_seg, segs, vshift, face_emb, audio_emb, out):
+    """w2l_lse_score_segments into `out`, fp32 [n_seg * (4 + win)]: the [n_seg][4] scores, then the [n_seg][win] mean distances"""
+    check(load().w2l_lse_score_segments(current_stream(), n_seg, ptr(segs), face_emb.shape[1], vshift, ptr(face_emb),
+                                        ptr(audio_emb), out.data_ptr() + 16 * n_seg, ptr(out)), "lse_score_segments")
+
+
+def _score_group(syncnet, clips, vshift, batch_size):
+    """One group on the device.  clips: [(faces, mel, rows)], every `rows` (sync_rows) non-empty.  The windows of the group are
+    the rows of one embedding arena pair, clip after clip; batches of exactly `batch_size` rows walk the arena, the last one padded
+    with copies of its last row whose embeddings fall into the scratch rows behind the arena.  Returns numpy [clips, 4 + win]:
+    (lse_d, lse_c, offset, n) and the mean distances of every clip."""
+    dev = clips[0][1].device
+    win = 2 * vshift + 1
+    W = sum(len(rows) for _, _, rows in clips)
+    padded = (W + batch_size - 1) // batch_size * batch_size
+    # ---- one staging buffer: [window table, `padded` rows][segment table][host faces of the group]
+    seg_off = _align(padded * SYNC_ROW.itemsize)
+    off = _align(seg_off + len(clips) * LSE_SEGMENT.itemsize)
+    face_off = []
+    for faces, _, _ in clips:
+        if isinstance(faces, torch.Tensor):
+            face_off.append(None)
+        else:
+            face_off.append(off)
+            off = _align(off + faces.nbytes)
+    pinned = dev.type == "cuda"
+    host = torch.empty(off, dtype=torch.uint8, pin_memory=pinned)
+    stage_dev = torch.empty(off, dtype=torch.uint8, device=dev)
+    stage = host.numpy()
+    table = stage[:padded * SYNC_ROW.itemsize].view(SYNC_ROW)
+    segs = stage[seg_off:seg_off + len(clips) * LSE_SEGMENT.itemsize].view(LSE_SEGMENT)
+    table["pad"] = 0
+    frame_bytes = img_size * img_size * 3
+    r = 0
+    for c, (faces, mel, rows) in enumerate(clips):
+        if face_off[c] is None:
+            base = faces.data_ptr()
+        else:
+            stage[face_off[c]:face_off[c] + faces.nbytes] = faces.reshape(-1)
+            base = stage_dev.data_ptr() + face_off[c]
+        vs = np.asarray(rows, dtype=np.int64)
+        t = table[r:r + len(rows)]
+        t["frames"] = base + vs[:, 0] * frame_bytes
+        t["mel"], t["T"], t["start"] = mel.data_ptr(), mel.shape[1], vs[:, 1]
+        segs[c] = (r, len(rows))
+        r += len(rows)
+    table[W:] = table[W - 1]
+    stage_dev.copy_(host, non_blocking=pinned)
+    audio_emb = torch.empty((padded, 512), dtype=torch.float32, device=dev)     # rows [W, padded): the scratch tail
+    face_emb = torch.empty((padded, 512), dtype=torch.float32, device=dev)
+    for lo in range(0, padded, batch_size):
+        syncnet.embed_rows(stage_dev[lo * SYNC_ROW.itemsize:(lo + batch_size) * SYNC_ROW.itemsize], batch_size, audio_emb, face_emb, lo)
+    out = torch.empty(len(clips) * (4 + win), dtype=torch.float32, device=dev)
+    _score_segments(len(clips), stage_dev[seg_off:seg_off + len(clips) * LSE_SEGMENT.itemsize], vshift, face_emb, audio_emb, out)
+    res = out.cpu().numpy()                      # the group's one copy back; it also ends the stream's use of the staging buffers
+    return np.concatenate([res[:4 * len(clips)].reshape(len(clips), 4), res[4 * len(clips):].reshape(len(clips), win)], axis=1)
+
+
+def _checked_job(job):
+    """(faces, mel) of a ScoreJob: faces a contiguous uint8 [T,96,96,3] device tensor or host array; a ValueError names the job"""
+    faces, mel = job.faces, job.mel
+    try:
+        if not isinstance(mel, torch.Tensor) or mel.dtype != torch.float32 or mel.dim() != 2 or mel.shape[0] != 80:
+            raise ValueError("mel must be a float32 [80,Tm] device tensor")
+        if isinstance(faces, torch.Tensor):
+            if faces.device != mel.device:
+                raise ValueError("faces are on %s, mel on %s" % (faces.device, mel.device))
+            faces = faces.contiguous()
+        else:
+            faces = np.ascontiguousarray(faces)
+        if faces.dtype not in (torch.uint8, np.uint8) or faces.ndim != 4 or tuple(faces.shape[1:]) != (img_size, img_size, 3):
+            raise ValueError("faces must be uint8 [T,%d,%d,3], got %s %s" % (img_size, img_size, faces.dtype, tuple(faces.shape)))
+    except ValueError as e:
+        raise ValueError("job %r: %s" % (job.key, e)) from None
+    return faces, mel.contiguous()
+
+
+@torch.no_grad()
+def lse_many(syncnet, jobs, fps=25., vshift=15, batch_size=128, sink=None):
+    """`lse_like` for every `ScoreJob` of the iterable `jobs` (consumed lazily), the windows of successive clips packed into
+    SyncNet batches of exactly `batch_size` (evaluation/scores_LSE/calculate_scores_LRS.py:41-47 scores one video per call).
+
+    Jobs are taken until a group holds at least GROUP_BATCHES * batch_size windows or the iterator ends; the group's windows are
+    embedded, w2l_lse_score_segments scores all its clips in one launch, one copy brings the scores back, and the group is
+    released: the memory alive is one group plus the job being read.  Results arrive in job order as
+    dict(key, offset, lse_c, lse_d, n, mdist) - at `sink(result)`, or in the returned list.  A clip without one full window
+    gives n = 0 and None for the rest, and takes part in no launch.  The model runs in eval mode and is put back afterwards."""
+    if batch_size < 1:
+        raise ValueError("batch_size must be at least 1")
+    if not 0 <= vshift <= 127:
+        raise ValueError("vshift must be in 0..127")
+    collected = None
+    if sink is None:
+        collected = []
+        sink = collected.append
+    group, windows = [], 0          # (key, faces, mel, rows) of the jobs read since the last group ran
+
+    def flush():
+        nonlocal group, windows
+        clips = [(faces, mel, rows) for _, faces, mel, rows in group if rows]
+        scored = iter(_score_group(syncnet, clips, vshift, batch_size)) if clips else None
+        keys = [(key, bool(rows)) for key, _, _, rows in group]
+        group, windows = [], 0      # released before the results go out
+        del clips
+        for key, has_rows in keys:
+            if not has_rows:
+                sink(dict(key=key, offset=None, lse_c=None, lse_d=None, n=0, mdist=None))
+                continue
+            row = next(scored)
+            sink(dict(key=key, offset=int(row[2]), lse_c=float(row[1]), lse_d=float(row[0]), n=int(row[3]), mdist=row[4:].copy()))
+
+    was_training = syncnet.training
+    syncnet.eval()
+    try:
+        for job in jobs:
+            faces, mel = _checked_job(job)
+            rows = sync_rows(faces.shape[0], mel.shape[1], fps)
+            group.append((job.key, faces if rows else None, mel if rows else None, rows))
+            del job, faces, mel
+            windows += len(rows)
+            if windows >= GROUP_BATCHES * batch_size:
+                flush()
+        if group:
+            flush()
+    finally:
+        syncnet.train(was_training)
+    return collected

@@ -57,14 +57,7 @@ class SyncNet_color(nn.Module):
             a, v = autograd.run_graph(self._train_graphs, self, (N, H, W, str(face.device)), (N, H, W, face.device),
                                       (audio, face))
             return autograd.L2NormRows.apply(a.reshape(N, -1)), autograd.L2NormRows.apply(v.reshape(N, -1))
-        ver = engine.param_version(self)
-        key = (N, H, W, str(face.device))
-        g = self._graphs.get(key)
-        if g is None or g[0] != ver:
-            self._graphs.clear()
-            g = (ver, _SyncGraph(self, N, H, W, face.device))
-            self._graphs[key] = g
-        g = g[1]
+        g = self._eval_graph(N, H, W, face.device)
         s = current_stream()
         check(g.lib.w2l_nchw_to_nhwc(s, N, C_, H, W, ptr(face), ptr(g.face_in), 16, 16), "nchw_to_nhwc")
         check(g.lib.w2l_nchw_to_nhwc(s, N, 1, 80, 16, ptr(audio), ptr(g.mel_in), 4, 4), "nchw_to_nhwc")
@@ -74,3 +67,38 @@ class SyncNet_color(nn.Module):
         check(g.lib.w2l_l2norm_rows(s, N, 512, g.audio_out.ptr, g.audio_out.cs, ptr(a)), "l2norm_rows")
         check(g.lib.w2l_l2norm_rows(s, N, 512, g.face_out.ptr, g.face_out.cs, ptr(v)), "l2norm_rows")
         return a, v
+
+    def _eval_graph(self, N, H, W, device):
+        """the one cached inference graph: another (N, H, W), device or weight version replaces it"""
+        ver = engine.param_version(self)
+        key = (N, H, W, str(device))
+        g = self._graphs.get(key)
+        if g is None or g[0] != ver:
+            self._graphs.clear()
+            g = (ver, _SyncGraph(self, N, H, W, device))
+            self._graphs[key] = g
+        return g[1]
+
+    def embed_rows(self, rows, B, audio_out, face_out, offset=0):
+        """Eval mode only: the embeddings of the `B` windows of a device row table (w2l_sync_row, include/w2l_hip.h; 96x96 face
+        crops) into audio_out[offset:offset+B] and face_out[offset:offset+B], two contiguous fp32 [rows, 512] device tensors.
+        w2l_sync_window_rows writes the graph's two inputs from the table, the plan runs, w2l_l2norm_rows writes the outputs:
+        no tensor is made on the way.  The graph cache is `forward`'s: a caller that keeps to one `B` builds one plan."""
+        if self.training:
+            raise RuntimeError("SyncNet_color.embed_rows is an inference path: call .eval() first")
+        engine.require_cuda(face_out, "face_out")
+        for name, t in (("audio_out", audio_out), ("face_out", face_out)):
+            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 512 or not t.is_contiguous() or t.device != face_out.device:
+                raise ValueError("%s must be a contiguous fp32 [rows, 512] tensor on %s" % (name, face_out.device))
+            if not 0 <= offset <= t.shape[0] - B:
+                raise ValueError("rows [%d, %d) are outside the %d rows of %s" % (offset, offset + B, t.shape[0], name))
+        if rows.device != face_out.device or rows.dtype != torch.uint8 or not rows.is_contiguous() or rows.numel() < 32 * B or B < 1:
+            raise ValueError("rows must be a contiguous uint8 device tensor holding B >= 1 w2l_sync_row entries")
+        with engine.on_device_of(face_out, self):
+            g = self._eval_graph(B, 48, 96, face_out.device)
+            s = current_stream()
+            check(g.lib.w2l_sync_window_rows(s, B, ptr(rows), 96, ptr(g.face_in), 16, ptr(g.mel_in), 4), "sync_window_rows")
+            g.plan.run()
+            check(g.lib.w2l_l2norm_rows(s, B, 512, g.audio_out.ptr, g.audio_out.cs, audio_out.data_ptr() + 2048 * offset),
+                  "l2norm_rows")
+            check(g.lib.w2l_l2norm_rows(s, B, 512, g.face_out.ptr, g.face_out.cs, face_out.data_ptr() + 2048 * offset), "l2norm_rows")
