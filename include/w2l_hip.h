@@ -695,6 +695,12 @@ int w2l_conv_exclude_families(int mask);
  * weights once); 2 = groups of order_r M-tiles phase by phase (a stride-2 transposed layer's four phases re-read their input out of an
  * XCD's L2 instead of HBM).  The launcher chooses per shape. */
 int w2l_igemm_block_order(int order, int order_r, int tiles_m, int tiles_n, int nphase, int* out);
+/* How configuration 11 (Winograd F(4x4,3x3)) packs its 32 tile slots for N images of H x W (test aid, host code, runs without a
+ * GPU; a function of the shape alone).  out[8] = {form, blocks, r, c, ni, pitch, pad, cells}: form 0 = rectangles of r x c tiles in
+ * each of ni images (pad = the image stride in plane cells), form 1 = runs of r consecutive (image, tile row) units at the full
+ * tile width c, crossing image boundaries (pad = extra plane cells in front of every segment after the first); blocks = work items
+ * per 64-cout tile, pitch = plane cells per staged raw row, cells = cells per raw plane. */
+int w2l_wino4_block_plan(int N, int H, int W, int* out);
 /* time each recorded launch with HIP events on `stream` (reps runs, averaged): ms_out[w2l_plan_size] */
 int w2l_plan_profile(const w2l_plan_t* p, void* stream, int reps, float* ms_out);
 

@@ -23,6 +23,9 @@
 // pixels per image for bh x bw tiles) is loaded once into LDS (<= 3 float4 per thread) in (channel quad, x & 3) planes; waves
 // 0-5 each compute one row of B^T d B for every (tile, channel quad) - 24 conflict-free LDS reads, 124 VALU, 6 LDS writes per
 // thread, one raw column per MFMA slot; every wave reads 9 V fragments and 9 weight fragments for its 36 MFMAs.
+// A workgroup's 32 tile slots are either a bh x bw rectangle of tiles in each of ni images or, where that packs better (24x24,
+// 12x12: 30 of 32 slots instead of 27), a run of consecutive (image, tile row) units across image boundaries - the segment form,
+// the SEG instantiation; the K loop and the epilogue do not know which.
 // What was measured and dropped on the way (profiles/r02/k2-k5): a two-workgroup / 32-cout / 4-channel design,
 // epilogue prefetches that spill next to the accumulators, a carried-state item loop that spills raw-block offsets in the K loop.
 #include "w2l_common.h"
@@ -131,12 +134,19 @@ constexpr int kW4RAW4 = 512 * kW4NRAW;           // float4 slots per raw buffer
 // cell = image * istride + y * pitch + (x >> 2).  A transform read (all lanes the same (row, column) of their own tile) then
 // touches consecutive cells of one plane instead of entries 4 pixels apart (4-way bank conflicts in the first version), and
 // the host picks pitch / istride so that the 16 lanes of a ds_read_b128 group land on 16 distinct 16-byte bank slots.
-constexpr int kW4PS = 186;                       // = 2 mod 8: 8 consecutive pixels of a store group hit 8 distinct slots
+constexpr int kW4PS = 202;                       // = 2 mod 8: 8 consecutive pixels of a store group hit 8 distinct slots
 constexpr int kW4QS = 4 * kW4PS;                 // = 8 mod 16: the two channel quads of a read group use disjoint halves
-static_assert(2 * kW4QS <= kW4RAW4 && kW4PS % 8 == 2 && kW4QS % 16 == 8, "raw plane geometry");
+constexpr int kW4RAWB = 2 * kW4QS;               // float4 entries per raw buffer: the planes, not the load slots, set its size (a row
+                                                 // of 4bw+2 pixels takes bw+1 cells in EVERY plane: 48 rows of 14 pixels are 192 cells)
+static_assert(kW4RAWB >= kW4RAW4 && kW4PS % 8 == 2 && kW4QS % 16 == 8, "raw plane geometry");
 constexpr int kW4LDY = kW4BC + 4;
-constexpr int kW4LdsFloats = 2 * kW4VBUF + 2 * kW4RAW4 * 4;
-constexpr int kW4LdsBytes = kW4LdsFloats * 4 + 2 * kW4BT * 4;
+constexpr int kW4LdsFloats = 2 * kW4VBUF + 2 * kW4RAWB * 4;
+// Segment form of a tile block (wino4_pick_seg below): a run of R consecutive (image, tile row) units, full tile width, cut into
+// <= kW4S segments = the unit runs inside one image.  A segment stages its own 4nr+2 raw rows (rows of one image share their
+// halo); per segment the table holds {image, first tile row, tile rows, first raw row, first plane cell, first tile slot}.
+constexpr int kW4S = 8;
+constexpr int kW4SegInts = 8;
+constexpr int kW4LdsBytes = kW4LdsFloats * 4 + 2 * kW4BT * 4 + kW4S * kW4SegInts * 4;
 static_assert(4 * kW4BT * 4 * kW4LDY <= kW4LdsFloats, "one round of the four partial staging tiles must fit");
 static_assert(kW4LdsBytes <= 160 * 1024, "LDS budget");
 
@@ -150,7 +160,9 @@ struct Wino4KArgs {
     int N, H, W, cin, x_cs;
     int cout, y_cs, res_cs;
     int TH, TW;          // 4x4 output tiles per image
-    int bh, bw, ni;      // tile block of a workgroup
+    int bh, bw, ni;      // tile block of a workgroup (rectangular form)
+    int seg_r, seg_pad;  // segment form: units (tile rows) per block, extra plane cells in front of every segment after the first
+    int units;           // N * TH
     int nby, nbx, ngi;
     int RH, RW, R4;      // raw region per image (4bh+2, 4bw+2) and pixels per K-step ni*RH*RW (two float4 each)
     int pitch, istride;  // raw planes: cells per region row (>= bw+1) and per image (>= RH*pitch)
@@ -161,12 +173,14 @@ struct Wino4KArgs {
     int act;
 };
 
+template <bool SEG>
 __global__ __launch_bounds__(512, 2) void conv_wino4_f32_kernel(const Wino4KArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* Vs = reinterpret_cast<float*>(smem);                  // [2][36][32][LDK]
     float* Rs = Vs + 2 * kW4VBUF;                                // [2][RAW4] float4 slots, linear in the load index
-    int* s_opix = reinterpret_cast<int*>(Rs + 2 * kW4RAW4 * 4);  // [32] output pixel (4ty, 4tx) of a tile or -1
+    int* s_opix = reinterpret_cast<int*>(Rs + 2 * kW4RAWB * 4);  // [32] output pixel (4ty, 4tx) of a tile or -1
     int* s_oflag = s_opix + kW4BT;                               // [32] valid rows (bits 0-3) and columns (bits 4-7) of the tile
+    int* s_seg = s_oflag + kW4BT;                                // [kW4S][kW4SegInts] segment table (segment form)
 
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(a.x), 0, (int)((((long long)a.N * a.H * a.W - 1) * a.x_cs + a.cin) * 4), 0x00020000);
@@ -199,8 +213,39 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_f32_kernel(const Wino4KArgs
     const int gi = (int)(mb / (unsigned)a.nby);
     const int n0 = tile_n * kW4BC;
     const int bhw = a.bh * a.bw;
+    // segment form: this item's units are u0 .. u1-1 of the (image, tile row) list; mb is the block index
+    const int u0 = (int)(bid / (unsigned)a.tiles_n) * a.seg_r;
+    const int u1 = min(u0 + a.seg_r, a.units);
+    const int nfirst = SEG ? u0 / a.TH : 0;
 
-    if (t < kW4BT) {
+    if (SEG) {
+        if (t < kW4S) {          // segment t = the units of image nfirst + t inside [u0, u1)
+            const int n = nfirst + t;
+            const int ua = max(u0, n * a.TH), ub = min(u1, (n + 1) * a.TH);
+            const int row0 = ua - u0;                                  // block row of the segment's first tile row
+            int* sg = s_seg + t * kW4SegInts;
+            sg[0] = n;
+            sg[1] = ua - n * a.TH;
+            sg[2] = max(ub - ua, 0);
+            sg[3] = 4 * row0 + 2 * t;                                  // every segment in front staged 4nr+2 raw rows
+            sg[4] = (4 * row0 + 2 * t) * a.pitch + t * a.seg_pad;
+            sg[5] = row0 * a.TW;
+        }
+        if (t < kW4BT) {
+            const int r = t / a.TW, txl = t - r * a.TW;
+            const int u = u0 + r;
+            int o = -1, f = 0;
+            if (u < u1) {
+                const int n = u / a.TH, ty = u - n * a.TH;
+                o = (n * a.H + 4 * ty) * a.W + 4 * txl;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) f |= ((4 * ty + k < a.H) ? (1 << k) : 0) | ((4 * txl + k < a.W) ? (16 << k) : 0);
+            }
+            s_opix[t] = o;
+            s_oflag[t] = f;
+        }
+        __syncthreads();         // the raw-block gather reads the segment table
+    } else if (t < kW4BT) {
         const int il = t / bhw, r = t - il * bhw;
         const int tyl = r / a.bw, txl = r - tyl * a.bw;
         const int n = gi * a.ni + il, ty = by_i * a.bh + tyl, tx = bx_i * a.bw + txl;
@@ -224,7 +269,24 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_f32_kernel(const Wino4KArgs
         const int q = (e >> 3) & 1, pix = (e >> 4) * 8 + (e & 7);
         unsigned off = kW4Oob;
         int st = -1;
-        if (pix < a.R4) {
+        if (SEG) {
+            // raw row p2 of the block -> the segment whose staged rows hold it (segments are in raw-row order; empty ones
+            // follow the last used one)
+            const int p2 = (int)(((float)pix + 0.5f) * a.inv_rw);
+            const int rxx = pix - p2 * a.RW;
+            int j = 0;
+#pragma unroll
+            for (int sgi = 1; sgi < kW4S; ++sgi)
+                if (s_seg[sgi * kW4SegInts + 2] > 0 && p2 >= s_seg[sgi * kW4SegInts + 3]) j = sgi;
+            const int* sg = s_seg + j * kW4SegInts;
+            const int ry = p2 - sg[3];
+            if (ry < 4 * sg[2] + 2) {      // nr = 0 (a block past the last unit) stages nothing
+                st = (q * kW4QS + (rxx & 3) * kW4PS + sg[4] + ry * a.pitch + (rxx >> 2)) * 16;
+                const int iy = 4 * sg[1] - 1 + ry, ix = rxx - 1;
+                if ((unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W)
+                    off = ((unsigned)((sg[0] * a.H + iy) * a.W + ix) * (unsigned)a.x_cs + (unsigned)(q * 4)) * 4u;
+            }
+        } else if (pix < a.R4) {
             // exact small-integer division through the reciprocal (half-integer numerators, pix < 768)
             const int p2 = (int)(((float)pix + 0.5f) * a.inv_rw);
             const int rxx = pix - p2 * a.RW;
@@ -247,7 +309,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_f32_kernel(const Wino4KArgs
             rawreg[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)goff[k], (int)soff, 0));
     };
     auto raw_store = [&](int buf) {
-        char* dst = reinterpret_cast<char*>(Rs) + buf * (kW4RAW4 * 16);
+        char* dst = reinterpret_cast<char*>(Rs) + buf * (kW4RAWB * 16);
 #pragma unroll
         for (int k = 0; k < kW4NRAW; ++k)
             if (rst[k] >= 0) *reinterpret_cast<f32x4*>(dst + rst[k]) = rawreg[k];
@@ -268,7 +330,14 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_f32_kernel(const Wino4KArgs
         default: ra = 1; ca = 0.f; rb = 1; cb = 4.f; rc = 3; cc = -5.f; rd = 5; break;
     }
     int tf_base;
-    {
+    if (SEG) {
+        // tile slot -> (block row, column); the row's image is segment j, and every segment in front of it adds two halo rows
+        const int tl = lane >> 1;
+        int r = tl / a.TW, txl = tl - r * a.TW;
+        if (u0 + r >= u1) r = 0, txl = 0;        // unused tile slots read slot 0's patch: inside the buffer, never stored
+        const int j = (u0 + r) / a.TH - nfirst;
+        tf_base = (q * kW4QS + (4 * r + 2 * j) * a.pitch + j * a.seg_pad + txl) * 16;
+    } else {
         const int tl = lane >> 1;
         const int il = tl / bhw, r = tl - il * bhw;
         const int tyl = r / a.bw, txl = r - tyl * a.bw;
@@ -280,7 +349,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_f32_kernel(const Wino4KArgs
     float* const vwr = Vs + ((wave < 6 ? wave : 0) * 6) * kW4VPOS + (lane >> 1) * kW4LDK + q * 4;
     f32x4 rr[6];
     auto tf_rows = [&](int buf, int c0) {         // rr[c0] = row i of B^T d, column c0
-        const char* src = reinterpret_cast<const char*>(Rs) + buf * (kW4RAW4 * 16);
+        const char* src = reinterpret_cast<const char*>(Rs) + buf * (kW4RAWB * 16);
 #pragma unroll
         for (int c = c0; c < c0 + 1; ++c) {
             const int co = ((c & 3) * kW4PS + (c >> 2)) * 16;      // plane of the column, next cell for columns 4, 5
@@ -528,9 +597,10 @@ struct W4Block { int bh, bw, ni; };
 static const W4Block kW4Blocks[] = {{4, 8, 1}, {8, 4, 1}, {4, 4, 2}, {2, 8, 2}, {8, 2, 1}, {2, 4, 3}, {4, 2, 3}, {3, 3, 3},
                                     {2, 2, 6}, {2, 3, 4}, {3, 2, 4}, {1, 4, 6}, {4, 1, 5}, {1, 2, 10}, {2, 1, 9}, {1, 1, 15}};
 
+constexpr int kW4RectCells = 186;   // plane cells the rectangular blocks were chosen under (the planes grew for the segment form)
 static bool wino4_block_fits(const W4Block& b) {
     const int RH = 4 * b.bh + 2, RW = 4 * b.bw + 2;
-    return b.bh * b.bw * b.ni <= kW4BT && b.ni * RH * RW * 2 <= kW4RAW4 && b.ni * RH * (b.bw + 1) <= kW4PS;
+    return b.bh * b.bw * b.ni <= kW4BT && b.ni * RH * RW * 2 <= kW4RAW4 && b.ni * RH * (b.bw + 1) <= kW4RectCells;
 }
 
 // raw-plane geometry of a block: the row pitch and image stride (cells) under which the 16 lanes of every ds_read_b128 lane group
@@ -545,7 +615,7 @@ static void wino4_plane_geom(const W4Block& b, int* pitch, int* istride) {
     *istride = RH * (b.bw + 1);
     for (int p = b.bw + 1; p <= b.bw + 4; ++p)
         for (int is = RH * p; is <= RH * p + 15; ++is) {
-            if (b.ni * is > kW4PS) break;
+            if (b.ni * is > kW4RectCells) break;
             int cost = (p - b.bw - 1) + (is - RH * p);
             for (int g = 0; g < 4; ++g) {
                 int cnt[16] = {0};
@@ -562,7 +632,7 @@ static void wino4_plane_geom(const W4Block& b, int* pitch, int* istride) {
         }
 }
 
-static W4Block wino4_pick_block(int N, int TH, int TW) {
+static W4Block wino4_pick_block(int N, int TH, int TW, double* cost_out) {
     W4Block best = {1, 1, 1};
     double best_cost = 1e300;
     for (const W4Block& b : kW4Blocks) {
@@ -572,7 +642,71 @@ static W4Block wino4_pick_block(int N, int TH, int TW) {
         const double cost = items * (1.0 + 0.05 * halo);
         if (cost < best_cost) { best_cost = cost; best = b; }
     }
+    *cost_out = best_cost;
     return best;
+}
+
+// ---- segment form.  Units = the (image, tile row) pairs in order, a block = R consecutive units at full tile width, so a block
+// may run across image boundaries: 12x12 (3x3 tiles) packs 10 rows = 30 of 32 tile slots where the best rectangle (3x3x3) fills 27,
+// 24x24 5 rows of 6.  Block b starts at tile row (b*R) % TH of its first image and touches (that + R - 1) / TH + 1 images =
+// segments; a segment of nr rows stages 4nr+2 raw rows of 4TW+2 pixels.
+struct W4Seg { int R, pitch, pad, nblk; double cost; };
+
+static int wino4_seg_count(int off, int R, int TH) { return (off + R - 1) / TH + 1; }
+
+// most segments any block of the launch has (block starts repeat with period <= TH)
+static int wino4_seg_worst(int R, int TH, int nblk) {
+    int worst = 1;
+    for (int b = 0; b < nblk && b < TH; ++b) worst = std::max(worst, wino4_seg_count((b * R) % TH, R, TH));
+    return worst;
+}
+
+// bank-slot collisions of the transform reads (wino4_plane_geom's measure) summed over the block starts of the launch
+static int wino4_seg_conflicts(int R, int TH, int TW, int nblk, int pitch, int pad) {
+    static const int kGroup[2][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
+                                      {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31}};
+    int cost = 0;
+    for (int b = 0; b < nblk && b < TH; ++b) {
+        const int off = (b * R) % TH;
+        for (int g = 0; g < 4; ++g) {
+            int cnt[16] = {0};
+            for (int k = 0; k < 16; ++k) {
+                const int lane = kGroup[g & 1][k] + 32 * (g >> 1);
+                const int tl = lane >> 1, q = lane & 1;
+                int r = tl / TW, c = tl % TW;
+                if (r >= R) r = 0, c = 0;
+                const int j = (off + r) / TH;
+                ++cnt[(q * kW4QS + (4 * r + 2 * j) * pitch + j * pad + c) & 15];
+            }
+            for (int k = 0; k < 16; ++k) cost += cnt[k] > 1 ? (cnt[k] - 1) * 64 * cnt[k] : 0;
+        }
+    }
+    return cost;
+}
+
+// R = the most rows per block under the three limits (tile slots, raw pixels, plane cells at the tightest pitch), for the worst
+// split over images the launch has; then the (pitch, per-segment pad) inside the plane with the fewest bank-slot collisions.
+// R = 0: no segment block fits.  A function of the shape alone.
+static W4Seg wino4_pick_seg(int N, int TH, int TW) {
+    W4Seg s = {0, 0, 0, 0, 1e300};
+    const int units = N * TH, RW = 4 * TW + 2;
+    for (int R = std::min(kW4BT / TW, units); R >= 1; --R) {
+        const int nblk = ceil_div(units, R);
+        const int ns = wino4_seg_worst(R, TH, nblk), rows = 4 * R + 2 * ns;
+        if (ns > kW4S || rows * RW * 2 > kW4RAW4 || rows * (TW + 1) > kW4PS) continue;
+        s.R = R;
+        s.nblk = nblk;
+        s.cost = (double)nblk * (1.0 + 0.05 * (double)(rows * RW) / (16.0 * R * TW));
+        int best = 1 << 30;
+        for (int p = TW + 1; p <= TW + 4; ++p)
+            for (int pad = 0; pad < 8; ++pad) {
+                if (rows * p + (ns - 1) * pad > kW4PS) break;
+                const int c = wino4_seg_conflicts(R, TH, TW, nblk, p, pad) + (p - TW - 1) + pad;
+                if (c < best) { best = c; s.pitch = p; s.pad = pad; }
+            }
+        break;
+    }
+    return s;
 }
 
 bool wino4_ok(int cin, int cout) { return cin % kW4KS == 0 && cout % kW4BC == 0; }
@@ -592,7 +726,9 @@ int wino4_pack(const float* w, float* u, int cin, int cout, int transposed, hipS
 int wino4_init_attrs() {   // called under the lock of init_kernel_attrs (conv_igemm.hip)
     static bool done = false;
     if (done) return W2L_OK;
-    W2L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino4_f32_kernel),
+    W2L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino4_f32_kernel<false>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, kW4LdsBytes));
+    W2L_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino4_f32_kernel<true>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, kW4LdsBytes));
     done = true;
     return W2L_OK;
@@ -605,20 +741,37 @@ int wino4_launch(const WinoKArgs& w, const float* u4, hipStream_t stream, long l
     a.cout = w.cout; a.y_cs = w.y_cs; a.res_cs = w.res_cs; a.act = w.act;
     a.TH = (a.H + 3) / 4;
     a.TW = (a.W + 3) / 4;
-    const W4Block b = wino4_pick_block(a.N, a.TH, a.TW);
-    a.bh = b.bh; a.bw = b.bw; a.ni = b.ni;
-    a.nby = ceil_div(a.TH, b.bh);
-    a.nbx = ceil_div(a.TW, b.bw);
-    a.ngi = ceil_div(a.N, b.ni);
-    a.RH = 4 * b.bh + 2;
-    a.RW = 4 * b.bw + 2;
-    a.R4 = b.ni * a.RH * a.RW;
-    wino4_plane_geom(b, &a.pitch, &a.istride);
-    a.inv_rw = 1.0f / (float)a.RW;
-    a.inv_rh = 1.0f / (float)a.RH;
+    W2L_REQUIRE((long long)a.N * a.TH < (1ll << 30), "grid too large");
+    double rect_cost;
+    const W4Block b = wino4_pick_block(a.N, a.TH, a.TW, &rect_cost);
+    const W4Seg sg = wino4_pick_seg(a.N, a.TH, a.TW);
+    const bool seg = sg.R > 0 && sg.cost < rect_cost;      // the same cost on both sides: items x (1 + 0.05 halo)
     a.nks = a.cin / 8;
     a.tiles_n = a.cout / kW4BC;
-    a.total = (long long)a.ngi * a.nby * a.nbx * a.tiles_n;
+    a.units = a.N * a.TH;
+    if (seg) {
+        a.bh = a.bw = a.ni = a.nby = a.nbx = 1;
+        a.ngi = sg.nblk;
+        a.seg_r = sg.R; a.seg_pad = sg.pad;
+        a.RH = 0;
+        a.RW = 4 * a.TW + 2;
+        a.R4 = 0;
+        a.pitch = sg.pitch; a.istride = 0;
+        a.total = (long long)sg.nblk * a.tiles_n;
+    } else {
+        a.bh = b.bh; a.bw = b.bw; a.ni = b.ni;
+        a.seg_r = 0; a.seg_pad = 0;
+        a.nby = ceil_div(a.TH, b.bh);
+        a.nbx = ceil_div(a.TW, b.bw);
+        a.ngi = ceil_div(a.N, b.ni);
+        a.RH = 4 * b.bh + 2;
+        a.RW = 4 * b.bw + 2;
+        a.R4 = b.ni * a.RH * a.RW;
+        wino4_plane_geom(b, &a.pitch, &a.istride);
+        a.total = (long long)a.ngi * a.nby * a.nbx * a.tiles_n;
+    }
+    a.inv_rw = 1.0f / (float)a.RW;
+    a.inv_rh = a.RH ? 1.0f / (float)a.RH : 0.f;
     W2L_REQUIRE(a.total < (1ll << 31), "grid too large");
     W2L_REQUIRE((long long)a.N * a.H * a.W < (1ll << 31), "tensor too large");
     if (flops_out) {   // dry run: 36 position-GEMMs of [items*32] x [64] x cin
@@ -627,12 +780,36 @@ int wino4_launch(const WinoKArgs& w, const float* u4, hipStream_t stream, long l
     }
     long long grid = (a.total + 7) / 8 * 8;
     if (grid > 256) grid = 256;        // persistent, one 512-thread workgroup per CU
-    hipLaunchKernelGGL(conv_wino4_f32_kernel, dim3((unsigned)grid), dim3(512), kW4LdsBytes, stream, a);
+    if (seg)
+        hipLaunchKernelGGL(conv_wino4_f32_kernel<true>, dim3((unsigned)grid), dim3(512), kW4LdsBytes, stream, a);
+    else
+        hipLaunchKernelGGL(conv_wino4_f32_kernel<false>, dim3((unsigned)grid), dim3(512), kW4LdsBytes, stream, a);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }
 
 }  // namespace w2l
+
+extern "C" int w2l_wino4_block_plan(int N, int H, int W, int* out) {
+    using namespace w2l;
+    W2L_REQUIRE(out && N >= 1 && H >= 1 && W >= 1 && (long long)N * ((H + 3) / 4) < (1ll << 30), "wino4_block_plan: bad arguments");
+    const int TH = (H + 3) / 4, TW = (W + 3) / 4;
+    double rect_cost;
+    const W4Block b = wino4_pick_block(N, TH, TW, &rect_cost);
+    const W4Seg sg = wino4_pick_seg(N, TH, TW);
+    const bool seg = sg.R > 0 && sg.cost < rect_cost;
+    int pitch = sg.pitch, istride = 0;
+    if (!seg) wino4_plane_geom(b, &pitch, &istride);
+    out[0] = seg;
+    out[1] = seg ? sg.nblk : ceil_div(TH, b.bh) * ceil_div(TW, b.bw) * ceil_div(N, b.ni);
+    out[2] = seg ? sg.R : b.bh;
+    out[3] = seg ? TW : b.bw;
+    out[4] = seg ? 0 : b.ni;
+    out[5] = pitch;
+    out[6] = seg ? sg.pad : istride;
+    out[7] = kW4PS;
+    return W2L_OK;
+}
 
 #ifdef W4_TRACE
 extern "C" int w2l_dbg_w4_trace(unsigned long long* out) {
