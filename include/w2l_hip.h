@@ -26,6 +26,9 @@
  *   w2l_crop_resize_rows_u8  evaluation/gen_videos_from_filelist.py:85-95 (the same crop + resize, one frame per row)
  *   w2l_compose_rows_u8   evaluation/gen_videos_from_filelist.py:221-227 (resize + paste + the frame copy, one pass)
  *   w2l_mel_gather_rows   evaluation/gen_videos_from_filelist.py:176-183 (mel windows, one spectrogram per row)
+ *   w2l_s3fd_pack_rows    face_detection/api.py:62 + detection/sfd/detect.py:57-63 (the detector's input), one frame per row
+ *   w2l_face_boxes_segments  evaluation/gen_videos_from_filelist.py:35-42, :61-77 = inference.py:59-66, :90-104 (pads, clipping,
+ *                         "Face not detected", get_smoothened_boxes) for every clip of a group in one launch
  *   w2l_melspectrogram    audio.py:45-51 (preemphasis, STFT, mel basis, dB, normalise)
  *   w2l_mel_gather        inference.py:231-240 (16-frame mel windows at host-computed starts)
  *   w2l_resample_sinc     audio.py:9-10 (librosa.core.load's sample-rate conversion: resampy 'kaiser_best' sinc interpolation)
@@ -212,6 +215,11 @@ int w2l_compose_rows_u8(void* stream, int B, const uint8_t* pred, int S, const w
 /* bgr u8 [npix][3] -> y fp32 [npix][y_cs]: RGB order (api.py:62 images[..., ::-1]) minus (104,117,123) (detect.py:57),
  * channel 3 zero when y_cs %% 4 == 0 */
 int w2l_s3fd_pack(void* stream, long long npix, const uint8_t* bgr, float* y, int y_cs);
+/* The row-table form of w2l_s3fd_pack: `frames` is a device table of B addresses (8-byte aligned); entry b is pixel (0,0) of a u8
+ * [H,W,3] BGR frame anywhere in device memory, at ANY byte alignment (dword loads where the frame is 4-byte aligned, bytes
+ * elsewhere).  Image b of y [B,H,W,y_cs] is what w2l_s3fd_pack writes for that frame, byte for byte: a batch may hold frames of
+ * several clips, read where they lie (face_detection/many.py).  B <= 65535, H * W <= 2^29. */
+int w2l_s3fd_pack_rows(void* stream, int B, int H, int W, const uint64_t* frames, float* y, int y_cs);
 /* F.max_pool2d(x, 2, 2) on NHWC: y [N,H/2,W/2,y_cs] (net_s3fd.py:75-97); C %% 4 == 0 */
 int w2l_maxpool2x2(void* stream, int N, int H, int W, int C, const float* x, int x_cs, float* y, int y_cs);
 /* L2Norm (net_s3fd.py:6-19): y[row][c] = x[row][c] / (sqrt(sum_c x^2) + 1e-10) * weight[c] */
@@ -240,12 +248,38 @@ int w2l_s3fd_nms(void* stream, int B, int P, const float* table, float gate, flo
 int w2l_s3fd_first_rect(void* stream, int B, int P, const float* table, const int* keep, const int* counts, float thresh,
                         int* rects, int* flags);
 
+/* The per-clip finish of face_detect (inference.py:90-104 pads + clipping + "Face not detected", :59-66 get_smoothened_boxes;
+ * evaluation/gen_videos_from_filelist.py:35-42, :61-77 is the same code) for many clips in one launch.  rects [R][4] = (x1, y1, x2, y2)
+ * and flags [R] are arenas w2l_s3fd_first_rect filled (its two output pointers aimed at the rows of each batch); segment k is
+ * one clip: rows [row0, row0 + n) of them, frames of H x W.
+ *
+ * w2l_box_segment, 16 bytes, the table 16-byte aligned:
+ *   bytes 0..7   int32 row0, n   the clip's rows of the arenas (n <= 0: nothing is read or written, status (0, 0))
+ *   bytes 8..15  int32 H, W      its frame size
+ *
+ * boxes [R][4] = (y1, y2, x1, x2), the `coords` order face_detect returns: (max(0, y1 - top), min(H, y2 + bottom),
+ * max(0, x1 - left), min(W, x2 + right)) - a negative pad or a rect beyond the frame is not pulled back from the other side, as
+ * there - then for T >= 1 get_smoothened_boxes exactly: in place and in row order, window [i, i + T) while i + T <= n, else
+ * Python's boxes[n - T:] (for n < T the negative start wraps and is clipped at 0), every mean an integer sum divided in fp64 and
+ * truncated towards zero on assignment.  T = 0: no smoothing.  0 <= T <= 64.
+ * status [n_seg][2] = (code, row inside the segment): 2 when a row is flagged 2 (the host must decide; the first such row - the
+ * detector meets it before face_detect looks for None), else 1 when a row is flagged 0 (no face; the first such row), else
+ * (0, 0).  For a non-zero code the segment's boxes are zeros.  A segment reads and writes its own rows only. */
+typedef struct {
+    int32_t row0, n, H, W;
+} w2l_box_segment;
+int w2l_face_boxes_segments(void* stream, int n_seg, const w2l_box_segment* segs, const int32_t* rects, const int32_t* flags,
+                            int top, int bottom, int left, int right, int T, int32_t* boxes, int32_t* status);
+
 /* The opt-in bf16-storage detector (face_detection/s3fd.py, precision="bf16"): the backbone convolutions are w2l_convb layers
  * (scale 1, shift = bias, ReLU); these are the ops between them and the fused detection head.  Tensors are NHWC bf16 with channel
  * strides that are multiples of 8, 16-byte aligned; no buffer may reach 2 GiB (the convb rule: split the batch). */
 /* bgr u8 [npix][3] -> y bf16 [npix][y_cs]: the values of w2l_s3fd_pack (api.py:62 + detect.py:57, integers with |v| <= 152, so
  * exact), channels 3 .. y_cs-1 zero */
 int w2l_s3fd_pack_bf16(void* stream, long long npix, const uint8_t* bgr, void* y, int y_cs);
+/* The row-table form (w2l_s3fd_pack_rows): image b of y bf16 [B,H,W,y_cs] is what w2l_s3fd_pack_bf16 writes for the frame at
+ * frames[b], byte for byte */
+int w2l_s3fd_pack_rows_bf16(void* stream, int B, int H, int W, const uint64_t* frames, void* y, int y_cs);
 /* F.max_pool2d(x, 2, 2) on bf16 NHWC (net_s3fd.py:75-97, floor semantics): bit-equal to torch on the same tensor; C %% 8 == 0 */
 int w2l_maxpool2x2_bf16(void* stream, int N, int H, int W, int C, const void* x, int x_cs, void* y, int y_cs);
 /* L2Norm (net_s3fd.py:6-19) on bf16 rows: sum of squares and x / (sqrt(.) + 1e-10) * weight[c] in fp32 (weight fp32 [C]),

@@ -1,0 +1,237 @@
+"""Packed face detection without a device: the grouping, batching, arena rows, padding and result order of
+`face_detection.detect_many` with the two device steps stubbed and host tensors standing in for device ones, its fall-backs to
+`inference.face_detect`, the host statement of the per-clip finish against `face_detect` itself, and the flag of the two commands."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+H, W = 12, 10
+NONE_BYTE, HOST_BYTE = 254, 253        # a frame filled with one of these is flagged RECT_NONE / RECT_HOST by the fake detector
+
+
+def _rect_of(v):
+    return (v, v + 1, v + 20, v + 30)
+
+
+class FakeDetector:
+    """rects_for_rows reads the first byte of every frame through the address table (so staged host frames and frames that were
+    tensors already are both followed) and writes a rect that names it; every call is recorded"""
+    device, precision = "cpu", "f32"
+
+    def __init__(self, limit=None):
+        self.calls, self.limit = [], limit
+
+    def rects_for_rows(self, frames, B, H_, W_, rects, flags, offset):
+        from wav2lip_amd.face_detection.s3fd import RECT_FOUND, RECT_HOST, RECT_NONE
+        if self.limit is not None and B > self.limit:
+            raise RuntimeError("out of memory")
+        addr = frames.numpy().view("<u8")
+        assert len(addr) == B
+        first = [ctypes.c_uint8.from_address(int(a)).value for a in addr]
+        for k, v in enumerate(first):
+            rects[offset + k] = torch.tensor(_rect_of(v) if v < HOST_BYTE else (0, 0, 0, 0), dtype=torch.int32)
+            flags[offset + k] = RECT_NONE if v == NONE_BYTE else RECT_HOST if v == HOST_BYTE else RECT_FOUND
+        self.calls.append((B, H_, W_, offset, tuple(rects.shape), addr.copy(), first))
+
+
+def _host_finish(log):
+    def finish(n_seg, segs, rects, flags, pads, T, boxes, status):
+        from wav2lip_amd.face_detection import many
+        from wav2lip_amd.face_detection.s3fd import RECT_HOST, RECT_NONE
+        s = segs.numpy().view(many.BOX_SEGMENT).copy()
+        assert len(s) == n_seg
+        log.append(s)
+        b, st = boxes.numpy().reshape(-1, 4), status.numpy().reshape(-1, 2)
+        for k, (row0, n, h, w) in enumerate(s.tolist()):
+            f = flags[row0:row0 + n].tolist()
+            host = [i for i, x in enumerate(f) if x == RECT_HOST]
+            none = [i for i, x in enumerate(f) if x == RECT_NONE]
+            st[k] = (2, host[0]) if host else (1, none[0]) if none else (0, 0)
+            b[row0:row0 + n] = 0 if host or none else many.host_boxes(rects[row0:row0 + n].tolist(), h, w, pads, T)
+    return finish
+
+
+def _jobs(spec, pulled, shape=(H, W)):
+    """spec: [(frames, fill byte or None, shape or None)]; clip c's frame v is filled with 10 * (c % 20) + v % 10 unless a fill byte
+    is given; odd clips are tensors ("device" frames), even clips lists of host arrays"""
+    from wav2lip_amd import face_detection
+    for c, item in enumerate(spec):
+        n, fill, shp = item if isinstance(item, tuple) else (item, None, None)
+        h, w = shp or shape
+        frames = np.empty((n, h, w, 3), np.uint8)
+        frames[:] = (10 * (c % 20) + np.arange(n) % 10).astype(np.uint8)[:, None, None, None]
+        if fill is not None:
+            frames[n // 2] = fill
+        pulled.append(c)
+        yield face_detection.DetectJob("clip%d" % c, torch.from_numpy(frames) if c % 2 else list(frames))
+
+
+def _want(c, n, pads=(0, 0, 0, 0), T=5, shape=(H, W)):
+    from wav2lip_amd.face_detection import many
+    return many.host_boxes([_rect_of(10 * (c % 20) + v % 10) for v in range(n)], shape[0], shape[1], pads, T)
+
+
+def test_groups_batches_arena_rows_padding_and_job_order(monkeypatch):
+    from wav2lip_amd import face_detection
+    from wav2lip_amd.face_detection import many
+    det, segs, pulled, seen = FakeDetector(), [], [], []
+    monkeypatch.setattr(many, "_finish_segments", _host_finish(segs))
+    counts = [5, 0, 7, 3, 9, 1, 2]
+    bs = 4
+    # group_batches 3: a group closes once it holds 12 frames -> [5, 0, 7] [3, 9] [1, 2]
+    for key, boxes, error in face_detection.detect_many(det, _jobs(counts, pulled), pads=(1, 2, 3, 4), T=5, batch_size=bs, group_batches=3):
+        seen.append((key, boxes, error, len(pulled), len(segs)))
+    assert [s[0] for s in seen] == ["clip%d" % c for c in range(len(counts))]           # job order, the empty clip in its place
+    for c, (key, boxes, error, _, _) in enumerate(seen):
+        assert error is None and boxes.shape == (counts[c], 4) and boxes.dtype.kind == "i"
+        assert np.array_equal(boxes, _want(c, counts[c], (1, 2, 3, 4)))
+    assert [s["n"].tolist() for s in segs] == [[5, 7], [3, 9], [1, 2]]
+    # lazily consumed: the jobs of the next group are read after the previous group's results went out
+    assert [s[3] for s in seen] == [3, 3, 3, 5, 5, 7, 7] and [s[4] for s in seen] == [1, 1, 1, 2, 2, 3, 3]
+    done = 0
+    for s in segs:
+        R = int(s["n"].sum())
+        padded = -(-R // bs) * bs
+        assert s["row0"].tolist() == [0] + np.cumsum(s["n"])[:-1].tolist()              # segments tile the arena without gaps
+        assert (s["H"] == H).all() and (s["W"] == W).all()
+        calls = det.calls[done:done + padded // bs]
+        done += padded // bs
+        assert [c[0] for c in calls] == [bs] * len(calls)                               # every batch has exactly batch_size rows
+        assert [c[3] for c in calls] == list(range(0, padded, bs)) and all(c[4] == (padded, 4) for c in calls)
+        addr = np.concatenate([c[5] for c in calls])
+        assert (addr[R:] == addr[R - 1]).all()                                          # padding repeats the last address, behind row R
+        first = sum((c[6] for c in calls), [])
+        for row0, n, _, _ in s.tolist():                                                # every arena row holds the frame it should
+            assert [v % 10 for v in first[row0:row0 + n]] == [v % 10 for v in range(n)]
+            assert len({v // 10 for v in first[row0:row0 + n]}) == 1
+    assert done == len(det.calls)
+
+
+def test_a_group_closes_on_shape_change_byte_cap_and_iterator_end(monkeypatch):
+    from wav2lip_amd import face_detection
+    from wav2lip_amd.face_detection import many
+    det, segs, pulled = FakeDetector(), [], []
+    monkeypatch.setattr(many, "_finish_segments", _host_finish(segs))
+    other = (8, 14)
+    spec = [(3, None, None), (2, None, None), (4, None, other), (1, None, other), (2, None, None)]
+    res = list(face_detection.detect_many(det, _jobs(spec, pulled), T=0, batch_size=4, group_batches=100))
+    assert [s["n"].tolist() for s in segs] == [[3, 2], [4, 1], [2]]
+    assert [(c[1], c[2]) for c in det.calls] == [(H, W)] * 2 + [other] * 2 + [(H, W)]
+    assert np.array_equal(res[2][1], _want(2, 4, T=0, shape=other)) and np.array_equal(res[4][1], _want(4, 2, T=0))
+    # the byte cap: a frame is 360 bytes; 3 + 2 frames fit 2000 bytes, the next 2 do not; a group always holds one job
+    det, segs = FakeDetector(), []
+    monkeypatch.setattr(many, "_finish_segments", _host_finish(segs))
+    res = list(face_detection.detect_many(det, _jobs([3, 2, 2, 5, 1], []), batch_size=4, group_batches=100, max_group_bytes=2000))
+    assert [s["n"].tolist() for s in segs] == [[3, 2], [2], [5], [1]] and [r[0] for r in res] == ["clip%d" % c for c in range(5)]
+    assert list(face_detection.detect_many(det, iter(()))) == []
+    with pytest.raises(ValueError, match="job 'b'"):
+        list(face_detection.detect_many(det, [face_detection.DetectJob("b", [np.zeros((4, 4, 3), np.float32)])]))
+    with pytest.raises(ValueError, match="job 'c'"):
+        list(face_detection.detect_many(det, [face_detection.DetectJob("c", [np.zeros((4, 4, 3), np.uint8), np.zeros((4, 5, 3), np.uint8)])]))
+    for bad in (dict(batch_size=0), dict(T=65), dict(T=-1), dict(pads=(0, 0, 0))):
+        with pytest.raises(ValueError):
+            list(face_detection.detect_many(det, [], **bad))
+
+
+def test_no_face_is_an_error_text_and_a_host_flag_reruns_that_clip_alone(monkeypatch):
+    from wav2lip_amd import face_detection, inference
+    from wav2lip_amd.face_detection import many
+    det, segs, reruns = FakeDetector(), [], []
+    monkeypatch.setattr(many, "_finish_segments", _host_finish(segs))
+
+    def fake_face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None):
+        reruns.append((len(images), int(images[0][0, 0, 0]), detector, pads, nosmooth, batch_size))
+        if len(images) == 6:
+            raise ValueError("cannot convert float NaN to integer")
+        return [[im, (1, 2, 3, 4)] for im in images]
+
+    monkeypatch.setattr(inference, "face_detect", fake_face_detect)
+    spec = [4, (5, NONE_BYTE, None), (3, HOST_BYTE, None), 2, (6, HOST_BYTE, None)]
+    res = list(face_detection.detect_many(det, _jobs(spec, []), pads=(0, 10, 0, 0), batch_size=8))
+    assert [r[0] for r in res] == ["clip%d" % c for c in range(5)]
+    assert res[0][2] is None and np.array_equal(res[0][1], _want(0, 4, (0, 10, 0, 0)))          # the neighbours are unaffected
+    assert res[3][2] is None and np.array_equal(res[3][1], _want(3, 2, (0, 10, 0, 0)))
+    assert res[1][1] is None and res[1][2] == 'Face not detected! Ensure the video contains a face in all the frames.'
+    assert res[2][2] is None and res[2][1].tolist() == [[1, 2, 3, 4]] * 3                       # face_detect's answer for that clip
+    assert res[4][1] is None and res[4][2] == "cannot convert float NaN to integer"             # or its exception
+    assert reruns == [(3, 20, det, [0, 10, 0, 0], False, 8), (6, 40, det, [0, 10, 0, 0], False, 8)]
+
+
+def test_a_detector_runtime_error_halves_the_batch_and_reruns_the_group(monkeypatch, capsys):
+    from wav2lip_amd import face_detection
+    from wav2lip_amd.face_detection import many
+    det, segs = FakeDetector(limit=2), []
+    monkeypatch.setattr(many, "_finish_segments", _host_finish(segs))
+    res = list(face_detection.detect_many(det, _jobs([5, 4, 3], []), batch_size=8, group_batches=1))
+    assert capsys.readouterr().out.splitlines() == ['Recovering from OOM error; New batch size: 4', 'Recovering from OOM error; New batch size: 2']
+    assert all(c[0] == 2 for c in det.calls)                                   # the rest of the run keeps the halved size
+    assert [s["n"].tolist() for s in segs] == [[5, 4], [3]]                    # 8 frames closed the first group; the second closes at 2
+    for c, n in enumerate([5, 4, 3]):
+        assert np.array_equal(res[c][1], _want(c, n))
+    with pytest.raises(RuntimeError, match="Image too big to run face detection on GPU"):
+        list(face_detection.detect_many(FakeDetector(limit=0), _jobs([2], []), batch_size=2))
+
+
+def test_an_oversize_job_takes_the_per_clip_path_in_its_place(monkeypatch):
+    from wav2lip_amd import face_detection, inference
+    from wav2lip_amd.face_detection import many
+    det, segs, reruns = FakeDetector(), [], []
+    monkeypatch.setattr(many, "_finish_segments", _host_finish(segs))
+
+    def fake_face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None):
+        reruns.append((len(images), nosmooth))
+        return [[im, (9, 8, 7, 6)] for im in images]
+
+    monkeypatch.setattr(inference, "face_detect", fake_face_detect)
+    res = list(face_detection.detect_many(det, _jobs([2, 9, 3], []), T=0, batch_size=4, max_group_bytes=5 * H * W * 3))
+    assert [r[0] for r in res] == ["clip0", "clip1", "clip2"] and reruns == [(9, True)]
+    assert res[1][1].tolist() == [[9, 8, 7, 6]] * 9 and [s["n"].tolist() for s in segs] == [[2], [3]]
+
+
+class StubDetector:
+    precision = "f32"
+
+    def __init__(self, rects):
+        self.rects = list(rects)
+
+    def get_detections_for_batch(self, images):
+        out, self.rects = self.rects[:len(images)], self.rects[len(images):]
+        return out
+
+
+@pytest.mark.parametrize("pads", [(0, 10, 0, 0), (3, 10, 5, 7), (-2, -10, -4, -3)])
+def test_host_boxes_is_face_detect_with_a_stub_detector(pads):
+    """n in 1..7 (n < T wraps the window's negative start), rects reaching beyond the 40 x 50 frame, both smoothing settings"""
+    from wav2lip_amd import inference
+    from wav2lip_amd.face_detection import many
+    r = np.random.default_rng(11)
+    for n in range(1, 8):
+        for _ in range(20):
+            rects = [tuple(int(v) for v in r.integers(0, 70, 4)) for _ in range(n)]
+            images = [np.zeros((40, 50, 3), np.uint8)] * n
+            for T, nosmooth in ((5, False), (0, True)):
+                det = inference.face_detect(images, detector=StubDetector(rects), pads=list(pads), nosmooth=nosmooth, batch_size=3)
+                assert np.array_equal(many.host_boxes(rects, 40, 50, pads, T), np.array([c for _, c in det])), (n, rects, T)
+    assert many.host_boxes([], 40, 50, pads, 5).shape == (0, 4)
+
+
+def test_segment_mirror_has_the_size_of_the_header_and_the_symbols_are_bound():
+    from wav2lip_amd import _lib
+    from wav2lip_amd.face_detection import many
+    assert many.BOX_SEGMENT.itemsize == ctypes.sizeof(_lib.BoxSegment) == 16
+    assert [many.BOX_SEGMENT.fields[n][1] for n in ("row0", "n", "H", "W")] == [getattr(_lib.BoxSegment, n).offset for n in ("row0", "n", "H", "W")] == [0, 4, 8, 12]
+    for sym in ("w2l_s3fd_pack_rows", "w2l_s3fd_pack_rows_bf16", "w2l_face_boxes_segments"):
+        assert sym in _lib.SIGNATURES
+
+
+def test_both_commands_take_the_flag_and_default_to_off():
+    from wav2lip_amd import calculate_scores as cs, gen_videos_from_filelist as gv
+    base = ["--filelist", "f", "--results_dir", "r", "--data_root", "d", "--checkpoint_path", "c"]
+    assert gv.main_parser.parse_args(base).packed_face_det is False
+    assert gv.main_parser.parse_args(base + ["--packed_face_det"]).packed_face_det is True
+    assert gv.main_parser.parse_args(base).face_det_batch_size == 64
+    base = ["--data_root", "d", "--checkpoint_path", "c"]
+    assert cs.cli_parser.parse_args(base).packed_face_det is False
+    assert cs.cli_parser.parse_args(base + ["--packed_face_det"]).packed_face_det is True

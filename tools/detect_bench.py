@@ -1,0 +1,134 @@
+"""Packed face detection against the per-clip loop, alternated in one process: frames/s of `face_detection.detect_many` and of
+`for clip: inference.face_detect(frames, detector, ...)` over the same seeded clips.
+
+    python tools/detect_bench.py [--clips 200] [--alternations 5] [--batch 16] [--precision f32] [--seed 0]
+
+The clips are those of tools/filelist_bench.py (160x160 frames, lengths uniform in 30..120, 16 distinct frames cycled), each frame
+with the saturated block of synthetic.filelist_frame pasted in so that the seeded S3FD (synthetic.s3fd_state_dict) finds a face;
+frames start on the host in both loops, as the commands have them, and both end with every clip's boxes on the host.  Pads
+(0, 0, 0, 0), smoothing T = 5: the filelist command's settings.  The per-clip loop is the code path of the commands without
+`--packed_face_det`.  Each loop owns a detector, so the graphs it builds are its own.  Pass 0 of each loop is its warm-up and is
+reported separately; then the two loops alternate, --alternations pairs.  Prints one JSON line: per loop the frames/s of every pass
+with median, min and max, the first-pass seconds, detector graph builds per pass, torch.cuda.max_memory_allocated after the loop's
+first pass (the peak since process start for the packed loop, which runs first, and the peak over everything for the per-clip
+loop), and how many boxes and clips differ between the two paths."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from filelist_bench import make_clips  # noqa: E402
+from wav2lip_amd import face_detection, inference  # noqa: E402
+from wav2lip_amd import synthetic as synth  # noqa: E402
+
+PADS = (0, 0, 0, 0)
+BUILDS = [0]
+_mod = sys.modules["wav2lip_amd.face_detection.s3fd"]        # `face_detection.s3fd` is the class; this is its module
+_real = {"_Graph": _mod._Graph, "_GraphB": _mod._GraphB}
+
+
+def _counting(name):
+    def make(*a, **k):
+        BUILDS[0] += 1
+        return _real[name](*a, **k)
+    return make
+
+
+def clips_with_faces(n, seed):
+    """[frames] of filelist_bench.make_clips with a seeded saturated block in each of the 16 distinct frames"""
+    clips = make_clips(n, seed)
+    pool = []
+    for j, f in enumerate(clips[0][0][:16]):                 # clip 0 starts with the pool in order
+        g = f.copy()
+        r = np.random.default_rng([seed, j, 9])
+        h, w = r.integers(40, 80, 2)
+        y, x = r.integers(0, 160 - h), r.integers(0, 160 - w)
+        g[y:y + h, x:x + w] = 255 if j % 2 else 0
+        pool.append(g)
+    return [[pool[(i + k) % 16] for k in range(len(frames))] for i, (frames, _) in enumerate(clips)]
+
+
+def detector(dev, precision):
+    return face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False, device=str(dev),
+                                        state_dict=synth.s3fd_state_dict(), precision=precision)
+
+
+def run_packed(det, clips, batch):
+    t0 = time.perf_counter()
+    res = [b for _, b, _ in face_detection.detect_many(det, (face_detection.DetectJob(i, f) for i, f in enumerate(clips)), pads=PADS,
+                                                       T=5, batch_size=batch)]
+    torch.cuda.synchronize()
+    return res, time.perf_counter() - t0
+
+
+def run_loop(det, clips, batch):
+    t0 = time.perf_counter()
+    res = []
+    for frames in clips:
+        try:
+            res.append(np.array([c for _, c in inference.face_detect(frames, detector=det, pads=list(PADS), nosmooth=False, batch_size=batch)]))
+        except ValueError:                                  # a frame without a face
+            res.append(None)
+    torch.cuda.synchronize()
+    return res, time.perf_counter() - t0
+
+
+def stats(v):
+    return {"samples": [round(x, 1) for x in v], "median": round(float(np.median(v)), 1), "min": round(min(v), 1), "max": round(max(v), 1)}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--clips", type=int, default=200)
+    ap.add_argument("--alternations", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--precision", default="f32", choices=["f32", "bf16"])
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args(argv)
+    dev = torch.device("cuda", 0)
+    clips = clips_with_faces(a.clips, a.seed)
+    frames = sum(len(c) for c in clips)
+    _mod._Graph, _mod._GraphB = _counting("_Graph"), _counting("_GraphB")
+    out = {"clips": a.clips, "frames": frames, "batch": a.batch, "precision": a.precision, "alternations": a.alternations}
+    loops = {"packed": (run_packed, detector(dev, a.precision)), "per_clip": (run_loop, detector(dev, a.precision))}
+    res = {k: {"frames_per_s": [], "graph_builds": []} for k in loops}
+    last = {}
+
+    def one_pass(name):
+        fn, det = loops[name]
+        BUILDS[0] = 0
+        last[name], t = fn(det, clips, a.batch)
+        print("%s: %d frames, %.2f s, %d graph builds" % (name, frames, t, BUILDS[0]), file=sys.stderr, flush=True)
+        return t, BUILDS[0]
+
+    for name in loops:                                      # pass 0: warm-up
+        t, b = one_pass(name)
+        res[name].update(first_pass_s=round(t, 2), first_pass_graph_builds=b,
+                         max_memory_allocated_gb=round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2))
+    for _ in range(a.alternations):
+        for name in loops:
+            t, b = one_pass(name)
+            res[name]["frames_per_s"].append(frames / t)
+            res[name]["graph_builds"].append(b)
+    for name in loops:
+        res[name]["frames_per_s"] = stats(res[name]["frames_per_s"])
+    out.update(res)
+    both = [(p, q) for p, q in zip(last["packed"], last["per_clip"]) if p is not None and q is not None]
+    out["clips_with_boxes_in_both"] = len(both)
+    out["clips_where_only_one_path_found_faces"] = sum((p is None) != (q is None) for p, q in zip(last["packed"], last["per_clip"]))
+    out["boxes_compared"] = int(sum(len(p) for p, _ in both))
+    out["boxes_that_differ"] = int(sum((p != q).any(axis=1).sum() for p, q in both))
+    out["packed_over_per_clip_median"] = round(res["packed"]["frames_per_s"]["median"] / res["per_clip"]["frames_per_s"]["median"], 3)
+    out["ahead_by_more_than_the_spread"] = bool(res["packed"]["frames_per_s"]["min"] > res["per_clip"]["frames_per_s"]["max"])
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

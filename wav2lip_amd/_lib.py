@@ -56,6 +56,11 @@ class LseSegment(C.Structure):
     _fields_ = [("row0", C.c_int32), ("n", C.c_int32)]
 
 
+class BoxSegment(C.Structure):
+    """w2l_box_segment: one clip's rows of w2l_face_boxes_segments, 16 bytes"""
+    _fields_ = [("row0", C.c_int32), ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
+
 class MelStream(C.Structure):
     """w2l_mel_stream: one stream of w2l_mel_stream_cols, 48 bytes"""
     _fields_ = [("samples", C.c_uint64), ("first", C.c_int64), ("total", C.c_int64), ("window", C.c_uint64), ("held", C.c_int32),
@@ -99,12 +104,15 @@ SIGNATURES = {
     "w2l_crop_resize_rows_u8": (_i, [_vp, _i, _vp, _i, _vp]),
     "w2l_compose_rows_u8": (_i, [_vp, _i, _vp, _i, _vp, _i]),
     "w2l_s3fd_pack": (_i, [_vp, _ll, _vp, _vp, _i]),
+    "w2l_s3fd_pack_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _i]),
     "w2l_maxpool2x2": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i]),
     "w2l_l2norm_scale": (_i, [_vp, _ll, _i, _vp, _i, _vp, _vp, _i]),
     "w2l_s3fd_decode": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
     "w2l_s3fd_nms": (_i, [_vp, _i, _i, _vp, _f, _f, _vp, _vp, _vp, _ll]),
     "w2l_s3fd_first_rect": (_i, [_vp, _i, _i, _vp, _vp, _vp, _f, _vp, _vp]),
+    "w2l_face_boxes_segments": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "w2l_s3fd_pack_bf16": (_i, [_vp, _ll, _vp, _vp, _i]),
+    "w2l_s3fd_pack_rows_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp, _i]),
     "w2l_maxpool2x2_bf16": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i]),
     "w2l_l2norm_scale_bf16": (_i, [_vp, _ll, _i, _vp, _i, _vp, _vp, _i]),
     "w2l_s3fd_headb_create": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),

@@ -13,7 +13,9 @@ values are not comparable to the paper's); inputs are the uncompressed AVIs of c
 track, read back with `audio.load_wav(path, 16000)`; `--tmp_dir` and `--reference` are accepted and unused (nothing is unpacked to
 disk).  The network sees the lower half of a face crop, so every frame needs a face box: `--box y1 y2 x1 x2` for all frames, or
 `inference.face_detect` per clip as the filelist command runs it (no pads, smoothing on).  `--fps` is the frame rate the mel
-windows are placed at, `--face_det_precision` the detector's arithmetic.
+windows are placed at, `--face_det_precision` the detector's arithmetic.  `--packed_face_det` (off by default) detects the
+faces of successive clips in shared detector batches (`face_detection.detect_many`); scored clips, skipped clips and
+their messages stay what they are without it.
 
 One line per scored clip goes to stdout, then the reference's two lines (:49-50), averaged over the scored clips.  A clip that
 cannot be decoded, has no audio, has a frame without a face or is too short for one window is named on stderr with the reason.
@@ -50,6 +52,8 @@ def build_cli_parser():
                    help='One face box for every frame; without it the face detector runs on every clip')
     p.add_argument('--face_det_precision', default='fp32', choices=['fp32', 'bf16'],
                    help='Face detector arithmetic: fp32 (default, matches the reference) or bf16 storage')
+    p.add_argument('--packed_face_det', default=False, action='store_true',
+                   help='Detect faces of successive clips in shared detector batches (face_detection.detect_many)')
     return p
 
 
@@ -82,29 +86,42 @@ def face_crops(frames, boxes, device):
     return out
 
 
+def _read_clip(video, name, tmpdir, skip):
+    """(wav, frames uint8 [T,H,W,3]) of one clip, or None after `skip(name, why, traceback text or None)`"""
+    from .gen_videos_from_filelist import _load_audio
+    try:
+        wav, _, _ = _load_audio(video, tmpdir)
+        frames = container.read_avi(video)["frames"]
+    except KeyboardInterrupt:
+        raise
+    except Exception as e:
+        skip(name, "could not be decoded (uncompressed BGR AVI with PCM16 audio only): {}".format(e), traceback.format_exc())
+        return None
+    if len(frames) == 0:
+        skip(name, "no frames", None)
+        return None
+    return wav, frames
+
+
 def score_jobs(args, videos, device, detector, skipped):
     """the producer: one evaluation.ScoreJob per readable clip, in `videos` order; `skipped` collects the names it passes over"""
     from . import audio, inference
     from .evaluation import ScoreJob
-    from .gen_videos_from_filelist import _load_audio
+
+    def skip(name, why, trace):
+        if trace:
+            sys.stderr.write(trace)
+        _skip(name, why)
+        skipped.append(name)
+
     with tempfile.TemporaryDirectory(prefix="w2l_scores_") as tmpdir:
         for video in videos:
             name = os.path.basename(video)
             try:
-                try:
-                    wav, _, _ = _load_audio(video, tmpdir)
-                    frames = container.read_avi(video)["frames"]
-                except KeyboardInterrupt:
-                    raise
-                except Exception as e:
-                    traceback.print_exc()
-                    _skip(name, "could not be decoded (uncompressed BGR AVI with PCM16 audio only): {}".format(e))
-                    skipped.append(name)
+                got = _read_clip(video, name, tmpdir, skip)
+                if got is None:
                     continue
-                if len(frames) == 0:
-                    _skip(name, "no frames")
-                    skipped.append(name)
-                    continue
+                wav, frames = got
                 if args.box is not None:
                     boxes = inference.validate_boxes([args.box], frames.shape[1], frames.shape[2]) * len(frames)
                 else:
@@ -117,6 +134,50 @@ def score_jobs(args, videos, device, detector, skipped):
             except ValueError as e:                      # no face in a frame, a box outside its frame
                 _skip(name, str(e))
                 skipped.append(name)
+
+
+def score_jobs_packed(args, videos, device, detector, skipped):
+    """`score_jobs` with detection packed across clips (`--packed_face_det`, no `--box`): clips are read ahead, their frames go
+    through `face_detection.detect_many`, and crops + mel are made as each clip's boxes arrive.  What the reading stage has to say
+    about a clip it passes over is held back until the scorable clip after it is answered, so stderr and `skipped` read as they do
+    from `score_jobs`."""
+    from . import audio, face_detection, inference
+    from .evaluation import ScoreJob
+    held, notes, tail = {}, {}, []       # name -> (wav, frames); name -> [(name, why, trace)] due before it; after the last
+
+    def flush(items):
+        for name, why, trace in items:
+            if trace:
+                sys.stderr.write(trace)
+            _skip(name, why)
+            skipped.append(name)
+
+    def inputs(tmpdir):
+        said = []
+        for video in videos:
+            name = os.path.basename(video)
+            got = _read_clip(video, name, tmpdir, lambda *a: said.append(a))
+            if got is None:
+                continue
+            held[name] = got
+            notes[name], said = said, []
+            yield face_detection.DetectJob(name, got[1])
+        tail.extend(said)
+
+    with tempfile.TemporaryDirectory(prefix="w2l_scores_") as tmpdir:
+        for name, boxes, error in face_detection.detect_many(detector, inputs(tmpdir), pads=(0, 0, 0, 0), T=5,
+                                                             batch_size=FACE_DET_BATCH_SIZE):
+            flush(notes.pop(name))
+            wav, frames = held.pop(name)
+            try:
+                if error is not None:
+                    raise ValueError(error)
+                boxes = inference.validate_boxes(boxes, frames.shape[1], frames.shape[2])
+                yield ScoreJob(name, face_crops(frames, boxes, device), audio.melspectrogram_device(wav, device))
+            except ValueError as e:                      # no face in a frame, a box outside its frame
+                _skip(name, str(e))
+                skipped.append(name)
+        flush(tail)
 
 
 def main(argv=None, state_dict=None):
@@ -148,7 +209,8 @@ def main(argv=None, state_dict=None):
             res["key"], res["offset"], res["lse_c"], res["lse_d"], res["n"]))
         scored.append(res)
 
-    evaluation.lse_many(model, score_jobs(args, videos, device, detector, skipped), fps=args.fps, vshift=args.vshift,
+    producer = score_jobs_packed if args.packed_face_det and args.box is None else score_jobs
+    evaluation.lse_many(model, producer(args, videos, device, detector, skipped), fps=args.fps, vshift=args.vshift,
                         batch_size=args.batch_size, sink=sink)
     if not scored:
         raise SystemExit("no clip of {} could be scored ({} skipped)".format(args.data_root, len(skipped)))

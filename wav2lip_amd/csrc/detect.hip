@@ -1,11 +1,14 @@
 // S3FD face-detector glue kernels (reference face_detection/detection/sfd/): everything between the 3x3 convolutions, which
 // are the SAME fused conv launches as the generator's (conv_igemm.hip / conv_wino.hip with bias + ReLU, no BatchNorm).
 //   w2l_s3fd_pack       detect.py:57-58 + api.py:62  uint8 BGR frames -> RGB order, minus (104,117,123), fp32 NHWC4
+//   w2l_s3fd_pack_rows  the same per frame of an address table: frames of several clips in one batch, read where they lie
 //   w2l_maxpool2x2      net_s3fd.py:75,79,85,91,97   F.max_pool2d(h, 2, 2)
 //   w2l_l2norm_scale    net_s3fd.py:6-19             x / (sqrt(sum_c x^2) + 1e-10) * weight[c]
 //   w2l_s3fd_decode     net_s3fd.py:123-126 (max-out background), detect.py:66-84 (softmax, priors, decode)
 //   w2l_s3fd_nms        sfd_detector.py:39-45 gate + bbox.py:44-64 greedy NMS, bit-exact keep list
 //   w2l_s3fd_first_rect sfd_detector.py:45 + api.py:61-77  first kept box above 0.5 -> int rect, one row per image
+//   w2l_face_boxes_segments  inference.py:59-66, :90-104 / gen_videos_from_filelist.py:35-42, :61-77  pads, clipping, temporal
+//                       smoothing and "no face" of many clips in one launch
 // All HBM-bound, NHWC, float4 where the channel count allows.
 #include "w2l_common.h"
 
@@ -13,17 +16,39 @@ namespace w2l {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+__device__ __forceinline__ void s3fd_store(float* o, int y_cs, float c0, float c1, float c2) {
+    if (y_cs >= 4 && (y_cs & 3) == 0) *reinterpret_cast<f32x4*>(o) = f32x4{c0, c1, c2, 0.f};
+    else { o[0] = c0; o[1] = c1; o[2] = c2; }
+}
+
 __global__ void s3fd_pack_kernel(long long npix, const uint8_t* __restrict__ x, float* __restrict__ y, int y_cs,
                                  float m0, float m1, float m2) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x) {
-        const uint8_t* p = x + i * 3;
-        // images[..., ::-1] (api.py:62) then float64 subtraction of the per-channel mean, cast to float32 (detect.py:57-63)
-        const float c0 = (float)((double)p[2] - (double)m0);
-        const float c1 = (float)((double)p[1] - (double)m1);
-        const float c2 = (float)((double)p[0] - (double)m2);
-        float* o = y + i * y_cs;
-        if (y_cs >= 4 && (y_cs & 3) == 0) *reinterpret_cast<f32x4*>(o) = f32x4{c0, c1, c2, 0.f};
-        else { o[0] = c0; o[1] = c1; o[2] = c2; }
+        float c0, c1, c2;
+        s3fd_pixel(x + i * 3, m0, m1, m2, c0, c1, c2);
+        s3fd_store(y + i * y_cs, y_cs, c0, c1, c2);
+    }
+}
+
+// The row-table form: blockIdx.y is the image, its frame lies at frames[b].  A thread owns four consecutive pixels (12 bytes =
+// three dwords of an aligned frame); HBM-bound byte traffic, no LDS.
+__global__ void s3fd_pack_rows_kernel(int npix, const uint64_t* __restrict__ frames, float* __restrict__ y, int y_cs, float m0,
+                                      float m1, float m2) {
+    const int b = blockIdx.y;
+    const uint64_t addr = frames[b];
+    const uint8_t* x = reinterpret_cast<const uint8_t*>(addr);
+    const bool dwords = (addr & 3) == 0;
+    float* yb = y + (long long)b * npix * y_cs;
+    const int ngroups = (npix + 3) >> 2;
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += gridDim.x * blockDim.x) {
+        const int i0 = g << 2, n = min(4, npix - i0);
+        uint8_t px[12];
+        s3fd_load_group(x + (long long)i0 * 3, dwords, n, px);
+        for (int k = 0; k < n; ++k) {
+            float c0, c1, c2;
+            s3fd_pixel(px + 3 * k, m0, m1, m2, c0, c1, c2);
+            s3fd_store(yb + (long long)(i0 + k) * y_cs, y_cs, c0, c1, c2);
+        }
     }
 }
 
@@ -233,6 +258,100 @@ __global__ __launch_bounds__(64) void s3fd_first_rect_kernel(int P, const float*
     if (lane == 0) { r[0] = r[1] = r[2] = r[3] = 0; flags[b] = kRectNone; }
 }
 
+// ---- the per-clip finish of face_detect (inference.py:90-104; gen_videos_from_filelist.py:61-77 is the same code) for many
+// clips: one wave per segment = one clip's rows [row0, row0 + n) of the rect / flag arenas w2l_s3fd_first_rect filled.
+//   1. the flags: any row the device did not convert (kRectHost, or a word that is no flag at all) -> status (2, first such row):
+//      the detector would have met it before face_detect looks for None; else any kRectNone -> (1, first such row), the
+//      "Face not detected" ValueError; boxes of such a segment are zeros.
+//   2. the padded box of a row, in the output's (y1, y2, x1, x2) order: (max(0, y1 - top), min(H, y2 + bottom), max(0, x1 - left),
+//      min(W, x2 + right)) - near edges clipped at 0 and far edges at the frame ONLY, as there.
+//   3. get_smoothened_boxes (inference.py:59-66), in place and in row order: row i <= n - T is the mean of the T unsmoothed rows
+//      from i on (every row of its window comes after it), so those rows are independent and go lane by lane.  The rows after
+//      that all take Python's `boxes[n - T:]`: rows [ws, n) with ws = n - T, or for n < T the wrapped negative start
+//      max(0, 2n - T); that window holds rows already smoothed, so they run in order - one lane per coordinate (the four columns
+//      never mix) over a copy of the window in LDS.  A mean is an exact integer sum, one fp64 division, truncation towards zero:
+//      numpy's float64 mean assigned into an integer array.
+constexpr int kBoxMaxT = 64;
+struct BoxSeg { int row0, n, H, W; };
+static_assert(sizeof(BoxSeg) == 16 && sizeof(w2l_box_segment) == 16, "w2l_box_segment is 16 bytes");
+
+__device__ __forceinline__ int padded_coord(const int* r, int c, const BoxSeg& s, int top, int bottom, int left, int right) {
+    long long v;
+    if (c == 0) v = max(0ll, (long long)r[1] - top);
+    else if (c == 1) v = min((long long)s.H, (long long)r[3] + bottom);
+    else if (c == 2) v = max(0ll, (long long)r[0] - left);
+    else v = min((long long)s.W, (long long)r[2] + right);
+    return (int)v;
+}
+
+__device__ __forceinline__ int trunc_mean(long long sum, int len) { return (int)((double)sum / (double)len); }
+
+__global__ __launch_bounds__(64) void face_boxes_segments_kernel(const BoxSeg* __restrict__ segs, const int* __restrict__ rects,
+                                                                 const int* __restrict__ flags, int top, int bottom, int left,
+                                                                 int right, int T, int* __restrict__ boxes, int* __restrict__ status) {
+    __shared__ int s_win[kBoxMaxT][4];
+    const int lane = threadIdx.x;
+    const BoxSeg s = segs[blockIdx.x];
+    int* st = status + 2 * (long long)blockIdx.x;
+    const int n = s.n;
+    if (n <= 0) {                                        // uniform
+        if (lane == 0) { st[0] = 0; st[1] = 0; }
+        return;
+    }
+    const int* fl = flags + s.row0;
+    const int* rc = rects + (long long)s.row0 * 4;
+    int* bx = boxes + (long long)s.row0 * 4;
+    int first_host = 0x7fffffff, first_none = 0x7fffffff;
+    for (int i = lane; i < n; i += 64) {
+        const int f = fl[i];
+        if (f == kRectNone) first_none = min(first_none, i);
+        else if (f != kRectFound) first_host = min(first_host, i);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        first_host = min(first_host, __shfl_xor(first_host, o));
+        first_none = min(first_none, __shfl_xor(first_none, o));
+    }
+    if (first_host != 0x7fffffff || first_none != 0x7fffffff) {      // uniform after the butterfly
+        for (int i = lane; i < 4 * n; i += 64) bx[i] = 0;
+        if (lane == 0) {
+            st[0] = first_host != 0x7fffffff ? 2 : 1;
+            st[1] = first_host != 0x7fffffff ? first_host : first_none;
+        }
+        return;
+    }
+    if (lane == 0) { st[0] = 0; st[1] = 0; }
+    if (T == 0) {
+        for (int i = lane; i < 4 * n; i += 64) bx[i] = padded_coord(rc + (i >> 2) * 4, i & 3, s, top, bottom, left, right);
+        return;
+    }
+    const int ws = n >= T ? n - T : max(0, 2 * n - T);       // first row of Python's boxes[n - T:]
+    const int L = n - ws;                                    // 1 <= L <= T <= kBoxMaxT
+    const int seq0 = n >= T ? n - T : 0;                     // rows from here on run in order
+    for (int i = lane; i < seq0; i += 64) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            long long sum = 0;
+            for (int j = 0; j < T; ++j) sum += padded_coord(rc + (long long)(i + j) * 4, c, s, top, bottom, left, right);
+            bx[(long long)i * 4 + c] = trunc_mean(sum, T);
+        }
+    }
+    if (lane < L) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) s_win[lane][c] = padded_coord(rc + (long long)(ws + lane) * 4, c, s, top, bottom, left, right);
+    }
+    __syncthreads();
+    if (lane < 4) {
+        const int c = lane;
+        for (int i = seq0; i < n; ++i) {
+            long long sum = 0;
+            for (int j = 0; j < L; ++j) sum += s_win[j][c];
+            const int m = trunc_mean(sum, L);
+            if (i >= ws) s_win[i - ws][c] = m;
+            bx[(long long)i * 4 + c] = m;
+        }
+    }
+}
+
 static inline int grid1d(long long work, int block, int cap = 16384) {
     long long g = (work + block - 1) / block;
     if (g > cap) g = cap;
@@ -251,6 +370,18 @@ int w2l_s3fd_pack(void* stream, long long npix, const uint8_t* bgr, float* y, in
     W2L_REQUIRE((y_cs & 3) != 0 || (reinterpret_cast<uintptr_t>(y) & 15) == 0, "s3fd_pack: y must be 16-byte aligned");
     hipLaunchKernelGGL(s3fd_pack_kernel, dim3(grid1d(npix, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), npix, bgr, y,
                        y_cs, 104.f, 117.f, 123.f);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_s3fd_pack_rows(void* stream, int B, int H, int W, const uint64_t* frames, float* y, int y_cs) {
+    W2L_REQUIRE(frames && y && B >= 1 && H >= 1 && W >= 1 && y_cs >= 3, "bad s3fd_pack_rows arguments");
+    W2L_REQUIRE(B <= 65535 && (long long)H * W <= (1ll << 29), "s3fd_pack_rows: B <= 65535 and H * W <= 2^29");
+    W2L_REQUIRE((reinterpret_cast<uintptr_t>(frames) & 7) == 0, "s3fd_pack_rows: the address table must be 8-byte aligned");
+    W2L_REQUIRE((y_cs & 3) != 0 || (reinterpret_cast<uintptr_t>(y) & 15) == 0, "s3fd_pack_rows: y must be 16-byte aligned");
+    const int npix = H * W;
+    hipLaunchKernelGGL(s3fd_pack_rows_kernel, dim3(grid1d((npix + 3) / 4, 256, 1024), B), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), npix, frames, y, y_cs, 104.f, 117.f, 123.f);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }
@@ -311,6 +442,18 @@ int w2l_s3fd_first_rect(void* stream, int B, int P, const float* table, const in
     W2L_REQUIRE((long long)B * P * 5 < (1ll << 31), "s3fd_first_rect: table too large");
     hipLaunchKernelGGL(s3fd_first_rect_kernel, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), P, table, keep, counts,
                        thresh, rects, flags);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_face_boxes_segments(void* stream, int n_seg, const w2l_box_segment* segs, const int32_t* rects, const int32_t* flags,
+                            int top, int bottom, int left, int right, int T, int32_t* boxes, int32_t* status) {
+    W2L_REQUIRE(segs && rects && flags && boxes && status, "face_boxes_segments: NULL argument");
+    W2L_REQUIRE(n_seg >= 1, "face_boxes_segments: n_seg=%d must be at least 1", n_seg);
+    W2L_REQUIRE(T >= 0 && T <= kBoxMaxT, "face_boxes_segments: T=%d outside 0..%d", T, kBoxMaxT);
+    W2L_REQUIRE((reinterpret_cast<uintptr_t>(segs) & 15) == 0, "face_boxes_segments: the segment table must be 16-byte aligned");
+    hipLaunchKernelGGL(face_boxes_segments_kernel, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const BoxSeg*>(segs), rects, flags, top, bottom, left, right, T, boxes, status);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

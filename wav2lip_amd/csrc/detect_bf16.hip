@@ -1,6 +1,7 @@
 // The S3FD face detector's glue on the opt-in bf16-storage path (face_detection/s3fd.py _GraphB): the ops between the backbone
 // convolutions, which are w2l_convb launches (bias as the fp32 shift, ReLU), and the fused detection head.
 //   w2l_s3fd_pack_bf16       detect.py:57-58 + api.py:62  uint8 BGR -> RGB minus (104,117,123), bf16 NHWC (integers: exact)
+//   w2l_s3fd_pack_rows_bf16  the same per frame of an address table (frames of several clips in one batch, read in place)
 //   w2l_maxpool2x2_bf16      net_s3fd.py:75,79,85,91,97   F.max_pool2d(h, 2, 2) on bf16 (max is exact)
 //   w2l_l2norm_scale_bf16    net_s3fd.py:6-19             sum of squares in fp32, one rounding on the store
 //   w2l_s3fd_headb_*         net_s3fd.py:99-120 (conf + loc convolutions of one level) + net_s3fd.py:123-126 + detect.py:66-84:
@@ -39,12 +40,38 @@ __global__ void s3fd_pack_bf16_kernel(long long npix, const uint8_t* __restrict_
         for (int e = 0; e < 8; ++e) o[e] = (__bf16)0.f;
         if (g == 0) {
             // the fp32 pack's values (w2l_s3fd_pack): integers with |v| <= 152, exact in bf16
-            const uint8_t* p = x + pix * 3;
-            o[0] = (__bf16)(float)((double)p[2] - 104.0);
-            o[1] = (__bf16)(float)((double)p[1] - 117.0);
-            o[2] = (__bf16)(float)((double)p[0] - 123.0);
+            float c0, c1, c2;
+            s3fd_pixel(x + pix * 3, 104.f, 117.f, 123.f, c0, c1, c2);
+            o[0] = (__bf16)c0; o[1] = (__bf16)c1; o[2] = (__bf16)c2;
         }
         *reinterpret_cast<bf16x8*>(y + pix * y_cs + g * 8) = o;
+    }
+}
+
+// The row-table form (s3fd_pack_rows_kernel of detect.hip): blockIdx.y is the image, a thread owns four consecutive pixels and
+// writes every 8-channel group of each (group 0: the pixel, the rest zeros)
+__global__ void s3fd_pack_rows_bf16_kernel(int npix, const uint64_t* __restrict__ frames, __bf16* __restrict__ y, int y_cs) {
+    const int b = blockIdx.y;
+    const uint64_t addr = frames[b];
+    const uint8_t* x = reinterpret_cast<const uint8_t*>(addr);
+    const bool dwords = (addr & 3) == 0;
+    __bf16* yb = y + (long long)b * npix * y_cs;
+    const int ngroups = (npix + 3) >> 2, groups = y_cs >> 3;
+    for (int g4 = blockIdx.x * blockDim.x + threadIdx.x; g4 < ngroups; g4 += gridDim.x * blockDim.x) {
+        const int i0 = g4 << 2, n = min(4, npix - i0);
+        uint8_t px[12];
+        s3fd_load_group(x + (long long)i0 * 3, dwords, n, px);
+        for (int k = 0; k < n; ++k) {
+            float c0, c1, c2;
+            s3fd_pixel(px + 3 * k, 104.f, 117.f, 123.f, c0, c1, c2);
+            bf16x8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (__bf16)0.f;
+            __bf16* op = yb + (long long)(i0 + k) * y_cs;
+            for (int g = 1; g < groups; ++g) *reinterpret_cast<bf16x8*>(op + g * 8) = o;
+            o[0] = (__bf16)c0; o[1] = (__bf16)c1; o[2] = (__bf16)c2;
+            *reinterpret_cast<bf16x8*>(op) = o;
+        }
     }
 }
 
@@ -232,6 +259,19 @@ int w2l_s3fd_pack_bf16(void* stream, long long npix, const uint8_t* bgr, void* y
     W2L_REQUIRE(npix * y_cs * 2 < kLim2G, "s3fd_pack_bf16: buffer larger than 2 GiB: split the batch");
     hipLaunchKernelGGL(s3fd_pack_bf16_kernel, dim3(grid1db(npix * (y_cs / 8), 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        npix, bgr, static_cast<__bf16*>(y), y_cs);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_s3fd_pack_rows_bf16(void* stream, int B, int H, int W, const uint64_t* frames, void* y, int y_cs) {
+    W2L_REQUIRE(frames && y && B >= 1 && H >= 1 && W >= 1 && y_cs >= 8 && (y_cs & 7) == 0, "bad s3fd_pack_rows_bf16 arguments (y_cs %% 8 == 0)");
+    W2L_REQUIRE(B <= 65535 && (long long)H * W <= (1ll << 29), "s3fd_pack_rows_bf16: B <= 65535 and H * W <= 2^29");
+    W2L_REQUIRE((reinterpret_cast<uintptr_t>(frames) & 7) == 0, "s3fd_pack_rows_bf16: the address table must be 8-byte aligned");
+    W2L_REQUIRE((reinterpret_cast<uintptr_t>(y) & 15) == 0, "s3fd_pack_rows_bf16: y must be 16-byte aligned");
+    W2L_REQUIRE((long long)B * H * W * y_cs * 2 < kLim2G, "s3fd_pack_rows_bf16: buffer larger than 2 GiB: split the batch");
+    const int npix = H * W;
+    hipLaunchKernelGGL(s3fd_pack_rows_bf16_kernel, dim3(grid1db((npix + 3) / 4, 256, 1024), B), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), npix, frames, static_cast<__bf16*>(y), y_cs);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

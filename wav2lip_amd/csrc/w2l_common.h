@@ -58,6 +58,29 @@ __device__ __forceinline__ float shifted_pdist_wave(const float* __restrict__ a,
     return sqrtf(s);
 }
 
+// The S3FD detector's input pixel: one BGR byte triple -> RGB order (api.py:62 `images[..., ::-1]`) minus the per-channel mean in
+// float64, cast to float32 (detect.py:57-63).  Every pack kernel calls it - s3fd_pack_kernel / s3fd_pack_rows_kernel (detect.hip) and
+// their bf16 forms (detect_bf16.hip) - so that the frame-batch and the row-table forms agree byte for byte.
+__device__ __forceinline__ void s3fd_pixel(const uint8_t* bgr, float m0, float m1, float m2, float& c0, float& c1, float& c2) {
+    c0 = (float)((double)bgr[2] - (double)m0);
+    c1 = (float)((double)bgr[1] - (double)m1);
+    c2 = (float)((double)bgr[0] - (double)m2);
+}
+
+// `npx` (1..4) consecutive pixels of a u8 [.,3] frame at `p` into px[12]: three dword loads when the frame is 4-byte aligned (a
+// group of four pixels is 12 bytes, so every full group of an aligned frame is aligned too), bytes otherwise and for the frame's
+// last, shorter group.  Nothing outside the npx pixels is read.
+__device__ __forceinline__ void s3fd_load_group(const uint8_t* __restrict__ p, bool dwords, int npx, uint8_t px[12]) {
+    if (dwords && npx == 4) {
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+        const uint32_t v[3] = {q[0], q[1], q[2]};
+#pragma unroll
+        for (int k = 0; k < 12; ++k) px[k] = (uint8_t)(v[k >> 2] >> (8 * (k & 3)));
+    } else {
+        for (int k = 0; k < 3 * npx; ++k) px[k] = p[k];
+    }
+}
+
 // Workgroup ids are dealt round-robin to the 8 XCDs (id % 8), each with its own L2.  This maps the hardware id to a
 // logical id such that every XCD walks one CONTIGUOUS range of logical ids: neighbouring tiles (which share input halos
 // and A/B operand tiles) then meet in the same L2 instead of being fetched from HBM once per XCD.

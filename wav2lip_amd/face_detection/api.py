@@ -72,6 +72,23 @@ class FaceAlignment:
         keep, counts = nms_batch(table, 0.05, 0.3)
         return table, keep, counts
 
+    def rects_for_rows(self, frames, B, H, W, rects, flags, offset):
+        """`get_detections_for_batch` for the B frames of a device address table (`s3fd.dense_boxes_rows`), left on the device:
+        rows [offset, offset + B) of the int32 arenas `rects` [R,4] = (x1, y1, x2, y2) and `flags` [R] receive what
+        `w2l_s3fd_first_rect` writes.  No host read: an image whose NMS overflowed is flagged RECT_HOST like any other the device
+        does not decide (face_detection/many.py re-runs that clip through `inference.face_detect`)."""
+        from .._lib import check, current_stream, load
+        if (rects.dtype != torch.int32 or flags.dtype != torch.int32 or not rects.is_contiguous() or not flags.is_contiguous()
+                or rects.dim() != 2 or rects.shape[1] != 4 or flags.dim() != 1 or flags.shape[0] != rects.shape[0]
+                or offset < 0 or offset + B > rects.shape[0]):
+            raise ValueError("rects_for_rows: int32 arenas [R,4] and [R] with rows [%d, %d) inside them" % (offset, offset + B))
+        with torch.no_grad():
+            levels = self.face_detector.dense_boxes_rows(frames, B, H, W, precision=self.precision)
+            table = torch.cat(levels, dim=1).contiguous()
+            keep, counts = nms_batch(table, 0.05, 0.3, host_overflow=False)
+            check(load().w2l_s3fd_first_rect(current_stream(), B, table.shape[1], table.data_ptr(), keep.data_ptr(), counts.data_ptr(),
+                                             0.5, rects.data_ptr() + 16 * offset, flags.data_ptr() + 4 * offset), "s3fd_first_rect")
+
     def get_detections_for_batch(self, images):
         """api.py:61-77 (the BGR->RGB flip of :62 happens inside the device pack kernel).  The rect of every image comes from one
         launch (`w2l_s3fd_first_rect`) and one copy back per batch; an image the device flags (a non-finite or huge coordinate)

@@ -1,0 +1,242 @@
+"""`inference.face_detect` for many clips in shared detector batches.
+
+The evaluation commands call `face_detect` once per clip (evaluation/gen_videos_from_filelist.py:44-77 is the reference's copy of
+inference.py:68-104): every clip uploads its own batches, ends in a ragged batch of its own - another detector graph - and waits for
+the device twice per batch.  Frames are independent given the weights, so here the frames of successive clips are the rows of
+detector batches of ONE size:
+
+    per group of clips of one frame shape
+        one pinned staging buffer  [frame address table][segment table][the frames that were host arrays]  -> one copy to the device
+        batches of exactly `batch_size` addresses   w2l_s3fd_pack_rows -> S3FD -> gate + NMS -> w2l_s3fd_first_rect
+                                                    (rects and flags land in the rows of the group's arenas; no host read)
+        one launch                                  w2l_face_boxes_segments: pads, clipping, smoothing, "no face" per clip
+        one copy back                               boxes [R,4] + status [clips,2]
+
+The last batch of a group is padded with copies of its last address; those rects fall into scratch rows behind the arena.  A run
+over clips of one frame shape therefore builds one detector graph.
+"""
+import collections
+
+import numpy as np
+import torch
+
+# numpy mirror of w2l_box_segment (16 bytes); the ctypes mirror is _lib.BoxSegment
+BOX_SEGMENT = np.dtype([("row0", "<i4"), ("n", "<i4"), ("H", "<i4"), ("W", "<i4")])
+MAX_T = 64           # w2l_face_boxes_segments' largest smoothing window
+NO_FACE = 'Face not detected! Ensure the video contains a face in all the frames.'      # inference.py:89
+
+DetectJob = collections.namedtuple("DetectJob", "key frames")
+DetectJob.__doc__ = """one clip to detect faces in: `frames` a sequence of uint8 [H,W,3] BGR host arrays of one shape, or one uint8 device
+tensor [T,H,W,3] (read where it lies)"""
+
+_Clip = collections.namedtuple("_Clip", "key frames n H W nbytes")
+
+
+def _align(n):
+    return (n + 15) // 16 * 16
+
+
+def host_boxes(rects, H, W, pads, T):
+    """the finish of `face_detect` (inference.py:90-104) on the host: rects [(x1, y1, x2, y2)] of one clip of H x W frames ->
+    int array [n,4] of (y1, y2, x1, x2).  What w2l_face_boxes_segments computes per segment."""
+    from ..inference import get_smoothened_boxes
+    top, bottom, left, right = pads
+    boxes = np.array([[max(0, r[1] - top), min(H, r[3] + bottom), max(0, r[0] - left), min(W, r[2] + right)] for r in rects],
+                     dtype=np.int64).reshape(-1, 4)
+    if T:
+        boxes = get_smoothened_boxes(boxes, T=T)
+    return boxes
+
+
+def _checked(job):
+    """a DetectJob as a _Clip: frames a contiguous uint8 [T,H,W,3] tensor or a list of contiguous uint8 [H,W,3] arrays of one shape;
+    a ValueError names the job"""
+    frames = job.frames
+    try:
+        if isinstance(frames, torch.Tensor):
+            if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+                raise ValueError("a frame tensor must be uint8 [T,H,W,3], got %s %s" % (frames.dtype, tuple(frames.shape)))
+            frames = frames.contiguous()
+            n, H, W = (int(v) for v in frames.shape[:3])
+        else:
+            frames = [np.ascontiguousarray(f) for f in frames]
+            for f in frames:
+                if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape != frames[0].shape:
+                    raise ValueError("frames must be uint8 [H,W,3] arrays of one shape, got %s %s" % (f.dtype, f.shape))
+            n = len(frames)
+            H, W = (int(v) for v in frames[0].shape[:2]) if n else (0, 0)
+        if n and (H < 1 or W < 1):
+            raise ValueError("empty frames (%d x %d)" % (H, W))
+    except ValueError as e:
+        raise ValueError("job %r: %s" % (job.key, e)) from None
+    return _Clip(job.key, frames, n, H, W, n * H * W * 3)
+
+
+def _detect_batch(detector, frames, B, H, W, rects, flags, offset):
+    """one detector batch: rows [offset, offset + B) of the arenas from the B addresses of `frames`"""
+    detector.rects_for_rows(frames, B, H, W, rects, flags, offset)
+
+
+def _finish_segments(n_seg, segs, rects, flags, pads, T, boxes, status):
+    """w2l_face_boxes_segments: the group's clips in one launch"""
+    from .._lib import check, current_stream, load, ptr
+    top, bottom, left, right = pads
+    check(load().w2l_face_boxes_segments(current_stream(), n_seg, ptr(segs), ptr(rects), ptr(flags), top, bottom, left, right, T,
+                                         ptr(boxes), ptr(status)), "face_boxes_segments")
+
+
+def _detect_group(detector, clips, pads, T, batch_size):
+    """One group on the device.  clips: _Clips of one frame shape, each with at least one frame.  Returns numpy (boxes int32 [R,4]
+    in (y1, y2, x1, x2) order, rows in clip order; status int32 [clips,2])."""
+    dev = torch.device(detector.device)
+    H, W = clips[0].H, clips[0].W
+    R = sum(c.n for c in clips)
+    padded = (R + batch_size - 1) // batch_size * batch_size
+    # ---- one staging buffer: [address table, `padded` entries][segment table][host frames of the group]
+    seg_off = _align(padded * 8)
+    off = _align(seg_off + len(clips) * BOX_SEGMENT.itemsize)
+    frame_off = []
+    for c in clips:
+        if isinstance(c.frames, torch.Tensor):
+            frame_off.append(None)
+        else:
+            frame_off.append(off)
+            off = _align(off + c.nbytes)
+    pinned = dev.type == "cuda"
+    host = torch.empty(off, dtype=torch.uint8, pin_memory=pinned)
+    stage_dev = torch.empty(off, dtype=torch.uint8, device=dev)
+    stage = host.numpy()
+    addr = stage[:padded * 8].view("<u8")
+    segs = stage[seg_off:seg_off + len(clips) * BOX_SEGMENT.itemsize].view(BOX_SEGMENT)
+    frame_bytes = H * W * 3
+    r = 0
+    for k, c in enumerate(clips):
+        if frame_off[k] is None:
+            base = c.frames.data_ptr()
+        else:
+            dst = stage[frame_off[k]:frame_off[k] + c.nbytes].reshape(c.n, H, W, 3)
+            for i, f in enumerate(c.frames):
+                dst[i] = f
+            base = stage_dev.data_ptr() + frame_off[k]
+        addr[r:r + c.n] = np.uint64(base) + np.arange(c.n, dtype=np.uint64) * np.uint64(frame_bytes)
+        segs[k] = (r, c.n, H, W)
+        r += c.n
+    addr[R:] = addr[R - 1]
+    stage_dev.copy_(host, non_blocking=pinned)
+    rects = torch.empty((padded, 4), dtype=torch.int32, device=dev)            # rows [R, padded): the scratch tail
+    flags = torch.empty((padded,), dtype=torch.int32, device=dev)
+    for lo in range(0, padded, batch_size):
+        _detect_batch(detector, stage_dev[lo * 8:(lo + batch_size) * 8], batch_size, H, W, rects, flags, lo)
+    out = torch.empty(4 * R + 2 * len(clips), dtype=torch.int32, device=dev)    # boxes [R][4], then status [clips][2]: one copy back
+    _finish_segments(len(clips), stage_dev[seg_off:seg_off + len(clips) * BOX_SEGMENT.itemsize], rects, flags, pads, T, out[:4 * R],
+                     out[4 * R:])
+    res = out.cpu().numpy()                      # the group's one copy back; it also ends the stream's use of the staging buffers
+    return res[:4 * R].reshape(R, 4), res[4 * R:].reshape(len(clips), 2)
+
+
+def _per_clip(detector, clip, pads, T, batch_size):
+    """one clip alone through `inference.face_detect` (batch by batch uploads, the host rules): (key, boxes, error)"""
+    from .. import inference
+    frames = list(clip.frames.cpu().numpy()) if isinstance(clip.frames, torch.Tensor) else list(clip.frames)
+    try:
+        if T in (0, 5):
+            det = inference.face_detect(frames, detector=detector, pads=list(pads), nosmooth=(T == 0), batch_size=batch_size)
+            boxes = np.array([c for _, c in det], dtype=np.int64).reshape(-1, 4)
+        else:                                    # face_detect's window is 5: its two halves with another T
+            rects = inference._detect_rects(frames, detector, batch_size)
+            if any(r is None for r in rects):
+                raise ValueError(NO_FACE)
+            boxes = host_boxes(rects, clip.H, clip.W, pads, T)
+    except (ValueError, OverflowError) as e:     # no face; a coordinate int() refuses
+        return clip.key, None, str(e)
+    return clip.key, boxes, None
+
+
+def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_batches=16, max_group_bytes=1 << 30):
+    """`inference.face_detect(frames, detector, pads, nosmooth=(T == 0))` for every `DetectJob` of the iterable `jobs`, the frames
+    of successive clips packed into detector batches of exactly `batch_size`.  A generator: jobs are consumed lazily and one
+    `(key, boxes, error)` comes out per job, in job order - `boxes` the int array [n,4] of (y1, y2, x1, x2) `face_detect` returns
+    as coords and `error` None, or `boxes` None and `error` the text of the ValueError `face_detect` raises (a frame without a
+    face).  `T` is the smoothing window (`get_smoothened_boxes`; the reference uses 5), 0 for none.
+
+    A group takes consecutive jobs of one frame shape; it closes once it holds `group_batches * batch_size` frames, before a job
+    that would take its frames past `max_group_bytes` or has another shape (that one job has been read by then), or when the
+    iterator ends, and always holds at least one job.  The group is detected (see the module text), its results are yielded and
+    it is released before more jobs are read: the memory alive is one group plus the job that closed it.  A single job larger
+    than `max_group_bytes` goes through `inference.face_detect` on its own (batch by batch uploads), and so does a clip with a
+    frame the device does not decide (RECT_HOST: a non-finite or huge coordinate, an NMS overflow); that call's result, or the
+    text of its ValueError, is the job's.
+
+    A RuntimeError of the detector (out of device memory on a large frame) halves `batch_size` for the rest of the run, prints
+    the reference's message and runs the group again; at 1 it raises the reference's error (inference.py:75-88)."""
+    if batch_size < 1 or group_batches < 1:
+        raise ValueError("batch_size and group_batches must be at least 1")
+    if not 0 <= int(T) <= MAX_T:
+        raise ValueError("T must be in 0..%d" % MAX_T)
+    pads = tuple(int(p) for p in pads)
+    if len(pads) != 4:
+        raise ValueError("pads must be (top, bottom, left, right)")
+    T = int(T)
+    it = iter(jobs)
+    held, ended = None, False           # the job read but not yet placed
+    while not ended or held is not None:
+        group, shape, n_frames, n_bytes = [], None, 0, 0
+        while True:
+            if held is None:
+                try:
+                    held = _checked(next(it))
+                except StopIteration:
+                    ended = True
+                    break
+            c = held
+            if c.n == 0:                                   # nothing to detect: answered in its place
+                group.append(c)
+                held = None
+                continue
+            if c.nbytes > max_group_bytes:
+                if group:
+                    break                                  # the jobs before it first
+                held = None
+                yield _per_clip(detector, c, pads, T, batch_size)
+                del c
+                continue
+            if shape is not None and ((c.H, c.W) != shape or n_bytes + c.nbytes > max_group_bytes):
+                break
+            group.append(c)
+            held = None
+            shape, n_frames, n_bytes = (c.H, c.W), n_frames + c.n, n_bytes + c.nbytes
+            del c
+            if n_frames >= group_batches * batch_size:
+                break
+        if not group:
+            continue
+        clips = [c for c in group if c.n]
+        boxes = status = None
+        while clips:
+            try:
+                boxes, status = _detect_group(detector, clips, pads, T, batch_size)
+                break
+            except RuntimeError:
+                if batch_size == 1:
+                    raise RuntimeError('Image too big to run face detection on GPU. Please use the --resize_factor argument')
+                batch_size //= 2
+                print('Recovering from OOM error; New batch size: {}'.format(batch_size))
+        results, row, k = [], 0, 0
+        for c in group:
+            if c.n == 0:
+                results.append((c.key, np.zeros((0, 4), np.int64), None))
+                continue
+            code = int(status[k][0])                       # status[k][1]: the frame that decided it
+            if code == 0:
+                results.append((c.key, boxes[row:row + c.n].astype(np.int64), None))
+            elif code == 1:
+                results.append((c.key, None, NO_FACE))
+            else:
+                results.append(c)                          # the device left a frame to the host: the clip alone, below
+            row += c.n
+            k += 1
+        group = clips = None                               # released before the results go out (a re-run keeps its own clip)
+        del c
+        while results:
+            res = results.pop(0)
+            yield _per_clip(detector, res, pads, T, batch_size) if isinstance(res, _Clip) else res

@@ -375,10 +375,33 @@ class s3fd(nn.Module):
         return g.decode()
 
 
-def nms_batch(table, gate, thresh):
+    def dense_boxes_rows(self, frames, B, H, W, precision="f32"):
+        """`dense_boxes` for B frames named by a device address table: `frames` is a device tensor holding B uint64 addresses, each
+        of pixel (0,0) of a uint8 [H,W,3] BGR frame in device memory at any byte alignment (`w2l_s3fd_pack_rows`); the frames of a
+        batch need not be neighbours, nor of one clip.  Same graph, same launches and the same tables as `dense_boxes` on the
+        gathered frames."""
+        from ..models.wav2lip import check_precision
+        check_precision(precision)
+        engine.require_cuda(frames, "frame address table")
+        if frames.numel() * frames.element_size() < 8 * B or frames.data_ptr() % 8:
+            raise RuntimeError("dense_boxes_rows: the table must hold %d 8-byte aligned addresses" % B)
+        g = self._graph(B, H, W, frames.device, precision)
+        if precision == "bf16":
+            check(load().w2l_s3fd_pack_rows_bf16(current_stream(), B, H, W, ptr(frames), ptr(g.x_in), 8), "s3fd_pack_rows_bf16")
+            return g.run()
+        check(load().w2l_s3fd_pack_rows(current_stream(), B, H, W, ptr(frames), ptr(g.x_in), 4), "s3fd_pack_rows")
+        g.run()
+        return g.decode()
+
+
+def nms_batch(table, gate, thresh, host_overflow=True):
     """sfd_detector.py:39-45 + bbox.py:44-64 on the device for a batch: table = torch float32 [B, P, 5] (x1, y1, x2, y2, score)
     on the HIP device; per image the rows with score > gate compete (`w2l_s3fd_nms`).  Returns (keep int32 [B, P], counts int32
-    [B]): keep[b, :counts[b]] are the kept row indices of image b, best score first."""
+    [B]): keep[b, :counts[b]] are the kept row indices of image b, best score first.
+
+    `host_overflow=False` leaves out the one host read of `counts` and the host pass it may start: an image whose survivors of
+    the gate overflowed the device pass keeps counts = -1, which `w2l_s3fd_first_rect` flags RECT_HOST - the caller decides that
+    image later (face_detection/many.py re-runs its clip), and nothing waits for the device here."""
     engine.require_cuda(table, "box table")
     if table.dtype != torch.float32 or table.dim() != 3 or table.shape[2] != 5:
         raise RuntimeError("nms_batch: table must be float32 [B, P, 5]")
@@ -389,6 +412,8 @@ def nms_batch(table, gate, thresh):
     scratch = torch.empty((B * P * 12 + 8,), device=table.device, dtype=torch.uint8)
     check(load().w2l_s3fd_nms(current_stream(), B, P, ptr(table), float(gate), float(thresh), ptr(keep), ptr(counts),
                               ptr(scratch), scratch.numel()), "s3fd_nms")
+    if not host_overflow:
+        return keep, counts
     over = (counts < 0).nonzero().flatten().tolist()
     for b in over:
         # more rows above the gate than the device pass holds (> 262 144: a multi-megapixel frame with a permissive gate): this

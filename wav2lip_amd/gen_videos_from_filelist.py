@@ -22,7 +22,10 @@ than mel chunks (:195) or a frame has no face (:200-203); every skip names its r
 for one full 16-column window is skipped too: the reference would fail there on an unbound `out` (:229), no batch having opened
 the writer.  Detection is `inference.face_detect` per clip: pads from `--pads`, smoothing always on with T = 5 (:74).
 
-Two flags the reference does not have, as in `inference.main`: `--precision` and `--face_det_precision`.  Under
+Two flags the reference does not have, as in `inference.main`: `--precision` and `--face_det_precision`.  A third,
+`--packed_face_det` (off by default), runs detection through `face_detection.detect_many`: the frames of successive clips share
+detector batches of `--face_det_batch_size`, the per-clip finish runs once per group on the device, and lines, skip messages and
+written files stay what they are without it.  Under
 torch.distributed.run rank r takes the lines i with i % WORLD_SIZE == r and writes its own result files; no collectives.
 """
 import argparse
@@ -60,8 +63,18 @@ def build_cli_parser():
     return p
 
 
+def build_main_parser():
+    """what `main()` parses: `build_cli_parser` plus `--packed_face_det`, which changes how the work is scheduled and nothing of
+    what is computed (`cli_parser` stays the surface whose every flag changes arithmetic or is the reference's)"""
+    p = build_cli_parser()
+    p.add_argument('--packed_face_det', default=False, action='store_true',
+                   help='Detect faces of successive clips in shared detector batches (face_detection.detect_many)')
+    return p
+
+
 parser = build_parser()
 cli_parser = build_cli_parser()
+main_parser = build_main_parser()
 fps = 25                  # gen_videos_from_filelist.py:120
 
 
@@ -70,8 +83,12 @@ def lines_of_rank(lines, ranks):
     return [(i, line) for i, line in enumerate(lines) if i % ranks.world == ranks.rank]
 
 
+def _skip_text(idx, line, why):
+    return "line {} ({}): skipped: {}\n".format(idx, line.strip(), why)
+
+
 def _skip(idx, line, why):
-    print("line {} ({}): skipped: {}".format(idx, line.strip(), why), file=sys.stderr)
+    sys.stderr.write(_skip_text(idx, line, why))
 
 
 def _load_audio(audio_src, tmpdir):
@@ -91,39 +108,49 @@ def _load_audio(audio_src, tmpdir):
     return audio.load_wav(temp_audio, 16000), pcm, int(a["audio_sr"])
 
 
+def _read_line(args, idx, line, ranks, tmpdir, say):
+    """everything of one line up to detection: (frames truncated to the chunk count, mel, PCM16 audio, rate), or None after
+    `say(text)` has been given the stderr text of the reason"""
+    import torch
+    from . import audio, multiclip
+    audio_src, video = line.strip().split()
+    audio_src = os.path.join(args.data_root, audio_src) + '.avi'
+    video = os.path.join(args.data_root, video) + '.avi'
+    try:
+        wav, pcm, sr = _load_audio(audio_src, tmpdir)
+        clip = container.read_avi(video)
+    except KeyboardInterrupt:
+        raise
+    except Exception:
+        say(traceback.format_exc())
+        say(_skip_text(idx, line, "an input could not be decoded (uncompressed BGR AVI with PCM16 audio only)"))
+        return None
+    mel = audio.melspectrogram_device(wav, ranks.device)
+    if bool(torch.isnan(mel).any()):
+        say(_skip_text(idx, line, "the mel spectrogram contains NaN"))
+        return None
+    n_chunks = len(multiclip.filelist_chunk_starts(mel.shape[1]))
+    if n_chunks == 0:
+        say(_skip_text(idx, line, "the audio is shorter than one 16-column mel window"))
+        return None
+    full_frames = list(clip["frames"])
+    if len(full_frames) < n_chunks:
+        say(_skip_text(idx, line, "the video has fewer frames ({}) than mel chunks ({})".format(len(full_frames), n_chunks)))
+        return None
+    return full_frames[:n_chunks], mel, pcm, sr
+
+
 def clip_jobs(args, lines, ranks, detector, tracks):
     """the producer: one multiclip.ClipJob per runnable line of this rank, in line order.  `tracks[line index]` receives
     (frame size (w, h), PCM16 audio, rate) for the sink that opens the line's writer."""
-    import torch
-    from . import audio, inference, multiclip
+    from . import inference, multiclip
     with tempfile.TemporaryDirectory(prefix="w2l_filelist_") as tmpdir:
         for idx, line in lines_of_rank(lines, ranks):
             try:
-                audio_src, video = line.strip().split()
-                audio_src = os.path.join(args.data_root, audio_src) + '.avi'
-                video = os.path.join(args.data_root, video) + '.avi'
-                try:
-                    wav, pcm, sr = _load_audio(audio_src, tmpdir)
-                    clip = container.read_avi(video)
-                except KeyboardInterrupt:
-                    raise
-                except Exception:
-                    traceback.print_exc()
-                    _skip(idx, line, "an input could not be decoded (uncompressed BGR AVI with PCM16 audio only)")
+                got = _read_line(args, idx, line, ranks, tmpdir, sys.stderr.write)
+                if got is None:
                     continue
-                mel = audio.melspectrogram_device(wav, ranks.device)
-                if bool(torch.isnan(mel).any()):
-                    _skip(idx, line, "the mel spectrogram contains NaN")
-                    continue
-                n_chunks = len(multiclip.filelist_chunk_starts(mel.shape[1]))
-                if n_chunks == 0:
-                    _skip(idx, line, "the audio is shorter than one 16-column mel window")
-                    continue
-                full_frames = list(clip["frames"])
-                if len(full_frames) < n_chunks:
-                    _skip(idx, line, "the video has fewer frames ({}) than mel chunks ({})".format(len(full_frames), n_chunks))
-                    continue
-                full_frames = full_frames[:n_chunks]
+                full_frames, mel, pcm, sr = got
                 try:
                     det = inference.face_detect(full_frames, detector=detector, pads=args.pads, nosmooth=False,
                                                 batch_size=args.face_det_batch_size)
@@ -139,6 +166,53 @@ def clip_jobs(args, lines, ranks, detector, tracks):
             except ValueError as e:                      # a malformed line, a box outside its frame
                 traceback.print_exc()
                 _skip(idx, line, str(e))
+
+
+def clip_jobs_packed(args, lines, ranks, detector, tracks):
+    """`clip_jobs` with detection packed across lines (`--packed_face_det`), in three stages: `_read_line` for the lines ahead,
+    `face_detection.detect_many` over their frames, then rows and the ClipJob as each line's boxes arrive.  detect_many reads a
+    group of lines before it answers the first, so what the first stage has to say about a line it passes over is held back
+    and written when the runnable line after it is answered: stderr reads as it does from `clip_jobs`."""
+    from . import face_detection, multiclip
+    held, notes, tail = {}, {}, []       # line index -> (line, frames, mel, pcm, rate); -> stderr text due before it; after the last
+
+    def inputs(tmpdir):
+        said = []
+        for idx, line in lines_of_rank(lines, ranks):
+            try:
+                got = _read_line(args, idx, line, ranks, tmpdir, said.append)
+            except KeyboardInterrupt:
+                raise
+            except ValueError as e:                      # a malformed line
+                said.append(traceback.format_exc())
+                said.append(_skip_text(idx, line, str(e)))
+                continue
+            if got is None:
+                continue
+            held[idx] = (line,) + got
+            notes[idx], said = "".join(said), []
+            yield face_detection.DetectJob(idx, got[0])
+        tail.extend(said)
+
+    with tempfile.TemporaryDirectory(prefix="w2l_filelist_") as tmpdir:
+        for idx, boxes, error in face_detection.detect_many(detector, inputs(tmpdir), pads=args.pads, T=5,
+                                                            batch_size=args.face_det_batch_size):
+            sys.stderr.write(notes.pop(idx))
+            line, full_frames, mel, pcm, sr = held.pop(idx)
+            try:
+                if error is not None:
+                    _skip(idx, line, error)
+                    continue
+                rows = multiclip.rows_filelist(mel.shape[1], len(full_frames), [tuple(b) for b in boxes])
+                frame_h, frame_w = full_frames[0].shape[:-1]
+                tracks[idx] = ((frame_w, frame_h), pcm, sr)
+                yield multiclip.ClipJob(idx, full_frames, mel, rows)
+            except KeyboardInterrupt:
+                raise
+            except ValueError as e:                      # a box outside its frame
+                traceback.print_exc()
+                _skip(idx, line, str(e))
+        sys.stderr.write("".join(tail))
 
 
 class ResultSink:
@@ -171,7 +245,7 @@ def main(argv=None, state_dict=None, backend="nccl"):
     """gen_videos_from_filelist.py:152-235.  `state_dict` (S3FD weights) replaces face_detection/s3fd.pth; `backend` is the
     process group's.  Returns the line indices this rank wrote, in order."""
     from . import face_detection, inference, multiclip, sharding
-    args = cli_parser.parse_args(argv)
+    args = main_parser.parse_args(argv)
     args.img_size = 96
     ranks = sharding.init_from_env(backend)
     try:
@@ -188,7 +262,8 @@ def main(argv=None, state_dict=None, backend="nccl"):
         tracks = {}
         sink = ResultSink(args.results_dir, tracks)
         try:
-            multiclip.lipsync_many(model, clip_jobs(args, lines, ranks, detector, tracks), batch_size=args.wav2lip_batch_size,
+            producer = clip_jobs_packed if args.packed_face_det else clip_jobs
+            multiclip.lipsync_many(model, producer(args, lines, ranks, detector, tracks), batch_size=args.wav2lip_batch_size,
                                    precision=inference.CLI_PRECISION[args.precision], sink=sink)
         finally:
             sink.close()
