@@ -164,8 +164,16 @@ int w2l_datagen_pack_bf16(void* stream, int N, int S, const uint8_t* faces, void
 int w2l_frames_to_u8(void* stream, int N, int H, int W, const float* x, int x_cs, uint8_t* y);
 
 /* Box tensors below: int32 [B][4] = (y1, y2, x1, x2) per item, device memory, 16-byte aligned, 0 <= y1 < y2 <= H and
- * 0 <= x1 < x2 <= W (validated by the caller); frame_idx int32 [B] selects the frame of each item (NULL = item b uses
- * frame b).  Resizing follows cv::resize(INTER_LINEAR) for CV_8UC3 (OpenCV 4.1.0 fixed-point path, see csrc/resize.hip). */
+ * 0 <= x1 < x2 <= W; frame_idx int32 [B] selects the frame of each item (NULL = item b uses frame b).  Resizing follows
+ * cv::resize(INTER_LINEAR) for CV_8UC3 (OpenCV 4.1.0 fixed-point path, see csrc/resize.hip).
+ *
+ * PRECONDITION of the five image entry points (w2l_crop_resize_u8, w2l_resize_u8, w2l_resize_paste_u8, w2l_crop_resize_rows_u8,
+ * w2l_compose_rows_u8): every box is non-empty and inside its frame, and every frame_idx names an existing frame.  The boxes
+ * live in device memory, so the entry points cannot look at them and the kernels do not: an empty or inverted box makes the tap
+ * clamp of a source size <= 0 read index -1, and two negative extents give the paste a positive pixel count.  The HOST caller
+ * checks them before the launch (wav2lip_amd/inference.py validate_boxes, and what multiclip, streaming, calculate_scores and
+ * data build on it).  What the entry points do check and refuse with an error code, writing nothing: NULL pointers, B outside
+ * [1, 65535], sizes below 1, a box or row table that is not 16-byte aligned. */
 
 /* out u8 [B,S,S,3] = resize(frames[frame_idx[b]][y1:y2, x1:x2], (S,S)):  inference.py:121-126 */
 int w2l_crop_resize_u8(void* stream, int B, const uint8_t* frames, int H, int W, const int32_t* frame_idx,

@@ -11,6 +11,10 @@ nor importable in this image, and the reference has no test for it.  This restat
     rows are clipped instead of the coefficient being zeroed); horizontal pass in int32 (S0*a0 + S1*a1), vertical pass
     uchar(( ((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2).
 Plain numpy, vectorised over the destination grid.
+
+What IS pinned: tests/test_frame_cases_cpu.py holds this module strictly within one grey level of a float64 bilinear interpolation
+written without it (tests/_frame_cases.py), on every size class the product uses: the half-pixel mapping, the clamps and the taps
+are therefore right; OpenCV's exact rounding of coefficients and results is what stays unpinned.
 """
 import numpy as np
 

@@ -69,8 +69,14 @@ def _skip(name, why):
 def face_crops(frames, boxes, device):
     """uint8 [T,96,96,3] on the device: frame i cropped to boxes[i] and resized (w2l_crop_resize_rows_u8, one launch per clip)"""
     import torch
-    from . import _lib, multiclip
+    from . import _lib, inference, multiclip
     from .evaluation import img_size
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[3] != 3:
+        raise ValueError("face_crops: frames must be uint8 [T,H,W,3], got %s %s" % (frames.dtype, frames.shape))
+    boxes = inference.validate_boxes(boxes, frames.shape[1], frames.shape[2])      # the kernel takes the boxes as they are
+    if len(boxes) != len(frames):
+        raise ValueError("face_crops: %d boxes for %d frames" % (len(boxes), len(frames)))
     src = torch.from_numpy(np.ascontiguousarray(frames)).to(device)
     T, H, W = src.shape[:3]
     table = np.zeros(T, multiclip.FRAME_ROW)
