@@ -41,6 +41,12 @@ class FrameRow(C.Structure):
                 ("y2", C.c_int32), ("x1", C.c_int32), ("x2", C.c_int32), ("pad", C.c_int32 * 2)]
 
 
+class ResizeRow(C.Structure):
+    """w2l_resize_row: one frame of the whole-frame row-table resize, 32 bytes"""
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("Hs", C.c_int32), ("Ws", C.c_int32), ("Hd", C.c_int32),
+                ("Wd", C.c_int32)]
+
+
 class MelRow(C.Structure):
     """w2l_mel_row: one mel window of the row-table gather, 16 bytes"""
     _fields_ = [("mel", C.c_uint64), ("T", C.c_int32), ("start", C.c_int32)]
@@ -103,6 +109,7 @@ SIGNATURES = {
     "w2l_resize_paste_u8": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i]),
     "w2l_crop_resize_rows_u8": (_i, [_vp, _i, _vp, _i, _vp]),
     "w2l_compose_rows_u8": (_i, [_vp, _i, _vp, _i, _vp, _i]),
+    "w2l_resize_rows_u8": (_i, [_vp, _i, _vp, _i]),
     "w2l_s3fd_pack": (_i, [_vp, _ll, _vp, _vp, _i]),
     "w2l_s3fd_pack_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _i]),
     "w2l_maxpool2x2": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i]),

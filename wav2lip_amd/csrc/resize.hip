@@ -35,6 +35,23 @@ __device__ __forceinline__ AxisTap axis_tap(int d, int ssize, int dsize, bool ho
     return t;
 }
 
+// the bilinear path of resize_px for taps already computed: r0 / r1 = the two source lines of the vertical tap
+__device__ __forceinline__ void lerp_px(const uint8_t* __restrict__ r0, const uint8_t* __restrict__ r1, const AxisTap tx,
+                                        const AxisTap ty, uint8_t out[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int h0 = (int)r0[tx.s0 * 3 + c] * tx.a0 + (int)r0[tx.s1 * 3 + c] * tx.a1;
+        const int h1 = (int)r1[tx.s0 * 3 + c] * tx.a0 + (int)r1[tx.s1 * 3 + c] * tx.a1;
+        int v = (((ty.a0 * (h0 >> 4)) >> 16) + ((ty.a1 * (h1 >> 4)) >> 16) + 2) >> 2;
+        out[c] = (uint8_t)min(max(v, 0), 255);
+    }
+}
+
+// true when resize_px takes one of its two tap-free branches (the equal-size copy, the exact 2x INTER_AREA average)
+__device__ __forceinline__ bool resize_is_direct(int Hs, int Ws, int h, int w) {
+    return (Hs == h && Ws == w) || (Hs == 2 * h && Ws == 2 * w);
+}
+
 // src: pointer to pixel (0,0) of the source region, row stride in bytes; Hs x Ws -> pixel (dx,dy) of an h x w result
 __device__ __forceinline__ void resize_px(const uint8_t* __restrict__ src, long long row_stride, int Hs, int Ws, int dx,
                                           int dy, int w, int h, uint8_t out[3]) {
@@ -52,15 +69,7 @@ __device__ __forceinline__ void resize_px(const uint8_t* __restrict__ src, long 
     }
     const AxisTap tx = axis_tap(dx, Ws, w, true);
     const AxisTap ty = axis_tap(dy, Hs, h, false);
-    const uint8_t* r0 = src + ty.s0 * row_stride;
-    const uint8_t* r1 = src + ty.s1 * row_stride;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int h0 = (int)r0[tx.s0 * 3 + c] * tx.a0 + (int)r0[tx.s1 * 3 + c] * tx.a1;
-        const int h1 = (int)r1[tx.s0 * 3 + c] * tx.a0 + (int)r1[tx.s1 * 3 + c] * tx.a1;
-        int v = (((ty.a0 * (h0 >> 4)) >> 16) + ((ty.a1 * (h1 >> 4)) >> 16) + 2) >> 2;
-        out[c] = (uint8_t)min(max(v, 0), 255);
-    }
+    lerp_px(src + ty.s0 * row_stride, src + ty.s1 * row_stride, tx, ty, out);
 }
 
 __global__ void crop_resize_kernel(int B, const uint8_t* __restrict__ frames, int H, int W,
@@ -180,6 +189,71 @@ __global__ void compose_rows_kernel(int B, const uint8_t* __restrict__ pred, int
     }
 }
 
+// ---- whole-frame row-table resize (evaluation/real_videos_inference.py:239-245 the `max_frame_res` cap at read time, :51-70
+// rescale_frames by an integer factor): every row names its own source and destination frame and their sizes, so frames of any
+// shapes share one launch and two rows may read one source.  Same resize_px arithmetic: byte-equal to resize_frames_kernel.
+// An item is 4 neighbouring pixels of one destination line (12 bytes): the vertical tap is computed once per item, the
+// horizontal taps once per pixel, and the 12 bytes leave as three dwords when their address is 4-byte aligned.  Destinations lie
+// at any byte address (H*W*3 is rarely a multiple of 4, and so is W*3), so a line that starts m bytes past a dword boundary
+// stores 4-m bytes, the two aligned dwords inside the item and m bytes; the ragged last item of a line goes byte by byte.
+// Source reads are byte gathers (<= 4 items share a source pixel: L1/L2 hits).  HBM-bound, no LDS.
+struct ResizeRow {          // mirrors w2l_resize_row (include/w2l_hip.h), 32 bytes
+    unsigned long long src, dst;
+    int Hs, Ws, Hd, Wd;
+};
+static_assert(sizeof(ResizeRow) == 32, "w2l_resize_row is 32 bytes");
+
+__global__ __launch_bounds__(256) void resize_rows_kernel(int B, const ResizeRow* __restrict__ rows) {
+    const int b = blockIdx.y;
+    const ResizeRow r = rows[b];
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(r.src);
+    uint8_t* dst = reinterpret_cast<uint8_t*>(r.dst);
+    const long long sstride = (long long)r.Ws * 3, dstride = (long long)r.Wd * 3;
+    const int groups = (r.Wd + 3) >> 2;
+    const int nitems = r.Hd * groups;                   // <= Hd*Wd < 2^29 (checked by the caller's max_dst_pixels)
+    const bool direct = resize_is_direct(r.Hs, r.Ws, r.Hd, r.Wd);
+    for (int item = blockIdx.x * blockDim.x + threadIdx.x; item < nitems; item += gridDim.x * blockDim.x) {
+        const int dy = item / groups, x0 = (item - dy * groups) << 2;
+        const int np = min(4, r.Wd - x0);
+        uint8_t px[4][3];
+        if (direct) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < np) resize_px(src, sstride, r.Hs, r.Ws, x0 + k, dy, r.Wd, r.Hd, px[k]);
+        } else {
+            const AxisTap ty = axis_tap(dy, r.Hs, r.Hd, false);
+            const uint8_t* r0 = src + ty.s0 * sstride;
+            const uint8_t* r1 = src + ty.s1 * sstride;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < np) lerp_px(r0, r1, axis_tap(x0 + k, r.Ws, r.Wd, true), ty, px[k]);
+        }
+        uint8_t* o = dst + dy * dstride + (long long)x0 * 3;
+        if (np < 4) {
+            for (int k = 0; k < np; ++k) {
+                o[3 * k] = px[k][0]; o[3 * k + 1] = px[k][1]; o[3 * k + 2] = px[k][2];
+            }
+            continue;
+        }
+        uint32_t w[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 12; ++k) w[k >> 2] |= (uint32_t)px[k / 3][k % 3] << (8 * (k & 3));
+        const unsigned m = (unsigned)(reinterpret_cast<uintptr_t>(o) & 3);
+        if (m == 0) {
+            uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
+            o4[0] = w[0]; o4[1] = w[1]; o4[2] = w[2];
+            continue;
+        }
+        // bytes [0, 4-m) | dwords at byte 4-m and 8-m of the item (both aligned) | bytes [12-m, 12)
+        const unsigned head = 4 - m, sh = 8 * head;
+        for (unsigned k = 0; k < head; ++k) o[k] = (uint8_t)(w[0] >> (8 * k));
+        uint32_t* o4 = reinterpret_cast<uint32_t*>(o + head);
+        o4[0] = (uint32_t)((((unsigned long long)w[1] << 32) | w[0]) >> sh);
+        o4[1] = (uint32_t)((((unsigned long long)w[2] << 32) | w[1]) >> sh);
+        for (unsigned k = 0; k < m; ++k) o[12 - m + k] = (uint8_t)(w[2] >> (8 * (head + k)));
+    }
+}
+
 }  // namespace w2l
 
 using namespace w2l;
@@ -242,6 +316,18 @@ int w2l_compose_rows_u8(void* stream, int B, const uint8_t* pred, int S, const w
     if (gx > 1024) gx = 1024;
     hipLaunchKernelGGL(compose_rows_kernel, dim3(gx, B), dim3(256), 0, static_cast<hipStream_t>(stream), B, pred, S,
                        reinterpret_cast<const FrameRow*>(rows));
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_resize_rows_u8(void* stream, int B, const w2l_resize_row* rows, int max_dst_pixels) {
+    W2L_REQUIRE(rows && max_dst_pixels >= 1 && max_dst_pixels <= (1 << 29), "bad resize_rows arguments");
+    W2L_REQUIRE(B >= 1 && B <= 65535 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0,
+                "resize_rows: 1 <= B <= 65535 and a 16-byte aligned row table");
+    int gx = ceil_div(ceil_div(max_dst_pixels, 4), 256);
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(resize_rows_kernel, dim3(gx, B), dim3(256), 0, static_cast<hipStream_t>(stream), B,
+                       reinterpret_cast<const ResizeRow*>(rows));
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

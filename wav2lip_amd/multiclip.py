@@ -12,6 +12,10 @@ together with the two row tables (w2l_frame_row / w2l_mel_row, include/w2l_hip.h
 stream  w2l_crop_resize_rows_u8 -> w2l_datagen_pack -> w2l_mel_gather_rows -> the plan -> w2l_frames_to_u8 (fp32 only) ->
 w2l_compose_rows_u8,  and the composed frames come back in one copy.  Frames of different clips may have different shapes.
 
+A clip's frames may already be on the device (`ClipJob.frames` a contiguous uint8 tensor [F,H,W,3]; real_videos_inference.py
+resizes and detects there): such a job stages nothing - a row's `src` is the address of the frame where it lies, only the two
+tables travel up, and the outputs come back as for any other job.
+
 `rows_inference` / `rows_filelist` are the two row conventions of the reference (inference.py:231-240 and
 gen_videos_from_filelist.py:176-198); the packer knows nothing about either.
 """
@@ -28,8 +32,9 @@ MEL_ROW = np.dtype([("mel", "<u8"), ("T", "<i4"), ("start", "<i4")])
 _ALIGN = 16          # every staged frame and both tables start on a 16-byte boundary
 
 ClipJob = collections.namedtuple("ClipJob", "key frames mel rows")
-ClipJob.__doc__ = """one clip: `frames` uint8 [H,W,3] BGR frames (one shape per clip; a list or an [F,H,W,3] array), `mel` the device
-[80,T] spectrogram (audio.melspectrogram_device), `rows` a list of (frame_index, (y1, y2, x1, x2), mel_start)"""
+ClipJob.__doc__ = """one clip: `frames` uint8 [H,W,3] BGR frames (one shape per clip; a list or an [F,H,W,3] array, or a contiguous uint8
+device tensor [F,H,W,3] that is read where it lies), `mel` the device [80,T] spectrogram (audio.melspectrogram_device), `rows` a list
+of (frame_index, (y1, y2, x1, x2), mel_start)"""
 
 
 def rows_inference(n_mel, n_frames, boxes, fps=25., static=False):
@@ -77,6 +82,45 @@ def _align(n):
     return (n + _ALIGN - 1) // _ALIGN * _ALIGN
 
 
+def _resident(frames):
+    """True for a frame tensor (torch, [F,H,W,3]): its frames are addressed where they lie, never staged"""
+    return hasattr(frames, "data_ptr")
+
+
+def _frame_hw(job, fi):
+    f = job.frames
+    return (int(f.shape[1]), int(f.shape[2])) if _resident(f) else np.asarray(f[fi]).shape[:2]
+
+
+def _frame_bytes(job, fi):
+    if _resident(job.frames):
+        H, W = _frame_hw(job, fi)
+        return H * W * 3
+    return np.asarray(job.frames[fi]).nbytes
+
+
+def staging_layout(rows, n):
+    """where everything of a batch of `rows` launched as n >= len(rows) rows lies: (bytes of the staging buffer, offset of the
+    mel-row table, {(id(job), frame): offset of a staged host frame}, [(offset, host frame)], [output offset per row], output
+    bytes).  The staging buffer is [frame-row table][mel-row table][deduplicated host frames]; frames of a device-resident job are
+    not in it.  Outputs have a buffer of their own."""
+    off = _align(n * FRAME_ROW.itemsize)
+    mel_off = off
+    off = _align(off + n * MEL_ROW.itemsize)
+    src_off, frames = {}, []
+    for job, fi, _, _ in rows:
+        if not _resident(job.frames) and (id(job), fi) not in src_off:
+            f = np.asarray(job.frames[fi])
+            src_off[(id(job), fi)] = off
+            frames.append((off, f))
+            off = _align(off + f.nbytes)
+    out_off, out_bytes = [], 0
+    for job, fi, _, _ in rows:
+        out_off.append(out_bytes)
+        out_bytes = _align(out_bytes + _frame_bytes(job, fi))
+    return off, mel_off, src_off, frames, out_off, out_bytes
+
+
 class BatchRunner:
     """the device side of the packer: `submit(rows)` stages, launches and starts the copy back of one packed batch on the
     next lane and returns a ticket, `result(ticket)` waits for it and returns one uint8 [H,W,3] array per row.
@@ -97,26 +141,12 @@ class BatchRunner:
         torch = self.torch
         real = len(rows)
         n = max(real, pad_to or 0)
-        # ---- layout of the staging buffer: [frame-row table][mel-row table][deduplicated frames]; outputs in a buffer of their own
-        off = _align(n * FRAME_ROW.itemsize)
-        mel_off = off
-        off = _align(off + n * MEL_ROW.itemsize)
-        src_off, frames = {}, []
-        for job, fi, _, _ in rows:
-            if (id(job), fi) not in src_off:
-                f = np.asarray(job.frames[fi])
-                src_off[(id(job), fi)] = off
-                frames.append((off, f))
-                off = _align(off + f.nbytes)
-        out_off, out_bytes = [], 0
-        for job, fi, _, _ in rows:
-            out_off.append(out_bytes)
-            out_bytes = _align(out_bytes + np.asarray(job.frames[fi]).nbytes)
+        off, mel_off, src_off, frames, out_off, out_bytes = staging_layout(rows, n)
         host = torch.empty(off, dtype=torch.uint8, pin_memory=True)
         dev = torch.empty(off, dtype=torch.uint8, device=self.device)
         scratch = 0
         if n > real:                             # one scratch frame behind the outputs for the padded rows
-            scratch = _align(np.asarray(rows[-1][0].frames[rows[-1][1]]).nbytes)
+            scratch = _align(_frame_bytes(rows[-1][0], rows[-1][1]))
         dev_out = torch.empty(out_bytes + scratch, dtype=torch.uint8, device=self.device)
         host_out = torch.empty(out_bytes, dtype=torch.uint8, pin_memory=True)
         stage = host.numpy()
@@ -124,10 +154,15 @@ class BatchRunner:
             stage[o:o + f.nbytes] = f.reshape(-1)
         ft = stage[:n * FRAME_ROW.itemsize].view(FRAME_ROW)
         mt = stage[mel_off:mel_off + n * MEL_ROW.itemsize].view(MEL_ROW)
-        shapes, mels, max_px = [], {}, 1
+        shapes, mels, max_px = [], {}, 1             # mels: every device tensor the lane reads, spectrograms and resident frames
         for r, (job, fi, (y1, y2, x1, x2), start) in enumerate(rows):
-            H, W = np.asarray(job.frames[fi]).shape[:2]
-            ft[r] = (dev.data_ptr() + src_off[(id(job), fi)], dev_out.data_ptr() + out_off[r], H, W, y1, y2, x1, x2, (0, 0))
+            H, W = _frame_hw(job, fi)
+            if _resident(job.frames):                # read where it lies; the lane keeps the tensor alive
+                src = job.frames.data_ptr() + fi * H * W * 3
+                mels[id(job.frames)] = job.frames
+            else:
+                src = dev.data_ptr() + src_off[(id(job), fi)]
+            ft[r] = (src, dev_out.data_ptr() + out_off[r], H, W, y1, y2, x1, x2, (0, 0))
             mel, T, start = start if isinstance(start, tuple) else (job.mel, job.mel.shape[1], start)
             mt[r] = (mel.data_ptr(), T, start)
             mels[id(mel)] = mel
@@ -158,6 +193,8 @@ def _checked_rows(job):
     """the job's rows with every box, frame number and mel window validated; a ValueError names the job"""
     rows = []
     T = int(job.mel.shape[1])
+    if _resident(job.frames):
+        return _checked_rows_resident(job, T)
     for fi, box, start in job.rows:
         fi, start = int(fi), int(start)
         try:
@@ -172,6 +209,26 @@ def _checked_rows(job):
         except ValueError as e:
             raise ValueError("job %r: %s" % (job.key, e)) from None
         rows.append((fi, box, start))
+    return rows
+
+
+def _checked_rows_resident(job, T):
+    """`_checked_rows` for a frame tensor on the device: shapes and flags only, nothing that waits for the device"""
+    f = job.frames
+    rows = []
+    try:
+        if str(f.dtype) != "torch.uint8" or f.dim() != 4 or f.shape[3] != 3 or not f.is_contiguous():
+            raise ValueError("a frame tensor must be contiguous uint8 [F,H,W,3], got %s %s" % (f.dtype, tuple(f.shape)))
+        F, H, W = (int(v) for v in f.shape[:3])
+        for fi, box, start in job.rows:
+            fi, start = int(fi), int(start)
+            if not 0 <= fi < F:
+                raise ValueError("frame index %d outside the clip's %d frames" % (fi, F))
+            if start < 0 or start + mel_step_size > T:
+                raise ValueError("mel window [%d, %d) outside the %d columns of the spectrogram" % (start, start + mel_step_size, T))
+            rows.append((fi, validate_boxes([box], H, W)[0], start))
+    except ValueError as e:
+        raise ValueError("job %r: %s" % (job.key, e)) from None
     return rows
 
 

@@ -224,3 +224,47 @@ def filelist_clips(seed=3):
         pcm = _rng(seed * 1000 + i, "filelist_audio").integers(-8000, 8000, (filelist_samples(chunks), 1)).astype(np.int16)
         clips[name] = (frames, pcm)
     return clips
+
+
+# ---------------------------------------------------------------- real-video generation (evaluation/real_videos_inference.py)
+REAL_SHAPES = [(180, 240), (168, 216), (72, 96)]        # (H, W): the first two exceed --max_frame_res 144, the third does not
+# seeds of the distinct frames per shape (a clip cycles through its shape's pool), picked so that the seeded S3FD's decisions on
+# them - at the size the detector sees them - keep the margins tests/golden/make_golden_real_videos.py asserts
+REAL_FRAME_SEEDS = [[5000, 5001, 5002, 5006], [5100, 5101, 5102, 5103], [5200, 5201, 5202, 5203]]
+REAL_POOL = 4
+# (clip name, shape index, frames, mel chunks of its audio at its fps, fps, first frame face-less?)
+REAL_CLIPS = [("r0", 2, 12, 10, 25., False), ("r1", 0, 14, 14, 25., False), ("r2", 1, 9, 11, 25., False), ("r3", 2, 4, 4, 25., False),
+              ("r4", 0, 8, 8, 25., True), ("r5", 1, 10, 10, 30., False)]
+# (video, audio source) per line, run in `tts` mode with REAL_FLAGS: 10 rows (neither resize), 14 (both resizes), 11 from 9 frames
+# (two duplicated), skipped (no face in the first frame), 10 from 4 frames (duplicated twice over), 10 at 30 fps
+REAL_LINES = [("r0", "r0"), ("r1", "r1"), ("r2", "r2"), ("r4", "r4"), ("r3", "r0"), ("r5", "r5")]
+REAL_FLAGS = ["--max_frame_res", "144", "--min_frame_res", "60", "--face_res", "24", "--face_det_batch_size", "4"]
+
+
+def real_frame(seed, H, W):
+    """one uint8 BGR noise frame with a saturated block about half the frame high at a seeded place (the seeded S3FD's "face")"""
+    r = _rng(seed, "real_videos")
+    out = r.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    h, w = r.integers(9 * H // 20, 11 * H // 20), r.integers(9 * H // 20, 11 * H // 20)
+    y, x = r.integers(H // 8, H - h - H // 8), r.integers(W // 8, W - w - W // 8)
+    out[y:y + h, x:x + w] = 255 if r.uniform() < 0.5 else 0
+    return out
+
+
+def real_samples(n_chunks, fps):
+    """audio samples whose spectrogram (1 + n // 200 columns) holds exactly `n_chunks` full 16-column windows at `fps`"""
+    return (int((n_chunks - 1) * (80. / fps)) + 16 - 1) * 200 + 50
+
+
+def real_video_clips(seed=5):
+    """{clip name: (frames uint8 [T,H,W,3] BGR, fps, mono PCM16 audio int16 [n,1] at 16 kHz)} of REAL_CLIPS"""
+    pools = [[real_frame(k, H, W) for k in REAL_FRAME_SEEDS[s]] for s, (H, W) in enumerate(REAL_SHAPES)]
+    clips = {}
+    for i, (name, s, t, chunks, fps, faceless) in enumerate(REAL_CLIPS):
+        frames = np.stack([pools[s][(k + i) % REAL_POOL] for k in range(t)])
+        if faceless:
+            H, W = REAL_SHAPES[s]
+            frames[0] = 120 + _rng(seed * 1000 + i, "real_videos_grey").integers(-1, 2, (H, W, 3))
+        pcm = _rng(seed * 1000 + i, "real_videos_audio").integers(-8000, 8000, (real_samples(chunks, fps), 1)).astype(np.int16)
+        clips[name] = (frames, fps, pcm)
+    return clips
