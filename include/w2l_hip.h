@@ -524,8 +524,8 @@ int w2l_convb_forward_head(const w2l_convb_t* c, void* stream, int N, int H, int
 int w2l_convb_set_tile(w2l_convb_t* c, int tile);
 int w2l_convb_num_tiles(void);
 /* The kernel a launch of this layer over [N,H,W] (has_res: with a residual) resolves to - what w2l_convb_forward with
- * ksplit_force 0, a w2l_plan_add_convb item or, for a layer with a fused head, w2l_convb_forward_head would run: the launcher's
- * own dry run with dense strides.  Launches nothing, touches no device memory.
+ * ksplit_force 0, a w2l_plan_add_convb item or, for a layer with a fused head, w2l_convb_forward_head would run: the function
+ * of the shape the launcher itself calls before it launches, over dense strides.  Launches nothing, touches no device memory.
  *   *family: W2L_CONVB_IGEMM (*tile = tile id, *ksplit = split-K), W2L_CONVB_STEM (*tile = the stem kernel's layer family 1..4),
  *            W2L_CONVB_BOX64, W2L_CONVB_TP2B or W2L_CONVB_HEAD (the fused output block); *tile = -1, *ksplit = 1 where not given. */
 #define W2L_CONVB_IGEMM 0
@@ -534,6 +534,10 @@ int w2l_convb_num_tiles(void);
 #define W2L_CONVB_TP2B 3
 #define W2L_CONVB_HEAD 4
 int w2l_convb_resolve(const w2l_convb_t* c, int N, int H, int W, int has_res, int* family, int* tile, int* ksplit);
+/* The same answer from the geometry alone (no layer handle, no device, automatic tile), and *flops: the FLOPs the matrix cores
+ * execute for that launch (padded tiles and K), as w2l_plan_executed_flops and the w2l_flops_begin counter report them. */
+int w2l_convb_resolve_geom(const w2l_conv_geom* g, int N, int H, int W, int has_res, int* family, int* tile, int* ksplit,
+                           long long* flops);
 
 /* Weight gradient on the bf16-storage path: dweight (fp32, torch layout of `g`, fully overwritten) from the layer input
  * x bf16 [N,H,W,x_cs] and the gradient dz bf16 [N,Ho,Wo,dz_cs] of the convolution output.  Same contract as w2l_conv_wgrad

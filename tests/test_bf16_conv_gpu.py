@@ -68,6 +68,8 @@ def _run(cuda, transposed, cin, cout, k, stride, pad, outpad, N, H, W, act=ACT_R
     shift = torch.randn(cout) * 0.2 if affine else None
     g = ConvGeom(int(transposed), cin, cout, kh, kw, s[0], s[1], p[0], p[1], op[0], op[1], act)
     layer = bf16.ConvB(g, w.to(cuda))
+    # the layer resolves (automatic tile) as the geometry alone does: one function of the shape behind both
+    assert layer.resolve(N, H, W, res=with_res) == bf16.ConvB.resolve_geom(g, N, H, W, res=with_res)
     if tile is not None:
         layer.set_tile(tile)
     Ho, Wo = layer.out_hw(H, W)

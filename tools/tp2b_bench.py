@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Isolated launch times of the stride-2 transposed 3x3 layers of the bf16 training path (forward of the decoder's upsampling
-layers, data gradients of the stride-2 convs; 320 frames) - run once per setting of W2L_CONVB_TP2B (0: four-phase implicit GEMM,
-1: fused-phase kernel for the 32-cout tile, 2: for every tile):
-    for v in 0 1 2; do W2L_CONVB_TP2B=$v python tools/tp2b_bench.py; done"""
+layers, data gradients of the stride-2 convs; 320 frames), each on the kernel the launcher's shape rules give it (printed beside
+the time) and on the four-phase implicit GEMM (a tile override):
+    python tools/tp2b_bench.py"""
 import os
 import sys
 
@@ -38,19 +38,23 @@ def timed(fn, reps=10):
 
 def main():
     dev = torch.device("cuda")
-    print("W2L_CONVB_TP2B=%s" % os.environ.get("W2L_CONVB_TP2B", "1"))
     for name, cin, cout, N, H, W, with_res in SHAPES:
         w = torch.randn(cin, cout, 3, 3, device=dev) / (cin * 9) ** 0.5
-        layer = bf16.ConvB(ConvGeom(1, cin, cout, 3, 3, 2, 2, 1, 1, 1, 1, ACT_NONE), w)
+        g = ConvGeom(1, cin, cout, 3, 3, 2, 2, 1, 1, 1, 1, ACT_NONE)
         x = torch.randn(N, H, W, bf16.round8(cin), device=dev).to(torch.bfloat16)
         y = torch.zeros(N, 2 * H, 2 * W, bf16.round8(cout), device=dev, dtype=torch.bfloat16)
         A = bf16.ActB
         res = A(y, 0, cout) if with_res else None
-        ms = timed(lambda: layer.run(A(x, 0, cin), A(y, 0, cout), res, None, None, 0))
         gf = 2.0 * N * H * W * cin * cout * 9 / 1e9
         mb = (x.numel() + y.numel() * (2 if with_res else 1)) * 2 / 1e6
-        print("  %-36s %7.3f ms  %7.1f TFLOP/s  %6.0f GB/s of %5.0f MB in + out" % (name, ms, gf / ms, mb / ms, mb))
-
+        igemm_tile = bf16.ConvB.resolve_geom(g, 1, H, W, with_res)[1]      # one frame: always the implicit GEMM
+        for tile in (None, igemm_tile):
+            layer = bf16.ConvB(g, w)
+            if tile is not None:
+                layer.set_tile(tile)
+            ms = timed(lambda: layer.run(A(x, 0, cin), A(y, 0, cout), res, None, None, 0))
+            print("  %-36s %-16s %7.3f ms  %7.1f TFLOP/s  %6.0f GB/s of %5.0f MB in + out"
+                  % (name, "%s/%d/%d" % layer.resolve(N, H, W, with_res), ms, gf / ms, mb / ms, mb))
 
 if __name__ == "__main__":
     main()

@@ -159,6 +159,8 @@ SIGNATURES = {
     "w2l_convb_set_tile": (_i, [_vp, _i]),
     "w2l_convb_num_tiles": (_i, []),
     "w2l_convb_resolve": (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "w2l_convb_resolve_geom": (_i, [C.POINTER(ConvGeom), _i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                    C.POINTER(_ll)]),
     "w2l_conv_wgrad_bf16": (_i, [C.POINTER(ConvGeom), _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "w2l_conv_wgrad_bf16_resolve": (_i, [C.POINTER(ConvGeom), _i, _i, _i, _i, _i, C.POINTER(WgradBf16Info)]),
     "w2l_bn_train_stats_bf16": (_i, [_vp, _ll, _i, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -117,17 +117,30 @@ class ConvB:
 
     FAMILIES = {0: "igemm", 1: "stem", 2: "box64", 3: "tp2b", 4: "k3s_head"}     # W2L_CONVB_IGEMM .. W2L_CONVB_HEAD
 
+    @classmethod
+    def _resolved(cls, fam, tile, ks):
+        name = cls.FAMILIES[fam]
+        return ("stem%d" % tile, -1, 1) if name == "stem" else (name, tile, ks)
+
     def resolve(self, N, H, W, res=False):
         """(family, tile, ksplit) of the kernel a launch over [N,H,W] (with a residual: `res`) runs (w2l_convb_resolve, the
-        launcher's own dry run): family "igemm" with its tile id and split-K, "stem<k>" (k = the stem kernel's layer family),
-        "box64", "tp2b" or "k3s_head" (a layer with a fused head) with tile -1 and split-K 1.  Launches nothing."""
+        function of the shape the launcher calls first): family "igemm" with its tile id and split-K, "stem<k>" (k = the stem
+        kernel's layer family), "box64", "tp2b" or "k3s_head" (a layer with a fused head) with tile -1 and split-K 1.  Launches
+        nothing."""
         fam, tile, ks = C.c_int(), C.c_int(), C.c_int()
         check(self._lib.w2l_convb_resolve(self.handle, int(N), int(H), int(W), int(bool(res)), C.byref(fam), C.byref(tile),
                                           C.byref(ks)), "convb_resolve")
-        name = self.FAMILIES[fam.value]
-        if name == "stem":
-            return "stem%d" % tile.value, -1, 1
-        return name, tile.value, ks.value
+        return self._resolved(fam.value, tile.value, ks.value)
+
+    @classmethod
+    def resolve_geom(cls, geom, N, H, W, res=False, flops=False):
+        """resolve() from the geometry alone: no layer, no device, automatic tile (w2l_convb_resolve_geom); `flops`: the FLOPs
+        the matrix cores execute for that launch as a fourth entry"""
+        fam, tile, ks, fl = C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
+        check(_lib.load().w2l_convb_resolve_geom(C.byref(geom), int(N), int(H), int(W), int(bool(res)), C.byref(fam), C.byref(tile),
+                                                 C.byref(ks), C.byref(fl)), "convb_resolve_geom")
+        r = cls._resolved(fam.value, tile.value, ks.value)
+        return r + (fl.value,) if flops else r
 
     def run(self, x, y, res=None, scale=None, shift=None, ksplit=0):
         check(self._lib.w2l_convb_forward(self.handle, current_stream(), x.N, x.H, x.W, x.ptr, x.cs, y.ptr, y.cs,

@@ -22,8 +22,6 @@
 #include <new>
 #include <vector>
 
-#include <stdlib.h>
-
 #include "w2l_common.h"
 
 namespace w2l {
@@ -626,16 +624,21 @@ static const BTile kBTiles[] = {
 };
 constexpr int kNumBTiles = sizeof(kBTiles) / sizeof(kBTiles[0]);
 
-struct BVariant {
+// host phase / tap tables of one variant of a layer: a function of the geometry alone (build_tables)
+struct BTables {
     int nphase = 0;
     int sy = 1, sx = 1, omy = 1, omx = 1;
     bool q_is_out = true;
     ConvPhase ph[kMaxPhases];
-    int* taps_dev = nullptr;    // [0, ntab): (dy, dx); [ntab, 2 ntab): (ky, kx) for the packer
-    std::vector<int> taps_host; // the (dy, dx) half on the host: the shape rules of the special-case kernels read it
+    std::vector<int> taps_host; // (dy, dx) per entry: the shape rules of the special-case kernels read it
+    std::vector<int> tapk_host; // (ky, kx) per entry, for the packer
     int ntab = 0;
-    __bf16* w_dev = nullptr;
     long long w_elems = 0;
+};
+// ... and its device side (uploadb): the tap tables and the bf16 weight slabs
+struct BVariant : BTables {
+    int* taps_dev = nullptr;    // [0, ntab): (dy, dx); [ntab, 2 ntab): (ky, kx)
+    __bf16* w_dev = nullptr;
     bool built = false;
 };
 
@@ -651,23 +654,13 @@ int box64_grid(int N, int H, int W);
 // in one workgroup
 bool tp2b_ok(int transposed, int kh, int kw, int sh, int sw, int ph, int pw, int nphase, const ConvPhase* phs, const int* taps_host, int cin_p,
              int cout_p, int N, int H, int W, int Ho, int Wo);
-int tp2b_npart(int cout_p, int N, int H, int W);
+int tp2b_npart(int N, int H, int W);
 int tp2b_launch(hipStream_t stream, const void* x, int x_cs, void* y, int y_cs, const void* res, int res_cs, const void* w, long long w_elems,
-                const float* scale, const float* shift, float* stats, const ConvPhase* phs, const int* taps_host, int N, int H, int W,
-                int cin_p, int cout, int cout_p, int act);
-struct BoxBwd {             // conv_box_bf16.hip: the block whose dy a BWD launch completes
-    const void* z;
-    const void* y;
-    int z_cs, y_cs, store_g;
-    float neg;
-    const float* mean;
-    const float* rstd;
-    const float* scale;
-    const float* shift;
-};
+                const float* scale, const float* shift, float* stats, const ConvPhase* phs, int N, int H, int W, int cin_p, int cout,
+                int cout_p, int act);
 int box64_launch(hipStream_t stream, const void* x, int x_cs, void* y, int y_cs, const void* res, int res_cs, const void* w,
                  const float* scale, const float* shift, const int* taps, float* stats, int N, int H, int W, int cout, int act,
-                 const BoxBwd* bwd);
+                 const BEpilogue* bwd);
 
 }  // namespace w2l
 
@@ -717,9 +710,10 @@ static int packb(const w2l_convb* c, const BVariant& v, const float* weight, hip
     return W2L_OK;
 }
 
-static int buildb(w2l_convb* c, BVariant& v, bool unit_input) {
-    const w2l_conv_geom& g = c->g;
-    std::vector<int> tapd, tapk;
+static int build_tables(const w2l_conv_geom& g, int cin_p, int cout_p, bool unit_input, BTables& v) {
+    std::vector<int>& tapd = v.taps_host;
+    std::vector<int>& tapk = v.tapk_host;
+    tapd.clear(); tapk.clear();
     long long woff = 0;
     v.nphase = 0;
     auto add_phase = [&](int poy, int pox) -> ConvPhase& {
@@ -733,9 +727,9 @@ static int buildb(w2l_convb* c, BVariant& v, bool unit_input) {
         ++p.ntaps;
     };
     auto close_phase = [&](ConvPhase& p) {
-        p.kp = round_up(p.ntaps * c->cin_p, kBKH);
+        p.kp = round_up(p.ntaps * cin_p, kBKH);
         p.w_off = woff;
-        woff += (long long)c->cout_p * p.kp;
+        woff += (long long)cout_p * p.kp;
     };
     if (!g.transposed) {
         v.sy = g.sh; v.sx = g.sw; v.omy = 1; v.omx = 1; v.q_is_out = true;
@@ -774,18 +768,36 @@ static int buildb(w2l_convb* c, BVariant& v, bool unit_input) {
     }
     for (int i = 0; i < v.nphase; ++i)
         if (v.ph[i].ntaps > 64) { set_error("bf16 conv: too many taps"); return W2L_ERR_ARG; }
-    const int ntab = (int)tapd.size();
-    v.ntab = ntab;
-    v.taps_host = tapd;
+    v.ntab = (int)tapd.size();
     v.w_elems = woff;
+    return W2L_OK;
+}
+
+static int uploadb(BVariant& v) {
+    const int ntab = v.ntab;
     W2L_HIP_CHECK(hipMalloc(&v.taps_dev, sizeof(int) * 2 * (ntab > 0 ? ntab : 1)));
-    W2L_HIP_CHECK(hipMalloc(&v.w_dev, sizeof(__bf16) * (woff > 0 ? woff : 1)));
+    W2L_HIP_CHECK(hipMalloc(&v.w_dev, sizeof(__bf16) * (v.w_elems > 0 ? v.w_elems : 1)));
     if (ntab > 0) {
-        W2L_HIP_CHECK(hipMemcpy(v.taps_dev, tapd.data(), sizeof(int) * ntab, hipMemcpyHostToDevice));
-        W2L_HIP_CHECK(hipMemcpy(v.taps_dev + ntab, tapk.data(), sizeof(int) * ntab, hipMemcpyHostToDevice));
+        W2L_HIP_CHECK(hipMemcpy(v.taps_dev, v.taps_host.data(), sizeof(int) * ntab, hipMemcpyHostToDevice));
+        W2L_HIP_CHECK(hipMemcpy(v.taps_dev + ntab, v.tapk_host.data(), sizeof(int) * ntab, hipMemcpyHostToDevice));
     }
     v.built = true;
     return W2L_OK;
+}
+
+// a layer's padded channel counts and host tables from its geometry: the generic variant and, for a transposed stride-1 layer
+// (*has_unit), the one for a 1x1 input with a single-tap phase per output position
+static int geom_tables(const w2l_conv_geom* g, int* cin_p, int* cout_p, BTables& generic, BTables& unit_in, bool* has_unit) {
+    W2L_REQUIRE(g->cin >= 1 && g->cout >= 1 && g->kh >= 1 && g->kw >= 1 && g->kh * g->kw <= kMaxTaps, "bad geometry");
+    W2L_REQUIRE(g->sh >= 1 && g->sw >= 1 && g->ph >= 0 && g->pw >= 0, "bad stride/pad");
+    W2L_REQUIRE(g->act >= W2L_ACT_NONE && g->act <= W2L_ACT_LEAKY, "bad act %d", g->act);
+    W2L_REQUIRE(g->transposed || (g->oph == 0 && g->opw == 0), "output_padding on a plain conv");
+    *cin_p = round_up(g->cin, 8);
+    *cout_p = round_up(g->cout, 32);
+    *has_unit = g->transposed && g->sh == 1 && g->sw == 1 && g->kh * g->kw <= kMaxPhases;
+    int rc = build_tables(*g, *cin_p, *cout_p, false, generic);
+    if (rc == W2L_OK && *has_unit) rc = build_tables(*g, *cin_p, *cout_p, true, unit_in);
+    return rc;
 }
 
 static void freeb(BVariant& v) {
@@ -806,7 +818,7 @@ static int convb_init_attrs() {
     return W2L_OK;
 }
 
-static int max_stepsb(const BVariant& v) {
+static int max_stepsb(const BTables& v) {
     int m = 0;
     for (int i = 0; i < v.nphase; ++i) m = v.ph[i].kp / kBKH > m ? v.ph[i].kp / kBKH : m;
     return m;
@@ -816,20 +828,19 @@ static int max_stepsb(const BVariant& v) {
 // generator's training shapes (profiles/r03/d_bf16_conv_sweep.txt): N-tile = the layer's couts up to 128 (a 32-cout layer on a
 // 128-wide tile multiplies 75 % padding), M-tile 128 unless that leaves the chip under-filled, split-K for the deep
 // small-spatial layers whose grid cannot reach one workgroup per CU otherwise
-static void pickb(const w2l_convb* c, const BVariant& v, int M, int* tile, int* ksplit) {
-    const int bn = c->cout_p <= 32 ? 32 : (c->cout_p <= 64 ? 64 : 128);
+static void pickb(int cout_p, const BTables& v, int M, int* tile, int* ksplit) {
+    const int bn = cout_p <= 32 ? 32 : (cout_p <= 64 ? 64 : 128);
     int bm = 128;
-    const long long blocks128 = (long long)ceil_div(M, 128) * ceil_div(c->cout_p, bn) * v.nphase;
+    const long long blocks128 = (long long)ceil_div(M, 128) * ceil_div(cout_p, bn) * v.nphase;
     if (bn != 32 && blocks128 < 384) bm = 64;
     int ti = 0;
     for (int i = 0; i < kNumBTiles; ++i)
         if (kBTiles[i].bm == bm && kBTiles[i].bn == bn) ti = i;
     // the eight-wave 256x256 tile (128x64 wave tiles: 6 fragment reads per 8 MFMAs instead of 8): only where its N tiles are full
     // (cout a multiple of 256) and >= 512 of them fill the chip twice - 256 -> 256 at 24x24 x 320 frames 0.227 -> 0.209 ms, 384-
-    // and 512-channel layers lose (half-empty N tile / too few M tiles): profiles/r06/i_bf16_sweep_all_tiles.log.  W2L_CONVB_T256=0: off
-    static const bool t256_on = [] { const char* e = getenv("W2L_CONVB_T256"); return e ? atoi(e) != 0 : true; }();
-    if (t256_on && bm == 128 && c->cout_p % 256 == 0 && (long long)ceil_div(M, 256) * (c->cout_p / 256) * v.nphase >= 512) ti = 5;
-    const long long blocks = (long long)ceil_div(M, kBTiles[ti].bm) * ceil_div(c->cout_p, kBTiles[ti].bn) * v.nphase;
+    // and 512-channel layers lose (half-empty N tile / too few M tiles): profiles/r06/i_bf16_sweep_all_tiles.log
+    if (bm == 128 && cout_p % 256 == 0 && (long long)ceil_div(M, 256) * (cout_p / 256) * v.nphase >= 512) ti = 5;
+    const long long blocks = (long long)ceil_div(M, kBTiles[ti].bm) * ceil_div(cout_p, kBTiles[ti].bn) * v.nphase;
     const int steps = max_stepsb(v);
     int ks = 1;
     while (ks < 16 && blocks * ks * 2 <= 512 && steps / (ks * 2) >= 4) ks *= 2;
@@ -845,19 +856,15 @@ extern "C" {
 
 int w2l_convb_create(const w2l_conv_geom* g, const float* weight, void* stream, w2l_convb_t** out) {
     W2L_REQUIRE(g && weight && out, "NULL argument");
-    W2L_REQUIRE(g->cin >= 1 && g->cout >= 1 && g->kh >= 1 && g->kw >= 1 && g->kh * g->kw <= kMaxTaps, "bad geometry");
-    W2L_REQUIRE(g->sh >= 1 && g->sw >= 1 && g->ph >= 0 && g->pw >= 0, "bad stride/pad");
-    W2L_REQUIRE(g->act >= W2L_ACT_NONE && g->act <= W2L_ACT_LEAKY, "bad act %d", g->act);
-    W2L_REQUIRE(g->transposed || (g->oph == 0 && g->opw == 0), "output_padding on a plain conv");
-    if (convb_init_attrs() != W2L_OK) return W2L_ERR_HIP;
     w2l_convb* c = new (std::nothrow) w2l_convb();
     if (!c) { set_error("out of host memory"); return W2L_ERR_NOMEM; }
     c->g = *g;
-    c->cin_p = round_up(g->cin, 8);
-    c->cout_p = round_up(g->cout, 32);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = buildb(c, c->generic, false);
-    if (rc == W2L_OK && g->transposed && g->sh == 1 && g->sw == 1 && g->kh * g->kw <= kMaxPhases) rc = buildb(c, c->unit_in, true);
+    bool has_unit = false;
+    int rc = geom_tables(g, &c->cin_p, &c->cout_p, c->generic, c->unit_in, &has_unit);
+    if (rc == W2L_OK) rc = convb_init_attrs();
+    if (rc == W2L_OK) rc = uploadb(c->generic);
+    if (rc == W2L_OK && has_unit) rc = uploadb(c->unit_in);
     if (rc == W2L_OK) rc = w2l_convb_update(c, weight, stream);
     if (rc == W2L_OK && hipStreamSynchronize(s) != hipSuccess) { set_error("sync after bf16 weight packing failed"); rc = W2L_ERR_HIP; }
     if (rc != W2L_OK) { w2l_convb_destroy(c); return rc; }
@@ -1024,220 +1031,191 @@ int w2l_convb_num_tiles(void) { return kNumBTiles; }
 
 }  // extern "C"
 
-// stats_out != NULL: BatchNorm statistics wanted.  If this launch can carry them in its epilogue (no split-K) *stats_out receives
-// the partial buffer [*npart_out][2][cout_p] (stream scratch), else NULL and the caller runs the column reduction over y.
-struct BnBwdOperands {      // the BatchNorm block whose dy this launch produces (w2l_convb_forward_bnbwd)
-    const void* z;
-    const void* y;          // or NULL: ReLU block without residual, mask from z * scale + shift
-    int z_cs, y_cs, act;
-    const float* mean;
-    const float* rstd;
-    const float* scale;
-    const float* shift;
-    int store_g;            // ReLU block: the launch stores the masked gradient (W2L_BNBWD_STORE_MASKED)
+// ---- resolution: which kernel a launch runs, as a function of the shape alone ------------------
+// what w2l_convb_resolve reports, plus what the launcher needs to run it
+struct BLaunch {
+    int family, tile, ksplit;   // W2L_CONVB_*; igemm: kBTiles index and split-K, stem: the stem kernel's layer family, else -1 / 1
+    bool unit;                  // on the unit-input variant's tables
+    long long flops;            // FLOPs the matrix cores execute: padded tiles and K (w2l_flops_begin, w2l_plan_executed_flops)
+    int Ho, Wo, Hq, Wq, M;      // output extent; rows per phase of the implicit GEMM: M = N * Hq * Wq
+    int steps_per_split;        // igemm: K-steps per split
 };
 
-// set by a dry run (w2l_plan_executed_flops, w2l_convb_resolve): the branch that would launch stores its executed FLOPs and what it
-// chose here and launches nothing
-struct ConvbDry {
-    long long flops = 0;
-    int family = W2L_CONVB_IGEMM, tile = -1, ksplit = 1;
-};
-static thread_local ConvbDry* t_dry = nullptr;
-
-static int convb_forward_impl(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, void* y, int y_cs,
-                              const void* res, int res_cs, const float* scale, const float* shift, int ksplit_force,
-                              float** stats_out, int* npart_out, const BnBwdOperands* bb = nullptr) {
-    W2L_REQUIRE(c && x && y, "NULL argument");
+// The families in the order they are tried; the first whose rule accepts the shape runs it:
+//   1. stem   (conv_stem_bf16.hip)  7x7 stems and the 3x3 small-channel layers, input box + weight set resident in LDS
+//   2. box64  (conv_box_bf16.hip)   3x3 / stride 1 / 64 -> 64
+//   3. tp2b   (conv_tp2b_bf16.hip)  3x3 / stride 2 transposed, all four phases per workgroup
+//   4. igemm  (this file)           everything else: tile and split-K from pickb, then the overrides and clamps
+// A unit-input launch, a tile override and a forced split-K all mean the implicit GEMM.  unit_in: the layer's unit-input tables or
+// NULL.  Pure: reads no device, no handle, no environment.
+static int resolve_b(const w2l_conv_geom& g, int cin_p, int cout_p, const BTables& generic, const BTables* unit_in, int N, int H, int W,
+                     bool has_res, int tile_override, int ksplit_force, BLaunch* out) {
     W2L_REQUIRE(N >= 1 && H >= 1 && W >= 1, "bad shape N=%d H=%d W=%d", N, H, W);
-    const int cout8 = round_up(c->g.cout, 8);
+    BLaunch L;
+    if (w2l_conv_out_hw(&g, H, W, &L.Ho, &L.Wo) != W2L_OK) return W2L_ERR_ARG;
+    const int Ho = L.Ho, Wo = L.Wo;
+    W2L_REQUIRE(Ho >= 1 && Wo >= 1, "empty output %dx%d", Ho, Wo);
+    L.unit = g.transposed && g.sh == 1 && g.sw == 1 && H == 1 && W == 1 && unit_in != nullptr;
+    const BTables& v = L.unit ? *unit_in : generic;
+    if (L.unit) { L.Hq = 1; L.Wq = 1; }
+    else if (v.q_is_out) { L.Hq = Ho; L.Wq = Wo; }
+    else { L.Hq = ceil_div(Ho, v.omy); L.Wq = ceil_div(Wo, v.omx); }
+    const long long M = (long long)N * L.Hq * L.Wq;
+    W2L_REQUIRE(M < (1ll << 31), "tensor too large");
+    L.M = (int)M;
+    L.tile = -1; L.ksplit = 1; L.steps_per_split = 0;
+    const bool special = !L.unit && tile_override < 0 && ksplit_force < 1;
+    const bool dense_out = v.q_is_out || (v.omy == 1 && v.omx == 1);
+    int stem_fam = 0;
+    if (special && dense_out && v.nphase == 1 && v.ph[0].ntaps == g.kh * g.kw && Ho == H && Wo == W && v.sy == 1 && v.sx == 1 &&
+        (stem_fam = stem_ok(g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, cin_p, g.cout, N, H, W, has_res)) != 0) {
+        L.family = W2L_CONVB_STEM; L.tile = stem_fam;
+        L.flops = 2ll * N * H * W * cout_p * v.ph[0].kp;
+    } else if (special && dense_out && g.kh == 3 && g.kw == 3 && g.ph == 1 && g.pw == 1 && v.ph[0].kp == 576 &&
+               box64_ok(v.nphase, v.ph[0].ntaps, cin_p, g.cout, cout_p, N, H, W, Ho, Wo, v.sy, v.sx)) {
+        L.family = W2L_CONVB_BOX64;
+        L.flops = 2ll * N * H * W * 64 * 576;
+    } else if (special && tp2b_ok(g.transposed, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, v.nphase, v.ph, v.taps_host.data(), cin_p, cout_p, N, H,
+                                  W, Ho, Wo)) {
+        long long k = 0;                    // unpadded: the kernel walks 32-channel chunks of each (phase, tap) row
+        for (int i = 0; i < v.nphase; ++i) k += (long long)v.ph[i].ntaps * cin_p;
+        L.family = W2L_CONVB_TP2B;
+        L.flops = 2ll * N * H * W * cout_p * k;
+    } else {
+        int ti, ks;
+        pickb(cout_p, v, L.M, &ti, &ks);
+        if (tile_override >= 0) { ti = tile_override; ks = 1; }
+        if (ksplit_force >= 1) ks = ksplit_force;
+        const int steps = max_stepsb(v);
+        if (ks > steps) ks = steps;
+        if (ks < 1) ks = 1;
+        L.steps_per_split = ceil_div(steps, ks);
+        L.family = W2L_CONVB_IGEMM; L.tile = ti;
+        L.ksplit = ceil_div(steps, L.steps_per_split);
+        long long kp = 0;
+        for (int i = 0; i < v.nphase; ++i) kp += v.ph[i].kp;
+        L.flops = 2ll * ceil_div(L.M, kBTiles[ti].bm) * kBTiles[ti].bm * ceil_div(cout_p, kBTiles[ti].bn) * kBTiles[ti].bn * kp;
+    }
+    *out = L;
+    return W2L_OK;
+}
+
+static int resolve_layer(const w2l_convb_t* c, int N, int H, int W, bool has_res, int ksplit_force, BLaunch* out) {
+    return resolve_b(c->g, c->cin_p, c->cout_p, c->generic, c->unit_in.built ? &c->unit_in : nullptr, N, H, W, has_res, c->tile_override,
+                     ksplit_force, out);
+}
+
+// buffer descriptors use 32-bit byte offsets with 0x80000000 as "out of range"; res_cs 0: no residual
+static int check_2gib(int N, int H, int W, int x_cs, int Ho, int Wo, int y_cs, int res_cs) {
+    const long long lim = 1ll << 31;
+    W2L_REQUIRE(((long long)N * H * W * x_cs) * 2 < lim && ((long long)N * Ho * Wo * y_cs) * 2 < lim && ((long long)N * Ho * Wo * res_cs) * 2 < lim,
+                "activation buffer larger than 2 GiB: split the batch");
+    return W2L_OK;
+}
+
+// resolve_b for dense buffers (what w2l_convb_resolve and w2l_convb_resolve_geom answer for)
+static int resolve_dense(const w2l_conv_geom& g, int cin_p, int cout_p, const BTables& generic, const BTables* unit_in, int N, int H, int W,
+                         bool has_res, int tile_override, BLaunch* out) {
+    const int rc = resolve_b(g, cin_p, cout_p, generic, unit_in, N, H, W, has_res, tile_override, 0, out);
+    return rc != W2L_OK ? rc : check_2gib(N, H, W, cin_p, out->Ho, out->Wo, cout_p, has_res ? cout_p : 0);
+}
+
+static float act_neg_slope(int act) { return act == W2L_ACT_RELU ? 0.f : (act == W2L_ACT_LEAKY ? 0.01f : 1.f); }
+
+// the b* fields of ConvBArgs from a BNBWD / MASK epilogue; ep NULL: none
+static void bind_epilogue(ConvBArgs& a, const BEpilogue* ep) {
+    const BEpilogue e = ep ? *ep : BEpilogue();
+    a.bz = e.z; a.by = e.y; a.bz_cs = e.z_cs; a.by_cs = e.y_cs;
+    a.bmean = e.mean; a.brstd = e.rstd; a.bscale = e.scale; a.bshift = e.shift;
+    a.bneg = e.neg;
+    a.bstore_g = e.kind == BEpilogue::BNBWD ? e.store_g : 0;
+    a.bmask_only = e.kind == BEpilogue::MASK;
+}
+
+// per-wave column partials [npart][2][cout_p] for the launch's epilogue, in the stream's scratch
+static float* epilogue_partials(hipStream_t s, int npart, int cout_p, BEpilogueOut* eo) {
+    float* part = conv_workspace(s, (size_t)npart * 2 * cout_p * sizeof(float));
+    if (part) { eo->part = part; eo->npart = npart; }
+    return part;
+}
+
+// ---- the launcher: validate the operands, resolve, bind the epilogue, launch the resolved family ---
+// ep != NULL (with eo): an epilogue request; *eo says whether this launch could carry it (split-K launches and some families cannot:
+// the caller then runs the stand-alone pass)
+static int convb_launch(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, void* y, int y_cs,
+                        const void* res, int res_cs, const float* scale, const float* shift, int ksplit_force,
+                        const BEpilogue* ep = nullptr, BEpilogueOut* eo = nullptr) {
+    W2L_REQUIRE(c && x && y, "NULL argument");
+    const w2l_conv_geom& g = c->g;
+    const int cout8 = round_up(g.cout, 8);
     W2L_REQUIRE(x_cs >= c->cin_p && (x_cs & 7) == 0, "x_cs=%d must be a multiple of 8 and >= %d", x_cs, c->cin_p);
     W2L_REQUIRE(y_cs >= cout8 && (y_cs & 7) == 0, "y_cs=%d must be a multiple of 8 and >= %d", y_cs, cout8);
     W2L_REQUIRE(res == nullptr || (res_cs >= cout8 && (res_cs & 7) == 0), "res_cs=%d must be a multiple of 8 and >= %d", res_cs, cout8);
     W2L_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res)) & 15) == 0,
                 "x / y / res must be 16-byte aligned");
-    const w2l_conv_geom& g = c->g;
-    int Ho, Wo;
-    if (w2l_conv_out_hw(&g, H, W, &Ho, &Wo) != W2L_OK) return W2L_ERR_ARG;
-    W2L_REQUIRE(Ho >= 1 && Wo >= 1, "empty output %dx%d", Ho, Wo);
-    const long long lim = 1ll << 31;   // buffer descriptors use 32-bit byte offsets with 0x80000000 as "out of range"
-    W2L_REQUIRE(((long long)N * H * W * x_cs) * 2 < lim && ((long long)N * Ho * Wo * y_cs) * 2 < lim &&
-                    (res == nullptr || ((long long)N * Ho * Wo * res_cs) * 2 < lim),
-                "activation buffer larger than 2 GiB: split the batch");
-    const bool unit = g.transposed && g.sh == 1 && g.sw == 1 && H == 1 && W == 1 && c->unit_in.built;
-    const BVariant& v = unit ? c->unit_in : c->generic;
+    BLaunch L;
+    int rc = resolve_layer(c, N, H, W, res != nullptr, ksplit_force, &L);
+    if (rc == W2L_OK) rc = check_2gib(N, H, W, x_cs, L.Ho, L.Wo, y_cs, res ? res_cs : 0);
+    if (rc != W2L_OK) return rc;
+    if (flops_counting()) flops_add(L.flops, 5);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const BVariant& v = L.unit ? c->unit_in : c->generic;
+    if (eo) *eo = BEpilogueOut();
+    float* stats = nullptr;
+    switch (L.family) {
+    case W2L_CONVB_STEM:        // no partials / sums: the stand-alone reductions follow (few channels: cheap passes)
+        return stem_launch(s, x, x_cs, y, y_cs, res, res_cs, v.w_dev, c->cout_p, v.ph[0].kp, scale, shift, v.taps_dev, N, H, W, g.kh,
+                           c->cin_p, g.cout, g.act);
+    case W2L_CONVB_BOX64:       // forward statistics or the BatchNorm-backward sums: per-wave partials; no mask-only form
+        if (ep && ep->kind != BEpilogue::MASK && !(stats = epilogue_partials(s, box64_grid(N, H, W) * 8, c->cout_p, eo))) return W2L_ERR_NOMEM;
+        return box64_launch(s, x, x_cs, y, y_cs, res, res_cs, v.w_dev, scale, shift, v.taps_dev, stats, N, H, W, g.cout, g.act,
+                            ep && ep->kind == BEpilogue::BNBWD ? ep : nullptr);
+    case W2L_CONVB_TP2B:        // forward statistics only (a data-gradient launch reports "not fused")
+        if (ep && ep->kind == BEpilogue::STATS && !(stats = epilogue_partials(s, tp2b_npart(N, H, W), c->cout_p, eo))) return W2L_ERR_NOMEM;
+        return tp2b_launch(s, x, x_cs, y, y_cs, res, res_cs, v.w_dev, v.w_elems, scale, shift, stats, v.ph, N, H, W, c->cin_p, g.cout,
+                           c->cout_p, g.act);
+    default:
+        break;
+    }
+    const BTile& tc = kBTiles[L.tile];
     ConvBArgs a;
     a.x = x; a.y = y; a.res = res; a.w = v.w_dev; a.scale = scale; a.shift = shift; a.taps = v.taps_dev;
     a.N = N; a.H = H; a.W = W; a.cin_p = c->cin_p; a.x_cs = x_cs;
-    a.Ho = Ho; a.Wo = Wo; a.cout = g.cout; a.cout_p = c->cout_p; a.y_cs = y_cs; a.res_cs = res_cs;
-    if (unit) { a.Hq = 1; a.Wq = 1; }
-    else if (v.q_is_out) { a.Hq = Ho; a.Wq = Wo; }
-    else { a.Hq = ceil_div(Ho, v.omy); a.Wq = ceil_div(Wo, v.omx); }
-    a.sy = v.sy; a.sx = v.sx; a.omy = v.omy; a.omx = v.omx;
+    a.Ho = L.Ho; a.Wo = L.Wo; a.cout = g.cout; a.cout_p = c->cout_p; a.y_cs = y_cs; a.res_cs = res_cs;
+    a.Hq = L.Hq; a.Wq = L.Wq; a.sy = v.sy; a.sx = v.sx; a.omy = v.omy; a.omx = v.omx;
     a.act = g.act;
-    const long long M = (long long)N * a.Hq * a.Wq;
-    W2L_REQUIRE(M < lim, "tensor too large");
-    a.M = (int)M;
+    a.M = L.M;
     for (int i = 0; i < v.nphase; ++i) a.ph[i] = v.ph[i];
-    // W2L_CONVB_BOX=0 (read once): every layer on the implicit GEMM below - A/B switch of the LDS-resident-box kernel
-    static const int box_level = [] { const char* e = getenv("W2L_CONVB_BOX"); return e ? atoi(e) : 1; }();   // 2: without the 3x3 small-channel families (A/B)
-    const bool box_on = box_level != 0;
-    int stem_fam = 0;
-    if (box_on && !unit && (v.q_is_out || (v.omy == 1 && v.omx == 1)) && c->tile_override < 0 && ksplit_force < 1 && v.nphase == 1 &&
-        v.ph[0].ntaps == g.kh * g.kw && Ho == H && Wo == W && v.sy == 1 && v.sx == 1 && (g.kh == 7 || box_level != 2) &&
-        (stem_fam = stem_ok(g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, c->cin_p, g.cout, N, H, W, res != nullptr)) != 0) {
-        if (stats_out) *stats_out = nullptr;      // no partials / sums: the stand-alone reductions follow (few channels: cheap passes)
-        if (t_dry) {
-            t_dry->flops = 2ll * N * H * W * c->cout_p * v.ph[0].kp;
-            t_dry->family = W2L_CONVB_STEM; t_dry->tile = stem_fam; t_dry->ksplit = 1;
-            return W2L_OK;
-        }
-        if (flops_counting()) flops_add(2ll * N * H * W * c->cout_p * v.ph[0].kp, 5);
-        return stem_launch(static_cast<hipStream_t>(stream), x, x_cs, y, y_cs, res, res_cs, v.w_dev, c->cout_p, v.ph[0].kp, scale, shift,
-                           v.taps_dev, N, H, W, g.kh, c->cin_p, g.cout, g.act);
-    }
-    if (box_on && !unit && (v.q_is_out || (v.omy == 1 && v.omx == 1)) && c->tile_override < 0 && ksplit_force < 1 && g.kh == 3 && g.kw == 3 && g.ph == 1 && g.pw == 1 &&
-        v.ph[0].kp == 576 && box64_ok(v.nphase, v.ph[0].ntaps, c->cin_p, g.cout, c->cout_p, N, H, W, Ho, Wo, v.sy, v.sx)) {
-        // forward statistics, or (bb) the BatchNorm-backward sums of the block whose dy this launch completes: per-wave partials
-        static const bool box_bwd = [] { const char* e = getenv("W2L_BOX_BWD_SUMS"); return e ? atoi(e) != 0 : true; }();   // A/B switch
-        if (t_dry) {
-            t_dry->flops = 2ll * N * H * W * 64 * 576;
-            t_dry->family = W2L_CONVB_BOX64; t_dry->tile = -1; t_dry->ksplit = 1;
-            return W2L_OK;
-        }
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        float* stats = nullptr;
-        BoxBwd bw;
-        const bool bwd = bb != nullptr && bb->z != nullptr && box_bwd && stats_out != nullptr;
-        if (stats_out) {
-            *stats_out = nullptr;
-            if (!bb || bwd) {
-                const int npart = box64_grid(N, H, W) * 8;
-                stats = conv_workspace(s, (size_t)npart * 2 * c->cout_p * sizeof(float));
-                if (!stats) return W2L_ERR_NOMEM;
-                *stats_out = stats;
-                *npart_out = npart;
-            }
-        }
-        if (bwd) {
-            bw.z = bb->z; bw.y = bb->y; bw.z_cs = bb->z_cs; bw.y_cs = bb->y_cs; bw.store_g = bb->store_g;
-            bw.neg = bb->act == W2L_ACT_RELU ? 0.f : (bb->act == W2L_ACT_LEAKY ? 0.01f : 1.f);
-            bw.mean = bb->mean; bw.rstd = bb->rstd; bw.scale = bb->scale; bw.shift = bb->shift;
-        }
-        if (flops_counting()) flops_add(2ll * N * H * W * 64 * 576, 5);
-        return box64_launch(s, x, x_cs, y, y_cs, res, res_cs, v.w_dev, scale, shift, v.taps_dev, stats, N, H, W, g.cout, g.act,
-                            bwd ? &bw : nullptr);
-    }
-    // W2L_CONVB_TP2B=0 (read once): the stride-2 transposed layers stay on the four-phase implicit GEMM below (A/B switch)
-    static const bool tp2b_on = [] { const char* e = getenv("W2L_CONVB_TP2B"); return e ? atoi(e) != 0 : true; }();
-    if (tp2b_on && !unit && c->tile_override < 0 && ksplit_force < 1 &&
-        tp2b_ok(g.transposed, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, v.nphase, v.ph, v.taps_host.data(), c->cin_p, c->cout_p, N, H, W, Ho, Wo)) {
-        if (t_dry) {
-            long long kp = 0;
-            for (int i = 0; i < v.nphase; ++i) kp += (long long)v.ph[i].ntaps * c->cin_p;
-            t_dry->flops = 2ll * N * H * W * c->cout_p * kp;
-            t_dry->family = W2L_CONVB_TP2B; t_dry->tile = -1; t_dry->ksplit = 1;
-            return W2L_OK;
-        }
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        float* stats = nullptr;
-        if (stats_out) {
-            *stats_out = nullptr;       // (a data-gradient launch with `bb` reports "not fused": the stand-alone reduction runs)
-            if (!bb) {
-                const int npart = tp2b_npart(c->cout_p, N, H, W);
-                stats = conv_workspace(s, (size_t)npart * 2 * c->cout_p * sizeof(float));
-                if (!stats) return W2L_ERR_NOMEM;
-                *stats_out = stats;
-                *npart_out = npart;
-            }
-        }
-        if (flops_counting()) {
-            long long kp = 0;
-            for (int i = 0; i < v.nphase; ++i) kp += (long long)v.ph[i].ntaps * c->cin_p;
-            flops_add(2ll * N * H * W * c->cout_p * kp, 5);
-        }
-        return tp2b_launch(s, x, x_cs, y, y_cs, res, res_cs, v.w_dev, v.w_elems, scale, shift, stats, v.ph, v.taps_host.data(), N, H, W,
-                           c->cin_p, g.cout, c->cout_p, g.act);
-    }
-    int ti, ks;
-    pickb(c, v, a.M, &ti, &ks);
-    if (c->tile_override >= 0) { ti = c->tile_override; ks = 1; }
-    if (ksplit_force >= 1) ks = ksplit_force;
-    const int steps = max_stepsb(v);
-    if (ks > steps) ks = steps;
-    if (ks < 1) ks = 1;
-    a.steps_per_split = ceil_div(steps, ks);
-    a.ksplit = ceil_div(steps, a.steps_per_split);
+    a.steps_per_split = L.steps_per_split;
+    a.ksplit = L.ksplit;
     a.ws = nullptr;
     a.stats = nullptr;
-    a.bz = nullptr; a.by = nullptr; a.bmean = nullptr; a.brstd = nullptr; a.bscale = nullptr; a.bshift = nullptr;
-    a.bz_cs = 0; a.by_cs = 0; a.bneg = 1.f; a.bstore_g = 0; a.bmask_only = 0;
-    const BTile& tc = kBTiles[ti];
-    if (t_dry) {
-        long long kp = 0;
-        for (int i = 0; i < v.nphase; ++i) kp += v.ph[i].kp;
-        t_dry->flops = 2ll * ceil_div(a.M, tc.bm) * tc.bm * ceil_div(c->cout_p, tc.bn) * tc.bn * kp;
-        t_dry->family = W2L_CONVB_IGEMM; t_dry->tile = ti; t_dry->ksplit = a.ksplit;
-        return W2L_OK;
+    a.tiles_m = ceil_div(a.M, tc.bm);
+    a.tiles_n = ceil_div(c->cout_p, tc.bn);
+    const bool carried = ep && a.ksplit == 1;       // un-split launches carry every epilogue
+    bind_epilogue(a, carried && ep->kind != BEpilogue::STATS ? ep : nullptr);
+    if (carried) {
+        // a mask-only launch has partials only where the column sums of the stored dz (the block's bias gradient) are wanted
+        if ((ep->kind != BEpilogue::MASK || ep->store_g) &&
+            !(a.stats = epilogue_partials(s, v.nphase * a.tiles_m * tc.wm, c->cout_p, eo)))
+            return W2L_ERR_NOMEM;
+        eo->masked = ep->kind == BEpilogue::MASK;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long npix = (long long)N * Ho * Wo;
-    if (stats_out && !(bb && bb->z == nullptr)) {
-        *stats_out = nullptr;
-        if (a.ksplit == 1) {
-            const int npart = v.nphase * ceil_div(a.M, tc.bm) * tc.wm;
-            a.stats = conv_workspace(s, (size_t)npart * 2 * c->cout_p * sizeof(float));
-            if (!a.stats) return W2L_ERR_NOMEM;
-            *stats_out = a.stats;
-            *npart_out = npart;
-            if (bb) {
-                a.bz = bb->z; a.by = bb->y; a.bz_cs = bb->z_cs; a.by_cs = bb->y_cs;
-                a.bmean = bb->mean; a.brstd = bb->rstd; a.bscale = bb->scale; a.bshift = bb->shift;
-                a.bneg = bb->act == W2L_ACT_RELU ? 0.f : (bb->act == W2L_ACT_LEAKY ? 0.01f : 1.f);
-                a.bstore_g = bb->store_g;
-            }
-        }
-    }
-    if (bb && bb->z == nullptr && stats_out) {      // mask-only request (w2l_convb_forward_actbwd): served by un-split launches
-        *stats_out = nullptr;
-        if (a.ksplit == 1) {
-            a.by = bb->y; a.by_cs = bb->y_cs; a.bmask_only = 1;
-            a.bneg = bb->act == W2L_ACT_RELU ? 0.f : (bb->act == W2L_ACT_LEAKY ? 0.01f : 1.f);
-            *npart_out = -1;                         // "masked": the output IS the masked gradient
-            if (bb->store_g) {
-                // ... and its per-wave column sums (the forward-statistics accumulators over the stored values: sum dz is the
-                // block's bias gradient) are wanted too
-                const int npart = v.nphase * ceil_div(a.M, tc.bm) * tc.wm;
-                a.stats = conv_workspace(s, (size_t)npart * 2 * c->cout_p * sizeof(float));
-                if (!a.stats) return W2L_ERR_NOMEM;
-                *stats_out = a.stats;
-                *npart_out = -npart - 1;             // <= -2: masked, with npart partial rows
-            }
-        }
-    }
+    const long long npix = (long long)N * L.Ho * L.Wo;
     if (a.ksplit > 1) {
         a.ws = conv_workspace(s, (size_t)a.ksplit * npix * c->cout_p * sizeof(float));
         if (!a.ws) return W2L_ERR_NOMEM;
         // Every (split, output pixel, channel < round8(cout)) entry the reduce kernel reads is WRITTEN by the workgroup that owns
         // the pixel's tile row in that split - a split whose K range holds only padding writes zeros - provided every phase has
         // taps (a phase without taps launches no K-step and its pixels would stay unwritten: kernel smaller than the stride).
-        // Only then are the partials cleared first.  (Rounds 3-5 cleared them always: 46 memsets per wav2lip_train step.)
-        // W2L_SPLITK_MEMSET=1 restores that (A/B).
-        static const bool always = [] { const char* e = getenv("W2L_SPLITK_MEMSET"); return e ? atoi(e) != 0 : false; }();
-        bool need = always;
+        // Only then are the partials cleared first.
+        bool need = false;
         for (int i = 0; i < v.nphase; ++i) need |= v.ph[i].ntaps <= 0;
-        need |= !v.q_is_out && !unit && (Ho % v.omy || Wo % v.omx);      // ragged transposed extents: as conv_igemm.hip keeps it
+        need |= !v.q_is_out && !L.unit && (L.Ho % v.omy || L.Wo % v.omx);      // ragged transposed extents: as conv_igemm.hip keeps it
         if (need) W2L_HIP_CHECK(hipMemsetAsync(a.ws, 0, (size_t)a.ksplit * npix * c->cout_p * sizeof(float), s));
     }
-    a.tiles_m = ceil_div(a.M, tc.bm);
-    a.tiles_n = ceil_div(c->cout_p, tc.bn);
     const long long nblk = (long long)a.tiles_m * a.tiles_n;
-    W2L_REQUIRE(nblk < lim, "grid too large");
-    if (flops_counting()) {
-        long long kp = 0;
-        for (int i = 0; i < v.nphase; ++i) kp += v.ph[i].kp;
-        flops_add(2ll * a.tiles_m * tc.bm * a.tiles_n * tc.bn * kp, 5);
-    }
+    W2L_REQUIRE(nblk < (1ll << 31), "grid too large");
     hipLaunchKernelGGL(tc.kernel, dim3((unsigned)nblk, v.nphase, a.ksplit), dim3(tc.threads), tc.lds, s, a);
     W2L_HIP_CHECK(hipGetLastError());
     if (a.ksplit > 1) {
@@ -1257,7 +1235,7 @@ extern "C" {
 int w2l_convb_forward(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, void* y, int y_cs,
                       const void* res, int res_cs, const float* scale, const float* shift, int ksplit_force) {
     W2L_REQUIRE(c == nullptr || c->k3_u == nullptr, "convb_forward: the layer has a fused head, run it with w2l_convb_forward_head");
-    return convb_forward_impl(c, stream, N, H, W, x, x_cs, y, y_cs, res, res_cs, scale, shift, ksplit_force, nullptr, nullptr);
+    return convb_launch(c, stream, N, H, W, x, x_cs, y, y_cs, res, res_cs, scale, shift, ksplit_force);
 }
 
 }  // extern "C"
@@ -1284,16 +1262,15 @@ int convb_head_impl(const w2l_convb_t* c, void* stream, int N, int H, int W, con
                        c->head_act, N, H, W, c->g.cin, c->g.act, static_cast<hipStream_t>(stream), flops_out);
 }
 
-// plan items (api.hip): a plain launch; flops_out != NULL: dry run
+// plan items (api.hip): a plain launch; flops_out != NULL: the executed FLOPs of the launch the shape rules resolve to, counted as
+// w2l_flops_begin counts them - nothing is launched
 int convb_plan_launch(const w2l_convb_t* c, void* stream, int N, int H, int W, const void* x, int x_cs, void* y, int y_cs,
                       const void* res, int res_cs, const float* scale, const float* shift, long long* flops_out) {
-    if (!flops_out) return convb_forward_impl(c, stream, N, H, W, x, x_cs, y, y_cs, res, res_cs, scale, shift, 0, nullptr, nullptr);
-    // executed FLOPs of the launch the shape rules resolve to, counted as w2l_flops_begin counts them; nothing is launched
-    ConvbDry dry;
-    t_dry = &dry;
-    const int rc = convb_forward_impl(c, stream, N, H, W, x, x_cs, y, y_cs, res, res_cs, scale, shift, 0, nullptr, nullptr);
-    t_dry = nullptr;
-    if (rc == W2L_OK) *flops_out = dry.flops;
+    if (!flops_out) return convb_launch(c, stream, N, H, W, x, x_cs, y, y_cs, res, res_cs, scale, shift, 0);
+    W2L_REQUIRE(c, "NULL argument");
+    BLaunch L;
+    const int rc = resolve_layer(c, N, H, W, res != nullptr, 0, &L);
+    if (rc == W2L_OK) *flops_out = L.flops;
     return rc;
 }
 }  // namespace w2l
@@ -1312,16 +1289,26 @@ int w2l_convb_resolve(const w2l_convb_t* c, int N, int H, int W, int has_res, in
         *family = W2L_CONVB_HEAD; *tile = -1; *ksplit = 1;
         return W2L_OK;
     }
-    // the launcher's dry run over dense strides; the operand pointers only pass its NULL / alignment checks, nothing reads them
-    alignas(16) static const unsigned char operand[16] = {};
-    const void* p = operand;
-    ConvbDry dry;
-    t_dry = &dry;
-    const int rc = convb_forward_impl(c, nullptr, N, H, W, p, c->cin_p, const_cast<void*>(p), c->cout_p, has_res ? p : nullptr,
-                                      c->cout_p, nullptr, nullptr, 0, nullptr, nullptr);
-    t_dry = nullptr;
+    BLaunch L;
+    const int rc = resolve_dense(c->g, c->cin_p, c->cout_p, c->generic, c->unit_in.built ? &c->unit_in : nullptr, N, H, W, has_res != 0,
+                                 c->tile_override, &L);
     if (rc != W2L_OK) return rc;
-    *family = dry.family; *tile = dry.tile; *ksplit = dry.ksplit;
+    *family = L.family; *tile = L.tile; *ksplit = L.ksplit;
+    return W2L_OK;
+}
+
+int w2l_convb_resolve_geom(const w2l_conv_geom* g, int N, int H, int W, int has_res, int* family, int* tile, int* ksplit,
+                           long long* flops) {
+    W2L_REQUIRE(g && family && tile && ksplit && flops, "NULL argument");
+    int cin_p, cout_p;
+    bool has_unit;
+    BTables generic, unit_in;
+    int rc = geom_tables(g, &cin_p, &cout_p, generic, unit_in, &has_unit);
+    if (rc != W2L_OK) return rc;
+    BLaunch L;
+    rc = resolve_dense(*g, cin_p, cout_p, generic, has_unit ? &unit_in : nullptr, N, H, W, has_res != 0, -1, &L);
+    if (rc != W2L_OK) return rc;
+    *family = L.family; *tile = L.tile; *ksplit = L.ksplit; *flops = L.flops;
     return W2L_OK;
 }
 
@@ -1330,17 +1317,17 @@ int w2l_convb_forward_bn(const w2l_convb_t* c, void* stream, int N, int H, int W
                          float* running_var, float* mean, float* rstd, float* scale, float* shift) {
     W2L_REQUIRE(c && mean && rstd && scale && shift, "NULL argument");
     W2L_REQUIRE(c->g.act == W2L_ACT_NONE, "convb_forward_bn: the layer in front of a batch-statistics BatchNorm has no activation");
-    float* part = nullptr;
-    int npart = 0;
-    int rc = convb_forward_impl(c, stream, N, H, W, x, x_cs, z, z_cs, nullptr, 0, nullptr, bias, 0, &part, &npart);
+    const BEpilogue ep;      // STATS
+    BEpilogueOut eo;
+    int rc = convb_launch(c, stream, N, H, W, x, x_cs, z, z_cs, nullptr, 0, nullptr, bias, 0, &ep, &eo);
     if (rc != W2L_OK) return rc;
     int Ho, Wo;
     if (w2l_conv_out_hw(&c->g, H, W, &Ho, &Wo) != W2L_OK) return W2L_ERR_ARG;
     const long long rows = (long long)N * Ho * Wo;
     const int C8 = round_up(c->g.cout, 8);
-    if (part)
-        return bn_stats_from_partials(static_cast<hipStream_t>(stream), part, npart, c->cout_p, rows, C8, c->g.cout, gamma, beta, eps,
-                                      momentum, running_mean, running_var, mean, rstd, scale, shift);
+    if (eo.part)
+        return bn_stats_from_partials(static_cast<hipStream_t>(stream), eo.part, eo.npart, c->cout_p, rows, C8, c->g.cout, gamma, beta,
+                                      eps, momentum, running_mean, running_var, mean, rstd, scale, shift);
     return w2l_bn_train_stats_bf16(stream, rows, C8, c->g.cout, z, z_cs, gamma, beta, eps, momentum, running_mean, running_var, mean,
                                    rstd, scale, shift);
 }
@@ -1365,14 +1352,16 @@ int w2l_convb_forward_bnbwd(const w2l_convb_t* c, void* stream, int N, int H, in
     if (w2l_conv_out_hw(&c->g, H, W, &Ho, &Wo) != W2L_OK) return W2L_ERR_ARG;
     W2L_REQUIRE(((long long)N * Ho * Wo * bz_cs) * 2 < (1ll << 31) && (by == nullptr || ((long long)N * Ho * Wo * by_cs) * 2 < (1ll << 31)),
                 "activation buffer larger than 2 GiB: split the batch");
-    BnBwdOperands bb = {bz, by, bz_cs, by_cs, bact, mean, rstd, bscale, bshift, store_g};
-    float* part = nullptr;
-    int npart = 0;
+    BEpilogue ep;
+    ep.kind = BEpilogue::BNBWD;
+    ep.z = bz; ep.y = by; ep.z_cs = bz_cs; ep.y_cs = by_cs; ep.neg = act_neg_slope(bact);
+    ep.mean = mean; ep.rstd = rstd; ep.scale = bscale; ep.shift = bshift; ep.store_g = store_g;
+    BEpilogueOut eo;
     *fused_out = 0;
-    int rc = convb_forward_impl(c, stream, N, H, W, x, x_cs, y, y_cs, res, res_cs, nullptr, nullptr, 0, &part, &npart, &bb);
-    if (rc != W2L_OK || !part) return rc;        // split-K launch: no sums, the caller runs the stand-alone reduction
+    int rc = convb_launch(c, stream, N, H, W, x, x_cs, y, y_cs, res, res_cs, nullptr, nullptr, 0, &ep, &eo);
+    if (rc != W2L_OK || !eo.part) return rc;        // split-K launch: no sums, the caller runs the stand-alone reduction
     *fused_out = 1;
-    return bn_bwd_sums_from_partials(static_cast<hipStream_t>(stream), part, npart, c->cout_p, C8, c->g.cout, dgamma, dbeta);
+    return bn_bwd_sums_from_partials(static_cast<hipStream_t>(stream), eo.part, eo.npart, c->cout_p, C8, c->g.cout, dgamma, dbeta);
 }
 
 /* header: w2l_convb_forward_actbwd */
@@ -1387,15 +1376,16 @@ int w2l_convb_forward_actbwd(const w2l_convb_t* c, void* stream, int N, int H, i
     int Ho, Wo;
     if (w2l_conv_out_hw(&c->g, H, W, &Ho, &Wo) != W2L_OK) return W2L_ERR_ARG;
     W2L_REQUIRE(((long long)N * Ho * Wo * by_cs) * 2 < (1ll << 31), "activation buffer larger than 2 GiB: split the batch");
-    BnBwdOperands bb = {nullptr, by, 0, by_cs, bact, nullptr, nullptr, nullptr, nullptr, dbias != nullptr ? 1 : 0};
-    float* part = nullptr;
-    int npart = 0;
+    BEpilogue ep;
+    ep.kind = BEpilogue::MASK;
+    ep.y = by; ep.y_cs = by_cs; ep.neg = act_neg_slope(bact); ep.store_g = dbias != nullptr;
+    BEpilogueOut eo;
     *fused_out = 0;
-    const int rc = convb_forward_impl(c, stream, N, H, W, x, x_cs, y, y_cs, res, res_cs, nullptr, nullptr, 0, &part, &npart, &bb);
-    if (rc != W2L_OK || npart >= 0) return rc;
+    const int rc = convb_launch(c, stream, N, H, W, x, x_cs, y, y_cs, res, res_cs, nullptr, nullptr, 0, &ep, &eo);
+    if (rc != W2L_OK || !eo.masked) return rc;
     *fused_out = 1;
-    if (dbias && part && npart <= -2)         // column sums of the stored dz: fixed-order two-level finish, pad entries zero
-        return bn_bwd_sums_from_partials(static_cast<hipStream_t>(stream), part, -npart - 1, c->cout_p, C8, c->g.cout, nullptr, dbias);
+    if (eo.part)         // column sums of the stored dz: fixed-order two-level finish, pad entries zero
+        return bn_bwd_sums_from_partials(static_cast<hipStream_t>(stream), eo.part, eo.npart, c->cout_p, C8, c->g.cout, nullptr, dbias);
     return W2L_OK;
 }
 

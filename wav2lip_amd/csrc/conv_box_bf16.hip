@@ -359,17 +359,6 @@ __global__ __launch_bounds__(512, 1) void conv_box64_bf16_kernel(const BoxArgs a
 }
 
 // ---- host side (called from conv_bf16.hip's launcher)
-struct BoxBwd {             // the block whose dy a BWD launch completes
-    const void* z;
-    const void* y;
-    int z_cs, y_cs, store_g;
-    float neg;
-    const float* mean;
-    const float* rstd;
-    const float* scale;
-    const float* shift;
-};
-
 // A shape-only rule (bit-reproducible): the layer must be LARGE - every workgroup fetches the 74 KB weight set once, which 8 tiles
 // amortise and 3 do not (64 @24x24 x 320 frames and 64 @46x47 x 64 pairs were measured slower here than on the implicit GEMM,
 // profiles/r04/z_*) - and its extents must fill their 16x16 tiles to 85 % (24x24 fills 56 %)
@@ -390,14 +379,11 @@ int box64_grid(int N, int H, int W) {
 
 int box64_launch(hipStream_t stream, const void* x, int x_cs, void* y, int y_cs, const void* res, int res_cs, const void* w,
                  const float* scale, const float* shift, const int* taps, float* stats, int N, int H, int W, int cout, int act,
-                 const BoxBwd* bwd) {
+                 const BEpilogue* bwd) {          // bwd: the BatchNorm block whose dy this launch completes, or NULL
     BoxArgs a;
-    a.bz = nullptr; a.by = nullptr; a.bmean = nullptr; a.brstd = nullptr; a.bscale = nullptr; a.bshift = nullptr;
-    a.bz_cs = 0; a.by_cs = 0; a.bstore_g = 0; a.bneg = 1.f;
-    if (bwd) {
-        a.bz = bwd->z; a.by = bwd->y; a.bz_cs = bwd->z_cs; a.by_cs = bwd->y_cs; a.bmean = bwd->mean; a.brstd = bwd->rstd;
-        a.bscale = bwd->scale; a.bshift = bwd->shift; a.bstore_g = bwd->store_g; a.bneg = bwd->neg;
-    }
+    const BEpilogue e = bwd ? *bwd : BEpilogue();
+    a.bz = e.z; a.by = e.y; a.bz_cs = e.z_cs; a.by_cs = e.y_cs; a.bmean = e.mean; a.brstd = e.rstd;
+    a.bscale = e.scale; a.bshift = e.shift; a.bstore_g = e.store_g; a.bneg = e.neg;
     a.x = x; a.y = y; a.res = res; a.w = w; a.scale = scale; a.shift = shift; a.taps = taps; a.stats = stats;
     a.N = N; a.H = H; a.W = W; a.x_cs = x_cs; a.y_cs = y_cs; a.res_cs = res_cs; a.cout = cout; a.act = act;
     a.tiles_x = (W + kBoxT - 1) / kBoxT; a.tiles_y = (H + kBoxT - 1) / kBoxT;

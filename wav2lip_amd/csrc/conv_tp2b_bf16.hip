@@ -282,20 +282,16 @@ __global__ __launch_bounds__(512) void conv_tp2b_bf16_kernel(const Tp2bArgs a) {
 // 1: the decoder's layers, and the data gradient of a 3x3 / stride 2 / padding 1 conv over an even extent), four phases whose taps
 // reach input offsets 0 / 1 only, cin a multiple of the 32-channel chunk.  A shape-only rule (bit-reproducible): the launch must
 // fill the chip (>= 256 workgroups) - smaller ones keep the implicit GEMM and its split-K.
-static int tp2b_level() {
-    static const int level = [] { const char* e = getenv("W2L_CONVB_TP2B"); return e ? atoi(e) : 1; }();
-    return level;
-}
-// 32-cout tiles: 128 registers, two workgroups per CU; the 64-cout tile (206 registers, one workgroup per CU) only at level 2 (A/B);
-// level 3: every layer on 32-cout tiles
-int tp2b_tile(int cout_p) { return (cout_p <= 64 || tp2b_level() >= 3) ? 32 : 64; }
+// 32-cout tiles (128 registers, two workgroups per CU) serve layers up to 64 couts; wider layers stay on the implicit GEMM: a
+// 64-cout tile (206 registers, one workgroup per CU) lost to it (EXPERIMENTS.md, profiles/r06/h_*)
+constexpr int kTpBN = 32;
 
 static long long tp2b_groups(int N, int H, int W) { return (long long)N * ((H + 3) / 4) * ((W + 7) / 8); }
 
 bool tp2b_ok(int transposed, int kh, int kw, int sh, int sw, int ph, int pw, int nphase, const ConvPhase* phs, const int* taps_host, int cin_p,
              int cout_p, int N, int H, int W, int Ho, int Wo) {
     if (!(transposed && kh == 3 && kw == 3 && sh == 2 && sw == 2 && ph == 1 && pw == 1 && nphase == 4 && Ho == 2 * H && Wo == 2 * W)) return false;
-    if (cin_p % kTpKC != 0) return false;
+    if (cin_p % kTpKC != 0 || cout_p > 64) return false;
     int i = 0;
     for (int p = 0; p < 4; ++p) {
         if (phs[p].po_y * 2 + phs[p].po_x != p) return false;
@@ -307,29 +303,26 @@ bool tp2b_ok(int transposed, int kh, int kw, int sh, int sw, int ph, int pw, int
         }
     }
     if (i != 9) return false;
-    const int bn = tp2b_tile(cout_p);
-    const long long wgs = (tp2b_groups(N, H, W) + 7) / 8 * ((cout_p + bn - 1) / bn);
-    if (bn == 64 && tp2b_level() < 2) return false;
+    const long long wgs = (tp2b_groups(N, H, W) + 7) / 8 * ((cout_p + kTpBN - 1) / kTpBN);
     // measured (tools/tp2b_bench.py, profiles/r06/h_*): with 33..64 couts (two 32-cout tiles over the same boxes) the kernel is ahead
     // of the four-phase implicit GEMM only on large extents (160 -> 64 at 48x48 x 320 frames: 0.35 against 0.42 ms; 128 -> 64 at
     // 12x12: 0.030 against 0.023)
-    if (cout_p > 32 && tp2b_level() < 3 && (long long)N * H * W < 400000) return false;
+    if (cout_p > 32 && (long long)N * H * W < 400000) return false;
     return wgs >= 256;
 }
 
-int tp2b_npart(int cout_p, int N, int H, int W) { (void)cout_p; return (int)tp2b_groups(N, H, W); }
+int tp2b_npart(int N, int H, int W) { return (int)tp2b_groups(N, H, W); }
 
 int tp2b_launch(hipStream_t stream, const void* x, int x_cs, void* y, int y_cs, const void* res, int res_cs, const void* w, long long w_elems,
-                const float* scale, const float* shift, float* stats, const ConvPhase* phs, const int* taps_host, int N, int H, int W,
-                int cin_p, int cout, int cout_p, int act) {
+                const float* scale, const float* shift, float* stats, const ConvPhase* phs, int N, int H, int W, int cin_p, int cout,
+                int cout_p, int act) {
     Tp2bArgs a;
     a.x = x; a.y = y; a.res = res; a.w = w; a.scale = scale; a.shift = shift; a.stats = stats; a.w_elems = w_elems;
     a.N = N; a.H = H; a.W = W; a.x_cs = x_cs; a.y_cs = y_cs; a.res_cs = res_cs; a.cin_p = cin_p; a.cout = cout; a.cout_p = cout_p; a.act = act;
-    const int bn = tp2b_tile(cout_p);
     a.tiles_x = (W + 7) / 8;              // 4 x 8 pixel groups per image row / column
     a.tiles_y = (H + 3) / 4;
     const long long groups = tp2b_groups(N, H, W);
-    a.cout_tiles = (cout_p + bn - 1) / bn;
+    a.cout_tiles = (cout_p + kTpBN - 1) / kTpBN;
     const long long gblocks = (groups + 7) / 8;
     W2L_REQUIRE(gblocks * a.cout_tiles < (1ll << 31) && groups < (1ll << 28), "grid too large");
     a.ntiles = (int)groups;
@@ -339,10 +332,7 @@ int tp2b_launch(hipStream_t stream, const void* x, int x_cs, void* y, int y_cs, 
             a.pt_base[i] = phs[p].w_off + (long long)t * cin_p;
             a.pt_kp[i] = phs[p].kp;
         }
-    (void)taps_host;
-    const dim3 grid((unsigned)(gblocks * a.cout_tiles)), block(512);
-    if (bn == 64) hipLaunchKernelGGL(conv_tp2b_bf16_kernel<64>, grid, block, 0, stream, a);
-    else hipLaunchKernelGGL(conv_tp2b_bf16_kernel<32>, grid, block, 0, stream, a);
+    hipLaunchKernelGGL(conv_tp2b_bf16_kernel<kTpBN>, dim3((unsigned)(gblocks * a.cout_tiles)), dim3(512), 0, stream, a);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

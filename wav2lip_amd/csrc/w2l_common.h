@@ -300,4 +300,30 @@ int tp2s_launch(const float* x, int x_cs, float* y, int y_cs, const __bf16* u, c
 int tp2_launch(const float* x, int x_cs, float* y, int y_cs, const float* u, const float* scale, const float* shift, int N, int H,
                int W, int cin, int cout, int act, hipStream_t stream, long long* flops_out);
 
+// bf16-storage conv launches (conv_bf16.hip, conv_box_bf16.hip): what the epilogue does beside storing the output
+struct BEpilogue {
+    enum Kind {
+        STATS,   // BatchNorm statistics of the output (w2l_convb_forward_bn); no operands
+        BNBWD,   // the output is the dy of a BatchNorm block: that block's backward sums (w2l_convb_forward_bnbwd)
+        MASK     // the output is the dy of an activation block without BatchNorm: dy * act'(y) is stored (w2l_convb_forward_actbwd)
+    };
+    Kind kind = STATS;
+    const void* z = nullptr;    // BNBWD: the block's pre-BatchNorm output
+    const void* y = nullptr;    // the block's output; BNBWD of a ReLU block without residual: NULL, mask from z * scale + shift
+    int z_cs = 0, y_cs = 0;
+    float neg = 1.f;            // act'(.) on the non-positive side: 0 ReLU, 0.01 LeakyReLU, 1 none
+    const float* mean = nullptr;
+    const float* rstd = nullptr;
+    const float* scale = nullptr;
+    const float* shift = nullptr;
+    int store_g = 0;            // BNBWD of a ReLU block: store the masked gradient (W2L_BNBWD_STORE_MASKED); MASK: column sums wanted
+};
+// ... and what the launch did about it: part != NULL: per-wave column partials [npart][2][cout_p] in the stream's scratch (else the
+// caller runs the stand-alone reduction); masked: a MASK launch stored the masked gradient
+struct BEpilogueOut {
+    float* part = nullptr;
+    int npart = 0;
+    bool masked = false;
+};
+
 }  // namespace w2l
