@@ -772,6 +772,12 @@ int w2l_igemm_block_order(int order, int order_r, int tiles_m, int tiles_n, int 
  * tile width c, crossing image boundaries (pad = extra plane cells in front of every segment after the first); blocks = work items
  * per 64-cout tile, pitch = plane cells per staged raw row, cells = cells per raw plane. */
 int w2l_wino4_block_plan(int N, int H, int W, int* out);
+/* The block of output a work item of a GROUPED kernel family covers for N images of H x W input (test aid, host code, runs without
+ * a GPU; a function of the shape alone, the launcher's own choice): out[3] = {bh, bw, ni} - bh x bw tiles of 2 x 2 output pixels
+ * (conv_wino2 ids 8, 9, 12, conv_wino2s) or input pixels (conv_tp2, conv_tp2s) or output pixels (conv_k3s) in each of ni images;
+ * ceil(N / ni) image groups, the last of which runs past the batch when N % ni != 0.  Error for an id of another family
+ * (conv_wino4 has w2l_wino4_block_plan; the implicit GEMM and conv_wino walk a flat pixel / tile index, conv_stem7s one image). */
+int w2l_conv_block_plan(int id, int N, int H, int W, int* out);
 /* time each recorded launch with HIP events on `stream` (reps runs, averaged): ms_out[w2l_plan_size] */
 int w2l_plan_profile(const w2l_plan_t* p, void* stream, int reps, float* ms_out);
 

@@ -90,6 +90,7 @@ SIGNATURES = {
     "w2l_device_arch": (_i, [_i, C.c_char_p, C.c_size_t]),
     "w2l_conv_create": (_i, [C.POINTER(ConvGeom), _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "w2l_conv_destroy": (_i, [_vp]),
+    "w2l_conv_block_plan": (_i, [_i, _i, _i, _i, C.POINTER(_i)]),
     "w2l_conv_cin_padded": (_i, [_i]),
     "w2l_conv_out_hw": (_i, [C.POINTER(ConvGeom), _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "w2l_conv_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i]),

@@ -1869,6 +1869,20 @@ int w2l_tune_entry_applicable(const int* key, int tile) {
 
 int w2l_conv_config_family(int id) { return config_decode(id).family; }
 
+int w2l_conv_block_plan(int id, int N, int H, int W, int* out) {
+    W2L_REQUIRE(out && N >= 1 && H >= 1 && W >= 1, "conv_block_plan: bad arguments");
+    const ConfigId ci = config_decode(id);
+    switch (ci.family) {
+    case kFamWino2: wino2_block_plan(ci.index, N, H, W, out); return W2L_OK;
+    case kFamWino2s: wino2s_block_plan(N, H, W, out); return W2L_OK;
+    case kFamTp2: tp2_block_plan(N, H, W, out); return W2L_OK;
+    case kFamTp2s: tp2s_block_plan(N, H, W, out); return W2L_OK;
+    case kFamK3s: k3s_block_plan(N, H, W, out); return W2L_OK;
+    }
+    W2L_REQUIRE(false, "conv_block_plan: configuration %d does not group images", id);
+    return W2L_ERR_ARG;
+}
+
 int w2l_tune_clear(void) {
     std::lock_guard<std::mutex> lock(g_tune_mutex);
     g_tune.clear();

@@ -388,6 +388,11 @@ int k3sb_init_attrs() {  // called under the lock of convb_init_attrs (conv_bf16
     return W2L_OK;
 }
 
+void k3s_block_plan(int N, int H, int W, int out[3]) {   // the block k3s_launch_t picks
+    const K3Block b = k3s_pick_block(N, H, W);
+    out[0] = b.bh; out[1] = b.bw; out[2] = b.ni;
+}
+
 template <bool kBf16In, bool kU8Out>
 static int k3s_launch_t(const void* x, int x_cs, float* y, int y_cs, uint8_t* frames, const float* res, int res_cs, const __bf16* u,
                         const float* scale, const float* shift, const float* head_w, const float* head_b, int head_c, int head_act,

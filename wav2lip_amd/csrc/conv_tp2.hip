@@ -322,6 +322,11 @@ int tp2_init_attrs() {   // called under the lock of init_kernel_attrs (conv_ige
     return W2L_OK;
 }
 
+void tp2_block_plan(int N, int H, int W, int out[3]) {   // the block tp2_launch picks
+    const TpBlock b = tp2_pick_block(N, H, W);
+    out[0] = b.bh; out[1] = b.bw; out[2] = b.ni;
+}
+
 int tp2_launch(const float* x, int x_cs, float* y, int y_cs, const float* u, const float* scale, const float* shift, int N, int H,
                int W, int cin, int cout, int act, hipStream_t stream, long long* flops_out) {
     Tp2KArgs a;

@@ -415,6 +415,11 @@ int tp2s_init_attrs() {   // called under the lock of init_kernel_attrs (conv_ig
 
 // ksplit > 1: `ws` holds ksplit * N * 4HW * cout floats of partial sums, the caller runs the reduce launch; *ksplit_out = the number of
 // non-empty K ranges actually used
+void tp2s_block_plan(int N, int H, int W, int out[3]) {   // the block tp2s_launch picks
+    const TsBlock b = tp2s_pick_block(N, H, W);
+    out[0] = b.bh; out[1] = b.bw; out[2] = b.ni;
+}
+
 int tp2s_launch(const float* x, int x_cs, float* y, int y_cs, const __bf16* u, const float* scale, const float* shift, int N, int H,
                 int W, int cin, int cout, int act, int ksplit, float* ws, int* ksplit_out, hipStream_t stream, long long* flops_out) {
     Tp2sKArgs a;

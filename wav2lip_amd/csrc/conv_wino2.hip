@@ -794,6 +794,13 @@ int wino2_init_attrs() {   // called under the lock of init_kernel_attrs (conv_i
     return W2L_OK;
 }
 
+// the block a launch of configuration cfg (kNumWino2Cfgs: the quarter-split shape) stages per work item: what the launchers below pick
+void wino2_block_plan(int cfg, int N, int H, int W, int out[3]) {
+    const bool q = cfg >= kNumW2;
+    const W2Block b = wino2_pick_block(N, (H + 1) / 2, (W + 1) / 2, q ? kW2qBT : kW2Cfgs[cfg].bt, q ? kW2qRAW4 : kW2Cfgs[cfg].raw4);
+    out[0] = b.bh; out[1] = b.bw; out[2] = b.ni;
+}
+
 int wino2_launch(int cfg, const WinoKArgs& w, const float* head_w, const float* head_b, int head_c, int head_act,
                  hipStream_t stream, long long* flops_out) {
     const W2Cfg& wc = kW2Cfgs[cfg];

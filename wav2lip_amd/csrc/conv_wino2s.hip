@@ -626,6 +626,11 @@ int wino2s_pack(const float* u32, __bf16* u, int cin, int cout, hipStream_t stre
     return W2L_OK;
 }
 
+void wino2s_block_plan(int N, int H, int W, int out[3]) {   // the block wino2s_launch picks
+    const W2sBlock b = wino2s_pick_block(N, (H + 1) / 2, (W + 1) / 2);
+    out[0] = b.bh; out[1] = b.bw; out[2] = b.ni;
+}
+
 int wino2s_launch(const WinoKArgs& w, const __bf16* u, hipStream_t stream, long long* flops_out) {
     Wino2sKArgs a;
     a.x = w.x; a.y = w.y; a.res = w.res; a.u = u; a.scale = w.scale; a.shift = w.shift;

@@ -262,6 +262,12 @@ long long wino2s_u_elems(int cin, int cout);
 int wino2s_pack(const float* wino_u32, __bf16* u, int cin, int cout, hipStream_t stream);   // from wino_pack's fp32 U
 int wino2s_launch(const WinoKArgs& a, const __bf16* u, hipStream_t stream, long long* flops_out);
 void wino2s_plane_geom(int bh, int bw, int ni, int* pitch, int* istride);
+// the (bh, bw, ni) block each grouped family's launcher picks for a shape (host code; w2l_conv_block_plan)
+void wino2_block_plan(int cfg, int N, int H, int W, int out[3]);   // cfg kNumWino2Cfgs: the quarter-split shape
+void wino2s_block_plan(int N, int H, int W, int out[3]);
+void tp2_block_plan(int N, int H, int W, int out[3]);
+void tp2s_block_plan(int N, int H, int W, int out[3]);
+void k3s_block_plan(int N, int H, int W, int out[3]);
 
 // fused-phase stride-2 transposed 3x3 convolution (conv_tp2.hip): the configuration id after the Winograd families
 bool tp2_ok(const w2l_conv_geom& g);
