@@ -28,6 +28,15 @@ bf16 pieces carry such a value exactly too (the split-operand families).  The bo
     input channels (the residual that aliases the input needs cin = cout = 64) gives every cout W4_LIVE_CIN = 8 live input channels
     and zero weights on the others: the same bound.  The Gaussian
     accuracy run covers dense taps.  No regime of conv_wino4 had to fall back from equality to a bound check.
+
+BACKWARD (tests/test_conv_backward_exact_gpu.py).  The data gradient of a layer is the forward kernel on the other interpretation of
+the layer's weight tensor (dgrad_of: roles swapped, no activation, scale 1, shift 0, the output padding that restores what the strided
+conv's floor division dropped), and an accumulating launch passes the OUTPUT slice as its residual (res = 3): the slice is pre-loaded
+with a prior gradient of integers in [-3, 3] and must come back as prior + reference.  IN-PLACE BOUND: the prior takes the residual's
+place in every bound above with |prior| <= 3 instead of |res| <= 1 (extra = |shift| + 3 in exact_bound); the sum is still an integer
+(a multiple of 1/4 for F(2x2)) below 2^24, so "prior + reference" has ONE value whatever the order in which an epilogue adds the prior,
+and a kernel that read the prior after a store to that address, twice, or not at all cannot produce it.  For bf16 storage the prior is
+exact in bf16, the kernel adds it in fp32 and rounds ONCE: the result equals the float64 "prior + reference" rounded once to bf16.
 """
 import ctypes as C
 import itertools
@@ -89,12 +98,15 @@ def config_id(family, index=0):
 
 class Case:
     """one launch.  path: 'f32' (w2l_conv_*), 'bf16' (w2l_convb_*) or 'thin' (w2l_thin1x1_forward_bf16); force: fp32 configuration id
-    or bf16 tile (-1: the launcher's own choice); ks: forced split-K (0: none); res: 0 none, 1 its own buffer, 2 the input slice;
+    or bf16 tile (-1: the launcher's own choice); ks: forced split-K (0: none); res: 0 none, 1 its own buffer, 2 the input slice,
+    3 the OUTPUT slice (an accumulating data-gradient launch: y holds a prior gradient, integers in [-3, 3]); bwd: scale 1, shift 0
+    (what NodeF gives a data-gradient handle); fwd: the forward layer (signature, H, W) a dgrad_of() case belongs to; declines:
+    configuration ids that must refuse this launch (w2l_tune_entry_applicable), whichever id the case itself runs on;
     sliced: x / y / res are channel slices of wider buffers at non-zero offsets; wide: channel stride of x, y, res (0: dense) - the
     large-offset cases reach 1 GiB with it; wmode: 'dense' taps or 'w4' (see the module docstring)"""
 
     def __init__(self, path, family, tr, cin, cout, k, s, p, op, N, H, W, force=-1, ks=0, res=0, act=ACT_RELU, sliced=False, wide=0,
-                 seed=0, head=0, x_wide=0):
+                 seed=0, head=0, x_wide=0, bwd=False, fwd=None, declines=()):
         self.path, self.family = path, family
         self.tr, self.cin, self.cout = int(tr), cin, cout
         self.k, self.s, self.p, self.op = _pair(k), _pair(s), _pair(p), _pair(op)
@@ -109,6 +121,7 @@ class Case:
         if head:
             self.cout_w = head                                                # fp32 scalars, for either storage
         self.wmode = "w4" if family == "wino4" else "dense"
+        self.bwd, self.fwd, self.declines = bwd, fwd, tuple(declines)
 
     # ---- geometry
     def geom(self):
@@ -131,7 +144,7 @@ class Case:
         if self.head:          # the head writes scalars: the plan's stride of 4, or a slice of a wider pixel
             return (self.cin_p + 24, 8, 12, 4, 0, 0) if self.sliced else (self.cin_p, 0, 4, 0, 0, 0)
         if self.sliced:
-            return (self.cin_p + 24, 8, self.cout_w + 24, 8, self.cout_w + 16, 8)
+            return (self.cin_p + 24, 8, self.cout_w + 24, 8, self.cout_w + (24 if self.res == 3 else 16), 8)
         return (self.cin_p, 0, self.cout_w, 0, self.cout_w, 0)
 
     def wide_x(self):
@@ -146,7 +159,7 @@ class Case:
     def nbytes(self):
         ho, wo = self.out_hw()
         xs, _, ys, _, rs, _ = self.strides()
-        return (self.N * self.H * self.W * xs * self.esz, self.N * ho * wo * ys * self.esz, self.N * ho * wo * rs * self.esz if self.res else 0)
+        return (self.N * self.H * self.W * xs * self.esz, self.N * ho * wo * ys * self.esz, self.N * ho * wo * rs * self.esz if self.res in (1, 2) else 0)
 
     def macs(self):
         ho, wo = self.out_hw()
@@ -222,7 +235,7 @@ class Case:
         """the largest magnitude an intermediate can reach, counted in the finest unit that occurs (so that it is an integer); must be
         < LIMIT.  A is the accumulator's bound in its own unit q (1, or 1/4 for F(2x2)); A * scale is exact for a power-of-two scale;
         adding shift and residual (|.| <= extra) to A * 2 needs 2 A + extra / q, to A / 2 (unit q / 2) needs A + 2 extra / q."""
-        extra = 3 + (1 if self.res else 0)                              # |shift| <= 3, |res| <= 1
+        extra = 3 + (3 if self.res == 3 else 1 if self.res else 0)      # |shift| <= 3, |res| <= 1, |prior| <= 3 (in place)
         smax = max(abs(s) for s in self.scales())
         if self.head:          # a sum of cout such values times weights from {-1, 0, 1}, plus a bias |.| <= 3
             inner = Case(self.path, "k3s" if self.family == "k3s_head" else self.family, self.tr, self.cin, self.cout, self.k, self.s,
@@ -239,14 +252,15 @@ class Case:
 
     def describe(self):
         s = "%s %d->%d %dx%d s%dx%d p%d%s @%dx%d N=%d" % ("convT" if self.tr else "conv", self.cin, self.cout, self.k[0], self.k[1],
-                                                          self.s[0], self.s[1], self.p[0], "+%d" % self.op[0] if self.op[0] else "",
+                                                          self.s[0], self.s[1], self.p[0],
+                                                          "+(%d,%d)" % self.op if self.op[0] != self.op[1] else "+%d" % self.op[0] if self.op[0] else "",
                                                           self.H, self.W, self.N)
         if self.force >= 0:
             s += " id %d" % self.force
         if self.ks:
             s += " ks %d" % self.ks
         if self.res:
-            s += " res" + ("=x" if self.res == 2 else "")
+            s += " res" + {1: "", 2: "=x", 3: "=y"}[self.res]
         if self.head:
             s += " head %d" % self.head
         if self.sliced:
@@ -257,7 +271,14 @@ class Case:
 
     def key(self):
         return (self.path, self.family, self.tr, self.cin, self.cout, self.k, self.s, self.p, self.op, self.N, self.H, self.W, self.force,
-                self.ks, self.res, self.act, self.sliced, self.wide, self.head)
+                self.ks, self.res, self.act, self.sliced, self.wide, self.head, self.bwd, self.declines)
+
+    def with_seed(self, seed):
+        """the same launch with operands from another seed"""
+        import copy
+        c = copy.copy(self)
+        c.seed = seed
+        return c
 
     def __repr__(self):
         return "%s/%s %s" % (self.path, self.family, self.describe())
@@ -316,6 +337,10 @@ def int_operands(case):
     elif case.res == 2:
         assert case.cin == case.cout and (ho, wo) == (case.H, case.W)
         res = x
+    elif case.res == 3:                                                  # the prior gradient the output slice already holds
+        res = (torch.randint(0, 7, (D, case.cout, ho, wo), generator=g) - 3).double()
+    if case.bwd:
+        scale, shift = torch.ones_like(scale), torch.zeros_like(shift)
     if case.wide:
         x[2] = 0
         if case.res == 1:
@@ -348,7 +373,9 @@ def gauss_operands(case):
     w = torch.randn(wshape, generator=g) / float(np.sqrt(case.cin * case.k[0] * case.k[1]))
     scale = torch.rand(case.cout, generator=g) + 0.5
     shift = torch.randn(case.cout, generator=g) * 0.2
-    res = torch.randn(D, case.cout, ho, wo, generator=g) if case.res == 1 else (x if case.res == 2 else None)
+    res = torch.randn(D, case.cout, ho, wo, generator=g) if case.res in (1, 3) else (x if case.res == 2 else None)
+    if case.bwd:
+        scale, shift = torch.ones_like(scale), torch.zeros_like(shift)
     if case.path == "thin":
         scale = torch.ones_like(scale)
     if case.path != "f32":
@@ -592,6 +619,195 @@ def large_candidates():
     return out
 
 
+# ---------------------------------------------------------------- the backward pass: data-gradient launches and weight re-packs
+def dgrad_op(tr, k, s, p, H, W):
+    """the output padding of the data-gradient launch of a layer over an [H, W] input, restated from the definition: the gradient of a
+    transposed layer is a plain conv (no output padding); a conv's floor division drops (H + 2p - k) % s rows (columns) of the padded
+    input, and its gradient - a transposed conv over the conv's output - must produce them again"""
+    k, s, p = _pair(k), _pair(s), _pair(p)
+    if tr:
+        return (0, 0)
+    return ((H + 2 * p[0] - k[0]) % s[0], (W + 2 * p[1] - k[1]) % s[1])
+
+
+def dgrad_of(path, family, sig, N, H, W, **kw):
+    """the Case of the data-gradient launch of the forward layer sig = (tr, cin, cout, k, s, p, op) over an [N, H, W] input, as
+    autograd.NodeF builds it: the other interpretation of the same weight tensor, channel roles swapped, no activation, scale 1, shift 0;
+    its input is dz (the forward output's extent), its output the gradient of x.  None if the forward layer has no output."""
+    tr, cin, cout, k, s, p, op = sig
+    hw = Case(path, "igemm", tr, cin, cout, k, s, p, op, N, H, W).out_hw()
+    if hw is None or min(hw) < 1:
+        return None
+    return Case(path, family, 0 if tr else 1, cout, cin, k, s, p, dgrad_op(tr, k, s, p, H, W), N, hw[0], hw[1], act=ACT_NONE, bwd=True,
+                fwd=(sig, H, W), **kw)
+
+
+def geom_label(tr, k, s, p, op):
+    s = _pair(s)
+    return "%s %dx%d s%s p%d%s" % ("convT" if tr else "conv", k, k, "%d" % s[0] if s[0] == s[1] else "(%d,%d)" % s, p, "+%d" % op if op else "")
+
+
+# forward input extents per (transposed, k, stride, pad, output padding) row of SIGS_GEOMS: the smallest at which the backward form can
+# go wrong.  Stride 3 takes {4, 5, 6} (output padding 0, 1, 2), stride 2 takes {5, 6}, each against a small odd extent on the other axis.
+BWD_EXTENTS = {
+    (False, 3, (1, 1), 1, 0): ((1, 1), (5, 4)),
+    (False, 3, (3, 1), 1, 0): ((4, 3), (5, 3), (6, 5)),
+    (False, 3, (3, 3), 1, 0): ((4, 5), (5, 7), (6, 5), (5, 6), (3, 4)),
+    (False, 3, (3, 2), 1, 0): ((4, 5), (5, 6), (6, 5), (4, 6)),
+    (False, 3, (1, 1), 0, 0): ((3, 3), (4, 5)),                  # 3x3 -> 1x1: the backward launch is the unit-input variant
+    (False, 1, (1, 1), 0, 0): ((1, 1), (5, 4)),
+    (False, 7, (1, 1), 3, 0): ((5, 3), (10, 12)),
+    (False, 3, (2, 2), 1, 0): ((5, 3), (6, 5), (5, 6), (6, 6)),
+    (True, 3, (1, 1), 0, 0): ((1, 1), (3, 2)),                   # backward: a plain 3x3 s1 p0 conv
+    (True, 3, (2, 2), 1, 1): ((3, 3), (2, 3)),                   # backward: a 3x3 s2 p1 conv
+    (False, 5, (1, 2), 1, 0): ((6, 7), (6, 8)),
+    (False, 5, (1, 2), 2, 0): ((6, 7), (6, 8)),
+    (False, 5, (1, 1), 2, 0): ((5, 4),),
+    (False, 5, (2, 2), 2, 0): ((5, 6), (6, 5), (6, 6)),
+}
+
+
+def bwd_igemm_candidates(path, family):
+    """the data gradient of every SIGS geometry at every extent of BWD_EXTENTS, tiles and the forward cout (the launch's cin) rotating,
+    forward cin (the launch's cout) = tile width + 8 (ragged), N in {2, 3}; on every tile the accumulating forms: in place, in place
+    with split-K 2 and 3 (ten fp32 / five bf16 K-steps), in place into a channel slice, in place for a stride-1 layer and for a
+    transposed layer (whose gradient is a plain conv), in place with 15 couts; once the x-paired variant"""
+    tiles = (F32_TILES if path == "f32" else BF16_TILES)[:num_tiles(path)]
+    base = 0 if family != "split" else config_id("split")
+    out = []
+    for gi, (tr, k, s, p, op, _H, _W) in enumerate(SIGS_GEOMS):
+        for ei, hw in enumerate(BWD_EXTENTS[(tr, k, s, p, op)]):
+            ti = (gi + ei) % len(tiles)
+            ch = IGEMM_CIN[(gi + 2 * ei) % len(IGEMM_CIN)]
+            out.append(dgrad_of(path, family, (tr, tiles[ti][1] + 8, ch, k, s, p, op), 2 + (gi + ei) % 2, hw[0], hw[1], force=base + ti,
+                                seed=2000 + gi * 8 + ei))
+    for ti, (_bm, bn) in enumerate(tiles):
+        f, c = base + ti, bn + 8
+        out.append(dgrad_of(path, family, (0, c, 15, 3, 2, 1, 0), 3, 6, 5, force=f, res=3, seed=2200 + ti))
+        for ks in (2, 3):
+            out.append(dgrad_of(path, family, (0, c, 80, 3, 2, 1, 0), 2, 6, 5, force=f, res=3, ks=ks, seed=2210 + ti))
+        out.append(dgrad_of(path, family, (0, c, 15, 3, 2, 1, 0), 3, 5, 6, force=f, res=3, sliced=True, seed=2220 + ti))
+        out.append(dgrad_of(path, family, (0, c, 80, 3, 2, 1, 0), 2, 6, 6, force=f, res=3, sliced=True, ks=2, seed=2230 + ti))
+        out.append(dgrad_of(path, family, (0, c, 15, 3, 1, 1, 0), 3, 5, 4, force=f, res=3, seed=2240 + ti))
+        out.append(dgrad_of(path, family, (1, c, 15, 3, 2, 1, 1), 3, 3, 2, force=f, res=3, seed=2250 + ti))
+        # 15 couts: rows that are no multiple of 16 bytes in fp32, so the epilogue that adds the prior is the scalar one
+        out.append(dgrad_of(path, family, (0, 15, 32, 3, 2, 1, 0), 3, 6, 5, force=f, res=3, seed=2260 + ti))
+        out.append(dgrad_of(path, family, (0, 15, 80, 3, 2, 1, 0), 2, 6, 5, force=f, res=3, ks=2, seed=2270 + ti))
+    # the gradient of a transposed s1 p0 layer with 16 input channels is a plain conv with 16 couts and an even output width: the
+    # fp32 launcher takes its x-paired variant
+    out.append(dgrad_of(path, family, (1, 16, 15, 3, 1, 0, 0), 2, 3, 2, force=base + 4, seed=2280))
+    return [c for c in out if c is not None]
+
+
+BWD_WINO_HW = ((1, 1), (3, 3), (5, 4), (13, 11))
+
+
+def bwd_wino_candidates(cid):
+    """a Winograd kernel run with transposed = 1 (the data gradient of a 3x3 s1 p1 layer: the packer reads the weights flipped, channel
+    roles swapped) at the launch's minimum channel counts"""
+    fam = [f for f, ids in WINO_IDS.items() if cid in ids][0]
+    cin, cout = WINO_CH[cid]
+    sig = (0, cout, cin, 3, 1, 1, 0)                                     # the forward layer: its cout is the launch's cin
+    out = []
+    for (H, W), N in itertools.product(BWD_WINO_HW, (2, 3, 5)):
+        out.append(dgrad_of("f32", fam, sig, N, H, W, force=cid, seed=2400 + cid * 20 + H + N))
+    for (H, W), N in (((1, 1), 5), ((5, 4), 3), ((13, 11), 2), ((13, 11), 5)):
+        out.append(dgrad_of("f32", fam, sig, N, H, W, force=cid, res=3, seed=2410 + cid * 20 + H))
+    for (H, W), N in (((5, 4), 3), ((13, 11), 3)):
+        out.append(dgrad_of("f32", fam, sig, N, H, W, force=cid, res=3, sliced=True, seed=2415 + cid * 20 + H))
+    return out
+
+
+def bwd_tp2_candidates(family):
+    """conv_tp2 / conv_tp2s as the data gradient of a 3x3 s2 p1 conv over EVEN extents (output padding 1 on both axes); in the "tp2"
+    pool also the launches the two kernels must decline - an accumulating launch (neither kernel has a residual operand) and an odd
+    extent (output padding 0) - which run on an implicit-GEMM tile instead"""
+    cid = config_id(family)
+    c0 = 16 if family == "tp2s" else 8
+    out = []
+    for (cin, cout, H, W), N in itertools.product(((c0, 64, 3, 2), (16, 128, 1, 1), (64, 64, 2, 3)), (2, 3)):
+        sig = (0, cout, cin, 3, 2, 1, 0)
+        out.append(dgrad_of("f32", family, sig, N, 2 * H, 2 * W, force=cid, seed=2600 + cin + N))
+        if family == "tp2s":
+            out.append(dgrad_of("f32", family, sig, N, 2 * H, 2 * W, force=cid, ks=2, seed=2620 + cin + N))
+    if family == "tp2":
+        both = (config_id("tp2"), config_id("tp2s"))
+        sig = (0, 64, 16, 3, 2, 1, 0)
+        out.append(dgrad_of("f32", "igemm", sig, 3, 6, 4, force=3, res=3, declines=both, seed=2640))
+        for H, W in ((5, 5), (5, 6), (6, 5)):
+            out.append(dgrad_of("f32", "igemm", sig, 2, H, W, force=3, declines=both, seed=2641 + H + 2 * W))
+    return out
+
+
+def bwd_convb_special_candidates():
+    """the bf16 launcher's special-case kernels in backward form: box64 with transposed = 1 (the data gradient of a 64 -> 64 3x3 s1 p1
+    layer), tp2b as the data gradient of a 3x3 s2 p1 conv; each plain and accumulating in place; batches that fill the chip, seven
+    distinct images (image_map)"""
+    out = []
+    for N in (2048, 2051):
+        for res in (0, 3):
+            out.append(dgrad_of("bf16", "box64", (0, 64, 64, 3, 1, 1, 0), N, 16, 16, res=res, seed=2700 + res))
+    for (c, H, W), N in itertools.product(((32, 10, 14), (32, 2, 2)), (1030, 2049)):
+        for res in (0, 3):
+            out.append(dgrad_of("bf16", "tp2b", (0, c, c, 3, 2, 1, 0), N, H, W, res=res, seed=2720 + H + res))
+    out.append(dgrad_of("bf16", "tp2b", (0, 32, 32, 3, 2, 1, 0), 1030, 10, 14, res=3, sliced=True, seed=2740))
+    return out
+
+
+def update_candidates():
+    """one small launch per packed weight form that w2l_conv_update / w2l_convb_update(_many) must refresh"""
+    sp, out = config_id("split"), []
+
+    def f32(family, cid, tr, cin, cout, k, s, p, op, N, H, W, **kw):
+        out.append(Case("f32", family, tr, cin, cout, k, s, p, op, N, H, W, force=cid, seed=3100 + len(out), **kw))
+    for fam, base in (("igemm", 0), ("split", sp)):                      # w_dev of each variant, then its lazily built w_split planes
+        f32(fam, base + 4, 0, 15, 40, 3, 1, 1, 0, 2, 5, 4)               # generic
+        f32(fam, base + 4, 1, 6, 40, 3, 1, 0, 0, 3, 1, 1)                # unit-input: transposed s1 over a 1x1 input
+        f32(fam, base + 4, 0, 6, 16, 7, 1, 3, 0, 2, 5, 4)                # x-paired: cout <= 16, even output width, no residual
+        f32(fam, base + 3, 1, 15, 72, 3, 2, 1, 1, 2, 3, 2)               # generic, four phases
+    for cid in (6, 7, 8, 9, 12, 11, 19):
+        fam = [f for f, ids in WINO_IDS.items() if cid in ids][0]
+        cin, cout = WINO_CH[cid]
+        for tr in (0, 1):
+            f32(fam, cid, tr, cin, cout, 3, 1, 1, 0, 2, 5, 4, act=ACT_NONE if tr else ACT_RELU)
+    f32("tp2", config_id("tp2"), 1, 8, 64, 3, 2, 1, 1, 2, 3, 2)
+    f32("tp2s", config_id("tp2s"), 1, 32, 64, 3, 2, 1, 1, 2, 3, 2)
+    f32("tp2s", config_id("tp2s"), 1, 32, 64, 3, 2, 1, 1, 2, 3, 2, ks=2)
+    f32("stem7s", config_id("stem7s"), 0, 6, 16, 7, 1, 3, 0, 2, 5, 3)
+    f32("k3s", config_id("k3s"), 0, 16, 32, 3, 1, 1, 0, 3, 5, 7)
+    f32("k3s", config_id("k3s"), 0, 16, 32, 3, 1, 1, 0, 3, 5, 7, head=3)
+
+    def b16(family, tr, cin, cout, k, s, p, op, N, H, W, **kw):
+        out.append(Case("bf16", family, tr, cin, cout, k, s, p, op, N, H, W, seed=3200 + len(out), **kw))
+    b16("igemm", 0, 15, 40, 3, 1, 1, 0, 2, 5, 4, force=4)                # generic
+    b16("igemm", 1, 6, 40, 3, 1, 0, 0, 3, 1, 1, force=4)                 # unit-input
+    b16("igemm", 1, 15, 72, 3, 2, 1, 1, 2, 3, 2, force=3)                # four phases
+    b16("stem", 0, 3, 16, 7, 1, 3, 0, 1024, 16, 16)                      # stem1
+    b16("stem", 0, 80, 32, 3, 1, 1, 0, 2048, 16, 16)                     # stem2
+    b16("stem", 0, 32, 32, 3, 1, 1, 0, 2048, 16, 16, res=1)              # stem3
+    b16("box64", 0, 64, 64, 3, 1, 1, 0, 2048, 16, 16)
+    b16("tp2b", 1, 32, 32, 3, 2, 1, 1, 1030, 5, 7)
+    b16("k3s_head", 0, 16, 32, 3, 1, 1, 0, 3, 5, 7, head=3)
+    return out
+
+
+def update_operands(case):
+    """(x, w0, w1, scale, shift, scale2, shift2, res): w0 and w1 from different seeds, a second scale / shift draw"""
+    x, w0, scale, shift, res = int_operands(case)
+    _x, w1, _s, _h, _r = int_operands(case.with_seed(case.seed + 7919))
+    _x, _w, scale2, shift2, _r = int_operands(case.with_seed(case.seed + 104729))
+    return x, w0, w1, scale, shift, scale2, shift2, res
+
+
+def update_refs(case):
+    """(ref(w0), ref(w1), ref(w1) under the second scale / shift) in float64, fused head applied"""
+    x, w0, w1, scale, shift, scale2, shift2, res = update_operands(case)
+    refs = [ref64(case, x, w, sc, sh, res) for w, sc, sh in ((w0, scale, shift), (w1, scale, shift), (w1, scale2, shift2))]
+    if case.head:
+        refs = [head_ref(r, *head_operands(case)) for r in refs]
+    return refs
+
+
 _CACHE = {}
 
 
@@ -604,6 +820,17 @@ def candidates(name):
             _CACHE[name] = wino_candidates(int(name.split()[-1]))
         elif name in ("tp2", "tp2s"):
             _CACHE[name] = tp2_candidates(name)
+        elif name in ("bwd f32 igemm", "bwd f32 split", "bwd bf16 igemm"):
+            _bwd, path, fam = name.split()
+            _CACHE[name] = bwd_igemm_candidates(path, fam)
+        elif name.startswith("bwd wino id "):
+            _CACHE[name] = bwd_wino_candidates(int(name.split()[-1]))
+        elif name in ("bwd tp2", "bwd tp2s"):
+            _CACHE[name] = bwd_tp2_candidates(name.split()[1])
+        elif name == "bwd bf16 special":
+            _CACHE[name] = bwd_convb_special_candidates()
+        elif name == "update":
+            _CACHE[name] = update_candidates()
         else:
             _CACHE[name] = {"stem7s": stem7s_candidates, "k3s": k3s_candidates, "bf16 special": convb_special_candidates,
                             "thin": thin_candidates, "large": large_candidates, "heads": head_candidates}[name]()
@@ -612,6 +839,8 @@ def candidates(name):
 
 POOLS = ["f32 igemm", "f32 split"] + ["wino id %d" % i for i in (6, 7, 8, 9, 12, 11, 19)] + ["tp2", "tp2s", "stem7s", "k3s", "bf16 igemm",
                                                                                               "bf16 special", "thin", "heads"]
+BWD_POOLS = ["bwd f32 igemm", "bwd f32 split", "bwd bf16 igemm"] + ["bwd wino id %d" % i for i in (6, 7, 8, 9, 12, 11, 19)] + [
+    "bwd tp2", "bwd tp2s", "bwd bf16 special"]
 
 
 def eligible(case):
@@ -751,23 +980,97 @@ _regime("thin: cin not a multiple of 8", "thin", lambda c: c.cin % 8 != 0)
 _regime("thin: channel slices of wider buffers", "thin", lambda c: c.sliced)
 
 
-def select():
+# ---- the backward pass (tests/test_conv_backward_exact_gpu.py)
+BWD_REGIMES = []
+
+
+def _bwd_regime(name, pool, pred):
+    BWD_REGIMES.append((name, pool, pred))
+
+
+def _row(c):
+    """the SIGS_GEOMS row (transposed, k, stride, pad, output padding) of the forward layer a dgrad_of() case belongs to"""
+    (tr, _ci, _co, k, s, p, op), _H, _W = c.fwd
+    return (bool(tr), k, _pair(s), p, op)
+
+
+for _p in ("f32 igemm", "f32 split", "bf16 igemm"):
+    for _g in SIGS_GEOMS:
+        _bwd_regime("%s: data gradient of %s" % (_p, geom_label(*_g[:5])), "bwd " + _p,
+                    lambda c, row=_g[:5]: _row(c) == row and not c.res and not c.ks)
+    _bwd_regime("%s: output padding differs between the axes" % _p, "bwd " + _p, lambda c: c.op[0] != c.op[1] and not c.res)
+    _bwd_regime("%s: output padding 2" % _p, "bwd " + _p, lambda c: 2 in c.op and not c.res)
+    _bwd_regime("%s: the unit-input variant (gradient of 3x3 p0 over 3x3)" % _p, "bwd " + _p,
+                lambda c: c.tr and c.s == (1, 1) and (c.H, c.W) == (1, 1) and c.k == (3, 3))
+    _bwd_regime("%s: accumulate in place" % _p, "bwd " + _p,
+                lambda c: c.res == 3 and not c.ks and not c.sliced and c.s == (2, 2) and c.tr and c.cout > 16)
+    _bwd_regime("%s: accumulate in place, split-K 2" % _p, "bwd " + _p,
+                lambda c: c.res == 3 and c.ks == 2 and c.splits()[0] == 2 and not c.sliced and c.cout > 16)
+    _bwd_regime("%s: accumulate in place, split-K 3" % _p, "bwd " + _p,
+                lambda c: c.res == 3 and c.ks == 3 and c.splits()[0] == 3 and not c.sliced)
+    _bwd_regime("%s: accumulate in place into a channel slice of a wider buffer" % _p, "bwd " + _p,
+                lambda c: c.res == 3 and c.sliced and not c.ks)
+    _bwd_regime("%s: in place into a channel slice, split-K 2" % _p, "bwd " + _p, lambda c: c.res == 3 and c.sliced and c.ks == 2)
+    _bwd_regime("%s: accumulate in place, 15 couts (fp32: scalar epilogue)" % _p, "bwd " + _p, lambda c: c.res == 3 and c.cout == 15 and not c.ks)
+    _bwd_regime("%s: in place, 15 couts, split-K 2" % _p, "bwd " + _p, lambda c: c.res == 3 and c.cout == 15 and c.ks == 2)
+    _bwd_regime("%s: gradient of a transposed layer with 16 input channels (fp32: x-paired variant)" % _p, "bwd " + _p,
+                lambda c: not c.tr and c.cout == 16 and c.out_hw()[1] % 2 == 0 and not c.res)
+    _bwd_regime("%s: accumulate in place, stride 1" % _p, "bwd " + _p, lambda c: c.res == 3 and c.tr and c.s == (1, 1))
+    _bwd_regime("%s: accumulate in place, gradient of a transposed layer" % _p, "bwd " + _p, lambda c: c.res == 3 and not c.tr)
+for _cid in (6, 7, 8, 9, 12, 11, 19):
+    _p = "wino id %d" % _cid
+    _bwd_regime("%s transposed: a single pixel" % _p, "bwd " + _p, lambda c: (c.H, c.W) == (1, 1) and not c.res)
+    _bwd_regime("%s transposed: odd extents, several tiles" % _p, "bwd " + _p, lambda c: (c.H, c.W) == (13, 11) and not c.res)
+    if _cid in (8, 9, 12, 19):      # conv_wino (ids 6, 7) holds one image per block
+        _bwd_regime("%s transposed: several images per block, last group past the batch" % _p, "bwd " + _p,
+                    lambda c: c.group_past_batch() and not c.res)
+    _bwd_regime("%s transposed: accumulate in place" % _p, "bwd " + _p, lambda c: c.res == 3 and not c.sliced)
+    _bwd_regime("%s transposed: accumulate in place, sliced" % _p, "bwd " + _p, lambda c: c.res == 3 and c.sliced)
+for _f, _n in ((0, "rectangles"), (1, "segments")):
+    _bwd_regime("wino4 transposed: %s" % _n, "bwd wino id 11", lambda c, f=_f: c.wino4_plan()["form"] == f and not c.res)
+    _bwd_regime("wino4 transposed: %s, accumulate in place" % _n, "bwd wino id 11",
+                lambda c, f=_f: c.wino4_plan()["form"] == f and c.res == 3 and not c.sliced)
+_bwd_regime("wino4 transposed: rectangles, several images per block, last group past the batch", "bwd wino id 11",
+            lambda c: c.wino4_plan()["form"] == 0 and c.wino4_plan()["ni"] > 1 and c.N % c.wino4_plan()["ni"] != 0 and not c.res)
+for _p in ("tp2", "tp2s"):
+    _bwd_regime("%s: data gradient of conv 3x3 s2 p1 at even extents" % _p, "bwd " + _p,
+                lambda c, f=_p: c.family == f and not c.ks and c.H * c.W > 1)
+    _bwd_regime("%s: the same over a single pixel of dz" % _p, "bwd " + _p, lambda c, f=_p: c.family == f and not c.ks and c.H * c.W == 1)
+_bwd_regime("tp2s: data gradient with split-K 2", "bwd tp2s", lambda c: c.ks == 2 and c.cin // 16 >= 2)
+# FINDING: neither kernel has a residual operand (config_fits: "plain"), so an accumulating data gradient never runs on them
+_bwd_regime("tp2 / tp2s DECLINE accumulate in place (no residual operand): the implicit GEMM runs it", "bwd tp2",
+            lambda c: bool(c.declines) and c.res == 3 and c.op == (1, 1))
+_bwd_regime("tp2 / tp2s DECLINE an odd extent (output padding 0 on both axes): the implicit GEMM runs it", "bwd tp2",
+            lambda c: bool(c.declines) and c.op == (0, 0))
+_bwd_regime("tp2 / tp2s DECLINE output padding (0, 1): the implicit GEMM runs it", "bwd tp2", lambda c: bool(c.declines) and c.op == (0, 1))
+_bwd_regime("tp2 / tp2s DECLINE output padding (1, 0): the implicit GEMM runs it", "bwd tp2", lambda c: bool(c.declines) and c.op == (1, 0))
+_bwd_regime("bf16 box64 transposed", "bwd bf16 special", lambda c: c.family == "box64" and c.tr and not c.res)
+_bwd_regime("bf16 box64 transposed: accumulate in place", "bwd bf16 special", lambda c: c.family == "box64" and c.tr and c.res == 3)
+_bwd_regime("bf16 box64 transposed: batch not a multiple of the 7-image period", "bwd bf16 special",
+            lambda c: c.family == "box64" and c.N % 7 != 0 and c.N > 16)
+_bwd_regime("bf16 tp2b: data gradient of conv 3x3 s2 p1", "bwd bf16 special", lambda c: c.family == "tp2b" and not c.res and c.H > 1)
+_bwd_regime("bf16 tp2b: the same over a single pixel of dz", "bwd bf16 special", lambda c: c.family == "tp2b" and not c.res and c.H == 1)
+_bwd_regime("bf16 tp2b: accumulate in place", "bwd bf16 special", lambda c: c.family == "tp2b" and c.res == 3 and not c.sliced)
+_bwd_regime("bf16 tp2b: accumulate in place, sliced", "bwd bf16 special", lambda c: c.family == "tp2b" and c.res == 3 and c.sliced)
+
+
+def select(regimes=None):
     """[(regime name, pool, case or None)]: the cheapest eligible candidate of the pool that satisfies the predicate"""
     out = []
-    for name, pool, pred in REGIMES:
+    for name, pool, pred in (REGIMES if regimes is None else regimes):
         fits = [c for c in exact_cases(pool) if pred(c)]
         fits.sort(key=lambda c: (c.macs(), sum(c.nbytes())))
         out.append((name, pool, fits[0] if fits else None))
     return out
 
 
-def regime_pred(name):
-    return [p for n, _pool, p in REGIMES if n == name][0]
+def regime_pred(name, regimes=None):
+    return [p for n, _pool, p in (REGIMES if regimes is None else regimes) if n == name][0]
 
 
-def table(ran=None):
+def table(ran=None, regimes=None):
     """the selection table; ran: {regime name: text of the kernel that ran} from a GPU run"""
     lines = []
-    for name, _pool, c in select():
+    for name, _pool, c in select(regimes):
         lines.append("  %-72s %s%s" % (name, c.describe() if c else "EMPTY", " | " + ran[name] if ran and name in ran else ""))
     return "\n".join(lines)

@@ -1,6 +1,8 @@
 """The host side of tests/test_conv_exact_gpu.py, without a GPU: the float64 reference against a plain-loop convolution, every
 case's exactness bound, and the selection table (every regime has a case; both conv_wino4 forms, every implicit-GEMM tile with a
-ragged M and a ragged cout, split-K with a short last split, an image group running past the batch)."""
+ragged M and a ragged cout, split-K with a short last split, an image group running past the batch); and of
+tests/test_conv_backward_exact_gpu.py: the float64 reference of every backward case against torch's float64 AUTOGRAD input gradient of
+the forward layer, the restated output-padding rule against autograd.dgrad_geom, and ref(w0) != ref(w1) for every update case."""
 import numpy as np
 import pytest
 import torch
@@ -134,3 +136,121 @@ def test_guards_cover_the_largest_block():
     for cs, esz in ((4, 4), (8, 2), (512, 4), (1024, 2)):
         n = cc.guard_elems(cs, esz)
         assert n >= 512 * cs and n * esz >= 64 * 1024 and (n * esz) % 16 == 0
+
+
+# ---------------------------------------------------------------- the backward pass
+def _bwd_candidates():
+    return [(pool, c) for pool in cc.BWD_POOLS for c in cc.candidates(pool)]
+
+
+@pytest.mark.parametrize("pool", cc.BWD_POOLS + ["update"])
+def test_every_backward_case_meets_its_exactness_bound(pool):
+    cases = cc.exact_cases(pool)
+    assert cases, pool
+    for c in cases:
+        assert c.exact_bound() < cc.LIMIT, (c, c.exact_bound())
+        assert sum(c.nbytes()) < (64 << 20) or (c.path == "bf16" and c.N > 16), (c, c.nbytes())      # small, but for the large-N families
+
+
+def test_in_place_bound_counts_the_prior():
+    a = cc.Case("f32", "igemm", 1, 15, 40, 3, 2, 1, 1, 2, 3, 3, force=4, res=3, act=cc.ACT_NONE, bwd=True)
+    b = cc.Case("f32", "igemm", 1, 15, 40, 3, 2, 1, 1, 2, 3, 3, force=4, res=1, act=cc.ACT_NONE, bwd=True)
+    assert a.exact_bound() - b.exact_bound() == 2 * (3 - 1)
+    x, w, scale, shift, prior = cc.int_operands(a)
+    assert float(prior.abs().max()) == 3 and bool((prior == prior.round()).all()) and prior.shape == (2, 40, 6, 6)
+    assert bool((scale == 1).all()) and bool((shift == 0).all())            # as NodeF builds a data-gradient handle
+    assert a.nbytes()[2] == 0 and a.strides()[2:4] == a.strides()[4:6]      # the residual is the output slice, no buffer of its own
+    s = cc.Case("f32", "igemm", 1, 15, 40, 3, 2, 1, 1, 2, 3, 3, force=4, res=3, sliced=True, bwd=True)
+    assert s.strides()[2:4] == s.strides()[4:6]
+
+
+def test_every_backward_regime_has_a_case_and_a_name_of_its_own():
+    empty = [name for name, _pool, c in cc.select(cc.BWD_REGIMES) if c is None]
+    assert not empty, empty
+    names = [n for n, _p, _f in cc.REGIMES + cc.BWD_REGIMES]
+    assert len(names) == len(set(names))
+
+
+def test_backward_grid_covers_the_signature_table():
+    """every (transposed, k, stride, pad, output padding) row in backward form on each implicit-GEMM path; output padding 0, 1 and 2 on
+    an axis and different paddings on the two axes; every Winograd id with transposed = 1; both conv_wino4 forms"""
+    assert set(cc.BWD_EXTENTS) == {g[:5] for g in cc.SIGS_GEOMS}
+    for pool in ("bwd f32 igemm", "bwd f32 split", "bwd bf16 igemm"):
+        cases = cc.exact_cases(pool)
+        assert {cc._row(c) for c in cases} == {g[:5] for g in cc.SIGS_GEOMS}, pool
+        assert {c.op for c in cases if c.s == (3, 3)} >= {(0, 1), (1, 0), (2, 1), (1, 2), (2, 0)}
+        assert {c.op for c in cases if c.s == (3, 1)} == {(0, 0), (1, 0), (2, 0)}
+        assert {c.op for c in cases if c.s == (1, 2)} == {(0, 0), (0, 1)}
+        base = cc.config_id("split") if pool == "bwd f32 split" else 0
+        assert {c.force - base for c in cases if c.res == 3 and not c.ks and c.cout > 16} == set(range(6)), pool                    # every tile in place
+        assert {c.force - base for c in cases if c.res == 3 and c.ks == 3} == set(range(6)), pool
+        assert {c.N for c in cases} == {2, 3}
+    sel = {n: c for n, _p, c in cc.select(cc.BWD_REGIMES)}
+    for cid in (6, 7, 8, 9, 12, 11, 19):
+        for c in cc.exact_cases("bwd wino id %d" % cid):
+            assert c.tr == 1 and c.force == cid and (c.cin, c.cout) == cc.WINO_CH[cid]
+    assert sel["wino4 transposed: rectangles, accumulate in place"].wino4_plan()["form"] == 0
+    assert sel["wino4 transposed: segments, accumulate in place"].wino4_plan()["form"] == 1
+    both = (cc.config_id("tp2"), cc.config_id("tp2s"))
+    for c in cc.exact_cases("bwd tp2") + cc.exact_cases("bwd tp2s"):
+        if c.declines:      # no residual operand; output padding (1, 1) only
+            assert c.declines == both and not c.applicable(both[0]) and not c.applicable(both[1]) and c.family == "igemm", c
+            assert c.res == 3 or c.op != (1, 1), c
+        else:
+            assert c.op == (1, 1) and not c.res and c.applicable(), c
+    fams = {c.convb_resolve()[0] for c in cc.exact_cases("bwd bf16 special")}
+    assert fams == {"box64", "tp2b"}
+    assert {(c.family, c.res) for c in cc.exact_cases("bwd bf16 special")} == {("box64", 0), ("box64", 3), ("tp2b", 0), ("tp2b", 3)}
+
+
+def test_restated_output_padding_is_that_of_dgrad_geom():
+    from wav2lip_amd import autograd
+    from wav2lip_amd._lib import ConvGeom
+    n = 0
+    for _pool, c in _bwd_candidates():
+        (tr, cin, cout, k, s, p, op), H, W = c.fwd
+        k, s, p, op = (cc._pair(v) for v in (k, s, p, op))
+        g = autograd.dgrad_geom(ConvGeom(int(tr), cin, cout, k[0], k[1], s[0], s[1], p[0], p[1], op[0], op[1], cc.ACT_RELU), H, W)
+        mine = c.geom()
+        for f in ("transposed", "cin", "cout", "kh", "kw", "sh", "sw", "ph", "pw", "oph", "opw", "act"):
+            assert getattr(g, f) == getattr(mine, f), (c, f, getattr(g, f), getattr(mine, f))
+        assert c.out_hw() == (H, W), c                                    # the gradient has the extent of the forward input
+        n += 1
+    assert n > 300
+
+
+def test_backward_reference_is_the_autograd_input_gradient():
+    """independence of the reference: the float64 conv_transpose2d / conv2d of the backward Case == torch's float64 autograd gradient
+    of the FORWARD layer with respect to its input, bit for bit (same w, same dz; both sides hold integers)"""
+    import torch.nn.functional as F
+    seen = set()
+    for _pool, c in _bwd_candidates():
+        key = (c.fwd, c.N if c.N <= 16 else 7, c.seed, c.wmode)
+        if key in seen:
+            continue
+        seen.add(key)
+        (tr, cin, cout, k, s, p, op), H, W = c.fwd
+        dz, w, scale, shift, _prior = cc.int_operands(c)
+        x = torch.zeros(dz.shape[0], cin, H, W, dtype=torch.float64, requires_grad=True)
+        z = F.conv_transpose2d(x, w, None, cc._pair(s), cc._pair(p), cc._pair(op)) if tr else F.conv2d(x, w, None, cc._pair(s), cc._pair(p))
+        assert z.shape == dz.shape, (c, z.shape, dz.shape)
+        z.backward(dz)
+        got = cc.ref64(c, dz, w, scale, shift, None)
+        assert got.shape == x.grad.shape, (c, got.shape, x.grad.shape)
+        assert torch.equal(got, x.grad), (c, float((got - x.grad).abs().max()))
+        assert bool((got == got.round()).all()) or c.wmode == "w4"
+    assert len(seen) > 100
+
+
+def test_update_cases_cannot_pass_on_stale_weights():
+    cases = cc.exact_cases("update")
+    assert len(cases) == len(cc.candidates("update"))
+    for c in cases:
+        r0, r1, r2 = cc.update_refs(c)
+        assert not torch.equal(r0, r1) and not torch.equal(r1, r2), c
+        if c.path == "bf16" and not c.head:                                # ... nor after the one rounding to bf16
+            assert not torch.equal(r0.float().bfloat16(), r1.float().bfloat16()), c
+    ids = {c.force for c in cases if c.path == "f32"}
+    assert ids >= {4, 17, 6, 7, 8, 9, 12, 11, 19, cc.config_id("tp2"), cc.config_id("tp2s"), cc.config_id("stem7s"), cc.config_id("k3s")}
+    assert {c.tr for c in cases if c.family.startswith("wino")} == {0, 1}
+    assert {c.convb_resolve()[0] for c in cases if c.path == "bf16" and not c.head and c.force < 0} == {"stem1", "stem2", "stem3", "box64", "tp2b"}

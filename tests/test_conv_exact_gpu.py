@@ -306,20 +306,24 @@ def _launcher(case, w, scale, shift, device):
         gf = cc.GUARD_MIN_BYTES  # guard bytes on either side of the uint8 frames
         frames = torch.full((2 * gf + N * H * W * case.head,), 0xA5, dtype=torch.uint8, device=device)
 
+        aff = {"sc": sc, "sh": sh}      # a bf16 launch takes scale / shift per call: the update test swaps them here
+
         def run(x, y, res, _keep=(hw, hb)):
             frames.fill_(0xA5)
             check(lib.w2l_convb_forward_head(layer.handle, current_stream(), N, H, W, x.ptr, x.cs, C.c_void_p(frames.data_ptr() + gf),
-                                             y.ptr, y.cs, _lib.ptr(sc), _lib.ptr(sh)), "convb_forward_head")
-        run.frames, run.gf = frames, gf
+                                             y.ptr, y.cs, _lib.ptr(aff["sc"]), _lib.ptr(aff["sh"])), "convb_forward_head")
+        run.frames, run.gf, run.layer, run.aff = frames, gf, layer, aff
         return run, lambda x, y, res: layer.resolve(N, H, W) + (None,)
     if case.path == "bf16":
         layer = bf16.ConvB(case.geom(), wd)
         if case.force >= 0:
             layer.set_tile(case.force)
+        aff = {"sc": sc, "sh": sh}
 
         def run(x, y, res):
             check(lib.w2l_convb_forward(layer.handle, current_stream(), N, H, W, x.ptr, x.cs, y.ptr, y.cs, res.ptr if res else None,
-                                        res.cs if res else 0, _lib.ptr(sc), _lib.ptr(sh), case.ks), "convb_forward")
+                                        res.cs if res else 0, _lib.ptr(aff["sc"]), _lib.ptr(aff["sh"]), case.ks), "convb_forward")
+        run.layer, run.aff = layer, aff
 
         def ran(x, y, res):      # w2l_convb_resolve answers for ksplit_force 0: a forced split-K is not reported by the launcher
             fam, tile, ks = layer.resolve(N, H, W, res=bool(case.res))
@@ -350,6 +354,7 @@ def _launcher(case, w, scale, shift, device):
     def run(x, y, res, _o=owner):
         add(x, y, res)
         check(lib.w2l_plan_run(p, current_stream()), "plan_run")
+    run.handle = h
 
     def ran(x, y, res):
         add(x, y, res)
@@ -400,6 +405,8 @@ def _buffers(case, device):
         res = Buf(case, case.N, ho, wo, rs, ro, case.cout_w, device, out=False)
     elif case.res == 2:
         res = x
+    elif case.res == 3:      # an accumulating launch: the residual IS the output slice (test_conv_backward_exact_gpu.py)
+        res = y
     return x, y, res
 
 
@@ -416,6 +423,21 @@ def _expected(case, ref, imap, device):
     return t.to(device)[torch.tensor(imap, device=device)]
 
 
+def _load_prior(case, y, res64, imap):
+    """res = 3: the output slice holds the prior gradient before every launch (pad channels zero); everything around it the sentinel"""
+    if case.res == 3:
+        y.load(res64, imap)
+
+
+def _compare(case, y, want, what):
+    """guards and neighbour channels untouched, every element written, the slice equal to `want`"""
+    y.check_untouched(what)
+    got = y.body[..., y.off:y.off + y.cw]
+    bad = int((got != want).sum())            # NaN != anything: a poisoned element counts
+    assert bad == 0, "%s: %d of %d elements differ from the float64 reference; first at %s" % (
+        what, bad, want.numel(), (got != want).nonzero()[0].tolist())
+
+
 def run_exact(case, device):
     assert not _FAULTED, "an earlier case ended in a HIP error: nothing more is launched"
     assert cc.eligible(case), case
@@ -430,23 +452,21 @@ def run_exact(case, device):
     x.load(x64, imap)
     if case.res == 1:
         res.load(res64, imap)
+    _load_prior(case, y, res64, imap)
     run, ran = _launcher(case, w64, scale, shift, device)
     got_ran = ran(x, y, res)
     _assert_ran(case, got_ran)
     run(x, y, res)
     _sync()
-    y.check_untouched(repr(case))
     first = y.written()
     want = _expected(case, ref, imap, device)
-    got = y.body[..., y.off:y.off + y.cw]
-    bad = int((got != want).sum())            # NaN != anything: a poisoned element counts
-    assert bad == 0, "%r: %d of %d elements differ from the float64 reference; first at %s" % (
-        case, bad, want.numel(), (got != want).nonzero()[0].tolist())
+    _compare(case, y, want, repr(case))
     if case.head and case.path == "bf16":      # the uint8 frames: (uint8)(int)(v * 255.f) of the same values, nothing around them
         fr = run.frames[run.gf:-run.gf].view(want.shape).long()
         assert torch.equal(fr, (want * 255.0).trunc().long() % 256), "%r: uint8 frames differ" % (case,)
         assert bool((run.frames[:run.gf] == 0xA5).all()) and bool((run.frames[-run.gf:] == 0xA5).all()), "%r: wrote around the frames" % (case,)
     y.reset()
+    _load_prior(case, y, res64, imap)
     run(x, y, res)
     _sync()
     y.check_untouched(repr(case) + " (second run)")
@@ -497,8 +517,7 @@ def _accuracy_cases():
     return out
 
 
-@pytest.mark.parametrize("case", _accuracy_cases())
-def test_accuracy(case, cuda):
+def run_accuracy(case, cuda):
     """Gaussian operands on the guard-banded buffers against float64, at the project's own tolerances"""
     assert not _FAULTED, "an earlier case ended in a HIP error: nothing more is launched"
     x64, w64, scale, shift, res64 = cc.gauss_operands(case)
@@ -514,6 +533,7 @@ def test_accuracy(case, cuda):
     x.load(x64, imap)
     if case.res == 1:
         res.load(res64, imap)
+    _load_prior(case, y, res64, imap)
     run, ran = _launcher(case, w64, scale, shift, cuda)
     _assert_ran(case, ran(x, y, res))
     run(x, y, res)
@@ -525,6 +545,12 @@ def test_accuracy(case, cuda):
     ratio = float(((got - want).abs() / tolm).max())
     print("accuracy %-8s %-60s worst error / bound %.3f   torch fp32 / bound %.3f" % (case.family, case.describe(), ratio, torch_ratio))
     assert ratio <= 1.0, (case, ratio)      # NaN fails too
+
+
+@pytest.mark.parametrize("case", _accuracy_cases())
+def test_accuracy(case, cuda):
+    """Gaussian operands on the guard-banded buffers against float64, at the project's own tolerances"""
+    run_accuracy(case, cuda)
 
 
 # ---------------------------------------------------------------- the 2 GiB guard
