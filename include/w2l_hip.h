@@ -56,7 +56,9 @@
  *   w2l_bce_bwd           backward of F.binary_cross_entropy (models/wav2lip.py:171, hq_wav2lip_train.py:249,253)
  *   w2l_adam_*            optim.Adam (wav2lip_train.py:359, hq_wav2lip_train.py:418-421)
  *   w2l_shifted_pdist     calc_pdist of the LSE-D / LSE-C scorer (evaluation/scores_LSE/SyncNetInstance_calc_scores.py:19-31)
- *   w2l_sync_window_rows  the scorer's window building (SyncNetInstance_calc_scores.py:105-127), one clip per row
+ *   w2l_sync_window_rows,
+ *   w2l_sync_window_rows_bf16  the scorer's window building (SyncNetInstance_calc_scores.py:105-127), one clip per row
+ *   w2l_sync_embeddings_bf16  models/syncnet.py:62-63 (F.normalize(p=2, dim=1)) of both bf16 encoder outputs in one launch
  *   w2l_lse_score_segments  its scores (SyncNetInstance_calc_scores.py:19-31,129-137) for every clip of a directory run
  *                         (evaluation/scores_LSE/calculate_scores_LRS.py:28-50) in one launch
  */
@@ -670,6 +672,17 @@ typedef struct {
  * face_cs >= 16 and mel_cs >= 4, both multiples of 4; outputs 16-byte aligned; 1 <= B <= 65535. */
 int w2l_sync_window_rows(void* stream, int B, const w2l_sync_row* rows, int S, float* face_in, int face_cs, float* mel_in,
                          int mel_cs);
+/* The same for the bf16-storage plan: face_in / mel_in are bf16, every value the fp32 one above rounded once (round to nearest
+ * even), pad channels written as zeros.  8 channels (16 bytes) per store: face_cs >= 16 and mel_cs >= 8, both multiples of 8;
+ * outputs 16-byte aligned; 1 <= B <= 65535. */
+int w2l_sync_window_rows_bf16(void* stream, int B, const w2l_sync_row* rows, int S, void* face_in, int face_cs, void* mel_in,
+                              int mel_cs);
+/* The tail of the bf16-storage SyncNet plan, both encoders in one launch: row b of audio_x bf16 [B][audio_cs] -> row b of
+ * audio_out fp32 [B][C] (contiguous), face_x bf16 [B][face_cs] -> face_out likewise, y = x / max(||x||_2, 1e-12) over the first C
+ * channels (the others are not read), the sum of squares in fp32.  C and both strides (>= C) are multiples of 8; all four
+ * pointers 16-byte aligned; B >= 1.  A caller that fills rows [offset, offset+B) of an arena passes arena + offset*C. */
+int w2l_sync_embeddings_bf16(void* stream, int B, int C, const void* audio_x, int audio_cs, const void* face_x, int face_cs,
+                             float* audio_out, float* face_out);
 /* SyncNetInstance_calc_scores.py:129-137 for n_seg clips in one launch.  face_emb, audio_emb fp32 [rows][C]; segment s owns rows
  * [row0, row0+n) of both.  With win = 2*vshift+1 and dist(i, j) the entry of w2l_shifted_pdist run on the segment alone (zero
  * padding at the segment's own ends; no row of another segment is read; the same arithmetic, bit for bit):

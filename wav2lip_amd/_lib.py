@@ -190,6 +190,8 @@ SIGNATURES = {
     "w2l_bce_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "w2l_shifted_pdist": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "w2l_sync_window_rows": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i]),
+    "w2l_sync_window_rows_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i]),
+    "w2l_sync_embeddings_bf16": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "w2l_lse_score_segments": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "w2l_adam_create": (_i, [_i, C.POINTER(_ll), C.POINTER(_vp)]),
     "w2l_adam_destroy": (_i, [_vp]),

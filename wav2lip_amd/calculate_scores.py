@@ -13,7 +13,8 @@ values are not comparable to the paper's); inputs are the uncompressed AVIs of c
 track, read back with `audio.load_wav(path, 16000)`; `--tmp_dir` and `--reference` are accepted and unused (nothing is unpacked to
 disk).  The network sees the lower half of a face crop, so every frame needs a face box: `--box y1 y2 x1 x2` for all frames, or
 `inference.face_detect` per clip as the filelist command runs it (no pads, smoothing on).  `--fps` is the frame rate the mel
-windows are placed at, `--face_det_precision` the detector's arithmetic.  `--packed_face_det` (off by default) detects the
+windows are placed at, `--face_det_precision` the detector's arithmetic, `--precision` SyncNet's (fp32, or the opt-in bf16-storage
+plan of DESIGN.md 3o).  `--packed_face_det` (off by default) detects the
 faces of successive clips in shared detector batches (`face_detection.detect_many`); scored clips, skipped clips and
 their messages stay what they are without it.
 
@@ -52,6 +53,8 @@ def build_cli_parser():
                    help='One face box for every frame; without it the face detector runs on every clip')
     p.add_argument('--face_det_precision', default='fp32', choices=['fp32', 'bf16'],
                    help='Face detector arithmetic: fp32 (default, matches the reference) or bf16 storage')
+    p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
+                   help='SyncNet arithmetic: fp32 (default, matches the reference) or bf16 storage')
     p.add_argument('--packed_face_det', default=False, action='store_true',
                    help='Detect faces of successive clips in shared detector batches (face_detection.detect_many)')
     return p
@@ -217,7 +220,7 @@ def main(argv=None, state_dict=None):
 
     producer = score_jobs_packed if args.packed_face_det and args.box is None else score_jobs
     evaluation.lse_many(model, producer(args, videos, device, detector, skipped), fps=args.fps, vshift=args.vshift,
-                        batch_size=args.batch_size, sink=sink)
+                        batch_size=args.batch_size, sink=sink, precision=inference.CLI_PRECISION[args.precision])
     if not scored:
         raise SystemExit("no clip of {} could be scored ({} skipped)".format(args.data_root, len(skipped)))
     print('Average Confidence: {}'.format(sum(r["lse_c"] for r in scored) / len(scored)))

@@ -1,5 +1,6 @@
 // Filelist scoring (evaluation/scores_LSE/calculate_scores_LRS.py:28-50 over SyncNetInstance_calc_scores.py:19-31,105-137) with
-// the windows of many clips in shared SyncNet batches: the kernel that builds a batch's two network inputs from a row table, and
+// the windows of many clips in shared SyncNet batches: the kernel that builds a batch's two network inputs from a row table (fp32,
+// or bf16 for the bf16-storage plan), the kernel that normalises that plan's two bf16 outputs into the fp32 embedding arenas, and
 // the kernel that turns the embeddings of a group of clips into one score row per clip.
 #include <math.h>
 
@@ -24,11 +25,15 @@ constexpr int kSyncT = 5;        // frames per window (hparams.syncnet_T)
 constexpr int kSyncMels = 80;
 constexpr int kSyncCols = 16;    // mel columns per window (syncnet_mel_step_size)
 
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
 // Row b of both SyncNet inputs.  A face item is 4 neighbouring pixels of one output line: per frame t the 12 bytes are three
 // dwords of the frame line when the address allows it (bytes otherwise, and at a ragged line end), each byte is read once, and
-// the item writes its pixels' channels 0 .. face_cs-1 whole.  A mel item is one (mel row, column).
-__global__ __launch_bounds__(256) void sync_window_rows_kernel(const SyncRow* __restrict__ rows, int S, float* __restrict__ face_in,
-                                                               int face_cs, float* __restrict__ mel_in, int mel_cs) {
+// the item writes its pixels' channels 0 .. face_cs-1 whole.  A mel item is one (mel row, column).  T = float, or __bf16 for the
+// bf16-storage plan: the fp32 value rounded once (RNE), 8 channels (16 bytes) per store
+template <typename T>
+__global__ __launch_bounds__(256) void sync_window_rows_kernel(const SyncRow* __restrict__ rows, int S, T* __restrict__ face_in,
+                                                               int face_cs, T* __restrict__ mel_in, int mel_cs) {
     const int b = blockIdx.y;
     const SyncRow r = rows[b];
     const int Ho = S >> 1, groups = (S + 3) >> 2;
@@ -56,15 +61,31 @@ __global__ __launch_bounds__(256) void sync_window_rows_kernel(const SyncRow* __
 #pragma unroll
             for (int k = 0; k < 12; ++k) v[k / 3][3 * t + k % 3] = (float)((w[k >> 2] >> (8 * (k & 3))) & 255u) / 255.f;
         }
-        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int px = 0; px < 4; ++px) {
             if (px >= np) break;
             v[px][3 * kSyncT] = 0.f;
-            float4* o = reinterpret_cast<float4*>(face_in + (((size_t)b * Ho + y) * S + x0 + px) * face_cs);
+            T* op = face_in + (((size_t)b * Ho + y) * S + x0 + px) * face_cs;
+            if constexpr (sizeof(T) == 2) {
+                bf16x8* o = reinterpret_cast<bf16x8*>(op);
+                bf16x8 zero;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) o[q] = make_float4(v[px][4 * q], v[px][4 * q + 1], v[px][4 * q + 2], v[px][4 * q + 3]);
-            for (int q = 4; q < (face_cs >> 2); ++q) o[q] = zero;
+                for (int c = 0; c < 8; ++c) zero[c] = (__bf16)0.f;
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    bf16x8 h;
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) h[c] = (__bf16)v[px][8 * q + c];
+                    o[q] = h;
+                }
+                for (int q = 2; q < (face_cs >> 3); ++q) o[q] = zero;
+            } else {
+                const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+                float4* o = reinterpret_cast<float4*>(op);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) o[q] = make_float4(v[px][4 * q], v[px][4 * q + 1], v[px][4 * q + 2], v[px][4 * q + 3]);
+                for (int q = 4; q < (face_cs >> 2); ++q) o[q] = zero;
+            }
         }
         return;
     }
@@ -73,9 +94,48 @@ __global__ __launch_bounds__(256) void sync_window_rows_kernel(const SyncRow* __
     const int s = r.start + (m & (kSyncCols - 1));
     const float* mel = reinterpret_cast<const float*>(r.mel);
     const float val = (s >= 0 && s < r.T) ? mel[(long long)(m >> 4) * r.T + s] : 0.f;
-    float4* o = reinterpret_cast<float4*>(mel_in + ((size_t)b * kSyncMels * kSyncCols + m) * mel_cs);
-    o[0] = make_float4(val, 0.f, 0.f, 0.f);
-    for (int q = 1; q < (mel_cs >> 2); ++q) o[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    T* op = mel_in + ((size_t)b * kSyncMels * kSyncCols + m) * mel_cs;
+    if constexpr (sizeof(T) == 2) {
+        bf16x8* o = reinterpret_cast<bf16x8*>(op);
+        bf16x8 h;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) h[c] = (__bf16)0.f;
+        for (int q = 1; q < (mel_cs >> 3); ++q) o[q] = h;
+        h[0] = (__bf16)val;
+        o[0] = h;
+    } else {
+        float4* o = reinterpret_cast<float4*>(op);
+        o[0] = make_float4(val, 0.f, 0.f, 0.f);
+        for (int q = 1; q < (mel_cs >> 2); ++q) o[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// The tail of the bf16-storage SyncNet plan: F.normalize(p=2, dim=1) of both encoders' outputs in one launch.  blockIdx.y picks the
+// encoder, one wave per row; a lane reads 8 channels (16 bytes) at a time, the sum of squares is fp32 (a bf16 square is exact in
+// fp32), and y = x / max(sqrt(sum), 1e-12) goes out as two float4 per 8 channels.  Channels C .. cs-1 are never read.
+__global__ __launch_bounds__(256) void sync_embeddings_bf16_kernel(int B, int C, const __bf16* __restrict__ audio_x, int audio_cs,
+                                                                   const __bf16* __restrict__ face_x, int face_cs,
+                                                                   float* __restrict__ audio_out, float* __restrict__ face_out) {
+    const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= B) return;
+    const bool face = blockIdx.y != 0;
+    const __bf16* p = face ? face_x + (size_t)row * face_cs : audio_x + (size_t)row * audio_cs;
+    float* y = (face ? face_out : audio_out) + (size_t)row * C;
+    float s = 0.f;
+    for (int c = lane * 8; c < C; c += 512) {
+        const bf16x8 h = *reinterpret_cast<const bf16x8*>(p + c);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += (float)h[k] * (float)h[k];
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const float d = fmaxf(sqrtf(s), 1e-12f);
+    for (int c = lane * 8; c < C; c += 512) {
+        const bf16x8 h = *reinterpret_cast<const bf16x8*>(p + c);
+        float4* o = reinterpret_cast<float4*>(y + c);
+        o[0] = make_float4((float)h[0] / d, (float)h[1] / d, (float)h[2] / d, (float)h[3] / d);
+        o[1] = make_float4((float)h[4] / d, (float)h[5] / d, (float)h[6] / d, (float)h[7] / d);
+    }
 }
 
 // order of the selection below: NaN before every number (torch.min returns the first NaN, and conf = median - NaN is NaN as
@@ -165,8 +225,40 @@ int w2l_sync_window_rows(void* stream, int B, const w2l_sync_row* rows, int S, f
     W2L_REQUIRE(((reinterpret_cast<uintptr_t>(face_in) | reinterpret_cast<uintptr_t>(mel_in)) & 15) == 0,
                 "sync_window_rows: 16-byte aligned outputs");
     const int items = (S / 2) * ((S + 3) / 4) + kSyncMels * kSyncCols;
-    hipLaunchKernelGGL(sync_window_rows_kernel, dim3(ceil_div(items, 256), B), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(sync_window_rows_kernel<float>, dim3(ceil_div(items, 256), B), dim3(256), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const SyncRow*>(rows), S, face_in, face_cs, mel_in, mel_cs);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_sync_window_rows_bf16(void* stream, int B, const w2l_sync_row* rows, int S, void* face_in, int face_cs, void* mel_in,
+                              int mel_cs) {
+    W2L_REQUIRE(rows && face_in && mel_in && S >= 2 && S <= 4096, "bad sync_window_rows_bf16 arguments");
+    W2L_REQUIRE(B >= 1 && B <= 65535 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0,
+                "sync_window_rows_bf16: 1 <= B <= 65535 and a 16-byte aligned row table");
+    W2L_REQUIRE(face_cs >= 16 && face_cs % 8 == 0 && mel_cs >= 8 && mel_cs % 8 == 0,
+                "sync_window_rows_bf16: face_cs=%d (>= 16) and mel_cs=%d (>= 8) must be multiples of 8", face_cs, mel_cs);
+    W2L_REQUIRE(((reinterpret_cast<uintptr_t>(face_in) | reinterpret_cast<uintptr_t>(mel_in)) & 15) == 0,
+                "sync_window_rows_bf16: 16-byte aligned outputs");
+    const int items = (S / 2) * ((S + 3) / 4) + kSyncMels * kSyncCols;
+    hipLaunchKernelGGL(sync_window_rows_kernel<__bf16>, dim3(ceil_div(items, 256), B), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const SyncRow*>(rows), S, static_cast<__bf16*>(face_in), face_cs,
+                       static_cast<__bf16*>(mel_in), mel_cs);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_sync_embeddings_bf16(void* stream, int B, int C, const void* audio_x, int audio_cs, const void* face_x, int face_cs,
+                             float* audio_out, float* face_out) {
+    W2L_REQUIRE(audio_x && face_x && audio_out && face_out && B >= 1 && C >= 8, "bad sync_embeddings_bf16 arguments");
+    W2L_REQUIRE(C % 8 == 0 && audio_cs >= C && face_cs >= C && audio_cs % 8 == 0 && face_cs % 8 == 0,
+                "sync_embeddings_bf16: C=%d and the strides %d, %d (>= C) must be multiples of 8", C, audio_cs, face_cs);
+    W2L_REQUIRE(((reinterpret_cast<uintptr_t>(audio_x) | reinterpret_cast<uintptr_t>(face_x) | reinterpret_cast<uintptr_t>(audio_out) |
+                  reinterpret_cast<uintptr_t>(face_out)) & 15) == 0,
+                "sync_embeddings_bf16: 16-byte aligned inputs and outputs");
+    hipLaunchKernelGGL(sync_embeddings_bf16_kernel, dim3(ceil_div(B, 4), 2), dim3(256), 0, static_cast<hipStream_t>(stream), B, C,
+                       static_cast<const __bf16*>(audio_x), audio_cs, static_cast<const __bf16*>(face_x), face_cs, audio_out,
+                       face_out);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

@@ -71,15 +71,17 @@ def lse_from_embeddings(face_emb, audio_emb, vshift=15):
 
 
 @torch.no_grad()
-def lse_like(syncnet, frames_u8, mel, fps=25., vshift=15, batch_size=64):
-    """scores of a generated clip under the in-tree SyncNet_color (eval mode): dict(offset, lse_c, lse_d, n)"""
+def lse_like(syncnet, frames_u8, mel, fps=25., vshift=15, batch_size=64, precision="f32"):
+    """scores of a generated clip under the in-tree SyncNet_color (eval mode): dict(offset, lse_c, lse_d, n).  `precision`: SyncNet
+    arithmetic, "f32" (default) or "bf16" (the opt-in bf16-storage plan; embeddings and scores stay fp32)"""
+    kw = _precision_kw(precision)
     was_training = syncnet.training
     syncnet.eval()
     try:
         faces, mels = sync_windows(frames_u8, mel, fps)
         a_all, v_all = [], []
         for lo in range(0, faces.shape[0], batch_size):
-            a, v = syncnet(mels[lo:lo + batch_size], faces[lo:lo + batch_size])
+            a, v = syncnet(mels[lo:lo + batch_size], faces[lo:lo + batch_size], **kw)
             a_all.append(a)
             v_all.append(v)
         offset, conf, minval, mdist = lse_from_embeddings(torch.cat(v_all), torch.cat(a_all), vshift)
@@ -111,7 +113,14 @@ def _score_segments(n_seg, segs, vshift, face_emb, audio_emb, out):
                                         ptr(audio_emb), out.data_ptr() + 16 * n_seg, ptr(out)), "lse_score_segments")
 
 
-def _score_group(syncnet, clips, vshift, batch_size):
+def _precision_kw(precision):
+    """the keyword a SyncNet call takes for `precision`, checked first (models.wav2lip.check_precision): none for "f32", so a
+    scorer object that knows nothing of the switch keeps working on the default path"""
+    from .models.wav2lip import check_precision
+    return {} if check_precision(precision) == "f32" else {"precision": precision}
+
+
+def _score_group(syncnet, clips, vshift, batch_size, precision="f32"):
     """One group on the device.  clips: [(faces, mel, rows)], every `rows` (sync_rows) non-empty.  The windows of the group are
     the rows of one embedding arena pair, clip after clip; batches of exactly `batch_size` rows walk the arena, the last one padded
     with copies of its last row whose embeddings fall into the scratch rows behind the arena.  Returns numpy [clips, 4 + win]:
@@ -156,7 +165,8 @@ def _score_group(syncnet, clips, vshift, batch_size):
     audio_emb = torch.empty((padded, 512), dtype=torch.float32, device=dev)     # rows [W, padded): the scratch tail
     face_emb = torch.empty((padded, 512), dtype=torch.float32, device=dev)
     for lo in range(0, padded, batch_size):
-        syncnet.embed_rows(stage_dev[lo * SYNC_ROW.itemsize:(lo + batch_size) * SYNC_ROW.itemsize], batch_size, audio_emb, face_emb, lo)
+        syncnet.embed_rows(stage_dev[lo * SYNC_ROW.itemsize:(lo + batch_size) * SYNC_ROW.itemsize], batch_size, audio_emb, face_emb, lo,
+                           **_precision_kw(precision))
     out = torch.empty(len(clips) * (4 + win), dtype=torch.float32, device=dev)
     _score_segments(len(clips), stage_dev[seg_off:seg_off + len(clips) * LSE_SEGMENT.itemsize], vshift, face_emb, audio_emb, out)
     res = out.cpu().numpy()                      # the group's one copy back; it also ends the stream's use of the staging buffers
@@ -183,7 +193,7 @@ def _checked_job(job):
 
 
 @torch.no_grad()
-def lse_many(syncnet, jobs, fps=25., vshift=15, batch_size=128, sink=None):
+def lse_many(syncnet, jobs, fps=25., vshift=15, batch_size=128, sink=None, precision="f32"):
     """`lse_like` for every `ScoreJob` of the iterable `jobs` (consumed lazily), the windows of successive clips packed into
     SyncNet batches of exactly `batch_size` (evaluation/scores_LSE/calculate_scores_LRS.py:41-47 scores one video per call).
 
@@ -191,7 +201,9 @@ def lse_many(syncnet, jobs, fps=25., vshift=15, batch_size=128, sink=None):
     embedded, w2l_lse_score_segments scores all its clips in one launch, one copy brings the scores back, and the group is
     released: the memory alive is one group plus the job being read.  Results arrive in job order as
     dict(key, offset, lse_c, lse_d, n, mdist) - at `sink(result)`, or in the returned list.  A clip without one full window
-    gives n = 0 and None for the rest, and takes part in no launch.  The model runs in eval mode and is put back afterwards."""
+    gives n = 0 and None for the rest, and takes part in no launch.  The model runs in eval mode and is put back afterwards.
+    `precision`: SyncNet arithmetic, "f32" (default) or "bf16" (`SyncNet_color.embed_rows(..., precision="bf16")`)."""
+    _precision_kw(precision)
     if batch_size < 1:
         raise ValueError("batch_size must be at least 1")
     if not 0 <= vshift <= 127:
@@ -205,7 +217,7 @@ def lse_many(syncnet, jobs, fps=25., vshift=15, batch_size=128, sink=None):
     def flush():
         nonlocal group, windows
         clips = [(faces, mel, rows) for _, faces, mel, rows in group if rows]
-        scored = iter(_score_group(syncnet, clips, vshift, batch_size)) if clips else None
+        scored = iter(_score_group(syncnet, clips, vshift, batch_size, precision)) if clips else None
         keys = [(key, bool(rows)) for key, _, _, rows in group]
         group, windows = [], 0      # released before the results go out
         del clips

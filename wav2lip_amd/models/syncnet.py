@@ -3,9 +3,9 @@
 import torch
 from torch import nn
 
-from .. import autograd, engine
+from .. import autograd, bf16, engine
 from .._lib import check, current_stream, load, ptr
-from .wav2lip import _down, _res, audio_encoder_rows, make_stack
+from .wav2lip import _BufPoolB, _down, _res, _run_chain_b, audio_encoder_rows, check_precision, make_stack
 
 SYNC_FACE_ENCODER = (                              # models/syncnet.py:11-33
     [("c", 15, 32, 7, 1, 3, 0),
@@ -32,6 +32,68 @@ class _SyncGraph:
         self.plan = plan
 
 
+BUF_LIMIT = 1 << 31      # bytes: the per-buffer rule of the bf16 kernels (32-bit byte offsets, W2L_REQUIRE in every launch)
+
+
+def bf16_buffer_sizes(N, H=48, W=96):
+    """bytes of every buffer _SyncGraphB allocates for batch N and an H x W face input, from the layer tables alone: the two bf16
+    inputs (16 and 8 channels), then every layer's bf16 output"""
+    sizes = [2 * N * H * W * 16, 2 * N * 80 * 16 * 8]
+    for rows, (h, w) in ((SYNC_FACE_ENCODER, (H, W)), (audio_encoder_rows(2), (80, 16))):
+        for _, _, cout, k, s, p, _ in rows:
+            sh, sw = engine._pair(s)
+            h, w = (h + 2 * p - k) // sh + 1, (w + 2 * p - k) // sw + 1
+            if h < 1 or w < 1:
+                raise RuntimeError("input too small for the SyncNet encoders")
+            sizes.append(2 * N * h * w * bf16.round8(cout))
+    return sizes
+
+
+def bf16_batch_limit(H=48, W=96):
+    """the first batch size at which a buffer of _SyncGraphB reaches 2 GiB (every size is linear in N)"""
+    return -(-BUF_LIMIT // max(bf16_buffer_sizes(1, H, W)))
+
+
+def check_bf16_buffers(N, H=48, W=96):
+    big = max(bf16_buffer_sizes(N, H, W))
+    if big >= BUF_LIMIT:
+        raise RuntimeError("SyncNet bf16: a batch of %d windows (%d x %d) needs a %d-byte buffer, over the kernels' 2 GiB limit: "
+                           "batches below %d fit" % (N, H, W, big, bf16_batch_limit(H, W)))
+
+
+class _SyncGraphB:
+    """The bf16-STORAGE inference plan of both encoders for one (batch, height, width, device): bf16 NHWC inputs (15 + 1 and 1 + 7
+    channels), every layer a bf16.ConvB launch with its eval-mode BatchNorm folded into the fp32 epilogue (_run_chain_b), the two
+    512-channel outputs stored in bf16 like every other layer.  w2l_sync_embeddings_bf16 normalises them into fp32."""
+
+    def __init__(self, model, N, H, W, device):
+        check_bf16_buffers(N, H, W)        # before anything is allocated
+        self.lib = load()
+        self.N, self.H, self.W = N, H, W
+        pool = _BufPoolB(device)
+        plan = engine.Plan()
+        self.face_in = bf16.new_buf(N, H, W, 16, device)       # 15 channels + 1 zero pad
+        self.mel_in = bf16.new_buf(N, 80, 16, 8, device)       # 1 mel channel + 7 zero pad
+        self.face_out, _ = _run_chain_b(plan, pool, "face_encoder", list(model.face_encoder), bf16.ActB(self.face_in, 0, 15), device)
+        self.audio_out, _ = _run_chain_b(plan, pool, "audio_encoder", list(model.audio_encoder), bf16.ActB(self.mel_in, 0, 1), device)
+        for o in (self.face_out, self.audio_out):
+            if (o.H, o.W) != (1, 1):
+                raise RuntimeError("SyncNet encoders must end at 1x1, got %dx%d" % (o.H, o.W))
+        plan.tuned = True          # launch configurations come from the shapes: nothing to autotune
+        self.plan = plan
+        self.scratch_bytes = pool.total_bytes
+
+    def dispatch(self, N=None):
+        """[(record name, family, tile, ksplit)] of every launch of the plan (bf16.plan_dispatch): the kernel each one runs, or
+        would run at batch N"""
+        return bf16.plan_dispatch(self.plan, N)
+
+    def embeddings(self, B, audio_ptr, face_ptr):
+        """the plan's two outputs, L2-normalised, into fp32 [B, 512] rows at the two addresses (one launch)"""
+        check(self.lib.w2l_sync_embeddings_bf16(current_stream(), B, 512, self.audio_out.ptr, self.audio_out.cs, self.face_out.ptr,
+                                                self.face_out.cs, audio_ptr, face_ptr), "sync_embeddings_bf16")
+
+
 class SyncNet_color(nn.Module):
     def __init__(self):
         super().__init__()
@@ -40,25 +102,38 @@ class SyncNet_color(nn.Module):
         self._graphs = {}
         object.__setattr__(self, "_train_graphs", autograd.GraphCache(autograd.build_syncnet))
 
-    def forward(self, audio_sequences, face_sequences):
+    def forward(self, audio_sequences, face_sequences, precision="f32"):
+        """`precision` "bf16" (inference only): the opt-in bf16-storage plan, _SyncGraphB; the embeddings stay fp32"""
+        check_precision(precision)
         engine.require_cuda(face_sequences, "face_sequences")
         with engine.on_device_of(face_sequences, self):      # launches go to the current stream of the INPUT's device; refuses a device mismatch
-            return self._forward_impl(audio_sequences, face_sequences)
+            return self._forward_impl(audio_sequences, face_sequences, precision)
 
-    def _forward_impl(self, audio_sequences, face_sequences):
+    def _forward_impl(self, audio_sequences, face_sequences, precision="f32"):
         engine.require_cuda(face_sequences, "face_sequences")
         engine.require_cuda(audio_sequences, "audio_sequences")
         face = face_sequences.contiguous().float()
         audio = audio_sequences.contiguous().float()
         N, C_, H, W = face.shape
         if autograd.needs_graph(self, (audio, face)):
+            if precision != "f32":
+                raise ValueError("SyncNet_color: precision=%r is an inference switch (eval mode, no gradients); training precision "
+                                 "is engine.set_train_precision" % (precision,))
             # train mode (color_syncnet_train.py:150-158) or the frozen expert inside the generator's loss
             # (wav2lip_train.py:187-198, which never calls .eval(): BN runs on batch statistics there too)
             a, v = autograd.run_graph(self._train_graphs, self, (N, H, W, str(face.device)), (N, H, W, face.device),
                                       (audio, face))
             return autograd.L2NormRows.apply(a.reshape(N, -1)), autograd.L2NormRows.apply(v.reshape(N, -1))
-        g = self._eval_graph(N, H, W, face.device)
+        g = self._eval_graph(N, H, W, face.device, precision)
         s = current_stream()
+        if precision == "bf16":
+            check(g.lib.w2l_nchw_to_nhwc_bf16(s, N, C_, H, W, ptr(face), ptr(g.face_in), 16, 16), "nchw_to_nhwc_bf16")
+            check(g.lib.w2l_nchw_to_nhwc_bf16(s, N, 1, 80, 16, ptr(audio), ptr(g.mel_in), 8, 8), "nchw_to_nhwc_bf16")
+            g.plan.run()
+            a = torch.empty((N, 512), device=face.device, dtype=torch.float32)
+            v = torch.empty((N, 512), device=face.device, dtype=torch.float32)
+            g.embeddings(N, ptr(a), ptr(v))
+            return a, v
         check(g.lib.w2l_nchw_to_nhwc(s, N, C_, H, W, ptr(face), ptr(g.face_in), 16, 16), "nchw_to_nhwc")
         check(g.lib.w2l_nchw_to_nhwc(s, N, 1, 80, 16, ptr(audio), ptr(g.mel_in), 4, 4), "nchw_to_nhwc")
         g.plan.run()
@@ -68,22 +143,24 @@ class SyncNet_color(nn.Module):
         check(g.lib.w2l_l2norm_rows(s, N, 512, g.face_out.ptr, g.face_out.cs, ptr(v)), "l2norm_rows")
         return a, v
 
-    def _eval_graph(self, N, H, W, device):
-        """the one cached inference graph: another (N, H, W), device or weight version replaces it"""
+    def _eval_graph(self, N, H, W, device, precision="f32"):
+        """the one cached inference graph: another (N, H, W), device, precision or weight version replaces it"""
         ver = engine.param_version(self)
-        key = (N, H, W, str(device))
+        key = (N, H, W, str(device), precision)
         g = self._graphs.get(key)
         if g is None or g[0] != ver:
             self._graphs.clear()
-            g = (ver, _SyncGraph(self, N, H, W, device))
+            g = (ver, (_SyncGraphB if precision == "bf16" else _SyncGraph)(self, N, H, W, device))
             self._graphs[key] = g
         return g[1]
 
-    def embed_rows(self, rows, B, audio_out, face_out, offset=0):
+    def embed_rows(self, rows, B, audio_out, face_out, offset=0, precision="f32"):
         """Eval mode only: the embeddings of the `B` windows of a device row table (w2l_sync_row, include/w2l_hip.h; 96x96 face
         crops) into audio_out[offset:offset+B] and face_out[offset:offset+B], two contiguous fp32 [rows, 512] device tensors.
         w2l_sync_window_rows writes the graph's two inputs from the table, the plan runs, w2l_l2norm_rows writes the outputs:
-        no tensor is made on the way.  The graph cache is `forward`'s: a caller that keeps to one `B` builds one plan."""
+        no tensor is made on the way.  The graph cache is `forward`'s: a caller that keeps to one `B` builds one plan.
+        `precision` "bf16": w2l_sync_window_rows_bf16, the bf16-storage plan, w2l_sync_embeddings_bf16; the outputs stay fp32."""
+        check_precision(precision)
         if self.training:
             raise RuntimeError("SyncNet_color.embed_rows is an inference path: call .eval() first")
         engine.require_cuda(face_out, "face_out")
@@ -95,8 +172,13 @@ class SyncNet_color(nn.Module):
         if rows.device != face_out.device or rows.dtype != torch.uint8 or not rows.is_contiguous() or rows.numel() < 32 * B or B < 1:
             raise ValueError("rows must be a contiguous uint8 device tensor holding B >= 1 w2l_sync_row entries")
         with engine.on_device_of(face_out, self):
-            g = self._eval_graph(B, 48, 96, face_out.device)
+            g = self._eval_graph(B, 48, 96, face_out.device, precision)
             s = current_stream()
+            if precision == "bf16":
+                check(g.lib.w2l_sync_window_rows_bf16(s, B, ptr(rows), 96, ptr(g.face_in), 16, ptr(g.mel_in), 8), "sync_window_rows_bf16")
+                g.plan.run()
+                g.embeddings(B, audio_out.data_ptr() + 2048 * offset, face_out.data_ptr() + 2048 * offset)
+                return
             check(g.lib.w2l_sync_window_rows(s, B, ptr(rows), 96, ptr(g.face_in), 16, ptr(g.mel_in), 4), "sync_window_rows")
             g.plan.run()
             check(g.lib.w2l_l2norm_rows(s, B, 512, g.audio_out.ptr, g.audio_out.cs, audio_out.data_ptr() + 2048 * offset),
