@@ -29,6 +29,9 @@
  *                         cap and of rescale_frames, one frame per row)
  *   w2l_mel_gather_rows   evaluation/gen_videos_from_filelist.py:176-183 (mel windows, one spectrogram per row)
  *   w2l_s3fd_pack_rows    face_detection/api.py:62 + detection/sfd/detect.py:57-63 (the detector's input), one frame per row
+ *   w2l_s3fd_pack_rows_scaled  inference.py:202-203 (the `cv2.resize(frame, (w // k, h // k))` of --resize_factor) fused into the
+ *                         detector's input: detection at reduced size, output frames untouched (--face_det_scale)
+ *   w2l_s3fd_first_rect_scaled  face_detection/api.py:61-77 with the rect mapped back to the full frame first
  *   w2l_face_boxes_segments  evaluation/gen_videos_from_filelist.py:35-42, :61-77 = inference.py:59-66, :90-104 (pads, clipping,
  *                         "Face not detected", get_smoothened_boxes) for every clip of a group in one launch
  *   w2l_melspectrogram    audio.py:45-51 (preemphasis, STFT, mel basis, dB, normalise)
@@ -255,6 +258,14 @@ int w2l_s3fd_pack(void* stream, long long npix, const uint8_t* bgr, float* y, in
  * elsewhere).  Image b of y [B,H,W,y_cs] is what w2l_s3fd_pack writes for that frame, byte for byte: a batch may hold frames of
  * several clips, read where they lie (face_detection/many.py).  B <= 65535, H * W <= 2^29. */
 int w2l_s3fd_pack_rows(void* stream, int B, int H, int W, const uint64_t* frames, float* y, int y_cs);
+/* The reduced-resolution row-table pack (`--face_det_scale k`: the detector sees cv2.resize(frame, (w // k, h // k)), the resize of
+ * inference.py:202-203, while every output frame keeps its size).  Entry b of `frames` is a u8 [Hs,Ws,3] BGR frame at any byte
+ * address; image b of y fp32 [B,Hd,Wd,y_cs] is what w2l_s3fd_pack_rows writes for the Hd x Wd frame w2l_resize_rows_u8 makes of
+ * it, byte for byte (the equal-size copy, the exact-2x average and the 11-bit bilinear path included) - the reduced frame itself
+ * is never stored.  Any (Hd, Wd) is taken, not only (Hs / k, Ws / k).  Refused with an error code, nothing written: a NULL
+ * pointer, B outside [1, 65535], a size below 1, Hs * Ws or Hd * Wd above 2^29, a table that is not 8-byte aligned, y not 16-byte
+ * aligned, y_cs not a multiple of 4 (a pixel leaves as one 16-byte store; channels >= 4 are left as they are). */
+int w2l_s3fd_pack_rows_scaled(void* stream, int B, int Hs, int Ws, int Hd, int Wd, const uint64_t* frames, float* y, int y_cs);
 /* F.max_pool2d(x, 2, 2) on NHWC: y [N,H/2,W/2,y_cs] (net_s3fd.py:75-97); C %% 4 == 0 */
 int w2l_maxpool2x2(void* stream, int N, int H, int W, int C, const float* x, int x_cs, float* y, int y_cs);
 /* L2Norm (net_s3fd.py:6-19): y[row][c] = x[row][c] / (sqrt(sum_c x^2) + 1e-10) * weight[c] */
@@ -282,6 +293,13 @@ int w2l_s3fd_nms(void* stream, int B, int P, const float* table, float gate, flo
  * [0, P), or counts[b] is not in [0, P]; rect zeros).  The table is fp32 for either detector precision. */
 int w2l_s3fd_first_rect(void* stream, int B, int P, const float* table, const int* keep, const int* counts, float thresh,
                         int* rects, int* flags);
+/* w2l_s3fd_first_rect for a detector that ran on a reduced frame: the kept row's x1, x2 are multiplied by sx and its y1, y2 by sy
+ * (one fp32 multiply each, round to nearest, no contraction) BEFORE the clip at 0 and the truncation of api.py:61-77, and the
+ * "host must decide" flag (NaN, +inf, >= 2^31) is decided on the product.  The caller passes sx = float32(W / Wd) and
+ * sy = float32(H / Hd), divided in double and rounded once.  sx = sy = 1 gives w2l_s3fd_first_rect's output byte for byte.
+ * Refused: sx or sy that is not finite and positive. */
+int w2l_s3fd_first_rect_scaled(void* stream, int B, int P, const float* table, const int* keep, const int* counts, float thresh,
+                               float sx, float sy, int* rects, int* flags);
 
 /* The per-clip finish of face_detect (inference.py:90-104 pads + clipping + "Face not detected", :59-66 get_smoothened_boxes;
  * evaluation/gen_videos_from_filelist.py:35-42, :61-77 is the same code) for many clips in one launch.  rects [R][4] = (x1, y1, x2, y2)
@@ -315,6 +333,9 @@ int w2l_s3fd_pack_bf16(void* stream, long long npix, const uint8_t* bgr, void* y
 /* The row-table form (w2l_s3fd_pack_rows): image b of y bf16 [B,H,W,y_cs] is what w2l_s3fd_pack_bf16 writes for the frame at
  * frames[b], byte for byte */
 int w2l_s3fd_pack_rows_bf16(void* stream, int B, int H, int W, const uint64_t* frames, void* y, int y_cs);
+/* w2l_s3fd_pack_rows_scaled for the bf16 detector: y bf16 [B,Hd,Wd,y_cs], y_cs %% 8 == 0, channels 3 .. y_cs-1 zero; the values
+ * are integers with |v| <= 152, exact in bf16.  Byte-equal to w2l_resize_rows_u8 followed by w2l_s3fd_pack_rows_bf16. */
+int w2l_s3fd_pack_rows_scaled_bf16(void* stream, int B, int Hs, int Ws, int Hd, int Wd, const uint64_t* frames, void* y, int y_cs);
 /* F.max_pool2d(x, 2, 2) on bf16 NHWC (net_s3fd.py:75-97, floor semantics): bit-equal to torch on the same tensor; C %% 8 == 0 */
 int w2l_maxpool2x2_bf16(void* stream, int N, int H, int W, int C, const void* x, int x_cs, void* y, int y_cs);
 /* L2Norm (net_s3fd.py:6-19) on bf16 rows: sum of squares and x / (sqrt(.) + 1e-10) * weight[c] in fp32 (weight fp32 [C]),

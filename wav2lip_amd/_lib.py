@@ -113,14 +113,17 @@ SIGNATURES = {
     "w2l_resize_rows_u8": (_i, [_vp, _i, _vp, _i]),
     "w2l_s3fd_pack": (_i, [_vp, _ll, _vp, _vp, _i]),
     "w2l_s3fd_pack_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _i]),
+    "w2l_s3fd_pack_rows_scaled": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i]),
     "w2l_maxpool2x2": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i]),
     "w2l_l2norm_scale": (_i, [_vp, _ll, _i, _vp, _i, _vp, _vp, _i]),
     "w2l_s3fd_decode": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
     "w2l_s3fd_nms": (_i, [_vp, _i, _i, _vp, _f, _f, _vp, _vp, _vp, _ll]),
     "w2l_s3fd_first_rect": (_i, [_vp, _i, _i, _vp, _vp, _vp, _f, _vp, _vp]),
+    "w2l_s3fd_first_rect_scaled": (_i, [_vp, _i, _i, _vp, _vp, _vp, _f, _f, _f, _vp, _vp]),
     "w2l_face_boxes_segments": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "w2l_s3fd_pack_bf16": (_i, [_vp, _ll, _vp, _vp, _i]),
     "w2l_s3fd_pack_rows_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp, _i]),
+    "w2l_s3fd_pack_rows_scaled_bf16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i]),
     "w2l_maxpool2x2_bf16": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i]),
     "w2l_l2norm_scale_bf16": (_i, [_vp, _ll, _i, _vp, _i, _vp, _vp, _i]),
     "w2l_s3fd_headb_create": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),

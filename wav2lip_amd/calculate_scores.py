@@ -13,7 +13,7 @@ values are not comparable to the paper's); inputs are the uncompressed AVIs of c
 track, read back with `audio.load_wav(path, 16000)`; `--tmp_dir` and `--reference` are accepted and unused (nothing is unpacked to
 disk).  The network sees the lower half of a face crop, so every frame needs a face box: `--box y1 y2 x1 x2` for all frames, or
 `inference.face_detect` per clip as the filelist command runs it (no pads, smoothing on).  `--fps` is the frame rate the mel
-windows are placed at, `--face_det_precision` the detector's arithmetic, `--precision` SyncNet's (fp32, or the opt-in bf16-storage
+windows are placed at, `--face_det_precision` the detector's arithmetic, `--face_det_scale K` the size of the frame it sees (1/K), `--precision` SyncNet's (fp32, or the opt-in bf16-storage
 plan of DESIGN.md 3o).  `--packed_face_det` (off by default) detects the
 faces of successive clips in shared detector batches (`face_detection.detect_many`); scored clips, skipped clips and
 their messages stay what they are without it.
@@ -53,6 +53,8 @@ def build_cli_parser():
                    help='One face box for every frame; without it the face detector runs on every clip')
     p.add_argument('--face_det_precision', default='fp32', choices=['fp32', 'bf16'],
                    help='Face detector arithmetic: fp32 (default, matches the reference) or bf16 storage')
+    from .inference import add_det_scale_flag
+    add_det_scale_flag(p)
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
                    help='SyncNet arithmetic: fp32 (default, matches the reference) or bf16 storage')
     p.add_argument('--packed_face_det', default=False, action='store_true',
@@ -205,7 +207,8 @@ def main(argv=None, state_dict=None):
         from . import face_detection
         detector = face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False, device=str(device),
                                                 state_dict=state_dict,
-                                                **inference._precision_kw(inference.CLI_PRECISION[args.face_det_precision]))
+                                                **inference._precision_kw(inference.CLI_PRECISION[args.face_det_precision]),
+                                                **inference._det_scale_kw(args.face_det_scale))
     videos = sorted(glob.glob(os.path.join(args.data_root, "*.avi")))
     scored, skipped = [], []
 

@@ -2,19 +2,24 @@
 // are the SAME fused conv launches as the generator's (conv_igemm.hip / conv_wino.hip with bias + ReLU, no BatchNorm).
 //   w2l_s3fd_pack       detect.py:57-58 + api.py:62  uint8 BGR frames -> RGB order, minus (104,117,123), fp32 NHWC4
 //   w2l_s3fd_pack_rows  the same per frame of an address table: frames of several clips in one batch, read where they lie
+//   w2l_s3fd_pack_rows_scaled[_bf16]  inference.py:202-203 (`cv2.resize(frame, (w // k, h // k))`) fused into the row-table pack:
+//                       the detector reads a frame at reduced size, the reduced frame is never stored
 //   w2l_maxpool2x2      net_s3fd.py:75,79,85,91,97   F.max_pool2d(h, 2, 2)
 //   w2l_l2norm_scale    net_s3fd.py:6-19             x / (sqrt(sum_c x^2) + 1e-10) * weight[c]
 //   w2l_s3fd_decode     net_s3fd.py:123-126 (max-out background), detect.py:66-84 (softmax, priors, decode)
 //   w2l_s3fd_nms        sfd_detector.py:39-45 gate + bbox.py:44-64 greedy NMS, bit-exact keep list
 //   w2l_s3fd_first_rect sfd_detector.py:45 + api.py:61-77  first kept box above 0.5 -> int rect, one row per image
+//   w2l_s3fd_first_rect_scaled  the same with the box mapped back to the full frame (x * sx, y * sy) before the clip and int()
 //   w2l_face_boxes_segments  inference.py:59-66, :90-104 / gen_videos_from_filelist.py:35-42, :61-77  pads, clipping, temporal
 //                       smoothing and "no face" of many clips in one launch
 // All HBM-bound, NHWC, float4 where the channel count allows.
 #include "w2l_common.h"
+#include "resize_px.h"
 
 namespace w2l {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ void s3fd_store(float* o, int y_cs, float c0, float c1, float c2) {
     if (y_cs >= 4 && (y_cs & 3) == 0) *reinterpret_cast<f32x4*>(o) = f32x4{c0, c1, c2, 0.f};
@@ -48,6 +53,97 @@ __global__ void s3fd_pack_rows_kernel(int npix, const uint64_t* __restrict__ fra
             float c0, c1, c2;
             s3fd_pixel(px + 3 * k, m0, m1, m2, c0, c1, c2);
             s3fd_store(yb + (long long)(i0 + k) * y_cs, y_cs, c0, c1, c2);
+        }
+    }
+}
+
+// ---- the reduced-resolution pack (--face_det_scale k): image b of y [B,Hd,Wd,y_cs] is the pack of cv2.resize(frame b, (Wd, Hd)),
+// the arithmetic of resize_px / resize_rows_kernel (resize_px.h, resize.hip) followed by s3fd_pixel, so the result is byte-equal
+// to w2l_resize_rows_u8 into a scratch frame + w2l_s3fd_pack_rows on it - without the scratch frame.  An item is 4 neighbouring
+// destination pixels of one line, as in resize_rows_kernel: the vertical tap once per item, the horizontal tap once per pixel;
+// a pixel leaves as one 16-byte store (fp32 at 4 channels, bf16 at 8).  The two tap-free branches read contiguous bytes (12 of
+// one line for the copy, 24 of each of two lines for the exact 2x average): dword loads where their address is 4-byte aligned -
+// frames lie at any byte address and Ws * 3 is rarely a multiple of 4, so that is decided per line segment.  The bilinear branch
+// gathers bytes (neighbouring items share source pixels: L1/L2 hits).  HBM-bound: reads <= Hs*Ws*3 bytes, writes Hd*Wd*16; no LDS.
+template <int N>
+__device__ __forceinline__ void load_span(const uint8_t* __restrict__ p, uint8_t out[N]) {
+    static_assert(N % 4 == 0, "whole dwords");
+    if ((reinterpret_cast<uintptr_t>(p) & 3) == 0) {
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+#pragma unroll
+        for (int k = 0; k < N / 4; ++k) {
+            const uint32_t v = q[k];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) out[4 * k + e] = (uint8_t)(v >> (8 * e));
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; ++k) out[k] = p[k];
+    }
+}
+
+__device__ __forceinline__ void s3fd_store_px(float* o, int, float c0, float c1, float c2) {
+    *reinterpret_cast<f32x4*>(o) = f32x4{c0, c1, c2, 0.f};              // y_cs % 4 == 0: channels >= 4 stay as they are (s3fd_store)
+}
+__device__ __forceinline__ void s3fd_store_px(__bf16* o, int y_cs, float c0, float c1, float c2) {
+    bf16x8 v;                                                           // every 8-channel group, as s3fd_pack_rows_bf16_kernel
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (__bf16)0.f;
+    for (int g = 1; g < (y_cs >> 3); ++g) *reinterpret_cast<bf16x8*>(o + g * 8) = v;
+    v[0] = (__bf16)c0; v[1] = (__bf16)c1; v[2] = (__bf16)c2;          // integers with |v| <= 152: exact
+    *reinterpret_cast<bf16x8*>(o) = v;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void s3fd_pack_rows_scaled_kernel(int Hs, int Ws, int Hd, int Wd,
+                                                                    const uint64_t* __restrict__ frames, T* __restrict__ y,
+                                                                    int y_cs, float m0, float m1, float m2) {
+    const int b = blockIdx.y;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(frames[b]);
+    const long long sstride = (long long)Ws * 3;
+    T* yb = y + (long long)b * Hd * Wd * y_cs;
+    const int groups = (Wd + 3) >> 2;
+    const int nitems = Hd * groups;                     // <= Hd*Wd <= 2^29 (checked by the entry point)
+    const bool same = Hs == Hd && Ws == Wd, half = Hs == 2 * Hd && Ws == 2 * Wd;
+    for (int item = blockIdx.x * blockDim.x + threadIdx.x; item < nitems; item += gridDim.x * blockDim.x) {
+        const int dy = item / groups, x0 = (item - dy * groups) << 2;
+        const int np = min(4, Wd - x0);
+        uint8_t px[4][3];
+        if (same && np == 4) {
+            uint8_t raw[12];
+            load_span<12>(src + dy * sstride + (long long)x0 * 3, raw);
+#pragma unroll
+            for (int k = 0; k < 12; ++k) px[k / 3][k % 3] = raw[k];
+        } else if (half && np == 4) {
+            const uint8_t* p0 = src + (2 * dy) * sstride + (long long)x0 * 6;
+            uint8_t r0[24], r1[24];
+            load_span<24>(p0, r0);
+            load_span<24>(p0 + sstride, r1);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    px[k][c] = (uint8_t)(((int)r0[6 * k + c] + r0[6 * k + 3 + c] + r1[6 * k + c] + r1[6 * k + 3 + c] + 2) >> 2);
+        } else if (same || half) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < np) resize_px(src, sstride, Hs, Ws, x0 + k, dy, Wd, Hd, px[k]);
+        } else {
+            const AxisTap ty = axis_tap(dy, Hs, Hd, false);
+            const uint8_t* r0 = src + ty.s0 * sstride;
+            const uint8_t* r1 = src + ty.s1 * sstride;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < np) lerp_px(r0, r1, axis_tap(x0 + k, Ws, Wd, true), ty, px[k]);
+        }
+        T* o = yb + ((long long)dy * Wd + x0) * y_cs;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k < np) {
+                float c0, c1, c2;
+                s3fd_pixel(px[k], m0, m1, m2, c0, c1, c2);
+                s3fd_store_px(o + (long long)k * y_cs, y_cs, c0, c1, c2);
+            }
         }
     }
 }
@@ -213,11 +309,14 @@ __global__ __launch_bounds__(kNmsThreads) void s3fd_nms_kernel(int P, const floa
 // truncated as Python's int() truncates.  One wave per image scans the keep list 64 entries at a time; the lowest lane that
 // decides (a passing row, or a row index outside the table) writes the image's result.  A coordinate Python's int() would
 // refuse or that int32 cannot hold (NaN, inf, >= 2^31) is not converted: the image is flagged and the caller's host rule runs.
+// kScaled (w2l_s3fd_first_rect_scaled, the detector ran on a reduced frame): x1, x2 are multiplied by sx and y1, y2 by sy first -
+// one fp32 multiply each, never contracted - and the clip, the truncation and the flag are decided on the product.
 constexpr int kRectNone = 0, kRectFound = 1, kRectHost = 2;
 
+template <bool kScaled>
 __global__ __launch_bounds__(64) void s3fd_first_rect_kernel(int P, const float* __restrict__ table, const int* __restrict__ keep,
-                                                             const int* __restrict__ counts, float thresh, int* __restrict__ rects,
-                                                             int* __restrict__ flags) {
+                                                             const int* __restrict__ counts, float thresh, float sx, float sy,
+                                                             int* __restrict__ rects, int* __restrict__ flags) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const float* tb = table + (long long)b * P * 5;
     const int* kp = keep + (long long)b * P;
@@ -244,8 +343,9 @@ __global__ __launch_bounds__(64) void s3fd_first_rect_kernel(int P, const float*
             else {
                 const float* d = tb + (long long)row * 5;
                 for (int k = 0; k < 4; ++k) {
-                    const float x = d[k] > 0.f ? d[k] : 0.f;
-                    if (!(d[k] == d[k]) || !(x < 2147483648.f)) { flag = kRectHost; break; }   // NaN, +inf, >= 2^31
+                    const float c = kScaled ? __fmul_rn(d[k], (k & 1) ? sy : sx) : d[k];
+                    const float x = c > 0.f ? c : 0.f;
+                    if (!(c == c) || !(x < 2147483648.f)) { flag = kRectHost; break; }       // NaN, +inf, >= 2^31
                     v[k] = (int)x;                                                          // x >= 0: truncation = int()
                 }
                 if (flag == kRectHost) v[0] = v[1] = v[2] = v[3] = 0;
@@ -352,6 +452,8 @@ __global__ __launch_bounds__(64) void face_boxes_segments_kernel(const BoxSeg* _
     }
 }
 
+constexpr int kPackScaledGridCap = 1024;      // workgroups per image of the reduced-resolution pack, as its row-table siblings
+
 static inline int grid1d(long long work, int block, int cap = 16384) {
     long long g = (work + block - 1) / block;
     if (g > cap) g = cap;
@@ -382,6 +484,37 @@ int w2l_s3fd_pack_rows(void* stream, int B, int H, int W, const uint64_t* frames
     const int npix = H * W;
     hipLaunchKernelGGL(s3fd_pack_rows_kernel, dim3(grid1d((npix + 3) / 4, 256, 1024), B), dim3(256), 0,
                        static_cast<hipStream_t>(stream), npix, frames, y, y_cs, 104.f, 117.f, 123.f);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+// the checks the two reduced-resolution packs share; the frame addresses live in device memory and are the caller's
+static int pack_rows_scaled_check(const char* name, int B, int Hs, int Ws, int Hd, int Wd, const void* frames, const void* y) {
+    W2L_REQUIRE(frames && y, "%s: NULL argument", name);
+    W2L_REQUIRE(B >= 1 && B <= 65535, "%s: B=%d outside 1..65535", name, B);
+    W2L_REQUIRE(Hs >= 1 && Ws >= 1 && Hd >= 1 && Wd >= 1, "%s: sizes %d x %d -> %d x %d must all be at least 1", name, Hs, Ws, Hd, Wd);
+    W2L_REQUIRE((long long)Hs * Ws <= (1ll << 29) && (long long)Hd * Wd <= (1ll << 29), "%s: Hs * Ws and Hd * Wd <= 2^29", name);
+    W2L_REQUIRE((reinterpret_cast<uintptr_t>(frames) & 7) == 0, "%s: the address table must be 8-byte aligned", name);
+    W2L_REQUIRE((reinterpret_cast<uintptr_t>(y) & 15) == 0, "%s: y must be 16-byte aligned", name);
+    return W2L_OK;
+}
+
+int w2l_s3fd_pack_rows_scaled(void* stream, int B, int Hs, int Ws, int Hd, int Wd, const uint64_t* frames, float* y, int y_cs) {
+    if (int e = pack_rows_scaled_check("s3fd_pack_rows_scaled", B, Hs, Ws, Hd, Wd, frames, y)) return e;
+    W2L_REQUIRE(y_cs >= 4 && (y_cs & 3) == 0, "s3fd_pack_rows_scaled: y_cs=%d must be a multiple of 4 (16-byte pixel stores)", y_cs);
+    hipLaunchKernelGGL(s3fd_pack_rows_scaled_kernel<float>, dim3(grid1d((long long)Hd * ((Wd + 3) / 4), 256, kPackScaledGridCap), B),
+                       dim3(256), 0, static_cast<hipStream_t>(stream), Hs, Ws, Hd, Wd, frames, y, y_cs, 104.f, 117.f, 123.f);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_s3fd_pack_rows_scaled_bf16(void* stream, int B, int Hs, int Ws, int Hd, int Wd, const uint64_t* frames, void* y, int y_cs) {
+    if (int e = pack_rows_scaled_check("s3fd_pack_rows_scaled_bf16", B, Hs, Ws, Hd, Wd, frames, y)) return e;
+    W2L_REQUIRE(y_cs >= 8 && (y_cs & 7) == 0, "s3fd_pack_rows_scaled_bf16: y_cs=%d must be a multiple of 8 (16-byte pixel stores)", y_cs);
+    W2L_REQUIRE((long long)B * Hd * Wd * y_cs * 2 < (1ll << 31), "s3fd_pack_rows_scaled_bf16: buffer larger than 2 GiB: split the batch");
+    hipLaunchKernelGGL(s3fd_pack_rows_scaled_kernel<__bf16>, dim3(grid1d((long long)Hd * ((Wd + 3) / 4), 256, kPackScaledGridCap), B),
+                       dim3(256), 0, static_cast<hipStream_t>(stream), Hs, Ws, Hd, Wd, frames, static_cast<__bf16*>(y), y_cs, 104.f,
+                       117.f, 123.f);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }
@@ -440,8 +573,20 @@ int w2l_s3fd_first_rect(void* stream, int B, int P, const float* table, const in
                         int* rects, int* flags) {
     W2L_REQUIRE(table && keep && counts && rects && flags && B >= 1 && P >= 1, "bad s3fd_first_rect arguments");
     W2L_REQUIRE((long long)B * P * 5 < (1ll << 31), "s3fd_first_rect: table too large");
-    hipLaunchKernelGGL(s3fd_first_rect_kernel, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), P, table, keep, counts,
-                       thresh, rects, flags);
+    hipLaunchKernelGGL(s3fd_first_rect_kernel<false>, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), P, table, keep,
+                       counts, thresh, 1.f, 1.f, rects, flags);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_s3fd_first_rect_scaled(void* stream, int B, int P, const float* table, const int* keep, const int* counts, float thresh,
+                               float sx, float sy, int* rects, int* flags) {
+    W2L_REQUIRE(table && keep && counts && rects && flags && B >= 1 && P >= 1, "bad s3fd_first_rect_scaled arguments");
+    W2L_REQUIRE((long long)B * P * 5 < (1ll << 31), "s3fd_first_rect_scaled: table too large");
+    W2L_REQUIRE(sx > 0.f && sy > 0.f && sx < INFINITY && sy < INFINITY,
+                "s3fd_first_rect_scaled: sx=%g and sy=%g must be finite and positive", (double)sx, (double)sy);
+    hipLaunchKernelGGL(s3fd_first_rect_kernel<true>, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), P, table, keep,
+                       counts, thresh, sx, sy, rects, flags);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

@@ -1,13 +1,16 @@
 """`FaceAlignment` (face_detection/api.py:41-77) over the HIP S3FD detector: `get_detections_for_batch(images)` takes the
 reference's numpy uint8 BGR batch [B,H,W,3] and returns one (x1, y1, x2, y2) int tuple or None per image.  `precision="bf16"`
-(opt-in) runs the detector network on its bf16-storage graph; the gate, NMS and thresholds are the same."""
+(opt-in) runs the detector network on its bf16-storage graph; the gate, NMS and thresholds are the same.  `det_scale=k` (opt-in,
+1..8) runs it on the frames at (H // k, W // k) and maps every rect back to the full frame: x * float32(W / (W // k)),
+y * float32(H / (H // k)), then the clip at 0 and int() of api.py:61-77 as before."""
 import os
 from enum import Enum
 
 import numpy as np
 import torch
 
-from .s3fd import RECT_FOUND, RECT_HOST, first_rects, nms, nms_batch, s3fd
+from .s3fd import (RECT_FOUND, RECT_HOST, check_det_scale, det_rect_scale, det_size, first_rects, nms, nms_batch, s3fd,
+                   scale_box)
 
 
 class LandmarksType(Enum):
@@ -28,9 +31,10 @@ DEFAULT_WEIGHTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "s3fd
 
 class FaceAlignment:
     def __init__(self, landmarks_type=LandmarksType._2D, network_size=NetworkSize.LARGE, device="cuda", flip_input=False,
-                 face_detector="sfd", verbose=False, path_to_detector=None, state_dict=None, precision="f32"):
+                 face_detector="sfd", verbose=False, path_to_detector=None, state_dict=None, precision="f32", det_scale=1):
         from ..models.wav2lip import check_precision
         self.precision = check_precision(precision)
+        self.det_scale = check_det_scale(det_scale)
         if face_detector != "sfd":
             raise NotImplementedError("only the 'sfd' detector of the reference is mirrored")
         if not torch.cuda.is_available() or "cuda" not in str(device):
@@ -47,19 +51,34 @@ class FaceAlignment:
         net.load_state_dict(state_dict)
         self.face_detector = net.to(device).eval()
 
+    def _scale_kw(self):
+        """the keyword `dense_boxes` / `dense_boxes_rows` take for a reduced detection frame: none at scale 1"""
+        k = getattr(self, "det_scale", 1)
+        return {} if k == 1 else {"det_scale": k}
+
+    def rect_scale(self, H, W):
+        """(sx, sy) that map a rect of the detection frame back to an H x W frame (`s3fd.det_rect_scale`); None at scale 1.
+        ValueError when the reduced frame would be too small for the network."""
+        k = getattr(self, "det_scale", 1)
+        return None if k == 1 else det_rect_scale(H, W, *det_size(H, W, k))
+
     def detect_from_batch(self, images_bgr):
         """sfd_detector.py:39-45 semantics per image: candidates (score > 0.05), NMS 0.3, keep score > 0.5.
-        images: numpy uint8 [B,H,W,3] BGR (or a torch uint8 tensor already on the device)"""
+        images: numpy uint8 [B,H,W,3] BGR (or a torch uint8 tensor already on the device).  At det_scale > 1 the boxes come back in
+        full-frame coordinates (`s3fd.scale_box`); the scores are the detector's."""
+        scale = None if getattr(self, "det_scale", 1) == 1 else self.rect_scale(*images_bgr.shape[1:3])
         if isinstance(images_bgr, np.ndarray):
             images_bgr = torch.from_numpy(np.ascontiguousarray(images_bgr)).to(self.device)
         with torch.no_grad():
-            levels = self.face_detector.dense_boxes(images_bgr, precision=self.precision)
+            levels = self.face_detector.dense_boxes(images_bgr, precision=self.precision, **self._scale_kw())
             table = torch.cat(levels, dim=1).contiguous()       # [B, sum FH*FW, 5]
             keep, counts = nms_batch(table, 0.05, 0.3)          # gate + NMS on the device: only the survivors cross PCIe
             counts_h = counts.cpu().tolist()
             out = []
             for b, n in enumerate(counts_h):
                 d = table[b].index_select(0, keep[b, :n].long()).cpu().numpy()
+                if scale is not None:
+                    d[:, :4] = scale_box(d[:, :4], *scale)
                 out.append([x for x in d if x[-1] > 0.5])
         return out
 
@@ -67,7 +86,7 @@ class FaceAlignment:
         """the batch's box table [B, P, 5] and its gated NMS (keep, counts), all on the device"""
         if isinstance(images_bgr, np.ndarray):
             images_bgr = torch.from_numpy(np.ascontiguousarray(images_bgr)).to(self.device)
-        levels = self.face_detector.dense_boxes(images_bgr, precision=self.precision)
+        levels = self.face_detector.dense_boxes(images_bgr, precision=self.precision, **self._scale_kw())
         table = torch.cat(levels, dim=1).contiguous()           # [B, sum FH*FW, 5]
         keep, counts = nms_batch(table, 0.05, 0.3)
         return table, keep, counts
@@ -76,33 +95,45 @@ class FaceAlignment:
         """`get_detections_for_batch` for the B frames of a device address table (`s3fd.dense_boxes_rows`), left on the device:
         rows [offset, offset + B) of the int32 arenas `rects` [R,4] = (x1, y1, x2, y2) and `flags` [R] receive what
         `w2l_s3fd_first_rect` writes.  No host read: an image whose NMS overflowed is flagged RECT_HOST like any other the device
-        does not decide (face_detection/many.py re-runs that clip through `inference.face_detect`)."""
+        does not decide (face_detection/many.py re-runs that clip through `inference.face_detect`).  At det_scale > 1 the rects are
+        full-frame coordinates (`w2l_s3fd_first_rect_scaled`)."""
         from .._lib import check, current_stream, load
+        scale = self.rect_scale(H, W)
         if (rects.dtype != torch.int32 or flags.dtype != torch.int32 or not rects.is_contiguous() or not flags.is_contiguous()
                 or rects.dim() != 2 or rects.shape[1] != 4 or flags.dim() != 1 or flags.shape[0] != rects.shape[0]
                 or offset < 0 or offset + B > rects.shape[0]):
             raise ValueError("rects_for_rows: int32 arenas [R,4] and [R] with rows [%d, %d) inside them" % (offset, offset + B))
         with torch.no_grad():
-            levels = self.face_detector.dense_boxes_rows(frames, B, H, W, precision=self.precision)
+            levels = self.face_detector.dense_boxes_rows(frames, B, H, W, precision=self.precision, **self._scale_kw())
             table = torch.cat(levels, dim=1).contiguous()
             keep, counts = nms_batch(table, 0.05, 0.3, host_overflow=False)
-            check(load().w2l_s3fd_first_rect(current_stream(), B, table.shape[1], table.data_ptr(), keep.data_ptr(), counts.data_ptr(),
-                                             0.5, rects.data_ptr() + 16 * offset, flags.data_ptr() + 4 * offset), "s3fd_first_rect")
+            out = (rects.data_ptr() + 16 * offset, flags.data_ptr() + 4 * offset)
+            if scale is None:
+                check(load().w2l_s3fd_first_rect(current_stream(), B, table.shape[1], table.data_ptr(), keep.data_ptr(),
+                                                 counts.data_ptr(), 0.5, *out), "s3fd_first_rect")
+            else:
+                check(load().w2l_s3fd_first_rect_scaled(current_stream(), B, table.shape[1], table.data_ptr(), keep.data_ptr(),
+                                                        counts.data_ptr(), 0.5, float(scale[0]), float(scale[1]), *out),
+                      "s3fd_first_rect_scaled")
 
     def get_detections_for_batch(self, images):
         """api.py:61-77 (the BGR->RGB flip of :62 happens inside the device pack kernel).  The rect of every image comes from one
         launch (`w2l_s3fd_first_rect`) and one copy back per batch; an image the device flags (a non-finite or huge coordinate)
-        takes the per-image host rule below, which raises what Python's int() raises there."""
+        takes the per-image host rule below, which raises what Python's int() raises there.  At det_scale > 1 both map the row back
+        to the full frame first, by the same float32 multiply."""
+        scale = None if getattr(self, "det_scale", 1) == 1 else self.rect_scale(*images.shape[1:3])
+
         def first_rect(dets):
             # the best-scoring detection, clipped at the image origin and truncated to ints; None when nothing survived NMS
             if len(dets) == 0:
                 return None
-            box = np.maximum(np.asarray(dets[0][:4]), 0)
+            box = dets[0][:4] if scale is None else scale_box(dets[0][:4], *scale)
+            box = np.maximum(np.asarray(box), 0)
             return tuple(int(v) for v in box)
 
         with torch.no_grad():
             table, keep, counts = self._candidates(images)
-            res = first_rects(table, keep, counts, 0.5)
+            res = first_rects(table, keep, counts, 0.5, scale)
             out = []
             for b, r in enumerate(res):
                 if r[4] == RECT_HOST:

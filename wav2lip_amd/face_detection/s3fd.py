@@ -6,7 +6,11 @@ Activations are NHWC fp32; the detection heads write (conf, loc) maps that `w2l_
 
 `dense_boxes(images, precision="bf16")` runs the opt-in bf16-storage graph (_GraphB) instead: bf16 NHWC activations, the
 convolutions as `w2l_convb` launches (bias as the fp32 shift, ReLU), the bf16 glue kernels of csrc/detect_bf16.hip and one fused
-head per level (`w2l_s3fd_headb_decode`: conf + loc contraction and decode, the logits never leave the chip)."""
+head per level (`w2l_s3fd_headb_decode`: conf + loc contraction and decode, the logits never leave the chip).
+
+`det_scale=k` (opt-in, 1..8) runs either graph on the frame at (H // k, W // k) - `cv2.resize(frame, (w // k, h // k))`, the sizes
+of inference.py:202-203 - which `w2l_s3fd_pack_rows_scaled` computes while it fills the graph's input; the tables stay in the
+reduced frame's coordinates and `det_rect_scale` gives the two fp32 factors that map a rect back."""
 import ctypes as C
 
 import numpy as np
@@ -119,6 +123,41 @@ class _Graph:
             check(self.lib.w2l_s3fd_decode(s, self.B, conf.H, conf.W, stride, conf.ptr, conf.cs, ncls, loc.ptr, loc.cs,
                                            ptr(out)), "s3fd_decode")
         return self.dense
+
+
+MIN_FRAME = 32           # the smallest height / width both graphs take: five 2x2 max-pools, each of at least 2 x 2 (_Graph, _GraphB)
+MAX_DET_SCALE = 8
+
+
+def check_det_scale(k):
+    """`det_scale` as an int in 1..MAX_DET_SCALE, or ValueError (a bool or a float is not an integer here)"""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_DET_SCALE:
+        raise ValueError("det_scale must be an integer in 1..%d, got %r" % (MAX_DET_SCALE, k))
+    return int(k)
+
+
+def det_size(H, W, k):
+    """(Hd, Wd) = (H // k, W // k), the frame the detector sees at det_scale k (inference.py:202-203's sizes); ValueError when a
+    reduced side falls below MIN_FRAME.  k = 1 returns (H, W) unchecked: that path is the graph's own business, as it was."""
+    k = check_det_scale(k)
+    if k == 1:
+        return int(H), int(W)
+    Hd, Wd = int(H) // k, int(W) // k
+    if Hd < MIN_FRAME or Wd < MIN_FRAME:
+        raise ValueError("det_scale=%d turns a %d x %d frame into %d x %d, below the %d x %d the S3FD graph needs (five 2x2 "
+                         "max-pools)" % (k, H, W, Hd, Wd, MIN_FRAME, MIN_FRAME))
+    return Hd, Wd
+
+
+def det_rect_scale(H, W, Hd, Wd):
+    """(sx, sy) = (float32(W / Wd), float32(H / Hd)): divided in double, rounded once - the factors of `scale_box`"""
+    return np.float32(float(W) / float(Wd)), np.float32(float(H) / float(Hd))
+
+
+def scale_box(box, sx, sy):
+    """(x1, y1, x2, y2) of the reduced frame -> the full frame: x * sx, y * sy, one float32 multiply each (numpy float32 arrays
+    multiply in float32) - what `w2l_s3fd_first_rect_scaled` does with `__fmul_rn` before its clip and truncation"""
+    return np.asarray(box, dtype=np.float32) * np.array([sx, sy, sx, sy], dtype=np.float32)
 
 
 BUF_LIMIT = 1 << 31      # bytes: the per-buffer rule of the bf16 kernels (32-bit byte offsets, W2L_REQUIRE in every launch)
@@ -355,17 +394,25 @@ class s3fd(nn.Module):
         outs[0] = torch.cat([torch.max(torch.max(chunk[0], chunk[1]), chunk[2]), chunk[3]], dim=1)
         return outs
 
-    def dense_boxes(self, images_bgr_u8, precision="f32"):
+    def dense_boxes(self, images_bgr_u8, precision="f32", det_scale=1):
         """images: torch uint8 [B,H,W,3] BGR on the device -> per level torch float32 [B, FH*FW, 5] (x1,y1,x2,y2,score):
         api.py:62 (BGR->RGB) + detect.py:57-84 for every position.  `precision`: "f32" (default) or "bf16" (the opt-in
-        bf16-storage graph; a batch whose buffers would reach 2 GiB raises RuntimeError before anything is allocated)"""
+        bf16-storage graph; a batch whose buffers would reach 2 GiB raises RuntimeError before anything is allocated).
+        `det_scale` k > 1: the graph of (H // k, W // k) on the frames resized as cv2.resize does (`dense_boxes_rows` over an
+        address table of the batch); the tables are in the reduced frame's coordinates."""
         from ..models.wav2lip import check_precision
         check_precision(precision)
+        det_scale = check_det_scale(det_scale)
         if images_bgr_u8.dtype != torch.uint8 or images_bgr_u8.dim() != 4 or images_bgr_u8.shape[3] != 3:
             raise RuntimeError("dense_boxes: images must be uint8 [B,H,W,3]")
+        if det_scale > 1:
+            det_size(*images_bgr_u8.shape[1:3], det_scale)            # ValueError before the device is touched
         engine.require_cuda(images_bgr_u8, "images")
         img = images_bgr_u8.contiguous()
         B, H, W = img.shape[:3]
+        if det_scale > 1:
+            frames = torch.arange(B, dtype=torch.int64, device=img.device) * (H * W * 3) + img.data_ptr()
+            return self.dense_boxes_rows(frames, B, H, W, precision, det_scale)
         g = self._graph(B, H, W, img.device, precision)
         if precision == "bf16":
             check(load().w2l_s3fd_pack_bf16(current_stream(), B * H * W, ptr(img), ptr(g.x_in), 8), "s3fd_pack_bf16")
@@ -374,22 +421,30 @@ class s3fd(nn.Module):
         g.run()
         return g.decode()
 
-
-    def dense_boxes_rows(self, frames, B, H, W, precision="f32"):
+    def dense_boxes_rows(self, frames, B, H, W, precision="f32", det_scale=1):
         """`dense_boxes` for B frames named by a device address table: `frames` is a device tensor holding B uint64 addresses, each
         of pixel (0,0) of a uint8 [H,W,3] BGR frame in device memory at any byte alignment (`w2l_s3fd_pack_rows`); the frames of a
         batch need not be neighbours, nor of one clip.  Same graph, same launches and the same tables as `dense_boxes` on the
-        gathered frames."""
+        gathered frames.  `det_scale` k > 1: the graph is the one of (B, H // k, W // k) and `w2l_s3fd_pack_rows_scaled` fills its
+        input from the full-size frames."""
         from ..models.wav2lip import check_precision
         check_precision(precision)
+        Hd, Wd = det_size(H, W, det_scale)
         engine.require_cuda(frames, "frame address table")
         if frames.numel() * frames.element_size() < 8 * B or frames.data_ptr() % 8:
             raise RuntimeError("dense_boxes_rows: the table must hold %d 8-byte aligned addresses" % B)
-        g = self._graph(B, H, W, frames.device, precision)
+        g = self._graph(B, Hd, Wd, frames.device, precision)
+        lib, s = load(), current_stream()
         if precision == "bf16":
-            check(load().w2l_s3fd_pack_rows_bf16(current_stream(), B, H, W, ptr(frames), ptr(g.x_in), 8), "s3fd_pack_rows_bf16")
+            if det_scale > 1:
+                check(lib.w2l_s3fd_pack_rows_scaled_bf16(s, B, H, W, Hd, Wd, ptr(frames), ptr(g.x_in), 8), "s3fd_pack_rows_scaled_bf16")
+            else:
+                check(lib.w2l_s3fd_pack_rows_bf16(s, B, H, W, ptr(frames), ptr(g.x_in), 8), "s3fd_pack_rows_bf16")
             return g.run()
-        check(load().w2l_s3fd_pack_rows(current_stream(), B, H, W, ptr(frames), ptr(g.x_in), 4), "s3fd_pack_rows")
+        if det_scale > 1:
+            check(lib.w2l_s3fd_pack_rows_scaled(s, B, H, W, Hd, Wd, ptr(frames), ptr(g.x_in), 4), "s3fd_pack_rows_scaled")
+        else:
+            check(lib.w2l_s3fd_pack_rows(s, B, H, W, ptr(frames), ptr(g.x_in), 4), "s3fd_pack_rows")
         g.run()
         return g.decode()
 
@@ -429,11 +484,12 @@ def nms_batch(table, gate, thresh, host_overflow=True):
 RECT_NONE, RECT_FOUND, RECT_HOST = 0, 1, 2       # w2l_s3fd_first_rect flags
 
 
-def first_rects(table, keep, counts, thresh):
+def first_rects(table, keep, counts, thresh, scale=None):
     """sfd_detector.py:45 + api.py:61-77 for a batch on the device (`w2l_s3fd_first_rect`): nms_batch's (keep, counts) over `table`
     -> numpy int32 [B, 5] in ONE device-to-host copy, per image (x1, y1, x2, y2, flag): the first kept row above `thresh`, clipped
     at 0 and truncated, with flag RECT_FOUND; RECT_NONE when no row passes; RECT_HOST when a coordinate is one the device does not
-    convert (NaN, +inf, >= 2^31) - the caller decides that image on the host."""
+    convert (NaN, +inf, >= 2^31) - the caller decides that image on the host.  `scale` = (sx, sy) (`det_rect_scale`): the row is
+    mapped back to the full frame first (`w2l_s3fd_first_rect_scaled`); None is the plain launch."""
     engine.require_cuda(table, "box table")
     if table.dtype != torch.float32 or table.dim() != 3 or table.shape[2] != 5:
         raise RuntimeError("first_rects: table must be float32 [B, P, 5]")
@@ -443,8 +499,13 @@ def first_rects(table, keep, counts, thresh):
         raise RuntimeError("first_rects: keep must be int32 [B, P] and counts int32 [B] (nms_batch's outputs)")
     keep, counts = keep.contiguous(), counts.contiguous()
     out = torch.empty((5 * B,), device=table.device, dtype=torch.int32)       # rects [B][4], then flags [B]: one copy back
-    check(load().w2l_s3fd_first_rect(current_stream(), B, P, ptr(table), ptr(keep), ptr(counts), float(thresh), ptr(out),
-                                     ptr(out[4 * B:])), "s3fd_first_rect")
+    if scale is None:
+        check(load().w2l_s3fd_first_rect(current_stream(), B, P, ptr(table), ptr(keep), ptr(counts), float(thresh), ptr(out),
+                                         ptr(out[4 * B:])), "s3fd_first_rect")
+    else:
+        check(load().w2l_s3fd_first_rect_scaled(current_stream(), B, P, ptr(table), ptr(keep), ptr(counts), float(thresh),
+                                                float(scale[0]), float(scale[1]), ptr(out), ptr(out[4 * B:])),
+              "s3fd_first_rect_scaled")
     h = out.cpu().numpy()
     return np.concatenate([h[:4 * B].reshape(B, 4), h[4 * B:].reshape(B, 1)], axis=1)
 

@@ -22,7 +22,8 @@ than mel chunks (:195) or a frame has no face (:200-203); every skip names its r
 for one full 16-column window is skipped too: the reference would fail there on an unbound `out` (:229), no batch having opened
 the writer.  Detection is `inference.face_detect` per clip: pads from `--pads`, smoothing always on with T = 5 (:74).
 
-Two flags the reference does not have, as in `inference.main`: `--precision` and `--face_det_precision`.  A third,
+Flags the reference does not have, as in `inference.main`: `--precision`, `--face_det_precision` and `--face_det_scale K` (the
+detector sees every frame at 1/K of its size; boxes are mapped back, written frames keep their size).  Another,
 `--packed_face_det` (off by default), runs detection through `face_detection.detect_many`: the frames of successive clips share
 detector batches of `--face_det_batch_size`, the per-clip finish runs once per group on the device, and lines, skip messages and
 written files stay what they are without it.  Under
@@ -65,10 +66,13 @@ def build_cli_parser():
 
 def build_main_parser():
     """what `main()` parses: `build_cli_parser` plus `--packed_face_det`, which changes how the work is scheduled and nothing of
-    what is computed (`cli_parser` stays the surface whose every flag changes arithmetic or is the reference's)"""
+    what is computed, and `--face_det_scale K`, the size of the frame the detector sees (`inference.add_det_scale_flag`).
+    `cli_parser` stays the reference's surface plus the two precision flags."""
+    from .inference import add_det_scale_flag
     p = build_cli_parser()
     p.add_argument('--packed_face_det', default=False, action='store_true',
                    help='Detect faces of successive clips in shared detector batches (face_detection.detect_many)')
+    add_det_scale_flag(p)
     return p
 
 
@@ -257,7 +261,8 @@ def main(argv=None, state_dict=None, backend="nccl"):
         print('Using {} for inference.'.format(ranks.device))
         detector = face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False, device=str(ranks.device),
                                                 state_dict=state_dict,
-                                                **inference._precision_kw(inference.CLI_PRECISION[args.face_det_precision]))
+                                                **inference._precision_kw(inference.CLI_PRECISION[args.face_det_precision]),
+                                                **inference._det_scale_kw(getattr(args, 'face_det_scale', 1)))
         model = inference.load_model(args.checkpoint_path, ranks.device)
         tracks = {}
         sink = ResultSink(args.results_dir, tracks)

@@ -64,10 +64,33 @@ def build_parser():
     return parser
 
 
+def det_scale_arg(text):
+    """argparse type of `--face_det_scale`: an integer in 1..8 (a parse error otherwise)"""
+    import argparse
+    try:
+        k = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is not an integer" % (text,))
+    if not 1 <= k <= 8:
+        raise argparse.ArgumentTypeError("%d is outside 1..8" % k)
+    return k
+
+
+DET_SCALE_HELP = ('Run the face detector on every frame at 1/K of its height and width (K = 1..8; default 1, as the reference). '
+                  'The detector then costs about 1/K^2 as much and its boxes are mapped back to the full frame, so output frames '
+                  'keep their size (unlike --resize_factor). Boxes move with K: this is not accuracy-neutral')
+
+
+def add_det_scale_flag(p):
+    """`--face_det_scale K` on a command's parser; independent of --resize_factor, --face_det_precision and --packed_face_det"""
+    p.add_argument('--face_det_scale', default=1, type=det_scale_arg, metavar='K', help=DET_SCALE_HELP)
+
+
 def build_cli_parser():
-    """the command line `main()` parses: the reference's flags (`build_parser`, whose surface stays the reference's) plus two
-    documented additions that are not among them, each fp32 by default and independent of the other:
-    `--precision {fp32,bf16}`, the generator's arithmetic, and `--face_det_precision {fp32,bf16}`, the S3FD detector's"""
+    """the command line `main()` parses: the reference's flags (`build_parser`, whose surface stays the reference's) plus three
+    documented additions that are not among them, each the reference's behaviour by default and independent of the others:
+    `--precision {fp32,bf16}`, the generator's arithmetic, `--face_det_precision {fp32,bf16}`, the S3FD detector's, and
+    `--face_det_scale K`, the detector's frame size (1/K; output frames keep theirs)"""
     p = build_parser()
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
                    help='Generator arithmetic: fp32 (default, matches the reference) or bf16 storage (faster; frames differ by '
@@ -75,6 +98,7 @@ def build_cli_parser():
     p.add_argument('--face_det_precision', default='fp32', choices=['fp32', 'bf16'],
                    help='Face detector arithmetic: fp32 (default, matches the reference) or bf16 storage (faster; boxes move by '
                         'about what bf16 rounding alone moves them)')
+    add_det_scale_flag(p)
     return p
 
 
@@ -522,26 +546,44 @@ def _detect_rects(images, detector, batch_size, ranks=None):
             print('Recovering from OOM error; New batch size: {}'.format(batch_size))
 
 
-def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None, ranks=None, precision=None):
+def _det_scale_kw(det_scale):
+    """detector keyword for a reduced detection frame: scale 1 builds the detector with the same arguments as before the option"""
+    return {} if det_scale == 1 else {"det_scale": det_scale}
+
+
+def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None, ranks=None, precision=None, det_scale=None):
     """inference.py:68-104: S3FD boxes per frame (HIP detector), padding, temporal smoothing; returns
     [[face crop, (y1, y2, x1, x2)], ...].  Called as the reference calls it - `face_detect(images)` - pads / nosmooth /
     face_det_batch_size come from the module-level `args` and the detector is built as inference.py:69-70 does
     (`face_detection.FaceAlignment(LandmarksType._2D, flip_input=False, device=device)`, weights `face_detection/s3fd.pth`);
     a ready `wav2lip_amd.face_detection.FaceAlignment` may be passed instead.  `precision` ("f32" or "bf16") selects the
     detector's arithmetic; None means: a passed detector keeps its own, a built one takes the module-level
-    `args.face_det_precision` (fp32 when absent)."""
+    `args.face_det_precision` (fp32 when absent).  `det_scale` (1..8) is the detector's frame size, 1/det_scale of the frames'
+    (the boxes come back in full-frame coordinates; pads, clipping and smoothing below are on those); None follows the same rule
+    with `args.face_det_scale` (1 when absent)."""
+    from .face_detection.s3fd import check_det_scale
     from .models.wav2lip import check_precision
     if precision is not None:
         check_precision(precision)
+    if det_scale is not None:
+        det_scale = check_det_scale(det_scale)
     if detector is None:
         from . import face_detection
         if precision is None:
             precision = check_precision(CLI_PRECISION[getattr(args, "face_det_precision", "fp32")])
+        if det_scale is None:
+            det_scale = check_det_scale(getattr(args, "face_det_scale", 1))
         detector = face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False, device=device,
-                                                **_precision_kw(precision))
-    elif precision is not None and precision != getattr(detector, "precision", "f32"):
-        detector = copy.copy(detector)          # same network and graph cache, the other arithmetic
-        detector.precision = precision
+                                                **_precision_kw(precision), **_det_scale_kw(det_scale))
+    else:
+        other_precision = precision is not None and precision != getattr(detector, "precision", "f32")
+        other_scale = det_scale is not None and det_scale != getattr(detector, "det_scale", 1)
+        if other_precision or other_scale:
+            detector = copy.copy(detector)          # same network and graph cache, the other arithmetic / frame size
+            if other_precision:
+                detector.precision = precision
+            if other_scale:
+                detector.det_scale = det_scale
     pads = args.pads if pads is None else pads
     nosmooth = args.nosmooth if nosmooth is None else nosmooth
     batch_size = args.face_det_batch_size if batch_size is None else batch_size
@@ -617,9 +659,10 @@ def main(argv=None, keep_frames=True, backend="nccl"):
     """inference.py:181-277 on the HIP path.  Same flags, same steps, same messages; differences, all on the file-format
     side: video input is the uncompressed AVI of wav2lip_amd/container.py (no codecs here), `--audio` must be a WAV (the
     reference shells out to ffmpeg for anything else), and the result - the reference's `temp/result.avi` + ffmpeg mux - is
-    written as ONE AVI (BGR video + the driving audio as PCM16) at `--outfile`.  Two flags the reference does not have, both
-    fp32 by default and independent: `--precision {fp32,bf16}` selects the generator's arithmetic, `--face_det_precision
-    {fp32,bf16}` the S3FD face detector's (every rank of a sharded run detects its shard with it).
+    written as ONE AVI (BGR video + the driving audio as PCM16) at `--outfile`.  Three flags the reference does not have, each
+    the reference's behaviour by default and independent: `--precision {fp32,bf16}` selects the generator's arithmetic,
+    `--face_det_precision {fp32,bf16}` the S3FD face detector's and `--face_det_scale K` the size of the frame it sees (1/K;
+    the output keeps the input's size) - every rank of a sharded run detects its shard with both.
 
     Like the reference's loop (inference.py:249-274) this one STREAMS: every batch uploads only the frames it pastes into
     (deduplicated, `frame_idx` remapped) and its output frames go to the AVI writer as soon as they are back, so device and host
@@ -653,7 +696,7 @@ def main(argv=None, keep_frames=True, backend="nccl"):
         full_frames = full_frames[:len(starts)]
         if args.box[0] == -1:
             det = face_detect(full_frames if not args.static else [full_frames[0]], ranks=ranks,
-                              precision=CLI_PRECISION[args.face_det_precision])
+                              precision=CLI_PRECISION[args.face_det_precision], det_scale=args.face_det_scale)
             coords = [c for _, c in det]
         else:
             say('Using the specified bounding box instead of face detection...')

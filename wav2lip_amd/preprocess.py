@@ -49,22 +49,35 @@ def build_parser():
     return parser
 
 
+def build_main_parser():
+    """what the command line parses: `build_parser` plus `--face_det_scale K` (`inference.add_det_scale_flag`): the detector sees
+    every frame at 1/K of its size, the crops are cut from the full-resolution frame at the rects mapped back"""
+    from .inference import add_det_scale_flag
+    p = build_parser()
+    add_det_scale_flag(p)
+    return p
+
+
 parser = build_parser()
+main_parser = build_main_parser()
 
 # preprocess.py:30-31 builds one FaceAlignment per GPU at import time; here a detector is built on first use, per device index
 fa = {}
 
 
 def get_detector(gpu_id, args, state_dict=None):
-    """the FaceAlignment of cuda:<gpu_id> at `args.face_det_precision`; `state_dict` (S3FD weights) replaces the default
-    face_detection/s3fd.pth when the detector is first built"""
+    """the FaceAlignment of cuda:<gpu_id> at `args.face_det_precision` and `args.face_det_scale` (its rects are full-frame
+    coordinates at any scale, so the crops are cut from the full-resolution frame); `state_dict` (S3FD weights) replaces the
+    default face_detection/s3fd.pth when the detector is first built"""
     from . import face_detection
-    from .inference import CLI_PRECISION
+    from .inference import CLI_PRECISION, _det_scale_kw
     precision = CLI_PRECISION[getattr(args, "face_det_precision", "fp32")]
-    key = (gpu_id, precision)
+    det_scale = getattr(args, "face_det_scale", 1)
+    key = (gpu_id, precision) if det_scale == 1 else (gpu_id, precision, det_scale)
     if key not in fa or state_dict is not None:
         fa[key] = face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False,
-                                               device='cuda:{}'.format(gpu_id), state_dict=state_dict, precision=precision)
+                                               device='cuda:{}'.format(gpu_id), state_dict=state_dict, precision=precision,
+                                               **_det_scale_kw(det_scale))
     return fa[key]
 
 
@@ -180,7 +193,7 @@ def list_videos(data_root):
 
 
 def main(args, state_dict=None, backend="nccl"):
-    """preprocess.py:80-102.  `args` as `parser.parse_args()` returns it; `state_dict` (S3FD weights) replaces
+    """preprocess.py:80-102.  `args` as `main_parser.parse_args()` (or `parser.parse_args()`) returns it; `state_dict` (S3FD weights) replaces
     face_detection/s3fd.pth; `backend` is the process group's (the tests run two ranks on one device over "gloo")."""
     from . import sharding
     check_world(args.ngpu, int(os.environ.get("WORLD_SIZE", "1")))
@@ -214,4 +227,4 @@ def main(args, state_dict=None, backend="nccl"):
 
 
 if __name__ == '__main__':
-    main(parser.parse_args())
+    main(main_parser.parse_args())

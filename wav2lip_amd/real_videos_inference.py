@@ -27,7 +27,7 @@ the clips in flight.  Skipped lines leave gaps in the numbering, as in the refer
 Differences from the reference, all deliberate:
   * `--face_res`, `--min_frame_res` and `--max_frame_res` are declared `type=int`.  The reference declares no type, so a value
     given on its command line arrives as a string and fails at the first subtraction (:61, :64, :239); its defaults are ints.
-  * `--precision` and `--face_det_precision` are added, as in the sibling commands.
+  * `--precision`, `--face_det_precision` and `--face_det_scale` are added, as in the sibling commands.
   * `dubbed` mode lists `data_root` SORTED and pairs every file with itself; the reference's `listdir` order (:203) is the
     filesystem's, so its numbering is not reproducible from one machine to the next.
   * file formats are those of gen_videos_from_filelist: a name is `<data_root>/<name>` when that file exists, else
@@ -83,8 +83,18 @@ def build_cli_parser():
     return p
 
 
+def build_main_parser():
+    """what `main()` parses: `build_cli_parser` plus `--face_det_scale K`, the size of the frame the detector sees
+    (`inference.add_det_scale_flag`); `cli_parser` stays the reference's surface plus the two precision flags"""
+    from .inference import add_det_scale_flag
+    p = build_cli_parser()
+    add_det_scale_flag(p)
+    return p
+
+
 parser = build_parser()
 cli_parser = build_cli_parser()
+main_parser = build_main_parser()
 MODES = ('random', 'dubbed', 'tts')
 
 
@@ -345,7 +355,7 @@ def main(argv=None, state_dict=None, backend="nccl", report=None):
     """real_videos_inference.py:199-301.  `state_dict` (S3FD weights) replaces face_detection/s3fd.pth; `backend` is the process
     group's.  Returns the line indices this rank wrote, in order."""
     from . import face_detection, inference, sharding
-    args = cli_parser.parse_args(argv)
+    args = main_parser.parse_args(argv)
     if args.mode not in MODES:
         raise ValueError("--mode must be one of random | dubbed | tts")
     args.img_size = 96
@@ -357,7 +367,8 @@ def main(argv=None, state_dict=None, backend="nccl", report=None):
         print('Using {} for inference.'.format(ranks.device))
         detector = face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False, device=str(ranks.device),
                                                 state_dict=state_dict,
-                                                **inference._precision_kw(inference.CLI_PRECISION[args.face_det_precision]))
+                                                **inference._precision_kw(inference.CLI_PRECISION[args.face_det_precision]),
+                                                **inference._det_scale_kw(getattr(args, 'face_det_scale', 1)))
         model = inference.load_model(args.checkpoint_path, ranks.device)
         return run(args, lines, ranks, detector, model, report)
     finally:

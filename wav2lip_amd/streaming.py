@@ -423,6 +423,8 @@ def build_parser():
     p.add_argument('--nosmooth', default=False, action='store_true', help='Prevent smoothing face detections over a short temporal window')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='Generator arithmetic')
     p.add_argument('--face_det_precision', default='fp32', choices=['fp32', 'bf16'], help='Face detector arithmetic')
+    from .inference import add_det_scale_flag
+    add_det_scale_flag(p)
     return p
 
 
@@ -449,7 +451,8 @@ def main(argv=None):
             raise ValueError("--audio %s: pass a .wav" % wav_path)
         if a.box[0] == -1:
             det = inference.face_detect(frames if not one.static else [frames[0]], pads=a.pads, nosmooth=a.nosmooth,
-                                        batch_size=a.face_det_batch_size, precision=inference.CLI_PRECISION[a.face_det_precision])
+                                        batch_size=a.face_det_batch_size, precision=inference.CLI_PRECISION[a.face_det_precision],
+                                        det_scale=a.face_det_scale)
             boxes = [c for _, c in det]
         else:
             boxes = [tuple(a.box)] * len(frames)
