@@ -34,6 +34,7 @@
  *   w2l_s3fd_first_rect_scaled  face_detection/api.py:61-77 with the rect mapped back to the full frame first
  *   w2l_face_boxes_segments  evaluation/gen_videos_from_filelist.py:35-42, :61-77 = inference.py:59-66, :90-104 (pads, clipping,
  *                         "Face not detected", get_smoothened_boxes) for every clip of a group in one launch
+ *   w2l_face_boxes_stream  inference.py:59-66, :90-104 for live streams: the same boxes, written tick by tick as frames arrive
  *   w2l_melspectrogram    audio.py:45-51 (preemphasis, STFT, mel basis, dB, normalise)
  *   w2l_mel_gather        inference.py:231-240 (16-frame mel windows at host-computed starts)
  *   w2l_resample_sinc     audio.py:9-10 (librosa.core.load's sample-rate conversion: resampy 'kaiser_best' sinc interpolation)
@@ -323,6 +324,38 @@ typedef struct {
 } w2l_box_segment;
 int w2l_face_boxes_segments(void* stream, int n_seg, const w2l_box_segment* segs, const int32_t* rects, const int32_t* flags,
                             int top, int bottom, int left, int right, int T, int32_t* boxes, int32_t* status);
+
+/* The same finish (inference.py:59-66, :90-104) for many LIVE streams, one launch per tick: frames arrive a few at a time and a
+ * box leaves as soon as it is final.  get_smoothened_boxes looks forward - box i <= n - T is the mean of the unsmoothed rows
+ * i .. i + T - 1 - so it is final once T - 1 more frames are there; only the last T - 1 boxes of a video depend on its end.  A
+ * stream carries its last max(T, 1) RAW rects (x1, y1, x2, y2) from tick to tick in a slot of carry [n_slots][64][4] int32.
+ *
+ * w2l_box_stream_segment, 32 bytes, the table 16-byte aligned: one stream that takes part in the tick
+ *   bytes 0..7    int32 row0, n_new   its new rows [row0, row0 + n_new) of the rect / flag arenas (n_new = 0: an empty tick)
+ *   bytes 8..15   int32 H, W          its frame size
+ *   bytes 16..23  int32 slot, seen    its carry slot; frames of this stream finished before this tick
+ *   bytes 24..31  int32 closed, out0  1: the video ended with this tick; first row of the segment in boxes
+ *
+ * With n = seen + n_new the rows held are [the slot's first min(seen, max(T, 1)) rows][the new rows].  While open the segment
+ * writes the boxes of frames [max(0, seen - T + 1), max(0, n - T + 1)) by the forward rule (T = 0: the new frames unsmoothed;
+ * T = 1: each frame's own truncated mean).  With closed it writes every remaining frame - [max(0, seen - T + 1), n) - by
+ * w2l_face_boxes_segments' rule on the WHOLE length n: the forward rule below n - T, then in order over the window
+ * boxes[n - T:] (n < T: from max(0, 2n - T)), whose entry n - T is computed again from raw rows.  So the boxes of a stream,
+ * tick after tick, are w2l_face_boxes_segments' of the finished video however it was cut.  Then the last min(n, max(T, 1)) raw
+ * rects go back into the slot.  boxes rows [out0, out0 + count) = (y1, y2, x1, x2), count as above.
+ * status [n_seg][2] = (code, absolute frame index): 2 when a NEW row is flagged neither found nor none (the first such row; it
+ * wins over an earlier "none"), else 1 when a new row is flagged 0 (no face; the first), else (0, 0).  For a non-zero code no
+ * box of the segment is written and its slot is left as it was.  A segment touches its own arena rows, output rows and slot only.
+ * segs_host is the same table in host memory (the staging copy): it is checked before anything is launched - n_new, seen not
+ * negative, seen + n_new < 2^31, slot in [0, n_slots) and named once, rows inside n_rows, output rows inside n_out and disjoint -
+ * and refused with w2l_last_error set.  The kernel reads segs (device) and does not follow a segment that fails those bounds:
+ * status (3, 0), nothing else written.  Also refused: a NULL pointer, n_seg < 1, T outside 0..64, a misaligned table. */
+typedef struct {
+    int32_t row0, n_new, H, W, slot, seen, closed, out0;
+} w2l_box_stream_segment;
+int w2l_face_boxes_stream(void* stream, int n_seg, const w2l_box_stream_segment* segs_host, const w2l_box_stream_segment* segs,
+                          const int32_t* rects, const int32_t* flags, int n_rows, int32_t* carry, int n_slots, int top, int bottom,
+                          int left, int right, int T, int32_t* boxes, int n_out, int32_t* status);
 
 /* The opt-in bf16-storage detector (face_detection/s3fd.py, precision="bf16"): the backbone convolutions are w2l_convb layers
  * (scale 1, shift = bias, ReLU); these are the ops between them and the fused detection head.  Tensors are NHWC bf16 with channel

@@ -18,7 +18,19 @@ stream per tick once the first window is there).  Two loops over the same seeded
 (b) paced: tick k is fed at k * 40 ms (a loop that cannot keep up falls behind and its latency grows); per row the time from the
     `feed` that completed it to the delivery of its frame; p50 / p99 over all rows.  While it waits for the next tick the shared
     loop polls `step()` (nothing new to compute: it only delivers what has finished).
-Pass 0 of each loop is its warm-up (plans built) and is not reported.  Then the loops alternate.  Prints one JSON line."""
+Pass 0 of each loop is its warm-up (plans built) and is not reported.  Then the loops alternate.  Prints one JSON line.
+
+    python tools/stream_bench.py --live_video [--streams 8] [--ticks 100] [--alternations 5]
+
+compares, on S copies of a seeded 160x160 video whose faces the seeded S3FD finds (one frame and 40 ms of audio per tick):
+
+  upfront  what `python -m wav2lip_amd.streaming` does without `--live_video`: `inference.face_detect` over every frame of every
+           video, one clip after another, then the streams opened with frames and boxes and fed tick by tick
+  live     `open_live`: per tick `feed` + `feed_frames` of every stream and one `step(flush=True)`; detection runs as frames arrive
+
+frames/s over the whole pass (detection included on both sides), and per row the number of ticks between the tick whose audio
+completed it and the tick in which its frame was delivered: the lag live detection adds is T - 1 frames plus one tick by
+construction, and this is what is measured of it."""
 import argparse
 import json
 import os
@@ -129,6 +141,98 @@ def run_per_stream(G, wavs, frames, ticks, batch, dev, pace):
     return clock, time.perf_counter() - t_start
 
 
+def live_clip(ticks):
+    frames = synth.filelist_clips()["c3"][0]                  # 160x160, a face in every frame
+    return np.stack([frames[k % len(frames)] for k in range(ticks)])
+
+
+class TickClock:
+    """per row: ticks between the tick that completed its audio and the tick of its delivery"""
+
+    def __init__(self, ticks):
+        self.ready, self.count, self.lag, self.tick = ready_ticks(ticks), {}, [], 0
+
+    def sink(self, key, frame):
+        if frame is not None:
+            i = self.count.get(key, 0)
+            self.count[key] = i + 1
+            self.lag.append(self.tick - self.ready[i])
+
+
+def run_upfront(G, det, video, wavs, ticks, batch):
+    clock = TickClock(ticks)
+    t_start = time.perf_counter()
+    boxes = [[c for _, c in inference.face_detect(list(video), detector=det, pads=[0, 10, 0, 0], nosmooth=False, batch_size=16)]
+             for _ in wavs]
+    ls = streaming.LipsyncStreams(G, batch_size=batch, sink=clock.sink)
+    for k in range(len(wavs)):
+        ls.open(k, list(video), boxes[k])
+    for t in range(ticks):
+        clock.tick = t
+        for k, w in enumerate(wavs):
+            ls.feed(k, w[t * TICK:(t + 1) * TICK])
+            if t == ticks - 1:
+                ls.close(k)
+        ls.step(flush=True)
+    clock.tick = ticks
+    ls.drain()
+    torch.cuda.synchronize()
+    return clock, time.perf_counter() - t_start
+
+
+def run_live(G, det, video, wavs, ticks, batch):
+    clock = TickClock(ticks)
+    t_start = time.perf_counter()
+    ls = streaming.LipsyncStreams(G, batch_size=batch, sink=clock.sink, detector=det, pads=(0, 10, 0, 0), smooth_T=5,
+                                  face_det_batch_size=16)
+    for k in range(len(wavs)):
+        ls.open_live(k)
+    for t in range(ticks):
+        clock.tick = t
+        for k, w in enumerate(wavs):
+            ls.feed(k, w[t * TICK:(t + 1) * TICK])
+            ls.feed_frames(k, [video[t]])
+            if t == ticks - 1:
+                ls.close_video(k)
+                ls.close(k)
+        ls.step(flush=True)
+    clock.tick = ticks
+    ls.drain()
+    torch.cuda.synchronize()
+    if ls.errors:
+        raise SystemExit("live detection ended streams: %s" % ls.errors)
+    return clock, time.perf_counter() - t_start
+
+
+def bench_live(S, ticks, a, dev):
+    from wav2lip_amd import face_detection
+    det = face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False, device=str(dev),
+                                       state_dict=synth.s3fd_state_dict())
+    video = live_clip(ticks)
+    wavs = [synth.noise_wav(ticks * TICK, seed=a.seed * 100003 + k) for k in range(S)]
+    loops = {"upfront": (run_upfront, model(dev)), "live": (run_live, model(dev))}
+    res = {k: {"fps": [], "lag_ticks_median": [], "lag_ticks_max": []} for k in loops}
+    for name, (fn, G) in loops.items():                   # pass 0: warm-up, plans and detector graphs built
+        clock, t = fn(G, det, video, wavs, ticks, a.batch)
+        res[name].update(frames=len(clock.lag), first_pass_s=round(t, 2))
+    for _ in range(a.alternations):
+        for name, (fn, G) in loops.items():
+            clock, t = fn(G, det, video, wavs, ticks, a.batch)
+            res[name]["fps"].append(len(clock.lag) / t)
+            res[name]["lag_ticks_median"].append(float(np.median(clock.lag)))
+            res[name]["lag_ticks_max"].append(float(max(clock.lag)))
+    for name in loops:
+        for key in ("fps", "lag_ticks_median", "lag_ticks_max"):
+            res[name][key] = stats(res[name][key])
+    out = {"mode": "live_video", "streams": S, "ticks": ticks, "batch": a.batch, "alternations": a.alternations}
+    out.update(res)
+    out["live_over_upfront_median"] = round(res["live"]["fps"]["median"] / res["upfront"]["fps"]["median"], 3)
+    out["apart_by_more_than_the_spread"] = bool(res["live"]["fps"]["min"] > res["upfront"]["fps"]["max"]
+                                                or res["live"]["fps"]["max"] < res["upfront"]["fps"]["min"])
+    out["added_lag_ticks_median"] = round(res["live"]["lag_ticks_median"]["median"] - res["upfront"]["lag_ticks_median"]["median"], 1)
+    return out
+
+
 def stats(v, nd=1):
     return {"samples": [round(x, nd) for x in v], "median": round(float(np.median(v)), nd), "min": round(min(v), nd), "max": round(max(v), nd)}
 
@@ -186,8 +290,13 @@ def main(argv=None):
     ap.add_argument("--paced_alternations", type=int, default=5)
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--live_video", action="store_true", help="live face detection against detection up front (see the module text)")
     a = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
+    if a.live_video:
+        for S, t in zip(a.streams, per_count(a.ticks, len(a.streams), "ticks")):
+            print(json.dumps(bench_live(S, t, a, dev)), flush=True)
+        return
     ticks = per_count(a.ticks, len(a.streams), "ticks")
     paced = per_count(a.paced_ticks, len(a.streams), "paced_ticks")
     for S, t, pt in zip(a.streams, ticks, paced):

@@ -67,6 +67,11 @@ class BoxSegment(C.Structure):
     _fields_ = [("row0", C.c_int32), ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
 
 
+class BoxStreamSegment(C.Structure):
+    """w2l_box_stream_segment: one live stream's rows of a tick of w2l_face_boxes_stream, 32 bytes"""
+    _fields_ = [(n, C.c_int32) for n in ("row0", "n_new", "H", "W", "slot", "seen", "closed", "out0")]
+
+
 class MelStream(C.Structure):
     """w2l_mel_stream: one stream of w2l_mel_stream_cols, 48 bytes"""
     _fields_ = [("samples", C.c_uint64), ("first", C.c_int64), ("total", C.c_int64), ("window", C.c_uint64), ("held", C.c_int32),
@@ -121,6 +126,7 @@ SIGNATURES = {
     "w2l_s3fd_first_rect": (_i, [_vp, _i, _i, _vp, _vp, _vp, _f, _vp, _vp]),
     "w2l_s3fd_first_rect_scaled": (_i, [_vp, _i, _i, _vp, _vp, _vp, _f, _f, _f, _vp, _vp]),
     "w2l_face_boxes_segments": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "w2l_face_boxes_stream": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "w2l_s3fd_pack_bf16": (_i, [_vp, _ll, _vp, _vp, _i]),
     "w2l_s3fd_pack_rows_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp, _i]),
     "w2l_s3fd_pack_rows_scaled_bf16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i]),

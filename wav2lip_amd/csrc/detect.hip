@@ -12,6 +12,7 @@
 //   w2l_s3fd_first_rect_scaled  the same with the box mapped back to the full frame (x * sx, y * sy) before the clip and int()
 //   w2l_face_boxes_segments  inference.py:59-66, :90-104 / gen_videos_from_filelist.py:35-42, :61-77  pads, clipping, temporal
 //                       smoothing and "no face" of many clips in one launch
+//   w2l_face_boxes_stream  the same finish for LIVE streams, tick by tick: a box is written once the T - 1 frames after it are there
 // All HBM-bound, NHWC, float4 where the channel count allows.
 #include "w2l_common.h"
 #include "resize_px.h"
@@ -375,7 +376,8 @@ constexpr int kBoxMaxT = 64;
 struct BoxSeg { int row0, n, H, W; };
 static_assert(sizeof(BoxSeg) == 16 && sizeof(w2l_box_segment) == 16, "w2l_box_segment is 16 bytes");
 
-__device__ __forceinline__ int padded_coord(const int* r, int c, const BoxSeg& s, int top, int bottom, int left, int right) {
+template <class Seg>      // BoxSeg or BoxStreamSeg: anything with the frame size H, W
+__device__ __forceinline__ int padded_coord(const int* r, int c, const Seg& s, int top, int bottom, int left, int right) {
     long long v;
     if (c == 0) v = max(0ll, (long long)r[1] - top);
     else if (c == 1) v = min((long long)s.H, (long long)r[3] + bottom);
@@ -449,6 +451,126 @@ __global__ __launch_bounds__(64) void face_boxes_segments_kernel(const BoxSeg* _
             if (i >= ws) s_win[i - ws][c] = m;
             bx[(long long)i * 4 + c] = m;
         }
+    }
+}
+
+// ---- the same finish for LIVE streams, one launch per tick (inference.py:59-66, :90-104): one wave per segment = the rows one
+// stream added to the arenas in this tick.  get_smoothened_boxes looks FORWARD: box i <= n - T is the mean of the unsmoothed
+// rows i .. i + T - 1, so it is final once row i + T - 1 is there, whatever follows; only the rows after n - T depend on the end
+// (the in-place boxes[n - T:] window).  The stream therefore carries its last max(T, 1) RAW rects from tick to tick (a slot of
+// `carry`), and the rows this launch holds are  [carry: min(seen, max(T, 1)) rows][the new rows]  = frames [base, n), n = seen +
+// n_new.  While open it writes frames [max(0, seen - T + 1), max(0, n - T + 1)) by the forward rule; with `closed` every
+// remaining frame by face_boxes_segments_kernel's tail on the whole length n - its entry n - T, already smoothed there, is the
+// forward mean of raw rows and is computed again.  The slot is read into LDS before anything is written to it.
+struct BoxStreamSeg { int row0, n_new, H, W, slot, seen, closed, out0; };
+static_assert(sizeof(BoxStreamSeg) == 32 && sizeof(w2l_box_stream_segment) == 32, "w2l_box_stream_segment is 32 bytes");
+constexpr int kBoxStreamBadSegment = 3;
+
+// frames [lo, hi) are what a tick writes for a segment (host and device: the same expression)
+__host__ __device__ inline void box_stream_range(long long seen, long long n, int closed, int T, long long* lo, long long* hi) {
+    if (T == 0) { *lo = seen; *hi = n; return; }
+    *lo = seen - T + 1 > 0 ? seen - T + 1 : 0;
+    *hi = closed ? n : (n - T + 1 > 0 ? n - T + 1 : 0);
+}
+
+__global__ __launch_bounds__(64) void face_boxes_stream_kernel(const BoxStreamSeg* __restrict__ segs, const int* __restrict__ rects,
+                                                               const int* __restrict__ flags, int n_rows, int* __restrict__ carry,
+                                                               int n_slots, int top, int bottom, int left, int right, int T,
+                                                               int* __restrict__ boxes, int n_out, int* __restrict__ status) {
+    __shared__ int s_carry[kBoxMaxT][4];
+    __shared__ int s_win[kBoxMaxT][4];
+    const int lane = threadIdx.x;
+    const BoxStreamSeg s = segs[blockIdx.x];
+    int* st = status + 2 * (long long)blockIdx.x;
+    // the launcher checked the host copy of the table; a device copy that says otherwise is not followed
+    const long long n_ll = (long long)s.seen + s.n_new;
+    bool bad = s.n_new < 0 || s.seen < 0 || s.slot < 0 || s.slot >= n_slots || s.row0 < 0 || (long long)s.row0 + s.n_new > n_rows ||
+               n_ll > 0x7fffffffll || s.out0 < 0;
+    long long lo_ll = 0, hi_ll = 0;
+    if (!bad) {
+        box_stream_range(s.seen, n_ll, s.closed, T, &lo_ll, &hi_ll);
+        bad = s.out0 + (hi_ll - lo_ll) > n_out;
+    }
+    if (bad) {                                           // uniform
+        if (lane == 0) { st[0] = kBoxStreamBadSegment; st[1] = 0; }
+        return;
+    }
+    const int n = (int)n_ll, lo = (int)lo_ll, n_new = s.n_new;
+    const int* fl = flags + s.row0;
+    const int* rc = rects + (long long)s.row0 * 4;
+    int* bx = boxes + (long long)s.out0 * 4;
+    int first_host = 0x7fffffff, first_none = 0x7fffffff;
+    for (int i = lane; i < n_new; i += 64) {
+        const int f = fl[i];
+        if (f == kRectNone) first_none = min(first_none, i);
+        else if (f != kRectFound) first_host = min(first_host, i);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        first_host = min(first_host, __shfl_xor(first_host, o));
+        first_none = min(first_none, __shfl_xor(first_none, o));
+    }
+    if (first_host != 0x7fffffff || first_none != 0x7fffffff) {      // uniform: no box written, the carry left as it was
+        if (lane == 0) {
+            st[0] = first_host != 0x7fffffff ? 2 : 1;
+            st[1] = s.seen + (first_host != 0x7fffffff ? first_host : first_none);
+        }
+        return;
+    }
+    if (lane == 0) { st[0] = 0; st[1] = 0; }
+    const int Tm = max(T, 1);
+    const int c = min(s.seen, Tm);                       // carried rows; held row h is frame base + h
+    const int base = s.seen - c, m = c + n_new;
+    int* slot = carry + (long long)s.slot * (kBoxMaxT * 4);
+    if (lane < c) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s_carry[lane][k] = slot[lane * 4 + k];
+    }
+    __syncthreads();
+    auto raw = [&](int h) -> const int* { return h < c ? &s_carry[h][0] : rc + (long long)(h - c) * 4; };
+    // the next tick's carry: the last min(n, max(T, 1)) raw rows, taken now, stored last
+    const int keep = min(n, Tm);
+    int kv[4] = {0, 0, 0, 0};
+    if (lane < keep) {
+        const int* r = raw(m - keep + lane);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) kv[k] = r[k];
+    }
+    if (T == 0) {
+        for (int i = lane; i < 4 * n_new; i += 64) bx[i] = padded_coord(rc + (i >> 2) * 4, i & 3, s, top, bottom, left, right);
+    } else {
+        const int fwd_hi = s.closed ? (n >= T ? n - T : 0) : (int)hi_ll;
+        for (int i = lo + lane; i < fwd_hi; i += 64) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                long long sum = 0;
+                for (int j = 0; j < T; ++j) sum += padded_coord(raw(i - base + j), k, s, top, bottom, left, right);
+                bx[(long long)(i - lo) * 4 + k] = trunc_mean(sum, T);
+            }
+        }
+        if (s.closed && n > 0) {                             // uniform
+            const int ws = n >= T ? n - T : max(0, 2 * n - T);   // first row of Python's boxes[n - T:]; ws >= base
+            const int L = n - ws;                                // 1 <= L <= T <= kBoxMaxT
+            const int seq0 = n >= T ? n - T : 0;
+            if (lane < L) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) s_win[lane][k] = padded_coord(raw(ws - base + lane), k, s, top, bottom, left, right);
+            }
+            __syncthreads();
+            if (lane < 4) {
+                const int k = lane;
+                for (int i = seq0; i < n; ++i) {
+                    long long sum = 0;
+                    for (int j = 0; j < L; ++j) sum += s_win[j][k];
+                    const int mean = trunc_mean(sum, L);
+                    if (i >= ws) s_win[i - ws][k] = mean;
+                    if (i >= lo) bx[(long long)(i - lo) * 4 + k] = mean;     // entry n - T may have gone out in an earlier tick
+                }
+            }
+        }
+    }
+    if (lane < keep) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) slot[lane * 4 + k] = kv[k];
     }
 }
 
@@ -599,6 +721,43 @@ int w2l_face_boxes_segments(void* stream, int n_seg, const w2l_box_segment* segs
     W2L_REQUIRE((reinterpret_cast<uintptr_t>(segs) & 15) == 0, "face_boxes_segments: the segment table must be 16-byte aligned");
     hipLaunchKernelGGL(face_boxes_segments_kernel, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const BoxSeg*>(segs), rects, flags, top, bottom, left, right, T, boxes, status);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_face_boxes_stream(void* stream, int n_seg, const w2l_box_stream_segment* segs_host, const w2l_box_stream_segment* segs,
+                          const int32_t* rects, const int32_t* flags, int n_rows, int32_t* carry, int n_slots, int top, int bottom,
+                          int left, int right, int T, int32_t* boxes, int n_out, int32_t* status) {
+    W2L_REQUIRE(segs_host && segs && rects && flags && carry && boxes && status, "face_boxes_stream: NULL argument");
+    W2L_REQUIRE(n_seg >= 1, "face_boxes_stream: n_seg=%d must be at least 1", n_seg);
+    W2L_REQUIRE(T >= 0 && T <= kBoxMaxT, "face_boxes_stream: T=%d outside 0..%d", T, kBoxMaxT);
+    W2L_REQUIRE(n_rows >= 0 && n_slots >= 1 && n_out >= 0, "face_boxes_stream: n_rows=%d, n_slots=%d, n_out=%d", n_rows, n_slots, n_out);
+    W2L_REQUIRE((reinterpret_cast<uintptr_t>(segs) & 15) == 0, "face_boxes_stream: the segment table must be 16-byte aligned");
+    // a tick has a segment per live stream: the pairwise checks below are a few thousand comparisons, and allocate nothing
+    for (int k = 0; k < n_seg; ++k) {
+        const w2l_box_stream_segment& s = segs_host[k];
+        W2L_REQUIRE(s.n_new >= 0 && s.seen >= 0, "face_boxes_stream: segment %d: n_new=%d and seen=%d must not be negative", k,
+                    s.n_new, s.seen);
+        W2L_REQUIRE((long long)s.seen + s.n_new <= 0x7fffffffll, "face_boxes_stream: segment %d: more than 2^31 - 1 frames", k);
+        W2L_REQUIRE(s.slot >= 0 && s.slot < n_slots, "face_boxes_stream: segment %d: slot %d outside [0, %d)", k, s.slot, n_slots);
+        W2L_REQUIRE(s.row0 >= 0 && (long long)s.row0 + s.n_new <= n_rows, "face_boxes_stream: segment %d: rows [%d, %d + %d) outside the %d arena rows",
+                    k, s.row0, s.row0, s.n_new, n_rows);
+        long long lo, hi;
+        box_stream_range(s.seen, (long long)s.seen + s.n_new, s.closed, T, &lo, &hi);
+        W2L_REQUIRE(s.out0 >= 0 && s.out0 + (hi - lo) <= n_out, "face_boxes_stream: segment %d: output rows [%d, %d + %lld) outside the %d rows",
+                    k, s.out0, s.out0, hi - lo, n_out);
+        for (int j = 0; j < k; ++j) {
+            const w2l_box_stream_segment& o = segs_host[j];      // checked above: its counts are in range
+            W2L_REQUIRE(o.slot != s.slot, "face_boxes_stream: segments %d and %d name carry slot %d", j, k, s.slot);
+            long long olo, ohi;
+            box_stream_range(o.seen, (long long)o.seen + o.n_new, o.closed, T, &olo, &ohi);
+            W2L_REQUIRE(hi == lo || ohi == olo || s.out0 + (hi - lo) <= o.out0 || o.out0 + (ohi - olo) <= s.out0,
+                        "face_boxes_stream: the output rows of segments %d and %d overlap", j, k);
+        }
+    }
+    hipLaunchKernelGGL(face_boxes_stream_kernel, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const BoxStreamSeg*>(segs), rects, flags, n_rows, carry, n_slots, top, bottom, left, right, T,
+                       boxes, n_out, status);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

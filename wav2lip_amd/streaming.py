@@ -29,8 +29,35 @@ Memory per stream does not grow with its duration: a spectrogram window of `mel_
 the stream continues in a FRESH window that starts with the at most 16 columns still needed; batches in flight keep the old one
 alive (the runner's `keep=`), and no column is ever moved or overwritten under a batch that may read it.
 
+Live video.  A stream whose camera frames arrive with its audio has neither frames nor boxes to open with:
+
+    streams = LipsyncStreams(model, sink=deliver, detector=face_detection.FaceAlignment(...), pads=(0, 10, 0, 0), smooth_T=5)
+    streams.open_live(key)                    # no frames, no boxes; cycle=False: the rows end with the video
+    streams.feed_frames(key, frames)          # uint8 [H,W,3] BGR host arrays, or one uint8 device tensor [n,H,W,3]
+    streams.close_video(key)                  # end of video; `close(key)` still ends the audio
+
+The contract, next to the one above: however a live stream's audio and frames are cut into `feed` / `feed_frames` calls and
+interleaved with other streams, with F the frames it was fed the rows it runs are exactly
+`multiclip.rows_inference(n_mel, len(F), boxes, fps)` - or, with cycle=False, their first `min(len(rows), len(F))` - where `boxes`
+is the finish of `face_detect(F, detector, pads, nosmooth=(smooth_T == 0))` (pads, clipping, smoothing, "no face") on the rects
+the detector gives IN WHOLE BATCHES of `face_det_batch_size` frames, the last batch padded with its last frame.  A rect from a
+whole batch does not depend on which frames fill the batch; `face_detect` itself ends a video in a ragged batch, and a
+detector's launches are a function of the batch size.  With the fp32 detector the rects of a ragged batch have been equal on
+every clip tried, so the boxes are `face_detect`'s as it stands; with `precision="bf16"` another split-K factor sums in another
+order and a rect of the ragged batch does come out different now and then (4 boxes of a 52-frame clip) - there
+the boxes are those of `face_detect` run in whole batches.  The finish is exact because `get_smoothened_boxes` looks forward: box i is final once frame i + smooth_T - 1 has
+been detected, and the last boxes once the video is closed (face_detection/live.py).
+Per `step` the frames fed since the last one go up in ONE pinned buffer, through detector batches of exactly
+`face_det_batch_size`, and ONE w2l_face_boxes_stream launch (csrc/detect.hip) finishes the boxes of all streams; the NEXT `step`
+first waits for that launch's event (it never polls, so the batching stays a function of the call sequence).  Row i is ready
+when its spectrogram window is final and frame i % n_frames is there with a final box: boxes lag smooth_T - 1 frames plus one
+tick.  The uploaded frames stay on the device and the generator reads them there.  A frame without a face ends its stream only:
+the rows already taken are delivered, `sink(key, None)` follows and `errors[key]` says why.  A stream is gone once its last row is
+delivered; `feed` / `feed_frames` on it then raise KeyError.
+
 `python -m wav2lip_amd.streaming --checkpoint_path C --face F0 --audio A0 --face F1 --audio A1 ... --outdir D` feeds every audio
-file in `--chunk_ms` slices round-robin, steps after each round and writes one AVI per stream.
+file in `--chunk_ms` slices round-robin, steps after each round and writes one AVI per stream; with `--live_video` every video is
+fed frame by frame as its audio goes by and `face_detect` is never called.
 """
 import collections
 import os
@@ -91,6 +118,7 @@ def bucket(n, batch_size):
 
 class StreamState:
     """host bookkeeping of one stream, no device in it: samples held, columns done, the window's position, rows emitted"""
+    live = False
 
     def __init__(self, key, frames, boxes, static, fps, cap):
         self.key, self.frames, self.boxes, self.static, self.fps, self.cap = key, frames, boxes, bool(static), float(fps), int(cap)
@@ -169,6 +197,232 @@ class StreamState:
 
     def finished(self):
         return self.rows_done and self.delivered == self.n_rows
+
+    def locate(self, fi):
+        """(the object whose `.frames` the runner reads frame fi from, its index there)"""
+        return self, fi
+
+    def release_delivered(self):
+        """called after every delivered row; a live stream lets go of frames no later row reads"""
+
+
+class FrameChunk:
+    """the frames [first, first + n) of a live stream, resident on the device: what one tick uploaded for it (a view of the
+    tick's staging buffer), or a tensor the caller fed.  `BatchRunner` reads `.frames` where it lies."""
+
+    def __init__(self, key, first, frames):
+        self.key, self.first, self.frames, self.n = key, int(first), frames, int(frames.shape[0])
+        self.nbytes = self.n * int(frames.shape[1]) * int(frames.shape[2]) * 3
+
+
+class LiveState(StreamState):
+    """a stream whose video arrives with its audio (`open_live`): the frames fed since the last tick, the chunks resident on
+    the device, the boxes that are final so far - still no device in it"""
+    live = True
+
+    def __init__(self, key, fps, cap, cycle):
+        StreamState.__init__(self, key, None, [], False, fps, cap)
+        self.cycle = bool(cycle)
+        self.shape = None                     # (H, W): fixed by the first frame fed
+        self.fresh, self.n_frames = [], 0     # host arrays / device tensors fed since the last tick; frames fed in all
+        self.seen = 0                         # frames handed to the detector
+        self.video_closed = self.close_sent = self.video_done = False      # close_video called / in a launch / its boxes final
+        self.video = []                       # FrameChunks, in frame order
+        self.error = None
+
+    def feed_frames(self, frames):
+        if self.video_closed:
+            raise ValueError("stream %r: its video is closed" % (self.key,))
+        if hasattr(frames, "data_ptr"):
+            if str(frames.dtype) != "torch.uint8" or frames.dim() != 4 or frames.shape[3] != 3:
+                raise ValueError("stream %r: a frame tensor must be uint8 [n,H,W,3], got %s %s"
+                                 % (self.key, frames.dtype, tuple(frames.shape)))
+            items, shapes = ([frames.contiguous()] if frames.shape[0] else []), [tuple(int(v) for v in frames.shape[1:3])]
+        else:
+            if isinstance(frames, np.ndarray) and frames.ndim == 3:
+                frames = [frames]
+            items = []
+            for f in frames:
+                if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
+                    raise ValueError("stream %r: frames must be uint8 [H,W,3] arrays" % (self.key,))
+                items.append(np.ascontiguousarray(f).copy())
+            shapes = [f.shape[:2] for f in items]
+        for s in shapes:
+            if min(s) < 1 or (self.shape or s) != s or s != shapes[0]:
+                raise ValueError("stream %r: a frame of shape %s in a stream of %s frames" % (self.key, s, self.shape or shapes[0]))
+        if items:
+            self.shape = shapes[0]
+            self.fresh += items
+            self.n_frames += sum(int(f.shape[0]) if hasattr(f, "data_ptr") else 1 for f in items)
+
+    def n_fresh(self):
+        return self.n_frames - self.seen
+
+    def plan(self):
+        """`StreamState.plan`; but a window full of columns whose rows still wait for their frames can neither advance nor
+        roll over: then the samples wait on the host until rows have been taken"""
+        keep_from = max(0, min(row_start(self.next_row, self.fps), self.cols_done - mel_step_size))
+        if self.target() > self.cols_done >= self.col0 + self.cap and keep_from <= self.col0:
+            return None
+        return StreamState.plan(self)
+
+    def take_rows(self):
+        """`StreamState.take_rows` with the second condition of a live row: frame i % n_frames is there with a final box.
+        While the video is open that is frame i itself; once the closed video's boxes are all final the rows cycle over it, or
+        with cycle=False end with it."""
+        out = []
+        while not self.rows_done:
+            i = self.next_row
+            if self.video_done and not self.cycle and i >= self.n_frames:
+                self.rows_done, self.n_rows = True, i         # the prefix of the rows that the video covers
+                break
+            s, tail = row_start(i, self.fps), False
+            if s + mel_step_size <= self.cols_done:
+                pass
+            elif self.closed and self.cols_done == self.target():
+                s, tail = self.cols_done - mel_step_size, True
+            else:
+                break
+            if self.video_done:
+                fi = i % self.n_frames
+            elif i < len(self.boxes):
+                fi = i
+            else:
+                break
+            if tail:
+                self.rows_done, self.n_rows = True, i + 1
+            out.append((i, fi, self.boxes[fi], s))
+            self.next_row += 1
+        return out
+
+    def locate(self, fi):
+        for ch in reversed(self.video):
+            if ch.first <= fi:
+                return ch, fi - ch.first
+        raise RuntimeError("stream %r: frame %d is not resident" % (self.key, fi))
+
+    def release_delivered(self):
+        if not self.cycle:                    # row i reads frame i: a chunk whose rows are all delivered is read no more
+            while self.video and self.delivered >= self.video[0].first + self.video[0].n:
+                self.video.pop(0)
+
+
+class DeviceBoxes:
+    """the device side of live face detection: per call one staged copy, the detector batches, ONE w2l_face_boxes_stream launch
+    (csrc/detect.hip) for every stream of the tick and one copy back - in the manner of `face_detection.many._detect_group`"""
+
+    def __init__(self, device, detector, pads, T, batch_size):
+        import torch
+        from . import _lib
+        from .face_detection import live
+        self.torch, self.device, self.lib, self.live = torch, device, _lib.load(), live
+        self.detector, self.pads, self.T, self.B = detector, pads, T, batch_size
+        self.carry = torch.zeros((64, live.CARRY_ROWS, 4), dtype=torch.int32, device=device)
+
+    def reserve(self, n_slots):
+        """room for carry slots [0, n_slots); the table grows on the launches' stream, so in order with them"""
+        old = self.carry.shape[0]
+        if n_slots > old:
+            grown = self.torch.zeros((max(n_slots, 2 * old),) + tuple(self.carry.shape[1:]), dtype=self.torch.int32, device=self.device)
+            grown[:old].copy_(self.carry)
+            self.carry = grown
+
+    def launch(self, items):
+        """items: [(fresh, H, W, slot, seen, closed)] - `fresh` the stream's new frames in order (host arrays, device tensors
+        [n,H,W,3]).  Returns a ticket; `ticket["chunks"][k]` are item k's new frames on the device, [(frame count, tensor)]:
+        runs of host frames as views of the staging buffer, fed tensors as they are."""
+        from ._lib import check, current_stream, ptr
+        torch, live, B, T = self.torch, self.live, self.B, self.T
+        SEG = live.BOX_STREAM_SEGMENT
+        # ---- rows: the items of one frame shape are one run of arena rows, padded to whole detector batches
+        runs, n_new, groups = [], [], collections.OrderedDict()
+        for k, (fresh, H, W, _, _, _) in enumerate(items):
+            mine = []                                      # [host arrays] or a tensor, consecutive host frames joined
+            for f in fresh:
+                if hasattr(f, "data_ptr"):
+                    mine.append(f)
+                elif mine and isinstance(mine[-1], list):
+                    mine[-1].append(f)
+                else:
+                    mine.append([f])
+            runs.append(mine)
+            n_new.append(sum(len(r) if isinstance(r, list) else int(r.shape[0]) for r in mine))
+            if n_new[k]:
+                groups.setdefault((H, W), []).append(k)
+        row0, spans, total = {}, [], 0
+        for (H, W), members in groups.items():
+            first = total
+            for k in members:
+                row0[k] = total
+                total += n_new[k]
+            padded = first + (total - first + B - 1) // B * B
+            spans.append((H, W, first, total, padded))
+            total = padded
+        # ---- one staging buffer: [address table][segment table][the frames that were host arrays]
+        seg_off = _align(total * 8)
+        off = _align(seg_off + len(items) * SEG.itemsize)
+        at = {}
+        for k, mine in enumerate(runs):
+            for j, r in enumerate(mine):
+                if isinstance(r, list):
+                    at[(k, j)] = off
+                    off = _align(off + len(r) * r[0].nbytes)
+        host = torch.empty(off, dtype=torch.uint8, pin_memory=True)
+        stage_dev = torch.empty(off, dtype=torch.uint8, device=self.device)
+        stage = host.numpy()
+        addr = stage[:total * 8].view("<u8")
+        segs = stage[seg_off:seg_off + len(items) * SEG.itemsize].view(SEG)
+        chunks, out0 = [], 0
+        for k, (fresh, H, W, slot, seen, closed) in enumerate(items):
+            fb, r, mine = H * W * 3, row0.get(k, 0), []
+            for j, run in enumerate(runs[k]):
+                if isinstance(run, list):
+                    o, n = at[(k, j)], len(run)
+                    dst = stage[o:o + n * fb].reshape(n, H, W, 3)
+                    for i, f in enumerate(run):
+                        dst[i] = f
+                    t = stage_dev[o:o + n * fb].view(n, H, W, 3)
+                else:
+                    t, n = run, int(run.shape[0])
+                addr[r:r + n] = np.uint64(t.data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(fb)
+                mine.append((n, t))
+                r += n
+            chunks.append(mine)
+            segs[k] = (row0.get(k, 0), n_new[k], H, W, slot, seen, int(bool(closed)), out0)
+            out0 += live.new_final_count(seen, n_new[k], closed, T)
+        for H, W, first, end, padded in spans:
+            addr[end:padded] = addr[end - 1]               # the last batch of a shape: its last address again, into scratch rows
+        stage_dev.copy_(host, non_blocking=True)
+        rects = torch.empty((max(total, 1), 4), dtype=torch.int32, device=self.device)
+        flags = torch.empty((max(total, 1),), dtype=torch.int32, device=self.device)
+        for H, W, first, end, padded in spans:
+            for lo in range(first, padded, B):
+                self.detector.rects_for_rows(stage_dev[lo * 8:(lo + B) * 8], B, H, W, rects, flags, lo)
+        out = torch.empty(4 * out0 + 2 * len(items), dtype=torch.int32, device=self.device)     # boxes, then status: one copy back
+        top, bottom, left, right = self.pads
+        with torch.cuda.device(self.device):
+            check(self.lib.w2l_face_boxes_stream(current_stream(), len(items), host.data_ptr() + seg_off, stage_dev.data_ptr() + seg_off,
+                                                 ptr(rects), ptr(flags), total, ptr(self.carry), int(self.carry.shape[0]), top, bottom,
+                                                 left, right, T, ptr(out), out0, out.data_ptr() + 16 * out0), "face_boxes_stream")
+        host_out = torch.empty(out.numel(), dtype=torch.int32, pin_memory=True)
+        host_out.copy_(out, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        counts = [int(c) for c in np.diff(np.append(segs["out0"], out0))]
+        return dict(chunks=chunks, counts=counts, host_out=host_out, done=done, keep=(host, stage_dev, rects, flags, out))
+
+    @staticmethod
+    def collect(ticket):
+        """wait for the launch's event; [(boxes int32 [count,4] of (y1, y2, x1, x2), (code, frame))] per item"""
+        ticket["done"].synchronize()
+        res = ticket["host_out"].numpy()
+        n = sum(ticket["counts"])
+        status = res[4 * n:].reshape(-1, 2)
+        out, r = [], 0
+        for k, c in enumerate(ticket["counts"]):
+            out.append((res[4 * r:4 * (r + c)].reshape(c, 4).copy(), (int(status[k][0]), int(status[k][1]))))
+            r += c
+        return out
 
 
 class DeviceMel:
@@ -269,7 +523,8 @@ class LipsyncStreams:
     stream's frames in row order, then `sink(key, None)`; without a sink the frames are collected in `self.frames[key]` (which
     `drain` returns).  `on_batch(rows)` receives each launched batch's [(key, row index)] including the padding rows."""
 
-    def __init__(self, model, batch_size=128, depth=None, precision="f32", fps=25., sink=None, on_batch=None, mel_window=1024):
+    def __init__(self, model, batch_size=128, depth=None, precision="f32", fps=25., sink=None, on_batch=None, mel_window=1024,
+                 detector=None, pads=(0, 10, 0, 0), smooth_T=5, face_det_batch_size=16):
         from .models.wav2lip import check_precision
         self.precision = check_precision(precision)
         if batch_size < 1:
@@ -292,6 +547,21 @@ class LipsyncStreams:
         self._pending = collections.deque()              # (ticket, [(stream, row)]) of the batches in flight, oldest first
         self._runner = self._mel = None
         self.launches = 0                                # w2l_mel_stream_cols staging copies + launches so far
+        # ---- live streams only (`open_live`)
+        from .face_detection.live import CARRY_ROWS
+        self.detector, self.pads, self.smooth_T = detector, tuple(int(p) for p in pads), int(smooth_T)
+        self.face_det_batch_size = int(face_det_batch_size)
+        if len(self.pads) != 4:
+            raise ValueError("pads must be (top, bottom, left, right)")
+        if not 0 <= self.smooth_T <= CARRY_ROWS:
+            raise ValueError("smooth_T must be in 0..%d" % CARRY_ROWS)
+        if self.face_det_batch_size < 1:
+            raise ValueError("face_det_batch_size must be at least 1")
+        self.errors = {}                                 # key -> message of a live stream that ended on a frame (many.NO_FACE, ...)
+        self.box_launches = 0                            # w2l_face_boxes_stream launches so far: at most one per step
+        self._boxes = None                               # DeviceBoxes
+        self._detecting = None                           # (ticket, [stream per item]) of the detection the last step launched
+        self._slots, self._free_slots = {}, []           # carry slot per live stream whose video is under way
 
     # ---- the stream's life
     def open(self, key, frames, boxes, static=False, fps=None):
@@ -311,6 +581,34 @@ class LipsyncStreams:
         if len(checked) != (1 if static else len(frames)):
             raise ValueError("stream %r: one box per frame" % (key,))
         self._streams[key] = StreamState(key, frames, checked, static, self.fps if fps is None else fps, self.mel_window)
+
+    def open_live(self, key, fps=None, cycle=True):
+        """a stream whose video arrives with its audio: no frames and no boxes; `feed_frames` brings frames, the detector of
+        the constructor finds the faces as they come.  cycle=False: the rows end with the video instead of cycling over it."""
+        if self.detector is None:
+            raise ValueError("stream %r: open_live needs LipsyncStreams(detector=...)" % (key,))
+        if key in self._streams:
+            raise ValueError("stream %r is already open" % (key,))
+        self._streams[key] = LiveState(key, self.fps if fps is None else fps, self.mel_window, cycle)
+
+    def _get_live(self, key):
+        st = self._get(key)
+        if not st.live:
+            raise ValueError("stream %r was opened with its frames" % (key,))
+        return st
+
+    def feed_frames(self, key, frames):
+        """uint8 [H,W,3] BGR host arrays, or one uint8 device tensor [n,H,W,3], of the stream's shape (the first frame fixes it)"""
+        self._get_live(key).feed_frames(frames)
+
+    def close_video(self, key):
+        """end of video: the boxes that depend on it become final with the next tick, then the rows cycle over the frames"""
+        st = self._get_live(key)
+        if st.video_closed:
+            raise ValueError("stream %r: its video is closed" % (key,))
+        if st.n_frames == 0:
+            raise ValueError("stream %r: no frames; its video stays open" % (key,))
+        st.video_closed = True
 
     def _get(self, key):
         try:
@@ -340,6 +638,8 @@ class LipsyncStreams:
         if self._runner is None:
             self._runner = BatchRunner(self.model, self.batch_size, self.depth, self.precision)
             self._mel = DeviceMel(self._runner.device)
+        if self._boxes is None and self.detector is not None:
+            self._boxes = DeviceBoxes(self._runner.device, self.detector, self.pads, self.smooth_T, self.face_det_batch_size)
 
     def _columns_round(self):
         more = advance_columns(self._mel, self._streams.values())
@@ -350,6 +650,7 @@ class LipsyncStreams:
         """compute the newly final columns (one launch for all streams; more only while a stream's backlog exceeds its window),
         launch the full batches of ready rows - with `flush` the remainder too - and deliver the batches that have finished"""
         self._backend()
+        self._collect_boxes()
         while True:
             more = self._columns_round()
             for st in self._streams.values():
@@ -358,10 +659,88 @@ class LipsyncStreams:
             self._launch(False)
             if not more:
                 break
+        for st in [st for st in self._streams.values() if st.live and st.finished()]:
+            self._end(st)                                # cycle=False: the video ended behind the last delivered row
+        self._detect_round()
         if flush:
             self._launch(True)
         while self._pending and self._runner.ready(self._pending[0][0]):
             self._collect()
+
+    # ---- live streams: the boxes of the previous tick in, the frames of this tick out
+    def _end(self, st):
+        """a live stream none of whose rows is under way leaves"""
+        if self._streams.get(st.key) is st:
+            del self._streams[st.key]
+        st.frames = st.window = None
+        st.video, st.fresh = [], []
+        self.sink(st.key, None)
+
+    def _fail(self, st, message):
+        """a frame ended the stream: the rows taken so far are delivered, then `sink(key, None)`; `errors[key]` says why"""
+        self.errors[st.key] = st.error = message
+        if not st.rows_done:
+            st.rows_done, st.n_rows = True, st.next_row
+        if self._streams.get(st.key) is st:
+            del self._streams[st.key]
+        st.fresh = []
+        if st.finished():
+            self._end(st)
+
+    def _collect_boxes(self):
+        """WAIT for the detection the previous step launched (an event, never a poll: what is ready when is a function of the
+        call sequence) and append every stream's newly final boxes"""
+        if self._detecting is None:
+            return
+        from .face_detection.many import NO_FACE
+        (ticket, sts), self._detecting = self._detecting, None
+        for st, (boxes, (code, frame)) in zip(sts, self._boxes.collect(ticket)):
+            if self._streams.get(st.key) is not st:      # it ended meanwhile
+                continue
+            if code == 1:
+                self._fail(st, NO_FACE)
+                continue
+            if code == 2:
+                self._fail(st, "frame %d: the device left the frame's box to the host - a non-finite or huge coordinate, where the "
+                               "reference's int() raises too, or more candidates than its NMS holds" % frame)
+                continue
+            if code:
+                self._fail(st, "internal error: w2l_face_boxes_stream did not follow this stream's segment (status %d): the device "
+                               "copy of the segment table failed the kernel's bounds" % code)
+                continue
+            try:
+                st.boxes += validate_boxes(boxes, *st.shape) if len(boxes) else []
+            except ValueError as e:
+                self._fail(st, "frame %d..%d: %s" % (len(st.boxes), len(st.boxes) + len(boxes) - 1, e))
+                continue
+            if st.close_sent and len(st.boxes) == st.n_frames:
+                st.video_done = True
+
+    def _detect_round(self):
+        """the frames fed since the last tick, and the videos closed since: one staged copy, the detector batches and ONE
+        w2l_face_boxes_stream launch for all of them (DeviceBoxes.launch)"""
+        for st in [st for st in self._slots if self._streams.get(st.key) is not st or st.close_sent]:
+            self._free_slots.append(self._slots.pop(st))
+        items, sts = [], []
+        for st in self._streams.values():
+            if not st.live or st.close_sent or not (st.n_fresh() or st.video_closed):
+                continue
+            if st not in self._slots:
+                self._slots[st] = self._free_slots.pop() if self._free_slots else len(self._slots)
+            items.append((st.fresh, st.shape[0], st.shape[1], self._slots[st], st.seen, st.video_closed))
+            sts.append(st)
+        if not items:
+            return
+        self._boxes.reserve(1 + max(it[3] for it in items))
+        ticket = self._boxes.launch(items)
+        self.box_launches += 1
+        for st, chunks in zip(sts, ticket["chunks"]):
+            for n, frames in chunks:
+                st.video.append(FrameChunk(st.key, st.seen, frames))
+                st.seen += n
+            assert st.seen == st.n_frames
+            st.fresh, st.close_sent = [], st.video_closed
+        self._detecting = (ticket, sts)
 
     def _launch(self, flush):
         bs = self.batch_size
@@ -369,7 +748,7 @@ class LipsyncStreams:
             rows = [self._ready.popleft() for _ in range(min(bs, len(self._ready)))]
             n = len(rows)
             size = bs if n == bs else bucket(n, bs)
-            ticket = self._runner.submit([(st, fi, box, mel) for st, _, fi, box, mel in rows], pad_to=size)
+            ticket = self._runner.submit([st.locate(fi) + (box, mel) for st, _, fi, box, mel in rows], pad_to=size)
             owners = [(st, row) for st, row, _, _, _ in rows]
             if self.on_batch is not None:
                 self.on_batch([(st.key, row) for st, row in owners] + [(owners[-1][0].key, owners[-1][1])] * (size - n))
@@ -382,6 +761,7 @@ class LipsyncStreams:
         for (st, _), frame in zip(owners, self._runner.result(item)):
             self.sink(st.key, frame)
             st.delivered += 1
+            st.release_delivered()
             if st.finished():
                 if self._streams.get(st.key) is st:
                     del self._streams[st.key]
@@ -391,14 +771,18 @@ class LipsyncStreams:
     def drain(self):
         """close nothing; run and deliver everything that is ready or in flight"""
         self.step(flush=True)
+        while self._detecting is not None:               # live streams: the boxes in flight may make rows ready
+            self.step(flush=True)
         while self._pending:
             self._collect()
         return self.frames
 
     def device_bytes(self, key=None):
-        """device memory held per stream between ticks: its spectrogram window (the staging of a tick is transient)"""
-        sts = self._streams.values() if key is None else [self._get(key)]
-        return sum(DeviceMel.window_bytes(st.window) for st in sts if st.window is not None)
+        """device memory held per stream between ticks: its spectrogram window (the staging of a tick is transient), and of a
+        live stream the frames resident on the device"""
+        sts = list(self._streams.values() if key is None else [self._get(key)])
+        return (sum(DeviceMel.window_bytes(st.window) for st in sts if st.window is not None)
+                + sum(ch.nbytes for st in sts if st.live for ch in st.video))
 
 
 # ---------------------------------------------------------------- command line
@@ -423,14 +807,18 @@ def build_parser():
     p.add_argument('--nosmooth', default=False, action='store_true', help='Prevent smoothing face detections over a short temporal window')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='Generator arithmetic')
     p.add_argument('--face_det_precision', default='fp32', choices=['fp32', 'bf16'], help='Face detector arithmetic')
+    p.add_argument('--live_video', default=False, action='store_true',
+                   help='Feed the frames of every video as they become due with the audio and detect faces as they arrive')
     from .inference import add_det_scale_flag
     add_det_scale_flag(p)
     return p
 
 
-def main(argv=None):
+def main(argv=None, state_dict=None):
     """feed every `--audio` in `--chunk_ms` slices round-robin to its `--face`, step after each round, write <outdir>/<k>.avi as
-    each stream ends; returns the written paths in stream order"""
+    each stream ends; returns the written paths in stream order.  With `--live_video` a video (not an image, no `--box`) is fed
+    frame by frame as its audio goes by - floor(fps * samples fed / 16000) frames so far - and `face_detect` is never called.
+    `state_dict` (S3FD weights) replaces face_detection/s3fd.pth."""
     import copy
 
     import torch
@@ -440,6 +828,12 @@ def main(argv=None):
     if len(a.face) != len(a.audio):
         raise ValueError("%d --face for %d --audio: pass them in pairs" % (len(a.face), len(a.audio)))
     dev = torch.device("cuda", torch.cuda.current_device())
+    detector = None
+    if a.live_video or state_dict is not None:
+        from . import face_detection
+        detector = face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False, device=str(dev), state_dict=state_dict,
+                                                **inference._precision_kw(inference.CLI_PRECISION[a.face_det_precision]),
+                                                **inference._det_scale_kw(a.face_det_scale))
     jobs = []
     for k, (face, wav_path) in enumerate(zip(a.face, a.audio)):
         one = copy.copy(a)
@@ -449,15 +843,18 @@ def main(argv=None):
         frames, fps = inference.read_frames(one)
         if not wav_path.endswith('.wav'):
             raise ValueError("--audio %s: pass a .wav" % wav_path)
-        if a.box[0] == -1:
-            det = inference.face_detect(frames if not one.static else [frames[0]], pads=a.pads, nosmooth=a.nosmooth,
+        live = a.live_video and a.box[0] == -1 and not one.static
+        if live:
+            boxes = None
+        elif a.box[0] == -1:
+            det = inference.face_detect(frames if not one.static else [frames[0]], detector=detector, pads=a.pads, nosmooth=a.nosmooth,
                                         batch_size=a.face_det_batch_size, precision=inference.CLI_PRECISION[a.face_det_precision],
                                         det_scale=a.face_det_scale)
             boxes = [c for _, c in det]
         else:
             boxes = [tuple(a.box)] * len(frames)
         jobs.append(dict(key=k, frames=frames, fps=fps, boxes=boxes, static=one.static, wav=audio.load_wav(wav_path, 16000),
-                         audio=wav_path, out=os.path.join(a.outdir, "%d.avi" % k), pos=0))
+                         audio=wav_path, out=os.path.join(a.outdir, "%d.avi" % k), pos=0, live=live, fed=0))
     os.makedirs(a.outdir, exist_ok=True)
     model = inference.load_model(a.checkpoint_path, dev)
     got = {j["key"]: [] for j in jobs}
@@ -467,22 +864,38 @@ def main(argv=None):
             got[key].append(frame)
             return
         j = jobs[key]
-        inference.write_result(j["out"], got.pop(key), j["fps"], j["audio"])
+        if key not in streams.errors:
+            inference.write_result(j["out"], got.pop(key), j["fps"], j["audio"])
 
-    streams = LipsyncStreams(model, batch_size=a.wav2lip_batch_size, precision=inference.CLI_PRECISION[a.precision], sink=sink)
+    streams = LipsyncStreams(model, batch_size=a.wav2lip_batch_size, precision=inference.CLI_PRECISION[a.precision], sink=sink,
+                             detector=detector, pads=a.pads, smooth_T=0 if a.nosmooth else 5, face_det_batch_size=a.face_det_batch_size)
     for j in jobs:
-        streams.open(j["key"], j["frames"], j["boxes"], static=j["static"], fps=j["fps"])
+        if j["live"]:
+            streams.open_live(j["key"], fps=j["fps"])
+        else:
+            streams.open(j["key"], j["frames"], j["boxes"], static=j["static"], fps=j["fps"])
     chunk = max(1, int(round(16000 * a.chunk_ms / 1000.)))
     live = list(jobs)
     while live:
         for j in live:
             streams.feed(j["key"], j["wav"][j["pos"]:j["pos"] + chunk])
             j["pos"] += chunk
+            if j["live"] and j["fed"] is not None:
+                # the frames that have become due; the audio's end brings the rest of the video
+                due = len(j["frames"]) if j["pos"] >= len(j["wav"]) else min(len(j["frames"]), int(j["fps"] * j["pos"] / 16000.))
+                if due > j["fed"]:
+                    streams.feed_frames(j["key"], j["frames"][j["fed"]:due])
+                    j["fed"] = due
+                if due == len(j["frames"]):
+                    streams.close_video(j["key"])
+                    j["fed"] = None
             if j["pos"] >= len(j["wav"]):
                 streams.close(j["key"])
-        live = [j for j in live if j["pos"] < len(j["wav"])]
         streams.step()
+        live = [j for j in live if j["pos"] < len(j["wav"]) and j["key"] not in streams.errors]      # a frame without a face ends it
     streams.drain()
+    for key, message in streams.errors.items():
+        raise ValueError("--face %s: %s" % (a.face[key], message))
     return [j["out"] for j in jobs]
 
 
