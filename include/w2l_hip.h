@@ -27,6 +27,7 @@
  *   w2l_compose_rows_u8   evaluation/gen_videos_from_filelist.py:221-227 (resize + paste + the frame copy, one pass)
  *   w2l_resize_rows_u8    evaluation/real_videos_inference.py:51-70,239-245 (the whole-frame cv2.resize of the `max_frame_res`
  *                         cap and of rescale_frames, one frame per row)
+ *   w2l_jpeg_encode_rows  preprocess.py:62 (cv2.imwrite of every face crop as <i>.jpg), one crop per row
  *   w2l_mel_gather_rows   evaluation/gen_videos_from_filelist.py:176-183 (mel windows, one spectrogram per row)
  *   w2l_s3fd_pack_rows    face_detection/api.py:62 + detection/sfd/detect.py:57-63 (the detector's input), one frame per row
  *   w2l_s3fd_pack_rows_scaled  inference.py:202-203 (the `cv2.resize(frame, (w // k, h // k))` of --resize_factor) fused into the
@@ -247,6 +248,35 @@ typedef struct {
     int32_t Hs, Ws, Hd, Wd;
 } w2l_resize_row;
 int w2l_resize_rows_u8(void* stream, int B, const w2l_resize_row* rows, int max_dst_pixels);
+
+/* Row-table JPEG encoding of face crops (preprocess.py:62 `cv2.imwrite(<i>.jpg, fb[j][y1:y2, x1:x2])`: baseline JFIF, 4:2:0,
+ * standard Huffman tables, no restart markers).  Row b is a w2l_frame_row: src is the frame u8 [H,W,3] BGR at ANY byte address,
+ * the box y1:y2, x1:x2 is the crop, dst is the row's output slot of cap[b] bytes at any byte address.  After the launch
+ * dst[0 : lengths[b]] is the complete file of that crop, byte-equal to what libjpeg(-turbo) writes for the same pixels at
+ * `quality` (PIL.Image.save(format="JPEG", quality=q, subsampling=2), cv2.imwrite's IMWRITE_JPEG_QUALITY): 623 header bytes (SOI,
+ * APP0 JFIF 1.1, DQT luma, DQT chroma, SOF0, DHT DC0 AC0 DC1 AC1, SOS; height at offset 163, width at 165), the entropy stream,
+ * EOI.  Rows of different crop sizes share the launch, two rows may name one frame, no pixel outside a box is read.  Two kernel
+ * launches per call, whatever B is; the bytes are a function of the pixels alone (integer arithmetic, no run-to-run variation).
+ *
+ * max_blocks >= the largest 6 * ceil(h / 16) * ceil(w / 16) of the batch (h, w: crop sizes) sizes the launch and the workspace;
+ * workspace: device memory, 16-byte aligned, at least w2l_jpeg_workspace_bytes(B, max_blocks) bytes, contents unspecified before
+ * and after.  cap, lengths: device int32 [B].
+ *
+ * A row whose file would not fit cap[b], whose crop has more blocks than max_blocks, or whose crop is higher or wider than 65535
+ * gets lengths[b] = -1 and nothing of its slot is written.  Bytes of a slot beyond lengths[b] are unspecified; bytes outside every
+ * slot are never written.  No file can exceed 625 + 416 * (its number of blocks) bytes: a block codes at most 22 bits of DC and
+ * 63 x 26 bits of AC = 208 bytes, byte stuffing can double that, and header + EOI are 625 (wav2lip_amd/jpeg.py capacity).
+ *
+ * PRECONDITION: every box is non-empty and inside its frame (0 <= y1 < y2 <= H, 0 <= x1 < x2 <= W), checked by the HOST caller
+ * (wav2lip_amd/jpeg.py) as for the other row-table kernels.  Refused with an error code, nothing written: NULL pointers, B outside
+ * [1, 65535], a row table that is not 16-byte aligned, quality outside [1, 100], max_blocks outside [1, 2^20], a workspace that
+ * is misaligned or too small. */
+int w2l_jpeg_encode_rows(void* stream, int B, const w2l_frame_row* rows, const int32_t* cap, int quality, int max_blocks,
+                         int32_t* lengths, void* workspace, size_t workspace_bytes);
+/* bytes of workspace one w2l_jpeg_encode_rows launch needs; 0 for B outside [1, 65535] or max_blocks outside [1, 2^20] */
+size_t w2l_jpeg_workspace_bytes(int B, int max_blocks);
+/* host only: the 623 header bytes of an h x w file at `quality` into out[623] (what the kernel copies and patches the size into) */
+int w2l_jpeg_header(int h, int w, int quality, uint8_t* out);
 
 /* ---------------------------------------------------------------- S3FD face detector glue (face_detection/detection/sfd/)
  * The detector's convolutions are w2l_conv_* layers (bias + ReLU, no BatchNorm); these are the ops between them. */

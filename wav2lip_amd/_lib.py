@@ -116,6 +116,9 @@ SIGNATURES = {
     "w2l_crop_resize_rows_u8": (_i, [_vp, _i, _vp, _i, _vp]),
     "w2l_compose_rows_u8": (_i, [_vp, _i, _vp, _i, _vp, _i]),
     "w2l_resize_rows_u8": (_i, [_vp, _i, _vp, _i]),
+    "w2l_jpeg_encode_rows": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, C.c_size_t]),
+    "w2l_jpeg_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "w2l_jpeg_header": (_i, [_i, _i, _i, _vp]),
     "w2l_s3fd_pack": (_i, [_vp, _ll, _vp, _vp, _i]),
     "w2l_s3fd_pack_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _i]),
     "w2l_s3fd_pack_rows_scaled": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i]),

@@ -10,8 +10,10 @@ the layout `trainer.main_*` and `data.ClipStore.from_directory` read.
 Per frame batch: the detector graph (fp32, or bf16 storage with `--face_det_precision bf16`), the gate + NMS and the rect rule run
 on the device and one [B][5] int32 array comes back (FaceAlignment.get_detections_for_batch).  The ragged last batch of a clip is
 padded with copies of its last frame, so that every batch of a clip size runs the same cached detector graph.  The JPEG encoding
-(what cv2.imwrite does by default: quality 95, 4:2:0) stays on the host, in a small thread pool that overlaps the next batch's
-detection (PIL releases the GIL while it encodes).
+(what cv2.imwrite does by default: quality 95, 4:2:0) runs by default on the host, in a small thread pool that overlaps the next
+batch's detection (PIL releases the GIL while it encodes).  With `--jpeg device` the batch is uploaded once, the detector reads it
+from device memory and the crops are encoded there, out of the same tensor (jpeg.CropEncoder, w2l_jpeg_encode_rows): only the
+files' bytes come back, and the pool's job is the file write.  Both write the same bytes.
 
 Differences from the reference, all on the file-format side: video is read with container.read_avi (uncompressed 24-bit
 BGR AVI with PCM16 audio); an .mp4 cannot be decoded here and is reported and skipped like any failing clip.  The reference's
@@ -51,10 +53,14 @@ def build_parser():
 
 def build_main_parser():
     """what the command line parses: `build_parser` plus `--face_det_scale K` (`inference.add_det_scale_flag`): the detector sees
-    every frame at 1/K of its size, the crops are cut from the full-resolution frame at the rects mapped back"""
+    every frame at 1/K of its size, the crops are cut from the full-resolution frame at the rects mapped back; and `--jpeg`, where
+    the crops are encoded"""
     from .inference import add_det_scale_flag
     p = build_parser()
     add_det_scale_flag(p)
+    p.add_argument('--jpeg', default='host', choices=['host', 'device'],
+                   help='Where the face crops are JPEG-encoded: host (default, a PIL thread pool) or device (a HIP kernel on the '
+                        'frames the detector has just read; the same bytes)')
     return p
 
 
@@ -110,6 +116,20 @@ def _jpeg_pool():
     return _pool
 
 
+_encoder = None
+
+
+def _crop_encoder(bs):
+    """`--jpeg device`: the process's jpeg.CropEncoder (one worker thread and one stream, whatever the number of clips); its file
+    writes go to the pool above, bounded as the host path bounds its pending crops"""
+    global _encoder
+    if _encoder is None:
+        from . import jpeg
+        _encoder = jpeg.CropEncoder(JPEG_QUALITY, pool=_jpeg_pool())
+    _encoder.max_files = 4 * bs
+    return _encoder
+
+
 def process_video_file(vfile, args, gpu_id):
     """preprocess.py:35-66: detect every frame of `vfile` in batches of args.batch_size on cuda:<gpu_id> and write the face crops
     fb[y1:y2, x1:x2] as <i>.jpg.  Returns when every crop is on disk."""
@@ -121,6 +141,11 @@ def process_video_file(vfile, args, gpu_id):
     det = get_detector(gpu_id, args)
     bs = args.batch_size
     pending = []
+    enc = None
+    if getattr(args, "jpeg", "host") == "device":
+        import torch
+        enc = _crop_encoder(bs)
+        dev = torch.device('cuda:{}'.format(gpu_id))
     try:
         i = -1
         for lo in range(0, len(frames), bs):
@@ -128,24 +153,43 @@ def process_video_file(vfile, args, gpu_id):
             if len(fb) < bs:
                 # the ragged last batch runs the full batch's graph (no rebuild per clip); the copies' rects are dropped
                 fb = np.concatenate([fb, np.repeat(fb[-1:], bs - len(fb), axis=0)])
+            if enc is not None:
+                fb = torch.from_numpy(np.ascontiguousarray(fb)).to(dev)        # the batch's one upload: detector and encoder read it
             preds = det.get_detections_for_batch(fb)[:min(bs, len(frames) - lo)]
 
+            boxes, rows, paths = [], [], []
             for j, f in enumerate(preds):
                 i += 1
                 if f is None:
                     continue
 
                 x1, y1, x2, y2 = f
+                if enc is not None:
+                    # what the slice fb[j][y1:y2, x1:x2] keeps: numpy cuts a rect that overhangs the frame at its edge
+                    box = (min(x1, fb.shape[2]), min(y1, fb.shape[1]), min(x2, fb.shape[2]), min(y2, fb.shape[1]))
+                    if box[2] <= box[0] or box[3] <= box[1]:
+                        raise ValueError("%s: frame %d: empty face crop %r (cv2.imwrite refuses an empty image)" % (vfile, i, f))
+                    boxes.append(box)
+                    rows.append(j)
+                    paths.append(path.join(fulldir, '{}.jpg'.format(i)))
+                    continue
                 crop = fb[j][y1:y2, x1:x2]
                 if crop.size == 0:
                     raise ValueError("%s: frame %d: empty face crop %r (cv2.imwrite refuses an empty image)" % (vfile, i, f))
                 pending.append(_jpeg_pool().submit(_write_jpeg, path.join(fulldir, '{}.jpg'.format(i)), crop))
+            if boxes:
+                with torch.cuda.device(dev):
+                    enc.submit(fb, boxes, paths, frame_index=rows)      # bounded: CropEncoder holds at most two batches back
             while len(pending) > 4 * bs:          # bounded: at most a few batches of crops wait for the encoder
                 pending.pop(0).result()
         for p in pending:
             p.result()
+        if enc is not None:
+            enc.finish()
     finally:
         wait(pending)
+        if enc is not None:
+            enc.drain()
 
 
 def process_audio_file(vfile, args):
