@@ -28,6 +28,7 @@
  *   w2l_resize_rows_u8    evaluation/real_videos_inference.py:51-70,239-245 (the whole-frame cv2.resize of the `max_frame_res`
  *                         cap and of rescale_frames, one frame per row)
  *   w2l_jpeg_encode_rows  preprocess.py:62 (cv2.imwrite of every face crop as <i>.jpg), one crop per row
+ *   w2l_jpeg_decode_rows  wav2lip_train.py:66, color_syncnet_train.py:97 (cv2.imread of every <id>.jpg), one file per row
  *   w2l_mel_gather_rows   evaluation/gen_videos_from_filelist.py:176-183 (mel windows, one spectrogram per row)
  *   w2l_s3fd_pack_rows    face_detection/api.py:62 + detection/sfd/detect.py:57-63 (the detector's input), one frame per row
  *   w2l_s3fd_pack_rows_scaled  inference.py:202-203 (the `cv2.resize(frame, (w // k, h // k))` of --resize_factor) fused into the
@@ -277,6 +278,84 @@ int w2l_jpeg_encode_rows(void* stream, int B, const w2l_frame_row* rows, const i
 size_t w2l_jpeg_workspace_bytes(int B, int max_blocks);
 /* host only: the 623 header bytes of an h x w file at `quality` into out[623] (what the kernel copies and patches the size into) */
 int w2l_jpeg_header(int h, int w, int quality, uint8_t* out);
+
+/* Row-table JPEG DECODING of face crops (wav2lip_train.py:66 / color_syncnet_train.py:97 `cv2.imread(fname)` of every <id>.jpg):
+ * the read side of w2l_jpeg_encode_rows.  The pixels are byte-equal to what libjpeg(-turbo) decodes with its defaults (PIL's
+ * Image.open(...).convert("RGB"), cv2.imread): jpeg_idct_islow, h2v2 "fancy" chroma upsampling (plain 2x2 replication for images of 1 to 4 columns, as
+ * libjpeg chooses), ycc_rgb_convert.
+ *
+ * Accepted class (w2l_jpeg_parse refuses everything else): baseline SOF0, 8-bit samples, three components sampled 2x2, 1x1, 1x1
+ * (4:2:0) with Cb and Cr on the same tables, 8-bit quantisers, ONE interleaved scan with Ss = 0, Se = 63, Ah = Al = 0, no restart
+ * interval (no DRI, or DRI = 0), JFIF or no APPn segment at all, any valid Huffman tables (not only Annex K's).
+ *
+ * w2l_jpeg_info: what w2l_jpeg_parse reads from one file's markers (host only, touches no device):
+ *   H, W                   image size, each in [1, 65535]
+ *   ecs_offset, ecs_bytes  the entropy-coded segment: from behind the SOS header to the EOI marker (eoi = 1), or, where the
+ *                          file has no EOI, to its last byte (eoi = 0).  A file cut inside its stream, or ending in a lone
+ *                          FF, is then refused by the kernel; one that lacks nothing but the EOI decodes with status 0
+ *   quant[2][64]           quantisers of luma and chroma in zigzag order, as the DQT segments carry them
+ *   bits[4][16], vals[4][256], nvals[4]   Huffman tables DC luma, AC luma, DC chroma, AC chroma as DHT carries them
+ * Return value: 0, or one of the reasons below with w2l_last_error() set; W2L_JPEG_MALFORMED is a file that is no JPEG or is cut
+ * inside its header, the others are well-formed files outside the class.  Never reads data[n] or beyond, whatever the
+ * segment lengths in the file claim. */
+#define W2L_JPEG_MALFORMED (-100)        /* no SOI, a segment running past the file, a missing table or SOF, RSTn without DRI ... */
+#define W2L_JPEG_NOT_BASELINE (-101)     /* progressive, extended, lossless or arithmetic-coded (any SOFn but SOF0) */
+#define W2L_JPEG_PRECISION (-102)        /* samples that are not 8 bits wide */
+#define W2L_JPEG_COMPONENTS (-103)       /* not three components (grayscale, CMYK) */
+#define W2L_JPEG_SAMPLING (-104)         /* sampling factors other than 2x2, 1x1, 1x1 (4:4:4, 4:2:2, ...) */
+#define W2L_JPEG_RESTART (-105)          /* a restart interval */
+#define W2L_JPEG_QUANT16 (-106)          /* 16-bit quantisation tables */
+#define W2L_JPEG_SCANS (-107)            /* more than one scan, a scan that is not all three components, or Ss/Se/Ah/Al set */
+#define W2L_JPEG_APPN (-108)             /* an APPn segment that is not JFIF / JFXX (Adobe APP14, Exif ...) */
+#define W2L_JPEG_SIZE (-109)             /* a height or width of 0 */
+#define W2L_JPEG_TABLES (-110)           /* Cb and Cr on different tables, or table ids outside 0..3 */
+#define W2L_JPEG_COLORSPACE (-111)       /* no JFIF segment and component ids 'R' 'G' 'B': libjpeg decodes such a file as RGB */
+typedef struct {
+    int32_t H, W;
+    int32_t ecs_offset, ecs_bytes;
+    int32_t eoi;
+    int32_t nvals[4];
+    uint8_t quant[2][64];
+    uint8_t bits[4][16];
+    uint8_t vals[4][256];
+} w2l_jpeg_info;
+int w2l_jpeg_parse(const uint8_t* data, size_t n, w2l_jpeg_info* info);
+
+/* host only: the table set of a parsed file in the lookup form the kernel reads (a 9-bit lookahead, then maxcode / valptr of
+ * T.81 F.2.2.3 for longer codes; quantisers widened to 16 bits), w2l_jpeg_table_bytes() = 5952 bytes into `out`.  Refused with
+ * w2l_last_error() set: (bits, vals) that form no prefix code or oversubscribe the code space (more than 2^l codes of up to l
+ * bits), more than 256 symbols, a symbol listed twice, a DC category above 11, a quantiser of 0. */
+size_t w2l_jpeg_table_bytes(void);
+int w2l_jpeg_build_tables(const w2l_jpeg_info* info, void* out);
+
+/* w2l_jpeg_row, 32 bytes, alignment 16:
+ *   bytes  0 ..  7  src (uint64)     device address of the file's entropy-coded segment, at ANY byte address
+ *   bytes  8 .. 15  dst (uint64)     device address of the row's output image u8 [H,W,3] BGR, at ANY byte address
+ *   bytes 16 .. 19  nbytes (int32)   bytes of the segment (w2l_jpeg_info.ecs_bytes)
+ *   bytes 20 .. 27  H, W (int32)     the image's size
+ *   bytes 28 .. 31  table (int32)    index of its table set in `tables`
+ * tables: n_tables sets of w2l_jpeg_table_bytes() each, back to back, device memory, 16-byte aligned.  Rows of different sizes
+ * and table sets share the launch; two rows may name one file.  One memset and three kernel launches per call, whatever B is:
+ * entropy decoding (one lane per file; sequential within a file, parallel across files), the inverse DCT, upsampling + colour.
+ *
+ * After the launch status[b] (device int32 [B]) is 0 and the image complete, or a negative reason and the image's bytes
+ * unspecified: -1 bits that are no code of the row's table, -2 a zero run past coefficient 63, -3 a marker other than the stuffed
+ * FF 00 (or bytes left over) before the end of the last MCU, -4 the stream ended early, -5 a row the launch cannot take (a size
+ * outside [1, 65535], more than max_blocks blocks, nbytes < 1, table outside [0, n_tables)).  Every read of a stream is bounded by
+ * its nbytes; a failed row writes nothing outside its own workspace slot and output image and does not affect the other rows.
+ *
+ * max_blocks >= the largest 6 * ceil(H / 16) * ceil(W / 16) of the batch; workspace: device memory, 16-byte aligned, at least
+ * w2l_jpeg_decode_workspace_bytes(B, max_blocks) bytes (192 per block: int16 coefficients and the three sample planes).
+ * Refused with an error code, nothing written: NULL pointers, B outside [1, 65535], max_blocks outside [1, 2^20], n_tables
+ * outside [1, 65535], rows or tables not 16-byte aligned, a workspace that is misaligned or too small. */
+typedef struct {
+    uint64_t src, dst;
+    int32_t nbytes, H, W, table;
+} w2l_jpeg_row;
+int w2l_jpeg_decode_rows(void* stream, int B, const w2l_jpeg_row* rows, const void* tables, int n_tables, int max_blocks,
+                         int32_t* status, void* workspace, size_t workspace_bytes);
+/* 0 for B outside [1, 65535] or max_blocks outside [1, 2^20] */
+size_t w2l_jpeg_decode_workspace_bytes(int B, int max_blocks);
 
 /* ---------------------------------------------------------------- S3FD face detector glue (face_detection/detection/sfd/)
  * The detector's convolutions are w2l_conv_* layers (bias + ReLU, no BatchNorm); these are the ops between them. */

@@ -47,6 +47,13 @@ class ResizeRow(C.Structure):
                 ("Wd", C.c_int32)]
 
 
+class JpegInfo(C.Structure):
+    """w2l_jpeg_info: what w2l_jpeg_parse reads from one file's markers"""
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("ecs_offset", C.c_int32), ("ecs_bytes", C.c_int32), ("eoi", C.c_int32),
+                ("nvals", C.c_int32 * 4), ("quant", (C.c_uint8 * 64) * 2), ("bits", (C.c_uint8 * 16) * 4),
+                ("vals", (C.c_uint8 * 256) * 4)]
+
+
 class MelRow(C.Structure):
     """w2l_mel_row: one mel window of the row-table gather, 16 bytes"""
     _fields_ = [("mel", C.c_uint64), ("T", C.c_int32), ("start", C.c_int32)]
@@ -119,6 +126,11 @@ SIGNATURES = {
     "w2l_jpeg_encode_rows": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, C.c_size_t]),
     "w2l_jpeg_workspace_bytes": (C.c_size_t, [_i, _i]),
     "w2l_jpeg_header": (_i, [_i, _i, _i, _vp]),
+    "w2l_jpeg_parse": (_i, [C.c_char_p, C.c_size_t, C.POINTER(JpegInfo)]),
+    "w2l_jpeg_table_bytes": (C.c_size_t, []),
+    "w2l_jpeg_build_tables": (_i, [C.POINTER(JpegInfo), _vp]),
+    "w2l_jpeg_decode_rows": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, C.c_size_t]),
+    "w2l_jpeg_decode_workspace_bytes": (C.c_size_t, [_i, _i]),
     "w2l_s3fd_pack": (_i, [_vp, _ll, _vp, _vp, _i]),
     "w2l_s3fd_pack_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _i]),
     "w2l_s3fd_pack_rows_scaled": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i]),

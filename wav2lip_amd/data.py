@@ -13,6 +13,9 @@ from Python's `random` like the reference.  `picks` records what was drawn so th
 host path (`train.make_generator_sample`).
 
 Image files are decoded with PIL (cv2 is not in the image); JPEG decoding is a libjpeg matter on both sides and is not pinned.
+`from_directory(..., decode="device")` (opt-in; W2L_JPEG_DECODE=device for `trainer.main_*`) takes the files' BYTES instead and
+decodes them on the device (`jpeg.decode_files`, byte-equal to PIL / libjpeg-turbo), many files per launch, then resizes a whole
+clip with one row-table launch: the rows in the store are the same bytes either way.
 """
 import os
 import random
@@ -42,6 +45,7 @@ class ClipStore:
         self._parts = []
         self._frames = None
         self.n_rows = 0
+        self.host_decoded = 0        # files of a decode="device" load that went through PIL (outside the class the device decodes)
 
     # ---------------------------------------------------------------- building
     def _resize(self, frame):
@@ -65,7 +69,11 @@ class ClipStore:
             if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
                 raise ValueError("frames must be uint8 [h, w, 3] (BGR), got %s %s" % (f.dtype, f.shape))
             rows.append(self._resize(f) if f.shape[:2] != (IMG, IMG) else torch.from_numpy(np.ascontiguousarray(f)).to(self.device)[None])
-        self._parts.append(torch.cat(rows, dim=0))
+        return self._append(torch.cat(rows, dim=0), frame_ids, wav, name)
+
+    def _append(self, rows, frame_ids, wav, name):
+        """a clip's finished rows u8 [n,96,96,3] into the store"""
+        self._parts.append(rows)
         self._frames = None
         self.first.append(self.n_rows)
         ids = [int(i) for i in frame_ids]
@@ -76,15 +84,74 @@ class ClipStore:
         self.names.append(name if name is not None else "clip%d" % len(self.names))
         return len(self.names) - 1
 
+    def _resize_rows(self, frames):
+        """device uint8 [h,w,3] frames (any sizes, any byte addresses) -> u8 [n,96,96,3]: every frame that is not 96x96 already is
+        resized by ONE w2l_crop_resize_rows_u8 launch (the row-table form, byte-equal to `_resize`'s w2l_crop_resize_u8); a
+        96x96 frame is stored as it is, as `add_clip` does"""
+        from .multiclip import FRAME_ROW
+        out = torch.empty((len(frames), IMG, IMG, 3), dtype=torch.uint8, device=self.device)
+        todo = [k for k, f in enumerate(frames) if tuple(f.shape[:2]) != (IMG, IMG)]
+        for k, f in enumerate(frames):
+            if tuple(f.shape[:2]) == (IMG, IMG):
+                out[k].copy_(f)
+        if todo:
+            table = np.zeros(len(todo), FRAME_ROW)
+            table["src"] = [frames[k].data_ptr() for k in todo]
+            table["H"] = table["y2"] = [int(frames[k].shape[0]) for k in todo]
+            table["W"] = table["x2"] = [int(frames[k].shape[1]) for k in todo]
+            tdev = torch.from_numpy(table.view(np.uint8).copy()).to(self.device)
+            res = out if len(todo) == len(frames) else torch.empty((len(todo), IMG, IMG, 3), dtype=torch.uint8, device=self.device)
+            check(self.lib.w2l_crop_resize_rows_u8(current_stream(), len(todo), ptr(tdev), IMG, ptr(res)), "crop_resize_rows_u8")
+            if res is not out:
+                out[torch.tensor(todo, dtype=torch.int64, device=self.device)] = res
+        return out
+
+    def _add_device_frames(self, frames, frame_ids, wav, name):
+        if len(frames) != len(frame_ids) or not len(frames):
+            raise ValueError("add_clip_files: need one frame id per frame")
+        for f in frames:
+            if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3 or not f.is_cuda or not f.is_contiguous():
+                raise ValueError("frames must be contiguous device uint8 [h, w, 3] (BGR), got %s %s on %s"
+                                 % (f.dtype, tuple(f.shape), f.device))
+        return self._append(self._resize_rows(frames), frame_ids, wav, name)
+
+    def add_clip_files(self, datas, frame_ids, wav, name=None):
+        """`add_clip` from the BYTES of the clip's `<id>.jpg` files: decoded on the device (`jpeg.decode_files`: UnsupportedJpeg
+        for a file outside the class it decodes, ValueError for a corrupt one), then every frame of the clip resized to 96x96
+        by one launch.  The rows are byte-equal to `add_clip` of the PIL-decoded frames.  Returns the clip index."""
+        from . import jpeg
+        if len(datas) != len(frame_ids) or not len(datas):
+            raise ValueError("add_clip_files: need one frame id per file")
+        with torch.cuda.device(self.device):
+            return self._add_device_frames(jpeg.decode_files(datas, self.device), frame_ids, wav, name)
+
+    DEVICE_BATCH_FILES = 4096            # caps of one decode launch of from_directory(decode="device"): files ...
+    DEVICE_BATCH_BYTES = 64 << 20        # ... bytes of files ...
+    DEVICE_BATCH_BLOCKS = 1 << 23        # ... and files x 8x8 blocks of the largest file (the workspace: 192 bytes each, 1.5 GiB)
+
     @classmethod
-    def from_directory(cls, data_root, split, device, filelist_dir="filelists"):
+    def from_directory(cls, data_root, split, device, filelist_dir="filelists", decode="host"):
         """the on-disk layout the reference trains from: `filelists/<split>.txt` names clip directories under `data_root`, each
-        holding `<id>.jpg` face crops and `audio.wav` (hparams.get_image_list, wav2lip_train.py:42,119,137)"""
+        holding `<id>.jpg` face crops and `audio.wav` (hparams.get_image_list, wav2lip_train.py:42,119,137).
+
+        decode="host" (default): every file is opened with PIL, uploaded and resized on its own.  decode="device": the files'
+        bytes are read and decoded on the device in batches that span clips - a batch is closed at DEVICE_BATCH_FILES = 4096 files,
+        at DEVICE_BATCH_BYTES = 64 MiB of files, or where the number of files times the 8x8 blocks of its largest file would
+        pass DEVICE_BATCH_BLOCKS = 2^23 (the launch's workspace is 192 bytes for each: 1.5 GiB), whichever comes first; a file
+        larger than that is a batch of its own - and the store holds the same bytes as with "host".  A file outside the class the
+        device decodes (`jpeg.probe` raises UnsupportedJpeg: progressive, not 4:2:0, restart intervals ...) goes through PIL,
+        alone, and is counted in `store.host_decoded`; a file whose stream is corrupt raises ValueError naming its path (PIL
+        raises OSError there)."""
         from PIL import Image
         from . import audio
+        if decode not in ("host", "device"):
+            raise ValueError("from_directory: decode must be 'host' or 'device', got %r" % (decode,))
         store = cls(device)
         with open(os.path.join(filelist_dir, "%s.txt" % split)) as fh:
             clips = [line.split()[0] for line in (l.strip() for l in fh) if line]
+        if decode == "device":
+            store._load_device(data_root, clips)
+            return store
         for rel in clips:
             d = os.path.join(data_root, rel)
             names = sorted((n for n in os.listdir(d) if n.endswith(".jpg")), key=lambda n: int(n.split(".")[0]))
@@ -92,6 +159,57 @@ class ClipStore:
             wav = audio.load_wav(os.path.join(d, "audio.wav"), hparams.sample_rate)
             store.add_clip(frames, [int(n.split(".")[0]) for n in names], wav, name=rel)
         return store
+
+    def _load_device(self, data_root, clips):
+        """from_directory(decode="device"): clips wait until the batch that holds their last file is decoded, and enter the store
+        in the filelist's order"""
+        from PIL import Image
+        from . import audio, jpeg
+        waiting = []                     # [rel, frame ids, paths, frames (None: in the open batch)]
+        batch = []                       # (clip entry, index in the clip, path, bytes, parsed info)
+        nbytes = max_blocks = 0
+
+        def flush():
+            nonlocal batch, nbytes, max_blocks
+            if batch:
+                imgs, st = jpeg._decode([b[3] for b in batch], [b[4] for b in batch], self.device)
+                if (st != 0).any():
+                    i = int(np.flatnonzero(st)[0])
+                    raise ValueError("%s is corrupt: %s (status %d)" % (batch[i][2], jpeg.STATUS_TEXT.get(int(st[i]), "?"), int(st[i])))
+                for (entry, k, _, _, _), img in zip(batch, imgs):
+                    entry[3][k] = img
+                batch, nbytes, max_blocks = [], 0, 0
+            while waiting and all(f is not None for f in waiting[0][3]):
+                rel, ids, _, frames = waiting.pop(0)
+                wav = audio.load_wav(os.path.join(data_root, rel, "audio.wav"), hparams.sample_rate)
+                self._add_device_frames(frames, ids, wav, rel)
+
+        with torch.cuda.device(self.device):
+            for rel in clips:
+                d = os.path.join(data_root, rel)
+                names = sorted((n for n in os.listdir(d) if n.endswith(".jpg")), key=lambda n: int(n.split(".")[0]))
+                entry = [rel, [int(n.split(".")[0]) for n in names], [os.path.join(d, n) for n in names], [None] * len(names)]
+                waiting.append(entry)
+                for k, path in enumerate(entry[2]):
+                    with open(path, "rb") as fh:
+                        data = fh.read()
+                    try:
+                        info = jpeg.parse(data)
+                    except jpeg.UnsupportedJpeg:
+                        img = np.asarray(Image.open(path).convert("RGB"))[:, :, ::-1]            # the host path, for this file alone
+                        entry[3][k] = torch.from_numpy(np.ascontiguousarray(img)).to(self.device)
+                        self.host_decoded += 1
+                        continue
+                    except ValueError as e:
+                        raise ValueError("%s: %s" % (path, e)) from None
+                    nb = jpeg.blocks(info.H, info.W)
+                    if batch and (len(batch) >= self.DEVICE_BATCH_FILES or nbytes + len(data) > self.DEVICE_BATCH_BYTES
+                                  or (len(batch) + 1) * max(max_blocks, nb) > self.DEVICE_BATCH_BLOCKS):
+                        flush()
+                    batch.append((entry, k, path, data, info))
+                    nbytes += len(data)
+                    max_blocks = max(max_blocks, nb)
+            flush()
 
     def frames(self):
         if self._frames is None:

@@ -10,6 +10,16 @@ Per batch: the row table (w2l_frame_row) and the slots' capacities are staged in
 run whatever the batch size is (on the current stream; CropEncoder's worker thread has a stream of its own), and two copies come
 back: the lengths, then the used part of the slots.  There is no host fallback: a CPU tensor or a missing library raises
 RuntimeError.
+
+The read side (w2l_jpeg_decode_rows, csrc/jpeg_decode.hip): baseline 4:2:0 files - what `preprocess` writes in either mode, and
+what cv2.imwrite wrote for the reference - are decoded on the device to the pixels PIL / libjpeg-turbo decodes, byte for byte.
+
+    probe(data)                  -> (H, W); UnsupportedJpeg with the parser's reason for a file outside that class
+    decode_files(datas, device)  -> list of device uint8 [H,W,3] BGR tensors, views of one buffer
+
+Per batch: the files' entropy-coded segments, the row table (w2l_jpeg_row) and the de-duplicated table sets are staged in ONE
+pinned buffer and copied in once, one memset and three kernels run on the current stream whatever the batch size is, and one copy
+of `status` comes back.  No host fallback here either.
 """
 import ctypes as C
 from concurrent.futures import ThreadPoolExecutor, wait
@@ -227,3 +237,115 @@ class CropEncoder:
                 self.pool.shutdown()
 
 
+# ---------------------------------------------------------------- decoding
+JPEG_ROW = np.dtype([("src", "<u8"), ("dst", "<u8"), ("nbytes", "<i4"), ("H", "<i4"), ("W", "<i4"), ("table", "<i4")])
+MALFORMED = -100                  # w2l_jpeg_parse: not a JPEG, or cut inside its header; the other reasons: outside the class
+STATUS_TEXT = {-1: "bits that are no code of the file's Huffman table", -2: "a zero run past coefficient 63",
+               -3: "a marker or left-over bytes before the end of the last MCU", -4: "the stream ends early",
+               -5: "a row the launch cannot take"}
+
+
+class UnsupportedJpeg(ValueError):
+    """a well-formed JPEG file outside the class the device decodes (progressive, 4:4:4, grayscale, restart intervals, ...);
+    `.code` is the parser's reason (W2L_JPEG_* of include/w2l_hip.h)"""
+
+    def __init__(self, msg, code):
+        super().__init__(msg)
+        self.code = code
+
+
+def parse(data):
+    """the _lib.JpegInfo of one file's bytes; UnsupportedJpeg for a file outside the class, plain ValueError for one that is no
+    JPEG or is cut inside its header"""
+    lib = _lib.load()
+    info = _lib.JpegInfo()
+    data = bytes(data)
+    rc = lib.w2l_jpeg_parse(data, len(data), C.byref(info))
+    if rc != 0:
+        msg = (lib.w2l_last_error() or b"?").decode()
+        if rc == MALFORMED or rc > MALFORMED:
+            raise ValueError(msg)
+        raise UnsupportedJpeg(msg, rc)
+    return info
+
+
+def probe(data):
+    """(H, W) of a file the device decodes; raises UnsupportedJpeg with the parser's reason otherwise"""
+    info = parse(data)
+    return info.H, info.W
+
+
+def _decode(datas, infos, device):
+    """(tensors, status int32 numpy [n]) of parsed files: one pinned buffer and one copy in, the kernels on the current stream,
+    one copy of status back.  tensors[i] is complete where status[i] == 0."""
+    import torch
+    lib = _lib.load()
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("jpeg: decode_files needs a HIP device (there is no host fallback), got %s" % device)
+    n = len(datas)
+    if n < 1 or n > MAX_ROWS:
+        raise ValueError("jpeg: %d files in one batch (1 .. %d)" % (n, MAX_ROWS))
+    tb = int(lib.w2l_jpeg_table_bytes())
+    sets, table = {}, np.zeros(n, JPEG_ROW)
+    for i, info in enumerate(infos):
+        key = C.string_at(C.addressof(info) + 20, C.sizeof(_lib.JpegInfo) - 20)    # nvals, quant, bits, vals
+        if key not in sets:
+            buf = (C.c_uint8 * tb)()
+            rc = lib.w2l_jpeg_build_tables(C.byref(info), buf)
+            if rc != 0:
+                raise ValueError("jpeg: file %d: %s" % (i, (lib.w2l_last_error() or b"?").decode()))
+            sets[key] = (len(sets), bytes(buf))
+        table[i] = (0, 0, info.ecs_bytes, info.H, info.W, sets[key][0])
+    max_blocks = int(max(blocks(h, w) for h, w in zip(table["H"], table["W"])))
+    if max_blocks > MAX_BLOCKS:
+        raise ValueError("jpeg: a file of %d blocks (at most %d)" % (max_blocks, MAX_BLOCKS))
+    rows_b = -(-table.nbytes // 16) * 16
+    tabs_b = tb * len(sets)                                                     # a multiple of 16
+    src_off = rows_b + tabs_b + np.concatenate([[0], np.cumsum(table["nbytes"].astype(np.int64))])
+    dst_off = np.concatenate([[0], np.cumsum(table["H"].astype(np.int64) * table["W"] * 3)])
+    with torch.cuda.device(device):
+        staged = torch.empty(int(src_off[-1]), dtype=torch.uint8, device=device)
+        out = torch.empty(int(dst_off[-1]), dtype=torch.uint8, device=device)
+        host = torch.empty(int(src_off[-1]), dtype=torch.uint8, pin_memory=True)
+        table["src"] = staged.data_ptr() + src_off[:-1]
+        table["dst"] = out.data_ptr() + dst_off[:-1]
+        h = host.numpy()
+        h[:table.nbytes] = table.view(np.uint8)
+        for idx, blob in sets.values():
+            h[rows_b + idx * tb:rows_b + (idx + 1) * tb] = np.frombuffer(blob, np.uint8)
+        for i, (d, info) in enumerate(zip(datas, infos)):
+            h[src_off[i]:src_off[i + 1]] = np.frombuffer(d, np.uint8, info.ecs_bytes, info.ecs_offset)
+        staged.copy_(host, non_blocking=True)                                   # one copy in
+        ws_bytes = int(lib.w2l_jpeg_decode_workspace_bytes(n, max_blocks))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+        status = torch.empty(n, dtype=torch.int32, device=device)
+        _lib.check(lib.w2l_jpeg_decode_rows(_lib.current_stream(), n, _lib.ptr(staged), C.c_void_p(staged.data_ptr() + rows_b), len(sets),
+                                            max_blocks, _lib.ptr(status), _lib.ptr(ws), ws_bytes), "jpeg_decode_rows")
+        st = status.cpu().numpy()                                               # one copy back (waits for the kernels)
+    imgs = [out[int(dst_off[i]):int(dst_off[i + 1])].view(int(table["H"][i]), int(table["W"][i]), 3) for i in range(n)]
+    return imgs, st
+
+
+def decode_files(datas, device):
+    """The images of JPEG files given as bytes: a list of device uint8 [H,W,3] BGR tensors (cv2.imread's order), views of one
+    buffer, byte-equal to `np.asarray(Image.open(BytesIO(d)).convert("RGB"))[:, :, ::-1]`.  Runs on the current stream of `device`.
+    UnsupportedJpeg (from `probe`'s parser) for a file outside the class the device decodes, ValueError naming the index and the
+    reason for a file whose stream the kernel refuses; RuntimeError for a CPU device."""
+    import torch
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("jpeg: decode_files needs a HIP device (there is no host fallback), got %s" % (device,))
+    datas = [bytes(d) for d in datas]
+    infos = []
+    for i, d in enumerate(datas):
+        try:
+            infos.append(parse(d))
+        except UnsupportedJpeg as e:
+            raise UnsupportedJpeg("jpeg: file %d: %s" % (i, e), e.code) from None
+        except ValueError as e:
+            raise ValueError("jpeg: file %d: %s" % (i, e)) from None
+    imgs, st = _decode(datas, infos, device)
+    if (st != 0).any():
+        i = int(np.flatnonzero(st)[0])
+        raise ValueError("jpeg: file %d is corrupt: %s (status %d)" % (i, STATUS_TEXT.get(int(st[i]), "?"), int(st[i])))
+    return imgs

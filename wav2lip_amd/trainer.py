@@ -348,9 +348,14 @@ def _loader_rng(ranks):
 
 
 def _loaders(data_root, device, batch_size, kind, rng=None):
+    """W2L_JPEG_DECODE=device decodes the `<id>.jpg` crops on the device (ClipStore.from_directory's `decode`; default host: PIL);
+    the parsers mirror the reference's flags, so this is an environment variable like W2L_DATA_SEED"""
     from .data import ClipStore
-    train_store = ClipStore.from_directory(data_root, 'train', device)
-    val_store = ClipStore.from_directory(data_root, 'val', device)
+    decode = os.environ.get("W2L_JPEG_DECODE", "host")
+    if decode not in ("host", "device"):
+        raise ValueError("W2L_JPEG_DECODE must be 'host' or 'device', got %r" % decode)
+    train_store = ClipStore.from_directory(data_root, 'train', device, decode=decode)
+    val_store = ClipStore.from_directory(data_root, 'val', device, decode=decode)
     return ClipLoader(train_store, batch_size, kind, rng=rng), ClipLoader(val_store, batch_size, kind, rng=rng)
 
 
