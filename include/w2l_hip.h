@@ -29,6 +29,10 @@
  *                         cap and of rescale_frames, one frame per row)
  *   w2l_jpeg_encode_rows  preprocess.py:62 (cv2.imwrite of every face crop as <i>.jpg), one crop per row
  *   w2l_jpeg_decode_rows  wav2lip_train.py:66, color_syncnet_train.py:97 (cv2.imread of every <id>.jpg), one file per row
+ *   w2l_jpeg_encode_rows_rst  inference.py:256-257,272 (cv2.VideoWriter + out.write(f): the compressed result video; here Motion-JPEG,
+ *                         every frame a JPEG with restart intervals), one frame per row
+ *   w2l_jpeg_decode_rows_rst  inference.py:189-215 (cv2.VideoCapture(args.face) ... video_stream.read()) for a Motion-JPEG video,
+ *                         one lane per restart interval
  *   w2l_mel_gather_rows   evaluation/gen_videos_from_filelist.py:176-183 (mel windows, one spectrogram per row)
  *   w2l_s3fd_pack_rows    face_detection/api.py:62 + detection/sfd/detect.py:57-63 (the detector's input), one frame per row
  *   w2l_s3fd_pack_rows_scaled  inference.py:202-203 (the `cv2.resize(frame, (w // k, h // k))` of --resize_factor) fused into the
@@ -279,6 +283,27 @@ size_t w2l_jpeg_workspace_bytes(int B, int max_blocks);
 /* host only: the 623 header bytes of an h x w file at `quality` into out[623] (what the kernel copies and patches the size into) */
 int w2l_jpeg_header(int h, int w, int quality, uint8_t* out);
 
+/* w2l_jpeg_encode_rows with restart intervals: the frames of a Motion-JPEG stream (inference.py:256-257 `cv2.VideoWriter(...)`,
+ * :272 `out.write(f)`: the reference's compressed result video), each frame coded in independent byte-aligned pieces so that a
+ * decoder need not walk it serially.  Same arguments, rows and properties as w2l_jpeg_encode_rows; restart_rows >= 1 is libjpeg's
+ * restart_in_rows (PIL.Image.save(..., restart_marker_rows=restart_rows)) and the files are byte-equal to libjpeg's:
+ *   - 629 header bytes: the 623 of w2l_jpeg_header with DRI (FF DD 00 04 Ri) at offset 609, between the last DHT and SOS;
+ *     Ri = min(restart_rows * ceil(w / 16), 65535) MCUs
+ *   - at the end of every interval but the last (jchuff.c emit_restart): the last byte filled up with 1 bits, byte stuffing applied
+ *     to that byte too (FF becomes FF 00), the marker FF D0+(k mod 8) for interval k, and the three DC predictions back to 0
+ *   - dummy blocks keep jccoefct.c's rule inside their MCU; behind the last interval the padding and EOI, no marker.
+ * No file can exceed 631 + 416 * blocks + 4 * intervals bytes (intervals = ceil(MCUs / Ri): a padding byte, its stuffed 00 and
+ * the marker each; w2l_jpeg_capacity_rst).  workspace: at least w2l_jpeg_workspace_bytes_rst(B, max_blocks) bytes.  Two kernel
+ * launches per call, whatever B is.  Refused as w2l_jpeg_encode_rows refuses, and restart_rows < 1. */
+int w2l_jpeg_encode_rows_rst(void* stream, int B, const w2l_frame_row* rows, const int32_t* cap, int quality, int max_blocks,
+                             int restart_rows, int32_t* lengths, void* workspace, size_t workspace_bytes);
+/* 0 for B outside [1, 65535] or max_blocks outside [1, 2^20] */
+size_t w2l_jpeg_workspace_bytes_rst(int B, int max_blocks);
+/* host only: bytes no file of an h x w image at restart_rows can exceed; 0 for sizes outside [1, 65535] or restart_rows < 1 */
+size_t w2l_jpeg_capacity_rst(int h, int w, int restart_rows);
+/* host only: the 629 header bytes of an h x w file at `quality` and restart_rows into out[629] */
+int w2l_jpeg_header_rst(int h, int w, int quality, int restart_rows, uint8_t* out);
+
 /* Row-table JPEG DECODING of face crops (wav2lip_train.py:66 / color_syncnet_train.py:97 `cv2.imread(fname)` of every <id>.jpg):
  * the read side of w2l_jpeg_encode_rows.  The pixels are byte-equal to what libjpeg(-turbo) decodes with its defaults (PIL's
  * Image.open(...).convert("RGB"), cv2.imread): jpeg_idct_islow, h2v2 "fancy" chroma upsampling (plain 2x2 replication for images of 1 to 4 columns, as
@@ -356,6 +381,48 @@ int w2l_jpeg_decode_rows(void* stream, int B, const w2l_jpeg_row* rows, const vo
                          int32_t* status, void* workspace, size_t workspace_bytes);
 /* 0 for B outside [1, 65535] or max_blocks outside [1, 2^20] */
 size_t w2l_jpeg_decode_workspace_bytes(int B, int max_blocks);
+
+/* Decoding of files WITH restart intervals: the frames of a Motion-JPEG video (inference.py:189-215, `cv2.VideoCapture(args.face)`
+ * ... `video_stream.read()`, for a compressed --face video) and what w2l_jpeg_encode_rows_rst writes.
+ *
+ * w2l_jpeg_parse_rst (host only): w2l_jpeg_parse for the same class plus a restart interval: *restart_interval is the DRI value
+ * in MCUs (0: none).  ecs_offset / ecs_bytes cover the whole scan, RSTn markers included.
+ *
+ * w2l_jpeg_restart_segments (host only): the intervals of an entropy-coded segment `ecs` of n_mcus = ceil(H / 16) * ceil(W / 16)
+ * MCUs at interval ri.  A data byte FF is always followed by 00, so FF D0..D7 is a marker and one linear pass is exact.  Writes at
+ * most `cap` records into `out` (row = 0; offset / nbytes relative to ecs, markers excluded; first_mcu = k * ri) and returns the
+ * number of intervals ceil(n_mcus / ri) >= 1, or W2L_JPEG_MALFORMED with w2l_last_error() set: not exactly ceil(n_mcus / ri) - 1
+ * markers, marker k not RST(k mod 8), or another marker.  ri = 0: one record covering ecs.  Never reads ecs[ecs_bytes] or beyond.
+ *
+ * w2l_jpeg_segment, 32 bytes, alignment 16:
+ *   bytes  0 ..  3  row (int32)        index of the record's row in `rows`
+ *   bytes  4 ..  7  offset (int32)     first byte of the interval, relative to the row's src
+ *   bytes  8 .. 11  nbytes (int32)     its bytes (the marker behind it excluded)
+ *   bytes 12 .. 15  first_mcu (int32)  the first MCU it codes, in raster order
+ *   bytes 16 .. 19  n_mcus (int32)     how many
+ *   bytes 20 .. 31  0
+ *
+ * w2l_jpeg_decode_rows_rst: w2l_jpeg_decode_rows with the entropy pass split over `segments` (device, n_segments records, 16-byte
+ * aligned): ONE LANE PER SEGMENT, the lanes of a wave taking consecutive records; a segment starts with its DC predictions at 0
+ * and writes the coefficients of its own MCUs only.  A file without restarts is one segment of all its MCUs, so both kinds share
+ * a launch.  The inverse DCT and the colour kernel are those of w2l_jpeg_decode_rows.  PRECONDITION (the host caller's, as
+ * w2l_jpeg_restart_segments delivers it): the segments of a row do not overlap.
+ * status[b]: 0 and the image complete, or the MINIMUM (the most negative) of the reasons of the row's segments (the codes of
+ * w2l_jpeg_decode_rows; -5 also for a record whose row, offset, nbytes or MCU range lies outside its row) - a rule that does not
+ * depend on the order in which segments finish; a row whose good segments do not add up to its MCUs gets -5.  Every read of a
+ * stream is bounded by the segment's bytes inside the row's nbytes; a bad segment leaves other rows intact.
+ * Two memsets and four launches per call, whatever B and n_segments are.  workspace: w2l_jpeg_decode_workspace_bytes_rst(B,
+ * max_blocks) bytes.  Refused as w2l_jpeg_decode_rows refuses, and n_segments outside [1, 2^24] or a misaligned table. */
+typedef struct {
+    int32_t row, offset, nbytes, first_mcu, n_mcus;
+    int32_t pad[3];
+} w2l_jpeg_segment;
+int w2l_jpeg_parse_rst(const uint8_t* data, size_t n, w2l_jpeg_info* info, int32_t* restart_interval);
+int w2l_jpeg_restart_segments(const uint8_t* ecs, size_t ecs_bytes, int restart_interval, int n_mcus, w2l_jpeg_segment* out, int cap);
+int w2l_jpeg_decode_rows_rst(void* stream, int B, const w2l_jpeg_row* rows, const void* tables, int n_tables, int max_blocks,
+                             const w2l_jpeg_segment* segments, int n_segments, int32_t* status, void* workspace,
+                             size_t workspace_bytes);
+size_t w2l_jpeg_decode_workspace_bytes_rst(int B, int max_blocks);
 
 /* ---------------------------------------------------------------- S3FD face detector glue (face_detection/detection/sfd/)
  * The detector's convolutions are w2l_conv_* layers (bias + ReLU, no BatchNorm); these are the ops between them. */

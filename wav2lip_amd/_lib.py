@@ -131,6 +131,14 @@ SIGNATURES = {
     "w2l_jpeg_build_tables": (_i, [C.POINTER(JpegInfo), _vp]),
     "w2l_jpeg_decode_rows": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, C.c_size_t]),
     "w2l_jpeg_decode_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "w2l_jpeg_encode_rows_rst": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, C.c_size_t]),
+    "w2l_jpeg_workspace_bytes_rst": (C.c_size_t, [_i, _i]),
+    "w2l_jpeg_capacity_rst": (C.c_size_t, [_i, _i, _i]),
+    "w2l_jpeg_header_rst": (_i, [_i, _i, _i, _i, _vp]),
+    "w2l_jpeg_parse_rst": (_i, [C.c_char_p, C.c_size_t, C.POINTER(JpegInfo), C.POINTER(C.c_int32)]),
+    "w2l_jpeg_restart_segments": (_i, [_vp, C.c_size_t, _i, _i, _vp, _i]),
+    "w2l_jpeg_decode_rows_rst": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, C.c_size_t]),
+    "w2l_jpeg_decode_workspace_bytes_rst": (C.c_size_t, [_i, _i]),
     "w2l_s3fd_pack": (_i, [_vp, _ll, _vp, _vp, _i]),
     "w2l_s3fd_pack_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _i]),
     "w2l_s3fd_pack_rows_scaled": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i]),

@@ -8,7 +8,12 @@ the pixels the generator produced.  The audio stream is PCM16, interleaved with 
 :276-277 becomes part of the same file.  `read_avi` reads the files written here (and any BI_RGB-24 / PCM16 AVI), which also gives
 the `--face <video>` side (inference.py:189-215, `cv2.VideoCapture`) an input format that works offline.
 
-Host-side byte shuffling only: the frames are already uint8 BGR in host memory when they reach the writer (the paste-back kernel
+`codec="mjpg"` (opt-in) writes and `read_avi` reads the standard Motion-JPEG stream instead ('MJPG' handler and biCompression, one
+JPEG file per '00dc' chunk, every chunk a keyframe: what `cv2.VideoWriter_fourcc(*'MJPG')` writes): the frames come finished from
+the device encoder (`write_jpeg(jpeg.encode_frames(...))`) or, for a host array, through PIL with the same quality, 4:2:0 and
+restart interval - the same bytes; `read_avi(path, device=)` decodes them on the device (jpeg.decode_frames).
+
+Otherwise host-side byte shuffling only: the frames are already uint8 BGR in host memory when they reach the writer (the paste-back kernel
 w2l_resize_paste_u8 wrote them); nothing here is on the GPU path.  Limits: RIFF sizes are 32-bit (files below 4 GiB; the OpenDML
 extension is not written), BI_RGB 24-bit video, PCM16 audio.
 """
@@ -19,6 +24,36 @@ import numpy as np
 _AVIF_HASINDEX, _AVIF_ISINTERLEAVED = 0x10, 0x100
 _AVIIF_KEYFRAME = 0x10
 _MAX_RIFF = (1 << 32) - (1 << 20)
+_MJPG = struct.unpack("<I", b"MJPG")[0]
+
+
+def encode_jpeg_host(frame, quality=95, restart_rows=1):
+    """one uint8 [H,W,3] BGR frame as the JPEG file of a Motion-JPEG stream, on the host: PIL / libjpeg-turbo at 4:2:0 with a
+    restart interval of `restart_rows` MCU rows - the bytes jpeg.encode_frames writes on the device"""
+    import io
+    from PIL import Image
+    buf = io.BytesIO()
+    Image.fromarray(np.ascontiguousarray(frame[:, :, ::-1])).save(buf, format="JPEG", quality=int(quality), subsampling=2,
+                                                                  restart_marker_rows=int(restart_rows))
+    return buf.getvalue()
+
+
+def decode_jpeg_host(data):
+    """uint8 [H,W,3] BGR of any JPEG file PIL reads"""
+    import io
+    from PIL import Image
+    return np.ascontiguousarray(np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))[:, :, ::-1])
+
+
+def _jpeg_size(data):
+    """(width, height) of a JPEG file's SOF segment, None where there is none"""
+    import io
+    from PIL import Image
+    try:
+        im = Image.open(io.BytesIO(data))
+        return im.size if im.format == "JPEG" else None
+    except Exception:
+        return None
 
 
 def _fps_rational(fps):
@@ -47,10 +82,16 @@ class AviWriter:
     Frames stream to disk as they arrive; the headers and the index are completed by `release()`.  Unlike cv2 (which drops a frame
     of the wrong size silently) a mismatching frame is an error."""
 
-    def __init__(self, path, fps, frame_size, audio=None, audio_sr=16000):
+    def __init__(self, path, fps, frame_size, audio=None, audio_sr=16000, codec="raw", quality=95, restart_rows=1):
         self.w, self.h = int(frame_size[0]), int(frame_size[1])
         if self.w <= 0 or self.h <= 0:
             raise ValueError("bad frame size %r" % (frame_size,))
+        if codec not in ("raw", "mjpg"):
+            raise ValueError("codec must be 'raw' or 'mjpg' (got %r)" % (codec,))
+        if codec == "mjpg" and not (1 <= int(quality) <= 100 and int(restart_rows) >= 1):
+            raise ValueError("mjpg: quality in [1, 100] and restart_rows >= 1 (got %r, %r)" % (quality, restart_rows))
+        self.codec, self.quality, self.restart_rows = codec, int(quality), int(restart_rows)
+        self.max_chunk, self.video_bytes = 0, 0            # mjpg: the largest frame and the sum, for the headers release() writes
         self.rate, self.scale = _fps_rational(fps)
         self.stride = (self.w * 3 + 3) & ~3                # DIB rows are padded to 4 bytes
         self.frame_bytes = self.stride * self.h
@@ -75,13 +116,21 @@ class AviWriter:
     def _headers(self, n_frames, movi_bytes):
         n_streams = 2 if self.audio is not None else 1
         audio_rate = self.audio_sr * self.block_align if self.audio is not None else 0
+        if self.codec == "mjpg":
+            # what cv2.VideoWriter(fourcc 'MJPG') / ffmpeg write: handler and biCompression 'MJPG', 24 bits, positive height (the
+            # JPEG itself is top-down); buffer sizes = the largest frame, the byte rate = what was written per second of video
+            handler, compression, frame_bytes = b"MJPG", _MJPG, self.max_chunk
+            video_rate = self.video_bytes * self.rate // (self.scale * n_frames) if n_frames else 0
+        else:
+            handler, compression, frame_bytes = b"DIB ", 0, self.frame_bytes
+            video_rate = self.frame_bytes * self.rate // self.scale
         avih = struct.pack("<14I", int(round(1e6 * self.scale / self.rate)),            # dwMicroSecPerFrame
-                           self.frame_bytes * self.rate // self.scale + audio_rate,     # dwMaxBytesPerSec
+                           video_rate + audio_rate,                                     # dwMaxBytesPerSec
                            0, _AVIF_HASINDEX | (_AVIF_ISINTERLEAVED if n_streams == 2 else 0), n_frames, 0, n_streams,
-                           self.frame_bytes, self.w, self.h, 0, 0, 0, 0)
-        strh_v = struct.pack("<4s4sIHHIIIIIIII4h", b"vids", b"DIB ", 0, 0, 0, 0, self.scale, self.rate, 0, n_frames,
-                             self.frame_bytes, 0xFFFFFFFF, 0, 0, 0, self.w, self.h)
-        strf_v = struct.pack("<IiiHHIIiiII", 40, self.w, self.h, 1, 24, 0, self.frame_bytes, 0, 0, 0, 0)   # BITMAPINFOHEADER, bottom-up
+                           frame_bytes, self.w, self.h, 0, 0, 0, 0)
+        strh_v = struct.pack("<4s4sIHHIIIIIIII4h", b"vids", handler, 0, 0, 0, 0, self.scale, self.rate, 0, n_frames,
+                             frame_bytes, 0xFFFFFFFF, 0, 0, 0, self.w, self.h)
+        strf_v = struct.pack("<IiiHHIIiiII", 40, self.w, self.h, 1, 24, compression, frame_bytes, 0, 0, 0, 0)   # BITMAPINFOHEADER, bottom-up
         hdrl = _chunk(b"avih", avih) + _list(b"strl", _chunk(b"strh", strh_v) + _chunk(b"strf", strf_v))
         if self.audio is not None:
             n_samples = self.audio.shape[0]
@@ -111,12 +160,32 @@ class AviWriter:
         frame = np.asarray(frame)
         if frame.dtype != np.uint8 or frame.shape != (self.h, self.w, 3):
             raise ValueError("frame must be uint8 [%d, %d, 3], got %s %s" % (self.h, self.w, frame.dtype, frame.shape))
+        if self.codec == "mjpg":                           # the host path: the bytes jpeg.encode_frames gives for the same pixels
+            return self.write_jpeg(encode_jpeg_host(frame, self.quality, self.restart_rows))
         rows = frame[::-1].reshape(self.h, self.w * 3)     # DIBs are stored bottom-up; BGR order is the DIB order already
         if self.stride != self.w * 3:
             padded = np.zeros((self.h, self.stride), dtype=np.uint8)
             padded[:, :self.w * 3] = rows
             rows = padded
         self._emit(b"00db", np.ascontiguousarray(rows).tobytes())
+        self._frame_done()
+
+    def write_jpeg(self, data):
+        """mjpg: one finished JPEG file (jpeg.encode_frames', or any encoder's) as the next frame"""
+        if self.released:
+            raise ValueError("write_jpeg() after release()")
+        if self.codec != "mjpg":
+            raise ValueError("write_jpeg() needs codec='mjpg' (this stream is %r)" % self.codec)
+        data = bytes(data)
+        size = _jpeg_size(data)
+        if size != (self.w, self.h):
+            raise ValueError("JPEG frame of %s, the stream is %dx%d (width x height)" % ("%dx%d" % size if size else "no readable size", self.w, self.h))
+        self._emit(b"00dc", data)
+        self.max_chunk = max(self.max_chunk, len(data))
+        self.video_bytes += len(data)
+        self._frame_done()
+
+    def _frame_done(self):
         self.n_frames += 1
         if self.audio is not None:                          # this frame's share of the audio, cut on sample boundaries
             end = min(self.audio.shape[0], (self.n_frames * self.audio_sr * self.scale) // self.rate)
@@ -148,13 +217,13 @@ class AviWriter:
         self.release()
 
 
-def write_avi(path, frames, fps, audio=None, audio_sr=16000):
-    """all frames at once: `frames` uint8 [T, H, W, 3] BGR (or a list of [H, W, 3])"""
+def write_avi(path, frames, fps, audio=None, audio_sr=16000, codec="raw", quality=95, restart_rows=1):
+    """all frames at once: `frames` uint8 [T, H, W, 3] BGR (or a list of [H, W, 3]); codec / quality / restart_rows as AviWriter's"""
     frames = list(frames)
     if not frames:
         raise ValueError("no frames to write")
     h, w = np.asarray(frames[0]).shape[:2]
-    with AviWriter(path, fps, (w, h), audio=audio, audio_sr=audio_sr) as out:
+    with AviWriter(path, fps, (w, h), audio=audio, audio_sr=audio_sr, codec=codec, quality=quality, restart_rows=restart_rows) as out:
         for f in frames:
             out.write(f)
 
@@ -181,9 +250,53 @@ def _walk(buf, start, end):
         pos += 8 + size + (size & 1)
 
 
-def read_avi(path):
+def _decode_mjpg(path, chunks, w, h, device):
+    """the frames of an MJPG stream.  device None: every chunk through PIL, a numpy array.  Otherwise the chunks of the class
+    jpeg.decode_frames takes are decoded on the device in batches, a chunk outside it (progressive, 4:4:4 ...) goes through PIL
+    alone and is uploaded, and the result is a device tensor."""
+    def host(k):
+        try:
+            img = decode_jpeg_host(chunks[k])
+        except Exception as e:
+            raise ValueError("%s: video frame %d is no JPEG file PIL reads (%s)" % (path, k, e)) from None
+        if img.shape != (h, w, 3):
+            raise ValueError("%s: video frame %d is %dx%d, the stream is %dx%d" % (path, k, img.shape[1], img.shape[0], w, h))
+        return img
+
+    if device is None:
+        return np.stack([host(k) for k in range(len(chunks))]) if chunks else np.zeros((0, h, w, 3), np.uint8)
+    import torch
+    from . import jpeg
+    out = torch.empty((len(chunks), h, w, 3), dtype=torch.uint8, device=device)
+    on_device = []
+    for k, d in enumerate(chunks):
+        try:
+            info, _ = jpeg.parse_frame(d)
+        except jpeg.UnsupportedJpeg:
+            out[k] = torch.from_numpy(host(k)).to(device)
+            continue
+        except ValueError as e:
+            raise ValueError("%s: video frame %d is corrupt: %s" % (path, k, e)) from None
+        if (info.W, info.H) != (w, h):
+            raise ValueError("%s: video frame %d is %dx%d, the stream is %dx%d" % (path, k, info.W, info.H, w, h))
+        on_device.append(k)
+    per = max(1, min(256, (128 << 20) // (h * w * 3)))               # frames per launch: about 128 MiB of pixels
+    for i in range(0, len(on_device), per):
+        ks = on_device[i:i + per]
+        try:
+            imgs = jpeg.decode_frames([chunks[k] for k in ks], device)
+        except jpeg.CorruptJpeg as e:
+            raise ValueError("%s: video frame %d is corrupt: %s" % (path, ks[e.index], e)) from None
+        for k, img in zip(ks, imgs):
+            out[k] = img
+    return out
+
+
+def read_avi(path, device=None):
     """-> dict(frames uint8 [T,H,W,3] BGR top-down, fps, audio int16 [n, channels] or None, audio_sr).  Reads uncompressed
-    24-bit video and PCM16 audio (the subset AviWriter produces); anything else is an error, not a guess."""
+    24-bit video or Motion-JPEG ('MJPG': what AviWriter(codec="mjpg"), cv2.VideoWriter and ffmpeg write) and PCM16 audio;
+    anything else is an error, not a guess.  device None: `frames` is a numpy array (MJPG frames through PIL); a HIP device:
+    `frames` is a uint8 tensor there, MJPG frames decoded by jpeg.decode_frames."""
     with open(path, "rb") as f:
         buf = memoryview(f.read())
     if len(buf) < 12 or bytes(buf[:4]) != b"RIFF" or bytes(buf[8:12]) != b"AVI ":
@@ -212,8 +325,9 @@ def read_avi(path):
         raise ValueError("%s: no video stream" % path)
     vs = streams[vid[0]]
     _, w, h, _, bits, comp = struct.unpack_from("<IiiHHI", vs["strf"], 0)
-    if comp != 0 or bits != 24:
-        raise ValueError("%s: only uncompressed 24-bit video is supported (compression %#x, %d bits)" % (path, comp, bits))
+    mjpg = comp == _MJPG
+    if (comp != 0 and not mjpg) or bits != 24:
+        raise ValueError("%s: only uncompressed or Motion-JPEG 24-bit video is supported (compression %#x, %d bits)" % (path, comp, bits))
     top_down = h < 0
     h = abs(h)
     stride = (w * 3 + 3) & ~3
@@ -221,14 +335,25 @@ def read_avi(path):
     frames, pcm = [], []
     for cc, off, size in _walk(buf, movi[0], movi[1]):
         if cc == vtag or cc == vtag[:2] + b"dc":
+            if mjpg:
+                if size:                                    # (an empty chunk is a dropped frame in files other writers made)
+                    frames.append(bytes(buf[off:off + size]))
+                continue
             if size != stride * h:
                 raise ValueError("%s: video chunk of %d bytes, expected %d" % (path, size, stride * h))
             rows = np.frombuffer(buf, dtype=np.uint8, count=size, offset=off).reshape(h, stride)[:, :w * 3].reshape(h, w, 3)
             frames.append(rows if top_down else rows[::-1])
         elif atag is not None and cc == atag:
             pcm.append(np.frombuffer(buf, dtype=np.uint8, count=size, offset=off))
-    out = {"frames": np.ascontiguousarray(np.stack(frames)) if frames else np.zeros((0, h, w, 3), np.uint8),
-           "fps": vs["rate"] / float(vs["scale"]), "audio": None, "audio_sr": None}
+    if mjpg:
+        video = _decode_mjpg(path, frames, w, h, device)
+    else:
+        video = np.ascontiguousarray(np.stack(frames)) if frames else np.zeros((0, h, w, 3), np.uint8)
+        if device is not None:
+            import torch
+            video = torch.from_numpy(video).to(device)
+    out = {"frames": video,
+           "fps":vs["rate"] / float(vs["scale"]), "audio": None, "audio_sr": None}
     if aud:
         fmt, ch, sr, _, _, bps = struct.unpack_from("<HHIIHH", streams[aud[0]]["strf"], 0)
         if fmt != 1 or bps != 16:

@@ -101,7 +101,8 @@ void huff_codes(const uint8_t bits[16], const uint8_t* vals, uint32_t* out, int 
 }
 
 // SOI, APP0 (JFIF 1.1, no units, 1x1), DQT luma, DQT chroma, SOF0 (Y 2x2 table 0; Cb, Cr 1x1 table 1), DHT DC0 AC0 DC1 AC1, SOS
-int build_header(int h, int w, int quality, uint8_t* out) {
+// ri > 0: DRI (restart interval of ri MCUs) between the last DHT and SOS, where jcmarker.c write_scan_header puts it
+int build_header(int h, int w, int quality, uint8_t* out, int ri = 0) {
     uint8_t* p = out;
     auto put = [&](std::initializer_list<int> v) { for (int b : v) *p++ = (uint8_t)b; };
     put({0xFF, 0xD8});
@@ -121,12 +122,17 @@ int build_header(int h, int w, int quality, uint8_t* out) {
         for (int i = 0; i < 16; ++i) *p++ = kAcBits[t][i];
         for (int i = 0; i < 162; ++i) *p++ = kAcVals[t][i];
     }
+    if (ri > 0) put({0xFF, 0xDD, 0, 4, ri >> 8, ri & 255});
     put({0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
     return (int)(p - out);
 }
 
 size_t row_coef_bytes(int max_blocks) { return (size_t)max_blocks * kBlockBytes; }
 size_t row_stage_bytes(int max_blocks) { return (size_t)max_blocks * kBlockStreamBytes + 16; }   // + the word behind the last bit
+// the restart form: every interval (at most one per MCU) adds less than a byte of padding to the staged stream, and the staged
+// byte offsets at which the intervals end follow it, one uint32 each
+size_t row_stage_bytes_rst(int max_blocks) { return (row_stage_bytes(max_blocks) + (size_t)max_blocks / 6 + 1 + 15) & ~(size_t)15; }
+size_t row_ends_bytes_rst(int max_blocks) { return (((size_t)max_blocks / 6 + 1) * 4 + 15) & ~(size_t)15; }
 
 // ---- device side
 
@@ -481,6 +487,198 @@ __global__ __launch_bounds__(kThreads) void jpeg_entropy_kernel(const FrameRow* 
     }
 }
 
+// ---- the restart form (w2l_jpeg_encode_rows_rst): the same scheme with byte-aligned intervals in the staging stream.
+// Interval k holds MCUs [k * ri, (k + 1) * ri); its last block is followed by 1 bits up to the byte boundary (the last interval's
+// too: that is the end of the stream), its first MCU predicts its DCs from 0.  Where the intervals end in the staged bytes goes into
+// ends[]; the stuffing pass, which treats the padded bytes like any other, shifts each byte by 2 per marker in front of it and
+// writes the marker FF D0+(k mod 8) behind the last byte of interval k < n_int - 1.
+constexpr int kHeaderBytesRst = kHeaderBytes + 6;
+
+struct EntropyTablesRst {
+    uint32_t dc[2][16];
+    uint32_t ac[2][256];
+    uint8_t header[632];    // of a 1x1 file with Ri = 1: size and Ri are patched per row
+};
+
+__device__ __forceinline__ int restart_mcus(const CropGeom& g, int restart_rows) {
+    const long long ri = (long long)restart_rows * g.mw;
+    return ri > 65535 ? 65535 : (int)ri;
+}
+
+__device__ __forceinline__ int pred_dc_rst(const int16_t* __restrict__ coef, const CropGeom& g, int id, int ri) {
+    const int mcu = id / 6, k = id - mcu * 6;
+    const bool first = mcu % ri == 0;
+    if (k >= 4) return first ? 0 : coef[(size_t)(id - 6) * 64];
+    if (k > 0) return coded_dc(coef, g, id - 1);
+    return first ? 0 : coded_dc(coef, g, id - 3);
+}
+
+// What a run of blocks adds to the staged stream.  cut = 0: `head` bits and no interval end.  cut = 1: `head` bits up to the run's
+// first interval end, `mid` BYTES from there to its last interval end (whole intervals, each padded), `tail` bits behind it.
+struct RunBits {
+    unsigned cut, head, mid, tail;
+};
+__device__ __forceinline__ RunBits run_join(const RunBits& a, const RunBits& b) {       // a, then b: associative
+    if (!b.cut) return a.cut ? RunBits{1u, a.head, a.mid, a.tail + b.head} : RunBits{0u, a.head + b.head, 0u, 0u};
+    if (!a.cut) return RunBits{1u, a.head + b.head, b.mid, b.tail};
+    return RunBits{1u, a.head, a.mid + ((a.tail + b.head + 7u) >> 3) + b.mid, b.tail};
+}
+// the bit at which the stream stands behind a prefix of runs that began at bit 0
+__device__ __forceinline__ unsigned run_end_bit(const RunBits& p) { return p.cut ? 8u * (((p.head + 7u) >> 3) + p.mid) + p.tail : p.head; }
+
+struct BitSinkAt : BitSink {        // a BitSink that knows the bit it stands at
+    unsigned at;
+    __device__ __forceinline__ void put(unsigned code, int len) {
+        BitSink::put(code, len);
+        at += (unsigned)len;
+    }
+};
+
+__global__ __launch_bounds__(kThreads) void jpeg_entropy_rst_kernel(const FrameRow* __restrict__ rows, const int32_t* __restrict__ cap,
+                                                                    int max_blocks, int restart_rows, int32_t* __restrict__ lengths,
+                                                                    uint8_t* __restrict__ ws, size_t row_stride, size_t stage_off,
+                                                                    size_t ends_off, const EntropyTablesRst tab) {
+    __shared__ unsigned sh[kThreads];
+    __shared__ RunBits runs[kThreads];
+    __shared__ uint32_t dct[2][16];
+    __shared__ uint32_t act[2][256];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const FrameRow r = rows[b];
+    const CropGeom g = crop_geom(r);
+    const int room = cap[b];
+    if (!crop_ok(g, max_blocks) || room < kHeaderBytesRst + 2) {           // uniform over the workgroup
+        if (t == 0) lengths[b] = -1;
+        return;
+    }
+    for (int i = t; i < 32; i += kThreads) dct[i >> 4][i & 15] = tab.dc[i >> 4][i & 15];
+    for (int i = t; i < 512; i += kThreads) act[i >> 8][i & 255] = tab.ac[i >> 8][i & 255];
+    __syncthreads();
+
+    const int16_t* coef = reinterpret_cast<const int16_t*>(ws + b * row_stride);
+    uint32_t* stage = reinterpret_cast<uint32_t*>(ws + b * row_stride + stage_off);
+    uint32_t* ends = reinterpret_cast<uint32_t*>(ws + b * row_stride + ends_off);
+    const int ri = restart_mcus(g, restart_rows), n_mcus = g.nblocks / 6;
+    const int n_int = (n_mcus + ri - 1) / ri;                              // <= max_blocks / 6: ends[] holds them
+    // thread t owns blocks [lo, hi)
+    const int per = (g.nblocks + kThreads - 1) / kThreads;
+    const int lo = min(t * per, g.nblocks), hi = min(lo + per, g.nblocks);
+
+    RunBits mine{0u, 0u, 0u, 0u};
+    for (int id = lo; id < hi; ++id) {
+        const int c = (id % 6) >= 4;
+        BitCount cnt{0};
+        encode_block(coef + (size_t)id * 64, is_dummy(g, id), coded_dc(coef, g, id), pred_dc_rst(coef, g, id, ri), dct[c], act[c], cnt);
+        const int mcu = id / 6;
+        const bool last = id - mcu * 6 == 5 && ((mcu + 1) % ri == 0 || mcu + 1 == n_mcus);
+        if (!mine.cut) {
+            mine.head += cnt.bits;
+            if (last) mine.cut = 1u;
+        } else {
+            mine.tail += cnt.bits;
+            if (last) {
+                mine.mid += (mine.tail + 7u) >> 3;
+                mine.tail = 0u;
+            }
+        }
+    }
+    // a fixed-order inclusive scan of the runs
+    runs[t] = mine;
+    __syncthreads();
+    for (int o = 1; o < kThreads; o <<= 1) {
+        RunBits v = runs[t];
+        if (t >= o) v = run_join(runs[t - o], v);
+        __syncthreads();
+        runs[t] = v;
+        __syncthreads();
+    }
+    const unsigned bit0 = t ? run_end_bit(runs[t - 1]) : 0u, bit1 = run_end_bit(runs[t]);
+    const unsigned nbytes = run_end_bit(runs[kThreads - 1]) >> 3;          // the last block ends an interval: a whole number
+    __syncthreads();
+
+    // the words two runs may share: zero before anyone ORs into them
+    if (hi > lo) {
+        stage[bit0 >> 5] = 0;
+        stage[bit1 >> 5] = 0;
+    }
+    __threadfence();
+    __syncthreads();
+    if (hi > lo) {
+        BitSinkAt sink;
+        sink.begin(stage, bit0);
+        sink.at = bit0;
+        for (int id = lo; id < hi; ++id) {
+            const int c = (id % 6) >= 4;
+            encode_block(coef + (size_t)id * 64, is_dummy(g, id), coded_dc(coef, g, id), pred_dc_rst(coef, g, id, ri), dct[c], act[c], sink);
+            const int mcu = id / 6;
+            if (id - mcu * 6 == 5 && ((mcu + 1) % ri == 0 || mcu + 1 == n_mcus)) {
+                const int fill = (int)((0u - sink.at) & 7u);               // the last byte is filled up with 1 bits
+                if (fill) sink.put((1u << fill) - 1u, fill);
+                ends[mcu / ri] = sink.at >> 3;
+            }
+        }
+        sink.end();
+    }
+    __threadfence();
+    __syncthreads();
+
+    // byte stuffing: thread t owns staged bytes [s0, s1), whole words
+    const unsigned nwords = (nbytes + 3) >> 2;
+    const unsigned wper = (nwords + kThreads - 1) / kThreads;
+    const unsigned w0 = min((unsigned)t * wper, nwords), w1 = min(w0 + wper, nwords);
+    unsigned nff = 0;
+    for (unsigned i = w0; i < w1; ++i) {
+        const uint32_t v = __hip_atomic_load(stage + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) nff += (i * 4 + k < nbytes && ((v >> (8 * k)) & 255u) == 255u) ? 1u : 0u;
+    }
+    unsigned total_ff;
+    const unsigned ff0 = block_scan(nff, sh, total_ff);
+    const long long length = (long long)kHeaderBytesRst + nbytes + total_ff + 2ll * (n_int - 1) + 2;
+    if (length > room) {                                                   // uniform: nothing of this row is written
+        if (t == 0) lengths[b] = -1;
+        return;
+    }
+    uint8_t* dst = reinterpret_cast<uint8_t*>(r.dst);
+    for (int i = t; i < kHeaderBytesRst; i += kThreads) {
+        uint8_t v = tab.header[i];
+        if (i == 163) v = (uint8_t)(g.h >> 8);
+        if (i == 164) v = (uint8_t)(g.h & 255);
+        if (i == 165) v = (uint8_t)(g.w >> 8);
+        if (i == 166) v = (uint8_t)(g.w & 255);
+        if (i == 613) v = (uint8_t)(ri >> 8);
+        if (i == 614) v = (uint8_t)(ri & 255);
+        dst[i] = v;
+    }
+    // markers in front of this thread's first byte: the intervals k < n_int - 1 that end at or before it
+    int k0 = 0;
+    for (int k1 = n_int - 1; k0 < k1;) {
+        const int m = (k0 + k1) >> 1;
+        if (__hip_atomic_load(ends + m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= w0 * 4) k0 = m + 1; else k1 = m;
+    }
+    uint32_t next_end = k0 < n_int - 1 ? __hip_atomic_load(ends + k0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xffffffffu;
+    uint8_t* o = dst + kHeaderBytesRst + (size_t)w0 * 4 + ff0 + 2 * (size_t)k0;
+    for (unsigned i = w0; i < w1; ++i) {
+        const uint32_t v = __hip_atomic_load(stage + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int k = 0; k < 4; ++k) {
+            if (i * 4 + k >= nbytes) break;
+            const uint8_t by = (uint8_t)(v >> (8 * k));
+            *o++ = by;
+            if (by == 255) *o++ = 0;
+            if (i * 4 + k + 1 == next_end) {                               // never stuffed
+                *o++ = 0xFF;
+                *o++ = (uint8_t)(0xD0 + (k0 & 7));
+                ++k0;
+                next_end = k0 < n_int - 1 ? __hip_atomic_load(ends + k0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xffffffffu;
+            }
+        }
+    }
+    if (t == 0) {
+        dst[length - 2] = 0xFF;
+        dst[length - 1] = 0xD9;
+        lengths[b] = (int32_t)length;
+    }
+}
+
 }  // namespace
 
 }  // namespace w2l
@@ -533,6 +731,64 @@ int w2l_jpeg_encode_rows(void* stream, int B, const w2l_frame_row* rows, const i
     W2L_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(B), dim3(kThreads), 0, s, reinterpret_cast<const FrameRow*>(rows), cap, max_blocks,
                        lengths, static_cast<uint8_t*>(workspace), row_stride, stage_off, et);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_jpeg_header_rst(int h, int w, int quality, int restart_rows, uint8_t* out) {
+    W2L_REQUIRE(out && h >= 1 && h <= 65535 && w >= 1 && w <= 65535 && quality >= 1 && quality <= 100 && restart_rows >= 1,
+                "jpeg_header_rst: sizes in [1, 65535], quality in [1, 100] and restart_rows >= 1");
+    const long long ri = (long long)restart_rows * ((w + 15) / 16);
+    uint8_t buf[640];
+    const int n = build_header(h, w, quality, buf, ri > 65535 ? 65535 : (int)ri);
+    W2L_REQUIRE(n == kHeaderBytesRst, "jpeg_header_rst: internal header length %d", n);
+    memcpy(out, buf, kHeaderBytesRst);
+    return W2L_OK;
+}
+
+size_t w2l_jpeg_capacity_rst(int h, int w, int restart_rows) {
+    if (h < 1 || h > 65535 || w < 1 || w > 65535 || restart_rows < 1) return 0;
+    const long long mw = (w + 15) / 16, n_mcus = mw * ((h + 15) / 16);
+    const long long ri = restart_rows * mw > 65535 ? 65535 : restart_rows * mw;
+    return (size_t)(kHeaderBytesRst + 2 + 2 * kBlockStreamBytes * 6 * n_mcus + 4 * ((n_mcus + ri - 1) / ri));
+}
+
+size_t w2l_jpeg_workspace_bytes_rst(int B, int max_blocks) {
+    if (B < 1 || B > 65535 || max_blocks < 1 || max_blocks > kMaxBlocksLimit) return 0;
+    return (size_t)B * (row_coef_bytes(max_blocks) + row_stage_bytes_rst(max_blocks) + row_ends_bytes_rst(max_blocks));
+}
+
+int w2l_jpeg_encode_rows_rst(void* stream, int B, const w2l_frame_row* rows, const int32_t* cap, int quality, int max_blocks,
+                             int restart_rows, int32_t* lengths, void* workspace, size_t workspace_bytes) {
+    W2L_REQUIRE(rows && cap && lengths && workspace, "bad jpeg_encode_rows_rst arguments");
+    W2L_REQUIRE(B >= 1 && B <= 65535 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0,
+                "jpeg_encode_rows_rst: 1 <= B <= 65535 and a 16-byte aligned row table");
+    W2L_REQUIRE(quality >= 1 && quality <= 100, "jpeg_encode_rows_rst: quality %d is outside [1, 100]", quality);
+    W2L_REQUIRE(restart_rows >= 1, "jpeg_encode_rows_rst: restart_rows %d is below 1", restart_rows);
+    W2L_REQUIRE(max_blocks >= 1 && max_blocks <= kMaxBlocksLimit, "jpeg_encode_rows_rst: max_blocks %d is outside [1, 2^20]", max_blocks);
+    W2L_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && workspace_bytes >= w2l_jpeg_workspace_bytes_rst(B, max_blocks),
+                "jpeg_encode_rows_rst: the workspace must be 16-byte aligned and hold w2l_jpeg_workspace_bytes_rst(B, max_blocks) = %zu bytes",
+                w2l_jpeg_workspace_bytes_rst(B, max_blocks));
+    TransformTables tt;
+    EntropyTablesRst et;
+    memset(&et, 0, sizeof(et));
+    for (int t = 0; t < 2; ++t) {
+        uint8_t q[64];
+        quant_table(quality, t, q);
+        for (int i = 0; i < 64; ++i) tt.div[t][i] = (uint16_t)(8 * q[i]);
+        huff_codes(kDcBits[t], kDcVals, et.dc[t], 16);
+        huff_codes(kAcBits[t], kAcVals[t], et.ac[t], 256);
+    }
+    for (int i = 0; i < 64; ++i) tt.zzpos[kZigzag[i]] = (uint8_t)i;
+    W2L_REQUIRE(build_header(1, 1, quality, et.header, 1) == kHeaderBytesRst, "jpeg_encode_rows_rst: internal header length");
+    const size_t stage_off = row_coef_bytes(max_blocks), ends_off = stage_off + row_stage_bytes_rst(max_blocks);
+    const size_t row_stride = ends_off + row_ends_bytes_rst(max_blocks);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(jpeg_transform_kernel, dim3(ceil_div(max_blocks, kThreads / 8), B), dim3(kThreads), 0, s,
+                       reinterpret_cast<const FrameRow*>(rows), max_blocks, static_cast<uint8_t*>(workspace), row_stride, tt);
+    W2L_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_entropy_rst_kernel, dim3(B), dim3(kThreads), 0, s, reinterpret_cast<const FrameRow*>(rows), cap, max_blocks,
+                       restart_rows, lengths, static_cast<uint8_t*>(workspace), row_stride, stage_off, ends_off, et);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

@@ -143,15 +143,19 @@ W2L_JD_FN int huff_symbol(BitReader& br, const HuffLookup& h) {
 W2L_JD_FN int extend(int r, int s) { return r < (1 << (s - 1)) ? r - (1 << s) + 1 : r; }     // T.81 F.2.2.1, s >= 1
 W2L_JD_FN int16_t to_i16(long long v) { return (int16_t)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
 
-// The entropy-coded segment of one file (jdhuff.c decode_mcu for an interleaved 4:2:0 scan without restarts): dequantised
-// coefficients in row-major order into coef[nblocks][64], which the caller has ZEROED - only non-zero values are written, each at an
-// index < 64 of its own block.  Returns kOk or the reason the stream is refused; what was written until then stays.
-W2L_JD_FN int decode_scan(const uint8_t* data, int nbytes, const Geom& g, const TableSet& t, int16_t* coef) {
-    if (nbytes < 1) return kBadRow;
+// MCUs [first_mcu, first_mcu + n_mcus) of one file from the bytes that code exactly them (jdhuff.c decode_mcu for an interleaved
+// 4:2:0 scan): the whole entropy-coded segment of a file without restarts, or ONE restart interval - jdhuff.c process_restart puts
+// the three DC predictions back to 0 and starts at a byte boundary, which is how this routine begins.  Dequantised coefficients in
+// row-major order into coef[nblocks][64] (the file's first block, not the range's), which the caller has ZEROED - only non-zero
+// values are written, each at an index < 64 of a block of the range.  Returns kOk or the reason the bytes are refused (kBadRow for
+// a range outside the file); what was written until then stays.
+W2L_JD_FN int decode_mcus(const uint8_t* data, int nbytes, const Geom& g, const TableSet& t, int16_t* coef, int first_mcu, int n_mcus) {
+    if (nbytes < 1 || first_mcu < 0 || n_mcus < 1 || n_mcus > g.nblocks / 6 - first_mcu) return kBadRow;
     BitReader br;
     br.begin(data, nbytes);
     int pred[3] = {0, 0, 0};
-    for (int id = 0; id < g.nblocks; ++id) {
+    const int id_end = 6 * (first_mcu + n_mcus);
+    for (int id = 6 * first_mcu; id < id_end; ++id) {
         const int k6 = id % 6;
         const int c = k6 < 4 ? 0 : k6 - 3, tq = k6 < 4 ? 0 : 1;
         const HuffLookup& hdc = t.huff[2 * tq];
@@ -190,6 +194,11 @@ W2L_JD_FN int decode_scan(const uint8_t* data, int nbytes, const Geom& g, const 
         if (br.overrun()) return br.why(kOk);
     }
     return br.finish();
+}
+
+// The entropy-coded segment of one file without restarts: every MCU from one stream
+W2L_JD_FN int decode_scan(const uint8_t* data, int nbytes, const Geom& g, const TableSet& t, int16_t* coef) {
+    return decode_mcus(data, nbytes, g, t, coef, 0, g.nblocks / 6);
 }
 
 // ---- pixels

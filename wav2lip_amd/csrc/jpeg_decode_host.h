@@ -23,9 +23,12 @@ struct ErrText {
     }
 };
 
-// Walks the markers of one file (T.81 B.2).  Every index is checked against n before the byte is read.
-inline int parse(const uint8_t* d, size_t n, w2l_jpeg_info* info, ErrText& err) {
+// Walks the markers of one file (T.81 B.2).  Every index is checked against n before the byte is read.  restart_interval NULL:
+// the class of w2l_jpeg_parse, a DRI above 0 is refused; otherwise the class of w2l_jpeg_parse_rst: DRI's value goes there (0: none)
+// and, where it is above 0, RSTn markers inside the scan are passed over (w2l_jpeg_restart_segments checks their count and order).
+inline int parse(const uint8_t* d, size_t n, w2l_jpeg_info* info, ErrText& err, int* restart_interval = nullptr) {
     memset(info, 0, sizeof(*info));
+    if (restart_interval) *restart_interval = 0;
     if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return err.fail(W2L_JPEG_MALFORMED, "jpeg: no SOI marker (not a JPEG file)");
     bool have_q[4] = {false, false, false, false}, have_h[2][4] = {{false, false, false, false}, {false, false, false, false}};
     uint8_t q[4][64], hbits[2][4][16], hvals[2][4][256];
@@ -104,7 +107,8 @@ inline int parse(const uint8_t* d, size_t n, w2l_jpeg_info* info, ErrText& err) 
         } else if (m == 0xDD) {
             if (sl != 2) return err.fail(W2L_JPEG_MALFORMED, "jpeg: DRI segment of %zu bytes", sl);
             const int ri = (s[0] << 8) | s[1];
-            if (ri != 0) return err.fail(W2L_JPEG_RESTART, "jpeg: restart interval %d", ri);
+            if (ri != 0 && !restart_interval) return err.fail(W2L_JPEG_RESTART, "jpeg: restart interval %d", ri);
+            if (restart_interval) *restart_interval = ri;
         } else if (m >= 0xE0 && m <= 0xEF) {
             const bool app0 = m == 0xE0 && sl >= 5 && (memcmp(s, "JFIF", 5) == 0 || memcmp(s, "JFXX", 5) == 0);
             if (app0 && s[2] == 'I') jfif = true;
@@ -169,6 +173,10 @@ inline int parse(const uint8_t* d, size_t n, w2l_jpeg_info* info, ErrText& err) 
             info->eoi = 1;
             break;
         } else if (m >= 0xD0 && m <= 0xD7) {
+            if (restart_interval && *restart_interval > 0) {
+                i += 2;
+                continue;
+            }
             return err.fail(W2L_JPEG_MALFORMED, "jpeg: restart marker RST%d in a scan without restart interval", m - 0xD0);
         } else if (m == 0xFF) {
             ++i;
@@ -182,7 +190,57 @@ inline int parse(const uint8_t* d, size_t n, w2l_jpeg_info* info, ErrText& err) 
     return 0;
 }
 
-// (bits, vals) -> the lookup form.  Canonical codes of T.81 Annex C; refuses what is no prefix code.
+// The restart intervals of one entropy-coded segment (T.81 B.2.1, E.1.4): interval k codes MCUs [k * ri, min((k + 1) * ri, n_mcus))
+// and ends in front of the marker FF D0+(k mod 8); behind the last interval there is none.  A data byte FF is always followed by
+// 00, so FF D0..D7 in the bytes IS a marker and one linear pass finds them all.  Writes at most `cap` records (row = 0) and
+// returns the number of intervals, ceil(n_mcus / ri), or W2L_JPEG_MALFORMED: a marker too many or too few, one out of order, or
+// any other marker.  ri = 0: one record, the whole segment (RSTn markers are then refused).  Never reads ecs[n] or beyond.
+inline int restart_segments(const uint8_t* ecs, size_t n, int ri, int n_mcus, w2l_jpeg_segment* out, int cap, ErrText& err) {
+    if (n < 1 || n > 0x7fffffffu || ri < 0 || ri > 65535 || n_mcus < 1 || cap < 0)
+        return err.fail(W2L_JPEG_MALFORMED, "jpeg: restart_segments of %zu bytes, interval %d, %d MCUs", n, ri, n_mcus);
+    const int expected = ri > 0 ? (n_mcus + ri - 1) / ri : 1;
+    int k = 0;
+    size_t start = 0, i = 0;
+    auto emit = [&](size_t end) {
+        if (k < cap) {
+            w2l_jpeg_segment s;
+            memset(&s, 0, sizeof(s));
+            s.offset = (int32_t)start;
+            s.nbytes = (int32_t)(end - start);
+            s.first_mcu = ri > 0 ? k * ri : 0;
+            s.n_mcus = ri > 0 && (k + 1) * ri < n_mcus ? ri : n_mcus - s.first_mcu;
+            out[k] = s;
+        }
+    };
+    while (i < n) {
+        if (ecs[i] != 0xFF) {
+            ++i;
+            continue;
+        }
+        if (i + 1 >= n) break;                  // a lone FF at the end: part of the last interval, whose decoder refuses it
+        const int m = ecs[i + 1];
+        if (m == 0x00) {
+            i += 2;
+            continue;
+        }
+        if (m < 0xD0 || m > 0xD7) return err.fail(W2L_JPEG_MALFORMED, "jpeg: marker FF %02X at byte %zu of the scan", m, i);
+        if (ri == 0) return err.fail(W2L_JPEG_MALFORMED, "jpeg: restart marker RST%d in a scan without restart interval", m - 0xD0);
+        if (k >= expected - 1)
+            return err.fail(W2L_JPEG_MALFORMED, "jpeg: more than the %d restart markers of %d MCUs at interval %d", expected - 1, n_mcus, ri);
+        if (m - 0xD0 != (k & 7))
+            return err.fail(W2L_JPEG_MALFORMED, "jpeg: restart marker %d is RST%d, not RST%d", k, m - 0xD0, k & 7);
+        emit(i);
+        ++k;
+        i += 2;
+        start = i;
+    }
+    if (k != expected - 1)
+        return err.fail(W2L_JPEG_MALFORMED, "jpeg: %d restart markers where %d MCUs at interval %d have %d", k, n_mcus, ri, expected - 1);
+    emit(n);
+    return expected;
+}
+
+// (bits, vals) -> the lookup form. Canonical codes of T.81 Annex C; refuses what is no prefix code.
 inline int build_huff(const uint8_t bits[16], const uint8_t* vals, int nvals, bool dc, HuffLookup& h, ErrText& err) {
     memset(&h, 0, sizeof(h));
     int total = 0;

@@ -99,6 +99,11 @@ def build_cli_parser():
                    help='Face detector arithmetic: fp32 (default, matches the reference) or bf16 storage (faster; boxes move by '
                         'about what bf16 rounding alone moves them)')
     add_det_scale_flag(p)
+    p.add_argument('--out_codec', default='raw', choices=['raw', 'mjpg'],
+                   help='Video stream of --outfile: raw (default, uncompressed 24-bit BGR) or mjpg (Motion-JPEG, what '
+                        "cv2.VideoWriter_fourcc(*'MJPG') writes: every frame is JPEG-encoded on the device and only the files' "
+                        'bytes come back; lossy, about a tenth of the size at quality 95)')
+    p.add_argument('--out_quality', default=95, type=int, help='JPEG quality of --out_codec mjpg, 1..100 (default 95)')
     return p
 
 
@@ -623,9 +628,9 @@ def resize_frames_u8(frames, wh):
 
 
 def read_frames(a):
-    """inference.py:185-213: the frames of `--face` and the frame rate.  Images through PIL; video from the uncompressed-AVI
-    container this package writes (wav2lip_amd/container.py) - compressed video needs a codec (cv2.VideoCapture / ffmpeg),
-    which this image does not have and which is not arithmetic of the path."""
+    """inference.py:185-213: the frames of `--face` and the frame rate.  Images through PIL; video from the AVI container of
+    wav2lip_amd/container.py, uncompressed or Motion-JPEG (this loop takes host frames, so MJPG frames are decoded by PIL here;
+    `real_videos_inference` decodes them on the device) - inter-frame codecs need cv2.VideoCapture / ffmpeg, which are not here."""
     if not os.path.isfile(a.face):
         raise ValueError('--face argument must be a valid path to video/image file')
     if is_image_path(a.face):
@@ -635,8 +640,8 @@ def read_frames(a):
         clip = container.read_avi(a.face)
         frames, fps = clip["frames"], clip["fps"]
     except Exception as e:      # noqa: BLE001
-        raise ValueError("--face %s: only images (jpg/png/jpeg) and uncompressed BGR AVI video can be read here (no video "
-                         "codecs in this build): %s" % (a.face, e))
+        raise ValueError("--face %s: only images (jpg/png/jpeg) and AVI video, uncompressed BGR or Motion-JPEG, can be read here "
+                         "(no other video codecs in this build): %s" % (a.face, e))
     print('Reading video frames...')
     frames = list(frames)
     if a.resize_factor > 1 and frames:
@@ -677,6 +682,11 @@ def main(argv=None, keep_frames=True, backend="nccl"):
     global args
     from . import sharding
     args = parse_args(argv)
+    mjpg = args.out_codec == "mjpg"
+    if mjpg and not 1 <= args.out_quality <= 100:
+        raise ValueError("--out_quality %d is outside [1, 100]" % args.out_quality)
+    if mjpg and int(os.environ.get("WORLD_SIZE", "1")) > 1:         # before the process group and any device work
+        raise ValueError("--out_codec mjpg runs on one GPU: a sharded run gathers raw frames (compressed shards are not gathered yet)")
     ranks = sharding.init_from_env(backend)
     sharded = ranks.dist is not None and ranks.world > 1
     say = print if ranks.writer else (lambda *a, **k: None)
@@ -722,7 +732,8 @@ def main(argv=None, keep_frames=True, backend="nccl"):
             sr, pcm = wavfile.read(args.audio)
             if pcm.dtype != np.int16:
                 pcm = np.clip(np.round(audio._pcm_to_float32(pcm) * 32768.0), -32768, 32767).astype(np.int16)
-            writer = container.AviWriter(args.outfile, fps, (frame_w, frame_h), audio=pcm, audio_sr=sr)
+            writer = container.AviWriter(args.outfile, fps, (frame_w, frame_h), audio=pcm, audio_sr=sr, codec=args.out_codec,
+                                         quality=args.out_quality)
             writer.__enter__()
         try:
             def emit(f):
@@ -731,6 +742,16 @@ def main(argv=None, keep_frames=True, backend="nccl"):
                     out_frames.append(f)
 
             def drain(ticket):
+                if mjpg:
+                    # the frames are encoded where they lie and only the files come back; the raw frames follow them to the
+                    # host for keep_frames alone (mjpg is never sharded)
+                    from . import jpeg
+                    res = runner.result(ticket)
+                    for data in jpeg.encode_frames(res, quality=args.out_quality, restart_rows=writer.restart_rows):
+                        writer.write_jpeg(data)
+                    if keep_frames:
+                        out_frames.extend(res.cpu().numpy())
+                    return
                 for f in runner.result(ticket).cpu().numpy():
                     if sharded:
                         local.append(f)         # this rank's shard, exchanged below

@@ -20,6 +20,14 @@ what cv2.imwrite wrote for the reference - are decoded on the device to the pixe
 Per batch: the files' entropy-coded segments, the row table (w2l_jpeg_row) and the de-duplicated table sets are staged in ONE
 pinned buffer and copied in once, one memset and three kernels run on the current stream whatever the batch size is, and one copy
 of `status` comes back.  No host fallback here either.
+
+Motion-JPEG frames (w2l_jpeg_encode_rows_rst, w2l_jpeg_decode_rows_rst): whole frames coded with RESTART INTERVALS, so that a
+frame is many independent byte-aligned streams instead of one serial one - byte-equal to PIL's `restart_marker_rows` in both
+directions.  The functions above keep refusing such files; these take them and the plain class together.
+
+    encode_frames(frames, quality=95, restart_rows=1, boxes=None)  -> list[bytes], one complete file per frame (or per box)
+    parse_frame(data)                                               -> (the _lib.JpegInfo, Ri in MCUs; 0: no restart interval)
+    decode_frames(datas, device)                                    -> list of device uint8 [H,W,3] BGR tensors; one lane per interval
 """
 import ctypes as C
 from concurrent.futures import ThreadPoolExecutor, wait
@@ -29,6 +37,7 @@ import numpy as np
 from . import _lib
 
 HEADER_BYTES = 623                # SOI .. SOS; height at offset 163, width at 165 (big-endian 16-bit each)
+HEADER_BYTES_RST = 629            # with DRI (FF DD 00 04 Ri) at offset 609, between the last DHT and SOS
 MAX_BLOCK_BYTES = 2 * 208         # a block codes at most 22 bits of DC + 63 x 26 bits of AC = 208 bytes; stuffing can double them
 MAX_ROWS = 65535                  # rows of one w2l_jpeg_encode_rows launch
 MAX_BLOCKS = 1 << 20              # blocks of one crop
@@ -85,10 +94,14 @@ def _frame_list(frames):
 class _Plan:
     """a validated batch: the row table and the capacities as host arrays, made without touching the device"""
 
-    def __init__(self, frames, boxes, quality, frame_index):
+    def __init__(self, frames, boxes, quality, frame_index, restart_rows=None):
         from .multiclip import FRAME_ROW
         fl = _frame_list(frames)
+        if boxes is None:                                  # whole frames
+            boxes = [(0, 0, f[3], f[2]) for f in fl]
         n = len(boxes)
+        if restart_rows is not None and not 1 <= int(restart_rows) <= 65535:
+            raise ValueError("jpeg: restart_rows %r is outside [1, 65535]" % (restart_rows,))
         if n < 1 or n > MAX_ROWS:
             raise ValueError("jpeg: %d crops in one batch (1 .. %d)" % (n, MAX_ROWS))
         if not 1 <= int(quality) <= 100:
@@ -112,6 +125,11 @@ class _Plan:
             raise ValueError("jpeg: a crop of %d blocks (at most %d)" % (self.max_blocks, MAX_BLOCKS))
         # every slot holds the largest crop's bound, so that the used part of all slots comes back as one strided copy
         self.stride = -(-(HEADER_BYTES + 2 + MAX_BLOCK_BYTES * self.max_blocks) // 16) * 16
+        self.restart_rows = None if restart_rows is None else int(restart_rows)
+        if self.restart_rows is not None:                  # capacity_rst of the largest crop: DRI and 4 bytes per interval on top
+            mw, mh = -(-(x2 - x1) // 16), -(-(y2 - y1) // 16)
+            ri = np.minimum(self.restart_rows * mw, 65535)
+            self.stride = -(-int((HEADER_BYTES_RST + 2 + MAX_BLOCK_BYTES * 6 * mw * mh + 4 * (-(-(mw * mh) // ri))).max()) // 16) * 16
         self.table = np.zeros(n, FRAME_ROW)
         self.table["src"] = np.asarray([f[1] for f in fl], dtype=np.uint64)[idx]
         self.table["H"], self.table["W"] = H, W
@@ -132,12 +150,19 @@ class _Plan:
             host.numpy()[:self.table.nbytes] = self.table.view(np.uint8)
             host.numpy()[nb:].view(np.int32)[:] = stride
             staged = host.to(self.device, non_blocking=True)                             # one copy in
-            ws_bytes = int(lib.w2l_jpeg_workspace_bytes(n, self.max_blocks))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
             lengths_dev = torch.empty(n, dtype=torch.int32, device=self.device)
-            _lib.check(lib.w2l_jpeg_encode_rows(_lib.current_stream(), n, _lib.ptr(staged), C.c_void_p(staged.data_ptr() + nb),
-                                                self.quality, self.max_blocks, _lib.ptr(lengths_dev), _lib.ptr(ws), ws_bytes),
-                       "jpeg_encode_rows")
+            if self.restart_rows is None:
+                ws_bytes = int(lib.w2l_jpeg_workspace_bytes(n, self.max_blocks))
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+                _lib.check(lib.w2l_jpeg_encode_rows(_lib.current_stream(), n, _lib.ptr(staged), C.c_void_p(staged.data_ptr() + nb),
+                                                    self.quality, self.max_blocks, _lib.ptr(lengths_dev), _lib.ptr(ws), ws_bytes),
+                           "jpeg_encode_rows")
+            else:
+                ws_bytes = int(lib.w2l_jpeg_workspace_bytes_rst(n, self.max_blocks))
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+                _lib.check(lib.w2l_jpeg_encode_rows_rst(_lib.current_stream(), n, _lib.ptr(staged), C.c_void_p(staged.data_ptr() + nb),
+                                                        self.quality, self.max_blocks, self.restart_rows, _lib.ptr(lengths_dev),
+                                                        _lib.ptr(ws), ws_bytes), "jpeg_encode_rows_rst")
             lengths = lengths_dev.cpu().numpy().astype(np.int64)                         # the first copy back (waits for the kernels)
             if (lengths < HEADER_BYTES + 2).any() or (lengths > stride).any():
                 raise RuntimeError("jpeg: the device encoder refused a crop (lengths %s at capacity %d)" % (lengths.tolist(), stride))
@@ -152,6 +177,55 @@ def encode_crops(frames, boxes, quality=95, frame_index=None):
     of such tensors (or single [H,W,3] frames) of different shapes, counted through; frame_index None: crop i reads frame i.  Runs
     on the current stream; boxes are validated here (ValueError), the kernel takes them as they are."""
     return _Plan(frames, boxes, quality, frame_index).run()
+
+
+def capacity_rst(h, w, restart_rows=1):
+    """`capacity` for a file with restart intervals (w2l_jpeg_capacity_rst): 6 more header bytes, and per interval a padding
+    byte, its possible stuffed 00 and the marker"""
+    n = int(_lib.load().w2l_jpeg_capacity_rst(int(h), int(w), int(restart_rows)))
+    if n == 0:
+        raise ValueError("jpeg: size %r x %r or restart_rows %r is out of range" % (h, w, restart_rows))
+    return n
+
+
+def header_rst(h, w, quality, restart_rows=1):
+    """the 629 bytes in front of the entropy stream of a file with restart intervals (`header` plus the DRI segment)"""
+    buf = (C.c_uint8 * HEADER_BYTES_RST)()
+    _lib.check(_lib.load().w2l_jpeg_header_rst(int(h), int(w), int(quality), int(restart_rows), buf), "jpeg_header_rst")
+    return bytes(buf)
+
+
+ENCODE_SLOT_BYTES = 1 << 30       # encode_frames: device bytes of one launch's output slots (each holds the worst case)
+
+
+def encode_frames(frames, quality=95, restart_rows=1, boxes=None, frame_index=None):
+    """The frames of a Motion-JPEG stream: whole device frames (uint8 [N,H,W,3] BGR, or a list of such tensors / single frames),
+    or with `boxes` their crops as in `encode_crops`, each as a complete JFIF file with a restart interval of `restart_rows` MCU
+    rows - byte-equal to PIL's `save(format="JPEG", quality=quality, subsampling=2, restart_marker_rows=restart_rows)`.  Staging as
+    `encode_crops`: one pinned copy in, two kernels, the lengths back, then the used bytes; frames whose worst-case slots would
+    exceed ENCODE_SLOT_BYTES together are encoded in several such launches."""
+    if restart_rows is None:
+        raise ValueError("jpeg: encode_frames writes restart intervals (restart_rows >= 1); encode_crops writes files without")
+    plan = _Plan(frames, boxes, quality, frame_index, restart_rows)
+    per = max(1, ENCODE_SLOT_BYTES // plan.stride)
+    if plan.n <= per:
+        return plan.run()
+    fl = _frame_list(frames)
+    tensors = [_as_frame(f) for f in fl]
+    bx = [(0, 0, f[3], f[2]) for f in fl] if boxes is None else list(boxes)
+    idx = list(range(len(bx))) if frame_index is None else [int(i) for i in frame_index]
+    out = []
+    for i in range(0, len(bx), per):
+        used = sorted(set(idx[i:i + per]))
+        out += _Plan([tensors[j] for j in used], bx[i:i + per], quality, [used.index(j) for j in idx[i:i + per]], restart_rows).run()
+    return out
+
+
+def _as_frame(f):
+    """the [H,W,3] view of one entry of `_frame_list`"""
+    t, addr, H, W = f
+    off = (addr - t.data_ptr()) // (H * W * 3)
+    return t[off] if t.dim() == 4 else t
 
 
 def _write_file(dst, data):
@@ -275,9 +349,10 @@ def probe(data):
     return info.H, info.W
 
 
-def _decode(datas, infos, device):
+def _decode(datas, infos, device, segments=None):
     """(tensors, status int32 numpy [n]) of parsed files: one pinned buffer and one copy in, the kernels on the current stream,
-    one copy of status back.  tensors[i] is complete where status[i] == 0."""
+    one copy of status back.  tensors[i] is complete where status[i] == 0.  segments: None for w2l_jpeg_decode_rows (one lane per
+    file), or the JPEG_SEGMENT records of all files for w2l_jpeg_decode_rows_rst (one lane per record), staged in the same buffer."""
     import torch
     lib = _lib.load()
     device = torch.device(device)
@@ -302,7 +377,8 @@ def _decode(datas, infos, device):
         raise ValueError("jpeg: a file of %d blocks (at most %d)" % (max_blocks, MAX_BLOCKS))
     rows_b = -(-table.nbytes // 16) * 16
     tabs_b = tb * len(sets)                                                     # a multiple of 16
-    src_off = rows_b + tabs_b + np.concatenate([[0], np.cumsum(table["nbytes"].astype(np.int64))])
+    segs_b = 0 if segments is None else segments.nbytes                         # 32 bytes each
+    src_off = rows_b + tabs_b + segs_b + np.concatenate([[0], np.cumsum(table["nbytes"].astype(np.int64))])
     dst_off = np.concatenate([[0], np.cumsum(table["H"].astype(np.int64) * table["W"] * 3)])
     with torch.cuda.device(device):
         staged = torch.empty(int(src_off[-1]), dtype=torch.uint8, device=device)
@@ -316,12 +392,21 @@ def _decode(datas, infos, device):
             h[rows_b + idx * tb:rows_b + (idx + 1) * tb] = np.frombuffer(blob, np.uint8)
         for i, (d, info) in enumerate(zip(datas, infos)):
             h[src_off[i]:src_off[i + 1]] = np.frombuffer(d, np.uint8, info.ecs_bytes, info.ecs_offset)
+        if segments is not None:
+            h[rows_b + tabs_b:rows_b + tabs_b + segs_b] = segments.view(np.uint8)
         staged.copy_(host, non_blocking=True)                                   # one copy in
-        ws_bytes = int(lib.w2l_jpeg_decode_workspace_bytes(n, max_blocks))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
         status = torch.empty(n, dtype=torch.int32, device=device)
-        _lib.check(lib.w2l_jpeg_decode_rows(_lib.current_stream(), n, _lib.ptr(staged), C.c_void_p(staged.data_ptr() + rows_b), len(sets),
-                                            max_blocks, _lib.ptr(status), _lib.ptr(ws), ws_bytes), "jpeg_decode_rows")
+        if segments is None:
+            ws_bytes = int(lib.w2l_jpeg_decode_workspace_bytes(n, max_blocks))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+            _lib.check(lib.w2l_jpeg_decode_rows(_lib.current_stream(), n, _lib.ptr(staged), C.c_void_p(staged.data_ptr() + rows_b), len(sets),
+                                                max_blocks, _lib.ptr(status), _lib.ptr(ws), ws_bytes), "jpeg_decode_rows")
+        else:
+            ws_bytes = int(lib.w2l_jpeg_decode_workspace_bytes_rst(n, max_blocks))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+            _lib.check(lib.w2l_jpeg_decode_rows_rst(_lib.current_stream(), n, _lib.ptr(staged), C.c_void_p(staged.data_ptr() + rows_b),
+                                                    len(sets), max_blocks, C.c_void_p(staged.data_ptr() + rows_b + tabs_b), len(segments),
+                                                    _lib.ptr(status), _lib.ptr(ws), ws_bytes), "jpeg_decode_rows_rst")
         st = status.cpu().numpy()                                               # one copy back (waits for the kernels)
     imgs = [out[int(dst_off[i]):int(dst_off[i + 1])].view(int(table["H"][i]), int(table["W"][i]), 3) for i in range(n)]
     return imgs, st
@@ -348,4 +433,75 @@ def decode_files(datas, device):
     if (st != 0).any():
         i = int(np.flatnonzero(st)[0])
         raise ValueError("jpeg: file %d is corrupt: %s (status %d)" % (i, STATUS_TEXT.get(int(st[i]), "?"), int(st[i])))
+    return imgs
+
+
+# ---------------------------------------------------------------- Motion-JPEG frames: files with restart intervals
+JPEG_SEGMENT = np.dtype([("row", "<i4"), ("offset", "<i4"), ("nbytes", "<i4"), ("first_mcu", "<i4"), ("n_mcus", "<i4"),
+                         ("pad", "<i4", (3,))])
+
+
+class CorruptJpeg(ValueError):
+    """a frame of `decode_frames` that is cut, whose restart markers are wrong or whose stream the kernel refuses; `.index` is its
+    position in the call's list"""
+
+    def __init__(self, msg, index):
+        super().__init__(msg)
+        self.index = index
+
+
+def parse_frame(data):
+    """(the _lib.JpegInfo, Ri) of one frame's bytes: `parse` for the same class plus a restart interval of Ri MCUs (0: none), the
+    class `decode_frames` takes.  Raises as `parse` does."""
+    lib = _lib.load()
+    info, ri = _lib.JpegInfo(), C.c_int32(0)
+    data = bytes(data)
+    rc = lib.w2l_jpeg_parse_rst(data, len(data), C.byref(info), C.byref(ri))
+    if rc != 0:
+        msg = (lib.w2l_last_error() or b"?").decode()
+        if rc == MALFORMED or rc > MALFORMED:
+            raise ValueError(msg)
+        raise UnsupportedJpeg(msg, rc)
+    return info, int(ri.value)
+
+
+def restart_segments(data, info, ri):
+    """the JPEG_SEGMENT records (row = 0) of a parsed frame: one per restart interval, found by the host's linear marker scan
+    (w2l_jpeg_restart_segments); ValueError where the markers' count or order is wrong"""
+    lib = _lib.load()
+    n_mcus = (-(-info.H // 16)) * (-(-info.W // 16))
+    n = -(-n_mcus // ri) if ri > 0 else 1
+    out = np.zeros(n, JPEG_SEGMENT)
+    ecs = np.frombuffer(data, np.uint8, info.ecs_bytes, info.ecs_offset)
+    rc = lib.w2l_jpeg_restart_segments(C.c_void_p(ecs.ctypes.data), info.ecs_bytes, int(ri), n_mcus, C.c_void_p(out.ctypes.data), n)
+    if rc != n:
+        raise ValueError((lib.w2l_last_error() or b"?").decode() if rc < 0 else "jpeg: %d restart intervals, expected %d" % (rc, n))
+    return out
+
+
+def decode_frames(datas, device):
+    """`decode_files` for the frames of a Motion-JPEG stream: files with restart intervals and files without share one launch
+    (w2l_jpeg_decode_rows_rst: one lane per interval; a file without is one interval).  A list of device uint8 [H,W,3] BGR
+    tensors, views of one buffer, byte-equal to PIL's decode.  UnsupportedJpeg for a frame outside the class, ValueError naming
+    the frame index for one that is cut, whose markers are wrong or whose stream the kernel refuses; RuntimeError for a CPU device."""
+    import torch
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("jpeg: decode_frames needs a HIP device (there is no host fallback), got %s" % (device,))
+    datas = [bytes(d) for d in datas]
+    infos, segs = [], []
+    for i, d in enumerate(datas):
+        try:
+            info, ri = parse_frame(d)
+            s = restart_segments(d, info, ri)
+        except UnsupportedJpeg as e:
+            raise UnsupportedJpeg("jpeg: frame %d: %s" % (i, e), e.code) from None
+        except ValueError as e:
+            raise CorruptJpeg("jpeg: frame %d is corrupt: %s" % (i, e), i) from None
+        s["row"] = i
+        infos.append(info)
+        segs.append(s)
+    imgs, st = _decode(datas, infos, device, np.concatenate(segs))
+    if (st != 0).any():
+        i = int(np.flatnonzero(st)[0])
+        raise CorruptJpeg("jpeg: frame %d is corrupt: %s (status %d)" % (i, STATUS_TEXT.get(int(st[i]), "?"), int(st[i])), i)
     return imgs

@@ -267,9 +267,12 @@ def clip_boxes(detector, frames, index, pads, batch_size):
 
 
 def read_inputs(video, audio_src, tmpdir):
-    """(frames uint8 [F,H,W,3], fps, wav float32 at 16 kHz, the audio track's PCM16 samples, its rate)"""
+    """(frames uint8 [F,H,W,3], fps, wav float32 at 16 kHz, the audio track's PCM16 samples, its rate).  The frames are read
+    onto the current HIP device (the rank's: sharding.init_from_env binds it), where this command keeps each clip anyway: a
+    Motion-JPEG clip is decoded there, an uncompressed one uploaded."""
+    import torch
     wav, pcm, sr = gv._load_audio(audio_src, tmpdir)
-    clip = container.read_avi(video)
+    clip = container.read_avi(video, device=torch.device("cuda", torch.cuda.current_device()))
     return clip["frames"], clip["fps"], wav, pcm, sr
 
 
@@ -288,7 +291,7 @@ def clip_jobs(args, lines, ranks, detector, tracks, report=None):
                 raise
             except Exception:
                 traceback.print_exc()
-                gv._skip(idx, line, "an input could not be decoded (uncompressed BGR AVI with PCM16 audio only)")
+                gv._skip(idx, line, "an input could not be decoded (uncompressed or Motion-JPEG AVI with PCM16 audio only)")
                 continue
             mel = device_mel(wav, ranks.device)
             starts = real_chunk_starts(int(mel.shape[1]), fps)
@@ -296,7 +299,12 @@ def clip_jobs(args, lines, ranks, detector, tracks, report=None):
                 gv._skip(idx, line, "the audio is shorter than one 16-column mel window")
                 continue
             index = frame_index(len(frames), len(starts), args.mode)         # raises in random / dubbed: not caught (:261)
-            frames = upload_frames(frames[:len(starts)], ranks.device)
+            frames = frames[:len(starts)]
+            if not hasattr(frames, "is_cuda"):                               # host frames (a caller's own read_inputs): one trip up
+                frames = upload_frames(frames, ranks.device)
+            elif frames.device != ranks.device:
+                frames = frames.to(ranks.device)
+            frames = frames.contiguous()
             note = {"read": tuple(int(v) for v in frames.shape[1:3])}
             cap = capped_size(int(frames.shape[1]), int(frames.shape[2]), args.max_frame_res)
             if cap is not None:
