@@ -122,7 +122,7 @@ def _restate(mdist, vshift, n):
     return np.array([mdist[amin], np.float32(med - mdist[amin]), np.float32(vshift - amin), np.float32(n)], np.float32)
 
 
-def _score(lib, cuda, segs, C, vshift, f1, f2):
+def _score(lib, cuda, segs, C, vshift, f1, f2, fill=float("nan")):
     from wav2lip_amd import evaluation
     from wav2lip_amd._lib import check, current_stream, ptr
     win = 2 * vshift + 1
@@ -130,8 +130,8 @@ def _score(lib, cuda, segs, C, vshift, f1, f2):
     for k, s in enumerate(segs):
         t[k] = s
     t_dev = torch.from_numpy(t.view(np.uint8)).to(cuda)
-    mdist = torch.full((len(segs), win), float("nan"), device=cuda)
-    scores = torch.full((len(segs), 4), float("nan"), device=cuda)
+    mdist = torch.full((len(segs), win), fill, device=cuda)
+    scores = torch.full((len(segs), 4), fill, device=cuda)
     check(lib.w2l_lse_score_segments(current_stream(), len(segs), ptr(t_dev), C, vshift, ptr(f1), ptr(f2), ptr(mdist), ptr(scores)),
           "lse_score_segments")
     return mdist.cpu().numpy(), scores.cpu().numpy()
@@ -145,16 +145,13 @@ def _pdist_alone(lib, cuda, f1, f2, vshift):
     return d.cpu().numpy()
 
 
-@pytest.mark.parametrize("C", [512, 7])
-@pytest.mark.parametrize("vshift", [0, 3, 15])
-def test_score_segments_equals_pdist_per_segment_and_a_numpy_reduction(cuda, C, vshift):
-    """segments of 1, 2, vshift+1 and 40 rows side by side, fenced by rows of large distinct values: one read across a boundary
-    changes a distance by hundreds.  Unit rows keep every distance in [2**-16, 4), so with n < 2**12 the fp64 sum of a column
-    is exact in any order, and the mean is one correctly rounded division: bit-equality is the right bar."""
+def _fenced_segments_equal_pdist_and_numpy(cuda, C, vshift, lengths):
+    """segments side by side, fenced by rows of large distinct values: one read across a boundary changes a distance by hundreds.
+    Unit rows keep every distance in [2**-16, 4), so with n < 2**12 the fp64 sum of a column is exact in any order, and the mean
+    is one correctly rounded division: bit-equality is the right bar."""
     from wav2lip_amd import _lib
     lib = _lib.load()
     g = torch.Generator().manual_seed(100 * vshift + C)
-    lengths = [1, 2, vshift + 1, 40]
     total = sum(lengths) + 2 * (len(lengths) + 1)
     f1 = 1e3 + torch.arange(total * C, dtype=torch.float32).reshape(total, C)          # the fences (and everything else, for now)
     f2 = -2e3 - torch.arange(total * C, dtype=torch.float32).reshape(total, C)
@@ -172,6 +169,58 @@ def test_score_segments_equals_pdist_per_segment_and_a_numpy_reduction(cuda, C, 
         want = d.astype(np.float64).mean(0).astype(np.float32)
         assert np.array_equal(mdist[k], want), (k, n, float(np.abs(mdist[k] - want).max()))
         assert np.array_equal(scores[k], _restate(want, vshift, n)), (k, n, scores[k], _restate(want, vshift, n))
+
+
+@pytest.mark.parametrize("C", [512, 7])
+@pytest.mark.parametrize("vshift", [0, 3, 15])
+def test_score_segments_equals_pdist_per_segment_and_a_numpy_reduction(cuda, C, vshift):
+    """segments of 1, 2, vshift+1 and 40 rows (_fenced_segments_equal_pdist_and_numpy)"""
+    _fenced_segments_equal_pdist_and_numpy(cuda, C, vshift, [1, 2, vshift + 1, 40])
+
+
+@pytest.mark.parametrize("C", [512, 7])
+@pytest.mark.parametrize("vshift", [0, 3])
+def test_score_segments_at_the_sixteen_wave_round_boundary(cuda, C, vshift):
+    """16, 17, 32 and 33 rows: the kernel takes the rows sixteen at a time, one wave each - a full round, a round and one row,
+    two full rounds, two and one row"""
+    _fenced_segments_equal_pdist_and_numpy(cuda, C, vshift, [16, 17, 32, 33])
+
+
+@pytest.mark.parametrize("n", [1, 6])
+def test_score_segments_orders_nan_as_the_reference_does(cuda, n):
+    """one NaN in f2 (tests/_audio_cases.py; tests/test_audio_cases_cpu.py pins what oracle/lse_ref.py makes of it): with n = 1 and
+    vshift = 2 exactly one of the five mean distances is NaN, the minimum is that NaN, at its index, and the confidence is NaN;
+    with n = 6 every entry is NaN and the offset is that of index 0"""
+    import _audio_cases as ac
+    from wav2lip_amd import _lib
+    lib = _lib.load()
+    f1, f2 = (torch.from_numpy(f) for f in ac.lse_nan_inputs(n))
+    off, conf, minval, ref = lse_ref.scores(f1, f2, vshift=ac.LSE_VSHIFT)
+    ref = ref.numpy()
+    assert np.isnan(conf) and np.isnan(minval) and int(np.isnan(ref).sum()) == (1 if n == 1 else 5)
+    mdist, scores = _score(lib, cuda, [(0, n)], ac.LSE_C, ac.LSE_VSHIFT, f1.to(cuda), f2.to(cuda), fill=7.0)
+    assert np.array_equal(np.isnan(mdist[0]), np.isnan(ref)), (mdist[0], ref)
+    live = ~np.isnan(ref)
+    assert (np.abs(mdist[0][live] - ref[live]) <= ac.LSE_PDIST_TOL).all()
+    assert np.isnan(scores[0, 0]) and np.isnan(scores[0, 1]), scores[0]
+    assert scores[0, 2] == off == (0 if n == 1 else ac.LSE_VSHIFT) and scores[0, 3] == n
+
+
+def test_score_segments_writes_an_empty_segment_as_nan_and_reads_nothing_for_it(cuda):
+    """a segment of no rows between two live ones, its row0 far behind both arenas: its mean distances are NaN, its scores
+    (NaN, NaN, NaN, 0), and its neighbours' rows are the bits of a run without it"""
+    from wav2lip_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(77)
+    C, vshift = 70, 3
+    f1 = torch.nn.functional.normalize(torch.randn(12, C, generator=g), dim=1).to(cuda)
+    f2 = torch.nn.functional.normalize(torch.randn(12, C, generator=g), dim=1).to(cuda)
+    mdist, scores = _score(lib, cuda, [(0, 5), (10 ** 6, 0), (5, 7)], C, vshift, f1, f2, fill=7.0)
+    m2, s2 = _score(lib, cuda, [(0, 5), (5, 7)], C, vshift, f1, f2, fill=7.0)
+    assert np.isnan(mdist[1]).all() and np.isnan(scores[1, :3]).all() and scores[1, 3] == 0
+    assert not np.isnan(m2).any() and not np.isnan(s2).any() and not (m2 == 7.0).any()
+    assert mdist[[0, 2]].tobytes() == m2.tobytes() and scores[[0, 2]].tobytes() == s2.tobytes()
+    assert s2[:, 3].tolist() == [5.0, 7.0]
 
 
 def test_score_segments_takes_the_lowest_index_among_equal_minima(cuda):

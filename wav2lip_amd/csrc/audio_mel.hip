@@ -318,7 +318,7 @@ template <typename T_>
 static int mel_gather_t(void* stream, const float* mel, int T, const int32_t* starts, int B, T_* out, int out_cs, int c_zero_to) {
     W2L_REQUIRE(mel && starts && out && T >= 16 && B >= 1, "bad mel_gather arguments");
     if (c_zero_to < 1) c_zero_to = 1;
-    W2L_REQUIRE(out_cs >= c_zero_to, "out_cs=%d < %d", out_cs, c_zero_to);
+    W2L_REQUIRE(out_cs >= c_zero_to, "mel_gather: out_cs=%d < c_zero_to=%d", out_cs, c_zero_to);
     const long long total = (long long)B * kMels * 16;
     long long g = (total + 255) / 256;
     if (g > 4096) g = 4096;
@@ -333,7 +333,7 @@ static int mel_gather_rows_t(void* stream, const w2l_mel_row* rows, int B, T_* o
     W2L_REQUIRE(B >= 1 && B <= 65535 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0,
                 "mel_gather_rows: 1 <= B <= 65535 and a 16-byte aligned row table");
     if (c_zero_to < 1) c_zero_to = 1;
-    W2L_REQUIRE(out_cs >= c_zero_to, "out_cs=%d < %d", out_cs, c_zero_to);
+    W2L_REQUIRE(out_cs >= c_zero_to, "mel_gather_rows: out_cs=%d < c_zero_to=%d", out_cs, c_zero_to);
     const long long total = (long long)B * kMels * 16;
     long long g = (total + 255) / 256;
     if (g > 4096) g = 4096;
