@@ -224,13 +224,12 @@ def _packed_run(cuda, precision):
     jobs = _filelist_jobs()
     dev_frames = [(idx, torch.from_numpy(np.ascontiguousarray(f)).to(cuda)) for idx, f in jobs]
     built, batches = [], []
-    real = {"_Graph": s3fd._Graph, "_GraphB": s3fd._GraphB, "batch": many._detect_batch}
+    real = {"_Graph": s3fd._Graph, "batch": many._detect_batch}
 
-    def counting(name):
-        def make(*a, **k):
-            built.append(a[1:4])
-            return real[name](*a, **k)
-        return make
+    def counting(*a, **k):
+        assert (a[5:] + (k.get("precision", "f32"),))[0] == precision            # every graph of the run is one of its precision
+        built.append(a[1:4])
+        return real["_Graph"](*a, **k)
 
     def recording(detector, frames, B, H, W, rects, flags, offset):
         batches.append((frames.cpu().numpy().view("<u8").copy(), B, H, W, offset))
@@ -240,8 +239,7 @@ def _packed_run(cuda, precision):
         return list(face_detection.detect_many(det, (face_detection.DetectJob(i, f) for i, f in items), pads=PADS, T=5, batch_size=BS))
 
     with pytest.MonkeyPatch.context() as mp:
-        mp.setattr(s3fd, "_Graph", counting("_Graph"))
-        mp.setattr(s3fd, "_GraphB", counting("_GraphB"))
+        mp.setattr(s3fd, "_Graph", counting)
         mp.setattr(many, "_detect_batch", recording)
         first = run(dev_frames)
     again = run(dev_frames)

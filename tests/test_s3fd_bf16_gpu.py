@@ -135,14 +135,13 @@ def test_conv1_2_at_480x640_on_the_resident_box_kernel(cuda):
 
 
 def _convb_check(cuda, cin, cout, k, st, p, N, H, W, seed, family=None):
-    from wav2lip_amd.face_detection.s3fd import _ConvBiasB
     g = torch.Generator().manual_seed(seed)
     conv = torch.nn.Conv2d(cin, cout, k, stride=st, padding=p)
     with torch.no_grad():
         conv.weight.copy_(torch.randn(conv.weight.shape, generator=g) * (2.0 / (cin * k * k)) ** 0.5)
         conv.bias.copy_(torch.randn(cout, generator=g) * 0.1)
     conv = conv.to(cuda)
-    f = _ConvBiasB(conv, ACT_RELU, cuda)
+    f = bf16.FoldedConvB(conv, None, ACT_RELU)
     x = torch.zeros(N, H, W, bf16.round8(cin), dtype=torch.bfloat16)
     x[..., :cin] = torch.randn(N, H, W, cin, generator=g).to(torch.bfloat16)
     ho, wo = f.layer.out_hw(H, W)

@@ -300,6 +300,7 @@ def many(cuda):
     real_graph, real_embed = syncnet._SyncGraph, S.embed_rows
 
     def counting_graph(*a, **k):
+        assert (a[5:] + (k.get("precision", "f32"),))[0] == "f32"                 # this module scores in fp32 only
         built.append(a[1:4])
         return real_graph(*a, **k)
 

@@ -55,7 +55,7 @@ def test_bf16_buffer_rule_is_a_function_of_the_batch_size():
     with pytest.raises(RuntimeError, match=r"batch of %d windows" % first):
         syncnet.check_bf16_buffers(first)
     with pytest.raises(RuntimeError, match="2 GiB"):                   # the graph checks before it allocates: no device is needed
-        syncnet._SyncGraphB(None, first, 48, 96, torch.device("cpu"))
+        syncnet._SyncGraph(None, first, 48, 96, torch.device("cpu"), precision="bf16")
 
 
 def _layers():

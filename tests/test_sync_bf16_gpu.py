@@ -257,25 +257,26 @@ def test_one_live_graph_and_the_switch_is_inference_only(cuda, oracle, monkeypat
     from wav2lip_amd.models import syncnet
     S = _syncnet(cuda)
     built = []
-    real = syncnet._SyncGraphB
+    real = syncnet._SyncGraph
 
     def counting(*a, **k):
-        built.append(a[1:4])
+        if (a[5:] + (k.get("precision", "f32"),))[0] == "bf16":                            # counts the bf16 graphs, as before
+            built.append(a[1:4])
         return real(*a, **k)
 
-    monkeypatch.setattr(syncnet, "_SyncGraphB", counting)
+    monkeypatch.setattr(syncnet, "_SyncGraph", counting)
     m, f = oracle["mels"].to(cuda), oracle["faces"].to(cuda)
     a0, v0 = S(m, f)
     assert len(S._graphs) == 1 and built == []
     ab, vb = S(m, f, precision="bf16")
     assert len(S._graphs) == 1 and built == [(8, 48, 96)]
-    assert isinstance(next(iter(S._graphs.values()))[1], real)
+    assert next(iter(S._graphs.values()))[1].precision == "bf16"
     ab2, vb2 = S(m, f, precision="bf16")
     assert built == [(8, 48, 96)] and _same(ab, ab2) and _same(vb, vb2)          # the second call builds nothing new
     names = [d[0] for d in next(iter(S._graphs.values()))[1].dispatch()]
     assert len(names) == 17 + 14 and names[0] == "face_encoder.0" and names[-1] == "audio_encoder.13"
     a1, v1 = S(m, f)
-    assert len(S._graphs) == 1 and isinstance(next(iter(S._graphs.values()))[1], syncnet._SyncGraph)
+    assert len(S._graphs) == 1 and next(iter(S._graphs.values()))[1].precision == "f32"
     assert _same(a0, a1) and _same(v0, v1)
     assert not _same(a0, ab)                                                        # and bf16 was a different computation
     S.train()

@@ -31,14 +31,12 @@ from wav2lip_amd import synthetic as synth  # noqa: E402
 PADS = (0, 0, 0, 0)
 BUILDS = [0]
 _mod = sys.modules["wav2lip_amd.face_detection.s3fd"]        # `face_detection.s3fd` is the class; this is its module
-_real = {"_Graph": _mod._Graph, "_GraphB": _mod._GraphB}
+_real_graph = _mod._Graph
 
 
-def _counting(name):
-    def make(*a, **k):
-        BUILDS[0] += 1
-        return _real[name](*a, **k)
-    return make
+def _counting_graph(*a, **k):
+    BUILDS[0] += 1
+    return _real_graph(*a, **k)
 
 
 def clips_with_faces(n, seed):
@@ -95,7 +93,7 @@ def main(argv=None):
     dev = torch.device("cuda", 0)
     clips = clips_with_faces(a.clips, a.seed)
     frames = sum(len(c) for c in clips)
-    _mod._Graph, _mod._GraphB = _counting("_Graph"), _counting("_GraphB")
+    _mod._Graph = _counting_graph
     out = {"clips": a.clips, "frames": frames, "batch": a.batch, "precision": a.precision, "alternations": a.alternations}
     loops = {"packed": (run_packed, detector(dev, a.precision)), "per_clip": (run_loop, detector(dev, a.precision))}
     res = {k: {"frames_per_s": [], "graph_builds": []} for k in loops}

@@ -78,7 +78,7 @@ def _time(net, img, steps, prec, det_scale=1):
 
 
 def _macs(g, B):
-    if hasattr(g, "plans"):          # bf16 graph: the convb plans (executed FLOPs / 2) and the heads' 3x3 contractions
+    if g.precision == "bf16":        # bf16 graph: the convb plans (executed FLOPs / 2) and the heads' 3x3 contractions
         macs = sum(fl for p in g.plans for _, fl, _, _ in p.resolved()) // 2
         return macs + sum(op[2].N * op[2].H * op[2].W * op[2].C * 9 * (op[1].ncls + 4) for op in g.ops if op[0] == "head")
     return sum(op[1].macs() for op in g.ops if op[0] == "convs")

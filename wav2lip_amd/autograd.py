@@ -130,12 +130,7 @@ def describe(blk):
 def block_geom(blk, act=None):
     """the ConvGeom of a block's conv, with the block's own activation or `act` in its place"""
     conv, _, blk_act, transposed, _ = describe(blk)
-    kh, kw = engine._pair(conv.kernel_size)
-    sh, sw = engine._pair(conv.stride)
-    ph, pw = engine._pair(conv.padding)
-    oph, opw = engine._pair(conv.output_padding) if transposed else (0, 0)
-    return ConvGeom(int(transposed), conv.in_channels, conv.out_channels, kh, kw, sh, sw, ph, pw, oph, opw,
-                    blk_act if act is None else act)
+    return bf16.conv_geom(conv, transposed, blk_act if act is None else act)
 
 
 def out_hw(geom, H, W):

@@ -14,8 +14,24 @@ from . import _lib
 from ._lib import ConvGeom, check, current_stream, ptr
 
 
+BUF_LIMIT = 1 << 31      # bytes: the per-buffer rule of the bf16 kernels (32-bit byte offsets, W2L_REQUIRE in every launch)
+
+
 def round8(c):
     return (c + 7) // 8 * 8
+
+
+def _pair(v):
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
+def conv_geom(conv, transposed, act):
+    """the ConvGeom of a torch Conv2d / ConvTranspose2d with activation `act`"""
+    kh, kw = _pair(conv.kernel_size)
+    sh, sw = _pair(conv.stride)
+    ph, pw = _pair(conv.padding)
+    oph, opw = _pair(conv.output_padding) if transposed else (0, 0)
+    return ConvGeom(int(transposed), conv.in_channels, conv.out_channels, kh, kw, sh, sw, ph, pw, oph, opw, act)
 
 
 class ActB:
@@ -187,6 +203,26 @@ class ConvB:
                 self.handle = None
         except Exception:
             pass
+
+
+class FoldedConvB:
+    """one convolution as a bf16-storage layer for inference: the ConvB handle (unscaled bf16 weights) and its bias - with `bn`, an
+    eval-mode BatchNorm, folded in as well - as fp32 scale / shift vectors that the launch applies to its fp32 accumulators
+    (w2l_bn_fold; the fold of NodeB's "bn_eval" kind).  The scale is NOT folded into the bf16 weights: that would round them a
+    second time."""
+
+    def __init__(self, conv, bn, act, transposed=False):
+        self.geom = conv_geom(conv, transposed, act)
+        self.layer = ConvB(self.geom, conv.weight)
+        self.weight = conv.weight
+        self.cout, self.out_hw = self.layer.cout, self.layer.out_hw       # the conv's own (a head attached later changes layer.cout)
+        cp = (self.cout + 31) // 32 * 32
+        self.scale = torch.zeros(cp, device=conv.weight.device)
+        self.shift = torch.zeros(cp, device=conv.weight.device)
+        stats = [] if bn is None else [bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        self._keep = [None if t is None else t.detach().float().contiguous() for t in [conv.bias] + stats] + [None] * (4 - len(stats))
+        check(_lib.load().w2l_bn_fold(current_stream(), self.cout, *[ptr(t) for t in self._keep], float(bn.eps) if bn is not None else 0.0,
+                                      ptr(self.scale), ptr(self.shift)), "bn_fold")
 
 
 def plan_dispatch(plan, N=None):

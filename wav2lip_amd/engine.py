@@ -11,8 +11,9 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, bf16
 from ._lib import ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID, ConvGeom, check, ptr
+from .bf16 import _pair, conv_geom
 
 
 # Launch configurations (tile, split-K) come from the committed shape-keyed table (wav2lip_amd/tune_table.json, loaded by
@@ -132,10 +133,6 @@ HIP_GRAPHS = os.environ.get("W2L_HIP_GRAPHS", "0") == "1"
 WGRAD_OVERLAP = os.environ.get("W2L_WGRAD_OVERLAP", "1") != "0"
 
 
-def _pair(v):
-    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
-
-
 def require_cuda(t, what):
     if not t.is_cuda:
         raise RuntimeError(
@@ -153,15 +150,11 @@ class FusedConv:
         require_cuda(w, "conv weight")
         w = w.contiguous().float()
         dev = w.device
-        kh, kw = _pair(conv.kernel_size)
-        sh, sw = _pair(conv.stride)
-        ph, pw = _pair(conv.padding)
-        oph, opw = _pair(conv.output_padding) if transposed else (0, 0)
         if _pair(conv.dilation) != (1, 1) or conv.groups != 1:
             raise RuntimeError("dilation/groups are not part of the Wav2Lip hot path")
         cin = conv.in_channels
         cout = conv.out_channels
-        self.geom = ConvGeom(int(transposed), cin, cout, kh, kw, sh, sw, ph, pw, oph, opw, act)
+        self.geom = conv_geom(conv, transposed, act)
         self.cin, self.cout = cin, cout
         self.cin_p = lib.w2l_conv_cin_padded(cin)
         self.device = dev
@@ -387,21 +380,98 @@ class Plan:
             pass
 
 
-class BufPool:
-    """Trivial free-list of NHWC scratch buffers keyed by shape: ping-pong reuse inside a plan."""
+PRECISIONS = ("f32", "bf16")
 
-    def __init__(self, device):
-        self.device = device
+
+def check_precision(precision):
+    if precision not in PRECISIONS:
+        raise ValueError("precision must be 'f32' or 'bf16', got %r" % (precision,))
+    return precision
+
+
+class _StorageF32:
+    """How an INFERENCE graph stores its activations, and everything that follows from it: the buffers, the layer objects and how
+    a plan records them, and the glue entry points.  F32 (below): NHWC fp32, exact channel counts, FusedConv layers (BatchNorm
+    folded into the weights' epilogue at creation, cached on their block), configurations from the table / plan_configs.json."""
+    name, suffix, itemsize = "f32", "", 4
+    act = Act
+    shape_tuned = False         # the finished plan still takes its configurations from the table / the per-plan lists
+
+    def channels(self, c):
+        return c
+
+    def new_buf(self, N, H, W, Ctot, device, zero=False):
+        return new_buf(N, H, W, Ctot, device, zero)
+
+    def layer_of(self, obj, act, cache=None):
+        """the layer of a mirrored block (its own activation) or of a bare nn.Conv2d with `act` (kept in `cache`, the owner's)"""
+        if hasattr(obj, "fused"):
+            return obj.fused()
+        if (obj, act) not in cache:
+            cache[(obj, act)] = FusedConv(obj, None, act)
+        return cache[(obj, act)]
+
+    def record(self, plan, name, layer, src, dst, res=None):
+        plan.add(name, layer, src, dst, res)
+
+    def bind(self, lib, name):
+        """entry point `w2l_<name>` of this storage as a checked call (looked up once, when a graph is built)"""
+        fn, what = getattr(lib, "w2l_" + name + self.suffix), name + self.suffix
+
+        def call(*args):
+            check(fn(*args), what)
+        return call
+
+
+class _StorageBF16(_StorageF32):
+    """BF16: NHWC bf16, channel counts rounded up to 8 and always zeroed (bf16.new_buf), a fresh bf16.FoldedConvB per layer and
+    graph (fp32 scale / shift applied by the launch), configurations from the shapes alone."""
+    name, suffix, itemsize = "bf16", "_bf16", 2
+    act = bf16.ActB
+    shape_tuned = True          # nothing to autotune
+
+    def channels(self, c):
+        return bf16.round8(c)
+
+    def new_buf(self, N, H, W, Ctot, device, zero=False):
+        return bf16.new_buf(N, H, W, Ctot, device)
+
+    def layer_of(self, obj, act, cache=None):
+        if not hasattr(obj, "conv_block"):
+            return bf16.FoldedConvB(obj, None, act)
+        bn = obj.conv_block[1] if obj._norm else None
+        if bn is not None and bn.training:
+            obj.fused()          # raises: a train-mode BatchNorm block has no folded form
+        return bf16.FoldedConvB(obj.conv_block[0], bn, obj._act, obj._transposed)
+
+    def record(self, plan, name, layer, src, dst, res=None):
+        plan.add_convb(name, layer.layer, src, dst, res, layer.scale, layer.shift)
+        plan.keep.append(layer)
+
+
+F32, BF16 = _StorageF32(), _StorageBF16()
+
+
+def storage(precision):
+    """the storage descriptor of an inference `precision` ("f32" | "bf16"; ValueError otherwise)"""
+    return BF16 if check_precision(precision) == "bf16" else F32
+
+
+class BufPool:
+    """Trivial free-list of NHWC scratch buffers of one storage keyed by shape: ping-pong reuse inside a plan."""
+
+    def __init__(self, device, st=F32):
+        self.device, self.st = device, st
         self.free = {}
         self.total_bytes = 0
 
     def get(self, N, H, W, Ctot):
-        key = (N, H, W, Ctot)
+        key = (N, H, W, self.st.channels(Ctot))
         lst = self.free.get(key)
         if lst:
             return lst.pop()
-        self.total_bytes += 4 * N * H * W * Ctot
-        return new_buf(N, H, W, Ctot, self.device)
+        self.total_bytes += self.st.itemsize * N * H * W * key[3]
+        return self.st.new_buf(N, H, W, Ctot, self.device)
 
     def put(self, buf):
         self.free.setdefault(tuple(buf.shape), []).append(buf)
@@ -446,17 +516,13 @@ class on_device_of:
             self._ctx.__exit__(*a)
 
 
-def layers_of(seq):
-    """fused layers of an nn.Sequential of mirrored blocks (builds lazily, cached on the block)"""
-    return [blk.fused() for blk in seq]
-
-
 def run_chain(plan, pool, name, blocks, src, final_dst=None):
-    """Record a chain of blocks src -> ... -> final_dst (or a pooled scratch buffer); returns the last Act."""
+    """Record a chain of blocks src -> ... -> final_dst (or a pooled scratch buffer) in the pool's storage; returns the last Act."""
+    st = pool.st
     x = src
     owned = None  # scratch buffer currently holding x (to be released when dead)
     for j, blk in enumerate(blocks):
-        layer = blk.fused()
+        layer = st.layer_of(blk, None)
         ho, wo = layer.out_hw(x.H, x.W)
         last = j == len(blocks) - 1
         if last and final_dst is not None:
@@ -464,10 +530,10 @@ def run_chain(plan, pool, name, blocks, src, final_dst=None):
             new_owned = None
         else:
             buf = pool.get(x.N, ho, wo, layer.cout)
-            dst = Act(buf, 0, layer.cout)
+            dst = st.act(buf, 0, layer.cout)
             new_owned = buf
         res = x if getattr(blk, "residual", False) else None
-        plan.add("%s.%d" % (name, j), layer, x, dst, res)
+        st.record(plan, "%s.%d" % (name, j), layer, x, dst, res)
         if owned is not None:
             pool.put(owned)
         owned = new_owned

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from ._lib import check, current_stream, load, ptr
+from .inference import _precision_kw
 
 syncnet_T = 5
 mel_step = 16
@@ -111,13 +112,6 @@ def _score_segments(n_seg, segs, vshift, face_emb, audio_emb, out):
     """w2l_lse_score_segments into `out`, fp32 [n_seg * (4 + win)]: the [n_seg][4] scores, then the [n_seg][win] mean distances"""
     check(load().w2l_lse_score_segments(current_stream(), n_seg, ptr(segs), face_emb.shape[1], vshift, ptr(face_emb),
                                         ptr(audio_emb), out.data_ptr() + 16 * n_seg, ptr(out)), "lse_score_segments")
-
-
-def _precision_kw(precision):
-    """the keyword a SyncNet call takes for `precision`, checked first (models.wav2lip.check_precision): none for "f32", so a
-    scorer object that knows nothing of the switch keeps working on the default path"""
-    from .models.wav2lip import check_precision
-    return {} if check_precision(precision) == "f32" else {"precision": precision}
 
 
 def _score_group(syncnet, clips, vshift, batch_size, precision="f32"):

@@ -4,7 +4,7 @@ through the Winograd kernel), max-pools, L2Norm and the box decode are the glue 
 Activations are NHWC fp32; the detection heads write (conf, loc) maps that `w2l_s3fd_decode` turns into dense
 (x1, y1, x2, y2, score) tables, one per pyramid level.
 
-`dense_boxes(images, precision="bf16")` runs the opt-in bf16-storage graph (_GraphB) instead: bf16 NHWC activations, the
+`dense_boxes(images, precision="bf16")` runs the graph in bf16 storage instead (opt-in): bf16 NHWC activations, the
 convolutions as `w2l_convb` launches (bias as the fp32 shift, ReLU), the bf16 glue kernels of csrc/detect_bf16.hip and one fused
 head per level (`w2l_s3fd_headb_decode`: conf + loc contraction and decode, the logits never leave the chip).
 
@@ -18,8 +18,7 @@ import torch
 from torch import nn
 
 from .. import bf16, engine
-from .._lib import ACT_NONE, ACT_RELU, ConvGeom, check, current_stream, load, ptr
-from ..engine import Act
+from .._lib import ACT_NONE, ACT_RELU, check, current_stream, load, ptr
 
 # (name, cin, cout, kernel, stride, padding), net_s3fd.py:25-48
 BACKBONE = [("conv1_1", 3, 64, 3, 1, 1), ("conv1_2", 64, 64, 3, 1, 1), "pool",
@@ -44,88 +43,7 @@ class L2Norm(nn.Module):
         self.weight = nn.Parameter(torch.full((n_channels,), float(scale)))
 
 
-class _Graph:
-    """buffers + launch list for one (batch, height, width)"""
-
-    def __init__(self, model, B, H, W, device):
-        self.lib = load()
-        self.B, self.H, self.W = B, H, W
-        self.x_in = engine.new_buf(B, H, W, 4, device, zero=True)
-        self.ops = []          # ("convs", Plan) | ("pool", src, dst) | ("l2norm", src, weight, dst)
-        self.keep = []
-        plan = None
-
-        def flush():
-            nonlocal plan
-            if plan is not None:
-                self.ops.append(("convs", plan))
-                plan = None
-
-        def conv(name, src, act, cout_buf=None):
-            nonlocal plan
-            layer = model._layer(name, act)
-            ho, wo = layer.out_hw(src.H, src.W)
-            ct = (layer.cout + 3) // 4 * 4
-            dst = Act(engine.new_buf(B, ho, wo, ct, device, zero=(ct != layer.cout)), 0, layer.cout)
-            if plan is None:
-                plan = engine.Plan()
-            plan.add(name, layer, src, dst)
-            return dst
-
-        x = Act(self.x_in, 0, 4)
-        taps = {}
-        for item in BACKBONE:
-            if item == "pool":
-                flush()
-                if x.H < 2 or x.W < 2:
-                    raise RuntimeError("image too small for the S3FD pyramid")
-                dst = Act(engine.new_buf(B, x.H // 2, x.W // 2, x.C, device), 0, x.C)
-                self.ops.append(("pool", x, dst))
-                x = dst
-            elif isinstance(item, str):
-                taps[item[4:]] = x
-            else:
-                x = conv(item[0], x, ACT_RELU)
-        flush()
-        self.levels = []       # (conf Act, loc Act, ncls, stride)
-        for i, (feat, norm, ncls) in enumerate(HEADS):
-            f = taps[feat]
-            src = f
-            prefix = feat
-            if norm is not None:
-                flush()
-                nb = Act(engine.new_buf(B, f.H, f.W, f.C, device), 0, f.C)
-                self.ops.append(("l2norm", f, getattr(model, norm).weight, nb))
-                src = nb
-                prefix = norm
-            conf = conv(prefix + "_mbox_conf", src, ACT_NONE)
-            loc = conv(prefix + "_mbox_loc", src, ACT_NONE)
-            self.levels.append((conf, loc, ncls, 2 ** (i + 2)))
-        flush()
-        self.dense = [torch.empty((B, c.H * c.W, 5), device=device, dtype=torch.float32) for c, _, _, _ in self.levels]
-
-    def run(self):
-        s = current_stream()
-        lib = self.lib
-        for op in self.ops:
-            if op[0] == "convs":
-                op[1].run()
-            elif op[0] == "pool":
-                _, a, d = op
-                check(lib.w2l_maxpool2x2(s, a.N, a.H, a.W, a.C, a.ptr, a.cs, d.ptr, d.cs), "maxpool2x2")
-            else:
-                _, a, w, d = op
-                check(lib.w2l_l2norm_scale(s, a.N * a.H * a.W, a.C, a.ptr, a.cs, ptr(w.detach()), d.ptr, d.cs), "l2norm_scale")
-
-    def decode(self):
-        s = current_stream()
-        for (conf, loc, ncls, stride), out in zip(self.levels, self.dense):
-            check(self.lib.w2l_s3fd_decode(s, self.B, conf.H, conf.W, stride, conf.ptr, conf.cs, ncls, loc.ptr, loc.cs,
-                                           ptr(out)), "s3fd_decode")
-        return self.dense
-
-
-MIN_FRAME = 32           # the smallest height / width both graphs take: five 2x2 max-pools, each of at least 2 x 2 (_Graph, _GraphB)
+MIN_FRAME = 32           # the smallest height / width the graph takes: five 2x2 max-pools, each of at least 2 x 2 (_Graph)
 MAX_DET_SCALE = 8
 
 
@@ -160,11 +78,8 @@ def scale_box(box, sx, sy):
     return np.asarray(box, dtype=np.float32) * np.array([sx, sy, sx, sy], dtype=np.float32)
 
 
-BUF_LIMIT = 1 << 31      # bytes: the per-buffer rule of the bf16 kernels (32-bit byte offsets, W2L_REQUIRE in every launch)
-
-
 def _bf16_buffer_sizes(B, H, W):
-    """bytes of every buffer _GraphB would allocate for (B, H, W), computed from the shapes alone"""
+    """bytes of every buffer the bf16 _Graph would allocate for (B, H, W), computed from the shapes alone"""
     sizes = [2 * B * H * W * 8]                                   # packed input, 8 channels
     h, w, taps = H, W, {}
     for item in BACKBONE:
@@ -187,26 +102,6 @@ def _bf16_buffer_sizes(B, H, W):
             sizes.append(2 * B * fh * fw * c)
         sizes.append(4 * B * fh * fw * 5)                         # the level's dense table (fp32)
     return sizes
-
-
-class _ConvBiasB:
-    """one plain convolution (bias + activation, no BatchNorm) as a bf16-storage layer: the bf16.ConvB handle and the bias as the
-    fp32 shift with scale 1 (w2l_bn_fold without BatchNorm), applied to the fp32 accumulators - the counterpart of
-    models.wav2lip._FoldedConvB"""
-
-    def __init__(self, conv, act, device):
-        kh, kw = engine._pair(conv.kernel_size)
-        sh, sw = engine._pair(conv.stride)
-        ph, pw = engine._pair(conv.padding)
-        self.geom = ConvGeom(0, conv.in_channels, conv.out_channels, kh, kw, sh, sw, ph, pw, 0, 0, act)
-        self.layer = bf16.ConvB(self.geom, conv.weight)
-        cp = (conv.out_channels + 31) // 32 * 32
-        self.scale = torch.zeros(cp, device=device)
-        self.shift = torch.zeros(cp, device=device)
-        bias = conv.bias.detach().float().contiguous() if conv.bias is not None else None
-        check(load().w2l_bn_fold(current_stream(), conv.out_channels, ptr(bias), None, None, None, None, 0.0, ptr(self.scale),
-                                 ptr(self.shift)), "bn_fold")
-        self._keep = bias
 
 
 class _HeadB:
@@ -236,19 +131,25 @@ class _HeadB:
             pass
 
 
-class _GraphB:
-    """the bf16-storage detector for one (batch, height, width): bf16 NHWC buffers, the backbone as convb plans (bias as shift,
-    ReLU), bf16 max-pools and L2Norms, one fused head per level writing the dense tables directly"""
+class _Graph:
+    """buffers + launch list for one (batch, height, width) in one storage (engine.storage).  "f32": fp32 NHWC buffers, FusedConv
+    plans, two head convolutions per level and `decode`.  "bf16", the opt-in bf16-storage detector: bf16 NHWC buffers, the backbone
+    as convb plans (bias as the fp32 shift, ReLU), bf16 max-pools and L2Norms, one fused head per level writing the dense tables
+    directly."""
 
-    def __init__(self, model, B, H, W, device):
-        big = max(_bf16_buffer_sizes(B, H, W))
-        if big >= BUF_LIMIT:
-            # checked before anything is allocated: inference._detect_rects halves the batch on this error, as for fp32
-            raise RuntimeError("S3FD bf16: a %d x %d x %d batch needs a %d-byte buffer, over the kernels' 2 GiB limit: split the "
-                               "batch" % (B, H, W, big))
-        self.lib = load()
+    def __init__(self, model, B, H, W, device, precision="f32"):
+        st = self.st = engine.storage(precision)
+        self.precision = st.name
+        if st is engine.BF16:
+            big = max(_bf16_buffer_sizes(B, H, W))
+            if big >= bf16.BUF_LIMIT:
+                # checked before anything is allocated: inference._detect_rects halves the batch on this error, as for fp32
+                raise RuntimeError("S3FD bf16: a %d x %d x %d batch needs a %d-byte buffer, over the kernels' 2 GiB limit: split the "
+                                   "batch" % (B, H, W, big))
+        self.lib = lib = load()
         self.B, self.H, self.W = B, H, W
-        self.x_in = bf16.new_buf(B, H, W, 8, device)
+        self.x_in = st.new_buf(B, H, W, 4, device, zero=True)        # RGB + zero pad: 4 channels in fp32, 8 in bf16
+        self.x_cs = self.x_in.shape[3]
         self.ops = []          # ("convs", Plan) | ("pool", src, dst) | ("l2norm", src, weight, dst) | ("head", _HeadB, src, stride, out)
         self.plans = []
         plan = None
@@ -256,84 +157,114 @@ class _GraphB:
         def flush():
             nonlocal plan
             if plan is not None:
-                plan.tuned = True          # launch configurations come from the shapes: nothing to autotune
+                plan.tuned = st.shape_tuned
                 self.ops.append(("convs", plan))
                 self.plans.append(plan)
                 plan = None
 
-        x = bf16.ActB(self.x_in, 0, 3)
+        def conv(name, src, act):
+            nonlocal plan
+            layer = st.layer_of(getattr(model, name), act, model._layers)
+            ho, wo = layer.out_hw(src.H, src.W)
+            ct = (layer.cout + 3) // 4 * 4          # fp32 rounds an output to 4 channels (bf16 buffers round to 8 and are zeroed anyway)
+            dst = st.act(st.new_buf(B, ho, wo, ct, device, zero=(ct != layer.cout)), 0, layer.cout)
+            if plan is None:
+                plan = engine.Plan()
+            st.record(plan, name, layer, src, dst)
+            return dst
+
+        x = st.act(self.x_in, 0, 3)
         taps = {}
         for item in BACKBONE:
             if item == "pool":
                 flush()
-                dst = bf16.ActB(bf16.new_buf(B, x.H // 2, x.W // 2, x.C, device), 0, x.C)
+                if x.H < 2 or x.W < 2:
+                    raise RuntimeError("image too small for the S3FD pyramid")
+                dst = st.act(st.new_buf(B, x.H // 2, x.W // 2, x.C, device), 0, x.C)
                 self.ops.append(("pool", x, dst))
                 x = dst
             elif isinstance(item, str):
                 taps[item[4:]] = x
             else:
-                f = _ConvBiasB(getattr(model, item[0]), ACT_RELU, device)
-                ho, wo = f.layer.out_hw(x.H, x.W)
-                dst = bf16.ActB(bf16.new_buf(B, ho, wo, f.layer.cout, device), 0, f.layer.cout)
-                if plan is None:
-                    plan = engine.Plan()
-                plan.add_convb(item[0], f.layer, x, dst, None, f.scale, f.shift)
-                plan.keep.append(f)
-                x = dst
+                x = conv(item[0], x, ACT_RELU)
         flush()
+        self.levels = []       # fp32 only: (conf Act, loc Act, ncls, stride), what `decode` and s3fd.forward read
         self.dense = []
         for i, (feat, norm, ncls) in enumerate(HEADS):
-            src = taps[feat]
-            prefix = feat
+            src, prefix = taps[feat], feat
             if norm is not None:
-                nb = bf16.ActB(bf16.new_buf(B, src.H, src.W, src.C, device), 0, src.C)
+                flush()
+                nb = st.act(st.new_buf(B, src.H, src.W, src.C, device), 0, src.C)
                 self.ops.append(("l2norm", src, getattr(model, norm).weight, nb))
-                src = nb
-                prefix = norm
-            head = _HeadB(getattr(model, prefix + "_mbox_conf"), getattr(model, prefix + "_mbox_loc"), ncls)
+                src, prefix = nb, norm
             out = torch.empty((B, src.H * src.W, 5), device=device, dtype=torch.float32)
-            self.ops.append(("head", head, src, 2 ** (i + 2), out))
+            if st is engine.F32:
+                conf = conv(prefix + "_mbox_conf", src, ACT_NONE)
+                loc = conv(prefix + "_mbox_loc", src, ACT_NONE)
+                self.levels.append((conf, loc, ncls, 2 ** (i + 2)))
+            else:
+                head = _HeadB(getattr(model, prefix + "_mbox_conf"), getattr(model, prefix + "_mbox_loc"), ncls)
+                self.ops.append(("head", head, src, 2 ** (i + 2), out))
             self.dense.append(out)
+        flush()
+        self._maxpool, self._l2norm = st.bind(lib, "maxpool2x2"), st.bind(lib, "l2norm_scale")
+        self._pack, self._pack_rows = st.bind(lib, "s3fd_pack"), st.bind(lib, "s3fd_pack_rows")
+        self._pack_rows_scaled = st.bind(lib, "s3fd_pack_rows_scaled")
 
-    def run(self):
+    def pack(self, img):
+        """`x_in` from contiguous uint8 [B,H,W,3] BGR frames on the device"""
+        self._pack(current_stream(), self.B * self.H * self.W, ptr(img), ptr(self.x_in), self.x_cs)
+
+    def pack_rows(self, frames, H, W, det_scale):
+        """`x_in` from a device table of B frame addresses (uint8 [H,W,3] BGR each); det_scale > 1: resized to the graph's size"""
+        if det_scale > 1:
+            self._pack_rows_scaled(current_stream(), self.B, H, W, self.H, self.W, ptr(frames), ptr(self.x_in), self.x_cs)
+        else:
+            self._pack_rows(current_stream(), self.B, H, W, ptr(frames), ptr(self.x_in), self.x_cs)
+
+    def run_ops(self):
         s = current_stream()
-        lib = self.lib
         for op in self.ops:
             if op[0] == "convs":
                 op[1].run()
             elif op[0] == "pool":
                 _, a, d = op
-                check(lib.w2l_maxpool2x2_bf16(s, a.N, a.H, a.W, a.C, a.ptr, a.cs, d.ptr, d.cs), "maxpool2x2_bf16")
+                self._maxpool(s, a.N, a.H, a.W, a.C, a.ptr, a.cs, d.ptr, d.cs)
             elif op[0] == "l2norm":
                 _, a, w, d = op
-                check(lib.w2l_l2norm_scale_bf16(s, a.N * a.H * a.W, a.C, a.ptr, a.cs, ptr(w.detach()), d.ptr, d.cs),
-                      "l2norm_scale_bf16")
+                self._l2norm(s, a.N * a.H * a.W, a.C, a.ptr, a.cs, ptr(w.detach()), d.ptr, d.cs)
             else:
                 _, head, a, stride, out = op
                 head.decode(a, stride, out)
+
+    def run(self):
+        """every launch of the graph; returns the dense tables, one float32 [B, FH*FW, 5] per level"""
+        self.run_ops()
+        s = current_stream()
+        for (conf, loc, ncls, stride), out in zip(self.levels, self.dense):      # fp32: the bf16 heads wrote the tables themselves
+            check(self.lib.w2l_s3fd_decode(s, self.B, conf.H, conf.W, stride, conf.ptr, conf.cs, ncls, loc.ptr, loc.cs,
+                                           ptr(out)), "s3fd_decode")
         return self.dense
 
     def dispatch(self):
-        """[(layer, family, tile, ksplit)] of every backbone convolution (bf16.plan_dispatch): the convb kernel each one runs"""
+        """[(layer, family, tile, ksplit)] of every bf16-storage convolution (bf16.plan_dispatch): the convb kernel each one runs"""
         return [d for p in self.plans for d in bf16.plan_dispatch(p)]
 
     def resolved(self):
-        """[(layer, kernel family)] of every launch in order: the convb plans' Plan.resolved() families and the glue launches
-        (pool1..pool5, the L2Norm modules, the heads named by their feature)"""
-        fams, npool, heads = [], 0, iter(HEADS)
+        """[(layer, kernel family)] of every launch of `run_ops` in order: the plans' Plan.resolved() families and the glue launches
+        (pool1..pool5, the L2Norm modules, the fused heads named by their feature)"""
+        fams, npool, norms, heads = [], 0, iter(n for _, n, _ in HEADS if n), iter(HEADS)
         for op in self.ops:
             if op[0] == "convs":
                 fams += [(name, fam) for name, _, fam, _ in op[1].resolved()]
             elif op[0] == "pool":
                 npool += 1
-                fams.append(("pool%d" % npool, "maxpool2x2_bf16"))
+                fams.append(("pool%d" % npool, "maxpool2x2" + self.st.suffix))
             elif op[0] == "l2norm":
-                fams.append(("l2norm", "l2norm_scale_bf16"))
+                fams.append((next(norms), "l2norm_scale" + self.st.suffix))
             else:
                 feat, norm, _ = next(heads)
                 fams.append(("%s_mbox" % (norm or feat), "s3fd_headb"))
-                if norm is not None:
-                    fams[-2] = (norm, "l2norm_scale_bf16")
         return fams
 
 
@@ -352,15 +283,9 @@ class s3fd(nn.Module):
             prefix = norm or feat
             setattr(self, prefix + "_mbox_conf", nn.Conv2d(cins[feat], ncls, kernel_size=3, stride=1, padding=1))
             setattr(self, prefix + "_mbox_loc", nn.Conv2d(cins[feat], 4, kernel_size=3, stride=1, padding=1))
-        self._layers = {}
+        self._layers = {}       # the fp32 layers, (conv, activation) -> engine.FusedConv: shared by the graphs of one weight version
         self._graphs = {}
         self._version = None
-
-    def _layer(self, name, act):
-        key = (name, act)
-        if key not in self._layers:
-            self._layers[key] = engine.FusedConv(getattr(self, name), None, act)
-        return self._layers[key]
 
     def _graph(self, B, H, W, device, precision="f32"):
         ver = engine.param_version(self)
@@ -369,7 +294,7 @@ class s3fd(nn.Module):
         key = (B, H, W, str(device), precision)
         g = self._graphs.get(key)
         if g is None:
-            g = (_GraphB if precision == "bf16" else _Graph)(self, B, H, W, torch.device(device))
+            g = _Graph(self, B, H, W, torch.device(device), precision)
             self._graphs = {key: g}        # one live geometry: VGG activations of a video frame batch are large
         return g
 
@@ -383,7 +308,7 @@ class s3fd(nn.Module):
         lib = load()
         s = current_stream()
         check(lib.w2l_nchw_to_nhwc(s, B, Cn, H, W, ptr(x), ptr(g.x_in), 4, 4), "nchw_to_nhwc")
-        g.run()
+        g.run_ops()
         outs = []
         for conf, loc, ncls, _ in g.levels:
             for a in (conf, loc):
@@ -400,8 +325,7 @@ class s3fd(nn.Module):
         bf16-storage graph; a batch whose buffers would reach 2 GiB raises RuntimeError before anything is allocated).
         `det_scale` k > 1: the graph of (H // k, W // k) on the frames resized as cv2.resize does (`dense_boxes_rows` over an
         address table of the batch); the tables are in the reduced frame's coordinates."""
-        from ..models.wav2lip import check_precision
-        check_precision(precision)
+        engine.check_precision(precision)
         det_scale = check_det_scale(det_scale)
         if images_bgr_u8.dtype != torch.uint8 or images_bgr_u8.dim() != 4 or images_bgr_u8.shape[3] != 3:
             raise RuntimeError("dense_boxes: images must be uint8 [B,H,W,3]")
@@ -414,12 +338,8 @@ class s3fd(nn.Module):
             frames = torch.arange(B, dtype=torch.int64, device=img.device) * (H * W * 3) + img.data_ptr()
             return self.dense_boxes_rows(frames, B, H, W, precision, det_scale)
         g = self._graph(B, H, W, img.device, precision)
-        if precision == "bf16":
-            check(load().w2l_s3fd_pack_bf16(current_stream(), B * H * W, ptr(img), ptr(g.x_in), 8), "s3fd_pack_bf16")
-            return g.run()
-        check(load().w2l_s3fd_pack(current_stream(), B * H * W, ptr(img), ptr(g.x_in), 4), "s3fd_pack")
-        g.run()
-        return g.decode()
+        g.pack(img)
+        return g.run()
 
     def dense_boxes_rows(self, frames, B, H, W, precision="f32", det_scale=1):
         """`dense_boxes` for B frames named by a device address table: `frames` is a device tensor holding B uint64 addresses, each
@@ -427,26 +347,14 @@ class s3fd(nn.Module):
         batch need not be neighbours, nor of one clip.  Same graph, same launches and the same tables as `dense_boxes` on the
         gathered frames.  `det_scale` k > 1: the graph is the one of (B, H // k, W // k) and `w2l_s3fd_pack_rows_scaled` fills its
         input from the full-size frames."""
-        from ..models.wav2lip import check_precision
-        check_precision(precision)
+        engine.check_precision(precision)
         Hd, Wd = det_size(H, W, det_scale)
         engine.require_cuda(frames, "frame address table")
         if frames.numel() * frames.element_size() < 8 * B or frames.data_ptr() % 8:
             raise RuntimeError("dense_boxes_rows: the table must hold %d 8-byte aligned addresses" % B)
         g = self._graph(B, Hd, Wd, frames.device, precision)
-        lib, s = load(), current_stream()
-        if precision == "bf16":
-            if det_scale > 1:
-                check(lib.w2l_s3fd_pack_rows_scaled_bf16(s, B, H, W, Hd, Wd, ptr(frames), ptr(g.x_in), 8), "s3fd_pack_rows_scaled_bf16")
-            else:
-                check(lib.w2l_s3fd_pack_rows_bf16(s, B, H, W, ptr(frames), ptr(g.x_in), 8), "s3fd_pack_rows_bf16")
-            return g.run()
-        if det_scale > 1:
-            check(lib.w2l_s3fd_pack_rows_scaled(s, B, H, W, Hd, Wd, ptr(frames), ptr(g.x_in), 4), "s3fd_pack_rows_scaled")
-        else:
-            check(lib.w2l_s3fd_pack_rows(s, B, H, W, ptr(frames), ptr(g.x_in), 4), "s3fd_pack_rows")
-        g.run()
-        return g.decode()
+        g.pack_rows(frames, H, W, det_scale)
+        return g.run()
 
 
 def nms_batch(table, gate, thresh, host_overflow=True):

@@ -192,28 +192,8 @@ class Wav2LipRunner:
                 return out
             return allf
         g = self._graph(n)
-        s = current_stream()
-        faces_u8 = faces_u8.contiguous()
-        if self.precision == "bf16":
-            check(self.lib.w2l_datagen_pack_bf16(s, n, img_size, ptr(faces_u8), ptr(g.x_in), 8, 8), "datagen_pack_bf16")
-            if mel_rows is not None:
-                check(self.lib.w2l_mel_gather_rows_bf16(s, ptr(mel_rows), n, ptr(g.mel_in), 8, 8), "mel_gather_rows_bf16")
-            elif mel_windows is not None:
-                mw = mel_windows.contiguous().float().view(n, 1, 80, 16)
-                check(self.lib.w2l_nchw_to_nhwc_bf16(s, n, 1, 80, 16, ptr(mw), ptr(g.mel_in), 8, 8), "nchw_to_nhwc_bf16")
-            else:
-                check(self.lib.w2l_mel_gather_bf16(s, ptr(mel), mel.shape[1], ptr(starts), n, ptr(g.mel_in), 8, 8),
-                      "mel_gather_bf16")
-        else:
-            check(self.lib.w2l_datagen_pack(s, n, img_size, ptr(faces_u8), ptr(g.x_in), 8, 8), "datagen_pack")
-            if mel_rows is not None:
-                check(self.lib.w2l_mel_gather_rows(s, ptr(mel_rows), n, ptr(g.mel_in), 4, 4), "mel_gather_rows")
-            elif mel_windows is not None:
-                mw = mel_windows.contiguous().float().view(n, 1, 80, 16)
-                check(self.lib.w2l_nchw_to_nhwc(s, n, 1, 80, 16, ptr(mw), ptr(g.mel_in), 4, 4), "nchw_to_nhwc")
-            else:
-                check(self.lib.w2l_mel_gather(s, ptr(mel), mel.shape[1], ptr(starts), n, ptr(g.mel_in), 4, 4),
-                      "mel_gather")
+        g.pack_faces(faces_u8.contiguous())
+        g.load_mel(mel, starts, windows=mel_windows, rows=mel_rows)
         g.run()
         if out is not None:
             if out.dtype != torch.uint8 or tuple(out.shape) != (n, img_size, img_size, 3) or not out.is_cuda or not out.is_contiguous():
@@ -223,10 +203,7 @@ class Wav2LipRunner:
         if out is None:
             out = torch.empty((n, img_size, img_size, 3), dtype=torch.uint8, device=self.device)
             self._out_u8[n] = out
-        if self.precision == "bf16":
-            out.copy_(g.frames)         # the plan's last launch wrote the uint8 frames
-        else:
-            check(self.lib.w2l_frames_to_u8(s, n, img_size, img_size, g.out.ptr, g.out.cs, ptr(out)), "frames_to_u8")
+        g.frames_into(out)
         self._last = g
         return out
 
@@ -429,8 +406,11 @@ LIPSYNC_DEPTH = 4     # batches in flight in lipsync() / main(): the depth bench
 
 
 def _precision_kw(precision):
-    """runner keyword for a non-default precision: fp32 runs build their runner with the same arguments as before the option"""
-    return {} if precision == "f32" else {"precision": precision}
+    """the keyword a runner, a detector or a SyncNet call takes for `precision`, checked first (engine.check_precision): none for
+    "f32", so the default path is called with the same arguments as before the option, and an object that knows nothing of the
+    switch keeps working on it"""
+    from .engine import check_precision
+    return {} if check_precision(precision) == "f32" else {"precision": precision}
 
 
 def lipsync(model, frames, wav, fps=25., batch_size=128, static=False, box=None, ranks=None, depth=None, precision="f32"):

@@ -5,7 +5,7 @@ from torch import nn
 
 from .. import autograd, bf16, engine
 from .._lib import check, current_stream, load, ptr
-from .wav2lip import _BufPoolB, _down, _res, _run_chain_b, audio_encoder_rows, check_precision, make_stack
+from .wav2lip import _down, _res, audio_encoder_rows, check_precision, make_stack
 
 SYNC_FACE_ENCODER = (                              # models/syncnet.py:11-33
     [("c", 15, 32, 7, 1, 3, 0),
@@ -14,29 +14,8 @@ SYNC_FACE_ENCODER = (                              # models/syncnet.py:11-33
     + [("c", 512, 512, 3, 2, 1, 0), ("c", 512, 512, 3, 1, 0, 0), ("c", 512, 512, 1, 1, 0, 0)])
 
 
-class _SyncGraph:
-    def __init__(self, model, N, H, W, device):
-        self.lib = load()
-        self.N, self.H, self.W = N, H, W
-        pool = engine.BufPool(device)
-        plan = engine.Plan()
-        self.face_in = engine.new_buf(N, H, W, 16, device, zero=True)   # 15 channels + 1 zero pad
-        self.mel_in = engine.new_buf(N, 80, 16, 4, device, zero=True)
-        self.face_out, _ = engine.run_chain(plan, pool, "face_encoder", list(model.face_encoder),
-                                            engine.Act(self.face_in, 0, 16))
-        self.audio_out, _ = engine.run_chain(plan, pool, "audio_encoder", list(model.audio_encoder),
-                                             engine.Act(self.mel_in, 0, 4))
-        for o in (self.face_out, self.audio_out):
-            if (o.H, o.W) != (1, 1):
-                raise RuntimeError("SyncNet encoders must end at 1x1, got %dx%d" % (o.H, o.W))
-        self.plan = plan
-
-
-BUF_LIMIT = 1 << 31      # bytes: the per-buffer rule of the bf16 kernels (32-bit byte offsets, W2L_REQUIRE in every launch)
-
-
 def bf16_buffer_sizes(N, H=48, W=96):
-    """bytes of every buffer _SyncGraphB allocates for batch N and an H x W face input, from the layer tables alone: the two bf16
+    """bytes of every buffer the bf16 _SyncGraph allocates for batch N and an H x W face input, from the layer tables alone: the two bf16
     inputs (16 and 8 channels), then every layer's bf16 output"""
     sizes = [2 * N * H * W * 16, 2 * N * 80 * 16 * 8]
     for rows, (h, w) in ((SYNC_FACE_ENCODER, (H, W)), (audio_encoder_rows(2), (80, 16))):
@@ -50,48 +29,69 @@ def bf16_buffer_sizes(N, H=48, W=96):
 
 
 def bf16_batch_limit(H=48, W=96):
-    """the first batch size at which a buffer of _SyncGraphB reaches 2 GiB (every size is linear in N)"""
-    return -(-BUF_LIMIT // max(bf16_buffer_sizes(1, H, W)))
+    """the first batch size at which a buffer of the bf16 _SyncGraph reaches 2 GiB (every size is linear in N)"""
+    return -(-bf16.BUF_LIMIT // max(bf16_buffer_sizes(1, H, W)))
 
 
 def check_bf16_buffers(N, H=48, W=96):
     big = max(bf16_buffer_sizes(N, H, W))
-    if big >= BUF_LIMIT:
+    if big >= bf16.BUF_LIMIT:
         raise RuntimeError("SyncNet bf16: a batch of %d windows (%d x %d) needs a %d-byte buffer, over the kernels' 2 GiB limit: "
                            "batches below %d fit" % (N, H, W, big, bf16_batch_limit(H, W)))
 
 
-class _SyncGraphB:
-    """The bf16-STORAGE inference plan of both encoders for one (batch, height, width, device): bf16 NHWC inputs (15 + 1 and 1 + 7
-    channels), every layer a bf16.ConvB launch with its eval-mode BatchNorm folded into the fp32 epilogue (_run_chain_b), the two
-    512-channel outputs stored in bf16 like every other layer.  w2l_sync_embeddings_bf16 normalises them into fp32."""
+class _SyncGraph:
+    """The inference plan of both encoders for one (batch, height, width, device) in one storage (engine.storage): "f32", or "bf16",
+    the opt-in bf16-STORAGE plan - bf16 NHWC inputs (15 + 1 and 1 + 7 channels), every layer a bf16.ConvB launch with its eval-mode
+    BatchNorm folded into the fp32 epilogue, the two 512-channel outputs stored in bf16 like every other layer.  `embeddings`
+    normalises the two outputs into fp32."""
 
-    def __init__(self, model, N, H, W, device):
-        check_bf16_buffers(N, H, W)        # before anything is allocated
-        self.lib = load()
+    def __init__(self, model, N, H, W, device, precision="f32"):
+        st = self.st = engine.storage(precision)
+        self.precision = st.name
+        if st is engine.BF16:
+            check_bf16_buffers(N, H, W)        # before anything is allocated
+        self.lib = lib = load()
         self.N, self.H, self.W = N, H, W
-        pool = _BufPoolB(device)
+        pool = engine.BufPool(device, st)
         plan = engine.Plan()
-        self.face_in = bf16.new_buf(N, H, W, 16, device)       # 15 channels + 1 zero pad
-        self.mel_in = bf16.new_buf(N, 80, 16, 8, device)       # 1 mel channel + 7 zero pad
-        self.face_out, _ = _run_chain_b(plan, pool, "face_encoder", list(model.face_encoder), bf16.ActB(self.face_in, 0, 15), device)
-        self.audio_out, _ = _run_chain_b(plan, pool, "audio_encoder", list(model.audio_encoder), bf16.ActB(self.mel_in, 0, 1), device)
+        self.face_in = st.new_buf(N, H, W, 16, device, zero=True)      # 15 channels + 1 zero pad
+        self.mel_in = st.new_buf(N, 80, 16, 4, device, zero=True)      # 1 mel channel + zero pad: 4 channels in fp32, 8 in bf16
+        self.face_cs, self.mel_cs = self.face_in.shape[3], self.mel_in.shape[3]
+        self.face_out, _ = engine.run_chain(plan, pool, "face_encoder", list(model.face_encoder), st.act(self.face_in, 0, 15))
+        self.audio_out, _ = engine.run_chain(plan, pool, "audio_encoder", list(model.audio_encoder), st.act(self.mel_in, 0, 1))
         for o in (self.face_out, self.audio_out):
             if (o.H, o.W) != (1, 1):
                 raise RuntimeError("SyncNet encoders must end at 1x1, got %dx%d" % (o.H, o.W))
-        plan.tuned = True          # launch configurations come from the shapes: nothing to autotune
+        plan.tuned = st.shape_tuned
         self.plan = plan
         self.scratch_bytes = pool.total_bytes
+        self._to_nhwc, self._window_rows = st.bind(lib, "nchw_to_nhwc"), st.bind(lib, "sync_window_rows")
 
     def dispatch(self, N=None):
-        """[(record name, family, tile, ksplit)] of every launch of the plan (bf16.plan_dispatch): the kernel each one runs, or
-        would run at batch N"""
+        """[(record name, family, tile, ksplit)] of every bf16-storage launch of the plan (bf16.plan_dispatch): the kernel each one
+        runs, or would run at batch N"""
         return bf16.plan_dispatch(self.plan, N)
 
+    def load_nchw(self, audio, face):
+        """contiguous fp32 [N,1,80,16] and [N,C,H,W] device tensors -> the plan's two inputs"""
+        s, fc, mc = current_stream(), self.face_cs, self.mel_cs
+        self._to_nhwc(s, self.N, face.shape[1], self.H, self.W, ptr(face), ptr(self.face_in), fc, fc)
+        self._to_nhwc(s, self.N, 1, 80, 16, ptr(audio), ptr(self.mel_in), mc, mc)
+
+    def load_rows(self, rows, B):
+        """the plan's two inputs from B w2l_sync_row entries (96x96 face crops)"""
+        self._window_rows(current_stream(), B, ptr(rows), 96, ptr(self.face_in), self.face_cs, ptr(self.mel_in), self.mel_cs)
+
     def embeddings(self, B, audio_ptr, face_ptr):
-        """the plan's two outputs, L2-normalised, into fp32 [B, 512] rows at the two addresses (one launch)"""
-        check(self.lib.w2l_sync_embeddings_bf16(current_stream(), B, 512, self.audio_out.ptr, self.audio_out.cs, self.face_out.ptr,
-                                                self.face_out.cs, audio_ptr, face_ptr), "sync_embeddings_bf16")
+        """the plan's two outputs, L2-normalised, into fp32 [B, 512] rows at the two addresses: two w2l_l2norm_rows launches in
+        fp32, one w2l_sync_embeddings_bf16 launch in bf16"""
+        s, a, v = current_stream(), self.audio_out, self.face_out
+        if self.st is engine.BF16:
+            check(self.lib.w2l_sync_embeddings_bf16(s, B, 512, a.ptr, a.cs, v.ptr, v.cs, audio_ptr, face_ptr), "sync_embeddings_bf16")
+        else:
+            check(self.lib.w2l_l2norm_rows(s, B, 512, a.ptr, a.cs, audio_ptr), "l2norm_rows")
+            check(self.lib.w2l_l2norm_rows(s, B, 512, v.ptr, v.cs, face_ptr), "l2norm_rows")
 
 
 class SyncNet_color(nn.Module):
@@ -103,7 +103,7 @@ class SyncNet_color(nn.Module):
         object.__setattr__(self, "_train_graphs", autograd.GraphCache(autograd.build_syncnet))
 
     def forward(self, audio_sequences, face_sequences, precision="f32"):
-        """`precision` "bf16" (inference only): the opt-in bf16-storage plan, _SyncGraphB; the embeddings stay fp32"""
+        """`precision` "bf16" (inference only): the opt-in bf16-storage plan; the embeddings stay fp32"""
         check_precision(precision)
         engine.require_cuda(face_sequences, "face_sequences")
         with engine.on_device_of(face_sequences, self):      # launches go to the current stream of the INPUT's device; refuses a device mismatch
@@ -125,22 +125,11 @@ class SyncNet_color(nn.Module):
                                       (audio, face))
             return autograd.L2NormRows.apply(a.reshape(N, -1)), autograd.L2NormRows.apply(v.reshape(N, -1))
         g = self._eval_graph(N, H, W, face.device, precision)
-        s = current_stream()
-        if precision == "bf16":
-            check(g.lib.w2l_nchw_to_nhwc_bf16(s, N, C_, H, W, ptr(face), ptr(g.face_in), 16, 16), "nchw_to_nhwc_bf16")
-            check(g.lib.w2l_nchw_to_nhwc_bf16(s, N, 1, 80, 16, ptr(audio), ptr(g.mel_in), 8, 8), "nchw_to_nhwc_bf16")
-            g.plan.run()
-            a = torch.empty((N, 512), device=face.device, dtype=torch.float32)
-            v = torch.empty((N, 512), device=face.device, dtype=torch.float32)
-            g.embeddings(N, ptr(a), ptr(v))
-            return a, v
-        check(g.lib.w2l_nchw_to_nhwc(s, N, C_, H, W, ptr(face), ptr(g.face_in), 16, 16), "nchw_to_nhwc")
-        check(g.lib.w2l_nchw_to_nhwc(s, N, 1, 80, 16, ptr(audio), ptr(g.mel_in), 4, 4), "nchw_to_nhwc")
+        g.load_nchw(audio, face)
         g.plan.run()
         a = torch.empty((N, 512), device=face.device, dtype=torch.float32)
         v = torch.empty((N, 512), device=face.device, dtype=torch.float32)
-        check(g.lib.w2l_l2norm_rows(s, N, 512, g.audio_out.ptr, g.audio_out.cs, ptr(a)), "l2norm_rows")
-        check(g.lib.w2l_l2norm_rows(s, N, 512, g.face_out.ptr, g.face_out.cs, ptr(v)), "l2norm_rows")
+        g.embeddings(N, ptr(a), ptr(v))
         return a, v
 
     def _eval_graph(self, N, H, W, device, precision="f32"):
@@ -150,7 +139,7 @@ class SyncNet_color(nn.Module):
         g = self._graphs.get(key)
         if g is None or g[0] != ver:
             self._graphs.clear()
-            g = (ver, (_SyncGraphB if precision == "bf16" else _SyncGraph)(self, N, H, W, device))
+            g = (ver, _SyncGraph(self, N, H, W, device, precision))
             self._graphs[key] = g
         return g[1]
 
@@ -173,14 +162,6 @@ class SyncNet_color(nn.Module):
             raise ValueError("rows must be a contiguous uint8 device tensor holding B >= 1 w2l_sync_row entries")
         with engine.on_device_of(face_out, self):
             g = self._eval_graph(B, 48, 96, face_out.device, precision)
-            s = current_stream()
-            if precision == "bf16":
-                check(g.lib.w2l_sync_window_rows_bf16(s, B, ptr(rows), 96, ptr(g.face_in), 16, ptr(g.mel_in), 8), "sync_window_rows_bf16")
-                g.plan.run()
-                g.embeddings(B, audio_out.data_ptr() + 2048 * offset, face_out.data_ptr() + 2048 * offset)
-                return
-            check(g.lib.w2l_sync_window_rows(s, B, ptr(rows), 96, ptr(g.face_in), 16, ptr(g.mel_in), 4), "sync_window_rows")
+            g.load_rows(rows, B)
             g.plan.run()
-            check(g.lib.w2l_l2norm_rows(s, B, 512, g.audio_out.ptr, g.audio_out.cs, audio_out.data_ptr() + 2048 * offset),
-                  "l2norm_rows")
-            check(g.lib.w2l_l2norm_rows(s, B, 512, g.face_out.ptr, g.face_out.cs, face_out.data_ptr() + 2048 * offset), "l2norm_rows")
+            g.embeddings(B, audio_out.data_ptr() + 2048 * offset, face_out.data_ptr() + 2048 * offset)

@@ -9,7 +9,8 @@ import torch
 from torch import nn
 
 from .. import autograd, bf16, engine
-from .._lib import ACT_NONE, ACT_SIGMOID, ConvGeom, check, current_stream, load, ptr
+from .._lib import ACT_NONE, ACT_SIGMOID, check, current_stream, load, ptr
+from ..engine import PRECISIONS, check_precision  # noqa: F401  (the names the runners and the tests import from here)
 from .conv import Conv2d, Conv2dTranspose, HeadFusedBlock, PlainConv, nonorm_Conv2d
 
 
@@ -89,40 +90,45 @@ def fold_time(audio_sequences, face_sequences):
 
 
 class _GeneratorGraph:
-    """Buffers + launch plan of the generator for one (batch, height, width, device)."""
+    """Buffers + launch plan of the generator for one (batch, height, width, device) in one storage (engine.storage): "f32", NHWC
+    fp32 buffers and FusedConv launches (the parity path), or "bf16", the opt-in bf16-STORAGE plan - bf16 NHWC buffers (8-channel
+    granules) and bf16.ConvB launches (w2l_plan_add_convb) over the same concat-buffer layout, face / audio two-stream split,
+    optional HIP-graph replay and three sub-plans.  Either output block runs with its 1x1 head fused and leaves the fp32 prediction
+    in `out`; the bf16 one (w2l_plan_add_convb_head, fp32 epilogue) also writes the uint8 frames, into `frames`."""
 
-    def __init__(self, model, N, H, W, device):
-        self.lib = load()
+    def __init__(self, model, N, H, W, device, precision="f32"):
+        st = self.st = engine.storage(precision)
+        self.precision = st.name
+        self.lib = lib = load()
         self.N, self.H, self.W = N, H, W
-        pool = engine.BufPool(device)
-        pool_audio = engine.BufPool(device)     # the audio branch runs on its own stream: no scratch shared with the face branch
+        pool = engine.BufPool(device, st)
+        pool_audio = engine.BufPool(device, st)     # the audio branch runs on its own stream: no scratch shared with the face branch
         plan = engine.Plan()
         enc = model.face_encoder_blocks
         dec = model.face_decoder_blocks
-        self.x_in = engine.new_buf(N, H, W, 8, device, zero=True)         # 6 image channels + 2 zero pad
-        self.mel_in = engine.new_buf(N, 80, 16, 4, device, zero=True)     # 1 mel channel + 3 zero pad
+        self.x_in = st.new_buf(N, H, W, 8, device, zero=True)         # 6 image channels + 2 zero pad
+        self.mel_in = st.new_buf(N, 80, 16, 4, device, zero=True)     # 1 mel channel + zero pad: 4 channels in fp32, 8 in bf16
+        self.x_cs, self.mel_cs = self.x_in.shape[3], self.mel_in.shape[3]
         # shapes of the encoder pyramid / decoder outputs -> one concat buffer per decoder stage
         enc_hw, h, w = [], H, W
         for blk in enc:
             for b in blk:
-                h, w = b.fused().out_hw(h, w)
-            enc_hw.append((h, w, blk[-1].fused().cout))
+                h, w = autograd.out_hw(autograd.block_geom(b), h, w)
+            enc_hw.append((h, w, blk[-1].conv_block[0].out_channels))
         nb = len(dec)
         cats = []
         for i, blk in enumerate(dec):
             eh, ew, ec = enc_hw[nb - 1 - i]
-            dc = blk[-1].fused().cout
-            cats.append((engine.new_buf(N, eh, ew, dc + ec, device), dc, ec))
+            dc = blk[-1].conv_block[0].out_channels
+            cats.append((st.new_buf(N, eh, ew, dc + ec, device), dc, ec))
         # face encoder: last layer of block i writes the skip slice of concat buffer nb-1-i
-        x = engine.Act(self.x_in, 0, 8)
+        x = st.act(self.x_in, 0, 6)
         for i, blk in enumerate(enc):
             buf, dc, ec = cats[nb - 1 - i]
-            x, _ = engine.run_chain(plan, pool, "face_encoder_blocks.%d" % i, list(blk), x,
-                                    engine.Act(buf, dc, ec))
+            x, _ = engine.run_chain(plan, pool, "face_encoder_blocks.%d" % i, list(blk), x, st.act(buf, dc, ec))
         self.n_face = len(plan.records)
         # audio encoder
-        a, a_buf = engine.run_chain(plan, pool_audio, "audio_encoder", list(model.audio_encoder),
-                                    engine.Act(self.mel_in, 0, 4))
+        a, _ = engine.run_chain(plan, pool_audio, "audio_encoder", list(model.audio_encoder), st.act(self.mel_in, 0, 1))
         self.n_audio = len(plan.records) - self.n_face
         if (a.H, a.W) != (1, 1):
             raise RuntimeError("audio encoder must reduce the mel window to 1x1, got %dx%d" % (a.H, a.W))
@@ -130,16 +136,26 @@ class _GeneratorGraph:
         x = a
         for i, blk in enumerate(dec):
             buf, dc, ec = cats[i]
-            x, _ = engine.run_chain(plan, pool, "face_decoder_blocks.%d" % i, list(blk), x,
-                                    engine.Act(buf, 0, dc))
-            x = engine.Act(buf, 0, dc + ec)
-        # output block: conv 80->32 + BN + ReLU with the 1x1 32->3 + sigmoid head fused into its epilogue (one launch)
-        self.out = engine.Act(engine.new_buf(N, H, W, 4, device, zero=True), 0, 3)
-        engine.run_chain(plan, pool, "output_block", [model._head], x, self.out)
+            x, _ = engine.run_chain(plan, pool, "face_decoder_blocks.%d" % i, list(blk), x, st.act(buf, 0, dc))
+            x = st.act(buf, 0, dc + ec)
         if (x.H, x.W) != (H, W):
             raise RuntimeError("generator output is %dx%d for a %dx%d input" % (x.H, x.W, H, W))
+        # output block: conv 80->32 + BN + ReLU with the 1x1 32->3 + sigmoid head fused into its epilogue (one launch)
+        self.out = engine.Act(engine.new_buf(N, H, W, 4, device, zero=True), 0, 3)
+        self.frames = None
+        if st is engine.F32:
+            engine.run_chain(plan, pool, "output_block", [model._head], x, self.out)
+        else:
+            head = st.layer_of(model.output_block[0], None)
+            head.layer.attach_head(head.weight, model.output_block[1], ACT_SIGMOID)
+            self.frames = torch.empty((N, H, W, 3), dtype=torch.uint8, device=device)
+            plan.add_convb_head("output_block.0", head.layer, x, self.frames, self.out, head.scale, head.shift)
+            plan.keep.append(head)
+        plan.tuned = st.shape_tuned
         self.plan = plan
         self.scratch_bytes = pool.total_bytes + pool_audio.total_bytes
+        self._to_nhwc, self._pack = st.bind(lib, "nchw_to_nhwc"), st.bind(lib, "datagen_pack")
+        self._mel_gather, self._mel_gather_rows = st.bind(lib, "mel_gather"), st.bind(lib, "mel_gather_rows")
         # execution: the face and audio encoders are independent until the decoder's first concat and neither fills the chip
         # in its deep layers, so they run concurrently on two streams; `plan` (all launches in one sequence) stays the
         # object that is autotuned, profiled and counted
@@ -147,11 +163,39 @@ class _GeneratorGraph:
         self.hip_graph = None
         self.side = torch.cuda.Stream(device=device) if device.type == "cuda" and engine.TWO_STREAM_ENCODERS else None
 
+    def dispatch(self, N=None):
+        """[(record name, family, tile, ksplit)] of every bf16-storage launch of the plan (bf16.plan_dispatch): the kernel each one
+        runs, or would run at batch N"""
+        return bf16.plan_dispatch(self.plan, N)
+
     def load_nchw(self, audio, face):
-        s = current_stream()
-        N = self.N
-        check(self.lib.w2l_nchw_to_nhwc(s, N, 6, self.H, self.W, ptr(face), ptr(self.x_in), 8, 8), "nchw_to_nhwc")
-        check(self.lib.w2l_nchw_to_nhwc(s, N, 1, 80, 16, ptr(audio), ptr(self.mel_in), 4, 4), "nchw_to_nhwc")
+        self._to_nhwc(current_stream(), self.N, 6, self.H, self.W, ptr(face), ptr(self.x_in), self.x_cs, self.x_cs)
+        self.load_mel(windows=audio)
+
+    def pack_faces(self, faces_u8):
+        """uint8 BGR crops [N,H,H,3] (contiguous, on the device) -> `x_in`, the masked + reference 6-channel input (w2l_datagen_pack)"""
+        self._pack(current_stream(), self.N, self.H, ptr(faces_u8), ptr(self.x_in), self.x_cs, self.x_cs)
+
+    def load_mel(self, mel=None, starts=None, windows=None, rows=None):
+        """`mel_in` from one of: `rows`, N w2l_mel_row entries; `windows`, float [N,80,16] (or [N,1,80,16]); the spectrogram
+        `mel` [80,T] plus int32 `starts` [N] - all device tensors"""
+        s, n, mc = current_stream(), self.N, self.mel_cs
+        if rows is not None:
+            self._mel_gather_rows(s, ptr(rows), n, ptr(self.mel_in), mc, mc)
+        elif windows is not None:
+            mw = windows.contiguous().float().view(n, 1, 80, 16)
+            self._to_nhwc(s, n, 1, 80, 16, ptr(mw), ptr(self.mel_in), mc, mc)
+        else:
+            self._mel_gather(s, ptr(mel), mel.shape[1], ptr(starts), n, ptr(self.mel_in), mc, mc)
+
+    def frames_into(self, out_u8):
+        """the uint8 frames of the last run into `out_u8` [N,H,W,3]: the plan's last launch wrote them (bf16), or w2l_frames_to_u8
+        makes them from `out` (fp32)"""
+        if self.frames is not None:
+            out_u8.copy_(self.frames)
+        else:
+            check(self.lib.w2l_frames_to_u8(current_stream(), self.N, self.H, self.W, self.out.ptr, self.out.cs, ptr(out_u8)),
+                  "frames_to_u8")
 
     def _split(self):
         """three sub-plans over the same launches (face encoder | audio encoder | decoder + output) carrying the tuned configs"""
@@ -209,160 +253,6 @@ class _GeneratorGraph:
         return y
 
 
-PRECISIONS = ("f32", "bf16")
-
-
-def check_precision(precision):
-    if precision not in PRECISIONS:
-        raise ValueError("precision must be 'f32' or 'bf16', got %r" % (precision,))
-    return precision
-
-
-class _FoldedConvB:
-    """one block as a bf16-storage layer for inference: the bf16.ConvB handle (unscaled bf16 weights) and the block's eval-mode
-    BatchNorm (+ conv bias) folded into fp32 scale / shift vectors that the launch applies to its fp32 accumulators - the fold of
-    NodeB's "bn_eval" kind.  The scale is NOT folded into the bf16 weights: that would round them a second time."""
-
-    def __init__(self, blk, device):
-        conv = blk.conv_block[0]
-        bn = blk.conv_block[1] if blk._norm else None
-        if bn is not None and bn.training:
-            blk.fused()          # raises: a train-mode BatchNorm block has no folded form
-        kh, kw = engine._pair(conv.kernel_size)
-        sh, sw = engine._pair(conv.stride)
-        ph, pw = engine._pair(conv.padding)
-        oph, opw = engine._pair(conv.output_padding) if blk._transposed else (0, 0)
-        self.geom = ConvGeom(int(blk._transposed), conv.in_channels, conv.out_channels, kh, kw, sh, sw, ph, pw, oph, opw, blk._act)
-        self.layer = bf16.ConvB(self.geom, conv.weight)
-        self.weight = conv.weight
-        self.residual = blk.residual
-        cout = conv.out_channels
-        cp = (cout + 31) // 32 * 32
-        self.scale = torch.zeros(cp, device=device)
-        self.shift = torch.zeros(cp, device=device)
-        bias = conv.bias.detach().float().contiguous() if conv.bias is not None else None
-        if bn is not None:
-            check(load().w2l_bn_fold(current_stream(), cout, ptr(bias), ptr(bn.weight.detach().float().contiguous()),
-                                     ptr(bn.bias.detach().float().contiguous()), ptr(bn.running_mean.detach().float().contiguous()),
-                                     ptr(bn.running_var.detach().float().contiguous()), float(bn.eps), ptr(self.scale),
-                                     ptr(self.shift)), "bn_fold")
-        else:
-            check(load().w2l_bn_fold(current_stream(), cout, ptr(bias), None, None, None, None, 0.0, ptr(self.scale), ptr(self.shift)),
-                  "bn_fold")
-        self._keep = bias
-
-
-class _BufPoolB(engine.BufPool):
-    """BufPool of NHWC bf16 scratch buffers"""
-
-    def get(self, N, H, W, Ctot):
-        key = (N, H, W, bf16.round8(Ctot))
-        lst = self.free.get(key)
-        if lst:
-            return lst.pop()
-        self.total_bytes += 2 * N * H * W * key[3]
-        return bf16.new_buf(N, H, W, Ctot, self.device)
-
-
-def _run_chain_b(plan, pool, name, blocks, src, device, final_dst=None):
-    """engine.run_chain on the bf16-storage path: src / final_dst are bf16.ActB slices"""
-    x, owned = src, None
-    for j, blk in enumerate(blocks):
-        f = _FoldedConvB(blk, device)
-        ho, wo = f.layer.out_hw(x.H, x.W)
-        if j == len(blocks) - 1 and final_dst is not None:
-            dst, new_owned = final_dst, None
-        else:
-            buf = pool.get(x.N, ho, wo, f.layer.cout)
-            dst, new_owned = bf16.ActB(buf, 0, f.layer.cout), buf
-        plan.add_convb("%s.%d" % (name, j), f.layer, x, dst, x if f.residual else None, f.scale, f.shift)
-        plan.keep.append(f)
-        if owned is not None:
-            pool.put(owned)
-        owned, x = new_owned, dst
-    return x, owned
-
-
-class _GeneratorGraphB(_GeneratorGraph):
-    """The generator's bf16-STORAGE inference plan for one (batch, height, width, device): the same concat-buffer layout (8-channel
-    granules), face / audio two-stream split, optional HIP-graph replay and three sub-plans as _GeneratorGraph, over bf16 NHWC
-    buffers and bf16.ConvB launches (w2l_plan_add_convb).  The output block runs with its 1x1 head fused
-    (w2l_plan_add_convb_head): fp32 epilogue, uint8 frames in `frames`, the fp32 prediction in `out`."""
-
-    def __init__(self, model, N, H, W, device):
-        self.lib = load()
-        self.N, self.H, self.W = N, H, W
-        pool = _BufPoolB(device)
-        pool_audio = _BufPoolB(device)
-        plan = engine.Plan()
-        enc = model.face_encoder_blocks
-        dec = model.face_decoder_blocks
-        self.x_in = bf16.new_buf(N, H, W, 8, device)          # 6 image channels + 2 zero pad
-        self.mel_in = bf16.new_buf(N, 80, 16, 8, device)      # 1 mel channel + 7 zero pad
-        enc_hw, h, w = [], H, W
-        for blk in enc:
-            for b in blk:
-                h, w = _out_hw(b, h, w)
-            enc_hw.append((h, w, blk[-1].conv_block[0].out_channels))
-        nb = len(dec)
-        cats = []
-        for i, blk in enumerate(dec):
-            eh, ew, ec = enc_hw[nb - 1 - i]
-            dc = blk[-1].conv_block[0].out_channels
-            cats.append((bf16.new_buf(N, eh, ew, dc + ec, device), dc, ec))
-        x = bf16.ActB(self.x_in, 0, 6)
-        for i, blk in enumerate(enc):
-            buf, dc, ec = cats[nb - 1 - i]
-            x, _ = _run_chain_b(plan, pool, "face_encoder_blocks.%d" % i, list(blk), x, device, bf16.ActB(buf, dc, ec))
-        self.n_face = len(plan.records)
-        a, _ = _run_chain_b(plan, pool_audio, "audio_encoder", list(model.audio_encoder), bf16.ActB(self.mel_in, 0, 1), device)
-        self.n_audio = len(plan.records) - self.n_face
-        if (a.H, a.W) != (1, 1):
-            raise RuntimeError("audio encoder must reduce the mel window to 1x1, got %dx%d" % (a.H, a.W))
-        x = a
-        for i, blk in enumerate(dec):
-            buf, dc, ec = cats[i]
-            x, _ = _run_chain_b(plan, pool, "face_decoder_blocks.%d" % i, list(blk), x, device, bf16.ActB(buf, 0, dc))
-            x = bf16.ActB(buf, 0, dc + ec)
-        if (x.H, x.W) != (H, W):
-            raise RuntimeError("generator output is %dx%d for a %dx%d input" % (x.H, x.W, H, W))
-        head = _FoldedConvB(model.output_block[0], device)
-        head.layer.attach_head(head.weight, model.output_block[1], ACT_SIGMOID)
-        self.frames = torch.empty((N, H, W, 3), dtype=torch.uint8, device=device)
-        self.out = engine.Act(engine.new_buf(N, H, W, 4, device, zero=True), 0, 3)
-        plan.add_convb_head("output_block.0", head.layer, x, self.frames, self.out, head.scale, head.shift)
-        plan.keep.append(head)
-        plan.tuned = True          # launch configurations come from the shapes: nothing to autotune
-        self.plan = plan
-        self.scratch_bytes = pool.total_bytes + pool_audio.total_bytes
-        self.parts = None
-        self.hip_graph = None
-        self.side = torch.cuda.Stream(device=device) if device.type == "cuda" and engine.TWO_STREAM_ENCODERS else None
-
-    def dispatch(self, N=None):
-        """[(record name, family, tile, ksplit)] of every launch of the plan (bf16.plan_dispatch): the kernel each one runs, or
-        would run at batch N"""
-        return bf16.plan_dispatch(self.plan, N)
-
-    def load_nchw(self, audio, face):
-        s = current_stream()
-        check(self.lib.w2l_nchw_to_nhwc_bf16(s, self.N, 6, self.H, self.W, ptr(face), ptr(self.x_in), 8, 8), "nchw_to_nhwc_bf16")
-        check(self.lib.w2l_nchw_to_nhwc_bf16(s, self.N, 1, 80, 16, ptr(audio), ptr(self.mel_in), 8, 8), "nchw_to_nhwc_bf16")
-
-
-def _out_hw(blk, H, W):
-    """output size of a block's conv (the library's rule, w2l_conv_out_hw)"""
-    import ctypes as C
-    conv = blk.conv_block[0]
-    kh, kw = engine._pair(conv.kernel_size)
-    sh, sw = engine._pair(conv.stride)
-    ph, pw = engine._pair(conv.padding)
-    oph, opw = engine._pair(conv.output_padding) if blk._transposed else (0, 0)
-    g = ConvGeom(int(blk._transposed), conv.in_channels, conv.out_channels, kh, kw, sh, sw, ph, pw, oph, opw, blk._act)
-    ho, wo = C.c_int(), C.c_int()
-    check(load().w2l_conv_out_hw(C.byref(g), H, W, C.byref(ho), C.byref(wo)), "conv_out_hw")
-    return ho.value, wo.value
-
 
 class Wav2Lip(nn.Module):
     MAX_PLAN_BATCH = 512      # frames per static plan: larger inference batches are chunked (see forward)
@@ -382,7 +272,7 @@ class Wav2Lip(nn.Module):
     def graph(self, N, H=96, W=96, device=None, lane=0, precision="f32"):
         """the static launch plan for batch N (built on first use, rebuilt if the weights changed); `lane` selects one of
         several independent buffer sets for batches in flight on different streams (inference.PipelinedRunner); `precision`
-        "f32" (default, the parity path) or "bf16" (the opt-in bf16-storage plan, _GeneratorGraphB)"""
+        "f32" (default, the parity path) or "bf16" (the opt-in bf16-storage plan)"""
         check_precision(precision)
         device = device or next(self.parameters()).device
         ver = engine.param_version(self)
@@ -391,18 +281,16 @@ class Wav2Lip(nn.Module):
         if g is None or g[0] != ver:
             if any(v[0] != ver for v in self._graphs.values()):
                 self._graphs.clear()
-            if precision == "bf16":
-                g = (ver, _GeneratorGraphB(self, N, H, W, torch.device(device)))
-                self._graphs[key] = g
-                return g[1]
-            g = (ver, _GeneratorGraph(self, N, H, W, torch.device(device)))
-            if (H, W) == (96, 96):    # batch sizes the launch table does not hold: committed per-plan configurations (engine.py)
-                engine.apply_plan_configs(g[1].plan, "generator_96", N)
-            twin = next((v[1] for k, v in self._graphs.items() if k[:4] == key[:4] and k[5] == precision and v[1].plan.tuned), None)
-            if twin is not None:      # another lane of the same geometry is already tuned: same launches, same configurations
+            g = (ver, _GeneratorGraph(self, N, H, W, torch.device(device), precision))
+            plan = g[1].plan
+            if not plan.tuned and (H, W) == (96, 96):    # fp32 batch sizes the launch table does not hold: committed per-plan configurations (engine.py)
+                engine.apply_plan_configs(plan, "generator_96", N)
+            twin = None if plan.tuned else next((v[1] for k, v in self._graphs.items()
+                                                 if k[:4] == key[:4] and k[5] == precision and v[1].plan.tuned), None)
+            if twin is not None:      # another fp32 lane of the same geometry is already tuned: same launches, same configurations
                 for i, (_, t_, k_) in enumerate(twin.plan.configs()):
-                    g[1].plan.set_config(i, t_, k_)
-                g[1].plan.tuned = True
+                    plan.set_config(i, t_, k_)
+                plan.tuned = True
             self._graphs[key] = g
         return g[1]
 
