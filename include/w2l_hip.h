@@ -44,6 +44,7 @@
  *   w2l_melspectrogram    audio.py:45-51 (preemphasis, STFT, mel basis, dB, normalise)
  *   w2l_mel_gather        inference.py:231-240 (16-frame mel windows at host-computed starts)
  *   w2l_resample_sinc     audio.py:9-10 (librosa.core.load's sample-rate conversion: resampy 'kaiser_best' sinc interpolation)
+ *   w2l_resample_stream   the same conversion for live streams: the final output samples of many streams per launch
  *   w2l_l2norm_rows       models/syncnet.py:62-63 (F.normalize(p=2, dim=1))
  *   w2l_cosine_bce        wav2lip_train.py:179-184 (cosine_similarity + BCELoss)
  *   w2l_plan_*            the per-batch forward loop inference.py:262-263 -> models/wav2lip.py:87-125
@@ -632,6 +633,68 @@ int w2l_mel_gather_rows_bf16(void* stream, const w2l_mel_row* rows, int B, void*
  * resampy's resample_f. */
 int w2l_resample_sinc(void* stream, const float* x, int n_in, const double* tr, int n_out, double sample_ratio,
                       const double* win, const double* delta, int nwin, int num_table, float* y);
+
+/* The same conversion, incrementally and for MANY streams in one launch (wav2lip_amd/streaming.py): the streams may have
+ * different source rates, each with its own filter tables.  With K = nwin / index_step an output sample t whose time register
+ * has the integer part n reads the source samples n - K + 1 .. n + K, so on an open stream (src_total = -1) that holds m samples
+ * it is FINAL - bit-equal to output t of the whole signal - once n + K <= m - 1; on a closed stream (src_total = its length N,
+ * n_res = int(N * ratio)) the wings are cut by the end as w2l_resample_sinc cuts them, and the outputs t >= n_res are written as
+ * 0 (librosa's fix_length pads at most one).  One workgroup per block entry, one thread per output: thread j starts from the
+ * block's time register tr0 (the host's, by repeated float64 addition) and adds `inc` j times, the reference loop's additions in
+ * its order.  A block with copy != 0 copies its outputs from the stream's `carry` buffer (the tail of its previous destination)
+ * instead of computing them.  The caller lists final outputs only and checks that [src_first, src_first + src_held) covers what
+ * they read; the kernel clamps nothing: an output whose reads leave the held samples, whose stream index is out of range or
+ * whose place is outside the destination is skipped, so a wrong table writes nothing, never a fault.  Tables live in device
+ * memory, 16-byte aligned; `streams_host` is the host's copy of the stream table (the staging buffer), which the entry point
+ * checks before it launches.
+ *
+ * w2l_resample_stream_entry, 128 bytes, alignment 16:
+ *   at   0  uint64  src         device address of the held source samples, fp32 [src_held]
+ *   at   8  int64   src_first   absolute index (in the stream's source signal) of src[0]
+ *   at  16  int64   src_total   the source signal's length once the stream is closed, -1 while it is open
+ *   at  24  int64   n_res       int(src_total * ratio) once the stream is closed, -1 while it is open
+ *   at  32  uint64  dst16       device address of the destination, fp32 [dst_cap]
+ *   at  40  int64   dst_first   absolute index (in the resampled signal) of dst16[0]
+ *   at  48  uint64  win         device address of the half window, f64 [nwin] (scaled by the ratio when it is < 1)
+ *   at  56  uint64  delta       device address of its first differences, f64 [nwin], last entry 0
+ *   at  64  uint64  carry       device address of the previous destination's samples, fp32 [carry_held], or 0
+ *   at  72  int64   carry_first absolute index of carry[0]
+ *   at  80  float64 scale       min(1, ratio)
+ *   at  88  float64 inc         1 / ratio, the time register's increment
+ *   at  96  int32   src_held    source samples held
+ *   at 100  int32   dst_cap     samples of the destination
+ *   at 104  int32   index_step  int(scale * num_table), >= 1
+ *   at 108  int32   nwin        entries of win and delta
+ *   at 112  int32   carry_held  samples behind `carry`
+ *   at 116  int32   unused      [3]
+ * w2l_resample_block, 32 bytes, alignment 16:
+ *   at   0  int32   stream      row of the stream table
+ *   at   4  int32   count       outputs of this block, 1 .. 128
+ *   at   8  int64   t0          absolute index of its first output; output t0 + j goes to dst16[t0 + j - dst_first]
+ *   at  16  float64 tr0         time register of output t0
+ *   at  24  int32   copy        non-zero: copy the outputs from `carry` instead of computing them
+ *   at  28  int32   unused */
+typedef struct {
+    uint64_t src;
+    int64_t src_first, src_total, n_res;
+    uint64_t dst16;
+    int64_t dst_first;
+    uint64_t win, delta, carry;
+    int64_t carry_first;
+    double scale, inc;
+    int32_t src_held, dst_cap, index_step, nwin, carry_held, unused[3];
+} w2l_resample_stream_entry;
+typedef struct {
+    int32_t stream, count;
+    int64_t t0;
+    double tr0;
+    int32_t copy, unused;
+} w2l_resample_block;
+/* 1 <= nstreams <= 65535, 1 <= nblocks <= 1048576, num_table >= 1; every stream with non-NULL src, dst16, win and delta,
+ * index_step >= 1, nwin >= 2 and counts >= 1; non-zero with w2l_last_error() set otherwise, or for a NULL / misaligned table, and
+ * then nothing is launched */
+int w2l_resample_stream(void* stream, const w2l_resample_stream_entry* streams_host, const w2l_resample_stream_entry* streams,
+                        int nstreams, const w2l_resample_block* blocks, int nblocks, int num_table);
 
 /* ---------------------------------------------------------------- SyncNet tail / losses */
 

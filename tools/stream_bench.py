@@ -30,7 +30,13 @@ compares, on S copies of a seeded 160x160 video whose faces the seeded S3FD find
 
 frames/s over the whole pass (detection included on both sides), and per row the number of ticks between the tick whose audio
 completed it and the tick in which its frame was delivered: the lag live detection adds is T - 1 frames plus one tick by
-construction, and this is what is measured of it."""
+construction, and this is what is measured of it.
+
+    python tools/stream_bench.py --sample_rate 48000 [--streams 64] [--ticks 80] [--alternations 5]
+
+compares S streams opened at that rate and fed 40 ms of it per tick (converted to 16 kHz on the device as they stream, one
+w2l_resample_stream launch per tick) with the same streams fed the same audio converted beforehand, outside the timed loop:
+frames/s, and the wall time per tick over the whole pass."""
 import argparse
 import json
 import os
@@ -233,6 +239,59 @@ def bench_live(S, ticks, a, dev):
     return out
 
 
+def run_rate(G, wavs, frames, ticks, batch, rate):
+    """S streams opened at `rate`, each fed a 40 ms slice per tick (the rest with the last), one `step(flush=True)` per tick"""
+    n, tick = [0], int(rate * 0.040)
+    ls = streaming.LipsyncStreams(G, batch_size=batch, sink=lambda key, frame: n.__setitem__(0, n[0] + (frame is not None)))
+    for k in range(len(wavs)):
+        ls.open(k, frames, [BOX] * len(frames), sample_rate=rate)
+    per_tick = []
+    t_start = time.perf_counter()
+    for t in range(ticks):
+        t0 = time.perf_counter()
+        for k, w in enumerate(wavs):
+            ls.feed(k, w[t * tick:] if t == ticks - 1 else w[t * tick:(t + 1) * tick])
+            if t == ticks - 1:
+                ls.close(k)
+        ls.step(flush=True)
+        per_tick.append(time.perf_counter() - t0)
+    ls.drain()
+    torch.cuda.synchronize()
+    return n[0], time.perf_counter() - t_start, per_tick, ls.resample_launches
+
+
+def bench_rate(S, ticks, a, dev):
+    """streams fed at --sample_rate (converted on the device as they stream) against the same streams fed the same audio
+    converted to 16 kHz beforehand (`audio.resample` of the whole signal, outside the timed loop)"""
+    rate = a.sample_rate
+    r = np.random.default_rng(a.seed)
+    frames = list(r.integers(0, 256, (16, 160, 160, 3), dtype=np.uint8))
+    src = [synth.noise_wav(ticks * int(rate * 0.040), seed=a.seed * 100003 + k) for k in range(S)]
+    pre = [audio.resample(w, rate, 16000) for w in src]
+    loops = {"native": (model(dev), src, rate), "pre16": (model(dev), pre, 16000)}
+    res = {k: {"fps": [], "tick_ms": [], "step_host_ms_median": []} for k in loops}
+    for name, (G, wavs, rt) in loops.items():              # pass 0: warm-up, plans built, filter tables uploaded
+        n, t, _, launches = run_rate(G, wavs, frames, ticks, a.batch, rt)
+        res[name].update(frames=n, first_pass_s=round(t, 2), resample_launches=launches)
+    for _ in range(a.alternations):
+        for name, (G, wavs, rt) in loops.items():
+            n, t, per_tick, _ = run_rate(G, wavs, frames, ticks, a.batch, rt)
+            res[name]["fps"].append(n / t)
+            res[name]["tick_ms"].append(1e3 * t / ticks)                 # the whole pass, drain and synchronize included
+            res[name]["step_host_ms_median"].append(1e3 * float(np.median(per_tick)))
+    for name in loops:
+        for key in ("fps", "tick_ms", "step_host_ms_median"):
+            res[name][key] = stats(res[name][key], 1 if key == "fps" else 3)
+    out = {"mode": "sample_rate", "sample_rate": rate, "streams": S, "ticks": ticks, "batch": a.batch, "alternations": a.alternations,
+           "outputs_per_tick": S * 640}
+    out.update(res)
+    out["native_over_pre16_median"] = round(res["native"]["fps"]["median"] / res["pre16"]["fps"]["median"], 3)
+    out["added_tick_ms_median"] = round(res["native"]["tick_ms"]["median"] - res["pre16"]["tick_ms"]["median"], 3)
+    out["apart_by_more_than_the_spread"] = bool(res["native"]["fps"]["max"] < res["pre16"]["fps"]["min"]
+                                                or res["native"]["fps"]["min"] > res["pre16"]["fps"]["max"])
+    return out
+
+
 def stats(v, nd=1):
     return {"samples": [round(x, nd) for x in v], "median": round(float(np.median(v)), nd), "min": round(min(v), nd), "max": round(max(v), nd)}
 
@@ -291,8 +350,14 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--live_video", action="store_true", help="live face detection against detection up front (see the module text)")
+    ap.add_argument("--sample_rate", type=int, default=16000,
+                    help="other than 16000: streams fed at this rate against the same streams fed audio converted beforehand")
     a = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
+    if a.sample_rate != 16000:
+        for S, t in zip(a.streams, per_count(a.ticks, len(a.streams), "ticks")):
+            print(json.dumps(bench_rate(S, t, a, dev)), flush=True)
+        return
     if a.live_video:
         for S, t in zip(a.streams, per_count(a.ticks, len(a.streams), "ticks")):
             print(json.dumps(bench_live(S, t, a, dev)), flush=True)

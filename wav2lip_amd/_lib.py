@@ -90,6 +90,20 @@ class MelCol(C.Structure):
     _fields_ = [("stream", C.c_int32), ("rsv", C.c_int32), ("col", C.c_int64)]
 
 
+class ResampleStreamEntry(C.Structure):
+    """w2l_resample_stream_entry: one stream of w2l_resample_stream, 128 bytes"""
+    _fields_ = [("src", C.c_uint64), ("src_first", C.c_int64), ("src_total", C.c_int64), ("n_res", C.c_int64), ("dst16", C.c_uint64),
+                ("dst_first", C.c_int64), ("win", C.c_uint64), ("delta", C.c_uint64), ("carry", C.c_uint64), ("carry_first", C.c_int64),
+                ("scale", C.c_double), ("inc", C.c_double), ("src_held", C.c_int32), ("dst_cap", C.c_int32), ("index_step", C.c_int32),
+                ("nwin", C.c_int32), ("carry_held", C.c_int32), ("unused", C.c_int32 * 3)]
+
+
+class ResampleBlock(C.Structure):
+    """w2l_resample_block: up to 128 consecutive outputs of one stream of w2l_resample_stream, 32 bytes"""
+    _fields_ = [("stream", C.c_int32), ("count", C.c_int32), ("t0", C.c_int64), ("tr0", C.c_double), ("copy", C.c_int32),
+                ("unused", C.c_int32)]
+
+
 WGRAD_WINO, WGRAD_DIRECT, WGRAD_SMALL = 0, 1, 2
 
 _vp, _i, _ll, _f = C.c_void_p, C.c_int, C.c_longlong, C.c_float
@@ -169,6 +183,7 @@ SIGNATURES = {
     "w2l_mel_gather_rows": (_i, [_vp, _vp, _i, _vp, _i, _i]),
     "w2l_mel_gather_rows_bf16": (_i, [_vp, _vp, _i, _vp, _i, _i]),
     "w2l_resample_sinc": (_i, [_vp, _vp, _i, _vp, _i, C.c_double, _vp, _vp, _i, _i, _vp]),
+    "w2l_resample_stream": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i]),
     "w2l_l2norm_rows": (_i, [_vp, _i, _i, _vp, _i, _vp]),
     "w2l_cosine_bce": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "w2l_bce_mean": (_i, [_vp, _i, _vp, _vp, _vp]),

@@ -63,6 +63,28 @@ def _kaiser_best_filter():
     return _KAISER_BEST
 
 
+_resample_tables = {}      # (device index, orig_sr, target_sr) -> (win, delta) on the device
+
+
+def resample_tables(device, orig_sr, target_sr=16000):
+    """the interpolation filter of `resample` for one pair of rates, resident on `device`: (half window f64 [nwin], scaled by the
+    ratio when it is < 1; its first differences f64 [nwin], last entry 0), built and uploaded once per (device, rates) - what the
+    streaming resampler (streaming.DeviceResampler, w2l_resample_stream) reads tick after tick"""
+    device = torch.device(device)
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (idx, int(orig_sr), int(target_sr))
+    t = _resample_tables.get(key)
+    if t is None:
+        ratio = float(target_sr) / orig_sr
+        win, _ = _kaiser_best_filter()
+        if ratio < 1:
+            win = win * ratio
+        delta = np.zeros_like(win)
+        delta[:-1] = np.diff(win)
+        t = _resample_tables[key] = tuple(torch.from_numpy(a).to(torch.device("cuda", idx)) for a in (win, delta))
+    return t
+
+
 def resample(y, orig_sr, target_sr, device=None):
     """librosa 0.7.0 `resample(y, orig_sr, target_sr, res_type='kaiser_best', fix=True, scale=False)` for 1-D float32 input:
     resampy's sinc interpolation (csrc/audio_mel.hip: w2l_resample_sinc, one thread per output sample, the reference's term

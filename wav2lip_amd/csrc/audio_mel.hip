@@ -244,6 +244,93 @@ __global__ void resample_sinc_kernel(const ResampleKArgs a) {
     a.y[t] = acc;
 }
 
+// The same interpolation, incrementally and for MANY streams of any source rates in one launch (w2l_resample_stream_entry /
+// w2l_resample_block, include/w2l_hip.h; wav2lip_amd/streaming.py): one workgroup per block entry, one thread per output sample.
+// A stream holds only the source samples [src_first, src_first + src_held) of its signal.  An output is FINAL - equal to the same
+// output of the whole signal - once its right wing is no longer cut by the end of the data; the host lists final outputs only
+// and checks that the held samples cover what they read.  The kernel does not clamp a read: an output whose wings leave the held
+// range, an entry that names no stream and an output outside the destination are skipped, so that a wrong table writes nothing.
+// The time register of a block's first output comes from the host (repeated float64 addition); thread j adds the increment j
+// more times with __dadd_rn: the additions of the reference loop, in its order.
+struct ResampleStream {
+    unsigned long long src;
+    long long src_first, src_total, n_res;
+    unsigned long long dst;
+    long long dst_first;
+    unsigned long long win, delta, carry;
+    long long carry_first;
+    double scale, inc;
+    int src_held, dst_cap, index_step, nwin, carry_held, rsv[3];
+};
+struct ResampleBlock {
+    int stream, count;
+    long long t0;
+    double tr0;
+    int copy, rsv;
+};
+static_assert(sizeof(ResampleStream) == 128 && sizeof(ResampleBlock) == 32, "w2l_resample_stream_entry is 128 bytes, w2l_resample_block 32");
+constexpr int kResampleBlock = 128;
+
+struct ResampleStreamKArgs {
+    const ResampleStream* streams;
+    int nstreams;
+    const ResampleBlock* blocks;
+    int num_table;
+};
+
+__global__ __launch_bounds__(kResampleBlock) void resample_stream_kernel(const ResampleStreamKArgs a) {
+    const ResampleBlock b = a.blocks[blockIdx.x];
+    const int j = threadIdx.x;
+    if (b.stream < 0 || b.stream >= a.nstreams || j >= b.count || b.count > kResampleBlock || b.t0 < 0) return;
+    const ResampleStream s = a.streams[b.stream];
+    const long long t = b.t0 + j;
+    const long long rel = t - s.dst_first;
+    if (!s.dst || rel < 0 || rel >= s.dst_cap) return;
+    float* y = reinterpret_cast<float*>(s.dst) + rel;
+    if (b.copy) {                                  // the tail of the stream's previous buffer, carried into the fresh one
+        const long long c = t - s.carry_first;
+        if (s.carry && c >= 0 && c < s.carry_held) *y = reinterpret_cast<const float*>(s.carry)[c];
+        return;
+    }
+    if (s.n_res >= 0 && t >= s.n_res) {            // librosa's fix_length: the padded zero behind resampy's last output
+        *y = 0.f;
+        return;
+    }
+    if (!s.src || !s.win || !s.delta || s.index_step < 1 || s.src_held < 1) return;
+    double time_register = b.tr0;
+    for (int i = 0; i < j; ++i) time_register = __dadd_rn(time_register, s.inc);
+    const long long n = (long long)time_register;
+    const double* win = reinterpret_cast<const double*>(s.win);
+    const double* delta = reinterpret_cast<const double*>(s.delta);
+    double frac = __dmul_rn(s.scale, time_register - (double)n);
+    double index_frac = __dmul_rn(frac, (double)a.num_table);
+    int offset = (int)index_frac;
+    double eta = index_frac - (double)offset;
+    const long long i_max = min(n + 1, (long long)((s.nwin - offset) / s.index_step));
+    frac = s.scale - frac;
+    const double index_frac_r = __dmul_rn(frac, (double)a.num_table);
+    const int offset_r = (int)index_frac_r;
+    long long k_max = (s.nwin - offset_r) / s.index_step;
+    if (s.src_total >= 0) k_max = min(s.src_total - n - 1, k_max);
+    // what the two wings read: x[n - i_max + 1 .. n] and x[n + 1 .. n + k_max], all of it inside the held samples or nothing
+    const long long lo = n - (i_max > 0 ? i_max - 1 : 0), hi = n + (k_max > 0 ? k_max : 0);
+    if (n < 0 || offset < 0 || offset_r < 0 || lo < s.src_first || hi >= s.src_first + s.src_held) return;
+    const float* x = reinterpret_cast<const float*>(s.src) + (n - s.src_first);
+    float acc = 0.f;
+    for (long long i = 0; i < i_max; ++i) {
+        const int idx = offset + (int)i * s.index_step;
+        const double w = __dadd_rn(win[idx], __dmul_rn(eta, delta[idx]));
+        acc = (float)__dadd_rn((double)acc, __dmul_rn(w, (double)x[-i]));
+    }
+    eta = index_frac_r - (double)offset_r;
+    for (long long k = 0; k < k_max; ++k) {
+        const int idx = offset_r + (int)k * s.index_step;
+        const double w = __dadd_rn(win[idx], __dmul_rn(eta, delta[idx]));
+        acc = (float)__dadd_rn((double)acc, __dmul_rn(w, (double)x[k + 1]));
+    }
+    *y = acc;
+}
+
 extern "C" {
 
 int w2l_mel_num_frames(long long nsamples) { return (int)(1 + nsamples / kHop); }
@@ -375,6 +462,32 @@ int w2l_resample_sinc(void* stream, const float* x, int n_in, const double* tr, 
     a.index_step = (int)(a.scale * num_table);
     W2L_REQUIRE(a.index_step >= 1, "sample ratio %g too small for a table of %d samples per zero crossing", sample_ratio, num_table);
     hipLaunchKernelGGL(resample_sinc_kernel, dim3((unsigned)((n_out + 127) / 128)), dim3(128), 0, static_cast<hipStream_t>(stream), a);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_resample_stream(void* stream, const w2l_resample_stream_entry* streams_host, const w2l_resample_stream_entry* streams,
+                        int nstreams, const w2l_resample_block* blocks, int nblocks, int num_table) {
+    W2L_REQUIRE(streams_host && streams && blocks, "resample_stream: NULL argument");
+    W2L_REQUIRE(nstreams >= 1 && nstreams <= 65535 && nblocks >= 1 && nblocks <= (1 << 20) && num_table >= 1,
+                "resample_stream: 1 <= nstreams <= 65535, 1 <= nblocks <= 1048576 and num_table >= 1 (got %d, %d, %d)", nstreams,
+                nblocks, num_table);
+    W2L_REQUIRE(((reinterpret_cast<uintptr_t>(streams_host) | reinterpret_cast<uintptr_t>(streams) |
+                  reinterpret_cast<uintptr_t>(blocks)) & 15) == 0,
+                "resample_stream: 16-byte aligned stream and block tables");
+    for (int k = 0; k < nstreams; ++k) {
+        const w2l_resample_stream_entry& s = streams_host[k];
+        W2L_REQUIRE(s.src && s.dst16 && s.win && s.delta, "resample_stream: stream %d has a NULL pointer", k);
+        W2L_REQUIRE(s.index_step >= 1, "resample_stream: stream %d: index_step %d; the sample ratio is too small for the table", k,
+                    s.index_step);
+        W2L_REQUIRE(s.src_held >= 1 && s.dst_cap >= 1 && s.nwin >= 2 && s.src_first >= 0 && s.dst_first >= 0 && s.carry_held >= 0 &&
+                        (s.carry_held == 0 || s.carry) && s.scale > 0.0 && s.scale <= 1.0 && s.inc > 0.0,
+                    "resample_stream: stream %d: counts out of range", k);
+    }
+    ResampleStreamKArgs a;
+    a.streams = reinterpret_cast<const ResampleStream*>(streams); a.nstreams = nstreams;
+    a.blocks = reinterpret_cast<const ResampleBlock*>(blocks); a.num_table = num_table;
+    hipLaunchKernelGGL(resample_stream_kernel, dim3((unsigned)nblocks), dim3(kResampleBlock), 0, static_cast<hipStream_t>(stream), a);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

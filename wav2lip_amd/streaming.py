@@ -29,6 +29,28 @@ Memory per stream does not grow with its duration: a spectrogram window of `mel_
 the stream continues in a FRESH window that starts with the at most 16 columns still needed; batches in flight keep the old one
 alive (the runner's `keep=`), and no column is ever moved or overwritten under a batch that may read it.
 
+Audio at its own rate.  No live source delivers float32 mono at 16 kHz: microphones, WebRTC and capture cards
+give 48 kHz or 44.1 kHz int16, often stereo.
+
+    streams.open(key, frames, boxes, sample_rate=48000)       # `open_live(key, sample_rate=...)` likewise
+    streams.feed(key, pcm)                    # what a WAV of that rate decodes to: int16 / int32 / uint8 / float32 / float64,
+                                              # 1-D or [n, channels]; converted and mixed down as `audio.load_wav` does
+
+The contract: a stream opened at rate R and fed N source samples in all, however they are cut and interleaved, has a spectrogram
+that equals `audio.melspectrogram_device(audio.resample(whole, R, 16000))` bit for bit, and runs exactly the rows
+`multiclip.rows_inference(1 + M // 200, ...)` with M = ceil(N * 16000 / R), in order; the batching stays a deterministic function
+of the call sequence.  The conversion is `audio.resample`'s (librosa.load's resampy 'kaiser_best') and can keep that contract
+because its filter is finite: with ratio = 16000 / R, index_step = int(min(1, ratio) * 512) and K = 32769 // index_step (192
+source samples at 48 kHz, 177 at 44.1 kHz, 64 when the rate goes up) the output sample t, whose time register has the integer
+part n_t, reads the source samples n_t - K + 1 .. n_t + K: with m samples fed it is FINAL once n_t + K <= m - 1.  Per `step` ONE
+staged copy (the new source samples of every such stream plus the at most K + 1 earlier ones the left wings read) and ONE
+w2l_resample_stream launch (csrc/audio_mel.hip) compute the newly final 16 kHz samples of all streams, whatever their rates, into
+per-stream device buffers of `resample_buffer` samples; w2l_mel_stream_cols reads them where they lie, with the count of final
+samples in the place of the samples fed.  The time register is continued by sequential float64 addition from tick to tick, as the
+reference accumulates it.  A full buffer continues in a fresh one whose head - the at most 801 samples a column not yet done
+reads - is copied in the same launch.  `close` applies its length checks to M.  A stream at 16000 Hz is what it always was: the
+same launches, float32 1-D input only.  `launches` counts the spectrogram launches, `resample_launches` these.
+
 Live video.  A stream whose camera frames arrive with its audio has neither frames nor boxes to open with:
 
     streams = LipsyncStreams(model, sink=deliver, detector=face_detection.FaceAlignment(...), pads=(0, 10, 0, 0), smooth_T=5)
@@ -57,7 +79,8 @@ delivered; `feed` / `feed_frames` on it then raise KeyError.
 
 `python -m wav2lip_amd.streaming --checkpoint_path C --face F0 --audio A0 --face F1 --audio A1 ... --outdir D` feeds every audio
 file in `--chunk_ms` slices round-robin, steps after each round and writes one AVI per stream; with `--live_video` every video is
-fed frame by frame as its audio goes by and `face_detect` is never called.
+fed frame by frame as its audio goes by and `face_detect` is never called; with `--native_rate` every WAV is fed at the file's
+own rate and sample format instead of being converted up front.
 """
 import collections
 import os
@@ -77,6 +100,53 @@ MAX_COLS_PER_LAUNCH = 1 << 20         # w2l_mel_stream_cols' limit
 MEL_STREAM = np.dtype([("samples", "<u8"), ("first", "<i8"), ("total", "<i8"), ("window", "<u8"), ("held", "<i4"), ("cap", "<i4"),
                        ("col0", "<i8")])
 MEL_COL = np.dtype([("stream", "<i4"), ("rsv", "<i4"), ("col", "<i8")])
+
+RATE16 = 16000                        # hparams.py: sample_rate, the rate the spectrogram is specialised to
+RESAMPLE_TABLE, RESAMPLE_NWIN = 512, 64 * 512 + 1         # resampy's kaiser_best: table samples per zero crossing, half window
+RESAMPLE_BLOCK = 128                  # outputs per block entry of w2l_resample_stream (one thread each)
+MAX_BLOCKS_PER_LAUNCH = 1 << 20       # w2l_resample_stream's limit
+MIN_BUFFER16 = 2048                   # 16 kHz samples: the at most 801 the spectrogram still reads + room to go on
+# numpy mirrors of w2l_resample_stream_entry (128 bytes) and w2l_resample_block (32 bytes); ctypes: _lib.ResampleStreamEntry / ResampleBlock
+RESAMPLE_STREAM = np.dtype([("src", "<u8"), ("src_first", "<i8"), ("src_total", "<i8"), ("n_res", "<i8"), ("dst16", "<u8"),
+                            ("dst_first", "<i8"), ("win", "<u8"), ("delta", "<u8"), ("carry", "<u8"), ("carry_first", "<i8"),
+                            ("scale", "<f8"), ("inc", "<f8"), ("src_held", "<i4"), ("dst_cap", "<i4"), ("index_step", "<i4"),
+                            ("nwin", "<i4"), ("carry_held", "<i4"), ("unused", "<i4", (3,))])
+RESAMPLE_BLOCKS = np.dtype([("stream", "<i4"), ("count", "<i4"), ("t0", "<i8"), ("tr0", "<f8"), ("copy", "<i4"), ("unused", "<i4")])
+
+
+def resample_params(rate):
+    """(ratio, increment of the time register, scale, index_step, K) of resampy's kaiser_best from `rate` to 16 kHz; K is how
+    many source samples each wing of the filter reaches.  ValueError for a rate that is no positive integer or whose table step
+    would be 0 (above 8 192 000 Hz)"""
+    if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)) or rate < 1:
+        raise ValueError("sample_rate must be a positive integer, got %r" % (rate,))
+    ratio = float(RATE16) / int(rate)
+    scale = min(1.0, ratio)
+    index_step = int(scale * RESAMPLE_TABLE)
+    if index_step < 1:
+        raise ValueError("sample_rate %d: the interpolation table has no step that small (at most %d Hz)" % (rate, RATE16 * RESAMPLE_TABLE))
+    return ratio, 1.0 / ratio, scale, index_step, RESAMPLE_NWIN // index_step
+
+
+def resample_sample_range(tr, K, total=-1):
+    """[lo, hi] of the source samples the output with time register `tr` reads: its left wing x[n], x[n-1], ... and its right
+    wing x[n+1], ..., K samples each at the most, cut by the start and - total: the signal's length once known, else -1 - the end"""
+    n = int(tr)
+    return max(0, n - K + 1), (n + K if total < 0 else max(n, min(n + K, total - 1)))
+
+
+def native_samples(samples):
+    """what `audio.load_wav` makes of decoded PCM before it resamples, with its numpy expressions: int16 / int32 / uint8 /
+    float32 / float64, 1-D or [n, channels] -> float32 mono.  Both steps are sample-wise, so they do not depend on the cut."""
+    from . import audio
+    data = np.asarray(samples)
+    if data.ndim not in (1, 2) or data.dtype not in (np.int16, np.int32, np.uint8, np.float32, np.float64):
+        raise ValueError("feed: int16, int32, uint8, float32 or float64 samples, 1-D or [n, channels], expected; got %s %s"
+                         % (data.dtype, data.shape))
+    x = audio._pcm_to_float32(data)
+    if x.ndim > 1:
+        x = x.T.mean(axis=0)
+    return np.ascontiguousarray(x, dtype=np.float32)
 
 
 def final_columns(n, closed=False):
@@ -116,21 +186,115 @@ def bucket(n, batch_size):
     return batch_size
 
 
+class ResampleState:
+    """host bookkeeping of one stream's conversion to 16 kHz, no device in it: the source samples a later
+    output's left wing reads, the running time register, the count of final 16 kHz samples and where they lie"""
+
+    def __init__(self, key, rate, cap16):
+        self.key, self.rate, self.cap16 = key, int(rate), int(cap16)
+        self.ratio, self.inc, self.scale, self.index_step, self.K = resample_params(rate)
+        self.n_src, self.closed = 0, False
+        self.held, self.held_first, self.chunks = np.empty(0, np.float32), 0, []
+        self.n16, self.tr_next = 0, 0.0       # final 16 kHz samples computed; the time register of the next one
+        self.n_res = self.total16 = None      # after close: resampy's int(N * ratio), librosa's ceil(N * ratio)
+        self.buf, self.buf_first = None, 0    # the device buffer that holds the 16 kHz samples [buf_first, n16)
+        self.need16 = 0                       # the first 16 kHz sample a spectrogram column not yet done reads
+
+    def feed(self, x):
+        if x.size:
+            self.chunks.append(x)
+            self.n_src += x.size
+
+    def close(self):
+        self.closed = True
+        self.n_res, self.total16 = int(self.n_src * self.ratio), int(np.ceil(self.n_src * self.ratio))
+
+    def samples(self):
+        """the held source samples as one array (absolute index of [0]: held_first)"""
+        if self.chunks:
+            self.held = np.concatenate([self.held] + self.chunks)
+            self.chunks = []
+        return self.held
+
+    def registers(self, count):
+        """the time registers of the next `count` outputs: the running one continued by sequential float64 addition (cumsum),
+        as the reference accumulates them - never t * increment"""
+        inc = np.full(count, self.inc, dtype=np.float64)
+        inc[0] = self.tr_next
+        return np.cumsum(inc)
+
+    def new_final(self, at_most):
+        """(how many of the next `at_most` outputs are final, their time registers).  Output t with n = int(register) reads up
+        to source sample n + K: final once n + K <= n_src - 1, i.e. register < n_src - K; all of them once the stream is closed"""
+        if self.closed:
+            c = min(at_most, self.total16 - self.n16)
+            return c, (self.registers(c) if c else None)
+        limit = self.n_src - self.K
+        est = min(at_most, int(max(0.0, limit - self.tr_next) * self.ratio) + 2)
+        while limit > 0:
+            tr = self.registers(est)
+            c = int(np.searchsorted(tr, limit, "left"))
+            if c < est or est == at_most:
+                return c, tr[:c]
+            est = min(at_most, 2 * est)
+        return 0, None
+
+    def plan(self):
+        """what the next launch computes: None, or (roll, first output, count, time registers).  roll: None, or the absolute
+        16 kHz sample a fresh buffer starts at because the outputs wanted do not fit behind the ones done"""
+        c, tr = self.new_final(self.cap16)
+        if c == 0:
+            return None
+        roll, first = None, self.buf_first
+        if self.n16 + c > first + self.cap16 and self.need16 > first:
+            roll = first = self.need16
+        c = min(c, first + self.cap16 - self.n16)
+        if c <= 0:
+            return None                       # full of samples the spectrogram has yet to read
+        return roll, self.n16, c, tr[:c]
+
+    def commit(self, count, tr):
+        self.n16 += count
+        self.tr_next = float(tr[count - 1]) + self.inc
+        x = self.samples()
+        lo = self.n_src if self.closed and self.n16 == self.total16 else max(0, int(self.tr_next) - self.K)
+        if lo > self.held_first:
+            self.held = x[lo - self.held_first:].copy()
+            self.held_first = lo
+
+
+class Resident:
+    """samples that already lie on the device: `size` float32 values from element `offset` of `buffer` (a stream's 16 kHz
+    buffer).  `DeviceMel.compute` reads them where they lie and stages nothing."""
+
+    def __init__(self, buffer, offset, size):
+        self.buffer, self.offset, self.size = buffer, int(offset), int(size)
+
+    def address(self):
+        return self.buffer.data_ptr() + 4 * self.offset
+
+
 class StreamState:
-    """host bookkeeping of one stream, no device in it: samples held, columns done, the window's position, rows emitted"""
+    """host bookkeeping of one stream, no device in it: samples held, columns done, the window's position, rows emitted.
+    sample_rate other than 16000: the samples fed are converted on the device first (`rs`, a ResampleState with a buffer of
+    `cap16` samples) and the spectrogram reads the 16 kHz samples there."""
     live = False
 
-    def __init__(self, key, frames, boxes, static, fps, cap):
+    def __init__(self, key, frames, boxes, static, fps, cap, sample_rate=RATE16, cap16=MIN_BUFFER16):
         self.key, self.frames, self.boxes, self.static, self.fps, self.cap = key, frames, boxes, bool(static), float(fps), int(cap)
         self.n_fed, self.closed = 0, False
         self.held, self.held_first, self.chunks = np.empty(0, np.float32), 0, []
         self.cols_done, self.col0, self.window = 0, 0, None
         self.next_row, self.rows_done, self.n_rows, self.delivered = 0, False, None, 0
+        self.rs = None if sample_rate == RATE16 else ResampleState(key, sample_rate, cap16)
 
     # ---- audio
     def feed(self, samples):
         if self.closed:
             raise ValueError("stream %r is closed" % (self.key,))
+        if self.rs is not None:
+            self.rs.feed(native_samples(samples))
+            return
         x = np.ascontiguousarray(samples, dtype=np.float32)
         if x.ndim != 1:
             raise ValueError("feed: 1-D samples expected, got shape %s" % (x.shape,))
@@ -145,9 +309,23 @@ class StreamState:
             self.chunks = []
         return self.held
 
+    def end_audio(self):
+        """no more samples follow"""
+        self.closed = True
+        if self.rs is not None:
+            self.rs.close()
+
+    def mel_samples(self):
+        """the 16 kHz samples the spectrogram can read so far"""
+        return self.n_fed if self.rs is None else self.rs.n16
+
+    def mel_closed(self):
+        """closed for the spectrogram: the stream is closed and every 16 kHz sample of it is there"""
+        return self.closed and (self.rs is None or self.rs.n16 == self.rs.total16)
+
     # ---- columns
     def target(self):
-        return final_columns(self.n_fed, self.closed)
+        return final_columns(self.mel_samples(), self.mel_closed())
 
     def plan(self):
         """what the next launch computes for this stream: None, or (roll, first column, count).  roll: None, or the absolute
@@ -168,11 +346,15 @@ class StreamState:
 
     def commit(self, count):
         self.cols_done += count
-        x = self.samples()
+        n = self.mel_samples()
         lo = first_sample_needed(self.cols_done)
-        if self.closed:
+        if self.mel_closed():
             # every column done: no sample is needed again; else the reflected end reads back to n - 402
-            lo = self.n_fed if self.cols_done == self.target() else min(lo, max(0, self.n_fed - NFFT // 2 - 2))
+            lo = n if self.cols_done == self.target() else min(lo, max(0, n - NFFT // 2 - 2))
+        if self.rs is not None:
+            self.rs.need16 = lo               # the samples stay where they are: a fresh 16 kHz buffer starts here
+            return
+        x = self.samples()
         if lo > self.held_first:
             self.held = x[lo - self.held_first:].copy()
             self.held_first = lo
@@ -185,7 +367,7 @@ class StreamState:
             s = row_start(self.next_row, self.fps)
             if s + mel_step_size <= self.cols_done:
                 pass
-            elif self.closed and self.cols_done == self.target():
+            elif self.mel_closed() and self.cols_done == self.target():
                 s = self.cols_done - mel_step_size            # the tail window, re-anchored at the end (inference.py:237-239)
                 self.rows_done, self.n_rows = True, self.next_row + 1
             else:
@@ -220,8 +402,8 @@ class LiveState(StreamState):
     the device, the boxes that are final so far - still no device in it"""
     live = True
 
-    def __init__(self, key, fps, cap, cycle):
-        StreamState.__init__(self, key, None, [], False, fps, cap)
+    def __init__(self, key, fps, cap, cycle, sample_rate=RATE16, cap16=MIN_BUFFER16):
+        StreamState.__init__(self, key, None, [], False, fps, cap, sample_rate=sample_rate, cap16=cap16)
         self.cycle = bool(cycle)
         self.shape = None                     # (H, W): fixed by the first frame fed
         self.fresh, self.n_frames = [], 0     # host arrays / device tensors fed since the last tick; frames fed in all
@@ -279,7 +461,7 @@ class LiveState(StreamState):
             s, tail = row_start(i, self.fps), False
             if s + mel_step_size <= self.cols_done:
                 pass
-            elif self.closed and self.cols_done == self.target():
+            elif self.mel_closed() and self.cols_done == self.target():
                 s, tail = self.cols_done - mel_step_size, True
             else:
                 break
@@ -446,7 +628,8 @@ class DeviceMel:
         return window.numel() * window.element_size()
 
     def compute(self, items):
-        """items: (samples float32 array, absolute index of samples[0], total or -1, window, cap, col0, first column, count)"""
+        """items: (samples float32 array, absolute index of samples[0], total or -1, window, cap, col0, first column, count);
+        samples may be a `Resident` instead: they lie on the device already and nothing is staged for them"""
         from . import _lib
         from ._lib import check, ptr
         torch = self.torch
@@ -457,7 +640,8 @@ class DeviceMel:
         at = []
         for it in items:
             at.append(off)
-            off = _align(off + it[0].nbytes)
+            if not isinstance(it[0], Resident):
+                off = _align(off + it[0].nbytes)
         host = torch.empty(off, dtype=torch.uint8, pin_memory=True)
         dev = torch.empty(off, dtype=torch.uint8, device=self.device)
         stage = host.numpy()
@@ -465,8 +649,11 @@ class DeviceMel:
         ct = stage[col_off:col_off + ncols * MEL_COL.itemsize].view(MEL_COL)
         c = 0
         for k, (x, first, total, window, cap, col0, lo, count) in enumerate(items):
-            stage[at[k]:at[k] + x.nbytes] = x.view(np.uint8)
-            st[k] = (dev.data_ptr() + at[k], first, total, window.data_ptr(), x.size, cap, col0)
+            if isinstance(x, Resident):
+                st[k] = (x.address(), first, total, window.data_ptr(), x.size, cap, col0)
+            else:
+                stage[at[k]:at[k] + x.nbytes] = x.view(np.uint8)
+                st[k] = (dev.data_ptr() + at[k], first, total, window.data_ptr(), x.size, cap, col0)
             ct["stream"][c:c + count] = k
             ct["rsv"][c:c + count] = 0
             ct["col"][c:c + count] = np.arange(lo, lo + count)
@@ -506,15 +693,134 @@ def advance_columns(mel, states):
             st.window, st.col0 = fresh, roll
         elif st.window is None:
             st.window = mel.new_window(st.cap)
-        x = st.samples()
-        total = st.n_fed if st.closed else -1
-        check_coverage(st.held_first, x.size, total, lo, count, st.key)
-        items.append((x, st.held_first, total, st.window, st.cap, st.col0, lo, count))
+        if st.rs is not None:                 # the 16 kHz samples [buf_first, n16) lie in the stream's device buffer
+            x, first = Resident(st.rs.buf, 0, st.rs.n16 - st.rs.buf_first), st.rs.buf_first
+        else:
+            x, first = st.samples(), st.held_first
+        total = st.mel_samples() if st.mel_closed() else -1
+        check_coverage(first, x.size, total, lo, count, st.key)
+        items.append((x, first, total, st.window, st.cap, st.col0, lo, count))
         done.append((st, count))
     if items:
         mel.compute(items)
         for st, count in done:
             st.commit(count)
+    return bool(items)
+
+
+class DeviceResampler:
+    """the device side of the incremental sample-rate conversion: 16 kHz buffers, the filter tables of every source rate
+    (resident, `audio.resample_tables`), and one staged copy + one w2l_resample_stream launch per call"""
+
+    def __init__(self, device):
+        import torch
+        from . import _lib
+        self.torch, self.device, self.lib = torch, device, _lib.load()
+
+    def new_buffer(self, cap16):
+        return self.torch.zeros(cap16, dtype=self.torch.float32, device=self.device)
+
+    @staticmethod
+    def buffer_bytes(buf):
+        return buf.numel() * buf.element_size()
+
+    def compute(self, items):
+        """items: (source samples float32 array, absolute index of [0], total or -1, n_res or -1, buffer, absolute 16 kHz index
+        of buffer[0], its samples, carry or None, source rate, first output, count, time registers of the outputs).
+        carry: (previous buffer, absolute index of its [0], first sample to copy, count) - the copy runs in the same launch"""
+        from . import _lib, audio
+        from ._lib import check, ptr
+        torch, B = self.torch, RESAMPLE_BLOCK
+        nblocks = sum((it[10] + B - 1) // B + ((it[7][3] + B - 1) // B if it[7] else 0) for it in items)
+        blk_off = _align(len(items) * RESAMPLE_STREAM.itemsize)
+        off = _align(blk_off + nblocks * RESAMPLE_BLOCKS.itemsize)
+        at = []
+        for it in items:
+            at.append(off)
+            off = _align(off + it[0].nbytes)
+        host = torch.empty(off, dtype=torch.uint8, pin_memory=True)
+        dev = torch.empty(off, dtype=torch.uint8, device=self.device)
+        stage = host.numpy()
+        st = stage[:len(items) * RESAMPLE_STREAM.itemsize].view(RESAMPLE_STREAM)
+        bt = stage[blk_off:blk_off + nblocks * RESAMPLE_BLOCKS.itemsize].view(RESAMPLE_BLOCKS)
+        b = 0
+        for k, (x, first, total, n_res, buf, buf_first, cap16, carry, rate, t0, count, tr) in enumerate(items):
+            _, inc, scale, index_step, _ = resample_params(rate)
+            win, delta = audio.resample_tables(self.device, rate, RATE16)
+            stage[at[k]:at[k] + x.nbytes] = x.view(np.uint8)
+            old, old_first, c0, cn = carry if carry else (None, 0, 0, 0)
+            st[k] = (dev.data_ptr() + at[k], first, total, n_res, buf.data_ptr(), buf_first, win.data_ptr(), delta.data_ptr(),
+                     old.data_ptr() if cn else 0, old_first, scale, inc, x.size, cap16, index_step, win.numel(),
+                     old.numel() if cn else 0, (0, 0, 0))
+            mine = resample_blocks(k, t0, tr, c0, cn)
+            bt[b:b + len(mine)] = mine
+            b += len(mine)
+        assert b == nblocks
+        dev.copy_(host, non_blocking=True)
+        with torch.cuda.device(self.device):
+            for lo in range(0, nblocks, MAX_BLOCKS_PER_LAUNCH):
+                n = min(MAX_BLOCKS_PER_LAUNCH, nblocks - lo)
+                check(self.lib.w2l_resample_stream(_lib.current_stream(), host.data_ptr(), ptr(dev), len(items),
+                                                   dev.data_ptr() + blk_off + lo * RESAMPLE_BLOCKS.itemsize, n, RESAMPLE_TABLE),
+                      "resample_stream")
+
+
+def resample_blocks(stream, t0, tr, carry_first=0, carry_count=0):
+    """the block entries (RESAMPLE_BLOCKS) of one stream in a launch: copy blocks for the `carry_count` samples from
+    `carry_first` on that a fresh buffer takes over, then compute blocks for the outputs t0 .. t0 + len(tr) - 1, each of up to 128
+    consecutive outputs with the time register of its FIRST one; the kernel's thread j adds the increment j times to it"""
+    B, count = RESAMPLE_BLOCK, len(tr)
+    out = np.zeros((carry_count + B - 1) // B + (count + B - 1) // B, RESAMPLE_BLOCKS)
+    b = 0
+    for lo in range(0, carry_count, B):
+        out[b] = (stream, min(B, carry_count - lo), carry_first + lo, 0.0, 1, 0)
+        b += 1
+    for lo in range(0, count, B):
+        out[b] = (stream, min(B, count - lo), t0 + lo, tr[lo], 0, 0)
+        b += 1
+    return out
+
+
+def check_resample_coverage(x_first, x_size, total, K, tr, key=None):
+    """the held source samples [x_first, x_first + x_size) cover what the outputs with the time registers `tr` read; the kernel
+    does not clamp (it would skip the output) - so this is checked before every launch.  The registers grow: the first output's
+    left wing and the last one's right wing bound the rest."""
+    a, b = resample_sample_range(tr[0], K, total)[0], resample_sample_range(tr[-1], K, total)[1]
+    if a < x_first or b >= x_first + x_size:
+        raise RuntimeError("stream %r: %d outputs read source samples [%d, %d], held are [%d, %d)"
+                           % (key, len(tr), a, b, x_first, x_first + x_size))
+
+
+def advance_samples(resampler, states):
+    """one staged copy + one launch on `resampler` (a DeviceResampler): the final 16 kHz samples every stream of `states` with
+    a source rate of its own has buffer room for, continuing a full buffer in a fresh one first (its tail is carried over in
+    the same launch); False when no stream had any"""
+    items, done = [], []
+    for st in states:
+        rs = st.rs
+        p = rs.plan() if rs is not None else None
+        if p is None:
+            continue
+        roll, t0, count, tr = p
+        carry = None
+        if roll is not None or rs.buf is None:
+            fresh = resampler.new_buffer(rs.cap16)
+            if roll is not None and rs.n16 > roll:
+                carry = (rs.buf, rs.buf_first, roll, rs.n16 - roll)
+            rs.buf, rs.buf_first = fresh, roll or 0
+        x = rs.samples()
+        total, n_res = (rs.n_src, rs.n_res) if rs.closed else (-1, -1)
+        reading = count if n_res < 0 else max(0, min(count, n_res - t0))      # behind n_res: the padded zero, which reads nothing
+        if reading:
+            check_resample_coverage(rs.held_first, x.size, total, rs.K, tr[:reading], st.key)
+        if x.size < 1:
+            raise RuntimeError("stream %r: no source samples held for outputs [%d, %d)" % (st.key, t0, t0 + count))
+        items.append((x, rs.held_first, total, n_res, rs.buf, rs.buf_first, rs.cap16, carry, rs.rate, t0, count, tr))
+        done.append((rs, count, tr))
+    if items:
+        resampler.compute(items)
+        for rs, count, tr in done:
+            rs.commit(count, tr)
     return bool(items)
 
 
@@ -524,13 +830,18 @@ class LipsyncStreams:
     `drain` returns).  `on_batch(rows)` receives each launched batch's [(key, row index)] including the padding rows."""
 
     def __init__(self, model, batch_size=128, depth=None, precision="f32", fps=25., sink=None, on_batch=None, mel_window=1024,
-                 detector=None, pads=(0, 10, 0, 0), smooth_T=5, face_det_batch_size=16):
+                 detector=None, pads=(0, 10, 0, 0), smooth_T=5, face_det_batch_size=16, resample_buffer=1 << 16):
         from .models.wav2lip import check_precision
         self.precision = check_precision(precision)
         if batch_size < 1:
             raise ValueError("batch_size must be at least 1")
         if mel_window < MIN_WINDOW:
             raise ValueError("mel_window must be at least %d columns" % MIN_WINDOW)
+        if resample_buffer < MIN_BUFFER16:
+            raise ValueError("resample_buffer must be at least %d samples" % MIN_BUFFER16)
+        self.resample_buffer = int(resample_buffer)      # 16 kHz samples per stream opened at another rate
+        self._resampler = None                           # DeviceResampler, once such a stream has something to convert
+        self.resample_launches = 0                       # w2l_resample_stream staging copies + launches so far
         self.model, self.batch_size, self.depth, self.fps = model, int(batch_size), depth or LIPSYNC_DEPTH, float(fps)
         self.mel_window, self.on_batch = int(mel_window), on_batch
         self.frames = None
@@ -564,9 +875,11 @@ class LipsyncStreams:
         self._slots, self._free_slots = {}, []           # carry slot per live stream whose video is under way
 
     # ---- the stream's life
-    def open(self, key, frames, boxes, static=False, fps=None):
+    def open(self, key, frames, boxes, static=False, fps=None, *, sample_rate=RATE16):
+        """sample_rate: the rate of the samples `feed` will bring; other than 16000 they are converted on the device"""
         if key in self._streams:
             raise ValueError("stream %r is already open" % (key,))
+        resample_params(sample_rate)
         frames = list(frames)
         if not frames:
             raise ValueError("stream %r: no frames" % (key,))
@@ -580,16 +893,19 @@ class LipsyncStreams:
                 raise ValueError("stream %r: %s" % (key, e)) from None
         if len(checked) != (1 if static else len(frames)):
             raise ValueError("stream %r: one box per frame" % (key,))
-        self._streams[key] = StreamState(key, frames, checked, static, self.fps if fps is None else fps, self.mel_window)
+        self._streams[key] = StreamState(key, frames, checked, static, self.fps if fps is None else fps, self.mel_window,
+                                         sample_rate=int(sample_rate), cap16=self.resample_buffer)
 
-    def open_live(self, key, fps=None, cycle=True):
+    def open_live(self, key, fps=None, cycle=True, *, sample_rate=RATE16):
         """a stream whose video arrives with its audio: no frames and no boxes; `feed_frames` brings frames, the detector of
         the constructor finds the faces as they come.  cycle=False: the rows end with the video instead of cycling over it."""
         if self.detector is None:
             raise ValueError("stream %r: open_live needs LipsyncStreams(detector=...)" % (key,))
         if key in self._streams:
             raise ValueError("stream %r is already open" % (key,))
-        self._streams[key] = LiveState(key, self.fps if fps is None else fps, self.mel_window, cycle)
+        resample_params(sample_rate)
+        self._streams[key] = LiveState(key, self.fps if fps is None else fps, self.mel_window, cycle, sample_rate=int(sample_rate),
+                                       cap16=self.resample_buffer)
 
     def _get_live(self, key):
         st = self._get(key)
@@ -617,13 +933,16 @@ class LipsyncStreams:
             raise KeyError("no open stream %r" % (key,)) from None
 
     def feed(self, key, samples):
+        """float32 1-D samples at 16 kHz; on a stream opened at another rate what a WAV of that rate decodes to: int16, int32,
+        uint8, float32 or float64, 1-D or [n, channels] (`native_samples`)"""
         self._get(key).feed(samples)
 
     def close(self, key):
         st = self._get(key)
         if st.closed:
             raise ValueError("stream %r is closed" % (key,))
-        n = st.n_fed
+        # the length of the 16 kHz signal: librosa's ceil(N * ratio) for a stream at another rate
+        n = st.n_fed if st.rs is None else int(np.ceil(st.rs.n_src * st.rs.ratio))
         if n < MIN_SAMPLES or final_columns(n, True) < mel_step_size:
             del self._streams[key]
             if n < MIN_SAMPLES:
@@ -631,7 +950,7 @@ class LipsyncStreams:
             # lipsync() on such audio fails in w2l_mel_gather (T >= 16): the same exception type, at close
             raise RuntimeError("stream %r: %d samples give %d mel columns; the generator needs a window of %d"
                                % (key, n, final_columns(n, True), mel_step_size))
-        st.closed = True
+        st.end_audio()
 
     # ---- the tick
     def _backend(self):
@@ -642,9 +961,15 @@ class LipsyncStreams:
             self._boxes = DeviceBoxes(self._runner.device, self.detector, self.pads, self.smooth_T, self.face_det_batch_size)
 
     def _columns_round(self):
+        converted = False
+        if any(st.rs is not None for st in self._streams.values()):      # streams at 16 kHz: no launch, nothing built
+            if self._resampler is None:
+                self._resampler = DeviceResampler(self._runner.device)
+            converted = advance_samples(self._resampler, self._streams.values())
+            self.resample_launches += converted
         more = advance_columns(self._mel, self._streams.values())
         self.launches += more
-        return more
+        return more or converted
 
     def step(self, flush=False):
         """compute the newly final columns (one launch for all streams; more only while a stream's backlog exceeds its window),
@@ -672,7 +997,7 @@ class LipsyncStreams:
         """a live stream none of whose rows is under way leaves"""
         if self._streams.get(st.key) is st:
             del self._streams[st.key]
-        st.frames = st.window = None
+        st.frames = st.window = st.rs = None
         st.video, st.fresh = [], []
         self.sink(st.key, None)
 
@@ -765,7 +1090,7 @@ class LipsyncStreams:
             if st.finished():
                 if self._streams.get(st.key) is st:
                     del self._streams[st.key]
-                st.frames = st.window = None
+                st.frames = st.window = st.rs = None
                 self.sink(st.key, None)
 
     def drain(self):
@@ -778,10 +1103,11 @@ class LipsyncStreams:
         return self.frames
 
     def device_bytes(self, key=None):
-        """device memory held per stream between ticks: its spectrogram window (the staging of a tick is transient), and of a
-        live stream the frames resident on the device"""
+        """device memory held per stream between ticks: its spectrogram window (the staging of a tick is transient), of a
+        stream at another rate than 16 kHz its buffer of converted samples, and of a live stream the frames resident on the device"""
         sts = list(self._streams.values() if key is None else [self._get(key)])
         return (sum(DeviceMel.window_bytes(st.window) for st in sts if st.window is not None)
+                + sum(DeviceResampler.buffer_bytes(st.rs.buf) for st in sts if st.rs is not None and st.rs.buf is not None)
                 + sum(ch.nbytes for st in sts if st.live for ch in st.video))
 
 
@@ -809,6 +1135,8 @@ def build_parser():
     p.add_argument('--face_det_precision', default='fp32', choices=['fp32', 'bf16'], help='Face detector arithmetic')
     p.add_argument('--live_video', default=False, action='store_true',
                    help='Feed the frames of every video as they become due with the audio and detect faces as they arrive')
+    p.add_argument('--native_rate', default=False, action='store_true',
+                   help="Feed every WAV at the file's own rate and format; it is converted to 16 kHz on the device as it streams")
     from .inference import add_det_scale_flag
     add_det_scale_flag(p)
     return p
@@ -818,10 +1146,12 @@ def main(argv=None, state_dict=None):
     """feed every `--audio` in `--chunk_ms` slices round-robin to its `--face`, step after each round, write <outdir>/<k>.avi as
     each stream ends; returns the written paths in stream order.  With `--live_video` a video (not an image, no `--box`) is fed
     frame by frame as its audio goes by - floor(fps * samples fed / 16000) frames so far - and `face_detect` is never called.
-    `state_dict` (S3FD weights) replaces face_detection/s3fd.pth."""
+    With `--native_rate` a WAV is not converted up front: its samples are fed as the file holds them, in `--chunk_ms` slices of
+    its own rate, to a stream opened at that rate.  `state_dict` (S3FD weights) replaces face_detection/s3fd.pth."""
     import copy
 
     import torch
+    from scipy.io import wavfile
 
     from . import audio, inference
     a = build_parser().parse_args(argv)
@@ -853,7 +1183,12 @@ def main(argv=None, state_dict=None):
             boxes = [c for _, c in det]
         else:
             boxes = [tuple(a.box)] * len(frames)
-        jobs.append(dict(key=k, frames=frames, fps=fps, boxes=boxes, static=one.static, wav=audio.load_wav(wav_path, 16000),
+        # --native_rate: the samples as the file holds them (int16 / int32 / uint8 / float, 1-D or [n, channels]) at its rate
+        rate, wav = wavfile.read(wav_path) if a.native_rate else (RATE16, None)
+        if rate == RATE16:                    # a 16 kHz stream takes float32 mono, as it always has
+            wav = audio.load_wav(wav_path, RATE16)
+        jobs.append(dict(key=k, frames=frames, fps=fps, boxes=boxes, static=one.static, wav=wav, rate=int(rate),
+                         chunk=max(1, int(round(rate * a.chunk_ms / 1000.))),
                          audio=wav_path, out=os.path.join(a.outdir, "%d.avi" % k), pos=0, live=live, fed=0))
     os.makedirs(a.outdir, exist_ok=True)
     model = inference.load_model(a.checkpoint_path, dev)
@@ -871,18 +1206,17 @@ def main(argv=None, state_dict=None):
                              detector=detector, pads=a.pads, smooth_T=0 if a.nosmooth else 5, face_det_batch_size=a.face_det_batch_size)
     for j in jobs:
         if j["live"]:
-            streams.open_live(j["key"], fps=j["fps"])
+            streams.open_live(j["key"], fps=j["fps"], sample_rate=j["rate"])
         else:
-            streams.open(j["key"], j["frames"], j["boxes"], static=j["static"], fps=j["fps"])
-    chunk = max(1, int(round(16000 * a.chunk_ms / 1000.)))
+            streams.open(j["key"], j["frames"], j["boxes"], static=j["static"], fps=j["fps"], sample_rate=j["rate"])
     live = list(jobs)
     while live:
         for j in live:
-            streams.feed(j["key"], j["wav"][j["pos"]:j["pos"] + chunk])
-            j["pos"] += chunk
+            streams.feed(j["key"], j["wav"][j["pos"]:j["pos"] + j["chunk"]])
+            j["pos"] += j["chunk"]
             if j["live"] and j["fed"] is not None:
                 # the frames that have become due; the audio's end brings the rest of the video
-                due = len(j["frames"]) if j["pos"] >= len(j["wav"]) else min(len(j["frames"]), int(j["fps"] * j["pos"] / 16000.))
+                due = len(j["frames"]) if j["pos"] >= len(j["wav"]) else min(len(j["frames"]), int(j["fps"] * j["pos"] / float(j["rate"])))
                 if due > j["fed"]:
                     streams.feed_frames(j["key"], j["frames"][j["fed"]:due])
                     j["fed"] = due
