@@ -217,15 +217,6 @@ def test_host_boxes_is_face_detect_with_a_stub_detector(pads):
     assert many.host_boxes([], 40, 50, pads, 5).shape == (0, 4)
 
 
-def test_segment_mirror_has_the_size_of_the_header_and_the_symbols_are_bound():
-    from wav2lip_amd import _lib
-    from wav2lip_amd.face_detection import many
-    assert many.BOX_SEGMENT.itemsize == ctypes.sizeof(_lib.BoxSegment) == 16
-    assert [many.BOX_SEGMENT.fields[n][1] for n in ("row0", "n", "H", "W")] == [getattr(_lib.BoxSegment, n).offset for n in ("row0", "n", "H", "W")] == [0, 4, 8, 12]
-    for sym in ("w2l_s3fd_pack_rows", "w2l_s3fd_pack_rows_bf16", "w2l_face_boxes_segments"):
-        assert sym in _lib.SIGNATURES
-
-
 def test_both_commands_take_the_flag_and_default_to_off():
     from wav2lip_amd import calculate_scores as cs, gen_videos_from_filelist as gv
     base = ["--filelist", "f", "--results_dir", "r", "--data_root", "d", "--checkpoint_path", "c"]

@@ -1,11 +1,8 @@
 """Host side of the filelist generation path (wav2lip_amd/multiclip.py, wav2lip_amd/gen_videos_from_filelist.py): the two row
 conventions against the executed reference (tests/golden/golden_filelist_v1.npz) and `mel_chunk_starts`, the packer with its
-device side stubbed at the `BatchRunner` seam, the command-line surface, the dealing of lines to ranks and the Python mirrors of
-the two row structs."""
-import ctypes
+device side stubbed at the `BatchRunner` seam, the command-line surface and the dealing of lines to ranks."""
 import json
 import os
-import re
 import types
 
 import numpy as np
@@ -189,21 +186,3 @@ def test_lines_are_dealt_to_ranks_round_robin():
     assert [[i for i, _ in p] for p in parts] == [[0, 3, 6], [1, 4], [2, 5]]
     assert sorted(x for p in parts for x in p) == list(enumerate(lines))       # every line once, with its own index
     assert gv.lines_of_rank(lines, types.SimpleNamespace(rank=0, world=1)) == list(enumerate(lines))
-
-
-def test_row_struct_mirrors_have_the_layout_the_header_states():
-    from wav2lip_amd import _lib, multiclip
-    text = open(os.path.join(ROOT, "include", "w2l_hip.h")).read()
-    stated = {name: int(size) for name, size in re.findall(r"(w2l_frame_row|w2l_mel_row), (\d+) bytes, alignment 16", text)}
-    assert stated == {"w2l_frame_row": 48, "w2l_mel_row": 16}
-    offsets = {m[1]: int(m[0]) for m in re.findall(r"offset +(\d+) +u?int\d+ +(\w+)", text)}
-    assert ctypes.sizeof(_lib.FrameRow) == multiclip.FRAME_ROW.itemsize == 48 and 48 % 16 == 0
-    assert ctypes.sizeof(_lib.MelRow) == multiclip.MEL_ROW.itemsize == 16
-    for name, field in (("src", "src"), ("dst", "dst"), ("H", "H"), ("y1", "y1"), ("pad", "pad")):
-        assert getattr(_lib.FrameRow, field).offset == multiclip.FRAME_ROW.fields[field][1] == offsets[name], name
-    assert [multiclip.FRAME_ROW.fields[f][1] for f in ("W", "y2", "x1", "x2")] == [20, 28, 32, 36]
-    assert [getattr(_lib.FrameRow, f).offset for f in ("W", "y2", "x1", "x2")] == [20, 28, 32, 36]
-    for field in ("mel", "T", "start"):
-        assert getattr(_lib.MelRow, field).offset == multiclip.MEL_ROW.fields[field][1] == offsets[field], field
-    for sym in ("w2l_crop_resize_rows_u8", "w2l_compose_rows_u8", "w2l_mel_gather_rows", "w2l_mel_gather_rows_bf16"):
-        assert sym in _lib.SIGNATURES

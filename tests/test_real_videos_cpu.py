@@ -3,7 +3,6 @@ executed reference (tests/golden/golden_real_videos_v1.npz, tests/golden/make_go
 and the producer with the device steps stubbed at their seams and the generator at the `BatchRunner` seam: pairing and order in
 `dubbed` mode, the numbering after a skipped clip, the frame / audio mismatch per mode, `tts` duplicates as rows, lazy
 consumption, and a device-tensor job that stages no frame bytes."""
-import ctypes
 import json
 import os
 import types
@@ -96,16 +95,6 @@ def test_cli_surface_is_the_references_with_typed_resolutions_plus_the_two_preci
     a = rv.cli_parser.parse_args(["--mode", "tts", "--results_dir", "r", "--data_root", "d", "--checkpoint_path", "c", "--face_res", "90"])
     assert (a.pads, a.face_det_batch_size, a.wav2lip_batch_size, a.face_res, a.min_frame_res, a.max_frame_res, a.filelist,
             a.precision, a.face_det_precision) == ([0, 10, 0, 0], 16, 128, 90, 480, 720, None, "fp32", "fp32")
-
-
-def test_resize_row_mirrors_have_the_layout_the_header_states():
-    from wav2lip_amd import _lib, real_videos_inference as rv
-    text = open(os.path.join(ROOT, "include", "w2l_hip.h")).read()
-    assert "w2l_resize_row, 32 bytes, alignment 16" in text and "evaluation/real_videos_inference.py:51-70,239-245" in text
-    assert ctypes.sizeof(_lib.ResizeRow) == rv.RESIZE_ROW.itemsize == 32
-    for field, off in (("src", 0), ("dst", 8), ("Hs", 16), ("Ws", 20), ("Hd", 24), ("Wd", 28)):
-        assert getattr(_lib.ResizeRow, field).offset == rv.RESIZE_ROW.fields[field][1] == off, field
-    assert "w2l_resize_rows_u8" in _lib.SIGNATURES
 
 
 # ---------------------------------------------------------------- the producer, device steps stubbed
@@ -290,12 +279,12 @@ def test_jobs_are_produced_lazily(seams, tmp_path):
 
 
 def test_a_device_tensor_job_stages_no_frame_bytes():
-    from wav2lip_amd import multiclip
+    from wav2lip_amd import multiclip, staging
     mel = types.SimpleNamespace(shape=(80, 100))
     host = np.zeros((4, 12, 10, 3), np.uint8)
     resident = torch.zeros((4, 12, 10, 3), dtype=torch.uint8)
     rows = [(0, (1, 9, 2, 8), 0), (0, (1, 9, 2, 8), 3), (3, (1, 9, 2, 8), 6)]          # frame 0 twice
-    tables = multiclip._align(3 * multiclip.FRAME_ROW.itemsize) + multiclip._align(3 * multiclip.MEL_ROW.itemsize)
+    tables = staging.align(3 * multiclip.FRAME_ROW.itemsize) + staging.align(3 * multiclip.MEL_ROW.itemsize)
     for frames, staged in ((host, 2), (resident, 0)):
         job = multiclip.ClipJob("k", frames, mel, rows)
         checked = multiclip._checked_rows(job)

@@ -152,14 +152,6 @@ def test_lse_many_streams_results_to_a_sink_and_refuses_bad_jobs(monkeypatch):
         evaluation.lse_many(net, [], vshift=128)
 
 
-def test_row_and_segment_mirrors_have_the_sizes_of_the_header():
-    from wav2lip_amd import _lib, evaluation
-    assert evaluation.SYNC_ROW.itemsize == ctypes.sizeof(_lib.SyncRow) == 32
-    assert evaluation.LSE_SEGMENT.itemsize == ctypes.sizeof(_lib.LseSegment) == 8
-    assert [evaluation.SYNC_ROW.fields[n][1] for n in ("frames", "mel", "T", "start", "pad")] == [0, 8, 16, 20, 24]
-    assert [getattr(_lib.SyncRow, n).offset for n in ("frames", "mel", "T", "start", "pad")] == [0, 8, 16, 20, 24]
-
-
 def test_parser_has_the_reference_flags_and_defaults():
     """calculate_scores_LRS.py:14-21; --checkpoint_path in place of --initial_model"""
     from wav2lip_amd import calculate_scores as cs

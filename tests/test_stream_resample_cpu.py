@@ -1,16 +1,11 @@
 """Host side of streaming at a source rate of its own (wav2lip_amd/streaming.py: ResampleState, advance_samples) with the device
 stubbed at the seams `DeviceResampler`, `DeviceMel` and `BatchRunner`: which 16 kHz samples are final (against
-oracle/resample_ref.py), the time registers across any cut, coverage of every launch, the rows of any cut, the lengths, the
-struct mirrors, and the errors of `open` / `feed` / `close`."""
-import ctypes
-import os
-import re
-
+oracle/resample_ref.py), the time registers across any cut, coverage of every launch, the rows of any cut, the lengths, and the
+errors of `open` / `feed` / `close`."""
 import numpy as np
 import pytest
 
 import _stream_resample_cases as sc
-from conftest import ROOT
 from oracle import resample_ref
 from test_streaming_cpu import StubRunner, _frames
 
@@ -182,26 +177,6 @@ def test_lengths_are_librosas(stub):
     st.end_audio()
     res = stub.DeviceResampler(None)
     assert stub.advance_samples(res, [st]) and st.rs.n16 == 835 and st.mel_closed() and st.target() == 1 + 835 // 200
-
-
-def test_table_struct_mirrors_have_the_layout_the_header_states():
-    from wav2lip_amd import _lib, streaming
-    text = open(os.path.join(ROOT, "include", "w2l_hip.h")).read()
-    pairs = (("w2l_resample_stream_entry", 128, _lib.ResampleStreamEntry, streaming.RESAMPLE_STREAM),
-             ("w2l_resample_block", 32, _lib.ResampleBlock, streaming.RESAMPLE_BLOCKS))
-    for name, size, ct, dt in pairs:
-        m = re.search(r"%s, (\d+) bytes, alignment 16:\n((?: \*   at .*\n)+)" % name, text)
-        assert m and int(m.group(1)) == size == ctypes.sizeof(ct) == dt.itemsize and size % 16 == 0, name
-        stated = [(f, int(off), kind) for off, kind, f in re.findall(r"at +(\d+) +(u?int\d+|float64) +(\w+)", m.group(2))]
-        assert [f for f, _, _ in stated] == list(dt.names) == [f for f, _ in ct._fields_], name
-        for f, off, kind in stated:
-            assert getattr(ct, f).offset == dt.fields[f][1] == off, (name, f)
-            base = dt.fields[f][0].base
-            assert {"uint64": "<u8", "int64": "<i8", "int32": "<i4", "float64": "<f8"}[kind] == base.str, (name, f)
-        declared = re.search(r"typedef struct \{([^}]*)\} %s;" % name, text).group(1)
-        assert re.findall(r"(\w+)(?:\[\d+\])?[,;]", declared) == list(dt.names), name
-    assert _lib.SIGNATURES["w2l_resample_stream"][1] == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                                         ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
 
 
 def test_open_feed_and_close_errors(stub):

@@ -1,15 +1,8 @@
 """Host side of streaming lip-sync (wav2lip_amd/streaming.py) with the device stubbed at the two seams `BatchRunner` and
 `DeviceMel`: which columns are final, when a row is ready, that the rows of any feed split are `multiclip.rows_inference` of the
-whole audio, what a ragged batch is padded to, the spectrogram window filling and continuing, and the Python mirrors of the two
-table structs."""
-import ctypes
-import os
-import re
-
+whole audio, what a ragged batch is padded to, and the spectrogram window filling and continuing."""
 import numpy as np
 import pytest
-
-from conftest import ROOT
 
 
 def _reads(col, total=-1):
@@ -290,21 +283,6 @@ def test_close_fails_the_way_lipsync_fails_on_audio_that_is_too_short(stub):
     ls.open("dup", _frames(1), box)
     with pytest.raises(ValueError, match="already open"):
         ls.open("dup", _frames(1), box)
-
-
-def test_table_struct_mirrors_have_the_layout_the_header_states():
-    from wav2lip_amd import _lib, streaming
-    text = open(os.path.join(ROOT, "include", "w2l_hip.h")).read()
-    stated = {name: int(size) for name, size in re.findall(r"(w2l_mel_stream|w2l_mel_col), (\d+) bytes, alignment 16", text)}
-    assert stated == {"w2l_mel_stream": 48, "w2l_mel_col": 16}
-    offsets = {m[1]: int(m[0]) for m in re.findall(r"offset +(\d+) +u?int\d+ +(\w+)", text)}
-    assert ctypes.sizeof(_lib.MelStream) == streaming.MEL_STREAM.itemsize == 48
-    assert ctypes.sizeof(_lib.MelCol) == streaming.MEL_COL.itemsize == 16
-    for f in ("samples", "first", "total", "window", "held", "cap", "col0"):
-        assert getattr(_lib.MelStream, f).offset == streaming.MEL_STREAM.fields[f][1] == offsets[f], f
-    for f in ("stream", "rsv", "col"):
-        assert getattr(_lib.MelCol, f).offset == streaming.MEL_COL.fields[f][1] == offsets[f], f
-    assert "w2l_mel_stream_cols" in _lib.SIGNATURES
 
 
 def test_cli_surface():

@@ -2,15 +2,12 @@
 `face_detect` against `many.host_boxes` of the whole video for EVERY cut of it into ticks, and `LipsyncStreams` with the device
 stubbed at its three seams (`BatchRunner`, `DeviceMel`, `DeviceBoxes`): the rows of any interleaving of `feed` and `feed_frames`
 are `multiclip.rows_inference` of the whole inputs, no row runs before its frame's box is final, one box launch per tick, a frame
-without a face ends its stream only, the argument errors, the command line and the struct mirrors."""
+without a face ends its stream only, the argument errors and the command line."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
 from test_streaming_cpu import StubMel, StubRunner, _audio
 
 FH, FW = 40, 50
@@ -343,20 +340,6 @@ def test_cli_surface():
     argv = ["--checkpoint_path", "c", "--face", "f0", "--audio", "a0"]
     assert streaming.build_parser().parse_args(argv).live_video is False
     assert streaming.build_parser().parse_args(argv + ["--live_video"]).live_video is True
-
-
-def test_struct_mirrors_have_the_layout_the_header_states():
-    from wav2lip_amd import _lib
-    from wav2lip_amd.face_detection import live, many
-    text = open(os.path.join(ROOT, "include", "w2l_hip.h")).read()
-    assert re.search(r"w2l_box_stream_segment, 32 bytes, the table 16-byte aligned", text)
-    stated = re.search(r"typedef struct \{\s*int32_t ([\w, ]+);\s*\} w2l_box_stream_segment;", text).group(1).split(", ")
-    assert stated == ["row0", "n_new", "H", "W", "slot", "seen", "closed", "out0"] == list(live.BOX_STREAM_SEGMENT.names)
-    assert live.BOX_STREAM_SEGMENT.itemsize == ctypes.sizeof(_lib.BoxStreamSegment) == 32
-    for k, name in enumerate(stated):
-        assert live.BOX_STREAM_SEGMENT.fields[name][1] == getattr(_lib.BoxStreamSegment, name).offset == 4 * k
-    assert live.CARRY_ROWS == many.MAX_T == 64
-    assert "w2l_face_boxes_stream" in _lib.SIGNATURES and len(_lib.SIGNATURES["w2l_face_boxes_stream"][1]) == 17
 
 
 def _bf16_backbone_launches(N, H, W):

@@ -6,6 +6,8 @@ There is no fallback: if the shared library is missing or a call fails, a Runtim
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # W2L_HIP_LIB selects an alternative build of the same ABI (kernel A/B experiments); default = the in-tree build
 LIB_PATH = os.environ.get("W2L_HIP_LIB") or os.path.join(_HERE, "lib", "libw2l_hip.so")
@@ -35,16 +37,25 @@ class WgradBf16Info(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("ni", "bh", "bw", "nboxes", "splits", "boxes_per_split", "ntg", "tg", "ncq", "mt", "qp")]
 
 
+# The table structs of the packed paths.  The typedef in include/w2l_hip.h is the authority, the class here mirrors it
+# (tests/test_struct_mirrors_cpu.py holds every pair together), and the numpy dtype the modules fill their tables through is
+# derived from the class, so a layout is typed once on this side.
 class FrameRow(C.Structure):
     """w2l_frame_row (include/w2l_hip.h): one face row of the row-table kernels, 48 bytes"""
     _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("H", C.c_int32), ("W", C.c_int32), ("y1", C.c_int32),
                 ("y2", C.c_int32), ("x1", C.c_int32), ("x2", C.c_int32), ("pad", C.c_int32 * 2)]
 
 
+FRAME_ROW = np.dtype(FrameRow)
+
+
 class ResizeRow(C.Structure):
     """w2l_resize_row: one frame of the whole-frame row-table resize, 32 bytes"""
     _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("Hs", C.c_int32), ("Ws", C.c_int32), ("Hd", C.c_int32),
                 ("Wd", C.c_int32)]
+
+
+RESIZE_ROW = np.dtype(ResizeRow)
 
 
 class JpegInfo(C.Structure):
@@ -54,9 +65,29 @@ class JpegInfo(C.Structure):
                 ("vals", (C.c_uint8 * 256) * 4)]
 
 
+class JpegRow(C.Structure):
+    """w2l_jpeg_row: one file of w2l_jpeg_decode_rows, 32 bytes"""
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("nbytes", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("table", C.c_int32)]
+
+
+JPEG_ROW = np.dtype(JpegRow)
+
+
+class JpegSegment(C.Structure):
+    """w2l_jpeg_segment: one restart interval of w2l_jpeg_decode_rows_rst, 32 bytes"""
+    _fields_ = [(n, C.c_int32) for n in ("row", "offset", "nbytes", "first_mcu", "n_mcus")] + [("pad", C.c_int32 * 3)]
+
+
+JPEG_SEGMENT = np.dtype(JpegSegment)
+
+
 class MelRow(C.Structure):
     """w2l_mel_row: one mel window of the row-table gather, 16 bytes"""
     _fields_ = [("mel", C.c_uint64), ("T", C.c_int32), ("start", C.c_int32)]
+
+
+MEL_ROW = np.dtype(MelRow)
 
 
 class SyncRow(C.Structure):
@@ -64,9 +95,15 @@ class SyncRow(C.Structure):
     _fields_ = [("frames", C.c_uint64), ("mel", C.c_uint64), ("T", C.c_int32), ("start", C.c_int32), ("pad", C.c_int32 * 2)]
 
 
+SYNC_ROW = np.dtype(SyncRow)
+
+
 class LseSegment(C.Structure):
     """w2l_lse_segment: one clip's rows of w2l_lse_score_segments, 8 bytes"""
     _fields_ = [("row0", C.c_int32), ("n", C.c_int32)]
+
+
+LSE_SEGMENT = np.dtype(LseSegment)
 
 
 class BoxSegment(C.Structure):
@@ -74,9 +111,15 @@ class BoxSegment(C.Structure):
     _fields_ = [("row0", C.c_int32), ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
 
 
+BOX_SEGMENT = np.dtype(BoxSegment)
+
+
 class BoxStreamSegment(C.Structure):
     """w2l_box_stream_segment: one live stream's rows of a tick of w2l_face_boxes_stream, 32 bytes"""
     _fields_ = [(n, C.c_int32) for n in ("row0", "n_new", "H", "W", "slot", "seen", "closed", "out0")]
+
+
+BOX_STREAM_SEGMENT = np.dtype(BoxStreamSegment)
 
 
 class MelStream(C.Structure):
@@ -85,9 +128,15 @@ class MelStream(C.Structure):
                 ("cap", C.c_int32), ("col0", C.c_int64)]
 
 
+MEL_STREAM = np.dtype(MelStream)
+
+
 class MelCol(C.Structure):
     """w2l_mel_col: one (stream, column) entry of w2l_mel_stream_cols, 16 bytes"""
     _fields_ = [("stream", C.c_int32), ("rsv", C.c_int32), ("col", C.c_int64)]
+
+
+MEL_COL = np.dtype(MelCol)
 
 
 class ResampleStreamEntry(C.Structure):
@@ -98,10 +147,16 @@ class ResampleStreamEntry(C.Structure):
                 ("nwin", C.c_int32), ("carry_held", C.c_int32), ("unused", C.c_int32 * 3)]
 
 
+RESAMPLE_STREAM = np.dtype(ResampleStreamEntry)
+
+
 class ResampleBlock(C.Structure):
     """w2l_resample_block: up to 128 consecutive outputs of one stream of w2l_resample_stream, 32 bytes"""
     _fields_ = [("stream", C.c_int32), ("count", C.c_int32), ("t0", C.c_int64), ("tr0", C.c_double), ("copy", C.c_int32),
                 ("unused", C.c_int32)]
+
+
+RESAMPLE_BLOCKS = np.dtype(ResampleBlock)
 
 
 WGRAD_WINO, WGRAD_DIRECT, WGRAD_SMALL = 0, 1, 2

@@ -14,23 +14,22 @@ With identical weights on both sides, equal scores for the engine's frames and t
 "LSE-D / LSE-C parity"; the absolute values are not comparable to the paper's (different scorer network).
 
 `lse_like` scores one clip per call.  `lse_many` scores a whole filelist (evaluation/scores_LSE/calculate_scores_LRS.py:28-50): the
-windows of successive clips are rows of SyncNet batches of one size, and a group of clips is scored in one launch.
+windows of successive clips are rows of SyncNet batches of one size, and a group of clips is scored in one launch (DESIGN.md 3l);
+the group's tables and host faces go up in one staging buffer (staging.py).
 """
 import collections
 
 import numpy as np
 import torch
 
-from ._lib import check, current_stream, load, ptr
+from ._lib import LSE_SEGMENT, SYNC_ROW, check, current_stream, load, ptr
 from .inference import _precision_kw
+from .staging import Staging
 
 syncnet_T = 5
 mel_step = 16
 img_size = 96
 
-# numpy mirrors of w2l_sync_row (32 bytes) and w2l_lse_segment (8 bytes); the ctypes mirrors are _lib.SyncRow / _lib.LseSegment
-SYNC_ROW = np.dtype([("frames", "<u8"), ("mel", "<u8"), ("T", "<i4"), ("start", "<i4"), ("pad", "<i4", (2,))])
-LSE_SEGMENT = np.dtype([("row0", "<i4"), ("n", "<i4")])
 GROUP_BATCHES = 16   # lse_many closes a group of clips once it holds this many full batches of windows
 
 ScoreJob = collections.namedtuple("ScoreJob", "key faces mel")
@@ -104,10 +103,6 @@ def sync_rows(T, Tm, fps=25.):
     return rows
 
 
-def _align(n):
-    return (n + 15) // 16 * 16
-
-
 def _score_segments(n_seg, segs, vshift, face_emb, audio_emb, out):
     """w2l_lse_score_segments into `out`, fp32 [n_seg * (4 + win)]: the [n_seg][4] scores, then the [n_seg][win] mean distances"""
     check(load().w2l_lse_score_segments(current_stream(), n_seg, ptr(segs), face_emb.shape[1], vshift, ptr(face_emb),
@@ -124,45 +119,31 @@ def _score_group(syncnet, clips, vshift, batch_size, precision="f32"):
     W = sum(len(rows) for _, _, rows in clips)
     padded = (W + batch_size - 1) // batch_size * batch_size
     # ---- one staging buffer: [window table, `padded` rows][segment table][host faces of the group]
-    seg_off = _align(padded * SYNC_ROW.itemsize)
-    off = _align(seg_off + len(clips) * LSE_SEGMENT.itemsize)
-    face_off = []
-    for faces, _, _ in clips:
-        if isinstance(faces, torch.Tensor):
-            face_off.append(None)
-        else:
-            face_off.append(off)
-            off = _align(off + faces.nbytes)
-    pinned = dev.type == "cuda"
-    host = torch.empty(off, dtype=torch.uint8, pin_memory=pinned)
-    stage_dev = torch.empty(off, dtype=torch.uint8, device=dev)
-    stage = host.numpy()
-    table = stage[:padded * SYNC_ROW.itemsize].view(SYNC_ROW)
-    segs = stage[seg_off:seg_off + len(clips) * LSE_SEGMENT.itemsize].view(LSE_SEGMENT)
+    st = Staging(dev)
+    window_rows, segments = st.table(SYNC_ROW, padded), st.table(LSE_SEGMENT, len(clips))
+    src = [st.place(faces) for faces, _, _ in clips]
+    st.allocate()
+    table, segs = st.view(window_rows), st.view(segments)
     table["pad"] = 0
     frame_bytes = img_size * img_size * 3
     r = 0
-    for c, (faces, mel, rows) in enumerate(clips):
-        if face_off[c] is None:
-            base = faces.data_ptr()
-        else:
-            stage[face_off[c]:face_off[c] + faces.nbytes] = faces.reshape(-1)
-            base = stage_dev.data_ptr() + face_off[c]
+    for c, (_, mel, rows) in enumerate(clips):
         vs = np.asarray(rows, dtype=np.int64)
         t = table[r:r + len(rows)]
-        t["frames"] = base + vs[:, 0] * frame_bytes
+        t["frames"] = st.address(src[c]) + vs[:, 0] * frame_bytes
         t["mel"], t["T"], t["start"] = mel.data_ptr(), mel.shape[1], vs[:, 1]
         segs[c] = (r, len(rows))
         r += len(rows)
     table[W:] = table[W - 1]
-    stage_dev.copy_(host, non_blocking=pinned)
+    st.upload()
     audio_emb = torch.empty((padded, 512), dtype=torch.float32, device=dev)     # rows [W, padded): the scratch tail
     face_emb = torch.empty((padded, 512), dtype=torch.float32, device=dev)
+    rows_dev = st.tensor(window_rows)
     for lo in range(0, padded, batch_size):
-        syncnet.embed_rows(stage_dev[lo * SYNC_ROW.itemsize:(lo + batch_size) * SYNC_ROW.itemsize], batch_size, audio_emb, face_emb, lo,
+        syncnet.embed_rows(rows_dev[lo * SYNC_ROW.itemsize:(lo + batch_size) * SYNC_ROW.itemsize], batch_size, audio_emb, face_emb, lo,
                            **_precision_kw(precision))
     out = torch.empty(len(clips) * (4 + win), dtype=torch.float32, device=dev)
-    _score_segments(len(clips), stage_dev[seg_off:seg_off + len(clips) * LSE_SEGMENT.itemsize], vshift, face_emb, audio_emb, out)
+    _score_segments(len(clips), st.tensor(segments), vshift, face_emb, audio_emb, out)
     res = out.cpu().numpy()                      # the group's one copy back; it also ends the stream's use of the staging buffers
     return np.concatenate([res[:4 * len(clips)].reshape(len(clips), 4), res[4 * len(clips):].reshape(len(clips), win)], axis=1)
 

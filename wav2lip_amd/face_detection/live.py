@@ -10,9 +10,8 @@ on the finished video however the video was cut into ticks.
 """
 import numpy as np
 
-# numpy mirror of w2l_box_stream_segment (32 bytes); the ctypes mirror is _lib.BoxStreamSegment
-BOX_STREAM_SEGMENT = np.dtype([("row0", "<i4"), ("n_new", "<i4"), ("H", "<i4"), ("W", "<i4"), ("slot", "<i4"), ("seen", "<i4"),
-                               ("closed", "<i4"), ("out0", "<i4")])
+from .._lib import BOX_STREAM_SEGMENT  # noqa: F401  -- the tick's segment table, filled by streaming.DeviceBoxes
+
 CARRY_ROWS = 64      # rows of a carry slot = w2l_face_boxes_stream's largest smoothing window (many.MAX_T)
 
 

@@ -7,6 +7,7 @@ detector batches of ONE size:
 
     per group of clips of one frame shape
         one pinned staging buffer  [frame address table][segment table][the frames that were host arrays]  -> one copy to the device
+                                   (laid out by wav2lip_amd/staging.py)
         batches of exactly `batch_size` addresses   w2l_s3fd_pack_rows -> S3FD -> gate + NMS -> w2l_s3fd_first_rect
                                                     (rects and flags land in the rows of the group's arenas; no host read)
         one launch                                  w2l_face_boxes_segments: pads, clipping, smoothing, "no face" per clip
@@ -20,8 +21,9 @@ import collections
 import numpy as np
 import torch
 
-# numpy mirror of w2l_box_segment (16 bytes); the ctypes mirror is _lib.BoxSegment
-BOX_SEGMENT = np.dtype([("row0", "<i4"), ("n", "<i4"), ("H", "<i4"), ("W", "<i4")])
+from .._lib import BOX_SEGMENT
+from ..staging import ADDRESS, Staging
+
 MAX_T = 64           # w2l_face_boxes_segments' largest smoothing window
 NO_FACE = 'Face not detected! Ensure the video contains a face in all the frames.'      # inference.py:89
 
@@ -30,10 +32,6 @@ DetectJob.__doc__ = """one clip to detect faces in: `frames` a sequence of uint8
 tensor [T,H,W,3] (read where it lies)"""
 
 _Clip = collections.namedtuple("_Clip", "key frames n H W nbytes")
-
-
-def _align(n):
-    return (n + 15) // 16 * 16
 
 
 def host_boxes(rects, H, W, pads, T):
@@ -93,43 +91,26 @@ def _detect_group(detector, clips, pads, T, batch_size):
     R = sum(c.n for c in clips)
     padded = (R + batch_size - 1) // batch_size * batch_size
     # ---- one staging buffer: [address table, `padded` entries][segment table][host frames of the group]
-    seg_off = _align(padded * 8)
-    off = _align(seg_off + len(clips) * BOX_SEGMENT.itemsize)
-    frame_off = []
-    for c in clips:
-        if isinstance(c.frames, torch.Tensor):
-            frame_off.append(None)
-        else:
-            frame_off.append(off)
-            off = _align(off + c.nbytes)
-    pinned = dev.type == "cuda"
-    host = torch.empty(off, dtype=torch.uint8, pin_memory=pinned)
-    stage_dev = torch.empty(off, dtype=torch.uint8, device=dev)
-    stage = host.numpy()
-    addr = stage[:padded * 8].view("<u8")
-    segs = stage[seg_off:seg_off + len(clips) * BOX_SEGMENT.itemsize].view(BOX_SEGMENT)
+    st = Staging(dev)
+    addresses, segments = st.table(ADDRESS, padded), st.table(BOX_SEGMENT, len(clips))
+    src = [st.place(c.frames) for c in clips]
+    st.allocate()
+    addr, segs = st.view(addresses), st.view(segments)
     frame_bytes = H * W * 3
     r = 0
     for k, c in enumerate(clips):
-        if frame_off[k] is None:
-            base = c.frames.data_ptr()
-        else:
-            dst = stage[frame_off[k]:frame_off[k] + c.nbytes].reshape(c.n, H, W, 3)
-            for i, f in enumerate(c.frames):
-                dst[i] = f
-            base = stage_dev.data_ptr() + frame_off[k]
-        addr[r:r + c.n] = np.uint64(base) + np.arange(c.n, dtype=np.uint64) * np.uint64(frame_bytes)
+        addr[r:r + c.n] = np.uint64(st.address(src[k])) + np.arange(c.n, dtype=np.uint64) * np.uint64(frame_bytes)
         segs[k] = (r, c.n, H, W)
         r += c.n
     addr[R:] = addr[R - 1]
-    stage_dev.copy_(host, non_blocking=pinned)
+    st.upload()
     rects = torch.empty((padded, 4), dtype=torch.int32, device=dev)            # rows [R, padded): the scratch tail
     flags = torch.empty((padded,), dtype=torch.int32, device=dev)
+    addr_dev = st.tensor(addresses)
     for lo in range(0, padded, batch_size):
-        _detect_batch(detector, stage_dev[lo * 8:(lo + batch_size) * 8], batch_size, H, W, rects, flags, lo)
+        _detect_batch(detector, addr_dev[lo * 8:(lo + batch_size) * 8], batch_size, H, W, rects, flags, lo)
     out = torch.empty(4 * R + 2 * len(clips), dtype=torch.int32, device=dev)    # boxes [R][4], then status [clips][2]: one copy back
-    _finish_segments(len(clips), stage_dev[seg_off:seg_off + len(clips) * BOX_SEGMENT.itemsize], rects, flags, pads, T, out[:4 * R],
-                     out[4 * R:])
+    _finish_segments(len(clips), st.tensor(segments), rects, flags, pads, T, out[:4 * R], out[4 * R:])
     res = out.cpu().numpy()                      # the group's one copy back; it also ends the stream's use of the staging buffers
     return res[:4 * R].reshape(R, 4), res[4 * R:].reshape(len(clips), 2)
 

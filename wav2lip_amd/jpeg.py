@@ -6,8 +6,8 @@ Huffman tables): baseline JPEG is integer arithmetic end to end.
     encode_crops(frames, boxes, quality=95)      -> list[bytes], one complete JFIF file per box
     CropEncoder(...).submit(frames, boxes, paths); .collect(); .finish()     the asynchronous form `preprocess --jpeg device` uses
 
-Per batch: the row table (w2l_frame_row) and the slots' capacities are staged in ONE pinned buffer and copied in once, two kernels
-run whatever the batch size is (on the current stream; CropEncoder's worker thread has a stream of its own), and two copies come
+Per batch: the row table (w2l_frame_row) and the slots' capacities are staged in ONE pinned buffer (staging.py) and copied in once,
+two kernels run whatever the batch size is (on the current stream; CropEncoder's worker thread has a stream of its own), and two copies come
 back: the lengths, then the used part of the slots.  There is no host fallback: a CPU tensor or a missing library raises
 RuntimeError.
 
@@ -35,6 +35,8 @@ from concurrent.futures import ThreadPoolExecutor, wait
 import numpy as np
 
 from . import _lib
+from ._lib import FRAME_ROW, JPEG_ROW, JPEG_SEGMENT
+from .staging import Staging, align
 
 HEADER_BYTES = 623                # SOI .. SOS; height at offset 163, width at 165 (big-endian 16-bit each)
 HEADER_BYTES_RST = 629            # with DRI (FF DD 00 04 Ri) at offset 609, between the last DHT and SOS
@@ -95,7 +97,6 @@ class _Plan:
     """a validated batch: the row table and the capacities as host arrays, made without touching the device"""
 
     def __init__(self, frames, boxes, quality, frame_index, restart_rows=None):
-        from .multiclip import FRAME_ROW
         fl = _frame_list(frames)
         if boxes is None:                                  # whole frames
             boxes = [(0, 0, f[3], f[2]) for f in fl]
@@ -124,12 +125,12 @@ class _Plan:
         if self.max_blocks > MAX_BLOCKS:
             raise ValueError("jpeg: a crop of %d blocks (at most %d)" % (self.max_blocks, MAX_BLOCKS))
         # every slot holds the largest crop's bound, so that the used part of all slots comes back as one strided copy
-        self.stride = -(-(HEADER_BYTES + 2 + MAX_BLOCK_BYTES * self.max_blocks) // 16) * 16
+        self.stride = align(HEADER_BYTES + 2 + MAX_BLOCK_BYTES * self.max_blocks)
         self.restart_rows = None if restart_rows is None else int(restart_rows)
         if self.restart_rows is not None:                  # capacity_rst of the largest crop: DRI and 4 bytes per interval on top
             mw, mh = -(-(x2 - x1) // 16), -(-(y2 - y1) // 16)
             ri = np.minimum(self.restart_rows * mw, 65535)
-            self.stride = -(-int((HEADER_BYTES_RST + 2 + MAX_BLOCK_BYTES * 6 * mw * mh + 4 * (-(-(mw * mh) // ri))).max()) // 16) * 16
+            self.stride = align(int((HEADER_BYTES_RST + 2 + MAX_BLOCK_BYTES * 6 * mw * mh + 4 * (-(-(mw * mh) // ri))).max()))
         self.table = np.zeros(n, FRAME_ROW)
         self.table["src"] = np.asarray([f[1] for f in fl], dtype=np.uint64)[idx]
         self.table["H"], self.table["W"] = H, W
@@ -142,25 +143,26 @@ class _Plan:
         import torch
         lib = _lib.load()
         n, stride = self.n, self.stride
-        nb = -(-self.table.nbytes // 16) * 16
         with torch.cuda.device(self.device):
             out = torch.empty(n * stride, dtype=torch.uint8, device=self.device)
-            host = torch.empty(nb + 4 * n, dtype=torch.uint8, pin_memory=True)          # the table, then cap[n]
-            self.table["dst"] = out.data_ptr() + np.arange(n, dtype=np.int64) * stride
-            host.numpy()[:self.table.nbytes] = self.table.view(np.uint8)
-            host.numpy()[nb:].view(np.int32)[:] = stride
-            staged = host.to(self.device, non_blocking=True)                             # one copy in
+            st = Staging(self.device)
+            rows, cap = st.table(FRAME_ROW, n), st.reserve(4 * n, dtype=np.int32)         # the table, then cap[n]
+            st.allocate()
+            st.view(rows)[:] = self.table
+            st.view(rows)["dst"] = out.data_ptr() + np.arange(n, dtype=np.int64) * stride
+            st.view(cap)[:] = stride
+            st.upload()                                                                  # one copy in
             lengths_dev = torch.empty(n, dtype=torch.int32, device=self.device)
             if self.restart_rows is None:
                 ws_bytes = int(lib.w2l_jpeg_workspace_bytes(n, self.max_blocks))
                 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-                _lib.check(lib.w2l_jpeg_encode_rows(_lib.current_stream(), n, _lib.ptr(staged), C.c_void_p(staged.data_ptr() + nb),
+                _lib.check(lib.w2l_jpeg_encode_rows(_lib.current_stream(), n, _lib.ptr(st.dev), C.c_void_p(st.address(cap)),
                                                     self.quality, self.max_blocks, _lib.ptr(lengths_dev), _lib.ptr(ws), ws_bytes),
                            "jpeg_encode_rows")
             else:
                 ws_bytes = int(lib.w2l_jpeg_workspace_bytes_rst(n, self.max_blocks))
                 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-                _lib.check(lib.w2l_jpeg_encode_rows_rst(_lib.current_stream(), n, _lib.ptr(staged), C.c_void_p(staged.data_ptr() + nb),
+                _lib.check(lib.w2l_jpeg_encode_rows_rst(_lib.current_stream(), n, _lib.ptr(st.dev), C.c_void_p(st.address(cap)),
                                                         self.quality, self.max_blocks, self.restart_rows, _lib.ptr(lengths_dev),
                                                         _lib.ptr(ws), ws_bytes), "jpeg_encode_rows_rst")
             lengths = lengths_dev.cpu().numpy().astype(np.int64)                         # the first copy back (waits for the kernels)
@@ -312,7 +314,6 @@ class CropEncoder:
 
 
 # ---------------------------------------------------------------- decoding
-JPEG_ROW = np.dtype([("src", "<u8"), ("dst", "<u8"), ("nbytes", "<i4"), ("H", "<i4"), ("W", "<i4"), ("table", "<i4")])
 MALFORMED = -100                  # w2l_jpeg_parse: not a JPEG, or cut inside its header; the other reasons: outside the class
 STATUS_TEXT = {-1: "bits that are no code of the file's Huffman table", -2: "a zero run past coefficient 63",
                -3: "a marker or left-over bytes before the end of the last MCU", -4: "the stream ends early",
@@ -375,37 +376,38 @@ def _decode(datas, infos, device, segments=None):
     max_blocks = int(max(blocks(h, w) for h, w in zip(table["H"], table["W"])))
     if max_blocks > MAX_BLOCKS:
         raise ValueError("jpeg: a file of %d blocks (at most %d)" % (max_blocks, MAX_BLOCKS))
-    rows_b = -(-table.nbytes // 16) * 16
-    tabs_b = tb * len(sets)                                                     # a multiple of 16
-    segs_b = 0 if segments is None else segments.nbytes                         # 32 bytes each
-    src_off = rows_b + tabs_b + segs_b + np.concatenate([[0], np.cumsum(table["nbytes"].astype(np.int64))])
+    src_off = np.concatenate([[0], np.cumsum(table["nbytes"].astype(np.int64))])
     dst_off = np.concatenate([[0], np.cumsum(table["H"].astype(np.int64) * table["W"] * 3)])
     with torch.cuda.device(device):
-        staged = torch.empty(int(src_off[-1]), dtype=torch.uint8, device=device)
+        # ---- one staging buffer: [rows][table sets][segments][the files' entropy-coded segments, back to back]
+        st = Staging(device)
+        rows, tabs = st.table(JPEG_ROW, n), st.reserve(tb * len(sets))
+        segs = st.table(JPEG_SEGMENT, 0 if segments is None else len(segments))
+        ecs = st.reserve(int(src_off[-1]), boundary=1)
+        st.allocate()
         out = torch.empty(int(dst_off[-1]), dtype=torch.uint8, device=device)
-        host = torch.empty(int(src_off[-1]), dtype=torch.uint8, pin_memory=True)
-        table["src"] = staged.data_ptr() + src_off[:-1]
+        table["src"] = st.address(ecs) + src_off[:-1]
         table["dst"] = out.data_ptr() + dst_off[:-1]
-        h = host.numpy()
-        h[:table.nbytes] = table.view(np.uint8)
+        st.view(rows)[:] = table
+        tabs_host, ecs_host = st.view(tabs), st.view(ecs)
         for idx, blob in sets.values():
-            h[rows_b + idx * tb:rows_b + (idx + 1) * tb] = np.frombuffer(blob, np.uint8)
+            tabs_host[idx * tb:(idx + 1) * tb] = np.frombuffer(blob, np.uint8)
         for i, (d, info) in enumerate(zip(datas, infos)):
-            h[src_off[i]:src_off[i + 1]] = np.frombuffer(d, np.uint8, info.ecs_bytes, info.ecs_offset)
+            ecs_host[src_off[i]:src_off[i + 1]] = np.frombuffer(d, np.uint8, info.ecs_bytes, info.ecs_offset)
         if segments is not None:
-            h[rows_b + tabs_b:rows_b + tabs_b + segs_b] = segments.view(np.uint8)
-        staged.copy_(host, non_blocking=True)                                   # one copy in
+            st.view(segs)[:] = segments
+        st.upload()                                                             # one copy in
         status = torch.empty(n, dtype=torch.int32, device=device)
         if segments is None:
             ws_bytes = int(lib.w2l_jpeg_decode_workspace_bytes(n, max_blocks))
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-            _lib.check(lib.w2l_jpeg_decode_rows(_lib.current_stream(), n, _lib.ptr(staged), C.c_void_p(staged.data_ptr() + rows_b), len(sets),
+            _lib.check(lib.w2l_jpeg_decode_rows(_lib.current_stream(), n, _lib.ptr(st.dev), C.c_void_p(st.address(tabs)), len(sets),
                                                 max_blocks, _lib.ptr(status), _lib.ptr(ws), ws_bytes), "jpeg_decode_rows")
         else:
             ws_bytes = int(lib.w2l_jpeg_decode_workspace_bytes_rst(n, max_blocks))
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-            _lib.check(lib.w2l_jpeg_decode_rows_rst(_lib.current_stream(), n, _lib.ptr(staged), C.c_void_p(staged.data_ptr() + rows_b),
-                                                    len(sets), max_blocks, C.c_void_p(staged.data_ptr() + rows_b + tabs_b), len(segments),
+            _lib.check(lib.w2l_jpeg_decode_rows_rst(_lib.current_stream(), n, _lib.ptr(st.dev), C.c_void_p(st.address(tabs)),
+                                                    len(sets), max_blocks, C.c_void_p(st.address(segs)), len(segments),
                                                     _lib.ptr(status), _lib.ptr(ws), ws_bytes), "jpeg_decode_rows_rst")
         st = status.cpu().numpy()                                               # one copy back (waits for the kernels)
     imgs = [out[int(dst_off[i]):int(dst_off[i + 1])].view(int(table["H"][i]), int(table["W"][i]), 3) for i in range(n)]
@@ -437,10 +439,6 @@ def decode_files(datas, device):
 
 
 # ---------------------------------------------------------------- Motion-JPEG frames: files with restart intervals
-JPEG_SEGMENT = np.dtype([("row", "<i4"), ("offset", "<i4"), ("nbytes", "<i4"), ("first_mcu", "<i4"), ("n_mcus", "<i4"),
-                         ("pad", "<i4", (3,))])
-
-
 class CorruptJpeg(ValueError):
     """a frame of `decode_frames` that is cut, whose restart markers are wrong or whose stream the kernel refuses; `.index` is its
     position in the call's list"""

@@ -8,7 +8,8 @@ per lane whatever the clip lengths, every batch but the last runs the committed 
 `LIPSYNC_DEPTH` batches are in flight from the first clip to the last.
 
 Per batch (`BatchRunner.submit`): the (clip, frame) pairs the batch touches are deduplicated and staged in ONE pinned buffer
-together with the two row tables (w2l_frame_row / w2l_mel_row, include/w2l_hip.h), copied to the device once, then on the lane's
+(staging.py lays it out) together with the two row tables (w2l_frame_row / w2l_mel_row, include/w2l_hip.h), copied to the device
+once, then on the lane's
 stream  w2l_crop_resize_rows_u8 -> w2l_datagen_pack -> w2l_mel_gather_rows -> the plan -> w2l_frames_to_u8 (fp32 only) ->
 w2l_compose_rows_u8,  and the composed frames come back in one copy.  Frames of different clips may have different shapes.
 
@@ -23,13 +24,9 @@ import collections
 
 import numpy as np
 
+from ._lib import FRAME_ROW, MEL_ROW
 from .inference import LIPSYNC_DEPTH, mel_chunk_starts, mel_step_size, validate_boxes
-
-# numpy mirrors of w2l_frame_row (48 bytes) and w2l_mel_row (16 bytes); the ctypes mirrors are _lib.FrameRow / _lib.MelRow
-FRAME_ROW = np.dtype([("src", "<u8"), ("dst", "<u8"), ("H", "<i4"), ("W", "<i4"), ("y1", "<i4"), ("y2", "<i4"), ("x1", "<i4"),
-                      ("x2", "<i4"), ("pad", "<i4", (2,))])
-MEL_ROW = np.dtype([("mel", "<u8"), ("T", "<i4"), ("start", "<i4")])
-_ALIGN = 16          # every staged frame and both tables start on a 16-byte boundary
+from .staging import Staging, align
 
 ClipJob = collections.namedtuple("ClipJob", "key frames mel rows")
 ClipJob.__doc__ = """one clip: `frames` uint8 [H,W,3] BGR frames (one shape per clip; a list or an [F,H,W,3] array, or a contiguous uint8
@@ -78,12 +75,9 @@ class _Job:
         self.frames = self.mel = None
 
 
-def _align(n):
-    return (n + _ALIGN - 1) // _ALIGN * _ALIGN
-
-
 def _resident(frames):
-    """True for a frame tensor (torch, [F,H,W,3]): its frames are addressed where they lie, never staged"""
+    """True for a frame tensor (torch, [F,H,W,3]) rather than a sequence of host frames: what its shape and its checks go by
+    (whether anything of it is staged is `Staging.place`'s question)"""
     return hasattr(frames, "data_ptr")
 
 
@@ -99,26 +93,34 @@ def _frame_bytes(job, fi):
     return np.asarray(job.frames[fi]).nbytes
 
 
-def staging_layout(rows, n):
-    """where everything of a batch of `rows` launched as n >= len(rows) rows lies: (bytes of the staging buffer, offset of the
-    mel-row table, {(id(job), frame): offset of a staged host frame}, [(offset, host frame)], [output offset per row], output
-    bytes).  The staging buffer is [frame-row table][mel-row table][deduplicated host frames]; frames of a device-resident job are
-    not in it.  Outputs have a buffer of their own."""
-    off = _align(n * FRAME_ROW.itemsize)
-    mel_off = off
-    off = _align(off + n * MEL_ROW.itemsize)
-    src_off, frames = {}, []
+def _reserve(st, rows, n):
+    """a batch of `rows` launched as n >= len(rows) rows, reserved in the Staging `st`: [frame-row table][mel-row table]
+    [deduplicated host frames]; frames of a device-resident job are not in it.  Returns the handles (frame-row table, mel-row table,
+    {(id(job), frame): the row's source frame})"""
+    ft, mt, src = st.table(FRAME_ROW, n), st.table(MEL_ROW, n), {}
     for job, fi, _, _ in rows:
-        if not _resident(job.frames) and (id(job), fi) not in src_off:
-            f = np.asarray(job.frames[fi])
-            src_off[(id(job), fi)] = off
-            frames.append((off, f))
-            off = _align(off + f.nbytes)
+        if (id(job), fi) not in src:
+            src[(id(job), fi)] = st.place(job.frames, fi)
+    return ft, mt, src
+
+
+def _output_layout(rows):
+    """([output offset per row], output bytes): the outputs have a buffer of their own, every frame on a 16-byte boundary"""
     out_off, out_bytes = [], 0
     for job, fi, _, _ in rows:
         out_off.append(out_bytes)
-        out_bytes = _align(out_bytes + _frame_bytes(job, fi))
-    return off, mel_off, src_off, frames, out_off, out_bytes
+        out_bytes = align(out_bytes + _frame_bytes(job, fi))
+    return out_off, out_bytes
+
+
+def staging_layout(rows, n):
+    """where everything of a batch of `rows` launched as n >= len(rows) rows lies: (bytes of the staging buffer, offset of the
+    mel-row table, {(id(job), frame): offset of a staged host frame}, [(offset, host frame)], [output offset per row], output
+    bytes) - `_reserve` and `_output_layout`, nothing allocated"""
+    st = Staging("cpu")
+    _, mt, src = _reserve(st, rows, n)
+    src_off = {k: h.offset for k, h in src.items() if h.resident is None}
+    return (st.size, mt.offset, src_off, [(h.offset, f) for h, f in st.placed]) + _output_layout(rows)
 
 
 class BatchRunner:
@@ -141,28 +143,21 @@ class BatchRunner:
         torch = self.torch
         real = len(rows)
         n = max(real, pad_to or 0)
-        off, mel_off, src_off, frames, out_off, out_bytes = staging_layout(rows, n)
-        host = torch.empty(off, dtype=torch.uint8, pin_memory=True)
-        dev = torch.empty(off, dtype=torch.uint8, device=self.device)
+        out_off, out_bytes = _output_layout(rows)
+        st = Staging(self.device)
+        frame_rows, mel_rows, src = _reserve(st, rows, n)
+        st.allocate()
         scratch = 0
         if n > real:                             # one scratch frame behind the outputs for the padded rows
-            scratch = _align(_frame_bytes(rows[-1][0], rows[-1][1]))
+            scratch = align(_frame_bytes(rows[-1][0], rows[-1][1]))
         dev_out = torch.empty(out_bytes + scratch, dtype=torch.uint8, device=self.device)
         host_out = torch.empty(out_bytes, dtype=torch.uint8, pin_memory=True)
-        stage = host.numpy()
-        for o, f in frames:
-            stage[o:o + f.nbytes] = f.reshape(-1)
-        ft = stage[:n * FRAME_ROW.itemsize].view(FRAME_ROW)
-        mt = stage[mel_off:mel_off + n * MEL_ROW.itemsize].view(MEL_ROW)
-        shapes, mels, max_px = [], {}, 1             # mels: every device tensor the lane reads, spectrograms and resident frames
+        src = {k: st.address(h) for k, h in src.items()}     # a resident frame's own address: read where it lies
+        ft, mt = st.view(frame_rows), st.view(mel_rows)
+        shapes, mels, max_px = [], {}, 1             # mels: every spectrogram the lane reads
         for r, (job, fi, (y1, y2, x1, x2), start) in enumerate(rows):
             H, W = _frame_hw(job, fi)
-            if _resident(job.frames):                # read where it lies; the lane keeps the tensor alive
-                src = job.frames.data_ptr() + fi * H * W * 3
-                mels[id(job.frames)] = job.frames
-            else:
-                src = dev.data_ptr() + src_off[(id(job), fi)]
-            ft[r] = (src, dev_out.data_ptr() + out_off[r], H, W, y1, y2, x1, x2, (0, 0))
+            ft[r] = (src[(id(job), fi)], dev_out.data_ptr() + out_off[r], H, W, y1, y2, x1, x2, (0, 0))
             mel, T, start = start if isinstance(start, tuple) else (job.mel, job.mel.shape[1], start)
             mt[r] = (mel.data_ptr(), T, start)
             mels[id(mel)] = mel
@@ -170,11 +165,12 @@ class BatchRunner:
             max_px = max(max_px, H * W)
         # padding: the last row again, composed into the scratch frame.  All padded rows write that one frame at the same time,
         # and all write the same bytes (the same row), so the overlap is harmless
-        for r in range(real, n):
-            ft[r], mt[r] = ft[real - 1], mt[real - 1]
-            ft["dst"][r] = dev_out.data_ptr() + out_bytes
-        ticket = self.runner.submit(None, rows=(n, dev[:n * FRAME_ROW.itemsize], dev[mel_off:mel_off + n * MEL_ROW.itemsize], max_px),
-                                    upload=(dev, host), download=(host_out, dev_out[:out_bytes] if scratch else dev_out), keep=tuple(mels.values()))
+        ft[real:], mt[real:] = ft[real - 1], mt[real - 1]
+        ft["dst"][real:] = dev_out.data_ptr() + out_bytes
+        # the lane keeps the spectrograms and the resident frame tensors alive
+        ticket = self.runner.submit(None, rows=(n, st.tensor(frame_rows), st.tensor(mel_rows), max_px), upload=(st.dev, st.host),
+                                    download=(host_out, dev_out[:out_bytes] if scratch else dev_out),
+                                    keep=tuple(mels.values()) + st.residents)
         return ticket, host_out, out_off, shapes
 
     def result(self, item):

@@ -48,10 +48,10 @@ import numpy as np
 
 from . import container
 from . import gen_videos_from_filelist as gv
+from ._lib import RESIZE_ROW
+from .staging import Staging
 
 mel_step_size = 16
-# numpy mirror of w2l_resize_row (32 bytes); the ctypes mirror is _lib.ResizeRow
-RESIZE_ROW = np.dtype([("src", "<u8"), ("dst", "<u8"), ("Hs", "<i4"), ("Ws", "<i4"), ("Hd", "<i4"), ("Wd", "<i4")])
 MAX_ROWS = 65535          # rows of one w2l_resize_rows_u8 launch
 MAX_PIXELS = 1 << 29      # its largest destination frame
 
@@ -190,11 +190,12 @@ def resize_rows(rows):
     dev = torch.device("cuda", torch.cuda.current_device())
     for lo in range(0, len(rows), MAX_ROWS):
         part = rows[lo:lo + MAX_ROWS]
-        table = np.zeros(len(part), RESIZE_ROW)
-        for i, r in enumerate(part):
-            table[i] = tuple(int(v) for v in r)
-        table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
-        check(load().w2l_resize_rows_u8(current_stream(), len(part), ptr(table_dev), max(r[4] * r[5] for r in part)),
+        st = Staging(dev)
+        table = st.table(RESIZE_ROW, len(part))
+        st.allocate()
+        st.view(table)[:] = [tuple(int(v) for v in r) for r in part]
+        st.upload()
+        check(load().w2l_resize_rows_u8(current_stream(), len(part), ptr(st.dev), max(r[4] * r[5] for r in part)),
               "resize_rows_u8")
 
 

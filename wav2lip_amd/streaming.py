@@ -16,9 +16,9 @@ equals `audio.melspectrogram_device(whole audio)` bit for bit.
 
 The spectrogram is streamable exactly: column t reads samples [t*200 - 401, t*200 + 400), so it is FINAL once
 t*200 + 400 <= the samples fed (the reflect padding only touches the two ends; the start is known, the end comes with `close`).
-Per `step` the host stages, in ONE pinned buffer, the new samples of every stream plus the at most 801 earlier ones its next
-columns read (it keeps that tail and nothing older), and ONE w2l_mel_stream_cols launch (csrc/audio_mel.hip) computes the newly
-final columns of all streams into their windows.  Row i of an open stream is ready once the columns through start_i + 15 are
+Per `step` the host stages, in ONE pinned buffer (every staging buffer of this module is laid out by staging.py), the new
+samples of every stream plus the at most 801 earlier ones its next columns read (it keeps that tail and nothing older), and
+ONE w2l_mel_stream_cols launch (csrc/audio_mel.hip) computes the newly final columns of all streams into their windows.  Row i of an open stream is ready once the columns through start_i + 15 are
 final.  Ready rows are taken in stream-open order, each stream's in row order, and packed by `multiclip.BatchRunner` into shared
 batches on `depth` lanes: a full `batch_size` launches at once, the remainder with `flush=True` or in `drain`, padded to the next
 of BUCKETS that is <= batch_size (else batch_size) by repeating the last row into a scratch frame - so the model holds a handful
@@ -87,8 +87,10 @@ import os
 
 import numpy as np
 
+from ._lib import MEL_COL, MEL_STREAM, RESAMPLE_BLOCKS, RESAMPLE_STREAM
 from .inference import LIPSYNC_DEPTH, mel_step_size, validate_boxes
-from .multiclip import BatchRunner, _align
+from .multiclip import BatchRunner
+from .staging import ADDRESS, Staging
 
 HOP, NFFT = 200, 800                  # hparams.py: hop_size, n_fft (the kernels are specialised to them)
 BUCKETS = (8, 16, 32, 64, 128)        # batch sizes of plan_configs.json's table a ragged batch is padded to
@@ -96,22 +98,11 @@ MIN_SAMPLES = NFFT // 2 + 1           # one reflection needs 401 samples (w2l_me
 MIN_WINDOW = 64                       # columns: 16 carried over + room to go on
 MAX_COLS_PER_LAUNCH = 1 << 20         # w2l_mel_stream_cols' limit
 
-# numpy mirrors of w2l_mel_stream (48 bytes) and w2l_mel_col (16 bytes); the ctypes mirrors are _lib.MelStream / _lib.MelCol
-MEL_STREAM = np.dtype([("samples", "<u8"), ("first", "<i8"), ("total", "<i8"), ("window", "<u8"), ("held", "<i4"), ("cap", "<i4"),
-                       ("col0", "<i8")])
-MEL_COL = np.dtype([("stream", "<i4"), ("rsv", "<i4"), ("col", "<i8")])
-
 RATE16 = 16000                        # hparams.py: sample_rate, the rate the spectrogram is specialised to
 RESAMPLE_TABLE, RESAMPLE_NWIN = 512, 64 * 512 + 1         # resampy's kaiser_best: table samples per zero crossing, half window
 RESAMPLE_BLOCK = 128                  # outputs per block entry of w2l_resample_stream (one thread each)
 MAX_BLOCKS_PER_LAUNCH = 1 << 20       # w2l_resample_stream's limit
 MIN_BUFFER16 = 2048                   # 16 kHz samples: the at most 801 the spectrogram still reads + room to go on
-# numpy mirrors of w2l_resample_stream_entry (128 bytes) and w2l_resample_block (32 bytes); ctypes: _lib.ResampleStreamEntry / ResampleBlock
-RESAMPLE_STREAM = np.dtype([("src", "<u8"), ("src_first", "<i8"), ("src_total", "<i8"), ("n_res", "<i8"), ("dst16", "<u8"),
-                            ("dst_first", "<i8"), ("win", "<u8"), ("delta", "<u8"), ("carry", "<u8"), ("carry_first", "<i8"),
-                            ("scale", "<f8"), ("inc", "<f8"), ("src_held", "<i4"), ("dst_cap", "<i4"), ("index_step", "<i4"),
-                            ("nwin", "<i4"), ("carry_held", "<i4"), ("unused", "<i4", (3,))])
-RESAMPLE_BLOCKS = np.dtype([("stream", "<i4"), ("count", "<i4"), ("t0", "<i8"), ("tr0", "<f8"), ("copy", "<i4"), ("unused", "<i4")])
 
 
 def resample_params(rate):
@@ -186,7 +177,29 @@ def bucket(n, batch_size):
     return batch_size
 
 
-class ResampleState:
+class HeldSamples:
+    """samples that arrive in chunks and leave from the front: chunks appended, concatenated on demand, `held_first` the
+    absolute index of `samples()[0]`"""
+
+    def __init__(self):
+        self.held, self.held_first, self.chunks = np.empty(0, np.float32), 0, []
+
+    def samples(self):
+        """the held samples as one array (absolute index of [0]: held_first)"""
+        if self.chunks:
+            self.held = np.concatenate([self.held] + self.chunks)
+            self.chunks = []
+        return self.held
+
+    def drop_below(self, lo):
+        """let go of the samples before the absolute index `lo`"""
+        x = self.samples()
+        if lo > self.held_first:
+            self.held = x[lo - self.held_first:].copy()
+            self.held_first = lo
+
+
+class ResampleState(HeldSamples):
     """host bookkeeping of one stream's conversion to 16 kHz, no device in it: the source samples a later
     output's left wing reads, the running time register, the count of final 16 kHz samples and where they lie"""
 
@@ -194,7 +207,7 @@ class ResampleState:
         self.key, self.rate, self.cap16 = key, int(rate), int(cap16)
         self.ratio, self.inc, self.scale, self.index_step, self.K = resample_params(rate)
         self.n_src, self.closed = 0, False
-        self.held, self.held_first, self.chunks = np.empty(0, np.float32), 0, []
+        HeldSamples.__init__(self)            # the source samples a later output's left wing reads
         self.n16, self.tr_next = 0, 0.0       # final 16 kHz samples computed; the time register of the next one
         self.n_res = self.total16 = None      # after close: resampy's int(N * ratio), librosa's ceil(N * ratio)
         self.buf, self.buf_first = None, 0    # the device buffer that holds the 16 kHz samples [buf_first, n16)
@@ -208,13 +221,6 @@ class ResampleState:
     def close(self):
         self.closed = True
         self.n_res, self.total16 = int(self.n_src * self.ratio), int(np.ceil(self.n_src * self.ratio))
-
-    def samples(self):
-        """the held source samples as one array (absolute index of [0]: held_first)"""
-        if self.chunks:
-            self.held = np.concatenate([self.held] + self.chunks)
-            self.chunks = []
-        return self.held
 
     def registers(self, count):
         """the time registers of the next `count` outputs: the running one continued by sequential float64 addition (cumsum),
@@ -256,25 +262,21 @@ class ResampleState:
     def commit(self, count, tr):
         self.n16 += count
         self.tr_next = float(tr[count - 1]) + self.inc
-        x = self.samples()
-        lo = self.n_src if self.closed and self.n16 == self.total16 else max(0, int(self.tr_next) - self.K)
-        if lo > self.held_first:
-            self.held = x[lo - self.held_first:].copy()
-            self.held_first = lo
+        self.drop_below(self.n_src if self.closed and self.n16 == self.total16 else max(0, int(self.tr_next) - self.K))
 
 
 class Resident:
     """samples that already lie on the device: `size` float32 values from element `offset` of `buffer` (a stream's 16 kHz
-    buffer).  `DeviceMel.compute` reads them where they lie and stages nothing."""
+    buffer).  `DeviceMel.compute` reads them where they lie and stages nothing: to `Staging.place` this is a device object."""
 
     def __init__(self, buffer, offset, size):
-        self.buffer, self.offset, self.size = buffer, int(offset), int(size)
+        self.buffer, self.offset, self.size, self.nbytes = buffer, int(offset), int(size), 4 * int(size)
 
-    def address(self):
+    def data_ptr(self):
         return self.buffer.data_ptr() + 4 * self.offset
 
 
-class StreamState:
+class StreamState(HeldSamples):
     """host bookkeeping of one stream, no device in it: samples held, columns done, the window's position, rows emitted.
     sample_rate other than 16000: the samples fed are converted on the device first (`rs`, a ResampleState with a buffer of
     `cap16` samples) and the spectrogram reads the 16 kHz samples there."""
@@ -283,7 +285,7 @@ class StreamState:
     def __init__(self, key, frames, boxes, static, fps, cap, sample_rate=RATE16, cap16=MIN_BUFFER16):
         self.key, self.frames, self.boxes, self.static, self.fps, self.cap = key, frames, boxes, bool(static), float(fps), int(cap)
         self.n_fed, self.closed = 0, False
-        self.held, self.held_first, self.chunks = np.empty(0, np.float32), 0, []
+        HeldSamples.__init__(self)            # the 16 kHz samples a column not yet done reads (none with `rs`: those lie on the device)
         self.cols_done, self.col0, self.window = 0, 0, None
         self.next_row, self.rows_done, self.n_rows, self.delivered = 0, False, None, 0
         self.rs = None if sample_rate == RATE16 else ResampleState(key, sample_rate, cap16)
@@ -301,13 +303,6 @@ class StreamState:
         if x.size:
             self.chunks.append(x.copy())
             self.n_fed += x.size
-
-    def samples(self):
-        """the held samples as one array (absolute index of [0]: held_first)"""
-        if self.chunks:
-            self.held = np.concatenate([self.held] + self.chunks)
-            self.chunks = []
-        return self.held
 
     def end_audio(self):
         """no more samples follow"""
@@ -354,10 +349,7 @@ class StreamState:
         if self.rs is not None:
             self.rs.need16 = lo               # the samples stay where they are: a fresh 16 kHz buffer starts here
             return
-        x = self.samples()
-        if lo > self.held_first:
-            self.held = x[lo - self.held_first:].copy()
-            self.held_first = lo
+        self.drop_below(lo)
 
     # ---- rows
     def take_rows(self):
@@ -491,7 +483,7 @@ class LiveState(StreamState):
 
 class DeviceBoxes:
     """the device side of live face detection: per call one staged copy, the detector batches, ONE w2l_face_boxes_stream launch
-    (csrc/detect.hip) for every stream of the tick and one copy back - in the manner of `face_detection.many._detect_group`"""
+    (csrc/detect.hip) for every stream of the tick and one copy back"""
 
     def __init__(self, device, detector, pads, T, batch_size):
         import torch
@@ -541,49 +533,35 @@ class DeviceBoxes:
             spans.append((H, W, first, total, padded))
             total = padded
         # ---- one staging buffer: [address table][segment table][the frames that were host arrays]
-        seg_off = _align(total * 8)
-        off = _align(seg_off + len(items) * SEG.itemsize)
-        at = {}
-        for k, mine in enumerate(runs):
-            for j, r in enumerate(mine):
-                if isinstance(r, list):
-                    at[(k, j)] = off
-                    off = _align(off + len(r) * r[0].nbytes)
-        host = torch.empty(off, dtype=torch.uint8, pin_memory=True)
-        stage_dev = torch.empty(off, dtype=torch.uint8, device=self.device)
-        stage = host.numpy()
-        addr = stage[:total * 8].view("<u8")
-        segs = stage[seg_off:seg_off + len(items) * SEG.itemsize].view(SEG)
+        st = Staging(self.device)
+        addresses, segments = st.table(ADDRESS, total), st.table(SEG, len(items))
+        src = [[st.place(run) for run in mine] for mine in runs]
+        st.allocate()
+        addr, segs = st.view(addresses), st.view(segments)
         chunks, out0 = [], 0
         for k, (fresh, H, W, slot, seen, closed) in enumerate(items):
             fb, r, mine = H * W * 3, row0.get(k, 0), []
-            for j, run in enumerate(runs[k]):
-                if isinstance(run, list):
-                    o, n = at[(k, j)], len(run)
-                    dst = stage[o:o + n * fb].reshape(n, H, W, 3)
-                    for i, f in enumerate(run):
-                        dst[i] = f
-                    t = stage_dev[o:o + n * fb].view(n, H, W, 3)
-                else:
-                    t, n = run, int(run.shape[0])
-                addr[r:r + n] = np.uint64(t.data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(fb)
-                mine.append((n, t))
+            for h in src[k]:
+                n = h.nbytes // fb
+                addr[r:r + n] = np.uint64(st.address(h)) + np.arange(n, dtype=np.uint64) * np.uint64(fb)
+                mine.append((n, st.tensor(h).view(n, H, W, 3)))
                 r += n
             chunks.append(mine)
             segs[k] = (row0.get(k, 0), n_new[k], H, W, slot, seen, int(bool(closed)), out0)
             out0 += live.new_final_count(seen, n_new[k], closed, T)
         for H, W, first, end, padded in spans:
             addr[end:padded] = addr[end - 1]               # the last batch of a shape: its last address again, into scratch rows
-        stage_dev.copy_(host, non_blocking=True)
+        st.upload()
         rects = torch.empty((max(total, 1), 4), dtype=torch.int32, device=self.device)
         flags = torch.empty((max(total, 1),), dtype=torch.int32, device=self.device)
+        addr_dev = st.tensor(addresses)
         for H, W, first, end, padded in spans:
             for lo in range(first, padded, B):
-                self.detector.rects_for_rows(stage_dev[lo * 8:(lo + B) * 8], B, H, W, rects, flags, lo)
+                self.detector.rects_for_rows(addr_dev[lo * 8:(lo + B) * 8], B, H, W, rects, flags, lo)
         out = torch.empty(4 * out0 + 2 * len(items), dtype=torch.int32, device=self.device)     # boxes, then status: one copy back
         top, bottom, left, right = self.pads
         with torch.cuda.device(self.device):
-            check(self.lib.w2l_face_boxes_stream(current_stream(), len(items), host.data_ptr() + seg_off, stage_dev.data_ptr() + seg_off,
+            check(self.lib.w2l_face_boxes_stream(current_stream(), len(items), st.host_address(segments), st.address(segments),
                                                  ptr(rects), ptr(flags), total, ptr(self.carry), int(self.carry.shape[0]), top, bottom,
                                                  left, right, T, ptr(out), out0, out.data_ptr() + 16 * out0), "face_boxes_stream")
         host_out = torch.empty(out.numel(), dtype=torch.int32, pin_memory=True)
@@ -591,7 +569,7 @@ class DeviceBoxes:
         done = torch.cuda.Event()
         done.record()
         counts = [int(c) for c in np.diff(np.append(segs["out0"], out0))]
-        return dict(chunks=chunks, counts=counts, host_out=host_out, done=done, keep=(host, stage_dev, rects, flags, out))
+        return dict(chunks=chunks, counts=counts, host_out=host_out, done=done, keep=(st.host, st.dev, rects, flags, out))
 
     @staticmethod
     def collect(ticket):
@@ -634,36 +612,24 @@ class DeviceMel:
         from ._lib import check, ptr
         torch = self.torch
         ncols = sum(it[7] for it in items)
-        off = _align(len(items) * MEL_STREAM.itemsize)
-        col_off = off
-        off = _align(off + ncols * MEL_COL.itemsize)
-        at = []
-        for it in items:
-            at.append(off)
-            if not isinstance(it[0], Resident):
-                off = _align(off + it[0].nbytes)
-        host = torch.empty(off, dtype=torch.uint8, pin_memory=True)
-        dev = torch.empty(off, dtype=torch.uint8, device=self.device)
-        stage = host.numpy()
-        st = stage[:len(items) * MEL_STREAM.itemsize].view(MEL_STREAM)
-        ct = stage[col_off:col_off + ncols * MEL_COL.itemsize].view(MEL_COL)
-        c = 0
+        stage = Staging(self.device)
+        streams, cols = stage.table(MEL_STREAM, len(items)), stage.table(MEL_COL, ncols)
+        src = [stage.place(it[0]) for it in items]
+        stage.allocate()
+        st, ct = stage.view(streams), stage.view(cols)
+        ct["rsv"] = 0
+        col_stream, col_col, c = ct["stream"], ct["col"], 0
         for k, (x, first, total, window, cap, col0, lo, count) in enumerate(items):
-            if isinstance(x, Resident):
-                st[k] = (x.address(), first, total, window.data_ptr(), x.size, cap, col0)
-            else:
-                stage[at[k]:at[k] + x.nbytes] = x.view(np.uint8)
-                st[k] = (dev.data_ptr() + at[k], first, total, window.data_ptr(), x.size, cap, col0)
-            ct["stream"][c:c + count] = k
-            ct["rsv"][c:c + count] = 0
-            ct["col"][c:c + count] = np.arange(lo, lo + count)
+            st[k] = (stage.address(src[k]), first, total, window.data_ptr(), x.size, cap, col0)
+            col_stream[c:c + count] = k
+            col_col[c:c + count] = np.arange(lo, lo + count)
             c += count
-        dev.copy_(host, non_blocking=True)
+        stage.upload()
         with torch.cuda.device(self.device):
             for lo in range(0, ncols, MAX_COLS_PER_LAUNCH):
                 n = min(MAX_COLS_PER_LAUNCH, ncols - lo)
-                check(self.lib.w2l_mel_stream_cols(self.ctx, _lib.current_stream(), ptr(dev), len(items),
-                                                   dev.data_ptr() + col_off + lo * MEL_COL.itemsize, n), "mel_stream_cols")
+                check(self.lib.w2l_mel_stream_cols(self.ctx, _lib.current_stream(), ptr(stage.dev), len(items),
+                                                   stage.address(cols) + lo * MEL_COL.itemsize, n), "mel_stream_cols")
 
 
 def check_coverage(x_first, x_size, total, lo, count, key=None):
@@ -732,36 +698,29 @@ class DeviceResampler:
         from ._lib import check, ptr
         torch, B = self.torch, RESAMPLE_BLOCK
         nblocks = sum((it[10] + B - 1) // B + ((it[7][3] + B - 1) // B if it[7] else 0) for it in items)
-        blk_off = _align(len(items) * RESAMPLE_STREAM.itemsize)
-        off = _align(blk_off + nblocks * RESAMPLE_BLOCKS.itemsize)
-        at = []
-        for it in items:
-            at.append(off)
-            off = _align(off + it[0].nbytes)
-        host = torch.empty(off, dtype=torch.uint8, pin_memory=True)
-        dev = torch.empty(off, dtype=torch.uint8, device=self.device)
-        stage = host.numpy()
-        st = stage[:len(items) * RESAMPLE_STREAM.itemsize].view(RESAMPLE_STREAM)
-        bt = stage[blk_off:blk_off + nblocks * RESAMPLE_BLOCKS.itemsize].view(RESAMPLE_BLOCKS)
+        stage = Staging(self.device)
+        streams, blocks = stage.table(RESAMPLE_STREAM, len(items)), stage.table(RESAMPLE_BLOCKS, nblocks)
+        src = [stage.place(it[0]) for it in items]
+        stage.allocate()
+        st, bt = stage.view(streams), stage.view(blocks)
         b = 0
         for k, (x, first, total, n_res, buf, buf_first, cap16, carry, rate, t0, count, tr) in enumerate(items):
             _, inc, scale, index_step, _ = resample_params(rate)
             win, delta = audio.resample_tables(self.device, rate, RATE16)
-            stage[at[k]:at[k] + x.nbytes] = x.view(np.uint8)
             old, old_first, c0, cn = carry if carry else (None, 0, 0, 0)
-            st[k] = (dev.data_ptr() + at[k], first, total, n_res, buf.data_ptr(), buf_first, win.data_ptr(), delta.data_ptr(),
+            st[k] = (stage.address(src[k]), first, total, n_res, buf.data_ptr(), buf_first, win.data_ptr(), delta.data_ptr(),
                      old.data_ptr() if cn else 0, old_first, scale, inc, x.size, cap16, index_step, win.numel(),
                      old.numel() if cn else 0, (0, 0, 0))
             mine = resample_blocks(k, t0, tr, c0, cn)
             bt[b:b + len(mine)] = mine
             b += len(mine)
         assert b == nblocks
-        dev.copy_(host, non_blocking=True)
+        stage.upload()
         with torch.cuda.device(self.device):
             for lo in range(0, nblocks, MAX_BLOCKS_PER_LAUNCH):
                 n = min(MAX_BLOCKS_PER_LAUNCH, nblocks - lo)
-                check(self.lib.w2l_resample_stream(_lib.current_stream(), host.data_ptr(), ptr(dev), len(items),
-                                                   dev.data_ptr() + blk_off + lo * RESAMPLE_BLOCKS.itemsize, n, RESAMPLE_TABLE),
+                check(self.lib.w2l_resample_stream(_lib.current_stream(), stage.host_address(streams), ptr(stage.dev), len(items),
+                                                   stage.address(blocks) + lo * RESAMPLE_BLOCKS.itemsize, n, RESAMPLE_TABLE),
                       "resample_stream")
 
 
