@@ -183,7 +183,7 @@ int w2l_frames_to_u8(void* stream, int N, int H, int W, const float* x, int x_cs
  * cv::resize(INTER_LINEAR) for CV_8UC3 (OpenCV 4.1.0 fixed-point path, see csrc/resize.hip).
  *
  * PRECONDITION of the five image entry points (w2l_crop_resize_u8, w2l_resize_u8, w2l_resize_paste_u8, w2l_crop_resize_rows_u8,
- * w2l_compose_rows_u8): every box is non-empty and inside its frame, and every frame_idx names an existing frame.  The boxes
+ * w2l_compose_rows_u8) and of the two blend forms (w2l_resize_blend_u8, w2l_compose_blend_rows_u8): every box is non-empty and inside its frame, and every frame_idx names an existing frame.  The boxes
  * live in device memory, so the entry points cannot look at them and the kernels do not: an empty or inverted box makes the tap
  * clamp of a source size <= 0 read index -1, and two negative extents give the paste a positive pixel count.  The HOST caller
  * checks them before the launch (wav2lip_amd/inference.py validate_boxes, and what multiclip, streaming, calculate_scores and
@@ -231,6 +231,25 @@ int w2l_crop_resize_rows_u8(void* stream, int B, const w2l_frame_row* rows, int 
  * (byte-equal to a frame copy + w2l_resize_paste_u8).  src == dst: paste in place.  max_frame_pixels >= the largest H*W of
  * the batch (sizes the launch). */
 int w2l_compose_rows_u8(void* stream, int B, const uint8_t* pred, int S, const w2l_frame_row* rows, int max_frame_pixels);
+
+/* Feathered, mouth-region forms of the two pastes (opt-in: NOT the reference's output, which is the hard rectangle above).
+ * Integer-only and exact.  Per box of h x w pixels, with feather F in [0, 64] (pixels of the output frame) and top_q8 T in
+ * [0, 255] (T = 128 keeps the original upper half of the box), box-relative row j and column i:
+ *   t0 = (h*T) >> 8;  hr = h - t0 (>= 1);  Fe = min(F, (min(w, hr) - 1) / 2);  D = (Fe+1)^2
+ *   wy(j) = 0 for j < t0, else min(Fe+1, j-t0+1, h-j);  wx(i) = min(Fe+1, i+1, w-i);  a = wx*wy
+ *   out_c = (a*p_c + (D-a)*o_c + D/2) / D      (floor; at most 4225*255 + 2112, 32-bit)
+ * p = the pixel the plain paste writes (the same copy / 2x area / 11-bit bilinear resize), o = the frame's own pixel.  Fe is per
+ * box, so the centre of a small box still reaches a == D.  F = 0, T = 0: a == D == 1, byte-equal to the plain paste.  Pixels with
+ * a == 0 are never resized: copied from the source, or skipped in place.
+ *
+ * w2l_resize_blend_u8: in place, as w2l_resize_paste_u8 (one thread reads and writes a pixel); same preconditions and argument
+ * checks.  Two items that name one destination frame are undefined, as there.
+ * w2l_compose_blend_rows_u8: as w2l_compose_rows_u8; o is read from src, dst is written, src == dst blends in place.
+ * Both refuse feather outside [0, 64] and top_q8 outside [0, 255] with an error code, writing nothing. */
+int w2l_resize_blend_u8(void* stream, int B, const uint8_t* pred, int S, const int32_t* boxes, const int32_t* frame_idx,
+                        uint8_t* frames, int H, int W, int max_box_pixels, int feather, int top_q8);
+int w2l_compose_blend_rows_u8(void* stream, int B, const uint8_t* pred, int S, const w2l_frame_row* rows, int max_frame_pixels,
+                              int feather, int top_q8);
 
 /* Whole-frame row-table resize (evaluation/real_videos_inference.py:51-70 rescale_frames, :239-245 the `max_frame_res` cap at read
  * time): row b gives dst_b u8 [Hd,Wd,3] = cv2.resize(src_b u8 [Hs,Ws,3], (Wd,Hd)), byte-equal to w2l_resize_u8 for that frame

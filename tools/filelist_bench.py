@@ -1,7 +1,7 @@
 """Packed filelist generation against the per-clip loop, alternated in one process: frames/s of `multiclip.lipsync_many` and of
 `for clip: inference.lipsync(model, frames, wav, box=...)` over the same seeded clips.
 
-    python tools/filelist_bench.py [--clips 200] [--alternations 5] [--batch 128] [--seed 0]
+    python tools/filelist_bench.py [--clips 200] [--alternations 5] [--batch 128] [--seed 0] [--blend_feather N] [--blend_top FRACTION]
 
 The clips are 160x160 with a fixed 110x110 face box (no detection: only the generator path is timed) and lengths uniform in
 30..120 mel chunks.  Both loops start from the 16 kHz samples (the mel spectrogram is part of both) and end with every output
@@ -11,7 +11,8 @@ of what that loop costs on a filelist it has not seen.  Then the two loops alter
 (every plan built).  Prints one JSON line: per loop the frames/s of every pass, median, min and max (the spread), the first-pass
 seconds, the number of cached plans, and torch.cuda.max_memory_allocated after the loop's first pass (the device is reset to
 the other loop's state in between only as far as the caching allocator allows: the figure is the peak since process start for
-the packed loop, which runs first, and the peak over everything for the per-clip loop)."""
+the packed loop, which runs first, and the peak over everything for the per-clip loop).  `--blend_feather` / `--blend_top` are
+passed to both loops (the feathered mouth-region paste) and recorded in the result."""
 import argparse
 import json
 import os
@@ -46,7 +47,7 @@ def model(dev):
     return G.to(dev).eval()
 
 
-def run_packed(G, clips, batch, dev):
+def run_packed(G, clips, batch, dev, blend=None):
     def jobs():
         for i, (frames, wav) in enumerate(clips):
             mel = audio.melspectrogram_device(wav, dev)
@@ -56,16 +57,16 @@ def run_packed(G, clips, batch, dev):
     def sink(key, frame):
         n[0] += frame is not None
     t0 = time.perf_counter()
-    multiclip.lipsync_many(G, jobs(), batch_size=batch, sink=sink)
+    multiclip.lipsync_many(G, jobs(), batch_size=batch, sink=sink, **inference._blend_kw(blend))
     torch.cuda.synchronize()
     return n[0], time.perf_counter() - t0
 
 
-def run_loop(G, clips, batch, dev):
+def run_loop(G, clips, batch, dev, blend=None):
     n = 0
     t0 = time.perf_counter()
     for frames, wav in clips:
-        n += len(inference.lipsync(G, frames, wav, batch_size=batch, box=BOX))
+        n += len(inference.lipsync(G, frames, wav, batch_size=batch, box=BOX, **inference._blend_kw(blend)))
     torch.cuda.synchronize()
     return n, time.perf_counter() - t0
 
@@ -80,20 +81,22 @@ def main(argv=None):
     ap.add_argument("--alternations", type=int, default=5)
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--seed", type=int, default=0)
+    inference.add_blend_flags(ap)
     a = ap.parse_args(argv)
+    blend = inference.blend_from_args(a)
     dev = torch.device("cuda", 0)
     clips = make_clips(a.clips, a.seed)
     out = {"clips": a.clips, "batch": a.batch, "alternations": a.alternations,
-           "distinct_lengths": len({len(f) for f, _ in clips})}
+           "distinct_lengths": len({len(f) for f, _ in clips}), "blend": blend}
     loops = {"packed": (run_packed, model(dev)), "per_clip": (run_loop, model(dev))}
     res = {k: {"fps": []} for k in loops}
     for name, (fn, G) in loops.items():                   # pass 0: warm-up, plans built
-        n, t = fn(G, clips, a.batch, dev)
+        n, t = fn(G, clips, a.batch, dev, blend)
         res[name].update(frames=n, first_pass_s=round(t, 2), first_pass_fps=round(n / t, 1), plans=len(G._graphs),
                          max_memory_allocated_gb=round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2))
     for _ in range(a.alternations):
         for name, (fn, G) in loops.items():
-            n, t = fn(G, clips, a.batch, dev)
+            n, t = fn(G, clips, a.batch, dev, blend)
             res[name]["fps"].append(n / t)
     for name in loops:
         res[name]["fps"] = stats(res[name]["fps"])

@@ -126,6 +126,111 @@ __global__ void compose_rows_kernel(int B, const uint8_t* __restrict__ pred, int
     }
 }
 
+// ---- feathered, mouth-region paste (opt-in; not the reference's output): the blend forms of the two paste kernels above.
+// Integers only.  Per box of h x w pixels, feather F (0..64) and top_q8 T (0..255):
+//   t0 = (h*T) >> 8, hr = h - t0 (>= 1), Fe = min(F, (min(w, hr) - 1) / 2), D = (Fe+1)^2
+//   wy(j) = 0 for j < t0, else min(Fe+1, j-t0+1, h-j);  wx(i) = min(Fe+1, i+1, w-i);  a = wx*wy
+//   out_c = (a*p_c + (D-a)*o_c + D/2) / D, p = resize_px (unchanged), o = the frame's own pixel
+// Rows above t0 (a == 0) are never resized: the kernels treat the box as starting at row y1 + t0, where a >= 1 everywhere.
+// a == D (the box's centre; every pixel when F = 0) stores p without reading o.  In the band the quotient is
+// umulhi(n, ceil(2^32 / D)): equal to n / D for every D = (Fe+1)^2 > 1 and n <= 255*D + D/2 (tests/test_blend_cases_cpu.py
+// checks every such pair on the host); D == 1 has no band.
+struct BlendBox {
+    int t0, fe1;            // first blended row of the box; Fe + 1
+    uint32_t D, magic;      // (Fe+1)^2; ceil(2^32 / D), unused for D == 1
+};
+
+__device__ __forceinline__ BlendBox blend_box(int h, int w, int feather, int top_q8) {
+    BlendBox k;
+    k.t0 = (int)(((long long)h * top_q8) >> 8);
+    k.fe1 = min(feather, (min(w, h - k.t0) - 1) >> 1) + 1;
+    k.D = (uint32_t)(k.fe1 * k.fe1);
+    k.magic = 0xFFFFFFFFu / k.D + 1u;
+    return k;
+}
+
+// weight of box-relative column i, row j >= t0
+__device__ __forceinline__ uint32_t blend_weight(const BlendBox& k, int i, int j, int h, int w) {
+    const int wy = min(k.fe1, min(j - k.t0 + 1, h - j));
+    const int wx = min(k.fe1, min(i + 1, w - i));
+    return (uint32_t)(wx * wy);
+}
+
+// px = the resized prediction's pixel, o = the frame's: px becomes the blend (a < D), or stays (a == D, o is not read)
+__device__ __forceinline__ void blend_px(const BlendBox& k, uint32_t a, const uint8_t* o, uint8_t* px) {
+    if (a == k.D) return;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        px[c] = (uint8_t)__umulhi(a * px[c] + (k.D - a) * o[c] + (k.D >> 1), k.magic);
+}
+
+__global__ void resize_blend_kernel(int B, const uint8_t* __restrict__ pred, int S, const int32_t* __restrict__ boxes,
+                                    const int32_t* __restrict__ frame_idx, uint8_t* frames, int H, int W, int feather,
+                                    int top_q8) {
+    const int b = blockIdx.y;
+    const int4 box = *reinterpret_cast<const int4*>(boxes + 4 * b);
+    const int fo = frame_idx ? frame_idx[b] : b;
+    const int h = box.y - box.x, w = box.w - box.z;
+    const BlendBox k = blend_box(h, w, feather, top_q8);
+    const uint8_t* src = pred + (long long)b * S * S * 3;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < (h - k.t0) * w; i += gridDim.x * blockDim.x) {
+        const int dy = k.t0 + i / w, dx = i - (dy - k.t0) * w;
+        uint8_t px[3];
+        resize_px(src, (long long)S * 3, S, S, dx, dy, w, h, px);
+        uint8_t* o = frames + (((long long)fo * H + box.x + dy) * W + box.z + dx) * 3;
+        blend_px(k, blend_weight(k, dx, dy, h, w), o, px);
+        o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
+    }
+}
+
+// compose_rows_kernel with the blend: the same groups, the three-dword move for every group that misses the blended part of the
+// box (rows y1 + t0 .. y2); a box pixel reads o from src and writes dst in one thread, so src == dst stays in place
+__global__ void compose_blend_rows_kernel(int B, const uint8_t* __restrict__ pred, int S, const FrameRow* __restrict__ rows,
+                                          int feather, int top_q8) {
+    const int b = blockIdx.y;
+    const FrameRow r = rows[b];
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(r.src);
+    uint8_t* dst = reinterpret_cast<uint8_t*>(r.dst);
+    const uint8_t* p = pred + (long long)b * S * S * 3;
+    const int h = r.y2 - r.y1, w = r.x2 - r.x1;
+    const BlendBox k = blend_box(h, w, feather, top_q8);
+    const int y1 = r.y1 + k.t0;                         // first blended frame row
+    const int npx = r.H * r.W;                          // < 2^31 / 3 (checked by the caller's max_frame_pixels)
+    const int ngroups = (npx + 3) >> 2;
+    const bool in_place = src == dst;
+    const bool dwords = (((r.src | r.dst) & 3) == 0);
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += gridDim.x * blockDim.x) {
+        const int i0 = g << 2, i1 = min(i0 + 4, npx);
+        const int ya = i0 / r.W, xa = i0 - ya * r.W;
+        const int yb = (i1 - 1) / r.W, xb = (i1 - 1) - yb * r.W;
+        const bool a_in = ya >= y1 && ya < r.y2 && xa < r.x2 && (ya == yb ? xb : r.W - 1) >= r.x1;
+        const bool b_in = yb != ya && yb >= y1 && yb < r.y2 && xb >= r.x1;
+        if (r.W >= 4 && !a_in && !b_in) {
+            if (in_place) continue;
+            if (dwords && i1 - i0 == 4) {
+                const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src + (long long)i0 * 3);
+                uint32_t* d4 = reinterpret_cast<uint32_t*>(dst + (long long)i0 * 3);
+                const uint32_t v0 = s4[0], v1 = s4[1], v2 = s4[2];
+                d4[0] = v0; d4[1] = v1; d4[2] = v2;
+                continue;
+            }
+        }
+        for (int i = i0; i < i1; ++i) {
+            const int y = i / r.W, x = i - y * r.W;
+            const uint8_t* q = src + (long long)i * 3;
+            uint8_t* o = dst + (long long)i * 3;
+            if (y >= y1 && y < r.y2 && x >= r.x1 && x < r.x2) {
+                uint8_t px[3];
+                resize_px(p, (long long)S * 3, S, S, x - r.x1, y - r.y1, w, h, px);
+                blend_px(k, blend_weight(k, x - r.x1, y - r.y1, h, w), q, px);
+                o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
+            } else if (!in_place) {
+                o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
+            }
+        }
+    }
+}
+
 // ---- whole-frame row-table resize (evaluation/real_videos_inference.py:239-245 the `max_frame_res` cap at read time, :51-70
 // rescale_frames by an integer factor): every row names its own source and destination frame and their sizes, so frames of any
 // shapes share one launch and two rows may read one source.  Same resize_px arithmetic: byte-equal to resize_frames_kernel.
@@ -253,6 +358,35 @@ int w2l_compose_rows_u8(void* stream, int B, const uint8_t* pred, int S, const w
     if (gx > 1024) gx = 1024;
     hipLaunchKernelGGL(compose_rows_kernel, dim3(gx, B), dim3(256), 0, static_cast<hipStream_t>(stream), B, pred, S,
                        reinterpret_cast<const FrameRow*>(rows));
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_resize_blend_u8(void* stream, int B, const uint8_t* pred, int S, const int32_t* boxes, const int32_t* frame_idx,
+                        uint8_t* frames, int H, int W, int max_box_pixels, int feather, int top_q8) {
+    W2L_REQUIRE(pred && boxes && frames && B >= 1 && H >= 1 && W >= 1 && S >= 1 && max_box_pixels >= 1,
+                "bad resize_blend arguments");
+    W2L_REQUIRE(B <= 65535 && (reinterpret_cast<uintptr_t>(boxes) & 15) == 0, "resize_blend: B <= 65535 and 16-byte aligned boxes");
+    W2L_REQUIRE(feather >= 0 && feather <= 64 && top_q8 >= 0 && top_q8 <= 255, "resize_blend: feather in [0, 64], top_q8 in [0, 255]");
+    int gx = ceil_div(max_box_pixels, 256);
+    if (gx > 256) gx = 256;
+    hipLaunchKernelGGL(resize_blend_kernel, dim3(gx, B), dim3(256), 0, static_cast<hipStream_t>(stream), B, pred, S, boxes,
+                       frame_idx, frames, H, W, feather, top_q8);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_compose_blend_rows_u8(void* stream, int B, const uint8_t* pred, int S, const w2l_frame_row* rows, int max_frame_pixels,
+                              int feather, int top_q8) {
+    W2L_REQUIRE(pred && rows && S >= 1 && max_frame_pixels >= 1 && max_frame_pixels <= (1 << 29), "bad compose_blend_rows arguments");
+    W2L_REQUIRE(B >= 1 && B <= 65535 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0,
+                "compose_blend_rows: 1 <= B <= 65535 and a 16-byte aligned row table");
+    W2L_REQUIRE(feather >= 0 && feather <= 64 && top_q8 >= 0 && top_q8 <= 255,
+                "compose_blend_rows: feather in [0, 64], top_q8 in [0, 255]");
+    int gx = ceil_div(ceil_div(max_frame_pixels, 4), 256);
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(compose_blend_rows_kernel, dim3(gx, B), dim3(256), 0, static_cast<hipStream_t>(stream), B, pred, S,
+                       reinterpret_cast<const FrameRow*>(rows), feather, top_q8);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

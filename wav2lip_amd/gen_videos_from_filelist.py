@@ -67,12 +67,14 @@ def build_cli_parser():
 def build_main_parser():
     """what `main()` parses: `build_cli_parser` plus `--packed_face_det`, which changes how the work is scheduled and nothing of
     what is computed, and `--face_det_scale K`, the size of the frame the detector sees (`inference.add_det_scale_flag`).
+    `--blend_feather N` / `--blend_top FRACTION` blend every generated face into its frame (`inference.add_blend_flags`).
     `cli_parser` stays the reference's surface plus the two precision flags."""
-    from .inference import add_det_scale_flag
+    from .inference import add_blend_flags, add_det_scale_flag
     p = build_cli_parser()
     p.add_argument('--packed_face_det', default=False, action='store_true',
                    help='Detect faces of successive clips in shared detector batches (face_detection.detect_many)')
     add_det_scale_flag(p)
+    add_blend_flags(p)
     return p
 
 
@@ -251,6 +253,7 @@ def main(argv=None, state_dict=None, backend="nccl"):
     from . import face_detection, inference, multiclip, sharding
     args = main_parser.parse_args(argv)
     args.img_size = 96
+    blend_kw = inference._blend_kw(inference.blend_from_args(args))
     ranks = sharding.init_from_env(backend)
     try:
         assert args.data_root is not None
@@ -269,7 +272,7 @@ def main(argv=None, state_dict=None, backend="nccl"):
         try:
             producer = clip_jobs_packed if args.packed_face_det else clip_jobs
             multiclip.lipsync_many(model, producer(args, lines, ranks, detector, tracks), batch_size=args.wav2lip_batch_size,
-                                   precision=inference.CLI_PRECISION[args.precision], sink=sink)
+                                   precision=inference.CLI_PRECISION[args.precision], sink=sink, **blend_kw)
         finally:
             sink.close()
         return sink.written

@@ -86,11 +86,93 @@ def add_det_scale_flag(p):
     p.add_argument('--face_det_scale', default=1, type=det_scale_arg, metavar='K', help=DET_SCALE_HELP)
 
 
+# ---------------------------------------------------------------- the feathered, mouth-region paste (opt-in)
+BLEND_MAX_FEATHER = 64
+
+
+def check_blend(blend):
+    """the `blend=` of the runners, `lipsync`, `multiclip.lipsync_many` and `streaming.LipsyncStreams`: None (the reference's
+    hard-rectangle paste) or a pair (feather, top).  `feather`: an int in 0..64, the width in output-frame pixels of the ramp
+    inside the box edge; `top`: a float in [0, 1), the fraction of the box height, from its top, that keeps the original frame
+    (0.5: the mouth half alone is pasted).  Returns None when the pair asks for the plain paste (feather 0 and int(top*256) == 0),
+    else (feather, top) as (int, float); a ValueError names what is wrong."""
+    if blend is None:
+        return None
+    try:
+        feather, top = blend
+    except (TypeError, ValueError):
+        raise ValueError("blend must be None or a (feather, top) pair, got %r" % (blend,)) from None
+    if isinstance(feather, bool) or not isinstance(feather, (int, np.integer)):
+        raise ValueError("blend feather must be an integer in 0..%d, got %r" % (BLEND_MAX_FEATHER, feather))
+    if not 0 <= feather <= BLEND_MAX_FEATHER:
+        raise ValueError("blend feather %d is outside 0..%d" % (feather, BLEND_MAX_FEATHER))
+    if isinstance(top, bool) or not isinstance(top, (int, float, np.integer, np.floating)):
+        raise ValueError("blend top must be a fraction in [0, 1), got %r" % (top,))
+    top = float(top)
+    if not 0.0 <= top < 1.0:                # NaN fails both comparisons
+        raise ValueError("blend top %r is outside [0, 1)" % (top,))
+    if feather == 0 and blend_top_q8(top) == 0:
+        return None
+    return int(feather), top
+
+
+def blend_top_q8(top):
+    """`top_q8` of the blend kernels for a checked `top` in [0, 1): 0..255"""
+    return int(top * 256)
+
+
+def _blend_kw(blend):
+    """the keyword a runner (or what builds one) takes for `blend`, checked first: none for the plain paste, so the default path is
+    called with the same arguments as before the option (as `_precision_kw`)"""
+    blend = check_blend(blend)
+    return {} if blend is None else {"blend": blend}
+
+
+def blend_feather_arg(text):
+    """argparse type of `--blend_feather`: an integer in 0..64 (a parse error otherwise)"""
+    try:
+        f = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is not an integer" % (text,))
+    if not 0 <= f <= BLEND_MAX_FEATHER:
+        raise argparse.ArgumentTypeError("%d is outside 0..%d" % (f, BLEND_MAX_FEATHER))
+    return f
+
+
+def blend_top_arg(text):
+    """argparse type of `--blend_top`: a fraction in [0, 1) (a parse error otherwise)"""
+    try:
+        t = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is not a number" % (text,))
+    if not 0.0 <= t < 1.0:
+        raise argparse.ArgumentTypeError("%r is outside [0, 1)" % (t,))
+    return t
+
+
+def add_blend_flags(p):
+    """`--blend_feather N --blend_top FRACTION` on a command's parser; both 0 by default (the reference's paste) and independent
+    of --precision, --out_codec and sharded runs"""
+    p.add_argument('--blend_feather', default=0, type=blend_feather_arg, metavar='N',
+                   help='Blend the generated face into the frame over a ramp of N pixels (0..64) inside the box edge instead of '
+                        'pasting a hard rectangle (default 0, as the reference). Not the reference\'s output')
+    p.add_argument('--blend_top', default=0.0, type=blend_top_arg, metavar='FRACTION',
+                   help='Keep the original frame in this fraction of the face box, from its top (in [0, 1); default 0.0, as the '
+                        'reference). 0.5 pastes the mouth half alone. Not the reference\'s output')
+
+
+def blend_from_args(a):
+    """the `blend=` of a parsed command line (`add_blend_flags`): None when both flags are at their defaults, or when the
+    namespace comes from a parser without them"""
+    return check_blend((getattr(a, "blend_feather", 0), getattr(a, "blend_top", 0.0)))
+
+
 def build_cli_parser():
-    """the command line `main()` parses: the reference's flags (`build_parser`, whose surface stays the reference's) plus three
+    """the command line `main()` parses: the reference's flags (`build_parser`, whose surface stays the reference's) plus
     documented additions that are not among them, each the reference's behaviour by default and independent of the others:
-    `--precision {fp32,bf16}`, the generator's arithmetic, `--face_det_precision {fp32,bf16}`, the S3FD detector's, and
-    `--face_det_scale K`, the detector's frame size (1/K; output frames keep theirs)"""
+    `--precision {fp32,bf16}`, the generator's arithmetic, `--face_det_precision {fp32,bf16}`, the S3FD detector's,
+    `--face_det_scale K`, the detector's frame size (1/K; output frames keep theirs), `--out_codec` / `--out_quality`, and
+    `--blend_feather N` / `--blend_top FRACTION`, the feathered mouth-region paste"""
     p = build_parser()
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
                    help='Generator arithmetic: fp32 (default, matches the reference) or bf16 storage (faster; frames differ by '
@@ -104,6 +186,7 @@ def build_cli_parser():
                         "cv2.VideoWriter_fourcc(*'MJPG') writes: every frame is JPEG-encoded on the device and only the files' "
                         'bytes come back; lossy, about a tenth of the size at quality 95)')
     p.add_argument('--out_quality', default=95, type=int, help='JPEG quality of --out_codec mjpg, 1..100 (default 95)')
+    add_blend_flags(p)
     return p
 
 
@@ -156,12 +239,13 @@ def mel_chunk_starts(n_mel_frames, fps):
 class Wav2LipRunner:
     """Device-resident replacement of the body of the reference's batch loop for one model and batch size."""
 
-    def __init__(self, model, batch_size=128, lane=0, precision="f32"):
+    def __init__(self, model, batch_size=128, lane=0, precision="f32", blend=None):
         from .models.wav2lip import check_precision
         self.model = model
         self.batch_size = batch_size
         self.lane = lane
         self.precision = check_precision(precision)
+        self.blend = check_blend(blend)      # None: the reference's paste; (feather, top): `run_frames` / `run_rows` blend
         self.device = next(model.parameters()).device
         if self.device.type != "cuda":
             raise RuntimeError("wav2lip_amd.inference: the model must be on a HIP device (no CPU path)")
@@ -218,14 +302,18 @@ class Wav2LipRunner:
         faces = torch.empty((n, img_size, img_size, 3), dtype=torch.uint8, device=self.device)
         check(self.lib.w2l_crop_resize_rows_u8(s, n, ptr(frame_rows), img_size, ptr(faces)), "crop_resize_rows_u8")
         pred = self.run_batch(faces, mel_rows=mel_rows)
-        check(self.lib.w2l_compose_rows_u8(s, n, ptr(pred), img_size, ptr(frame_rows), int(max_frame_pixels)), "compose_rows_u8")
+        if self.blend is None:
+            check(self.lib.w2l_compose_rows_u8(s, n, ptr(pred), img_size, ptr(frame_rows), int(max_frame_pixels)), "compose_rows_u8")
+        else:
+            check(self.lib.w2l_compose_blend_rows_u8(s, n, ptr(pred), img_size, ptr(frame_rows), int(max_frame_pixels),
+                                                     self.blend[0], blend_top_q8(self.blend[1])), "compose_blend_rows_u8")
         return pred
 
     def run_frames(self, frames, frame_idx, boxes, mel_windows=None, mel=None, starts=None):
         """Full-frame variant of `run_batch` (inference.py:121-126 + :259-271).  frames: torch uint8 [F,H,W,3] on the
         device; frame_idx: n frame numbers; boxes: n (y1, y2, x1, x2) face boxes.  Crops and resizes the faces to 96x96,
-        runs the batch, resizes each generated crop to its box and pastes it into a copy of its frame.
-        Returns torch uint8 [n,H,W,3] (a fresh tensor)."""
+        runs the batch, resizes each generated crop to its box and pastes it into a copy of its frame (with `blend`: blends it
+        in, w2l_resize_blend_u8).  Returns torch uint8 [n,H,W,3] (a fresh tensor)."""
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_cuda:
             raise RuntimeError("run_frames: frames must be a uint8 [F,H,W,3] tensor on the HIP device")
         frames = frames.contiguous()
@@ -244,8 +332,12 @@ class Wav2LipRunner:
         pred = self.run_batch(faces, mel_windows=mel_windows, mel=mel, starts=starts)
         out = frames.index_select(0, idx_dev.long())            # frame_batch copies (inference.py:131)
         max_px = max((y2 - y1) * (x2 - x1) for y1, y2, x1, x2 in boxes)
-        check(self.lib.w2l_resize_paste_u8(s, n, ptr(pred), img_size, ptr(boxes_dev), None, ptr(out), H, W, max_px),
-              "resize_paste_u8")
+        if self.blend is None:
+            check(self.lib.w2l_resize_paste_u8(s, n, ptr(pred), img_size, ptr(boxes_dev), None, ptr(out), H, W, max_px),
+                  "resize_paste_u8")
+        else:
+            check(self.lib.w2l_resize_blend_u8(s, n, ptr(pred), img_size, ptr(boxes_dev), None, ptr(out), H, W, max_px,
+                                               self.blend[0], blend_top_q8(self.blend[1])), "resize_blend_u8")
         return out
 
 
@@ -256,8 +348,8 @@ class PipelinedRunner:
     ticket; `result(ticket)` makes the caller's stream wait for that batch and returns its uint8 frames (valid until the lane is
     reused `depth` submits later)."""
 
-    def __init__(self, model, batch_size=128, depth=2, precision="f32"):
-        self.lanes = [Wav2LipRunner(model, batch_size, lane=k, precision=precision) for k in range(depth)]
+    def __init__(self, model, batch_size=128, depth=2, precision="f32", blend=None):
+        self.lanes = [Wav2LipRunner(model, batch_size, lane=k, precision=precision, **_blend_kw(blend)) for k in range(depth)]
         dev = self.lanes[0].device
         self.streams = [torch.cuda.Stream(device=dev) for _ in range(depth)]
         self.depth = depth
@@ -413,9 +505,12 @@ def _precision_kw(precision):
     return {} if check_precision(precision) == "f32" else {"precision": precision}
 
 
-def lipsync(model, frames, wav, fps=25., batch_size=128, static=False, box=None, ranks=None, depth=None, precision="f32"):
+def lipsync(model, frames, wav, fps=25., batch_size=128, static=False, box=None, ranks=None, depth=None, precision="f32",
+            blend=None):
     """End-to-end body of inference.py:main for in-memory inputs: returns the list of output frames (uint8).
     `precision`: "f32" (default) or "bf16" - the generator's arithmetic (Wav2LipRunner); everything else is the same.
+    `blend`: None (default, the reference's paste) or (feather, top), the feathered mouth-region paste (`check_blend`).  It is a
+    device paste: frames of one shape and a `box` (a 96x96 one included); anything else raises ValueError before any device work.
 
     `ranks` (sharding.init_from_env(), one process per GPU): the mel chunks are cut into contiguous per-rank shards
     (sharding.shard_range), every rank runs ITS chunks through its own runner with the replicated weights, and the generated
@@ -423,6 +518,10 @@ def lipsync(model, frames, wav, fps=25., batch_size=128, static=False, box=None,
     rank returns None (the reference's loop, inference.py:249-272, is single-process)."""
     from .models.wav2lip import check_precision
     check_precision(precision)
+    blend = check_blend(blend)
+    if blend is not None and (box is None or len({tuple(f.shape) for f in frames}) != 1):
+        raise ValueError("blend=%r needs the device paste: frames of one shape and a `box`; the host paste of pre-sized faces has "
+                         "no blend" % (blend,))
     dev = next(model.parameters()).device
     mel = audio.melspectrogram_device(wav, dev)
     if bool(torch.isnan(mel).any()):
@@ -434,15 +533,15 @@ def lipsync(model, frames, wav, fps=25., batch_size=128, static=False, box=None,
     from . import sharding
     first, last = sharding.shard_range(len(starts), rank, world)
     # later batches are enqueued before batch i is collected; the default precision constructs the runner exactly as before
-    runner = PipelinedRunner(model, batch_size, depth=depth or LIPSYNC_DEPTH, **_precision_kw(precision))
+    runner = PipelinedRunner(model, batch_size, depth=depth or LIPSYNC_DEPTH, **_precision_kw(precision), **_blend_kw(blend))
     out_frames = []
     starts_dev = torch.tensor(starts, dtype=torch.int32, device=dev)
     shapes = {tuple(f.shape) for f in frames}
     if world > 1 and len(shapes) != 1:
         raise ValueError("sharded inference gathers frames of ONE shape (a video); got %d shapes" % len(shapes))
     pending = []
-    if len(shapes) == 1 and box is not None and (box[1] - box[0], box[3] - box[2]) != (img_size, img_size):
-        # faces that need resizing: keep the frames on the device, crop/resize/paste there (inference.py:121-126, 270-271)
+    if len(shapes) == 1 and box is not None and (blend is not None or (box[1] - box[0], box[3] - box[2]) != (img_size, img_size)):
+        # faces that need resizing (or blending): keep the frames on the device, crop/resize/paste there (inference.py:121-126, 270-271)
         frames_dev = torch.from_numpy(np.stack(frames)).to(dev)
         for lo in range(first, last, batch_size):
             n = min(batch_size, last - lo)
@@ -644,8 +743,9 @@ def main(argv=None, keep_frames=True, backend="nccl"):
     """inference.py:181-277 on the HIP path.  Same flags, same steps, same messages; differences, all on the file-format
     side: video input is the uncompressed AVI of wav2lip_amd/container.py (no codecs here), `--audio` must be a WAV (the
     reference shells out to ffmpeg for anything else), and the result - the reference's `temp/result.avi` + ffmpeg mux - is
-    written as ONE AVI (BGR video + the driving audio as PCM16) at `--outfile`.  Three flags the reference does not have, each
-    the reference's behaviour by default and independent: `--precision {fp32,bf16}` selects the generator's arithmetic,
+    written as ONE AVI (BGR video + the driving audio as PCM16) at `--outfile`.  Flags the reference does not have, each
+    the reference's behaviour by default and independent: `--blend_feather N` / `--blend_top FRACTION` blend the generated face
+    into the frame instead of pasting a rectangle (every rank of a sharded run pastes its own shard), `--precision {fp32,bf16}` selects the generator's arithmetic,
     `--face_det_precision {fp32,bf16}` the S3FD face detector's and `--face_det_scale K` the size of the frame it sees (1/K;
     the output keeps the input's size) - every rank of a sharded run detects its shard with both.
 
@@ -662,6 +762,7 @@ def main(argv=None, keep_frames=True, backend="nccl"):
     global args
     from . import sharding
     args = parse_args(argv)
+    blend = blend_from_args(args)
     mjpg = args.out_codec == "mjpg"
     if mjpg and not 1 <= args.out_quality <= 100:
         raise ValueError("--out_quality %d is outside [1, 100]" % args.out_quality)
@@ -697,7 +798,8 @@ def main(argv=None, keep_frames=True, backend="nccl"):
         idx = [0 if args.static else i % len(full_frames) for i in range(n)]
         boxes = [validate_boxes([coords[0 if args.static else j]], *full_frames[j].shape[:2])[0] for j in idx]
         starts_dev = torch.tensor(starts, dtype=torch.int32, device=dev)
-        runner = PipelinedRunner(model, args.wav2lip_batch_size, depth=LIPSYNC_DEPTH, **_precision_kw(CLI_PRECISION[args.precision]))
+        runner = PipelinedRunner(model, args.wav2lip_batch_size, depth=LIPSYNC_DEPTH, **_precision_kw(CLI_PRECISION[args.precision]),
+                                 **_blend_kw(blend))
         bs = args.wav2lip_batch_size
         first, last = sharding.shard_range(n, ranks.rank, ranks.world)
         frame_h, frame_w = full_frames[0].shape[:2]

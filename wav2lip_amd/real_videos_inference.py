@@ -85,10 +85,12 @@ def build_cli_parser():
 
 def build_main_parser():
     """what `main()` parses: `build_cli_parser` plus `--face_det_scale K`, the size of the frame the detector sees
-    (`inference.add_det_scale_flag`); `cli_parser` stays the reference's surface plus the two precision flags"""
-    from .inference import add_det_scale_flag
+    (`inference.add_det_scale_flag`), and `--blend_feather N` / `--blend_top FRACTION`, the blended paste
+    (`inference.add_blend_flags`); `cli_parser` stays the reference's surface plus the two precision flags"""
+    from .inference import add_blend_flags, add_det_scale_flag
     p = build_cli_parser()
     add_det_scale_flag(p)
+    add_blend_flags(p)
     return p
 
 
@@ -354,7 +356,8 @@ def run(args, lines, ranks, detector, model, report=None):
     sink = ResultSink(args.results_dir, tracks)
     try:
         multiclip.lipsync_many(model, clip_jobs(args, lines, ranks, detector, tracks, report), batch_size=args.wav2lip_batch_size,
-                               precision=inference.CLI_PRECISION[args.precision], sink=sink)
+                               precision=inference.CLI_PRECISION[args.precision], sink=sink,
+                               **inference._blend_kw(inference.blend_from_args(args)))
     finally:
         sink.close()
     return sink.written
@@ -365,6 +368,7 @@ def main(argv=None, state_dict=None, backend="nccl", report=None):
     group's.  Returns the line indices this rank wrote, in order."""
     from . import face_detection, inference, sharding
     args = main_parser.parse_args(argv)
+    inference.blend_from_args(args)              # a bad pair raises here, before the process group and any device work
     if args.mode not in MODES:
         raise ValueError("--mode must be one of random | dubbed | tts")
     args.img_size = 96

@@ -789,9 +789,11 @@ class LipsyncStreams:
     `drain` returns).  `on_batch(rows)` receives each launched batch's [(key, row index)] including the padding rows."""
 
     def __init__(self, model, batch_size=128, depth=None, precision="f32", fps=25., sink=None, on_batch=None, mel_window=1024,
-                 detector=None, pads=(0, 10, 0, 0), smooth_T=5, face_det_batch_size=16, resample_buffer=1 << 16):
+                 detector=None, pads=(0, 10, 0, 0), smooth_T=5, face_det_batch_size=16, resample_buffer=1 << 16, blend=None):
+        from .inference import check_blend
         from .models.wav2lip import check_precision
         self.precision = check_precision(precision)
+        self.blend = check_blend(blend)                  # None, or (feather, top): every frame's face is blended in
         if batch_size < 1:
             raise ValueError("batch_size must be at least 1")
         if mel_window < MIN_WINDOW:
@@ -914,7 +916,8 @@ class LipsyncStreams:
     # ---- the tick
     def _backend(self):
         if self._runner is None:
-            self._runner = BatchRunner(self.model, self.batch_size, self.depth, self.precision)
+            from .inference import _blend_kw
+            self._runner = BatchRunner(self.model, self.batch_size, self.depth, self.precision, **_blend_kw(self.blend))
             self._mel = DeviceMel(self._runner.device)
         if self._boxes is None and self.detector is not None:
             self._boxes = DeviceBoxes(self._runner.device, self.detector, self.pads, self.smooth_T, self.face_det_batch_size)
@@ -1096,8 +1099,9 @@ def build_parser():
                    help='Feed the frames of every video as they become due with the audio and detect faces as they arrive')
     p.add_argument('--native_rate', default=False, action='store_true',
                    help="Feed every WAV at the file's own rate and format; it is converted to 16 kHz on the device as it streams")
-    from .inference import add_det_scale_flag
+    from .inference import add_blend_flags, add_det_scale_flag
     add_det_scale_flag(p)
+    add_blend_flags(p)
     return p
 
 
@@ -1114,6 +1118,7 @@ def main(argv=None, state_dict=None):
 
     from . import audio, inference
     a = build_parser().parse_args(argv)
+    blend = inference.blend_from_args(a)
     if len(a.face) != len(a.audio):
         raise ValueError("%d --face for %d --audio: pass them in pairs" % (len(a.face), len(a.audio)))
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -1162,7 +1167,8 @@ def main(argv=None, state_dict=None):
             inference.write_result(j["out"], got.pop(key), j["fps"], j["audio"])
 
     streams = LipsyncStreams(model, batch_size=a.wav2lip_batch_size, precision=inference.CLI_PRECISION[a.precision], sink=sink,
-                             detector=detector, pads=a.pads, smooth_T=0 if a.nosmooth else 5, face_det_batch_size=a.face_det_batch_size)
+                             detector=detector, pads=a.pads, smooth_T=0 if a.nosmooth else 5, face_det_batch_size=a.face_det_batch_size,
+                             **inference._blend_kw(blend))
     for j in jobs:
         if j["live"]:
             streams.open_live(j["key"], fps=j["fps"], sample_rate=j["rate"])
