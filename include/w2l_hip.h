@@ -41,6 +41,8 @@
  *   w2l_face_boxes_segments  evaluation/gen_videos_from_filelist.py:35-42, :61-77 = inference.py:59-66, :90-104 (pads, clipping,
  *                         "Face not detected", get_smoothened_boxes) for every clip of a group in one launch
  *   w2l_face_boxes_stream  inference.py:59-66, :90-104 for live streams: the same boxes, written tick by tick as frames arrive
+ *   w2l_face_boxes_runs, w2l_face_boxes_stream_runs  the two above with frames without a face passed through (opt-in, not the
+ *                         reference's: `no_face_hold`)
  *   w2l_melspectrogram    audio.py:45-51 (preemphasis, STFT, mel basis, dB, normalise)
  *   w2l_mel_gather        inference.py:231-240 (16-frame mel windows at host-computed starts)
  *   w2l_resample_sinc     audio.py:9-10 (librosa.core.load's sample-rate conversion: resampy 'kaiser_best' sinc interpolation)
@@ -552,6 +554,36 @@ typedef struct {
 int w2l_face_boxes_stream(void* stream, int n_seg, const w2l_box_stream_segment* segs_host, const w2l_box_stream_segment* segs,
                           const int32_t* rects, const int32_t* flags, int n_rows, int32_t* carry, int n_slots, int top, int bottom,
                           int left, int right, int T, int32_t* boxes, int n_out, int32_t* status);
+
+/* The two finishes above with the opt-in pass-through for frames without a face (`no_face_hold`; not the
+ * reference's behaviour).  A row flagged 0 no longer decides its clip.  With hold in 0..250:
+ *   - a detected frame is BOXED with its own rect; an undetected frame i is boxed with the raw rect of the last detected frame
+ *     p < i while i - p <= hold; any other frame (every frame before the first detection too) is a GAP.  The hold looks back only.
+ *   - maximal sequences of boxed frames are runs, and each run is finished exactly as w2l_face_boxes_segments finishes a clip
+ *     that consists of the run's frames alone: pads, clipping, then get_smoothened_boxes over the run.
+ * valid [R] is 1 for a boxed row and 0 for a gap row, whose box is zeros.  A clip with no undetected frame is one run: its boxes
+ * are w2l_face_boxes_segments' bytes.
+ *
+ * w2l_face_boxes_runs takes w2l_face_boxes_segments' table and arenas of n_rows rows.  status [n_seg][2]: (2, row) when a row
+ * is flagged neither found nor none (boxes and valid of the segment zeros), (3, 0) for a segment with rows outside
+ * [0, n_rows) - nothing of it is read or written - else (0, 0); code 1 does not occur.  Refused: a NULL pointer, n_seg < 1,
+ * n_rows < 0, T outside 0..64, hold outside 0..250, a misaligned table.
+ *
+ * w2l_face_boxes_stream_runs is the per-tick form, with w2l_face_boxes_stream's table, checks, status (code 1 does not occur) and
+ * range: the frames a tick writes are the same [max(0, seen - T + 1), closed ? n : max(0, n - T + 1)) (T = 0 as T = 1), so a gap
+ * frame leaves in the tick in which a boxed one would.  A boxed frame of the range takes the forward mean when its next T - 1
+ * frames are boxed, else the tail rule of its run, whose end b is then known (frame b is a gap, or the video is closed).  A run may
+ * have ended up to T - 2 frames before the tick's first new frame and its tail reads raw rows back to b - T, so the carry holds
+ * the last 2 * max(T, 1) frames: carry [n_slots][644] int32, a slot being 128 rows of (x1, y1, x2, y2, boxed) - the held-filled
+ * raw rect, zeros for a gap - of which the first min(seen, 2 * max(T, 1)) are in use, oldest first, then 4 words: the number
+ * of frames since the last detected one (0 when the last frame was detected; 251 for anything above 250 and before the first
+ * detection), and three zeros.  The boxes and valid of a stream, tick after tick, are w2l_face_boxes_runs' of the finished video
+ * however it was cut.  valid rows [out0, out0 + count) lie beside the box rows. */
+int w2l_face_boxes_runs(void* stream, int n_seg, const w2l_box_segment* segs, const int32_t* rects, const int32_t* flags, int n_rows,
+                        int top, int bottom, int left, int right, int T, int hold, int32_t* boxes, int32_t* valid, int32_t* status);
+int w2l_face_boxes_stream_runs(void* stream, int n_seg, const w2l_box_stream_segment* segs_host, const w2l_box_stream_segment* segs,
+                               const int32_t* rects, const int32_t* flags, int n_rows, int32_t* carry, int n_slots, int top, int bottom,
+                               int left, int right, int T, int hold, int32_t* boxes, int32_t* valid, int n_out, int32_t* status);
 
 /* The opt-in bf16-storage detector (face_detection/s3fd.py, precision="bf16"): the backbone convolutions are w2l_convb layers
  * (scale 1, shift = bias, ReLU); these are the ops between them and the fused detection head.  Tensors are NHWC bf16 with channel

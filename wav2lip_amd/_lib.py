@@ -221,6 +221,8 @@ SIGNATURES = {
     "w2l_s3fd_first_rect_scaled": (_i, [_vp, _i, _i, _vp, _vp, _vp, _f, _f, _f, _vp, _vp]),
     "w2l_face_boxes_segments": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "w2l_face_boxes_stream": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "w2l_face_boxes_runs": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "w2l_face_boxes_stream_runs": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "w2l_s3fd_pack_bf16": (_i, [_vp, _ll, _vp, _vp, _i]),
     "w2l_s3fd_pack_rows_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp, _i]),
     "w2l_s3fd_pack_rows_scaled_bf16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i]),

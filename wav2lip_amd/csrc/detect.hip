@@ -13,6 +13,7 @@
 //   w2l_face_boxes_segments  inference.py:59-66, :90-104 / gen_videos_from_filelist.py:35-42, :61-77  pads, clipping, temporal
 //                       smoothing and "no face" of many clips in one launch
 //   w2l_face_boxes_stream  the same finish for LIVE streams, tick by tick: a box is written once the T - 1 frames after it are there
+//   w2l_face_boxes_runs, w2l_face_boxes_stream_runs  the two finishes with frames without a face passed through (opt-in)
 // All HBM-bound, NHWC, float4 where the channel count allows.
 #include "w2l_common.h"
 #include "resize_px.h"
@@ -574,6 +575,211 @@ __global__ __launch_bounds__(64) void face_boxes_stream_kernel(const BoxStreamSe
     }
 }
 
+// ---- the opt-in pass-through for frames without a face: the two finishes above with "no face" as a state of a
+// frame instead of the end of its clip.  One rule for both forms:
+//   hold   an undetected frame i takes the raw rect of the last detected frame p < i while i - p <= hold (it is BOXED, as a
+//          detected frame is); else, and before the first detection, it is a GAP: box zeros, valid 0.
+//   runs   maximal sequences of boxed frames; each is finished as face_boxes_segments_kernel finishes a clip of those frames alone.
+// A wave walks its frames in chunks of 64 with three chunks of held-filled rows (x1, y1, x2, y2, boxed) in an LDS ring: the fill of a
+// chunk is a max-scan for "last detected frame" continued from the chunk before; a boxed frame i whose next T - 1 frames are all
+// boxed takes the forward mean of raw rows (those reach into the next chunk), any other boxed frame lies in the tail of its run,
+// and the tail of a run that ends at b (frame b is a gap, or the end of a closed video) reads raw rows back to b - T (those reach
+// into the chunk before) and runs in order, one lane per coordinate.  T = 0 is T = 1 here: the truncated mean of one integer.
+// The stream form holds the frames [seen - min(seen, 2T), seen) in its carry slot: a run may have ended up to T - 2 frames before
+// the tick's first new frame and its tail then reads back to seen - 2T + 2.
+constexpr int kHoldMax = 250;                            // frames a rect is held for at the most
+constexpr int kRunsCarryRows = 2 * kBoxMaxT;             // rows of a slot: (x1, y1, x2, y2, boxed) of the last 2 * max(T, 1) frames
+constexpr int kRunsCarryInts = kRunsCarryRows * 5 + 4;   // then (frames since the last detection, capped at kHoldMax + 1; 0; 0; 0)
+constexpr int kRunsRing = 3 * 64;
+
+// One segment.  Frames [f0, n) with f0 = seen - c: the c carried rows (s_carry), then rows of the arenas (rc, fl: frame `seen` is
+// their row 0).  Writes boxes and valid of the frames [lo, hi) at bx / vd (frame lo is row 0 there).  Afterwards the ring holds
+// the last three chunks and *p_out the last detected frame (-1: none within reach).
+template <class Seg>
+__device__ __forceinline__ void face_boxes_runs_wave(const Seg& s, const int* __restrict__ rc, const int* __restrict__ fl, int seen,
+                                                     long long n, bool closed, int c, int dist0, int top, int bottom, int left,
+                                                     int right, int Tm, int hold, long long lo, long long hi, int* __restrict__ bx,
+                                                     int* __restrict__ vd, const int (*s_carry)[5], int (*s_ring)[5],
+                                                     int (*s_win)[4], long long* p_out) {
+    const int lane = threadIdx.x;
+    const long long f0 = (long long)seen - c;
+    long long p = (c > 0 && s_carry[c - 1][4] != 0 && dist0 <= hold && seen - 1 - dist0 >= 0) ? (long long)seen - 1 - dist0 : -1;
+    const int nch = (int)((n - f0 + 63) / 64);
+    auto fill = [&](int k) {                             // chunk k into its third of the ring; every lane takes part in the scan
+        const long long g0 = f0 + 64ll * k, i = g0 + lane;
+        int v = (i >= seen && i < n && fl[i - seen] == kRectFound) ? lane : -1;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(v, o);
+            if (lane >= o) v = max(v, t);
+        }
+        const long long pl = v >= 0 ? g0 + v : p;        // the last detected frame at or before i
+        int r[5] = {0, 0, 0, 0, 0};
+        if (i < seen) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) r[q] = s_carry[i - f0][q];
+            r[4] = s_carry[i - f0][4] != 0;
+        } else if (i < n && pl >= 0 && i - pl <= hold) {
+            const int* src = pl >= seen ? rc + (pl - seen) * 4 : &s_carry[c - 1][0];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) r[q] = src[q];
+            r[4] = 1;
+        }
+        int* dst = s_ring[(64 * k + lane) % kRunsRing];
+#pragma unroll
+        for (int q = 0; q < 5; ++q) dst[q] = r[q];
+        const int vl = __shfl(v, 63);
+        if (vl >= 0) p = g0 + vl;
+    };
+    auto row = [&](long long i) -> const int* { return s_ring[(int)((i - f0) % kRunsRing)]; };
+    auto boxed = [&](long long i) -> bool { return i >= f0 && i < n && row(i)[4] != 0; };
+    if (nch > 0) fill(0);
+    for (int k = 0; k < nch; ++k) {
+        if (k + 1 < nch) fill(k + 1);
+        __syncthreads();
+        const long long g0 = f0 + 64ll * k;
+        {                                                // gap rows, and the boxed rows with T boxed rows from them on
+            const long long i = g0 + lane;
+            if (i >= lo && i < hi) {
+                int* o = bx + (i - lo) * 4;
+                const bool me = boxed(i);
+                vd[i - lo] = me;
+                bool all = me;
+                for (int j = 1; j < Tm && all; ++j) all = boxed(i + j);
+                if (!me) o[0] = o[1] = o[2] = o[3] = 0;
+                else if (all) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        long long sum = 0;
+                        for (int j = 0; j < Tm; ++j) sum += padded_coord(row(i + j), q, s, top, bottom, left, right);
+                        o[q] = trunc_mean(sum, Tm);
+                    }
+                }
+            }
+        }
+        // the runs that end at b in (g0, g0 + 64] and have a row to write: frame b - 1 is boxed and frame b is a gap or the end
+        const long long b_mine = g0 + 1 + lane;
+        unsigned long long ends = __ballot(b_mine <= n && b_mine - 1 >= lo && boxed(b_mine - 1) && (b_mine == n ? closed : !boxed(b_mine)));
+        while (ends != 0ull) {                           // uniform
+            const long long b = g0 + __ffsll((long long)ends);
+            ends &= ends - 1;
+            const unsigned long long gaps = __ballot(lane < Tm && !boxed(b - 1 - lane));
+            // the run's length where it is shorter than T: Python's boxes[len - T:] then wraps to max(0, 2 * len - T)
+            const int len = gaps != 0ull ? __ffsll((long long)gaps) - 1 : Tm;
+            const long long seq0 = b - len;              // rows from here on run in order
+            const long long ws = gaps != 0ull ? seq0 + max(0, 2 * len - Tm) : seq0;
+            const int L = (int)(b - ws);                 // 1 <= L <= T <= kBoxMaxT
+            __syncthreads();                             // the window of the run before this one has been read
+            if (lane < L) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) s_win[lane][q] = padded_coord(row(ws + lane), q, s, top, bottom, left, right);
+            }
+            __syncthreads();
+            if (lane < 4) {
+                for (long long i = seq0; i < b; ++i) {
+                    long long sum = 0;
+                    for (int j = 0; j < L; ++j) sum += s_win[j][lane];
+                    const int mean = trunc_mean(sum, L);
+                    if (i >= ws) s_win[i - ws][lane] = mean;
+                    if (i >= lo && i < hi) bx[(i - lo) * 4 + lane] = mean;      // the others went out, or go out, in another tick
+                }
+            }
+        }
+        __syncthreads();                                 // the next fill overwrites the chunk before this one
+    }
+    *p_out = p;
+}
+
+// the first row of [0, n) whose flag is neither found nor none (0x7fffffff: none), the same on every lane
+__device__ __forceinline__ int first_host_row(const int* __restrict__ fl, int n) {
+    int first = 0x7fffffff;
+    for (int i = threadIdx.x; i < n; i += 64) {
+        const int f = fl[i];
+        if (f != kRectFound && f != kRectNone) first = min(first, i);
+    }
+    for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o));
+    return first;
+}
+
+__global__ __launch_bounds__(64) void face_boxes_runs_kernel(const BoxSeg* __restrict__ segs, const int* __restrict__ rects,
+                                                             const int* __restrict__ flags, int n_rows, int top, int bottom, int left,
+                                                             int right, int T, int hold, int* __restrict__ boxes,
+                                                             int* __restrict__ valid, int* __restrict__ status) {
+    __shared__ int s_ring[kRunsRing][5];
+    __shared__ int s_win[kBoxMaxT][4];
+    const int lane = threadIdx.x;
+    const BoxSeg s = segs[blockIdx.x];
+    int* st = status + 2 * (long long)blockIdx.x;
+    if (s.n <= 0 || s.row0 < 0 || (long long)s.row0 + s.n > n_rows) {       // uniform: a segment outside the arenas is not followed
+        if (lane == 0) { st[0] = s.n <= 0 ? 0 : kBoxStreamBadSegment; st[1] = 0; }
+        return;
+    }
+    const int* fl = flags + s.row0;
+    int* bx = boxes + (long long)s.row0 * 4;
+    int* vd = valid + s.row0;
+    const int host = first_host_row(fl, s.n);
+    if (host != 0x7fffffff) {                            // uniform: left to the host, as face_boxes_segments_kernel leaves it
+        for (int i = lane; i < 4 * s.n; i += 64) bx[i] = 0;
+        for (int i = lane; i < s.n; i += 64) vd[i] = 0;
+        if (lane == 0) { st[0] = 2; st[1] = host; }
+        return;
+    }
+    if (lane == 0) { st[0] = 0; st[1] = 0; }
+    long long p;
+    face_boxes_runs_wave(s, rects + (long long)s.row0 * 4, fl, 0, s.n, true, 0, kHoldMax + 1, top, bottom, left, right, max(T, 1), hold,
+                         0, s.n, bx, vd, nullptr, s_ring, s_win, &p);
+}
+
+__global__ __launch_bounds__(64) void face_boxes_stream_runs_kernel(const BoxStreamSeg* __restrict__ segs, const int* __restrict__ rects,
+                                                                    const int* __restrict__ flags, int n_rows, int* __restrict__ carry,
+                                                                    int n_slots, int top, int bottom, int left, int right, int T,
+                                                                    int hold, int* __restrict__ boxes, int* __restrict__ valid,
+                                                                    int n_out, int* __restrict__ status) {
+    __shared__ int s_carry[kRunsCarryRows][5];
+    __shared__ int s_ring[kRunsRing][5];
+    __shared__ int s_win[kBoxMaxT][4];
+    const int lane = threadIdx.x;
+    const BoxStreamSeg s = segs[blockIdx.x];
+    int* st = status + 2 * (long long)blockIdx.x;
+    // the launcher checked the host copy of the table; a device copy that says otherwise is not followed
+    const long long n = (long long)s.seen + s.n_new;
+    bool bad = s.n_new < 0 || s.seen < 0 || s.slot < 0 || s.slot >= n_slots || s.row0 < 0 || (long long)s.row0 + s.n_new > n_rows ||
+               n > 0x7fffffffll || s.out0 < 0;
+    const int Tm = max(T, 1);
+    long long lo = 0, hi = 0;
+    if (!bad) {
+        box_stream_range(s.seen, n, s.closed, Tm, &lo, &hi);
+        bad = s.out0 + (hi - lo) > n_out;
+    }
+    if (bad) {                                           // uniform
+        if (lane == 0) { st[0] = kBoxStreamBadSegment; st[1] = 0; }
+        return;
+    }
+    const int* fl = flags + s.row0;
+    const int host = first_host_row(fl, s.n_new);
+    if (host != 0x7fffffff) {                            // uniform: no box written, the carry left as it was
+        if (lane == 0) { st[0] = 2; st[1] = s.seen + host; }
+        return;
+    }
+    if (lane == 0) { st[0] = 0; st[1] = 0; }
+    const int c = min(s.seen, 2 * Tm);                   // carried rows: frames [seen - c, seen)
+    int* slot = carry + (long long)s.slot * kRunsCarryInts;
+    for (int i = lane; i < c * 5; i += 64) s_carry[i / 5][i % 5] = slot[i];
+    const int dist0 = min(max(slot[kRunsCarryRows * 5], 0), kHoldMax + 1);
+    __syncthreads();
+    long long p;
+    face_boxes_runs_wave(s, rects + (long long)s.row0 * 4, fl, s.seen, n, s.closed != 0, c, s.seen > 0 ? dist0 : kHoldMax + 1, top,
+                         bottom, left, right, Tm, hold, lo, hi, boxes + (long long)s.out0 * 4, valid + s.out0, s_carry, s_ring, s_win,
+                         &p);
+    // the next tick's carry: the last min(n, 2 * max(T, 1)) rows, which the ring still holds, and the distance from the detection
+    const int keep = (int)min(n, (long long)(2 * Tm));
+    const long long f0 = (long long)s.seen - c;
+    for (int i = lane; i < keep * 5; i += 64) slot[i] = s_ring[(int)((n - keep + i / 5 - f0) % kRunsRing)][i % 5];
+    if (lane == 0) {
+        const long long d = p >= s.seen ? n - 1 - p : (long long)(s.seen > 0 ? dist0 : kHoldMax + 1) + s.n_new;
+        slot[kRunsCarryRows * 5] = (int)min(d, (long long)(kHoldMax + 1));
+    }
+}
+
 constexpr int kPackScaledGridCap = 1024;      // workgroups per image of the reduced-resolution pack, as its row-table siblings
 
 static inline int grid1d(long long work, int block, int cap = 16384) {
@@ -725,6 +931,33 @@ int w2l_face_boxes_segments(void* stream, int n_seg, const w2l_box_segment* segs
     return W2L_OK;
 }
 
+// the checks of a tick's segment table on its host copy, shared by the two stream finishes (`name` opens the messages)
+static int box_stream_table_check(const char* name, int n_seg, const w2l_box_stream_segment* segs_host, int n_rows, int n_slots, int T,
+                                  int n_out) {
+    // a tick has a segment per live stream: the pairwise checks below are a few thousand comparisons, and allocate nothing
+    for (int k = 0; k < n_seg; ++k) {
+        const w2l_box_stream_segment& s = segs_host[k];
+        W2L_REQUIRE(s.n_new >= 0 && s.seen >= 0, "%s: segment %d: n_new=%d and seen=%d must not be negative", name, k, s.n_new, s.seen);
+        W2L_REQUIRE((long long)s.seen + s.n_new <= 0x7fffffffll, "%s: segment %d: more than 2^31 - 1 frames", name, k);
+        W2L_REQUIRE(s.slot >= 0 && s.slot < n_slots, "%s: segment %d: slot %d outside [0, %d)", name, k, s.slot, n_slots);
+        W2L_REQUIRE(s.row0 >= 0 && (long long)s.row0 + s.n_new <= n_rows, "%s: segment %d: rows [%d, %d + %d) outside the %d arena rows",
+                    name, k, s.row0, s.row0, s.n_new, n_rows);
+        long long lo, hi;
+        box_stream_range(s.seen, (long long)s.seen + s.n_new, s.closed, T, &lo, &hi);
+        W2L_REQUIRE(s.out0 >= 0 && s.out0 + (hi - lo) <= n_out, "%s: segment %d: output rows [%d, %d + %lld) outside the %d rows", name,
+                    k, s.out0, s.out0, hi - lo, n_out);
+        for (int j = 0; j < k; ++j) {
+            const w2l_box_stream_segment& o = segs_host[j];      // checked above: its counts are in range
+            W2L_REQUIRE(o.slot != s.slot, "%s: segments %d and %d name carry slot %d", name, j, k, s.slot);
+            long long olo, ohi;
+            box_stream_range(o.seen, (long long)o.seen + o.n_new, o.closed, T, &olo, &ohi);
+            W2L_REQUIRE(hi == lo || ohi == olo || s.out0 + (hi - lo) <= o.out0 || o.out0 + (ohi - olo) <= s.out0,
+                        "%s: the output rows of segments %d and %d overlap", name, j, k);
+        }
+    }
+    return W2L_OK;
+}
+
 int w2l_face_boxes_stream(void* stream, int n_seg, const w2l_box_stream_segment* segs_host, const w2l_box_stream_segment* segs,
                           const int32_t* rects, const int32_t* flags, int n_rows, int32_t* carry, int n_slots, int top, int bottom,
                           int left, int right, int T, int32_t* boxes, int n_out, int32_t* status) {
@@ -733,31 +966,42 @@ int w2l_face_boxes_stream(void* stream, int n_seg, const w2l_box_stream_segment*
     W2L_REQUIRE(T >= 0 && T <= kBoxMaxT, "face_boxes_stream: T=%d outside 0..%d", T, kBoxMaxT);
     W2L_REQUIRE(n_rows >= 0 && n_slots >= 1 && n_out >= 0, "face_boxes_stream: n_rows=%d, n_slots=%d, n_out=%d", n_rows, n_slots, n_out);
     W2L_REQUIRE((reinterpret_cast<uintptr_t>(segs) & 15) == 0, "face_boxes_stream: the segment table must be 16-byte aligned");
-    // a tick has a segment per live stream: the pairwise checks below are a few thousand comparisons, and allocate nothing
-    for (int k = 0; k < n_seg; ++k) {
-        const w2l_box_stream_segment& s = segs_host[k];
-        W2L_REQUIRE(s.n_new >= 0 && s.seen >= 0, "face_boxes_stream: segment %d: n_new=%d and seen=%d must not be negative", k,
-                    s.n_new, s.seen);
-        W2L_REQUIRE((long long)s.seen + s.n_new <= 0x7fffffffll, "face_boxes_stream: segment %d: more than 2^31 - 1 frames", k);
-        W2L_REQUIRE(s.slot >= 0 && s.slot < n_slots, "face_boxes_stream: segment %d: slot %d outside [0, %d)", k, s.slot, n_slots);
-        W2L_REQUIRE(s.row0 >= 0 && (long long)s.row0 + s.n_new <= n_rows, "face_boxes_stream: segment %d: rows [%d, %d + %d) outside the %d arena rows",
-                    k, s.row0, s.row0, s.n_new, n_rows);
-        long long lo, hi;
-        box_stream_range(s.seen, (long long)s.seen + s.n_new, s.closed, T, &lo, &hi);
-        W2L_REQUIRE(s.out0 >= 0 && s.out0 + (hi - lo) <= n_out, "face_boxes_stream: segment %d: output rows [%d, %d + %lld) outside the %d rows",
-                    k, s.out0, s.out0, hi - lo, n_out);
-        for (int j = 0; j < k; ++j) {
-            const w2l_box_stream_segment& o = segs_host[j];      // checked above: its counts are in range
-            W2L_REQUIRE(o.slot != s.slot, "face_boxes_stream: segments %d and %d name carry slot %d", j, k, s.slot);
-            long long olo, ohi;
-            box_stream_range(o.seen, (long long)o.seen + o.n_new, o.closed, T, &olo, &ohi);
-            W2L_REQUIRE(hi == lo || ohi == olo || s.out0 + (hi - lo) <= o.out0 || o.out0 + (ohi - olo) <= s.out0,
-                        "face_boxes_stream: the output rows of segments %d and %d overlap", j, k);
-        }
-    }
+    if (int e = box_stream_table_check("face_boxes_stream", n_seg, segs_host, n_rows, n_slots, T, n_out)) return e;
     hipLaunchKernelGGL(face_boxes_stream_kernel, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const BoxStreamSeg*>(segs), rects, flags, n_rows, carry, n_slots, top, bottom, left, right, T,
                        boxes, n_out, status);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_face_boxes_runs(void* stream, int n_seg, const w2l_box_segment* segs, const int32_t* rects, const int32_t* flags, int n_rows,
+                        int top, int bottom, int left, int right, int T, int hold, int32_t* boxes, int32_t* valid, int32_t* status) {
+    W2L_REQUIRE(segs && rects && flags && boxes && valid && status, "face_boxes_runs: NULL argument");
+    W2L_REQUIRE(n_seg >= 1 && n_rows >= 0, "face_boxes_runs: n_seg=%d must be at least 1 and n_rows=%d at least 0", n_seg, n_rows);
+    W2L_REQUIRE(T >= 0 && T <= kBoxMaxT, "face_boxes_runs: T=%d outside 0..%d", T, kBoxMaxT);
+    W2L_REQUIRE(hold >= 0 && hold <= kHoldMax, "face_boxes_runs: hold=%d outside 0..%d", hold, kHoldMax);
+    W2L_REQUIRE((reinterpret_cast<uintptr_t>(segs) & 15) == 0, "face_boxes_runs: the segment table must be 16-byte aligned");
+    hipLaunchKernelGGL(face_boxes_runs_kernel, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const BoxSeg*>(segs), rects, flags, n_rows, top, bottom, left, right, T, hold, boxes, valid,
+                       status);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_face_boxes_stream_runs(void* stream, int n_seg, const w2l_box_stream_segment* segs_host, const w2l_box_stream_segment* segs,
+                               const int32_t* rects, const int32_t* flags, int n_rows, int32_t* carry, int n_slots, int top, int bottom,
+                               int left, int right, int T, int hold, int32_t* boxes, int32_t* valid, int n_out, int32_t* status) {
+    W2L_REQUIRE(segs_host && segs && rects && flags && carry && boxes && valid && status, "face_boxes_stream_runs: NULL argument");
+    W2L_REQUIRE(n_seg >= 1, "face_boxes_stream_runs: n_seg=%d must be at least 1", n_seg);
+    W2L_REQUIRE(T >= 0 && T <= kBoxMaxT, "face_boxes_stream_runs: T=%d outside 0..%d", T, kBoxMaxT);
+    W2L_REQUIRE(hold >= 0 && hold <= kHoldMax, "face_boxes_stream_runs: hold=%d outside 0..%d", hold, kHoldMax);
+    W2L_REQUIRE(n_rows >= 0 && n_slots >= 1 && n_out >= 0, "face_boxes_stream_runs: n_rows=%d, n_slots=%d, n_out=%d", n_rows, n_slots,
+                n_out);
+    W2L_REQUIRE((reinterpret_cast<uintptr_t>(segs) & 15) == 0, "face_boxes_stream_runs: the segment table must be 16-byte aligned");
+    if (int e = box_stream_table_check("face_boxes_stream_runs", n_seg, segs_host, n_rows, n_slots, T, n_out)) return e;
+    hipLaunchKernelGGL(face_boxes_stream_runs_kernel, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const BoxStreamSeg*>(segs), rects, flags, n_rows, carry, n_slots, top, bottom, left, right, T,
+                       hold, boxes, valid, n_out, status);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

@@ -15,6 +15,10 @@ detector batches of ONE size:
 
 The last batch of a group is padded with copies of its last address; those rects fall into scratch rows behind the arena.  A run
 over clips of one frame shape therefore builds one detector graph.
+
+With `no_face_hold=G` (opt-in) the one launch is w2l_face_boxes_runs: a frame without a face keeps the last rect for
+up to G frames or becomes a gap frame, every run of boxed frames is finished as a clip of its own, and `valid [R]` comes back with
+the boxes.  `host_boxes_runs` is that rule on the host.
 """
 import collections
 
@@ -44,6 +48,93 @@ def host_boxes(rects, H, W, pads, T):
     if T:
         boxes = get_smoothened_boxes(boxes, T=T)
     return boxes
+
+
+MAX_HOLD = 250       # frames a rect is held over undetected frames at the most (w2l_face_boxes_runs' limit)
+
+
+def check_hold(no_face_hold):
+    """the `no_face_hold=` of `face_detect`, `detect_many` and `LipsyncStreams`: None (a frame without a face is the reference's
+    ValueError) or an int in 0..250, the number of undetected frames the last rect is held for before frames pass through.  Returns
+    None or the int; a ValueError names what is wrong."""
+    if no_face_hold is None:
+        return None
+    if isinstance(no_face_hold, bool) or not isinstance(no_face_hold, (int, np.integer)):
+        raise ValueError("no_face_hold must be None or an integer in 0..%d, got %r" % (MAX_HOLD, no_face_hold))
+    if not 0 <= no_face_hold <= MAX_HOLD:
+        raise ValueError("no_face_hold %d is outside 0..%d" % (no_face_hold, MAX_HOLD))
+    return int(no_face_hold)
+
+
+def hold_arg(text):
+    """argparse type of `--no_face_hold`: an integer in 0..250 (a parse error otherwise)"""
+    import argparse
+    try:
+        return check_hold(int(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def add_hold_flag(p):
+    """`--no_face_hold G` on a command's parser: absent by default (the reference's behaviour), independent of every other flag"""
+    p.add_argument('--no_face_hold', default=None, type=hold_arg, metavar='G',
+                   help='Do not stop at a frame without a face: keep the last detected box for up to G such frames (0..250), and '
+                        'pass frames beyond that through unchanged. Default: absent, a frame without a face is an error as in the '
+                        'reference. Not the reference\'s output')
+
+
+def hold_fill(rects, hold):
+    """the hold of the pass-through rule: rects with None for undetected frames -> the same list with an undetected
+    frame i given the rect of the last detected frame p < i while i - p <= hold; what stays None is a gap frame"""
+    out, last, at = [], None, 0
+    for i, r in enumerate(rects):
+        if r is not None:
+            last, at = r, i
+        out.append(last if last is not None and i - at <= hold else None)
+    return out
+
+
+def boxed_runs(valid):
+    """[a, b) of every maximal run of true entries"""
+    a, n = 0, len(valid)
+    while a < n:
+        b = a
+        while b < n and valid[b]:
+            b += 1
+        if b > a:
+            yield a, b
+        a = b + 1
+
+
+def host_boxes_runs(rects, H, W, pads, T, hold):
+    """`host_boxes` under the pass-through rule, what w2l_face_boxes_runs computes per segment: rects may hold None; after the hold
+    every maximal run of boxed frames is finished as `host_boxes` finishes a clip of those frames alone.  Returns (boxes int64
+    [n,4] of (y1, y2, x1, x2), zeros on gap rows; valid bool [n])."""
+    filled = hold_fill(rects, hold)
+    n = len(filled)
+    boxes, valid = np.zeros((n, 4), dtype=np.int64), np.array([r is not None for r in filled], dtype=bool).reshape(n)
+    for a, b in boxed_runs(valid):
+        boxes[a:b] = host_boxes(filled[a:b], H, W, pads, T)
+    return boxes, valid
+
+
+class RunBoxes:
+    """what `detect_many(..., no_face_hold=G)` yields for a clip: indexable per frame - `boxes[i]` is the int array (y1, y2, x1, x2)
+    or None for a gap frame - with the arrays behind it as `.boxes` (int64 [n,4], zeros on gap rows) and `.valid` (bool [n])"""
+
+    def __init__(self, boxes, valid):
+        self.boxes, self.valid = np.asarray(boxes, dtype=np.int64).reshape(-1, 4), np.asarray(valid, dtype=bool).reshape(-1)
+
+    def __len__(self):
+        return len(self.valid)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        return self.boxes[i] if self.valid[i] else None
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
 
 
 def _checked(job):
@@ -83,9 +174,18 @@ def _finish_segments(n_seg, segs, rects, flags, pads, T, boxes, status):
                                          ptr(boxes), ptr(status)), "face_boxes_segments")
 
 
-def _detect_group(detector, clips, pads, T, batch_size):
+def _finish_runs(n_seg, segs, rects, flags, n_rows, pads, T, hold, boxes, valid, status):
+    """w2l_face_boxes_runs: the group's clips in one launch under the pass-through rule"""
+    from .._lib import check, current_stream, load, ptr
+    top, bottom, left, right = pads
+    check(load().w2l_face_boxes_runs(current_stream(), n_seg, ptr(segs), ptr(rects), ptr(flags), n_rows, top, bottom, left, right, T,
+                                     hold, ptr(boxes), ptr(valid), ptr(status)), "face_boxes_runs")
+
+
+def _detect_group(detector, clips, pads, T, batch_size, hold=None):
     """One group on the device.  clips: _Clips of one frame shape, each with at least one frame.  Returns numpy (boxes int32 [R,4]
-    in (y1, y2, x1, x2) order, rows in clip order; status int32 [clips,2])."""
+    in (y1, y2, x1, x2) order, rows in clip order; status int32 [clips,2]); with `hold` (the pass-through rule) a third array,
+    valid int32 [R], comes between them - still one launch and one copy back."""
     dev = torch.device(detector.device)
     H, W = clips[0].H, clips[0].W
     R = sum(c.n for c in clips)
@@ -109,17 +209,25 @@ def _detect_group(detector, clips, pads, T, batch_size):
     addr_dev = st.tensor(addresses)
     for lo in range(0, padded, batch_size):
         _detect_batch(detector, addr_dev[lo * 8:(lo + batch_size) * 8], batch_size, H, W, rects, flags, lo)
+    if hold is not None:
+        out = torch.empty(5 * R + 2 * len(clips), dtype=torch.int32, device=dev)     # boxes [R][4], valid [R], status [clips][2]
+        _finish_runs(len(clips), st.tensor(segments), rects, flags, R, pads, T, hold, out[:4 * R], out[4 * R:5 * R], out[5 * R:])
+        res = out.cpu().numpy()
+        return res[:4 * R].reshape(R, 4), res[4 * R:5 * R], res[5 * R:].reshape(len(clips), 2)
     out = torch.empty(4 * R + 2 * len(clips), dtype=torch.int32, device=dev)    # boxes [R][4], then status [clips][2]: one copy back
     _finish_segments(len(clips), st.tensor(segments), rects, flags, pads, T, out[:4 * R], out[4 * R:])
     res = out.cpu().numpy()                      # the group's one copy back; it also ends the stream's use of the staging buffers
     return res[:4 * R].reshape(R, 4), res[4 * R:].reshape(len(clips), 2)
 
 
-def _per_clip(detector, clip, pads, T, batch_size):
+def _per_clip(detector, clip, pads, T, batch_size, hold=None):
     """one clip alone through `inference.face_detect` (batch by batch uploads, the host rules): (key, boxes, error)"""
     from .. import inference
     frames = list(clip.frames.cpu().numpy()) if isinstance(clip.frames, torch.Tensor) else list(clip.frames)
     try:
+        if hold is not None:                     # the pass-through rule on the host: the same rects, `host_boxes_runs`
+            rects = inference._detect_rects(frames, detector, batch_size)
+            return clip.key, RunBoxes(*host_boxes_runs(rects, clip.H, clip.W, pads, T, hold)), None
         if T in (0, 5):
             det = inference.face_detect(frames, detector=detector, pads=list(pads), nosmooth=(T == 0), batch_size=batch_size)
             boxes = np.array([c for _, c in det], dtype=np.int64).reshape(-1, 4)
@@ -133,7 +241,7 @@ def _per_clip(detector, clip, pads, T, batch_size):
     return clip.key, boxes, None
 
 
-def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_batches=16, max_group_bytes=1 << 30):
+def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_batches=16, max_group_bytes=1 << 30, no_face_hold=None):
     """`inference.face_detect(frames, detector, pads, nosmooth=(T == 0))` for every `DetectJob` of the iterable `jobs`, the frames
     of successive clips packed into detector batches of exactly `batch_size`.  A generator: jobs are consumed lazily and one
     `(key, boxes, error)` comes out per job, in job order - `boxes` the int array [n,4] of (y1, y2, x1, x2) `face_detect` returns
@@ -149,7 +257,14 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
     text of its ValueError, is the job's.
 
     A RuntimeError of the detector (out of device memory on a large frame) halves `batch_size` for the rest of the run, prints
-    the reference's message and runs the group again; at 1 it raises the reference's error (inference.py:75-88)."""
+    the reference's message and runs the group again; at 1 it raises the reference's error (inference.py:75-88).
+
+    `no_face_hold`: None (default) is all of the above.  An int G in 0..250 switches the pass-through rule on (not
+    the reference's behaviour): a frame without a face keeps the last detected rect for up to G frames and is a gap frame beyond
+    that, and every run of boxed frames is finished as a clip of its own.  `boxes` is then a `RunBoxes`: `boxes[i]` is frame i's
+    (y1, y2, x1, x2) or None for a gap frame (`.boxes` / `.valid` are the arrays); `error` stays for real errors (a coordinate
+    int() refuses)."""
+    hold = check_hold(no_face_hold)
     if batch_size < 1 or group_batches < 1:
         raise ValueError("batch_size and group_batches must be at least 1")
     if not 0 <= int(T) <= MAX_T:
@@ -178,7 +293,7 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
                 if group:
                     break                                  # the jobs before it first
                 held = None
-                yield _per_clip(detector, c, pads, T, batch_size)
+                yield _per_clip(detector, c, pads, T, batch_size, hold)
                 del c
                 continue
             if shape is not None and ((c.H, c.W) != shape or n_bytes + c.nbytes > max_group_bytes):
@@ -192,10 +307,13 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
         if not group:
             continue
         clips = [c for c in group if c.n]
-        boxes = status = None
+        boxes = status = valid = None
         while clips:
             try:
-                boxes, status = _detect_group(detector, clips, pads, T, batch_size)
+                if hold is None:
+                    boxes, status = _detect_group(detector, clips, pads, T, batch_size)
+                else:
+                    boxes, valid, status = _detect_group(detector, clips, pads, T, batch_size, hold)
                 break
             except RuntimeError:
                 if batch_size == 1:
@@ -205,10 +323,13 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
         results, row, k = [], 0, 0
         for c in group:
             if c.n == 0:
-                results.append((c.key, np.zeros((0, 4), np.int64), None))
+                empty = np.zeros((0, 4), np.int64)
+                results.append((c.key, empty if hold is None else RunBoxes(empty, []), None))
                 continue
             code = int(status[k][0])                       # status[k][1]: the frame that decided it
-            if code == 0:
+            if code == 0 and hold is not None:
+                results.append((c.key, RunBoxes(boxes[row:row + c.n], valid[row:row + c.n] != 0), None))
+            elif code == 0:
                 results.append((c.key, boxes[row:row + c.n].astype(np.int64), None))
             elif code == 1:
                 results.append((c.key, None, NO_FACE))
@@ -220,4 +341,4 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
         del c
         while results:
             res = results.pop(0)
-            yield _per_clip(detector, res, pads, T, batch_size) if isinstance(res, _Clip) else res
+            yield _per_clip(detector, res, pads, T, batch_size, hold) if isinstance(res, _Clip) else res

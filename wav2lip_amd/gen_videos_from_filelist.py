@@ -68,13 +68,15 @@ def build_main_parser():
     """what `main()` parses: `build_cli_parser` plus `--packed_face_det`, which changes how the work is scheduled and nothing of
     what is computed, and `--face_det_scale K`, the size of the frame the detector sees (`inference.add_det_scale_flag`).
     `--blend_feather N` / `--blend_top FRACTION` blend every generated face into its frame (`inference.add_blend_flags`).
+    `--no_face_hold G` generates a line with frames without a face instead of skipping it (`inference.add_hold_flag`).
     `cli_parser` stays the reference's surface plus the two precision flags."""
-    from .inference import add_blend_flags, add_det_scale_flag
+    from .inference import add_blend_flags, add_det_scale_flag, add_hold_flag
     p = build_cli_parser()
     p.add_argument('--packed_face_det', default=False, action='store_true',
                    help='Detect faces of successive clips in shared detector batches (face_detection.detect_many)')
     add_det_scale_flag(p)
     add_blend_flags(p)
+    add_hold_flag(p)
     return p
 
 
@@ -159,7 +161,8 @@ def clip_jobs(args, lines, ranks, detector, tracks):
                 full_frames, mel, pcm, sr = got
                 try:
                     det = inference.face_detect(full_frames, detector=detector, pads=args.pads, nosmooth=False,
-                                                batch_size=args.face_det_batch_size)
+                                                batch_size=args.face_det_batch_size,
+                                                **inference._hold_kw(getattr(args, 'no_face_hold', None)))
                 except ValueError as e:
                     _skip(idx, line, str(e))
                     continue
@@ -179,7 +182,7 @@ def clip_jobs_packed(args, lines, ranks, detector, tracks):
     `face_detection.detect_many` over their frames, then rows and the ClipJob as each line's boxes arrive.  detect_many reads a
     group of lines before it answers the first, so what the first stage has to say about a line it passes over is held back
     and written when the runnable line after it is answered: stderr reads as it does from `clip_jobs`."""
-    from . import face_detection, multiclip
+    from . import face_detection, inference, multiclip
     held, notes, tail = {}, {}, []       # line index -> (line, frames, mel, pcm, rate); -> stderr text due before it; after the last
 
     def inputs(tmpdir):
@@ -202,14 +205,15 @@ def clip_jobs_packed(args, lines, ranks, detector, tracks):
 
     with tempfile.TemporaryDirectory(prefix="w2l_filelist_") as tmpdir:
         for idx, boxes, error in face_detection.detect_many(detector, inputs(tmpdir), pads=args.pads, T=5,
-                                                            batch_size=args.face_det_batch_size):
+                                                            batch_size=args.face_det_batch_size,
+                                                            **inference._hold_kw(getattr(args, 'no_face_hold', None))):
             sys.stderr.write(notes.pop(idx))
             line, full_frames, mel, pcm, sr = held.pop(idx)
             try:
                 if error is not None:
                     _skip(idx, line, error)
                     continue
-                rows = multiclip.rows_filelist(mel.shape[1], len(full_frames), [tuple(b) for b in boxes])
+                rows = multiclip.rows_filelist(mel.shape[1], len(full_frames), [None if b is None else tuple(b) for b in boxes])
                 frame_h, frame_w = full_frames[0].shape[:-1]
                 tracks[idx] = ((frame_w, frame_h), pcm, sr)
                 yield multiclip.ClipJob(idx, full_frames, mel, rows)

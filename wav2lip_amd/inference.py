@@ -171,8 +171,9 @@ def build_cli_parser():
     """the command line `main()` parses: the reference's flags (`build_parser`, whose surface stays the reference's) plus
     documented additions that are not among them, each the reference's behaviour by default and independent of the others:
     `--precision {fp32,bf16}`, the generator's arithmetic, `--face_det_precision {fp32,bf16}`, the S3FD detector's,
-    `--face_det_scale K`, the detector's frame size (1/K; output frames keep theirs), `--out_codec` / `--out_quality`, and
-    `--blend_feather N` / `--blend_top FRACTION`, the feathered mouth-region paste"""
+    `--face_det_scale K`, the detector's frame size (1/K; output frames keep theirs), `--out_codec` / `--out_quality`,
+    `--blend_feather N` / `--blend_top FRACTION`, the feathered mouth-region paste, and `--no_face_hold G`, the pass-through for
+    frames without a face (absent by default)"""
     p = build_parser()
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
                    help='Generator arithmetic: fp32 (default, matches the reference) or bf16 storage (faster; frames differ by '
@@ -187,7 +188,22 @@ def build_cli_parser():
                         'bytes come back; lossy, about a tenth of the size at quality 95)')
     p.add_argument('--out_quality', default=95, type=int, help='JPEG quality of --out_codec mjpg, 1..100 (default 95)')
     add_blend_flags(p)
+    add_hold_flag(p)
     return p
+
+
+def add_hold_flag(p):
+    """`--no_face_hold G` on a command's parser (face_detection/many.py holds the rule's host side): absent by default"""
+    from .face_detection.many import add_hold_flag as add
+    add(p)
+
+
+def _hold_kw(no_face_hold):
+    """the keyword `face_detect`, `detect_many` and `LipsyncStreams` take for `no_face_hold`, checked first: none for None, so the
+    default path is called with the same arguments as before the option (as `_precision_kw`)"""
+    from .face_detection.many import check_hold
+    hold = check_hold(no_face_hold)
+    return {} if hold is None else {"no_face_hold": hold}
 
 
 CLI_PRECISION = {"fp32": "f32", "bf16": "bf16"}     # --precision / --face_det_precision value -> the `precision=` of the API
@@ -635,7 +651,8 @@ def _det_scale_kw(det_scale):
     return {} if det_scale == 1 else {"det_scale": det_scale}
 
 
-def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None, ranks=None, precision=None, det_scale=None):
+def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None, ranks=None, precision=None, det_scale=None,
+                no_face_hold=None):
     """inference.py:68-104: S3FD boxes per frame (HIP detector), padding, temporal smoothing; returns
     [[face crop, (y1, y2, x1, x2)], ...].  Called as the reference calls it - `face_detect(images)` - pads / nosmooth /
     face_det_batch_size come from the module-level `args` and the detector is built as inference.py:69-70 does
@@ -644,9 +661,17 @@ def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None
     detector's arithmetic; None means: a passed detector keeps its own, a built one takes the module-level
     `args.face_det_precision` (fp32 when absent).  `det_scale` (1..8) is the detector's frame size, 1/det_scale of the frames'
     (the boxes come back in full-frame coordinates; pads, clipping and smoothing below are on those); None follows the same rule
-    with `args.face_det_scale` (1 when absent)."""
+    with `args.face_det_scale` (1 when absent).
+
+    `no_face_hold`: None (default) raises the reference's ValueError at a frame without a face.  An int G in 0..250 switches the
+    pass-through rule on instead (not the reference's behaviour): such a frame keeps the last detected rect for up to
+    G frames (no look-ahead), beyond that - and before the first detection - it is a gap frame whose entry is [None, None], and
+    every run of boxed frames is padded, clipped and smoothed as a clip of its own (`face_detection.many.host_boxes_runs` states
+    the same for one frame shape).  A single frame without a face is still the ValueError."""
+    from .face_detection.many import boxed_runs, check_hold, hold_fill
     from .face_detection.s3fd import check_det_scale
     from .models.wav2lip import check_precision
+    hold = check_hold(no_face_hold)
     if precision is not None:
         check_precision(precision)
     if det_scale is not None:
@@ -672,6 +697,17 @@ def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None
     nosmooth = args.nosmooth if nosmooth is None else nosmooth
     batch_size = args.face_det_batch_size if batch_size is None else batch_size
     rects = _detect_rects(images, detector, batch_size, ranks)
+    if hold is not None and not (len(rects) == 1 and rects[0] is None):
+        rects = hold_fill(rects, hold)
+        top, bottom, left, right = pads
+        boxes = np.array([[0, 0, 0, 0] if r is None else
+                          [max(0, r[0] - left), max(0, r[1] - top), min(im.shape[1], r[2] + right), min(im.shape[0], r[3] + bottom)]
+                          for r, im in zip(rects, images)], dtype=np.int64).reshape(-1, 4)
+        if not nosmooth:
+            for a, b in boxed_runs([r is not None for r in rects]):
+                get_smoothened_boxes(boxes[a:b], T=5)                  # a view: in place, as on a clip of the run's frames alone
+        return [[None, None] if r is None else [im[y1:y2, x1:x2], (y1, y2, x1, x2)]
+                for r, im, (x1, y1, x2, y2) in zip(rects, images, boxes)]
     if any(r is None for r in rects):
         raise ValueError('Face not detected! Ensure the video contains a face in all the frames.')
     top, bottom, left, right = pads
@@ -768,6 +804,9 @@ def main(argv=None, keep_frames=True, backend="nccl"):
         raise ValueError("--out_quality %d is outside [1, 100]" % args.out_quality)
     if mjpg and int(os.environ.get("WORLD_SIZE", "1")) > 1:         # before the process group and any device work
         raise ValueError("--out_codec mjpg runs on one GPU: a sharded run gathers raw frames (compressed shards are not gathered yet)")
+    hold_kw = _hold_kw(args.no_face_hold)
+    if hold_kw and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--no_face_hold runs on one GPU: the hold looks back over the frames of other shards")
     ranks = sharding.init_from_env(backend)
     sharded = ranks.dist is not None and ranks.world > 1
     say = print if ranks.writer else (lambda *a, **k: None)
@@ -787,7 +826,7 @@ def main(argv=None, keep_frames=True, backend="nccl"):
         full_frames = full_frames[:len(starts)]
         if args.box[0] == -1:
             det = face_detect(full_frames if not args.static else [full_frames[0]], ranks=ranks,
-                              precision=CLI_PRECISION[args.face_det_precision], det_scale=args.face_det_scale)
+                              precision=CLI_PRECISION[args.face_det_precision], det_scale=args.face_det_scale, **hold_kw)
             coords = [c for _, c in det]
         else:
             say('Using the specified bounding box instead of face detection...')
@@ -796,7 +835,9 @@ def main(argv=None, keep_frames=True, backend="nccl"):
         say("Model loaded")
         n = len(starts)
         idx = [0 if args.static else i % len(full_frames) for i in range(n)]
-        boxes = [validate_boxes([coords[0 if args.static else j]], *full_frames[j].shape[:2])[0] for j in idx]
+        # a gap frame (--no_face_hold) has no box: its rows run no generator row and carry the input frame
+        boxes = [None if coords[0 if args.static else j] is None else
+                 validate_boxes([coords[0 if args.static else j]], *full_frames[j].shape[:2])[0] for j in idx]
         starts_dev = torch.tensor(starts, dtype=torch.int32, device=dev)
         runner = PipelinedRunner(model, args.wav2lip_batch_size, depth=LIPSYNC_DEPTH, **_precision_kw(CLI_PRECISION[args.precision]),
                                  **_blend_kw(blend))
@@ -823,18 +864,30 @@ def main(argv=None, keep_frames=True, backend="nccl"):
                 if keep_frames:
                     out_frames.append(f)
 
-            def drain(ticket):
+            def batch_frames(item):
+                """the batch's output frames on the device; with gap rows: every row's input frame, the generated ones pasted
+                over the rows that ran"""
+                ticket, gaps = item
+                if gaps is None:
+                    return runner.result(ticket)
+                frames_dev, which, ran = gaps
+                full = frames_dev.index_select(0, torch.tensor(which, dtype=torch.long, device=dev))
+                if ticket is not None:
+                    full[torch.tensor(ran, dtype=torch.long, device=dev)] = runner.result(ticket)
+                return full
+
+            def drain(item):
                 if mjpg:
                     # the frames are encoded where they lie and only the files come back; the raw frames follow them to the
                     # host for keep_frames alone (mjpg is never sharded)
                     from . import jpeg
-                    res = runner.result(ticket)
+                    res = batch_frames(item)
                     for data in jpeg.encode_frames(res, quality=args.out_quality, restart_rows=writer.restart_rows):
                         writer.write_jpeg(data)
                     if keep_frames:
                         out_frames.extend(res.cpu().numpy())
                     return
-                for f in runner.result(ticket).cpu().numpy():
+                for f in batch_frames(item).cpu().numpy():
                     if sharded:
                         local.append(f)         # this rank's shard, exchanged below
                     else:
@@ -845,8 +898,16 @@ def main(argv=None, keep_frames=True, backend="nccl"):
                 uniq = sorted(set(idx[lo:hi]))                              # a static image: one frame per batch
                 remap = {j: k for k, j in enumerate(uniq)}
                 frames_dev = torch.from_numpy(np.stack([full_frames[j] for j in uniq])).to(dev)
-                pending.append(runner.submit(None, mel=mel, starts=starts_dev[lo:hi].contiguous(), frames=frames_dev,
-                                             frame_idx=[remap[j] for j in idx[lo:hi]], boxes=boxes[lo:hi]))
+                ran = [k for k in range(lo, hi) if boxes[k] is not None]
+                if len(ran) == hi - lo:
+                    pending.append((runner.submit(None, mel=mel, starts=starts_dev[lo:hi].contiguous(), frames=frames_dev,
+                                                  frame_idx=[remap[j] for j in idx[lo:hi]], boxes=boxes[lo:hi]), None))
+                else:                                                       # the rows with a box run; the others pass through
+                    ticket = None
+                    if ran:
+                        ticket = runner.submit(None, mel=mel, starts=starts_dev[torch.tensor(ran, device=dev)].contiguous(),
+                                               frames=frames_dev, frame_idx=[remap[idx[k]] for k in ran], boxes=[boxes[k] for k in ran])
+                    pending.append((ticket, (frames_dev, [remap[j] for j in idx[lo:hi]], [k - lo for k in ran])))
                 if len(pending) >= runner.depth:
                     drain(pending.pop(0))
             while pending:

@@ -31,15 +31,20 @@ from .staging import Staging, align
 ClipJob = collections.namedtuple("ClipJob", "key frames mel rows")
 ClipJob.__doc__ = """one clip: `frames` uint8 [H,W,3] BGR frames (one shape per clip; a list or an [F,H,W,3] array, or a contiguous uint8
 device tensor [F,H,W,3] that is read where it lies), `mel` the device [80,T] spectrogram (audio.melspectrogram_device), `rows` a list
-of (frame_index, (y1, y2, x1, x2), mel_start)"""
+of (frame_index, (y1, y2, x1, x2), mel_start); a row whose box is None (a frame without a face under `no_face_hold`, DESIGN.md 3v)
+runs no generator row: its output frame is the frame itself"""
 
 
 def rows_inference(n_mel, n_frames, boxes, fps=25., static=False):
     """rows of inference.py:231-240 + :108-131: one row per mel chunk at `fps`, the tail window re-anchored at the end, chunk i
-    on frame i % n_frames (frame 0 when static) with that frame's box"""
+    on frame i % n_frames (frame 0 when static) with that frame's box; a box that is None (a gap frame) stays None"""
     starts = mel_chunk_starts(n_mel, fps)
     idx = [0 if static else i % n_frames for i in range(len(starts))]
-    return [(j, tuple(int(v) for v in boxes[j]), s) for j, s in zip(idx, starts)]
+    return [(j, _box(boxes[j]), s) for j, s in zip(idx, starts)]
+
+
+def _box(box):
+    return None if box is None else tuple(int(v) for v in box)
 
 
 def filelist_chunk_starts(n_mel):
@@ -61,7 +66,7 @@ def rows_filelist(n_mel, n_frames, boxes):
     starts = filelist_chunk_starts(n_mel)
     if n_frames < len(starts):
         raise ValueError("%d frames for %d mel chunks: the video is shorter than its audio" % (n_frames, len(starts)))
-    return [(i, tuple(int(v) for v in boxes[i]), s) for i, s in enumerate(starts)]
+    return [(i, _box(boxes[i]), s) for i, s in enumerate(starts)]
 
 
 class _Job:
@@ -201,7 +206,8 @@ def _checked_rows(job):
                 raise ValueError("frames must be uint8 [H,W,3] arrays, got %s %s" % (f.dtype, f.shape))
             if start < 0 or start + mel_step_size > T:
                 raise ValueError("mel window [%d, %d) outside the %d columns of the spectrogram" % (start, start + mel_step_size, T))
-            box = validate_boxes([box], f.shape[0], f.shape[1])[0]
+            if box is not None:
+                box = validate_boxes([box], f.shape[0], f.shape[1])[0]
         except ValueError as e:
             raise ValueError("job %r: %s" % (job.key, e)) from None
         rows.append((fi, box, start))
@@ -222,7 +228,7 @@ def _checked_rows_resident(job, T):
                 raise ValueError("frame index %d outside the clip's %d frames" % (fi, F))
             if start < 0 or start + mel_step_size > T:
                 raise ValueError("mel window [%d, %d) outside the %d columns of the spectrogram" % (start, start + mel_step_size, T))
-            rows.append((fi, validate_boxes([box], H, W)[0], start))
+            rows.append((fi, None if box is None else validate_boxes([box], H, W)[0], start))
     except ValueError as e:
         raise ValueError("job %r: %s" % (job.key, e)) from None
     return rows
@@ -237,7 +243,10 @@ def lipsync_many(model, jobs, batch_size=128, depth=None, precision="f32", sink=
     sink the frames are collected and returned as {key: [frames]}.  Memory is bounded whatever the number of jobs: a job's
     frames and mel are released when its last row has been delivered, and the jobs alive at any time are those the rows of at
     most `depth + 1` batches touch, plus the one being read.  `blend`: None (the reference's paste) or (feather, top), every
-    row's face blended into its frame (`inference.check_blend`, w2l_compose_blend_rows_u8)."""
+    row's face blended into its frame (`inference.check_blend`, w2l_compose_blend_rows_u8).
+
+    A row whose box is None takes no batch row: `sink` receives its frame's own bytes (copied back from the device for a
+    resident job) in its place in the row order, as soon as the rows before it have been delivered."""
     from .inference import _blend_kw
     from .models.wav2lip import check_precision
     check_precision(precision)
@@ -255,8 +264,8 @@ def lipsync_many(model, jobs, batch_size=128, depth=None, precision="f32", sink=
                 lst.append(frame)
 
     runner = None
-    pending = collections.deque()      # (ticket, [job per row]) of the batches in flight, oldest first
-    batch = []                         # rows of the batch being filled
+    pending = collections.deque()      # (ticket, [(job, None) per row, (job, frame) per pass-through row behind it]), oldest first
+    batch, order = [], []              # rows of the batch being filled; its entry of `pending` to be
     last = None                        # the newest job with undelivered rows
 
     def finish(job):
@@ -265,20 +274,37 @@ def lipsync_many(model, jobs, batch_size=128, depth=None, precision="f32", sink=
         for key in job.closed_after:
             sink(key, None)
 
+    def deliver(job, frame):
+        sink(job.key, frame)
+        job.delivered += 1
+        if job.delivered == job.n_rows:
+            finish(job)
+
+    def source_frame(job, fi):
+        f = job.frames[fi]
+        return f.cpu().numpy() if _resident(job.frames) else np.array(f)
+
     def collect():
         item, owners = pending.popleft()
-        for job, frame in zip(owners, runner.result(item)):
-            sink(job.key, frame)
-            job.delivered += 1
-            if job.delivered == job.n_rows:
-                finish(job)
+        generated = iter(runner.result(item))
+        for job, fi in owners:
+            deliver(job, next(generated) if fi is None else source_frame(job, fi))
 
     def flush():
-        nonlocal batch
-        pending.append((runner.submit(batch), [r[0] for r in batch]))
-        batch = []
+        nonlocal batch, order
+        pending.append((runner.submit(batch), order))
+        batch, order = [], []
         if len(pending) >= depth:
             collect()
+
+    def pass_through(job, fi):
+        """in row order: behind the rows of the batch being filled, else behind the newest batch in flight, else at once"""
+        if batch:
+            order.append((job, fi))
+        elif pending:
+            pending[-1][1].append((job, fi))
+        else:
+            deliver(job, source_frame(job, fi))
 
     for cj in jobs:
         rows = _checked_rows(cj)
@@ -293,7 +319,11 @@ def lipsync_many(model, jobs, batch_size=128, depth=None, precision="f32", sink=
         job = last = _Job(cj, len(rows))
         del cj
         for fi, box, start in rows:
+            if box is None:
+                pass_through(job, fi)
+                continue
             batch.append((job, fi, box, start))
+            order.append((job, None))
             if len(batch) == batch_size:
                 flush()
     if batch:

@@ -73,9 +73,18 @@ Per `step` the frames fed since the last one go up in ONE pinned buffer, through
 `face_det_batch_size`, and ONE w2l_face_boxes_stream launch (csrc/detect.hip) finishes the boxes of all streams; the NEXT `step`
 first waits for that launch's event (it never polls, so the batching stays a function of the call sequence).  Row i is ready
 when its spectrogram window is final and frame i % n_frames is there with a final box: boxes lag smooth_T - 1 frames plus one
-tick.  The uploaded frames stay on the device and the generator reads them there.  A frame without a face ends its stream only:
-the rows already taken are delivered, `sink(key, None)` follows and `errors[key]` says why.  A stream is gone once its last row is
-delivered; `feed` / `feed_frames` on it then raise KeyError.
+tick.  The uploaded frames stay on the device and the generator reads them there.  By default (the reference's rule) a frame
+without a face ends its stream only: the rows already taken are delivered, `sink(key, None)` follows and `errors[key]` says why.
+A stream is gone once its last row is delivered; `feed` / `feed_frames` on it then raise KeyError.
+
+Frames without a face (opt-in, not the reference's behaviour).  `LipsyncStreams(..., no_face_hold=G)` with G in
+0..250 keeps such a stream alive: the frame keeps the last detected rect for up to G frames (no look-ahead) and is a gap frame
+beyond that, and every run of boxed frames is padded, clipped and smoothed as a video of its own
+(`face_detection.many.host_boxes_runs` on the finished video, whatever the cut; ONE w2l_face_boxes_stream_runs launch per tick in
+the place of w2l_face_boxes_stream).  A gap frame's row becomes ready exactly when a boxed one would, takes no batch row, and is
+delivered unchanged - the input frame's bytes - by the same `sink` in its place in the row order; `errors` stays empty for it.
+Readiness of the other rows, bucketing and `on_batch` see boxed rows only, so the batching stays a function of the call sequence.
+`open(key, frames, boxes)` then accepts None among `boxes` with the same meaning.
 
 `python -m wav2lip_amd.streaming --checkpoint_path C --face F0 --audio A0 --face F1 --audio A1 ... --outdir D` feeds every audio
 file in `--chunk_ms` slices round-robin, steps after each round and writes one AVI per stream; with `--live_video` every video is
@@ -485,13 +494,15 @@ class DeviceBoxes:
     """the device side of live face detection: per call one staged copy, the detector batches, ONE w2l_face_boxes_stream launch
     (csrc/detect.hip) for every stream of the tick and one copy back"""
 
-    def __init__(self, device, detector, pads, T, batch_size):
+    def __init__(self, device, detector, pads, T, batch_size, hold=None):
+        """hold: None, or the G of the pass-through rule: w2l_face_boxes_stream_runs finishes the boxes, with its own carry slots"""
         import torch
         from . import _lib
         from .face_detection import live
         self.torch, self.device, self.lib, self.live = torch, device, _lib.load(), live
-        self.detector, self.pads, self.T, self.B = detector, pads, T, batch_size
-        self.carry = torch.zeros((64, live.CARRY_ROWS, 4), dtype=torch.int32, device=device)
+        self.detector, self.pads, self.T, self.B, self.hold = detector, pads, T, batch_size, hold
+        slot = (live.CARRY_ROWS, 4) if hold is None else (live.RUNS_CARRY_INTS,)
+        self.carry = torch.zeros((64,) + slot, dtype=torch.int32, device=device)
 
     def reserve(self, n_slots):
         """room for carry slots [0, n_slots); the table grows on the launches' stream, so in order with them"""
@@ -558,29 +569,40 @@ class DeviceBoxes:
         for H, W, first, end, padded in spans:
             for lo in range(first, padded, B):
                 self.detector.rects_for_rows(addr_dev[lo * 8:(lo + B) * 8], B, H, W, rects, flags, lo)
-        out = torch.empty(4 * out0 + 2 * len(items), dtype=torch.int32, device=self.device)     # boxes, then status: one copy back
+        # boxes, then (with a hold) valid, then status: one copy back
+        out = torch.empty((4 if self.hold is None else 5) * out0 + 2 * len(items), dtype=torch.int32, device=self.device)
         top, bottom, left, right = self.pads
         with torch.cuda.device(self.device):
-            check(self.lib.w2l_face_boxes_stream(current_stream(), len(items), st.host_address(segments), st.address(segments),
-                                                 ptr(rects), ptr(flags), total, ptr(self.carry), int(self.carry.shape[0]), top, bottom,
-                                                 left, right, T, ptr(out), out0, out.data_ptr() + 16 * out0), "face_boxes_stream")
+            if self.hold is None:
+                check(self.lib.w2l_face_boxes_stream(current_stream(), len(items), st.host_address(segments), st.address(segments),
+                                                     ptr(rects), ptr(flags), total, ptr(self.carry), int(self.carry.shape[0]), top, bottom,
+                                                     left, right, T, ptr(out), out0, out.data_ptr() + 16 * out0), "face_boxes_stream")
+            else:
+                check(self.lib.w2l_face_boxes_stream_runs(current_stream(), len(items), st.host_address(segments), st.address(segments),
+                                                          ptr(rects), ptr(flags), total, ptr(self.carry), int(self.carry.shape[0]), top,
+                                                          bottom, left, right, T, self.hold, ptr(out), out.data_ptr() + 16 * out0, out0,
+                                                          out.data_ptr() + 20 * out0), "face_boxes_stream_runs")
         host_out = torch.empty(out.numel(), dtype=torch.int32, pin_memory=True)
         host_out.copy_(out, non_blocking=True)
         done = torch.cuda.Event()
         done.record()
         counts = [int(c) for c in np.diff(np.append(segs["out0"], out0))]
-        return dict(chunks=chunks, counts=counts, host_out=host_out, done=done, keep=(st.host, st.dev, rects, flags, out))
+        return dict(chunks=chunks, counts=counts, host_out=host_out, done=done, keep=(st.host, st.dev, rects, flags, out),
+                    valid=self.hold is not None)
 
     @staticmethod
     def collect(ticket):
-        """wait for the launch's event; [(boxes int32 [count,4] of (y1, y2, x1, x2), (code, frame))] per item"""
+        """wait for the launch's event; [(boxes int32 [count,4] of (y1, y2, x1, x2), (code, frame))] per item, with a hold
+        [(boxes, (code, frame), valid int32 [count])]"""
         ticket["done"].synchronize()
         res = ticket["host_out"].numpy()
         n = sum(ticket["counts"])
-        status = res[4 * n:].reshape(-1, 2)
+        valid = res[4 * n:5 * n] if ticket["valid"] else None
+        status = res[(4 if valid is None else 5) * n:].reshape(-1, 2)
         out, r = [], 0
         for k, c in enumerate(ticket["counts"]):
-            out.append((res[4 * r:4 * (r + c)].reshape(c, 4).copy(), (int(status[k][0]), int(status[k][1]))))
+            item = (res[4 * r:4 * (r + c)].reshape(c, 4).copy(), (int(status[k][0]), int(status[k][1])))
+            out.append(item if valid is None else item + (valid[r:r + c].copy(),))
             r += c
         return out
 
@@ -789,9 +811,12 @@ class LipsyncStreams:
     `drain` returns).  `on_batch(rows)` receives each launched batch's [(key, row index)] including the padding rows."""
 
     def __init__(self, model, batch_size=128, depth=None, precision="f32", fps=25., sink=None, on_batch=None, mel_window=1024,
-                 detector=None, pads=(0, 10, 0, 0), smooth_T=5, face_det_batch_size=16, resample_buffer=1 << 16, blend=None):
+                 detector=None, pads=(0, 10, 0, 0), smooth_T=5, face_det_batch_size=16, resample_buffer=1 << 16, blend=None,
+                 no_face_hold=None):
+        from .face_detection.many import check_hold
         from .inference import check_blend
         from .models.wav2lip import check_precision
+        self.hold = check_hold(no_face_hold)             # None, or G: frames without a face pass through (module docstring)
         self.precision = check_precision(precision)
         self.blend = check_blend(blend)                  # None, or (feather, top): every frame's face is blended in
         if batch_size < 1:
@@ -816,7 +841,9 @@ class LipsyncStreams:
         self.sink = sink
         self._streams = collections.OrderedDict()       # open order
         self._ready = collections.deque()                # (stream, row, frame index, box, (window, cap, relative start))
-        self._pending = collections.deque()              # (ticket, [(stream, row)]) of the batches in flight, oldest first
+        self._ready_boxed = 0                            # how many of them have a box: those are the rows that fill batches
+        # (ticket, [(stream, row, None), and (stream, row, frame index) per pass-through row behind it]), oldest first
+        self._pending = collections.deque()
         self._runner = self._mel = None
         self.launches = 0                                # w2l_mel_stream_cols staging copies + launches so far
         # ---- live streams only (`open_live`)
@@ -849,7 +876,9 @@ class LipsyncStreams:
             if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
                 raise ValueError("stream %r: frames must be uint8 [H,W,3] arrays" % (key,))
             try:
-                checked.append(validate_boxes([b], f.shape[0], f.shape[1])[0])
+                if b is None and self.hold is None:
+                    raise ValueError("a frame without a box needs LipsyncStreams(no_face_hold=...)")
+                checked.append(None if b is None else validate_boxes([b], f.shape[0], f.shape[1])[0])
             except ValueError as e:
                 raise ValueError("stream %r: %s" % (key, e)) from None
         if len(checked) != (1 if static else len(frames)):
@@ -920,7 +949,8 @@ class LipsyncStreams:
             self._runner = BatchRunner(self.model, self.batch_size, self.depth, self.precision, **_blend_kw(self.blend))
             self._mel = DeviceMel(self._runner.device)
         if self._boxes is None and self.detector is not None:
-            self._boxes = DeviceBoxes(self._runner.device, self.detector, self.pads, self.smooth_T, self.face_det_batch_size)
+            self._boxes = DeviceBoxes(self._runner.device, self.detector, self.pads, self.smooth_T, self.face_det_batch_size,
+                                      **({} if self.hold is None else {"hold": self.hold}))
 
     def _columns_round(self):
         converted = False
@@ -943,6 +973,7 @@ class LipsyncStreams:
             for st in self._streams.values():
                 for row, fi, box, s in st.take_rows():
                     self._ready.append((st, row, fi, box, (st.window, st.cap, s - st.col0)))
+                    self._ready_boxed += box is not None
             self._launch(False)
             if not more:
                 break
@@ -981,7 +1012,8 @@ class LipsyncStreams:
             return
         from .face_detection.many import NO_FACE
         (ticket, sts), self._detecting = self._detecting, None
-        for st, (boxes, (code, frame)) in zip(sts, self._boxes.collect(ticket)):
+        for st, res in zip(sts, self._boxes.collect(ticket)):
+            boxes, (code, frame) = res[:2]
             if self._streams.get(st.key) is not st:      # it ended meanwhile
                 continue
             if code == 1:
@@ -996,7 +1028,10 @@ class LipsyncStreams:
                                "copy of the segment table failed the kernel's bounds" % code)
                 continue
             try:
-                st.boxes += validate_boxes(boxes, *st.shape) if len(boxes) else []
+                if len(res) > 2:                         # with a hold: a gap frame has no box
+                    st.boxes += [validate_boxes([b], *st.shape)[0] if v else None for b, v in zip(boxes, res[2])]
+                else:
+                    st.boxes += validate_boxes(boxes, *st.shape) if len(boxes) else []
             except ValueError as e:
                 self._fail(st, "frame %d..%d: %s" % (len(st.boxes), len(st.boxes) + len(boxes) - 1, e))
                 continue
@@ -1031,29 +1066,54 @@ class LipsyncStreams:
 
     def _launch(self, flush):
         bs = self.batch_size
-        while len(self._ready) >= bs or (flush and self._ready):
-            rows = [self._ready.popleft() for _ in range(min(bs, len(self._ready)))]
+        while True:
+            # pass-through rows at the front: in row order behind the newest batch in flight, else at once
+            while self._ready and self._ready[0][3] is None:
+                st, row, fi, _, _ = self._ready.popleft()
+                if self._pending:
+                    self._pending[-1][1].append((st, row, fi))
+                else:
+                    self._deliver(st, self._source_frame(st, fi))
+            if not (self._ready_boxed >= bs or (flush and self._ready_boxed)):
+                break
+            rows, owners = [], []                        # up to bs rows with a box, and the pass-through rows among and behind them
+            while self._ready and (len(rows) < bs or self._ready[0][3] is None):
+                st, row, fi, box, mel = self._ready.popleft()
+                owners.append((st, row, fi if box is None else None))
+                if box is not None:
+                    rows.append((st, row, fi, box, mel))
             n = len(rows)
+            self._ready_boxed -= n
             size = bs if n == bs else bucket(n, bs)
             ticket = self._runner.submit([st.locate(fi) + (box, mel) for st, _, fi, box, mel in rows], pad_to=size)
-            owners = [(st, row) for st, row, _, _, _ in rows]
             if self.on_batch is not None:
-                self.on_batch([(st.key, row) for st, row in owners] + [(owners[-1][0].key, owners[-1][1])] * (size - n))
+                self.on_batch([(st.key, row) for st, row, _, _, _ in rows] + [(rows[-1][0].key, rows[-1][1])] * (size - n))
             self._pending.append((ticket, owners))
             if len(self._pending) >= self.depth:
                 self._collect()
 
+    @staticmethod
+    def _source_frame(st, fi):
+        """the bytes of a stream's frame fi on the host: what a pass-through row delivers"""
+        where, j = st.locate(fi)
+        f = where.frames[j]
+        return f.cpu().numpy() if hasattr(f, "data_ptr") else np.array(f)
+
+    def _deliver(self, st, frame):
+        self.sink(st.key, frame)
+        st.delivered += 1
+        st.release_delivered()
+        if st.finished():
+            if self._streams.get(st.key) is st:
+                del self._streams[st.key]
+            st.frames = st.window = st.rs = None
+            self.sink(st.key, None)
+
     def _collect(self):
         item, owners = self._pending.popleft()
-        for (st, _), frame in zip(owners, self._runner.result(item)):
-            self.sink(st.key, frame)
-            st.delivered += 1
-            st.release_delivered()
-            if st.finished():
-                if self._streams.get(st.key) is st:
-                    del self._streams[st.key]
-                st.frames = st.window = st.rs = None
-                self.sink(st.key, None)
+        generated = iter(self._runner.result(item))
+        for st, _, fi in owners:
+            self._deliver(st, next(generated) if fi is None else self._source_frame(st, fi))
 
     def drain(self):
         """close nothing; run and deliver everything that is ready or in flight"""
@@ -1099,9 +1159,10 @@ def build_parser():
                    help='Feed the frames of every video as they become due with the audio and detect faces as they arrive')
     p.add_argument('--native_rate', default=False, action='store_true',
                    help="Feed every WAV at the file's own rate and format; it is converted to 16 kHz on the device as it streams")
-    from .inference import add_blend_flags, add_det_scale_flag
+    from .inference import add_blend_flags, add_det_scale_flag, add_hold_flag
     add_det_scale_flag(p)
     add_blend_flags(p)
+    add_hold_flag(p)
     return p
 
 
@@ -1119,6 +1180,7 @@ def main(argv=None, state_dict=None):
     from . import audio, inference
     a = build_parser().parse_args(argv)
     blend = inference.blend_from_args(a)
+    hold_kw = inference._hold_kw(a.no_face_hold)
     if len(a.face) != len(a.audio):
         raise ValueError("%d --face for %d --audio: pass them in pairs" % (len(a.face), len(a.audio)))
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -1143,7 +1205,7 @@ def main(argv=None, state_dict=None):
         elif a.box[0] == -1:
             det = inference.face_detect(frames if not one.static else [frames[0]], detector=detector, pads=a.pads, nosmooth=a.nosmooth,
                                         batch_size=a.face_det_batch_size, precision=inference.CLI_PRECISION[a.face_det_precision],
-                                        det_scale=a.face_det_scale)
+                                        det_scale=a.face_det_scale, **hold_kw)
             boxes = [c for _, c in det]
         else:
             boxes = [tuple(a.box)] * len(frames)
@@ -1168,7 +1230,7 @@ def main(argv=None, state_dict=None):
 
     streams = LipsyncStreams(model, batch_size=a.wav2lip_batch_size, precision=inference.CLI_PRECISION[a.precision], sink=sink,
                              detector=detector, pads=a.pads, smooth_T=0 if a.nosmooth else 5, face_det_batch_size=a.face_det_batch_size,
-                             **inference._blend_kw(blend))
+                             **inference._blend_kw(blend), **hold_kw)
     for j in jobs:
         if j["live"]:
             streams.open_live(j["key"], fps=j["fps"], sample_rate=j["rate"])
