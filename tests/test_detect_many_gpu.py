@@ -127,9 +127,10 @@ def _run_segments(cuda, t_dev, rects, flags, n_seg, pads, T):
 @pytest.mark.parametrize("pads", [(0, 10, 0, 0), (3, 10, 5, 7), (-2, -10, -4, -3)])
 def test_face_boxes_segments_is_the_host_expression(cuda, T, pads):
     """n = 1..4 are shorter than the window of 5 (the wrapped negative start, clipped at 0 for n = 1, 2), 5 and 6 sit on its edge,
-    70 is more than one wave.  Integer arithmetic and one correctly rounded fp64 division on both sides: equality is the bar."""
+    63, 64 and 65 on the edge of the kernel's chunk of 64 frames, 70 and 130 are two and three chunks, 200 is past the three
+    chunks its ring holds.  Integer arithmetic and one correctly rounded fp64 division on both sides: equality is the bar."""
     from wav2lip_amd.face_detection import many
-    lengths = [1, 2, 3, 4, 5, 6, 11, 70]
+    lengths = [1, 2, 3, 4, 5, 6, 11, 63, 64, 65, 70, 130, 200]
     t_dev, rects, flags, rects_h, segs = _segments_case(cuda, lengths, seed=100 + 10 * T + pads[0])
     boxes, status = _run_segments(cuda, t_dev, rects, flags, len(segs), pads, T)
     assert not status.any()
@@ -145,12 +146,13 @@ def test_face_boxes_segments_is_the_host_expression(cuda, T, pads):
 def test_face_boxes_segments_reports_no_face_and_host_rows_per_segment(cuda):
     from wav2lip_amd.face_detection import many
     from wav2lip_amd.face_detection.s3fd import RECT_HOST, RECT_NONE
-    lengths = [6, 70, 9, 3, 5]
-    edits = [(1, 66, RECT_NONE), (1, 68, RECT_NONE), (2, 2, RECT_NONE), (2, 7, RECT_HOST), (2, 8, RECT_HOST), (3, 0, RECT_HOST)]
+    lengths = [6, 70, 9, 3, 5, 200]
+    edits = [(1, 66, RECT_NONE), (1, 68, RECT_NONE), (2, 2, RECT_NONE), (2, 7, RECT_HOST), (2, 8, RECT_HOST), (3, 0, RECT_HOST),
+             (5, 195, RECT_NONE)]
     t_dev, rects, flags, rects_h, segs = _segments_case(cuda, lengths, seed=3, flag_edits=edits)
     boxes, status = _run_segments(cuda, t_dev, rects, flags, len(segs), (0, 10, 0, 0), 5)
     # a RECT_NONE at row k: (1, k), the first one; a RECT_HOST after an earlier RECT_NONE still wins: (2, its row)
-    assert status.tolist() == [[0, 0], [1, 66], [2, 7], [2, 0], [0, 0]]
+    assert status.tolist() == [[0, 0], [1, 66], [2, 7], [2, 0], [0, 0], [1, 195]]
     for k, (row0, n) in enumerate(segs):
         if status[k, 0]:
             assert not boxes[row0:row0 + n].any()

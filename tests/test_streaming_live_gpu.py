@@ -1,5 +1,5 @@
 """Live streams on the device: w2l_face_boxes_stream (csrc/detect.hip) against its host statement
-`face_detection.live.stream_boxes_host` by equality - eight streams per launch between fence rows, three ways of cutting them
+`face_detection.live.stream_boxes_host` by equality - nine streams per launch between fence rows, three ways of cutting them
 into ticks, the status rules and every refusal - and `LipsyncStreams.open_live` end to end on the seeded filelist clips: every
 delivered frame against `face_detect` + the whole audio's spectrogram + `rows_inference` run through the generator, a clip without
 a face, bounded memory with cycle=False, and the command line with `--live_video`."""
@@ -16,8 +16,8 @@ pytestmark = pytest.mark.gpu
 FH, FW = 40, 50
 FENCE = 1000000
 SENTINEL = -7
-LENGTHS = [1, 2, 3, 4, 5, 6, 11, 70]
-SLOTS = [1, 3, 4, 6, 7, 9, 10, 11]            # of 12: slots 0, 2, 5, 8 belong to nobody and must keep their sentinels
+LENGTHS = [1, 2, 3, 4, 5, 6, 11, 70, 130]     # 130: carried rows ahead of two boundaries of the kernel's chunks of 64 frames
+SLOTS = [1, 3, 4, 6, 7, 9, 10, 11, 2]         # of 12: slots 0, 5, 8 belong to nobody and must keep their sentinels
 N_SLOTS = 12
 
 
@@ -100,15 +100,13 @@ def _check_carry(carry, states):
     assert (got[[s for s in range(N_SLOTS) if s not in SLOTS]] == SENTINEL).all()
 
 
-@pytest.mark.parametrize("kind", ["whole", "each", "random"])
-@pytest.mark.parametrize("T,pads", [(0, (0, 10, 0, 0)), (1, (0, 10, 0, 0)), (5, (0, 10, 0, 0)), (5, (-2, -10, -4, -3)), (64, (3, 10, 5, 7))])
-def test_face_boxes_stream_is_the_host_statement_tick_by_tick(cuda, kind, T, pads):
-    """eight streams in one launch per tick; integer inputs and one correctly rounded fp64 division on both sides: equality.  The
-    streams' boxes over all ticks are `many.host_boxes` of the whole videos."""
+def _stream_ticks(cuda, lengths, kind, T, pads):
+    """streams of these lengths (stream k in slot SLOTS[k]) in one launch per tick; integer inputs and one correctly rounded fp64
+    division on both sides: equality.  The streams' boxes over all ticks are `many.host_boxes` of the whole videos."""
     from wav2lip_amd.face_detection import live, many
     rng = np.random.default_rng(1000 * T + 10 * len(kind) + pads[0])
-    videos = [rng.integers(0, 71, (n, 4)).tolist() for n in LENGTHS]              # beyond the 40 x 50 frame: both clips act
-    cuts = [_cuts(kind, n, rng) for n in LENGTHS]
+    videos = [rng.integers(0, 71, (n, 4)).tolist() for n in lengths]              # beyond the 40 x 50 frame: both clips act
+    cuts = [_cuts(kind, n, rng) for n in lengths]
     carry = _new_carry(cuda)
     states, pos, got = {}, [0] * len(videos), [[] for _ in videos]
     for t in range(max(len(c) for c in cuts)):
@@ -129,6 +127,19 @@ def test_face_boxes_stream_is_the_host_statement_tick_by_tick(cuda, kind, T, pad
         _check_carry(carry, states)
     for k, video in enumerate(videos):
         assert np.array_equal(np.concatenate(got[k]), many.host_boxes(video, FH, FW, pads, T))
+
+
+@pytest.mark.parametrize("kind", ["whole", "each", "random"])
+@pytest.mark.parametrize("T,pads", [(0, (0, 10, 0, 0)), (1, (0, 10, 0, 0)), (5, (0, 10, 0, 0)), (5, (-2, -10, -4, -3)), (64, (3, 10, 5, 7))])
+def test_face_boxes_stream_is_the_host_statement_tick_by_tick(cuda, kind, T, pads):
+    _stream_ticks(cuda, LENGTHS, kind, T, pads)
+
+
+@pytest.mark.parametrize("kind", ["whole", "random"])
+@pytest.mark.parametrize("T", [5, 64])
+def test_face_boxes_stream_is_the_host_statement_past_the_ring_of_three_chunks(cuda, kind, T):
+    """one stream of 200 frames: a tick of more than 192 frames reuses the kernel's ring, and random cuts carry rows across it"""
+    _stream_ticks(cuda, [200], kind, T, (0, 10, 0, 0))
 
 
 def test_face_boxes_stream_reports_no_face_and_host_rows_and_leaves_that_stream_as_it_was(cuda):

@@ -363,8 +363,8 @@ __global__ __launch_bounds__(64) void s3fd_first_rect_kernel(int P, const float*
 // ---- the per-clip finish of face_detect (inference.py:90-104; gen_videos_from_filelist.py:61-77 is the same code) for many
 // clips: one wave per segment = one clip's rows [row0, row0 + n) of the rect / flag arenas w2l_s3fd_first_rect filled.
 //   1. the flags: any row the device did not convert (kRectHost, or a word that is no flag at all) -> status (2, first such row):
-//      the detector would have met it before face_detect looks for None; else any kRectNone -> (1, first such row), the
-//      "Face not detected" ValueError; boxes of such a segment are zeros.
+//      the detector would have met it before face_detect looks for None; else, in the strict mode, any kRectNone -> (1, first such
+//      row), the "Face not detected" ValueError; boxes of such a segment are zeros.
 //   2. the padded box of a row, in the output's (y1, y2, x1, x2) order: (max(0, y1 - top), min(H, y2 + bottom), max(0, x1 - left),
 //      min(W, x2 + right)) - near edges clipped at 0 and far edges at the frame ONLY, as there.
 //   3. get_smoothened_boxes (inference.py:59-66), in place and in row order: row i <= n - T is the mean of the T unsmoothed rows
@@ -373,6 +373,8 @@ __global__ __launch_bounds__(64) void s3fd_first_rect_kernel(int P, const float*
 //      max(0, 2n - T); that window holds rows already smoothed, so they run in order - one lane per coordinate (the four columns
 //      never mix) over a copy of the window in LDS.  A mean is an exact integer sum, one fp64 division, truncation towards zero:
 //      numpy's float64 mean assigned into an integer array.
+// face_boxes_runs_wave below is the one device statement of steps 2 and 3, for clips and for live streams, strict or with the
+// pass-through for frames without a face.
 constexpr int kBoxMaxT = 64;
 struct BoxSeg { int row0, n, H, W; };
 static_assert(sizeof(BoxSeg) == 16 && sizeof(w2l_box_segment) == 16, "w2l_box_segment is 16 bytes");
@@ -389,80 +391,15 @@ __device__ __forceinline__ int padded_coord(const int* r, int c, const Seg& s, i
 
 __device__ __forceinline__ int trunc_mean(long long sum, int len) { return (int)((double)sum / (double)len); }
 
-__global__ __launch_bounds__(64) void face_boxes_segments_kernel(const BoxSeg* __restrict__ segs, const int* __restrict__ rects,
-                                                                 const int* __restrict__ flags, int top, int bottom, int left,
-                                                                 int right, int T, int* __restrict__ boxes, int* __restrict__ status) {
-    __shared__ int s_win[kBoxMaxT][4];
-    const int lane = threadIdx.x;
-    const BoxSeg s = segs[blockIdx.x];
-    int* st = status + 2 * (long long)blockIdx.x;
-    const int n = s.n;
-    if (n <= 0) {                                        // uniform
-        if (lane == 0) { st[0] = 0; st[1] = 0; }
-        return;
-    }
-    const int* fl = flags + s.row0;
-    const int* rc = rects + (long long)s.row0 * 4;
-    int* bx = boxes + (long long)s.row0 * 4;
-    int first_host = 0x7fffffff, first_none = 0x7fffffff;
-    for (int i = lane; i < n; i += 64) {
-        const int f = fl[i];
-        if (f == kRectNone) first_none = min(first_none, i);
-        else if (f != kRectFound) first_host = min(first_host, i);
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        first_host = min(first_host, __shfl_xor(first_host, o));
-        first_none = min(first_none, __shfl_xor(first_none, o));
-    }
-    if (first_host != 0x7fffffff || first_none != 0x7fffffff) {      // uniform after the butterfly
-        for (int i = lane; i < 4 * n; i += 64) bx[i] = 0;
-        if (lane == 0) {
-            st[0] = first_host != 0x7fffffff ? 2 : 1;
-            st[1] = first_host != 0x7fffffff ? first_host : first_none;
-        }
-        return;
-    }
-    if (lane == 0) { st[0] = 0; st[1] = 0; }
-    if (T == 0) {
-        for (int i = lane; i < 4 * n; i += 64) bx[i] = padded_coord(rc + (i >> 2) * 4, i & 3, s, top, bottom, left, right);
-        return;
-    }
-    const int ws = n >= T ? n - T : max(0, 2 * n - T);       // first row of Python's boxes[n - T:]
-    const int L = n - ws;                                    // 1 <= L <= T <= kBoxMaxT
-    const int seq0 = n >= T ? n - T : 0;                     // rows from here on run in order
-    for (int i = lane; i < seq0; i += 64) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            long long sum = 0;
-            for (int j = 0; j < T; ++j) sum += padded_coord(rc + (long long)(i + j) * 4, c, s, top, bottom, left, right);
-            bx[(long long)i * 4 + c] = trunc_mean(sum, T);
-        }
-    }
-    if (lane < L) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) s_win[lane][c] = padded_coord(rc + (long long)(ws + lane) * 4, c, s, top, bottom, left, right);
-    }
-    __syncthreads();
-    if (lane < 4) {
-        const int c = lane;
-        for (int i = seq0; i < n; ++i) {
-            long long sum = 0;
-            for (int j = 0; j < L; ++j) sum += s_win[j][c];
-            const int m = trunc_mean(sum, L);
-            if (i >= ws) s_win[i - ws][c] = m;
-            bx[(long long)i * 4 + c] = m;
-        }
-    }
-}
-
 // ---- the same finish for LIVE streams, one launch per tick (inference.py:59-66, :90-104): one wave per segment = the rows one
 // stream added to the arenas in this tick.  get_smoothened_boxes looks FORWARD: box i <= n - T is the mean of the unsmoothed
 // rows i .. i + T - 1, so it is final once row i + T - 1 is there, whatever follows; only the rows after n - T depend on the end
-// (the in-place boxes[n - T:] window).  The stream therefore carries its last max(T, 1) RAW rects from tick to tick (a slot of
-// `carry`), and the rows this launch holds are  [carry: min(seen, max(T, 1)) rows][the new rows]  = frames [base, n), n = seen +
-// n_new.  While open it writes frames [max(0, seen - T + 1), max(0, n - T + 1)) by the forward rule; with `closed` every
-// remaining frame by face_boxes_segments_kernel's tail on the whole length n - its entry n - T, already smoothed there, is the
-// forward mean of raw rows and is computed again.  The slot is read into LDS before anything is written to it.
+// (the in-place boxes[n - T:] window).  The strict stream therefore carries its last max(T, 1) RAW rects from tick to tick (a slot
+// of `carry`, [kBoxMaxT][4]: its first min(n, max(T, 1)) rows are rewritten, no other word), and the rows a launch holds are
+// [carry: min(seen, max(T, 1)) rows][the new rows]  = frames [seen - carried, n), n = seen + n_new.  While open it writes frames
+// [max(0, seen - T + 1), max(0, n - T + 1)) by the forward rule; with `closed` every remaining frame by step 3's tail on the whole
+// length n - its entry n - T, already smoothed there, is the forward mean of raw rows and is computed again.  The slot is read
+// into LDS before anything is written to it.
 struct BoxStreamSeg { int row0, n_new, H, W, slot, seen, closed, out0; };
 static_assert(sizeof(BoxStreamSeg) == 32 && sizeof(w2l_box_stream_segment) == 32, "w2l_box_stream_segment is 32 bytes");
 constexpr int kBoxStreamBadSegment = 3;
@@ -474,127 +411,29 @@ __host__ __device__ inline void box_stream_range(long long seen, long long n, in
     *hi = closed ? n : (n - T + 1 > 0 ? n - T + 1 : 0);
 }
 
-__global__ __launch_bounds__(64) void face_boxes_stream_kernel(const BoxStreamSeg* __restrict__ segs, const int* __restrict__ rects,
-                                                               const int* __restrict__ flags, int n_rows, int* __restrict__ carry,
-                                                               int n_slots, int top, int bottom, int left, int right, int T,
-                                                               int* __restrict__ boxes, int n_out, int* __restrict__ status) {
-    __shared__ int s_carry[kBoxMaxT][4];
-    __shared__ int s_win[kBoxMaxT][4];
-    const int lane = threadIdx.x;
-    const BoxStreamSeg s = segs[blockIdx.x];
-    int* st = status + 2 * (long long)blockIdx.x;
-    // the launcher checked the host copy of the table; a device copy that says otherwise is not followed
-    const long long n_ll = (long long)s.seen + s.n_new;
-    bool bad = s.n_new < 0 || s.seen < 0 || s.slot < 0 || s.slot >= n_slots || s.row0 < 0 || (long long)s.row0 + s.n_new > n_rows ||
-               n_ll > 0x7fffffffll || s.out0 < 0;
-    long long lo_ll = 0, hi_ll = 0;
-    if (!bad) {
-        box_stream_range(s.seen, n_ll, s.closed, T, &lo_ll, &hi_ll);
-        bad = s.out0 + (hi_ll - lo_ll) > n_out;
-    }
-    if (bad) {                                           // uniform
-        if (lane == 0) { st[0] = kBoxStreamBadSegment; st[1] = 0; }
-        return;
-    }
-    const int n = (int)n_ll, lo = (int)lo_ll, n_new = s.n_new;
-    const int* fl = flags + s.row0;
-    const int* rc = rects + (long long)s.row0 * 4;
-    int* bx = boxes + (long long)s.out0 * 4;
-    int first_host = 0x7fffffff, first_none = 0x7fffffff;
-    for (int i = lane; i < n_new; i += 64) {
-        const int f = fl[i];
-        if (f == kRectNone) first_none = min(first_none, i);
-        else if (f != kRectFound) first_host = min(first_host, i);
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        first_host = min(first_host, __shfl_xor(first_host, o));
-        first_none = min(first_none, __shfl_xor(first_none, o));
-    }
-    if (first_host != 0x7fffffff || first_none != 0x7fffffff) {      // uniform: no box written, the carry left as it was
-        if (lane == 0) {
-            st[0] = first_host != 0x7fffffff ? 2 : 1;
-            st[1] = s.seen + (first_host != 0x7fffffff ? first_host : first_none);
-        }
-        return;
-    }
-    if (lane == 0) { st[0] = 0; st[1] = 0; }
-    const int Tm = max(T, 1);
-    const int c = min(s.seen, Tm);                       // carried rows; held row h is frame base + h
-    const int base = s.seen - c, m = c + n_new;
-    int* slot = carry + (long long)s.slot * (kBoxMaxT * 4);
-    if (lane < c) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s_carry[lane][k] = slot[lane * 4 + k];
-    }
-    __syncthreads();
-    auto raw = [&](int h) -> const int* { return h < c ? &s_carry[h][0] : rc + (long long)(h - c) * 4; };
-    // the next tick's carry: the last min(n, max(T, 1)) raw rows, taken now, stored last
-    const int keep = min(n, Tm);
-    int kv[4] = {0, 0, 0, 0};
-    if (lane < keep) {
-        const int* r = raw(m - keep + lane);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) kv[k] = r[k];
-    }
-    if (T == 0) {
-        for (int i = lane; i < 4 * n_new; i += 64) bx[i] = padded_coord(rc + (i >> 2) * 4, i & 3, s, top, bottom, left, right);
-    } else {
-        const int fwd_hi = s.closed ? (n >= T ? n - T : 0) : (int)hi_ll;
-        for (int i = lo + lane; i < fwd_hi; i += 64) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                long long sum = 0;
-                for (int j = 0; j < T; ++j) sum += padded_coord(raw(i - base + j), k, s, top, bottom, left, right);
-                bx[(long long)(i - lo) * 4 + k] = trunc_mean(sum, T);
-            }
-        }
-        if (s.closed && n > 0) {                             // uniform
-            const int ws = n >= T ? n - T : max(0, 2 * n - T);   // first row of Python's boxes[n - T:]; ws >= base
-            const int L = n - ws;                                // 1 <= L <= T <= kBoxMaxT
-            const int seq0 = n >= T ? n - T : 0;
-            if (lane < L) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) s_win[lane][k] = padded_coord(raw(ws - base + lane), k, s, top, bottom, left, right);
-            }
-            __syncthreads();
-            if (lane < 4) {
-                const int k = lane;
-                for (int i = seq0; i < n; ++i) {
-                    long long sum = 0;
-                    for (int j = 0; j < L; ++j) sum += s_win[j][k];
-                    const int mean = trunc_mean(sum, L);
-                    if (i >= ws) s_win[i - ws][k] = mean;
-                    if (i >= lo) bx[(long long)(i - lo) * 4 + k] = mean;     // entry n - T may have gone out in an earlier tick
-                }
-            }
-        }
-    }
-    if (lane < keep) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) slot[lane * 4 + k] = kv[k];
-    }
-}
-
-// ---- the opt-in pass-through for frames without a face: the two finishes above with "no face" as a state of a
-// frame instead of the end of its clip.  One rule for both forms:
+// ---- the finish with "no face" as a state of a frame instead of the end of its clip (the opt-in pass-through).
+// One rule for clips and streams:
 //   hold   an undetected frame i takes the raw rect of the last detected frame p < i while i - p <= hold (it is BOXED, as a
 //          detected frame is); else, and before the first detection, it is a GAP: box zeros, valid 0.
-//   runs   maximal sequences of boxed frames; each is finished as face_boxes_segments_kernel finishes a clip of those frames alone.
+//   runs   maximal sequences of boxed frames; each is finished by steps 2 and 3 above as a clip of those frames alone.
+// The strict finish is the case in which every frame is detected: one run that ends at the close, no gap, and no `valid` output.
 // A wave walks its frames in chunks of 64 with three chunks of held-filled rows (x1, y1, x2, y2, boxed) in an LDS ring: the fill of a
 // chunk is a max-scan for "last detected frame" continued from the chunk before; a boxed frame i whose next T - 1 frames are all
 // boxed takes the forward mean of raw rows (those reach into the next chunk), any other boxed frame lies in the tail of its run,
 // and the tail of a run that ends at b (frame b is a gap, or the end of a closed video) reads raw rows back to b - T (those reach
-// into the chunk before) and runs in order, one lane per coordinate.  T = 0 is T = 1 here: the truncated mean of one integer.
-// The stream form holds the frames [seen - min(seen, 2T), seen) in its carry slot: a run may have ended up to T - 2 frames before
-// the tick's first new frame and its tail then reads back to seen - 2T + 2.
+// into the chunk before; frames before the first one held count as gaps, which gives a run shorter than T its wrapped window)
+// and runs in order, one lane per coordinate.  T = 0 is T = 1 here: the truncated mean of one integer.
+// The pass-through stream holds the frames [seen - min(seen, 2T), seen) in its carry slot: a run may have ended up to T - 2 frames
+// before the tick's first new frame and its tail then reads back to seen - 2T + 2.  The strict stream's only tail is the one at
+// the close, which reads back to n - T >= seen - T: its min(seen, T) raw rects suffice, and enter the ring as boxed rows.
 constexpr int kHoldMax = 250;                            // frames a rect is held for at the most
 constexpr int kRunsCarryRows = 2 * kBoxMaxT;             // rows of a slot: (x1, y1, x2, y2, boxed) of the last 2 * max(T, 1) frames
 constexpr int kRunsCarryInts = kRunsCarryRows * 5 + 4;   // then (frames since the last detection, capped at kHoldMax + 1; 0; 0; 0)
 constexpr int kRunsRing = 3 * 64;
 
 // One segment.  Frames [f0, n) with f0 = seen - c: the c carried rows (s_carry), then rows of the arenas (rc, fl: frame `seen` is
-// their row 0).  Writes boxes and valid of the frames [lo, hi) at bx / vd (frame lo is row 0 there).  Afterwards the ring holds
-// the last three chunks and *p_out the last detected frame (-1: none within reach).
+// their row 0).  Writes boxes and valid of the frames [lo, hi) at bx / vd (frame lo is row 0 there; vd may be NULL).  Afterwards
+// the ring holds the last three chunks and *p_out the last detected frame (-1: none within reach).
 template <class Seg>
 __device__ __forceinline__ void face_boxes_runs_wave(const Seg& s, const int* __restrict__ rc, const int* __restrict__ fl, int seen,
                                                      long long n, bool closed, int c, int dist0, int top, int bottom, int left,
@@ -642,7 +481,7 @@ __device__ __forceinline__ void face_boxes_runs_wave(const Seg& s, const int* __
             if (i >= lo && i < hi) {
                 int* o = bx + (i - lo) * 4;
                 const bool me = boxed(i);
-                vd[i - lo] = me;
+                if (vd) vd[i - lo] = me;
                 bool all = me;
                 for (int j = 1; j < Tm && all; ++j) all = boxed(i + j);
                 if (!me) o[0] = o[1] = o[2] = o[3] = 0;
@@ -689,17 +528,25 @@ __device__ __forceinline__ void face_boxes_runs_wave(const Seg& s, const int* __
     *p_out = p;
 }
 
-// the first row of [0, n) whose flag is neither found nor none (0x7fffffff: none), the same on every lane
-__device__ __forceinline__ int first_host_row(const int* __restrict__ fl, int n) {
-    int first = 0x7fffffff;
+// the first row of [0, n) whose flag is neither found nor none, and the first that is none (0x7fffffff: no such row), the same on
+// every lane
+__device__ __forceinline__ void first_unfound_rows(const int* __restrict__ fl, int n, int* host, int* none) {
+    int first_host = 0x7fffffff, first_none = 0x7fffffff;
     for (int i = threadIdx.x; i < n; i += 64) {
         const int f = fl[i];
-        if (f != kRectFound && f != kRectNone) first = min(first, i);
+        if (f == kRectNone) first_none = min(first_none, i);
+        else if (f != kRectFound) first_host = min(first_host, i);
     }
-    for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o));
-    return first;
+    for (int o = 32; o > 0; o >>= 1) {
+        first_host = min(first_host, __shfl_xor(first_host, o));
+        first_none = min(first_none, __shfl_xor(first_none, o));
+    }
+    *host = first_host;
+    *none = first_none;
 }
 
+// kStrict: a "none" row ends the segment as a host row does (a host row wins), `valid` and `hold` are not read
+template <bool kStrict>
 __global__ __launch_bounds__(64) void face_boxes_runs_kernel(const BoxSeg* __restrict__ segs, const int* __restrict__ rects,
                                                              const int* __restrict__ flags, int n_rows, int top, int bottom, int left,
                                                              int right, int T, int hold, int* __restrict__ boxes,
@@ -715,26 +562,31 @@ __global__ __launch_bounds__(64) void face_boxes_runs_kernel(const BoxSeg* __res
     }
     const int* fl = flags + s.row0;
     int* bx = boxes + (long long)s.row0 * 4;
-    int* vd = valid + s.row0;
-    const int host = first_host_row(fl, s.n);
-    if (host != 0x7fffffff) {                            // uniform: left to the host, as face_boxes_segments_kernel leaves it
+    int* vd = kStrict ? nullptr : valid + s.row0;
+    int host, none;
+    first_unfound_rows(fl, s.n, &host, &none);
+    const bool is_host = host != 0x7fffffff;
+    if (is_host || (kStrict && none != 0x7fffffff)) {    // uniform: left to the host, or to the caller's "Face not detected"
         for (int i = lane; i < 4 * s.n; i += 64) bx[i] = 0;
-        for (int i = lane; i < s.n; i += 64) vd[i] = 0;
-        if (lane == 0) { st[0] = 2; st[1] = host; }
+        for (int i = lane; vd && i < s.n; i += 64) vd[i] = 0;
+        if (lane == 0) { st[0] = is_host ? 2 : 1; st[1] = is_host ? host : none; }
         return;
     }
     if (lane == 0) { st[0] = 0; st[1] = 0; }
     long long p;
-    face_boxes_runs_wave(s, rects + (long long)s.row0 * 4, fl, 0, s.n, true, 0, kHoldMax + 1, top, bottom, left, right, max(T, 1), hold,
-                         0, s.n, bx, vd, nullptr, s_ring, s_win, &p);
+    face_boxes_runs_wave(s, rects + (long long)s.row0 * 4, fl, 0, s.n, true, 0, kHoldMax + 1, top, bottom, left, right, max(T, 1),
+                         kStrict ? 0 : hold, 0, s.n, bx, vd, nullptr, s_ring, s_win, &p);
 }
 
+// kStrict as above; the carry slot is then [kBoxMaxT][4] raw rects of the last max(T, 1) frames, every one of them boxed
+template <bool kStrict>
 __global__ __launch_bounds__(64) void face_boxes_stream_runs_kernel(const BoxStreamSeg* __restrict__ segs, const int* __restrict__ rects,
                                                                     const int* __restrict__ flags, int n_rows, int* __restrict__ carry,
                                                                     int n_slots, int top, int bottom, int left, int right, int T,
                                                                     int hold, int* __restrict__ boxes, int* __restrict__ valid,
                                                                     int n_out, int* __restrict__ status) {
-    __shared__ int s_carry[kRunsCarryRows][5];
+    constexpr int kCols = kStrict ? 4 : 5;               // words of a carried row
+    __shared__ int s_carry[kStrict ? kBoxMaxT : kRunsCarryRows][5];
     __shared__ int s_ring[kRunsRing][5];
     __shared__ int s_win[kBoxMaxT][4];
     const int lane = threadIdx.x;
@@ -755,27 +607,35 @@ __global__ __launch_bounds__(64) void face_boxes_stream_runs_kernel(const BoxStr
         return;
     }
     const int* fl = flags + s.row0;
-    const int host = first_host_row(fl, s.n_new);
-    if (host != 0x7fffffff) {                            // uniform: no box written, the carry left as it was
-        if (lane == 0) { st[0] = 2; st[1] = s.seen + host; }
+    int host, none;
+    first_unfound_rows(fl, s.n_new, &host, &none);
+    const bool is_host = host != 0x7fffffff;
+    if (is_host || (kStrict && none != 0x7fffffff)) {    // uniform: no box written, the carry left as it was
+        if (lane == 0) { st[0] = is_host ? 2 : 1; st[1] = s.seen + (is_host ? host : none); }
         return;
     }
     if (lane == 0) { st[0] = 0; st[1] = 0; }
-    const int c = min(s.seen, 2 * Tm);                   // carried rows: frames [seen - c, seen)
-    int* slot = carry + (long long)s.slot * kRunsCarryInts;
-    for (int i = lane; i < c * 5; i += 64) s_carry[i / 5][i % 5] = slot[i];
-    const int dist0 = min(max(slot[kRunsCarryRows * 5], 0), kHoldMax + 1);
+    const int reach = kStrict ? Tm : 2 * Tm;
+    const int c = min(s.seen, reach);                    // carried rows: frames [seen - c, seen)
+    int* slot = carry + (long long)s.slot * (kStrict ? kBoxMaxT * 4 : kRunsCarryInts);
+    for (int i = lane; i < c * kCols; i += 64) s_carry[i / kCols][i % kCols] = slot[i];
+    int dist0 = kHoldMax + 1;                            // frames since the last detection: beyond any hold
+    if constexpr (kStrict) {
+        if (lane < c) s_carry[lane][4] = 1;
+    } else if (s.seen > 0) {
+        dist0 = min(max(slot[kRunsCarryRows * 5], 0), kHoldMax + 1);
+    }
     __syncthreads();
     long long p;
-    face_boxes_runs_wave(s, rects + (long long)s.row0 * 4, fl, s.seen, n, s.closed != 0, c, s.seen > 0 ? dist0 : kHoldMax + 1, top,
-                         bottom, left, right, Tm, hold, lo, hi, boxes + (long long)s.out0 * 4, valid + s.out0, s_carry, s_ring, s_win,
-                         &p);
-    // the next tick's carry: the last min(n, 2 * max(T, 1)) rows, which the ring still holds, and the distance from the detection
-    const int keep = (int)min(n, (long long)(2 * Tm));
+    face_boxes_runs_wave(s, rects + (long long)s.row0 * 4, fl, s.seen, n, s.closed != 0, c, dist0, top, bottom, left, right, Tm,
+                         kStrict ? 0 : hold, lo, hi, boxes + (long long)s.out0 * 4, kStrict ? nullptr : valid + s.out0, s_carry,
+                         s_ring, s_win, &p);
+    // the next tick's carry: the last min(n, reach) rows, which the ring still holds, and the distance from the detection
+    const int keep = (int)min(n, (long long)reach);
     const long long f0 = (long long)s.seen - c;
-    for (int i = lane; i < keep * 5; i += 64) slot[i] = s_ring[(int)((n - keep + i / 5 - f0) % kRunsRing)][i % 5];
-    if (lane == 0) {
-        const long long d = p >= s.seen ? n - 1 - p : (long long)(s.seen > 0 ? dist0 : kHoldMax + 1) + s.n_new;
+    for (int i = lane; i < keep * kCols; i += 64) slot[i] = s_ring[(int)((n - keep + i / kCols - f0) % kRunsRing)][i % kCols];
+    if (!kStrict && lane == 0) {
+        const long long d = p >= s.seen ? n - 1 - p : (long long)dist0 + s.n_new;
         slot[kRunsCarryRows * 5] = (int)min(d, (long long)(kHoldMax + 1));
     }
 }
@@ -919,14 +779,23 @@ int w2l_s3fd_first_rect_scaled(void* stream, int B, int P, const float* table, c
     return W2L_OK;
 }
 
+// the argument checks the four box finishes share (`name` opens the messages; `pointers`: none of the entry's pointers is NULL)
+static int face_boxes_check(const char* name, bool pointers, int n_seg, const void* segs, int T, int hold) {
+    W2L_REQUIRE(pointers, "%s: NULL argument", name);
+    W2L_REQUIRE(n_seg >= 1, "%s: n_seg=%d must be at least 1", name, n_seg);
+    W2L_REQUIRE(T >= 0 && T <= kBoxMaxT, "%s: T=%d outside 0..%d", name, T, kBoxMaxT);
+    W2L_REQUIRE(hold >= 0 && hold <= kHoldMax, "%s: hold=%d outside 0..%d", name, hold, kHoldMax);
+    W2L_REQUIRE((reinterpret_cast<uintptr_t>(segs) & 15) == 0, "%s: the segment table must be 16-byte aligned", name);
+    return W2L_OK;
+}
+
+// the clip form of the strict finish names no arena size: its segments are followed as they stand
 int w2l_face_boxes_segments(void* stream, int n_seg, const w2l_box_segment* segs, const int32_t* rects, const int32_t* flags,
                             int top, int bottom, int left, int right, int T, int32_t* boxes, int32_t* status) {
-    W2L_REQUIRE(segs && rects && flags && boxes && status, "face_boxes_segments: NULL argument");
-    W2L_REQUIRE(n_seg >= 1, "face_boxes_segments: n_seg=%d must be at least 1", n_seg);
-    W2L_REQUIRE(T >= 0 && T <= kBoxMaxT, "face_boxes_segments: T=%d outside 0..%d", T, kBoxMaxT);
-    W2L_REQUIRE((reinterpret_cast<uintptr_t>(segs) & 15) == 0, "face_boxes_segments: the segment table must be 16-byte aligned");
-    hipLaunchKernelGGL(face_boxes_segments_kernel, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
-                       reinterpret_cast<const BoxSeg*>(segs), rects, flags, top, bottom, left, right, T, boxes, status);
+    if (int e = face_boxes_check("face_boxes_segments", segs && rects && flags && boxes && status, n_seg, segs, T, 0)) return e;
+    hipLaunchKernelGGL(face_boxes_runs_kernel<true>, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const BoxSeg*>(segs), rects, flags, 0x7fffffff, top, bottom, left, right, T, 0, boxes,
+                       static_cast<int*>(nullptr), status);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }
@@ -934,6 +803,7 @@ int w2l_face_boxes_segments(void* stream, int n_seg, const w2l_box_segment* segs
 // the checks of a tick's segment table on its host copy, shared by the two stream finishes (`name` opens the messages)
 static int box_stream_table_check(const char* name, int n_seg, const w2l_box_stream_segment* segs_host, int n_rows, int n_slots, int T,
                                   int n_out) {
+    W2L_REQUIRE(n_rows >= 0 && n_slots >= 1 && n_out >= 0, "%s: n_rows=%d, n_slots=%d, n_out=%d", name, n_rows, n_slots, n_out);
     // a tick has a segment per live stream: the pairwise checks below are a few thousand comparisons, and allocate nothing
     for (int k = 0; k < n_seg; ++k) {
         const w2l_box_stream_segment& s = segs_host[k];
@@ -961,27 +831,21 @@ static int box_stream_table_check(const char* name, int n_seg, const w2l_box_str
 int w2l_face_boxes_stream(void* stream, int n_seg, const w2l_box_stream_segment* segs_host, const w2l_box_stream_segment* segs,
                           const int32_t* rects, const int32_t* flags, int n_rows, int32_t* carry, int n_slots, int top, int bottom,
                           int left, int right, int T, int32_t* boxes, int n_out, int32_t* status) {
-    W2L_REQUIRE(segs_host && segs && rects && flags && carry && boxes && status, "face_boxes_stream: NULL argument");
-    W2L_REQUIRE(n_seg >= 1, "face_boxes_stream: n_seg=%d must be at least 1", n_seg);
-    W2L_REQUIRE(T >= 0 && T <= kBoxMaxT, "face_boxes_stream: T=%d outside 0..%d", T, kBoxMaxT);
-    W2L_REQUIRE(n_rows >= 0 && n_slots >= 1 && n_out >= 0, "face_boxes_stream: n_rows=%d, n_slots=%d, n_out=%d", n_rows, n_slots, n_out);
-    W2L_REQUIRE((reinterpret_cast<uintptr_t>(segs) & 15) == 0, "face_boxes_stream: the segment table must be 16-byte aligned");
+    if (int e = face_boxes_check("face_boxes_stream", segs_host && segs && rects && flags && carry && boxes && status, n_seg, segs, T, 0))
+        return e;
     if (int e = box_stream_table_check("face_boxes_stream", n_seg, segs_host, n_rows, n_slots, T, n_out)) return e;
-    hipLaunchKernelGGL(face_boxes_stream_kernel, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(face_boxes_stream_runs_kernel<true>, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const BoxStreamSeg*>(segs), rects, flags, n_rows, carry, n_slots, top, bottom, left, right, T,
-                       boxes, n_out, status);
+                       0, boxes, static_cast<int*>(nullptr), n_out, status);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }
 
 int w2l_face_boxes_runs(void* stream, int n_seg, const w2l_box_segment* segs, const int32_t* rects, const int32_t* flags, int n_rows,
                         int top, int bottom, int left, int right, int T, int hold, int32_t* boxes, int32_t* valid, int32_t* status) {
-    W2L_REQUIRE(segs && rects && flags && boxes && valid && status, "face_boxes_runs: NULL argument");
-    W2L_REQUIRE(n_seg >= 1 && n_rows >= 0, "face_boxes_runs: n_seg=%d must be at least 1 and n_rows=%d at least 0", n_seg, n_rows);
-    W2L_REQUIRE(T >= 0 && T <= kBoxMaxT, "face_boxes_runs: T=%d outside 0..%d", T, kBoxMaxT);
-    W2L_REQUIRE(hold >= 0 && hold <= kHoldMax, "face_boxes_runs: hold=%d outside 0..%d", hold, kHoldMax);
-    W2L_REQUIRE((reinterpret_cast<uintptr_t>(segs) & 15) == 0, "face_boxes_runs: the segment table must be 16-byte aligned");
-    hipLaunchKernelGGL(face_boxes_runs_kernel, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
+    if (int e = face_boxes_check("face_boxes_runs", segs && rects && flags && boxes && valid && status, n_seg, segs, T, hold)) return e;
+    W2L_REQUIRE(n_rows >= 0, "face_boxes_runs: n_seg=%d must be at least 1 and n_rows=%d at least 0", n_seg, n_rows);
+    hipLaunchKernelGGL(face_boxes_runs_kernel<false>, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const BoxSeg*>(segs), rects, flags, n_rows, top, bottom, left, right, T, hold, boxes, valid,
                        status);
     W2L_HIP_CHECK(hipGetLastError());
@@ -991,15 +855,11 @@ int w2l_face_boxes_runs(void* stream, int n_seg, const w2l_box_segment* segs, co
 int w2l_face_boxes_stream_runs(void* stream, int n_seg, const w2l_box_stream_segment* segs_host, const w2l_box_stream_segment* segs,
                                const int32_t* rects, const int32_t* flags, int n_rows, int32_t* carry, int n_slots, int top, int bottom,
                                int left, int right, int T, int hold, int32_t* boxes, int32_t* valid, int n_out, int32_t* status) {
-    W2L_REQUIRE(segs_host && segs && rects && flags && carry && boxes && valid && status, "face_boxes_stream_runs: NULL argument");
-    W2L_REQUIRE(n_seg >= 1, "face_boxes_stream_runs: n_seg=%d must be at least 1", n_seg);
-    W2L_REQUIRE(T >= 0 && T <= kBoxMaxT, "face_boxes_stream_runs: T=%d outside 0..%d", T, kBoxMaxT);
-    W2L_REQUIRE(hold >= 0 && hold <= kHoldMax, "face_boxes_stream_runs: hold=%d outside 0..%d", hold, kHoldMax);
-    W2L_REQUIRE(n_rows >= 0 && n_slots >= 1 && n_out >= 0, "face_boxes_stream_runs: n_rows=%d, n_slots=%d, n_out=%d", n_rows, n_slots,
-                n_out);
-    W2L_REQUIRE((reinterpret_cast<uintptr_t>(segs) & 15) == 0, "face_boxes_stream_runs: the segment table must be 16-byte aligned");
+    if (int e = face_boxes_check("face_boxes_stream_runs", segs_host && segs && rects && flags && carry && boxes && valid && status, n_seg,
+                                 segs, T, hold))
+        return e;
     if (int e = box_stream_table_check("face_boxes_stream_runs", n_seg, segs_host, n_rows, n_slots, T, n_out)) return e;
-    hipLaunchKernelGGL(face_boxes_stream_runs_kernel, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(face_boxes_stream_runs_kernel<false>, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const BoxStreamSeg*>(segs), rects, flags, n_rows, carry, n_slots, top, bottom, left, right, T,
                        hold, boxes, valid, n_out, status);
     W2L_HIP_CHECK(hipGetLastError());

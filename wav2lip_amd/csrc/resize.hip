@@ -26,22 +26,6 @@ __global__ void crop_resize_kernel(int B, const uint8_t* __restrict__ frames, in
     }
 }
 
-__global__ void resize_paste_kernel(int B, const uint8_t* __restrict__ pred, int S, const int32_t* __restrict__ boxes,
-                                    const int32_t* __restrict__ frame_idx, uint8_t* __restrict__ frames, int H, int W) {
-    const int b = blockIdx.y;
-    const int4 box = *reinterpret_cast<const int4*>(boxes + 4 * b);
-    const int fo = frame_idx ? frame_idx[b] : b;
-    const int h = box.y - box.x, w = box.w - box.z;
-    const uint8_t* src = pred + (long long)b * S * S * 3;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < h * w; i += gridDim.x * blockDim.x) {
-        const int dy = i / w, dx = i - dy * w;
-        uint8_t px[3];
-        resize_px(src, (long long)S * 3, S, S, dx, dy, w, h, px);
-        uint8_t* o = frames + (((long long)fo * H + box.x + dy) * W + box.z + dx) * 3;
-        o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
-    }
-}
-
 // whole-frame resize (inference.py:203: `cv2.resize(frame, (w // resize_factor, h // resize_factor))`)
 __global__ void resize_frames_kernel(int B, const uint8_t* __restrict__ src, int Hs, int Ws, uint8_t* __restrict__ dst,
                                      int Hd, int Wd) {
@@ -79,55 +63,9 @@ __global__ void crop_resize_rows_kernel(int B, const FrameRow* __restrict__ rows
     }
 }
 
-// One pass over the whole output frame: a thread owns 4 consecutive pixels (12 bytes = 3 dwords of the flattened frame).  A
-// group that lies outside the box in 4-byte aligned frames moves as three dwords (skipped when the paste is in place); any
-// other group goes pixel by pixel, box pixels from the resized prediction.  HBM-bound byte traffic, no LDS.
-__global__ void compose_rows_kernel(int B, const uint8_t* __restrict__ pred, int S, const FrameRow* __restrict__ rows) {
-    const int b = blockIdx.y;
-    const FrameRow r = rows[b];
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(r.src);
-    uint8_t* dst = reinterpret_cast<uint8_t*>(r.dst);
-    const uint8_t* p = pred + (long long)b * S * S * 3;
-    const int h = r.y2 - r.y1, w = r.x2 - r.x1;
-    const int npx = r.H * r.W;                          // < 2^31 / 3 (checked by the caller's max_frame_pixels)
-    const int ngroups = (npx + 3) >> 2;
-    const bool in_place = src == dst;
-    const bool dwords = (((r.src | r.dst) & 3) == 0);
-    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += gridDim.x * blockDim.x) {
-        const int i0 = g << 2, i1 = min(i0 + 4, npx);
-        const int ya = i0 / r.W, xa = i0 - ya * r.W;
-        const int yb = (i1 - 1) / r.W, xb = (i1 - 1) - yb * r.W;
-        // the group touches the box iff one of its frame rows does within its span of columns (frames narrower than 4 pixels,
-        // where a group can span three rows or more, take the per-pixel path)
-        const bool a_in = ya >= r.y1 && ya < r.y2 && xa < r.x2 && (ya == yb ? xb : r.W - 1) >= r.x1;
-        const bool b_in = yb != ya && yb >= r.y1 && yb < r.y2 && xb >= r.x1;
-        if (r.W >= 4 && !a_in && !b_in) {
-            if (in_place) continue;
-            if (dwords && i1 - i0 == 4) {
-                const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src + (long long)i0 * 3);
-                uint32_t* d4 = reinterpret_cast<uint32_t*>(dst + (long long)i0 * 3);
-                const uint32_t v0 = s4[0], v1 = s4[1], v2 = s4[2];
-                d4[0] = v0; d4[1] = v1; d4[2] = v2;
-                continue;
-            }
-        }
-        for (int i = i0; i < i1; ++i) {
-            const int y = i / r.W, x = i - y * r.W;
-            uint8_t* o = dst + (long long)i * 3;
-            if (y >= r.y1 && y < r.y2 && x >= r.x1 && x < r.x2) {
-                uint8_t px[3];
-                resize_px(p, (long long)S * 3, S, S, x - r.x1, y - r.y1, w, h, px);
-                o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
-            } else if (!in_place) {
-                const uint8_t* q = src + (long long)i * 3;
-                o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
-            }
-        }
-    }
-}
-
-// ---- feathered, mouth-region paste (opt-in; not the reference's output): the blend forms of the two paste kernels above.
-// Integers only.  Per box of h x w pixels, feather F (0..64) and top_q8 T (0..255):
+// ---- the paste-back, plain (the reference's) and with the feathered, mouth-region blend (opt-in; not the reference's output):
+// one body per kernel, two instantiations; the plain one computes nothing of the blend.  Integers only.  Per box of h x w
+// pixels, feather F (0..64) and top_q8 T (0..255):
 //   t0 = (h*T) >> 8, hr = h - t0 (>= 1), Fe = min(F, (min(w, hr) - 1) / 2), D = (Fe+1)^2
 //   wy(j) = 0 for j < t0, else min(Fe+1, j-t0+1, h-j);  wx(i) = min(Fe+1, i+1, w-i);  a = wx*wy
 //   out_c = (a*p_c + (D-a)*o_c + D/2) / D, p = resize_px (unchanged), o = the frame's own pixel
@@ -164,37 +102,44 @@ __device__ __forceinline__ void blend_px(const BlendBox& k, uint32_t a, const ui
         px[c] = (uint8_t)__umulhi(a * px[c] + (k.D - a) * o[c] + (k.D >> 1), k.magic);
 }
 
-__global__ void resize_blend_kernel(int B, const uint8_t* __restrict__ pred, int S, const int32_t* __restrict__ boxes,
+template <bool kBlend>      // false: feather and top_q8 are not read
+__global__ void resize_paste_kernel(int B, const uint8_t* __restrict__ pred, int S, const int32_t* __restrict__ boxes,
                                     const int32_t* __restrict__ frame_idx, uint8_t* frames, int H, int W, int feather,
                                     int top_q8) {
     const int b = blockIdx.y;
     const int4 box = *reinterpret_cast<const int4*>(boxes + 4 * b);
     const int fo = frame_idx ? frame_idx[b] : b;
     const int h = box.y - box.x, w = box.w - box.z;
-    const BlendBox k = blend_box(h, w, feather, top_q8);
+    BlendBox k = {};
+    if constexpr (kBlend) k = blend_box(h, w, feather, top_q8);
     const uint8_t* src = pred + (long long)b * S * S * 3;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < (h - k.t0) * w; i += gridDim.x * blockDim.x) {
         const int dy = k.t0 + i / w, dx = i - (dy - k.t0) * w;
         uint8_t px[3];
         resize_px(src, (long long)S * 3, S, S, dx, dy, w, h, px);
         uint8_t* o = frames + (((long long)fo * H + box.x + dy) * W + box.z + dx) * 3;
-        blend_px(k, blend_weight(k, dx, dy, h, w), o, px);
+        if constexpr (kBlend) blend_px(k, blend_weight(k, dx, dy, h, w), o, px);
         o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
     }
 }
 
-// compose_rows_kernel with the blend: the same groups, the three-dword move for every group that misses the blended part of the
-// box (rows y1 + t0 .. y2); a box pixel reads o from src and writes dst in one thread, so src == dst stays in place
-__global__ void compose_blend_rows_kernel(int B, const uint8_t* __restrict__ pred, int S, const FrameRow* __restrict__ rows,
-                                          int feather, int top_q8) {
+// One pass over the whole output frame: a thread owns 4 consecutive pixels (12 bytes = 3 dwords of the flattened frame).  A
+// group that lies outside the box in 4-byte aligned frames moves as three dwords (skipped when the paste is in place); any
+// other group goes pixel by pixel, box pixels from the resized prediction.  HBM-bound byte traffic, no LDS.  With the blend the
+// box is its blended part (rows y1 + t0 .. y2); a box pixel reads o from src and writes dst in one thread, so src == dst stays
+// in place.
+template <bool kBlend>      // false: feather and top_q8 are not read
+__global__ void compose_rows_kernel(int B, const uint8_t* __restrict__ pred, int S, const FrameRow* __restrict__ rows, int feather,
+                                    int top_q8) {
     const int b = blockIdx.y;
     const FrameRow r = rows[b];
     const uint8_t* src = reinterpret_cast<const uint8_t*>(r.src);
     uint8_t* dst = reinterpret_cast<uint8_t*>(r.dst);
     const uint8_t* p = pred + (long long)b * S * S * 3;
     const int h = r.y2 - r.y1, w = r.x2 - r.x1;
-    const BlendBox k = blend_box(h, w, feather, top_q8);
-    const int y1 = r.y1 + k.t0;                         // first blended frame row
+    BlendBox k = {};
+    if constexpr (kBlend) k = blend_box(h, w, feather, top_q8);
+    const int y1 = r.y1 + k.t0;                         // first pasted frame row
     const int npx = r.H * r.W;                          // < 2^31 / 3 (checked by the caller's max_frame_pixels)
     const int ngroups = (npx + 3) >> 2;
     const bool in_place = src == dst;
@@ -203,6 +148,8 @@ __global__ void compose_blend_rows_kernel(int B, const uint8_t* __restrict__ pre
         const int i0 = g << 2, i1 = min(i0 + 4, npx);
         const int ya = i0 / r.W, xa = i0 - ya * r.W;
         const int yb = (i1 - 1) / r.W, xb = (i1 - 1) - yb * r.W;
+        // the group touches the box iff one of its frame rows does within its span of columns (frames narrower than 4 pixels,
+        // where a group can span three rows or more, take the per-pixel path)
         const bool a_in = ya >= y1 && ya < r.y2 && xa < r.x2 && (ya == yb ? xb : r.W - 1) >= r.x1;
         const bool b_in = yb != ya && yb >= y1 && yb < r.y2 && xb >= r.x1;
         if (r.W >= 4 && !a_in && !b_in) {
@@ -222,7 +169,7 @@ __global__ void compose_blend_rows_kernel(int B, const uint8_t* __restrict__ pre
             if (y >= y1 && y < r.y2 && x >= r.x1 && x < r.x2) {
                 uint8_t px[3];
                 resize_px(p, (long long)S * 3, S, S, x - r.x1, y - r.y1, w, h, px);
-                blend_px(k, blend_weight(k, x - r.x1, y - r.y1, h, w), q, px);
+                if constexpr (kBlend) blend_px(k, blend_weight(k, x - r.x1, y - r.y1, h, w), q, px);
                 o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
             } else if (!in_place) {
                 o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
@@ -300,6 +247,34 @@ __global__ __launch_bounds__(256) void resize_rows_kernel(int B, const ResizeRow
 
 using namespace w2l;
 
+// the plain and the blend entry of each paste share a launcher (`name` opens the messages; blend: the <true> instantiation)
+static int resize_paste_launch(const char* name, bool blend, void* stream, int B, const uint8_t* pred, int S, const int32_t* boxes,
+                               const int32_t* frame_idx, uint8_t* frames, int H, int W, int max_box_pixels, int feather, int top_q8) {
+    W2L_REQUIRE(pred && boxes && frames && B >= 1 && H >= 1 && W >= 1 && S >= 1 && max_box_pixels >= 1, "bad %s arguments", name);
+    W2L_REQUIRE(B <= 65535 && (reinterpret_cast<uintptr_t>(boxes) & 15) == 0, "%s: B <= 65535 and 16-byte aligned boxes", name);
+    W2L_REQUIRE(feather >= 0 && feather <= 64 && top_q8 >= 0 && top_q8 <= 255, "%s: feather in [0, 64], top_q8 in [0, 255]", name);
+    int gx = ceil_div(max_box_pixels, 256);
+    if (gx > 256) gx = 256;
+    hipLaunchKernelGGL(blend ? resize_paste_kernel<true> : resize_paste_kernel<false>, dim3(gx, B), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), B, pred, S, boxes, frame_idx, frames, H, W, feather, top_q8);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+static int compose_rows_launch(const char* name, bool blend, void* stream, int B, const uint8_t* pred, int S, const w2l_frame_row* rows,
+                               int max_frame_pixels, int feather, int top_q8) {
+    W2L_REQUIRE(pred && rows && S >= 1 && max_frame_pixels >= 1 && max_frame_pixels <= (1 << 29), "bad %s arguments", name);
+    W2L_REQUIRE(B >= 1 && B <= 65535 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0,
+                "%s: 1 <= B <= 65535 and a 16-byte aligned row table", name);
+    W2L_REQUIRE(feather >= 0 && feather <= 64 && top_q8 >= 0 && top_q8 <= 255, "%s: feather in [0, 64], top_q8 in [0, 255]", name);
+    int gx = ceil_div(ceil_div(max_frame_pixels, 4), 256);
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(blend ? compose_rows_kernel<true> : compose_rows_kernel<false>, dim3(gx, B), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), B, pred, S, reinterpret_cast<const FrameRow*>(rows), feather, top_q8);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
 extern "C" {
 
 int w2l_crop_resize_u8(void* stream, int B, const uint8_t* frames, int H, int W, const int32_t* frame_idx,
@@ -327,15 +302,13 @@ int w2l_resize_u8(void* stream, int B, const uint8_t* src, int Hs, int Ws, uint8
 
 int w2l_resize_paste_u8(void* stream, int B, const uint8_t* pred, int S, const int32_t* boxes, const int32_t* frame_idx,
                         uint8_t* frames, int H, int W, int max_box_pixels) {
-    W2L_REQUIRE(pred && boxes && frames && B >= 1 && H >= 1 && W >= 1 && S >= 1 && max_box_pixels >= 1,
-                "bad resize_paste arguments");
-    W2L_REQUIRE(B <= 65535 && (reinterpret_cast<uintptr_t>(boxes) & 15) == 0, "resize_paste: B <= 65535 and 16-byte aligned boxes");
-    int gx = ceil_div(max_box_pixels, 256);
-    if (gx > 256) gx = 256;
-    hipLaunchKernelGGL(resize_paste_kernel, dim3(gx, B), dim3(256), 0, static_cast<hipStream_t>(stream), B, pred, S, boxes,
-                       frame_idx, frames, H, W);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
+    return resize_paste_launch("resize_paste", false, stream, B, pred, S, boxes, frame_idx, frames, H, W, max_box_pixels, 0, 0);
+}
+
+int w2l_resize_blend_u8(void* stream, int B, const uint8_t* pred, int S, const int32_t* boxes, const int32_t* frame_idx,
+                        uint8_t* frames, int H, int W, int max_box_pixels, int feather, int top_q8) {
+    return resize_paste_launch("resize_blend", true, stream, B, pred, S, boxes, frame_idx, frames, H, W, max_box_pixels, feather,
+                               top_q8);
 }
 
 int w2l_crop_resize_rows_u8(void* stream, int B, const w2l_frame_row* rows, int S, uint8_t* out) {
@@ -351,44 +324,12 @@ int w2l_crop_resize_rows_u8(void* stream, int B, const w2l_frame_row* rows, int 
 }
 
 int w2l_compose_rows_u8(void* stream, int B, const uint8_t* pred, int S, const w2l_frame_row* rows, int max_frame_pixels) {
-    W2L_REQUIRE(pred && rows && S >= 1 && max_frame_pixels >= 1 && max_frame_pixels <= (1 << 29), "bad compose_rows arguments");
-    W2L_REQUIRE(B >= 1 && B <= 65535 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0,
-                "compose_rows: 1 <= B <= 65535 and a 16-byte aligned row table");
-    int gx = ceil_div(ceil_div(max_frame_pixels, 4), 256);
-    if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(compose_rows_kernel, dim3(gx, B), dim3(256), 0, static_cast<hipStream_t>(stream), B, pred, S,
-                       reinterpret_cast<const FrameRow*>(rows));
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
-}
-
-int w2l_resize_blend_u8(void* stream, int B, const uint8_t* pred, int S, const int32_t* boxes, const int32_t* frame_idx,
-                        uint8_t* frames, int H, int W, int max_box_pixels, int feather, int top_q8) {
-    W2L_REQUIRE(pred && boxes && frames && B >= 1 && H >= 1 && W >= 1 && S >= 1 && max_box_pixels >= 1,
-                "bad resize_blend arguments");
-    W2L_REQUIRE(B <= 65535 && (reinterpret_cast<uintptr_t>(boxes) & 15) == 0, "resize_blend: B <= 65535 and 16-byte aligned boxes");
-    W2L_REQUIRE(feather >= 0 && feather <= 64 && top_q8 >= 0 && top_q8 <= 255, "resize_blend: feather in [0, 64], top_q8 in [0, 255]");
-    int gx = ceil_div(max_box_pixels, 256);
-    if (gx > 256) gx = 256;
-    hipLaunchKernelGGL(resize_blend_kernel, dim3(gx, B), dim3(256), 0, static_cast<hipStream_t>(stream), B, pred, S, boxes,
-                       frame_idx, frames, H, W, feather, top_q8);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
+    return compose_rows_launch("compose_rows", false, stream, B, pred, S, rows, max_frame_pixels, 0, 0);
 }
 
 int w2l_compose_blend_rows_u8(void* stream, int B, const uint8_t* pred, int S, const w2l_frame_row* rows, int max_frame_pixels,
                               int feather, int top_q8) {
-    W2L_REQUIRE(pred && rows && S >= 1 && max_frame_pixels >= 1 && max_frame_pixels <= (1 << 29), "bad compose_blend_rows arguments");
-    W2L_REQUIRE(B >= 1 && B <= 65535 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0,
-                "compose_blend_rows: 1 <= B <= 65535 and a 16-byte aligned row table");
-    W2L_REQUIRE(feather >= 0 && feather <= 64 && top_q8 >= 0 && top_q8 <= 255,
-                "compose_blend_rows: feather in [0, 64], top_q8 in [0, 255]");
-    int gx = ceil_div(ceil_div(max_frame_pixels, 4), 256);
-    if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(compose_blend_rows_kernel, dim3(gx, B), dim3(256), 0, static_cast<hipStream_t>(stream), B, pred, S,
-                       reinterpret_cast<const FrameRow*>(rows), feather, top_q8);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
+    return compose_rows_launch("compose_blend_rows", true, stream, B, pred, S, rows, max_frame_pixels, feather, top_q8);
 }
 
 int w2l_resize_rows_u8(void* stream, int B, const w2l_resize_row* rows, int max_dst_pixels) {
