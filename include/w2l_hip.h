@@ -38,6 +38,10 @@
  *   w2l_s3fd_pack_rows_scaled  inference.py:202-203 (the `cv2.resize(frame, (w // k, h // k))` of --resize_factor) fused into the
  *                         detector's input: detection at reduced size, output frames untouched (--face_det_scale)
  *   w2l_s3fd_first_rect_scaled  face_detection/api.py:61-77 with the rect mapped back to the full frame first
+ *   w2l_s3fd_top_rects    face_detection/detection/sfd/sfd_detector.py:45 + api.py:61-77 for the first K kept boxes above 0.5, where
+ *                         the reference keeps d[0] alone (opt-in: `face_track`)
+ *   w2l_face_track_segments  api.py:61-77's choice of one box per frame, made over the clip instead: a face is followed from
+ *                         frame to frame by overlap (opt-in, not the reference's rule: `face_track`)
  *   w2l_face_boxes_segments  evaluation/gen_videos_from_filelist.py:35-42, :61-77 = inference.py:59-66, :90-104 (pads, clipping,
  *                         "Face not detected", get_smoothened_boxes) for every clip of a group in one launch
  *   w2l_face_boxes_stream  inference.py:59-66, :90-104 for live streams: the same boxes, written tick by tick as frames arrive
@@ -499,6 +503,52 @@ int w2l_s3fd_first_rect(void* stream, int B, int P, const float* table, const in
  * Refused: sx or sy that is not finite and positive. */
 int w2l_s3fd_first_rect_scaled(void* stream, int B, int P, const float* table, const int* keep, const int* counts, float thresh,
                                float sx, float sy, int* rects, int* flags);
+
+/* Tracked face selection (opt-in `face_track`; the reference takes d[0] of every frame, api.py:61-77 after
+ * sfd_detector.py:45, which changes hands between two people in the picture).  Two launches between w2l_s3fd_nms and the box finishes.
+ *
+ * w2l_s3fd_top_rects: the CANDIDATES of each image - the first K rows of keep[b][:counts[b]], in keep order, whose score is
+ * > thresh, each converted as w2l_s3fd_first_rect[_scaled] converts its one row (x * sx, y * sy in fp32, round to nearest, no
+ * contraction; sx = sy = 1 gives the unscaled bits; clip at 0; truncation) -> cands [B][K][4] int32 (x1, y1, x2, y2), unused
+ * slots zeros, ncand [B], flags [B]: 1 with at least one candidate, 0 with none, 2 the host must decide (no candidates written) -
+ * counts[b] not in [0, P], a keep entry outside [0, P) among those examined (up to and including the K-th passing row; rows after
+ * it are not looked at), or a coordinate of a taken candidate that is NaN or, after the clip and the truncation, above 32767 (so
+ * +inf and >= 2^31 too).  That bound keeps every product of the track exact in int64.  Zero-area candidates are kept.  Candidate 0
+ * of an image flagged 1 is w2l_s3fd_first_rect's rect.  Refused: a NULL pointer, B or P < 1, B * P * 5 >= 2^31, sx or sy not
+ * finite and positive, K outside 1..16.
+ *
+ * w2l_face_track_segments: one candidate per frame, followed through the frames of a segment in order.  cands [n_rows][K][4],
+ * ncand [n_rows] and cflags [n_rows] are arenas w2l_s3fd_top_rects filled (coordinates in 0..32767); rects [n_rows][4] and
+ * flags [n_rows] come out in w2l_s3fd_first_rect's format, so the four box finishes below take them unchanged.
+ *
+ * w2l_track_segment, 16 bytes, the table 16-byte aligned:
+ *   bytes 0..7   int32 row0, n     the segment's rows [row0, row0 + n) of the arenas (n = 0: no frame; the state is carried on)
+ *   bytes 8..15  int32 slot, seen  slot -1: no carried state (a clip).  slot >= 0: the state is read from state[slot] when
+ *                                  seen > 0 (frames of this stream before the segment; 0: a fresh state) and ALWAYS written back
+ *
+ * The state is (ref rect, has, missed), fresh = no track.  state [n_slots][8] int32 = (x1, y1, x2, y2, has, missed, 0, 0), zeros
+ * without a track.  With pick 0 score, 1 largest, 2 left, 3 right; L in 0..250 missed frames tolerated; q in 1..256 (min IoU q/256):
+ *   - a frame flagged neither 0 nor 1: flag 2, rect zeros, the state unchanged.
+ *   - inter = max(0, min(x2) - max(x1)) * max(0, min(y2) - max(y1)), union = area(c) + area(ref) - inter, area = (x2 - x1) *
+ *     (y2 - y1), no + 1, all integers (not the float expression of the NMS).  Candidate c OVERLAPS when inter > 0 and
+ *     inter * 256 >= q * union.
+ *   - with a track: the overlapping candidate of the largest IoU (inter_a * union_b > inter_b * union_a in int64; ties to the
+ *     lower index) is the frame's rect, flag 1, becomes ref, missed = 0.  None: missed += 1; while missed <= L the frame is flag 0
+ *     with zeros; once missed > L the track is dropped and the SAME frame seeds a new one.
+ *   - without a track: no candidate -> flag 0, zeros; else the seed by pick - candidate 0; the largest area; the smallest
+ *     x1 + x2; the largest x1 + x2; every tie to the lower index - is the rect, flag 1, ref, has = 1, missed = 0.
+ * With L = 0 a frame that has a candidate is never flag 0.  status [n_seg] int32: 0, or 3 for a segment with rows outside
+ * [0, n_rows), n < 0, seen < 0 or a slot outside [-1, n_slots) - nothing else of it is read or written.  A segment writes its own
+ * rows and its own slot's eight words only.  Refused: a NULL pointer (state may be NULL with n_slots = 0), n_seg < 1, n_rows < 0,
+ * K outside 1..16, pick, L or q outside their ranges, a segment table, cands or rects that is not 16-byte aligned. */
+typedef struct {
+    int32_t row0, n, slot, seen;
+} w2l_track_segment;
+int w2l_s3fd_top_rects(void* stream, int B, int P, const float* table, const int* keep, const int* counts, float thresh, float sx,
+                       float sy, int K, int32_t* cands, int32_t* ncand, int32_t* flags);
+int w2l_face_track_segments(void* stream, int n_seg, const w2l_track_segment* segs, const int32_t* cands, const int32_t* ncand,
+                            const int32_t* cflags, int n_rows, int K, int pick, int L, int q, int32_t* state, int n_slots,
+                            int32_t* rects, int32_t* flags, int32_t* status);
 
 /* The per-clip finish of face_detect (inference.py:90-104 pads + clipping + "Face not detected", :59-66 get_smoothened_boxes;
  * evaluation/gen_videos_from_filelist.py:35-42, :61-77 is the same code) for many clips in one launch.  rects [R][4] = (x1, y1, x2, y2)

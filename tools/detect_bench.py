@@ -1,7 +1,7 @@
 """Packed face detection against the per-clip loop, alternated in one process: frames/s of `face_detection.detect_many` and of
 `for clip: inference.face_detect(frames, detector, ...)` over the same seeded clips.
 
-    python tools/detect_bench.py [--clips 200] [--alternations 5] [--batch 16] [--precision f32] [--seed 0]
+    python tools/detect_bench.py [--clips 200] [--alternations 5] [--batch 16] [--precision f32] [--seed 0] [--face_track PICK]
 
 The clips are those of tools/filelist_bench.py (160x160 frames, lengths uniform in 30..120, 16 distinct frames cycled), each frame
 with the saturated block of synthetic.filelist_frame pasted in so that the seeded S3FD (synthetic.s3fd_state_dict) finds a face;
@@ -11,7 +11,13 @@ frames start on the host in both loops, as the commands have them, and both end 
 reported separately; then the two loops alternate, --alternations pairs.  Prints one JSON line: per loop the frames/s of every pass
 with median, min and max, the first-pass seconds, detector graph builds per pass, torch.cuda.max_memory_allocated after the loop's
 first pass (the peak since process start for the packed loop, which runs first, and the peak over everything for the per-clip
-loop), and how many boxes and clips differ between the two paths."""
+loop), and how many boxes and clips differ between the two paths.
+
+With `--face_track PICK` (tracked face selection) the two loops are the packed detector without and with
+`face_track=PICK` (defaults K = 8, L = 0, min_iou = 0.25) - "packed" and "packed_tracked" - alternated the same way: what the two
+small launches per batch in place of one, and the track launch per group, cost.  The seeded clips hold one saturated block each;
+how often the seeded detector sees more than one candidate there is reported by `boxes_that_differ`, and says nothing about
+selection quality on real footage."""
 import argparse
 import json
 import os
@@ -58,10 +64,10 @@ def detector(dev, precision):
                                         state_dict=synth.s3fd_state_dict(), precision=precision)
 
 
-def run_packed(det, clips, batch):
+def run_packed(det, clips, batch, **kw):
     t0 = time.perf_counter()
     res = [b for _, b, _ in face_detection.detect_many(det, (face_detection.DetectJob(i, f) for i, f in enumerate(clips)), pads=PADS,
-                                                       T=5, batch_size=batch)]
+                                                       T=5, batch_size=batch, **kw)]
     torch.cuda.synchronize()
     return res, time.perf_counter() - t0
 
@@ -89,6 +95,8 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16"])
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--face_track", default=None, choices=["score", "largest", "left", "right"],
+                    help="compare the packed detector without and with face_track=PICK instead of packed against per-clip")
     a = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     clips = clips_with_faces(a.clips, a.seed)
@@ -96,6 +104,10 @@ def main(argv=None):
     _mod._Graph = _counting_graph
     out = {"clips": a.clips, "frames": frames, "batch": a.batch, "precision": a.precision, "alternations": a.alternations}
     loops = {"packed": (run_packed, detector(dev, a.precision)), "per_clip": (run_loop, detector(dev, a.precision))}
+    if a.face_track is not None:
+        out["face_track"] = a.face_track
+        loops["packed_tracked"] = (lambda det, clips, batch: run_packed(det, clips, batch, face_track=a.face_track), loops.pop("per_clip")[1])
+    first, second = list(loops)
     res = {k: {"frames_per_s": [], "graph_builds": []} for k in loops}
     last = {}
 
@@ -118,13 +130,14 @@ def main(argv=None):
     for name in loops:
         res[name]["frames_per_s"] = stats(res[name]["frames_per_s"])
     out.update(res)
-    both = [(p, q) for p, q in zip(last["packed"], last["per_clip"]) if p is not None and q is not None]
+    both = [(p, q) for p, q in zip(last[first], last[second]) if p is not None and q is not None]
     out["clips_with_boxes_in_both"] = len(both)
-    out["clips_where_only_one_path_found_faces"] = sum((p is None) != (q is None) for p, q in zip(last["packed"], last["per_clip"]))
+    out["clips_where_only_one_path_found_faces"] = sum((p is None) != (q is None) for p, q in zip(last[first], last[second]))
     out["boxes_compared"] = int(sum(len(p) for p, _ in both))
     out["boxes_that_differ"] = int(sum((p != q).any(axis=1).sum() for p, q in both))
-    out["packed_over_per_clip_median"] = round(res["packed"]["frames_per_s"]["median"] / res["per_clip"]["frames_per_s"]["median"], 3)
-    out["ahead_by_more_than_the_spread"] = bool(res["packed"]["frames_per_s"]["min"] > res["per_clip"]["frames_per_s"]["max"])
+    out["%s_over_%s_median" % (first, second)] = round(res[first]["frames_per_s"]["median"] / res[second]["frames_per_s"]["median"], 3)
+    out["ahead_by_more_than_the_spread"] = bool(res[first]["frames_per_s"]["min"] > res[second]["frames_per_s"]["max"])
+    out["behind_by_more_than_the_spread"] = bool(res[first]["frames_per_s"]["max"] < res[second]["frames_per_s"]["min"])
     print(json.dumps(out))
 
 

@@ -122,6 +122,14 @@ class BoxStreamSegment(C.Structure):
 BOX_STREAM_SEGMENT = np.dtype(BoxStreamSegment)
 
 
+class TrackSegment(C.Structure):
+    """w2l_track_segment: one clip's (or one live stream's new) rows of w2l_face_track_segments, 16 bytes"""
+    _fields_ = [(n, C.c_int32) for n in ("row0", "n", "slot", "seen")]
+
+
+TRACK_SEGMENT = np.dtype(TrackSegment)
+
+
 class MelStream(C.Structure):
     """w2l_mel_stream: one stream of w2l_mel_stream_cols, 48 bytes"""
     _fields_ = [("samples", C.c_uint64), ("first", C.c_int64), ("total", C.c_int64), ("window", C.c_uint64), ("held", C.c_int32),
@@ -219,6 +227,8 @@ SIGNATURES = {
     "w2l_s3fd_nms": (_i, [_vp, _i, _i, _vp, _f, _f, _vp, _vp, _vp, _ll]),
     "w2l_s3fd_first_rect": (_i, [_vp, _i, _i, _vp, _vp, _vp, _f, _vp, _vp]),
     "w2l_s3fd_first_rect_scaled": (_i, [_vp, _i, _i, _vp, _vp, _vp, _f, _f, _f, _vp, _vp]),
+    "w2l_s3fd_top_rects": (_i, [_vp, _i, _i, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _vp, _vp]),
+    "w2l_face_track_segments": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "w2l_face_boxes_segments": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "w2l_face_boxes_stream": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "w2l_face_boxes_runs": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

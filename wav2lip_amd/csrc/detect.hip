@@ -10,6 +10,9 @@
 //   w2l_s3fd_nms        sfd_detector.py:39-45 gate + bbox.py:44-64 greedy NMS, bit-exact keep list
 //   w2l_s3fd_first_rect sfd_detector.py:45 + api.py:61-77  first kept box above 0.5 -> int rect, one row per image
 //   w2l_s3fd_first_rect_scaled  the same with the box mapped back to the full frame (x * sx, y * sy) before the clip and int()
+//   w2l_s3fd_top_rects  sfd_detector.py:45 + api.py:61-77 for the first K kept boxes above 0.5 instead of d[0] alone (opt-in)
+//   w2l_face_track_segments  one of those candidates per frame, followed through a clip by overlap (opt-in; not the reference's
+//                       rule, which takes d[0] of every frame): rects and flags in w2l_s3fd_first_rect's format
 //   w2l_face_boxes_segments  inference.py:59-66, :90-104 / gen_videos_from_filelist.py:35-42, :61-77  pads, clipping, temporal
 //                       smoothing and "no face" of many clips in one launch
 //   w2l_face_boxes_stream  the same finish for LIVE streams, tick by tick: a box is written once the T - 1 frames after it are there
@@ -358,6 +361,168 @@ __global__ __launch_bounds__(64) void s3fd_first_rect_kernel(int P, const float*
         return;
     }
     if (lane == 0) { r[0] = r[1] = r[2] = r[3] = 0; flags[b] = kRectNone; }
+}
+
+// ---- tracked face selection (opt-in; not the reference's rule, which is s3fd_first_rect_kernel's d[0]).
+// Candidates of a frame: the first K rows of the keep list, in its order, whose score is > thresh, each converted as
+// s3fd_first_rect_kernel converts its one row (one __fmul_rn by sx / sy - a multiply by 1.0f gives the same bits, so one body
+// serves both - the clip at 0, the truncation).  One wave per image scans the keep list 64 entries at a time; a ballot and the
+// popcount of the lanes below give a passing lane its slot, and the scan stops after the K-th passing row: rows after it are not
+// looked at, so a keep entry outside the table counts only up to and including that row.  A coordinate that is NaN or above
+// 32767 after the clip and the truncation (that covers +inf and >= 2^31) flags the frame: with coordinates in 0..32767 every
+// product of the track below is exact in int64.  A flagged frame has no candidates, and unused slots are zeros.
+constexpr int kTrackMaxCands = 16;
+constexpr int kTrackMaxCoord = 32767;
+
+__global__ __launch_bounds__(64) void s3fd_top_rects_kernel(int P, const float* __restrict__ table, const int* __restrict__ keep,
+                                                            const int* __restrict__ counts, float thresh, float sx, float sy, int K,
+                                                            int* __restrict__ cands, int* __restrict__ ncand, int* __restrict__ flags) {
+    __shared__ int s_c[kTrackMaxCands][4];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const float* tb = table + (long long)b * P * 5;
+    const int* kp = keep + (long long)b * P;
+    const int n = counts[b];
+    int* cb = cands + (long long)b * K * 4;
+    bool host = n < 0 || n > P;                         // not a final count (an unresolved overflow): the host decides
+    int taken = 0;
+    for (int base = 0; !host && taken < K && base < n; base += 64) {      // uniform: host and taken are the same on every lane
+        const int i = base + lane;
+        int row = -1;
+        bool bad = false, pass = false;
+        if (i < n) {
+            row = kp[i];
+            bad = row < 0 || row >= P;
+            pass = !bad && tb[(long long)row * 5 + 4] > thresh;
+        }
+        const unsigned long long passing = __ballot(pass);
+        const int slot = taken + __popcll(passing & ((1ull << lane) - 1ull));      // passing rows before this one
+        const bool examined = i < n && slot < K;        // up to and including the K-th passing row
+        bool refuse = bad && examined;
+        if (pass && examined) {
+            const float* d = tb + (long long)row * 5;
+            for (int k = 0; k < 4; ++k) {
+                const float c = __fmul_rn(d[k], (k & 1) ? sy : sx);
+                const float x = c > 0.f ? c : 0.f;
+                if (!(c == c) || !(x < (float)(kTrackMaxCoord + 1))) { refuse = true; break; }
+                s_c[slot][k] = (int)x;                  // x >= 0: truncation = int()
+            }
+        }
+        host = __ballot(refuse) != 0ull;
+        taken = min(K, taken + __popcll(passing));
+    }
+    __syncthreads();
+    if (lane < 4 * K) cb[lane] = (!host && (lane >> 2) < taken) ? s_c[lane >> 2][lane & 3] : 0;
+    if (lane == 0) {
+        ncand[b] = host ? 0 : taken;
+        flags[b] = host ? kRectHost : (taken > 0 ? kRectFound : kRectNone);
+    }
+}
+
+// The track over a clip (or over the frames a live stream adds in a tick): one wave per segment walks its frames in order with the
+// state (ref rect, has, missed) in registers, the same on every lane.  Lane k < K holds candidate k of the frame; the next frame's
+// candidates are loaded while this one decides.  All integer arithmetic: inter = max(0, min(x2) - max(x1)) * max(0, min(y2) -
+// max(y1)), union = area(c) + area(ref) - inter, no + 1; a candidate continues the track when inter > 0 and inter * 256 >=
+// q * union (then both rects have positive sides and union > 0), the largest IoU wins - inter_a * union_b > inter_b * union_a in
+// int64 - and ties go to the lower index.  Without a track the frame's candidates seed one by `pick`, ties to the lower index.
+// A frame flagged neither found nor none is written as kRectHost with zeros and leaves the state alone.
+struct TrackSeg { int row0, n, slot, seen; };
+static_assert(sizeof(TrackSeg) == 16 && sizeof(w2l_track_segment) == 16, "w2l_track_segment is 16 bytes");
+constexpr int kTrackStateInts = 8;                      // (x1, y1, x2, y2, has, missed, 0, 0)
+constexpr int kTrackBadSegment = 3;                     // status of a segment that is not followed (as kBoxStreamBadSegment)
+constexpr int kTrackMaxReseed = 250;                    // missed frames tolerated at the most
+constexpr int kPickScore = 0, kPickLargest = 1, kPickLeft = 2, kPickRight = 3;
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// the lowest lane of each group of 16 ends up with the group's minimum of (key, index): lanes 0..15 hold the candidates
+__device__ __forceinline__ int track_argmin(long long key, int idx) {
+    for (int o = 8; o > 0; o >>= 1) {
+        const long long k2 = __shfl_xor(key, o);
+        const int i2 = __shfl_xor(idx, o);
+        if (k2 < key || (k2 == key && i2 < idx)) { key = k2; idx = i2; }
+    }
+    return __shfl(idx, 0);
+}
+
+__global__ __launch_bounds__(64) void face_track_segments_kernel(const TrackSeg* __restrict__ segs, const int* __restrict__ cands,
+                                                                 const int* __restrict__ ncand, const int* __restrict__ cflags,
+                                                                 int n_rows, int K, int pick, int L, int q, int* __restrict__ state,
+                                                                 int n_slots, int* __restrict__ rects, int* __restrict__ flags,
+                                                                 int* __restrict__ status) {
+    const int lane = threadIdx.x;
+    const TrackSeg s = segs[blockIdx.x];
+    if (s.n < 0 || s.row0 < 0 || (long long)s.row0 + s.n > n_rows || s.slot < -1 || s.slot >= n_slots || s.seen < 0) {    // uniform
+        if (lane == 0) status[blockIdx.x] = kTrackBadSegment;
+        return;
+    }
+    if (lane == 0) status[blockIdx.x] = 0;
+    int rx1 = 0, ry1 = 0, rx2 = 0, ry2 = 0, has = 0, missed = 0;
+    int* slot = s.slot >= 0 ? state + (long long)s.slot * kTrackStateInts : nullptr;
+    if (slot && s.seen > 0) {                           // read before anything is written: every lane takes the same words
+        rx1 = slot[0]; ry1 = slot[1]; rx2 = slot[2]; ry2 = slot[3];
+        has = slot[4] != 0;
+        missed = min(max(slot[5], 0), kTrackMaxReseed + 1);
+    }
+    const bool mine = lane < K;
+    auto load = [&](int i, i32x4* c, int* nc, int* cf) {
+        const long long row = (long long)s.row0 + i;
+        *c = mine ? *reinterpret_cast<const i32x4*>(cands + (row * K + lane) * 4) : i32x4{0, 0, 0, 0};
+        *nc = ncand[row];
+        *cf = cflags[row];
+    };
+    i32x4 c_next = {0, 0, 0, 0};
+    int nc_next = 0, cf_next = kRectNone;
+    if (s.n > 0) load(0, &c_next, &nc_next, &cf_next);
+    for (int i = 0; i < s.n; ++i) {
+        const i32x4 c = c_next;
+        const int cf = cf_next;
+        const int nc = cf == kRectFound ? min(max(nc_next, 0), K) : 0;
+        if (i + 1 < s.n) load(i + 1, &c_next, &nc_next, &cf_next);
+        const long long row = (long long)s.row0 + i;
+        int out_flag = kRectNone, best = -1;
+        if (cf != kRectFound && cf != kRectNone) out_flag = kRectHost;      // uniform from here on: cf, nc and the state are
+        else {
+            const bool valid = lane < nc;
+            const long long area = (long long)(c.z - c.x) * (c.w - c.y);
+            if (has) {
+                const long long iw = max(0, min(c.z, rx2) - max(c.x, rx1)), ih = max(0, min(c.w, ry2) - max(c.y, ry1));
+                long long inter = iw * ih;
+                long long uni = area + (long long)(rx2 - rx1) * (ry2 - ry1) - inter;
+                int idx = lane;
+                if (!(valid && inter > 0 && inter * 256 >= (long long)q * uni)) { inter = 0; uni = 1; idx = 0x7fffffff; }
+                for (int o = 8; o > 0; o >>= 1) {       // the group's best (IoU, then the lower index) on each of its lanes
+                    const long long i2 = __shfl_xor(inter, o), u2 = __shfl_xor(uni, o);
+                    const int x2 = __shfl_xor(idx, o);
+                    const long long a = i2 * uni, bb = inter * u2;
+                    if (a > bb || (a == bb && x2 < idx)) { inter = i2; uni = u2; idx = x2; }
+                }
+                idx = __shfl(idx, 0);
+                if (idx != 0x7fffffff) best = idx;
+                else if (++missed > L) has = 0;         // the track is dropped and seeded again on this same frame
+            }
+            if (!has && nc > 0) {
+                long long key = 0;
+                if (pick == kPickLargest) key = -area;
+                else if (pick == kPickLeft) key = (long long)c.x + c.z;
+                else if (pick == kPickRight) key = -((long long)c.x + c.z);
+                best = track_argmin(valid ? key : 0x7fffffffffffffffll, valid ? lane : 0x7fffffff);
+            }
+            if (best >= 0) {
+                rx1 = __shfl(c.x, best); ry1 = __shfl(c.y, best); rx2 = __shfl(c.z, best); ry2 = __shfl(c.w, best);
+                has = 1;
+                missed = 0;
+                out_flag = kRectFound;
+            }
+        }
+        if (lane == 0) {
+            const bool found = out_flag == kRectFound;
+            *reinterpret_cast<i32x4*>(rects + row * 4) = found ? i32x4{rx1, ry1, rx2, ry2} : i32x4{0, 0, 0, 0};
+            flags[row] = out_flag;
+        }
+    }
+    if (slot && lane < kTrackStateInts) {               // without a track the rect and the count mean nothing: zeros
+        const int w[kTrackStateInts] = {has ? rx1 : 0, has ? ry1 : 0, has ? rx2 : 0, has ? ry2 : 0, has, has ? missed : 0, 0, 0};
+        slot[lane] = w[lane];
+    }
 }
 
 // ---- the per-clip finish of face_detect (inference.py:90-104; gen_videos_from_filelist.py:61-77 is the same code) for many
@@ -775,6 +940,38 @@ int w2l_s3fd_first_rect_scaled(void* stream, int B, int P, const float* table, c
                 "s3fd_first_rect_scaled: sx=%g and sy=%g must be finite and positive", (double)sx, (double)sy);
     hipLaunchKernelGGL(s3fd_first_rect_kernel<true>, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), P, table, keep,
                        counts, thresh, sx, sy, rects, flags);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_s3fd_top_rects(void* stream, int B, int P, const float* table, const int* keep, const int* counts, float thresh, float sx,
+                       float sy, int K, int32_t* cands, int32_t* ncand, int32_t* flags) {
+    W2L_REQUIRE(table && keep && counts && cands && ncand && flags && B >= 1 && P >= 1, "bad s3fd_top_rects arguments");
+    W2L_REQUIRE((long long)B * P * 5 < (1ll << 31), "s3fd_top_rects: table too large");
+    W2L_REQUIRE(sx > 0.f && sy > 0.f && sx < INFINITY && sy < INFINITY, "s3fd_top_rects: sx=%g and sy=%g must be finite and positive",
+                (double)sx, (double)sy);
+    W2L_REQUIRE(K >= 1 && K <= kTrackMaxCands, "s3fd_top_rects: K=%d outside 1..%d", K, kTrackMaxCands);
+    hipLaunchKernelGGL(s3fd_top_rects_kernel, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), P, table, keep, counts, thresh,
+                       sx, sy, K, cands, ncand, flags);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_face_track_segments(void* stream, int n_seg, const w2l_track_segment* segs, const int32_t* cands, const int32_t* ncand,
+                            const int32_t* cflags, int n_rows, int K, int pick, int L, int q, int32_t* state, int n_slots,
+                            int32_t* rects, int32_t* flags, int32_t* status) {
+    W2L_REQUIRE(segs && cands && ncand && cflags && rects && flags && status, "face_track_segments: NULL argument");
+    W2L_REQUIRE(n_seg >= 1 && n_rows >= 0, "face_track_segments: n_seg=%d must be at least 1 and n_rows=%d at least 0", n_seg, n_rows);
+    W2L_REQUIRE(n_slots >= 0 && (state || n_slots == 0), "face_track_segments: n_slots=%d slots need a state table", n_slots);
+    W2L_REQUIRE(K >= 1 && K <= kTrackMaxCands, "face_track_segments: K=%d outside 1..%d", K, kTrackMaxCands);
+    W2L_REQUIRE(pick >= kPickScore && pick <= kPickRight, "face_track_segments: pick=%d outside 0..3", pick);
+    W2L_REQUIRE(L >= 0 && L <= kTrackMaxReseed, "face_track_segments: L=%d outside 0..%d", L, kTrackMaxReseed);
+    W2L_REQUIRE(q >= 1 && q <= 256, "face_track_segments: q=%d outside 1..256", q);
+    W2L_REQUIRE(((reinterpret_cast<uintptr_t>(segs) | reinterpret_cast<uintptr_t>(cands) | reinterpret_cast<uintptr_t>(rects)) & 15) == 0,
+                "face_track_segments: the segment table, cands and rects must be 16-byte aligned");
+    hipLaunchKernelGGL(face_track_segments_kernel, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const TrackSeg*>(segs), cands, ncand, cflags, n_rows, K, pick, L, q, state, n_slots, rects, flags,
+                       status);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

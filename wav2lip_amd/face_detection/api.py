@@ -82,13 +82,23 @@ class FaceAlignment:
                 out.append([x for x in d if x[-1] > 0.5])
         return out
 
-    def _candidates(self, images_bgr):
-        """the batch's box table [B, P, 5] and its gated NMS (keep, counts), all on the device"""
+    def _candidates(self, images_bgr, rows=None, resolve=True):
+        """the batch's box table [B, P, 5] and its gated NMS (keep, counts), all on the device: the one place the detector's boxes
+        come from, for `get_detections_for_batch`, `get_candidates_for_batch`, `rects_for_rows` and `cands_for_rows` (a test that
+        prescribes a box table overrides this).  `rows` = (B, H, W): `images_bgr` is a device address table of B frames
+        (`s3fd.dense_boxes_rows`) and nothing is read back - an image whose NMS overflowed keeps counts = -1, which the rect
+        kernels flag RECT_HOST; `resolve=False` asks the same of a batch of images."""
+        if rows is not None:
+            B, H, W = rows
+            levels = self.face_detector.dense_boxes_rows(images_bgr, B, H, W, precision=self.precision, **self._scale_kw())
+            table = torch.cat(levels, dim=1).contiguous()
+            keep, counts = nms_batch(table, 0.05, 0.3, host_overflow=False)
+            return table, keep, counts
         if isinstance(images_bgr, np.ndarray):
             images_bgr = torch.from_numpy(np.ascontiguousarray(images_bgr)).to(self.device)
         levels = self.face_detector.dense_boxes(images_bgr, precision=self.precision, **self._scale_kw())
         table = torch.cat(levels, dim=1).contiguous()           # [B, sum FH*FW, 5]
-        keep, counts = nms_batch(table, 0.05, 0.3)
+        keep, counts = nms_batch(table, 0.05, 0.3, host_overflow=resolve)
         return table, keep, counts
 
     def rects_for_rows(self, frames, B, H, W, rects, flags, offset):
@@ -104,9 +114,7 @@ class FaceAlignment:
                 or offset < 0 or offset + B > rects.shape[0]):
             raise ValueError("rects_for_rows: int32 arenas [R,4] and [R] with rows [%d, %d) inside them" % (offset, offset + B))
         with torch.no_grad():
-            levels = self.face_detector.dense_boxes_rows(frames, B, H, W, precision=self.precision, **self._scale_kw())
-            table = torch.cat(levels, dim=1).contiguous()
-            keep, counts = nms_batch(table, 0.05, 0.3, host_overflow=False)
+            table, keep, counts = self._candidates(frames, rows=(B, H, W))
             out = (rects.data_ptr() + 16 * offset, flags.data_ptr() + 4 * offset)
             if scale is None:
                 check(load().w2l_s3fd_first_rect(current_stream(), B, table.shape[1], table.data_ptr(), keep.data_ptr(),
@@ -115,6 +123,57 @@ class FaceAlignment:
                 check(load().w2l_s3fd_first_rect_scaled(current_stream(), B, table.shape[1], table.data_ptr(), keep.data_ptr(),
                                                         counts.data_ptr(), 0.5, float(scale[0]), float(scale[1]), *out),
                       "s3fd_first_rect_scaled")
+
+    def cands_for_rows(self, frames, B, H, W, cands, ncand, flags, offset, K):
+        """the device-resident twin of `rects_for_rows` for tracked face selection (`face_detection/track.py`): rows [offset,
+        offset + B) of the int32 arenas `cands` [R,K,4], `ncand` [R] and `flags` [R] receive what `w2l_s3fd_top_rects` writes - up to
+        K candidate rects per frame, in full-frame coordinates at det_scale > 1.  No host read."""
+        from .._lib import check, current_stream, load
+        scale = self.rect_scale(H, W) or (1.0, 1.0)
+        if (any(t.dtype != torch.int32 or not t.is_contiguous() for t in (cands, ncand, flags)) or cands.dim() != 3
+                or tuple(cands.shape[1:]) != (K, 4) or ncand.dim() != 1 or flags.dim() != 1
+                or not ncand.shape[0] == flags.shape[0] == cands.shape[0] or offset < 0 or offset + B > cands.shape[0]):
+            raise ValueError("cands_for_rows: int32 arenas [R,%d,4], [R] and [R] with rows [%d, %d) inside them" % (K, offset, offset + B))
+        with torch.no_grad():
+            table, keep, counts = self._candidates(frames, rows=(B, H, W))
+            check(load().w2l_s3fd_top_rects(current_stream(), B, table.shape[1], table.data_ptr(), keep.data_ptr(), counts.data_ptr(),
+                                            0.5, float(scale[0]), float(scale[1]), K, cands.data_ptr() + 16 * K * offset,
+                                            ncand.data_ptr() + 4 * offset, flags.data_ptr() + 4 * offset), "s3fd_top_rects")
+
+    def cands_for_batch(self, images, cands, ncand, flags, offset, K):
+        """`cands_for_rows` for a batch of images given as `get_detections_for_batch` takes them (numpy uint8 BGR [B,H,W,3]): the
+        arenas' rows [offset, offset + B) are written, the candidates stay on the device and nothing is read back (an image whose
+        NMS overflowed is flagged RECT_HOST)"""
+        from .._lib import check, current_stream, load
+        B = len(images)
+        scale = (None if getattr(self, "det_scale", 1) == 1 else self.rect_scale(*images.shape[1:3])) or (1.0, 1.0)
+        if (any(t.dtype != torch.int32 or not t.is_contiguous() for t in (cands, ncand, flags)) or cands.dim() != 3
+                or tuple(cands.shape[1:]) != (K, 4) or ncand.dim() != 1 or flags.dim() != 1
+                or not ncand.shape[0] == flags.shape[0] == cands.shape[0] or offset < 0 or offset + B > cands.shape[0]):
+            raise ValueError("cands_for_batch: int32 arenas [R,%d,4], [R] and [R] with rows [%d, %d) inside them" % (K, offset, offset + B))
+        with torch.no_grad():
+            table, keep, counts = self._candidates(images, resolve=False)
+            check(load().w2l_s3fd_top_rects(current_stream(), B, table.shape[1], table.data_ptr(), keep.data_ptr(), counts.data_ptr(),
+                                            0.5, float(scale[0]), float(scale[1]), K, cands.data_ptr() + 16 * K * offset,
+                                            ncand.data_ptr() + 4 * offset, flags.data_ptr() + 4 * offset), "s3fd_top_rects")
+
+    def get_candidates_for_batch(self, images, K):
+        """up to K candidate rects per image - `get_detections_for_batch`'s rect is the first of them: a list of (x1, y1, x2, y2)
+        int tuples per image, from one launch (`w2l_s3fd_top_rects`) and one copy back per batch; an image the device flags takes
+        `track.host_top_rects`, which raises what Python's int() raises."""
+        from .s3fd import top_rects
+        from .track import host_top_rects
+        scale = None if getattr(self, "det_scale", 1) == 1 else self.rect_scale(*images.shape[1:3])
+        with torch.no_grad():
+            table, keep, counts = self._candidates(images)
+            cands, ncand, flags = top_rects(table, keep, counts, 0.5, K, scale)
+            out = []
+            for b in range(len(flags)):
+                if flags[b] == RECT_HOST:
+                    out.append(host_top_rects(table[b].cpu().numpy(), keep[b].cpu().numpy(), int(counts[b].item()), K, scale))
+                else:
+                    out.append([tuple(int(v) for v in c) for c in cands[b, :ncand[b]]])
+        return out
 
     def get_detections_for_batch(self, images):
         """api.py:61-77 (the BGR->RGB flip of :62 happens inside the device pack kernel).  The rect of every image comes from one

@@ -19,13 +19,17 @@ over clips of one frame shape therefore builds one detector graph.
 With `no_face_hold=G` (opt-in) the one launch is w2l_face_boxes_runs: a frame without a face keeps the last rect for
 up to G frames or becomes a gap frame, every run of boxed frames is finished as a clip of its own, and `valid [R]` comes back with
 the boxes.  `host_boxes_runs` is that rule on the host.
+
+With `face_track=...` (opt-in) a batch ends in w2l_s3fd_top_rects instead of w2l_s3fd_first_rect - up to K candidate
+rects per frame, in arenas of their own - and ONE w2l_face_track_segments launch over the group's clips writes the rects and flags
+the finish reads: one face followed through each clip (`face_detection/track.py`).  Still one copy back per group.
 """
 import collections
 
 import numpy as np
 import torch
 
-from .._lib import BOX_SEGMENT
+from .._lib import BOX_SEGMENT, TRACK_SEGMENT
 from ..staging import ADDRESS, Staging
 
 MAX_T = 64           # w2l_face_boxes_segments' largest smoothing window
@@ -166,6 +170,17 @@ def _detect_batch(detector, frames, B, H, W, rects, flags, offset):
     detector.rects_for_rows(frames, B, H, W, rects, flags, offset)
 
 
+def _detect_batch_cands(detector, frames, B, H, W, cands, ncand, cflags, offset, K):
+    """one detector batch under tracked selection: rows [offset, offset + B) of the candidate arenas"""
+    detector.cands_for_rows(frames, B, H, W, cands, ncand, cflags, offset, K)
+
+
+def _track_group(n_seg, segs, cands, ncand, cflags, track, rects, flags, status):
+    """w2l_face_track_segments: one face followed through each of the group's clips, in one launch"""
+    from .track import track_segments
+    track_segments(segs, n_seg, cands, ncand, cflags, track, rects, flags, status)
+
+
 def _finish_segments(n_seg, segs, rects, flags, pads, T, boxes, status):
     """w2l_face_boxes_segments: the group's clips in one launch"""
     from .._lib import check, current_stream, load, ptr
@@ -182,10 +197,12 @@ def _finish_runs(n_seg, segs, rects, flags, n_rows, pads, T, hold, boxes, valid,
                                      hold, ptr(boxes), ptr(valid), ptr(status)), "face_boxes_runs")
 
 
-def _detect_group(detector, clips, pads, T, batch_size, hold=None):
+def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None):
     """One group on the device.  clips: _Clips of one frame shape, each with at least one frame.  Returns numpy (boxes int32 [R,4]
     in (y1, y2, x1, x2) order, rows in clip order; status int32 [clips,2]); with `hold` (the pass-through rule) a third array,
-    valid int32 [R], comes between them - still one launch and one copy back."""
+    valid int32 [R], comes between them - still one launch and one copy back.  With `track` (a FaceTrack) the batches leave
+    candidates and one more launch, before the finish, chooses the rect of every frame; its status words come back in the same
+    copy and are all 0 (the table is built here)."""
     dev = torch.device(detector.device)
     H, W = clips[0].H, clips[0].W
     R = sum(c.n for c in clips)
@@ -193,6 +210,7 @@ def _detect_group(detector, clips, pads, T, batch_size, hold=None):
     # ---- one staging buffer: [address table, `padded` entries][segment table][host frames of the group]
     st = Staging(dev)
     addresses, segments = st.table(ADDRESS, padded), st.table(BOX_SEGMENT, len(clips))
+    tracks = None if track is None else st.table(TRACK_SEGMENT, len(clips))
     src = [st.place(c.frames) for c in clips]
     st.allocate()
     addr, segs = st.view(addresses), st.view(segments)
@@ -201,38 +219,70 @@ def _detect_group(detector, clips, pads, T, batch_size, hold=None):
     for k, c in enumerate(clips):
         addr[r:r + c.n] = np.uint64(st.address(src[k])) + np.arange(c.n, dtype=np.uint64) * np.uint64(frame_bytes)
         segs[k] = (r, c.n, H, W)
+        if tracks is not None:
+            st.view(tracks)[k] = (r, c.n, -1, 0)             # a clip: no carried state
         r += c.n
     addr[R:] = addr[R - 1]
     st.upload()
     rects = torch.empty((padded, 4), dtype=torch.int32, device=dev)            # rows [R, padded): the scratch tail
     flags = torch.empty((padded,), dtype=torch.int32, device=dev)
     addr_dev = st.tensor(addresses)
-    for lo in range(0, padded, batch_size):
-        _detect_batch(detector, addr_dev[lo * 8:(lo + batch_size) * 8], batch_size, H, W, rects, flags, lo)
+    extra = 0 if track is None else len(clips)   # the track's status words, behind everything else in the one copy back
+    if track is None:
+        for lo in range(0, padded, batch_size):
+            _detect_batch(detector, addr_dev[lo * 8:(lo + batch_size) * 8], batch_size, H, W, rects, flags, lo)
+    else:
+        K = track.cands
+        cands = torch.empty((padded, K, 4), dtype=torch.int32, device=dev)
+        ncand = torch.empty((padded,), dtype=torch.int32, device=dev)
+        cflags = torch.empty((padded,), dtype=torch.int32, device=dev)
+        for lo in range(0, padded, batch_size):
+            _detect_batch_cands(detector, addr_dev[lo * 8:(lo + batch_size) * 8], batch_size, H, W, cands, ncand, cflags, lo, K)
     if hold is not None:
-        out = torch.empty(5 * R + 2 * len(clips), dtype=torch.int32, device=dev)     # boxes [R][4], valid [R], status [clips][2]
-        _finish_runs(len(clips), st.tensor(segments), rects, flags, R, pads, T, hold, out[:4 * R], out[4 * R:5 * R], out[5 * R:])
+        out = torch.empty(5 * R + 2 * len(clips) + extra, dtype=torch.int32, device=dev)    # boxes [R][4], valid [R], status [clips][2]
+        end = 5 * R + 2 * len(clips)
+        if track is not None:
+            _track_group(len(clips), st.tensor(tracks), cands, ncand, cflags, track, rects, flags, out[end:])
+        _finish_runs(len(clips), st.tensor(segments), rects, flags, R, pads, T, hold, out[:4 * R], out[4 * R:5 * R], out[5 * R:end])
         res = out.cpu().numpy()
-        return res[:4 * R].reshape(R, 4), res[4 * R:5 * R], res[5 * R:].reshape(len(clips), 2)
-    out = torch.empty(4 * R + 2 * len(clips), dtype=torch.int32, device=dev)    # boxes [R][4], then status [clips][2]: one copy back
-    _finish_segments(len(clips), st.tensor(segments), rects, flags, pads, T, out[:4 * R], out[4 * R:])
+        _tracked(res[end:])
+        return res[:4 * R].reshape(R, 4), res[4 * R:5 * R], res[5 * R:end].reshape(len(clips), 2)
+    out = torch.empty(4 * R + 2 * len(clips) + extra, dtype=torch.int32, device=dev)    # boxes [R][4], then status [clips][2]: one copy back
+    end = 4 * R + 2 * len(clips)
+    if track is not None:
+        _track_group(len(clips), st.tensor(tracks), cands, ncand, cflags, track, rects, flags, out[end:])
+    _finish_segments(len(clips), st.tensor(segments), rects, flags, pads, T, out[:4 * R], out[4 * R:end])
     res = out.cpu().numpy()                      # the group's one copy back; it also ends the stream's use of the staging buffers
-    return res[:4 * R].reshape(R, 4), res[4 * R:].reshape(len(clips), 2)
+    _tracked(res[end:])
+    return res[:4 * R].reshape(R, 4), res[4 * R:end].reshape(len(clips), 2)
 
 
-def _per_clip(detector, clip, pads, T, batch_size, hold=None):
+def _tracked(status):
+    """the status words of w2l_face_track_segments for a table built here: all 0"""
+    if len(status) and status.any():
+        raise AssertionError("w2l_face_track_segments did not follow a clip's segment (status %s)" % status.tolist())
+
+
+def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None):
     """one clip alone through `inference.face_detect` (batch by batch uploads, the host rules): (key, boxes, error)"""
     from .. import inference
     frames = list(clip.frames.cpu().numpy()) if isinstance(clip.frames, torch.Tensor) else list(clip.frames)
+
+    def clip_rects():
+        if track is None:
+            return inference._detect_rects(frames, detector, batch_size)
+        return inference._track_rects(frames, detector, batch_size, track)
+
     try:
         if hold is not None:                     # the pass-through rule on the host: the same rects, `host_boxes_runs`
-            rects = inference._detect_rects(frames, detector, batch_size)
+            rects = clip_rects()
             return clip.key, RunBoxes(*host_boxes_runs(rects, clip.H, clip.W, pads, T, hold)), None
         if T in (0, 5):
-            det = inference.face_detect(frames, detector=detector, pads=list(pads), nosmooth=(T == 0), batch_size=batch_size)
+            det = inference.face_detect(frames, detector=detector, pads=list(pads), nosmooth=(T == 0), batch_size=batch_size,
+                                        **({} if track is None else {"face_track": track}))
             boxes = np.array([c for _, c in det], dtype=np.int64).reshape(-1, 4)
         else:                                    # face_detect's window is 5: its two halves with another T
-            rects = inference._detect_rects(frames, detector, batch_size)
+            rects = clip_rects()
             if any(r is None for r in rects):
                 raise ValueError(NO_FACE)
             boxes = host_boxes(rects, clip.H, clip.W, pads, T)
@@ -241,7 +291,8 @@ def _per_clip(detector, clip, pads, T, batch_size, hold=None):
     return clip.key, boxes, None
 
 
-def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_batches=16, max_group_bytes=1 << 30, no_face_hold=None):
+def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_batches=16, max_group_bytes=1 << 30, no_face_hold=None,
+                face_track=None):
     """`inference.face_detect(frames, detector, pads, nosmooth=(T == 0))` for every `DetectJob` of the iterable `jobs`, the frames
     of successive clips packed into detector batches of exactly `batch_size`.  A generator: jobs are consumed lazily and one
     `(key, boxes, error)` comes out per job, in job order - `boxes` the int array [n,4] of (y1, y2, x1, x2) `face_detect` returns
@@ -263,8 +314,15 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
     the reference's behaviour): a frame without a face keeps the last detected rect for up to G frames and is a gap frame beyond
     that, and every run of boxed frames is finished as a clip of its own.  `boxes` is then a `RunBoxes`: `boxes[i]` is frame i's
     (y1, y2, x1, x2) or None for a gap frame (`.boxes` / `.valid` are the arrays); `error` stays for real errors (a coordinate
-    int() refuses)."""
+    int() refuses).
+
+    `face_track`: None (default), or a pick name / `track.FaceTrack`: one face is followed through every clip instead of taking
+    the best-scoring box of each frame (not the reference's behaviour), exactly as `face_detect(face_track=...)`
+    does for the clip alone."""
+    from .track import check_track
     hold = check_hold(no_face_hold)
+    track = check_track(face_track)
+    tkw = {} if track is None else {"track": track}    # the default path calls its helpers with the arguments it always did
     if batch_size < 1 or group_batches < 1:
         raise ValueError("batch_size and group_batches must be at least 1")
     if not 0 <= int(T) <= MAX_T:
@@ -293,7 +351,7 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
                 if group:
                     break                                  # the jobs before it first
                 held = None
-                yield _per_clip(detector, c, pads, T, batch_size, hold)
+                yield _per_clip(detector, c, pads, T, batch_size, hold, **tkw)
                 del c
                 continue
             if shape is not None and ((c.H, c.W) != shape or n_bytes + c.nbytes > max_group_bytes):
@@ -311,9 +369,9 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
         while clips:
             try:
                 if hold is None:
-                    boxes, status = _detect_group(detector, clips, pads, T, batch_size)
+                    boxes, status = _detect_group(detector, clips, pads, T, batch_size, **tkw)
                 else:
-                    boxes, valid, status = _detect_group(detector, clips, pads, T, batch_size, hold)
+                    boxes, valid, status = _detect_group(detector, clips, pads, T, batch_size, hold, **tkw)
                 break
             except RuntimeError:
                 if batch_size == 1:
@@ -341,4 +399,4 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
         del c
         while results:
             res = results.pop(0)
-            yield _per_clip(detector, res, pads, T, batch_size, hold) if isinstance(res, _Clip) else res
+            yield _per_clip(detector, res, pads, T, batch_size, hold, **tkw) if isinstance(res, _Clip) else res

@@ -418,6 +418,28 @@ def first_rects(table, keep, counts, thresh, scale=None):
     return np.concatenate([h[:4 * B].reshape(B, 4), h[4 * B:].reshape(B, 1)], axis=1)
 
 
+def top_rects(table, keep, counts, thresh, K, scale=None):
+    """the candidates of every image of a batch on the device (`w2l_s3fd_top_rects`, tracked face selection): `first_rects`'
+    arguments and K in 1..16 -> numpy int32 (cands [B, K, 4], ncand [B], flags [B]) in ONE device-to-host copy: the first K kept
+    rows above `thresh`, each converted as `first_rects` converts its one; RECT_HOST also for a coordinate above 32767."""
+    engine.require_cuda(table, "box table")
+    if table.dtype != torch.float32 or table.dim() != 3 or table.shape[2] != 5:
+        raise RuntimeError("top_rects: table must be float32 [B, P, 5]")
+    table = table.contiguous()
+    B, P = table.shape[:2]
+    if keep.dtype != torch.int32 or tuple(keep.shape) != (B, P) or counts.dtype != torch.int32 or tuple(counts.shape) != (B,):
+        raise RuntimeError("top_rects: keep must be int32 [B, P] and counts int32 [B] (nms_batch's outputs)")
+    keep, counts = keep.contiguous(), counts.contiguous()
+    K = int(K)
+    n = 4 * K * B
+    out = torch.empty((n + 2 * B,), device=table.device, dtype=torch.int32)   # cands [B][K][4], ncand [B], flags [B]: one copy back
+    sx, sy = (1.0, 1.0) if scale is None else (float(scale[0]), float(scale[1]))
+    check(load().w2l_s3fd_top_rects(current_stream(), B, P, ptr(table), ptr(keep), ptr(counts), float(thresh), sx, sy, K, ptr(out),
+                                    ptr(out[n:]), ptr(out[n + B:])), "s3fd_top_rects")
+    h = out.cpu().numpy()
+    return h[:n].reshape(B, K, 4), h[n:n + B], h[n + B:]
+
+
 def _nms_host(dets, thresh):
     """bbox.py:44-64 in its float32 operation order (numpy): kept row indices of `dets` [n, 5], best score first.  Only the
     overflow route of nms_batch comes here."""

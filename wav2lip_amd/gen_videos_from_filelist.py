@@ -69,14 +69,16 @@ def build_main_parser():
     what is computed, and `--face_det_scale K`, the size of the frame the detector sees (`inference.add_det_scale_flag`).
     `--blend_feather N` / `--blend_top FRACTION` blend every generated face into its frame (`inference.add_blend_flags`).
     `--no_face_hold G` generates a line with frames without a face instead of skipping it (`inference.add_hold_flag`).
-    `cli_parser` stays the reference's surface plus the two precision flags."""
-    from .inference import add_blend_flags, add_det_scale_flag, add_hold_flag
+    `--face_track PICK` follows one face through every line's clip (`inference.add_track_flags`), with and without
+    `--packed_face_det`.  `cli_parser` stays the reference's surface plus the two precision flags."""
+    from .inference import add_blend_flags, add_det_scale_flag, add_hold_flag, add_track_flags
     p = build_cli_parser()
     p.add_argument('--packed_face_det', default=False, action='store_true',
                    help='Detect faces of successive clips in shared detector batches (face_detection.detect_many)')
     add_det_scale_flag(p)
     add_blend_flags(p)
     add_hold_flag(p)
+    add_track_flags(p)
     return p
 
 
@@ -84,6 +86,13 @@ parser = build_parser()
 cli_parser = build_cli_parser()
 main_parser = build_main_parser()
 fps = 25                  # gen_videos_from_filelist.py:120
+
+
+def _track_kw(args):
+    """the `face_track=` keyword of a parsed command line (`--face_track PICK`): none without the flag"""
+    from . import inference
+    from .face_detection.track import track_from_args
+    return inference._track_kw(track_from_args(args))
 
 
 def lines_of_rank(lines, ranks):
@@ -162,7 +171,7 @@ def clip_jobs(args, lines, ranks, detector, tracks):
                 try:
                     det = inference.face_detect(full_frames, detector=detector, pads=args.pads, nosmooth=False,
                                                 batch_size=args.face_det_batch_size,
-                                                **inference._hold_kw(getattr(args, 'no_face_hold', None)))
+                                                **inference._hold_kw(getattr(args, 'no_face_hold', None)), **_track_kw(args))
                 except ValueError as e:
                     _skip(idx, line, str(e))
                     continue
@@ -206,7 +215,7 @@ def clip_jobs_packed(args, lines, ranks, detector, tracks):
     with tempfile.TemporaryDirectory(prefix="w2l_filelist_") as tmpdir:
         for idx, boxes, error in face_detection.detect_many(detector, inputs(tmpdir), pads=args.pads, T=5,
                                                             batch_size=args.face_det_batch_size,
-                                                            **inference._hold_kw(getattr(args, 'no_face_hold', None))):
+                                                            **inference._hold_kw(getattr(args, 'no_face_hold', None)), **_track_kw(args)):
             sys.stderr.write(notes.pop(idx))
             line, full_frames, mel, pcm, sr = held.pop(idx)
             try:
@@ -258,6 +267,7 @@ def main(argv=None, state_dict=None, backend="nccl"):
     args = main_parser.parse_args(argv)
     args.img_size = 96
     blend_kw = inference._blend_kw(inference.blend_from_args(args))
+    _track_kw(args)                                      # a flag of the track without --face_track: refused before any device work
     ranks = sharding.init_from_env(backend)
     try:
         assert args.data_root is not None

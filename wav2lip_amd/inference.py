@@ -172,8 +172,9 @@ def build_cli_parser():
     documented additions that are not among them, each the reference's behaviour by default and independent of the others:
     `--precision {fp32,bf16}`, the generator's arithmetic, `--face_det_precision {fp32,bf16}`, the S3FD detector's,
     `--face_det_scale K`, the detector's frame size (1/K; output frames keep theirs), `--out_codec` / `--out_quality`,
-    `--blend_feather N` / `--blend_top FRACTION`, the feathered mouth-region paste, and `--no_face_hold G`, the pass-through for
-    frames without a face (absent by default)"""
+    `--blend_feather N` / `--blend_top FRACTION`, the feathered mouth-region paste, `--no_face_hold G`, the pass-through for
+    frames without a face (absent by default), and `--face_track PICK` with its three companions, tracked face selection
+    (`face_detection/track.py`; absent by default)"""
     p = build_parser()
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
                    help='Generator arithmetic: fp32 (default, matches the reference) or bf16 storage (faster; frames differ by '
@@ -189,6 +190,7 @@ def build_cli_parser():
     p.add_argument('--out_quality', default=95, type=int, help='JPEG quality of --out_codec mjpg, 1..100 (default 95)')
     add_blend_flags(p)
     add_hold_flag(p)
+    add_track_flags(p)
     return p
 
 
@@ -196,6 +198,19 @@ def add_hold_flag(p):
     """`--no_face_hold G` on a command's parser (face_detection/many.py holds the rule's host side): absent by default"""
     from .face_detection.many import add_hold_flag as add
     add(p)
+
+
+def add_track_flags(p):
+    """`--face_track PICK` and its companions on a command's parser (face_detection/track.py holds the rule): absent by default"""
+    from .face_detection.track import add_track_flags as add
+    add(p)
+
+
+def _track_kw(face_track):
+    """the keyword `face_detect`, `detect_many` and `LipsyncStreams` take for `face_track`, checked first: none for None (as
+    `_hold_kw`)"""
+    from .face_detection.track import track_kw
+    return track_kw(face_track)
 
 
 def _hold_kw(no_face_hold):
@@ -646,13 +661,54 @@ def _detect_rects(images, detector, batch_size, ranks=None):
             print('Recovering from OOM error; New batch size: {}'.format(batch_size))
 
 
+def _track_rects(images, detector, batch_size, track):
+    """`_detect_rects` under tracked face selection (face_detection/track.py): the candidates of every batch go into
+    device arenas (`FaceAlignment.cands_for_batch`), ONE w2l_face_track_segments launch with one segment follows the face through
+    the clip and ONE copy brings rects and flags back.  A frame the device does not decide (RECT_HOST) sends the whole clip through
+    the host statement of the same rule: `get_candidates_for_batch` (which runs `host_top_rects` on such a frame) and
+    `host_track`.  The detector's RuntimeError halves the batch as there."""
+    from .face_detection.s3fd import RECT_FOUND, RECT_HOST
+    from .face_detection.track import TRACK_SEGMENT, host_track, track_segments
+    n, K = len(images), track.cands
+    if n == 0:
+        return []
+    while True:
+        try:
+            dev = torch.device(detector.device)
+            cands = torch.empty((n, K, 4), dtype=torch.int32, device=dev)
+            ncand = torch.empty((n,), dtype=torch.int32, device=dev)
+            cflags = torch.empty((n,), dtype=torch.int32, device=dev)
+            for lo in range(0, n, batch_size):
+                detector.cands_for_batch(np.array(images[lo:lo + batch_size]), cands, ncand, cflags, lo, K)
+            seg = np.zeros(1, dtype=TRACK_SEGMENT)
+            seg[0] = (0, n, -1, 0)
+            segs = torch.from_numpy(seg.view(np.uint8)).to(dev)
+            out = torch.empty(5 * n + 1, dtype=torch.int32, device=dev)        # rects [n][4], flags [n], status [1]: one copy back
+            track_segments(segs, 1, cands, ncand, cflags, track, out[:4 * n].view(n, 4), out[4 * n:5 * n], out[5 * n:])
+            res = out.cpu().numpy()
+            rects, flags = res[:4 * n].reshape(n, 4), res[4 * n:5 * n]
+            if res[5 * n] != 0:
+                raise AssertionError("w2l_face_track_segments did not follow the clip's segment (status %d)" % res[5 * n])
+            if (flags == RECT_HOST).any():
+                per_frame = []
+                for lo in range(0, n, batch_size):
+                    per_frame += detector.get_candidates_for_batch(np.array(images[lo:lo + batch_size]), K)
+                return host_track(per_frame, track)[0]
+            return [tuple(int(v) for v in r) if f == RECT_FOUND else None for r, f in zip(rects, flags)]
+        except RuntimeError:
+            if batch_size == 1:
+                raise RuntimeError('Image too big to run face detection on GPU. Please use the --resize_factor argument')
+            batch_size //= 2
+            print('Recovering from OOM error; New batch size: {}'.format(batch_size))
+
+
 def _det_scale_kw(det_scale):
     """detector keyword for a reduced detection frame: scale 1 builds the detector with the same arguments as before the option"""
     return {} if det_scale == 1 else {"det_scale": det_scale}
 
 
 def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None, ranks=None, precision=None, det_scale=None,
-                no_face_hold=None):
+                no_face_hold=None, face_track=None):
     """inference.py:68-104: S3FD boxes per frame (HIP detector), padding, temporal smoothing; returns
     [[face crop, (y1, y2, x1, x2)], ...].  Called as the reference calls it - `face_detect(images)` - pads / nosmooth /
     face_det_batch_size come from the module-level `args` and the detector is built as inference.py:69-70 does
@@ -667,11 +723,22 @@ def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None
     pass-through rule on instead (not the reference's behaviour): such a frame keeps the last detected rect for up to
     G frames (no look-ahead), beyond that - and before the first detection - it is a gap frame whose entry is [None, None], and
     every run of boxed frames is padded, clipped and smoothed as a clip of its own (`face_detection.many.host_boxes_runs` states
-    the same for one frame shape).  A single frame without a face is still the ValueError."""
+    the same for one frame shape).  A single frame without a face is still the ValueError.
+
+    `face_track`: None (default) takes the detector's best-scoring box of every frame, as the reference does.  A pick name or a
+    `face_detection.track.FaceTrack` follows one face through the clip instead (not the reference's behaviour when
+    more than one face is in the picture): the rect of a frame is the candidate that overlaps the tracked face's last rect most, a
+    frame on which the track is lost (possible with `reseed` > 0 only) is a frame without a face, and everything after the
+    rects - the strict ValueError or `no_face_hold`, pads, smoothing - is as without it.  Not with `ranks` of more than one
+    process: the track looks back over the frames of other shards."""
     from .face_detection.many import boxed_runs, check_hold, hold_fill
+    from .face_detection.track import check_track
     from .face_detection.s3fd import check_det_scale
     from .models.wav2lip import check_precision
     hold = check_hold(no_face_hold)
+    track = check_track(face_track)
+    if track is not None and ranks is not None and ranks.dist is not None and ranks.world > 1:
+        raise ValueError("face_track runs on one GPU: the track looks back over the frames of other shards")
     if precision is not None:
         check_precision(precision)
     if det_scale is not None:
@@ -696,7 +763,7 @@ def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None
     pads = args.pads if pads is None else pads
     nosmooth = args.nosmooth if nosmooth is None else nosmooth
     batch_size = args.face_det_batch_size if batch_size is None else batch_size
-    rects = _detect_rects(images, detector, batch_size, ranks)
+    rects = _detect_rects(images, detector, batch_size, ranks) if track is None else _track_rects(images, detector, batch_size, track)
     if hold is not None and not (len(rects) == 1 and rects[0] is None):
         rects = hold_fill(rects, hold)
         top, bottom, left, right = pads
@@ -807,6 +874,10 @@ def main(argv=None, keep_frames=True, backend="nccl"):
     hold_kw = _hold_kw(args.no_face_hold)
     if hold_kw and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError("--no_face_hold runs on one GPU: the hold looks back over the frames of other shards")
+    from .face_detection.track import track_from_args
+    track_kw = _track_kw(track_from_args(args))
+    if track_kw and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--face_track runs on one GPU: the track looks back over the frames of other shards")
     ranks = sharding.init_from_env(backend)
     sharded = ranks.dist is not None and ranks.world > 1
     say = print if ranks.writer else (lambda *a, **k: None)
@@ -826,7 +897,7 @@ def main(argv=None, keep_frames=True, backend="nccl"):
         full_frames = full_frames[:len(starts)]
         if args.box[0] == -1:
             det = face_detect(full_frames if not args.static else [full_frames[0]], ranks=ranks,
-                              precision=CLI_PRECISION[args.face_det_precision], det_scale=args.face_det_scale, **hold_kw)
+                              precision=CLI_PRECISION[args.face_det_precision], det_scale=args.face_det_scale, **hold_kw, **track_kw)
             coords = [c for _, c in det]
         else:
             say('Using the specified bounding box instead of face detection...')

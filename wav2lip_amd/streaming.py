@@ -96,7 +96,7 @@ import os
 
 import numpy as np
 
-from ._lib import MEL_COL, MEL_STREAM, RESAMPLE_BLOCKS, RESAMPLE_STREAM
+from ._lib import MEL_COL, MEL_STREAM, RESAMPLE_BLOCKS, RESAMPLE_STREAM, TRACK_SEGMENT
 from .inference import LIPSYNC_DEPTH, mel_step_size, validate_boxes
 from .multiclip import BatchRunner
 from .staging import ADDRESS, Staging
@@ -494,8 +494,10 @@ class DeviceBoxes:
     """the device side of live face detection: per call one staged copy, the detector batches, ONE w2l_face_boxes_stream launch
     (csrc/detect.hip) for every stream of the tick and one copy back"""
 
-    def __init__(self, device, detector, pads, T, batch_size, hold=None):
-        """hold: None, or the G of the pass-through rule: w2l_face_boxes_stream_runs finishes the boxes, with its own carry slots"""
+    def __init__(self, device, detector, pads, T, batch_size, hold=None, track=None):
+        """hold: None, or the G of the pass-through rule: w2l_face_boxes_stream_runs finishes the boxes, with its own carry slots.
+        track: None, or a FaceTrack: the batches leave candidates and ONE w2l_face_track_segments launch per tick, between
+        detection and the finish, follows each stream's face on from the state in its slot of `track_state`"""
         import torch
         from . import _lib
         from .face_detection import live
@@ -503,6 +505,10 @@ class DeviceBoxes:
         self.detector, self.pads, self.T, self.B, self.hold = detector, pads, T, batch_size, hold
         slot = (live.CARRY_ROWS, 4) if hold is None else (live.RUNS_CARRY_INTS,)
         self.carry = torch.zeros((64,) + slot, dtype=torch.int32, device=device)
+        self.track = track
+        if track is not None:
+            from .face_detection.track import STATE_INTS
+            self.track_state = torch.zeros((64, STATE_INTS), dtype=torch.int32, device=device)
 
     def reserve(self, n_slots):
         """room for carry slots [0, n_slots); the table grows on the launches' stream, so in order with them"""
@@ -511,6 +517,10 @@ class DeviceBoxes:
             grown = self.torch.zeros((max(n_slots, 2 * old),) + tuple(self.carry.shape[1:]), dtype=self.torch.int32, device=self.device)
             grown[:old].copy_(self.carry)
             self.carry = grown
+            if self.track is not None:
+                state = self.torch.zeros((grown.shape[0], self.track_state.shape[1]), dtype=self.torch.int32, device=self.device)
+                state[:old].copy_(self.track_state)
+                self.track_state = state
 
     def launch(self, items):
         """items: [(fresh, H, W, slot, seen, closed)] - `fresh` the stream's new frames in order (host arrays, device tensors
@@ -546,6 +556,7 @@ class DeviceBoxes:
         # ---- one staging buffer: [address table][segment table][the frames that were host arrays]
         st = Staging(self.device)
         addresses, segments = st.table(ADDRESS, total), st.table(SEG, len(items))
+        tracks = None if self.track is None else st.table(TRACK_SEGMENT, len(items))
         src = [[st.place(run) for run in mine] for mine in runs]
         st.allocate()
         addr, segs = st.view(addresses), st.view(segments)
@@ -559,6 +570,8 @@ class DeviceBoxes:
                 r += n
             chunks.append(mine)
             segs[k] = (row0.get(k, 0), n_new[k], H, W, slot, seen, int(bool(closed)), out0)
+            if tracks is not None:
+                st.view(tracks)[k] = (row0.get(k, 0), n_new[k], slot, seen)
             out0 += live.new_final_count(seen, n_new[k], closed, T)
         for H, W, first, end, padded in spans:
             addr[end:padded] = addr[end - 1]               # the last batch of a shape: its last address again, into scratch rows
@@ -566,13 +579,27 @@ class DeviceBoxes:
         rects = torch.empty((max(total, 1), 4), dtype=torch.int32, device=self.device)
         flags = torch.empty((max(total, 1),), dtype=torch.int32, device=self.device)
         addr_dev = st.tensor(addresses)
-        for H, W, first, end, padded in spans:
-            for lo in range(first, padded, B):
-                self.detector.rects_for_rows(addr_dev[lo * 8:(lo + B) * 8], B, H, W, rects, flags, lo)
-        # boxes, then (with a hold) valid, then status: one copy back
-        out = torch.empty((4 if self.hold is None else 5) * out0 + 2 * len(items), dtype=torch.int32, device=self.device)
+        if self.track is None:
+            for H, W, first, end, padded in spans:
+                for lo in range(first, padded, B):
+                    self.detector.rects_for_rows(addr_dev[lo * 8:(lo + B) * 8], B, H, W, rects, flags, lo)
+        else:
+            K = self.track.cands
+            cands = torch.empty((max(total, 1), K, 4), dtype=torch.int32, device=self.device)
+            ncand = torch.empty((max(total, 1),), dtype=torch.int32, device=self.device)
+            cflags = torch.empty((max(total, 1),), dtype=torch.int32, device=self.device)
+            for H, W, first, end, padded in spans:
+                for lo in range(first, padded, B):
+                    self.detector.cands_for_rows(addr_dev[lo * 8:(lo + B) * 8], B, H, W, cands, ncand, cflags, lo, K)
+        # boxes, then (with a hold) valid, then status, then (with a track) its status: one copy back
+        n_out = (4 if self.hold is None else 5) * out0 + 2 * len(items)
+        out = torch.empty(n_out + (0 if self.track is None else len(items)), dtype=torch.int32, device=self.device)
         top, bottom, left, right = self.pads
         with torch.cuda.device(self.device):
+            if self.track is not None:                   # every stream's face followed on from its slot: selection is causal, so
+                from .face_detection.track import track_segments      # box i is still final once frame i + T - 1 is there
+                track_segments(st.tensor(tracks), len(items), cands, ncand, cflags, self.track, rects, flags, out[n_out:],
+                               state=self.track_state)
             if self.hold is None:
                 check(self.lib.w2l_face_boxes_stream(current_stream(), len(items), st.host_address(segments), st.address(segments),
                                                      ptr(rects), ptr(flags), total, ptr(self.carry), int(self.carry.shape[0]), top, bottom,
@@ -588,7 +615,7 @@ class DeviceBoxes:
         done.record()
         counts = [int(c) for c in np.diff(np.append(segs["out0"], out0))]
         return dict(chunks=chunks, counts=counts, host_out=host_out, done=done, keep=(st.host, st.dev, rects, flags, out),
-                    valid=self.hold is not None)
+                    valid=self.hold is not None)         # the arenas of a track are freed in stream order: nothing else holds them
 
     @staticmethod
     def collect(ticket):
@@ -598,7 +625,10 @@ class DeviceBoxes:
         res = ticket["host_out"].numpy()
         n = sum(ticket["counts"])
         valid = res[4 * n:5 * n] if ticket["valid"] else None
-        status = res[(4 if valid is None else 5) * n:].reshape(-1, 2)
+        at = (4 if valid is None else 5) * n
+        status = res[at:at + 2 * len(ticket["counts"])].reshape(-1, 2)
+        if res[at + 2 * len(ticket["counts"]):].any():   # the words of w2l_face_track_segments, for a table built here: all 0
+            raise AssertionError("w2l_face_track_segments did not follow a stream's segment")
         out, r = [], 0
         for k, c in enumerate(ticket["counts"]):
             item = (res[4 * r:4 * (r + c)].reshape(c, 4).copy(), (int(status[k][0]), int(status[k][1])))
@@ -812,11 +842,13 @@ class LipsyncStreams:
 
     def __init__(self, model, batch_size=128, depth=None, precision="f32", fps=25., sink=None, on_batch=None, mel_window=1024,
                  detector=None, pads=(0, 10, 0, 0), smooth_T=5, face_det_batch_size=16, resample_buffer=1 << 16, blend=None,
-                 no_face_hold=None):
+                 no_face_hold=None, face_track=None):
         from .face_detection.many import check_hold
+        from .face_detection.track import check_track
         from .inference import check_blend
         from .models.wav2lip import check_precision
         self.hold = check_hold(no_face_hold)             # None, or G: frames without a face pass through (module docstring)
+        self.track = check_track(face_track)             # None, or a FaceTrack: live streams follow one face
         self.precision = check_precision(precision)
         self.blend = check_blend(blend)                  # None, or (feather, top): every frame's face is blended in
         if batch_size < 1:
@@ -950,7 +982,8 @@ class LipsyncStreams:
             self._mel = DeviceMel(self._runner.device)
         if self._boxes is None and self.detector is not None:
             self._boxes = DeviceBoxes(self._runner.device, self.detector, self.pads, self.smooth_T, self.face_det_batch_size,
-                                      **({} if self.hold is None else {"hold": self.hold}))
+                                      **({} if self.hold is None else {"hold": self.hold}),
+                                      **({} if self.track is None else {"track": self.track}))
 
     def _columns_round(self):
         converted = False
@@ -1159,10 +1192,11 @@ def build_parser():
                    help='Feed the frames of every video as they become due with the audio and detect faces as they arrive')
     p.add_argument('--native_rate', default=False, action='store_true',
                    help="Feed every WAV at the file's own rate and format; it is converted to 16 kHz on the device as it streams")
-    from .inference import add_blend_flags, add_det_scale_flag, add_hold_flag
+    from .inference import add_blend_flags, add_det_scale_flag, add_hold_flag, add_track_flags
     add_det_scale_flag(p)
     add_blend_flags(p)
     add_hold_flag(p)
+    add_track_flags(p)
     return p
 
 
@@ -1181,6 +1215,8 @@ def main(argv=None, state_dict=None):
     a = build_parser().parse_args(argv)
     blend = inference.blend_from_args(a)
     hold_kw = inference._hold_kw(a.no_face_hold)
+    from .face_detection.track import track_from_args
+    track_kw = inference._track_kw(track_from_args(a))   # `--face_track PICK`: one face followed through every video
     if len(a.face) != len(a.audio):
         raise ValueError("%d --face for %d --audio: pass them in pairs" % (len(a.face), len(a.audio)))
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -1205,7 +1241,7 @@ def main(argv=None, state_dict=None):
         elif a.box[0] == -1:
             det = inference.face_detect(frames if not one.static else [frames[0]], detector=detector, pads=a.pads, nosmooth=a.nosmooth,
                                         batch_size=a.face_det_batch_size, precision=inference.CLI_PRECISION[a.face_det_precision],
-                                        det_scale=a.face_det_scale, **hold_kw)
+                                        det_scale=a.face_det_scale, **hold_kw, **track_kw)
             boxes = [c for _, c in det]
         else:
             boxes = [tuple(a.box)] * len(frames)
@@ -1230,7 +1266,7 @@ def main(argv=None, state_dict=None):
 
     streams = LipsyncStreams(model, batch_size=a.wav2lip_batch_size, precision=inference.CLI_PRECISION[a.precision], sink=sink,
                              detector=detector, pads=a.pads, smooth_T=0 if a.nosmooth else 5, face_det_batch_size=a.face_det_batch_size,
-                             **inference._blend_kw(blend), **hold_kw)
+                             **inference._blend_kw(blend), **hold_kw, **track_kw)
     for j in jobs:
         if j["live"]:
             streams.open_live(j["key"], fps=j["fps"], sample_rate=j["rate"])
