@@ -204,11 +204,7 @@ def main(argv=None, state_dict=None):
     model = model.to(device).eval()
     detector = None
     if args.box is None:
-        from . import face_detection
-        detector = face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False, device=str(device),
-                                                state_dict=state_dict,
-                                                **inference._precision_kw(inference.CLI_PRECISION[args.face_det_precision]),
-                                                **inference._det_scale_kw(args.face_det_scale))
+        detector = inference.detector_from_args(args, device, state_dict)
     videos = sorted(glob.glob(os.path.join(args.data_root, "*.avi")))
     scored, skipped = [], []
 

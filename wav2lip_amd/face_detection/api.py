@@ -62,11 +62,15 @@ class FaceAlignment:
         k = getattr(self, "det_scale", 1)
         return None if k == 1 else det_rect_scale(H, W, *det_size(H, W, k))
 
+    def _batch_scale(self, images):
+        """`rect_scale` for a batch [B,H,W,3]; at scale 1 it is None and the batch is not looked at"""
+        return None if getattr(self, "det_scale", 1) == 1 else self.rect_scale(*images.shape[1:3])
+
     def detect_from_batch(self, images_bgr):
         """sfd_detector.py:39-45 semantics per image: candidates (score > 0.05), NMS 0.3, keep score > 0.5.
         images: numpy uint8 [B,H,W,3] BGR (or a torch uint8 tensor already on the device).  At det_scale > 1 the boxes come back in
         full-frame coordinates (`s3fd.scale_box`); the scores are the detector's."""
-        scale = None if getattr(self, "det_scale", 1) == 1 else self.rect_scale(*images_bgr.shape[1:3])
+        scale = self._batch_scale(images_bgr)
         if isinstance(images_bgr, np.ndarray):
             images_bgr = torch.from_numpy(np.ascontiguousarray(images_bgr)).to(self.device)
         with torch.no_grad():
@@ -124,38 +128,34 @@ class FaceAlignment:
                                                         counts.data_ptr(), 0.5, float(scale[0]), float(scale[1]), *out),
                       "s3fd_first_rect_scaled")
 
+    def _top_rects(self, who, B, scale, cands, ncand, flags, offset, K, candidates):
+        """the arena check and the one `w2l_s3fd_top_rects` call of `cands_for_rows` / `cands_for_batch` (`who` names the caller in
+        the error); `scale`: the batch's `rect_scale`; `candidates()`: its `_candidates`"""
+        from .._lib import check, current_stream, load
+        scale = scale or (1.0, 1.0)
+        if (any(t.dtype != torch.int32 or not t.is_contiguous() for t in (cands, ncand, flags)) or cands.dim() != 3
+                or tuple(cands.shape[1:]) != (K, 4) or ncand.dim() != 1 or flags.dim() != 1
+                or not ncand.shape[0] == flags.shape[0] == cands.shape[0] or offset < 0 or offset + B > cands.shape[0]):
+            raise ValueError("%s: int32 arenas [R,%d,4], [R] and [R] with rows [%d, %d) inside them" % (who, K, offset, offset + B))
+        with torch.no_grad():
+            table, keep, counts = candidates()
+            check(load().w2l_s3fd_top_rects(current_stream(), B, table.shape[1], table.data_ptr(), keep.data_ptr(), counts.data_ptr(),
+                                            0.5, float(scale[0]), float(scale[1]), K, cands.data_ptr() + 16 * K * offset,
+                                            ncand.data_ptr() + 4 * offset, flags.data_ptr() + 4 * offset), "s3fd_top_rects")
+
     def cands_for_rows(self, frames, B, H, W, cands, ncand, flags, offset, K):
         """the device-resident twin of `rects_for_rows` for tracked face selection (`face_detection/track.py`): rows [offset,
         offset + B) of the int32 arenas `cands` [R,K,4], `ncand` [R] and `flags` [R] receive what `w2l_s3fd_top_rects` writes - up to
         K candidate rects per frame, in full-frame coordinates at det_scale > 1.  No host read."""
-        from .._lib import check, current_stream, load
-        scale = self.rect_scale(H, W) or (1.0, 1.0)
-        if (any(t.dtype != torch.int32 or not t.is_contiguous() for t in (cands, ncand, flags)) or cands.dim() != 3
-                or tuple(cands.shape[1:]) != (K, 4) or ncand.dim() != 1 or flags.dim() != 1
-                or not ncand.shape[0] == flags.shape[0] == cands.shape[0] or offset < 0 or offset + B > cands.shape[0]):
-            raise ValueError("cands_for_rows: int32 arenas [R,%d,4], [R] and [R] with rows [%d, %d) inside them" % (K, offset, offset + B))
-        with torch.no_grad():
-            table, keep, counts = self._candidates(frames, rows=(B, H, W))
-            check(load().w2l_s3fd_top_rects(current_stream(), B, table.shape[1], table.data_ptr(), keep.data_ptr(), counts.data_ptr(),
-                                            0.5, float(scale[0]), float(scale[1]), K, cands.data_ptr() + 16 * K * offset,
-                                            ncand.data_ptr() + 4 * offset, flags.data_ptr() + 4 * offset), "s3fd_top_rects")
+        self._top_rects("cands_for_rows", B, self.rect_scale(H, W), cands, ncand, flags, offset, K,
+                        lambda: self._candidates(frames, rows=(B, H, W)))
 
     def cands_for_batch(self, images, cands, ncand, flags, offset, K):
         """`cands_for_rows` for a batch of images given as `get_detections_for_batch` takes them (numpy uint8 BGR [B,H,W,3]): the
         arenas' rows [offset, offset + B) are written, the candidates stay on the device and nothing is read back (an image whose
         NMS overflowed is flagged RECT_HOST)"""
-        from .._lib import check, current_stream, load
-        B = len(images)
-        scale = (None if getattr(self, "det_scale", 1) == 1 else self.rect_scale(*images.shape[1:3])) or (1.0, 1.0)
-        if (any(t.dtype != torch.int32 or not t.is_contiguous() for t in (cands, ncand, flags)) or cands.dim() != 3
-                or tuple(cands.shape[1:]) != (K, 4) or ncand.dim() != 1 or flags.dim() != 1
-                or not ncand.shape[0] == flags.shape[0] == cands.shape[0] or offset < 0 or offset + B > cands.shape[0]):
-            raise ValueError("cands_for_batch: int32 arenas [R,%d,4], [R] and [R] with rows [%d, %d) inside them" % (K, offset, offset + B))
-        with torch.no_grad():
-            table, keep, counts = self._candidates(images, resolve=False)
-            check(load().w2l_s3fd_top_rects(current_stream(), B, table.shape[1], table.data_ptr(), keep.data_ptr(), counts.data_ptr(),
-                                            0.5, float(scale[0]), float(scale[1]), K, cands.data_ptr() + 16 * K * offset,
-                                            ncand.data_ptr() + 4 * offset, flags.data_ptr() + 4 * offset), "s3fd_top_rects")
+        self._top_rects("cands_for_batch", len(images), self._batch_scale(images), cands, ncand, flags, offset, K,
+                        lambda: self._candidates(images, resolve=False))
 
     def get_candidates_for_batch(self, images, K):
         """up to K candidate rects per image - `get_detections_for_batch`'s rect is the first of them: a list of (x1, y1, x2, y2)
@@ -163,7 +163,7 @@ class FaceAlignment:
         `track.host_top_rects`, which raises what Python's int() raises."""
         from .s3fd import top_rects
         from .track import host_top_rects
-        scale = None if getattr(self, "det_scale", 1) == 1 else self.rect_scale(*images.shape[1:3])
+        scale = self._batch_scale(images)
         with torch.no_grad():
             table, keep, counts = self._candidates(images)
             cands, ncand, flags = top_rects(table, keep, counts, 0.5, K, scale)
@@ -180,7 +180,7 @@ class FaceAlignment:
         launch (`w2l_s3fd_first_rect`) and one copy back per batch; an image the device flags (a non-finite or huge coordinate)
         takes the per-image host rule below, which raises what Python's int() raises there.  At det_scale > 1 both map the row back
         to the full frame first, by the same float32 multiply."""
-        scale = None if getattr(self, "det_scale", 1) == 1 else self.rect_scale(*images.shape[1:3])
+        scale = self._batch_scale(images)
 
         def first_rect(dets):
             # the best-scoring detection, clipped at the image origin and truncated to ints; None when nothing survived NMS

@@ -175,10 +175,59 @@ def _detect_batch_cands(detector, frames, B, H, W, cands, ncand, cflags, offset,
     detector.cands_for_rows(frames, B, H, W, cands, ncand, cflags, offset, K)
 
 
-def _track_group(n_seg, segs, cands, ncand, cflags, track, rects, flags, status):
-    """w2l_face_track_segments: one face followed through each of the group's clips, in one launch"""
+Arenas = collections.namedtuple("Arenas", "rects flags cands ncand cflags")    # int32 [R,4], [R]; under a track [R,K,4], [R], [R]
+
+
+def detect_rows(detector, addr_dev, spans, batch_size, n_rows, track=None):
+    """The rect stage of the packed and the live path: arenas of `n_rows` rows, and the batches of exactly `batch_size` addresses
+    of the device address table over spans [(H, W, first row, padded end)], one per frame shape.  A batch fills rects / flags, or
+    with `track` the candidate arenas (`track_rows` then writes rects / flags).  No host read."""
+    shapes = [(n_rows, 4), (n_rows,)] + ([] if track is None else [(n_rows, track.cands, 4), (n_rows,), (n_rows,)])
+    rects, flags, cands, ncand, cflags = [torch.empty(s, dtype=torch.int32, device=addr_dev.device) for s in shapes] + [None] * (5 - len(shapes))
+    for H, W, first, padded in spans:
+        for lo in range(first, padded, batch_size):
+            frames = addr_dev[lo * 8:(lo + batch_size) * 8]
+            if track is None:
+                _detect_batch(detector, frames, batch_size, H, W, rects, flags, lo)
+            else:
+                _detect_batch_cands(detector, frames, batch_size, H, W, cands, ncand, cflags, lo, track.cands)
+    return Arenas(rects, flags, cands, ncand, cflags)
+
+
+def track_rows(n_seg, segs, arenas, track, status, state=None):
+    """w2l_face_track_segments, after the batches of `detect_rows`: one face followed through each segment (TRACK_SEGMENT rows) in
+    one launch, from the candidates into the arenas' rects and flags; `state`: the live streams' slot table"""
     from .track import track_segments
-    track_segments(segs, n_seg, cands, ncand, cflags, track, rects, flags, status)
+    track_segments(segs, n_seg, arenas.cands, arenas.ncand, arenas.cflags, track, arenas.rects, arenas.flags, status, state=state)
+
+
+class BoxOut:
+    """the one int32 buffer a finish writes and one copy brings back: boxes [n_boxes][4], with a hold valid [n_boxes], status
+    [n_seg][2], with a track its status words [n_seg] - in that order.  `buffer` is the device tensor; `boxes`, `valid` (None
+    without a hold), `status` and `track_status` (empty without a track) are flat views of it."""
+
+    def __init__(self, n_boxes, n_seg, hold, track, device):
+        self.sizes = (4 * n_boxes, n_boxes if hold else None, 2 * n_seg, n_seg if track else 0)
+        self.buffer = torch.empty(sum(n or 0 for n in self.sizes), dtype=torch.int32, device=device)
+        self.boxes, self.valid, self.status, self.track_status = self._parts(self.buffer)
+
+    def _parts(self, flat):
+        ends = np.cumsum([n or 0 for n in self.sizes]).tolist()
+        return [None if n is None else flat[e - n:e] for n, e in zip(self.sizes, ends)]
+
+    def ptr(self, view):
+        """the device address of a view, also of an empty one (whose own data_ptr() is 0)"""
+        import ctypes
+        return ctypes.c_void_p(self.buffer.data_ptr() + 4 * view.storage_offset())
+
+    def split(self, host, of="clip"):
+        """the parts of the buffer's host copy (numpy int32): (boxes [n_boxes,4], valid [n_boxes] or None, status [n_seg,2], track
+        status [n_seg] or empty); the status words of w2l_face_track_segments are all 0 for a table built here"""
+        boxes, valid, status, track_status = self._parts(host)
+        if track_status.any():
+            raise AssertionError("w2l_face_track_segments did not follow a %s's segment%s"
+                                 % (of, " (status %s)" % track_status.tolist() if of == "clip" else ""))
+        return boxes.reshape(-1, 4), valid, status.reshape(-1, 2), track_status
 
 
 def _finish_segments(n_seg, segs, rects, flags, pads, T, boxes, status):
@@ -224,43 +273,17 @@ def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None):
         r += c.n
     addr[R:] = addr[R - 1]
     st.upload()
-    rects = torch.empty((padded, 4), dtype=torch.int32, device=dev)            # rows [R, padded): the scratch tail
-    flags = torch.empty((padded,), dtype=torch.int32, device=dev)
-    addr_dev = st.tensor(addresses)
-    extra = 0 if track is None else len(clips)   # the track's status words, behind everything else in the one copy back
-    if track is None:
-        for lo in range(0, padded, batch_size):
-            _detect_batch(detector, addr_dev[lo * 8:(lo + batch_size) * 8], batch_size, H, W, rects, flags, lo)
-    else:
-        K = track.cands
-        cands = torch.empty((padded, K, 4), dtype=torch.int32, device=dev)
-        ncand = torch.empty((padded,), dtype=torch.int32, device=dev)
-        cflags = torch.empty((padded,), dtype=torch.int32, device=dev)
-        for lo in range(0, padded, batch_size):
-            _detect_batch_cands(detector, addr_dev[lo * 8:(lo + batch_size) * 8], batch_size, H, W, cands, ncand, cflags, lo, K)
-    if hold is not None:
-        out = torch.empty(5 * R + 2 * len(clips) + extra, dtype=torch.int32, device=dev)    # boxes [R][4], valid [R], status [clips][2]
-        end = 5 * R + 2 * len(clips)
-        if track is not None:
-            _track_group(len(clips), st.tensor(tracks), cands, ncand, cflags, track, rects, flags, out[end:])
-        _finish_runs(len(clips), st.tensor(segments), rects, flags, R, pads, T, hold, out[:4 * R], out[4 * R:5 * R], out[5 * R:end])
-        res = out.cpu().numpy()
-        _tracked(res[end:])
-        return res[:4 * R].reshape(R, 4), res[4 * R:5 * R], res[5 * R:end].reshape(len(clips), 2)
-    out = torch.empty(4 * R + 2 * len(clips) + extra, dtype=torch.int32, device=dev)    # boxes [R][4], then status [clips][2]: one copy back
-    end = 4 * R + 2 * len(clips)
+    arenas = detect_rows(detector, st.tensor(addresses), [(H, W, 0, padded)], batch_size, padded, track)    # rows [R, padded): scratch
+    out = BoxOut(R, len(clips), hold is not None, track is not None, dev)
     if track is not None:
-        _track_group(len(clips), st.tensor(tracks), cands, ncand, cflags, track, rects, flags, out[end:])
-    _finish_segments(len(clips), st.tensor(segments), rects, flags, pads, T, out[:4 * R], out[4 * R:end])
-    res = out.cpu().numpy()                      # the group's one copy back; it also ends the stream's use of the staging buffers
-    _tracked(res[end:])
-    return res[:4 * R].reshape(R, 4), res[4 * R:end].reshape(len(clips), 2)
-
-
-def _tracked(status):
-    """the status words of w2l_face_track_segments for a table built here: all 0"""
-    if len(status) and status.any():
-        raise AssertionError("w2l_face_track_segments did not follow a clip's segment (status %s)" % status.tolist())
+        track_rows(len(clips), st.tensor(tracks), arenas, track, out.track_status)
+    if hold is None:
+        _finish_segments(len(clips), st.tensor(segments), arenas.rects, arenas.flags, pads, T, out.boxes, out.status)
+    else:
+        _finish_runs(len(clips), st.tensor(segments), arenas.rects, arenas.flags, R, pads, T, hold, out.boxes, out.valid, out.status)
+    # the group's one copy back; it also ends the stream's use of the staging buffers
+    boxes, valid, status, _ = out.split(out.buffer.cpu().numpy())
+    return (boxes, status) if hold is None else (boxes, valid, status)
 
 
 def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None):
@@ -319,6 +342,7 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
     `face_track`: None (default), or a pick name / `track.FaceTrack`: one face is followed through every clip instead of taking
     the best-scoring box of each frame (not the reference's behaviour), exactly as `face_detect(face_track=...)`
     does for the clip alone."""
+    from ..inference import halving
     from .track import check_track
     hold = check_hold(no_face_hold)
     track = check_track(face_track)
@@ -366,18 +390,15 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
             continue
         clips = [c for c in group if c.n]
         boxes = status = valid = None
-        while clips:
-            try:
-                if hold is None:
-                    boxes, status = _detect_group(detector, clips, pads, T, batch_size, **tkw)
-                else:
-                    boxes, valid, status = _detect_group(detector, clips, pads, T, batch_size, hold, **tkw)
-                break
-            except RuntimeError:
-                if batch_size == 1:
-                    raise RuntimeError('Image too big to run face detection on GPU. Please use the --resize_factor argument')
-                batch_size //= 2
-                print('Recovering from OOM error; New batch size: {}'.format(batch_size))
+
+        def run_group(size):
+            nonlocal batch_size
+            batch_size = size                              # a halved batch holds for the rest of the run
+            return _detect_group(detector, clips, pads, T, size, *(() if hold is None else (hold,)), **tkw)
+
+        if clips:
+            res = halving(run_group, batch_size)
+            boxes, valid, status = res[0], res[1] if hold is not None else None, res[-1]
         results, row, k = [], 0, 0
         for c in group:
             if c.n == 0:

@@ -88,13 +88,6 @@ main_parser = build_main_parser()
 fps = 25                  # gen_videos_from_filelist.py:120
 
 
-def _track_kw(args):
-    """the `face_track=` keyword of a parsed command line (`--face_track PICK`): none without the flag"""
-    from . import inference
-    from .face_detection.track import track_from_args
-    return inference._track_kw(track_from_args(args))
-
-
 def lines_of_rank(lines, ranks):
     """[(line index, line)] this rank runs: line i belongs to rank i % world (the dealing of preprocess.py)"""
     return [(i, line) for i, line in enumerate(lines) if i % ranks.world == ranks.rank]
@@ -170,8 +163,7 @@ def clip_jobs(args, lines, ranks, detector, tracks):
                 full_frames, mel, pcm, sr = got
                 try:
                     det = inference.face_detect(full_frames, detector=detector, pads=args.pads, nosmooth=False,
-                                                batch_size=args.face_det_batch_size,
-                                                **inference._hold_kw(getattr(args, 'no_face_hold', None)), **_track_kw(args))
+                                                batch_size=args.face_det_batch_size, **inference.detect_kw_from_args(args))
                 except ValueError as e:
                     _skip(idx, line, str(e))
                     continue
@@ -215,7 +207,7 @@ def clip_jobs_packed(args, lines, ranks, detector, tracks):
     with tempfile.TemporaryDirectory(prefix="w2l_filelist_") as tmpdir:
         for idx, boxes, error in face_detection.detect_many(detector, inputs(tmpdir), pads=args.pads, T=5,
                                                             batch_size=args.face_det_batch_size,
-                                                            **inference._hold_kw(getattr(args, 'no_face_hold', None)), **_track_kw(args)):
+                                                            **inference.detect_kw_from_args(args)):
             sys.stderr.write(notes.pop(idx))
             line, full_frames, mel, pcm, sr = held.pop(idx)
             try:
@@ -263,11 +255,11 @@ class ResultSink:
 def main(argv=None, state_dict=None, backend="nccl"):
     """gen_videos_from_filelist.py:152-235.  `state_dict` (S3FD weights) replaces face_detection/s3fd.pth; `backend` is the
     process group's.  Returns the line indices this rank wrote, in order."""
-    from . import face_detection, inference, multiclip, sharding
+    from . import inference, multiclip, sharding
     args = main_parser.parse_args(argv)
     args.img_size = 96
     blend_kw = inference._blend_kw(inference.blend_from_args(args))
-    _track_kw(args)                                      # a flag of the track without --face_track: refused before any device work
+    inference.detect_kw_from_args(args)                  # a flag of the track without --face_track: refused before any device work
     ranks = sharding.init_from_env(backend)
     try:
         assert args.data_root is not None
@@ -276,10 +268,7 @@ def main(argv=None, state_dict=None, backend="nccl"):
         with open(args.filelist, 'r') as filelist:
             lines = filelist.readlines()
         print('Using {} for inference.'.format(ranks.device))
-        detector = face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False, device=str(ranks.device),
-                                                state_dict=state_dict,
-                                                **inference._precision_kw(inference.CLI_PRECISION[args.face_det_precision]),
-                                                **inference._det_scale_kw(getattr(args, 'face_det_scale', 1)))
+        detector = inference.detector_from_args(args, ranks.device, state_dict)
         model = inference.load_model(args.checkpoint_path, ranks.device)
         tracks = {}
         sink = ResultSink(args.results_dir, tracks)

@@ -636,11 +636,23 @@ def get_smoothened_boxes(boxes, T):
     return boxes
 
 
+def halving(run, batch_size):
+    """inference.py:75-88: `run(batch_size)`; a RuntimeError of the detector (out of device memory on a large frame) halves the
+    batch, prints the reference's message and starts over, down to single frames, where it is the reference's error"""
+    while True:
+        try:
+            return run(batch_size)
+        except RuntimeError:
+            if batch_size == 1:
+                raise RuntimeError('Image too big to run face detection on GPU. Please use the --resize_factor argument')
+            batch_size //= 2
+            print('Recovering from OOM error; New batch size: {}'.format(batch_size))
+
+
 def _detect_rects(images, detector, batch_size, ranks=None):
-    """inference.py:75-88: one rect (or None) per frame; a RuntimeError of the detector (out of device memory on a large
-    frame) halves the detection batch and starts over, down to single frames.  With `ranks` every rank detects the frames of its
-    contiguous shard and the per-frame rects (four numbers each) are all-gathered: the box smoothing that follows needs them
-    all, on every rank, in frame order."""
+    """inference.py:75-88: one rect (or None) per frame, in batches under `halving`.  With `ranks` every rank detects the frames
+    of its contiguous shard and the per-frame rects (four numbers each) are all-gathered: the box smoothing that follows needs
+    them all, on every rank, in frame order."""
     if ranks is not None and ranks.dist is not None and ranks.world > 1:
         from . import sharding
         lo, hi = sharding.shard_range(len(images), ranks.rank, ranks.world)
@@ -648,17 +660,14 @@ def _detect_rects(images, detector, batch_size, ranks=None):
         parts = [None] * ranks.world
         ranks.dist.all_gather_object(parts, mine)
         return [r for part in parts for r in part]
-    while True:
-        try:
-            rects = []
-            for lo in range(0, len(images), batch_size):
-                rects += detector.get_detections_for_batch(np.array(images[lo:lo + batch_size]))
-            return rects
-        except RuntimeError:
-            if batch_size == 1:
-                raise RuntimeError('Image too big to run face detection on GPU. Please use the --resize_factor argument')
-            batch_size //= 2
-            print('Recovering from OOM error; New batch size: {}'.format(batch_size))
+
+    def run(batch_size):
+        rects = []
+        for lo in range(0, len(images), batch_size):
+            rects += detector.get_detections_for_batch(np.array(images[lo:lo + batch_size]))
+        return rects
+
+    return halving(run, batch_size)
 
 
 def _track_rects(images, detector, batch_size, track):
@@ -672,39 +681,52 @@ def _track_rects(images, detector, batch_size, track):
     n, K = len(images), track.cands
     if n == 0:
         return []
-    while True:
-        try:
-            dev = torch.device(detector.device)
-            cands = torch.empty((n, K, 4), dtype=torch.int32, device=dev)
-            ncand = torch.empty((n,), dtype=torch.int32, device=dev)
-            cflags = torch.empty((n,), dtype=torch.int32, device=dev)
+
+    def run(batch_size):
+        dev = torch.device(detector.device)
+        cands = torch.empty((n, K, 4), dtype=torch.int32, device=dev)
+        ncand = torch.empty((n,), dtype=torch.int32, device=dev)
+        cflags = torch.empty((n,), dtype=torch.int32, device=dev)
+        for lo in range(0, n, batch_size):
+            detector.cands_for_batch(np.array(images[lo:lo + batch_size]), cands, ncand, cflags, lo, K)
+        seg = np.zeros(1, dtype=TRACK_SEGMENT)
+        seg[0] = (0, n, -1, 0)
+        segs = torch.from_numpy(seg.view(np.uint8)).to(dev)
+        out = torch.empty(5 * n + 1, dtype=torch.int32, device=dev)        # rects [n][4], flags [n], status [1]: one copy back
+        track_segments(segs, 1, cands, ncand, cflags, track, out[:4 * n].view(n, 4), out[4 * n:5 * n], out[5 * n:])
+        res = out.cpu().numpy()
+        rects, flags = res[:4 * n].reshape(n, 4), res[4 * n:5 * n]
+        if res[5 * n] != 0:
+            raise AssertionError("w2l_face_track_segments did not follow the clip's segment (status %d)" % res[5 * n])
+        if (flags == RECT_HOST).any():
+            per_frame = []
             for lo in range(0, n, batch_size):
-                detector.cands_for_batch(np.array(images[lo:lo + batch_size]), cands, ncand, cflags, lo, K)
-            seg = np.zeros(1, dtype=TRACK_SEGMENT)
-            seg[0] = (0, n, -1, 0)
-            segs = torch.from_numpy(seg.view(np.uint8)).to(dev)
-            out = torch.empty(5 * n + 1, dtype=torch.int32, device=dev)        # rects [n][4], flags [n], status [1]: one copy back
-            track_segments(segs, 1, cands, ncand, cflags, track, out[:4 * n].view(n, 4), out[4 * n:5 * n], out[5 * n:])
-            res = out.cpu().numpy()
-            rects, flags = res[:4 * n].reshape(n, 4), res[4 * n:5 * n]
-            if res[5 * n] != 0:
-                raise AssertionError("w2l_face_track_segments did not follow the clip's segment (status %d)" % res[5 * n])
-            if (flags == RECT_HOST).any():
-                per_frame = []
-                for lo in range(0, n, batch_size):
-                    per_frame += detector.get_candidates_for_batch(np.array(images[lo:lo + batch_size]), K)
-                return host_track(per_frame, track)[0]
-            return [tuple(int(v) for v in r) if f == RECT_FOUND else None for r, f in zip(rects, flags)]
-        except RuntimeError:
-            if batch_size == 1:
-                raise RuntimeError('Image too big to run face detection on GPU. Please use the --resize_factor argument')
-            batch_size //= 2
-            print('Recovering from OOM error; New batch size: {}'.format(batch_size))
+                per_frame += detector.get_candidates_for_batch(np.array(images[lo:lo + batch_size]), K)
+            return host_track(per_frame, track)[0]
+        return [tuple(int(v) for v in r) if f == RECT_FOUND else None for r, f in zip(rects, flags)]
+
+    return halving(run, batch_size)
 
 
 def _det_scale_kw(det_scale):
     """detector keyword for a reduced detection frame: scale 1 builds the detector with the same arguments as before the option"""
     return {} if det_scale == 1 else {"det_scale": det_scale}
+
+
+def detector_from_args(args, device, state_dict=None):
+    """the FaceAlignment of a parsed command line on `device`: `--face_det_precision` and `--face_det_scale`, each passed on only
+    when it is not the default; `state_dict` (S3FD weights) replaces face_detection/s3fd.pth"""
+    from . import face_detection
+    return face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False, device=str(device), state_dict=state_dict,
+                                        **_precision_kw(CLI_PRECISION[args.face_det_precision]),
+                                        **_det_scale_kw(getattr(args, 'face_det_scale', 1)))
+
+
+def detect_kw_from_args(args):
+    """the `no_face_hold=` / `face_track=` keywords of `face_detect`, `detect_many` and `LipsyncStreams` for a parsed command line:
+    none for an absent flag; a lone `--face_track_*` flag is a ValueError"""
+    from .face_detection.track import track_from_args
+    return {**_hold_kw(getattr(args, 'no_face_hold', None)), **_track_kw(track_from_args(args))}
 
 
 def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None, ranks=None, precision=None, det_scale=None,
@@ -764,28 +786,22 @@ def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None
     nosmooth = args.nosmooth if nosmooth is None else nosmooth
     batch_size = args.face_det_batch_size if batch_size is None else batch_size
     rects = _detect_rects(images, detector, batch_size, ranks) if track is None else _track_rects(images, detector, batch_size, track)
-    if hold is not None and not (len(rects) == 1 and rects[0] is None):
+    if hold is not None:
         rects = hold_fill(rects, hold)
-        top, bottom, left, right = pads
-        boxes = np.array([[0, 0, 0, 0] if r is None else
-                          [max(0, r[0] - left), max(0, r[1] - top), min(im.shape[1], r[2] + right), min(im.shape[0], r[3] + bottom)]
-                          for r, im in zip(rects, images)], dtype=np.int64).reshape(-1, 4)
-        if not nosmooth:
-            for a, b in boxed_runs([r is not None for r in rects]):
-                get_smoothened_boxes(boxes[a:b], T=5)                  # a view: in place, as on a clip of the run's frames alone
-        return [[None, None] if r is None else [im[y1:y2, x1:x2], (y1, y2, x1, x2)]
-                for r, im, (x1, y1, x2, y2) in zip(rects, images, boxes)]
-    if any(r is None for r in rects):
+    if any(r is None for r in rects) and (hold is None or len(rects) == 1):
         raise ValueError('Face not detected! Ensure the video contains a face in all the frames.')
     top, bottom, left, right = pads
     # (x1, y1, x2, y2) grown by the pads; the near edges are clipped at 0 and the far edges at the frame size ONLY (inference.py:91-98:
     # `max(0, rect[1] - pady1)`, `min(image.shape[0], rect[3] + pady2)`, ...) - a negative pad or a rect beyond the frame is not
-    # pulled back from the other side, exactly as there
-    boxes = np.array([[max(0, r[0] - left), max(0, r[1] - top), min(im.shape[1], r[2] + right), min(im.shape[0], r[3] + bottom)]
-                      for r, im in zip(rects, images)])
+    # pulled back from the other side, exactly as there.  A gap frame's row is zeros; the strict array keeps numpy's own dtype
+    boxes = np.array([[0, 0, 0, 0] if r is None else
+                      [max(0, r[0] - left), max(0, r[1] - top), min(im.shape[1], r[2] + right), min(im.shape[0], r[3] + bottom)]
+                      for r, im in zip(rects, images)], dtype=None if hold is None else np.int64).reshape(-1, 4)
     if not nosmooth:
-        boxes = get_smoothened_boxes(boxes, T=5)
-    return [[im[y1:y2, x1:x2], (y1, y2, x1, x2)] for im, (x1, y1, x2, y2) in zip(images, boxes)]
+        for a, b in boxed_runs([r is not None for r in rects]):    # a strict clip: the one run [0, n)
+            get_smoothened_boxes(boxes[a:b], T=5)                  # a view: in place, as on a clip of the run's frames alone
+    return [[None, None] if r is None else [im[y1:y2, x1:x2], (y1, y2, x1, x2)]
+            for r, im, (x1, y1, x2, y2) in zip(rects, images, boxes)]
 
 
 # ---------------------------------------------------------------- main (inference.py:181-277)
@@ -869,15 +885,12 @@ def main(argv=None, keep_frames=True, backend="nccl"):
     mjpg = args.out_codec == "mjpg"
     if mjpg and not 1 <= args.out_quality <= 100:
         raise ValueError("--out_quality %d is outside [1, 100]" % args.out_quality)
-    if mjpg and int(os.environ.get("WORLD_SIZE", "1")) > 1:         # before the process group and any device work
-        raise ValueError("--out_codec mjpg runs on one GPU: a sharded run gathers raw frames (compressed shards are not gathered yet)")
-    hold_kw = _hold_kw(args.no_face_hold)
-    if hold_kw and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError("--no_face_hold runs on one GPU: the hold looks back over the frames of other shards")
-    from .face_detection.track import track_from_args
-    track_kw = _track_kw(track_from_args(args))
-    if track_kw and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError("--face_track runs on one GPU: the track looks back over the frames of other shards")
+    detect_kw = detect_kw_from_args(args)
+    for given, why in ((mjpg, "--out_codec mjpg runs on one GPU: a sharded run gathers raw frames (compressed shards are not gathered yet)"),
+                       ("no_face_hold" in detect_kw, "--no_face_hold runs on one GPU: the hold looks back over the frames of other shards"),
+                       ("face_track" in detect_kw, "--face_track runs on one GPU: the track looks back over the frames of other shards")):
+        if given and int(os.environ.get("WORLD_SIZE", "1")) > 1:     # before the process group and any device work
+            raise ValueError(why)
     ranks = sharding.init_from_env(backend)
     sharded = ranks.dist is not None and ranks.world > 1
     say = print if ranks.writer else (lambda *a, **k: None)
@@ -897,7 +910,7 @@ def main(argv=None, keep_frames=True, backend="nccl"):
         full_frames = full_frames[:len(starts)]
         if args.box[0] == -1:
             det = face_detect(full_frames if not args.static else [full_frames[0]], ranks=ranks,
-                              precision=CLI_PRECISION[args.face_det_precision], det_scale=args.face_det_scale, **hold_kw, **track_kw)
+                              precision=CLI_PRECISION[args.face_det_precision], det_scale=args.face_det_scale, **detect_kw)
             coords = [c for _, c in det]
         else:
             say('Using the specified bounding box instead of face detection...')

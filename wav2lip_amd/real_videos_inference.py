@@ -366,7 +366,7 @@ def run(args, lines, ranks, detector, model, report=None):
 def main(argv=None, state_dict=None, backend="nccl", report=None):
     """real_videos_inference.py:199-301.  `state_dict` (S3FD weights) replaces face_detection/s3fd.pth; `backend` is the process
     group's.  Returns the line indices this rank wrote, in order."""
-    from . import face_detection, inference, sharding
+    from . import inference, sharding
     args = main_parser.parse_args(argv)
     inference.blend_from_args(args)              # a bad pair raises here, before the process group and any device work
     if args.mode not in MODES:
@@ -378,10 +378,7 @@ def main(argv=None, state_dict=None, backend="nccl", report=None):
             os.makedirs(args.results_dir, exist_ok=True)
         lines = lines_of(args)
         print('Using {} for inference.'.format(ranks.device))
-        detector = face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False, device=str(ranks.device),
-                                                state_dict=state_dict,
-                                                **inference._precision_kw(inference.CLI_PRECISION[args.face_det_precision]),
-                                                **inference._det_scale_kw(getattr(args, 'face_det_scale', 1)))
+        detector = inference.detector_from_args(args, ranks.device, state_dict)
         model = inference.load_model(args.checkpoint_path, ranks.device)
         return run(args, lines, ranks, detector, model, report)
     finally:

@@ -513,20 +513,23 @@ class DeviceBoxes:
     def reserve(self, n_slots):
         """room for carry slots [0, n_slots); the table grows on the launches' stream, so in order with them"""
         old = self.carry.shape[0]
+
+        def grown(table):
+            new = self.torch.zeros((max(n_slots, 2 * old),) + tuple(table.shape[1:]), dtype=self.torch.int32, device=self.device)
+            new[:old].copy_(table)
+            return new
+
         if n_slots > old:
-            grown = self.torch.zeros((max(n_slots, 2 * old),) + tuple(self.carry.shape[1:]), dtype=self.torch.int32, device=self.device)
-            grown[:old].copy_(self.carry)
-            self.carry = grown
+            self.carry = grown(self.carry)
             if self.track is not None:
-                state = self.torch.zeros((grown.shape[0], self.track_state.shape[1]), dtype=self.torch.int32, device=self.device)
-                state[:old].copy_(self.track_state)
-                self.track_state = state
+                self.track_state = grown(self.track_state)
 
     def launch(self, items):
         """items: [(fresh, H, W, slot, seen, closed)] - `fresh` the stream's new frames in order (host arrays, device tensors
         [n,H,W,3]).  Returns a ticket; `ticket["chunks"][k]` are item k's new frames on the device, [(frame count, tensor)]:
         runs of host frames as views of the staging buffer, fed tensors as they are."""
         from ._lib import check, current_stream, ptr
+        from .face_detection.many import BoxOut, detect_rows, track_rows
         torch, live, B, T = self.torch, self.live, self.B, self.T
         SEG = live.BOX_STREAM_SEGMENT
         # ---- rows: the items of one frame shape are one run of arena rows, padded to whole detector batches
@@ -576,62 +579,43 @@ class DeviceBoxes:
         for H, W, first, end, padded in spans:
             addr[end:padded] = addr[end - 1]               # the last batch of a shape: its last address again, into scratch rows
         st.upload()
-        rects = torch.empty((max(total, 1), 4), dtype=torch.int32, device=self.device)
-        flags = torch.empty((max(total, 1),), dtype=torch.int32, device=self.device)
-        addr_dev = st.tensor(addresses)
-        if self.track is None:
-            for H, W, first, end, padded in spans:
-                for lo in range(first, padded, B):
-                    self.detector.rects_for_rows(addr_dev[lo * 8:(lo + B) * 8], B, H, W, rects, flags, lo)
-        else:
-            K = self.track.cands
-            cands = torch.empty((max(total, 1), K, 4), dtype=torch.int32, device=self.device)
-            ncand = torch.empty((max(total, 1),), dtype=torch.int32, device=self.device)
-            cflags = torch.empty((max(total, 1),), dtype=torch.int32, device=self.device)
-            for H, W, first, end, padded in spans:
-                for lo in range(first, padded, B):
-                    self.detector.cands_for_rows(addr_dev[lo * 8:(lo + B) * 8], B, H, W, cands, ncand, cflags, lo, K)
-        # boxes, then (with a hold) valid, then status, then (with a track) its status: one copy back
-        n_out = (4 if self.hold is None else 5) * out0 + 2 * len(items)
-        out = torch.empty(n_out + (0 if self.track is None else len(items)), dtype=torch.int32, device=self.device)
+        arenas = detect_rows(self.detector, st.tensor(addresses), [(H, W, first, padded) for H, W, first, _, padded in spans], B,
+                             max(total, 1), self.track)
+        out = BoxOut(out0, len(items), self.hold is not None, self.track is not None, self.device)     # one copy back
         top, bottom, left, right = self.pads
         with torch.cuda.device(self.device):
             if self.track is not None:                   # every stream's face followed on from its slot: selection is causal, so
-                from .face_detection.track import track_segments      # box i is still final once frame i + T - 1 is there
-                track_segments(st.tensor(tracks), len(items), cands, ncand, cflags, self.track, rects, flags, out[n_out:],
-                               state=self.track_state)
+                track_rows(len(items), st.tensor(tracks), arenas, self.track, out.track_status,       # box i is still final once
+                           state=self.track_state)                                                    # frame i + T - 1 is there
             if self.hold is None:
                 check(self.lib.w2l_face_boxes_stream(current_stream(), len(items), st.host_address(segments), st.address(segments),
-                                                     ptr(rects), ptr(flags), total, ptr(self.carry), int(self.carry.shape[0]), top, bottom,
-                                                     left, right, T, ptr(out), out0, out.data_ptr() + 16 * out0), "face_boxes_stream")
+                                                     ptr(arenas.rects), ptr(arenas.flags), total, ptr(self.carry),
+                                                     int(self.carry.shape[0]), top, bottom, left, right, T, out.ptr(out.boxes), out0,
+                                                     out.ptr(out.status)), "face_boxes_stream")
             else:
                 check(self.lib.w2l_face_boxes_stream_runs(current_stream(), len(items), st.host_address(segments), st.address(segments),
-                                                          ptr(rects), ptr(flags), total, ptr(self.carry), int(self.carry.shape[0]), top,
-                                                          bottom, left, right, T, self.hold, ptr(out), out.data_ptr() + 16 * out0, out0,
-                                                          out.data_ptr() + 20 * out0), "face_boxes_stream_runs")
-        host_out = torch.empty(out.numel(), dtype=torch.int32, pin_memory=True)
-        host_out.copy_(out, non_blocking=True)
+                                                          ptr(arenas.rects), ptr(arenas.flags), total, ptr(self.carry),
+                                                          int(self.carry.shape[0]), top, bottom, left, right, T, self.hold,
+                                                          out.ptr(out.boxes), out.ptr(out.valid), out0, out.ptr(out.status)),
+                      "face_boxes_stream_runs")
+        host_out = torch.empty(out.buffer.numel(), dtype=torch.int32, pin_memory=True)
+        host_out.copy_(out.buffer, non_blocking=True)
         done = torch.cuda.Event()
         done.record()
         counts = [int(c) for c in np.diff(np.append(segs["out0"], out0))]
-        return dict(chunks=chunks, counts=counts, host_out=host_out, done=done, keep=(st.host, st.dev, rects, flags, out),
-                    valid=self.hold is not None)         # the arenas of a track are freed in stream order: nothing else holds them
+        # the arenas of a track are freed in stream order: nothing else holds them
+        return dict(chunks=chunks, counts=counts, host_out=host_out, done=done, keep=(st.host, st.dev, arenas.rects, arenas.flags),
+                    out=out)
 
     @staticmethod
     def collect(ticket):
         """wait for the launch's event; [(boxes int32 [count,4] of (y1, y2, x1, x2), (code, frame))] per item, with a hold
         [(boxes, (code, frame), valid int32 [count])]"""
         ticket["done"].synchronize()
-        res = ticket["host_out"].numpy()
-        n = sum(ticket["counts"])
-        valid = res[4 * n:5 * n] if ticket["valid"] else None
-        at = (4 if valid is None else 5) * n
-        status = res[at:at + 2 * len(ticket["counts"])].reshape(-1, 2)
-        if res[at + 2 * len(ticket["counts"]):].any():   # the words of w2l_face_track_segments, for a table built here: all 0
-            raise AssertionError("w2l_face_track_segments did not follow a stream's segment")
+        boxes, valid, status, _ = ticket["out"].split(ticket["host_out"].numpy(), of="stream")
         out, r = [], 0
         for k, c in enumerate(ticket["counts"]):
-            item = (res[4 * r:4 * (r + c)].reshape(c, 4).copy(), (int(status[k][0]), int(status[k][1])))
+            item = (boxes[r:r + c].copy(), (int(status[k][0]), int(status[k][1])))
             out.append(item if valid is None else item + (valid[r:r + c].copy(),))
             r += c
         return out
@@ -1214,18 +1198,13 @@ def main(argv=None, state_dict=None):
     from . import audio, inference
     a = build_parser().parse_args(argv)
     blend = inference.blend_from_args(a)
-    hold_kw = inference._hold_kw(a.no_face_hold)
-    from .face_detection.track import track_from_args
-    track_kw = inference._track_kw(track_from_args(a))   # `--face_track PICK`: one face followed through every video
+    detect_kw = inference.detect_kw_from_args(a)         # `--no_face_hold G`, `--face_track PICK`
     if len(a.face) != len(a.audio):
         raise ValueError("%d --face for %d --audio: pass them in pairs" % (len(a.face), len(a.audio)))
     dev = torch.device("cuda", torch.cuda.current_device())
     detector = None
     if a.live_video or state_dict is not None:
-        from . import face_detection
-        detector = face_detection.FaceAlignment(face_detection.LandmarksType._2D, flip_input=False, device=str(dev), state_dict=state_dict,
-                                                **inference._precision_kw(inference.CLI_PRECISION[a.face_det_precision]),
-                                                **inference._det_scale_kw(a.face_det_scale))
+        detector = inference.detector_from_args(a, dev, state_dict)
     jobs = []
     for k, (face, wav_path) in enumerate(zip(a.face, a.audio)):
         one = copy.copy(a)
@@ -1241,7 +1220,7 @@ def main(argv=None, state_dict=None):
         elif a.box[0] == -1:
             det = inference.face_detect(frames if not one.static else [frames[0]], detector=detector, pads=a.pads, nosmooth=a.nosmooth,
                                         batch_size=a.face_det_batch_size, precision=inference.CLI_PRECISION[a.face_det_precision],
-                                        det_scale=a.face_det_scale, **hold_kw, **track_kw)
+                                        det_scale=a.face_det_scale, **detect_kw)
             boxes = [c for _, c in det]
         else:
             boxes = [tuple(a.box)] * len(frames)
@@ -1266,7 +1245,7 @@ def main(argv=None, state_dict=None):
 
     streams = LipsyncStreams(model, batch_size=a.wav2lip_batch_size, precision=inference.CLI_PRECISION[a.precision], sink=sink,
                              detector=detector, pads=a.pads, smooth_T=0 if a.nosmooth else 5, face_det_batch_size=a.face_det_batch_size,
-                             **inference._blend_kw(blend), **hold_kw, **track_kw)
+                             **inference._blend_kw(blend), **detect_kw)
     for j in jobs:
         if j["live"]:
             streams.open_live(j["key"], fps=j["fps"], sample_rate=j["rate"])
