@@ -257,6 +257,24 @@ int w2l_resize_blend_u8(void* stream, int B, const uint8_t* pred, int S, const i
 int w2l_compose_blend_rows_u8(void* stream, int B, const uint8_t* pred, int S, const w2l_frame_row* rows, int max_frame_pixels,
                               int feather, int top_q8);
 
+/* Colour matching of generated faces to the crops they were generated from (opt-in: NOT the reference's output, which pastes
+ * the prediction as the generator gave it).  Integer-only and exact.  Row b: pred u8 [S,S,3] (the generator's output) and ref
+ * u8 [S,S,3] (the crop it was given), both BGR, rows contiguous.  The generator is shown the upper half of the crop unmasked,
+ * so the statistics are taken over rows 0 .. S/2-1 only (N = S/2 * S pixels), per channel:
+ *   Sp = sum pred, So = sum ref, Qp = sum pred^2, Qo = sum ref^2         (exact, uint32 for S <= 256)
+ *   Vp = N*Qp - Sp^2, Vo = N*Qo - So^2                                    (>= 0, uint64)
+ *   mode 1 (mean): g = 256
+ *   mode 2 (full): g = 256 if Vp == 0, else clamp(isqrt(floor((Vo << 16) / Vp)), 128, 512)   (floor square root; Q8, [0.5, 2])
+ * and every pixel x of that channel, in all S rows, becomes
+ *   out = clamp(floor((g*(N*x - Sp) + 256*So + 128*N) / (256*N)), 0, 255)      (int64; floor division of a signed numerator)
+ * Equal upper halves give out == pred everywhere.  The arithmetic is csrc/color_match_core.h, shared with a host program.
+ *
+ * out == pred is allowed (in place: a row's statistics are complete before any byte of it is written); out may otherwise not
+ * overlap pred; ref is never written; nothing outside out[0 .. B*S*S*3) is written.  Any base address works.  One launch
+ * whatever B; B == 0 launches nothing.  Refused with an error code, writing nothing: B < 0, S odd or outside [2, 256], mode
+ * other than 1 or 2, a NULL pointer with B > 0. */
+int w2l_color_match_u8(void* stream, int B, const uint8_t* pred, const uint8_t* ref, int S, int mode, uint8_t* out);
+
 /* Whole-frame row-table resize (evaluation/real_videos_inference.py:51-70 rescale_frames, :239-245 the `max_frame_res` cap at read
  * time): row b gives dst_b u8 [Hd,Wd,3] = cv2.resize(src_b u8 [Hs,Ws,3], (Wd,Hd)), byte-equal to w2l_resize_u8 for that frame
  * (the same arithmetic, the equal-size copy and the exact-2x INTER_AREA branch included).  Rows of different shapes share one

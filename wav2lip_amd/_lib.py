@@ -201,6 +201,7 @@ SIGNATURES = {
     "w2l_compose_rows_u8": (_i, [_vp, _i, _vp, _i, _vp, _i]),
     "w2l_resize_blend_u8": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "w2l_compose_blend_rows_u8": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i]),
+    "w2l_color_match_u8": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp]),
     "w2l_resize_rows_u8": (_i, [_vp, _i, _vp, _i]),
     "w2l_jpeg_encode_rows": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, C.c_size_t]),
     "w2l_jpeg_workspace_bytes": (C.c_size_t, [_i, _i]),

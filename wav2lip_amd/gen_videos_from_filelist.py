@@ -68,15 +68,17 @@ def build_main_parser():
     """what `main()` parses: `build_cli_parser` plus `--packed_face_det`, which changes how the work is scheduled and nothing of
     what is computed, and `--face_det_scale K`, the size of the frame the detector sees (`inference.add_det_scale_flag`).
     `--blend_feather N` / `--blend_top FRACTION` blend every generated face into its frame (`inference.add_blend_flags`).
+    `--color_match {mean,full}` matches every generated face's colours to its crop first (`inference.add_color_match_flag`).
     `--no_face_hold G` generates a line with frames without a face instead of skipping it (`inference.add_hold_flag`).
     `--face_track PICK` follows one face through every line's clip (`inference.add_track_flags`), with and without
     `--packed_face_det`.  `cli_parser` stays the reference's surface plus the two precision flags."""
-    from .inference import add_blend_flags, add_det_scale_flag, add_hold_flag, add_track_flags
+    from .inference import add_blend_flags, add_color_match_flag, add_det_scale_flag, add_hold_flag, add_track_flags
     p = build_cli_parser()
     p.add_argument('--packed_face_det', default=False, action='store_true',
                    help='Detect faces of successive clips in shared detector batches (face_detection.detect_many)')
     add_det_scale_flag(p)
     add_blend_flags(p)
+    add_color_match_flag(p)
     add_hold_flag(p)
     add_track_flags(p)
     return p
@@ -259,6 +261,7 @@ def main(argv=None, state_dict=None, backend="nccl"):
     args = main_parser.parse_args(argv)
     args.img_size = 96
     blend_kw = inference._blend_kw(inference.blend_from_args(args))
+    color_kw = inference._color_kw(inference.color_match_from_args(args))
     inference.detect_kw_from_args(args)                  # a flag of the track without --face_track: refused before any device work
     ranks = sharding.init_from_env(backend)
     try:
@@ -275,7 +278,7 @@ def main(argv=None, state_dict=None, backend="nccl"):
         try:
             producer = clip_jobs_packed if args.packed_face_det else clip_jobs
             multiclip.lipsync_many(model, producer(args, lines, ranks, detector, tracks), batch_size=args.wav2lip_batch_size,
-                                   precision=inference.CLI_PRECISION[args.precision], sink=sink, **blend_kw)
+                                   precision=inference.CLI_PRECISION[args.precision], sink=sink, **blend_kw, **color_kw)
         finally:
             sink.close()
         return sink.written

@@ -167,13 +167,50 @@ def blend_from_args(a):
     return check_blend((getattr(a, "blend_feather", 0), getattr(a, "blend_top", 0.0)))
 
 
+# ---------------------------------------------------------------- colour matching of the prediction (opt-in)
+COLOR_MATCH_MODES = {"mean": 1, "full": 2}      # the `color_match=` spelling -> the `mode` of w2l_color_match_u8
+
+
+def check_color_match(value):
+    """the `color_match=` of the runners, `lipsync`, `multiclip.lipsync_many` and `streaming.LipsyncStreams`: None (the
+    prediction is pasted as the generator gave it, the reference's behaviour), "mean" (every channel's mean over the upper half of
+    the prediction is moved onto the crop's) or "full" (mean and spread).  Returns the value; a ValueError names the choices."""
+    if value is None:
+        return None
+    if not isinstance(value, str) or value not in COLOR_MATCH_MODES:
+        raise ValueError("color_match must be None, 'mean' or 'full', got %r" % (value,))
+    return value
+
+
+def _color_kw(color_match):
+    """the keyword a runner (or what builds one) takes for `color_match`, checked first: none when it is off (as `_blend_kw`)"""
+    color_match = check_color_match(color_match)
+    return {} if color_match is None else {"color_match": color_match}
+
+
+def add_color_match_flag(p):
+    """`--color_match {mean,full}` on a command's parser; absent by default and independent of --blend_*, --precision,
+    --no_face_hold, --face_track, --out_codec and sharded runs"""
+    p.add_argument('--color_match', default=None, choices=sorted(COLOR_MATCH_MODES),
+                   help='Match the colours of every generated face to the crop it was generated from before it is pasted: the '
+                        'per-channel mean (mean) or mean and spread (full) over the upper half of the face, which the generator '
+                        'is shown. Off by default, as the reference. Not the reference\'s output')
+
+
+def color_match_from_args(a):
+    """the `color_match=` of a parsed command line (`add_color_match_flag`): None when the flag is absent, or when the namespace
+    comes from a parser without it"""
+    return check_color_match(getattr(a, "color_match", None))
+
+
 def build_cli_parser():
     """the command line `main()` parses: the reference's flags (`build_parser`, whose surface stays the reference's) plus
     documented additions that are not among them, each the reference's behaviour by default and independent of the others:
     `--precision {fp32,bf16}`, the generator's arithmetic, `--face_det_precision {fp32,bf16}`, the S3FD detector's,
     `--face_det_scale K`, the detector's frame size (1/K; output frames keep theirs), `--out_codec` / `--out_quality`,
-    `--blend_feather N` / `--blend_top FRACTION`, the feathered mouth-region paste, `--no_face_hold G`, the pass-through for
-    frames without a face (absent by default), and `--face_track PICK` with its three companions, tracked face selection
+    `--blend_feather N` / `--blend_top FRACTION`, the feathered mouth-region paste, `--color_match {mean,full}`, colour matching
+    of the prediction to its crop (absent by default), `--no_face_hold G`, the pass-through for frames without a face (absent by
+    default), and `--face_track PICK` with its three companions, tracked face selection
     (`face_detection/track.py`; absent by default)"""
     p = build_parser()
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
@@ -189,6 +226,7 @@ def build_cli_parser():
                         'bytes come back; lossy, about a tenth of the size at quality 95)')
     p.add_argument('--out_quality', default=95, type=int, help='JPEG quality of --out_codec mjpg, 1..100 (default 95)')
     add_blend_flags(p)
+    add_color_match_flag(p)
     add_hold_flag(p)
     add_track_flags(p)
     return p
@@ -270,13 +308,14 @@ def mel_chunk_starts(n_mel_frames, fps):
 class Wav2LipRunner:
     """Device-resident replacement of the body of the reference's batch loop for one model and batch size."""
 
-    def __init__(self, model, batch_size=128, lane=0, precision="f32", blend=None):
+    def __init__(self, model, batch_size=128, lane=0, precision="f32", blend=None, color_match=None):
         from .models.wav2lip import check_precision
         self.model = model
         self.batch_size = batch_size
         self.lane = lane
         self.precision = check_precision(precision)
         self.blend = check_blend(blend)      # None: the reference's paste; (feather, top): `run_frames` / `run_rows` blend
+        self.color_match = check_color_match(color_match)   # None, or "mean" / "full": `run_batch` matches its frames to the faces
         self.device = next(model.parameters()).device
         if self.device.type != "cuda":
             raise RuntimeError("wav2lip_amd.inference: the model must be on a HIP device (no CPU path)")
@@ -291,7 +330,8 @@ class Wav2LipRunner:
         float32 [n,80,16], or as the full spectrogram `mel` [80,T] plus int32 `starts` [n] (device tensors), or as
         `mel_rows`: a device uint8 tensor holding n w2l_mel_row entries (one spectrogram per row, wav2lip_amd/multiclip.py).
         Returns torch uint8 [n,96,96,3] (BGR order preserved), valid until the next call; `out` (a contiguous uint8
-        [n,96,96,3] device tensor, e.g. the send slot of the multi-GPU frame gatherer) receives the frames instead."""
+        [n,96,96,3] device tensor, e.g. the send slot of the multi-GPU frame gatherer) receives the frames instead.  With
+        `color_match` one more launch matches the frames to `faces_u8` in place (w2l_color_match_u8), whatever consumes them."""
         n = faces_u8.shape[0]
         cap = self.model.MAX_PLAN_BATCH
         if n > cap:     # one NHWC buffer must stay below 2 GiB: run equal chunks and concatenate the uint8 frames
@@ -307,7 +347,8 @@ class Wav2LipRunner:
                 return out
             return allf
         g = self._graph(n)
-        g.pack_faces(faces_u8.contiguous())
+        faces_u8 = faces_u8.contiguous()
+        g.pack_faces(faces_u8)
         g.load_mel(mel, starts, windows=mel_windows, rows=mel_rows)
         g.run()
         if out is not None:
@@ -319,6 +360,9 @@ class Wav2LipRunner:
             out = torch.empty((n, img_size, img_size, 3), dtype=torch.uint8, device=self.device)
             self._out_u8[n] = out
         g.frames_into(out)
+        if self.color_match is not None:
+            check(self.lib.w2l_color_match_u8(current_stream(), n, ptr(out), ptr(faces_u8), img_size,
+                                              COLOR_MATCH_MODES[self.color_match], ptr(out)), "color_match_u8")
         self._last = g
         return out
 
@@ -379,8 +423,9 @@ class PipelinedRunner:
     ticket; `result(ticket)` makes the caller's stream wait for that batch and returns its uint8 frames (valid until the lane is
     reused `depth` submits later)."""
 
-    def __init__(self, model, batch_size=128, depth=2, precision="f32", blend=None):
-        self.lanes = [Wav2LipRunner(model, batch_size, lane=k, precision=precision, **_blend_kw(blend)) for k in range(depth)]
+    def __init__(self, model, batch_size=128, depth=2, precision="f32", blend=None, color_match=None):
+        self.lanes = [Wav2LipRunner(model, batch_size, lane=k, precision=precision, **_blend_kw(blend), **_color_kw(color_match))
+                      for k in range(depth)]
         dev = self.lanes[0].device
         self.streams = [torch.cuda.Stream(device=dev) for _ in range(depth)]
         self.depth = depth
@@ -537,11 +582,13 @@ def _precision_kw(precision):
 
 
 def lipsync(model, frames, wav, fps=25., batch_size=128, static=False, box=None, ranks=None, depth=None, precision="f32",
-            blend=None):
+            blend=None, color_match=None):
     """End-to-end body of inference.py:main for in-memory inputs: returns the list of output frames (uint8).
     `precision`: "f32" (default) or "bf16" - the generator's arithmetic (Wav2LipRunner); everything else is the same.
     `blend`: None (default, the reference's paste) or (feather, top), the feathered mouth-region paste (`check_blend`).  It is a
     device paste: frames of one shape and a `box` (a 96x96 one included); anything else raises ValueError before any device work.
+    `color_match`: None (default), "mean" or "full" (`check_color_match`): every prediction is matched to its crop on the device
+    before either paste, the host one included.
 
     `ranks` (sharding.init_from_env(), one process per GPU): the mel chunks are cut into contiguous per-rank shards
     (sharding.shard_range), every rank runs ITS chunks through its own runner with the replicated weights, and the generated
@@ -550,6 +597,7 @@ def lipsync(model, frames, wav, fps=25., batch_size=128, static=False, box=None,
     from .models.wav2lip import check_precision
     check_precision(precision)
     blend = check_blend(blend)
+    color_kw = _color_kw(color_match)
     if blend is not None and (box is None or len({tuple(f.shape) for f in frames}) != 1):
         raise ValueError("blend=%r needs the device paste: frames of one shape and a `box`; the host paste of pre-sized faces has "
                          "no blend" % (blend,))
@@ -564,7 +612,8 @@ def lipsync(model, frames, wav, fps=25., batch_size=128, static=False, box=None,
     from . import sharding
     first, last = sharding.shard_range(len(starts), rank, world)
     # later batches are enqueued before batch i is collected; the default precision constructs the runner exactly as before
-    runner = PipelinedRunner(model, batch_size, depth=depth or LIPSYNC_DEPTH, **_precision_kw(precision), **_blend_kw(blend))
+    runner = PipelinedRunner(model, batch_size, depth=depth or LIPSYNC_DEPTH, **_precision_kw(precision), **_blend_kw(blend),
+                             **color_kw)
     out_frames = []
     starts_dev = torch.tensor(starts, dtype=torch.int32, device=dev)
     shapes = {tuple(f.shape) for f in frames}
@@ -864,7 +913,9 @@ def main(argv=None, keep_frames=True, backend="nccl"):
     reference shells out to ffmpeg for anything else), and the result - the reference's `temp/result.avi` + ffmpeg mux - is
     written as ONE AVI (BGR video + the driving audio as PCM16) at `--outfile`.  Flags the reference does not have, each
     the reference's behaviour by default and independent: `--blend_feather N` / `--blend_top FRACTION` blend the generated face
-    into the frame instead of pasting a rectangle (every rank of a sharded run pastes its own shard), `--precision {fp32,bf16}` selects the generator's arithmetic,
+    into the frame instead of pasting a rectangle (every rank of a sharded run pastes its own shard),
+    `--color_match {mean,full}` matches the colours of every generated face to its crop before the paste,
+    `--precision {fp32,bf16}` selects the generator's arithmetic,
     `--face_det_precision {fp32,bf16}` the S3FD face detector's and `--face_det_scale K` the size of the frame it sees (1/K;
     the output keeps the input's size) - every rank of a sharded run detects its shard with both.
 
@@ -882,6 +933,7 @@ def main(argv=None, keep_frames=True, backend="nccl"):
     from . import sharding
     args = parse_args(argv)
     blend = blend_from_args(args)
+    color_kw = _color_kw(color_match_from_args(args))
     mjpg = args.out_codec == "mjpg"
     if mjpg and not 1 <= args.out_quality <= 100:
         raise ValueError("--out_quality %d is outside [1, 100]" % args.out_quality)
@@ -924,7 +976,7 @@ def main(argv=None, keep_frames=True, backend="nccl"):
                  validate_boxes([coords[0 if args.static else j]], *full_frames[j].shape[:2])[0] for j in idx]
         starts_dev = torch.tensor(starts, dtype=torch.int32, device=dev)
         runner = PipelinedRunner(model, args.wav2lip_batch_size, depth=LIPSYNC_DEPTH, **_precision_kw(CLI_PRECISION[args.precision]),
-                                 **_blend_kw(blend))
+                                 **_blend_kw(blend), **color_kw)
         bs = args.wav2lip_batch_size
         first, last = sharding.shard_range(n, ranks.rank, ranks.world)
         frame_h, frame_w = full_frames[0].shape[:2]

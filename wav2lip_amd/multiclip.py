@@ -137,11 +137,12 @@ class BatchRunner:
     `submit(rows, pad_to=m)` launches m >= len(rows) rows: the last row repeated with a scratch destination, so that a ragged
     batch runs a plan of a committed size; the padded rows' outputs are dropped."""
 
-    def __init__(self, model, batch_size, depth, precision, blend=None):
+    def __init__(self, model, batch_size, depth, precision, blend=None, color_match=None):
         import torch
-        from .inference import PipelinedRunner, _blend_kw, _precision_kw
+        from .inference import PipelinedRunner, _blend_kw, _color_kw, _precision_kw
         self.torch = torch
-        self.runner = PipelinedRunner(model, batch_size, depth=depth, **_precision_kw(precision), **_blend_kw(blend))
+        self.runner = PipelinedRunner(model, batch_size, depth=depth, **_precision_kw(precision), **_blend_kw(blend),
+                                      **_color_kw(color_match))
         self.device = self.runner.lanes[0].device
 
     def submit(self, rows, pad_to=None):
@@ -234,7 +235,7 @@ def _checked_rows_resident(job, T):
     return rows
 
 
-def lipsync_many(model, jobs, batch_size=128, depth=None, precision="f32", sink=None, blend=None):
+def lipsync_many(model, jobs, batch_size=128, depth=None, precision="f32", sink=None, blend=None, color_match=None):
     """Run every `ClipJob` of the iterable `jobs` (consumed lazily) through the generator, rows packed across job boundaries
     into batches of `batch_size` (only the last one ragged) on `depth` (default LIPSYNC_DEPTH) lanes.
 
@@ -243,14 +244,15 @@ def lipsync_many(model, jobs, batch_size=128, depth=None, precision="f32", sink=
     sink the frames are collected and returned as {key: [frames]}.  Memory is bounded whatever the number of jobs: a job's
     frames and mel are released when its last row has been delivered, and the jobs alive at any time are those the rows of at
     most `depth + 1` batches touch, plus the one being read.  `blend`: None (the reference's paste) or (feather, top), every
-    row's face blended into its frame (`inference.check_blend`, w2l_compose_blend_rows_u8).
+    row's face blended into its frame (`inference.check_blend`, w2l_compose_blend_rows_u8).  `color_match`: None, "mean" or
+    "full", every row's prediction matched to its crop before the paste (`inference.check_color_match`, w2l_color_match_u8).
 
     A row whose box is None takes no batch row: `sink` receives its frame's own bytes (copied back from the device for a
     resident job) in its place in the row order, as soon as the rows before it have been delivered."""
-    from .inference import _blend_kw
+    from .inference import _blend_kw, _color_kw
     from .models.wav2lip import check_precision
     check_precision(precision)
-    blend_kw = _blend_kw(blend)
+    paste_kw = dict(_blend_kw(blend), **_color_kw(color_match))
     if batch_size < 1:
         raise ValueError("batch_size must be at least 1")
     depth = depth or LIPSYNC_DEPTH
@@ -309,7 +311,7 @@ def lipsync_many(model, jobs, batch_size=128, depth=None, precision="f32", sink=
     for cj in jobs:
         rows = _checked_rows(cj)
         if runner is None:
-            runner = BatchRunner(model, batch_size, depth, precision, **blend_kw)
+            runner = BatchRunner(model, batch_size, depth, precision, **paste_kw)
         if not rows:                                   # nothing to run: closed in job order
             if last is not None and last.delivered < last.n_rows:
                 last.closed_after.append(cj.key)

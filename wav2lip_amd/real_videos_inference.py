@@ -85,12 +85,14 @@ def build_cli_parser():
 
 def build_main_parser():
     """what `main()` parses: `build_cli_parser` plus `--face_det_scale K`, the size of the frame the detector sees
-    (`inference.add_det_scale_flag`), and `--blend_feather N` / `--blend_top FRACTION`, the blended paste
-    (`inference.add_blend_flags`); `cli_parser` stays the reference's surface plus the two precision flags"""
-    from .inference import add_blend_flags, add_det_scale_flag
+    (`inference.add_det_scale_flag`), `--blend_feather N` / `--blend_top FRACTION`, the blended paste
+    (`inference.add_blend_flags`), and `--color_match {mean,full}`, the prediction's colours matched to its crop
+    (`inference.add_color_match_flag`); `cli_parser` stays the reference's surface plus the two precision flags"""
+    from .inference import add_blend_flags, add_color_match_flag, add_det_scale_flag
     p = build_cli_parser()
     add_det_scale_flag(p)
     add_blend_flags(p)
+    add_color_match_flag(p)
     return p
 
 
@@ -357,7 +359,8 @@ def run(args, lines, ranks, detector, model, report=None):
     try:
         multiclip.lipsync_many(model, clip_jobs(args, lines, ranks, detector, tracks, report), batch_size=args.wav2lip_batch_size,
                                precision=inference.CLI_PRECISION[args.precision], sink=sink,
-                               **inference._blend_kw(inference.blend_from_args(args)))
+                               **inference._blend_kw(inference.blend_from_args(args)),
+                               **inference._color_kw(inference.color_match_from_args(args)))
     finally:
         sink.close()
     return sink.written

@@ -826,15 +826,16 @@ class LipsyncStreams:
 
     def __init__(self, model, batch_size=128, depth=None, precision="f32", fps=25., sink=None, on_batch=None, mel_window=1024,
                  detector=None, pads=(0, 10, 0, 0), smooth_T=5, face_det_batch_size=16, resample_buffer=1 << 16, blend=None,
-                 no_face_hold=None, face_track=None):
+                 no_face_hold=None, face_track=None, color_match=None):
         from .face_detection.many import check_hold
         from .face_detection.track import check_track
-        from .inference import check_blend
+        from .inference import check_blend, check_color_match
         from .models.wav2lip import check_precision
         self.hold = check_hold(no_face_hold)             # None, or G: frames without a face pass through (module docstring)
         self.track = check_track(face_track)             # None, or a FaceTrack: live streams follow one face
         self.precision = check_precision(precision)
         self.blend = check_blend(blend)                  # None, or (feather, top): every frame's face is blended in
+        self.color_match = check_color_match(color_match)   # None, "mean" or "full": every prediction is matched to its crop
         if batch_size < 1:
             raise ValueError("batch_size must be at least 1")
         if mel_window < MIN_WINDOW:
@@ -961,8 +962,9 @@ class LipsyncStreams:
     # ---- the tick
     def _backend(self):
         if self._runner is None:
-            from .inference import _blend_kw
-            self._runner = BatchRunner(self.model, self.batch_size, self.depth, self.precision, **_blend_kw(self.blend))
+            from .inference import _blend_kw, _color_kw
+            self._runner = BatchRunner(self.model, self.batch_size, self.depth, self.precision, **_blend_kw(self.blend),
+                                       **_color_kw(self.color_match))
             self._mel = DeviceMel(self._runner.device)
         if self._boxes is None and self.detector is not None:
             self._boxes = DeviceBoxes(self._runner.device, self.detector, self.pads, self.smooth_T, self.face_det_batch_size,
@@ -1176,9 +1178,10 @@ def build_parser():
                    help='Feed the frames of every video as they become due with the audio and detect faces as they arrive')
     p.add_argument('--native_rate', default=False, action='store_true',
                    help="Feed every WAV at the file's own rate and format; it is converted to 16 kHz on the device as it streams")
-    from .inference import add_blend_flags, add_det_scale_flag, add_hold_flag, add_track_flags
+    from .inference import add_blend_flags, add_color_match_flag, add_det_scale_flag, add_hold_flag, add_track_flags
     add_det_scale_flag(p)
     add_blend_flags(p)
+    add_color_match_flag(p)
     add_hold_flag(p)
     add_track_flags(p)
     return p
@@ -1198,6 +1201,7 @@ def main(argv=None, state_dict=None):
     from . import audio, inference
     a = build_parser().parse_args(argv)
     blend = inference.blend_from_args(a)
+    color_kw = inference._color_kw(inference.color_match_from_args(a))
     detect_kw = inference.detect_kw_from_args(a)         # `--no_face_hold G`, `--face_track PICK`
     if len(a.face) != len(a.audio):
         raise ValueError("%d --face for %d --audio: pass them in pairs" % (len(a.face), len(a.audio)))
@@ -1245,7 +1249,7 @@ def main(argv=None, state_dict=None):
 
     streams = LipsyncStreams(model, batch_size=a.wav2lip_batch_size, precision=inference.CLI_PRECISION[a.precision], sink=sink,
                              detector=detector, pads=a.pads, smooth_T=0 if a.nosmooth else 5, face_det_batch_size=a.face_det_batch_size,
-                             **inference._blend_kw(blend), **detect_kw)
+                             **inference._blend_kw(blend), **color_kw, **detect_kw)
     for j in jobs:
         if j["live"]:
             streams.open_live(j["key"], fps=j["fps"], sample_rate=j["rate"])
