@@ -1,18 +1,23 @@
 """Cases, float64 references, error bounds and launch rules shared by tests/test_glue_cases_cpu.py (numpy fp32 restatements of
-the kernels' arithmetic) and tests/test_glue_kernels_gpu.py (the fp32 detector glue of csrc/detect.hip - w2l_s3fd_decode,
-w2l_maxpool2x2, w2l_l2norm_scale, w2l_s3fd_pack - and the input packing of csrc/api.hip - w2l_datagen_pack(_bf16),
-w2l_frames_to_u8, w2l_nchw_to_nhwc, w2l_nhwc_to_nchw).  No fixtures, no tests: numpy only.
+the kernels' arithmetic) and tests/test_glue_kernels_gpu.py (the detector glue of csrc/detect.hip - w2l_s3fd_decode and, for
+fp32 and bf16 storage, w2l_maxpool2x2, w2l_l2norm_scale, w2l_s3fd_pack - and the input packing of csrc/api.hip -
+w2l_datagen_pack(_bf16), w2l_frames_to_u8, w2l_nchw_to_nhwc, w2l_nhwc_to_nchw).  No fixtures, no tests: numpy only.
 
 U = 2^-24 is the unit roundoff of fp32, R = 2^-21 = 8 U the allowance for one short fp32 expression with one transcendental
 (tests/_loss_cases.py).  Every bound below is derived from fp32 roundoff next to its reference; none is measured from a kernel.
 The float64 references follow the operation's definition (oracle/s3fd_ref.py::dense_boxes, ::l2norm), not the kernels; the
-`*_f32` functions restate the kernels operation by operation in numpy fp32 (no contraction), and the launch rules (`grid1d`,
-`grid_cap`, the store-path selections) are transcribed from detect.hip, api.hip and w2l_common.h.
+`*_f32` functions restate the kernels operation by operation in numpy fp32 (no contraction), and the launch rules (`grid_cap`,
+the cap of every launch, the store-path selections) are transcribed from detect.hip, api.hip and w2l_common.h.
+
+The glue kernels are one body for two storages, `kind` "fp32" or "bf16": a thread moves VEC[kind] channels (16 bytes).  The bf16
+case tables hold the smallest shapes at which each kernel can still go wrong; inputs are rounded to bf16 first (`to_bf16`), so
+the references start from what the kernel reads, and UB = 2^-8 is the unit roundoff of the one rounding on a bf16 store.
 
 `decode_ref` takes `xp`, the array namespace (numpy, or torch for the one case that is generated and compared on the device)."""
 import numpy as np
 
 U = 2.0 ** -24
+UB = 2.0 ** -8                     # bf16 holds 8 significant bits as fp32 holds 24
 R = 2.0 ** -21
 F32 = np.float32
 SENT = 12352.0                    # sentinel of every destination: exact in fp32 and in bf16
@@ -20,11 +25,22 @@ V_XY = float(F32(0.1))            # the variances as fp32 holds them
 V_WH = float(F32(0.2))
 EPS_NORM = float(F32(1e-10))      # L2Norm's eps as fp32 holds it
 BLOCK = 256
+VEC = {"fp32": 4, "bf16": 8}      # channels of one 16-byte item
+PACK_GRID_CAP = {"fp32": 16384, "bf16": 65536}
+POOL_GRID_CAP = 65536
+
+
+def to_bf16(x):
+    """fp32 values rounded to bf16 (nearest, ties to even), returned as fp32; NaN and +-inf stay what they are"""
+    b = np.ascontiguousarray(x, dtype=F32).view(np.uint32)
+    r = ((b + np.uint32(0x7FFF) + ((b >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xFFFF0000)).view(F32)
+    return np.where(np.isfinite(x), r, x).astype(F32)
 
 
 # ---------------------------------------------------------------- launch rules
 def grid1d(work, block=BLOCK, cap=16384):
-    """detect.hip"""
+    """detect.hip's launches are grid_cap with the cap named at each: 16384 the decode and the fp32 pack, PACK_GRID_CAP["bf16"] the
+    bf16 pack, POOL_GRID_CAP both max pools"""
     return max(1, min(-(-work // block), cap))
 
 
@@ -38,20 +54,20 @@ def _trips(work, grid, block=BLOCK):
     return -(-work // (grid * block))
 
 
-def pack_trips(npix):
-    return _trips(npix, grid1d(npix))
+def pack_trips(npix, kind="fp32"):
+    return _trips(npix, grid1d(npix, BLOCK, PACK_GRID_CAP[kind]))
 
 
 def decode_trips(B, FH, FW):
     return _trips(B * FH * FW, grid1d(B * FH * FW))
 
 
-def pool_items(N, H, W, C):
-    return N * (H // 2) * (W // 2) * (C // 4)
+def pool_items(N, H, W, C, kind="fp32"):
+    return N * (H // 2) * (W // 2) * (C // VEC[kind])
 
 
-def pool_trips(N, H, W, C):
-    return _trips(pool_items(N, H, W, C), grid1d(pool_items(N, H, W, C), BLOCK, 65536))
+def pool_trips(N, H, W, C, kind="fp32"):
+    return _trips(pool_items(N, H, W, C, kind), grid1d(pool_items(N, H, W, C, kind), BLOCK, POOL_GRID_CAP))
 
 
 def datagen_trips(N, S):
@@ -62,12 +78,13 @@ def frames_trips(N, H, W):
     return _trips(N * H * W, grid_cap(N * H * W, BLOCK, 8192))
 
 
-def l2norm_walk(rows, C):
+def l2norm_walk(rows, C, kind="fp32"):
     """l2norm_scale_kernel, one wave per row, four rows per workgroup: (workgroups, waves of the last workgroup that own no row,
-    256-channel trips of lane 0, lanes that take the last of those trips)"""
+    trips of lane 0 - 64 VEC channels each: 256 for fp32, 512 for bf16 -, lanes that take the last of those trips)"""
+    v = VEC[kind]
     wg = -(-rows // 4)
-    t = -(-C // 256)
-    return wg, 4 * wg - rows, t, sum(1 for lane in range(64) if lane * 4 + 256 * (t - 1) < C)
+    t = -(-C // (64 * v))
+    return wg, 4 * wg - rows, t, sum(1 for lane in range(64) if lane * v + 64 * v * (t - 1) < C)
 
 
 # ---------------------------------------------------------------- w2l_s3fd_decode
@@ -212,30 +229,34 @@ def decode_f32(case, conf, loc):
 # (N, H, W, C, x_cs, y_cs)
 POOL_CASES = [(2, 11, 14, 64, 64, 64), (1, 7, 9, 24, 40, 32), (3, 2, 3, 4, 4, 8), (1, 5, 5, 512, 512, 512), (2, 3, 2, 8, 16, 8)]
 POOL_BIG = (1, 2050, 2048, 64, 64, 64)            # 1025 * 1024 * 16 float4 items > 65536 * 256
+# bf16: one item; odd H and W (the dropped row and column hold +inf); two groups, two images, a free NaN group in x, y tight;
+# channels >= C of y keep the sentinel
+POOL_CASES_BF16 = [(1, 2, 2, 8, 8, 8), (1, 3, 5, 8, 8, 8), (2, 4, 6, 16, 24, 16), (1, 4, 4, 8, 8, 16)]
+POOL_BIG_BF16 = (1, 2050, 2048, 128, 128, 128)    # the same cap, so the same 1025 * 1024 * 16 items, of 8 bf16 each
 POOL_VARIANTS = ("second_row_stride_w_plus_1",)
 
 
-def pool_inputs(case, seed):
-    """x [N, H, W, x_cs] fp32: N(0, 1) with a fiftieth +inf and a fiftieth -inf, every third window negative only (a maximum
-    that starts from 0 shows there), the row and the column that an odd H or W drops +inf, channels >= C NaN.  No NaN and no
+def pool_inputs(case, seed, kind="fp32"):
+    """x [N, H, W, x_cs] fp32 (bf16: rounded to it, which makes no value 0): N(0, 1) with a fiftieth +inf and a fiftieth -inf,
+    every third window negative only (a maximum that starts from 0 shows there), the row and the column that an odd H or W drops +inf, channels >= C NaN.  No NaN and no
     zero inside the channels: fmaxf and torch differ on NaN and on windows that mix +0 and -0"""
     N, H, W, C, x_cs, _ = case
     rng = np.random.default_rng(seed)
     x = rng.standard_normal((N, H, W, x_cs)).astype(F32)
     x[x == 0] = F32(1)
-    kind = rng.random((N, H, W, x_cs))
+    what = rng.random((N, H, W, x_cs))
     oy, ox = np.mgrid[0:H, 0:W] // 2
     neg = ((oy + ox) % 3 == 0)[None, :, :, None]
     x = np.where(neg, -np.abs(x), x)
-    x[kind < 0.02] = np.inf
-    x[(kind >= 0.02) & (kind < 0.04)] = -np.inf
+    x[what < 0.02] = np.inf
+    x[(what >= 0.02) & (what < 0.04)] = -np.inf
     x = np.where(neg & (x == np.inf), F32(-np.inf), x).astype(F32)
     if H % 2:
         x[:, H - 1] = np.inf
     if W % 2:
         x[:, :, W - 1] = np.inf
     x[..., C:] = np.nan
-    return x
+    return to_bf16(x) if kind == "bf16" else x
 
 
 def pool_ref(x, C, variant=None):
@@ -279,20 +300,25 @@ def pool_f32(x, C, y_cs):
 L2_SHAPES = [(4, 4, 4), (24, 32, 24), (64, 64, 64), (256, 256, 256), (260, 264, 272), (512, 520, 512), (1024, 1024, 1024)]
 L2_ROWS = (1, 5, 70)
 L2_KINDS = ("normal", "zero", "tiny", "last")
+# bf16: lane 0 alone; exactly one 512-channel trip of all 64 lanes; a second trip that lane 0 takes alone.  Rows 1 and 5: the
+# second workgroup of four rows is partial
+L2_SHAPES_BF16 = [(8, 8, 8), (512, 512, 520), (520, 528, 520)]
+L2_ROWS_BF16 = (1, 5)
 L2_VARIANTS = ("eps_dropped", "eps_in_sqrt", "skip_from_256", "weight_mod_256")
 
 
-def l2norm_cases():
+def l2norm_cases(kind="fp32"):
     """(C, x_cs, y_cs, rows, rot): row r is of kind L2_KINDS[(r + rot) % 4]; one-row launches take every kind in turn"""
-    return [(C, xc, yc, rows, rot) for C, xc, yc in L2_SHAPES for rows in L2_ROWS for rot in (range(4) if rows == 1 else (0,))]
+    shapes, nrows = (L2_SHAPES_BF16, L2_ROWS_BF16) if kind == "bf16" else (L2_SHAPES, L2_ROWS)
+    return [(C, xc, yc, rows, rot) for C, xc, yc in shapes for rows in nrows for rot in (range(4) if rows == 1 else (0,))]
 
 
 def l2norm_kinds(rows, rot):
     return [L2_KINDS[(r + rot) % 4] for r in range(rows)]
 
 
-def l2norm_inputs(C, rows, rot, seed):
-    """x [rows, C], w [C] fp32.  zero: an all-zero row; tiny: N(0, 1) 1e-10, where the eps of the norm is a tenth of it and
+def l2norm_inputs(C, rows, rot, seed, kind="fp32"):
+    """x [rows, C] (bf16: rounded to it), w [C] fp32.  zero: an all-zero row; tiny: N(0, 1) 1e-10, where the eps of the norm is a tenth of it and
     more; last: zero but for the last channel"""
     rng = np.random.default_rng(seed)
     x = (rng.standard_normal((rows, C)) * 2).astype(F32)
@@ -305,7 +331,7 @@ def l2norm_inputs(C, rows, rot, seed):
         elif k == "last":
             x[r] = 0
             x[r, C - 1] = F32(2.5)
-    return x, w
+    return (to_bf16(x) if kind == "bf16" else x), w
 
 
 def l2norm_variant_applies(C, kinds, variant):
@@ -316,8 +342,8 @@ def l2norm_variant_applies(C, kinds, variant):
     return C > 256 and set(kinds) != {"zero"}
 
 
-def K2(C):
-    return 4 * (-(-C // 256)) + 7
+def K2(C, kind="fp32"):
+    return VEC[kind] * (-(-C // (64 * VEC[kind]))) + 7
 
 
 def l2norm_ref(x, w, variant=None):
@@ -336,12 +362,15 @@ def l2norm_ref(x, w, variant=None):
         return x / norm * ww[None, :]
 
 
-def l2norm_bound(ref, C):
+def l2norm_bound(ref, C, kind="fp32"):
     """|y - ref| <= (K2(C) / 2 + 4) U |ref|, K2(C) = 4 ceil(C / 256) + 7.  The sum of squares: one rounding per product, four
     additions per lane and 256-channel trip (contracted into FMAs or not), six xor folds - K2 U relative, with no cancellation
     since every term is >= 0.  The root halves that and adds its own rounding; the eps sum, the division and the product by the
-    weight one each: K2 / 2 + 4.  Where the reference is 0 the bound is 0: x = 0 gives 0 / norm * w = 0 exactly"""
-    return (K2(C) / 2.0 + 4.0) * U * np.abs(ref)
+    weight one each: K2 / 2 + 4.  Where the reference is 0 the bound is 0: x = 0 gives 0 / norm * w = 0 exactly.
+    bf16: the same fp32 arithmetic with eight additions per lane and 512-channel trip, K2 = 8 ceil(C / 512) + 7, gives a value v
+    within b32 = (K2 / 2 + 4) U |ref|; the store rounds it once, |y - v| <= UB |v| <= UB (|ref| + b32)"""
+    b32 = (K2(C, kind) / 2.0 + 4.0) * U * np.abs(ref)
+    return b32 + UB * (np.abs(ref) + b32) if kind == "bf16" else b32
 
 
 def l2norm_f32(x, w):
@@ -371,6 +400,8 @@ def l2norm_f32(x, w):
 PACK_YCS = (3, 4, 5, 8)
 PACK_NPIX = (1, 255, 257)
 PACK_BIG = 16384 * 256 + 3
+PACK_YCS_BF16 = (8, 16)           # at 16 the second 8-channel group must be zeros, not the sentinel
+PACK_BIG_BF16 = PACK_GRID_CAP["bf16"] * 256 + 1
 
 
 def pack_inputs(npix):
@@ -380,7 +411,7 @@ def pack_inputs(npix):
 
 
 def pack_vector_path(y_cs):
-    """s3fd_store: one 16-byte store of (c0, c1, c2, 0), else three scalar stores"""
+    """s3fd_store_px, fp32: one 16-byte store of (c0, c1, c2, 0), else three scalar stores"""
     return y_cs >= 4 and y_cs % 4 == 0
 
 
@@ -390,11 +421,12 @@ def pack_f32(bgr):
     return np.stack([b[:, 2] - 104.0, b[:, 1] - 117.0, b[:, 0] - 123.0], 1).astype(F32)
 
 
-def pack_expected(rgb, y_cs):
-    """the whole destination [npix, y_cs] after the launch on a SENT-filled buffer"""
-    y = np.full((rgb.shape[0], y_cs), SENT, F32)
+def pack_expected(rgb, y_cs, kind="fp32"):
+    """the whole destination [npix, y_cs] after the launch on a SENT-filled buffer; bf16 writes every 8-channel group, the pixel
+    (integers with |v| <= 152: exact) and zeros"""
+    y = np.full((rgb.shape[0], y_cs), F32(0) if kind == "bf16" else SENT, F32)
     y[:, :3] = rgb
-    if pack_vector_path(y_cs):
+    if kind == "fp32" and pack_vector_path(y_cs):
         y[:, 3] = 0
     return y
 

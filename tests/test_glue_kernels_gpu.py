@@ -1,13 +1,14 @@
-"""The fp32 detector glue of csrc/detect.hip (w2l_s3fd_decode, w2l_maxpool2x2, w2l_l2norm_scale, w2l_s3fd_pack) and the input
-packing of csrc/api.hip (w2l_datagen_pack, w2l_datagen_pack_bf16, w2l_frames_to_u8, w2l_nchw_to_nhwc, w2l_nhwc_to_nchw) at
-their edges, through the C ABI.  Cases, float64 references and derived bounds: tests/_glue_cases.py (tests/test_glue_cases_cpu.py
-holds numpy restatements to the same bounds and shows that the inputs tell the named wrong variants apart).  Every destination
+"""The detector glue of csrc/detect.hip (w2l_s3fd_decode and, on the fp32 and the bf16 instantiation of their one body each,
+w2l_maxpool2x2, w2l_l2norm_scale, w2l_s3fd_pack) and the input packing of csrc/api.hip (w2l_datagen_pack,
+w2l_datagen_pack_bf16, w2l_frames_to_u8, w2l_nchw_to_nhwc, w2l_nhwc_to_nchw) at their edges, through the C ABI.
+Cases, float64 references and derived bounds: tests/_glue_cases.py (tests/test_glue_cases_cpu.py holds numpy restatements to the same bounds and shows that the inputs tell the named wrong variants apart).  Every destination
 starts as a sentinel with a sentinel tail behind it, and every input channel that a stride leaves free is NaN: a read or a write
 outside the stated channels shows.  Each kernel also runs once at a size where its grid-stride loop takes a second trip, with
 inputs generated and compared on the device.
 
 Largest observed error as a fraction of its bound (MI355X; the numpy fp32 restatements reach 0.30, 0.19 and 0.16):
     w2l_l2norm_scale                 0.30
+    w2l_l2norm_scale_bf16            0.99  (the bound is all but the half ulp of the one bf16 rounding, which a store can reach)
     w2l_s3fd_decode, coordinates     0.17
     w2l_s3fd_decode, score           0.16
     w2l_s3fd_decode, two-trip case   0.31
@@ -58,6 +59,23 @@ def _read(buf, n, what, head=0):
     assert (h[:head] == sent).all(), "%s: written before the destination" % what
     assert (h[head + n:] == sent).all(), "%s: written past the destination" % what
     return h[head:head + n]
+
+
+# the two storages of the detector glue: kind -> (dtype, suffix of the entry point)
+GLUE = {"fp32": (torch.float32, ""), "bf16": (torch.bfloat16, "_bf16")}
+
+
+def _kind_cases(fp32, bf16):
+    """[(kind, case)] with their ids: the fp32 cases keep the ids they had before the bf16 ones joined them"""
+    return dict(argvalues=[("fp32", c) for c in fp32] + [("bf16", c) for c in bf16],
+                ids=[str(c) for c in fp32] + ["bf16-%s" % (c,) for c in bf16])
+
+
+def _up_as(a, cuda, kind):
+    """fp32 values (already rounded to bf16 where kind is bf16: the conversion is exact) as a device tensor of the kind's dtype"""
+    t = torch.from_numpy(np.ascontiguousarray(a)).to(cuda).to(GLUE[kind][0])
+    assert t.data_ptr() % 16 == 0
+    return t
 
 
 def _frac(err, bound):
@@ -136,34 +154,40 @@ def test_s3fd_decode_second_grid_stride_trip(cuda):
 
 
 # ---------------------------------------------------------------- w2l_maxpool2x2
-@pytest.mark.parametrize("case", G.POOL_CASES, ids=str)
-def test_maxpool2x2_equals_the_four_strided_slices(cuda, case):
+@pytest.mark.parametrize("kind,case", **_kind_cases(G.POOL_CASES, G.POOL_CASES_BF16))
+def test_maxpool2x2_equals_the_four_strided_slices(cuda, kind, case):
     """equal in value to the maximum of the four strided slices: odd H and W drop the last row and column (which hold +inf here),
     +-inf and negative-only windows, channels >= C of x NaN and of y untouched.  NaN and windows that mix +0 and -0 are left
-    out: fmaxf and torch differ there by definition, and post-ReLU activations hold neither"""
+    out: fmaxf and torch differ there by definition, and post-ReLU activations hold neither.  bf16: a maximum of bf16 values is
+    exact, so the comparison is the same equality"""
     lib, s, ptr = _lib3()
+    dtype, sfx = GLUE[kind]
     N, H, W, C_, x_cs, y_cs = case
-    x = G.pool_inputs(case, seed=sum(case))
+    x = G.pool_inputs(case, seed=sum(case), kind=kind)
     ref = G.pool_ref(x, C_)
     n = N * (H // 2) * (W // 2) * y_cs
-    xd, y = _up(x, cuda), _dest(n, cuda)
-    assert lib.w2l_maxpool2x2(s, N, H, W, C_, ptr(xd), x_cs, ptr(y), y_cs) == 0, lib.w2l_last_error()
-    got = _read(y, n, "maxpool %s" % (case,)).reshape(N, H // 2, W // 2, y_cs)
+    xd, y = _up_as(x, cuda, kind), _dest(n, cuda, dtype=dtype)
+    assert getattr(lib, "w2l_maxpool2x2" + sfx)(s, N, H, W, C_, ptr(xd), x_cs, ptr(y), y_cs) == 0, lib.w2l_last_error()
+    got = _read(y, n, "maxpool %s %s" % (kind, case)).reshape(N, H // 2, W // 2, y_cs)
     bad = np.argwhere(got[..., :C_] != ref)
     assert len(bad) == 0, "maxpool %s: %d of %d values differ, first at %s" % (case, len(bad), ref.size, bad[0].tolist())
     assert (got[..., C_:] == G.SENT).all(), "maxpool %s: channels >= C of y were written" % (case,)
 
 
-def test_maxpool2x2_second_grid_stride_trip(cuda):
-    """1025 x 1024 x 16 float4 items, 16384 more than 65536 workgroups of 256 hold; generated and compared on the device"""
+@pytest.mark.parametrize("kind", list(GLUE))
+def test_maxpool2x2_second_grid_stride_trip(cuda, kind):
+    """1025 x 1024 x 16 items of 16 bytes (float4, or 8 bf16), 16384 more than 65536 workgroups of 256 hold; generated and compared
+    on the device"""
     lib, s, ptr = _lib3()
-    N, H, W, C_, x_cs, y_cs = G.POOL_BIG
+    dtype, sfx = GLUE[kind]
+    N, H, W, C_, x_cs, y_cs = G.POOL_BIG_BF16 if kind == "bf16" else G.POOL_BIG
+    assert G.pool_trips(N, H, W, C_, kind) == 2 and G.pool_items(N, H, W, C_, kind) - G.POOL_GRID_CAP * G.BLOCK == 16384
     gen = torch.Generator(device=cuda).manual_seed(6)
-    x = torch.empty((N, H, W, x_cs), device=cuda).normal_(generator=gen)
+    x = torch.empty((N, H, W, x_cs), device=cuda, dtype=dtype).normal_(generator=gen)
     Ho, Wo = H // 2, W // 2
     n = N * Ho * Wo * y_cs
-    y = _dest(n, cuda)
-    assert lib.w2l_maxpool2x2(s, N, H, W, C_, ptr(x), x_cs, ptr(y), y_cs) == 0, lib.w2l_last_error()
+    y = _dest(n, cuda, dtype=dtype)
+    assert getattr(lib, "w2l_maxpool2x2" + sfx)(s, N, H, W, C_, ptr(x), x_cs, ptr(y), y_cs) == 0, lib.w2l_last_error()
     torch.cuda.synchronize()
     ref = torch.maximum(torch.maximum(x[:, 0:2 * Ho:2, 0:2 * Wo:2], x[:, 0:2 * Ho:2, 1:2 * Wo:2]),
                         torch.maximum(x[:, 1:2 * Ho:2, 0:2 * Wo:2], x[:, 1:2 * Ho:2, 1:2 * Wo:2]))
@@ -176,25 +200,28 @@ def test_maxpool2x2_second_grid_stride_trip(cuda):
 
 
 # ---------------------------------------------------------------- w2l_l2norm_scale
-@pytest.mark.parametrize("shape", G.L2_SHAPES, ids=str)
-def test_l2norm_scale_stays_inside_the_float64_bound(cuda, shape):
+@pytest.mark.parametrize("kind,shape", **_kind_cases(G.L2_SHAPES, G.L2_SHAPES_BF16))
+def test_l2norm_scale_stays_inside_the_float64_bound(cuda, kind, shape):
     """x / (sqrt(sum x^2) + 1e-10) w[c] within (K2(C) / 2 + 4) U |ref| for 1, 5 and 70 rows: one and several 256-channel trips,
     the last trip taken by lane 0 alone (C = 260), an all-zero row (exactly 0), a row at 1e-10 where the eps counts, a row whose
-    only value is its last channel; channels >= C of x are NaN, of y untouched"""
+    only value is its last channel; channels >= C of x are NaN, of y untouched.  bf16 (1 and 5 rows, 512-channel trips: lane 0
+    alone at C = 8, one full trip at 512, lane 0 alone in the second at 520): x holds bf16 values, and the bound grows by the one
+    rounding of the stored result (G.l2norm_bound)"""
     lib, s, ptr = _lib3()
+    dtype, sfx = GLUE[kind]
     C_, x_cs, y_cs = shape
     worst = 0.0
-    for _, _, _, rows, rot in [c for c in G.l2norm_cases() if c[0] == C_]:
-        what = "l2norm C=%d x_cs=%d y_cs=%d rows=%d kinds %s" % (C_, x_cs, y_cs, rows, G.l2norm_kinds(rows, rot)[:4])
-        x, w = G.l2norm_inputs(C_, rows, rot, seed=C_ + rows + rot)
+    for _, _, _, rows, rot in [c for c in G.l2norm_cases(kind) if c[0] == C_]:
+        what = "l2norm %s C=%d x_cs=%d y_cs=%d rows=%d kinds %s" % (kind, C_, x_cs, y_cs, rows, G.l2norm_kinds(rows, rot)[:4])
+        x, w = G.l2norm_inputs(C_, rows, rot, seed=C_ + rows + rot, kind=kind)
         ref = G.l2norm_ref(x, w)
-        bound = G.l2norm_bound(ref, C_)
+        bound = G.l2norm_bound(ref, C_, kind)
         xb = np.full((rows, x_cs), np.nan, np.float32)
         xb[:, :C_] = x
         wb = np.full(C_ + 4, np.nan, np.float32)
         wb[:C_] = w
-        xd, wd, y = _up(xb, cuda), _up(wb, cuda), _dest(rows * y_cs, cuda)
-        assert lib.w2l_l2norm_scale(s, rows, C_, ptr(xd), x_cs, ptr(wd), ptr(y), y_cs) == 0, lib.w2l_last_error()
+        xd, wd, y = _up_as(xb, cuda, kind), _up(wb, cuda), _dest(rows * y_cs, cuda, dtype=dtype)
+        assert getattr(lib, "w2l_l2norm_scale" + sfx)(s, rows, C_, ptr(xd), x_cs, ptr(wd), ptr(y), y_cs) == 0, lib.w2l_last_error()
         got = _read(y, rows * y_cs, what).reshape(rows, y_cs)
         assert (got[:, C_:] == G.SENT).all(), "%s: channels >= C of y were written" % what
         got = got[:, :C_].astype(np.float64)
@@ -204,43 +231,50 @@ def test_l2norm_scale_stays_inside_the_float64_bound(cuda, shape):
             what, int(bad.sum()), np.argwhere(bad)[0].tolist(), f)
         assert (got[ref == 0] == 0).all(), "%s: a zero of the reference is not exactly 0" % what
         worst = max(worst, f)
-    print("GLUE_FRACTION l2norm %.4f" % worst)
+    print("GLUE_FRACTION l2norm%s %.4f" % (sfx, worst))
 
 
 # ---------------------------------------------------------------- w2l_s3fd_pack
-@pytest.mark.parametrize("y_cs", G.PACK_YCS)
-def test_s3fd_pack_equals_the_oracle_bit_for_bit(cuda, y_cs):
+@pytest.mark.parametrize("kind,y_cs", **_kind_cases(G.PACK_YCS, G.PACK_YCS_BF16))
+def test_s3fd_pack_equals_the_oracle_bit_for_bit(cuda, kind, y_cs):
     """against s3fd_ref.preprocess on every byte value in every channel: channel 3 is 0 exactly when the 16-byte store is taken
-    (y_cs % 4 == 0), channels >= 4 are untouched; an odd stride needs no aligned base"""
+    (y_cs % 4 == 0), channels >= 4 are untouched; an odd stride needs no aligned base.  bf16: the fp32 pack's values (integers
+    with |v| <= 152: exact) and zeros in every other channel of every 8-channel group, the second group of y_cs = 16 included"""
     lib, s, ptr = _lib3()
+    dtype, sfx = GLUE[kind]
     for npix in G.PACK_NPIX:
-        for off in ((0,) if G.pack_vector_path(y_cs) else (0, 1)):
-            what = "pack npix=%d y_cs=%d base + %d" % (npix, y_cs, off)
+        for off in ((0,) if kind == "bf16" or G.pack_vector_path(y_cs) else (0, 1)):
+            what = "pack %s npix=%d y_cs=%d base + %d" % (kind, npix, y_cs, off)
             bgr = G.pack_inputs(npix)
             rgb = s3fd_ref.preprocess(bgr.reshape(1, 1, npix, 3)).permute(0, 2, 3, 1).reshape(npix, 3).numpy()
-            y = _dest(npix * y_cs, cuda, head=HEAD + off)
-            assert lib.w2l_s3fd_pack(s, npix, ptr(_up(bgr, cuda)), _at(y, HEAD + off), y_cs) == 0, lib.w2l_last_error()
+            y = _dest(npix * y_cs, cuda, dtype=dtype, head=HEAD + off)
+            assert getattr(lib, "w2l_s3fd_pack" + sfx)(s, npix, ptr(_up(bgr, cuda)), _at(y, HEAD + off), y_cs) == 0, lib.w2l_last_error()
             got = _read(y, npix * y_cs, what, head=HEAD + off).reshape(npix, y_cs)
-            _bits_equal(what, got, G.pack_expected(rgb, y_cs))
+            _bits_equal(what, got, G.pack_expected(rgb, y_cs, kind))
 
 
-@pytest.mark.parametrize("y_cs", [4, 3])
-def test_s3fd_pack_second_grid_stride_trip(cuda, y_cs):
+@pytest.mark.parametrize("kind,y_cs", **_kind_cases([4, 3], [8]))
+def test_s3fd_pack_second_grid_stride_trip(cuda, kind, y_cs):
+    """three pixels (bf16: one) more than the launch's cap of workgroups of 256 hold: 16384 for fp32, 65536 for bf16"""
     lib, s, ptr = _lib3()
-    npix = G.PACK_BIG
+    dtype, sfx = GLUE[kind]
+    npix = G.PACK_BIG_BF16 if kind == "bf16" else G.PACK_BIG
+    assert G.pack_trips(npix, kind) == 2
     gen = torch.Generator(device=cuda).manual_seed(7)
     x = torch.randint(0, 256, (npix, 3), dtype=torch.uint8, device=cuda, generator=gen)
-    y = _dest(npix * y_cs, cuda)
-    assert lib.w2l_s3fd_pack(s, npix, ptr(x), ptr(y), y_cs) == 0, lib.w2l_last_error()
+    y = _dest(npix * y_cs, cuda, dtype=dtype)
+    assert getattr(lib, "w2l_s3fd_pack" + sfx)(s, npix, ptr(x), ptr(y), y_cs) == 0, lib.w2l_last_error()
     torch.cuda.synchronize()
-    want = torch.full((npix, y_cs), G.SENT, device=cuda)
+    want = torch.full((npix, y_cs), 0.0 if kind == "bf16" else G.SENT, device=cuda)
     want[:, :3] = x[:, [2, 1, 0]].float() - torch.tensor([104.0, 117.0, 123.0], device=cuda)
-    if G.pack_vector_path(y_cs):
+    if kind == "fp32" and G.pack_vector_path(y_cs):
         want[:, 3] = 0
-    got = y[:npix * y_cs].view(npix, y_cs)
-    nbad = int((got.view(torch.int32) != want.view(torch.int32)).sum())
-    assert nbad == 0, "%d values differ, first at %s" % (nbad, torch.nonzero(got.view(torch.int32) != want.view(torch.int32))[0].tolist())
-    assert bool((y[npix * y_cs:] == G.SENT).all())
+    diff = _as_bits(y[:npix * y_cs].view(npix, y_cs)) != _as_bits(want.to(dtype))
+    nbad = int(diff.sum())
+    assert nbad == 0, "%d values differ, first at %s" % (nbad, torch.nonzero(diff)[0].tolist())
+    assert bool((y[npix * y_cs:].float() == G.SENT).all())
+    del x, y, want, diff
+    torch.cuda.empty_cache()
 
 
 # ---------------------------------------------------------------- w2l_datagen_pack / w2l_datagen_pack_bf16
@@ -393,28 +427,52 @@ def _untouched(buf, what):
     assert bool((buf.float() == sent).all()), "%s: a refused call wrote to its output" % what
 
 
-def test_detector_glue_refuses_bad_arguments_and_writes_nothing(cuda):
+@pytest.mark.parametrize("kind", list(GLUE))
+def test_detector_glue_refuses_bad_arguments_and_writes_nothing(cuda, kind):
+    """bf16: C or a stride that is no multiple of 8, a base pointer 8 bytes off a 16-byte boundary, and shapes that reach 2 GiB
+    in one buffer (the rule of the w2l_convb launches that consume these tensors; fp32 has no such rule) - shapes only, behind
+    small buffers: the refusal comes before any launch"""
     lib, s, ptr = _lib3()
     z = torch.zeros(4096, device=cuda)
     zu = torch.zeros(4096, dtype=torch.uint8, device=cuda)
-    out = _dest(4096, cuda)
-    x, o = ptr(z), ptr(out)
-    _refusals(lib, "w2l_s3fd_decode", {
-        "ncls = 3": (s, 1, 4, 4, 4, x, 4, 3, x, 4, o), "cls_cs < ncls": (s, 1, 4, 4, 4, x, 3, 4, x, 4, o),
-        "cls_cs < ncls = 2": (s, 1, 4, 4, 4, x, 1, 2, x, 4, o), "reg_cs < 4": (s, 1, 4, 4, 4, x, 4, 2, x, 3, o),
-        "no cls": (s, 1, 4, 4, 4, None, 4, 2, x, 4, o), "no reg": (s, 1, 4, 4, 4, x, 4, 2, None, 4, o),
-        "no out": (s, 1, 4, 4, 4, x, 4, 2, x, 4, None)})
-    _refusals(lib, "w2l_maxpool2x2", {
-        "C % 4 != 0": (s, 1, 4, 4, 6, x, 8, o, 8), "H < 2": (s, 1, 1, 4, 8, x, 8, o, 8), "x_cs < C": (s, 1, 4, 4, 8, x, 4, o, 8),
-        "misaligned x": (s, 1, 4, 4, 8, _at(z, 1), 8, o, 8), "misaligned y": (s, 1, 4, 4, 8, x, 8, _at(out, 1), 8)})
-    _refusals(lib, "w2l_l2norm_scale", {
-        "C % 4 != 0": (s, 4, 6, x, 8, x, o, 8), "y_cs < C": (s, 4, 8, x, 8, x, o, 4), "misaligned weight": (s, 4, 8, x, 8, _at(z, 2), o, 8)})
-    _refusals(lib, "w2l_s3fd_pack", {
-        "y_cs < 3": (s, 16, ptr(zu), o, 2), "misaligned y with y_cs % 4 == 0": (s, 16, ptr(zu), _at(out, 1), 4),
-        "misaligned y with y_cs = 8": (s, 16, ptr(zu), _at(out, 2), 8)})
-    _untouched(out, "detector glue")
-    assert lib.w2l_s3fd_pack(s, 16, ptr(zu), _at(out, 1), 5) == 0, "an odd stride needs no alignment"
-    torch.cuda.synchronize()
+    if kind == "fp32":
+        out = _dest(4096, cuda)
+        x, o = ptr(z), ptr(out)
+        _refusals(lib, "w2l_s3fd_decode", {
+            "ncls = 3": (s, 1, 4, 4, 4, x, 4, 3, x, 4, o), "cls_cs < ncls": (s, 1, 4, 4, 4, x, 3, 4, x, 4, o),
+            "cls_cs < ncls = 2": (s, 1, 4, 4, 4, x, 1, 2, x, 4, o), "reg_cs < 4": (s, 1, 4, 4, 4, x, 4, 2, x, 3, o),
+            "no cls": (s, 1, 4, 4, 4, None, 4, 2, x, 4, o), "no reg": (s, 1, 4, 4, 4, x, 4, 2, None, 4, o),
+            "no out": (s, 1, 4, 4, 4, x, 4, 2, x, 4, None)})
+        _refusals(lib, "w2l_maxpool2x2", {
+            "C % 4 != 0": (s, 1, 4, 4, 6, x, 8, o, 8), "H < 2": (s, 1, 1, 4, 8, x, 8, o, 8), "x_cs < C": (s, 1, 4, 4, 8, x, 4, o, 8),
+            "misaligned x": (s, 1, 4, 4, 8, _at(z, 1), 8, o, 8), "misaligned y": (s, 1, 4, 4, 8, x, 8, _at(out, 1), 8)})
+        _refusals(lib, "w2l_l2norm_scale", {
+            "C % 4 != 0": (s, 4, 6, x, 8, x, o, 8), "y_cs < C": (s, 4, 8, x, 8, x, o, 4), "misaligned weight": (s, 4, 8, x, 8, _at(z, 2), o, 8)})
+        _refusals(lib, "w2l_s3fd_pack", {
+            "y_cs < 3": (s, 16, ptr(zu), o, 2), "misaligned y with y_cs % 4 == 0": (s, 16, ptr(zu), _at(out, 1), 4),
+            "misaligned y with y_cs = 8": (s, 16, ptr(zu), _at(out, 2), 8)})
+        _untouched(out, "detector glue")
+        assert lib.w2l_s3fd_pack(s, 16, ptr(zu), _at(out, 1), 5) == 0, "an odd stride needs no alignment"
+        torch.cuda.synchronize()
+        return
+    zb = torch.zeros(4096, dtype=torch.bfloat16, device=cuda)
+    out = _dest(4096, cuda, dtype=torch.bfloat16)
+    x, w, o = ptr(zb), ptr(z), ptr(out)
+    assert _at(zb, 4).value % 16 == 8 and _at(out, 4).value % 16 == 8 and _at(z, 2).value % 16 == 8
+    _refusals(lib, "w2l_maxpool2x2_bf16", {
+        "C % 8 != 0": (s, 1, 4, 4, 12, x, 16, o, 16), "x_cs % 8 != 0": (s, 1, 4, 4, 8, x, 12, o, 8),
+        "y_cs % 8 != 0": (s, 1, 4, 4, 8, x, 8, o, 12), "H < 2": (s, 1, 1, 4, 8, x, 8, o, 8), "x_cs < C": (s, 1, 4, 4, 16, x, 8, o, 16),
+        "x 8 bytes off": (s, 1, 4, 4, 8, _at(zb, 4), 8, o, 8), "y 8 bytes off": (s, 1, 4, 4, 8, x, 8, _at(out, 4), 8),
+        "x of 2 GiB": (s, 1, 32768, 4096, 8, x, 8, o, 8)})
+    _refusals(lib, "w2l_l2norm_scale_bf16", {
+        "C % 8 != 0": (s, 4, 12, x, 16, w, o, 16), "x_cs % 8 != 0": (s, 4, 8, x, 12, w, o, 8), "y_cs % 8 != 0": (s, 4, 8, x, 8, w, o, 12),
+        "y_cs < C": (s, 4, 16, x, 16, w, o, 8), "weight 8 bytes off": (s, 4, 8, x, 8, _at(z, 2), o, 8),
+        "x 8 bytes off": (s, 4, 8, _at(zb, 4), 8, w, o, 8), "y 8 bytes off": (s, 4, 8, x, 8, w, _at(out, 4), 8),
+        "x of 2 GiB": (s, 1 << 27, 8, x, 8, w, o, 8), "y of 2 GiB": (s, 1 << 26, 8, x, 8, w, o, 16)})
+    _refusals(lib, "w2l_s3fd_pack_bf16", {
+        "y_cs < 8": (s, 16, ptr(zu), o, 4), "y_cs % 8 != 0": (s, 16, ptr(zu), o, 12), "y 8 bytes off": (s, 16, ptr(zu), _at(out, 4), 8),
+        "y of 2 GiB": (s, 1 << 27, ptr(zu), o, 8)})
+    _untouched(out, "detector glue, bf16")
 
 
 def test_input_packing_refuses_bad_arguments_and_writes_nothing(cuda):

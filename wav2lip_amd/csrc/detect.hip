@@ -1,11 +1,14 @@
 // S3FD face-detector glue kernels (reference face_detection/detection/sfd/): everything between the 3x3 convolutions, which
 // are the SAME fused conv launches as the generator's (conv_igemm.hip / conv_wino.hip with bias + ReLU, no BatchNorm).
-//   w2l_s3fd_pack       detect.py:57-58 + api.py:62  uint8 BGR frames -> RGB order, minus (104,117,123), fp32 NHWC4
+// The pack, max-pool and L2Norm ops exist for fp32 tensors and, with the suffix _bf16, for the bf16-storage path (channel strides
+// in elements, multiples of 8): one templated kernel body and one set of argument checks per op.
+//   w2l_s3fd_pack       detect.py:57-58 + api.py:62  uint8 BGR frames -> RGB order, minus (104,117,123), fp32 NHWC4; bf16:
+//                       the same integers (exact), zeros in every other channel
 //   w2l_s3fd_pack_rows  the same per frame of an address table: frames of several clips in one batch, read where they lie
 //   w2l_s3fd_pack_rows_scaled[_bf16]  inference.py:202-203 (`cv2.resize(frame, (w // k, h // k))`) fused into the row-table pack:
 //                       the detector reads a frame at reduced size, the reduced frame is never stored
-//   w2l_maxpool2x2      net_s3fd.py:75,79,85,91,97   F.max_pool2d(h, 2, 2)
-//   w2l_l2norm_scale    net_s3fd.py:6-19             x / (sqrt(sum_c x^2) + 1e-10) * weight[c]
+//   w2l_maxpool2x2      net_s3fd.py:75,79,85,91,97   F.max_pool2d(h, 2, 2) (exact in bf16 too)
+//   w2l_l2norm_scale    net_s3fd.py:6-19             x / (sqrt(sum_c x^2) + 1e-10) * weight[c]; bf16: fp32 arithmetic, one rounding
 //   w2l_s3fd_decode     net_s3fd.py:123-126 (max-out background), detect.py:66-84 (softmax, priors, decode)
 //   w2l_s3fd_nms        sfd_detector.py:39-45 gate + bbox.py:44-64 greedy NMS, bit-exact keep list
 //   w2l_s3fd_first_rect sfd_detector.py:45 + api.py:61-77  first kept box above 0.5 -> int rect, one row per image
@@ -17,38 +20,71 @@
 //                       smoothing and "no face" of many clips in one launch
 //   w2l_face_boxes_stream  the same finish for LIVE streams, tick by tick: a box is written once the T - 1 frames after it are there
 //   w2l_face_boxes_runs, w2l_face_boxes_stream_runs  the two finishes with frames without a face passed through (opt-in)
-// All HBM-bound, NHWC, float4 where the channel count allows.
+// All HBM-bound, NHWC, 16-byte vectors where the channel count allows.
 #include "w2l_common.h"
+#include "w2l_storage.h"
 #include "resize_px.h"
 
 namespace w2l {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+// ---- the glue between the convolutions: one kernel body per op, S = StF32 / StBf16 (w2l_storage.h) the storage of its tensors.
+// What the detector's two storages do NOT share is stated here, once:
+template <class S>
+struct GlueSt;
+template <>
+struct GlueSt<StF32> {
+    static constexpr int kPackGridCap = 16384;
+    static constexpr bool kConvbLimit = false;
+    // any channel stride from 3 on; only the 16-byte store of a stride that is a multiple of 4 needs an aligned base
+    static bool pack_ok(const void* y, int y_cs) { return y_cs >= 3 && ((y_cs & 3) != 0 || (reinterpret_cast<uintptr_t>(y) & 15) == 0); }
+    static constexpr const char* kPackRule = "y_cs >= 3, and y 16-byte aligned where y_cs % 4 == 0";
+};
+template <>
+struct GlueSt<StBf16> {
+    static constexpr int kPackGridCap = 65536;
+    // the tensors feed w2l_convb launches, which address a buffer with 32-bit byte offsets: no buffer of 2 GiB or more
+    static constexpr bool kConvbLimit = true;
+    static bool pack_ok(const void* y, int y_cs) { return y_cs >= 8 && (y_cs & 7) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0; }
+    static constexpr const char* kPackRule = "y_cs % 8 == 0 and y 16-byte aligned";
+};
 
-__device__ __forceinline__ void s3fd_store(float* o, int y_cs, float c0, float c1, float c2) {
+// A packed pixel leaves through one of these.  fp32: one 16-byte store of (c0, c1, c2, 0) where the stride is a multiple of 4 -
+// channels >= 4 stay as they are - else three scalar stores.  bf16 (y_cs % 8 == 0): every 8-channel group is written, group 0
+// with the pixel (integers with |v| <= 152: exact), the rest with zeros.
+__device__ __forceinline__ void s3fd_store_px(float* o, int y_cs, float c0, float c1, float c2) {
     if (y_cs >= 4 && (y_cs & 3) == 0) *reinterpret_cast<f32x4*>(o) = f32x4{c0, c1, c2, 0.f};
     else { o[0] = c0; o[1] = c1; o[2] = c2; }
 }
+__device__ __forceinline__ void s3fd_store_px(__bf16* o, int y_cs, float c0, float c1, float c2) {
+    bf16x8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (__bf16)0.f;
+    for (int g = 1; g < (y_cs >> 3); ++g) *reinterpret_cast<bf16x8*>(o + g * 8) = v;
+    v[0] = (__bf16)c0; v[1] = (__bf16)c1; v[2] = (__bf16)c2;
+    *reinterpret_cast<bf16x8*>(o) = v;
+}
 
-__global__ void s3fd_pack_kernel(long long npix, const uint8_t* __restrict__ x, float* __restrict__ y, int y_cs,
+// one thread per pixel, all its channel groups (the detector packs at y_cs = 4 and 8: one group)
+template <class S>
+__global__ void s3fd_pack_kernel(long long npix, const uint8_t* __restrict__ x, typename S::elem* __restrict__ y, int y_cs,
                                  float m0, float m1, float m2) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x) {
         float c0, c1, c2;
         s3fd_pixel(x + i * 3, m0, m1, m2, c0, c1, c2);
-        s3fd_store(y + i * y_cs, y_cs, c0, c1, c2);
+        s3fd_store_px(y + i * y_cs, y_cs, c0, c1, c2);
     }
 }
 
 // The row-table form: blockIdx.y is the image, its frame lies at frames[b].  A thread owns four consecutive pixels (12 bytes =
 // three dwords of an aligned frame); HBM-bound byte traffic, no LDS.
-__global__ void s3fd_pack_rows_kernel(int npix, const uint64_t* __restrict__ frames, float* __restrict__ y, int y_cs, float m0,
-                                      float m1, float m2) {
+template <class S>
+__global__ void s3fd_pack_rows_kernel(int npix, const uint64_t* __restrict__ frames, typename S::elem* __restrict__ y, int y_cs,
+                                      float m0, float m1, float m2) {
     const int b = blockIdx.y;
     const uint64_t addr = frames[b];
     const uint8_t* x = reinterpret_cast<const uint8_t*>(addr);
     const bool dwords = (addr & 3) == 0;
-    float* yb = y + (long long)b * npix * y_cs;
+    typename S::elem* yb = y + (long long)b * npix * y_cs;
     const int ngroups = (npix + 3) >> 2;
     for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += gridDim.x * blockDim.x) {
         const int i0 = g << 2, n = min(4, npix - i0);
@@ -57,7 +93,7 @@ __global__ void s3fd_pack_rows_kernel(int npix, const uint64_t* __restrict__ fra
         for (int k = 0; k < n; ++k) {
             float c0, c1, c2;
             s3fd_pixel(px + 3 * k, m0, m1, m2, c0, c1, c2);
-            s3fd_store(yb + (long long)(i0 + k) * y_cs, y_cs, c0, c1, c2);
+            s3fd_store_px(yb + (long long)(i0 + k) * y_cs, y_cs, c0, c1, c2);
         }
     }
 }
@@ -85,18 +121,6 @@ __device__ __forceinline__ void load_span(const uint8_t* __restrict__ p, uint8_t
 #pragma unroll
         for (int k = 0; k < N; ++k) out[k] = p[k];
     }
-}
-
-__device__ __forceinline__ void s3fd_store_px(float* o, int, float c0, float c1, float c2) {
-    *reinterpret_cast<f32x4*>(o) = f32x4{c0, c1, c2, 0.f};              // y_cs % 4 == 0: channels >= 4 stay as they are (s3fd_store)
-}
-__device__ __forceinline__ void s3fd_store_px(__bf16* o, int y_cs, float c0, float c1, float c2) {
-    bf16x8 v;                                                           // every 8-channel group, as s3fd_pack_rows_bf16_kernel
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (__bf16)0.f;
-    for (int g = 1; g < (y_cs >> 3); ++g) *reinterpret_cast<bf16x8*>(o + g * 8) = v;
-    v[0] = (__bf16)c0; v[1] = (__bf16)c1; v[2] = (__bf16)c2;          // integers with |v| <= 152: exact
-    *reinterpret_cast<bf16x8*>(o) = v;
 }
 
 template <typename T>
@@ -153,51 +177,68 @@ __global__ __launch_bounds__(256) void s3fd_pack_rows_scaled_kernel(int Hs, int 
     }
 }
 
-// one thread per (output pixel, float4 channel group)
-__global__ void maxpool2x2_kernel(int N, int H, int W, int C4, const float* __restrict__ x, int x_cs, float* __restrict__ y,
-                                  int y_cs) {
+// one thread per (output pixel, 16-byte channel group); a maximum of bf16 values is exact
+template <class S>
+__global__ void maxpool2x2_kernel(int N, int H, int W, int CG, const typename S::elem* __restrict__ x, int x_cs,
+                                  typename S::elem* __restrict__ y, int y_cs) {
+    constexpr int VEC = S::VEC;
     const int Ho = H / 2, Wo = W / 2;
-    const long long total = (long long)N * Ho * Wo * C4;
+    const long long total = (long long)N * Ho * Wo * CG;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c4 = (int)(i % C4);
-        long long pix = i / C4;
+        const int cg = (int)(i % CG);
+        long long pix = i / CG;
         const int ox = (int)(pix % Wo);
         pix /= Wo;
         const int oy = (int)(pix % Ho);
         const int n = (int)(pix / Ho);
-        const float* p = x + (((long long)n * H + 2 * oy) * W + 2 * ox) * x_cs + c4 * 4;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(p + x_cs);
-        const f32x4 c = *reinterpret_cast<const f32x4*>(p + (long long)W * x_cs);
-        const f32x4 d = *reinterpret_cast<const f32x4*>(p + (long long)W * x_cs + x_cs);
-        f32x4 o;
+        const typename S::elem* p = x + (((long long)n * H + 2 * oy) * W + 2 * ox) * x_cs + cg * VEC;
+        float a[VEC], b[VEC], c[VEC], d[VEC], o[VEC];
+        S::ld(p, a);
+        S::ld(p + x_cs, b);
+        S::ld(p + (long long)W * x_cs, c);
+        S::ld(p + (long long)W * x_cs + x_cs, d);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = fmaxf(fmaxf(a[e], b[e]), fmaxf(c[e], d[e]));
-        *reinterpret_cast<f32x4*>(y + (((long long)n * Ho + oy) * Wo + ox) * y_cs + c4 * 4) = o;
+        for (int e = 0; e < VEC; ++e) o[e] = fmaxf(fmaxf(a[e], b[e]), fmaxf(c[e], d[e]));
+        S::st(y + (((long long)n * Ho + oy) * Wo + ox) * y_cs + cg * VEC, o);
     }
 }
 
-// one wave per pixel: norm over channels, then scale by weight[c]
-__global__ void l2norm_scale_kernel(long long rows, int C, const float* __restrict__ x, int x_cs,
-                                    const float* __restrict__ w, float* __restrict__ y, int y_cs) {
+// A lane's sum of squares grows by one vector.  The two storages add in different orders - fp32 the four products first, bf16 the
+// eight one after the other - and each keeps its own: the detector's boxes do not move by a bit.
+__device__ __forceinline__ float add_squares(float s, const float (&v)[4]) {
+    return s + (v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
+}
+__device__ __forceinline__ float add_squares(float s, const float (&v)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s += v[e] * v[e];
+    return s;
+}
+
+// one wave per pixel, a lane takes 16 bytes of every 64 * VEC channels: fp32 sum of squares over the channels, then
+// x / norm * weight[c] in fp32 (bf16: rounded once on the store)
+template <class S>
+__global__ void l2norm_scale_kernel(long long rows, int C, const typename S::elem* __restrict__ x, int x_cs,
+                                    const float* __restrict__ w, typename S::elem* __restrict__ y, int y_cs) {
+    constexpr int VEC = S::VEC;
     const long long row = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
-    const float* p = x + row * x_cs;
+    const typename S::elem* p = x + row * x_cs;
     float s = 0.f;
-    for (int c = lane * 4; c < C; c += 256) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(p + c);
-        s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+    for (int c = lane * VEC; c < C; c += 64 * VEC) {
+        float v[VEC];
+        S::ld(p + c, v);
+        s = add_squares(s, v);
     }
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     const float norm = sqrtf(s) + 1e-10f;
-    for (int c = lane * 4; c < C; c += 256) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(p + c);
-        const f32x4 ww = *reinterpret_cast<const f32x4*>(w + c);
-        f32x4 o;
+    for (int c = lane * VEC; c < C; c += 64 * VEC) {
+        float v[VEC], ww[VEC], o[VEC];
+        S::ld(p + c, v);
+        ldv<VEC>(w + c, ww);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = v[e] / norm * ww[e];
-        *reinterpret_cast<f32x4*>(y + row * y_cs + c) = o;
+        for (int e = 0; e < VEC; ++e) o[e] = v[e] / norm * ww[e];
+        S::st(y + row * y_cs + c, o);
     }
 }
 
@@ -205,31 +246,8 @@ __global__ void l2norm_scale_kernel(long long rows, int C, const float* __restri
 __global__ void s3fd_decode_kernel(int B, int FH, int FW, int stride, const float* __restrict__ cls, int cls_cs, int ncls,
                                    const float* __restrict__ reg, int reg_cs, float* __restrict__ out) {
     const long long total = (long long)B * FH * FW;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int wx = (int)(i % FW);
-        const int hy = (int)((i / FW) % FH);
-        const float* c = cls + i * cls_cs;
-        float bg, fg;
-        if (ncls == 4) { bg = fmaxf(fmaxf(c[0], c[1]), c[2]); fg = c[3]; }   // max-out background label
-        else { bg = c[0]; fg = c[1]; }
-        // F.softmax over the two classes
-        const float mx = fmaxf(bg, fg);
-        const float eb = expf(bg - mx), ef = expf(fg - mx);
-        const float score = ef / (eb + ef);
-        const float* l = reg + i * reg_cs;
-        const float axc = (float)stride / 2.f + (float)wx * (float)stride;
-        const float ayc = (float)stride / 2.f + (float)hy * (float)stride;
-        const float pw = (float)(stride * 4);
-        // decode (bbox.py:91-108), variances (0.1, 0.2)
-        float cx = axc + l[0] * 0.1f * pw;
-        float cy = ayc + l[1] * 0.1f * pw;
-        const float bw = pw * expf(l[2] * 0.2f);
-        const float bh = pw * expf(l[3] * 0.2f);
-        cx -= bw / 2.f;
-        cy -= bh / 2.f;
-        float* o = out + i * 5;
-        o[0] = cx; o[1] = cy; o[2] = bw + cx; o[3] = bh + cy; o[4] = score;
-    }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x)
+        s3fd_decode_px(cls + i * cls_cs, ncls, reg + i * reg_cs, stride, (int)(i % FW), (int)((i / FW) % FH), out + i * 5);
 }
 
 
@@ -805,13 +823,97 @@ __global__ __launch_bounds__(64) void face_boxes_stream_runs_kernel(const BoxStr
     }
 }
 
-constexpr int kPackScaledGridCap = 1024;      // workgroups per image of the reduced-resolution pack, as its row-table siblings
+constexpr int kPackRowsGridCap = 1024;        // workgroups per image of the row-table packs, full size and reduced
 
-static inline int grid1d(long long work, int block, int cap = 16384) {
-    long long g = (work + block - 1) / block;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
+template <class S>
+static bool convb_fits(long long elems) {
+    return !GlueSt<S>::kConvbLimit || elems * (long long)sizeof(typename S::elem) < (1ll << 31);
+}
+static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+}
+
+// ---- one set of checks and one launch per glue op; the two entry points of an op forward here, S::suffix names the one called
+template <class S>
+static int s3fd_pack_t(hipStream_t s, long long npix, const uint8_t* bgr, typename S::elem* y, int y_cs) {
+    W2L_REQUIRE(bgr && y && npix >= 1, "s3fd_pack%s: bad arguments", S::suffix);
+    W2L_REQUIRE(GlueSt<S>::pack_ok(y, y_cs), "s3fd_pack%s: y_cs=%d: %s", S::suffix, y_cs, GlueSt<S>::kPackRule);
+    W2L_REQUIRE(convb_fits<S>(npix * y_cs), "s3fd_pack%s: buffer larger than 2 GiB: split the batch", S::suffix);
+    hipLaunchKernelGGL(s3fd_pack_kernel<S>, dim3(grid_cap(npix, 256, GlueSt<S>::kPackGridCap)), dim3(256), 0, s, npix, bgr, y, y_cs,
+                       104.f, 117.f, 123.f);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+// the checks every row-table pack shares; the frame addresses live in device memory and are the caller's
+static int pack_rows_check(const char* name, const char* suffix, int B, const void* frames, const void* y) {
+    W2L_REQUIRE(frames && y, "%s%s: NULL argument", name, suffix);
+    W2L_REQUIRE(B >= 1 && B <= 65535, "%s%s: B=%d outside 1..65535", name, suffix, B);
+    W2L_REQUIRE((reinterpret_cast<uintptr_t>(frames) & 7) == 0, "%s%s: the address table must be 8-byte aligned", name, suffix);
+    return W2L_OK;
+}
+
+template <class S>
+static int s3fd_pack_rows_t(hipStream_t s, int B, int H, int W, const uint64_t* frames, typename S::elem* y, int y_cs) {
+    if (int e = pack_rows_check("s3fd_pack_rows", S::suffix, B, frames, y)) return e;
+    W2L_REQUIRE(H >= 1 && W >= 1 && (long long)H * W <= (1ll << 29), "s3fd_pack_rows%s: H, W >= 1 and H * W <= 2^29", S::suffix);
+    W2L_REQUIRE(GlueSt<S>::pack_ok(y, y_cs), "s3fd_pack_rows%s: y_cs=%d: %s", S::suffix, y_cs, GlueSt<S>::kPackRule);
+    W2L_REQUIRE(convb_fits<S>((long long)B * H * W * y_cs), "s3fd_pack_rows%s: buffer larger than 2 GiB: split the batch", S::suffix);
+    const int npix = H * W;
+    hipLaunchKernelGGL(s3fd_pack_rows_kernel<S>, dim3(grid_cap((npix + 3) / 4, 256, kPackRowsGridCap), B), dim3(256), 0, s, npix,
+                       frames, y, y_cs, 104.f, 117.f, 123.f);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+template <class S>
+static int s3fd_pack_rows_scaled_t(hipStream_t s, int B, int Hs, int Ws, int Hd, int Wd, const uint64_t* frames, typename S::elem* y,
+                                   int y_cs) {
+    constexpr const char* name = "s3fd_pack_rows_scaled";
+    if (int e = pack_rows_check(name, S::suffix, B, frames, y)) return e;
+    W2L_REQUIRE(Hs >= 1 && Ws >= 1 && Hd >= 1 && Wd >= 1, "%s%s: sizes %d x %d -> %d x %d must all be at least 1", name, S::suffix, Hs,
+                Ws, Hd, Wd);
+    W2L_REQUIRE((long long)Hs * Ws <= (1ll << 29) && (long long)Hd * Wd <= (1ll << 29), "%s%s: Hs * Ws and Hd * Wd <= 2^29", name,
+                S::suffix);
+    W2L_REQUIRE(aligned16(y), "%s%s: y must be 16-byte aligned", name, S::suffix);
+    W2L_REQUIRE(y_cs >= S::VEC && y_cs % S::VEC == 0, "%s%s: y_cs=%d must be a multiple of %d (16-byte pixel stores)", name, S::suffix,
+                y_cs, S::VEC);
+    W2L_REQUIRE(convb_fits<S>((long long)B * Hd * Wd * y_cs), "%s%s: buffer larger than 2 GiB: split the batch", name, S::suffix);
+    hipLaunchKernelGGL(s3fd_pack_rows_scaled_kernel<typename S::elem>,
+                       dim3(grid_cap((long long)Hd * ((Wd + 3) / 4), 256, kPackRowsGridCap), B), dim3(256), 0, s, Hs, Ws, Hd, Wd, frames,
+                       y, y_cs, 104.f, 117.f, 123.f);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+template <class S>
+static int maxpool2x2_t(hipStream_t s, int N, int H, int W, int C, const typename S::elem* x, int x_cs, typename S::elem* y, int y_cs) {
+    constexpr int VEC = S::VEC;
+    W2L_REQUIRE(x && y && N >= 1 && H >= 2 && W >= 2 && C >= VEC && C % VEC == 0, "maxpool2x2%s: bad arguments (C %% %d == 0, H, W >= 2)",
+                S::suffix, VEC);
+    W2L_REQUIRE(x_cs % VEC == 0 && y_cs % VEC == 0 && x_cs >= C && y_cs >= C && aligned16(x, y),
+                "maxpool2x2%s: 16-byte aligned tensors with channel strides that are multiples of %d", S::suffix, VEC);
+    W2L_REQUIRE(convb_fits<S>((long long)N * H * W * x_cs), "maxpool2x2%s: buffer larger than 2 GiB: split the batch", S::suffix);
+    const long long total = (long long)N * (H / 2) * (W / 2) * (C / VEC);
+    hipLaunchKernelGGL(maxpool2x2_kernel<S>, dim3(grid_cap(total, 256, 65536)), dim3(256), 0, s, N, H, W, C / VEC, x, x_cs, y, y_cs);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+template <class S>
+static int l2norm_scale_t(hipStream_t s, long long rows, int C, const typename S::elem* x, int x_cs, const float* weight,
+                          typename S::elem* y, int y_cs) {
+    constexpr int VEC = S::VEC;
+    W2L_REQUIRE(x && y && weight && rows >= 1 && C >= VEC && C % VEC == 0, "l2norm_scale%s: bad arguments (C %% %d == 0)", S::suffix, VEC);
+    W2L_REQUIRE(x_cs % VEC == 0 && y_cs % VEC == 0 && x_cs >= C && y_cs >= C && aligned16(x, y, weight),
+                "l2norm_scale%s: 16-byte aligned tensors with channel strides that are multiples of %d", S::suffix, VEC);
+    W2L_REQUIRE(convb_fits<S>(rows * x_cs) && convb_fits<S>(rows * y_cs), "l2norm_scale%s: buffer larger than 2 GiB: split the batch",
+                S::suffix);
+    const long long blocks = (rows + 3) / 4;
+    W2L_REQUIRE(blocks < (1ll << 31), "l2norm_scale%s: too many rows", S::suffix);
+    hipLaunchKernelGGL(l2norm_scale_kernel<S>, dim3((unsigned)blocks), dim3(256), 0, s, rows, C, x, x_cs, weight, y, y_cs);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
 }
 
 }  // namespace w2l
@@ -820,81 +922,43 @@ using namespace w2l;
 
 extern "C" {
 
+static hipStream_t hs(void* stream) { return static_cast<hipStream_t>(stream); }
+static __bf16* bf(void* p) { return static_cast<__bf16*>(p); }
+static const __bf16* bf(const void* p) { return static_cast<const __bf16*>(p); }
+
 int w2l_s3fd_pack(void* stream, long long npix, const uint8_t* bgr, float* y, int y_cs) {
-    W2L_REQUIRE(bgr && y && npix >= 1 && y_cs >= 3, "bad s3fd_pack arguments");
-    W2L_REQUIRE((y_cs & 3) != 0 || (reinterpret_cast<uintptr_t>(y) & 15) == 0, "s3fd_pack: y must be 16-byte aligned");
-    hipLaunchKernelGGL(s3fd_pack_kernel, dim3(grid1d(npix, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), npix, bgr, y,
-                       y_cs, 104.f, 117.f, 123.f);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
+    return s3fd_pack_t<StF32>(hs(stream), npix, bgr, y, y_cs);
+}
+int w2l_s3fd_pack_bf16(void* stream, long long npix, const uint8_t* bgr, void* y, int y_cs) {
+    return s3fd_pack_t<StBf16>(hs(stream), npix, bgr, bf(y), y_cs);
 }
 
 int w2l_s3fd_pack_rows(void* stream, int B, int H, int W, const uint64_t* frames, float* y, int y_cs) {
-    W2L_REQUIRE(frames && y && B >= 1 && H >= 1 && W >= 1 && y_cs >= 3, "bad s3fd_pack_rows arguments");
-    W2L_REQUIRE(B <= 65535 && (long long)H * W <= (1ll << 29), "s3fd_pack_rows: B <= 65535 and H * W <= 2^29");
-    W2L_REQUIRE((reinterpret_cast<uintptr_t>(frames) & 7) == 0, "s3fd_pack_rows: the address table must be 8-byte aligned");
-    W2L_REQUIRE((y_cs & 3) != 0 || (reinterpret_cast<uintptr_t>(y) & 15) == 0, "s3fd_pack_rows: y must be 16-byte aligned");
-    const int npix = H * W;
-    hipLaunchKernelGGL(s3fd_pack_rows_kernel, dim3(grid1d((npix + 3) / 4, 256, 1024), B), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), npix, frames, y, y_cs, 104.f, 117.f, 123.f);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
+    return s3fd_pack_rows_t<StF32>(hs(stream), B, H, W, frames, y, y_cs);
 }
-
-// the checks the two reduced-resolution packs share; the frame addresses live in device memory and are the caller's
-static int pack_rows_scaled_check(const char* name, int B, int Hs, int Ws, int Hd, int Wd, const void* frames, const void* y) {
-    W2L_REQUIRE(frames && y, "%s: NULL argument", name);
-    W2L_REQUIRE(B >= 1 && B <= 65535, "%s: B=%d outside 1..65535", name, B);
-    W2L_REQUIRE(Hs >= 1 && Ws >= 1 && Hd >= 1 && Wd >= 1, "%s: sizes %d x %d -> %d x %d must all be at least 1", name, Hs, Ws, Hd, Wd);
-    W2L_REQUIRE((long long)Hs * Ws <= (1ll << 29) && (long long)Hd * Wd <= (1ll << 29), "%s: Hs * Ws and Hd * Wd <= 2^29", name);
-    W2L_REQUIRE((reinterpret_cast<uintptr_t>(frames) & 7) == 0, "%s: the address table must be 8-byte aligned", name);
-    W2L_REQUIRE((reinterpret_cast<uintptr_t>(y) & 15) == 0, "%s: y must be 16-byte aligned", name);
-    return W2L_OK;
+int w2l_s3fd_pack_rows_bf16(void* stream, int B, int H, int W, const uint64_t* frames, void* y, int y_cs) {
+    return s3fd_pack_rows_t<StBf16>(hs(stream), B, H, W, frames, bf(y), y_cs);
 }
 
 int w2l_s3fd_pack_rows_scaled(void* stream, int B, int Hs, int Ws, int Hd, int Wd, const uint64_t* frames, float* y, int y_cs) {
-    if (int e = pack_rows_scaled_check("s3fd_pack_rows_scaled", B, Hs, Ws, Hd, Wd, frames, y)) return e;
-    W2L_REQUIRE(y_cs >= 4 && (y_cs & 3) == 0, "s3fd_pack_rows_scaled: y_cs=%d must be a multiple of 4 (16-byte pixel stores)", y_cs);
-    hipLaunchKernelGGL(s3fd_pack_rows_scaled_kernel<float>, dim3(grid1d((long long)Hd * ((Wd + 3) / 4), 256, kPackScaledGridCap), B),
-                       dim3(256), 0, static_cast<hipStream_t>(stream), Hs, Ws, Hd, Wd, frames, y, y_cs, 104.f, 117.f, 123.f);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
+    return s3fd_pack_rows_scaled_t<StF32>(hs(stream), B, Hs, Ws, Hd, Wd, frames, y, y_cs);
 }
-
 int w2l_s3fd_pack_rows_scaled_bf16(void* stream, int B, int Hs, int Ws, int Hd, int Wd, const uint64_t* frames, void* y, int y_cs) {
-    if (int e = pack_rows_scaled_check("s3fd_pack_rows_scaled_bf16", B, Hs, Ws, Hd, Wd, frames, y)) return e;
-    W2L_REQUIRE(y_cs >= 8 && (y_cs & 7) == 0, "s3fd_pack_rows_scaled_bf16: y_cs=%d must be a multiple of 8 (16-byte pixel stores)", y_cs);
-    W2L_REQUIRE((long long)B * Hd * Wd * y_cs * 2 < (1ll << 31), "s3fd_pack_rows_scaled_bf16: buffer larger than 2 GiB: split the batch");
-    hipLaunchKernelGGL(s3fd_pack_rows_scaled_kernel<__bf16>, dim3(grid1d((long long)Hd * ((Wd + 3) / 4), 256, kPackScaledGridCap), B),
-                       dim3(256), 0, static_cast<hipStream_t>(stream), Hs, Ws, Hd, Wd, frames, static_cast<__bf16*>(y), y_cs, 104.f,
-                       117.f, 123.f);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
+    return s3fd_pack_rows_scaled_t<StBf16>(hs(stream), B, Hs, Ws, Hd, Wd, frames, bf(y), y_cs);
 }
 
 int w2l_maxpool2x2(void* stream, int N, int H, int W, int C, const float* x, int x_cs, float* y, int y_cs) {
-    W2L_REQUIRE(x && y && N >= 1 && H >= 2 && W >= 2 && C >= 4 && (C & 3) == 0, "bad maxpool2x2 arguments (C %% 4 == 0, H, W >= 2)");
-    W2L_REQUIRE((x_cs & 3) == 0 && (y_cs & 3) == 0 && x_cs >= C && y_cs >= C &&
-                    ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0,
-                "maxpool2x2: 16-byte aligned tensors with channel strides that are multiples of 4");
-    const long long total = (long long)N * (H / 2) * (W / 2) * (C / 4);
-    hipLaunchKernelGGL(maxpool2x2_kernel, dim3(grid1d(total, 256, 65536)), dim3(256), 0, static_cast<hipStream_t>(stream), N, H,
-                       W, C / 4, x, x_cs, y, y_cs);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
+    return maxpool2x2_t<StF32>(hs(stream), N, H, W, C, x, x_cs, y, y_cs);
+}
+int w2l_maxpool2x2_bf16(void* stream, int N, int H, int W, int C, const void* x, int x_cs, void* y, int y_cs) {
+    return maxpool2x2_t<StBf16>(hs(stream), N, H, W, C, bf(x), x_cs, bf(y), y_cs);
 }
 
 int w2l_l2norm_scale(void* stream, long long rows, int C, const float* x, int x_cs, const float* weight, float* y, int y_cs) {
-    W2L_REQUIRE(x && y && weight && rows >= 1 && C >= 4 && (C & 3) == 0, "bad l2norm_scale arguments");
-    W2L_REQUIRE((x_cs & 3) == 0 && (y_cs & 3) == 0 && x_cs >= C && y_cs >= C &&
-                    ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(weight)) & 15) == 0,
-                "l2norm_scale: 16-byte aligned tensors with channel strides that are multiples of 4");
-    const long long blocks = (rows + 3) / 4;
-    W2L_REQUIRE(blocks < (1ll << 31), "too many rows");
-    hipLaunchKernelGGL(l2norm_scale_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), rows, C, x,
-                       x_cs, weight, y, y_cs);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
+    return l2norm_scale_t<StF32>(hs(stream), rows, C, x, x_cs, weight, y, y_cs);
+}
+int w2l_l2norm_scale_bf16(void* stream, long long rows, int C, const void* x, int x_cs, const float* weight, void* y, int y_cs) {
+    return l2norm_scale_t<StBf16>(hs(stream), rows, C, bf(x), x_cs, weight, bf(y), y_cs);
 }
 
 int w2l_s3fd_decode(void* stream, int B, int FH, int FW, int stride, const float* cls, int cls_cs, int ncls, const float* reg,
@@ -902,7 +966,7 @@ int w2l_s3fd_decode(void* stream, int B, int FH, int FW, int stride, const float
     W2L_REQUIRE(cls && reg && out && B >= 1 && FH >= 1 && FW >= 1 && stride >= 1, "bad s3fd_decode arguments");
     W2L_REQUIRE((ncls == 2 || ncls == 4) && cls_cs >= ncls && reg_cs >= 4, "s3fd_decode: ncls must be 2 or 4");
     const long long total = (long long)B * FH * FW;
-    hipLaunchKernelGGL(s3fd_decode_kernel, dim3(grid1d(total, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, FH, FW,
+    hipLaunchKernelGGL(s3fd_decode_kernel, dim3(grid_cap(total, 256, 16384)), dim3(256), 0, static_cast<hipStream_t>(stream), B, FH, FW,
                        stride, cls, cls_cs, ncls, reg, reg_cs, out);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;

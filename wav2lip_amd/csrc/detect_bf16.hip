@@ -1,16 +1,10 @@
-// The S3FD face detector's glue on the opt-in bf16-storage path (face_detection/s3fd.py _GraphB): the ops between the backbone
-// convolutions, which are w2l_convb launches (bias as the fp32 shift, ReLU), and the fused detection head.
-//   w2l_s3fd_pack_bf16       detect.py:57-58 + api.py:62  uint8 BGR -> RGB minus (104,117,123), bf16 NHWC (integers: exact)
-//   w2l_s3fd_pack_rows_bf16  the same per frame of an address table (frames of several clips in one batch, read in place)
-//   w2l_maxpool2x2_bf16      net_s3fd.py:75,79,85,91,97   F.max_pool2d(h, 2, 2) on bf16 (max is exact)
-//   w2l_l2norm_scale_bf16    net_s3fd.py:6-19             sum of squares in fp32, one rounding on the store
+// The S3FD face detector's fused detection head on the opt-in bf16-storage path (face_detection/s3fd.py), and nothing else: the
+// glue between the backbone convolutions - pack, max pool, L2Norm - is one templated body per op for fp32 and bf16 in detect.hip.
 //   w2l_s3fd_headb_*         net_s3fd.py:99-120 (conf + loc convolutions of one level) + net_s3fd.py:123-126 + detect.py:66-84:
 //                            one 3x3 contraction on v_mfma_f32_16x16x32_bf16 and the decode from the fp32 accumulators
 // Layout: NHWC bf16, channel strides in elements and multiples of 8, 16-byte aligned pointers.
 #include "w2l_common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "w2l_storage.h"
 
 struct w2l_s3fd_headb {
     int cin, ncls;
@@ -22,110 +16,6 @@ namespace w2l {
 
 constexpr long long kLim2G = 1ll << 31;     // the convb launches' per-buffer rule (32-bit byte offsets)
 
-static inline int grid1db(long long work, int block, int cap = 65536) {
-    long long g = (work + block - 1) / block;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
-__global__ void s3fd_pack_bf16_kernel(long long npix, const uint8_t* __restrict__ x, __bf16* __restrict__ y, int y_cs) {
-    const int groups = y_cs >> 3;
-    const long long total = npix * groups;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const long long pix = i / groups;
-        const int g = (int)(i - pix * groups);
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (__bf16)0.f;
-        if (g == 0) {
-            // the fp32 pack's values (w2l_s3fd_pack): integers with |v| <= 152, exact in bf16
-            float c0, c1, c2;
-            s3fd_pixel(x + pix * 3, 104.f, 117.f, 123.f, c0, c1, c2);
-            o[0] = (__bf16)c0; o[1] = (__bf16)c1; o[2] = (__bf16)c2;
-        }
-        *reinterpret_cast<bf16x8*>(y + pix * y_cs + g * 8) = o;
-    }
-}
-
-// The row-table form (s3fd_pack_rows_kernel of detect.hip): blockIdx.y is the image, a thread owns four consecutive pixels and
-// writes every 8-channel group of each (group 0: the pixel, the rest zeros)
-__global__ void s3fd_pack_rows_bf16_kernel(int npix, const uint64_t* __restrict__ frames, __bf16* __restrict__ y, int y_cs) {
-    const int b = blockIdx.y;
-    const uint64_t addr = frames[b];
-    const uint8_t* x = reinterpret_cast<const uint8_t*>(addr);
-    const bool dwords = (addr & 3) == 0;
-    __bf16* yb = y + (long long)b * npix * y_cs;
-    const int ngroups = (npix + 3) >> 2, groups = y_cs >> 3;
-    for (int g4 = blockIdx.x * blockDim.x + threadIdx.x; g4 < ngroups; g4 += gridDim.x * blockDim.x) {
-        const int i0 = g4 << 2, n = min(4, npix - i0);
-        uint8_t px[12];
-        s3fd_load_group(x + (long long)i0 * 3, dwords, n, px);
-        for (int k = 0; k < n; ++k) {
-            float c0, c1, c2;
-            s3fd_pixel(px + 3 * k, 104.f, 117.f, 123.f, c0, c1, c2);
-            bf16x8 o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (__bf16)0.f;
-            __bf16* op = yb + (long long)(i0 + k) * y_cs;
-            for (int g = 1; g < groups; ++g) *reinterpret_cast<bf16x8*>(op + g * 8) = o;
-            o[0] = (__bf16)c0; o[1] = (__bf16)c1; o[2] = (__bf16)c2;
-            *reinterpret_cast<bf16x8*>(op) = o;
-        }
-    }
-}
-
-// one thread per (output pixel, 8-channel group)
-__global__ void maxpool2x2_bf16_kernel(int N, int H, int W, int C8, const __bf16* __restrict__ x, int x_cs, __bf16* __restrict__ y,
-                                       int y_cs) {
-    const int Ho = H / 2, Wo = W / 2;
-    const long long total = (long long)N * Ho * Wo * C8;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c8 = (int)(i % C8);
-        long long pix = i / C8;
-        const int ox = (int)(pix % Wo);
-        pix /= Wo;
-        const int oy = (int)(pix % Ho);
-        const int n = (int)(pix / Ho);
-        const __bf16* p = x + (((long long)n * H + 2 * oy) * W + 2 * ox) * x_cs + c8 * 8;
-        const bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
-        const bf16x8 b = *reinterpret_cast<const bf16x8*>(p + x_cs);
-        const bf16x8 c = *reinterpret_cast<const bf16x8*>(p + (long long)W * x_cs);
-        const bf16x8 d = *reinterpret_cast<const bf16x8*>(p + (long long)W * x_cs + x_cs);
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-            o[e] = (__bf16)fmaxf(fmaxf((float)a[e], (float)b[e]), fmaxf((float)c[e], (float)d[e]));   // exact: a max of bf16 values
-        *reinterpret_cast<bf16x8*>(y + (((long long)n * Ho + oy) * Wo + ox) * y_cs + c8 * 8) = o;
-    }
-}
-
-// one wave per pixel: fp32 sum of squares over the channels, then x / norm * weight[c] in fp32, rounded once (RNE)
-__global__ void l2norm_scale_bf16_kernel(long long rows, int C, const __bf16* __restrict__ x, int x_cs, const float* __restrict__ w,
-                                         __bf16* __restrict__ y, int y_cs) {
-    const long long row = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    const __bf16* p = x + row * x_cs;
-    float s = 0.f;
-    for (int c = lane * 8; c < C; c += 512) {
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(p + c);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += (float)v[e] * (float)v[e];
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float norm = sqrtf(s) + 1e-10f;
-    for (int c = lane * 8; c < C; c += 512) {
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(p + c);
-        const f32x4 w0 = *reinterpret_cast<const f32x4*>(w + c), w1 = *reinterpret_cast<const f32x4*>(w + c + 4);
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (__bf16)((float)v[e] / norm * (e < 4 ? w0[e] : w1[e - 4]));
-        *reinterpret_cast<bf16x8*>(y + row * y_cs + c) = o;
-    }
-}
-
-// ---- the fused detection head
 // weights: one thread per packed element; columns without a filter (ncls = 2: columns 2, 3) are zero
 __global__ void s3fd_headb_pack_kernel(int cin, int ncls, const float* __restrict__ conf_w, const float* __restrict__ conf_b,
                                        const float* __restrict__ loc_w, const float* __restrict__ loc_b, __bf16* __restrict__ w,
@@ -151,8 +41,8 @@ __global__ void s3fd_headb_pack_kernel(int cin, int ncls, const float* __restric
 // A workgroup of four waves computes an 8 x 16 tile of output positions: per 32-channel chunk the (8+2) x (16+2) halo box is
 // staged in LDS (every feature is read from HBM once plus the halo), each wave owns two rows of 16 positions = two 16x16 MFMA
 // tiles (M = positions, N = 16 columns of which 8 are used, K = 32 channels of one tap), nine taps per chunk.  The fp32
-// accumulators + bias go through LDS to one lane per position, which decodes them with s3fd_decode_kernel's fp32 operations
-// (detect.hip) and writes the (x1, y1, x2, y2, score) row.  Logits never leave the chip.
+// accumulators + bias go through LDS to one lane per position, which decodes them (s3fd_decode_px, w2l_common.h) and writes the
+// (x1, y1, x2, y2, score) row.  Logits never leave the chip.
 constexpr int kHTW = 16, kHTH = 8, kHBW = kHTW + 2, kHBH = kHTH + 2, kHBox = kHBW * kHBH;
 
 __global__ __launch_bounds__(256) void s3fd_headb_kernel(int FH, int FW, int stride, int cin, int ncls, const __bf16* __restrict__ x,
@@ -215,25 +105,7 @@ __global__ __launch_bounds__(256) void s3fd_headb_kernel(int FH, int FW, int str
         const int hy = y0 + wave * 2 + r, wx = x0 + pos;
         if (hy < FH && wx < FW) {
             const float* c = s_ep[wave][r][pos];
-            const float* l = c + 4;
-            // s3fd_decode_kernel (detect.hip), operation for operation
-            float bg, fg;
-            if (ncls == 4) { bg = fmaxf(fmaxf(c[0], c[1]), c[2]); fg = c[3]; }
-            else { bg = c[0]; fg = c[1]; }
-            const float mx = fmaxf(bg, fg);
-            const float eb = expf(bg - mx), ef = expf(fg - mx);
-            const float score = ef / (eb + ef);
-            const float axc = (float)stride / 2.f + (float)wx * (float)stride;
-            const float ayc = (float)stride / 2.f + (float)hy * (float)stride;
-            const float pw = (float)(stride * 4);
-            float cx = axc + l[0] * 0.1f * pw;
-            float cy = ayc + l[1] * 0.1f * pw;
-            const float bw_ = pw * expf(l[2] * 0.2f);
-            const float bh = pw * expf(l[3] * 0.2f);
-            cx -= bw_ / 2.f;
-            cy -= bh / 2.f;
-            float* o = out + (((long long)n * FH + hy) * FW + wx) * 5;
-            o[0] = cx; o[1] = cy; o[2] = bw_ + cx; o[3] = bh + cy; o[4] = score;
+            s3fd_decode_px(c, ncls, c + 4, stride, wx, hy, out + (((long long)n * FH + hy) * FW + wx) * 5);
         }
     }
 }
@@ -241,7 +113,7 @@ __global__ __launch_bounds__(256) void s3fd_headb_kernel(int FH, int FW, int str
 static int headb_pack(w2l_s3fd_headb* h, const float* conf_w, const float* conf_b, const float* loc_w, const float* loc_b,
                       hipStream_t s) {
     const long long total = (long long)h->cin * 9 * 8;
-    hipLaunchKernelGGL(s3fd_headb_pack_kernel, dim3(grid1db(total, 256, 1024)), dim3(256), 0, s, h->cin, h->ncls, conf_w, conf_b,
+    hipLaunchKernelGGL(s3fd_headb_pack_kernel, dim3(grid_cap(total, 256, 1024)), dim3(256), 0, s, h->cin, h->ncls, conf_w, conf_b,
                        loc_w, loc_b, h->w, h->b);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
@@ -252,55 +124,6 @@ static int headb_pack(w2l_s3fd_headb* h, const float* conf_w, const float* conf_
 using namespace w2l;
 
 extern "C" {
-
-int w2l_s3fd_pack_bf16(void* stream, long long npix, const uint8_t* bgr, void* y, int y_cs) {
-    W2L_REQUIRE(bgr && y && npix >= 1 && y_cs >= 8 && (y_cs & 7) == 0, "bad s3fd_pack_bf16 arguments (y_cs %% 8 == 0)");
-    W2L_REQUIRE((reinterpret_cast<uintptr_t>(y) & 15) == 0, "s3fd_pack_bf16: y must be 16-byte aligned");
-    W2L_REQUIRE(npix * y_cs * 2 < kLim2G, "s3fd_pack_bf16: buffer larger than 2 GiB: split the batch");
-    hipLaunchKernelGGL(s3fd_pack_bf16_kernel, dim3(grid1db(npix * (y_cs / 8), 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       npix, bgr, static_cast<__bf16*>(y), y_cs);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
-}
-
-int w2l_s3fd_pack_rows_bf16(void* stream, int B, int H, int W, const uint64_t* frames, void* y, int y_cs) {
-    W2L_REQUIRE(frames && y && B >= 1 && H >= 1 && W >= 1 && y_cs >= 8 && (y_cs & 7) == 0, "bad s3fd_pack_rows_bf16 arguments (y_cs %% 8 == 0)");
-    W2L_REQUIRE(B <= 65535 && (long long)H * W <= (1ll << 29), "s3fd_pack_rows_bf16: B <= 65535 and H * W <= 2^29");
-    W2L_REQUIRE((reinterpret_cast<uintptr_t>(frames) & 7) == 0, "s3fd_pack_rows_bf16: the address table must be 8-byte aligned");
-    W2L_REQUIRE((reinterpret_cast<uintptr_t>(y) & 15) == 0, "s3fd_pack_rows_bf16: y must be 16-byte aligned");
-    W2L_REQUIRE((long long)B * H * W * y_cs * 2 < kLim2G, "s3fd_pack_rows_bf16: buffer larger than 2 GiB: split the batch");
-    const int npix = H * W;
-    hipLaunchKernelGGL(s3fd_pack_rows_bf16_kernel, dim3(grid1db((npix + 3) / 4, 256, 1024), B), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), npix, frames, static_cast<__bf16*>(y), y_cs);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
-}
-
-int w2l_maxpool2x2_bf16(void* stream, int N, int H, int W, int C, const void* x, int x_cs, void* y, int y_cs) {
-    W2L_REQUIRE(x && y && N >= 1 && H >= 2 && W >= 2 && C >= 8 && (C & 7) == 0, "bad maxpool2x2_bf16 arguments (C %% 8 == 0, H, W >= 2)");
-    W2L_REQUIRE((x_cs & 7) == 0 && (y_cs & 7) == 0 && x_cs >= C && y_cs >= C &&
-                    ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0,
-                "maxpool2x2_bf16: 16-byte aligned tensors with channel strides that are multiples of 8");
-    W2L_REQUIRE((long long)N * H * W * x_cs * 2 < kLim2G, "maxpool2x2_bf16: buffer larger than 2 GiB: split the batch");
-    const long long total = (long long)N * (H / 2) * (W / 2) * (C / 8);
-    hipLaunchKernelGGL(maxpool2x2_bf16_kernel, dim3(grid1db(total, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), N, H, W,
-                       C / 8, static_cast<const __bf16*>(x), x_cs, static_cast<__bf16*>(y), y_cs);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
-}
-
-int w2l_l2norm_scale_bf16(void* stream, long long rows, int C, const void* x, int x_cs, const float* weight, void* y, int y_cs) {
-    W2L_REQUIRE(x && y && weight && rows >= 1 && C >= 8 && (C & 7) == 0, "bad l2norm_scale_bf16 arguments (C %% 8 == 0)");
-    W2L_REQUIRE((x_cs & 7) == 0 && (y_cs & 7) == 0 && x_cs >= C && y_cs >= C &&
-                    ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(weight)) & 15) == 0,
-                "l2norm_scale_bf16: 16-byte aligned tensors with channel strides that are multiples of 8");
-    W2L_REQUIRE(rows * x_cs * 2 < kLim2G && rows * y_cs * 2 < kLim2G, "l2norm_scale_bf16: buffer larger than 2 GiB: split the batch");
-    const long long blocks = (rows + 3) / 4;
-    hipLaunchKernelGGL(l2norm_scale_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), rows, C,
-                       static_cast<const __bf16*>(x), x_cs, weight, static_cast<__bf16*>(y), y_cs);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
-}
 
 int w2l_s3fd_headb_create(int cin, int ncls, const float* conf_w, const float* conf_b, const float* loc_w, const float* loc_b,
                           void* stream, w2l_s3fd_headb_t** out) {

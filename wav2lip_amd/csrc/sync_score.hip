@@ -214,38 +214,34 @@ __global__ __launch_bounds__(1024) void lse_score_segments_kernel(const Segment*
 
 using namespace w2l;
 
-extern "C" {
-
-int w2l_sync_window_rows(void* stream, int B, const w2l_sync_row* rows, int S, float* face_in, int face_cs, float* mel_in, int mel_cs) {
-    W2L_REQUIRE(rows && face_in && mel_in && S >= 2 && S <= 4096, "bad sync_window_rows arguments");
+template <typename T>
+static int sync_window_rows_t(void* stream, int B, const w2l_sync_row* rows, int S, T* face_in, int face_cs, T* mel_in, int mel_cs,
+                              const char* name) {
+    constexpr int VEC = 16 / (int)sizeof(T);      // channels of one 16-byte store
+    W2L_REQUIRE(rows && face_in && mel_in && S >= 2 && S <= 4096, "bad %s arguments", name);
     W2L_REQUIRE(B >= 1 && B <= 65535 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0,
-                "sync_window_rows: 1 <= B <= 65535 and a 16-byte aligned row table");
-    W2L_REQUIRE(face_cs >= 16 && face_cs % 4 == 0 && mel_cs >= 4 && mel_cs % 4 == 0,
-                "sync_window_rows: face_cs=%d (>= 16) and mel_cs=%d (>= 4) must be multiples of 4", face_cs, mel_cs);
-    W2L_REQUIRE(((reinterpret_cast<uintptr_t>(face_in) | reinterpret_cast<uintptr_t>(mel_in)) & 15) == 0,
-                "sync_window_rows: 16-byte aligned outputs");
+                "%s: 1 <= B <= 65535 and a 16-byte aligned row table", name);
+    W2L_REQUIRE(face_cs >= 16 && face_cs % VEC == 0 && mel_cs >= VEC && mel_cs % VEC == 0,
+                "%s: face_cs=%d (>= 16) and mel_cs=%d (>= %d) must be multiples of %d", name, face_cs, mel_cs, VEC, VEC);
+    W2L_REQUIRE(((reinterpret_cast<uintptr_t>(face_in) | reinterpret_cast<uintptr_t>(mel_in)) & 15) == 0, "%s: 16-byte aligned outputs",
+                name);
     const int items = (S / 2) * ((S + 3) / 4) + kSyncMels * kSyncCols;
-    hipLaunchKernelGGL(sync_window_rows_kernel<float>, dim3(ceil_div(items, 256), B), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(sync_window_rows_kernel<T>, dim3(ceil_div(items, 256), B), dim3(256), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const SyncRow*>(rows), S, face_in, face_cs, mel_in, mel_cs);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }
 
+extern "C" {
+
+int w2l_sync_window_rows(void* stream, int B, const w2l_sync_row* rows, int S, float* face_in, int face_cs, float* mel_in, int mel_cs) {
+    return sync_window_rows_t<float>(stream, B, rows, S, face_in, face_cs, mel_in, mel_cs, "sync_window_rows");
+}
+
 int w2l_sync_window_rows_bf16(void* stream, int B, const w2l_sync_row* rows, int S, void* face_in, int face_cs, void* mel_in,
                               int mel_cs) {
-    W2L_REQUIRE(rows && face_in && mel_in && S >= 2 && S <= 4096, "bad sync_window_rows_bf16 arguments");
-    W2L_REQUIRE(B >= 1 && B <= 65535 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0,
-                "sync_window_rows_bf16: 1 <= B <= 65535 and a 16-byte aligned row table");
-    W2L_REQUIRE(face_cs >= 16 && face_cs % 8 == 0 && mel_cs >= 8 && mel_cs % 8 == 0,
-                "sync_window_rows_bf16: face_cs=%d (>= 16) and mel_cs=%d (>= 8) must be multiples of 8", face_cs, mel_cs);
-    W2L_REQUIRE(((reinterpret_cast<uintptr_t>(face_in) | reinterpret_cast<uintptr_t>(mel_in)) & 15) == 0,
-                "sync_window_rows_bf16: 16-byte aligned outputs");
-    const int items = (S / 2) * ((S + 3) / 4) + kSyncMels * kSyncCols;
-    hipLaunchKernelGGL(sync_window_rows_kernel<__bf16>, dim3(ceil_div(items, 256), B), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       reinterpret_cast<const SyncRow*>(rows), S, static_cast<__bf16*>(face_in), face_cs,
-                       static_cast<__bf16*>(mel_in), mel_cs);
-    W2L_HIP_CHECK(hipGetLastError());
-    return W2L_OK;
+    return sync_window_rows_t<__bf16>(stream, B, rows, S, static_cast<__bf16*>(face_in), face_cs, static_cast<__bf16*>(mel_in), mel_cs,
+                                      "sync_window_rows_bf16");
 }
 
 int w2l_sync_embeddings_bf16(void* stream, int B, int C, const void* audio_x, int audio_cs, const void* face_x, int face_cs,

@@ -6,7 +6,7 @@
 // ReLU / LeakyReLU / Sigmoid (models/conv.py:12,27,43; models/wav2lip.py:85,152) and the residual add (models/conv.py:17-18).
 //
 // Tensors are NHWC "[rows][cs]" views (rows = N*H*W pixels, C channels, cs channel stride in elements) of fp32 or bf16 elements;
-// the storage type is a template argument (StF32 / StBf16 below), never a run-time switch.  Every thread moves 16 bytes per row
+// the storage type is a template argument (StF32 / StBf16, w2l_storage.h), never a run-time switch.  Every thread moves 16 bytes per row
 // and tensor - 4 fp32 or 8 bf16 channels - so a bf16 pass costs half the bytes of its fp32 twin.  Statistics, per-channel vectors
 // and every intermediate are fp32 / fp64 in both: column reductions accumulate in fp64 per thread, combine per workgroup through
 // LDS and finish in a second kernel in a fixed order (deterministic, no atomics); one rounding to bf16 per stored element.
@@ -15,54 +15,26 @@
 #include <vector>
 
 #include "w2l_common.h"
+#include "w2l_storage.h"
 
 namespace w2l {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// VEC consecutive fp32 values (per-channel vectors, fp32 rows) -> registers
-template <int VEC>
-__device__ __forceinline__ void ldv(const float* p, float* v) {
-#pragma unroll
-    for (int q = 0; q < VEC / 4; ++q) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p + 4 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[4 * q + e] = a[e];
-    }
-}
-
-// ---------------------------------------------------------------- storage traits: 16 bytes per thread, row and tensor
-struct StF32 {
-    typedef float elem;
-    static constexpr int kVecLog2 = 2, VEC = 1 << kVecLog2;
+// ---------------------------------------------------------------- what the training reductions add to a storage trait (w2l_storage.h)
+template <class S>
+struct TrainSt;
+template <>
+struct TrainSt<StF32> {
     static constexpr bool kMaskFromZ = false;   // no fp32 caller omits y: the recomputed ReLU mask is compiled out
     // column reduction: one row per iteration and one LDS round that carries both sums side by side.  The bf16 shape below has
     // not been measured for fp32 (it costs 9 more VGPRs in the BatchNorm-backward reduction), so fp32 keeps the shape it had
     static constexpr int kRowsInFlight = 1, kLdsRounds = 1;
-    static constexpr const char* suffix = "";
-    static __device__ __forceinline__ void ld(const float* p, float* v) { ldv<4>(p, v); }
-    static __device__ __forceinline__ void st(float* p, const float* v) { *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]}; }
 };
-struct StBf16 {
-    typedef __bf16 elem;
-    static constexpr int kVecLog2 = 3, VEC = 1 << kVecLog2;
+template <>
+struct TrainSt<StBf16> {
     static constexpr bool kMaskFromZ = true;    // BatchNorm backward may recompute the ReLU mask as z*scale + shift > 0 (y == NULL)
     // column reduction: two rows per iteration, all their loads issued before the first is consumed (with one load in flight per
     // thread it ran at 1.5 - 2.5 TB/s: latency, not bandwidth); the two sums go through LDS one after the other (18 KB, not 32)
     static constexpr int kRowsInFlight = 2, kLdsRounds = 2;
-    static constexpr const char* suffix = "_bf16";
-    static __device__ __forceinline__ void ld(const __bf16* p, float* v) {
-        const bf16x8 b = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (float)b[e];
-    }
-    static __device__ __forceinline__ void st(__bf16* p, const float* v) {   // the one rounding of a stored element (RNE)
-        bf16x8 b;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) b[e] = (__bf16)v[e];
-        *reinterpret_cast<bf16x8*>(p) = b;
-    }
 };
 
 // Branch-free forms for the row loops: `act` is wave-uniform, and a switch per ELEMENT compiles to a scalar branch per element
@@ -118,7 +90,7 @@ struct ColArgs {
 template <class S, int MODE>
 __global__ __launch_bounds__(256) void col_reduce_kernel(const ColArgs<S> a) {
     constexpr int VEC = S::VEC;
-    constexpr int ROUNDS = S::kLdsRounds;
+    constexpr int ROUNDS = TrainSt<S>::kLdsRounds;
     // one round: both sums side by side (fp32: 256 x 8 doubles = 16 KB); two rounds: one sum at a time + 1 pad column, the
     // combine walks rows CG apart (bf16: 256 x 9 doubles = 18 KB)
     __shared__ double red[256][ROUNDS == 1 ? 2 * VEC : VEC + 1];
@@ -139,7 +111,7 @@ __global__ __launch_bounds__(256) void col_reduce_kernel(const ColArgs<S> a) {
         float sc[VEC], sh[VEC];
 #pragma unroll
         for (int e = 0; e < VEC; ++e) { sc[e] = 0.f; sh[e] = 0.f; }
-        const bool no_y = S::kMaskFromZ && (MODE == kColBnBwd) && a.y == nullptr;
+        const bool no_y = TrainSt<S>::kMaskFromZ && (MODE == kColBnBwd) && a.y == nullptr;
         const ActK ak = act_consts(a.act);
         if (MODE == kColBnBwd) { ldv<VEC>(a.mean + cg * VEC, mu); ldv<VEC>(a.rstd + cg * VEC, rs); }
         if (no_y) { ldv<VEC>(a.scale + cg * VEC, sc); ldv<VEC>(a.shift + cg * VEC, sh); }
@@ -163,7 +135,7 @@ __global__ __launch_bounds__(256) void col_reduce_kernel(const ColArgs<S> a) {
         };
         // rows r0 + rl, + RPP, + 2 RPP, ... in this order whether one or two are loaded per iteration
         long long r = r0 + rl;
-        if (S::kRowsInFlight == 2) {
+        if (TrainSt<S>::kRowsInFlight == 2) {
             for (; r + RPP < r1; r += 2 * RPP) {
                 float va[VEC], vb[VEC], ya[VEC], yb[VEC], za[VEC], zb[VEC];
                 S::ld(a.a + r * a.a_cs + cg * VEC, va);
@@ -493,7 +465,7 @@ __global__ __launch_bounds__(256) void ew_kernel(const EwArgs<S> a) {
     float v5[VEC];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) v5[e] = 0.f;
-    if (S::kMaskFromZ && MODE == kEwBnBwd && a.v5) ldv<VEC>(a.v5 + c, v5);
+    if (TrainSt<S>::kMaskFromZ && MODE == kEwBnBwd && a.v5) ldv<VEC>(a.v5 + c, v5);
     const ActK ak = act_consts(a.act);
     for (long long r = (long long)blockIdx.x * RPP + rl; r < a.rows; r += (long long)gridDim.x * RPP) {
         float av[VEC], o[VEC];
@@ -509,7 +481,7 @@ __global__ __launch_bounds__(256) void ew_kernel(const EwArgs<S> a) {
         } else if (MODE == kEwBnBwd) {   // v0 gamma*rstd, v1 mean, v2 rstd, v3 sum g, v4 sum g*zhat
             float yv[VEC], zv[VEC], g[VEC];
             S::ld(a.c + r * a.c_cs + c, zv);
-            if (!S::kMaskFromZ || a.b) S::ld(a.b + r * a.b_cs + c, yv);
+            if (!TrainSt<S>::kMaskFromZ || a.b) S::ld(a.b + r * a.b_cs + c, yv);
             else {
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) yv[e] = zv[e] * v0[e] + v5[e];
@@ -605,7 +577,7 @@ static int bn_train_bwd(hipStream_t s, long long rows, int C, int Cvalid, const 
         return W2L_ERR_ARG;
     W2L_REQUIRE(mean && rstd && scale && dgamma && dbeta, "bn_train_bwd%s: NULL argument", S::suffix);
     W2L_REQUIRE(Cvalid >= 1 && Cvalid <= C, "bn_train_bwd%s: Cvalid=%d outside [1, C=%d]", S::suffix, Cvalid, C);
-    W2L_REQUIRE(y != nullptr || (S::kMaskFromZ && shift != nullptr && act == W2L_ACT_RELU && g_out == nullptr),
+    W2L_REQUIRE(y != nullptr || (TrainSt<S>::kMaskFromZ && shift != nullptr && act == W2L_ACT_RELU && g_out == nullptr),
                 "bn_train_bwd%s: y may be omitted only in bf16 storage, for a ReLU block without residual, with the forward shift given",
                 S::suffix);
     W2L_REQUIRE(g_out == nullptr || row_check<S>(rows, C, g_out, g_cs, "bn_train_bwd", " g") == W2L_OK, "bn_train_bwd%s: bad g_out", S::suffix);

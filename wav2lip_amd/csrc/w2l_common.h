@@ -59,8 +59,8 @@ __device__ __forceinline__ float shifted_pdist_wave(const float* __restrict__ a,
 }
 
 // The S3FD detector's input pixel: one BGR byte triple -> RGB order (api.py:62 `images[..., ::-1]`) minus the per-channel mean in
-// float64, cast to float32 (detect.py:57-63).  Every pack kernel calls it - s3fd_pack_kernel / s3fd_pack_rows_kernel (detect.hip) and
-// their bf16 forms (detect_bf16.hip) - so that the frame-batch and the row-table forms agree byte for byte.
+// float64, cast to float32 (detect.py:57-63).  Every pack kernel calls it - s3fd_pack_kernel, s3fd_pack_rows_kernel and
+// s3fd_pack_rows_scaled_kernel (detect.hip), each for fp32 and bf16 storage - so that all forms agree byte for byte.
 __device__ __forceinline__ void s3fd_pixel(const uint8_t* bgr, float m0, float m1, float m2, float& c0, float& c1, float& c2) {
     c0 = (float)((double)bgr[2] - (double)m0);
     c1 = (float)((double)bgr[1] - (double)m1);
@@ -79,6 +79,29 @@ __device__ __forceinline__ void s3fd_load_group(const uint8_t* __restrict__ p, b
     } else {
         for (int k = 0; k < 3 * npx; ++k) px[k] = p[k];
     }
+}
+
+// One position (wx, hy) of an S3FD level of the given stride, from its class logits c[ncls] and box regression l[4] to the row
+// (x1, y1, x2, y2, score) at o: max-out background label (net_s3fd.py:123-126), F.softmax over the two classes, the prior and the
+// decode with variances (0.1, 0.2) (detect.py:66-84, bbox.py:91-108).  s3fd_decode_kernel (detect.hip) reads the logits from HBM,
+// the fused bf16 head (s3fd_headb_kernel, detect_bf16.hip) from its fp32 accumulators in LDS.
+__device__ __forceinline__ void s3fd_decode_px(const float* c, int ncls, const float* l, int stride, int wx, int hy, float* o) {
+    float bg, fg;
+    if (ncls == 4) { bg = fmaxf(fmaxf(c[0], c[1]), c[2]); fg = c[3]; }
+    else { bg = c[0]; fg = c[1]; }
+    const float mx = fmaxf(bg, fg);
+    const float eb = expf(bg - mx), ef = expf(fg - mx);
+    const float score = ef / (eb + ef);
+    const float axc = (float)stride / 2.f + (float)wx * (float)stride;
+    const float ayc = (float)stride / 2.f + (float)hy * (float)stride;
+    const float pw = (float)(stride * 4);
+    float cx = axc + l[0] * 0.1f * pw;
+    float cy = ayc + l[1] * 0.1f * pw;
+    const float bw = pw * expf(l[2] * 0.2f);
+    const float bh = pw * expf(l[3] * 0.2f);
+    cx -= bw / 2.f;
+    cy -= bh / 2.f;
+    o[0] = cx; o[1] = cy; o[2] = bw + cx; o[3] = bh + cy; o[4] = score;
 }
 
 // Workgroup ids are dealt round-robin to the 8 XCDs (id % 8), each with its own L2.  This maps the hardware id to a

@@ -5,8 +5,8 @@ Activations are NHWC fp32; the detection heads write (conf, loc) maps that `w2l_
 (x1, y1, x2, y2, score) tables, one per pyramid level.
 
 `dense_boxes(images, precision="bf16")` runs the graph in bf16 storage instead (opt-in): bf16 NHWC activations, the
-convolutions as `w2l_convb` launches (bias as the fp32 shift, ReLU), the bf16 glue kernels of csrc/detect_bf16.hip and one fused
-head per level (`w2l_s3fd_headb_decode`: conf + loc contraction and decode, the logits never leave the chip).
+convolutions as `w2l_convb` launches (bias as the fp32 shift, ReLU), the bf16 instantiations of the same glue kernels and one fused
+head per level (`w2l_s3fd_headb_decode`, csrc/detect_bf16.hip: conf + loc contraction and decode, the logits never leave the chip).
 
 `det_scale=k` (opt-in, 1..8) runs either graph on the frame at (H // k, W // k) - `cv2.resize(frame, (w // k, h // k))`, the sizes
 of inference.py:202-203 - which `w2l_s3fd_pack_rows_scaled` computes while it fills the graph's input; the tables stay in the
