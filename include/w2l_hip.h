@@ -653,6 +653,30 @@ int w2l_face_boxes_stream_runs(void* stream, int n_seg, const w2l_box_stream_seg
                                const int32_t* rects, const int32_t* flags, int n_rows, int32_t* carry, int n_slots, int top, int bottom,
                                int left, int right, int T, int hold, int32_t* boxes, int32_t* valid, int n_out, int32_t* status);
 
+/* Scene-cut detection (opt-in `scene_cuts`; not the reference's behaviour, which treats a clip as one take): where
+ * the shots of a clip are, decided on the device from the frames the detector reads.  A shot then is a segment of the track and of
+ * the box finishes above, which stay as they are.  With one threshold in [1/256, 1), quantised as q = int(thresh * 256) in 1..255:
+ *   1. signature: a frame is H * W * 3 contiguous bytes, BGR interleaved; byte j belongs to channel j % 3 and bin byte >> 3;
+ *      sig[c * 32 + b] is a uint32 count - 96 words per frame, every channel sums to H * W.  Integers only, no luma, no float.
+ *   2. distance: D(i) = sum_k |sig_i[k] - sig_{i-1}[k]|, in 0 .. 6 * H * W.
+ *   3. cut: frame i >= 1 of a clip starts a new shot iff D(i) * 256 > q * 6 * H * W in int64; frame 0 never does.  The rule looks
+ *      one frame back only (causal).  Gradual transitions - fades, dissolves - are not detected.
+ *
+ * w2l_frame_hist_rows: `frames` is the address table w2l_s3fd_pack_rows takes (8-byte aligned; entry b = pixel (0,0) of a u8
+ * [H,W,3] frame at ANY byte address; an address may repeat) -> sig [B][96] uint32 (4-byte aligned; callers offset the pointer into
+ * an arena).  The rows are zeroed on the stream and then added to with integer atomics: the words are independent of the launch
+ * geometry and bit-reproducible.  No byte outside [frames[b], frames[b] + H * W * 3) is loaded.  Refused: a NULL pointer, B < 1, H or
+ * W < 1, 6 * H * W >= 2^31, a misaligned table or sig.
+ *
+ * w2l_scene_cuts: over w2l_face_boxes_segments' table, segment k = one clip, rows [row0, row0 + n) of sig [n_rows][96] with
+ * frames of H x W.  cuts [n_rows] int32: 1 where the row starts a new shot, a segment's first row always 0; dist [n_rows] int32 = D,
+ * 0 on a segment's first row (dist may be NULL).  status [n_seg] int32: 0, or 3 for a segment whose rows leave [0, n_rows) or whose
+ * H, W are below 1 or 6 * H * W >= 2^31 - nothing of such a segment is read or written.  n <= 0: status 0, nothing else touched.
+ * Refused: a NULL pointer other than dist, n_seg < 1, n_rows < 0, q outside 1..255, a table that is not 16-byte aligned. */
+int w2l_frame_hist_rows(void* stream, int B, int H, int W, const uint64_t* frames, uint32_t* sig);
+int w2l_scene_cuts(void* stream, int n_seg, const w2l_box_segment* segs, const uint32_t* sig, int n_rows, int q, int32_t* cuts,
+                   int32_t* dist, int32_t* status);
+
 /* The opt-in bf16-storage detector (face_detection/s3fd.py, precision="bf16"): the backbone convolutions are w2l_convb layers
  * (scale 1, shift = bias, ReLU); these are the ops between them and the fused detection head.  Tensors are NHWC bf16 with channel
  * strides that are multiples of 8, 16-byte aligned; no buffer may reach 2 GiB (the convb rule: split the batch). */

@@ -2,6 +2,7 @@
 `for clip: inference.face_detect(frames, detector, ...)` over the same seeded clips.
 
     python tools/detect_bench.py [--clips 200] [--alternations 5] [--batch 16] [--precision f32] [--seed 0] [--face_track PICK]
+                                 [--scene_cuts THRESH]
 
 The clips are those of tools/filelist_bench.py (160x160 frames, lengths uniform in 30..120, 16 distinct frames cycled), each frame
 with the saturated block of synthetic.filelist_frame pasted in so that the seeded S3FD (synthetic.s3fd_state_dict) finds a face;
@@ -17,7 +18,13 @@ With `--face_track PICK` (tracked face selection) the two loops ar
 `face_track=PICK` (defaults K = 8, L = 0, min_iou = 0.25) - "packed" and "packed_tracked" - alternated the same way: what the two
 small launches per batch in place of one, and the track launch per group, cost.  The seeded clips hold one saturated block each;
 how often the seeded detector sees more than one candidate there is reported by `boxes_that_differ`, and says nothing about
-selection quality on real footage."""
+selection quality on real footage.
+
+With `--scene_cuts THRESH` (scene-cut detection) the two loops are the packed detector without and with
+`scene_cuts=THRESH` - "packed" and "packed_scene" - alternated the same way: what the signature launch over every frame, the cut
+launch and the small copy per group cost.  The seeded clips cycle 16 noise frames whose histograms are alike, so at 0.3 no cut
+fires on them and `boxes_that_differ` must be 0 (a clip without a cut is the feature switched off); the per-shot tables are built
+all the same.  Nothing here says anything about detection quality on real footage."""
 import argparse
 import json
 import os
@@ -97,7 +104,11 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--face_track", default=None, choices=["score", "largest", "left", "right"],
                     help="compare the packed detector without and with face_track=PICK instead of packed against per-clip")
+    ap.add_argument("--scene_cuts", default=None, type=float, metavar="THRESH",
+                    help="compare the packed detector without and with scene_cuts=THRESH instead of packed against per-clip")
     a = ap.parse_args(argv)
+    if a.face_track is not None and a.scene_cuts is not None:
+        ap.error("--face_track and --scene_cuts are two comparisons: give one")
     dev = torch.device("cuda", 0)
     clips = clips_with_faces(a.clips, a.seed)
     frames = sum(len(c) for c in clips)
@@ -107,6 +118,9 @@ def main(argv=None):
     if a.face_track is not None:
         out["face_track"] = a.face_track
         loops["packed_tracked"] = (lambda det, clips, batch: run_packed(det, clips, batch, face_track=a.face_track), loops.pop("per_clip")[1])
+    if a.scene_cuts is not None:
+        out["scene_cuts"] = a.scene_cuts
+        loops["packed_scene"] = (lambda det, clips, batch: run_packed(det, clips, batch, scene_cuts=a.scene_cuts), loops.pop("per_clip")[1])
     first, second = list(loops)
     res = {k: {"frames_per_s": [], "graph_builds": []} for k in loops}
     last = {}

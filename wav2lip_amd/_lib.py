@@ -234,6 +234,8 @@ SIGNATURES = {
     "w2l_face_boxes_stream": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "w2l_face_boxes_runs": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "w2l_face_boxes_stream_runs": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "w2l_frame_hist_rows": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "w2l_scene_cuts": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "w2l_s3fd_pack_bf16": (_i, [_vp, _ll, _vp, _vp, _i]),
     "w2l_s3fd_pack_rows_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp, _i]),
     "w2l_s3fd_pack_rows_scaled_bf16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i]),

@@ -1,8 +1,10 @@
 """`face_detection` with the reference's surface (face_detection/__init__.py, api.py): `FaceAlignment`, `LandmarksType`,
 `NetworkSize`; the S3FD detector behind it runs on the HIP path (wav2lip_amd/face_detection/s3fd.py).  `detect_many` /
 `DetectJob` (wav2lip_amd/face_detection/many.py) run `inference.face_detect` for many clips in shared detector batches; `FaceTrack`
-(wav2lip_amd/face_detection/track.py) is the value their opt-in `face_track=` takes."""
+(wav2lip_amd/face_detection/track.py) is the value their opt-in `face_track=` takes, `SceneCuts`
+(wav2lip_amd/face_detection/scene.py) the value of their opt-in `scene_cuts=`."""
 from .api import FaceAlignment, LandmarksType, NetworkSize  # noqa: F401
 from .many import DetectJob, detect_many  # noqa: F401
 from .s3fd import s3fd  # noqa: F401
+from .scene import SceneCuts  # noqa: F401
 from .track import FaceTrack  # noqa: F401

@@ -23,6 +23,11 @@ the boxes.  `host_boxes_runs` is that rule on the host.
 With `face_track=...` (opt-in) a batch ends in w2l_s3fd_top_rects instead of w2l_s3fd_first_rect - up to K candidate
 rects per frame, in arenas of their own - and ONE w2l_face_track_segments launch over the group's clips writes the rects and flags
 the finish reads: one face followed through each clip (`face_detection/track.py`).  Still one copy back per group.
+
+With `scene_cuts=...` (opt-in) ONE w2l_frame_hist_rows launch reads the group's frames where they lie and ONE
+w2l_scene_cuts launch over the clip table flags the frames that start a shot; the flags come back in a small copy of their own,
+queued before the detector batches and waited for after them, and the host then writes one segment per SHOT for the track and the
+finish, which run as they are (`face_detection/scene.py`).
 """
 import collections
 
@@ -31,6 +36,7 @@ import torch
 
 from .._lib import BOX_SEGMENT, TRACK_SEGMENT
 from ..staging import ADDRESS, Staging
+from .scene import host_boxes_shots, split_shots
 
 MAX_T = 64           # w2l_face_boxes_segments' largest smoothing window
 NO_FACE = 'Face not detected! Ensure the video contains a face in all the frames.'      # inference.py:89
@@ -246,12 +252,27 @@ def _finish_runs(n_seg, segs, rects, flags, n_rows, pads, T, hold, boxes, valid,
                                      hold, ptr(boxes), ptr(valid), ptr(status)), "face_boxes_runs")
 
 
-def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None):
+def _fold_shot_status(shot_status, shots_of):
+    """the per-clip status [clips,2] of the shots' status [shots,2]: across a clip's shots code 2 wins over code 1, and the row is
+    the clip's frame that decided it (the first shot with the winning code); shots_of: [(a, b)] per clip, in clip order"""
+    out, k = np.zeros((len(shots_of), 2), dtype=shot_status.dtype), 0
+    for c, shots in enumerate(shots_of):
+        for a, _ in shots:
+            code, row = (int(v) for v in shot_status[k])
+            if code > out[c][0]:
+                out[c] = (code, a + row)
+            k += 1
+    return out
+
+
+def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None, scene=None):
     """One group on the device.  clips: _Clips of one frame shape, each with at least one frame.  Returns numpy (boxes int32 [R,4]
     in (y1, y2, x1, x2) order, rows in clip order; status int32 [clips,2]); with `hold` (the pass-through rule) a third array,
     valid int32 [R], comes between them - still one launch and one copy back.  With `track` (a FaceTrack) the batches leave
     candidates and one more launch, before the finish, chooses the rect of every frame; its status words come back in the same
-    copy and are all 0 (the table is built here)."""
+    copy and are all 0 (the table is built here).  With `scene` (a SceneCuts) the signature and the cut launch run first, their R
+    flags come back while the detector batches run, and the track and the finish get one segment per shot; the status returned is
+    still per clip (`_fold_shot_status`)."""
     dev = torch.device(detector.device)
     H, W = clips[0].H, clips[0].W
     R = sum(c.n for c in clips)
@@ -273,23 +294,77 @@ def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None):
         r += c.n
     addr[R:] = addr[R - 1]
     st.upload()
+    if scene is not None:                                    # queued before the batches: the flags cross while the detector runs
+        _, cuts_host, cuts_ready = _queue_cuts(st.tensor(addresses), st.tensor(segments), len(clips), R, H, W, scene, dev)
     arenas = detect_rows(detector, st.tensor(addresses), [(H, W, 0, padded)], batch_size, padded, track)    # rows [R, padded): scratch
-    out = BoxOut(R, len(clips), hold is not None, track is not None, dev)
+    n_seg, seg_dev, track_dev, shots_of = len(clips), st.tensor(segments), None if tracks is None else st.tensor(tracks), None
+    if scene is not None:
+        cuts_ready.synchronize()
+        cuts = cuts_host.numpy()
+        if cuts[R:].any():
+            raise AssertionError("w2l_scene_cuts did not follow a clip's segment (status %s)" % cuts[R:].tolist())
+        shots_of = [split_shots(c.n, cuts[r0:r0 + c.n]) for c, r0 in zip(clips, np.cumsum([0] + [c.n for c in clips[:-1]]).tolist())]
+        st2, n_seg = Staging(dev), sum(len(s) for s in shots_of)
+        segments2 = st2.table(BOX_SEGMENT, n_seg)
+        tracks2 = None if track is None else st2.table(TRACK_SEGMENT, n_seg)
+        st2.allocate()
+        k, r = 0, 0
+        for c, shots in zip(clips, shots_of):
+            for a, b in shots:
+                st2.view(segments2)[k] = (r + a, b - a, H, W)
+                if tracks2 is not None:
+                    st2.view(tracks2)[k] = (r + a, b - a, -1, 0)     # a shot: a fresh track
+                k += 1
+            r += c.n
+        st2.upload()
+        seg_dev, track_dev = st2.tensor(segments2), None if tracks2 is None else st2.tensor(tracks2)
+    out = BoxOut(R, n_seg, hold is not None, track is not None, dev)
     if track is not None:
-        track_rows(len(clips), st.tensor(tracks), arenas, track, out.track_status)
+        track_rows(n_seg, track_dev, arenas, track, out.track_status)
     if hold is None:
-        _finish_segments(len(clips), st.tensor(segments), arenas.rects, arenas.flags, pads, T, out.boxes, out.status)
+        _finish_segments(n_seg, seg_dev, arenas.rects, arenas.flags, pads, T, out.boxes, out.status)
     else:
-        _finish_runs(len(clips), st.tensor(segments), arenas.rects, arenas.flags, R, pads, T, hold, out.boxes, out.valid, out.status)
+        _finish_runs(n_seg, seg_dev, arenas.rects, arenas.flags, R, pads, T, hold, out.boxes, out.valid, out.status)
     # the group's one copy back; it also ends the stream's use of the staging buffers
     boxes, valid, status, _ = out.split(out.buffer.cpu().numpy())
+    if shots_of is not None:
+        status = _fold_shot_status(status, shots_of)
     return (boxes, status) if hold is None else (boxes, valid, status)
 
 
-def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None):
-    """one clip alone through `inference.face_detect` (batch by batch uploads, the host rules): (key, boxes, error)"""
+def _queue_cuts(addresses, segments, n_clips, R, H, W, scene, dev):
+    """the two scene launches of a group and the copy of their result, all queued on the current stream: signatures of the R frames of
+    the address table, cut flags over the clip table -> (the device buffer, its pinned host copy int32 [R + n_clips] = cuts [R] +
+    status [n_clips], the event that says the copy has landed)"""
+    from .scene import SIG_WORDS, cut_flags, frame_signatures, scene_q8
+    sig = torch.empty((R, SIG_WORDS), dtype=torch.int32, device=dev)
+    frame_signatures(addresses, sig, 0, rows=(R, H, W))
+    buf = torch.empty(R + n_clips, dtype=torch.int32, device=dev)
+    cut_flags(segments, n_clips, sig, scene_q8(scene.thresh), buf[:R], buf[R:])
+    host = torch.empty(R + n_clips, dtype=torch.int32, pin_memory=True)
+    host.copy_(buf, non_blocking=True)
+    ready = torch.cuda.Event()
+    ready.record()
+    return buf, host, ready
+
+
+def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None, scene=None):
+    """one clip alone through `inference.face_detect` (batch by batch uploads, the host rules): (key, boxes, error).  `scene` is passed
+    on to it; where `face_detect`'s own finish does not fit (a hold, or a window other than 5) the same host rules run per shot
+    here, on `inference._shot_rects`."""
     from .. import inference
     frames = list(clip.frames.cpu().numpy()) if isinstance(clip.frames, torch.Tensor) else list(clip.frames)
+    if scene is not None:
+        try:
+            if hold is None and T in (0, 5):
+                det = inference.face_detect(frames, detector=detector, pads=list(pads), nosmooth=(T == 0), batch_size=batch_size,
+                                            scene_cuts=scene, **({} if track is None else {"face_track": track}))
+                return clip.key, np.array([c for _, c in det], dtype=np.int64).reshape(-1, 4), None
+            rects, shots = inference._shot_rects(frames, detector, batch_size, track, scene)
+            boxes, valid = host_boxes_shots(rects, shots, clip.H, clip.W, pads, T, hold)
+            return clip.key, boxes if hold is None else RunBoxes(boxes, valid), None
+        except (ValueError, OverflowError) as e:
+            return clip.key, None, str(e)
 
     def clip_rects():
         if track is None:
@@ -315,7 +390,7 @@ def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None):
 
 
 def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_batches=16, max_group_bytes=1 << 30, no_face_hold=None,
-                face_track=None):
+                face_track=None, scene_cuts=None):
     """`inference.face_detect(frames, detector, pads, nosmooth=(T == 0))` for every `DetectJob` of the iterable `jobs`, the frames
     of successive clips packed into detector batches of exactly `batch_size`.  A generator: jobs are consumed lazily and one
     `(key, boxes, error)` comes out per job, in job order - `boxes` the int array [n,4] of (y1, y2, x1, x2) `face_detect` returns
@@ -341,12 +416,22 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
 
     `face_track`: None (default), or a pick name / `track.FaceTrack`: one face is followed through every clip instead of taking
     the best-scoring box of each frame (not the reference's behaviour), exactly as `face_detect(face_track=...)`
-    does for the clip alone."""
+    does for the clip alone.
+
+    `scene_cuts`: None (default), or a threshold in [1/256, 1) / `scene.SceneCuts`: every clip is split into shots where the colour
+    histogram of a frame differs from the previous frame's by more than the threshold, and every shot is tracked, held, padded,
+    clipped and smoothed as a clip of its own (not the reference's behaviour), exactly as
+    `face_detect(scene_cuts=...)` does for the clip alone.  A job still gets one result: in the strict mode a frame without a
+    face in any shot is the clip's error."""
     from ..inference import halving
+    from .scene import check_scene
     from .track import check_track
     hold = check_hold(no_face_hold)
     track = check_track(face_track)
+    scene = check_scene(scene_cuts)
     tkw = {} if track is None else {"track": track}    # the default path calls its helpers with the arguments it always did
+    if scene is not None:
+        tkw["scene"] = scene
     if batch_size < 1 or group_batches < 1:
         raise ValueError("batch_size and group_batches must be at least 1")
     if not 0 <= int(T) <= MAX_T:

@@ -210,8 +210,9 @@ def build_cli_parser():
     `--face_det_scale K`, the detector's frame size (1/K; output frames keep theirs), `--out_codec` / `--out_quality`,
     `--blend_feather N` / `--blend_top FRACTION`, the feathered mouth-region paste, `--color_match {mean,full}`, colour matching
     of the prediction to its crop (absent by default), `--no_face_hold G`, the pass-through for frames without a face (absent by
-    default), and `--face_track PICK` with its three companions, tracked face selection
-    (`face_detection/track.py`; absent by default)"""
+    default), `--face_track PICK` with its three companions, tracked face selection (`face_detection/track.py`; absent by
+    default), and `--scene_cuts THRESH`, every shot of the clip boxed and tracked alone (`face_detection/scene.py`; absent by
+    default)"""
     p = build_parser()
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
                    help='Generator arithmetic: fp32 (default, matches the reference) or bf16 storage (faster; frames differ by '
@@ -229,7 +230,14 @@ def build_cli_parser():
     add_color_match_flag(p)
     add_hold_flag(p)
     add_track_flags(p)
+    add_scene_flag(p)
     return p
+
+
+def add_scene_flag(p):
+    """`--scene_cuts THRESH` on a command's parser (face_detection/scene.py holds the rule): absent by default"""
+    from .face_detection.scene import add_scene_flag as add
+    add(p)
 
 
 def add_hold_flag(p):
@@ -757,6 +765,59 @@ def _track_rects(images, detector, batch_size, track):
     return halving(run, batch_size)
 
 
+def _shot_rects(images, detector, batch_size, track, scene):
+    """`_detect_rects` / `_track_rects` under scene-cut detection (face_detection/scene.py): (one rect or None per
+    frame, the shots [(a, b)] of the clip).  Every batch is uploaded ONCE as a device tensor: w2l_frame_hist_rows reads it into the
+    clip's signature arena and the detector takes the same tensor.  After the last batch ONE w2l_scene_cuts launch and one small
+    copy give the cut flags.  With `track` the single w2l_face_track_segments launch then gets one segment per shot - a fresh
+    track at every cut - and a frame the device does not decide (RECT_HOST) sends every shot through `host_track` on its own."""
+    from .face_detection.s3fd import RECT_FOUND, RECT_HOST
+    from .face_detection.scene import SIG_WORDS, clip_cuts, frame_signatures, host_track_shots, split_shots
+    from .face_detection.track import TRACK_SEGMENT, track_segments
+    n = len(images)
+    if n == 0:
+        return [], []
+    H, W = images[0].shape[:2]
+
+    def run(batch_size):
+        dev = torch.device(detector.device)
+        sig = torch.empty((n, SIG_WORDS), dtype=torch.int32, device=dev)
+        rects = []
+        if track is not None:
+            K = track.cands
+            cands = torch.empty((n, K, 4), dtype=torch.int32, device=dev)
+            ncand = torch.empty((n,), dtype=torch.int32, device=dev)
+            cflags = torch.empty((n,), dtype=torch.int32, device=dev)
+        for lo in range(0, n, batch_size):
+            batch = torch.from_numpy(np.ascontiguousarray(np.array(images[lo:lo + batch_size]))).to(dev)
+            frame_signatures(batch, sig, lo)
+            if track is None:
+                rects += detector.get_detections_for_batch(batch)
+            else:
+                detector.cands_for_batch(batch, cands, ncand, cflags, lo, K)
+        shots = split_shots(n, clip_cuts(sig, H, W, scene)[0])
+        if track is None:
+            return rects, shots
+        seg = np.zeros(len(shots), dtype=TRACK_SEGMENT)
+        for k, (a, b) in enumerate(shots):
+            seg[k] = (a, b - a, -1, 0)
+        segs = torch.from_numpy(seg.view(np.uint8)).to(dev)
+        out = torch.empty(5 * n + len(shots), dtype=torch.int32, device=dev)       # rects [n][4], flags [n], status [shots]
+        track_segments(segs, len(shots), cands, ncand, cflags, track, out[:4 * n].view(n, 4), out[4 * n:5 * n], out[5 * n:])
+        res = out.cpu().numpy()
+        rows, flags = res[:4 * n].reshape(n, 4), res[4 * n:5 * n]
+        if res[5 * n:].any():
+            raise AssertionError("w2l_face_track_segments did not follow a shot's segment (status %s)" % res[5 * n:].tolist())
+        if (flags == RECT_HOST).any():
+            per_frame = []
+            for lo in range(0, n, batch_size):
+                per_frame += detector.get_candidates_for_batch(np.array(images[lo:lo + batch_size]), K)
+            return host_track_shots(per_frame, shots, track), shots
+        return [tuple(int(v) for v in r) if f == RECT_FOUND else None for r, f in zip(rows, flags)], shots
+
+    return halving(run, batch_size)
+
+
 def _det_scale_kw(det_scale):
     """detector keyword for a reduced detection frame: scale 1 builds the detector with the same arguments as before the option"""
     return {} if det_scale == 1 else {"det_scale": det_scale}
@@ -772,14 +833,16 @@ def detector_from_args(args, device, state_dict=None):
 
 
 def detect_kw_from_args(args):
-    """the `no_face_hold=` / `face_track=` keywords of `face_detect`, `detect_many` and `LipsyncStreams` for a parsed command line:
-    none for an absent flag; a lone `--face_track_*` flag is a ValueError"""
+    """the `no_face_hold=` / `face_track=` keywords of `face_detect`, `detect_many` and `LipsyncStreams` for a parsed command line,
+    and the `scene_cuts=` of the first two (a parser of the live path has no such flag): none for an absent flag; a lone
+    `--face_track_*` flag is a ValueError"""
+    from .face_detection.scene import scene_from_args, scene_kw
     from .face_detection.track import track_from_args
-    return {**_hold_kw(getattr(args, 'no_face_hold', None)), **_track_kw(track_from_args(args))}
+    return {**_hold_kw(getattr(args, 'no_face_hold', None)), **_track_kw(track_from_args(args)), **scene_kw(scene_from_args(args))}
 
 
 def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None, ranks=None, precision=None, det_scale=None,
-                no_face_hold=None, face_track=None):
+                no_face_hold=None, face_track=None, scene_cuts=None):
     """inference.py:68-104: S3FD boxes per frame (HIP detector), padding, temporal smoothing; returns
     [[face crop, (y1, y2, x1, x2)], ...].  Called as the reference calls it - `face_detect(images)` - pads / nosmooth /
     face_det_batch_size come from the module-level `args` and the detector is built as inference.py:69-70 does
@@ -801,8 +864,16 @@ def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None
     more than one face is in the picture): the rect of a frame is the candidate that overlaps the tracked face's last rect most, a
     frame on which the track is lost (possible with `reseed` > 0 only) is a frame without a face, and everything after the
     rects - the strict ValueError or `no_face_hold`, pads, smoothing - is as without it.  Not with `ranks` of more than one
-    process: the track looks back over the frames of other shards."""
+    process: the track looks back over the frames of other shards.
+
+    `scene_cuts`: None (default) takes the clip as one continuous take, as the reference does.  A threshold in [1/256, 1) or a
+    `face_detection.scene.SceneCuts` splits it into shots where the colour histogram of a frame differs from the previous frame's by
+    more than the threshold (not the reference's behaviour), and every shot is handled as a clip of its frames alone:
+    a fresh track at its start, a hold that does not look back past it, pads, clipping and smoothing per shot (a shot shorter than
+    5 frames takes the wrapped short-clip window).  Without a hold a frame without a face in any shot is still the ValueError.  Not
+    with `ranks` of more than one process: a cut compares a frame with the one before it, which may lie in another shard."""
     from .face_detection.many import boxed_runs, check_hold, hold_fill
+    from .face_detection.scene import check_scene
     from .face_detection.track import check_track
     from .face_detection.s3fd import check_det_scale
     from .models.wav2lip import check_precision
@@ -810,6 +881,9 @@ def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None
     track = check_track(face_track)
     if track is not None and ranks is not None and ranks.dist is not None and ranks.world > 1:
         raise ValueError("face_track runs on one GPU: the track looks back over the frames of other shards")
+    scene = check_scene(scene_cuts)
+    if scene is not None and ranks is not None and ranks.dist is not None and ranks.world > 1:
+        raise ValueError("scene_cuts runs on one GPU: a cut compares a frame with the one before it, in another shard")
     if precision is not None:
         check_precision(precision)
     if det_scale is not None:
@@ -834,9 +908,13 @@ def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None
     pads = args.pads if pads is None else pads
     nosmooth = args.nosmooth if nosmooth is None else nosmooth
     batch_size = args.face_det_batch_size if batch_size is None else batch_size
-    rects = _detect_rects(images, detector, batch_size, ranks) if track is None else _track_rects(images, detector, batch_size, track)
+    if scene is None:
+        rects = _detect_rects(images, detector, batch_size, ranks) if track is None else _track_rects(images, detector, batch_size, track)
+        shots = [(0, len(rects))]                # the reference's one take
+    else:
+        rects, shots = _shot_rects(images, detector, batch_size, track, scene)
     if hold is not None:
-        rects = hold_fill(rects, hold)
+        rects = [r for a, b in shots for r in hold_fill(rects[a:b], hold)]
     if any(r is None for r in rects) and (hold is None or len(rects) == 1):
         raise ValueError('Face not detected! Ensure the video contains a face in all the frames.')
     top, bottom, left, right = pads
@@ -847,8 +925,9 @@ def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None
                       [max(0, r[0] - left), max(0, r[1] - top), min(im.shape[1], r[2] + right), min(im.shape[0], r[3] + bottom)]
                       for r, im in zip(rects, images)], dtype=None if hold is None else np.int64).reshape(-1, 4)
     if not nosmooth:
-        for a, b in boxed_runs([r is not None for r in rects]):    # a strict clip: the one run [0, n)
-            get_smoothened_boxes(boxes[a:b], T=5)                  # a view: in place, as on a clip of the run's frames alone
+        for lo, hi in shots:
+            for a, b in boxed_runs([r is not None for r in rects[lo:hi]]):     # a strict clip: the one run [0, n)
+                get_smoothened_boxes(boxes[lo + a:lo + b], T=5)                # a view: in place, as on a clip of the run's frames alone
     return [[None, None] if r is None else [im[y1:y2, x1:x2], (y1, y2, x1, x2)]
             for r, im, (x1, y1, x2, y2) in zip(rects, images, boxes)]
 
@@ -940,7 +1019,8 @@ def main(argv=None, keep_frames=True, backend="nccl"):
     detect_kw = detect_kw_from_args(args)
     for given, why in ((mjpg, "--out_codec mjpg runs on one GPU: a sharded run gathers raw frames (compressed shards are not gathered yet)"),
                        ("no_face_hold" in detect_kw, "--no_face_hold runs on one GPU: the hold looks back over the frames of other shards"),
-                       ("face_track" in detect_kw, "--face_track runs on one GPU: the track looks back over the frames of other shards")):
+                       ("face_track" in detect_kw, "--face_track runs on one GPU: the track looks back over the frames of other shards"),
+                       ("scene_cuts" in detect_kw, "--scene_cuts runs on one GPU: a cut compares a frame with the one before it, in another shard")):
         if given and int(os.environ.get("WORLD_SIZE", "1")) > 1:     # before the process group and any device work
             raise ValueError(why)
     ranks = sharding.init_from_env(backend)
