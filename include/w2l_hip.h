@@ -47,6 +47,8 @@
  *   w2l_face_boxes_stream  inference.py:59-66, :90-104 for live streams: the same boxes, written tick by tick as frames arrive
  *   w2l_face_boxes_runs, w2l_face_boxes_stream_runs  the two above with frames without a face passed through (opt-in, not the
  *                         reference's: `no_face_hold`)
+ *   w2l_face_spans_segments  the face tracks evaluation/scores_LSE/calculate_scores_real_videos.py scores: misses bridged by
+ *                         interpolation, short tracks dropped (opt-in, not the reference's code: `track_spans`)
  *   w2l_melspectrogram    audio.py:45-51 (preemphasis, STFT, mel basis, dB, normalise)
  *   w2l_mel_gather        inference.py:231-240 (16-frame mel windows at host-computed starts)
  *   w2l_resample_sinc     audio.py:9-10 (librosa.core.load's sample-rate conversion: resampy 'kaiser_best' sinc interpolation)
@@ -652,6 +654,31 @@ int w2l_face_boxes_runs(void* stream, int n_seg, const w2l_box_segment* segs, co
 int w2l_face_boxes_stream_runs(void* stream, int n_seg, const w2l_box_stream_segment* segs_host, const w2l_box_stream_segment* segs,
                                const int32_t* rects, const int32_t* flags, int n_rows, int32_t* carry, int n_slots, int top, int bottom,
                                int left, int right, int T, int hold, int32_t* boxes, int32_t* valid, int n_out, int32_t* status);
+
+/* The span rule for FINISHED clips (opt-in `track_spans`; what the real-video scorer needs, not the reference's
+ * code: evaluation/scores_LSE/calculate_scores_real_videos.py leaves it to syncnet_python's run_pipeline.py): the stretches of a
+ * segment in which the followed face is present.  Where the hold above looks back, this rule looks forward to the next detection,
+ * so a live stream cannot use it.  Over w2l_face_boxes_segments' table (with `scene_cuts` a segment is a shot; its H and W are
+ * not read) and the arenas rects [n_rows][4] = (x1, y1, x2, y2), flags [n_rows] that w2l_s3fd_first_rect or
+ * w2l_face_track_segments fill, integers only, per segment of n rows:
+ *   - a row flagged 1 is DETECTED.  For detected rows p < q with no detected row between them and 2 <= q - p <= bridge + 1 every
+ *     row p < i < q is BRIDGED: each coordinate is floor((r_p * (q - i) + r_q * (i - p)) / (q - p)) in int64.  Every other row -
+ *     before the first detection, after the last one, inside a longer miss - is a gap.
+ *   - a SPAN is a maximal sequence of detected and bridged rows; it begins and ends on a detected row.  With L its length and
+ *     sw = sum(x2 - x1), sh = sum(y2 - y1) over its rects (int64) it is KEPT iff L >= min_len and max(sw, sh) >= min_size * L.
+ *   - rects_out / flags_out (the format of the inputs): the rows of kept spans have flag 1 and the detected or bridged rect, every
+ *     other row flag 0 and zeros.  w2l_face_boxes_runs with hold 0 finishes them as they are: pads, clipping, smoothing per span.
+ *   - spans [n_rows][4]: the t-th kept span of segment k, in order, is row row0 + t = (its first row counted from the segment's
+ *     first, L, its number of detected rows, 0); the segment's span rows from the kept count on are zeros.
+ * status [n_seg][2]: (0, number of kept spans); (2, row) when a row is flagged neither 0 nor 1 - the first such row; rects_out and
+ * flags_out of the segment are then copies of the input, so that the finish reports the same row, and its span rows are not
+ * written; (3, 0) for a segment with rows outside [0, n_rows) - nothing of it is read or written.  n <= 0: (0, 0), nothing else
+ * touched.  A segment writes its own rows of the three output arenas and its own status only; the outputs must not overlap the
+ * inputs.  Refused: a NULL pointer, n_seg < 1, n_rows < 0, bridge outside 0..250, min_len outside 1..2^30, min_size outside
+ * 0..32767, a table, rects, rects_out or spans that is not 16-byte aligned. */
+int w2l_face_spans_segments(void* stream, int n_seg, const w2l_box_segment* segs, const int32_t* rects, const int32_t* flags, int n_rows,
+                            int bridge, int min_len, int min_size, int32_t* rects_out, int32_t* flags_out, int32_t* spans,
+                            int32_t* status);
 
 /* Scene-cut detection (opt-in `scene_cuts`; not the reference's behaviour, which treats a clip as one take): where
  * the shots of a clip are, decided on the device from the frames the detector reads.  A shot then is a segment of the track and of

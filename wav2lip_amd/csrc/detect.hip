@@ -823,6 +823,119 @@ __global__ __launch_bounds__(64) void face_boxes_stream_runs_kernel(const BoxStr
     }
 }
 
+// ---- the span rule for finished clips (opt-in `track_spans`): which rows of a segment a scorer may see.  Unlike the
+// hold it looks FORWARD: a miss between two detections p < q with q - p <= bridge + 1 is interpolated, anything else is a gap, and a
+// maximal sequence of detected and bridged rows - a span, which begins and ends on a detection - is kept iff it has min_len rows and
+// a mean size (the larger of the width and height sums) of min_size.  The outputs have the format of the inputs, so
+// face_boxes_runs_kernel<false> with hold 0 finishes them.
+// One wave per segment walks the rows in chunks of 64.  A ballot gives the chunk's detections; a lane's last detection at or before
+// its row is the highest such bit at or below the lane, else the carried one, and its next one the lowest bit at or above, else the
+// first detection behind the chunk (at most bridge + 1 <= 251 rows past the chunk's last row: up to four more ballots on the flags).
+// Every row goes out at once as if its span were kept; the spans that END in the chunk (its last row is here; the first detection
+// behind the chunk says whether the last row's span goes on) are then decided from the carried length, detection count and sums,
+// and the rows of a dropped one - in this chunk and the ones before it - are zeroed again, behind a fence: other lanes wrote them.
+// Span rows are written once, in order, by lane 0.
+constexpr int kSpanMaxBridge = 250, kSpanMaxSize = 32767, kSpanMaxLen = 1 << 30;
+constexpr int kSpanReachChunks = 4;                      // 64 * 4 rows behind a chunk cover bridge + 1 rows behind its last row
+static_assert(64 * kSpanReachChunks >= kSpanMaxBridge + 1, "the next detection is looked for this far");
+
+__device__ __forceinline__ long long wave_sum(long long v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ long long floor_div(long long a, long long b) {     // b > 0
+    const long long q = a / b;
+    return (a % b != 0 && a < 0) ? q - 1 : q;
+}
+
+__global__ __launch_bounds__(64) void face_spans_segments_kernel(const BoxSeg* __restrict__ segs, const int* rects, const int* flags,
+                                                                 int n_rows, int bridge, int min_len, int min_size, int* rects_out,
+                                                                 int* flags_out, int* spans, int* __restrict__ status) {
+    const int lane = threadIdx.x;
+    const BoxSeg s = segs[blockIdx.x];
+    int* st = status + 2 * (long long)blockIdx.x;
+    if (s.n <= 0 || s.row0 < 0 || (long long)s.row0 + s.n > n_rows) {       // uniform: a segment outside the arenas is not followed
+        if (lane == 0) { st[0] = s.n <= 0 ? 0 : kBoxStreamBadSegment; st[1] = 0; }
+        return;
+    }
+    const long long n = s.n;
+    const int* fl = flags + s.row0;
+    const int4* rc = reinterpret_cast<const int4*>(rects) + s.row0;
+    int* fo = flags_out + s.row0;
+    int4* ro = reinterpret_cast<int4*>(rects_out) + s.row0;
+    int4* sp = reinterpret_cast<int4*>(spans) + s.row0;
+    int host, none;
+    first_unfound_rows(fl, s.n, &host, &none);
+    if (host != 0x7fffffff) {                            // uniform: left to the host, the finish will report the same row
+        for (long long i = lane; i < n; i += 64) { fo[i] = fl[i]; ro[i] = rc[i]; }
+        if (lane == 0) { st[0] = 2; st[1] = host; }
+        return;
+    }
+    const unsigned long long below = (1ull << lane) - 1ull, upto = below | (1ull << lane);
+    long long p_last = -1, nxt = -1;                     // the last detection before the chunk, the first one behind it (-1: none)
+    long long a = 0, L = 0, nd = 0, sw = 0, sh = 0;      // the span that is open at the chunk's start: first row, rows, detections, sums
+    bool open = false;
+    int kept = 0;
+    for (long long g0 = 0; g0 < n; g0 += 64) {
+        const long long i = g0 + lane;
+        const bool det = i < n && fl[i] == kRectFound;
+        const unsigned long long dm = __ballot(det);
+        if (nxt < g0 + 64) {                             // uniform; a detection found earlier that still lies behind the chunk stands
+            nxt = -1;
+            for (int j = 1; j <= kSpanReachChunks && nxt < 0; ++j) {
+                const long long r = g0 + 64ll * j + lane;
+                const unsigned long long m = __ballot(r < n && fl[r] == kRectFound);
+                if (m != 0ull) nxt = g0 + 64ll * j + __ffsll((long long)m) - 1;
+            }
+        }
+        const unsigned long long lo = dm & upto, hi = dm & ~below;
+        const long long p = lo != 0ull ? g0 + 63 - __clzll((long long)lo) : p_last;
+        const long long q = hi != 0ull ? g0 + __ffsll((long long)hi) - 1 : nxt;
+        const bool in = i < n && p >= 0 && q >= 0 && q - p <= (long long)bridge + 1;
+        int4 r = make_int4(0, 0, 0, 0);
+        if (det) r = rc[i];
+        else if (in) {                                   // p < i < q, 2 <= q - p <= 251: the products stay below 2^39 in magnitude
+            const int4 rp = rc[p], rq = rc[q];
+            const long long wp = q - i, wq = i - p, d = q - p;
+            r.x = (int)floor_div(rp.x * wp + rq.x * wq, d);
+            r.y = (int)floor_div(rp.y * wp + rq.y * wq, d);
+            r.z = (int)floor_div(rp.z * wp + rq.z * wq, d);
+            r.w = (int)floor_div(rp.w * wp + rq.w * wq, d);
+        }
+        if (i < n) { fo[i] = in; ro[i] = r; }
+        if (dm != 0ull) p_last = g0 + 63 - __clzll((long long)dm);
+        unsigned long long im = __ballot(in);
+        // the span of the chunk's last row goes on iff the first detection behind the chunk is within reach of the last one so far
+        const bool goes_on = (im >> 63) != 0ull && nxt >= 0 && nxt - p_last <= (long long)bridge + 1;
+        while (im != 0ull) {                             // uniform: the chunk's runs of rows that are in a span, in order
+            const int b0 = __ffsll((long long)im) - 1;
+            const unsigned long long from = ~((1ull << b0) - 1ull), gaps = ~im & from;
+            const int b1 = gaps != 0ull ? __ffsll((long long)gaps) - 1 : 64;
+            const unsigned long long run = from & (b1 == 64 ? ~0ull : (1ull << b1) - 1ull);
+            const bool mine = ((run >> lane) & 1ull) != 0ull;
+            const long long rw = wave_sum(mine ? (long long)r.z - r.x : 0ll), rh = wave_sum(mine ? (long long)r.w - r.y : 0ll);
+            if (!(open && b0 == 0)) { a = g0 + b0; L = nd = sw = sh = 0; }
+            L += b1 - b0;
+            nd += __popcll(dm & run);
+            sw += rw;
+            sh += rh;
+            open = b1 == 64 && goes_on;
+            if (!open) {                                 // the span [a, a + L) ends here
+                if (L >= min_len && max(sw, sh) >= (long long)min_size * L) {
+                    if (lane == 0) sp[kept] = make_int4((int)a, (int)L, (int)nd, 0);
+                    ++kept;
+                } else {
+                    __threadfence();                     // the rows went out from other lanes, in this chunk and before
+                    for (long long j = a + lane; j < a + L; j += 64) { fo[j] = 0; ro[j] = make_int4(0, 0, 0, 0); }
+                }
+            }
+            im &= ~run;
+        }
+    }
+    for (long long j = kept + lane; j < n; j += 64) sp[j] = make_int4(0, 0, 0, 0);
+    if (lane == 0) { st[0] = 0; st[1] = kept; }
+}
+
 constexpr int kPackRowsGridCap = 1024;        // workgroups per image of the row-table packs, full size and reduced
 
 template <class S>
@@ -1109,6 +1222,23 @@ int w2l_face_boxes_runs(void* stream, int n_seg, const w2l_box_segment* segs, co
     hipLaunchKernelGGL(face_boxes_runs_kernel<false>, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const BoxSeg*>(segs), rects, flags, n_rows, top, bottom, left, right, T, hold, boxes, valid,
                        status);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_face_spans_segments(void* stream, int n_seg, const w2l_box_segment* segs, const int32_t* rects, const int32_t* flags, int n_rows,
+                            int bridge, int min_len, int min_size, int32_t* rects_out, int32_t* flags_out, int32_t* spans,
+                            int32_t* status) {
+    W2L_REQUIRE(segs && rects && flags && rects_out && flags_out && spans && status, "face_spans_segments: NULL argument");
+    W2L_REQUIRE(n_seg >= 1 && n_rows >= 0, "face_spans_segments: n_seg=%d must be at least 1 and n_rows=%d at least 0", n_seg, n_rows);
+    W2L_REQUIRE(bridge >= 0 && bridge <= kSpanMaxBridge, "face_spans_segments: bridge=%d outside 0..%d", bridge, kSpanMaxBridge);
+    W2L_REQUIRE(min_len >= 1 && min_len <= kSpanMaxLen, "face_spans_segments: min_len=%d outside 1..%d", min_len, kSpanMaxLen);
+    W2L_REQUIRE(min_size >= 0 && min_size <= kSpanMaxSize, "face_spans_segments: min_size=%d outside 0..%d", min_size, kSpanMaxSize);
+    W2L_REQUIRE(aligned16(segs, rects, rects_out) && aligned16(spans),
+                "face_spans_segments: the segment table, rects, rects_out and spans must be 16-byte aligned");
+    hipLaunchKernelGGL(face_spans_segments_kernel, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const BoxSeg*>(segs), rects, flags, n_rows, bridge, min_len, min_size, rects_out, flags_out,
+                       spans, status);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

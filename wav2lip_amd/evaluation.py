@@ -32,21 +32,22 @@ img_size = 96
 
 GROUP_BATCHES = 16   # lse_many closes a group of clips once it holds this many full batches of windows
 
-ScoreJob = collections.namedtuple("ScoreJob", "key faces mel")
+ScoreJob = collections.namedtuple("ScoreJob", "key faces mel first", defaults=(0,))
 ScoreJob.__doc__ = """one clip to score: `faces` uint8 [T,96,96,3] face crops (a device tensor or a host array), `mel` the device fp32
-[80,Tm] spectrogram (audio.melspectrogram_device)"""
+[80,Tm] spectrogram (audio.melspectrogram_device); `first` (default 0) the frame of the video the mel belongs to at which the
+crops start - a face span of a longer video (calculate_scores_real_videos.py) reads the mel columns of its own frames"""
 
 
-def sync_windows(frames_u8, mel, fps=25.):
+def sync_windows(frames_u8, mel, fps=25., first=0):
     """frames_u8: torch uint8 [T,96,96,3] generated crops (device); mel: torch float32 [80,Tm] (device).
     Returns (faces [n,15,48,96] float32 in [0,1], mels [n,1,80,16]) for every frame v with a full 5-frame and 16-column
-    window."""
+    window.  `first`: the crops start at this frame of the mel's video, so window v reads the columns of frame first + v."""
     T = frames_u8.shape[0]
     H = frames_u8.shape[1]
     x = frames_u8[:, H // 2:].permute(0, 3, 1, 2).float() / 255.           # [T,3,48,96]
     faces, mels = [], []
     for v in range(0, T - syncnet_T + 1):
-        s = int(80. * (v / float(fps)))
+        s = int(80. * ((first + v) / float(fps)))
         if s + mel_step > mel.shape[1]:
             break
         faces.append(x[v:v + syncnet_T].reshape(3 * syncnet_T, x.shape[2], x.shape[3]))
@@ -71,14 +72,15 @@ def lse_from_embeddings(face_emb, audio_emb, vshift=15):
 
 
 @torch.no_grad()
-def lse_like(syncnet, frames_u8, mel, fps=25., vshift=15, batch_size=64, precision="f32"):
+def lse_like(syncnet, frames_u8, mel, fps=25., vshift=15, batch_size=64, precision="f32", first=0):
     """scores of a generated clip under the in-tree SyncNet_color (eval mode): dict(offset, lse_c, lse_d, n).  `precision`: SyncNet
-    arithmetic, "f32" (default) or "bf16" (the opt-in bf16-storage plan; embeddings and scores stay fp32)"""
+    arithmetic, "f32" (default) or "bf16" (the opt-in bf16-storage plan; embeddings and scores stay fp32).  `first`: the frame of
+    the mel's video at which the crops start (`sync_windows`)"""
     kw = _precision_kw(precision)
     was_training = syncnet.training
     syncnet.eval()
     try:
-        faces, mels = sync_windows(frames_u8, mel, fps)
+        faces, mels = sync_windows(frames_u8, mel, fps, first)
         a_all, v_all = [], []
         for lo in range(0, faces.shape[0], batch_size):
             a, v = syncnet(mels[lo:lo + batch_size], faces[lo:lo + batch_size], **kw)
@@ -91,12 +93,12 @@ def lse_like(syncnet, frames_u8, mel, fps=25., vshift=15, batch_size=64, precisi
 
 
 # ---------------------------------------------------------------- many clips, shared SyncNet batches
-def sync_rows(T, Tm, fps=25.):
+def sync_rows(T, Tm, fps=25., first=0):
     """the (first frame v, first mel column) of every window `sync_windows` makes of T frames and Tm mel columns: the same
     expression and the same stop rule"""
     rows = []
     for v in range(0, T - syncnet_T + 1):
-        s = int(80. * (v / float(fps)))
+        s = int(80. * ((first + v) / float(fps)))
         if s + mel_step > Tm:
             break
         rows.append((v, s))
@@ -167,6 +169,14 @@ def _checked_job(job):
     return faces, mel.contiguous()
 
 
+def _checked_first(job):
+    """the `first` of a ScoreJob: a non-negative int; a ValueError names the job"""
+    first = job.first
+    if isinstance(first, bool) or not isinstance(first, (int, np.integer)) or first < 0:
+        raise ValueError("job %r: first must be a non-negative integer, got %r" % (job.key, first))
+    return int(first)
+
+
 @torch.no_grad()
 def lse_many(syncnet, jobs, fps=25., vshift=15, batch_size=128, sink=None, precision="f32"):
     """`lse_like` for every `ScoreJob` of the iterable `jobs` (consumed lazily), the windows of successive clips packed into
@@ -176,7 +186,8 @@ def lse_many(syncnet, jobs, fps=25., vshift=15, batch_size=128, sink=None, preci
     embedded, w2l_lse_score_segments scores all its clips in one launch, one copy brings the scores back, and the group is
     released: the memory alive is one group plus the job being read.  Results arrive in job order as
     dict(key, offset, lse_c, lse_d, n, mdist) - at `sink(result)`, or in the returned list.  A clip without one full window
-    gives n = 0 and None for the rest, and takes part in no launch.  The model runs in eval mode and is put back afterwards.
+    gives n = 0 and None for the rest, and takes part in no launch.  A job's `first` places its windows at the mel columns of the
+    frames first, first + 1, ... of its video.  The model runs in eval mode and is put back afterwards.
     `precision`: SyncNet arithmetic, "f32" (default) or "bf16" (`SyncNet_color.embed_rows(..., precision="bf16")`)."""
     _precision_kw(precision)
     if batch_size < 1:
@@ -208,7 +219,7 @@ def lse_many(syncnet, jobs, fps=25., vshift=15, batch_size=128, sink=None, preci
     try:
         for job in jobs:
             faces, mel = _checked_job(job)
-            rows = sync_rows(faces.shape[0], mel.shape[1], fps)
+            rows = sync_rows(faces.shape[0], mel.shape[1], fps, _checked_first(job))
             group.append((job.key, faces if rows else None, mel if rows else None, rows))
             del job, faces, mel
             windows += len(rows)

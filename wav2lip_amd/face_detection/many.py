@@ -28,6 +28,10 @@ With `scene_cuts=...` (opt-in) ONE w2l_frame_hist_rows launch read
 w2l_scene_cuts launch over the clip table flags the frames that start a shot; the flags come back in a small copy of their own,
 queued before the detector batches and waited for after them, and the host then writes one segment per SHOT for the track and the
 finish, which run as they are (`face_detection/scene.py`).
+
+With `track_spans=...` (opt-in) ONE w2l_face_spans_segments launch sits between the track and the finish: it bridges
+short misses, ends a span at its last detection and drops short or small spans, and w2l_face_boxes_runs with hold 0 finishes what
+it leaves.  Its span table rides in the group's one copy back (`face_detection/spans.py`).
 """
 import collections
 
@@ -147,6 +151,15 @@ class RunBoxes:
         return (self[i] for i in range(len(self)))
 
 
+class SpanBoxes(RunBoxes):
+    """what `detect_many(..., track_spans=...)` yields for a clip: a `RunBoxes` whose boxed frames are those of the kept face spans,
+    with `.spans` the [(a, b)] frame ranges of the spans, in order (a span never crosses a shot)"""
+
+    def __init__(self, boxes, valid, spans):
+        RunBoxes.__init__(self, boxes, valid)
+        self.spans = [(int(a), int(b)) for a, b in spans]
+
+
 def _checked(job):
     """a DetectJob as a _Clip: frames a contiguous uint8 [T,H,W,3] tensor or a list of contiguous uint8 [H,W,3] arrays of one shape;
     a ValueError names the job"""
@@ -210,12 +223,17 @@ def track_rows(n_seg, segs, arenas, track, status, state=None):
 class BoxOut:
     """the one int32 buffer a finish writes and one copy brings back: boxes [n_boxes][4], with a hold valid [n_boxes], status
     [n_seg][2], with a track its status words [n_seg] - in that order.  `buffer` is the device tensor; `boxes`, `valid` (None
-    without a hold), `status` and `track_status` (empty without a track) are flat views of it."""
+    without a hold), `status` and `track_status` (empty without a track) are flat views of it.  With `spans` (w2l_face_spans_segments'
+    outputs ride in the same copy) three more parts follow: up to 3 words that bring the next one to a 16-byte boundary, `span_rows`
+    [n_boxes][4] and `span_status` [n_seg][2]."""
 
-    def __init__(self, n_boxes, n_seg, hold, track, device):
+    def __init__(self, n_boxes, n_seg, hold, track, device, spans=False):
         self.sizes = (4 * n_boxes, n_boxes if hold else None, 2 * n_seg, n_seg if track else 0)
+        if spans:
+            self.sizes += (-sum(n or 0 for n in self.sizes) % 4, 4 * n_boxes, 2 * n_seg)
         self.buffer = torch.empty(sum(n or 0 for n in self.sizes), dtype=torch.int32, device=device)
-        self.boxes, self.valid, self.status, self.track_status = self._parts(self.buffer)
+        self.boxes, self.valid, self.status, self.track_status = self._parts(self.buffer)[:4]
+        self.span_rows, self.span_status = self._parts(self.buffer)[5:] if spans else (None, None)
 
     def _parts(self, flat):
         ends = np.cumsum([n or 0 for n in self.sizes]).tolist()
@@ -229,11 +247,16 @@ class BoxOut:
     def split(self, host, of="clip"):
         """the parts of the buffer's host copy (numpy int32): (boxes [n_boxes,4], valid [n_boxes] or None, status [n_seg,2], track
         status [n_seg] or empty); the status words of w2l_face_track_segments are all 0 for a table built here"""
-        boxes, valid, status, track_status = self._parts(host)
+        boxes, valid, status, track_status = self._parts(host)[:4]
         if track_status.any():
             raise AssertionError("w2l_face_track_segments did not follow a %s's segment%s"
                                  % (of, " (status %s)" % track_status.tolist() if of == "clip" else ""))
         return boxes.reshape(-1, 4), valid, status.reshape(-1, 2), track_status
+
+    def split_spans(self, host):
+        """the span parts of the buffer's host copy: (span rows [n_boxes,4], span status [n_seg,2])"""
+        span_rows, span_status = self._parts(host)[5:]
+        return span_rows.reshape(-1, 4), span_status.reshape(-1, 2)
 
 
 def _finish_segments(n_seg, segs, rects, flags, pads, T, boxes, status):
@@ -265,14 +288,14 @@ def _fold_shot_status(shot_status, shots_of):
     return out
 
 
-def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None, scene=None):
+def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None, scene=None, spans=None):
     """One group on the device.  clips: _Clips of one frame shape, each with at least one frame.  Returns numpy (boxes int32 [R,4]
     in (y1, y2, x1, x2) order, rows in clip order; status int32 [clips,2]); with `hold` (the pass-through rule) a third array,
     valid int32 [R], comes between them - still one launch and one copy back.  With `track` (a FaceTrack) the batches leave
     candidates and one more launch, before the finish, chooses the rect of every frame; its status words come back in the same
     copy and are all 0 (the table is built here).  With `scene` (a SceneCuts) the signature and the cut launch run first, their R
     flags come back while the detector batches run, and the track and the finish get one segment per shot; the status returned is
-    still per clip (`_fold_shot_status`)."""
+    still per clip (`_fold_shot_status`).  With `spans` (a TrackSpans, never with `hold`) the group ends in `_finish_spans`."""
     dev = torch.device(detector.device)
     H, W = clips[0].H, clips[0].W
     R = sum(c.n for c in clips)
@@ -318,6 +341,8 @@ def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None, s
             r += c.n
         st2.upload()
         seg_dev, track_dev = st2.tensor(segments2), None if tracks2 is None else st2.tensor(tracks2)
+    if spans is not None:
+        return _finish_spans(n_seg, seg_dev, track_dev, arenas, track, spans, R, pads, T, dev, [c.n for c in clips], shots_of)
     out = BoxOut(R, n_seg, hold is not None, track is not None, dev)
     if track is not None:
         track_rows(n_seg, track_dev, arenas, track, out.track_status)
@@ -330,6 +355,37 @@ def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None, s
     if shots_of is not None:
         status = _fold_shot_status(status, shots_of)
     return (boxes, status) if hold is None else (boxes, valid, status)
+
+
+def _finish_spans(n_seg, seg_dev, track_dev, arenas, track, spans, R, pads, T, dev, clip_lengths, shots_of):
+    """the end of `_detect_group` under `track_spans`: the track launch (if any), w2l_face_spans_segments over the same segments,
+    w2l_face_boxes_runs with hold 0 on its outputs, and the group's one copy back, which also brings the span table.  Returns numpy
+    (boxes [R,4], valid [R], status [clips,2], [the clip's kept spans [(a, b)] per clip])."""
+    from .spans import span_segments
+    out = BoxOut(R, n_seg, True, track is not None, dev, spans=True)
+    if track is not None:
+        track_rows(n_seg, track_dev, arenas, track, out.track_status)
+    rects = torch.empty((R, 4), dtype=torch.int32, device=dev)
+    flags = torch.empty((R,), dtype=torch.int32, device=dev)
+    span_segments(n_seg, seg_dev, arenas.rects, arenas.flags, R, spans, rects, flags, out.span_rows, out.span_status)
+    _finish_runs(n_seg, seg_dev, rects, flags, R, pads, T, 0, out.boxes, out.valid, out.status)
+    host = out.buffer.cpu().numpy()
+    boxes, valid, status, _ = out.split(host)
+    span_rows, span_status = out.split_spans(host)
+    if shots_of is None:
+        shots_of = [[(0, n)] for n in clip_lengths]
+    if (span_status[:, 0] == 3).any() or (status[:, 0] == 3).any():
+        raise AssertionError("w2l_face_spans_segments did not follow a clip's segment (status %s)" % span_status.tolist())
+    kept, k, r = [], 0, 0
+    for n, shots in zip(clip_lengths, shots_of):
+        mine = []
+        for a, _ in shots:                                  # segment k holds the rows from r + a on
+            if span_status[k][0] == 0:
+                mine += [(a + int(f), a + int(f) + int(L)) for f, L, _, _ in span_rows[r + a:r + a + int(span_status[k][1])]]
+            k += 1
+        kept.append(mine)
+        r += n
+    return boxes, valid, _fold_shot_status(status, shots_of), kept
 
 
 def _queue_cuts(addresses, segments, n_clips, R, H, W, scene, dev):
@@ -348,12 +404,27 @@ def _queue_cuts(addresses, segments, n_clips, R, H, W, scene, dev):
     return buf, host, ready
 
 
-def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None, scene=None):
+def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None, scene=None, spans=None):
     """one clip alone through `inference.face_detect` (batch by batch uploads, the host rules): (key, boxes, error).  `scene` is passed
     on to it; where `face_detect`'s own finish does not fit (a hold, or a window other than 5) the same host rules run per shot
-    here, on `inference._shot_rects`."""
+    here, on `inference._shot_rects`.  With `spans` the clip's rects go through `spans.host_spans` per shot and every kept span is
+    finished as a run."""
     from .. import inference
     frames = list(clip.frames.cpu().numpy()) if isinstance(clip.frames, torch.Tensor) else list(clip.frames)
+    if spans is not None:
+        from .spans import host_spans_shots
+        try:
+            if scene is not None:
+                rects, shots = inference._shot_rects(frames, detector, batch_size, track, scene)
+            elif track is not None:
+                rects, shots = inference._track_rects(frames, detector, batch_size, track), [(0, clip.n)]
+            else:
+                rects, shots = inference._detect_rects(frames, detector, batch_size), [(0, clip.n)]
+            filled, kept = host_spans_shots(rects, shots, spans)
+            boxes, valid = host_boxes_shots(filled, shots, clip.H, clip.W, pads, T, 0)
+            return clip.key, SpanBoxes(boxes, valid, kept), None
+        except (ValueError, OverflowError) as e:
+            return clip.key, None, str(e)
     if scene is not None:
         try:
             if hold is None and T in (0, 5):
@@ -390,7 +461,7 @@ def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None, scene=
 
 
 def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_batches=16, max_group_bytes=1 << 30, no_face_hold=None,
-                face_track=None, scene_cuts=None):
+                face_track=None, scene_cuts=None, track_spans=None):
     """`inference.face_detect(frames, detector, pads, nosmooth=(T == 0))` for every `DetectJob` of the iterable `jobs`, the frames
     of successive clips packed into detector batches of exactly `batch_size`.  A generator: jobs are consumed lazily and one
     `(key, boxes, error)` comes out per job, in job order - `boxes` the int array [n,4] of (y1, y2, x1, x2) `face_detect` returns
@@ -422,16 +493,29 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
     histogram of a frame differs from the previous frame's by more than the threshold, and every shot is tracked, held, padded,
     clipped and smoothed as a clip of its own (not the reference's behaviour), exactly as
     `face_detect(scene_cuts=...)` does for the clip alone.  A job still gets one result: in the strict mode a frame without a
-    face in any shot is the clip's error."""
+    face in any shot is the clip's error.
+
+    `track_spans`: None (default), or a `spans.TrackSpans`: for finished clips that a scorer reads (not the reference's
+    code).  Misses of up to `bridge` frames between two detections are interpolated, a longer miss ends the span at the last
+    detection, and spans shorter than `min_len` frames or smaller than `min_size` pixels are dropped; every kept span is padded,
+    clipped and smoothed as a clip of its own.  `boxes` is then a `SpanBoxes`: a `RunBoxes` over the frames of kept spans with
+    `.spans` = [(a, b)], the spans as frame ranges of the clip in order; with `scene_cuts` the rule runs per shot.  Together with
+    `no_face_hold` - the other answer to the same question - it is a ValueError."""
     from ..inference import halving
     from .scene import check_scene
+    from .spans import check_spans
     from .track import check_track
     hold = check_hold(no_face_hold)
     track = check_track(face_track)
     scene = check_scene(scene_cuts)
+    spans = check_spans(track_spans)
+    if spans is not None and hold is not None:
+        raise ValueError("track_spans and no_face_hold are two answers to the same question: give one of them")
     tkw = {} if track is None else {"track": track}    # the default path calls its helpers with the arguments it always did
     if scene is not None:
         tkw["scene"] = scene
+    if spans is not None:
+        tkw["spans"] = spans
     if batch_size < 1 or group_batches < 1:
         raise ValueError("batch_size and group_batches must be at least 1")
     if not 0 <= int(T) <= MAX_T:
@@ -474,7 +558,7 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
         if not group:
             continue
         clips = [c for c in group if c.n]
-        boxes = status = valid = None
+        boxes = status = valid = kept = None
 
         def run_group(size):
             nonlocal batch_size
@@ -483,15 +567,21 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
 
         if clips:
             res = halving(run_group, batch_size)
-            boxes, valid, status = res[0], res[1] if hold is not None else None, res[-1]
+            if spans is not None:
+                boxes, valid, status, kept = res
+            else:
+                boxes, valid, status = res[0], res[1] if hold is not None else None, res[-1]
         results, row, k = [], 0, 0
         for c in group:
             if c.n == 0:
                 empty = np.zeros((0, 4), np.int64)
-                results.append((c.key, empty if hold is None else RunBoxes(empty, []), None))
+                results.append((c.key, SpanBoxes(empty, [], []) if spans is not None else empty if hold is None else RunBoxes(empty, []),
+                                None))
                 continue
             code = int(status[k][0])                       # status[k][1]: the frame that decided it
-            if code == 0 and hold is not None:
+            if code == 0 and spans is not None:
+                results.append((c.key, SpanBoxes(boxes[row:row + c.n], valid[row:row + c.n] != 0, kept[k]), None))
+            elif code == 0 and hold is not None:
                 results.append((c.key, RunBoxes(boxes[row:row + c.n], valid[row:row + c.n] != 0), None))
             elif code == 0:
                 results.append((c.key, boxes[row:row + c.n].astype(np.int64), None))
