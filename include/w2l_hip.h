@@ -49,6 +49,8 @@
  *                         reference's: `no_face_hold`)
  *   w2l_face_spans_segments  the face tracks evaluation/scores_LSE/calculate_scores_real_videos.py scores: misses bridged by
  *                         interpolation, short tracks dropped (opt-in, not the reference's code: `track_spans`)
+ *   w2l_face_tracks_all_segments  the same file's :38-40, one line per face track: every face of a shot followed at once, where
+ *                         w2l_face_track_segments follows one (opt-in: `all_faces`)
  *   w2l_melspectrogram    audio.py:45-51 (preemphasis, STFT, mel basis, dB, normalise)
  *   w2l_mel_gather        inference.py:231-240 (16-frame mel windows at host-computed starts)
  *   w2l_resample_sinc     audio.py:9-10 (librosa.core.load's sample-rate conversion: resampy 'kaiser_best' sinc interpolation)
@@ -679,6 +681,38 @@ int w2l_face_boxes_stream_runs(void* stream, int n_seg, const w2l_box_stream_seg
 int w2l_face_spans_segments(void* stream, int n_seg, const w2l_box_segment* segs, const int32_t* rects, const int32_t* flags, int n_rows,
                             int bridge, int min_len, int min_size, int32_t* rects_out, int32_t* flags_out, int32_t* spans,
                             int32_t* status);
+
+/* Every face of a segment (opt-in `all_faces`; what syncnet_python's run_pipeline.py does before
+ * evaluation/scores_LSE/calculate_scores_real_videos.py:38-40 prints a line per face track): w2l_face_track_segments' rule with F
+ * track slots at once.  Over w2l_face_boxes_segments' table (with `scene_cuts` a segment is a shot; H and W are not read) and the
+ * arenas cands [n_rows][K][4], ncand [n_rows], cflags [n_rows] that w2l_s3fd_top_rects fills (coordinates in 0..32767, so every
+ * product is exact in int64), integers only, per segment of n rows.  F in 1..16 slots, K in 1..16, L in 0..250 missed frames
+ * tolerated, q in 1..256 (min IoU q/256).  inter, union and OVERLAPS are w2l_face_track_segments': no + 1, inter > 0 and
+ * inter * 256 >= q * union.  The state is F slots of (ref rect, alive, missed), all free at the segment's start; frames in order:
+ *   1. a frame flagged neither 0 nor 1: all F rows of the frame get flag 2 and zeros; the state is left alone, missed not counted.
+ *   2. m = ncand clipped to [0, K] for a frame flagged 1, else 0.
+ *   3. matching, best pair first: among the pairs (alive slot s, candidate c < m) that overlap, the pair of the largest IoU
+ *      (inter_a * union_b > inter_b * union_a in int64; ties to the lower slot, then to the lower candidate) is matched - the
+ *      slot's ref becomes the candidate, missed = 0 - and slot and candidate leave the contest; again until no overlapping pair
+ *      is left.  (Not slot order: two faces whose boxes cross get the nearer box each.)
+ *   4. misses: every alive slot that was not matched does missed += 1 and is freed once missed > L.
+ *   5. seeds: the unclaimed candidates, in index order, each take the lowest free slot - one freed in step 4 of this frame
+ *      counts as free: ref = candidate, alive, missed = 0, started += 1.  Without a free slot the candidate is dropped, dropped += 1.
+ *   6. slot t's row of the frame: flag 1 and the slot's rect if it was matched or seeded in this frame, else flag 0 and zeros.
+ * rects_out [F][n_rows][4] and flags_out [F][n_rows]: slot t's arena is the t-th block of n_rows rows, in w2l_s3fd_first_rect's
+ * format, so w2l_face_spans_segments and the box finishes take a table of F * n_seg segments (row0 + t * n_rows) over them as
+ * they are.  With F = 1 slot 0 is w2l_face_track_segments with pick 0 and the same K, L, q, byte for byte.  Two tracks that use
+ * one slot one after the other are at least L rows of flag 0 apart - exactly L when the slot is seeded again in the frame that
+ * freed it, L + 1 or more otherwise - so a span rule with bridge < L never joins them, and one with bridge = L joins exactly the
+ * tracks of a slot that was freed and seeded in one frame.
+ * status [n_seg][4] = (code, started, dropped, the largest number of slots alive after a frame): code 0, or 3 for a segment
+ * whose rows leave [0, n_rows) or with n < 0 - (3, 0, 0, 0), nothing else of it is read or written.  n = 0: (0, 0, 0, 0).  A
+ * segment writes its own rows of the F arenas and its own status only; no atomics, bit-reproducible.  Refused: a NULL pointer,
+ * n_seg < 1, n_rows < 0, K, F, L or q outside their ranges, F * n_rows >= 2^29, a table, cands or rects_out that is not 16-byte
+ * aligned. */
+int w2l_face_tracks_all_segments(void* stream, int n_seg, const w2l_box_segment* segs, const int32_t* cands, const int32_t* ncand,
+                                 const int32_t* cflags, int n_rows, int K, int F, int L, int q, int32_t* rects_out, int32_t* flags_out,
+                                 int32_t* status);
 
 /* Scene-cut detection (opt-in `scene_cuts`; not the reference's behaviour, which treats a clip as one take): where
  * the shots of a clip are, decided on the device from the frames the detector reads.  A shot then is a segment of the track and of

@@ -2,7 +2,7 @@
 `for clip: inference.face_detect(frames, detector, ...)` over the same seeded clips.
 
     python tools/detect_bench.py [--clips 200] [--alternations 5] [--batch 16] [--precision f32] [--seed 0] [--face_track PICK]
-                                 [--scene_cuts THRESH]
+                                 [--scene_cuts THRESH] [--all_faces F]
 
 The clips are those of tools/filelist_bench.py (160x160 frames, lengths uniform in 30..120, 16 distinct frames cycled), each frame
 with the saturated block of synthetic.filelist_frame pasted in so that the seeded S3FD (synthetic.s3fd_state_dict) finds a face;
@@ -24,7 +24,14 @@ With `--scene_cuts THRESH` (scene-cut detection) the two loops are
 `scene_cuts=THRESH` - "packed" and "packed_scene" - alternated the same way: what the signature launch over every frame, the cut
 launch and the small copy per group cost.  The seeded clips cycle 16 noise frames whose histograms are alike, so at 0.3 no cut
 fires on them and `boxes_that_differ` must be 0 (a clip without a cut is the feature switched off); the per-shot tables are built
-all the same.  Nothing here says anything about detection quality on real footage."""
+all the same.  Nothing here says anything about detection quality on real footage.
+
+With `--all_faces F` (every face of a shot) the two loops are the packed detector with `track_spans` alone
+(bridge 25, min_len 1) and with `all_faces=AllFaces(F)` as well - "packed_spans" and "packed_all_faces" - alternated the same way:
+what the candidate launch per batch in place of the rect launch, the walk over F slots and the span and run launches over F
+times the rows cost.  `boxes_that_differ` compares the first path's boxes with the boxes of the second path's slot-0 tracks on the
+frames both have.  `--track_kernel_ms` instead times the new launch alone over HIP events: one segment of 4096 frames with four
+faces that drift, F = 4, K = 8 - the serial walk's worst case - alternated with w2l_face_track_segments over the same arenas."""
 import argparse
 import json
 import os
@@ -91,6 +98,75 @@ def run_loop(det, clips, batch):
     return res, time.perf_counter() - t0
 
 
+def span_boxes(result):
+    """(boxes per clip, seconds) of a `track_spans` pass: the box arrays, zeros outside kept spans"""
+    res, t = result
+    return [r.boxes for r in res], t
+
+
+def slot0(result):
+    """(boxes per clip, seconds) of an `all_faces` pass in the shape of a `track_spans` pass: the boxes of the slot-0 tracks"""
+    res, t = result
+    out = []
+    for r in res:
+        boxes = np.zeros((len(r), 4), np.int64)
+        for tr in r.tracks:
+            if tr.slot == 0:
+                boxes[tr.a:tr.b] = tr.boxes
+        out.append(boxes)
+    return out, t
+
+
+def track_kernel_ms(dev, alternations, n=4096, F=4, K=8, L=25, q=64):
+    """milliseconds of w2l_face_tracks_all_segments and of w2l_face_track_segments over one segment of n frames with four drifting
+    faces whose order changes from frame to frame, each launch between two HIP events, the two alternated"""
+    from wav2lip_amd._lib import BOX_SEGMENT, TRACK_SEGMENT, check, current_stream, load, ptr
+    rng = np.random.default_rng(0)
+    cands = np.zeros((n, K, 4), np.int32)
+    base = np.array([(40 + 200 * j, 50, 140 + 200 * j, 170) for j in range(4)], np.int32)
+    for i in range(n):
+        d = (i % 7) - 3
+        cands[i, :4] = (base + np.array([d, 0, d, 0], np.int32))[rng.permutation(4)]
+    c = torch.from_numpy(cands).to(dev)
+    nc, cf = torch.full((n,), 4, dtype=torch.int32, device=dev), torch.ones((n,), dtype=torch.int32, device=dev)
+    seg = np.zeros(1, BOX_SEGMENT)
+    seg[0] = (0, n, 0, 0)
+    trk = np.zeros(1, TRACK_SEGMENT)
+    trk[0] = (0, n, -1, 0)
+    seg, trk = (torch.from_numpy(t.view(np.uint8)).to(dev) for t in (seg, trk))
+    rects, flags = torch.empty((F, n, 4), dtype=torch.int32, device=dev), torch.empty((F, n), dtype=torch.int32, device=dev)
+    status = torch.empty(4, dtype=torch.int32, device=dev)
+    lib = load()
+
+    def all_faces():
+        check(lib.w2l_face_tracks_all_segments(current_stream(), 1, ptr(seg), ptr(c), ptr(nc), ptr(cf), n, K, F, L, q, ptr(rects), ptr(flags),
+                                               ptr(status)), "face_tracks_all_segments")
+
+    def one_face():
+        check(lib.w2l_face_track_segments(current_stream(), 1, ptr(trk), ptr(c), ptr(nc), ptr(cf), n, K, 0, L, q, None, 0, ptr(rects),
+                                          ptr(flags), ptr(status)), "face_track_segments")
+
+    arms = {"all_faces_ms": all_faces, "one_face_ms": one_face}
+    ms = {k: [] for k in arms}
+    for rep in range(alternations + 1):                     # pass 0: warm-up
+        for name, fn in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if rep:
+                ms[name].append(e0.elapsed_time(e1))
+    all_faces()
+    st = status.cpu().tolist()
+    out = {"frames": n, "F": F, "K": K, "L": L, "q": q, "status": st, "alternations": alternations}
+    for name, v in ms.items():
+        out[name] = {"samples": [round(x, 4) for x in v], "median": round(float(np.median(v)), 4), "min": round(min(v), 4),
+                     "max": round(max(v), 4)}
+    out["us_per_frame_all_faces"] = round(1000 * out["all_faces_ms"]["median"] / n, 3)
+    print(json.dumps(out))
+
+
 def stats(v):
     return {"samples": [round(x, 1) for x in v], "median": round(float(np.median(v)), 1), "min": round(min(v), 1), "max": round(max(v), 1)}
 
@@ -106,9 +182,15 @@ def main(argv=None):
                     help="compare the packed detector without and with face_track=PICK instead of packed against per-clip")
     ap.add_argument("--scene_cuts", default=None, type=float, metavar="THRESH",
                     help="compare the packed detector without and with scene_cuts=THRESH instead of packed against per-clip")
+    ap.add_argument("--all_faces", default=None, type=int, metavar="F",
+                    help="compare the packed detector with track_spans alone and with all_faces=AllFaces(F) as well")
+    ap.add_argument("--track_kernel_ms", default=False, action="store_true",
+                    help="time w2l_face_tracks_all_segments alone (one segment of 4096 frames, four faces) and print one JSON line")
     a = ap.parse_args(argv)
-    if a.face_track is not None and a.scene_cuts is not None:
-        ap.error("--face_track and --scene_cuts are two comparisons: give one")
+    if sum(v is not None for v in (a.face_track, a.scene_cuts, a.all_faces)) > 1:
+        ap.error("--face_track, --scene_cuts and --all_faces are three comparisons: give one")
+    if a.track_kernel_ms:
+        return track_kernel_ms(torch.device("cuda", 0), a.alternations)
     dev = torch.device("cuda", 0)
     clips = clips_with_faces(a.clips, a.seed)
     frames = sum(len(c) for c in clips)
@@ -121,6 +203,13 @@ def main(argv=None):
     if a.scene_cuts is not None:
         out["scene_cuts"] = a.scene_cuts
         loops["packed_scene"] = (lambda det, clips, batch: run_packed(det, clips, batch, scene_cuts=a.scene_cuts), loops.pop("per_clip")[1])
+    if a.all_faces is not None:
+        out["all_faces"] = a.all_faces
+        spans = face_detection.TrackSpans(25, 1, 0)
+        faces = face_detection.AllFaces(a.all_faces)
+        loops = {"packed_spans": (lambda det, clips, batch: span_boxes(run_packed(det, clips, batch, track_spans=spans)), loops["packed"][1]),
+                 "packed_all_faces": (lambda det, clips, batch: slot0(run_packed(det, clips, batch, track_spans=spans, all_faces=faces)),
+                                      loops["per_clip"][1])}
     first, second = list(loops)
     res = {k: {"frames_per_s": [], "graph_builds": []} for k in loops}
     last = {}

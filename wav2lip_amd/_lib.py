@@ -234,6 +234,7 @@ SIGNATURES = {
     "w2l_face_boxes_stream": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "w2l_face_boxes_runs": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "w2l_face_spans_segments": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "w2l_face_tracks_all_segments": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "w2l_face_boxes_stream_runs": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "w2l_frame_hist_rows": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "w2l_scene_cuts": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),

@@ -12,15 +12,19 @@ Here `face_detection.detect_many(track_spans=...)` is that stage:
 with `--face_track` one face is followed through each, `w2l_face_spans_segments` turns the detections into face spans
 (`--num_failed_det`, `--min_track`, `--min_face_size`), and every kept span (a, b) is one `evaluation.ScoreJob` whose crops are
 frames a..b-1 and whose `first` is a, so its windows read the mel columns of its own frames.  All spans of all videos go through
-ONE `evaluation.lse_many` call.
+ONE `evaluation.lse_many` call.  With `--all_faces [--max_faces F]` every face in the picture is followed instead of
+one per shot - up to F at a time, `--face_track_cands` candidates per frame, `--face_track_iou` overlap, `--num_failed_det` missed
+frames tolerated - and every face track is a `ScoreJob` of its own: one line per face track of the video, as the reference's flow
+prints them.
 
 Output: stdout gets the reference's line per span (:40), `str(dist) + " " + str(conf)`, in video and span order and nothing else;
 `--scores_file PATH` appends the same lines (the .sh's all_scores.txt).  stderr names the videos that cannot be read or have no
-kept span, and the spans too short for one 5-frame / 16-column window.
+kept span, the spans too short for one 5-frame / 16-column window, and with `--all_faces` once per video the candidates that
+found no free track slot ("more than F faces: N candidates not followed").
 
 Differences and limits, stated plainly: the scorer is the in-tree `SyncNet_color` whose weights `--checkpoint_path` names in place
-of `--initial_model`, so absolute values are not the paper's; ONE face per shot is followed where run_pipeline.py tracks every face
-in the picture; the crops are the detector's box with `T = 5` mean smoothing, not run_pipeline.py's padded square with a median
+of `--initial_model`, so absolute values are not the paper's; without `--all_faces` ONE face per shot is followed where
+run_pipeline.py tracks every face in the picture, and with it at most `--max_faces` at a time; the crops are the detector's box with `T = 5` mean smoothing, not run_pipeline.py's padded square with a median
 filter; inputs are the AVIs of container.py with their own PCM track; `--data_dir` and `--reference` are accepted and unused
 (nothing is unpacked to disk).  The span defaults follow run_pipeline.py's published ones as far as they carry over and are
 choices, not measurements; the quality of the spans on real footage is unmeasured, and no throughput is claimed.
@@ -49,6 +53,7 @@ def build_parser():
 
 def build_cli_parser():
     """the reference's flags plus the .sh's loop and file, and what the in-tree detector and scorer need"""
+    from .face_detection.faces import add_faces_flags
     from .face_detection.spans import add_span_flags
     from .inference import add_det_scale_flag, add_scene_flag, add_track_flags
     p = build_parser()
@@ -65,6 +70,7 @@ def build_cli_parser():
     add_scene_flag(p)
     add_track_flags(p)
     add_span_flags(p)
+    add_faces_flags(p)
     return p
 
 
@@ -77,11 +83,13 @@ def span_jobs(args, videos, device, detector, skipped):
     videos (and "<name>#<t>" of the spans) it passes over"""
     from . import audio, face_detection
     from .evaluation import ScoreJob
+    from .face_detection.faces import faces_from_args, faces_kw
     from .face_detection.scene import scene_from_args, scene_kw
     from .face_detection.spans import spans_from_args
     from .face_detection.track import track_from_args, track_kw
     from .inference import validate_boxes
     spans = spans_from_args(args)
+    faces = faces_from_args(args)
     held = {}                            # name -> (wav, frames) of the clips read ahead of their boxes
 
     def skip(name, why, trace=None):
@@ -105,7 +113,7 @@ def span_jobs(args, videos, device, detector, skipped):
         for t, (a, b) in enumerate(kept):
             key = "{}#{}".format(name, t)
             try:
-                yield ScoreJob(key, face_crops(frames[a:b], boxes[a:b], device), mel, a)
+                yield ScoreJob(key, face_crops(frames[a:b], boxes[a:b] if faces is None else boxes[t], device), mel, a)
             except ValueError as e:                      # a box outside its frame
                 skip(key, str(e))
 
@@ -125,14 +133,19 @@ def span_jobs(args, videos, device, detector, skipped):
                 held[name] = got
                 yield face_detection.DetectJob(name, got[1])
 
-        kw = {**track_kw(track_from_args(args)), **scene_kw(scene_from_args(args))}
+        kw = {**(track_kw(track_from_args(args)) if faces is None else faces_kw(faces)), **scene_kw(scene_from_args(args))}
         for name, boxes, error in face_detection.detect_many(detector, inputs(), pads=(0, 0, 0, 0), T=5, batch_size=FACE_DET_BATCH_SIZE,
                                                              track_spans=spans, **kw):
             wav, frames = held.pop(name)
             if error is not None:
                 skip(name, error)
                 continue
-            yield from span_scores(name, wav, frames, boxes.boxes, boxes.spans)
+            if faces is None:
+                yield from span_scores(name, wav, frames, boxes.boxes, boxes.spans)
+                continue
+            if boxes.dropped:
+                sys.stderr.write("{}: more than {} faces: {} candidates not followed\n".format(name, faces.max_faces, boxes.dropped))
+            yield from span_scores(name, wav, frames, [t.boxes for t in boxes.tracks], [(t.a, t.b) for t in boxes.tracks])
 
 
 def main(argv=None, state_dict=None):
@@ -144,6 +157,10 @@ def main(argv=None, state_dict=None):
     args = cli_parser.parse_args(argv)
     if bool(args.videofile) == (args.data_root is not None):
         cli_parser.error("give one of --videofile FILE and --data_root DIR")
+    if args.all_faces and args.face_track is not None:
+        cli_parser.error("--all_faces follows every face and --face_track one: give one of them")
+    if args.all_faces and args.box is not None:
+        cli_parser.error("--box names the one face of every frame: --all_faces does not apply")
     device = torch.device("cuda", torch.cuda.current_device())
     model = SyncNet_color()
     model.load_state_dict(checkpoint.strip_module_prefix(checkpoint._load(args.checkpoint_path)["state_dict"]))

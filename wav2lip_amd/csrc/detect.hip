@@ -16,6 +16,8 @@
 //   w2l_s3fd_top_rects  sfd_detector.py:45 + api.py:61-77 for the first K kept boxes above 0.5 instead of d[0] alone (opt-in)
 //   w2l_face_track_segments  one of those candidates per frame, followed through a clip by overlap (opt-in; not the reference's
 //                       rule, which takes d[0] of every frame): rects and flags in w2l_s3fd_first_rect's format
+//   w2l_face_tracks_all_segments  every face of a segment followed at once in F track slots, best pair first (opt-in; what
+//                       run_pipeline.py does before calculate_scores_real_videos.py:38-40 scores every face track)
 //   w2l_face_boxes_segments  inference.py:59-66, :90-104 / gen_videos_from_filelist.py:35-42, :61-77  pads, clipping, temporal
 //                       smoothing and "no face" of many clips in one launch
 //   w2l_face_boxes_stream  the same finish for LIVE streams, tick by tick: a box is written once the T - 1 frames after it are there
@@ -543,6 +545,124 @@ __global__ __launch_bounds__(64) void face_track_segments_kernel(const TrackSeg*
     }
 }
 
+// ---- every face of a segment (opt-in `all_faces`): the same candidates, the same integer overlap and the same L,
+// but F track slots at once instead of one reference rect.  One wave per segment walks the frames in order.  Lane t < F owns slot
+// t - (ref rect, alive, missed) in its registers - and lane c < K holds candidate c; the next frame's candidates are loaded while
+// this one decides.  Per frame the refs and the candidates go through a few hundred bytes of LDS, from which the F * K <= 256
+// pairs (slot p / K, candidate p % K, pair p = lane + 64 j) take their inter and union, four per lane.  A greedy round is one
+// wave argmax over the pairs still in the contest - the largest IoU by the cross-multiplied int64 comparison, ties to the lower
+// key slot * 16 + candidate - and removes its slot and its candidate; the rounds end when no overlapping pair is left, after at
+// most min(alive, m) of them.  The masks of slots and candidates still in the contest are the same on every lane, so every branch
+// of the walk is uniform.  Then the misses, and the seeds: the i-th unclaimed candidate takes the i-th lowest free slot.
+constexpr int kFacesMaxSlots = 16;
+struct BoxSeg { int row0, n, H, W; };
+static_assert(sizeof(BoxSeg) == 16 && sizeof(w2l_box_segment) == 16, "w2l_box_segment is 16 bytes");
+
+__global__ __launch_bounds__(64) void face_tracks_all_segments_kernel(const BoxSeg* __restrict__ segs, const int* __restrict__ cands,
+                                                                      const int* __restrict__ ncand, const int* __restrict__ cflags,
+                                                                      int n_rows, int K, int F, int L, int q, int* __restrict__ rects_out,
+                                                                      int* __restrict__ flags_out, int* __restrict__ status) {
+    __shared__ i32x4 s_c[kTrackMaxCands];
+    __shared__ i32x4 s_ref[kFacesMaxSlots];
+    const int lane = threadIdx.x;
+    const BoxSeg s = segs[blockIdx.x];
+    int* st = status + (long long)blockIdx.x * 4;
+    if (s.n < 0 || s.row0 < 0 || (long long)s.row0 + s.n > n_rows) {       // uniform
+        if (lane < 4) st[lane] = lane == 0 ? kTrackBadSegment : 0;
+        return;
+    }
+    const bool mine = lane < K, owner = lane < F;
+    int ps[4], pc[4];                                       // the slot and the candidate of this lane's four pairs; -1: no pair
+    for (int j = 0; j < 4; ++j) {
+        const int p = lane + 64 * j;
+        ps[j] = p < F * K ? p / K : -1;
+        pc[j] = p < F * K ? p % K : -1;
+    }
+    i32x4 ref = {0, 0, 0, 0};
+    int alive = 0, missed = 0, started = 0, dropped = 0, peak = 0;
+    auto load = [&](int i, i32x4* c, int* nc, int* cf) {
+        const long long row = (long long)s.row0 + i;
+        *c = mine ? *reinterpret_cast<const i32x4*>(cands + (row * K + lane) * 4) : i32x4{0, 0, 0, 0};
+        *nc = ncand[row];
+        *cf = cflags[row];
+    };
+    i32x4 c_next = {0, 0, 0, 0};
+    int nc_next = 0, cf_next = kRectNone;
+    if (s.n > 0) load(0, &c_next, &nc_next, &cf_next);
+    for (int i = 0; i < s.n; ++i) {
+        const i32x4 c = c_next;
+        const int cf = cf_next;
+        const int m = cf == kRectFound ? min(max(nc_next, 0), K) : 0;
+        if (i + 1 < s.n) load(i + 1, &c_next, &nc_next, &cf_next);
+        const long long row = (long long)s.row0 + i;
+        int out_flag = kRectNone;
+        if (cf != kRectFound && cf != kRectNone) out_flag = kRectHost;      // uniform: the state is left alone
+        else {
+            __syncthreads();                                // the frame before has read its candidates
+            if (mine) s_c[lane] = c;
+            if (owner) s_ref[lane] = ref;
+            unsigned av_s = (unsigned)__ballot(owner && alive);             // slots and candidates still in the contest
+            unsigned av_c = (1u << m) - 1u;
+            __syncthreads();
+            long long inter[4], uni[4];
+            for (int j = 0; j < 4; ++j) {
+                inter[j] = 0;
+                uni[j] = 1;
+                if (ps[j] >= 0 && ((av_s >> ps[j]) & 1u) && pc[j] < m) {
+                    const i32x4 a = s_c[pc[j]], r = s_ref[ps[j]];
+                    const long long iw = max(0, min(a.z, r.z) - max(a.x, r.x)), ih = max(0, min(a.w, r.w) - max(a.y, r.y));
+                    const long long in = iw * ih;
+                    const long long un = (long long)(a.z - a.x) * (a.w - a.y) + (long long)(r.z - r.x) * (r.w - r.y) - in;
+                    if (in > 0 && in * 256 >= (long long)q * un) { inter[j] = in; uni[j] = un; }
+                }
+            }
+            while (av_s != 0u && av_c != 0u) {              // at most min(alive, m) rounds
+                long long bi = 0, bu = 1;
+                int bk = 0x7fffffff;
+                for (int j = 0; j < 4; ++j) {               // this lane's best pair; its keys rise with j
+                    if (inter[j] > 0 && ((av_s >> ps[j]) & 1u) && ((av_c >> pc[j]) & 1u) && inter[j] * bu > bi * uni[j]) {
+                        bi = inter[j]; bu = uni[j]; bk = ps[j] * 16 + pc[j];
+                    }
+                }
+                for (int o = 32; o > 0; o >>= 1) {          // the wave's best (IoU, then the lower key) on every lane
+                    const long long i2 = __shfl_xor(bi, o), u2 = __shfl_xor(bu, o);
+                    const int k2 = __shfl_xor(bk, o);
+                    const long long a = i2 * bu, b = bi * u2;
+                    if (a > b || (a == b && k2 < bk)) { bi = i2; bu = u2; bk = k2; }
+                }
+                if (bk == 0x7fffffff) break;                // uniform: every lane holds the same pair
+                const int ms = bk >> 4, mc = bk & 15;
+                av_s &= ~(1u << ms);
+                av_c &= ~(1u << mc);
+                if (lane == ms) { ref = s_c[mc]; missed = 0; out_flag = kRectFound; }
+            }
+            if (owner && alive && ((av_s >> lane) & 1u) && ++missed > L) { alive = 0; missed = 0; }      // not matched
+            const unsigned free_s = ~(unsigned)__ballot(owner && alive) & ((1u << F) - 1u);    // a slot freed just now counts
+            const int n_free = __popc(free_s), n_left = __popc(av_c);
+            started += min(n_free, n_left);
+            dropped += max(0, n_left - n_free);
+            if (owner && ((free_s >> lane) & 1u)) {
+                const int rank = __popc(free_s & ((1u << lane) - 1u));      // the rank-th free slot takes the rank-th unclaimed
+                if (rank < n_left) {
+                    unsigned left = av_c;
+                    for (int k = 0; k < rank; ++k) left &= left - 1u;
+                    ref = s_c[__ffs(left) - 1];
+                    alive = 1;
+                    missed = 0;
+                    out_flag = kRectFound;
+                }
+            }
+            peak = max(peak, __popc((unsigned)__ballot(owner && alive)));
+        }
+        if (owner) {
+            const long long o = (long long)lane * n_rows + row;
+            *reinterpret_cast<i32x4*>(rects_out + o * 4) = out_flag == kRectFound ? ref : i32x4{0, 0, 0, 0};
+            flags_out[o] = out_flag;
+        }
+    }
+    if (lane < 4) st[lane] = lane == 0 ? 0 : lane == 1 ? started : lane == 2 ? dropped : peak;
+}
+
 // ---- the per-clip finish of face_detect (inference.py:90-104; gen_videos_from_filelist.py:61-77 is the same code) for many
 // clips: one wave per segment = one clip's rows [row0, row0 + n) of the rect / flag arenas w2l_s3fd_first_rect filled.
 //   1. the flags: any row the device did not convert (kRectHost, or a word that is no flag at all) -> status (2, first such row):
@@ -559,8 +679,6 @@ __global__ __launch_bounds__(64) void face_track_segments_kernel(const TrackSeg*
 // face_boxes_runs_wave below is the one device statement of steps 2 and 3, for clips and for live streams, strict or with the
 // pass-through for frames without a face.
 constexpr int kBoxMaxT = 64;
-struct BoxSeg { int row0, n, H, W; };
-static_assert(sizeof(BoxSeg) == 16 && sizeof(w2l_box_segment) == 16, "w2l_box_segment is 16 bytes");
 
 template <class Seg>      // BoxSeg or BoxStreamSeg: anything with the frame size H, W
 __device__ __forceinline__ int padded_coord(const int* r, int c, const Seg& s, int top, int bottom, int left, int right) {
@@ -1222,6 +1340,26 @@ int w2l_face_boxes_runs(void* stream, int n_seg, const w2l_box_segment* segs, co
     hipLaunchKernelGGL(face_boxes_runs_kernel<false>, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const BoxSeg*>(segs), rects, flags, n_rows, top, bottom, left, right, T, hold, boxes, valid,
                        status);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_face_tracks_all_segments(void* stream, int n_seg, const w2l_box_segment* segs, const int32_t* cands, const int32_t* ncand,
+                                 const int32_t* cflags, int n_rows, int K, int F, int L, int q, int32_t* rects_out, int32_t* flags_out,
+                                 int32_t* status) {
+    W2L_REQUIRE(segs && cands && ncand && cflags && rects_out && flags_out && status, "face_tracks_all_segments: NULL argument");
+    W2L_REQUIRE(n_seg >= 1 && n_rows >= 0, "face_tracks_all_segments: n_seg=%d must be at least 1 and n_rows=%d at least 0", n_seg,
+                n_rows);
+    W2L_REQUIRE(K >= 1 && K <= kTrackMaxCands, "face_tracks_all_segments: K=%d outside 1..%d", K, kTrackMaxCands);
+    W2L_REQUIRE(F >= 1 && F <= kFacesMaxSlots, "face_tracks_all_segments: F=%d outside 1..%d", F, kFacesMaxSlots);
+    W2L_REQUIRE(L >= 0 && L <= kTrackMaxReseed, "face_tracks_all_segments: L=%d outside 0..%d", L, kTrackMaxReseed);
+    W2L_REQUIRE(q >= 1 && q <= 256, "face_tracks_all_segments: q=%d outside 1..256", q);
+    W2L_REQUIRE((long long)F * n_rows < (1ll << 29), "face_tracks_all_segments: F * n_rows = %lld rows, 2^29 or more",
+                (long long)F * n_rows);
+    W2L_REQUIRE(aligned16(segs, cands, rects_out),
+                "face_tracks_all_segments: the segment table, cands and rects_out must be 16-byte aligned");
+    hipLaunchKernelGGL(face_tracks_all_segments_kernel, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const BoxSeg*>(segs), cands, ncand, cflags, n_rows, K, F, L, q, rects_out, flags_out, status);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

@@ -32,6 +32,11 @@ finish, which run as they are (`face_detection/scene.py`).
 With `track_spans=...` (opt-in) ONE w2l_face_spans_segments launch sits between the track and the finish: it bridges
 short misses, ends a span at its last detection and drops short or small spans, and w2l_face_boxes_runs with hold 0 finishes what
 it leaves.  Its span table rides in the group's one copy back (`face_detection/spans.py`).
+
+With `all_faces=...` (opt-in; needs `track_spans`) the batches leave candidates as for a track and ONE
+w2l_face_tracks_all_segments launch follows every face of every segment in F slot arenas; the span launch and the run finish then
+run unchanged over a table of F segments per segment, and the one copy back also brings the new status
+(`face_detection/faces.py`).
 """
 import collections
 
@@ -197,19 +202,21 @@ def _detect_batch_cands(detector, frames, B, H, W, cands, ncand, cflags, offset,
 Arenas = collections.namedtuple("Arenas", "rects flags cands ncand cflags")    # int32 [R,4], [R]; under a track [R,K,4], [R], [R]
 
 
-def detect_rows(detector, addr_dev, spans, batch_size, n_rows, track=None):
+def detect_rows(detector, addr_dev, spans, batch_size, n_rows, track=None, K=None):
     """The rect stage of the packed and the live path: arenas of `n_rows` rows, and the batches of exactly `batch_size` addresses
     of the device address table over spans [(H, W, first row, padded end)], one per frame shape.  A batch fills rects / flags, or
-    with `track` the candidate arenas (`track_rows` then writes rects / flags).  No host read."""
-    shapes = [(n_rows, 4), (n_rows,)] + ([] if track is None else [(n_rows, track.cands, 4), (n_rows,), (n_rows,)])
+    with `track` the candidate arenas (`track_rows` then writes rects / flags) - also without a track when `K`, the candidates per
+    frame, is given (`all_faces`).  No host read."""
+    K = K if track is None else track.cands
+    shapes = [(n_rows, 4), (n_rows,)] + ([] if K is None else [(n_rows, K, 4), (n_rows,), (n_rows,)])
     rects, flags, cands, ncand, cflags = [torch.empty(s, dtype=torch.int32, device=addr_dev.device) for s in shapes] + [None] * (5 - len(shapes))
     for H, W, first, padded in spans:
         for lo in range(first, padded, batch_size):
             frames = addr_dev[lo * 8:(lo + batch_size) * 8]
-            if track is None:
+            if K is None:
                 _detect_batch(detector, frames, batch_size, H, W, rects, flags, lo)
             else:
-                _detect_batch_cands(detector, frames, batch_size, H, W, cands, ncand, cflags, lo, track.cands)
+                _detect_batch_cands(detector, frames, batch_size, H, W, cands, ncand, cflags, lo, K)
     return Arenas(rects, flags, cands, ncand, cflags)
 
 
@@ -225,15 +232,18 @@ class BoxOut:
     [n_seg][2], with a track its status words [n_seg] - in that order.  `buffer` is the device tensor; `boxes`, `valid` (None
     without a hold), `status` and `track_status` (empty without a track) are flat views of it.  With `spans` (w2l_face_spans_segments'
     outputs ride in the same copy) three more parts follow: up to 3 words that bring the next one to a 16-byte boundary, `span_rows`
-    [n_boxes][4] and `span_status` [n_seg][2]."""
+    [n_boxes][4] and `span_status` [n_seg][2]; then `extra` more words (`.extra`: w2l_face_tracks_all_segments' status)."""
 
-    def __init__(self, n_boxes, n_seg, hold, track, device, spans=False):
+    def __init__(self, n_boxes, n_seg, hold, track, device, spans=False, extra=0):
         self.sizes = (4 * n_boxes, n_boxes if hold else None, 2 * n_seg, n_seg if track else 0)
         if spans:
             self.sizes += (-sum(n or 0 for n in self.sizes) % 4, 4 * n_boxes, 2 * n_seg)
+        if extra:
+            self.sizes += (extra,)
         self.buffer = torch.empty(sum(n or 0 for n in self.sizes), dtype=torch.int32, device=device)
         self.boxes, self.valid, self.status, self.track_status = self._parts(self.buffer)[:4]
-        self.span_rows, self.span_status = self._parts(self.buffer)[5:] if spans else (None, None)
+        self.span_rows, self.span_status = self._parts(self.buffer)[5:7] if spans else (None, None)
+        self.extra = self._parts(self.buffer)[-1] if extra else None
 
     def _parts(self, flat):
         ends = np.cumsum([n or 0 for n in self.sizes]).tolist()
@@ -255,7 +265,7 @@ class BoxOut:
 
     def split_spans(self, host):
         """the span parts of the buffer's host copy: (span rows [n_boxes,4], span status [n_seg,2])"""
-        span_rows, span_status = self._parts(host)[5:]
+        span_rows, span_status = self._parts(host)[5:7]
         return span_rows.reshape(-1, 4), span_status.reshape(-1, 2)
 
 
@@ -288,14 +298,15 @@ def _fold_shot_status(shot_status, shots_of):
     return out
 
 
-def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None, scene=None, spans=None):
+def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None, scene=None, spans=None, faces=None):
     """One group on the device.  clips: _Clips of one frame shape, each with at least one frame.  Returns numpy (boxes int32 [R,4]
     in (y1, y2, x1, x2) order, rows in clip order; status int32 [clips,2]); with `hold` (the pass-through rule) a third array,
     valid int32 [R], comes between them - still one launch and one copy back.  With `track` (a FaceTrack) the batches leave
     candidates and one more launch, before the finish, chooses the rect of every frame; its status words come back in the same
     copy and are all 0 (the table is built here).  With `scene` (a SceneCuts) the signature and the cut launch run first, their R
     flags come back while the detector batches run, and the track and the finish get one segment per shot; the status returned is
-    still per clip (`_fold_shot_status`).  With `spans` (a TrackSpans, never with `hold`) the group ends in `_finish_spans`."""
+    still per clip (`_fold_shot_status`).  With `spans` (a TrackSpans, never with `hold`) the group ends in `_finish_spans`, and
+    with `faces` too (an AllFaces, never with `track`) in `_finish_faces`."""
     dev = torch.device(detector.device)
     H, W = clips[0].H, clips[0].W
     R = sum(c.n for c in clips)
@@ -304,6 +315,7 @@ def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None, s
     st = Staging(dev)
     addresses, segments = st.table(ADDRESS, padded), st.table(BOX_SEGMENT, len(clips))
     tracks = None if track is None else st.table(TRACK_SEGMENT, len(clips))
+    wide = None if faces is None or scene is not None else st.table(BOX_SEGMENT, faces.max_faces * len(clips))
     src = [st.place(c.frames) for c in clips]
     st.allocate()
     addr, segs = st.view(addresses), st.view(segments)
@@ -316,10 +328,15 @@ def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None, s
             st.view(tracks)[k] = (r, c.n, -1, 0)             # a clip: no carried state
         r += c.n
     addr[R:] = addr[R - 1]
+    if wide is not None:
+        from .faces import expand_segments
+        st.view(wide)[:] = np.array(expand_segments(segs.tolist(), faces.max_faces, R), dtype=BOX_SEGMENT)
     st.upload()
     if scene is not None:                                    # queued before the batches: the flags cross while the detector runs
         _, cuts_host, cuts_ready = _queue_cuts(st.tensor(addresses), st.tensor(segments), len(clips), R, H, W, scene, dev)
-    arenas = detect_rows(detector, st.tensor(addresses), [(H, W, 0, padded)], batch_size, padded, track)    # rows [R, padded): scratch
+    arenas = detect_rows(detector, st.tensor(addresses), [(H, W, 0, padded)], batch_size, padded, track,     # rows [R, padded): scratch
+                         **({} if faces is None else {"K": faces.cands}))
+    wide_dev = None if wide is None else st.tensor(wide)
     n_seg, seg_dev, track_dev, shots_of = len(clips), st.tensor(segments), None if tracks is None else st.tensor(tracks), None
     if scene is not None:
         cuts_ready.synchronize()
@@ -330,6 +347,7 @@ def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None, s
         st2, n_seg = Staging(dev), sum(len(s) for s in shots_of)
         segments2 = st2.table(BOX_SEGMENT, n_seg)
         tracks2 = None if track is None else st2.table(TRACK_SEGMENT, n_seg)
+        wide2 = None if faces is None else st2.table(BOX_SEGMENT, faces.max_faces * n_seg)
         st2.allocate()
         k, r = 0, 0
         for c, shots in zip(clips, shots_of):
@@ -339,8 +357,14 @@ def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None, s
                     st2.view(tracks2)[k] = (r + a, b - a, -1, 0)     # a shot: a fresh track
                 k += 1
             r += c.n
+        if wide2 is not None:
+            from .faces import expand_segments
+            st2.view(wide2)[:] = np.array(expand_segments(st2.view(segments2).tolist(), faces.max_faces, R), dtype=BOX_SEGMENT)
         st2.upload()
         seg_dev, track_dev = st2.tensor(segments2), None if tracks2 is None else st2.tensor(tracks2)
+        wide_dev = None if wide2 is None else st2.tensor(wide2)
+    if faces is not None:
+        return _finish_faces(n_seg, seg_dev, wide_dev, arenas, faces, spans, R, pads, T, dev, [c.n for c in clips], shots_of)
     if spans is not None:
         return _finish_spans(n_seg, seg_dev, track_dev, arenas, track, spans, R, pads, T, dev, [c.n for c in clips], shots_of)
     out = BoxOut(R, n_seg, hold is not None, track is not None, dev)
@@ -388,6 +412,49 @@ def _finish_spans(n_seg, seg_dev, track_dev, arenas, track, spans, R, pads, T, d
     return boxes, valid, _fold_shot_status(status, shots_of), kept
 
 
+def _finish_faces(n_seg, seg_dev, wide_dev, arenas, faces, spans, R, pads, T, dev, clip_lengths, shots_of):
+    """the end of `_detect_group` under `all_faces`: w2l_face_tracks_all_segments over the group's segments (L = `spans.bridge`) into
+    F slot arenas of R rows each, then the unchanged w2l_face_spans_segments and w2l_face_boxes_runs (hold 0) over `wide_dev`, the
+    table of F * n_seg segments on those arenas, and the group's one copy back, which also brings the span table and the new
+    status.  Returns (status [clips,2], [a `faces.FaceSpans` per clip]); a clip with a frame left to the host has code 2."""
+    from .faces import FaceSpan, FaceSpans, faces_segments
+    from .spans import span_segments
+    F = faces.max_faces
+    out = BoxOut(F * R, F * n_seg, True, False, dev, spans=True, extra=4 * n_seg)
+    slot_rects = torch.empty((2, F * R, 4), dtype=torch.int32, device=dev)          # the tracks, then the spans of them
+    slot_flags = torch.empty((2, F * R), dtype=torch.int32, device=dev)
+    faces_segments(n_seg, seg_dev, arenas.cands[:R], arenas.ncand[:R], arenas.cflags[:R], faces, spans.bridge, slot_rects[0], slot_flags[0],
+                   out.extra)
+    span_segments(F * n_seg, wide_dev, slot_rects[0], slot_flags[0], F * R, spans, slot_rects[1], slot_flags[1], out.span_rows,
+                  out.span_status)
+    _finish_runs(F * n_seg, wide_dev, slot_rects[1], slot_flags[1], F * R, pads, T, 0, out.boxes, out.valid, out.status)
+    host = out.buffer.cpu().numpy()                          # the group's one copy back
+    boxes, _, status, _ = out.split(host)
+    span_rows, span_status = out.split_spans(host)
+    faces_status = out._parts(host)[-1].reshape(-1, 4)
+    if shots_of is None:
+        shots_of = [[(0, n)] for n in clip_lengths]
+    if (span_status[:, 0] == 3).any() or (status[:, 0] == 3).any() or faces_status[:, 0].any():
+        raise AssertionError("w2l_face_tracks_all_segments did not follow a clip's segment (status %s, %s)"
+                             % (faces_status[:, 0].tolist(), span_status.tolist()))
+    per_clip, results, k, r = np.zeros((len(clip_lengths), 2), dtype=status.dtype), [], 0, 0
+    for c, (n, shots) in enumerate(zip(clip_lengths, shots_of)):
+        tracks, dropped = [], 0
+        for a, _ in shots:                                  # segment k holds the clip's frames from a on, in every slot
+            dropped += int(faces_status[k][2])
+            for t in range(F):
+                code, count = (int(v) for v in span_status[t * n_seg + k])
+                if code == 2 and per_clip[c][0] == 0:
+                    per_clip[c] = (2, a + count)
+                row = t * R + r + a
+                for f, L, det, _ in span_rows[row:row + (count if code == 0 else 0)].tolist():
+                    tracks.append(FaceSpan(t, a + f, a + f + L, boxes[row + f:row + f + L].astype(np.int64), det))
+            k += 1
+        results.append(FaceSpans(n, tracks, dropped))
+        r += n
+    return per_clip, results
+
+
 def _queue_cuts(addresses, segments, n_clips, R, H, W, scene, dev):
     """the two scene launches of a group and the copy of their result, all queued on the current stream: signatures of the R frames of
     the address table, cut flags over the clip table -> (the device buffer, its pinned host copy int32 [R + n_clips] = cuts [R] +
@@ -404,13 +471,60 @@ def _queue_cuts(addresses, segments, n_clips, R, H, W, scene, dev):
     return buf, host, ready
 
 
-def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None, scene=None, spans=None):
+def _host_faces(detector, clip, frames, pads, T, batch_size, scene, spans, faces):
+    """`all_faces` for one clip on the host: the candidates of every frame (`get_candidates_for_batch`, which runs `host_top_rects`
+    on a frame the device does not decide), the shots, `faces.host_all_tracks` per shot, then per slot `host_spans_shots` and
+    `host_boxes_shots` with hold 0 -> a `faces.FaceSpans`"""
+    from ..inference import halving
+    from .faces import FaceSpan, FaceSpans, host_all_tracks
+    from .spans import host_spans_shots
+    from .track import iou_q8
+
+    def run(size):
+        per_frame = []
+        for lo in range(0, clip.n, size):
+            per_frame += detector.get_candidates_for_batch(np.array(frames[lo:lo + size]), faces.cands)
+        return per_frame
+
+    per_frame = halving(run, batch_size)
+    shots = [(0, clip.n)] if scene is None else _host_shots(detector, frames, clip, batch_size, scene)
+    F, dropped = faces.max_faces, 0
+    slots = [[] for _ in range(F)]
+    for a, b in shots:
+        stats = {}
+        for t, rects in enumerate(host_all_tracks(per_frame[a:b], F, iou_q8(faces.min_iou), spans.bridge, stats)):
+            slots[t] += rects
+        dropped += stats["dropped"]
+    tracks = []
+    for t, rects in enumerate(slots):
+        filled, kept = host_spans_shots(rects, shots, spans)
+        boxes, _ = host_boxes_shots(filled, shots, clip.H, clip.W, pads, T, 0)
+        tracks += [FaceSpan(t, a, b, boxes[a:b], sum(r is not None for r in rects[a:b])) for a, b in kept]
+    return FaceSpans(clip.n, tracks, dropped)
+
+
+def _host_shots(detector, frames, clip, batch_size, scene):
+    """the shots [(a, b)] of one clip of host frames: its signatures batch by batch, one cut launch and one small copy"""
+    from .scene import SIG_WORDS, clip_cuts, frame_signatures
+    dev = torch.device(detector.device)
+    sig = torch.empty((clip.n, SIG_WORDS), dtype=torch.int32, device=dev)
+    for lo in range(0, clip.n, batch_size):
+        frame_signatures(torch.from_numpy(np.ascontiguousarray(np.array(frames[lo:lo + batch_size]))).to(dev), sig, lo)
+    return split_shots(clip.n, clip_cuts(sig, clip.H, clip.W, scene)[0])
+
+
+def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None, scene=None, spans=None, faces=None):
     """one clip alone through `inference.face_detect` (batch by batch uploads, the host rules): (key, boxes, error).  `scene` is passed
     on to it; where `face_detect`'s own finish does not fit (a hold, or a window other than 5) the same host rules run per shot
     here, on `inference._shot_rects`.  With `spans` the clip's rects go through `spans.host_spans` per shot and every kept span is
-    finished as a run."""
+    finished as a run; with `faces` too the clip goes through `_host_faces`."""
     from .. import inference
     frames = list(clip.frames.cpu().numpy()) if isinstance(clip.frames, torch.Tensor) else list(clip.frames)
+    if faces is not None:
+        try:
+            return clip.key, _host_faces(detector, clip, frames, pads, T, batch_size, scene, spans, faces), None
+        except (ValueError, OverflowError) as e:
+            return clip.key, None, str(e)
     if spans is not None:
         from .spans import host_spans_shots
         try:
@@ -461,7 +575,7 @@ def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None, scene=
 
 
 def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_batches=16, max_group_bytes=1 << 30, no_face_hold=None,
-                face_track=None, scene_cuts=None, track_spans=None):
+                face_track=None, scene_cuts=None, track_spans=None, all_faces=None):
     """`inference.face_detect(frames, detector, pads, nosmooth=(T == 0))` for every `DetectJob` of the iterable `jobs`, the frames
     of successive clips packed into detector batches of exactly `batch_size`.  A generator: jobs are consumed lazily and one
     `(key, boxes, error)` comes out per job, in job order - `boxes` the int array [n,4] of (y1, y2, x1, x2) `face_detect` returns
@@ -500,9 +614,17 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
     detection, and spans shorter than `min_len` frames or smaller than `min_size` pixels are dropped; every kept span is padded,
     clipped and smoothed as a clip of its own.  `boxes` is then a `SpanBoxes`: a `RunBoxes` over the frames of kept spans with
     `.spans` = [(a, b)], the spans as frame ranges of the clip in order; with `scene_cuts` the rule runs per shot.  Together with
-    `no_face_hold` - the other answer to the same question - it is a ValueError."""
+    `no_face_hold` - the other answer to the same question - it is a ValueError.
+
+    `all_faces`: None (default), or a `faces.AllFaces`: every face in the picture is followed, up to `max_faces` at a time
+    (not the reference's code), and every face track goes through the span rule on its own; the missed frames a
+    track tolerates are `track_spans.bridge`.  It needs `track_spans`; with `face_track` (one face) or `no_face_hold` it is a
+    ValueError.  `boxes` is then a `faces.FaceSpans`: `.tracks` is the list of `FaceSpan(slot, a, b, boxes)` - frames [a, b) of the
+    clip, `boxes` int [b - a, 4] of (y1, y2, x1, x2) - sorted by (a, slot), and `.dropped` the number of candidates that found no
+    free slot."""
     from ..inference import halving
     from .scene import check_scene
+    from .faces import FaceSpans, check_faces
     from .spans import check_spans
     from .track import check_track
     hold = check_hold(no_face_hold)
@@ -511,11 +633,21 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
     spans = check_spans(track_spans)
     if spans is not None and hold is not None:
         raise ValueError("track_spans and no_face_hold are two answers to the same question: give one of them")
+    faces = check_faces(all_faces)
+    if faces is not None:
+        if hold is not None:
+            raise ValueError("all_faces and no_face_hold do not go together")
+        if track is not None:
+            raise ValueError("all_faces follows every face and face_track one: give one of them")
+        if spans is None:
+            raise ValueError("all_faces needs track_spans: every face track goes through the span rule")
     tkw = {} if track is None else {"track": track}    # the default path calls its helpers with the arguments it always did
     if scene is not None:
         tkw["scene"] = scene
     if spans is not None:
         tkw["spans"] = spans
+    if faces is not None:
+        tkw["faces"] = faces
     if batch_size < 1 or group_batches < 1:
         raise ValueError("batch_size and group_batches must be at least 1")
     if not 0 <= int(T) <= MAX_T:
@@ -567,7 +699,9 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
 
         if clips:
             res = halving(run_group, batch_size)
-            if spans is not None:
+            if faces is not None:
+                status, kept = res
+            elif spans is not None:
                 boxes, valid, status, kept = res
             else:
                 boxes, valid, status = res[0], res[1] if hold is not None else None, res[-1]
@@ -575,11 +709,13 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
         for c in group:
             if c.n == 0:
                 empty = np.zeros((0, 4), np.int64)
-                results.append((c.key, SpanBoxes(empty, [], []) if spans is not None else empty if hold is None else RunBoxes(empty, []),
-                                None))
+                results.append((c.key, FaceSpans(0, [], 0) if faces is not None else SpanBoxes(empty, [], []) if spans is not None
+                                else empty if hold is None else RunBoxes(empty, []), None))
                 continue
             code = int(status[k][0])                       # status[k][1]: the frame that decided it
-            if code == 0 and spans is not None:
+            if code == 0 and faces is not None:
+                results.append((c.key, kept[k], None))
+            elif code == 0 and spans is not None:
                 results.append((c.key, SpanBoxes(boxes[row:row + c.n], valid[row:row + c.n] != 0, kept[k]), None))
             elif code == 0 and hold is not None:
                 results.append((c.key, RunBoxes(boxes[row:row + c.n], valid[row:row + c.n] != 0), None))
