@@ -51,6 +51,8 @@
  *                         interpolation, short tracks dropped (opt-in, not the reference's code: `track_spans`)
  *   w2l_face_tracks_all_segments  the same file's :38-40, one line per face track: every face of a shot followed at once, where
  *                         w2l_face_track_segments follows one (opt-in: `all_faces`)
+ *   w2l_face_rects_expand_segments  inference.py:77-78 (the detector's loop over ALL frames) made shorter: the detector sees every
+ *                         Nth frame and the rects between are interpolated (opt-in, not the reference's: `det_stride`)
  *   w2l_melspectrogram    audio.py:45-51 (preemphasis, STFT, mel basis, dB, normalise)
  *   w2l_mel_gather        inference.py:231-240 (16-frame mel windows at host-computed starts)
  *   w2l_resample_sinc     audio.py:9-10 (librosa.core.load's sample-rate conversion: resampy 'kaiser_best' sinc interpolation)
@@ -713,6 +715,36 @@ int w2l_face_spans_segments(void* stream, int n_seg, const w2l_box_segment* segs
 int w2l_face_tracks_all_segments(void* stream, int n_seg, const w2l_box_segment* segs, const int32_t* cands, const int32_t* ncand,
                                  const int32_t* cflags, int n_rows, int K, int F, int L, int q, int32_t* rects_out, int32_t* flags_out,
                                  int32_t* status);
+
+/* Key-frame detection (opt-in `det_stride`; not the reference's behaviour, which looks at every frame): the
+ * detector saw only the KEY frames of a segment and this launch writes the rects and flags of all its frames, in
+ * w2l_s3fd_first_rect's format, so that the track, the span rule and the four box finishes above run as they are.  With a stride
+ * N in 1..32 a segment of n >= 1 frames (a clip; with `scene_cuts` a shot) has the key frames 0, N, 2N, ... below n, and n - 1:
+ * m = (n - 1 + N - 1) / N + 1 of them, key j at frame pos(j) = min(j * N, n - 1).  key_rects [n_key_rows][4] = (x1, y1, x2, y2)
+ * and key_flags [n_key_rows] are COMPACT arenas, one row per key frame, that w2l_s3fd_first_rect or w2l_face_track_segments
+ * filled; rects [n_rows][4] and flags [n_rows] are the full arenas.  Integers only.
+ *
+ * w2l_stride_segment, 16 bytes, the table 16-byte aligned:
+ *   bytes 0..3    int32 key_row0   the segment's key rows [key_row0, key_row0 + m) of the key arenas
+ *   bytes 4..11   int32 row0, n    its rows [row0, row0 + n) of the full arenas (n <= 0: nothing is read or written, status 0)
+ *   bytes 12..15  int32 zero       not read
+ *
+ *   - frame pos(j) takes key row j's rect and flag as they are (0 none, 1 found, 2 the host must decide).
+ *   - a frame i with p = pos(j) < i < q = pos(j + 1): if both keys are flagged 1, flag 1 and every coordinate
+ *     floor((r_p * (q - i) + r_q * (i - p)) / (q - p)) in int64 - w2l_face_spans_segments' formula; else flag 0 and zeros.  A flag
+ *     2 stays on its key row alone, where the finish meets it.
+ * So a missed key leaves 2N - 1 rows of flag 0 (fewer at the segment's end).  With N = 1 every frame is a key and the launch is a
+ * copy; callers do not launch it then.  status [n_seg] int32: 0, or 3 for a segment whose key rows leave [0, n_key_rows) or whose
+ * rows leave [0, n_rows) - nothing else of it is read or written.  One thread per row, rows found by a division: a segment may be
+ * longer than a workgroup.  A segment writes its own rows (each rect one 16-byte store) and its own status only; the outputs must
+ * not overlap the inputs; no atomics, bit-reproducible.  Refused: a NULL pointer, n_seg < 1, N outside 1..32, n_key_rows < 0,
+ * n_rows < 0, a table, key_rects or rects that is not 16-byte aligned. */
+typedef struct {
+    int32_t key_row0, row0, n, zero;
+} w2l_stride_segment;
+int w2l_face_rects_expand_segments(void* stream, int n_seg, const w2l_stride_segment* segs, int N, const int32_t* key_rects,
+                                   const int32_t* key_flags, int n_key_rows, int32_t* rects, int32_t* flags, int n_rows,
+                                   int32_t* status);
 
 /* Scene-cut detection (opt-in `scene_cuts`; not the reference's behaviour, which treats a clip as one take): where
  * the shots of a clip are, decided on the device from the frames the detector reads.  A shot then is a segment of the track and of

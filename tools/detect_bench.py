@@ -2,7 +2,7 @@
 `for clip: inference.face_detect(frames, detector, ...)` over the same seeded clips.
 
     python tools/detect_bench.py [--clips 200] [--alternations 5] [--batch 16] [--precision f32] [--seed 0] [--face_track PICK]
-                                 [--scene_cuts THRESH] [--all_faces F]
+                                 [--scene_cuts THRESH] [--all_faces F] [--det_stride N]
 
 The clips are those of tools/filelist_bench.py (160x160 frames, lengths uniform in 30..120, 16 distinct frames cycled), each frame
 with the saturated block of synthetic.filelist_frame pasted in so that the seeded S3FD (synthetic.s3fd_state_dict) finds a face;
@@ -31,7 +31,15 @@ With `--all_faces F` (every face of a shot) the two loops are the
 what the candidate launch per batch in place of the rect launch, the walk over F slots and the span and run launches over F
 times the rows cost.  `boxes_that_differ` compares the first path's boxes with the boxes of the second path's slot-0 tracks on the
 frames both have.  `--track_kernel_ms` instead times the new launch alone over HIP events: one segment of 4096 frames with four
-faces that drift, F = 4, K = 8 - the serial walk's worst case - alternated with w2l_face_track_segments over the same arenas."""
+faces that drift, F = 4, K = 8 - the serial walk's worst case - alternated with w2l_face_track_segments over the same arenas.
+
+With `--det_stride N` (key-frame detection) the two loops are the packed detector without and with `det_stride=N` -
+"packed" and "packed_stride" - alternated the same way: the detector sees about 1/N of the frames, and the frames between the keys
+of a clip are not uploaded; the expand launch per group, the uploads that remain and the finish do not shrink.  The seeded clips
+cycle 16 frames whose blocks lie at unrelated places, so the interpolated boxes differ from the per-frame ones on most frames
+between keys: `boxes_that_differ` counts them and says nothing about the accuracy cost on real footage, where a face hardly moves
+between neighbouring frames.  `--expand_kernel_ms` instead times the new launch alone over HIP events: 64 segments of 4096 frames
+at stride N (2 without --det_stride)."""
 import argparse
 import json
 import os
@@ -167,6 +175,38 @@ def track_kernel_ms(dev, alternations, n=4096, F=4, K=8, L=25, q=64):
     print(json.dumps(out))
 
 
+def expand_kernel_ms(dev, alternations, N, n=4096, n_seg=64):
+    """milliseconds of w2l_face_rects_expand_segments over n_seg segments of n frames each at stride N, every key found, each launch
+    between two HIP events"""
+    from wav2lip_amd._lib import STRIDE_SEGMENT
+    from wav2lip_amd.face_detection.stride import expand_rects, key_frames
+    m = len(key_frames(n, N))
+    rng = np.random.default_rng(0)
+    key_rects = torch.from_numpy(rng.integers(0, 32768, (n_seg * m, 4)).astype(np.int32)).to(dev)
+    key_flags = torch.ones((n_seg * m,), dtype=torch.int32, device=dev)
+    seg = np.zeros(n_seg, STRIDE_SEGMENT)
+    for k in range(n_seg):
+        seg[k] = (k * m, k * n, n, 0)
+    seg = torch.from_numpy(seg.view(np.uint8)).to(dev)
+    rects, flags = torch.empty((n_seg * n, 4), dtype=torch.int32, device=dev), torch.empty((n_seg * n,), dtype=torch.int32, device=dev)
+    status = torch.empty(n_seg, dtype=torch.int32, device=dev)
+    ms = []
+    for rep in range(alternations + 1):                     # pass 0: warm-up
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        expand_rects(n_seg, seg, N, key_rects, key_flags, n_seg * m, rects, flags, n_seg * n, status)
+        e1.record()
+        e1.synchronize()
+        if rep:
+            ms.append(e0.elapsed_time(e1))
+    out = {"segments": n_seg, "frames_per_segment": n, "N": N, "key_rows": n_seg * m, "status": sorted(set(status.cpu().tolist())),
+           "alternations": alternations,
+           "expand_ms": {"samples": [round(x, 4) for x in ms], "median": round(float(np.median(ms)), 4), "min": round(min(ms), 4),
+                         "max": round(max(ms), 4)}}
+    out["ns_per_frame"] = round(1e6 * out["expand_ms"]["median"] / (n_seg * n), 3)
+    print(json.dumps(out))
+
+
 def stats(v):
     return {"samples": [round(x, 1) for x in v], "median": round(float(np.median(v)), 1), "min": round(min(v), 1), "max": round(max(v), 1)}
 
@@ -186,11 +226,17 @@ def main(argv=None):
                     help="compare the packed detector with track_spans alone and with all_faces=AllFaces(F) as well")
     ap.add_argument("--track_kernel_ms", default=False, action="store_true",
                     help="time w2l_face_tracks_all_segments alone (one segment of 4096 frames, four faces) and print one JSON line")
+    ap.add_argument("--det_stride", default=None, type=int, metavar="N",
+                    help="compare the packed detector without and with det_stride=N instead of packed against per-clip")
+    ap.add_argument("--expand_kernel_ms", default=False, action="store_true",
+                    help="time w2l_face_rects_expand_segments alone (64 segments of 4096 frames) and print one JSON line")
     a = ap.parse_args(argv)
-    if sum(v is not None for v in (a.face_track, a.scene_cuts, a.all_faces)) > 1:
-        ap.error("--face_track, --scene_cuts and --all_faces are three comparisons: give one")
+    if sum(v is not None for v in (a.face_track, a.scene_cuts, a.all_faces, a.det_stride)) > 1:
+        ap.error("--face_track, --scene_cuts, --all_faces and --det_stride are four comparisons: give one")
     if a.track_kernel_ms:
         return track_kernel_ms(torch.device("cuda", 0), a.alternations)
+    if a.expand_kernel_ms:
+        return expand_kernel_ms(torch.device("cuda", 0), a.alternations, 2 if a.det_stride is None else a.det_stride)
     dev = torch.device("cuda", 0)
     clips = clips_with_faces(a.clips, a.seed)
     frames = sum(len(c) for c in clips)
@@ -203,6 +249,9 @@ def main(argv=None):
     if a.scene_cuts is not None:
         out["scene_cuts"] = a.scene_cuts
         loops["packed_scene"] = (lambda det, clips, batch: run_packed(det, clips, batch, scene_cuts=a.scene_cuts), loops.pop("per_clip")[1])
+    if a.det_stride is not None:
+        out["det_stride"] = a.det_stride
+        loops["packed_stride"] = (lambda det, clips, batch: run_packed(det, clips, batch, det_stride=a.det_stride), loops.pop("per_clip")[1])
     if a.all_faces is not None:
         out["all_faces"] = a.all_faces
         spans = face_detection.TrackSpans(25, 1, 0)

@@ -130,6 +130,14 @@ class TrackSegment(C.Structure):
 TRACK_SEGMENT = np.dtype(TrackSegment)
 
 
+class StrideSegment(C.Structure):
+    """w2l_stride_segment: one clip's (or shot's) key rows and full rows of w2l_face_rects_expand_segments, 16 bytes"""
+    _fields_ = [(n, C.c_int32) for n in ("key_row0", "row0", "n", "zero")]
+
+
+STRIDE_SEGMENT = np.dtype(StrideSegment)
+
+
 class MelStream(C.Structure):
     """w2l_mel_stream: one stream of w2l_mel_stream_cols, 48 bytes"""
     _fields_ = [("samples", C.c_uint64), ("first", C.c_int64), ("total", C.c_int64), ("window", C.c_uint64), ("held", C.c_int32),
@@ -235,6 +243,7 @@ SIGNATURES = {
     "w2l_face_boxes_runs": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "w2l_face_spans_segments": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "w2l_face_tracks_all_segments": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "w2l_face_rects_expand_segments": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "w2l_face_boxes_stream_runs": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "w2l_frame_hist_rows": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "w2l_scene_cuts": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),

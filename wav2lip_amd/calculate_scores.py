@@ -53,8 +53,9 @@ def build_cli_parser():
                    help='One face box for every frame; without it the face detector runs on every clip')
     p.add_argument('--face_det_precision', default='fp32', choices=['fp32', 'bf16'],
                    help='Face detector arithmetic: fp32 (default, matches the reference) or bf16 storage')
-    from .inference import add_det_scale_flag
+    from .inference import add_det_scale_flag, add_stride_flag
     add_det_scale_flag(p)
+    add_stride_flag(p)
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
                    help='SyncNet arithmetic: fp32 (default, matches the reference) or bf16 storage')
     p.add_argument('--packed_face_det', default=False, action='store_true',
@@ -117,6 +118,7 @@ def _read_clip(video, name, tmpdir, skip):
 def score_jobs(args, videos, device, detector, skipped):
     """the producer: one evaluation.ScoreJob per readable clip, in `videos` order; `skipped` collects the names it passes over"""
     from . import audio, inference
+    from .face_detection.stride import stride_from_args
     from .evaluation import ScoreJob
 
     def skip(name, why, trace):
@@ -137,7 +139,7 @@ def score_jobs(args, videos, device, detector, skipped):
                     boxes = inference.validate_boxes([args.box], frames.shape[1], frames.shape[2]) * len(frames)
                 else:
                     det = inference.face_detect(list(frames), detector=detector, pads=[0, 0, 0, 0], nosmooth=False,
-                                                batch_size=FACE_DET_BATCH_SIZE)
+                                                batch_size=FACE_DET_BATCH_SIZE, **stride_from_args(args))
                     boxes = inference.validate_boxes([c for _, c in det], frames.shape[1], frames.shape[2])
                 yield ScoreJob(name, face_crops(frames, boxes, device), audio.melspectrogram_device(wav, device))
             except KeyboardInterrupt:
@@ -153,6 +155,7 @@ def score_jobs_packed(args, videos, device, detector, skipped):
     about a clip it passes over is held back until the scorable clip after it is answered, so stderr and `skipped` read as they do
     from `score_jobs`."""
     from . import audio, face_detection, inference
+    from .face_detection.stride import stride_from_args
     from .evaluation import ScoreJob
     held, notes, tail = {}, {}, []       # name -> (wav, frames); name -> [(name, why, trace)] due before it; after the last
 
@@ -177,7 +180,7 @@ def score_jobs_packed(args, videos, device, detector, skipped):
 
     with tempfile.TemporaryDirectory(prefix="w2l_scores_") as tmpdir:
         for name, boxes, error in face_detection.detect_many(detector, inputs(tmpdir), pads=(0, 0, 0, 0), T=5,
-                                                             batch_size=FACE_DET_BATCH_SIZE):
+                                                             batch_size=FACE_DET_BATCH_SIZE, **stride_from_args(args)):
             flush(notes.pop(name))
             wav, frames = held.pop(name)
             try:

@@ -55,7 +55,7 @@ def build_cli_parser():
     """the reference's flags plus the .sh's loop and file, and what the in-tree detector and scorer need"""
     from .face_detection.faces import add_faces_flags
     from .face_detection.spans import add_span_flags
-    from .inference import add_det_scale_flag, add_scene_flag, add_track_flags
+    from .inference import add_det_scale_flag, add_scene_flag, add_stride_flag, add_track_flags
     p = build_parser()
     p.add_argument('--data_root', type=str, default=None, help='Score every *.avi of this directory, in sorted order, instead of --videofile')
     p.add_argument('--scores_file', type=str, default=None, help='Append the printed lines to this file (the reference\'s all_scores.txt)')
@@ -65,6 +65,7 @@ def build_cli_parser():
     p.add_argument('--face_det_precision', default='fp32', choices=['fp32', 'bf16'],
                    help='Face detector arithmetic: fp32 (default, matches the reference) or bf16 storage')
     add_det_scale_flag(p)
+    add_stride_flag(p)
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
                    help='SyncNet arithmetic: fp32 (default, matches the reference) or bf16 storage')
     add_scene_flag(p)
@@ -86,6 +87,7 @@ def span_jobs(args, videos, device, detector, skipped):
     from .face_detection.faces import faces_from_args, faces_kw
     from .face_detection.scene import scene_from_args, scene_kw
     from .face_detection.spans import spans_from_args
+    from .face_detection.stride import stride_from_args
     from .face_detection.track import track_from_args, track_kw
     from .inference import validate_boxes
     spans = spans_from_args(args)
@@ -133,7 +135,8 @@ def span_jobs(args, videos, device, detector, skipped):
                 held[name] = got
                 yield face_detection.DetectJob(name, got[1])
 
-        kw = {**(track_kw(track_from_args(args)) if faces is None else faces_kw(faces)), **scene_kw(scene_from_args(args))}
+        kw = {**(track_kw(track_from_args(args)) if faces is None else faces_kw(faces)), **scene_kw(scene_from_args(args)),
+              **stride_from_args(args)}
         for name, boxes, error in face_detection.detect_many(detector, inputs(), pads=(0, 0, 0, 0), T=5, batch_size=FACE_DET_BATCH_SIZE,
                                                              track_spans=spans, **kw):
             wav, frames = held.pop(name)

@@ -1054,6 +1054,63 @@ __global__ __launch_bounds__(64) void face_spans_segments_kernel(const BoxSeg* _
     if (lane == 0) { st[0] = 0; st[1] = kept; }
 }
 
+// ---- key-frame detection (opt-in `det_stride`): the detector saw only the key frames 0, N, 2N, ... and n - 1 of a
+// segment of n frames; this launch turns their compact rect / flag rows into the n rows every later stage reads.  Key j lies at
+// pos(j) = min(j * N, n - 1) and there are m = (n - 1 + N - 1) / N + 1 of them, so a row finds its keys by one division: row i with
+// j = i / N is key j when i == j * N, key m - 1 when i == n - 1, and lies between keys j and j + 1 otherwise.  A key row is copied;
+// a row between two keys flagged 1 takes w2l_face_spans_segments' interpolation, any other row is flag 0 and zeros.
+// Row-parallel: workgroup (x = segment, y) strides over the segment's rows, one thread per row, no thread reads what another wrote.
+struct StrideSeg {
+    int key_row0, row0, n, zero;
+};
+static_assert(sizeof(StrideSeg) == 16 && sizeof(w2l_stride_segment) == 16, "w2l_stride_segment is 16 bytes");
+constexpr int kStrideMax = 32, kStrideThreads = 256, kStrideGridCap = 64;
+
+__global__ __launch_bounds__(kStrideThreads) void face_rects_expand_segments_kernel(const StrideSeg* __restrict__ segs, int N,
+                                                                                    const int* __restrict__ key_rects,
+                                                                                    const int* __restrict__ key_flags, int n_key_rows,
+                                                                                    int* __restrict__ rects, int* __restrict__ flags,
+                                                                                    int n_rows, int* __restrict__ status) {
+    const StrideSeg s = segs[blockIdx.x];
+    const bool first = blockIdx.y == 0 && threadIdx.x == 0;
+    if (s.n <= 0) {                                      // uniform
+        if (first) status[blockIdx.x] = 0;
+        return;
+    }
+    const long long n = s.n, m = (n - 1 + N - 1) / N + 1;
+    if (s.key_row0 < 0 || s.key_row0 + m > n_key_rows || s.row0 < 0 || s.row0 + n > n_rows) {     // uniform: not followed
+        if (first) status[blockIdx.x] = kBoxStreamBadSegment;
+        return;
+    }
+    const int* kf = key_flags + s.key_row0;
+    const int4* kr = reinterpret_cast<const int4*>(key_rects) + s.key_row0;
+    int* fo = flags + s.row0;
+    int4* ro = reinterpret_cast<int4*>(rects) + s.row0;
+    for (long long i = (long long)blockIdx.y * kStrideThreads + threadIdx.x; i < n; i += (long long)gridDim.y * kStrideThreads) {
+        const long long j = i / N, p = j * N;
+        int4 r = make_int4(0, 0, 0, 0);
+        int f = 0;
+        if (i == n - 1) {
+            f = kf[m - 1];
+            r = kr[m - 1];
+        } else if (i == p) {
+            f = kf[j];
+            r = kr[j];
+        } else if (kf[j] == kRectFound && kf[j + 1] == kRectFound) {      // p < i < q <= n - 1, so key j + 1 <= m - 1 exists
+            const long long q = min(p + N, n - 1), wp = q - i, wq = i - p, d = q - p;
+            const int4 rp = kr[j], rq = kr[j + 1];      // d <= 32: the products stay below 2^37 in magnitude
+            r.x = (int)floor_div(rp.x * wp + rq.x * wq, d);
+            r.y = (int)floor_div(rp.y * wp + rq.y * wq, d);
+            r.z = (int)floor_div(rp.z * wp + rq.z * wq, d);
+            r.w = (int)floor_div(rp.w * wp + rq.w * wq, d);
+            f = kRectFound;
+        }
+        fo[i] = f;
+        ro[i] = r;
+    }
+    if (first) status[blockIdx.x] = 0;
+}
+
 constexpr int kPackRowsGridCap = 1024;        // workgroups per image of the row-table packs, full size and reduced
 
 template <class S>
@@ -1377,6 +1434,24 @@ int w2l_face_spans_segments(void* stream, int n_seg, const w2l_box_segment* segs
     hipLaunchKernelGGL(face_spans_segments_kernel, dim3(n_seg), dim3(64), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const BoxSeg*>(segs), rects, flags, n_rows, bridge, min_len, min_size, rects_out, flags_out,
                        spans, status);
+    W2L_HIP_CHECK(hipGetLastError());
+    return W2L_OK;
+}
+
+int w2l_face_rects_expand_segments(void* stream, int n_seg, const w2l_stride_segment* segs, int N, const int32_t* key_rects,
+                                   const int32_t* key_flags, int n_key_rows, int32_t* rects, int32_t* flags, int n_rows,
+                                   int32_t* status) {
+    W2L_REQUIRE(segs && key_rects && key_flags && rects && flags && status, "face_rects_expand_segments: NULL argument");
+    W2L_REQUIRE(n_seg >= 1 && n_key_rows >= 0 && n_rows >= 0,
+                "face_rects_expand_segments: n_seg=%d must be at least 1, n_key_rows=%d and n_rows=%d at least 0", n_seg, n_key_rows,
+                n_rows);
+    W2L_REQUIRE(N >= 1 && N <= kStrideMax, "face_rects_expand_segments: N=%d outside 1..%d", N, kStrideMax);
+    W2L_REQUIRE(aligned16(segs, key_rects, rects),
+                "face_rects_expand_segments: the segment table, key_rects and rects must be 16-byte aligned");
+    const int chunks = (n_rows + kStrideThreads - 1) / kStrideThreads;       // a segment has at most n_rows rows
+    hipLaunchKernelGGL(face_rects_expand_segments_kernel, dim3(n_seg, std::min(std::max(chunks, 1), kStrideGridCap)),
+                       dim3(kStrideThreads), 0, static_cast<hipStream_t>(stream), reinterpret_cast<const StrideSeg*>(segs), N,
+                       key_rects, key_flags, n_key_rows, rects, flags, n_rows, status);
     W2L_HIP_CHECK(hipGetLastError());
     return W2L_OK;
 }

@@ -37,6 +37,11 @@ With `all_faces=...` (opt-in; needs `track_spans`) the batches le
 w2l_face_tracks_all_segments launch follows every face of every segment in F slot arenas; the span launch and the run finish then
 run unchanged over a table of F segments per segment, and the one copy back also brings the new status
 (`face_detection/faces.py`).
+
+With `det_stride=N` (opt-in) the address table, the batches and the rect or candidate arenas hold the KEY frames of
+every clip - of every shot under `scene_cuts` - alone, the track launches step from key to key, and ONE
+w2l_face_rects_expand_segments launch writes the full arenas every finish above then reads as it always did
+(`_detect_group_keys`, `face_detection/stride.py`).
 """
 import collections
 
@@ -381,14 +386,160 @@ def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None, s
     return (boxes, status) if hold is None else (boxes, valid, status)
 
 
-def _finish_spans(n_seg, seg_dev, track_dev, arenas, track, spans, R, pads, T, dev, clip_lengths, shots_of):
+class _KeyTables:
+    """The tables of one group under key-frame detection (`det_stride` N > 1), reserved in a Staging.  `segs`:
+    [(row0, n)] the group's segments - clips, or shots - as rows of the FULL arenas of R rows; segment k's key frames
+    (`stride.key_frames`) are the rows [key_row0_k, key_row0_k + m_k) of the KEY arenas, one segment after the other, Rk in all:
+        addresses      `padded` frame addresses, Rk padded to a batch multiple      (the detector batches)
+        segments       BOX_SEGMENT (row0, n, H, W)                                  (the finishes, on full rows)
+        stride         STRIDE_SEGMENT (t * Rk + key_row0, t * R + row0, n, 0), F * n_seg of them, slot t's after slot t - 1's
+        tracks         with `track`: TRACK_SEGMENT (key_row0, m, -1, 0)             (the track steps from key to key)
+        key_segments,  with `faces`: BOX_SEGMENT (key_row0, m, H, W) for w2l_face_tracks_all_segments, and the F-slot table of
+        wide           `faces.expand_segments` over the full rows for the span launch and the run finish"""
+
+    def __init__(self, st, segs, N, batch_size, H, W, R, track, faces):
+        from .._lib import STRIDE_SEGMENT
+        from .stride import key_frames
+        self.N, self.R, self.segs, self.shape = N, R, segs, (H, W)
+        self.keys = [key_frames(n, N) for _, n in segs]
+        self.Rk = sum(len(k) for k in self.keys)
+        self.padded = (self.Rk + batch_size - 1) // batch_size * batch_size
+        self.F = 1 if faces is None else faces.max_faces
+        n_seg = self.n_seg = len(segs)
+        self.addresses, self.segments = st.table(ADDRESS, self.padded), st.table(BOX_SEGMENT, n_seg)
+        self.stride = st.table(STRIDE_SEGMENT, self.F * n_seg)
+        self.tracks = None if track is None else st.table(TRACK_SEGMENT, n_seg)
+        self.key_segments = None if faces is None else st.table(BOX_SEGMENT, n_seg)
+        self.wide = None if faces is None else st.table(BOX_SEGMENT, self.F * n_seg)
+
+    def key_rows(self):
+        """the full-arena row of every key row, in key-row order"""
+        return np.array([row0 + i for (row0, _), keys in zip(self.segs, self.keys) for i in keys], dtype=np.int64)
+
+    def fill(self, st, key_addresses):
+        """the tables' contents, once `st` is allocated; key_addresses: uint64 [Rk], the frame every key row reads"""
+        H, W = self.shape
+        addr = st.view(self.addresses)
+        addr[:self.Rk] = key_addresses
+        addr[self.Rk:] = addr[self.Rk - 1]
+        kr = 0
+        for k, ((row0, n), keys) in enumerate(zip(self.segs, self.keys)):
+            st.view(self.segments)[k] = (row0, n, H, W)
+            for t in range(self.F):
+                st.view(self.stride)[t * self.n_seg + k] = (t * self.Rk + kr, t * self.R + row0, n, 0)
+            if self.tracks is not None:
+                st.view(self.tracks)[k] = (kr, len(keys), -1, 0)             # a clip or a shot: no carried state
+            if self.key_segments is not None:
+                st.view(self.key_segments)[k] = (kr, len(keys), H, W)
+            kr += len(keys)
+        if self.wide is not None:
+            from .faces import expand_segments
+            st.view(self.wide)[:] = np.array(expand_segments(st.view(self.segments).tolist(), self.F, self.R), dtype=BOX_SEGMENT)
+
+    def on_device(self, st):
+        """after the upload: the device tables the launches take"""
+        dev = lambda h: None if h is None else st.tensor(h)
+        self.addr_dev, self.seg_dev, self.stride_dev = st.tensor(self.addresses), st.tensor(self.segments), st.tensor(self.stride)
+        self.track_dev, self.key_seg_dev, self.wide_dev = dev(self.tracks), dev(self.key_segments), dev(self.wide)
+
+    def expand(self, key_rects, key_flags, status, out=None):
+        """w2l_face_rects_expand_segments: the key arenas (F * Rk rows, or the one slot's arenas with their scratch rows behind) ->
+        `Arenas` of the full rects [F * R, 4] and flags [F * R] (`out`, or new ones); status: int32 [F * n_seg] on the device"""
+        from .stride import expand_rects
+        n_rows = self.F * self.R
+        rects, flags = out if out is not None else (torch.empty((n_rows, 4), dtype=torch.int32, device=key_rects.device),
+                                                    torch.empty((n_rows,), dtype=torch.int32, device=key_rects.device))
+        expand_rects(self.F * self.n_seg, self.stride_dev, self.N, key_rects, key_flags, self.F * self.Rk, rects, flags, n_rows, status)
+        return Arenas(rects, flags, None, None, None)
+
+    @staticmethod
+    def check(status):
+        """the expand launch's status words on the host: all 0 for tables built here"""
+        if status.any():
+            raise AssertionError("w2l_face_rects_expand_segments did not follow a segment (status %s)" % status.tolist())
+
+
+def _detect_group_keys(detector, clips, pads, T, batch_size, N, hold=None, track=None, scene=None, spans=None, faces=None):
+    """`_detect_group` under key-frame detection (`det_stride` N > 1): the same results in the same formats, from
+    detector batches over the KEY frames of every clip - with `scene`, of every shot - alone.  The address table, the batches and
+    the rect or candidate arenas hold key rows (`_KeyTables`); the track launches, if any, run over key segments; ONE
+    w2l_face_rects_expand_segments launch then writes the full arenas and every finish runs on them unchanged.  Still one copy back
+    per group: the expand launch's status words ride in it.  Without `scene` the frames between the keys of a clip of host arrays are
+    not even uploaded.  With `scene` every frame goes up - the signatures read them all - and the group WAITS for the cut flags
+    before it builds the key tables and queues the detector batches: the one small wait the default path hides behind them."""
+    dev = torch.device(detector.device)
+    H, W = clips[0].H, clips[0].W
+    lengths = [c.n for c in clips]
+    R, frame_bytes = sum(lengths), H * W * 3
+    first = np.cumsum([0] + lengths[:-1]).tolist()
+    on_device = [isinstance(c.frames, torch.Tensor) for c in clips]
+    st, shots_of = Staging(dev), None
+    if scene is None:
+        kt = st                                              # one buffer: the key tables and the key frames
+        keys = _KeyTables(st, list(zip(first, lengths)), N, batch_size, H, W, R, track, faces)
+        src = [st.place(c.frames) if there else st.place([c.frames[i] for i in k]) for c, there, k in zip(clips, on_device, keys.keys)]
+        st.allocate()
+        keys.fill(st, np.concatenate([np.uint64(st.address(h)) + (np.array(k, dtype=np.uint64) if there else
+                                                                   np.arange(len(k), dtype=np.uint64)) * np.uint64(frame_bytes)
+                                      for h, there, k in zip(src, on_device, keys.keys)]))
+        st.upload()
+    else:
+        addresses, segments = st.table(ADDRESS, R), st.table(BOX_SEGMENT, len(clips))
+        src = [st.place(c.frames) for c in clips]
+        st.allocate()
+        addr = st.view(addresses)
+        for k, (c, r) in enumerate(zip(clips, first)):
+            addr[r:r + c.n] = np.uint64(st.address(src[k])) + np.arange(c.n, dtype=np.uint64) * np.uint64(frame_bytes)
+            st.view(segments)[k] = (r, c.n, H, W)
+        st.upload()
+        _, cuts_host, cuts_ready = _queue_cuts(st.tensor(addresses), st.tensor(segments), len(clips), R, H, W, scene, dev)
+        cuts_ready.synchronize()                             # the keys are per shot: nothing to detect on before the cuts are known
+        cuts = cuts_host.numpy()
+        if cuts[R:].any():
+            raise AssertionError("w2l_scene_cuts did not follow a clip's segment (status %s)" % cuts[R:].tolist())
+        shots_of = [split_shots(c.n, cuts[r:r + c.n]) for c, r in zip(clips, first)]
+        kt = Staging(dev)                                    # `st` stays: the frames lie in it
+        keys = _KeyTables(kt, [(r + a, b - a) for r, shots in zip(first, shots_of) for a, b in shots], N, batch_size, H, W, R, track,
+                          faces)
+        kt.allocate()
+        keys.fill(kt, addr[keys.key_rows()])
+        kt.upload()
+    keys.on_device(kt)
+    n_seg = keys.n_seg
+    arenas = detect_rows(detector, keys.addr_dev, [(H, W, 0, keys.padded)], batch_size, keys.padded, track,      # rows [Rk, padded): scratch
+                         **({} if faces is None else {"K": faces.cands}))
+    if faces is not None:
+        return _finish_faces(n_seg, keys.seg_dev, keys.wide_dev, arenas, faces, spans, R, pads, T, dev, lengths, shots_of, keys=keys)
+    if spans is not None:
+        return _finish_spans(n_seg, keys.seg_dev, keys.track_dev, arenas, track, spans, R, pads, T, dev, lengths, shots_of, keys=keys)
+    out = BoxOut(R, n_seg, hold is not None, track is not None, dev, extra=n_seg)
+    if track is not None:
+        track_rows(n_seg, keys.track_dev, arenas, track, out.track_status)
+    full = keys.expand(arenas.rects, arenas.flags, out.extra)
+    if hold is None:
+        _finish_segments(n_seg, keys.seg_dev, full.rects, full.flags, pads, T, out.boxes, out.status)
+    else:
+        _finish_runs(n_seg, keys.seg_dev, full.rects, full.flags, R, pads, T, hold, out.boxes, out.valid, out.status)
+    host = out.buffer.cpu().numpy()                          # the group's one copy back
+    boxes, valid, status, _ = out.split(host)
+    keys.check(out._parts(host)[-1])
+    if shots_of is not None:
+        status = _fold_shot_status(status, shots_of)
+    return (boxes, status) if hold is None else (boxes, valid, status)
+
+
+def _finish_spans(n_seg, seg_dev, track_dev, arenas, track, spans, R, pads, T, dev, clip_lengths, shots_of, keys=None):
     """the end of `_detect_group` under `track_spans`: the track launch (if any), w2l_face_spans_segments over the same segments,
     w2l_face_boxes_runs with hold 0 on its outputs, and the group's one copy back, which also brings the span table.  Returns numpy
-    (boxes [R,4], valid [R], status [clips,2], [the clip's kept spans [(a, b)] per clip])."""
+    (boxes [R,4], valid [R], status [clips,2], [the clip's kept spans [(a, b)] per clip]).  With `keys` (a `_KeyTables`: key-frame
+    detection) the arenas hold key rows, `track_dev` is the table of key segments, and the expand launch sits between the track
+    and the span rule; its status words ride in the same copy."""
     from .spans import span_segments
-    out = BoxOut(R, n_seg, True, track is not None, dev, spans=True)
+    out = BoxOut(R, n_seg, True, track is not None, dev, spans=True, **({} if keys is None else {"extra": n_seg}))
     if track is not None:
         track_rows(n_seg, track_dev, arenas, track, out.track_status)
+    if keys is not None:
+        arenas = keys.expand(arenas.rects, arenas.flags, out.extra)
     rects = torch.empty((R, 4), dtype=torch.int32, device=dev)
     flags = torch.empty((R,), dtype=torch.int32, device=dev)
     span_segments(n_seg, seg_dev, arenas.rects, arenas.flags, R, spans, rects, flags, out.span_rows, out.span_status)
@@ -396,6 +547,8 @@ def _finish_spans(n_seg, seg_dev, track_dev, arenas, track, spans, R, pads, T, d
     host = out.buffer.cpu().numpy()
     boxes, valid, status, _ = out.split(host)
     span_rows, span_status = out.split_spans(host)
+    if keys is not None:
+        keys.check(out._parts(host)[-1])
     if shots_of is None:
         shots_of = [[(0, n)] for n in clip_lengths]
     if (span_status[:, 0] == 3).any() or (status[:, 0] == 3).any():
@@ -412,26 +565,40 @@ def _finish_spans(n_seg, seg_dev, track_dev, arenas, track, spans, R, pads, T, d
     return boxes, valid, _fold_shot_status(status, shots_of), kept
 
 
-def _finish_faces(n_seg, seg_dev, wide_dev, arenas, faces, spans, R, pads, T, dev, clip_lengths, shots_of):
+def _finish_faces(n_seg, seg_dev, wide_dev, arenas, faces, spans, R, pads, T, dev, clip_lengths, shots_of, keys=None):
     """the end of `_detect_group` under `all_faces`: w2l_face_tracks_all_segments over the group's segments (L = `spans.bridge`) into
     F slot arenas of R rows each, then the unchanged w2l_face_spans_segments and w2l_face_boxes_runs (hold 0) over `wide_dev`, the
     table of F * n_seg segments on those arenas, and the group's one copy back, which also brings the span table and the new
-    status.  Returns (status [clips,2], [a `faces.FaceSpans` per clip]); a clip with a frame left to the host has code 2."""
+    status.  Returns (status [clips,2], [a `faces.FaceSpans` per clip]); a clip with a frame left to the host has code 2.  With
+    `keys` (a `_KeyTables`: key-frame detection) the candidates are those of key rows: the tracks run over `keys`' table of key
+    segments with L = `stride.faces_reseed(bridge, N)` into F slot arenas of key rows, and the expand launch over the F-slot wide
+    stride table writes the F full slot arenas the span launch reads; its status words ride in the same copy."""
     from .faces import FaceSpan, FaceSpans, faces_segments
     from .spans import span_segments
     F = faces.max_faces
-    out = BoxOut(F * R, F * n_seg, True, False, dev, spans=True, extra=4 * n_seg)
+    out = BoxOut(F * R, F * n_seg, True, False, dev, spans=True, extra=4 * n_seg + (0 if keys is None else F * n_seg))
     slot_rects = torch.empty((2, F * R, 4), dtype=torch.int32, device=dev)          # the tracks, then the spans of them
     slot_flags = torch.empty((2, F * R), dtype=torch.int32, device=dev)
-    faces_segments(n_seg, seg_dev, arenas.cands[:R], arenas.ncand[:R], arenas.cflags[:R], faces, spans.bridge, slot_rects[0], slot_flags[0],
-                   out.extra)
+    if keys is None:
+        faces_segments(n_seg, seg_dev, arenas.cands[:R], arenas.ncand[:R], arenas.cflags[:R], faces, spans.bridge, slot_rects[0],
+                       slot_flags[0], out.extra)
+    else:
+        from .stride import faces_reseed
+        Rk = keys.Rk
+        key_rects = torch.empty((F * Rk, 4), dtype=torch.int32, device=dev)
+        key_flags = torch.empty((F * Rk,), dtype=torch.int32, device=dev)
+        faces_segments(n_seg, keys.key_seg_dev, arenas.cands[:Rk], arenas.ncand[:Rk], arenas.cflags[:Rk], faces,
+                       faces_reseed(spans.bridge, keys.N), key_rects, key_flags, out.extra[:4 * n_seg])
+        keys.expand(key_rects, key_flags, out.extra[4 * n_seg:], out=(slot_rects[0], slot_flags[0]))
     span_segments(F * n_seg, wide_dev, slot_rects[0], slot_flags[0], F * R, spans, slot_rects[1], slot_flags[1], out.span_rows,
                   out.span_status)
     _finish_runs(F * n_seg, wide_dev, slot_rects[1], slot_flags[1], F * R, pads, T, 0, out.boxes, out.valid, out.status)
     host = out.buffer.cpu().numpy()                          # the group's one copy back
     boxes, _, status, _ = out.split(host)
     span_rows, span_status = out.split_spans(host)
-    faces_status = out._parts(host)[-1].reshape(-1, 4)
+    faces_status = out._parts(host)[-1][:4 * n_seg].reshape(-1, 4)
+    if keys is not None:
+        keys.check(out._parts(host)[-1][4 * n_seg:])
     if shots_of is None:
         shots_of = [[(0, n)] for n in clip_lengths]
     if (span_status[:, 0] == 3).any() or (status[:, 0] == 3).any() or faces_status[:, 0].any():
@@ -471,28 +638,40 @@ def _queue_cuts(addresses, segments, n_clips, R, H, W, scene, dev):
     return buf, host, ready
 
 
-def _host_faces(detector, clip, frames, pads, T, batch_size, scene, spans, faces):
+def _host_faces(detector, clip, frames, pads, T, batch_size, scene, spans, faces, stride=1):
     """`all_faces` for one clip on the host: the candidates of every frame (`get_candidates_for_batch`, which runs `host_top_rects`
     on a frame the device does not decide), the shots, `faces.host_all_tracks` per shot, then per slot `host_spans_shots` and
-    `host_boxes_shots` with hold 0 -> a `faces.FaceSpans`"""
+    `host_boxes_shots` with hold 0 -> a `faces.FaceSpans`.  With `stride` N > 1 the shots come first, the candidates are those of
+    every shot's key frames, the tracks step from key to key with `stride.faces_reseed(bridge, N)` tolerated misses, and every
+    slot's key rects go through `stride.host_stride_fill` per shot."""
     from ..inference import halving
     from .faces import FaceSpan, FaceSpans, host_all_tracks
     from .spans import host_spans_shots
+    from .stride import faces_reseed, host_stride_fill, key_frames, shot_key_frames
     from .track import iou_q8
+    shots = [(0, clip.n)] if scene is None else _host_shots(detector, frames, clip, batch_size, scene)
+    seen = frames if stride == 1 else [frames[i] for i in shot_key_frames(shots, stride)]
 
     def run(size):
         per_frame = []
-        for lo in range(0, clip.n, size):
-            per_frame += detector.get_candidates_for_batch(np.array(frames[lo:lo + size]), faces.cands)
+        for lo in range(0, len(seen), size):
+            per_frame += detector.get_candidates_for_batch(np.array(seen[lo:lo + size]), faces.cands)
         return per_frame
 
     per_frame = halving(run, batch_size)
-    shots = [(0, clip.n)] if scene is None else _host_shots(detector, frames, clip, batch_size, scene)
     F, dropped = faces.max_faces, 0
     slots = [[] for _ in range(F)]
+    k = 0
     for a, b in shots:
         stats = {}
-        for t, rects in enumerate(host_all_tracks(per_frame[a:b], F, iou_q8(faces.min_iou), spans.bridge, stats)):
+        if stride == 1:
+            per_slot = host_all_tracks(per_frame[a:b], F, iou_q8(faces.min_iou), spans.bridge, stats)
+        else:
+            m = len(key_frames(b - a, stride))
+            per_slot = [host_stride_fill(rects, b - a, stride) for rects in
+                        host_all_tracks(per_frame[k:k + m], F, iou_q8(faces.min_iou), faces_reseed(spans.bridge, stride), stats)]
+            k += m
+        for t, rects in enumerate(per_slot):
             slots[t] += rects
         dropped += stats["dropped"]
     tracks = []
@@ -513,27 +692,29 @@ def _host_shots(detector, frames, clip, batch_size, scene):
     return split_shots(clip.n, clip_cuts(sig, clip.H, clip.W, scene)[0])
 
 
-def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None, scene=None, spans=None, faces=None):
+def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None, scene=None, spans=None, faces=None, stride=1):
     """one clip alone through `inference.face_detect` (batch by batch uploads, the host rules): (key, boxes, error).  `scene` is passed
     on to it; where `face_detect`'s own finish does not fit (a hold, or a window other than 5) the same host rules run per shot
     here, on `inference._shot_rects`.  With `spans` the clip's rects go through `spans.host_spans` per shot and every kept span is
-    finished as a run; with `faces` too the clip goes through `_host_faces`."""
+    finished as a run; with `faces` too the clip goes through `_host_faces`.  With `stride` N > 1 `face_detect` and its helpers
+    look at key frames only and fill per shot with `stride.host_stride_fill`."""
     from .. import inference
+    skw = {} if stride == 1 else {"det_stride": stride}
     frames = list(clip.frames.cpu().numpy()) if isinstance(clip.frames, torch.Tensor) else list(clip.frames)
     if faces is not None:
         try:
-            return clip.key, _host_faces(detector, clip, frames, pads, T, batch_size, scene, spans, faces), None
+            return clip.key, _host_faces(detector, clip, frames, pads, T, batch_size, scene, spans, faces, stride), None
         except (ValueError, OverflowError) as e:
             return clip.key, None, str(e)
     if spans is not None:
         from .spans import host_spans_shots
         try:
             if scene is not None:
-                rects, shots = inference._shot_rects(frames, detector, batch_size, track, scene)
+                rects, shots = inference._shot_rects(frames, detector, batch_size, track, scene, **skw)
             elif track is not None:
-                rects, shots = inference._track_rects(frames, detector, batch_size, track), [(0, clip.n)]
+                rects, shots = inference._track_rects(frames, detector, batch_size, track, **skw), [(0, clip.n)]
             else:
-                rects, shots = inference._detect_rects(frames, detector, batch_size), [(0, clip.n)]
+                rects, shots = inference._detect_rects(frames, detector, batch_size, **skw), [(0, clip.n)]
             filled, kept = host_spans_shots(rects, shots, spans)
             boxes, valid = host_boxes_shots(filled, shots, clip.H, clip.W, pads, T, 0)
             return clip.key, SpanBoxes(boxes, valid, kept), None
@@ -543,9 +724,9 @@ def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None, scene=
         try:
             if hold is None and T in (0, 5):
                 det = inference.face_detect(frames, detector=detector, pads=list(pads), nosmooth=(T == 0), batch_size=batch_size,
-                                            scene_cuts=scene, **({} if track is None else {"face_track": track}))
+                                            scene_cuts=scene, **({} if track is None else {"face_track": track}), **skw)
                 return clip.key, np.array([c for _, c in det], dtype=np.int64).reshape(-1, 4), None
-            rects, shots = inference._shot_rects(frames, detector, batch_size, track, scene)
+            rects, shots = inference._shot_rects(frames, detector, batch_size, track, scene, **skw)
             boxes, valid = host_boxes_shots(rects, shots, clip.H, clip.W, pads, T, hold)
             return clip.key, boxes if hold is None else RunBoxes(boxes, valid), None
         except (ValueError, OverflowError) as e:
@@ -553,8 +734,8 @@ def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None, scene=
 
     def clip_rects():
         if track is None:
-            return inference._detect_rects(frames, detector, batch_size)
-        return inference._track_rects(frames, detector, batch_size, track)
+            return inference._detect_rects(frames, detector, batch_size, **skw)
+        return inference._track_rects(frames, detector, batch_size, track, **skw)
 
     try:
         if hold is not None:                     # the pass-through rule on the host: the same rects, `host_boxes_runs`
@@ -562,7 +743,7 @@ def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None, scene=
             return clip.key, RunBoxes(*host_boxes_runs(rects, clip.H, clip.W, pads, T, hold)), None
         if T in (0, 5):
             det = inference.face_detect(frames, detector=detector, pads=list(pads), nosmooth=(T == 0), batch_size=batch_size,
-                                        **({} if track is None else {"face_track": track}))
+                                        **({} if track is None else {"face_track": track}), **skw)
             boxes = np.array([c for _, c in det], dtype=np.int64).reshape(-1, 4)
         else:                                    # face_detect's window is 5: its two halves with another T
             rects = clip_rects()
@@ -575,7 +756,7 @@ def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None, scene=
 
 
 def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_batches=16, max_group_bytes=1 << 30, no_face_hold=None,
-                face_track=None, scene_cuts=None, track_spans=None, all_faces=None):
+                face_track=None, scene_cuts=None, track_spans=None, all_faces=None, det_stride=None):
     """`inference.face_detect(frames, detector, pads, nosmooth=(T == 0))` for every `DetectJob` of the iterable `jobs`, the frames
     of successive clips packed into detector batches of exactly `batch_size`.  A generator: jobs are consumed lazily and one
     `(key, boxes, error)` comes out per job, in job order - `boxes` the int array [n,4] of (y1, y2, x1, x2) `face_detect` returns
@@ -621,12 +802,22 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
     track tolerates are `track_spans.bridge`.  It needs `track_spans`; with `face_track` (one face) or `no_face_hold` it is a
     ValueError.  `boxes` is then a `faces.FaceSpans`: `.tracks` is the list of `FaceSpan(slot, a, b, boxes)` - frames [a, b) of the
     clip, `boxes` int [b - a, 4] of (y1, y2, x1, x2) - sorted by (a, slot), and `.dropped` the number of candidates that found no
-    free slot."""
+    free slot.
+
+    `det_stride`: None or 1 (default: every frame is shown to the detector), or an int N in 2..32: key-frame detection (DESIGN.md
+    3zb, not the reference's behaviour and not accuracy-neutral).  The detector sees the frames 0, N, 2N, ... and the last one of
+    every clip - with `scene_cuts`, of every shot - and one more launch interpolates the rects of the frames between two detected
+    key frames (`face_detection/stride.py` states the rule); a missed key frame leaves 2N - 1 frames without a face, which every
+    option above then treats as it treats any such frame.  With `face_track` the track steps from key frame to key frame: its
+    `reseed` counts key frames and its `min_iou` is unchanged; with `all_faces` a track tolerates `max(0, (bridge + 1) // N - 1)`
+    missed key frames, exactly the misses the span rule bridges.  Exactly as `face_detect(det_stride=N)` does for the clip alone."""
     from ..inference import halving
     from .scene import check_scene
     from .faces import FaceSpans, check_faces
     from .spans import check_spans
+    from .stride import check_stride
     from .track import check_track
+    stride = check_stride(det_stride)
     hold = check_hold(no_face_hold)
     track = check_track(face_track)
     scene = check_scene(scene_cuts)
@@ -648,6 +839,7 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
         tkw["spans"] = spans
     if faces is not None:
         tkw["faces"] = faces
+    pkw = dict(tkw) if stride == 1 else dict(tkw, stride=stride)       # `_per_clip`'s keywords
     if batch_size < 1 or group_batches < 1:
         raise ValueError("batch_size and group_batches must be at least 1")
     if not 0 <= int(T) <= MAX_T:
@@ -676,7 +868,7 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
                 if group:
                     break                                  # the jobs before it first
                 held = None
-                yield _per_clip(detector, c, pads, T, batch_size, hold, **tkw)
+                yield _per_clip(detector, c, pads, T, batch_size, hold, **pkw)
                 del c
                 continue
             if shape is not None and ((c.H, c.W) != shape or n_bytes + c.nbytes > max_group_bytes):
@@ -695,6 +887,8 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
         def run_group(size):
             nonlocal batch_size
             batch_size = size                              # a halved batch holds for the rest of the run
+            if stride > 1:
+                return _detect_group_keys(detector, clips, pads, T, size, stride, hold, **tkw)
             return _detect_group(detector, clips, pads, T, size, *(() if hold is None else (hold,)), **tkw)
 
         if clips:
@@ -731,4 +925,4 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
         del c
         while results:
             res = results.pop(0)
-            yield _per_clip(detector, res, pads, T, batch_size, hold, **tkw) if isinstance(res, _Clip) else res
+            yield _per_clip(detector, res, pads, T, batch_size, hold, **pkw) if isinstance(res, _Clip) else res

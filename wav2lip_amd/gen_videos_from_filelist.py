@@ -72,8 +72,10 @@ def build_main_parser():
     `--no_face_hold G` generates a line with frames without a face instead of skipping it (`inference.add_hold_flag`).
     `--face_track PICK` follows one face through every line's clip (`inference.add_track_flags`), with and without
     `--packed_face_det`, and so does `--scene_cuts THRESH`, which boxes and tracks every shot of a clip alone
-    (`inference.add_scene_flag`).  `cli_parser` stays the reference's surface plus the two precision flags."""
-    from .inference import add_blend_flags, add_color_match_flag, add_det_scale_flag, add_hold_flag, add_scene_flag, add_track_flags
+    (`inference.add_scene_flag`), and `--face_det_stride N`, which shows the detector every Nth frame of a clip or
+    shot and interpolates the boxes between (`inference.add_stride_flag`).  `cli_parser` stays the reference's surface plus the two precision flags."""
+    from .inference import (add_blend_flags, add_color_match_flag, add_det_scale_flag, add_hold_flag, add_scene_flag, add_stride_flag,
+                            add_track_flags)
     p = build_cli_parser()
     p.add_argument('--packed_face_det', default=False, action='store_true',
                    help='Detect faces of successive clips in shared detector batches (face_detection.detect_many)')
@@ -83,6 +85,7 @@ def build_main_parser():
     add_hold_flag(p)
     add_track_flags(p)
     add_scene_flag(p)
+    add_stride_flag(p)
     return p
 
 

@@ -211,8 +211,9 @@ def build_cli_parser():
     `--blend_feather N` / `--blend_top FRACTION`, the feathered mouth-region paste, `--color_match {mean,full}`, colour matching
     of the prediction to its crop (absent by default), `--no_face_hold G`, the pass-through for frames without a face (absent by
     default), `--face_track PICK` with its three companions, tracked face selection (`face_detection/track.py`; absent by
-    default), and `--scene_cuts THRESH`, every shot of the clip boxed and tracked alone (`face_detection/scene.py`; absent by
-    default)"""
+    default), `--scene_cuts THRESH`, every shot of the clip boxed and tracked alone (`face_detection/scene.py`; absent by
+    default), and `--face_det_stride N`, the detector on every Nth frame and interpolated boxes between
+    (`face_detection/stride.py`; 1 by default)"""
     p = build_parser()
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
                    help='Generator arithmetic: fp32 (default, matches the reference) or bf16 storage (faster; frames differ by '
@@ -231,12 +232,19 @@ def build_cli_parser():
     add_hold_flag(p)
     add_track_flags(p)
     add_scene_flag(p)
+    add_stride_flag(p)
     return p
 
 
 def add_scene_flag(p):
     """`--scene_cuts THRESH` on a command's parser (face_detection/scene.py holds the rule): absent by default"""
     from .face_detection.scene import add_scene_flag as add
+    add(p)
+
+
+def add_stride_flag(p):
+    """`--face_det_stride N` on a command's parser (face_detection/stride.py holds the rule): 1 by default"""
+    from .face_detection.stride import add_stride_flag as add
     add(p)
 
 
@@ -706,10 +714,15 @@ def halving(run, batch_size):
             print('Recovering from OOM error; New batch size: {}'.format(batch_size))
 
 
-def _detect_rects(images, detector, batch_size, ranks=None):
+def _detect_rects(images, detector, batch_size, ranks=None, det_stride=1):
     """inference.py:75-88: one rect (or None) per frame, in batches under `halving`.  With `ranks` every rank detects the frames
     of its contiguous shard and the per-frame rects (four numbers each) are all-gathered: the box smoothing that follows needs
-    them all, on every rank, in frame order."""
+    them all, on every rank, in frame order.  With `det_stride` N > 1 (face_detection/stride.py) the detector sees
+    the clip's key frames only and `host_stride_fill` gives the frames between them their rects."""
+    if det_stride > 1:
+        from .face_detection.stride import host_stride_fill, key_frames
+        keys = key_frames(len(images), det_stride)
+        return host_stride_fill(_detect_rects([images[i] for i in keys], detector, batch_size), len(images), det_stride)
     if ranks is not None and ranks.dist is not None and ranks.world > 1:
         from . import sharding
         lo, hi = sharding.shard_range(len(images), ranks.rank, ranks.world)
@@ -727,12 +740,17 @@ def _detect_rects(images, detector, batch_size, ranks=None):
     return halving(run, batch_size)
 
 
-def _track_rects(images, detector, batch_size, track):
+def _track_rects(images, detector, batch_size, track, det_stride=1):
     """`_detect_rects` under tracked face selection (face_detection/track.py): the candidates of every batch go into
     device arenas (`FaceAlignment.cands_for_batch`), ONE w2l_face_track_segments launch with one segment follows the face through
     the clip and ONE copy brings rects and flags back.  A frame the device does not decide (RECT_HOST) sends the whole clip through
     the host statement of the same rule: `get_candidates_for_batch` (which runs `host_top_rects` on such a frame) and
-    `host_track`.  The detector's RuntimeError halves the batch as there."""
+    `host_track`.  The detector's RuntimeError halves the batch as there.  With `det_stride` N > 1 the track steps through the
+    clip's key frames and `host_stride_fill` gives the frames between them their rects."""
+    if det_stride > 1:
+        from .face_detection.stride import host_stride_fill, key_frames
+        keys = key_frames(len(images), det_stride)
+        return host_stride_fill(_track_rects([images[i] for i in keys], detector, batch_size, track), len(images), det_stride)
     from .face_detection.s3fd import RECT_FOUND, RECT_HOST
     from .face_detection.track import TRACK_SEGMENT, host_track, track_segments
     n, K = len(images), track.cands
@@ -765,12 +783,28 @@ def _track_rects(images, detector, batch_size, track):
     return halving(run, batch_size)
 
 
-def _shot_rects(images, detector, batch_size, track, scene):
+def _shot_rects(images, detector, batch_size, track, scene, det_stride=1):
     """`_detect_rects` / `_track_rects` under scene-cut detection (face_detection/scene.py): (one rect or None per
     frame, the shots [(a, b)] of the clip).  Every batch is uploaded ONCE as a device tensor: w2l_frame_hist_rows reads it into the
     clip's signature arena and the detector takes the same tensor.  After the last batch ONE w2l_scene_cuts launch and one small
     copy give the cut flags.  With `track` the single w2l_face_track_segments launch then gets one segment per shot - a fresh
-    track at every cut - and a frame the device does not decide (RECT_HOST) sends every shot through `host_track` on its own."""
+    track at every cut - and a frame the device does not decide (RECT_HOST) sends every shot through `host_track` on its own.
+    With `det_stride` N > 1 the keys are per shot, so the cuts come first - a pass of signatures over every frame - and the key
+    frames of each shot then go through `_detect_rects` (all shots' keys in shared batches) or `_track_rects` (a shot at a time: a
+    fresh track each) and `host_stride_fill`."""
+    if det_stride > 1 and len(images):
+        from .face_detection.many import _Clip, _host_shots
+        from .face_detection.stride import host_stride_fill, host_stride_fill_shots, key_frames, shot_key_frames
+        h, w = images[0].shape[:2]
+        shots = halving(lambda size: _host_shots(detector, images, _Clip(None, images, len(images), h, w, 0), size, scene), batch_size)
+        if track is None:
+            key_rects = _detect_rects([images[i] for i in shot_key_frames(shots, det_stride)], detector, batch_size)
+            return host_stride_fill_shots(key_rects, shots, det_stride), shots
+        rects = []
+        for a, b in shots:
+            key_rects = _track_rects([images[a + i] for i in key_frames(b - a, det_stride)], detector, batch_size, track)
+            rects += host_stride_fill(key_rects, b - a, det_stride)
+        return rects, shots
     from .face_detection.s3fd import RECT_FOUND, RECT_HOST
     from .face_detection.scene import SIG_WORDS, clip_cuts, frame_signatures, host_track_shots, split_shots
     from .face_detection.track import TRACK_SEGMENT, track_segments
@@ -834,15 +868,17 @@ def detector_from_args(args, device, state_dict=None):
 
 def detect_kw_from_args(args):
     """the `no_face_hold=` / `face_track=` keywords of `face_detect`, `detect_many` and `LipsyncStreams` for a parsed command line,
-    and the `scene_cuts=` of the first two (a parser of the live path has no such flag): none for an absent flag; a lone
-    `--face_track_*` flag is a ValueError"""
+    and the `scene_cuts=` and `det_stride=` of the first two (a parser of the live path has no such flags): none for an absent
+    flag (for `--face_det_stride 1`); a lone `--face_track_*` flag is a ValueError"""
     from .face_detection.scene import scene_from_args, scene_kw
+    from .face_detection.stride import stride_from_args
     from .face_detection.track import track_from_args
-    return {**_hold_kw(getattr(args, 'no_face_hold', None)), **_track_kw(track_from_args(args)), **scene_kw(scene_from_args(args))}
+    return {**_hold_kw(getattr(args, 'no_face_hold', None)), **_track_kw(track_from_args(args)), **scene_kw(scene_from_args(args)),
+            **stride_from_args(args)}
 
 
 def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None, ranks=None, precision=None, det_scale=None,
-                no_face_hold=None, face_track=None, scene_cuts=None):
+                no_face_hold=None, face_track=None, scene_cuts=None, det_stride=None):
     """inference.py:68-104: S3FD boxes per frame (HIP detector), padding, temporal smoothing; returns
     [[face crop, (y1, y2, x1, x2)], ...].  Called as the reference calls it - `face_detect(images)` - pads / nosmooth /
     face_det_batch_size come from the module-level `args` and the detector is built as inference.py:69-70 does
@@ -871,8 +907,16 @@ def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None
     more than the threshold (not the reference's behaviour), and every shot is handled as a clip of its frames alone:
     a fresh track at its start, a hold that does not look back past it, pads, clipping and smoothing per shot (a shot shorter than
     5 frames takes the wrapped short-clip window).  Without a hold a frame without a face in any shot is still the ValueError.  Not
-    with `ranks` of more than one process: a cut compares a frame with the one before it, which may lie in another shard."""
+    with `ranks` of more than one process: a cut compares a frame with the one before it, which may lie in another shard.
+
+    `det_stride`: None or 1 (default) shows every frame to the detector, as the reference does.  An int N in 2..32 shows it the key
+    frames 0, N, 2N, ... and the last one of the clip - with `scene_cuts`, of every shot - and interpolates the rects of the frames
+    between two detected key frames (face_detection/stride.py; not the reference's behaviour, and not
+    accuracy-neutral).  A missed key frame leaves 2N - 1 frames without a face; everything after the rects is as without it.  With
+    `face_track` the track steps from key frame to key frame: `reseed` counts key frames, `min_iou` is unchanged.  Not with `ranks`
+    of more than one process: a frame is interpolated from key frames of other shards."""
     from .face_detection.many import boxed_runs, check_hold, hold_fill
+    from .face_detection.stride import check_stride, stride_kw
     from .face_detection.scene import check_scene
     from .face_detection.track import check_track
     from .face_detection.s3fd import check_det_scale
@@ -884,6 +928,9 @@ def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None
     scene = check_scene(scene_cuts)
     if scene is not None and ranks is not None and ranks.dist is not None and ranks.world > 1:
         raise ValueError("scene_cuts runs on one GPU: a cut compares a frame with the one before it, in another shard")
+    skw = stride_kw(check_stride(det_stride))
+    if skw and ranks is not None and ranks.dist is not None and ranks.world > 1:
+        raise ValueError("det_stride runs on one GPU: a frame is interpolated from key frames of other shards")
     if precision is not None:
         check_precision(precision)
     if det_scale is not None:
@@ -909,10 +956,11 @@ def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None
     nosmooth = args.nosmooth if nosmooth is None else nosmooth
     batch_size = args.face_det_batch_size if batch_size is None else batch_size
     if scene is None:
-        rects = _detect_rects(images, detector, batch_size, ranks) if track is None else _track_rects(images, detector, batch_size, track)
+        rects = (_detect_rects(images, detector, batch_size, ranks, **skw) if track is None else
+                 _track_rects(images, detector, batch_size, track, **skw))
         shots = [(0, len(rects))]                # the reference's one take
     else:
-        rects, shots = _shot_rects(images, detector, batch_size, track, scene)
+        rects, shots = _shot_rects(images, detector, batch_size, track, scene, **skw)
     if hold is not None:
         rects = [r for a, b in shots for r in hold_fill(rects[a:b], hold)]
     if any(r is None for r in rects) and (hold is None or len(rects) == 1):
@@ -1020,7 +1068,8 @@ def main(argv=None, keep_frames=True, backend="nccl"):
     for given, why in ((mjpg, "--out_codec mjpg runs on one GPU: a sharded run gathers raw frames (compressed shards are not gathered yet)"),
                        ("no_face_hold" in detect_kw, "--no_face_hold runs on one GPU: the hold looks back over the frames of other shards"),
                        ("face_track" in detect_kw, "--face_track runs on one GPU: the track looks back over the frames of other shards"),
-                       ("scene_cuts" in detect_kw, "--scene_cuts runs on one GPU: a cut compares a frame with the one before it, in another shard")):
+                       ("scene_cuts" in detect_kw, "--scene_cuts runs on one GPU: a cut compares a frame with the one before it, in another shard"),
+                       ("det_stride" in detect_kw, "--face_det_stride runs on one GPU: a frame is interpolated from key frames of other shards")):
         if given and int(os.environ.get("WORLD_SIZE", "1")) > 1:     # before the process group and any device work
             raise ValueError(why)
     ranks = sharding.init_from_env(backend)

@@ -87,10 +87,12 @@ def build_main_parser():
     """what `main()` parses: `build_cli_parser` plus `--face_det_scale K`, the size of the frame the detector sees
     (`inference.add_det_scale_flag`), `--blend_feather N` / `--blend_top FRACTION`, the blended paste
     (`inference.add_blend_flags`), and `--color_match {mean,full}`, the prediction's colours matched to its crop
-    (`inference.add_color_match_flag`); `cli_parser` stays the reference's surface plus the two precision flags"""
-    from .inference import add_blend_flags, add_color_match_flag, add_det_scale_flag
+    (`inference.add_color_match_flag`), and `--face_det_stride N`, the detector on every Nth frame of a line's frame sequence
+    (`inference.add_stride_flag`); `cli_parser` stays the reference's surface plus the two precision flags"""
+    from .inference import add_blend_flags, add_color_match_flag, add_det_scale_flag, add_stride_flag
     p = build_cli_parser()
     add_det_scale_flag(p)
+    add_stride_flag(p)
     add_blend_flags(p)
     add_color_match_flag(p)
     return p
@@ -251,20 +253,33 @@ def first_rect(detector, frames):
     return detector.get_detections_for_batch(frames[:1])[0]
 
 
-def clip_boxes(detector, frames, index, pads, batch_size):
+def clip_boxes(detector, frames, index, pads, batch_size, det_stride=1):
     """:73-103 for the frame sequence frames[index]: int array [len(index), 4] of (y1, y2, x1, x2), padded, clipped and smoothed
     with T = 5 over that sequence; ValueError('Face not detected!...') when a frame has no face.  A sequence without duplicates
     goes through `face_detection.detect_many` on the frames where they lie.  With duplicates (`tts`) every frame is detected
-    once, its rect is repeated per row, and the finish is detect_many's host form (`host_boxes`): no frame is copied."""
+    once, its rect is repeated per row, and the finish is detect_many's host form (`host_boxes`): no frame is copied.
+    `det_stride` N > 1 (`--face_det_stride`): the detector sees the key frames of the SEQUENCE only and the rows
+    between them are interpolated - `detect_many(det_stride=N)`; with duplicates the distinct key frames are gathered and detected
+    once each, and `stride.host_stride_fill` fills the sequence."""
     from . import face_detection
     from .face_detection import many
+    from .face_detection.stride import host_stride_fill, key_frames, stride_kw
     n = len(index)
     if list(index) == list(range(n)):
         (_, boxes, error), = face_detection.detect_many(detector, [face_detection.DetectJob(0, frames[:n])], pads=pads, T=5,
-                                                        batch_size=batch_size)
+                                                        batch_size=batch_size, **stride_kw(det_stride))
         if error is not None:
             raise ValueError(error)
         return boxes
+    if det_stride > 1:
+        import torch
+        keys = [index[k] for k in key_frames(n, det_stride)]
+        seen = sorted(set(keys))
+        found = dict(zip(seen, _device_rects(detector, frames[torch.tensor(seen, device=frames.device)], batch_size)))
+        rects = host_stride_fill([found[i] for i in keys], n, det_stride)
+        if any(r is None for r in rects):
+            raise ValueError(many.NO_FACE)
+        return many.host_boxes(rects, int(frames.shape[1]), int(frames.shape[2]), pads, 5)
     rects = _device_rects(detector, frames, batch_size)
     if any(rects[i] is None for i in index):
         raise ValueError(many.NO_FACE)
@@ -287,6 +302,7 @@ def clip_jobs(args, lines, ranks, detector, tracks, report=None):
     receives (fps, frame size (w, h), PCM16 audio, rate) for the sink that opens the line's writer; `report[line index]` (when
     given) what was decided: frame sizes after each resize, the factor, the index list, the boxes."""
     from . import multiclip
+    from .face_detection.stride import stride_kw
     with tempfile.TemporaryDirectory(prefix="w2l_real_videos_") as tmpdir:
         for idx, line in gv.lines_of_rank(lines, ranks):
             video, audio_src = line.strip().split()
@@ -329,7 +345,8 @@ def clip_jobs(args, lines, ranks, detector, tracks, report=None):
             h, w = int(frames.shape[1]), int(frames.shape[2])
             note.update(factor=factor, rescaled=(h, w), index=list(index))
             try:
-                boxes = clip_boxes(detector, frames, index, args.pads, args.face_det_batch_size)
+                boxes = clip_boxes(detector, frames, index, args.pads, args.face_det_batch_size,
+                                   **stride_kw(getattr(args, 'face_det_stride', 1)))
             except ValueError as e:
                 gv._skip(idx, line, str(e))
                 continue
