@@ -329,6 +329,63 @@ def test_the_detector_sees_the_batches_of_the_key_frames_only(cuda, env, monkeyp
     assert keys < frames and seen == [DET_BATCH] * -(-keys // DET_BATCH)
 
 
+# ---------------------------------------------------------------- the launches of a group
+HIST, CUTS, TRACK, ALL, SPAN = "w2l_frame_hist_rows", "w2l_scene_cuts", "w2l_face_track_segments", "w2l_face_tracks_all_segments", \
+    "w2l_face_spans_segments"
+SEGMENTS, RUNS = "w2l_face_boxes_segments", "w2l_face_boxes_runs"
+# option combination -> the library entries of one group in launch order (the module text of face_detection/many.py), at stride 1
+# and at stride 2: there the one expand launch sits between the track, if any, and what reads the full arenas
+LAUNCHES = {
+    "default": ([SEGMENTS], [NEW, SEGMENTS]),
+    "hold": ([RUNS], [NEW, RUNS]),
+    "track": ([TRACK, SEGMENTS], [TRACK, NEW, SEGMENTS]),
+    "scene": ([HIST, CUTS, SEGMENTS], [HIST, CUTS, NEW, SEGMENTS]),
+    "track+scene": ([HIST, CUTS, TRACK, SEGMENTS], [HIST, CUTS, TRACK, NEW, SEGMENTS]),
+    "spans": ([SPAN, RUNS], [NEW, SPAN, RUNS]),
+    "spans+all_faces": ([ALL, SPAN, RUNS], [ALL, NEW, SPAN, RUNS]),
+}
+
+
+def test_every_option_keeps_its_launch_sequence(cuda, env, monkeypatch):
+    """one group of three host clips under every option combination, at stride 1 and 2: the library entries in the order of
+    LAUNCHES, every detector batch before the finish, and exactly one `.cpu()` - read at the library and at torch, not at the
+    Python that sits between them"""
+    from wav2lip_amd import _lib, face_detection
+    det, clips = env["det"], env["clips"]
+    options = {
+        "default": {},
+        "hold": dict(no_face_hold=1),
+        "track": dict(face_track="largest"),
+        "scene": dict(scene_cuts=SCENE),
+        "track+scene": dict(face_track="largest", scene_cuts=SCENE),
+        "spans": dict(track_spans=face_detection.TrackSpans(1, 4, 0)),
+        "spans+all_faces": dict(track_spans=face_detection.TrackSpans(1, 4, 0), all_faces=face_detection.AllFaces(2, 4, 0.25)),
+    }
+    assert list(options) == list(LAUNCHES)
+    lib, log, copies = _lib.load(), [], []
+
+    def spied(name, fn):
+        return lambda *a, **k: log.append(name) or fn(*a, **k)
+
+    for name in (HIST, CUTS, TRACK, ALL, NEW, SPAN, SEGMENTS, RUNS):
+        monkeypatch.setattr(lib, name, spied(name, getattr(lib, name)))
+    for name in ("rects_for_rows", "cands_for_rows"):
+        monkeypatch.setattr(det, name, spied("batch", getattr(det, name)))
+    to_host = torch.Tensor.cpu
+    monkeypatch.setattr(torch.Tensor, "cpu", lambda t, *a, **k: copies.append(1) or to_host(t, *a, **k))
+    jobs = [face_detection.DetectJob(k, list(clips[k])) for k in ("c1", "c4", "kg")]
+    for which, kw in options.items():
+        for N, want in zip((None, 2), LAUNCHES[which]):
+            del log[:], copies[:]
+            out = list(face_detection.detect_many(det, jobs, pads=PADS, T=5, batch_size=DET_BATCH, det_stride=N, **kw))
+            assert [k for k, _, _ in out] == ["c1", "c4", "kg"]
+            assert [e for e in log if e != "batch"] == want, (which, N)
+            assert len(copies) == 1, (which, N)                # the group's one copy back
+            assert log.index(want[-1]) > len(log) - 1 - log[::-1].index("batch")       # every batch is queued before the finish
+            if "scene" in which and N is None:                 # the cut flags cross while the detector runs
+                assert log.index(CUTS) < log.index("batch") < log.index(want[-1]), which
+
+
 # ---------------------------------------------------------------- the command
 def test_the_inference_command_writes_a_video_whose_boxes_are_the_models(cuda, env, tmp_path, monkeypatch):
     from scipy.io import wavfile

@@ -24,7 +24,8 @@ With `--scene_cuts THRESH` (scene-cut detection) the two loops are
 `scene_cuts=THRESH` - "packed" and "packed_scene" - alternated the same way: what the signature launch over every frame, the cut
 launch and the small copy per group cost.  The seeded clips cycle 16 noise frames whose histograms are alike, so at 0.3 no cut
 fires on them and `boxes_that_differ` must be 0 (a clip without a cut is the feature switched off); the per-shot tables are built
-all the same.  Nothing here says anything about detection quality on real footage.
+all the same.  Nothing here says anything about detection quality on real footage.  `--face_track PICK` may be given with it: the
+second loop then runs with `scene_cuts=THRESH, face_track=PICK` - every shot tracked alone - against the same plain first loop.
 
 With `--all_faces F` (every face of a shot) the two loops are the packed detector with `track_spans` alone
 (bridge 25, min_len 1) and with `all_faces=AllFaces(F)` as well - "packed_spans" and "packed_all_faces" - alternated the same way:
@@ -231,8 +232,8 @@ def main(argv=None):
     ap.add_argument("--expand_kernel_ms", default=False, action="store_true",
                     help="time w2l_face_rects_expand_segments alone (64 segments of 4096 frames) and print one JSON line")
     a = ap.parse_args(argv)
-    if sum(v is not None for v in (a.face_track, a.scene_cuts, a.all_faces, a.det_stride)) > 1:
-        ap.error("--face_track, --scene_cuts, --all_faces and --det_stride are four comparisons: give one")
+    if sum(v is not None for v in (a.face_track if a.scene_cuts is None else None, a.scene_cuts, a.all_faces, a.det_stride)) > 1:
+        ap.error("--face_track, --scene_cuts (alone or with --face_track), --all_faces and --det_stride are four comparisons: give one")
     if a.track_kernel_ms:
         return track_kernel_ms(torch.device("cuda", 0), a.alternations)
     if a.expand_kernel_ms:
@@ -245,10 +246,12 @@ def main(argv=None):
     loops = {"packed": (run_packed, detector(dev, a.precision)), "per_clip": (run_loop, detector(dev, a.precision))}
     if a.face_track is not None:
         out["face_track"] = a.face_track
+    if a.face_track is not None and a.scene_cuts is None:
         loops["packed_tracked"] = (lambda det, clips, batch: run_packed(det, clips, batch, face_track=a.face_track), loops.pop("per_clip")[1])
     if a.scene_cuts is not None:
         out["scene_cuts"] = a.scene_cuts
-        loops["packed_scene"] = (lambda det, clips, batch: run_packed(det, clips, batch, scene_cuts=a.scene_cuts), loops.pop("per_clip")[1])
+        loops["packed_scene"] = (lambda det, clips, batch: run_packed(det, clips, batch, scene_cuts=a.scene_cuts, face_track=a.face_track),
+                                 loops.pop("per_clip")[1])
     if a.det_stride is not None:
         out["det_stride"] = a.det_stride
         loops["packed_stride"] = (lambda det, clips, batch: run_packed(det, clips, batch, det_stride=a.det_stride), loops.pop("per_clip")[1])

@@ -40,8 +40,13 @@ run unchanged over a table of F segments per segment, and the one copy back also
 
 With `det_stride=N` (opt-in) the address table, the batches and the rect or candidate arenas hold the KEY frames of
 every clip - of every shot under `scene_cuts` - alone, the track launches step from key to key, and ONE
-w2l_face_rects_expand_segments launch writes the full arenas every finish above then reads as it always did
-(`_detect_group_keys`, `face_detection/stride.py`).
+w2l_face_rects_expand_segments launch - after the track launch, if any - writes the full arenas every finish above then reads as
+it always did (`face_detection/stride.py`); under `scene_cuts` the cut flags are then waited for BEFORE the batches.
+
+One routine, `_detect_group`, is all of this: it takes the options as one `_Options` record, `_Tables` lays out and fills every
+table of a group - for its clips, for its shots, over full rows or key rows - and one of three finishes (`_finish_plain`,
+`_finish_spans`, `_finish_faces`) ends in the one copy back and returns `(boxes, valid, status, kept)`.  A clip the device leaves
+to the host goes through `_per_clip`: `inference.clip_rects` and the host statement of the same finish.
 """
 import collections
 
@@ -273,6 +278,10 @@ class BoxOut:
         span_rows, span_status = self._parts(host)[5:7]
         return span_rows.reshape(-1, 4), span_status.reshape(-1, 2)
 
+    def split_extra(self, host):
+        """the trailing `extra` words of the buffer's host copy"""
+        return self._parts(host)[-1]
+
 
 def _finish_segments(n_seg, segs, rects, flags, pads, T, boxes, status):
     """w2l_face_boxes_segments: the group's clips in one launch"""
@@ -303,143 +312,79 @@ def _fold_shot_status(shot_status, shots_of):
     return out
 
 
-def _detect_group(detector, clips, pads, T, batch_size, hold=None, track=None, scene=None, spans=None, faces=None):
-    """One group on the device.  clips: _Clips of one frame shape, each with at least one frame.  Returns numpy (boxes int32 [R,4]
-    in (y1, y2, x1, x2) order, rows in clip order; status int32 [clips,2]); with `hold` (the pass-through rule) a third array,
-    valid int32 [R], comes between them - still one launch and one copy back.  With `track` (a FaceTrack) the batches leave
-    candidates and one more launch, before the finish, chooses the rect of every frame; its status words come back in the same
-    copy and are all 0 (the table is built here).  With `scene` (a SceneCuts) the signature and the cut launch run first, their R
-    flags come back while the detector batches run, and the track and the finish get one segment per shot; the status returned is
-    still per clip (`_fold_shot_status`).  With `spans` (a TrackSpans, never with `hold`) the group ends in `_finish_spans`, and
-    with `faces` too (an AllFaces, never with `track`) in `_finish_faces`."""
-    dev = torch.device(detector.device)
-    H, W = clips[0].H, clips[0].W
-    R = sum(c.n for c in clips)
-    padded = (R + batch_size - 1) // batch_size * batch_size
-    # ---- one staging buffer: [address table, `padded` entries][segment table][host frames of the group]
-    st = Staging(dev)
-    addresses, segments = st.table(ADDRESS, padded), st.table(BOX_SEGMENT, len(clips))
-    tracks = None if track is None else st.table(TRACK_SEGMENT, len(clips))
-    wide = None if faces is None or scene is not None else st.table(BOX_SEGMENT, faces.max_faces * len(clips))
-    src = [st.place(c.frames) for c in clips]
-    st.allocate()
-    addr, segs = st.view(addresses), st.view(segments)
-    frame_bytes = H * W * 3
-    r = 0
-    for k, c in enumerate(clips):
-        addr[r:r + c.n] = np.uint64(st.address(src[k])) + np.arange(c.n, dtype=np.uint64) * np.uint64(frame_bytes)
-        segs[k] = (r, c.n, H, W)
-        if tracks is not None:
-            st.view(tracks)[k] = (r, c.n, -1, 0)             # a clip: no carried state
-        r += c.n
-    addr[R:] = addr[R - 1]
-    if wide is not None:
-        from .faces import expand_segments
-        st.view(wide)[:] = np.array(expand_segments(segs.tolist(), faces.max_faces, R), dtype=BOX_SEGMENT)
-    st.upload()
-    if scene is not None:                                    # queued before the batches: the flags cross while the detector runs
-        _, cuts_host, cuts_ready = _queue_cuts(st.tensor(addresses), st.tensor(segments), len(clips), R, H, W, scene, dev)
-    arenas = detect_rows(detector, st.tensor(addresses), [(H, W, 0, padded)], batch_size, padded, track,     # rows [R, padded): scratch
-                         **({} if faces is None else {"K": faces.cands}))
-    wide_dev = None if wide is None else st.tensor(wide)
-    n_seg, seg_dev, track_dev, shots_of = len(clips), st.tensor(segments), None if tracks is None else st.tensor(tracks), None
-    if scene is not None:
-        cuts_ready.synchronize()
-        cuts = cuts_host.numpy()
-        if cuts[R:].any():
-            raise AssertionError("w2l_scene_cuts did not follow a clip's segment (status %s)" % cuts[R:].tolist())
-        shots_of = [split_shots(c.n, cuts[r0:r0 + c.n]) for c, r0 in zip(clips, np.cumsum([0] + [c.n for c in clips[:-1]]).tolist())]
-        st2, n_seg = Staging(dev), sum(len(s) for s in shots_of)
-        segments2 = st2.table(BOX_SEGMENT, n_seg)
-        tracks2 = None if track is None else st2.table(TRACK_SEGMENT, n_seg)
-        wide2 = None if faces is None else st2.table(BOX_SEGMENT, faces.max_faces * n_seg)
-        st2.allocate()
-        k, r = 0, 0
-        for c, shots in zip(clips, shots_of):
-            for a, b in shots:
-                st2.view(segments2)[k] = (r + a, b - a, H, W)
-                if tracks2 is not None:
-                    st2.view(tracks2)[k] = (r + a, b - a, -1, 0)     # a shot: a fresh track
-                k += 1
-            r += c.n
-        if wide2 is not None:
-            from .faces import expand_segments
-            st2.view(wide2)[:] = np.array(expand_segments(st2.view(segments2).tolist(), faces.max_faces, R), dtype=BOX_SEGMENT)
-        st2.upload()
-        seg_dev, track_dev = st2.tensor(segments2), None if tracks2 is None else st2.tensor(tracks2)
-        wide_dev = None if wide2 is None else st2.tensor(wide2)
-    if faces is not None:
-        return _finish_faces(n_seg, seg_dev, wide_dev, arenas, faces, spans, R, pads, T, dev, [c.n for c in clips], shots_of)
-    if spans is not None:
-        return _finish_spans(n_seg, seg_dev, track_dev, arenas, track, spans, R, pads, T, dev, [c.n for c in clips], shots_of)
-    out = BoxOut(R, n_seg, hold is not None, track is not None, dev)
-    if track is not None:
-        track_rows(n_seg, track_dev, arenas, track, out.track_status)
-    if hold is None:
-        _finish_segments(n_seg, seg_dev, arenas.rects, arenas.flags, pads, T, out.boxes, out.status)
-    else:
-        _finish_runs(n_seg, seg_dev, arenas.rects, arenas.flags, R, pads, T, hold, out.boxes, out.valid, out.status)
-    # the group's one copy back; it also ends the stream's use of the staging buffers
-    boxes, valid, status, _ = out.split(out.buffer.cpu().numpy())
-    if shots_of is not None:
-        status = _fold_shot_status(status, shots_of)
-    return (boxes, status) if hold is None else (boxes, valid, status)
+_Options = collections.namedtuple("_Options", "pads T hold track scene spans faces stride")
+_Options.__doc__ = """what `detect_many` was asked for, checked: pads (top, bottom, left, right), the smoothing window T, and per option None
+or its checked value - hold (an int), track (a FaceTrack), scene (a SceneCuts), spans (a TrackSpans), faces (an AllFaces); stride is
+the int N >= 1"""
 
 
-class _KeyTables:
-    """The tables of one group under key-frame detection (`det_stride` N > 1), reserved in a Staging.  `segs`:
-    [(row0, n)] the group's segments - clips, or shots - as rows of the FULL arenas of R rows; segment k's key frames
-    (`stride.key_frames`) are the rows [key_row0_k, key_row0_k + m_k) of the KEY arenas, one segment after the other, Rk in all:
-        addresses      `padded` frame addresses, Rk padded to a batch multiple      (the detector batches)
-        segments       BOX_SEGMENT (row0, n, H, W)                                  (the finishes, on full rows)
-        stride         STRIDE_SEGMENT (t * Rk + key_row0, t * R + row0, n, 0), F * n_seg of them, slot t's after slot t - 1's
-        tracks         with `track`: TRACK_SEGMENT (key_row0, m, -1, 0)             (the track steps from key to key)
-        key_segments,  with `faces`: BOX_SEGMENT (key_row0, m, H, W) for w2l_face_tracks_all_segments, and the F-slot table of
-        wide           `faces.expand_segments` over the full rows for the span launch and the run finish"""
+class _Tables:
+    """The tables of one group, reserved in a Staging, and what the finishes need to know of the group.  `segs`: [(row0, n)] the
+    group's segments - clips, or shots - as rows of the FULL arenas of R rows.  The detector's rows are the full rows, or under
+    key-frame detection (`det_stride` N > 1) the KEY rows: segment k's key frames (`stride.key_frames`) are the rows
+    [key_row0_k, key_row0_k + m_k) of the key arenas, one segment after the other, Rk in all (N = 1: key_row0 = row0, m = n,
+    Rk = R).  In reservation order:
+        addresses      with `batch_size`: the frame address of every detector row, Rk padded to a batch multiple (`padded`) with
+                       copies of the last one                                       (the detector batches)
+        segments       BOX_SEGMENT (row0, n, H, W)                                  (the cut launch; the finishes, on full rows)
+        stride         N > 1: STRIDE_SEGMENT (t * Rk + key_row0, t * R + row0, n, 0), F * n_seg of them, slot t's after slot t - 1's
+        tracks         with `track`: TRACK_SEGMENT (key_row0, m, -1, 0)             (no carried state: a clip, or a shot)
+        key_segments   N > 1 with `faces`: BOX_SEGMENT (key_row0, m, H, W) for w2l_face_tracks_all_segments
+        wide           with `faces`: the F-slot table of `faces.expand_segments` over the full rows, for the span launch and the
+                       run finish
+    `_detect_group` adds `lengths` (frames per clip) and, under `scene_cuts`, `shots_of` ([(a, b)] per clip)."""
 
-    def __init__(self, st, segs, N, batch_size, H, W, R, track, faces):
+    def __init__(self, st, segs, shape, R, N=1, batch_size=None, track=None, faces=None):
         from .._lib import STRIDE_SEGMENT
         from .stride import key_frames
-        self.N, self.R, self.segs, self.shape = N, R, segs, (H, W)
-        self.keys = [key_frames(n, N) for _, n in segs]
-        self.Rk = sum(len(k) for k in self.keys)
-        self.padded = (self.Rk + batch_size - 1) // batch_size * batch_size
-        self.F = 1 if faces is None else faces.max_faces
+        self.st, self.dev, self.segs, self.shape, self.R, self.N = st, st.device, segs, shape, R, N
+        self.shots_of = None
         n_seg = self.n_seg = len(segs)
-        self.addresses, self.segments = st.table(ADDRESS, self.padded), st.table(BOX_SEGMENT, n_seg)
-        self.stride = st.table(STRIDE_SEGMENT, self.F * n_seg)
+        F = self.F = 1 if faces is None else faces.max_faces
+        self.keys = None if N == 1 else [key_frames(n, N) for _, n in segs]
+        self.Rk = R if N == 1 else sum(len(k) for k in self.keys)
+        self.padded = None if batch_size is None else (self.Rk + batch_size - 1) // batch_size * batch_size
+        self.addresses = None if batch_size is None else st.table(ADDRESS, self.padded)
+        self.segments = st.table(BOX_SEGMENT, n_seg)
+        self.stride = None if N == 1 else st.table(STRIDE_SEGMENT, F * n_seg)
         self.tracks = None if track is None else st.table(TRACK_SEGMENT, n_seg)
-        self.key_segments = None if faces is None else st.table(BOX_SEGMENT, n_seg)
-        self.wide = None if faces is None else st.table(BOX_SEGMENT, self.F * n_seg)
+        self.key_segments = None if N == 1 or faces is None else st.table(BOX_SEGMENT, n_seg)
+        self.wide = None if faces is None else st.table(BOX_SEGMENT, F * n_seg)
 
     def key_rows(self):
         """the full-arena row of every key row, in key-row order"""
         return np.array([row0 + i for (row0, _), keys in zip(self.segs, self.keys) for i in keys], dtype=np.int64)
 
-    def fill(self, st, key_addresses):
-        """the tables' contents, once `st` is allocated; key_addresses: uint64 [Rk], the frame every key row reads"""
-        H, W = self.shape
-        addr = st.view(self.addresses)
-        addr[:self.Rk] = key_addresses
-        addr[self.Rk:] = addr[self.Rk - 1]
+    def fill(self, addresses=None):
+        """the tables' contents, once the Staging is allocated; addresses: uint64 [Rk], the frame every detector row reads"""
+        (H, W), R, Rk, n_seg = self.shape, self.R, self.Rk, self.n_seg
+        view = lambda h: None if h is None else self.st.view(h)
+        addr, segments, stride, tracks, key_segments = (view(h) for h in (self.addresses, self.segments, self.stride, self.tracks,
+                                                                          self.key_segments))
+        if addr is not None:
+            addr[:Rk] = addresses
+            addr[Rk:] = addr[Rk - 1]
         kr = 0
-        for k, ((row0, n), keys) in enumerate(zip(self.segs, self.keys)):
-            st.view(self.segments)[k] = (row0, n, H, W)
-            for t in range(self.F):
-                st.view(self.stride)[t * self.n_seg + k] = (t * self.Rk + kr, t * self.R + row0, n, 0)
-            if self.tracks is not None:
-                st.view(self.tracks)[k] = (kr, len(keys), -1, 0)             # a clip or a shot: no carried state
-            if self.key_segments is not None:
-                st.view(self.key_segments)[k] = (kr, len(keys), H, W)
-            kr += len(keys)
+        for k, (row0, n) in enumerate(self.segs):
+            m = n if self.keys is None else len(self.keys[k])
+            segments[k] = (row0, n, H, W)
+            if stride is not None:
+                for t in range(self.F):
+                    stride[t * n_seg + k] = (t * Rk + kr, t * R + row0, n, 0)
+            if tracks is not None:
+                tracks[k] = (kr, m, -1, 0)
+            if key_segments is not None:
+                key_segments[k] = (kr, m, H, W)
+            kr += m
         if self.wide is not None:
             from .faces import expand_segments
-            st.view(self.wide)[:] = np.array(expand_segments(st.view(self.segments).tolist(), self.F, self.R), dtype=BOX_SEGMENT)
+            view(self.wide)[:] = np.array(expand_segments(segments.tolist(), self.F, R), dtype=BOX_SEGMENT)
 
-    def on_device(self, st):
-        """after the upload: the device tables the launches take"""
-        dev = lambda h: None if h is None else st.tensor(h)
-        self.addr_dev, self.seg_dev, self.stride_dev = st.tensor(self.addresses), st.tensor(self.segments), st.tensor(self.stride)
+    def upload(self):
+        """the Staging's one copy; the device tables the launches take"""
+        self.st.upload()
+        dev = lambda h: None if h is None else self.st.tensor(h)
+        self.addr_dev, self.seg_dev, self.stride_dev = dev(self.addresses), dev(self.segments), dev(self.stride)
         self.track_dev, self.key_seg_dev, self.wide_dev = dev(self.tracks), dev(self.key_segments), dev(self.wide)
 
     def expand(self, key_rects, key_flags, status, out=None):
@@ -459,167 +404,63 @@ class _KeyTables:
             raise AssertionError("w2l_face_rects_expand_segments did not follow a segment (status %s)" % status.tolist())
 
 
-def _detect_group_keys(detector, clips, pads, T, batch_size, N, hold=None, track=None, scene=None, spans=None, faces=None):
-    """`_detect_group` under key-frame detection (`det_stride` N > 1): the same results in the same formats, from
-    detector batches over the KEY frames of every clip - with `scene`, of every shot - alone.  The address table, the batches and
-    the rect or candidate arenas hold key rows (`_KeyTables`); the track launches, if any, run over key segments; ONE
-    w2l_face_rects_expand_segments launch then writes the full arenas and every finish runs on them unchanged.  Still one copy back
-    per group: the expand launch's status words ride in it.  Without `scene` the frames between the keys of a clip of host arrays are
-    not even uploaded.  With `scene` every frame goes up - the signatures read them all - and the group WAITS for the cut flags
-    before it builds the key tables and queues the detector batches: the one small wait the default path hides behind them."""
+def _detect_group(detector, clips, opts, batch_size):
+    """One group on the device.  clips: _Clips of one frame shape, each with at least one frame; opts: an `_Options`.  Returns numpy
+    (boxes, valid, status, kept) as the option's finish leaves them (`_finish_plain`, `_finish_spans`, `_finish_faces`): status is
+    int32 [clips,2] always, a part that does not exist is None.  The skeleton is fixed - stage, upload, batches, (track), (expand),
+    finish, ONE copy back - and every option hooks into it at one place:
+        `scene`   the signature and the cut launch are queued right after the upload, and the tables the track and the finish read
+                  hold one segment per SHOT: they are built once the flags are back - after the batches, which hide the wait;
+        `stride`  N > 1: the address table, the batches and the rect or candidate arenas hold KEY rows (`_Tables`), and the expand
+                  launch writes the full arenas every finish reads.  Without `scene` the frames between the keys of a clip of host
+                  arrays are not even uploaded.  With `scene` every frame goes up - the signatures read them all - and the group
+                  WAITS for the flags before the batches: the keys are per shot;
+        `track`, `faces`  the batches leave candidates; `hold`, `spans`, `faces` choose the finish."""
     dev = torch.device(detector.device)
     H, W = clips[0].H, clips[0].W
+    N, track, scene, faces = opts.stride, opts.track, opts.scene, opts.faces
     lengths = [c.n for c in clips]
-    R, frame_bytes = sum(lengths), H * W * 3
-    first = np.cumsum([0] + lengths[:-1]).tolist()
-    on_device = [isinstance(c.frames, torch.Tensor) for c in clips]
-    st, shots_of = Staging(dev), None
+    clip_segs = list(zip(np.cumsum([0] + lengths[:-1]).tolist(), lengths))
+    R = sum(lengths)
+    # ---- one staging buffer: [address table][segment tables][the frames that were host arrays]
+    st = Staging(dev)
     if scene is None:
-        kt = st                                              # one buffer: the key tables and the key frames
-        keys = _KeyTables(st, list(zip(first, lengths)), N, batch_size, H, W, R, track, faces)
-        src = [st.place(c.frames) if there else st.place([c.frames[i] for i in k]) for c, there, k in zip(clips, on_device, keys.keys)]
-        st.allocate()
-        keys.fill(st, np.concatenate([np.uint64(st.address(h)) + (np.array(k, dtype=np.uint64) if there else
-                                                                   np.arange(len(k), dtype=np.uint64)) * np.uint64(frame_bytes)
-                                      for h, there, k in zip(src, on_device, keys.keys)]))
-        st.upload()
-    else:
-        addresses, segments = st.table(ADDRESS, R), st.table(BOX_SEGMENT, len(clips))
-        src = [st.place(c.frames) for c in clips]
-        st.allocate()
-        addr = st.view(addresses)
-        for k, (c, r) in enumerate(zip(clips, first)):
-            addr[r:r + c.n] = np.uint64(st.address(src[k])) + np.arange(c.n, dtype=np.uint64) * np.uint64(frame_bytes)
-            st.view(segments)[k] = (r, c.n, H, W)
-        st.upload()
-        _, cuts_host, cuts_ready = _queue_cuts(st.tensor(addresses), st.tensor(segments), len(clips), R, H, W, scene, dev)
-        cuts_ready.synchronize()                             # the keys are per shot: nothing to detect on before the cuts are known
-        cuts = cuts_host.numpy()
-        if cuts[R:].any():
-            raise AssertionError("w2l_scene_cuts did not follow a clip's segment (status %s)" % cuts[R:].tolist())
-        shots_of = [split_shots(c.n, cuts[r:r + c.n]) for c, r in zip(clips, first)]
-        kt = Staging(dev)                                    # `st` stays: the frames lie in it
-        keys = _KeyTables(kt, [(r + a, b - a) for r, shots in zip(first, shots_of) for a, b in shots], N, batch_size, H, W, R, track,
-                          faces)
-        kt.allocate()
-        keys.fill(kt, addr[keys.key_rows()])
-        kt.upload()
-    keys.on_device(kt)
-    n_seg = keys.n_seg
-    arenas = detect_rows(detector, keys.addr_dev, [(H, W, 0, keys.padded)], batch_size, keys.padded, track,      # rows [Rk, padded): scratch
-                         **({} if faces is None else {"K": faces.cands}))
-    if faces is not None:
-        return _finish_faces(n_seg, keys.seg_dev, keys.wide_dev, arenas, faces, spans, R, pads, T, dev, lengths, shots_of, keys=keys)
-    if spans is not None:
-        return _finish_spans(n_seg, keys.seg_dev, keys.track_dev, arenas, track, spans, R, pads, T, dev, lengths, shots_of, keys=keys)
-    out = BoxOut(R, n_seg, hold is not None, track is not None, dev, extra=n_seg)
-    if track is not None:
-        track_rows(n_seg, keys.track_dev, arenas, track, out.track_status)
-    full = keys.expand(arenas.rects, arenas.flags, out.extra)
-    if hold is None:
-        _finish_segments(n_seg, keys.seg_dev, full.rects, full.flags, pads, T, out.boxes, out.status)
-    else:
-        _finish_runs(n_seg, keys.seg_dev, full.rects, full.flags, R, pads, T, hold, out.boxes, out.valid, out.status)
-    host = out.buffer.cpu().numpy()                          # the group's one copy back
-    boxes, valid, status, _ = out.split(host)
-    keys.check(out._parts(host)[-1])
-    if shots_of is not None:
-        status = _fold_shot_status(status, shots_of)
-    return (boxes, status) if hold is None else (boxes, valid, status)
+        tabs = _Tables(st, clip_segs, (H, W), R, N, batch_size, track, faces)
+    else:                                                    # the clips' table is the cut launch's; the shots' tables follow
+        tabs = _Tables(st, clip_segs, (H, W), R, 1, batch_size)
+    src = []
+    for k, c in enumerate(clips):
+        pick = np.arange(c.n, dtype=np.uint64) if tabs.keys is None else np.array(tabs.keys[k], dtype=np.uint64)
+        if tabs.keys is None or isinstance(c.frames, torch.Tensor):
+            src.append((st.place(c.frames), pick))
+        else:                                                # host arrays under key-frame detection: the key frames alone go up
+            src.append((st.place([c.frames[i] for i in tabs.keys[k]]), np.arange(len(pick), dtype=np.uint64)))
+    st.allocate()
+    addresses = np.concatenate([np.uint64(st.address(h)) + pick * np.uint64(H * W * 3) for h, pick in src])
+    tabs.fill(addresses)
+    tabs.upload()
 
+    def shot_tables():
+        shots_of = _wait_cuts(cuts, clip_segs, R)
+        shots = _Tables(Staging(dev), [(r + a, b - a) for (r, _), mine in zip(clip_segs, shots_of) for a, b in mine], (H, W), R, N,
+                        None if N == 1 else batch_size, track, faces)       # `st` stays: the frames lie in it
+        shots.st.allocate()
+        shots.fill(None if N == 1 else addresses[shots.key_rows()])
+        shots.upload()
+        shots.shots_of = shots_of
+        return shots
 
-def _finish_spans(n_seg, seg_dev, track_dev, arenas, track, spans, R, pads, T, dev, clip_lengths, shots_of, keys=None):
-    """the end of `_detect_group` under `track_spans`: the track launch (if any), w2l_face_spans_segments over the same segments,
-    w2l_face_boxes_runs with hold 0 on its outputs, and the group's one copy back, which also brings the span table.  Returns numpy
-    (boxes [R,4], valid [R], status [clips,2], [the clip's kept spans [(a, b)] per clip]).  With `keys` (a `_KeyTables`: key-frame
-    detection) the arenas hold key rows, `track_dev` is the table of key segments, and the expand launch sits between the track
-    and the span rule; its status words ride in the same copy."""
-    from .spans import span_segments
-    out = BoxOut(R, n_seg, True, track is not None, dev, spans=True, **({} if keys is None else {"extra": n_seg}))
-    if track is not None:
-        track_rows(n_seg, track_dev, arenas, track, out.track_status)
-    if keys is not None:
-        arenas = keys.expand(arenas.rects, arenas.flags, out.extra)
-    rects = torch.empty((R, 4), dtype=torch.int32, device=dev)
-    flags = torch.empty((R,), dtype=torch.int32, device=dev)
-    span_segments(n_seg, seg_dev, arenas.rects, arenas.flags, R, spans, rects, flags, out.span_rows, out.span_status)
-    _finish_runs(n_seg, seg_dev, rects, flags, R, pads, T, 0, out.boxes, out.valid, out.status)
-    host = out.buffer.cpu().numpy()
-    boxes, valid, status, _ = out.split(host)
-    span_rows, span_status = out.split_spans(host)
-    if keys is not None:
-        keys.check(out._parts(host)[-1])
-    if shots_of is None:
-        shots_of = [[(0, n)] for n in clip_lengths]
-    if (span_status[:, 0] == 3).any() or (status[:, 0] == 3).any():
-        raise AssertionError("w2l_face_spans_segments did not follow a clip's segment (status %s)" % span_status.tolist())
-    kept, k, r = [], 0, 0
-    for n, shots in zip(clip_lengths, shots_of):
-        mine = []
-        for a, _ in shots:                                  # segment k holds the rows from r + a on
-            if span_status[k][0] == 0:
-                mine += [(a + int(f), a + int(f) + int(L)) for f, L, _, _ in span_rows[r + a:r + a + int(span_status[k][1])]]
-            k += 1
-        kept.append(mine)
-        r += n
-    return boxes, valid, _fold_shot_status(status, shots_of), kept
-
-
-def _finish_faces(n_seg, seg_dev, wide_dev, arenas, faces, spans, R, pads, T, dev, clip_lengths, shots_of, keys=None):
-    """the end of `_detect_group` under `all_faces`: w2l_face_tracks_all_segments over the group's segments (L = `spans.bridge`) into
-    F slot arenas of R rows each, then the unchanged w2l_face_spans_segments and w2l_face_boxes_runs (hold 0) over `wide_dev`, the
-    table of F * n_seg segments on those arenas, and the group's one copy back, which also brings the span table and the new
-    status.  Returns (status [clips,2], [a `faces.FaceSpans` per clip]); a clip with a frame left to the host has code 2.  With
-    `keys` (a `_KeyTables`: key-frame detection) the candidates are those of key rows: the tracks run over `keys`' table of key
-    segments with L = `stride.faces_reseed(bridge, N)` into F slot arenas of key rows, and the expand launch over the F-slot wide
-    stride table writes the F full slot arenas the span launch reads; its status words ride in the same copy."""
-    from .faces import FaceSpan, FaceSpans, faces_segments
-    from .spans import span_segments
-    F = faces.max_faces
-    out = BoxOut(F * R, F * n_seg, True, False, dev, spans=True, extra=4 * n_seg + (0 if keys is None else F * n_seg))
-    slot_rects = torch.empty((2, F * R, 4), dtype=torch.int32, device=dev)          # the tracks, then the spans of them
-    slot_flags = torch.empty((2, F * R), dtype=torch.int32, device=dev)
-    if keys is None:
-        faces_segments(n_seg, seg_dev, arenas.cands[:R], arenas.ncand[:R], arenas.cflags[:R], faces, spans.bridge, slot_rects[0],
-                       slot_flags[0], out.extra)
-    else:
-        from .stride import faces_reseed
-        Rk = keys.Rk
-        key_rects = torch.empty((F * Rk, 4), dtype=torch.int32, device=dev)
-        key_flags = torch.empty((F * Rk,), dtype=torch.int32, device=dev)
-        faces_segments(n_seg, keys.key_seg_dev, arenas.cands[:Rk], arenas.ncand[:Rk], arenas.cflags[:Rk], faces,
-                       faces_reseed(spans.bridge, keys.N), key_rects, key_flags, out.extra[:4 * n_seg])
-        keys.expand(key_rects, key_flags, out.extra[4 * n_seg:], out=(slot_rects[0], slot_flags[0]))
-    span_segments(F * n_seg, wide_dev, slot_rects[0], slot_flags[0], F * R, spans, slot_rects[1], slot_flags[1], out.span_rows,
-                  out.span_status)
-    _finish_runs(F * n_seg, wide_dev, slot_rects[1], slot_flags[1], F * R, pads, T, 0, out.boxes, out.valid, out.status)
-    host = out.buffer.cpu().numpy()                          # the group's one copy back
-    boxes, _, status, _ = out.split(host)
-    span_rows, span_status = out.split_spans(host)
-    faces_status = out._parts(host)[-1][:4 * n_seg].reshape(-1, 4)
-    if keys is not None:
-        keys.check(out._parts(host)[-1][4 * n_seg:])
-    if shots_of is None:
-        shots_of = [[(0, n)] for n in clip_lengths]
-    if (span_status[:, 0] == 3).any() or (status[:, 0] == 3).any() or faces_status[:, 0].any():
-        raise AssertionError("w2l_face_tracks_all_segments did not follow a clip's segment (status %s, %s)"
-                             % (faces_status[:, 0].tolist(), span_status.tolist()))
-    per_clip, results, k, r = np.zeros((len(clip_lengths), 2), dtype=status.dtype), [], 0, 0
-    for c, (n, shots) in enumerate(zip(clip_lengths, shots_of)):
-        tracks, dropped = [], 0
-        for a, _ in shots:                                  # segment k holds the clip's frames from a on, in every slot
-            dropped += int(faces_status[k][2])
-            for t in range(F):
-                code, count = (int(v) for v in span_status[t * n_seg + k])
-                if code == 2 and per_clip[c][0] == 0:
-                    per_clip[c] = (2, a + count)
-                row = t * R + r + a
-                for f, L, det, _ in span_rows[row:row + (count if code == 0 else 0)].tolist():
-                    tracks.append(FaceSpan(t, a + f, a + f + L, boxes[row + f:row + f + L].astype(np.int64), det))
-            k += 1
-        results.append(FaceSpans(n, tracks, dropped))
-        r += n
-    return per_clip, results
+    if scene is not None:                                    # queued before the batches: the flags cross while the detector runs
+        cuts = _queue_cuts(tabs.addr_dev, tabs.seg_dev, len(clips), R, H, W, scene, dev)
+    if scene is not None and N > 1:                          # the keys are per shot: nothing to detect on before the cuts are known
+        tabs = shot_tables()
+    arenas = detect_rows(detector, tabs.addr_dev, [(H, W, 0, tabs.padded)], batch_size, tabs.padded, track,      # rows [Rk, padded): scratch
+                         None if faces is None else faces.cands)
+    if scene is not None and N == 1:                         # the batches hid the wait
+        tabs = shot_tables()
+    tabs.lengths = lengths
+    finish = _finish_faces if faces is not None else _finish_spans if opts.spans is not None else _finish_plain
+    return finish(tabs, arenas, opts)
 
 
 def _queue_cuts(addresses, segments, n_clips, R, H, W, scene, dev):
@@ -638,18 +479,152 @@ def _queue_cuts(addresses, segments, n_clips, R, H, W, scene, dev):
     return buf, host, ready
 
 
-def _host_faces(detector, clip, frames, pads, T, batch_size, scene, spans, faces, stride=1):
+def _wait_cuts(cuts, clip_segs, R):
+    """what `_queue_cuts` queued, once its copy has landed: the status words checked (all 0 for a table built here) and the shots
+    [(a, b)] of every clip [(row0, n)]"""
+    _, host, ready = cuts
+    ready.synchronize()
+    flags = host.numpy()
+    if flags[R:].any():
+        raise AssertionError("w2l_scene_cuts did not follow a clip's segment (status %s)" % flags[R:].tolist())
+    return [split_shots(n, flags[r:r + n]) for r, n in clip_segs]
+
+
+def _one_rect_rows(tabs, arenas, track, out):
+    """between the batches and what reads one rect per frame: with `track` w2l_face_track_segments over the group's segments (of key
+    rows under key-frame detection), then under key-frame detection the expand launch, whose status words ride in `out.extra`.
+    Returns the `Arenas` whose rects and flags hold the full rows."""
+    if track is not None:
+        track_rows(tabs.n_seg, tabs.track_dev, arenas, track, out.track_status)
+    if tabs.N > 1:
+        arenas = tabs.expand(arenas.rects, arenas.flags, out.extra)
+    return arenas
+
+
+def _finish_plain(tabs, arenas, opts):
+    """the end of `_detect_group` without `track_spans`: the track launch (if any), the expand launch (under key-frame detection),
+    w2l_face_boxes_segments - with `hold` w2l_face_boxes_runs - over the group's segments and the group's one copy back.  Returns
+    numpy (boxes int32 [R,4] in (y1, y2, x1, x2) order, rows in clip order; valid int32 [R] with `hold`, else None; status int32
+    [clips,2]; None).  The track's status words come back in the same copy and are all 0 (the table is built here); under
+    `scene_cuts` the status is folded per clip (`_fold_shot_status`)."""
+    n_seg, R, hold = tabs.n_seg, tabs.R, opts.hold
+    out = BoxOut(R, n_seg, hold is not None, opts.track is not None, tabs.dev, extra=n_seg if tabs.N > 1 else 0)
+    full = _one_rect_rows(tabs, arenas, opts.track, out)
+    if hold is None:
+        _finish_segments(n_seg, tabs.seg_dev, full.rects, full.flags, opts.pads, opts.T, out.boxes, out.status)
+    else:
+        _finish_runs(n_seg, tabs.seg_dev, full.rects, full.flags, R, opts.pads, opts.T, hold, out.boxes, out.valid, out.status)
+    host = out.buffer.cpu().numpy()                          # the group's one copy back; it also ends the stream's use of the staging buffers
+    boxes, valid, status, _ = out.split(host)
+    if tabs.N > 1:
+        tabs.check(out.split_extra(host))
+    if tabs.shots_of is not None:
+        status = _fold_shot_status(status, tabs.shots_of)
+    return boxes, valid, status, None
+
+
+def _finish_spans(tabs, arenas, opts):
+    """the end of `_detect_group` under `track_spans`: the track launch (if any), the expand launch (under key-frame detection),
+    w2l_face_spans_segments over the same segments, w2l_face_boxes_runs with hold 0 on its outputs, and the group's one copy back,
+    which also brings the span table.  Returns numpy (boxes [R,4], valid [R], status [clips,2], [the clip's kept spans [(a, b)] per
+    clip])."""
+    from .spans import span_segments
+    n_seg, R, dev = tabs.n_seg, tabs.R, tabs.dev
+    out = BoxOut(R, n_seg, True, opts.track is not None, dev, spans=True, extra=n_seg if tabs.N > 1 else 0)
+    full = _one_rect_rows(tabs, arenas, opts.track, out)
+    rects = torch.empty((R, 4), dtype=torch.int32, device=dev)
+    flags = torch.empty((R,), dtype=torch.int32, device=dev)
+    span_segments(n_seg, tabs.seg_dev, full.rects, full.flags, R, opts.spans, rects, flags, out.span_rows, out.span_status)
+    _finish_runs(n_seg, tabs.seg_dev, rects, flags, R, opts.pads, opts.T, 0, out.boxes, out.valid, out.status)
+    host = out.buffer.cpu().numpy()                          # the group's one copy back
+    boxes, valid, status, _ = out.split(host)
+    span_rows, span_status = out.split_spans(host)
+    if tabs.N > 1:
+        tabs.check(out.split_extra(host))
+    shots_of = tabs.shots_of if tabs.shots_of is not None else [[(0, n)] for n in tabs.lengths]
+    if (span_status[:, 0] == 3).any() or (status[:, 0] == 3).any():
+        raise AssertionError("w2l_face_spans_segments did not follow a clip's segment (status %s)" % span_status.tolist())
+    kept, k, r = [], 0, 0
+    for n, shots in zip(tabs.lengths, shots_of):
+        mine = []
+        for a, _ in shots:                                  # segment k holds the rows from r + a on
+            if span_status[k][0] == 0:
+                mine += [(a + int(f), a + int(f) + int(L)) for f, L, _, _ in span_rows[r + a:r + a + int(span_status[k][1])]]
+            k += 1
+        kept.append(mine)
+        r += n
+    return boxes, valid, _fold_shot_status(status, shots_of), kept
+
+
+def _finish_faces(tabs, arenas, opts):
+    """the end of `_detect_group` under `all_faces`: w2l_face_tracks_all_segments over the group's segments (L = `spans.bridge`) into
+    F slot arenas of R rows each, then the unchanged w2l_face_spans_segments and w2l_face_boxes_runs (hold 0) over `tabs.wide_dev`,
+    the table of F * n_seg segments on those arenas, and the group's one copy back, which also brings the span table and the new
+    status.  Returns (None, None, status [clips,2], [a `faces.FaceSpans` per clip]); a clip with a frame left to the host has code 2.
+    Under key-frame detection the candidates are those of key rows: the tracks run over the table of key segments with L =
+    `stride.faces_reseed(bridge, N)` into F slot arenas of key rows, and the expand launch over the F-slot wide stride table writes
+    the F full slot arenas the span launch reads; its status words ride in the same copy."""
+    from .faces import FaceSpan, FaceSpans, faces_segments
+    from .spans import span_segments
+    from .stride import faces_reseed
+    n_seg, R, Rk, dev, spans, keyed = tabs.n_seg, tabs.R, tabs.Rk, tabs.dev, opts.spans, tabs.N > 1
+    F = opts.faces.max_faces
+    out = BoxOut(F * R, F * n_seg, True, False, dev, spans=True, extra=4 * n_seg + (F * n_seg if keyed else 0))
+    slot_rects = torch.empty((2, F * R, 4), dtype=torch.int32, device=dev)          # the tracks, then the spans of them
+    slot_flags = torch.empty((2, F * R), dtype=torch.int32, device=dev)
+    if keyed:
+        key_rects = torch.empty((F * Rk, 4), dtype=torch.int32, device=dev)
+        key_flags = torch.empty((F * Rk,), dtype=torch.int32, device=dev)
+        faces_segments(n_seg, tabs.key_seg_dev, arenas.cands[:Rk], arenas.ncand[:Rk], arenas.cflags[:Rk], opts.faces,
+                       faces_reseed(spans.bridge, tabs.N), key_rects, key_flags, out.extra[:4 * n_seg])
+        tabs.expand(key_rects, key_flags, out.extra[4 * n_seg:], out=(slot_rects[0], slot_flags[0]))
+    else:
+        faces_segments(n_seg, tabs.seg_dev, arenas.cands[:R], arenas.ncand[:R], arenas.cflags[:R], opts.faces, spans.bridge,
+                       slot_rects[0], slot_flags[0], out.extra)
+    span_segments(F * n_seg, tabs.wide_dev, slot_rects[0], slot_flags[0], F * R, spans, slot_rects[1], slot_flags[1], out.span_rows,
+                  out.span_status)
+    _finish_runs(F * n_seg, tabs.wide_dev, slot_rects[1], slot_flags[1], F * R, opts.pads, opts.T, 0, out.boxes, out.valid, out.status)
+    host = out.buffer.cpu().numpy()                          # the group's one copy back
+    boxes, _, status, _ = out.split(host)
+    span_rows, span_status = out.split_spans(host)
+    faces_status = out.split_extra(host)[:4 * n_seg].reshape(-1, 4)
+    if keyed:
+        tabs.check(out.split_extra(host)[4 * n_seg:])
+    shots_of = tabs.shots_of if tabs.shots_of is not None else [[(0, n)] for n in tabs.lengths]
+    if (span_status[:, 0] == 3).any() or (status[:, 0] == 3).any() or faces_status[:, 0].any():
+        raise AssertionError("w2l_face_tracks_all_segments did not follow a clip's segment (status %s, %s)"
+                             % (faces_status[:, 0].tolist(), span_status.tolist()))
+    per_clip, results, k, r = np.zeros((len(tabs.lengths), 2), dtype=status.dtype), [], 0, 0
+    for c, (n, shots) in enumerate(zip(tabs.lengths, shots_of)):
+        tracks, dropped = [], 0
+        for a, _ in shots:                                  # segment k holds the clip's frames from a on, in every slot
+            dropped += int(faces_status[k][2])
+            for t in range(F):
+                code, count = (int(v) for v in span_status[t * n_seg + k])
+                if code == 2 and per_clip[c][0] == 0:
+                    per_clip[c] = (2, a + count)
+                row = t * R + r + a
+                for f, L, det, _ in span_rows[row:row + (count if code == 0 else 0)].tolist():
+                    tracks.append(FaceSpan(t, a + f, a + f + L, boxes[row + f:row + f + L].astype(np.int64), det))
+            k += 1
+        results.append(FaceSpans(n, tracks, dropped))
+        r += n
+    return None, None, per_clip, results
+
+
+def _host_faces(detector, clip, frames, opts, batch_size):
     """`all_faces` for one clip on the host: the candidates of every frame (`get_candidates_for_batch`, which runs `host_top_rects`
     on a frame the device does not decide), the shots, `faces.host_all_tracks` per shot, then per slot `host_spans_shots` and
-    `host_boxes_shots` with hold 0 -> a `faces.FaceSpans`.  With `stride` N > 1 the shots come first, the candidates are those of
-    every shot's key frames, the tracks step from key to key with `stride.faces_reseed(bridge, N)` tolerated misses, and every
+    `host_boxes_shots` with hold 0 -> a `faces.FaceSpans`.  With `opts.stride` N > 1 the shots come first, the candidates are those
+    of every shot's key frames, the tracks step from key to key with `stride.faces_reseed(bridge, N)` tolerated misses, and every
     slot's key rects go through `stride.host_stride_fill` per shot."""
     from ..inference import halving
     from .faces import FaceSpan, FaceSpans, host_all_tracks
     from .spans import host_spans_shots
     from .stride import faces_reseed, host_stride_fill, key_frames, shot_key_frames
     from .track import iou_q8
-    shots = [(0, clip.n)] if scene is None else _host_shots(detector, frames, clip, batch_size, scene)
+    spans, faces, stride = opts.spans, opts.faces, opts.stride
+    shots = [(0, clip.n)] if opts.scene is None else _host_shots(detector, frames, batch_size, opts.scene)
     seen = frames if stride == 1 else [frames[i] for i in shot_key_frames(shots, stride)]
 
     def run(size):
@@ -677,82 +652,49 @@ def _host_faces(detector, clip, frames, pads, T, batch_size, scene, spans, faces
     tracks = []
     for t, rects in enumerate(slots):
         filled, kept = host_spans_shots(rects, shots, spans)
-        boxes, _ = host_boxes_shots(filled, shots, clip.H, clip.W, pads, T, 0)
+        boxes, _ = host_boxes_shots(filled, shots, clip.H, clip.W, opts.pads, opts.T, 0)
         tracks += [FaceSpan(t, a, b, boxes[a:b], sum(r is not None for r in rects[a:b])) for a, b in kept]
     return FaceSpans(clip.n, tracks, dropped)
 
 
-def _host_shots(detector, frames, clip, batch_size, scene):
-    """the shots [(a, b)] of one clip of host frames: its signatures batch by batch, one cut launch and one small copy"""
+def _host_shots(detector, frames, batch_size, scene):
+    """the shots [(a, b)] of one clip of host frames (at least one, of one shape): its signatures batch by batch, one cut launch and
+    one small copy"""
     from .scene import SIG_WORDS, clip_cuts, frame_signatures
     dev = torch.device(detector.device)
-    sig = torch.empty((clip.n, SIG_WORDS), dtype=torch.int32, device=dev)
-    for lo in range(0, clip.n, batch_size):
+    n, (H, W) = len(frames), frames[0].shape[:2]
+    sig = torch.empty((n, SIG_WORDS), dtype=torch.int32, device=dev)
+    for lo in range(0, n, batch_size):
         frame_signatures(torch.from_numpy(np.ascontiguousarray(np.array(frames[lo:lo + batch_size]))).to(dev), sig, lo)
-    return split_shots(clip.n, clip_cuts(sig, clip.H, clip.W, scene)[0])
+    return split_shots(n, clip_cuts(sig, H, W, scene)[0])
 
 
-def _per_clip(detector, clip, pads, T, batch_size, hold=None, track=None, scene=None, spans=None, faces=None, stride=1):
-    """one clip alone through `inference.face_detect` (batch by batch uploads, the host rules): (key, boxes, error).  `scene` is passed
-    on to it; where `face_detect`'s own finish does not fit (a hold, or a window other than 5) the same host rules run per shot
-    here, on `inference._shot_rects`.  With `spans` the clip's rects go through `spans.host_spans` per shot and every kept span is
-    finished as a run; with `faces` too the clip goes through `_host_faces`.  With `stride` N > 1 `face_detect` and its helpers
-    look at key frames only and fill per shot with `stride.host_stride_fill`."""
+def _per_clip(detector, clip, opts, batch_size):
+    """one clip alone on the host path (batch by batch uploads, the host rules): (key, boxes, error).  The strict case with the
+    reference's windows goes through `inference.face_detect` as it stands, with the options that are set as its keywords.  Every
+    other case takes the clip's rects and shots from `inference.clip_rects` and finishes them with the host statement of its rule:
+    `spans.host_spans_shots` and the run finish with hold 0 under `track_spans`, else `scene.host_boxes_shots` with the hold;
+    `all_faces` goes through `_host_faces`."""
     from .. import inference
-    skw = {} if stride == 1 else {"det_stride": stride}
+    from .spans import host_spans_shots
+    pads, T, hold, track, scene, spans, faces, stride = opts
     frames = list(clip.frames.cpu().numpy()) if isinstance(clip.frames, torch.Tensor) else list(clip.frames)
-    if faces is not None:
-        try:
-            return clip.key, _host_faces(detector, clip, frames, pads, T, batch_size, scene, spans, faces, stride), None
-        except (ValueError, OverflowError) as e:
-            return clip.key, None, str(e)
-    if spans is not None:
-        from .spans import host_spans_shots
-        try:
-            if scene is not None:
-                rects, shots = inference._shot_rects(frames, detector, batch_size, track, scene, **skw)
-            elif track is not None:
-                rects, shots = inference._track_rects(frames, detector, batch_size, track, **skw), [(0, clip.n)]
-            else:
-                rects, shots = inference._detect_rects(frames, detector, batch_size, **skw), [(0, clip.n)]
+    try:
+        if faces is not None:
+            return clip.key, _host_faces(detector, clip, frames, opts, batch_size), None
+        if spans is None and hold is None and T in (0, 5):           # face_detect's own finish fits
+            kw = {k: v for k, v in (("face_track", track), ("scene_cuts", scene), ("det_stride", stride)) if v not in (None, 1)}
+            det = inference.face_detect(frames, detector=detector, pads=list(pads), nosmooth=(T == 0), batch_size=batch_size, **kw)
+            return clip.key, np.array([c for _, c in det], dtype=np.int64).reshape(-1, 4), None
+        rects, shots = inference.clip_rects(frames, detector, batch_size, track, scene, stride)
+        if spans is not None:
             filled, kept = host_spans_shots(rects, shots, spans)
             boxes, valid = host_boxes_shots(filled, shots, clip.H, clip.W, pads, T, 0)
             return clip.key, SpanBoxes(boxes, valid, kept), None
-        except (ValueError, OverflowError) as e:
-            return clip.key, None, str(e)
-    if scene is not None:
-        try:
-            if hold is None and T in (0, 5):
-                det = inference.face_detect(frames, detector=detector, pads=list(pads), nosmooth=(T == 0), batch_size=batch_size,
-                                            scene_cuts=scene, **({} if track is None else {"face_track": track}), **skw)
-                return clip.key, np.array([c for _, c in det], dtype=np.int64).reshape(-1, 4), None
-            rects, shots = inference._shot_rects(frames, detector, batch_size, track, scene, **skw)
-            boxes, valid = host_boxes_shots(rects, shots, clip.H, clip.W, pads, T, hold)
-            return clip.key, boxes if hold is None else RunBoxes(boxes, valid), None
-        except (ValueError, OverflowError) as e:
-            return clip.key, None, str(e)
-
-    def clip_rects():
-        if track is None:
-            return inference._detect_rects(frames, detector, batch_size, **skw)
-        return inference._track_rects(frames, detector, batch_size, track, **skw)
-
-    try:
-        if hold is not None:                     # the pass-through rule on the host: the same rects, `host_boxes_runs`
-            rects = clip_rects()
-            return clip.key, RunBoxes(*host_boxes_runs(rects, clip.H, clip.W, pads, T, hold)), None
-        if T in (0, 5):
-            det = inference.face_detect(frames, detector=detector, pads=list(pads), nosmooth=(T == 0), batch_size=batch_size,
-                                        **({} if track is None else {"face_track": track}), **skw)
-            boxes = np.array([c for _, c in det], dtype=np.int64).reshape(-1, 4)
-        else:                                    # face_detect's window is 5: its two halves with another T
-            rects = clip_rects()
-            if any(r is None for r in rects):
-                raise ValueError(NO_FACE)
-            boxes = host_boxes(rects, clip.H, clip.W, pads, T)
-    except (ValueError, OverflowError) as e:     # no face; a coordinate int() refuses
+        boxes, valid = host_boxes_shots(rects, shots, clip.H, clip.W, pads, T, hold)
+        return clip.key, boxes if hold is None else RunBoxes(boxes, valid), None
+    except (ValueError, OverflowError) as e:                         # no face; a coordinate int() refuses
         return clip.key, None, str(e)
-    return clip.key, boxes, None
 
 
 def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_batches=16, max_group_bytes=1 << 30, no_face_hold=None,
@@ -832,14 +774,6 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
             raise ValueError("all_faces follows every face and face_track one: give one of them")
         if spans is None:
             raise ValueError("all_faces needs track_spans: every face track goes through the span rule")
-    tkw = {} if track is None else {"track": track}    # the default path calls its helpers with the arguments it always did
-    if scene is not None:
-        tkw["scene"] = scene
-    if spans is not None:
-        tkw["spans"] = spans
-    if faces is not None:
-        tkw["faces"] = faces
-    pkw = dict(tkw) if stride == 1 else dict(tkw, stride=stride)       # `_per_clip`'s keywords
     if batch_size < 1 or group_batches < 1:
         raise ValueError("batch_size and group_batches must be at least 1")
     if not 0 <= int(T) <= MAX_T:
@@ -847,7 +781,7 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
     pads = tuple(int(p) for p in pads)
     if len(pads) != 4:
         raise ValueError("pads must be (top, bottom, left, right)")
-    T = int(T)
+    opts = _Options(pads, int(T), hold, track, scene, spans, faces, stride)
     it = iter(jobs)
     held, ended = None, False           # the job read but not yet placed
     while not ended or held is not None:
@@ -868,7 +802,7 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
                 if group:
                     break                                  # the jobs before it first
                 held = None
-                yield _per_clip(detector, c, pads, T, batch_size, hold, **pkw)
+                yield _per_clip(detector, c, opts, batch_size)
                 del c
                 continue
             if shape is not None and ((c.H, c.W) != shape or n_bytes + c.nbytes > max_group_bytes):
@@ -887,18 +821,10 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
         def run_group(size):
             nonlocal batch_size
             batch_size = size                              # a halved batch holds for the rest of the run
-            if stride > 1:
-                return _detect_group_keys(detector, clips, pads, T, size, stride, hold, **tkw)
-            return _detect_group(detector, clips, pads, T, size, *(() if hold is None else (hold,)), **tkw)
+            return _detect_group(detector, clips, opts, size)
 
         if clips:
-            res = halving(run_group, batch_size)
-            if faces is not None:
-                status, kept = res
-            elif spans is not None:
-                boxes, valid, status, kept = res
-            else:
-                boxes, valid, status = res[0], res[1] if hold is not None else None, res[-1]
+            boxes, valid, status, kept = halving(run_group, batch_size)
         results, row, k = [], 0, 0
         for c in group:
             if c.n == 0:
@@ -925,4 +851,4 @@ def detect_many(detector, jobs, pads=(0, 0, 0, 0), T=5, batch_size=16, group_bat
         del c
         while results:
             res = results.pop(0)
-            yield _per_clip(detector, res, pads, T, batch_size, hold, **pkw) if isinstance(res, _Clip) else res
+            yield _per_clip(detector, res, opts, batch_size) if isinstance(res, _Clip) else res

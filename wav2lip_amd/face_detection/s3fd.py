@@ -143,7 +143,7 @@ class _Graph:
         if st is engine.BF16:
             big = max(_bf16_buffer_sizes(B, H, W))
             if big >= bf16.BUF_LIMIT:
-                # checked before anything is allocated: inference._detect_rects halves the batch on this error, as for fp32
+                # checked before anything is allocated: inference.halving halves the batch on this error, as for fp32
                 raise RuntimeError("S3FD bf16: a %d x %d x %d batch needs a %d-byte buffer, over the kernels' 2 GiB limit: split the "
                                    "batch" % (B, H, W, big))
         self.lib = lib = load()

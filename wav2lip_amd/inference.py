@@ -701,147 +701,106 @@ def get_smoothened_boxes(boxes, T):
     return boxes
 
 
-def halving(run, batch_size):
+OOM_ERROR = 'Image too big to run face detection on GPU. Please use the --resize_factor argument'      # inference.py:81
+
+
+def halving(run, batch_size, error=OOM_ERROR):
     """inference.py:75-88: `run(batch_size)`; a RuntimeError of the detector (out of device memory on a large frame) halves the
-    batch, prints the reference's message and starts over, down to single frames, where it is the reference's error"""
+    batch, prints the reference's message and starts over, down to single frames, where it is the RuntimeError `error`: the
+    reference's text, or a command's own"""
     while True:
         try:
             return run(batch_size)
         except RuntimeError:
             if batch_size == 1:
-                raise RuntimeError('Image too big to run face detection on GPU. Please use the --resize_factor argument')
+                raise RuntimeError(error)
             batch_size //= 2
             print('Recovering from OOM error; New batch size: {}'.format(batch_size))
 
 
-def _detect_rects(images, detector, batch_size, ranks=None, det_stride=1):
-    """inference.py:75-88: one rect (or None) per frame, in batches under `halving`.  With `ranks` every rank detects the frames
-    of its contiguous shard and the per-frame rects (four numbers each) are all-gathered: the box smoothing that follows needs
-    them all, on every rank, in frame order.  With `det_stride` N > 1 (face_detection/stride.py) the detector sees
-    the clip's key frames only and `host_stride_fill` gives the frames between them their rects."""
-    if det_stride > 1:
-        from .face_detection.stride import host_stride_fill, key_frames
-        keys = key_frames(len(images), det_stride)
-        return host_stride_fill(_detect_rects([images[i] for i in keys], detector, batch_size), len(images), det_stride)
-    if ranks is not None and ranks.dist is not None and ranks.world > 1:
-        from . import sharding
-        lo, hi = sharding.shard_range(len(images), ranks.rank, ranks.world)
-        mine = _detect_rects(images[lo:hi], detector, batch_size) if hi > lo else []
-        parts = [None] * ranks.world
-        ranks.dist.all_gather_object(parts, mine)
-        return [r for part in parts for r in part]
+def clip_rects(images, detector, batch_size, track=None, scene=None, det_stride=1, ranks=None):
+    """inference.py:75-88 and every option in front of the finish: (one rect (x1, y1, x2, y2) or None per frame, the shots [(a, b)]
+    of the clip - [(0, n)] without `scene`), in batches under `halving`.
 
-    def run(batch_size):
-        rects = []
-        for lo in range(0, len(images), batch_size):
-            rects += detector.get_detections_for_batch(np.array(images[lo:lo + batch_size]))
-        return rects
+    Plain, the batches go to the detector as numpy arrays.  With `ranks` every rank detects the frames of its contiguous shard and
+    the per-frame rects (four numbers each) are all-gathered: the box smoothing that follows needs them all, on every rank, in frame
+    order.
 
-    return halving(run, batch_size)
+    `track` (face_detection/track.py): the candidates of every batch go into device arenas
+    (`FaceAlignment.cands_for_batch`), ONE w2l_face_track_segments launch over one segment per shot - a fresh track at every cut -
+    follows the face and ONE copy brings rects, flags and status back.  A frame the device does not decide (RECT_HOST) sends the
+    whole clip through the host statement of the same rule: `get_candidates_for_batch` (which runs `host_top_rects` on such a frame)
+    and `host_track_shots` (for one shot, `host_track`).
 
+    `scene` (face_detection/scene.py): every batch is uploaded ONCE as a device tensor; w2l_frame_hist_rows reads it
+    into the clip's signature arena and the detector takes the same tensor.  After the last batch ONE w2l_scene_cuts launch and one
+    small copy give the cut flags.
 
-def _track_rects(images, detector, batch_size, track, det_stride=1):
-    """`_detect_rects` under tracked face selection (face_detection/track.py): the candidates of every batch go into
-    device arenas (`FaceAlignment.cands_for_batch`), ONE w2l_face_track_segments launch with one segment follows the face through
-    the clip and ONE copy brings rects and flags back.  A frame the device does not decide (RECT_HOST) sends the whole clip through
-    the host statement of the same rule: `get_candidates_for_batch` (which runs `host_top_rects` on such a frame) and
-    `host_track`.  The detector's RuntimeError halves the batch as there.  With `det_stride` N > 1 the track steps through the
-    clip's key frames and `host_stride_fill` gives the frames between them their rects."""
-    if det_stride > 1:
-        from .face_detection.stride import host_stride_fill, key_frames
-        keys = key_frames(len(images), det_stride)
-        return host_stride_fill(_track_rects([images[i] for i in keys], detector, batch_size, track), len(images), det_stride)
-    from .face_detection.s3fd import RECT_FOUND, RECT_HOST
-    from .face_detection.track import TRACK_SEGMENT, host_track, track_segments
-    n, K = len(images), track.cands
-    if n == 0:
-        return []
-
-    def run(batch_size):
-        dev = torch.device(detector.device)
-        cands = torch.empty((n, K, 4), dtype=torch.int32, device=dev)
-        ncand = torch.empty((n,), dtype=torch.int32, device=dev)
-        cflags = torch.empty((n,), dtype=torch.int32, device=dev)
-        for lo in range(0, n, batch_size):
-            detector.cands_for_batch(np.array(images[lo:lo + batch_size]), cands, ncand, cflags, lo, K)
-        seg = np.zeros(1, dtype=TRACK_SEGMENT)
-        seg[0] = (0, n, -1, 0)
-        segs = torch.from_numpy(seg.view(np.uint8)).to(dev)
-        out = torch.empty(5 * n + 1, dtype=torch.int32, device=dev)        # rects [n][4], flags [n], status [1]: one copy back
-        track_segments(segs, 1, cands, ncand, cflags, track, out[:4 * n].view(n, 4), out[4 * n:5 * n], out[5 * n:])
-        res = out.cpu().numpy()
-        rects, flags = res[:4 * n].reshape(n, 4), res[4 * n:5 * n]
-        if res[5 * n] != 0:
-            raise AssertionError("w2l_face_track_segments did not follow the clip's segment (status %d)" % res[5 * n])
-        if (flags == RECT_HOST).any():
-            per_frame = []
-            for lo in range(0, n, batch_size):
-                per_frame += detector.get_candidates_for_batch(np.array(images[lo:lo + batch_size]), K)
-            return host_track(per_frame, track)[0]
-        return [tuple(int(v) for v in r) if f == RECT_FOUND else None for r, f in zip(rects, flags)]
-
-    return halving(run, batch_size)
-
-
-def _shot_rects(images, detector, batch_size, track, scene, det_stride=1):
-    """`_detect_rects` / `_track_rects` under scene-cut detection (face_detection/scene.py): (one rect or None per
-    frame, the shots [(a, b)] of the clip).  Every batch is uploaded ONCE as a device tensor: w2l_frame_hist_rows reads it into the
-    clip's signature arena and the detector takes the same tensor.  After the last batch ONE w2l_scene_cuts launch and one small
-    copy give the cut flags.  With `track` the single w2l_face_track_segments launch then gets one segment per shot - a fresh
-    track at every cut - and a frame the device does not decide (RECT_HOST) sends every shot through `host_track` on its own.
-    With `det_stride` N > 1 the keys are per shot, so the cuts come first - a pass of signatures over every frame - and the key
-    frames of each shot then go through `_detect_rects` (all shots' keys in shared batches) or `_track_rects` (a shot at a time: a
-    fresh track each) and `host_stride_fill`."""
-    if det_stride > 1 and len(images):
-        from .face_detection.many import _Clip, _host_shots
+    `det_stride` N > 1 (face_detection/stride.py): the detector sees the key frames of the clip - of every shot, so
+    under `scene` the cuts come first, a pass of signatures over every frame - and `host_stride_fill` gives the frames between them
+    their rects.  Plain, all shots' keys share batches; under `track` a shot goes at a time: a fresh track each, stepping from key to
+    key."""
+    n = len(images)
+    if det_stride > 1 and n:
+        from .face_detection.many import _host_shots
         from .face_detection.stride import host_stride_fill, host_stride_fill_shots, key_frames, shot_key_frames
-        h, w = images[0].shape[:2]
-        shots = halving(lambda size: _host_shots(detector, images, _Clip(None, images, len(images), h, w, 0), size, scene), batch_size)
+        shots = [(0, n)] if scene is None else halving(lambda size: _host_shots(detector, images, size, scene), batch_size)
         if track is None:
-            key_rects = _detect_rects([images[i] for i in shot_key_frames(shots, det_stride)], detector, batch_size)
+            key_rects, _ = clip_rects([images[i] for i in shot_key_frames(shots, det_stride)], detector, batch_size)
             return host_stride_fill_shots(key_rects, shots, det_stride), shots
         rects = []
         for a, b in shots:
-            key_rects = _track_rects([images[a + i] for i in key_frames(b - a, det_stride)], detector, batch_size, track)
+            key_rects, _ = clip_rects([images[a + i] for i in key_frames(b - a, det_stride)], detector, batch_size, track)
             rects += host_stride_fill(key_rects, b - a, det_stride)
         return rects, shots
+    if ranks is not None and ranks.dist is not None and ranks.world > 1:
+        from . import sharding
+        lo, hi = sharding.shard_range(n, ranks.rank, ranks.world)
+        mine = clip_rects(images[lo:hi], detector, batch_size)[0] if hi > lo else []
+        parts = [None] * ranks.world
+        ranks.dist.all_gather_object(parts, mine)
+        return [r for part in parts for r in part], [(0, n)]
+    if n == 0:
+        return [], [] if scene is not None else [(0, 0)]
     from .face_detection.s3fd import RECT_FOUND, RECT_HOST
     from .face_detection.scene import SIG_WORDS, clip_cuts, frame_signatures, host_track_shots, split_shots
     from .face_detection.track import TRACK_SEGMENT, track_segments
-    n = len(images)
-    if n == 0:
-        return [], []
-    H, W = images[0].shape[:2]
 
     def run(batch_size):
-        dev = torch.device(detector.device)
-        sig = torch.empty((n, SIG_WORDS), dtype=torch.int32, device=dev)
-        rects = []
+        rects, shots = [], [(0, n)]
+        if track is not None or scene is not None:
+            dev = torch.device(detector.device)
+        if scene is not None:
+            sig = torch.empty((n, SIG_WORDS), dtype=torch.int32, device=dev)
         if track is not None:
             K = track.cands
             cands = torch.empty((n, K, 4), dtype=torch.int32, device=dev)
             ncand = torch.empty((n,), dtype=torch.int32, device=dev)
             cflags = torch.empty((n,), dtype=torch.int32, device=dev)
         for lo in range(0, n, batch_size):
-            batch = torch.from_numpy(np.ascontiguousarray(np.array(images[lo:lo + batch_size]))).to(dev)
-            frame_signatures(batch, sig, lo)
+            batch = np.array(images[lo:lo + batch_size])
+            if scene is not None:                            # uploaded once: the signatures and the detector read the same tensor
+                batch = torch.from_numpy(np.ascontiguousarray(batch)).to(dev)
+                frame_signatures(batch, sig, lo)
             if track is None:
                 rects += detector.get_detections_for_batch(batch)
             else:
                 detector.cands_for_batch(batch, cands, ncand, cflags, lo, K)
-        shots = split_shots(n, clip_cuts(sig, H, W, scene)[0])
+        if scene is not None:
+            shots = split_shots(n, clip_cuts(sig, *images[0].shape[:2], scene)[0])
         if track is None:
             return rects, shots
         seg = np.zeros(len(shots), dtype=TRACK_SEGMENT)
         for k, (a, b) in enumerate(shots):
             seg[k] = (a, b - a, -1, 0)
         segs = torch.from_numpy(seg.view(np.uint8)).to(dev)
-        out = torch.empty(5 * n + len(shots), dtype=torch.int32, device=dev)       # rects [n][4], flags [n], status [shots]
+        out = torch.empty(5 * n + len(shots), dtype=torch.int32, device=dev)       # rects [n][4], flags [n], status [shots]: one copy back
         track_segments(segs, len(shots), cands, ncand, cflags, track, out[:4 * n].view(n, 4), out[4 * n:5 * n], out[5 * n:])
         res = out.cpu().numpy()
-        rows, flags = res[:4 * n].reshape(n, 4), res[4 * n:5 * n]
-        if res[5 * n:].any():
-            raise AssertionError("w2l_face_track_segments did not follow a shot's segment (status %s)" % res[5 * n:].tolist())
+        rows, flags, status = res[:4 * n].reshape(n, 4), res[4 * n:5 * n], res[5 * n:]
+        if status.any():
+            raise AssertionError("w2l_face_track_segments did not follow the clip's segment (status %d)" % status[0] if scene is None else
+                                 "w2l_face_track_segments did not follow a shot's segment (status %s)" % status.tolist())
         if (flags == RECT_HOST).any():
             per_frame = []
             for lo in range(0, n, batch_size):
@@ -850,6 +809,21 @@ def _shot_rects(images, detector, batch_size, track, scene, det_stride=1):
         return [tuple(int(v) for v in r) if f == RECT_FOUND else None for r, f in zip(rows, flags)], shots
 
     return halving(run, batch_size)
+
+
+def _detect_rects(images, detector, batch_size, ranks=None, det_stride=1):
+    """`clip_rects` without a track or a scene: one rect (or None) per frame"""
+    return clip_rects(images, detector, batch_size, det_stride=det_stride, ranks=ranks)[0]
+
+
+def _track_rects(images, detector, batch_size, track, det_stride=1):
+    """`clip_rects` under tracked face selection: one rect (or None) per frame"""
+    return clip_rects(images, detector, batch_size, track, det_stride=det_stride)[0]
+
+
+def _shot_rects(images, detector, batch_size, track, scene, det_stride=1):
+    """`clip_rects` under scene-cut detection: (one rect or None per frame, the shots [(a, b)] of the clip)"""
+    return clip_rects(images, detector, batch_size, track, scene, det_stride)
 
 
 def _det_scale_kw(det_scale):
@@ -955,12 +929,7 @@ def face_detect(images, detector=None, pads=None, nosmooth=None, batch_size=None
     pads = args.pads if pads is None else pads
     nosmooth = args.nosmooth if nosmooth is None else nosmooth
     batch_size = args.face_det_batch_size if batch_size is None else batch_size
-    if scene is None:
-        rects = (_detect_rects(images, detector, batch_size, ranks, **skw) if track is None else
-                 _track_rects(images, detector, batch_size, track, **skw))
-        shots = [(0, len(rects))]                # the reference's one take
-    else:
-        rects, shots = _shot_rects(images, detector, batch_size, track, scene, **skw)
+    rects, shots = clip_rects(images, detector, batch_size, track, scene, ranks=ranks, **skw)       # no scene: the reference's one take
     if hold is not None:
         rects = [r for a, b in shots for r in hold_fill(rects[a:b], hold)]
     if any(r is None for r in rects) and (hold is None or len(rects) == 1):

@@ -234,18 +234,16 @@ def device_mel(wav, device):
 
 def _device_rects(detector, frames, batch_size):
     """`inference._detect_rects` (:77-88) on device frames: one rect (or None) per frame of the tensor, batches halved on a
-    RuntimeError of the detector"""
-    while True:
-        try:
-            rects = []
-            for lo in range(0, int(frames.shape[0]), batch_size):
-                rects += detector.get_detections_for_batch(frames[lo:lo + batch_size])
-            return rects
-        except RuntimeError:
-            if batch_size == 1:
-                raise RuntimeError('Image too big to run face detection on GPU')
-            batch_size //= 2
-            print('Recovering from OOM error; New batch size: {}'.format(batch_size))
+    RuntimeError of the detector (`inference.halving`, with this command's final message)"""
+    from .inference import halving
+
+    def run(size):
+        rects = []
+        for lo in range(0, int(frames.shape[0]), size):
+            rects += detector.get_detections_for_batch(frames[lo:lo + size])
+        return rects
+
+    return halving(run, batch_size, error='Image too big to run face detection on GPU')
 
 
 def first_rect(detector, frames):
